@@ -15,7 +15,9 @@ the next frame's walks), the running mean is applied in frame order through an e
 ray tallies add up on the device.  Stage times, visit counts and the roofline block come from
 untimed frames run ALONE before the timed region (their HIP events see one frame's kernels only).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scene atrium|cornell] ...
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scene atrium|cornell] [--dump-outputs DIR] ...
+The result line is the last line on stdout.  It is kept to a few kB so a reader of the output's tail gets all of it: the
+other BASELINE shapes (`--other-configs`, tens of GB and a roofline block each) are measured only when asked for.
 `python bench.py --gpus N` with N > 1 starts its own ranks (one process per GPU, a torch.distributed.run child started
 before anything in this process touches a GPU); launched under torch.distributed.run it is one of the ranks.
 The per-rank frame loop is the package's (fyp-bidirectionalpathtracer_amd/tiling.py TileRenderer).
@@ -251,6 +253,27 @@ def timed_frames(R, pkg, K):
     return dt, rays, hinted
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(R, path, rank):
+    """--dump-outputs: what the timed path hands its caller after its last step — the frame's image, the running mean the
+    accumulation pass leaves in both its output channel and last_frame — as DIR/image.npy, [rows, W, 4] float32, the
+    whole frame on rank 0 (collective at N > 1).  An image larger than DUMP_BYTES is written as a fixed seeded sample of
+    its rows (ascending row indices; with the same arguments every run picks the same rows)."""
+    import numpy as np
+    img = R.gather()
+    if rank != 0:
+        return None
+    img = img.cpu().numpy().astype(np.float32, copy=False)
+    if img.nbytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(img.shape[0], DUMP_BYTES // img[0].nbytes, replace=False))
+        img = np.ascontiguousarray(img[rows])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "image.npy"), img)
+    return {"image": list(img.shape)}
+
+
 _CLOSE_LAST = []  # renderers of the side measurements: nothing is freed on the device before the last shape has been set up
 
 
@@ -345,7 +368,7 @@ def other_config(pkg, torch, name, scene, W, H, D, mat, keep, frames=3, pmc_sub=
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=16, help="timed steps (frames); ms_per_step = their wall time / K")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scene", default="atrium", choices=["atrium", "atrium_uneven", "cornell"],
                     help="built-in scene: the Sponza stand-in (default), the same hall with heavy-tailed triangle areas, the Cornell box")
@@ -359,8 +382,10 @@ def main():
     ap.add_argument("--inflight", type=int, default=3, help="frames in flight (contexts / streams per rank)")
     ap.add_argument("--no-single-pass", dest="single_pass", action="store_false",
                     help="skip the informational one-frame-in-flight pass at N=1")
-    ap.add_argument("--no-other-configs", dest="other_configs", action="store_false",
-                    help="skip the other BASELINE shapes (configs 2, 4 and 5 on this one GPU) at N=1")
+    ap.add_argument("--other-configs", dest="other_configs", action="store_true",
+                    help="also measure the other BASELINE shapes (configs 2, 4 and 5 on this one GPU) at N=1: "
+                    "config.other_configs")
+    ap.add_argument("--no-other-configs", dest="other_configs", action="store_false", help="the default")
     ap.add_argument("--dump-frames", type=int, default=0, help="render this many frames from a fresh state, write the "
                     "accumulated image of all ranks to --dump-path (rank 0) and exit: lets runs with different N be compared")
     ap.add_argument("--dump-path", default="bench_image.npy")
@@ -368,7 +393,12 @@ def main():
                     "(one whole-frame context, G-buffer pass -> BDPT pass -> accumulation pass, one frame at a time)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one handed its caller to DIR/<name>.npy (float32, "
+                    "at most 64 MB in all; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))
@@ -499,6 +529,7 @@ def main():
 
     # ---- timed region: exactly K steps, no host synchronisation inside
     elapsed, rays_total, hinted_total = timed_frames(R, pkg, args.steps)
+    dumped = dump_outputs(R, args.dump_outputs, rank) if args.dump_outputs else None
 
     t = torch.tensor([elapsed, float(rays_total), float(hinted_total)], dtype=torch.float64, device=dev)
     per_rank = None
@@ -566,6 +597,7 @@ def main():
             "rays_hinted_per_frame": int(hinted_all / K),
             "dtype": "f32",
             "data": "file" if args.scene_file else "synthetic",
+            "outputs_dumped": dumped,
             "config": {
                 "workload": workload,
                 "resolution": [W, H], "max_depth": D, "spp_per_step": 1, "mat_index": mat,
@@ -593,9 +625,10 @@ def main():
                                    "closest_alpha_tests": round(stat["alphaTestsClosest"] / n_closest, 3),
                                    "shadow_alpha_tests": round(stat["alphaTestsShadow"] / n_shadow, 3)},
                 "frames_in_flight": inflight,
-                "stage_timing": "HIP events over %d untimed frames run alone on rank 0's tile before the timed region "
-                                "(timed frames overlap each other); one stage = one kernel of the launch stream, a wait for the "
-                                "second stream (*_wait) or a kernel of the second stream (side:*, beside the stages before it)" % stage_frames,
+                # stage times: HIP events over stage_timing_frames untimed frames run alone on rank 0's tile before the timed
+                # region (timed frames overlap each other); one stage = one kernel of the launch stream, a wait for the second
+                # stream (*_wait) or a kernel of the second stream (side:*, beside the stages before it)
+                "stage_timing_frames": stage_frames,
                 "stage_ms_per_step": {k: round(v, 3) for k, v in ms.items()},
                 "stage_mrays": {"walk_kernel": round(closest_per_frame / (kernel_ms["walk_kernel"] * 1e-3) / 1e6, 1)
                                 if kernel_ms["walk_kernel"] > 0 else None,
@@ -624,17 +657,18 @@ def main():
                 # True: the PMC counts behind traffic / fractions were collected on exactly these sources; False: the
                 # committed counts belong to another build and are not quoted; None: no counts for this workload
                 "pmc_build_match": pmc_match,
+                # achieved / frac = ALGORITHMIC bytes (no cache credit, an interior-node visit costed at 64 B) /
+                # measured time against HBM peak: the contract's figure; it exceeds the HBM-side traffic (PMC) because the BVH
+                # is served from L1 / L2 / Infinity Cache, so it can pass 1 and does not say what binds.  `fractions` does: each
+                # is a measured rate over the ceiling that applies to it — hbm: 2 x FETCH_SIZE + WRITE_SIZE over 8 TB/s;
+                # l2_gather: L1-to-L2 read requests x 128 B (the request size, profiles/r3/fetch_calib.txt) over the guide's L2
+                # gather rate; infinity_cache_gather: L2 misses x 128 B over its random-row Infinity-Cache rate;
+                # vmem_address_unit: L1 accesses (lane-loads) per clock per CU over this repo's microbenchmarked ceiling;
+                # valu_issue: VALU wave-instructions x measured issue clocks (2.4 for the fma/mul/add class, 4.3 for the rest)
+                # over SIMD clocks.  `bound` names the largest; none of them can exceed 1 by construction except through the
+                # assumed 2.4 GHz clock.  Counts come from the committed PMC passes of this command (profiles/<PROFILE_ROUND>/),
+                # durations from this run.
                 "node_bytes_costed": SURVEY_NODE_BYTES, "node_bytes_fetched": info.nodeBytes,
-                "note": "achieved / frac = ALGORITHMIC bytes (SURVEY.md §8d: no cache credit, an interior-node visit costed at 64 B) / "
-                        "measured time against HBM peak: the contract's figure; it exceeds the HBM-side traffic (PMC) because the BVH "
-                        "is served from L1 / L2 / Infinity Cache, so it can pass 1 and does not say what binds.  `fractions` does: each "
-                        "is a measured rate over the ceiling that applies to it — hbm: 2 x FETCH_SIZE + WRITE_SIZE over 8 TB/s; l2_gather: "
-                        "L1-to-L2 read requests x 128 B (the request size, profiles/r3/fetch_calib.txt) over the guide's L2 gather rate; "
-                        "infinity_cache_gather: L2 misses x 128 B over its random-row Infinity-Cache rate; vmem_address_unit: L1 accesses (lane-loads) per clock per CU over this repo's "
-                        "microbenchmarked ceiling; valu_issue: VALU wave-instructions x measured issue clocks (2.4 for the fma/mul/add "
-                        "class, 4.3 for the rest) over SIMD clocks.  `bound` names the largest; none of them can exceed 1 by "
-                        "construction except through the assumed 2.4 GHz clock.  Counts come from the committed PMC passes of this "
-                        "command (profiles/%s/), durations from this run." % PROFILE_ROUND,
             },
         }
 

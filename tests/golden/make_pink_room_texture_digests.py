@@ -1,18 +1,20 @@
 #!/usr/bin/env python3
 """Writes tests/golden/pink_room_texture_digests.json: for every texture file the reference ships for its one scene
-(/root/reference/src/CommonPasses/Data/pink_room/textures/*: 26 PNG + 2 JPEG; the WoodFloor base-colour pair is among
-the blobs missing from the checkout), its size, whether it carries alpha, and the SHA-256 of its texels as decoded by
-Pillow (libpng / libjpeg-turbo) — an independent decoder.  The loader's own PNG / JPEG code (host/ImageDecode.cpp) must
-reproduce those texels bit for bit (tests/test_image_decode.py).  Data in, digests out: no reference source is read."""
+(CommonPasses/Data/pink_room/textures/*: 26 PNG + 2 JPEG; the WoodFloor base-colour pair is among the blobs missing from
+the checkout), its size, format, whether it carries alpha, and the SHA-256 of its texels as decoded by Pillow
+(libpng / libjpeg-turbo) — an independent decoder.  tests/test_image_decode.py writes a stand-in of each file's size,
+format and alpha verdict.  Data in, digests out: no reference source is read.
+Usage: python tests/golden/make_pink_room_texture_digests.py <pink_room/textures directory of a reference checkout>"""
 import glob
 import hashlib
 import json
 import os
+import sys
 
 import numpy as np
 from PIL import Image
 
-SRC = "/root/reference/src/CommonPasses/Data/pink_room/textures"
+SRC = sys.argv[1]
 out = {}
 for f in sorted(glob.glob(os.path.join(SRC, "*"))):
     im = Image.open(f)
