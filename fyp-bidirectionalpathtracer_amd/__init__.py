@@ -131,6 +131,18 @@ def msaa_jitter(counter_before_increment):
     return float(j[0]), float(j[1])
 
 
+def keep_for_stream(stream, arrays):
+    """GPU tensors read by work enqueued on `stream` (an update): tell torch's caching allocator, which otherwise only
+    orders a block's reuse after the stream that allocated it (Tensor.record_stream).  Not while capturing a graph: the
+    tensors a graph reads are the caller's to keep for as long as the graph is replayed."""
+    import torch
+    if torch.cuda.is_current_stream_capturing():
+        return
+    for a in arrays:
+        if a is not None and getattr(a, "is_cuda", False):
+            a.record_stream(stream)
+
+
 class Context:
     """One bdpt_ctx = one GPU (one ctx per GPU, not thread-safe)."""
 
@@ -159,6 +171,59 @@ class Context:
 
     def set_camera(self, cam):
         self._check(self._lib.bdpt_set_camera(self._h, C.byref(cam)), "bdpt_set_camera")
+
+    def update_geometry(self, positions, normals=None, bitangents=None, stream=None, keep_light_maps=False):
+        """bdpt_update_geometry: new vertex positions (and normals / bitangents) for the scene, the tree refitted in place.
+        GPU torch tensors take the device path: all of them must be contiguous float32 tensors on this context's device,
+        and they must stay alive until the stream reaches the update (FramePipeline / TileRenderer see to that).  numpy
+        arrays and CPU torch tensors take the host path: checked for finiteness and copied before this returns.  All
+        arrays are numVertices x 3 float32.  Nothing is enqueued when an argument is refused."""
+        u = abi.GeometryUpdate()
+        arrays = [positions, normals, bitangents]
+        given = [a for a in arrays if a is not None]
+        on_gpu = [bool(getattr(a, "is_cuda", False)) for a in given]
+        if any(on_gpu):
+            if not all(on_gpu):
+                raise BdptError("update_geometry: positions, normals and bitangents must all be GPU tensors or all host arrays")
+            for a in given:
+                if a.device.index != self.device:
+                    raise BdptError(f"update_geometry: a tensor on {a.device} for the context of device {self.device}")
+                if not a.is_contiguous() or str(a.dtype) != "torch.float32":
+                    raise BdptError("update_geometry: device inputs must be contiguous float32 tensors")
+            u.memory = abi.MEMORY_DEVICE
+            ptrs = [None if a is None else a.data_ptr() for a in arrays]
+            sizes = [None if a is None else a.numel() for a in arrays]
+        else:
+            import numpy as np
+            u.memory = abi.MEMORY_HOST
+            # (a CPU torch tensor is host memory: its numpy view, never its address as a device pointer)
+            arrays = [None if a is None else np.ascontiguousarray(a.detach().numpy() if hasattr(a, "detach") else a, np.float32).reshape(-1)
+                      for a in arrays]
+            ptrs = [None if a is None else a.ctypes.data for a in arrays]
+            sizes = [None if a is None else a.size for a in arrays]
+        n = sizes[0] // 3
+        if sizes[0] != 3 * n or any(m is not None and m != 3 * n for m in sizes[1:]):
+            raise BdptError("update_geometry: positions, normals and bitangents must be numVertices x 3 each")
+        u.positions, u.normals, u.bitangents = ptrs
+        u.numVertices = int(n)
+        u.flags = abi.UPDATE_KEEP_LIGHT_MAPS if keep_light_maps else 0
+        self._check(self._lib.bdpt_update_geometry(self._h, C.byref(u), stream), "bdpt_update_geometry")
+
+    def set_lights(self, lights, stream=None):
+        """bdpt_set_lights: the scene's lights moved (a sequence of abi.Light, as many as the scene has)."""
+        arr = (abi.Light * len(lights))(*lights)
+        self._check(self._lib.bdpt_set_lights(self._h, arr, len(lights), stream), "bdpt_set_lights")
+
+    def refit_info(self):
+        info = abi.RefitInfo()
+        self._check(self._lib.bdpt_get_refit_info(self._h, C.byref(info)), "bdpt_get_refit_info")
+        return info
+
+    def recs_hash(self):
+        """Test hook: FNV-1a over the context's acceleration-structure records as they stand (synchronises)."""
+        h = C.c_uint64()
+        self._check(self._lib.bdpt_ctx_recs_hash(self._h, C.byref(h)), "bdpt_ctx_recs_hash")
+        return h.value
 
     def set_environment(self, env_map_ptr=None, width=0, height=0, color=(0.0, 0.0, 0.0, 0.0)):
         """What BDPT_PARAM_ENV_ON_MISS looks up: a device RGBA32F lat-long map, or a constant colour."""
@@ -418,6 +483,19 @@ class FramePipeline:
                                          self.accum_limit, st)
         self.last_params = (gp, p)
         return gp, p
+
+    def update_geometry(self, positions, normals=None, bitangents=None, keep_light_maps=False):
+        """Move the scene's vertices (Context.update_geometry on this pipeline's stream); accumulation restarts, as after
+        a camera move.  GPU tensors are marked as in use by that stream (the caching allocator does not hand their memory
+        on before the stream has reached the update)."""
+        self.ctx.update_geometry(positions, normals, bitangents, self._stream_ptr(), keep_light_maps)
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (positions, normals, bitangents))
+        self.accum_count = 0
+
+    def set_lights(self, lights):
+        """Move the scene's lights (Context.set_lights on this pipeline's stream); accumulation restarts."""
+        self.ctx.set_lights(lights, self._stream_ptr())
+        self.accum_count = 0
 
     def close(self):
         self.ctx.close()

@@ -26,6 +26,9 @@ PARAM_ENV_ON_MISS = 1024
 PARAM_EMISSIVE_HITS = 2048
 PREPARE_PRIMARY = 1
 PREPARE_BMFR = 2
+PREPARE_REFIT = 4
+MEMORY_HOST, MEMORY_DEVICE = 0, 1
+UPDATE_KEEP_LIGHT_MAPS = 1
 
 
 class Material(C.Structure):
@@ -124,6 +127,15 @@ class BvhInfo(C.Structure):
                 ("numAlphaMode", C.c_uint32), ("numAlwaysPass", C.c_uint32)]
 
 
+class GeometryUpdate(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("bitangents", C.c_void_p), ("numVertices", C.c_uint32),
+                ("memory", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RefitInfo(C.Structure):
+    _fields_ = [("sahCost", C.c_float), ("sahCostBuilt", C.c_float), ("numUpdates", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 PROTOTYPES = {
     "bdpt_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -138,6 +150,14 @@ PROTOTYPES = {
     "bdpt_host_bvh_destroy": (None, [C.c_void_p]),
     "bdpt_host_bvh_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    "bdpt_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(GeometryUpdate), C.c_void_p]),
+    "bdpt_set_lights": (C.c_int, [C.c_void_p, C.POINTER(Light), C.c_uint32, C.c_void_p]),
+    "bdpt_get_refit_info": (C.c_int, [C.c_void_p, C.POINTER(RefitInfo)]),
+    "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),
+    "bdpt_host_bvh_recs_hash": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bdpt_host_bvh_refit_info": (C.c_int, [C.c_void_p, C.POINTER(RefitInfo)]),
+    "bdpt_ctx_recs_hash": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "bdpt_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,
                                       C.c_float, C.c_float, C.c_float, C.POINTER(Camera)]),
     "bdpt_msaa_jitter": (None, [C.c_uint32, C.POINTER(C.c_float)]),

@@ -26,6 +26,7 @@
 
 #include "bvh.h"
 #include "kernels.h"
+#include "refit.h"
 #include "scene_bvh.h"
 
 using namespace bdpt;
@@ -102,6 +103,21 @@ struct bdpt_ctx {
   // light-tracing rays aim anywhere); its own rows are refreshed by every G-buffer pass
   bdpt_camera hintCam{};
   bool hintCamValid = false;
+  // refit (bdpt_update_geometry / bdpt_set_lights): the plan and its scratch are made on first use or by
+  // bdpt_prepare(BDPT_PREPARE_REFIT) and live in sceneAllocs (a new scene drops them)
+  uint32_t numVertices = 0, numTriangles = 0;
+  uint32_t* lightMaps = nullptr;  // = S.lightMap (writable)
+  bool refitReady = false;
+  BvhRefitPlan refitPlan;  // (host copy: the SAH of bdpt_get_refit_info walks it)
+  RefitDev refit{};
+  uint32_t numUpdates = 0;
+  float* stage[3] = {nullptr, nullptr, nullptr};  // device copies of host-pointer inputs: positions, normals, bitangents
+  // host-pointer inputs go through pinned memory (copied before the call returns); evStage marks the end of the copy
+  // that last read it
+  void* pinned = nullptr;
+  size_t pinnedBytes = 0;
+  hipEvent_t evStage = nullptr, evOrder = nullptr;
+  bool stageInFlight = false;
 };
 
 namespace {
@@ -269,7 +285,9 @@ int bdpt_create(int device_ordinal, bdpt_ctx** out_ctx) {
   if (hipStreamCreateWithFlags(&c->walkStream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->evSplat, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&c->evSplat, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->evStage, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->evOrder, hipEventDisableTiming) != hipSuccess) {
     bdpt_destroy(c);
     return BDPT_E_HIP;
   }
@@ -299,6 +317,9 @@ void bdpt_destroy(bdpt_ctx* c) {
   if (c->evFork) (void)hipEventDestroy(c->evFork);
   if (c->evJoin) (void)hipEventDestroy(c->evJoin);
   if (c->evSplat) (void)hipEventDestroy(c->evSplat);
+  if (c->evStage) (void)hipEventDestroy(c->evStage);
+  if (c->evOrder) (void)hipEventDestroy(c->evOrder);
+  if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->walkStream) (void)hipStreamDestroy(c->walkStream);
   delete c;
 }
@@ -367,6 +388,13 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
   freePool(c->sceneAllocs);
   c->haveScene = false;
   c->S = SceneDev{};
+  c->refitReady = false;
+  c->refitPlan = BvhRefitPlan{};
+  c->refit = RefitDev{};
+  c->numUpdates = 0;
+  c->lightMaps = nullptr;
+  for (float*& p : c->stage) p = nullptr;
+  c->stageInFlight = false;
   c->S.stackOvf = c->stackOvf;
   c->S.stackOvfStride = c->stackOvfStride;
 
@@ -585,11 +613,14 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
       HIPCHK(c, hipDeviceSynchronize());
       c->S.lightMap = maps;
       c->S.lightMapRes = res;
+      c->lightMaps = maps;
     }
   }
   if (c->hintPix) HIPCHK(c, hipMemset(c->hintPix, 0xFF, (size_t)c->W * c->H * sizeof(uint32_t)));
   c->hintCamValid = false;
   lap("light maps");
+  c->numVertices = d->numVertices;
+  c->numTriangles = d->numTriangles;
   c->haveScene = true;
   return BDPT_OK;
 }
@@ -630,6 +661,214 @@ int bdpt_set_environment(bdpt_ctx* c, const bdpt_environment* env) {
   }
   c->env = env ? *env : bdpt_environment{};
   if (!c->env.envMap) c->env.width = c->env.height = 0;
+  return BDPT_OK;
+}
+
+// ---- animated scenes: refit in place (refit.hip, bvh.h "refit") ----
+namespace {
+// the plan (a top-down pass over the records, read back once) and the refit's scratch; not while capturing
+int ensureRefit(bdpt_ctx* c, hipStream_t st) {
+  if (c->refitReady) return BDPT_OK;
+  if (streamIsCapturing(st)) {
+    fail(c, "update: the first update needs bdpt_prepare(BDPT_PREPARE_REFIT) before stream capture");
+    return BDPT_E_STATE;
+  }
+  HIPCHK(c, hipDeviceSynchronize());
+  BvhRefitPlan plan;
+  {
+    std::vector<BvhRec> recs(c->S.numRecs);
+    HIPCHK(c, hipMemcpy(recs.data(), c->S.recs, recs.size() * sizeof(BvhRec), hipMemcpyDeviceToHost));
+    std::string err;
+    if (!bvhRefitMakePlan(recs.data(), recs.size(), plan, err)) {
+      fail(c, err);
+      return BDPT_E_HIP;
+    }
+  }
+  const size_t nn = std::max<size_t>(plan.nodes.size(), 1);
+  RefitDev R{};
+  const BvhRefitNode* dNodes = nullptr;
+  const uint32_t* dOrder = nullptr;
+  int rc;
+  if ((rc = devUpload(c, c->sceneAllocs, &dNodes, plan.nodes.data(), plan.nodes.size())) ||
+      (rc = devUpload(c, c->sceneAllocs, &dOrder, plan.levelOrder.data(), plan.levelOrder.size())) ||
+      (rc = devAlloc(c, c->sceneAllocs, &R.box, nn * 6)) || (rc = devAlloc(c, c->sceneAllocs, &R.childArea, nn * 4)) ||
+      (rc = devAlloc(c, c->sceneAllocs, &R.partial, (size_t)kRefitPartials * 6)) || (rc = devAlloc(c, c->sceneAllocs, &R.pad, 1)))
+    return rc;
+  R.nodes = dNodes;
+  R.levelOrder = dOrder;
+  R.levelStart = plan.levelStart;
+  R.numNodes = (uint32_t)plan.nodes.size();
+  c->refit = std::move(R);
+  c->refitPlan = std::move(plan);
+  c->refitReady = true;
+  return BDPT_OK;
+}
+// the update is ordered after everything this context enqueued before (its last stream joins its side stream)
+int orderAfterLast(bdpt_ctx* c, hipStream_t st) {
+  if (c->lastStream != st) {
+    HIPCHK(c, hipEventRecord(c->evOrder, c->lastStream));
+    HIPCHK(c, hipStreamWaitEvent(st, c->evOrder, 0));
+  }
+  return BDPT_OK;
+}
+// host arrays -> pinned memory (now) -> device copies (on st); arrays[k] may be null
+int stageHostArrays(bdpt_ctx* c, const void* const* arrays, const size_t* bytes, int n, float** dst, hipStream_t st) {
+  size_t total = 0;
+  for (int k = 0; k < n; k++) total += arrays[k] ? (bytes[k] + 255) / 256 * 256 : 0;
+  if (c->stageInFlight) HIPCHK(c, hipEventSynchronize(c->evStage));  // the copies of the last update have read the buffer
+  c->stageInFlight = false;
+  if (total > c->pinnedBytes) {
+    if (c->pinned) HIPCHK(c, hipHostFree(c->pinned));
+    c->pinned = nullptr;
+    c->pinnedBytes = 0;
+    if (hipHostMalloc(&c->pinned, total, hipHostMallocDefault) != hipSuccess) {
+      fail(c, "update: pinned staging memory");
+      return BDPT_E_NOMEM;
+    }
+    c->pinnedBytes = total;
+  }
+  size_t off = 0;
+  for (int k = 0; k < n; k++) {
+    if (!arrays[k]) continue;
+    std::memcpy(static_cast<char*>(c->pinned) + off, arrays[k], bytes[k]);
+    HIPCHK(c, hipMemcpyAsync(dst[k], static_cast<char*>(c->pinned) + off, bytes[k], hipMemcpyHostToDevice, st));
+    off += (bytes[k] + 255) / 256 * 256;
+  }
+  HIPCHK(c, hipEventRecord(c->evStage, st));
+  c->stageInFlight = true;
+  return BDPT_OK;
+}
+// the light cube maps of the occluder hints, re-traced on st
+void retraceLightMaps(bdpt_ctx* c, hipStream_t st) {
+  if (c->hints && c->lightMaps) launchLightMaps(c->S, c->lightMaps, c->S.lightMapRes, st);
+}
+}  // namespace
+
+int bdpt_update_geometry(bdpt_ctx* c, const bdpt_geometry_update* u, void* stream) {
+  if (!c || !u) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "update: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (!u->positions || u->numVertices != c->numVertices || u->memory > BDPT_MEMORY_DEVICE || (u->flags & ~BDPT_UPDATE_KEEP_LIGHT_MAPS)) {
+    fail(c, u->numVertices != c->numVertices ? "update: numVertices differs from the scene's" : "update: positions missing or bad memory / flags");
+    return BDPT_E_INVALID;
+  }
+  if (u->bitangents && !c->S.hasBitangents) {
+    fail(c, "update: bitangents given for a scene that has none");
+    return BDPT_E_INVALID;
+  }
+  const size_t nv3 = (size_t)c->numVertices * 3;
+  if (u->memory == BDPT_MEMORY_HOST) {
+    std::atomic<int> bad{0};
+    hostParallelFor(nv3, [&](size_t i0, size_t i1) {
+      for (size_t i = i0; i < i1; i++)
+        if (!std::isfinite(u->positions[i])) {
+          bad.store(1);
+          return;
+        }
+    });
+    if (bad.load()) {
+      fail(c, "update: a vertex position is not finite");
+      return BDPT_E_INVALID;
+    }
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = ensureRefit(c, st)) return rc;
+  const float* pos = u->positions;
+  const float* nrm = u->normals;
+  const float* bit = u->bitangents;
+  if (u->memory == BDPT_MEMORY_HOST) {
+    const float* in[3] = {u->positions, u->normals, u->bitangents};
+    for (int k = 0; k < 3; k++)
+      if (in[k] && !c->stage[k]) {
+        if (streamIsCapturing(st)) {
+          fail(c, "update: host-pointer inputs allocate their device copies on first use: not while capturing");
+          return BDPT_E_STATE;
+        }
+        if (int rc = devAlloc(c, c->sceneAllocs, &c->stage[k], nv3)) return rc;
+      }
+    if (int rc = orderAfterLast(c, st)) return rc;
+    const void* arrays[3] = {in[0], in[1], in[2]};
+    const size_t bytes[3] = {nv3 * 4, nv3 * 4, nv3 * 4};
+    if (int rc = stageHostArrays(c, arrays, bytes, 3, c->stage, st)) return rc;
+    pos = c->stage[0];
+    nrm = in[1] ? c->stage[1] : nullptr;
+    bit = in[2] ? c->stage[2] : nullptr;
+  } else {
+    if (int rc = orderAfterLast(c, st)) return rc;
+  }
+  launchRefit(c->refit, reinterpret_cast<BvhRec*>(const_cast<uint4*>(c->S.recs)), const_cast<float4*>(c->S.shade), c->S.indices, c->numTriangles, pos, nrm, st);
+  if (bit) HIPCHK(c, hipMemcpyAsync(const_cast<float*>(c->S.bitangents), bit, nv3 * 4, hipMemcpyDeviceToDevice, st));
+  if (!(u->flags & BDPT_UPDATE_KEEP_LIGHT_MAPS)) retraceLightMaps(c, st);
+  HIPCHK(c, hipGetLastError());
+  c->hintCamValid = false;
+  c->numUpdates++;
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
+int bdpt_set_lights(bdpt_ctx* c, const bdpt_light* lights, uint32_t numLights, void* stream) {
+  if (!c || !lights) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "set_lights: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (numLights > BDPT_MAX_LIGHTS) {
+    fail(c, "set_lights: more than BDPT_MAX_LIGHTS lights");
+    return BDPT_E_LIMIT;
+  }
+  if (numLights != c->S.numLights) {
+    fail(c, "set_lights: the light count differs from the scene's");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  const void* arrays[1] = {lights};
+  const size_t bytes[1] = {sizeof(bdpt_light) * numLights};
+  float* dst[1] = {reinterpret_cast<float*>(const_cast<SceneConst*>(c->S.sc)->lights)};
+  if (int rc = stageHostArrays(c, arrays, bytes, 1, dst, st)) return rc;
+  retraceLightMaps(c, st);
+  HIPCHK(c, hipGetLastError());
+  c->hintCamValid = false;
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
+int bdpt_get_refit_info(bdpt_ctx* c, bdpt_refit_info* out) {
+  if (!c || !out) return BDPT_E_INVALID;
+  if (!c->haveScene) return BDPT_E_STATE;
+  ENTER(c);
+  *out = bdpt_refit_info{};
+  out->sahCostBuilt = c->bvhInfo.sahCost;
+  out->sahCost = c->bvhInfo.sahCost;
+  out->numUpdates = c->numUpdates;
+  if (c->numUpdates == 0) return BDPT_OK;
+  HIPCHK(c, hipDeviceSynchronize());
+  std::vector<float> area((size_t)c->refit.numNodes * 4);
+  float root[6] = {0, 0, 0, 0, 0, 0};
+  if (c->refit.numNodes) {
+    HIPCHK(c, hipMemcpy(area.data(), c->refit.childArea, area.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(root, c->refit.box, sizeof(root), hipMemcpyDeviceToHost));
+  }
+  out->sahCost = bvhRefitSah(c->refitPlan, root, area.data());
+  return BDPT_OK;
+}
+
+// Test hook: FNV-1a over the context's records as they stand (synchronises)
+int bdpt_ctx_recs_hash(bdpt_ctx* c, uint64_t* out_hash) {
+  if (!c || !out_hash) return BDPT_E_INVALID;
+  if (!c->haveScene) return BDPT_E_STATE;
+  ENTER(c);
+  HIPCHK(c, hipDeviceSynchronize());
+  std::vector<BvhRec> recs(c->S.numRecs);
+  HIPCHK(c, hipMemcpy(recs.data(), c->S.recs, recs.size() * sizeof(BvhRec), hipMemcpyDeviceToHost));
+  uint64_t h = 1469598103934665603ull;
+  const uint8_t* b = reinterpret_cast<const uint8_t*>(recs.data());
+  for (size_t i = 0; i < recs.size() * sizeof(BvhRec); i++) h = (h ^ b[i]) * 1099511628211ull;
+  *out_hash = h;
   return BDPT_OK;
 }
 
@@ -1056,11 +1295,19 @@ int bdpt_execute_tail(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in,
 // Allocate the optional buffers up front so that no later execute allocates (hipGraph capture, latency).
 int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
   if (!c) return BDPT_E_INVALID;
-  if (!c->haveSize) {
-    fail(c, "prepare: bdpt_resize must be called first");
+  if ((what & ~BDPT_PREPARE_REFIT) || !what) {
+    if (!c->haveSize) {
+      fail(c, "prepare: bdpt_resize must be called first");
+      return BDPT_E_STATE;
+    }
+  }
+  if ((what & BDPT_PREPARE_REFIT) && !c->haveScene) {
+    fail(c, "prepare: BDPT_PREPARE_REFIT needs a scene");
     return BDPT_E_STATE;
   }
   ENTER(c);
+  if (what & BDPT_PREPARE_REFIT)
+    if (int rc = ensureRefit(c, nullptr)) return rc;
   if (what & BDPT_PREPARE_PRIMARY)
     if (int rc = allocOwnGbuffer(c)) return rc;
   if (what & BDPT_PREPARE_BMFR)  // (whole-frame history also on a band / stripes context: bdpt_bmfr_execute takes whole-frame buffers)

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <vector>
 
+#include <math.h>
 #include <cstdlib>
 #include <exception>
 #include <memory>
@@ -382,5 +383,179 @@ bool packBvh(Bvh& bvh, int threads = 0);
 
 // Decode one quantised plane exactly as the device does.
 inline float bvhDecodePlane(const BvhNode& n, int axis, uint8_t q) { return n.origin[axis] + (float)q * n.scale[axis]; }
+
+// ---- one node's quantisation: the host build, the device build (bvh_device.hip k_quantise) and both refits run this ----
+// clo / chi: the boxes of the node's nk (0..4) children, already padded.  Writes words 0-9 of the node's record: origin
+// (0-2), the biased scale exponents in bits 0-23 of word 3 (bits 24-31, the leaf bits, are cleared: the caller's), the
+// 8-bit planes (4-9, BvhNode byte layout; unused slots lo = 255, hi = 0).  Planes round outward.
+BVH_HD inline void bvhQuantiseNode(const float (*clo)[3], const float (*chi)[3], int nk, uint32_t* w) {
+  float blo[3] = {1e30f, 1e30f, 1e30f}, bhi[3] = {-1e30f, -1e30f, -1e30f};  // node box = union of the padded child boxes
+  for (int k = 0; k < nk; k++)
+    for (int a = 0; a < 3; a++) {
+      blo[a] = clo[k][a] < blo[a] ? clo[k][a] : blo[a];  // std::min(blo, clo)
+      bhi[a] = bhi[a] < chi[k][a] ? chi[k][a] : bhi[a];  // std::max(bhi, chi)
+    }
+  uint32_t ex[3];
+  for (int a = 0; a < 3; a++) {
+    __builtin_memcpy(&w[a], &blo[a], 4);
+    // smallest power of two s with 254 s >= extent (one code of headroom for outward rounding): ext / 254 = m 2^e with
+    // m in [0.5, 1) (frexp) — a normal number here (ext >= 1e-30), so e = exponent field - 126
+    const float d = bhi[a] - blo[a];
+    const float ext = d < 1e-30f ? 1e-30f : d;  // std::max(d, 1e-30f)
+    const float q = ext / 254.0f;
+    uint32_t qb;
+    __builtin_memcpy(&qb, &q, 4);
+    int biased = (int)((qb >> 23) & 0xffu) - 126 + 127;
+    if (biased < 1) biased = 1;
+    if (biased > 254) biased = 254;
+    ex[a] = (uint32_t)biased;
+    const uint32_t sb = (uint32_t)biased << 23;
+    float sc;
+    __builtin_memcpy(&sc, &sb, 4);
+    uint32_t lo4 = 0, hi4 = 0;
+    for (int k = 0; k < 4; k++) {
+      if (k >= nk) {
+        lo4 |= 255u << (8 * k);
+        continue;
+      }
+      int ql = (int)floorf((clo[k][a] - blo[a]) / sc);
+      ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql);
+      while (ql > 0 && blo[a] + (float)ql * sc > clo[k][a]) ql--;
+      int qh = (int)ceilf((chi[k][a] - blo[a]) / sc);
+      qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
+      while (qh < 255 && blo[a] + (float)qh * sc < chi[k][a]) qh++;
+      lo4 |= (uint32_t)ql << (8 * k);
+      hi4 |= (uint32_t)qh << (8 * k);
+    }
+    w[4 + a] = lo4;
+    w[7 + a] = hi4;
+  }
+  w[3] = ex[0] | (ex[1] << 8) | (ex[2] << 16);
+}
+
+// buildBvh "Triangle records": v0, e1 = v1 - v0, e2 = v2 - v0 of the triangle (a, b, c), and the box of the five points
+// (v0, v0 + e1, v0 + e2, v1, v2) with its min / max spelled as BvhBox::grow spells them.
+BVH_HD inline void bvhTriGeom(const float* a, const float* b, const float* c, float* v0, float* e1, float* e2, float* lo, float* hi) {
+  for (int k = 0; k < 3; k++) {
+    const float va = a[k], vb = b[k], vc = c[k];
+    v0[k] = va;
+    e1[k] = vb - va;
+    e2[k] = vc - va;
+    const float p1 = v0[k] + e1[k], p2 = v0[k] + e2[k];
+    float l = 1e30f, h = -1e30f;
+    const float pts[5] = {va, p1, p2, vb, vc};
+    for (int j = 0; j < 5; j++) {
+      l = pts[j] < l ? pts[j] : l;
+      h = h < pts[j] ? pts[j] : h;
+    }
+    lo[k] = l;
+    hi[k] = h;
+  }
+}
+BVH_HD inline float bvhBoxArea(const float* lo, const float* hi) {  // BvhBox::area
+  const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+  if (dx < 0 || dy < 0 || dz < 0) return 0.0f;
+  return 2.0f * (dx * dy + dy * dz + dz * dx);
+}
+// buildBvh's pad from the scene box (the union of the five-point boxes of ALL input triangles)
+BVH_HD inline float bvhPadOf(const float* lo, const float* hi, bool any) {
+  float diag = 0.0f;
+  if (any) {
+    const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+    diag = sqrtf(dx * dx + dy * dy + dz * dz);
+  }
+  return 2e-5f * diag + 1e-30f;
+}
+
+// ---- refit (bdpt_update_geometry): new vertex positions, the same tree ----
+// Everything in the records that derives from positions is rewritten in place; the layout, every record index, leaf bits,
+// childBase, child offsets and the prim / flags / aux words of the triangles stay.  A reference is bounded by its whole
+// triangle (conservative for split and alpha-clipped pieces), a node by the union of its children, then quantised with
+// bvhQuantiseNode and the pad of the new scene box.  The result is a pure function of the built topology and the positions.
+// The plan: the four-wide nodes in the order of the build (childBase ascending — packBvh hands the child blocks out in
+// node order), grouped by depth so that one pass per level, deepest first, sees every child done.
+constexpr uint32_t kRefitLeaf = 0x80000000u;  // BvhRefitNode::kid: leaf child of (kid & ~kRefitLeaf) references
+struct BvhRefitNode {
+  uint32_t rec;     // record index of the node
+  uint32_t nk;      // children
+  uint32_t kid[4];  // interior child: its node index (in plan order); leaf child: kRefitLeaf | reference count
+};
+static_assert(sizeof(BvhRefitNode) == 24, "refit node");
+struct BvhRefitPlan {
+  std::vector<BvhRefitNode> nodes;  // build order (the SAH sums in this order)
+  std::vector<uint32_t> levelOrder;  // node indices, deepest level first
+  std::vector<uint32_t> levelStart;  // level l = levelOrder[levelStart[l], levelStart[l + 1])
+};
+// Derives the plan by a top-down pass over the records (every index checked against numRecs).  false + err when the
+// records are not a tree of this format.
+bool bvhRefitMakePlan(const BvhRec* recs, size_t numRecs, BvhRefitPlan& plan, std::string& err);
+// One node of one level.  box: 6 floats (exact lo, hi) per plan node, read for interior children, written for this one;
+// childArea: 4 per plan node (BvhBox::area of each child's exact box, 0 for an unused slot).  The leaf children's
+// triangle records are rewritten here too (v0, e1, e2 from prim and the indices).
+BVH_HD inline void bvhRefitNode(const BvhRefitNode& nd, uint32_t self, BvhRec* recs, const float* pos, const uint32_t* idx, float* box, float* childArea,
+                                float pad) {
+  float lo[4][3], hi[4][3];
+  for (int k = 0; k < 4; k++) {
+    if (k >= (int)nd.nk) {
+      childArea[(size_t)self * 4 + k] = 0.0f;
+      continue;
+    }
+    const uint32_t kd = nd.kid[k];
+    if (kd & kRefitLeaf) {
+      BvhRec& parent = recs[nd.rec];
+      const uint32_t at = parent.w[10] + ((parent.w[11] >> (8 * k)) & 0xffu);
+      for (int a = 0; a < 3; a++) {
+        lo[k][a] = 1e30f;
+        hi[k][a] = -1e30f;
+      }
+      for (uint32_t j = 0; j < (kd & ~kRefitLeaf); j++) {
+        BvhRec& r = recs[at + j];
+        const uint32_t t = r.w[3];
+        const float* pa = pos + (size_t)idx[(size_t)t * 3] * 3;
+        const float* pb = pos + (size_t)idx[(size_t)t * 3 + 1] * 3;
+        const float* pc = pos + (size_t)idx[(size_t)t * 3 + 2] * 3;
+        float v0[3], e1[3], e2[3], tl[3], th[3];
+        bvhTriGeom(pa, pb, pc, v0, e1, e2, tl, th);
+        for (int a = 0; a < 3; a++) {
+          __builtin_memcpy(&r.w[a], &v0[a], 4);
+          __builtin_memcpy(&r.w[4 + a], &e1[a], 4);
+          __builtin_memcpy(&r.w[8 + a], &e2[a], 4);
+          lo[k][a] = tl[a] < lo[k][a] ? tl[a] : lo[k][a];  // BvhBox::grow
+          hi[k][a] = hi[k][a] < th[a] ? th[a] : hi[k][a];
+        }
+      }
+    } else {
+      for (int a = 0; a < 3; a++) {
+        lo[k][a] = box[(size_t)kd * 6 + a];
+        hi[k][a] = box[(size_t)kd * 6 + 3 + a];
+      }
+    }
+    childArea[(size_t)self * 4 + k] = bvhBoxArea(lo[k], hi[k]);
+  }
+  float blo[3] = {1e30f, 1e30f, 1e30f}, bhi[3] = {-1e30f, -1e30f, -1e30f};
+  float clo[4][3], chi[4][3];
+  for (int k = 0; k < (int)nd.nk; k++)
+    for (int a = 0; a < 3; a++) {
+      blo[a] = lo[k][a] < blo[a] ? lo[k][a] : blo[a];
+      bhi[a] = bhi[a] < hi[k][a] ? hi[k][a] : bhi[a];
+      clo[k][a] = lo[k][a] - pad;
+      chi[k][a] = hi[k][a] + pad;
+    }
+  for (int a = 0; a < 3; a++) {
+    box[(size_t)self * 6 + a] = blo[a];
+    box[(size_t)self * 6 + 3 + a] = bhi[a];
+  }
+  if (nd.nk == 0) return;  // (the one empty node of a scene nothing can hit: nothing to refit)
+  uint32_t w[10];
+  bvhQuantiseNode(clo, chi, (int)nd.nk, w);
+  BvhRec& r = recs[nd.rec];
+  for (int i = 0; i < 10; i++) r.w[i] = i == 3 ? (w[3] | (r.w[3] & 0xff000000u)) : w[i];
+}
+// The SAH cost of a refitted tree with the formula of the build (bvh_build.cpp sahCost, bvh_device.hip k_sah_terms /
+// k_sah_sum): float terms, summed in double in node order in blocks of 65536 nodes, the block sums in block order.
+float bvhRefitSah(const BvhRefitPlan& plan, const float* rootBox, const float* childArea);
+// The whole refit on the host (the definition the device refit matches bit for bit).  box / childArea: sized by it.
+void bvhRefitHost(BvhRec* recs, const BvhRefitPlan& plan, const float* positions, const uint32_t* indices, uint32_t numTris,
+                  std::vector<float>& box, std::vector<float>& childArea, int threads = 0);
 
 }  // namespace bdpt

@@ -1206,54 +1206,22 @@ void buildBvh(const float* positions, const uint32_t* indices, uint32_t nTris, c
     const Wide& w = wide[wi];
     BvhNode nd;
     std::memset(&nd, 0, sizeof(nd));
-    // node box = union of the padded child boxes
-    float blo[3] = {1e30f, 1e30f, 1e30f}, bhi[3] = {-1e30f, -1e30f, -1e30f};
+    // child boxes padded, then quantised (bvh.h bvhQuantiseNode: the device build and the refits run the same code)
     float clo[4][3], chi[4][3];
     for (int k = 0; k < w.nk; k++)
       for (int a = 0; a < 3; a++) {
         clo[k][a] = tmp[w.kids[k]].box.lo[a] - pad;
         chi[k][a] = tmp[w.kids[k]].box.hi[a] + pad;
-        blo[a] = std::min(blo[a], clo[k][a]);
-        bhi[a] = std::max(bhi[a], chi[k][a]);
       }
+    uint32_t q[10];
+    bvhQuantiseNode(clo, chi, w.nk, q);
+    std::memcpy(nd.origin, &q[0], 12);
     for (int a = 0; a < 3; a++) {
-      nd.origin[a] = blo[a];
-      // smallest power of two s with 254*s >= extent (one code of headroom for outward rounding)
-      const float ext = std::max(bhi[a] - blo[a], 1e-30f);
-      int e = 0;
-      (void)std::frexp(ext / 254.0f, &e);  // ext/254 = m * 2^e, m in [0.5,1) -> s = 2^e >= ext/254
-      int biased = e + 127;
-      if (biased < 1) biased = 1;
-      if (biased > 254) biased = 254;
-      {
-        union {
-          uint32_t u;
-          float f;
-        } sc0;
-        sc0.u = (uint32_t)biased << 23;
-        nd.scale[a] = sc0.f;
-      }
-      for (int k = 0; k < 4; k++) {
-        if (k >= w.nk) {
-          nd.lo[a][k] = 255;
-          nd.hi[a][k] = 0;
-          continue;
-        }
-        union {
-          uint32_t u;
-          float f;
-        } sc;
-        sc.u = (uint32_t)biased << 23;
-        int ql = (int)std::floor((clo[k][a] - blo[a]) / sc.f);
-        ql = std::min(std::max(ql, 0), 255);
-        while (ql > 0 && blo[a] + (float)ql * sc.f > clo[k][a]) ql--;
-        int qh = (int)std::ceil((chi[k][a] - blo[a]) / sc.f);
-        qh = std::min(std::max(qh, 0), 255);
-        while (qh < 255 && blo[a] + (float)qh * sc.f < chi[k][a]) qh++;
-        nd.lo[a][k] = (uint8_t)ql;
-        nd.hi[a][k] = (uint8_t)qh;
-      }
+      const uint32_t sb = ((q[3] >> (8 * a)) & 0xffu) << 23;
+      std::memcpy(&nd.scale[a], &sb, 4);
     }
+    std::memcpy(nd.lo, &q[4], 12);
+    std::memcpy(nd.hi, &q[7], 12);
     for (int k = 0; k < 4; k++) nd.child[k] = -1;
     for (int k = 0; k < w.nk; k++) {
       const TmpNode& c = tmp[w.kids[k]];
@@ -1341,6 +1309,152 @@ bool packBvh(Bvh& bvh, int threads) {
     }
   });
   return ok;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Refit (bvh.h "refit"): the plan from the records, the host refit, the SAH of a refitted tree.
+// ------------------------------------------------------------------------------------------------
+// children of a packed node: slots up to the last one whose box is not the unused slot's (lo = 255, hi = 0 on every
+// axis), as bvhNumChildren counts them on a BvhNode
+static uint32_t recNumChildren(const BvhRec& n) {
+  uint32_t nk = 0;
+  for (uint32_t c = 0; c < 4; c++) {
+    bool empty = true;
+    for (int a = 0; a < 3; a++)
+      if (((n.w[4 + a] >> (8 * c)) & 0xffu) != 255u || ((n.w[7 + a] >> (8 * c)) & 0xffu) != 0u) empty = false;
+    if (!empty) nk = c + 1;
+  }
+  return nk;
+}
+
+bool bvhRefitMakePlan(const BvhRec* recs, size_t numRecs, BvhRefitPlan& plan, std::string& err) {
+  plan.nodes.clear();
+  plan.levelOrder.clear();
+  plan.levelStart.clear();
+  if (numRecs <= kBvhPadRecs) {
+    err = "refit: no records";
+    return false;
+  }
+  const size_t used = numRecs - kBvhPadRecs;
+  // top-down, level by level: the interior records of every depth
+  std::vector<std::vector<uint32_t>> levels(1, std::vector<uint32_t>(1, 0u));
+  std::vector<uint8_t> seen(used, 0);
+  seen[0] = 1;
+  for (size_t l = 0; l < levels.size(); l++) {
+    std::vector<uint32_t> next;
+    for (uint32_t r : levels[l]) {
+      const BvhRec& n = recs[r];
+      const int nk = (int)recNumChildren(n);
+      for (int c = 0; c < nk; c++) {
+        const uint64_t at = (uint64_t)n.w[10] + ((n.w[11] >> (8 * c)) & 0xffu);
+        if (at >= used) {
+          err = "refit: a child lies outside the record array";
+          return false;
+        }
+        if ((n.w[3] >> (24 + c)) & 1u) continue;  // leaf: its triangles are counted below
+        if (seen[at]) {
+          err = "refit: a record is reached twice";
+          return false;
+        }
+        seen[at] = 1;
+        next.push_back((uint32_t)at);
+      }
+    }
+    if (!next.empty()) {
+      if (levels.size() > 64) {
+        err = "refit: the tree is deeper than 64 levels";
+        return false;
+      }
+      levels.push_back(std::move(next));
+    }
+  }
+  // build order: childBase ascending (packBvh / bvh_device.hip k_write_recs hand the child blocks out in node order)
+  std::vector<std::pair<uint32_t, uint32_t>> byBase;  // (childBase, record)
+  std::vector<uint32_t> depthOf;
+  for (size_t l = 0; l < levels.size(); l++)
+    for (uint32_t r : levels[l]) byBase.emplace_back(recs[r].w[10], r);
+  std::sort(byBase.begin(), byBase.end());
+  std::vector<uint32_t> nodeOfRec(used, 0xffffffffu);
+  for (size_t i = 0; i < byBase.size(); i++) nodeOfRec[byBase[i].second] = (uint32_t)i;
+  plan.nodes.resize(byBase.size());
+  for (size_t i = 0; i < byBase.size(); i++) {
+    const uint32_t r = byBase[i].second;
+    const BvhRec& n = recs[r];
+    BvhRefitNode& nd = plan.nodes[i];
+    nd.rec = r;
+    nd.nk = recNumChildren(n);
+    for (int c = 0; c < 4; c++) nd.kid[c] = 0;
+    for (uint32_t c = 0; c < nd.nk; c++) {
+      const size_t at = (size_t)n.w[10] + ((n.w[11] >> (8 * c)) & 0xffu);
+      if (!((n.w[3] >> (24 + c)) & 1u)) {
+        nd.kid[c] = nodeOfRec[at];
+        continue;
+      }
+      uint32_t cnt = 0;
+      for (;;) {  // a leaf's triangles end at the one flagged kTriLastOfLeaf; at most 8
+        if (at + cnt >= used || cnt >= 8 || nodeOfRec[at + cnt] != 0xffffffffu || seen[at + cnt]) {
+          err = "refit: a leaf's triangles are not where its parent says";
+          return false;
+        }
+        seen[at + cnt] = 1;
+        const bool last = (recs[at + cnt].w[7] & kTriLastOfLeaf) != 0;
+        cnt++;
+        if (last) break;
+      }
+      nd.kid[c] = kRefitLeaf | cnt;
+    }
+  }
+  for (size_t l = levels.size(); l-- > 0;) {
+    plan.levelStart.push_back((uint32_t)plan.levelOrder.size());
+    for (uint32_t r : levels[l]) plan.levelOrder.push_back(nodeOfRec[r]);
+  }
+  plan.levelStart.push_back((uint32_t)plan.levelOrder.size());
+  return true;
+}
+
+float bvhRefitSah(const BvhRefitPlan& plan, const float* rootBox, const float* childArea) {
+  const float rootArea = bvhBoxArea(rootBox, rootBox + 3);
+  constexpr size_t kCostBlock = (size_t)1 << 16;
+  double cost = 0.0;
+  if (rootArea > 0)
+    for (size_t b0 = 0; b0 < plan.nodes.size(); b0 += kCostBlock) {
+      double part = 0.0;
+      const size_t b1 = std::min(plan.nodes.size(), b0 + kCostBlock);
+      for (size_t wi = b0; wi < b1; wi++)
+        for (uint32_t k = 0; k < plan.nodes[wi].nk; k++) {
+          const uint32_t kd = plan.nodes[wi].kid[k];
+          part += (kd & kRefitLeaf ? kCostTri * (float)(kd & ~kRefitLeaf) : kCostTraverse) * childArea[wi * 4 + k] / rootArea;
+        }
+      cost += part;
+    }
+  return (float)cost + kCostTraverse;
+}
+
+void bvhRefitHost(BvhRec* recs, const BvhRefitPlan& plan, const float* positions, const uint32_t* indices, uint32_t numTris,
+                  std::vector<float>& box, std::vector<float>& childArea, int threads) {
+  if (threads <= 0) threads = bvhBuildThreads();
+  float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};  // the scene box over every input triangle
+  for (uint32_t t = 0; t < numTris; t++) {
+    float v0[3], e1[3], e2[3], tl[3], th[3];
+    bvhTriGeom(positions + (size_t)indices[(size_t)t * 3] * 3, positions + (size_t)indices[(size_t)t * 3 + 1] * 3,
+               positions + (size_t)indices[(size_t)t * 3 + 2] * 3, v0, e1, e2, tl, th);
+    for (int a = 0; a < 3; a++) {
+      lo[a] = tl[a] < lo[a] ? tl[a] : lo[a];
+      hi[a] = hi[a] < th[a] ? th[a] : hi[a];
+    }
+  }
+  const float pad = bvhPadOf(lo, hi, numTris != 0);
+  box.assign(plan.nodes.size() * 6, 0.0f);
+  childArea.assign(plan.nodes.size() * 4, 0.0f);
+  for (size_t l = 0; l + 1 < plan.levelStart.size(); l++) {
+    const size_t a = plan.levelStart[l], n = plan.levelStart[l + 1] - a;
+    parallelFor(n, threads, [&](size_t i0, size_t i1, int) {
+      for (size_t i = i0; i < i1; i++) {
+        const uint32_t self = plan.levelOrder[a + i];
+        bvhRefitNode(plan.nodes[self], self, recs, positions, indices, box.data(), childArea.data(), pad);
+      }
+    });
+  }
 }
 
 }  // namespace bdpt

@@ -886,7 +886,6 @@ __global__ void k_quantise(const BvhWideNode* __restrict__ wide, uint32_t nWide,
   const uint32_t wi = blockIdx.x * blockDim.x + threadIdx.x;
   if (wi >= nWide) return;
   const BvhWideNode w = wide[wi];
-  float blo[3] = {1e30f, 1e30f, 1e30f}, bhi[3] = {-1e30f, -1e30f, -1e30f};
   float clo[4][3], chi[4][3];
   uint32_t leafBits = 0, offs = 0, off = 0;
   for (int k = 0; k < 4; k++) {
@@ -895,8 +894,6 @@ __global__ void k_quantise(const BvhWideNode* __restrict__ wide, uint32_t nWide,
     for (int a = 0; a < 3; a++) {
       clo[k][a] = c.box.lo[a] - pad;
       chi[k][a] = c.box.hi[a] + pad;
-      blo[a] = clo[k][a] < blo[a] ? clo[k][a] : blo[a];  // std::min(blo, clo)
-      bhi[a] = bhi[a] < chi[k][a] ? chi[k][a] : bhi[a];  // std::max(bhi, chi)
     }
     offs |= off << (8 * k);
     if (c.left < 0) {
@@ -908,37 +905,8 @@ __global__ void k_quantise(const BvhWideNode* __restrict__ wide, uint32_t nWide,
   }
   BvhRec rec;
   for (int i = 0; i < 12; i++) rec.w[i] = 0;
-  uint32_t ex[3];
-  for (int a = 0; a < 3; a++) {
-    rec.w[a] = __float_as_uint(blo[a]);
-    const float d = bhi[a] - blo[a];
-    const float ext = d < 1e-30f ? 1e-30f : d;  // std::max(d, 1e-30f)
-    // frexp(ext / 254): ext / 254 = m 2^e, m in [0.5, 1) — a normal number here, so e = exponent field - 126
-    const int e = (int)((__float_as_uint(ext / 254.0f) >> 23) & 0xffu) - 126;
-    int biased = e + 127;
-    if (biased < 1) biased = 1;
-    if (biased > 254) biased = 254;
-    ex[a] = (uint32_t)biased;
-    const float sc = __uint_as_float((uint32_t)biased << 23);
-    uint32_t lo4 = 0, hi4 = 0;
-    for (int k = 0; k < 4; k++) {
-      if (k >= w.nk) {
-        lo4 |= 255u << (8 * k);
-        continue;
-      }
-      int ql = (int)floorf((clo[k][a] - blo[a]) / sc);
-      ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql);
-      while (ql > 0 && blo[a] + (float)ql * sc > clo[k][a]) ql--;
-      int qh = (int)ceilf((chi[k][a] - blo[a]) / sc);
-      qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
-      while (qh < 255 && blo[a] + (float)qh * sc < chi[k][a]) qh++;
-      lo4 |= (uint32_t)ql << (8 * k);
-      hi4 |= (uint32_t)qh << (8 * k);
-    }
-    rec.w[4 + a] = lo4;
-    rec.w[7 + a] = hi4;
-  }
-  rec.w[3] = ex[0] | (ex[1] << 8) | (ex[2] << 16) | (leafBits << 24);
+  bvhQuantiseNode(clo, chi, w.nk, rec.w);  // (bvh.h: the host build and the refits run the same code)
+  rec.w[3] |= leafBits << 24;
   rec.w[11] = offs;
   recTmp[wi] = rec;
   blockSize[wi] = off;

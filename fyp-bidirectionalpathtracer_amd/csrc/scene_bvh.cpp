@@ -144,6 +144,11 @@ struct HostScene {
   const bdpt_scene_desc* d;
   SceneBvh sb;
   std::vector<BvhTri> raw;  // one record per input triangle with the reference's per-material flags (the linear scan)
+  // bdpt_host_bvh_refit: the plan, the records as built, the last refit's boxes
+  bool refitted = false;
+  BvhRefitPlan plan;
+  std::vector<BvhRec> builtRecs;
+  std::vector<float> box, childArea;
 };
 
 inline float clampedRcpHost(float d) {
@@ -579,6 +584,158 @@ int bdpt_host_bvh_trace(void* h, const float* rays, uint32_t n, int mode, int br
     out_visits[0] = nodes.load();
     out_visits[1] = tris.load();
   }
+  return BDPT_OK;
+}
+
+// ---- host refit hooks (bdpt_update_geometry's definition on the CPU) --------------------------------------------
+int bdpt_host_bvh_refit(void* h, const float* positions) try {
+  if (!h || !positions) return BDPT_E_INVALID;
+  HostScene& S = *static_cast<HostScene*>(h);
+  Bvh& bvh = S.sb.bvh;
+  const bdpt_scene_desc* d = S.d;
+  if (bvh.recs.empty()) return BDPT_E_STATE;
+  if (!S.refitted) {
+    // the tree walk of bdpt_host_bvh_trace reads nodes / tris: they are decoded back from the refitted records below
+    // (plan order = node order, packBvh).  A plan of another size would leave that walk on the old tree: refused.
+    std::string err;
+    if (!bvhRefitMakePlan(bvh.recs.data(), bvh.recs.size(), S.plan, err)) return BDPT_E_INVALID;
+    if (bvh.nodes.size() != S.plan.nodes.size()) {
+      S.plan = BvhRefitPlan{};
+      return BDPT_E_STATE;
+    }
+    S.builtRecs.assign(bvh.recs.begin(), bvh.recs.end());
+    S.refitted = true;
+  }
+  bvhRefitHost(bvh.recs.data(), S.plan, positions, d->indices, d->numTriangles, S.box, S.childArea);
+  for (size_t w = 0; w < S.plan.nodes.size(); w++) {
+    const BvhRefitNode& pn = S.plan.nodes[w];
+    const BvhRec& r = bvh.recs[pn.rec];
+    BvhNode& nd = bvh.nodes[w];
+    std::memcpy(nd.origin, &r.w[0], 12);
+    for (int a = 0; a < 3; a++) {
+      const uint32_t sb = ((r.w[3] >> (8 * a)) & 0xffu) << 23;
+      std::memcpy(&nd.scale[a], &sb, 4);
+    }
+    std::memcpy(nd.lo, &r.w[4], 12);
+    std::memcpy(nd.hi, &r.w[7], 12);
+    for (uint32_t k = 0; k < pn.nk; k++) {
+      if (!(pn.kid[k] & kRefitLeaf) || nd.child[k] >= 0) continue;
+      const uint32_t first = ((uint32_t)(-1 - nd.child[k])) >> 3, at = r.w[10] + ((r.w[11] >> (8 * k)) & 0xffu);
+      for (uint32_t j = 0; j < (pn.kid[k] & ~kRefitLeaf); j++) {
+        BvhTri& t = bvh.tris[first + j];
+        std::memcpy(t.v0, &bvh.recs[at + j].w[0], 12);
+        std::memcpy(t.e1, &bvh.recs[at + j].w[4], 12);
+        std::memcpy(t.e2, &bvh.recs[at + j].w[8], 12);
+      }
+    }
+  }
+  for (uint32_t t = 0; t < d->numTriangles; t++) {
+    BvhTri& r = S.raw[t];
+    const float* a = positions + (size_t)d->indices[(size_t)t * 3] * 3;
+    const float* b = positions + (size_t)d->indices[(size_t)t * 3 + 1] * 3;
+    const float* c = positions + (size_t)d->indices[(size_t)t * 3 + 2] * 3;
+    for (int k = 0; k < 3; k++) {
+      r.v0[k] = a[k];
+      r.e1[k] = b[k] - a[k];
+      r.e2[k] = c[k] - a[k];
+    }
+  }
+  return BDPT_OK;
+} catch (const std::bad_alloc&) {
+  return BDPT_E_NOMEM;
+} catch (...) {
+  return BDPT_E_INVALID;
+}
+
+int bdpt_host_bvh_refit_check(void* h, char* msg, uint32_t msgCap) try {
+  auto say = [&](const std::string& m) {
+    if (msg && msgCap) std::snprintf(msg, msgCap, "%s", m.c_str());
+    return BDPT_E_INVALID;
+  };
+  if (!h) return BDPT_E_INVALID;
+  HostScene& S = *static_cast<HostScene*>(h);
+  if (!S.refitted) return say("not refitted");
+  const std::vector<BvhRec>& B = S.builtRecs;
+  const BigVec<BvhRec>& R = S.sb.bvh.recs;
+  if (B.size() != R.size()) return say("record count changed");
+  std::vector<uint8_t> reached(R.size(), 0);
+  // (record, the decoded boxes of all its ancestors as one intersection)
+  struct Item {
+    uint32_t rec;
+    float lo[3], hi[3];
+  };
+  std::vector<Item> stack{Item{0, {-INFINITY, -INFINITY, -INFINITY}, {INFINITY, INFINITY, INFINITY}}};
+  for (size_t w = 0; w < S.plan.nodes.size(); w++) reached[S.plan.nodes[w].rec] = 1;
+  std::vector<uint32_t> nodeOf(R.size(), 0xffffffffu);
+  for (size_t w = 0; w < S.plan.nodes.size(); w++) nodeOf[S.plan.nodes[w].rec] = (uint32_t)w;
+  size_t tris = 0;
+  while (!stack.empty()) {
+    const Item it = stack.back();
+    stack.pop_back();
+    const BvhRec& n = R[it.rec];
+    const BvhRec& b = B[it.rec];
+    if (n.w[10] != b.w[10] || n.w[11] != b.w[11] || (n.w[3] >> 24) != (b.w[3] >> 24)) return say("node words 10-11 or leaf bits changed");
+    if (nodeOf[it.rec] == 0xffffffffu) return say("node not in the plan");
+    const BvhRefitNode& pn = S.plan.nodes[nodeOf[it.rec]];
+    for (uint32_t k = 0; k < pn.nk; k++) {
+      Item c{0, {0, 0, 0}, {0, 0, 0}};
+      for (int a = 0; a < 3; a++) {
+        float org, sc;
+        std::memcpy(&org, &n.w[a], 4);
+        const uint32_t sb = ((n.w[3] >> (8 * a)) & 0xffu) << 23;
+        std::memcpy(&sc, &sb, 4);
+        const float lo = org + (float)((n.w[4 + a] >> (8 * k)) & 0xffu) * sc, hi = org + (float)((n.w[7 + a] >> (8 * k)) & 0xffu) * sc;
+        c.lo[a] = std::max(it.lo[a], lo);
+        c.hi[a] = std::min(it.hi[a], hi);
+      }
+      const uint32_t at = n.w[10] + ((n.w[11] >> (8 * k)) & 0xffu);
+      if (!(pn.kid[k] & kRefitLeaf)) {
+        c.rec = at;
+        stack.push_back(c);
+        continue;
+      }
+      for (uint32_t j = 0; j < (pn.kid[k] & ~kRefitLeaf); j++) {
+        const BvhRec& t = R[at + j];
+        const BvhRec& tb = B[at + j];
+        if (t.w[3] != tb.w[3] || t.w[7] != tb.w[7] || t.w[11] != tb.w[11]) return say("triangle prim / flags / aux changed");
+        reached[at + j] = 1;
+        tris++;
+        float v0[3], e1[3], e2[3];
+        std::memcpy(v0, &t.w[0], 12);
+        std::memcpy(e1, &t.w[4], 12);
+        std::memcpy(e2, &t.w[8], 12);
+        for (int a = 0; a < 3; a++) {
+          const float p[3] = {v0[a], v0[a] + e1[a], v0[a] + e2[a]};
+          for (float q : p)
+            if (!(q >= c.lo[a] && q <= c.hi[a])) return say("triangle " + std::to_string(t.w[3]) + " outside an ancestor box");
+        }
+      }
+    }
+  }
+  for (size_t i = 0; i + kBvhPadRecs < R.size(); i++)
+    if (!reached[i]) return say("a record is no longer reached");
+  if (tris != S.sb.bvh.tris.size()) return say("reference count changed");
+  return BDPT_OK;
+} catch (...) {
+  return BDPT_E_NOMEM;
+}
+
+int bdpt_host_bvh_recs_hash(void* h, uint64_t* out_hash) {
+  if (!h || !out_hash) return BDPT_E_INVALID;
+  const BigVec<BvhRec>& R = static_cast<HostScene*>(h)->sb.bvh.recs;
+  uint64_t x = 1469598103934665603ull;
+  const uint8_t* b = reinterpret_cast<const uint8_t*>(R.data());
+  for (size_t i = 0; i < R.size() * sizeof(BvhRec); i++) x = (x ^ b[i]) * 1099511628211ull;
+  *out_hash = x;
+  return BDPT_OK;
+}
+
+int bdpt_host_bvh_refit_info(void* h, bdpt_refit_info* out) {
+  if (!h || !out) return BDPT_E_INVALID;
+  const HostScene& S = *static_cast<HostScene*>(h);
+  *out = bdpt_refit_info{};
+  out->sahCostBuilt = S.sb.bvh.sahCost;
+  out->sahCost = S.refitted && !S.plan.nodes.empty() ? bvhRefitSah(S.plan, S.box.data(), S.childArea.data()) : S.sb.bvh.sahCost;
   return BDPT_OK;
 }
 

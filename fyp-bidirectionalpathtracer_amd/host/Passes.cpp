@@ -388,6 +388,32 @@ void RayLaunch::setScene(Scene::SharedPtr pScene) {
       mSceneSet = false;
     }
 }
+bool RayLaunch::updateGeometry(const bdpt_geometry_update& u, const std::vector<hipStream_t>& streams, uint32_t first) {
+  if (!mCtx || !mSceneSet) return false;
+  const uint32_t n = (uint32_t)mMore.size() + 1;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t s = (first + k) % n;
+    bdpt_ctx* c = s == 0 ? mCtx : mMore[s - 1];
+    if (bdpt_update_geometry(c, &u, s < streams.size() ? streams[s] : nullptr) != BDPT_OK) {
+      std::fprintf(stderr, "[RayLaunch] bdpt_update_geometry failed: %s\n", bdpt_last_error(c));
+      return false;
+    }
+  }
+  return true;
+}
+bool RayLaunch::setLights(const bdpt_light* lights, uint32_t numLights, const std::vector<hipStream_t>& streams, uint32_t first) {
+  if (!mCtx || !mSceneSet) return false;
+  const uint32_t n = (uint32_t)mMore.size() + 1;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t s = (first + k) % n;
+    bdpt_ctx* c = s == 0 ? mCtx : mMore[s - 1];
+    if (bdpt_set_lights(c, lights, numLights, s < streams.size() ? streams[s] : nullptr) != BDPT_OK) {
+      std::fprintf(stderr, "[RayLaunch] bdpt_set_lights failed: %s\n", bdpt_last_error(c));
+      return false;
+    }
+  }
+  return true;
+}
 bool RayLaunch::ensureSize(uint32_t w, uint32_t h) {
   if (!mCtx) return false;
   if (w == mW && h == mH && mSizedDepth == mMaxDepth) return true;
@@ -888,6 +914,7 @@ void RenderingPipeline::setPass(uint32_t passNum, RenderPass::SharedPtr pTargetP
 bool RenderingPipeline::initialize(Scene::SharedPtr pScene) {
   if (!mpResourceManager) return false;  // no size yet (default-constructed and neither run() nor setSize() called)
   mpScene = pScene;
+  mSceneMoved = mSceneUpdated = false;  // (the scene as loaded: checkpoints describe it again)
   mpResourceManager->requestTextureResource(ResourceManager::kOutputChannel);
   mpResourceManager->updateEnvironmentMap("");  // the HDR probe blob is absent: default constant environment
   for (auto& p : mActivePasses) {
@@ -929,7 +956,8 @@ void RenderingPipeline::applyGui(Gui* pGui) {
 }
 void RenderingPipeline::renderFrame() {
   if (mpScene && mpScene->getActiveCamera()) mpScene->getActiveCamera()->beginFrame();  // Scene::update, RenderingPipeline.cpp:630
-  bool refresh = false;
+  bool refresh = mSceneMoved;
+  mSceneMoved = false;
   for (auto& p : mActivePasses) refresh |= (p && p->isRefreshFlagSet());
   if (refresh)
     for (auto& p : mActivePasses)
@@ -1034,8 +1062,54 @@ uint64_t RenderingPipeline::sceneIdentity() const {
   return h;
 }
 
+// The stream of every frame slot's context for an update, and the slot of the next frame.  Frames in flight: slot k's own
+// stream.  Frames one by one (no slots, or a pass with temporal state has switched the slots off): slot 0 renders on the
+// pipeline's stream, the idle slots keep their own streams — an update of theirs waits for what is still on them, and
+// their next frame, once the slots are back, comes after it.
+std::vector<hipStream_t> RenderingPipeline::updateStreams(uint32_t& first) {
+  std::vector<hipStream_t> streams(mSlotStreams.empty() ? 1 : mSlotStreams.size(), nullptr);
+  for (size_t k = 0; k < streams.size(); k++) streams[k] = k < mSlotStreams.size() ? mSlotStreams[k] : mContext.getStream();
+  if (!inFlightActive()) {
+    first = 0;
+    streams[0] = mContext.getStream();
+    return streams;
+  }
+  first = (uint32_t)(mFrameIndex % mFramesInFlight);
+  return streams;
+}
+bool RenderingPipeline::updateGeometry(const float* positions, const float* normals, const float* bitangents, uint32_t memory, bool keepLightMaps) {
+  RayLaunch::SharedPtr rays = mpRays ? mpRays : RayLaunch::create(&mContext);  // (the launcher the passes share)
+  if (!rays || !mpScene || !positions) return false;
+  bdpt_geometry_update u{};
+  u.positions = positions;
+  u.normals = normals;
+  u.bitangents = bitangents;
+  u.numVertices = (uint32_t)(mpScene->positions.size() / 3);
+  u.memory = memory;
+  u.flags = keepLightMaps ? BDPT_UPDATE_KEEP_LIGHT_MAPS : 0u;
+  uint32_t first = 0;
+  const std::vector<hipStream_t> streams = updateStreams(first);
+  if (!rays->updateGeometry(u, streams, first)) return false;
+  mSceneMoved = mSceneUpdated = true;
+  return true;
+}
+bool RenderingPipeline::setLights(const bdpt_light* lights, uint32_t numLights) {
+  RayLaunch::SharedPtr rays = mpRays ? mpRays : RayLaunch::create(&mContext);
+  if (!rays || !lights) return false;
+  uint32_t first = 0;
+  const std::vector<hipStream_t> streams = updateStreams(first);
+  if (!rays->setLights(lights, numLights, streams, first)) return false;
+  mSceneMoved = mSceneUpdated = true;
+  return true;
+}
+
 // [magic][version][width][height][scene identity][pass count] then per pass [name length][name][state length][state]
 bool RenderingPipeline::saveCheckpoint(const std::string& path) {
+  if (mSceneUpdated) {
+    std::fprintf(stderr, "[RenderingPipeline] the scene was moved (updateGeometry / setLights) since it was loaded: checkpoints describe "
+                         "the scene as loaded, no checkpoint written\n");
+    return false;
+  }
   for (auto& pass : mActivePasses)
     if (pass && pass->onHasUnsavedCrossFrameState()) {
       std::fprintf(stderr, "[RenderingPipeline] pass '%s' holds cross-frame state that cannot be saved: no checkpoint written\n", pass->getName().c_str());

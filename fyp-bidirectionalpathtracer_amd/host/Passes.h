@@ -20,6 +20,11 @@ class RayLaunch {
   static SharedPtr create(RenderContext* ctx);
   ~RayLaunch();
   void setScene(Scene::SharedPtr pScene);           // RayLaunch::setScene -> bdpt_set_scene (BVH build)
+  // Animated scenes (RtScene::update -> the acceleration structure refitted in place, RtScene.cpp:74-83, 244-283):
+  // the same update for every frame slot's context (each holds the scene), slot k on streams[k], in frame order from
+  // slot `first`.  false + lastError() when a context refuses it.
+  bool updateGeometry(const bdpt_geometry_update& u, const std::vector<hipStream_t>& streams, uint32_t first);
+  bool setLights(const bdpt_light* lights, uint32_t numLights, const std::vector<hipStream_t>& streams, uint32_t first);
   void setMaxRecursionDepth(uint32_t d) { mMaxDepth = d; }
   bool readyToRender() const { return mCtx && mSceneSet; }
   // (re)size the per-pixel path state; called by execute when the screen size changed
@@ -246,6 +251,15 @@ class RenderingPipeline {
   // failed load the pipeline's state is unspecified: discard it.
   bool saveCheckpoint(const std::string& path);
   bool loadCheckpoint(const std::string& path);
+  // Animated scenes: new vertex positions (numVertices x 3; normals / bitangents may be null = unchanged) or moved
+  // lights (the scene's count) for every frame slot, each on its slot's stream, in frame order; every rank of a tiled
+  // pipeline applies the same update (the refit is deterministic: the replicas stay identical).  The next frame
+  // restarts the accumulation (the refresh notification a camera move gives).  `memory`: BDPT_MEMORY_HOST / _DEVICE.
+  // Checkpoints describe the scene as loaded: saveCheckpoint refuses after an update.
+  bool updateGeometry(const float* positions, const float* normals = nullptr, const float* bitangents = nullptr,
+                      uint32_t memory = BDPT_MEMORY_HOST, bool keepLightMaps = false);
+  bool setLights(const bdpt_light* lights, uint32_t numLights);
+  Scene::SharedPtr getScene() const { return mpScene; }
   size_t getPassCount() const { return mActivePasses.size(); }
 
  private:
@@ -261,6 +275,9 @@ class RenderingPipeline {
   std::vector<hipEvent_t> mOrderEvents;    // per ordered pass: recorded after it ran for the latest frame
   RayLaunch::SharedPtr mpRays;             // kept to switch the launcher's slot
   bool inFlightActive();
+  std::vector<hipStream_t> updateStreams(uint32_t& first);
+  bool mSceneMoved = false;    // the next frame delivers the refresh notification
+  bool mSceneUpdated = false;  // since initialize(): no checkpoint
   uint32_t mTileRank = 0, mTileWorld = 0;  // world 0: not tiled
   std::function<void()> mTileAbort;
   ncclComm_t mTileComm = nullptr;

@@ -8,7 +8,9 @@
 // interleaved stripes of the ONE frame (RenderingPipeline::setTiling), the splat accumulators are summed with one
 // ncclReduceScatter per frame, the frame is assembled with ncclAllGather when it is written.  `--gpus 1` takes the
 // same code path through a one-rank communicator.
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -37,6 +39,7 @@ struct Options {
   int frames = 8, depth = 3, mat = 0, device = 0, accumLimit = 100, inflight = 1, warmup = 0;
   int gpus = 0, rank = -1, world = 0;  // gpus: ranks as threads of this process; rank / world: this process is one rank
   bool denoise = false, denoiseRegression = false;
+  float sway = 0.0f;  // > 0: an animated scene — before every frame the vertices move by up to this fraction of the scene's extent
 };
 
 // How the ranks of a job stay together: a rank whose set-up fails must not leave its peers waiting in a
@@ -162,11 +165,43 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
 
   int warmup = o.warmup;
   if (warmup < 0 || warmup >= o.frames) warmup = 0;
-  for (int f = 0; f < warmup; f++) pipeline->renderFrame();
+  // --sway: a smooth displacement of every vertex before every frame (bdpt_update_geometry through the pipeline)
+  std::vector<float> base, moved;
+  float extent = 0.0f;
+  if (o.sway > 0.0f && pipeline->getScene()) {
+    base = pipeline->getScene()->positions;
+    for (int a = 0; a < 3; a++) {
+      float lo = 1e30f, hi = -1e30f;
+      for (size_t i = a; i < base.size(); i += 3) {
+        lo = std::min(lo, base[i]);
+        hi = std::max(hi, base[i]);
+      }
+      extent = std::max(extent, hi - lo);
+    }
+  }
+  bool swayOk = true;
+  auto frame = [&](int f) {
+    if (!base.empty()) {
+      moved = base;
+      const float a = o.sway * extent * std::sin(0.7f * (float)(f + 1));
+      for (size_t i = 0; i + 2 < moved.size(); i += 3) {
+        moved[i] += a * std::sin(base[i + 1] * 6.0f / extent);
+        moved[i + 2] += 0.5f * a * std::cos(base[i + 1] * 4.0f / extent);
+      }
+      swayOk = swayOk && pipeline->updateGeometry(moved.data());
+    }
+    pipeline->renderFrame();
+  };
+  for (int f = 0; f < warmup; f++) frame(f);
   (void)hipDeviceSynchronize();
   if (!env.barrier()) return res;
   auto t0 = std::chrono::steady_clock::now();
-  for (int f = warmup; f < o.frames; f++) pipeline->renderFrame();
+  for (int f = warmup; f < o.frames; f++) frame(f);
+  if (!swayOk) {
+    std::fprintf(stderr, "bdpt_render: updateGeometry failed\n");
+    env.failLate();
+    return res;
+  }
   (void)hipDeviceSynchronize();
   if (!env.barrier()) return res;  // the job is done when its slowest rank is
   res.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -227,6 +262,7 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--env")) o.envFile = v;
     else if (const char* v = next("--inflight")) o.inflight = std::atoi(v);
     else if (const char* v = next("--warmup")) o.warmup = std::atoi(v);  // of --frames: rendered before the clock starts (first-use allocations)
+    else if (const char* v = next("--sway")) o.sway = (float)std::atof(v);
     else if (const char* v = next("--gpus")) o.gpus = std::atoi(v);
     else if (const char* v = next("--rank")) o.rank = std::atoi(v);
     else if (const char* v = next("--world")) o.world = std::atoi(v);
@@ -235,7 +271,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }

@@ -181,6 +181,23 @@ class TileRenderer:
             state["accum_event"] = done
         return pp.ctx
 
+    def update_geometry(self, positions, normals=None, bitangents=None, keep_light_maps=False):
+        """The same update for every frame slot's context (each holds the scene), each on its slot's stream, in frame
+        order; the running mean restarts.  Every rank applies it: the refit is deterministic, the replicas stay equal."""
+        from . import keep_for_stream
+        for k in range(self.inflight):
+            i = (self.state["frame"] + k) % self.inflight
+            self.pipes[i].ctx.update_geometry(positions, normals, bitangents, C.c_void_p(self.streams[i].cuda_stream), keep_light_maps)
+            keep_for_stream(self.streams[i], (positions, normals, bitangents))  # (read on every slot's stream)
+        self.state["accum"] = 0
+
+    def set_lights(self, lights):
+        """Moved lights for every frame slot's context (as update_geometry); the running mean restarts."""
+        for k in range(self.inflight):
+            i = (self.state["frame"] + k) % self.inflight
+            self.pipes[i].ctx.set_lights(lights, C.c_void_p(self.streams[i].cuda_stream))
+        self.state["accum"] = 0
+
     def barrier(self):
         self.torch.cuda.synchronize(self.dev)
         if self.dist is not None:

@@ -12,6 +12,10 @@
  *                                   (SharedUtils/RayLaunch.cpp:105-167,
  *                                    Falcor/Framework/Source/Raytracing/RtModel.cpp:181-254,
  *                                    Falcor/Framework/Source/Raytracing/RtScene.cpp:220-308)
+ *   bdpt_update_geometry / bdpt_set_lights / bdpt_get_refit_info
+ *                                   RtScene::update marking the acceleration structure for refit every frame and
+ *                                   RtScene::createTlas updating it with PERFORM_UPDATE
+ *                                   (Falcor/Framework/Source/Raytracing/RtScene.cpp:74-83, 244-283): animated scenes
  *   bdpt_set_environment            the "EnvironmentMap" channel BDPTPass requests (BDPTPass.cpp:29; bound by no shader
  *                                   of the pass in the reference): read only with BDPT_PARAM_ENV_ON_MISS
  *   bdpt_bvh_build_check / _hash, bdpt_host_bvh_*
@@ -333,6 +337,50 @@ int bdpt_set_camera(bdpt_ctx* ctx, const bdpt_camera* cam);
  * the pass reads it in the reference).  NULL = none (black).  Only read with BDPT_PARAM_ENV_ON_MISS. */
 int bdpt_set_environment(bdpt_ctx* ctx, const bdpt_environment* env);
 
+/* ---- Animated scenes: new vertex positions and lights between frames, without a rebuild ----
+ * bdpt_update_geometry    RtScene::update marking the acceleration structure for refit every frame
+ *                         (Falcor/Framework/Source/Raytracing/RtScene.cpp:74-83) and RtScene::createTlas updating it in
+ *                         place with PERFORM_UPDATE (RtScene.cpp:244-283): the tree bdpt_set_scene built keeps its
+ *                         topology, every box is refitted on the device (DESIGN.md "Refit").
+ * bdpt_set_lights         the light data RtScene::update re-uploads when a light moves (RtScene.cpp:74-83 via
+ *                         Scene::update); the light count stays.
+ * bdpt_get_refit_info     (none in the reference: the DXR driver's structure is opaque) — what a caller needs to decide
+ *                         when a rebuild (bdpt_set_scene) pays off.
+ * Topology, texture coordinates, materials, textures and the light count stay as the last bdpt_set_scene set them.
+ * Both calls are enqueued on `stream`.  When the context's previous call used another stream, they first wait (an
+ * event) for what that call enqueued, which ends with everything of the context's own second stream; bdpt_gbuffer_execute
+ * and bdpt_execute calls enqueued after them on the same stream see the new scene.  Work on further streams is ordered by
+ * the caller, as for the other calls of this interface.
+ * Host inputs (BDPT_MEMORY_HOST) are checked and copied before the call returns: a position that is not finite gives
+ * BDPT_E_INVALID and leaves the scene as it was.  Device inputs (BDPT_MEMORY_DEVICE) must stay valid until the stream
+ * reaches the update, and their finiteness is the caller's responsibility.
+ * After the first update, or after bdpt_prepare(BDPT_PREPARE_REFIT), a device-pointer update neither allocates nor
+ * synchronises, so it can be captured into a hipGraph.
+ * Errors: no scene BDPT_E_STATE; numVertices or the light count not the scene's BDPT_E_INVALID; more than
+ * BDPT_MAX_LIGHTS lights BDPT_E_LIMIT. */
+#define BDPT_MEMORY_HOST 0u
+#define BDPT_MEMORY_DEVICE 1u
+typedef struct bdpt_geometry_update {
+  const float* positions;  /* numVertices x 3, required */
+  const float* normals;    /* numVertices x 3; NULL = unchanged */
+  const float* bitangents; /* numVertices x 3; NULL = unchanged (only for a scene that has them) */
+  uint32_t numVertices;    /* must equal the scene's */
+  uint32_t memory;         /* BDPT_MEMORY_HOST / BDPT_MEMORY_DEVICE */
+  uint32_t flags;          /* BDPT_UPDATE_* */
+  uint32_t reserved;
+} bdpt_geometry_update;
+/* do not re-trace the occluder cube maps (stale hints: the same image, fewer queries answered by a hint) */
+#define BDPT_UPDATE_KEEP_LIGHT_MAPS 1u
+typedef struct bdpt_refit_info {
+  float sahCost;       /* SAH cost of the tree as it stands now (after the last update) */
+  float sahCostBuilt;  /* the same formula for the tree bdpt_set_scene built (== bdpt_bvh_info.sahCost) */
+  uint32_t numUpdates; /* updates since bdpt_set_scene */
+  uint32_t reserved;
+} bdpt_refit_info;
+int bdpt_update_geometry(bdpt_ctx* ctx, const bdpt_geometry_update* upd, void* stream);
+int bdpt_set_lights(bdpt_ctx* ctx, const bdpt_light* lights, uint32_t numLights, void* stream);
+int bdpt_get_refit_info(bdpt_ctx* ctx, bdpt_refit_info* out); /* synchronises */
+
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
  * a split triangle covering it, every child box containing its subtree's pieces, depth within the traversal stack.
@@ -366,6 +414,18 @@ void* bdpt_host_bvh_create(const bdpt_scene_desc* scene, int threads, float spli
 void bdpt_host_bvh_destroy(void* handle);
 int bdpt_host_bvh_trace(void* handle, const float* rays, uint32_t n, int mode, int brute, int threads, int32_t* out_prim,
                         float* out_tuv, uint64_t* out_visits);
+/* Host-only test hooks of the refit (bdpt_update_geometry): refit the handle's tree to new positions (numVertices x 3
+ * host floats) with the host refit, which the device refit matches bit for bit; bdpt_host_bvh_trace then walks the
+ * refitted tree and its brute-force scan uses the new positions.  _refit_check: every record still reached as built,
+ * words 10-11 and the leaf bits of every node and prim / flags / aux of every triangle unchanged, every triangle inside
+ * every decoded ancestor box (BDPT_E_INVALID + msg otherwise).  _recs_hash: FNV-1a over the handle's records (as
+ * bdpt_bvh_recs_hash); bdpt_ctx_recs_hash: the same over a context's records (synchronises).  _refit_info: as
+ * bdpt_get_refit_info. */
+int bdpt_host_bvh_refit(void* handle, const float* positions);
+int bdpt_host_bvh_refit_check(void* handle, char* msg, uint32_t msgCap);
+int bdpt_host_bvh_recs_hash(void* handle, uint64_t* out_hash);
+int bdpt_host_bvh_refit_info(void* handle, bdpt_refit_info* out);
+int bdpt_ctx_recs_hash(bdpt_ctx* ctx, uint64_t* out_hash);
 
 /* Camera::calculateCameraParameters (Graphics/Camera/Camera.cpp:129-136) with
  * fovY = focalLengthToFovY (Utils/Math/FalcorMath.h:148-151).  Host-only helper. */
@@ -402,6 +462,7 @@ int bdpt_tile_row_ranges(const bdpt_ctx* ctx, uint32_t* out_first_last, uint32_t
  * BidirectionalPathtracing/Passes/DenoisePass.cpp:60-96). */
 #define BDPT_PREPARE_PRIMARY 1u
 #define BDPT_PREPARE_BMFR 2u
+#define BDPT_PREPARE_REFIT 4u /* the refit plan and scratch of bdpt_update_geometry now (needs a scene, not a size) */
 int bdpt_prepare(bdpt_ctx* ctx, uint32_t what);
 
 /* Primary-visibility pass.  Writes the tile rows of all six channels. */
