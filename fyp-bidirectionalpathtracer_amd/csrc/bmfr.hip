@@ -47,10 +47,10 @@ BD float hashRandom(uint32_t a) {
   a = (a ^ 0xb55a4f09u) ^ (a >> 16);
   return (float)a / 4294967296.0f;
 }
-BD float addRandom(float value, int id, int sub, int featureBuffer, int frame) {
+// the shader's int sum wraps before it reaches random(uint): uint32_t arithmetic, defined for every frame number
+BD float addRandom(float value, uint32_t id, uint32_t sub, uint32_t featureBuffer, uint32_t frame) {
   return value + 0.01f * 2 *
-                     (hashRandom((uint32_t)(id + sub * kLocal + featureBuffer * kBlockEdge * kBlockEdge +
-                                            frame * kBufferCount * kBlockEdge * kBlockEdge)) -
+                     (hashRandom(id + sub * kLocal + featureBuffer * kBlockEdge * kBlockEdge + frame * kBufferCount * kBlockEdge * kBlockEdge) -
                       0.5f);
 }
 
@@ -169,8 +169,9 @@ __global__ __launch_bounds__(256) void bmfr_fit_kernel(BmfrDev A, int horizontal
   __shared__ float rmat[kFeatures][kBufferCount];
   __shared__ float bcast[2];
   const int tid = (int)threadIdx.x, group = (int)blockIdx.x;
-  const int W = (int)A.W, H = (int)A.H, frame = (int)A.frame;
-  const int offx = kBlockOffsets[frame % 16][0], offy = kBlockOffsets[frame % 16][1];
+  const int W = (int)A.W, H = (int)A.H;
+  const uint32_t frame = A.frame;  // uint in the shader's constant buffer: frame % 16u stays inside the table
+  const int offx = kBlockOffsets[frame % 16u][0], offy = kBlockOffsets[frame % 16u][1];
   const int bx = (group % horizontalBlocks) * kBlockEdge + offx, by = (group / horizontalBlocks) * kBlockEdge + offy;
   float tmp[kSub][kFeatures];
   float spp[kSub];
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(256) void bmfr_fit_kernel(BmfrDev A, int horizontal
         const int index = s * kLocal + tid;
         if (index >= firstUpd) {
           float v = OUT(index, fb);
-          if (!IGNORE_LD && col == 0 && fb < kFeatures) v = addRandom(v, tid, s, fb, frame);
+          if (!IGNORE_LD && col == 0 && fb < kFeatures) v = addRandom(v, (uint32_t)tid, (uint32_t)s, (uint32_t)fb, frame);
           cache[s] = v;
           dot += v * u[s];
         }

@@ -7,8 +7,9 @@
 //   BidirectionalPathtracing/Data/preprocess.ps.hlsl:33-165   temporal reprojection of the noisy frame
 //   BidirectionalPathtracing/Data/regressionCP.hlsl:100-500   blockwise feature regression (Householder QR)
 //   BidirectionalPathtracing/Data/postprocess.ps.hlsl:22-91   temporal accumulation of the filtered frame
-// PARITY UNPINNED: the reference ships no images or vectors for this pass and its shaders cannot be
-// compiled here; the compute shader is simulated "thread" by thread between its group barriers, with
+// The reference ships no images or vectors for this pass and its shaders cannot be compiled here; this file is pinned
+// instead to a float64 reading of the shaders (tests/bmfr_reference_numpy.py, tests/test_bmfr_cross_check.py).
+// The compute shader is simulated "thread" by thread between its group barriers, with
 // its reductions in the shader's own pairing order, under the arithmetic contract of bdpt_oracle.cpp
 // (IEEE fp32, no FMA contraction, left-to-right).  Defined-away undefined behaviour:
 //   * regressionCP.hlsl reads gCurNoisy while other groups write it (mirrored border pixels): reads
@@ -48,10 +49,11 @@ inline float hashRandom(uint32_t a) {  // regressionCP.hlsl:75-84
   a = (a ^ 0xb55a4f09u) ^ (a >> 16);
   return (float)a / 4294967296.0f;
 }
-inline float addRandom(float value, int id, int sub, int featureBuffer, int frame) {  // :86-95
+// :86-95.  The shader adds these as int and passes the sum to random(uint): two's-complement wraparound, which is
+// uint32_t arithmetic here (an int sum overflows, undefined behaviour, from frame 161,319 on)
+inline float addRandom(float value, uint32_t id, uint32_t sub, uint32_t featureBuffer, uint32_t frame) {
   return value + 0.01f * 2 *
-                     (hashRandom((uint32_t)(id + sub * kLocal + featureBuffer * kBlockEdge * kBlockEdge +
-                                            frame * kBufferCount * kBlockEdge * kBlockEdge)) -
+                     (hashRandom(id + sub * kLocal + featureBuffer * kBlockEdge * kBlockEdge + frame * kBufferCount * kBlockEdge * kBlockEdge) -
                       0.5f);
 }
 // the shader's parallel reduction: v[i] (op)= v[i+128], +64, ... +2, then v[0] (op) v[1]
@@ -91,6 +93,15 @@ void oracle_bmfr_reset(oracle_bmfr* b) {
   if (!b) return;
   for (auto* v : {&b->prevPos, &b->prevNorm, &b->prevNoisy, &b->prevFiltered, &b->accumulated, &b->prevPixel}) std::fill(v->begin(), v->end(), 0.0f);
   std::fill(b->accept.begin(), b->accept.end(), 0u);
+}
+
+// Test hook: the history the next execute reads — the preprocessed noisy frame with its spp (BMFR_PrevNoisy), the
+// accept bools and prev_frame_pixel_f (RG16Float, decoded) — copied out; any pointer may be null.
+void oracle_bmfr_state(const oracle_bmfr* b, float* prevNoisy, uint32_t* accept, float* prevPixel) {
+  if (!b) return;
+  if (prevNoisy) std::memcpy(prevNoisy, b->prevNoisy.data(), b->prevNoisy.size() * 4);
+  if (accept) std::memcpy(accept, b->accept.data(), b->accept.size() * 4);
+  if (prevPixel) std::memcpy(prevPixel, b->prevPixel.data(), b->prevPixel.size() * 4);
 }
 
 // preprocess.ps.hlsl:33-165
@@ -178,7 +189,7 @@ static void preprocess(oracle_bmfr& B, const bdpt_bmfr_params& P, const float* c
 static void fitBlock(const oracle_bmfr& B, const bdpt_bmfr_params& P, int group, int horizontalBlocks, const float* curPos, const float* curNorm,
                      const float* albedo, const float* noisyIn, float* noisyOut) {
   const int W = (int)B.W, H = (int)B.H;
-  const int frame = (int)P.frameNumber;
+  const uint32_t frame = P.frameNumber;  // frame_number is a uint in the constant buffer (regressionCP.hlsl:3)
   const bool ignoreLD = !(P.flags & BDPT_BMFR_KEEP_LD_FEATURES);
   static thread_local std::vector<float> tmpV, outV;
   tmpV.assign((size_t)kBufferCount * kBlockPixels, 0.0f);
@@ -186,8 +197,8 @@ static void fitBlock(const oracle_bmfr& B, const bdpt_bmfr_params& P, int group,
   auto tmp = [&](int index, int buf) -> float& { return tmpV[(size_t)buf * kBlockPixels + index]; };
   auto out = [&](int index, int buf) -> float& { return outV[(size_t)buf * kBlockPixels + index]; };
   auto pixelOf = [&](int index, int& ux, int& uy) {
-    ux = (group % horizontalBlocks) * kBlockEdge + index % kBlockEdge + kBlockOffsets[frame % 16][0];
-    uy = (group / horizontalBlocks) * kBlockEdge + index / kBlockEdge + kBlockOffsets[frame % 16][1];
+    ux = (group % horizontalBlocks) * kBlockEdge + index % kBlockEdge + kBlockOffsets[frame % 16u][0];
+    uy = (group / horizontalBlocks) * kBlockEdge + index / kBlockEdge + kBlockOffsets[frame % 16u][1];
   };
   for (int index = 0; index < kBlockPixels; index++) {
     int ux, uy;
@@ -349,7 +360,7 @@ static void fitBlock(const oracle_bmfr& B, const bdpt_bmfr_params& P, int group,
             const int index = s * kLocal + t;
             if (index >= col) {
               float v = out(index, fb);
-              if (col == 0 && fb < kFeatures) v = addRandom(v, t, s, fb, frame);
+              if (col == 0 && fb < kFeatures) v = addRandom(v, (uint32_t)t, (uint32_t)s, (uint32_t)fb, frame);
               cache[index] = v;
               acc += v * uVec[index];
             }

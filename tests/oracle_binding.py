@@ -50,6 +50,7 @@ def load_oracle(abi):
     lib.oracle_bmfr_destroy.argtypes = [C.c_void_p]
     lib.oracle_bmfr_reset.argtypes = [C.c_void_p]
     lib.oracle_bmfr_execute.restype = C.c_int
+    lib.oracle_bmfr_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.oracle_bmfr_execute.argtypes = [C.c_void_p, C.POINTER(abi.BmfrParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
@@ -134,6 +135,13 @@ class OracleBmfr:
         rc = self.lib.oracle_bmfr_execute(self.h, C.byref(params), _p(cur_pos), _p(cur_norm), _p(albedo), _p(noisy))
         assert rc == 0
         return noisy
+
+    def state(self):
+        """(prev_noisy [n,4], accept [n], prev_pixel [n,2]): what the last execute left for the next one."""
+        n = self.W * self.H
+        noisy, accept, pixel = np.zeros((n, 4), np.float32), np.zeros(n, np.uint32), np.zeros((n, 2), np.float32)
+        self.lib.oracle_bmfr_state(self.h, _p(noisy), _p(accept), _p(pixel))
+        return noisy, accept, pixel
 
     def close(self):
         if self.h:

@@ -62,6 +62,15 @@ static int renderWith(const bdpt_scene_desc& d, const bdpt_camera& cam, uint32_t
     for (int i = 0; i < 4; i++) bp.prevViewProj[i * 5] = 1.0f;
     rc |= oracle_bmfr_execute(b, &bp, pos.data(), nrm.data(), dif.data(), out.data());
   }
+  // mAccumCount has no cap while the camera is still: frame numbers where int arithmetic of the noise-hash index
+  // overflows (161,320) and where a signed frame % 16 turns negative (2^31 + 5)
+  for (uint32_t frame : {161320u, 2147483653u}) {
+    bdpt_bmfr_params bp{};
+    bp.frameNumber = frame;
+    bp.flags = BDPT_BMFR_PREPROCESS | BDPT_BMFR_REGRESSION | BDPT_BMFR_POSTPROCESS | BDPT_BMFR_KEEP_LD_FEATURES;
+    for (int i = 0; i < 4; i++) bp.prevViewProj[i * 5] = 1.0f;
+    rc |= oracle_bmfr_execute(b, &bp, pos.data(), nrm.data(), dif.data(), out.data());
+  }
   oracle_bmfr_destroy(b);
   oracle_scene_destroy(s);
   double sum = 0;

@@ -1,8 +1,8 @@
 """BMFR denoise pass (DenoisePass.cpp:146-279 + preprocess / regressionCP / postprocess shaders).
 
-The reference ships no images or vectors for this pass (it is off by default, DenoisePass.h:71), so the oracle
-(oracle/bmfr_oracle.cpp) is a restatement pinned only by the properties checked below — PARITY UNPINNED — and the
-GPU kernels are compared with it bit for bit.
+The reference ships no images or vectors for this pass (it is off by default, DenoisePass.h:71).  The oracle
+(oracle/bmfr_oracle.cpp) is pinned to a float64 reading of the shaders by tests/test_bmfr_cross_check.py, and the GPU
+kernels are compared with it bit for bit here, on rendered frames and on synthetic G-buffers.
 """
 import ctypes as C
 import math
@@ -275,3 +275,118 @@ def test_bmfr_frame_smaller_than_the_block_offsets(pkg, ob):
     orc.close()
     pipe.close()
     scene.close()
+
+
+# ---- synthetic G-buffers straight into bdpt_bmfr_execute ----
+
+class _SyntheticBmfr:
+    """A context sized with resize (no scene) fed synthetic G-buffers as torch tensors: worldPosition fp32, worldNormal
+    and materialDiffuse as fp16 bit patterns, as abi.GBuffer carries them; the oracle gets the half-decoded floats."""
+
+    def __init__(self, pkg, ob, W, H):
+        import torch
+        self.torch, self.pkg, self.W, self.H = torch, pkg, W, H
+        self.ctx = pkg.Context(0)
+        self.ctx.resize(W, H, 0, H, 1)
+        self.orc = ob.OracleBmfr(pkg.abi, W, H)
+
+    def frame(self, p, g):
+        """One execute on both; returns (gpu, oracle) outputs as float32 [H*W, 4]."""
+        torch = self.torch
+        pos, nrm, alb, noisy = g
+        dev = torch.device("cuda", 0)
+        t_pos = torch.from_numpy(pos).to(dev)
+        t_nrm = torch.from_numpy(nrm.astype(np.float16)).to(dev)
+        t_alb = torch.from_numpy(alb.astype(np.float16)).to(dev)
+        t_noisy = torch.from_numpy(noisy).to(dev)
+        gb = self.pkg.abi.GBuffer()
+        gb.worldPosition, gb.worldNormal, gb.materialDiffuse = t_pos.data_ptr(), t_nrm.data_ptr(), t_alb.data_ptr()
+        self.ctx.bmfr_execute(p, gb, C.c_void_p(t_noisy.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        torch.cuda.synchronize()
+        ref = noisy.copy()
+        self.orc.execute(p, pos, nrm, alb, ref)
+        return t_noisy.cpu().numpy(), ref
+
+    def close(self):
+        self.orc.close()
+        self.ctx.close()
+
+
+def _assert_same(gpu, ref, what):
+    same = (gpu.view(np.uint32) == ref.view(np.uint32)) | (np.isnan(gpu) & np.isnan(ref))
+    assert same.all(), f"{what}: {(~same).any(axis=1).sum()} pixels differ, max |d| {np.nanmax(np.abs(gpu - ref))}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H", [(7, 5), (33, 31)])
+@pytest.mark.parametrize("full", [False, True], ids=["half", "full"])
+@pytest.mark.parametrize("keep_ld", [False, True], ids=["ignore_ld", "keep_ld"])
+def test_bmfr_synthetic_sequence_matches_oracle(pkg, ob, W, H, full, keep_ld):
+    """18 frames (every block offset and the wrap of frame % 16) of the moving-then-still synthetic sequence of
+    test_bmfr_cross_check.py through preprocess + regression + postprocess: GPU == oracle bit for bit."""
+    import test_bmfr_cross_check as xc
+    A = pkg.abi
+    flags = A.BMFR_PREPROCESS | A.BMFR_REGRESSION | A.BMFR_POSTPROCESS | (A.BMFR_FULL_FRAME if full else 0) \
+        | (A.BMFR_KEEP_LD_FEATURES if keep_ld else 0)
+    run = _SyntheticBmfr(pkg, ob, W, H)
+    for k in range(18):
+        g, vp = xc.sequence_gbuffer(pkg, W, H, k)
+        gpu, ref = run.frame(_params(pkg, k, flags, vp), g)
+        _assert_same(gpu, ref, f"frame {k}")
+    run.close()
+
+
+@pytest.mark.gpu
+def test_bmfr_synthetic_1080p_matches_oracle(pkg, ob):
+    """1920x1080, the default flags (preprocess + regression + postprocess, half frame, rank-dropping QR): about 1,050
+    blocks a frame; two frames, so that the second reprojects.  GPU == oracle bit for bit."""
+    import test_bmfr_cross_check as xc
+    A = pkg.abi
+    W, H = 1920, 1080
+    flags = A.BMFR_PREPROCESS | A.BMFR_REGRESSION | A.BMFR_POSTPROCESS
+    run = _SyntheticBmfr(pkg, ob, W, H)
+    for k in range(2):
+        g, vp = xc.sequence_gbuffer(pkg, W, H, k)
+        gpu, ref = run.frame(_params(pkg, k, flags, vp), g)
+        _assert_same(gpu, ref, f"frame {k}")
+    run.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("keep_ld", [False, True], ids=["ignore_ld", "keep_ld"])
+def test_bmfr_gpu_regression_matches_float64_reading(pkg, ob, keep_ld):
+    """The kernel's fit against the float64 reading directly, within the tolerance of test_bmfr_cross_check.py, so
+    the GPU stays pinned to the shaders even if the oracle changes; and against the oracle bit for bit."""
+    import bmfr_reference_numpy as rn
+    import test_bmfr_cross_check as xc
+    A = pkg.abi
+    W, H = 133, 77
+    flags = A.BMFR_REGRESSION | A.BMFR_FULL_FRAME | (A.BMFR_KEEP_LD_FEATURES if keep_ld else 0)
+    run = _SyntheticBmfr(pkg, ob, W, H)
+    for scene in xc.SCENES:
+        g = xc.synthetic_gbuffer(scene, W, H)
+        for frame in (3, 16):
+            gpu, ref = run.frame(_params(pkg, frame, flags), g)
+            _assert_same(gpu, ref, f"{scene} frame {frame}")
+            want, margin = rn.fit(W, H, frame, flags, *g)
+            err, w_bad, skipped = xc.fit_error(gpu, want, margin)
+            assert w_bad == 0 and err <= xc.fit_tol(flags) and skipped == 0, (scene, frame, err, w_bad, skipped)
+    run.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("keep_ld", [False, True], ids=["ignore_ld", "keep_ld"])
+def test_bmfr_large_frame_numbers_match_oracle(pkg, ob, keep_ld):
+    """Frame numbers where 32-bit arithmetic wraps: the noise-hash index past 161,319 and frame % 16 from 2^31 on,
+    where a signed remainder would index the kernel's offset table at -11.  GPU == oracle bit for bit."""
+    import test_bmfr_cross_check as xc
+    A = pkg.abi
+    W, H = 64, 48
+    flags = A.BMFR_PREPROCESS | A.BMFR_REGRESSION | A.BMFR_POSTPROCESS | A.BMFR_FULL_FRAME \
+        | (A.BMFR_KEEP_LD_FEATURES if keep_ld else 0)
+    run = _SyntheticBmfr(pkg, ob, W, H)
+    g = xc.synthetic_gbuffer("box", W, H)
+    for frame in (161320, 2**31 + 5, 2**32 - 1):
+        gpu, ref = run.frame(_params(pkg, frame, flags), g)
+        _assert_same(gpu, ref, f"frame {frame}")
+    run.close()
