@@ -143,6 +143,15 @@ def keep_for_stream(stream, arrays):
             a.record_stream(stream)
 
 
+_TRACE_MODES = {"closest": abi.TRACE_CLOSEST, "closest_cull_back": abi.TRACE_CLOSEST_CULL_BACK, "any": abi.TRACE_ANY}
+
+
+def _host_to_device(array, device):
+    """A host array's device copy (Context.trace_rays' host path)."""
+    import torch
+    return torch.from_numpy(array).to(device)
+
+
 class Context:
     """One bdpt_ctx = one GPU (one ctx per GPU, not thread-safe)."""
 
@@ -208,6 +217,86 @@ class Context:
         u.numVertices = int(n)
         u.flags = abi.UPDATE_KEEP_LIGHT_MAPS if keep_light_maps else 0
         self._check(self._lib.bdpt_update_geometry(self._h, C.byref(u), stream), "bdpt_update_geometry")
+
+    def trace_rays(self, rays, mode="closest", out=None, count=None, stream=None):
+        """bdpt_trace_rays: closest-hit or any-hit queries of a batch of rays against the scene (semantics: include/bdpt.h
+        "Ray queries").  `rays` is (N, 8) float32 in the bdpt_ray layout: origin xyz, tmin, direction xyz, tmax.
+        `mode`: "closest", "closest_cull_back" or "any".
+
+        GPU tensors (contiguous, on this context's device) are traced on `stream` without a synchronise: closest modes
+        return (tuv, prim), float32 (N, 3) and int32 (N,) views of one (N, 4) bdpt_hit buffer; "any" returns uint8 (N,),
+        1 = unoccluded.  `out` takes that buffer preallocated (closest modes: a contiguous (N, 4) float32 or int32 tensor;
+        "any": a contiguous (N,) uint8 tensor), for graph capture.  `count` is a 1-element int32 / uint32 device tensor: only
+        the first min(count, N) rays are traced, later outputs are left as they were.  The tensors must stay alive until
+        the stream has reached the call (FramePipeline.trace_rays sees to that).
+
+        numpy arrays and CPU tensors are copied to the device, traced, synchronised and returned as numpy arrays; no host
+        address ever reaches the library.  Anything else is refused before the library is called."""
+        if mode not in _TRACE_MODES:
+            raise BdptError(f"trace_rays: mode must be one of {sorted(_TRACE_MODES)}, not {mode!r}")
+        if getattr(rays, "is_cuda", False):
+            return self._trace_rays_device(rays, _TRACE_MODES[mode], out, count, stream)
+        if out is not None or count is not None:
+            raise BdptError("trace_rays: out= and count= go with GPU tensor rays")
+        if hasattr(rays, "is_cuda") and getattr(rays, "device", None) is not None and rays.device.type != "cpu":
+            raise BdptError(f"trace_rays: rays on {rays.device}: neither a GPU tensor nor host memory")
+        import numpy as np
+        host = rays.detach().numpy() if hasattr(rays, "detach") else rays
+        if not isinstance(host, np.ndarray) or host.dtype != np.float32 or host.ndim != 2 or host.shape[1] != 8:
+            raise BdptError("trace_rays: rays must be an (N, 8) float32 array")
+        import torch
+        if not torch.cuda.is_available():
+            raise BdptError("trace_rays: no GPU visible to torch (the queries have no CPU fallback)")
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            d = _host_to_device(np.ascontiguousarray(host), dev)
+            torch.cuda.synchronize(dev)  # the copy is done before the library's stream reads it
+            res = self._trace_rays_device(d, _TRACE_MODES[mode], None, None, stream)
+            torch.cuda.synchronize(dev)
+        if isinstance(res, tuple):
+            return tuple(r.cpu().numpy() for r in res)
+        return res.cpu().numpy()
+
+    def _trace_rays_device(self, rays, mode, out, count, stream):
+        import torch
+
+        def on_device(t, what):
+            if not getattr(t, "is_cuda", False) or t.device.index != self.device:
+                raise BdptError(f"trace_rays: {what} must be a GPU tensor on cuda:{self.device}, not on {getattr(t, 'device', type(t))}")
+            if not t.is_contiguous():
+                raise BdptError(f"trace_rays: {what} must be contiguous")
+
+        on_device(rays, "rays")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise BdptError(f"trace_rays: rays must be (N, 8) float32, not {tuple(rays.shape)} {rays.dtype}")
+        n = int(rays.shape[0])
+        if n >= 2**32:
+            raise BdptError("trace_rays: more than 2^32 - 1 rays")
+        if count is not None:
+            on_device(count, "count")
+            if count.dtype not in (torch.int32, torch.uint32) or count.numel() != 1:
+                raise BdptError("trace_rays: count must be a 1-element int32 or uint32 tensor")
+        closest = mode != abi.TRACE_ANY
+        if out is None:
+            out = torch.empty((n, 4) if closest else (n,), dtype=torch.float32 if closest else torch.uint8, device=rays.device)
+        else:
+            on_device(out, "out")
+            if closest and (out.dtype not in (torch.float32, torch.int32) or tuple(out.shape) != (n, 4)):
+                raise BdptError(f"trace_rays: out must be ({n}, 4) float32 or int32 for a closest-hit mode")
+            if not closest and (out.dtype != torch.uint8 or tuple(out.shape) != (n,)):
+                raise BdptError(f"trace_rays: out must be ({n},) uint8 for mode 'any'")
+        d = abi.TraceDesc()
+        d.rays, d.numRays, d.mode = rays.data_ptr(), n, mode
+        d.numRaysDevice = None if count is None else count.data_ptr()
+        if closest:
+            d.hits = out.data_ptr()
+        else:
+            d.visible = out.data_ptr()
+        self._check(self._lib.bdpt_trace_rays(self._h, C.byref(d), stream), "bdpt_trace_rays")
+        if not closest:
+            return out
+        hits = out if out.dtype == torch.float32 else out.view(torch.float32)
+        return hits[:, :3], hits.view(torch.int32)[:, 3]
 
     def set_lights(self, lights, stream=None):
         """bdpt_set_lights: the scene's lights moved (a sequence of abi.Light, as many as the scene has)."""
@@ -491,6 +580,14 @@ class FramePipeline:
         self.ctx.update_geometry(positions, normals, bitangents, self._stream_ptr(), keep_light_maps)
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (positions, normals, bitangents))
         self.accum_count = 0
+
+    def trace_rays(self, rays, mode="closest", out=None, count=None):
+        """Context.trace_rays on this pipeline's stream, ordered after its frames.  GPU tensors (rays, outputs, count) are
+        marked as in use by that stream."""
+        res = self.ctx.trace_rays(rays, mode, out, count, self._stream_ptr())
+        outs = res if isinstance(res, tuple) else (res,)
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (rays, count) + outs)
+        return res
 
     def set_lights(self, lights):
         """Move the scene's lights (Context.set_lights on this pipeline's stream); accumulation restarts."""

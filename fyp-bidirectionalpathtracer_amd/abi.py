@@ -29,6 +29,7 @@ PREPARE_BMFR = 2
 PREPARE_REFIT = 4
 MEMORY_HOST, MEMORY_DEVICE = 0, 1
 UPDATE_KEEP_LIGHT_MAPS = 1
+TRACE_CLOSEST, TRACE_CLOSEST_CULL_BACK, TRACE_ANY = 0, 1, 2
 
 
 class Material(C.Structure):
@@ -136,6 +137,19 @@ class RefitInfo(C.Structure):
     _fields_ = [("sahCost", C.c_float), ("sahCostBuilt", C.c_float), ("numUpdates", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Ray(C.Structure):
+    _fields_ = [("org", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class Hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_int32)]
+
+
+class TraceDesc(C.Structure):
+    _fields_ = [("rays", C.c_void_p), ("numRays", C.c_uint32), ("mode", C.c_uint32), ("numRaysDevice", C.c_void_p),
+                ("hits", C.c_void_p), ("visible", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 PROTOTYPES = {
     "bdpt_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -153,6 +167,7 @@ PROTOTYPES = {
     "bdpt_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(GeometryUpdate), C.c_void_p]),
     "bdpt_set_lights": (C.c_int, [C.c_void_p, C.POINTER(Light), C.c_uint32, C.c_void_p]),
     "bdpt_get_refit_info": (C.c_int, [C.c_void_p, C.POINTER(RefitInfo)]),
+    "bdpt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(TraceDesc), C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),
     "bdpt_host_bvh_recs_hash": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -82,6 +82,7 @@ struct bdpt_ctx {
   LaunchGrids grids{};  // persistent-grid sizes for this context's device
   int* stackOvf = nullptr;      // overflow rows of the persistent kernels' traversal stacks (kernels.h kStackLds)
   uint32_t stackOvfStride = 0;  // lanes per row: every wave a persistent grid can hold
+  unsigned long long* rayCursor = nullptr;  // fetch cursor and done count of bdpt_trace_rays (each launch leaves them zero)
   // channels of the built-in primary stage (bdpt_execute with in == NULL): bdpt_prepare or first use
   bdpt_gbuffer ownGb{};
   // BMFR history (bdpt_prepare or the first bdpt_bmfr_execute): [2] = ping-pong pair
@@ -298,6 +299,11 @@ int bdpt_create(int device_ordinal, bdpt_ctx** out_ctx) {
     bdpt_destroy(c);
     return BDPT_E_NOMEM;
   }
+  if (hipMalloc(reinterpret_cast<void**>(&c->rayCursor), 2 * sizeof(unsigned long long)) != hipSuccess ||
+      hipMemset(c->rayCursor, 0, 2 * sizeof(unsigned long long)) != hipSuccess) {
+    bdpt_destroy(c);
+    return BDPT_E_NOMEM;
+  }
   bvhPrewarmStaging(device_ordinal);  // (the pinned staging buffers bdpt_set_scene's uploads go through)
   *out_ctx = c;
   return BDPT_OK;
@@ -308,6 +314,7 @@ void bdpt_destroy(bdpt_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   if (c->stackOvf) (void)hipFree(c->stackOvf);
+  if (c->rayCursor) (void)hipFree(c->rayCursor);
   freePool(c->sceneAllocs);
   freePool(c->frameAllocs);
   if (c->evCreated)
@@ -833,6 +840,34 @@ int bdpt_set_lights(bdpt_ctx* c, const bdpt_light* lights, uint32_t numLights, v
   retraceLightMaps(c, st);
   HIPCHK(c, hipGetLastError());
   c->hintCamValid = false;
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
+static_assert(sizeof(bdpt_ray) == 32 && sizeof(bdpt_hit) == 16, "trace_rays_kernel reads a ray as two float4 and writes a hit as one");
+int bdpt_trace_rays(bdpt_ctx* c, const bdpt_trace_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "trace_rays: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (d->mode > BDPT_TRACE_ANY) {
+    fail(c, "trace_rays: unknown mode");
+    return BDPT_E_INVALID;
+  }
+  if (!d->numRays) return BDPT_OK;
+  const auto aligned = [](const void* p, uintptr_t a) { return p && (reinterpret_cast<uintptr_t>(p) % a) == 0; };
+  if (!aligned(d->rays, 16) || (d->numRaysDevice && !aligned(d->numRaysDevice, 4)) ||
+      (d->mode == BDPT_TRACE_ANY ? !d->visible : !aligned(d->hits, 16))) {
+    fail(c, "trace_rays: rays, hits or visible missing or not aligned (rays and hits 16 bytes, numRaysDevice 4)");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  launchTraceRays(c->S, reinterpret_cast<const float4*>(d->rays), d->numRays, d->numRaysDevice, c->rayCursor, (int)d->mode,
+                  reinterpret_cast<float4*>(d->hits), d->visible, c->grids, c->numCUs, st);
+  HIPCHK(c, hipGetLastError());
   c->lastStream = st;
   return BDPT_OK;
 }

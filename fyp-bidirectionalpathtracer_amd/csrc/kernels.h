@@ -24,7 +24,8 @@ constexpr int kMaxPersistentPerCU = 32;  // resident one-wave workgroups per CU 
 // Rows of the per-context stack overflow area (SceneDev::stackOvf).  INVARIANT the area relies on: it is indexed by
 // workgroup and lane only, so no two persistent traversal launches of one context may be resident at once — every
 // launchWalk / launchTraceShadow of a context goes to the caller's stream, the context's second stream only runs
-// generators (api.cpp bdpt_execute, evFork / evJoin), and the test hooks synchronise the device first.
+// generators (api.cpp bdpt_execute, evFork / evJoin), the test hooks synchronise the device first, and launchTraceRays
+// (bdpt_trace_rays) goes to the caller's stream ordered behind everything the context's previous call enqueued.
 constexpr int kStackOvfRows = KSTACK - kStackLds;
 constexpr int kShadeRecF4 = 7;  // float4s per triangle shading record (7 used = 112 B)
 constexpr uint32_t kNoRay = 0xFFFFFFFFu;
@@ -210,6 +211,7 @@ void launchInitPaths(const SceneDev& S, const FrameDev& F, const PathBuf& P, hip
 struct LaunchGrids {
   uint32_t walk[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // [EXT][GGX][COUNT]
   uint32_t shadow[2] = {0, 0};        // [COUNT]
+  uint32_t rays[3] = {0, 0, 0};       // [mode] (trace_rays.hip)
 };
 // both random walks of the frame: one persistent launch (trace + hit/miss shading in place)
 void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, LaunchGrids& G, int numCUs, hipStream_t st);
@@ -218,6 +220,12 @@ void launchGenNee(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStr
 void launchGenSplat(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st);
 void launchGenConnect(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st);
 void launchTraceShadow(const SceneDev& S, const FrameDev& F, const PathBuf& P, int rayClass, LaunchGrids& G, int numCUs, hipStream_t st);
+// bdpt_trace_rays (trace_rays.hip): `cap` bdpt_ray records (two float4 each), of which the first min(*count, cap) are
+// traced when `count` is set; mode 0 / 1 write bdpt_hit records (one float4 each) to `hits`, mode 2 visibility bytes to
+// `vis`.  `cursor` (two words of the context, zeroed by bdpt_create) must be zero when the launch starts; the launch leaves
+// it zero.
+void launchTraceRays(const SceneDev& S, const float4* rays, uint32_t cap, const uint32_t* count, unsigned long long* cursor, int mode,
+                     float4* hits, uint8_t* vis, LaunchGrids& G, int numCUs, hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch,

@@ -27,6 +27,7 @@
 #include "device_math.hpp"
 #include "device_scene.hpp"
 #include "device_trace.hpp"
+#include "launch.hpp"
 
 namespace bdpt {
 
@@ -1489,9 +1490,6 @@ __global__ void test_bsdf_kernel(const float* in, uint32_t n, bool fromLobe, flo
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-#ifndef PERCU
-#define PERCU 24
-#endif
 static inline uint32_t blocksFor(uint64_t n) { return (uint32_t)((n + kWave - 1) / kWave); }
 // grid of a dense kernel over a sharded path queue: every (list, chunk) pair gets a workgroup
 static inline uint32_t queueGrid(const PathBuf& P) { return (P.pathSubCap / kWave) * kNumSubQueues; }
@@ -1505,20 +1503,7 @@ static inline uint32_t queueGrid(const PathBuf& P) { return (P.pathSubCap / kWav
 // -> light lengths up to 15 -> slot indices past slotRay's planes -> the wrong terms and the memory fault recorded in
 // profiles/README.md).  So these kernels are launched through launchWave() only — there is no block size to get wrong —
 // and each starts with oneWavePerGroup(), which makes a launch of any other shape do nothing instead of corrupting.
-template <class K, class... Args>
-static void launchWave(K kernel, uint32_t grid, hipStream_t st, Args... args) {
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWave), 0, st, args...);
-}
-
-// Persistent grids: as many one-wave workgroups as can be resident (LDS 8 KiB/wave, VGPRs).
-template <class K>
-static uint32_t persistentGrid(K kernel, int numCUs) {
-  int perCU = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, kWave, 0) != hipSuccess || perCU <= 0) perCU = 8;
-  if (perCU > PERCU) perCU = PERCU;
-  if (perCU > kMaxPersistentPerCU) perCU = kMaxPersistentPerCU;  // the stack overflow area is sized for that many
-  return (uint32_t)(perCU * numCUs);
-}
+// (launchWave and persistentGrid: launch.hpp)
 
 void launchGBuffer(const SceneDev& S, const GBufferDev& G, hipStream_t st) {
   const uint32_t Np = G.Np;

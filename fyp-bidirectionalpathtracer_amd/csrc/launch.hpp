@@ -1,0 +1,32 @@
+// launch.hpp — host-side launch helpers of the one-wave-per-workgroup kernels (kernels.hip, trace_rays.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernels.h"
+
+namespace bdpt {
+
+#ifndef PERCU
+#define PERCU 24
+#endif
+
+// ONE WORKGROUP = ONE WAVE (kernels.hip, above its launchers, lists what relies on it).  The kernels declared
+// __launch_bounds__(kWave) are launched through launchWave() only — there is no block size to get wrong — and each
+// starts with BDPT_ONE_WAVE_PER_GROUP(), which makes a launch of any other shape do nothing instead of corrupting.
+template <class K, class... Args>
+static void launchWave(K kernel, uint32_t grid, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWave), 0, st, args...);
+}
+
+// Persistent grids: as many one-wave workgroups as can be resident (LDS 8 KiB/wave, VGPRs).
+template <class K>
+static uint32_t persistentGrid(K kernel, int numCUs) {
+  int perCU = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, kWave, 0) != hipSuccess || perCU <= 0) perCU = 8;
+  if (perCU > PERCU) perCU = PERCU;
+  if (perCU > kMaxPersistentPerCU) perCU = kMaxPersistentPerCU;  // the stack overflow area is sized for that many
+  return (uint32_t)(perCU * numCUs);
+}
+
+}  // namespace bdpt

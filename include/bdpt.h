@@ -16,6 +16,9 @@
  *                                   RtScene::update marking the acceleration structure for refit every frame and
  *                                   RtScene::createTlas updating it with PERFORM_UPDATE
  *                                   (Falcor/Framework/Source/Raytracing/RtScene.cpp:74-83, 244-283): animated scenes
+ *   bdpt_trace_rays                 TraceRay from a caller's own ray-generation shader
+ *                                   (CommonPasses/Data/CommonPasses/aoTracing.rt.hlsl:112,
+ *                                    lambertianPlusShadows.rt.hlsl:62, simpleDiffuseGI.rt.hlsl:127): ray queries
  *   bdpt_set_environment            the "EnvironmentMap" channel BDPTPass requests (BDPTPass.cpp:29; bound by no shader
  *                                   of the pass in the reference): read only with BDPT_PARAM_ENV_ON_MISS
  *   bdpt_bvh_build_check / _hash, bdpt_host_bvh_*
@@ -380,6 +383,54 @@ typedef struct bdpt_refit_info {
 int bdpt_update_geometry(bdpt_ctx* ctx, const bdpt_geometry_update* upd, void* stream);
 int bdpt_set_lights(bdpt_ctx* ctx, const bdpt_light* lights, uint32_t numLights, void* stream);
 int bdpt_get_refit_info(bdpt_ctx* ctx, bdpt_refit_info* out); /* synchronises */
+
+/* ---- Ray queries: a caller's own rays against the scene ----
+ * bdpt_trace_rays         TraceRay from a caller's own ray-generation shader: ambient occlusion
+ *                         (CommonPasses/Data/CommonPasses/aoTracing.rt.hlsl:112), shadow rays
+ *                         (lambertianPlusShadows.rt.hlsl:62, BDPT/standardShadowRay.hlsli:40), one-bounce GI
+ *                         (simpleDiffuseGI.rt.hlsl:127) — for picking, collision probes and custom integrators beside
+ *                         the BDPT pass.  One call traces a batch of rays in device memory (DESIGN.md "Ray queries").
+ * Semantics (those of the pass's own queries):
+ *   - a ray hits a triangle at t when tmin < t < tmax; directions need not be unit length (t is in units of |dir|);
+ *   - closest-hit ties go to the lowest primitive index; `prim` is the caller's input triangle index (also for the
+ *     pre-split references of a large scene);
+ *   - alpha-masked materials run the any-hit alpha test; triangles the build dropped as never visible are never hit;
+ *   - a miss writes prim = -1 and t = u = v = 0; a ray with a NaN or zero direction, a NaN origin or tmax <= tmin misses;
+ *   - with numRaysDevice set, rays at or beyond min(*numRaysDevice, numRays) are neither read nor written.
+ * Ordering: the call is enqueued on `stream`.  When the context's previous call used another stream, it first waits (an
+ * event) for what that call enqueued, as bdpt_update_geometry does; it sees the scene as of the last update enqueued
+ * before it.  Later calls of the context on the same stream are ordered behind it; work on further streams is ordered by
+ * the caller, as for the other calls of this interface.  The inputs must stay valid, and the outputs are written, when the
+ * stream reaches the call.
+ * It neither allocates nor synchronises (no prepare step), so it can be captured into a hipGraph, and it changes nothing
+ * bdpt_get_counters or bdpt_get_stage_times report.
+ * INVARIANT: the persistent traversal kernels of one context share its stack-overflow area, so no two of them may be
+ * resident at once.  This call keeps that by enqueuing only on `stream`, behind the context's previous call; a caller
+ * who then renders on another stream orders that stream behind this one (an event), as for every call of the context.
+ * Errors (nothing is enqueued): no scene BDPT_E_STATE; a NULL context or desc, an unknown mode, a missing or misaligned
+ * buffer BDPT_E_INVALID.  numRays == 0 returns BDPT_OK and does nothing. */
+typedef struct bdpt_ray {
+  float org[3];
+  float tmin;
+  float dir[3];
+  float tmax;
+} bdpt_ray; /* 32 bytes */
+typedef struct bdpt_hit {
+  float t, u, v; /* barycentrics: the hit point is (1-u-v) v0 + u v1 + v v2 */
+  int32_t prim;  /* input triangle index, -1 = miss */
+} bdpt_hit;      /* 16 bytes */
+#define BDPT_TRACE_CLOSEST 0u           /* closest hit */
+#define BDPT_TRACE_CLOSEST_CULL_BACK 1u /* closest hit, RAY_FLAG_CULL_BACK_FACING_TRIANGLES (double-sided materials are kept) */
+#define BDPT_TRACE_ANY 2u               /* RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH: visibility only */
+typedef struct bdpt_trace_desc {
+  const bdpt_ray* rays;          /* device, 16-byte aligned, numRays records */
+  uint32_t numRays;              /* rays to trace; the capacity when numRaysDevice is set */
+  uint32_t mode;                 /* BDPT_TRACE_* */
+  const uint32_t* numRaysDevice; /* optional device word, read by the kernel: trace min(*numRaysDevice, numRays) rays */
+  bdpt_hit* hits;                /* closest-hit modes: device, 16-byte aligned, one per ray (ignored for BDPT_TRACE_ANY) */
+  uint8_t* visible;              /* BDPT_TRACE_ANY: device, one byte per ray, 1 = unoccluded (ignored otherwise) */
+} bdpt_trace_desc;
+int bdpt_trace_rays(bdpt_ctx* ctx, const bdpt_trace_desc* desc, void* stream);
 
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
