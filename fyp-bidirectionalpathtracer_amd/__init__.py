@@ -355,6 +355,12 @@ class Context:
     def execute(self, params, gbuffer, out_ptr, stream=None):
         self._check(self._lib.bdpt_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_execute")
 
+    def execute_light_groups(self, params, gbuffer, out_ptr, groups_ptr, stream=None):
+        """bdpt_execute_light_groups: bdpt_execute into `out_ptr` plus (numLights + 1) RGBA32F planes of the frame at
+        `groups_ptr` (plane k = light k, the last = emission; contract in include/bdpt.h "Light groups")."""
+        self._check(self._lib.bdpt_execute_light_groups(self._h, C.byref(params), C.byref(gbuffer), out_ptr, groups_ptr, stream),
+                    "bdpt_execute_light_groups")
+
     def execute_tail(self, params, gbuffer, out_ptr, stream=None):
         self._check(self._lib.bdpt_execute_tail(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream),
                     "bdpt_execute_tail")
@@ -461,12 +467,19 @@ class FramePipeline:
     Pass 0 LightProbeGBufferPass (frame counter starts 0xdeadbeef, CommonPasses/LightProbeGBufferPass.h:79),
     pass 1 BDPTPass (0x1337, BDPTPass.h:44), pass 2 SimpleAccumulationPass (cap 100 by default,
     CommonPasses/SimpleAccumulationPass.h:70).  Channels live in torch tensors on ``cuda:<device>``.
+
+    light_groups=True renders every frame with bdpt_execute_light_groups: ``light_groups`` is a (numLights + 1, H, W, 4)
+    float32 tensor with the frame's planes (plane k = light k, the last = emission) and ``light_groups_accum`` their
+    running means, kept by one bdpt_accumulate over all planes with the beauty's counters.  As the beauty's ``output``,
+    ``light_groups`` holds the mean too after an accumulating frame.  Whole frames only: not with a tile or stripes.
     """
 
     def __init__(self, scene, width, height, max_depth=3, mat_index=0, device=0, tile=None, clamp_upper=0.9, min_t=1e-4,
-                 accum_limit=100, flags=0, stripes=None):
+                 accum_limit=100, flags=0, stripes=None, light_groups=False):
         import torch
         self.torch = torch
+        if light_groups and (stripes is not None or (tile is not None and (int(tile[0]), int(tile[1])) != (0, int(height)))):
+            raise BdptError("light groups need a pipeline that renders the whole frame (no tile, no stripes)")
         if not torch.cuda.is_available():
             raise BdptError("no GPU visible to torch: the render pass cannot run (no CPU fallback)")
         self.W, self.H = int(width), int(height)
@@ -503,6 +516,11 @@ class FramePipeline:
                 self.channels[name] = torch.zeros(self.H, self.W, 4, dtype=torch.float16, device=self.dev)
             self.channels[OUTPUT_CHANNEL] = torch.zeros(self.H, self.W, 4, dtype=torch.float32, device=self.dev)
             self.last_frame = torch.zeros(self.H, self.W, 4, dtype=torch.float32, device=self.dev)
+            self.light_groups = self.light_groups_accum = None
+            if light_groups:
+                k = int(scene.desc.numLights) + 1
+                self.light_groups = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
+                self.light_groups_accum = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
         torch.cuda.synchronize(self.dev)
         # where the set-up time went: the scene (acceleration structure + uploads) and the frame's buffers are separate things
         self.setup_times = {"context_s": t1 - t0, "resize_s": t2 - t1, "set_scene_s": t3 - t2, "channels_s": time.time() - t3}
@@ -557,7 +575,10 @@ class FramePipeline:
         if gbuffer:
             self.ctx.gbuffer_execute(gp, self.gb, st)
         p = self.bdpt_params(extra_flags)
-        self.ctx.execute(p, self.gb, C.c_void_p(self.output.data_ptr()), st)
+        if self.light_groups is None:
+            self.ctx.execute(p, self.gb, C.c_void_p(self.output.data_ptr()), st)
+        else:
+            self.ctx.execute_light_groups(p, self.gb, C.c_void_p(self.output.data_ptr()), C.c_void_p(self.light_groups.data_ptr()), st)
         self.gbuffer_frame += 1
         self.bdpt_frame += 1
         if accumulate:
@@ -567,6 +588,9 @@ class FramePipeline:
             if self.stripes is None:
                 self.ctx.accumulate(C.c_void_p(self.last_frame.data_ptr()), C.c_void_p(self.output.data_ptr()), n,
                                     self.accum_limit, self.W * self.H, st)
+                if self.light_groups is not None:
+                    self.ctx.accumulate(C.c_void_p(self.light_groups_accum.data_ptr()), C.c_void_p(self.light_groups.data_ptr()), n,
+                                        self.accum_limit, self.light_groups.shape[0] * self.W * self.H, st)
             else:
                 self.ctx.accumulate_tile(C.c_void_p(self.last_frame.data_ptr()), C.c_void_p(self.output.data_ptr()), n,
                                          self.accum_limit, st)

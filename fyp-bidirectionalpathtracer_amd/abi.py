@@ -27,6 +27,7 @@ PARAM_EMISSIVE_HITS = 2048
 PREPARE_PRIMARY = 1
 PREPARE_BMFR = 2
 PREPARE_REFIT = 4
+PREPARE_LIGHT_GROUPS = 8
 MEMORY_HOST, MEMORY_DEVICE = 0, 1
 UPDATE_KEEP_LIGHT_MAPS = 1
 TRACE_CLOSEST, TRACE_CLOSEST_CULL_BACK, TRACE_ANY = 0, 1, 2
@@ -180,6 +181,8 @@ PROTOTYPES = {
     "bdpt_gbuffer_execute": (C.c_int, [C.c_void_p, C.POINTER(GBufferParams), C.POINTER(GBuffer), C.c_void_p]),
     "bdpt_execute": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_execute_tail": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "bdpt_execute_light_groups": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
     "bdpt_prepare": (C.c_int, [C.c_void_p, C.c_uint32]),
     "bdpt_resize_stripes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, Stripes, C.c_uint32]),
     "bdpt_stripe_rows": (C.c_uint32, [C.c_uint32, C.c_uint32]),

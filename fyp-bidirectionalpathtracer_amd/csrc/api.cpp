@@ -119,6 +119,11 @@ struct bdpt_ctx {
   size_t pinnedBytes = 0;
   hipEvent_t evStage = nullptr, evOrder = nullptr;
   bool stageInFlight = false;
+  // light groups (bdpt_execute_light_groups): the per-light splat-value planes and each pixel's light, made by
+  // bdpt_prepare(BDPT_PREPARE_LIGHT_GROUPS) or the first call; they depend on the scene's light count and the frame size,
+  // so bdpt_set_scene and bdpt_resize drop them
+  unsigned long long* groupSplat = nullptr;
+  uint8_t* groupLightIdx = nullptr;
 };
 
 namespace {
@@ -185,6 +190,13 @@ int devUpload(bdpt_ctx* c, std::vector<void*>& pool, const T** out, const T* hos
 void freePool(std::vector<void*>& pool) {
   for (void* p : pool) (void)hipFree(p);
   pool.clear();
+}
+// (the device is idle, or the caller has synchronised it)
+void freeLightGroups(bdpt_ctx* c) {
+  if (c->groupSplat) (void)hipFree(c->groupSplat);
+  if (c->groupLightIdx) (void)hipFree(c->groupLightIdx);
+  c->groupSplat = nullptr;
+  c->groupLightIdx = nullptr;
 }
 
 // Every entry point that launches or allocates starts here: the context's device becomes current, so one
@@ -315,6 +327,7 @@ void bdpt_destroy(bdpt_ctx* c) {
   (void)hipDeviceSynchronize();
   if (c->stackOvf) (void)hipFree(c->stackOvf);
   if (c->rayCursor) (void)hipFree(c->rayCursor);
+  freeLightGroups(c);
   freePool(c->sceneAllocs);
   freePool(c->frameAllocs);
   if (c->evCreated)
@@ -393,6 +406,7 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
   freePool(c->sceneAllocs);
+  freeLightGroups(c);
   c->haveScene = false;
   c->S = SceneDev{};
   c->refitReady = false;
@@ -990,6 +1004,7 @@ int resizeRows(bdpt_ctx* c, uint32_t width, uint32_t height, uint32_t maxDepth) 
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
   freePool(c->frameAllocs);
+  freeLightGroups(c);
   for (int k = 0; k < 2; k++) c->bmfrPos[k] = c->bmfrNorm[k] = c->bmfrNoisy[k] = c->bmfrFiltered[k] = nullptr;
   c->ownGb = bdpt_gbuffer{};
   c->bmfrAccept = nullptr;  // history goes with the frame (BlockwiseMultiOrderFeatureRegression::resize)
@@ -1193,7 +1208,8 @@ int frameSetup(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float*
 
 // Connection pairs whose contribution is exactly zero, for the pixels no visible connection has saturated
 // yet (DESIGN.md "Lazy connection rounds"), then the splat fold-in unless the caller defers it.
-int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st) {
+// Grp (bdpt_execute_light_groups): the group variants of the lazy check and the resolve.
+int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st, const GroupDev* Grp = nullptr) {
   const PathBuf& P = c->P;
   const bdpt_params* p = &F.p;
   const int D = (int)p->maxDepth;
@@ -1216,11 +1232,18 @@ int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st) {
       stageMark(c, st, "lazy_gen");
       launchTraceShadow(c->S, F, P, RAY_PAIRS, c->grids, c->numCUs, st);
       stageMark(c, st, "lazy_trace");
-      launchLazyCheck(F, P, list, P.lazyCount + (size_t)r * kCursorBlock, batch, next, P.lazyCount + (size_t)(r + 1) * kCursorBlock, st);
+      if (Grp)
+        launchLazyCheckGroups(F, P, *Grp, list, P.lazyCount + (size_t)r * kCursorBlock, batch, next,
+                              P.lazyCount + (size_t)(r + 1) * kCursorBlock, st);
+      else
+        launchLazyCheck(F, P, list, P.lazyCount + (size_t)r * kCursorBlock, batch, next, P.lazyCount + (size_t)(r + 1) * kCursorBlock, st);
     }
     stageMark(c, st, "lazy_check");
   }
-  if (!(p->flags & BDPT_PARAM_DEFER_RESOLVE)) {
+  if (Grp) {
+    launchResolveGroups(F, P, *Grp, st);
+    stageMark(c, st, "resolve_groups");
+  } else if (!(p->flags & BDPT_PARAM_DEFER_RESOLVE)) {
     launchResolve(c->splat, false, 0, c->sl, F.out, c->W, c->P.pix, c->P.Np, st);
     stageMark(c, st, "resolve");
   }
@@ -1230,7 +1253,10 @@ int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st) {
 }
 }  // namespace
 
-int bdpt_execute(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream) {
+namespace {
+// bdpt_execute, and bdpt_execute_light_groups with Grp set: the same stages and the same rays; the group path swaps in
+// the group variants of init_paths, gather, the lazy check and the resolve, and clears its splat-value planes.
+int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream, const GroupDev* Grp) {
   FrameDev F;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = frameSetup(c, p, in, out, st, F)) return rc;
@@ -1254,10 +1280,14 @@ int bdpt_execute(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
   if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], st));
   HIPCHK(c, hipMemsetAsync(P.qcount, 0, (size_t)kCursorWords * sizeof(uint32_t), st));
   HIPCHK(c, hipMemsetAsync(c->splat, 0, (size_t)c->sl.owners * c->sl.chunkRows * c->W * 4 * sizeof(unsigned long long), st));
+  if (Grp) HIPCHK(c, hipMemsetAsync(Grp->splat, 0, (size_t)Grp->numLights * Grp->framePix * 4 * sizeof(unsigned long long), st));
   if (!(p->flags & BDPT_PARAM_KEEP_COUNTERS)) HIPCHK(c, hipMemsetAsync(c->counters, 0, sizeof(DevCounters), st));
   stageMark(c, st, "clear");
 
-  launchInitPaths(c->S, F, P, st);
+  if (Grp)
+    launchInitPathsGroups(c->S, F, P, *Grp, st);
+  else
+    launchInitPaths(c->S, F, P, st);
   stageMark(c, st, "init_paths");
 
   // Both walks (eye vertices 2..D, BDPTMain.rt.hlsl:106-112; light vertices 1..D, :138-145) in one persistent
@@ -1307,7 +1337,10 @@ int bdpt_execute(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
   }
   launchTraceShadow(c->S, F, P, RAY_PAIRS, c->grids, c->numCUs, st);
   stageMark(c, st, "trace_pairs");
-  launchGather(F, P, P.queue[1], P.lazyCount, st);
+  if (Grp)
+    launchGatherGroups(F, P, *Grp, P.queue[1], P.lazyCount, st);
+  else
+    launchGather(F, P, P.queue[1], P.lazyCount, st);
   stageMark(c, st, "gather");
   // Everything that touches the splat buffer is enqueued by now: a tiled host may start its exchange here
   // and run the connection tail beside it (BDPT_PARAM_DEFER_TAIL + bdpt_execute_tail).
@@ -1316,7 +1349,62 @@ int bdpt_execute(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
     c->lastStream = st;
     return BDPT_OK;
   }
-  return connectionTail(c, F, st);
+  return connectionTail(c, F, st, Grp);
+}
+
+// the group path's buffers; not while the stream is being captured
+int allocLightGroups(bdpt_ctx* c, hipStream_t st) {
+  if (c->groupSplat) return BDPT_OK;
+  if (streamIsCapturing(st)) {
+    fail(c, "light groups: the splat planes need bdpt_prepare(BDPT_PREPARE_LIGHT_GROUPS) before stream capture");
+    return BDPT_E_STATE;
+  }
+  const size_t n = (size_t)c->W * c->H;
+  void *sp = nullptr, *li = nullptr;
+  if (hipMalloc(&sp, std::max<size_t>((size_t)c->S.numLights * n * 4 * sizeof(unsigned long long), 16)) != hipSuccess ||
+      hipMalloc(&li, std::max<size_t>(c->P.Np, 16)) != hipSuccess) {
+    if (sp) (void)hipFree(sp);
+    fail(c, "light groups: hipMalloc of the splat planes failed");
+    return BDPT_E_NOMEM;
+  }
+  c->groupSplat = reinterpret_cast<unsigned long long*>(sp);
+  c->groupLightIdx = reinterpret_cast<uint8_t*>(li);
+  return BDPT_OK;
+}
+}  // namespace
+
+int bdpt_execute(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream) {
+  return executeFrame(c, p, in, out, stream, nullptr);
+}
+
+int bdpt_execute_light_groups(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, float* groups, void* stream) {
+  if (!c) return BDPT_E_INVALID;
+  if (!groups) {
+    fail(c, "light groups: groups is NULL");
+    return BDPT_E_INVALID;
+  }
+  if (p && (p->flags & (BDPT_PARAM_DEFER_RESOLVE | BDPT_PARAM_DEFER_TAIL))) {
+    fail(c, "light groups: BDPT_PARAM_DEFER_RESOLVE and BDPT_PARAM_DEFER_TAIL are not supported");
+    return BDPT_E_INVALID;
+  }
+  if (!c->haveScene || !c->haveSize) {
+    fail(c, "light groups: scene and size must be set first");
+    return BDPT_E_STATE;
+  }
+  if (c->stripes.stripeRows != 0 || c->tileRows != c->H) {
+    fail(c, "light groups: the context must render the whole frame (no tile, no stripes)");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = allocLightGroups(c, st)) return rc;
+  GroupDev G{};
+  G.planes = groups;
+  G.splat = c->groupSplat;
+  G.lightIdx = c->groupLightIdx;
+  G.numLights = c->S.numLights;
+  G.framePix = (uint64_t)c->W * c->H;
+  return executeFrame(c, p, in, out, stream, &G);
 }
 
 int bdpt_execute_tail(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream) {
@@ -1340,6 +1428,10 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
     fail(c, "prepare: BDPT_PREPARE_REFIT needs a scene");
     return BDPT_E_STATE;
   }
+  if ((what & BDPT_PREPARE_LIGHT_GROUPS) && !c->haveScene) {
+    fail(c, "prepare: BDPT_PREPARE_LIGHT_GROUPS needs a scene (the planes are per light)");
+    return BDPT_E_STATE;
+  }
   ENTER(c);
   if (what & BDPT_PREPARE_REFIT)
     if (int rc = ensureRefit(c, nullptr)) return rc;
@@ -1347,6 +1439,8 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
     if (int rc = allocOwnGbuffer(c)) return rc;
   if (what & BDPT_PREPARE_BMFR)  // (whole-frame history also on a band / stripes context: bdpt_bmfr_execute takes whole-frame buffers)
     if (int rc = allocBmfrHistory(c)) return rc;
+  if (what & BDPT_PREPARE_LIGHT_GROUPS)
+    if (int rc = allocLightGroups(c, nullptr)) return rc;
   return BDPT_OK;
 }
 

@@ -171,6 +171,18 @@ struct FrameDev {
   const uint32_t* hintPix;
 };
 
+// Light groups (bdpt_execute_light_groups): one RGBA32F plane per light plus one for emission, from the paths of the
+// plain frame.  Only the group variants of init_paths, gather and lazy_check and the group resolve take it, so the
+// argument layout of every other kernel stays as it is.  Whole-frame contexts only: planes and splat planes are indexed
+// by frame pixel (splat planes in SplatLayout order, which is frame order there).
+struct GroupDev {
+  float* planes;               // (numLights + 1) planes of W*H float4: plane k < numLights = light k, plane numLights = emission
+  unsigned long long* splat;   // numLights splat-value planes of W*H x 4 u64 (r, g, b, unused); counts stay in FrameDev::splat
+  uint8_t* lightIdx;           // tile-local pixel p -> the light its light subpath starts at (init_paths)
+  uint32_t numLights;
+  uint64_t framePix;           // W*H: the stride of both kinds of plane
+};
+
 struct GBufferDev {
   bdpt_camera cam;
   bdpt_gbuffer_params gp;
@@ -236,6 +248,14 @@ constexpr int kMaxLazyRounds = 8;   // cursor blocks reserved for lazy rounds  /
 // tile-local order (a reduce-scattered chunk); otherwise SplatLayout order, starting at frame row splatRow0 (owners == 1).
 void launchResolve(const unsigned long long* splat, bool tileLocal, uint32_t splatRow0, const SplatLayout& L, float* out, uint32_t W,
                    const uint32_t* pix, uint32_t Np, hipStream_t st);
+// Light-group variants (GroupDev): init_paths that also records each pixel's light and starts the background pixels'
+// planes, gather / lazy_check that also keep the planes, and the resolve of out and every plane in one pass (out's splat
+// values are the sums of the per-light splat planes: FrameDev::splat then only holds the counts).
+void launchInitPathsGroups(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr, hipStream_t st);
+void launchGatherGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
+void launchLazyCheckGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const uint32_t* list, const uint32_t* listCount,
+                           int batch, uint32_t* nextList, uint32_t* nextCount, hipStream_t st);
+void launchResolveGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, hipStream_t st);
 void launchAccumulate(float* last, float* cur, uint32_t accumCount, uint32_t maxAccum, uint64_t numTexels, hipStream_t st);
 void launchAccumulateTile(float* last, float* cur, uint32_t accumCount, uint32_t maxAccum, const uint32_t* pix, uint32_t Np,
                           hipStream_t st);

@@ -306,9 +306,10 @@ __global__ __launch_bounds__(kWave) void light_map_kernel(SceneDev S, uint32_t* 
 // init_paths: eye vertex 1 from the G-buffer, light vertex 0 from sampleLight, valid-pixel queue
 // (BDPTMain.rt.hlsl:51-103, 124-135; sampleLight BDPTUtils.hlsli:140-152)
 // ------------------------------------------------------------------------------------------------
-template <bool GGX>
-__global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev F, PathBuf P) {
-  BDPT_ONE_WAVE_PER_GROUP();
+// GROUPS (bdpt_execute_light_groups): also the light of each pixel's light subpath, and the planes of the pixels without
+// geometry — the emission plane what `out` gets, a light plane (0, 0, 0, 1): the frame with that background stripped
+template <bool GGX, bool GROUPS>
+BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr) {
   const uint32_t p = blockIdx.x * kWave + threadIdx.x;
   const bool inTile = p < P.Np;
   const size_t pix = inTile ? P.pix[p] : 0;
@@ -322,6 +323,11 @@ __global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev 
     if (!geom) {
       out4[pix] = make_float4(dr, dg, db, 1.0f);  // :62-66
       P.eyeLast[p] = 0;
+      if (GROUPS) {
+        float4* g4 = reinterpret_cast<float4*>(Gr.planes) + pix;
+        for (uint32_t k = 0; k < Gr.numLights; k++) g4[(size_t)k * Gr.framePix] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+        g4[(size_t)Gr.numLights * Gr.framePix] = make_float4(dr, dg, db, 1.0f);
+      }
     } else {
       float nx, ny, nz, nw, sr, sg, sb, sa, er, eg, eb, ea;
       unpackHalf4(F.gb.worldNormal, pix, nx, ny, nz, nw);
@@ -358,6 +364,7 @@ __global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev 
       const int lightsCount = (int)S.numLights;
       int index = (int)(nextRand(seed) * (float)lightsCount);
       if (index > lightsCount - 1) index = lightsCount - 1;
+      if (GROUPS) Gr.lightIdx[p] = (uint8_t)index;
       const bdpt_light& l = S.sc->lights[index];
       f3 lightDir;
       if (l.type == BDPT_LIGHT_DIRECTIONAL)
@@ -386,6 +393,16 @@ __global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev 
     }
   }
   wavePush(geom, p, P.queue[0], P.qcount, P.pathSubCap);
+}
+template <bool GGX>
+__global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev F, PathBuf P) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  initPathsLane<GGX, false>(S, F, P, GroupDev{});
+}
+template <bool GGX>
+__global__ __launch_bounds__(kWave) void init_paths_groups_kernel(SceneDev S, FrameDev F, PathBuf P, GroupDev Gr) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  initPathsLane<GGX, true>(S, F, P, Gr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1154,14 +1171,30 @@ BD void loadSlotChunk(const PathBuf& P, uint32_t p, int slot0, int n, SlotChunk&
   }
 }
 
-BD bool gatherLane(const FrameDev& F, const PathBuf& P, uint32_t p, uint32_t& nSplat) {
+// GROUPS (bdpt_execute_light_groups; contract in include/bdpt.h "Light groups"): the planes as well.  Every term has one
+// source: NEE term t the light gen_nee drew for it (recomputed here from seedL: draw t + 1), connections and splats the
+// pixel's light subpath (GroupDev::lightIdx).  A light plane's RGB lives in LDS (`la`: row (3k + channel) * kWave of the
+// lane's column) while its terms are summed; w is the same in every plane and in `out`, so it is kept once.  The frame
+// with only light k adds +0 for every NEE term of another light; the plane skips those adds, which changes no bit: its sum
+// starts at +0 and only ever adds values >= +0 (clampVec), and x + 0 == x for every such x.  The emission plane (the frame
+// with every intensity zero) adds its +0 terms for real, because it starts from `out`'s start, -0 included.
+template <bool GROUPS>
+BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, float* la, uint32_t p, uint32_t& nSplat) {
   bool pending = false;
   const size_t pix = P.pix[p];
   float4* out4 = reinterpret_cast<float4*>(F.out);
   float4 acc = out4[pix];
   const int D = (int)F.p.maxDepth;
+  const int K = GROUPS ? (int)Gr.numLights : 0;
+  float ex = acc.x, ey = acc.y, ez = acc.z;  // emission plane RGB
+  int own = 0;                               // light plane of the pixel's light subpath
+  if (GROUPS) {
+    for (int r = 0; r < 3 * K; r++) la[r * kWave] = 0.0f;
+    own = (int)Gr.lightIdx[p];
+  }
   SlotChunk c;
   if (!(F.p.flags & BDPT_PARAM_NO_NEE)) {
+    uint32_t seed = GROUPS ? P.seedL[p] : 0u;
     for (int t0 = 0; t0 < D; t0 += kGatherChunk) {
       const int n = (D - t0 < kGatherChunk) ? D - t0 : kGatherChunk;
       loadSlotChunk(P, p, t0, n, c);
@@ -1172,12 +1205,29 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, uint32_t p, uint32_t& nS
           acc.y = acc.y + c.cy[j];
           acc.z = acc.z + c.cz[j];
           acc.w = acc.w + 1.0f;
+          if (GROUPS) {
+            int l = (int)(nextRand(seed) * (float)K);  // gen_nee's lightToSample of term t0 + j
+            if (l > K - 1) l = K - 1;
+            float* a = la + 3 * l * kWave;
+            a[0] = a[0] + c.cx[j];
+            a[kWave] = a[kWave] + c.cy[j];
+            a[2 * kWave] = a[2 * kWave] + c.cz[j];
+            ex = ex + 0.0f;
+            ey = ey + 0.0f;
+            ez = ez + 0.0f;
+          }
         }
     }
   }
   if (!(F.p.flags & BDPT_PARAM_NO_CONNECT)) {
     const int nPairs = (int)numConnectPairs((uint32_t)D);
     bool sat = false;
+    float ox = 0.0f, oy = 0.0f, oz = 0.0f;  // the own light plane takes the saturating sequence of `out`
+    if (GROUPS) {
+      ox = la[(3 * own) * kWave];
+      oy = la[(3 * own + 1) * kWave];
+      oz = la[(3 * own + 2) * kWave];
+    }
     for (int s0 = 0; s0 < nPairs; s0 += kGatherChunk) {
       const int n = (nPairs - s0 < kGatherChunk) ? nPairs - s0 : kGatherChunk;
       loadSlotChunk(P, p, 2 * D + s0, n, c);
@@ -1188,12 +1238,34 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, uint32_t p, uint32_t& nS
           acc.y = saturate(acc.y + c.cy[j]);
           acc.z = saturate(acc.z + c.cz[j]);
           acc.w = saturate(acc.w + 1.0f);
+          if (GROUPS) {
+            ox = saturate(ox + c.cx[j]);
+            oy = saturate(oy + c.cy[j]);
+            oz = saturate(oz + c.cz[j]);
+          }
           sat = true;
         }
+    }
+    if (GROUPS) {
+      // every other plane: its pairs all carry 0, so it saturates once, where the first visible pair is
+      if (sat) {
+        for (int r = 0; r < 3 * K; r++) la[r * kWave] = saturate(la[r * kWave] + 0.0f);
+        ex = saturate(ex + 0.0f);
+        ey = saturate(ey + 0.0f);
+        ez = saturate(ez + 0.0f);
+      }
+      la[(3 * own) * kWave] = ox;
+      la[(3 * own + 1) * kWave] = oy;
+      la[(3 * own + 2) * kWave] = oz;
     }
     pending = (!sat && nPairs > 0);  // settled by the lazy rounds below
   }
   out4[pix] = acc;
+  if (GROUPS) {
+    float4* g4 = reinterpret_cast<float4*>(Gr.planes) + pix;
+    for (int k = 0; k < K; k++) g4[(size_t)k * Gr.framePix] = make_float4(la[(3 * k) * kWave], la[(3 * k + 1) * kWave], la[(3 * k + 2) * kWave], acc.w);
+    g4[(size_t)K * Gr.framePix] = make_float4(ex, ey, ez, acc.w);
+  }
   if (!(F.p.flags & BDPT_PARAM_NO_SPLAT)) {
     for (int t0 = 0; t0 < D; t0 += kGatherChunk) {
       const int n = (D - t0 < kGatherChunk) ? D - t0 : kGatherChunk;
@@ -1205,10 +1277,12 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, uint32_t p, uint32_t& nS
       for (int j = 0; j < kGatherChunk; j++) {
         if (!c.vis[j] || target[j] == kNoRay) continue;  // kNoRay: outside the frame (quirk 8)
         unsigned long long* sp = F.splat + (size_t)target[j] * 4;
+        // GROUPS: the value goes to the splat plane of the pixel's light only (resolve_groups sums the planes for `out`)
+        unsigned long long* sv = GROUPS ? Gr.splat + ((size_t)own * Gr.framePix + target[j]) * 4 : sp;
         const unsigned long long qx = toFixed(c.cx[j]), qy = toFixed(c.cy[j]), qz = toFixed(c.cz[j]);
-        if (qx) atomicAdd(&sp[0], qx);
-        if (qy) atomicAdd(&sp[1], qy);
-        if (qz) atomicAdd(&sp[2], qz);
+        if (qx) atomicAdd(&sv[0], qx);
+        if (qy) atomicAdd(&sv[1], qy);
+        if (qz) atomicAdd(&sv[2], qz);
         atomicAdd(&sp[3], 1ull);
         nSplat++;
       }
@@ -1227,7 +1301,24 @@ __global__ __launch_bounds__(kWave) void gather_kernel(FrameDev F, PathBuf P, ui
   bool pending = false;
   if (act) {
     p = P.queue[0][i];
-    pending = gatherLane(F, P, p, nSplat);
+    pending = gatherLane<false>(F, P, GroupDev{}, nullptr, p, nSplat);
+    if (pending) P.lazyCursor[p] = 0;
+  }
+  waveAddCount(F.counters, C_SPLATS, nSplat);
+  wavePush(pending, p, lazyList, lazyCount, P.pathSubCap);
+}
+__global__ __launch_bounds__(kWave) void gather_groups_kernel(FrameDev F, PathBuf P, GroupDev Gr, uint32_t* __restrict__ lazyList,
+                                                              uint32_t* __restrict__ lazyCount) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  __shared__ float s_acc[3 * BDPT_MAX_LIGHTS * kWave];  // light planes' RGB while a lane sums them (12 KiB)
+  bool act = false;
+  uint32_t i = 0;
+  if (!queueChunk(P.qcount, P.pathSubCap, act, i)) return;
+  uint32_t nSplat = 0, p = 0;
+  bool pending = false;
+  if (act) {
+    p = P.queue[0][i];
+    pending = gatherLane<true>(F, P, Gr, s_acc + threadIdx.x, p, nSplat);
     if (pending) P.lazyCursor[p] = 0;
   }
   waveAddCount(F.counters, C_SPLATS, nSplat);
@@ -1329,10 +1420,10 @@ __global__ __launch_bounds__(kWave) void lazy_gen_kernel(FrameDev F, PathBuf P, 
   waveAddCount(F.counters, C_RAYS_LAZY, nRays);
 }
 
-__global__ __launch_bounds__(kWave) void lazy_check_kernel(FrameDev F, PathBuf P, const uint32_t* __restrict__ list,
-                                                           const uint32_t* __restrict__ listCount, int batch,
-                                                           uint32_t* __restrict__ nextList, uint32_t* __restrict__ nextCount) {
-  BDPT_ONE_WAVE_PER_GROUP();
+// GROUPS: a visible lazy ray saturates every plane as it does `out` (no plane's pair carried anything: see gatherLane)
+template <bool GROUPS>
+BD void lazyCheck(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const uint32_t* list, const uint32_t* listCount, int batch,
+                  uint32_t* nextList, uint32_t* nextCount) {
   bool act = false;
   uint32_t i = 0;
   if (!queueChunk(listCount, P.pathSubCap, act, i)) return;
@@ -1354,12 +1445,35 @@ __global__ __launch_bounds__(kWave) void lazy_check_kernel(FrameDev F, PathBuf P
       acc.z = saturate(acc.z + 0.0f);
       acc.w = saturate(acc.w + 1.0f);
       out4[pix] = acc;
+      if (GROUPS) {
+        float4* g4 = reinterpret_cast<float4*>(Gr.planes) + pix;
+        for (uint32_t k = 0; k <= Gr.numLights; k++) {
+          float4 o = g4[(size_t)k * Gr.framePix];
+          o.x = saturate(o.x + 0.0f);
+          o.y = saturate(o.y + 0.0f);
+          o.z = saturate(o.z + 0.0f);
+          o.w = saturate(o.w + 1.0f);
+          g4[(size_t)k * Gr.framePix] = o;
+        }
+      }
     } else {
       const int nPairs = (int)numConnectPairs(F.p.maxDepth);
       again = (int)P.lazyCursor[p] < nPairs;
     }
   }
   wavePush(again, p, nextList, nextCount, P.pathSubCap);
+}
+__global__ __launch_bounds__(kWave) void lazy_check_kernel(FrameDev F, PathBuf P, const uint32_t* __restrict__ list,
+                                                           const uint32_t* __restrict__ listCount, int batch,
+                                                           uint32_t* __restrict__ nextList, uint32_t* __restrict__ nextCount) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  lazyCheck<false>(F, P, GroupDev{}, list, listCount, batch, nextList, nextCount);
+}
+__global__ __launch_bounds__(kWave) void lazy_check_groups_kernel(FrameDev F, PathBuf P, GroupDev Gr, const uint32_t* __restrict__ list,
+                                                                  const uint32_t* __restrict__ listCount, int batch,
+                                                                  uint32_t* __restrict__ nextList, uint32_t* __restrict__ nextCount) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  lazyCheck<true>(F, P, Gr, list, listCount, batch, nextList, nextCount);
 }
 
 // out = saturate(out + splat) where at least one splat landed
@@ -1380,6 +1494,48 @@ __global__ void resolve_kernel(const unsigned long long* __restrict__ splat, boo
     o.y = saturate(o.y + (float)a.y * 2.3283064365386963e-10f);
     o.z = saturate(o.z + (float)b.x * 2.3283064365386963e-10f);
     o.w = saturate(o.w + (float)b.y);
+    out[pix] = o;
+  }
+}
+
+// resolve_kernel for `out` and every light-group plane in one pass, where at least one splat landed (count word of
+// FrameDev::splat, shared by all).  `out`'s values are the sums of the light planes' values: integer sums, so equal to
+// what the plain frame's atomics add up to.  The emission plane lands splats of value 0.
+__global__ void resolve_groups_kernel(FrameDev F, const uint32_t* __restrict__ pixOf, uint32_t Np, GroupDev Gr) {
+  constexpr float kInvFix = 2.3283064365386963e-10f;
+  float4* out = reinterpret_cast<float4*>(F.out);
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < Np; p += (size_t)gridDim.x * blockDim.x) {
+    const size_t pix = pixOf[p];
+    const uint32_t y = (uint32_t)(pix / F.W), x = (uint32_t)(pix - (size_t)y * F.W);
+    const size_t sidx = splatIndex(F.sl, F.W, x, y);
+    const unsigned long long cnt = F.splat[sidx * 4 + 3];
+    if (cnt == 0ull) continue;
+    float4* g4 = reinterpret_cast<float4*>(Gr.planes) + pix;
+    unsigned long long tx = 0, ty = 0, tz = 0;
+    for (uint32_t k = 0; k <= Gr.numLights; k++) {
+      unsigned long long vx = 0, vy = 0, vz = 0;
+      if (k < Gr.numLights) {
+        const unsigned long long* sv = Gr.splat + ((size_t)k * Gr.framePix + sidx) * 4;
+        const ulonglong2 a = reinterpret_cast<const ulonglong2*>(sv)[0];
+        vx = a.x;
+        vy = a.y;
+        vz = sv[2];
+        tx += vx;
+        ty += vy;
+        tz += vz;
+      }
+      float4 o = g4[(size_t)k * Gr.framePix];
+      o.x = saturate(o.x + (float)vx * kInvFix);
+      o.y = saturate(o.y + (float)vy * kInvFix);
+      o.z = saturate(o.z + (float)vz * kInvFix);
+      o.w = saturate(o.w + (float)cnt);
+      g4[(size_t)k * Gr.framePix] = o;
+    }
+    float4 o = out[pix];
+    o.x = saturate(o.x + (float)tx * kInvFix);
+    o.y = saturate(o.y + (float)ty * kInvFix);
+    o.z = saturate(o.z + (float)tz * kInvFix);
+    o.w = saturate(o.w + (float)cnt);
     out[pix] = o;
   }
 }
@@ -1664,6 +1820,27 @@ void launchResolve(const unsigned long long* splat, bool tileLocal, uint32_t spl
   const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)Np + 255) / 256, 2048);
   hipLaunchKernelGGL(resolve_kernel, dim3(grid), dim3(256), 0, st, splat, tileLocal, splatRow0, L, reinterpret_cast<float4*>(out), W, pix,
                      Np);
+}
+void launchInitPathsGroups(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr, hipStream_t st) {
+  if (!P.Np) return;
+  if (F.p.matIndex == 0)
+    launchWave(init_paths_groups_kernel<true>, (uint32_t)(blocksFor(P.Np)), st, S, F, P, Gr);
+  else
+    launchWave(init_paths_groups_kernel<false>, (uint32_t)(blocksFor(P.Np)), st, S, F, P, Gr);
+}
+void launchGatherGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st) {
+  if (!P.Np) return;
+  launchWave(gather_groups_kernel, (uint32_t)(queueGrid(P)), st, F, P, Gr, lazyList, lazyCount);
+}
+void launchLazyCheckGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const uint32_t* list, const uint32_t* listCount,
+                           int batch, uint32_t* nextList, uint32_t* nextCount, hipStream_t st) {
+  if (!P.Np) return;
+  launchWave(lazy_check_groups_kernel, (uint32_t)(queueGrid(P)), st, F, P, Gr, list, listCount, batch, nextList, nextCount);
+}
+void launchResolveGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, hipStream_t st) {
+  if (!P.Np) return;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)P.Np + 255) / 256, 2048);
+  hipLaunchKernelGGL(resolve_groups_kernel, dim3(grid), dim3(256), 0, st, F, P.pix, P.Np, Gr);
 }
 void launchAccumulate(float* last, float* cur, uint32_t accumCount, uint32_t maxAccum, uint64_t numTexels, hipStream_t st) {
   if (!numTexels) return;

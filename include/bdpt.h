@@ -514,6 +514,7 @@ int bdpt_tile_row_ranges(const bdpt_ctx* ctx, uint32_t* out_first_last, uint32_t
 #define BDPT_PREPARE_PRIMARY 1u
 #define BDPT_PREPARE_BMFR 2u
 #define BDPT_PREPARE_REFIT 4u /* the refit plan and scratch of bdpt_update_geometry now (needs a scene, not a size) */
+#define BDPT_PREPARE_LIGHT_GROUPS 8u /* the per-light splat planes of bdpt_execute_light_groups (needs a scene and a size) */
 int bdpt_prepare(bdpt_ctx* ctx, uint32_t what);
 
 /* Primary-visibility pass.  Writes the tile rows of all six channels. */
@@ -528,6 +529,28 @@ int bdpt_gbuffer_execute(bdpt_ctx* ctx, const bdpt_gbuffer_params* p, const bdpt
  * bdpt_prepare(BDPT_PREPARE_PRIMARY), or else by the first such call — which therefore must not be
  * inside a stream capture (BDPT_E_STATE). */
 int bdpt_execute(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream);
+
+/* Light groups (light AOVs): bdpt_execute plus the frame broken down by light source, from the same paths and the same
+ * rays.  `groups` is device memory of (numLights + 1) x W x H RGBA32F planes, each laid out like `out`: plane k < numLights
+ * is light k (the scene's order), plane numLights is emission.  Every term of the frame has exactly one source — a
+ * next-event term the light drawn for it, a light-tracing splat and every connection the light the pixel's light subpath
+ * starts at, the G-buffer emissive, the background and the ENV_ON_MISS / EMISSIVE_HITS terms none — and paths, random
+ * draws, rays and w never depend on intensities.  Hence, bit for bit:
+ *   - `out` is what bdpt_execute writes, and the ray counters are the same;
+ *   - the emission plane (all four channels) is the bdpt_execute frame with every light's intensity zero;
+ *   - light plane k's RGB is the bdpt_execute frame with every other light's intensity zero, the G-buffer emissive RGB
+ *     zero, the background pixels' diffuse RGB zero and ENV_ON_MISS / EMISSIVE_HITS cleared;
+ *   - every plane's w is out.w.
+ * The planes add up to `out` only up to float reassociation, and only where `out` never saturates: each plane saturates
+ * on its own sums (the connection writes and the splat fold-in clamp to [0, 1]), as the frame it equals does.
+ * Ordering, stream use and in == NULL are those of bdpt_execute.  The per-light splat planes (numLights x W x H x 32 B,
+ * cleared every frame) are allocated by bdpt_prepare(BDPT_PREPARE_LIGHT_GROUPS) or by the first call, which then must not
+ * be inside a stream capture (BDPT_E_STATE); after the prepare the call allocates nothing and can be captured.
+ * bdpt_set_scene and bdpt_resize free them.
+ * Errors: a NULL ctx or groups BDPT_E_INVALID; BDPT_PARAM_DEFER_RESOLVE or BDPT_PARAM_DEFER_TAIL BDPT_E_INVALID; no scene
+ * or size BDPT_E_STATE; a context that renders a tile or stripes (not the whole frame) BDPT_E_INVALID — the splat
+ * exchange of tiled rendering has no group planes. */
+int bdpt_execute_light_groups(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, float* out, float* groups, void* stream);
 
 /* Second phase of a bdpt_execute issued with BDPT_PARAM_DEFER_TAIL (same params, channels and out). */
 int bdpt_execute_tail(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream);
