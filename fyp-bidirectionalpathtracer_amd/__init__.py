@@ -12,7 +12,8 @@ import ctypes as C
 from . import abi, tiling
 from .abi import (Camera, Counters, GBuffer, GBufferParams, Params, SceneDesc, Stripes, Tile, TileInfo, load_library)
 
-__all__ = ["abi", "tiling", "Scene", "Context", "FramePipeline", "load_library", "source_hash"]
+__all__ = ["abi", "tiling", "Scene", "Context", "FramePipeline", "load_library", "source_hash", "ADAPTIVE_DEFAULTS",
+           "adaptive_params"]
 
 # Channel names of the reference's ResourceManager (BDPTPass.cpp:27-29, LightProbeGBufferPass.cpp:46-51)
 GBUFFER_CHANNELS = ("WorldPosition", "WorldNormal", "MaterialDiffuse", "MaterialSpecRough", "MaterialExtraParams",
@@ -361,6 +362,24 @@ class Context:
         self._check(self._lib.bdpt_execute_light_groups(self._h, C.byref(params), C.byref(gbuffer), out_ptr, groups_ptr, stream),
                     "bdpt_execute_light_groups")
 
+    def execute_masked(self, params, gbuffer, mask_ptr, out_ptr, stream=None):
+        """bdpt_execute_masked: bdpt_execute for the pixels whose byte of `mask_ptr` (W x H uint8, device) is non-zero;
+        the others' `out` is left as it is (contract in include/bdpt.h)."""
+        self._check(self._lib.bdpt_execute_masked(self._h, C.byref(params), C.byref(gbuffer), mask_ptr, out_ptr, stream),
+                    "bdpt_execute_masked")
+
+    def adaptive_reset(self, state, stream=None):
+        """bdpt_adaptive_reset: `state` is an abi.AdaptiveState of device pointers (mean = m2 = count = 0, mask = 1)."""
+        self._check(self._lib.bdpt_adaptive_reset(self._h, C.byref(state), stream), "bdpt_adaptive_reset")
+
+    def adaptive_update(self, params, state, frame_ptr, stream=None):
+        """bdpt_adaptive_update: fold the frame at `frame_ptr` into `state`, write the next mask and the mean back to the
+        frame.  `params` is an abi.AdaptiveParams or a dict for adaptive_params()."""
+        if not isinstance(params, abi.AdaptiveParams):
+            params = adaptive_params(params)
+        self._check(self._lib.bdpt_adaptive_update(self._h, C.byref(params), C.byref(state), frame_ptr, stream),
+                    "bdpt_adaptive_update")
+
     def execute_tail(self, params, gbuffer, out_ptr, stream=None):
         self._check(self._lib.bdpt_execute_tail(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream),
                     "bdpt_execute_tail")
@@ -461,6 +480,28 @@ class Context:
             pass
 
 
+# Defaults of FramePipeline(adaptive={...}): measured on the bench frame (profiles/README.md "Adaptive sampling").
+ADAPTIVE_DEFAULTS = {"threshold": 0.15, "epsilon": 1e-3, "min_samples": 8, "max_samples": 256, "block_size": 8}
+
+
+def adaptive_params(d=None):
+    """abi.AdaptiveParams from a dict of ADAPTIVE_DEFAULTS' keys (missing keys take the defaults).  The checks are
+    bdpt_adaptive_update's, made here too so that a bad setting fails before a GPU is touched."""
+    d = dict(d or {})
+    unknown = set(d) - set(ADAPTIVE_DEFAULTS)
+    if unknown:
+        raise BdptError(f"adaptive: unknown setting(s) {sorted(unknown)}; known: {sorted(ADAPTIVE_DEFAULTS)}")
+    v = dict(ADAPTIVE_DEFAULTS, **d)
+    b, lo, hi = int(v["block_size"]), int(v["min_samples"]), int(v["max_samples"])
+    if b not in (1, 2, 4, 8, 16):
+        raise BdptError(f"adaptive: block_size must be 1, 2, 4, 8 or 16, not {v['block_size']!r}")
+    if lo < 2 or hi < lo:
+        raise BdptError(f"adaptive: need 2 <= min_samples <= max_samples (got {lo}, {hi})")
+    if hi >= 2 ** 32:
+        raise BdptError("adaptive: max_samples must fit in 32 bits")
+    return abi.AdaptiveParams(float(v["threshold"]), float(v["epsilon"]), lo, hi, b)
+
+
 class FramePipeline:
     """The reference's per-frame sequence for this path on one GPU / one tile.
 
@@ -472,12 +513,24 @@ class FramePipeline:
     float32 tensor with the frame's planes (plane k = light k, the last = emission) and ``light_groups_accum`` their
     running means, kept by one bdpt_accumulate over all planes with the beauty's counters.  As the beauty's ``output``,
     ``light_groups`` holds the mean too after an accumulating frame.  Whole frames only: not with a tile or stripes.
+
+    adaptive={...} (settings of ADAPTIVE_DEFAULTS; {} for the defaults) makes every frame adaptive: bdpt_execute_masked
+    renders the pixels of ``adaptive_state["mask"]`` and bdpt_adaptive_update folds them into the per-pixel running mean
+    (``adaptive_state``: mean, m2, count, mask, active), which ``output`` then shows.  This replaces the accumulation
+    pass: render_frame's ``accumulate`` has no effect.  active_pixels() reads how many pixels the next frame renders (0:
+    the image has converged); adaptive_reset() starts over (after a camera, scene or light change).  Whole frames only,
+    and not with light_groups.
     """
 
     def __init__(self, scene, width, height, max_depth=3, mat_index=0, device=0, tile=None, clamp_upper=0.9, min_t=1e-4,
-                 accum_limit=100, flags=0, stripes=None, light_groups=False):
+                 accum_limit=100, flags=0, stripes=None, light_groups=False, adaptive=None):
         import torch
         self.torch = torch
+        self.adaptive_params = None if adaptive is None else adaptive_params(adaptive)
+        if adaptive is not None and (light_groups or stripes is not None or
+                                     (tile is not None and (int(tile[0]), int(tile[1])) != (0, int(height)))):
+            raise BdptError("adaptive sampling needs a pipeline that renders the whole frame (no tile, no stripes) without "
+                            "light groups")
         if light_groups and (stripes is not None or (tile is not None and (int(tile[0]), int(tile[1])) != (0, int(height)))):
             raise BdptError("light groups need a pipeline that renders the whole frame (no tile, no stripes)")
         if not torch.cuda.is_available():
@@ -521,6 +574,18 @@ class FramePipeline:
                 k = int(scene.desc.numLights) + 1
                 self.light_groups = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
                 self.light_groups_accum = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
+            self.adaptive_state = None
+            if adaptive is not None:
+                self.adaptive_state = {
+                    "mean": torch.zeros(self.H, self.W, 4, dtype=torch.float32, device=self.dev),
+                    "m2": torch.zeros(self.H, self.W, dtype=torch.float32, device=self.dev),
+                    "count": torch.zeros(self.H, self.W, dtype=torch.int32, device=self.dev),  # (uint32 in the library)
+                    "mask": torch.ones(self.H, self.W, dtype=torch.uint8, device=self.dev),
+                    "active": torch.zeros(1, dtype=torch.int32, device=self.dev),
+                }
+                st = self.adaptive_state
+                self._adaptive_c = abi.AdaptiveState(*[st[k].data_ptr() for k in ("mean", "m2", "count", "mask", "active")])
+                self.ctx.adaptive_reset(self._adaptive_c, C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
         torch.cuda.synchronize(self.dev)
         # where the set-up time went: the scene (acceleration structure + uploads) and the frame's buffers are separate things
         self.setup_times = {"context_s": t1 - t0, "resize_s": t2 - t1, "set_scene_s": t3 - t2, "channels_s": time.time() - t3}
@@ -575,6 +640,13 @@ class FramePipeline:
         if gbuffer:
             self.ctx.gbuffer_execute(gp, self.gb, st)
         p = self.bdpt_params(extra_flags)
+        if self.adaptive_state is not None:
+            self.ctx.execute_masked(p, self.gb, C.c_void_p(self.adaptive_state["mask"].data_ptr()), C.c_void_p(self.output.data_ptr()), st)
+            self.ctx.adaptive_update(self.adaptive_params, self._adaptive_c, C.c_void_p(self.output.data_ptr()), st)
+            self.gbuffer_frame += 1
+            self.bdpt_frame += 1
+            self.last_params = (gp, p)
+            return gp, p
         if self.light_groups is None:
             self.ctx.execute(p, self.gb, C.c_void_p(self.output.data_ptr()), st)
         else:
@@ -596,6 +668,18 @@ class FramePipeline:
                                          self.accum_limit, st)
         self.last_params = (gp, p)
         return gp, p
+
+    def active_pixels(self):
+        """Adaptive pipelines: pixels the next frame renders (the `active` word; waits for the pipeline's stream)."""
+        if self.adaptive_state is None:
+            raise BdptError("active_pixels: the pipeline is not adaptive (FramePipeline(..., adaptive={...}))")
+        return int(self.adaptive_state["active"].item()) & 0xFFFFFFFF
+
+    def adaptive_reset(self):
+        """Adaptive pipelines: forget every pixel's mean and render all pixels again."""
+        if self.adaptive_state is None:
+            raise BdptError("adaptive_reset: the pipeline is not adaptive (FramePipeline(..., adaptive={...}))")
+        self.ctx.adaptive_reset(self._adaptive_c, self._stream_ptr())
 
     def update_geometry(self, positions, normals=None, bitangents=None, keep_light_maps=False):
         """Move the scene's vertices (Context.update_geometry on this pipeline's stream); accumulation restarts, as after

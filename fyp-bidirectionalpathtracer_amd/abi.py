@@ -146,6 +146,15 @@ class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_int32)]
 
 
+class AdaptiveState(C.Structure):
+    _fields_ = [("mean", C.c_void_p), ("m2", C.c_void_p), ("count", C.c_void_p), ("mask", C.c_void_p), ("active", C.c_void_p)]
+
+
+class AdaptiveParams(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("epsilon", C.c_float), ("minSamples", C.c_uint32), ("maxSamples", C.c_uint32),
+                ("blockSize", C.c_uint32)]
+
+
 class TraceDesc(C.Structure):
     _fields_ = [("rays", C.c_void_p), ("numRays", C.c_uint32), ("mode", C.c_uint32), ("numRaysDevice", C.c_void_p),
                 ("hits", C.c_void_p), ("visible", C.c_void_p)]
@@ -183,6 +192,9 @@ PROTOTYPES = {
     "bdpt_execute_tail": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_execute_light_groups": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
+    "bdpt_execute_masked": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdpt_adaptive_reset": (C.c_int, [C.c_void_p, C.POINTER(AdaptiveState), C.c_void_p]),
+    "bdpt_adaptive_update": (C.c_int, [C.c_void_p, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveState), C.c_void_p, C.c_void_p]),
     "bdpt_prepare": (C.c_int, [C.c_void_p, C.c_uint32]),
     "bdpt_resize_stripes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, Stripes, C.c_uint32]),
     "bdpt_stripe_rows": (C.c_uint32, [C.c_uint32, C.c_uint32]),

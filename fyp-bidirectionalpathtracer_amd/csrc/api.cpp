@@ -38,6 +38,12 @@ constexpr int kMaxStages = 64;
 constexpr size_t kCountBlocks = 1;  // lengths of the valid-pixel lists
 constexpr size_t kHeadBlocks = 2;   // fetch cursors of the walk kernel: pixel list x {eye, light}
 constexpr size_t kLazyBlocks = kMaxLazyRounds + 2;
+// bdpt_execute_masked's eye list borrows two things no stage before the lazy rounds uses: its items live in the second
+// lazy-round list (PathBuf::queue[2], which the first lazy round is the first to write, after the generators that read
+// the eye list), its lengths in the last lazy cursor block (rounds use blocks 0 .. kMaxLazyRounds), which the frame's
+// clear of kCursorWords zeroes with everything else.  So a masked frame allocates nothing and adds no memset.
+constexpr size_t kEyeCountBlock = kLazyBlocks - 1;
+static_assert(kEyeCountBlock > (size_t)kMaxLazyRounds, "the eye list's cursor block must be one no lazy round uses");
 constexpr size_t kCursorWords = (kCountBlocks + kHeadBlocks + kLazyBlocks) * kCursorBlock + 4 * kRayCursorBlock;  // + ray count / head blocks of two classes
 }
 
@@ -83,6 +89,7 @@ struct bdpt_ctx {
   int* stackOvf = nullptr;      // overflow rows of the persistent kernels' traversal stacks (kernels.h kStackLds)
   uint32_t stackOvfStride = 0;  // lanes per row: every wave a persistent grid can hold
   unsigned long long* rayCursor = nullptr;  // fetch cursor and done count of bdpt_trace_rays (each launch leaves them zero)
+  unsigned long long* adaptiveSum = nullptr;  // active-pixel sum and done count of bdpt_adaptive_update (each launch leaves them zero)
   // channels of the built-in primary stage (bdpt_execute with in == NULL): bdpt_prepare or first use
   bdpt_gbuffer ownGb{};
   // BMFR history (bdpt_prepare or the first bdpt_bmfr_execute): [2] = ping-pong pair
@@ -312,7 +319,9 @@ int bdpt_create(int device_ordinal, bdpt_ctx** out_ctx) {
     return BDPT_E_NOMEM;
   }
   if (hipMalloc(reinterpret_cast<void**>(&c->rayCursor), 2 * sizeof(unsigned long long)) != hipSuccess ||
-      hipMemset(c->rayCursor, 0, 2 * sizeof(unsigned long long)) != hipSuccess) {
+      hipMemset(c->rayCursor, 0, 2 * sizeof(unsigned long long)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&c->adaptiveSum), 2 * sizeof(unsigned long long)) != hipSuccess ||
+      hipMemset(c->adaptiveSum, 0, 2 * sizeof(unsigned long long)) != hipSuccess) {
     bdpt_destroy(c);
     return BDPT_E_NOMEM;
   }
@@ -327,6 +336,7 @@ void bdpt_destroy(bdpt_ctx* c) {
   (void)hipDeviceSynchronize();
   if (c->stackOvf) (void)hipFree(c->stackOvf);
   if (c->rayCursor) (void)hipFree(c->rayCursor);
+  if (c->adaptiveSum) (void)hipFree(c->adaptiveSum);
   freeLightGroups(c);
   freePool(c->sceneAllocs);
   freePool(c->frameAllocs);
@@ -1208,8 +1218,9 @@ int frameSetup(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float*
 
 // Connection pairs whose contribution is exactly zero, for the pixels no visible connection has saturated
 // yet (DESIGN.md "Lazy connection rounds"), then the splat fold-in unless the caller defers it.
-// Grp (bdpt_execute_light_groups): the group variants of the lazy check and the resolve.
-int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st, const GroupDev* Grp = nullptr) {
+// Grp (bdpt_execute_light_groups): the group variants of the lazy check and the resolve.  Msk (bdpt_execute_masked): the
+// masked resolve (the lazy rounds only ever see the active pixels gather handed them).
+int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st, const GroupDev* Grp = nullptr, const MaskDev* Msk = nullptr) {
   const PathBuf& P = c->P;
   const bdpt_params* p = &F.p;
   const int D = (int)p->maxDepth;
@@ -1243,6 +1254,9 @@ int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st, const GroupDe
   if (Grp) {
     launchResolveGroups(F, P, *Grp, st);
     stageMark(c, st, "resolve_groups");
+  } else if (Msk) {
+    launchResolveMasked(F, P, *Msk, st);
+    stageMark(c, st, "resolve_masked");
   } else if (!(p->flags & BDPT_PARAM_DEFER_RESOLVE)) {
     launchResolve(c->splat, false, 0, c->sl, F.out, c->W, c->P.pix, c->P.Np, st);
     stageMark(c, st, "resolve");
@@ -1256,11 +1270,27 @@ int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st, const GroupDe
 namespace {
 // bdpt_execute, and bdpt_execute_light_groups with Grp set: the same stages and the same rays; the group path swaps in
 // the group variants of init_paths, gather, the lazy check and the resolve, and clears its splat-value planes.
-int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream, const GroupDev* Grp) {
+// bdpt_execute_masked with Msk set: the masked init_paths, walk, gather and resolve, and the generators of eye-side
+// terms (NEE, connections) over the eye list (`PE`: the PathBuf with the eye list as its pixel list).
+int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream, const GroupDev* Grp,
+                 const MaskDev* Msk = nullptr) {
   FrameDev F;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = frameSetup(c, p, in, out, st, F)) return rc;
   const PathBuf& P = c->P;
+  PathBuf eyeP = P;
+  MaskDev M{};
+  if (Msk) {
+    M = *Msk;
+    M.eye = P.queue[2];
+    M.eyeCount = P.lazyCount + kEyeCountBlock * kCursorBlock;
+    const bool misOn = (p->flags & (BDPT_PARAM_MIS_POWER | BDPT_PARAM_MIS_LINEAR)) != 0;
+    M.walkEye = misOn ? P.queue[0] : M.eye;  // under MIS every valid pixel's eye prefix products are read by its splats
+    M.walkEyeCount = misOn ? P.qcount : M.eyeCount;
+    eyeP.queue[0] = M.eye;
+    eyeP.qcount = M.eyeCount;
+  }
+  const PathBuf& PE = Msk ? eyeP : P;
   if (!in) {
     // Built-in primary stage: pinhole camera, this frame's jitter and counter, the default constant
     // environment (SharedUtils/ResourceManager.cpp:77-87) — what LightProbeGBufferPass does with its defaults.
@@ -1286,13 +1316,18 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
 
   if (Grp)
     launchInitPathsGroups(c->S, F, P, *Grp, st);
+  else if (Msk)
+    launchInitPathsMasked(c->S, F, P, M, st);
   else
     launchInitPaths(c->S, F, P, st);
   stageMark(c, st, "init_paths");
 
   // Both walks (eye vertices 2..D, BDPTMain.rt.hlsl:106-112; light vertices 1..D, :138-145) in one persistent
   // launch: traversal and hit/miss shading alternate inside the kernel, lanes re-arm themselves per bounce.
-  launchWalk(c->S, F, P, c->grids, c->numCUs, st);
+  if (Msk)
+    launchWalkMasked(c->S, F, P, M, c->grids, c->numCUs, st);
+  else
+    launchWalk(c->S, F, P, c->grids, c->numCUs, st);
   stageMark(c, st, "walk");
 
   // NEE terms (caller's stream) and splat terms (second stream) are generated side by side and traced at once (ray
@@ -1302,11 +1337,11 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
   if (mis) {
     launchMisPrefix(F, P, st);
     stageMark(c, st, "mis_prefix");
-    launchGenNee(c->S, F, P, st);
+    launchGenNee(c->S, F, PE, st);
     stageMark(c, st, "gen_nee");
     launchGenSplat(c->S, F, P, st);
     stageMark(c, st, "gen_splat");
-    launchGenConnect(c->S, F, P, st);
+    launchGenConnect(c->S, F, PE, st);
     stageMark(c, st, "gen_connect");
     launchTraceShadow(c->S, F, P, RAY_TERMS, c->grids, c->numCUs, st);
     stageMark(c, st, "trace_terms");
@@ -1323,10 +1358,10 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
     sideEnd(c, c->walkStream);
     HIPCHK(c, hipEventRecord(c->evSplat, c->walkStream));
     sideBegin(c, c->walkStream, "side:gen_connect");
-    launchGenConnect(c->S, F, P, c->walkStream);
+    launchGenConnect(c->S, F, PE, c->walkStream);
     sideEnd(c, c->walkStream);
     HIPCHK(c, hipEventRecord(c->evJoin, c->walkStream));
-    launchGenNee(c->S, F, P, st);
+    launchGenNee(c->S, F, PE, st);
     stageMark(c, st, "gen_nee");
     HIPCHK(c, hipStreamWaitEvent(st, c->evSplat, 0));
     stageMark(c, st, "splat_wait");
@@ -1339,6 +1374,8 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
   stageMark(c, st, "trace_pairs");
   if (Grp)
     launchGatherGroups(F, P, *Grp, P.queue[1], P.lazyCount, st);
+  else if (Msk)
+    launchGatherMasked(F, P, M, P.queue[1], P.lazyCount, st);
   else
     launchGather(F, P, P.queue[1], P.lazyCount, st);
   stageMark(c, st, "gather");
@@ -1349,7 +1386,7 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
     c->lastStream = st;
     return BDPT_OK;
   }
-  return connectionTail(c, F, st, Grp);
+  return connectionTail(c, F, st, Grp, Msk);
 }
 
 // the group path's buffers; not while the stream is being captured
@@ -1405,6 +1442,106 @@ int bdpt_execute_light_groups(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuf
   G.numLights = c->S.numLights;
   G.framePix = (uint64_t)c->W * c->H;
   return executeFrame(c, p, in, out, stream, &G);
+}
+
+int bdpt_execute_masked(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, const uint8_t* mask, float* out, void* stream) {
+  if (!c) return BDPT_E_INVALID;
+  if (!mask) {
+    fail(c, "execute_masked: mask is NULL");
+    return BDPT_E_INVALID;
+  }
+  if (p && (p->flags & (BDPT_PARAM_DEFER_RESOLVE | BDPT_PARAM_DEFER_TAIL))) {
+    fail(c, "execute_masked: BDPT_PARAM_DEFER_RESOLVE and BDPT_PARAM_DEFER_TAIL are not supported");
+    return BDPT_E_INVALID;
+  }
+  if (!c->haveScene || !c->haveSize) {
+    fail(c, "execute_masked: scene and size must be set first");
+    return BDPT_E_STATE;
+  }
+  if (c->stripes.stripeRows != 0 || c->tileRows != c->H) {
+    fail(c, "execute_masked: the context must render the whole frame (no tile, no stripes)");
+    return BDPT_E_INVALID;
+  }
+  MaskDev M{};
+  M.mask = mask;  // (the eye list and what the walk reads: executeFrame)
+  return executeFrame(c, p, in, out, stream, nullptr, &M);
+}
+
+namespace {
+// the arguments of bdpt_adaptive_reset / _update: a whole-frame context and every state buffer
+int adaptiveSetup(bdpt_ctx* c, const bdpt_adaptive_state* s, const char* what, AdaptiveDev& A) {
+  if (!s || !s->mean || !s->m2 || !s->count || !s->mask || !s->active) {
+    fail(c, std::string(what) + ": a state buffer is NULL");
+    return BDPT_E_INVALID;
+  }
+  if (!c->haveScene || !c->haveSize) {
+    fail(c, std::string(what) + ": scene and size must be set first");
+    return BDPT_E_STATE;
+  }
+  if (c->stripes.stripeRows != 0 || c->tileRows != c->H) {
+    fail(c, std::string(what) + ": the context must render the whole frame (no tile, no stripes)");
+    return BDPT_E_INVALID;
+  }
+  if (reinterpret_cast<uintptr_t>(s->mean) % 16 != 0) {
+    fail(c, std::string(what) + ": mean must be 16-byte aligned (RGBA32F)");
+    return BDPT_E_INVALID;
+  }
+  A = AdaptiveDev{};
+  A.mean = reinterpret_cast<float4*>(s->mean);
+  A.m2 = s->m2;
+  A.count = s->count;
+  A.mask = s->mask;
+  A.active = s->active;
+  A.W = c->W;
+  A.H = c->H;
+  return BDPT_OK;
+}
+}  // namespace
+
+int bdpt_adaptive_reset(bdpt_ctx* c, const bdpt_adaptive_state* s, void* stream) {
+  if (!c) return BDPT_E_INVALID;
+  AdaptiveDev A;
+  if (int rc = adaptiveSetup(c, s, "adaptive_reset", A)) return rc;
+  ENTER(c);
+  launchAdaptiveReset(A, reinterpret_cast<hipStream_t>(stream));
+  HIPCHK(c, hipGetLastError());
+  return BDPT_OK;
+}
+
+int bdpt_adaptive_update(bdpt_ctx* c, const bdpt_adaptive_params* a, const bdpt_adaptive_state* s, float* frame, void* stream) {
+  if (!c) return BDPT_E_INVALID;
+  if (!a || !frame) {
+    fail(c, "adaptive_update: params or frame is NULL");
+    return BDPT_E_INVALID;
+  }
+  const uint32_t b = a->blockSize;
+  if (b != 1 && b != 2 && b != 4 && b != 8 && b != 16) {
+    fail(c, "adaptive_update: blockSize must be 1, 2, 4, 8 or 16");
+    return BDPT_E_INVALID;
+  }
+  if (a->minSamples < 2 || a->maxSamples < a->minSamples) {
+    fail(c, "adaptive_update: need 2 <= minSamples <= maxSamples");
+    return BDPT_E_INVALID;
+  }
+  if (reinterpret_cast<uintptr_t>(frame) % 16 != 0) {
+    fail(c, "adaptive_update: frame must be 16-byte aligned (RGBA32F)");
+    return BDPT_E_INVALID;
+  }
+  AdaptiveDev A;
+  if (int rc = adaptiveSetup(c, s, "adaptive_update", A)) return rc;
+  A.frame = reinterpret_cast<float4*>(frame);
+  A.threshold = a->threshold;
+  A.epsilon = a->epsilon;
+  A.minSamples = a->minSamples;
+  A.maxSamples = a->maxSamples;
+  A.blockSize = b;
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;  // (the sum words: one update of a context at a time)
+  launchAdaptiveUpdate(A, c->adaptiveSum, st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
 }
 
 int bdpt_execute_tail(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream) {

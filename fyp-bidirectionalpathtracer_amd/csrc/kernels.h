@@ -183,6 +183,19 @@ struct GroupDev {
   uint64_t framePix;           // W*H: the stride of both kinds of plane
 };
 
+// Masked frames (bdpt_execute_masked): only the pixels a caller's mask selects trace eye paths, NEE and connection rays,
+// gather and write `out`; every valid pixel still traces its light subpath and its splats.  Only the masked variants of
+// init_paths, walk, gather and resolve take it, so the argument layout of every other kernel stays as it is; gen_nee,
+// gen_connect and the lazy rounds run unchanged on a PathBuf copy whose queue[0] / qcount name the eye list.
+// Whole-frame contexts only (the mask is indexed by frame pixel).
+struct MaskDev {
+  const uint8_t* mask;          // W*H bytes, frame order: non-zero = active
+  uint32_t* eye;                // eye list: the active valid pixels, sharded as PathBuf::queue[0] (init_paths appends)
+  uint32_t* eyeCount;           // its cursor block (kCursorBlock words, zero when init_paths starts)
+  const uint32_t* walkEye;      // what the walk's eye lists read: `eye`, or under MIS the valid list (PathBuf::queue[0])
+  const uint32_t* walkEyeCount; // and their lengths
+};
+
 struct GBufferDev {
   bdpt_camera cam;
   bdpt_gbuffer_params gp;
@@ -222,6 +235,7 @@ void launchInitPaths(const SceneDev& S, const FrameDev& F, const PathBuf& P, hip
 // Persistent-grid sizes of one context's device, filled on first use (occupancy query per kernel variant).
 struct LaunchGrids {
   uint32_t walk[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // [EXT][GGX][COUNT]
+  uint32_t walkMasked[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for walk_masked_kernel
   uint32_t shadow[2] = {0, 0};        // [COUNT]
   uint32_t rays[3] = {0, 0, 0};       // [mode] (trace_rays.hip)
 };
@@ -256,6 +270,29 @@ void launchGatherGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr,
 void launchLazyCheckGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const uint32_t* list, const uint32_t* listCount,
                            int batch, uint32_t* nextList, uint32_t* nextCount, hipStream_t st);
 void launchResolveGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, hipStream_t st);
+// Masked-frame variants (MaskDev): init_paths that also builds the eye list and writes `out` for active pixels only, the
+// walk whose eye lists read MaskDev::walkEye (and that adds ENV_ON_MISS / EMISSIVE_HITS terms to active pixels only),
+// gather over every valid pixel that sums and writes only active ones (every pixel's splats still land), and the resolve
+// of active pixels.
+void launchInitPathsMasked(const SceneDev& S, const FrameDev& F, const PathBuf& P, const MaskDev& M, hipStream_t st);
+void launchWalkMasked(const SceneDev& S, const FrameDev& F, const PathBuf& P, const MaskDev& M, LaunchGrids& G, int numCUs, hipStream_t st);
+void launchGatherMasked(const FrameDev& F, const PathBuf& P, const MaskDev& M, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
+void launchResolveMasked(const FrameDev& F, const PathBuf& P, const MaskDev& M, hipStream_t st);
+// bdpt_adaptive_update (adaptive.hip; exact arithmetic in include/bdpt.h "Adaptive sampling").  `scratch`: two words of
+// the context, zero when the launch starts; the launch leaves them zero.
+struct AdaptiveDev {
+  float4* mean;
+  float* m2;
+  uint32_t* count;
+  uint8_t* mask;
+  uint32_t* active;
+  float4* frame;
+  uint32_t W, H;
+  float threshold, epsilon;
+  uint32_t minSamples, maxSamples, blockSize;
+};
+void launchAdaptiveUpdate(const AdaptiveDev& A, unsigned long long* scratch, hipStream_t st);
+void launchAdaptiveReset(const AdaptiveDev& A, hipStream_t st);
 void launchAccumulate(float* last, float* cur, uint32_t accumCount, uint32_t maxAccum, uint64_t numTexels, hipStream_t st);
 void launchAccumulateTile(float* last, float* cur, uint32_t accumCount, uint32_t maxAccum, const uint32_t* pix, uint32_t Np,
                           hipStream_t st);

@@ -308,12 +308,16 @@ __global__ __launch_bounds__(kWave) void light_map_kernel(SceneDev S, uint32_t* 
 // ------------------------------------------------------------------------------------------------
 // GROUPS (bdpt_execute_light_groups): also the light of each pixel's light subpath, and the planes of the pixels without
 // geometry — the emission plane what `out` gets, a light plane (0, 0, 0, 1): the frame with that background stripped
-template <bool GGX, bool GROUPS>
-BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr) {
+// MASKED (bdpt_execute_masked): every pixel's paths start as in the plain frame (its light subpath and seedL, which the
+// eye vertex's draws lead to, are needed whatever the mask says), but only active pixels get their `out` write, and the
+// active valid ones also go onto the eye list
+template <bool GGX, bool GROUPS, bool MASKED = false>
+BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const MaskDev& M = MaskDev{}) {
   const uint32_t p = blockIdx.x * kWave + threadIdx.x;
   const bool inTile = p < P.Np;
   const size_t pix = inTile ? P.pix[p] : 0;
   bool geom = false;
+  const bool active = !MASKED || (inTile && M.mask[pix] != 0);
   float4* out4 = reinterpret_cast<float4*>(F.out);
   if (inTile) {
     const float4 wp = reinterpret_cast<const float4*>(F.gb.worldPosition)[pix];
@@ -321,7 +325,7 @@ BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, co
     unpackHalf4(F.gb.materialDiffuse, pix, dr, dg, db, da);
     geom = (wp.w != 0.0f);
     if (!geom) {
-      out4[pix] = make_float4(dr, dg, db, 1.0f);  // :62-66
+      if (active) out4[pix] = make_float4(dr, dg, db, 1.0f);  // :62-66
       P.eyeLast[p] = 0;
       if (GROUPS) {
         float4* g4 = reinterpret_cast<float4*>(Gr.planes) + pix;
@@ -389,10 +393,11 @@ BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, co
       P.lightReal[p] = D;
       // gOutput cleared (BDPTPass.cpp:73) then += emissive (:155-158)
       const bool em = (er > 0.0f) || (eg > 0.0f) || (eb > 0.0f);
-      out4[pix] = em ? make_float4(0.0f + er, 0.0f + eg, 0.0f + eb, 0.0f + ea) : make_float4(0, 0, 0, 0);
+      if (active) out4[pix] = em ? make_float4(0.0f + er, 0.0f + eg, 0.0f + eb, 0.0f + ea) : make_float4(0, 0, 0, 0);
     }
   }
   wavePush(geom, p, P.queue[0], P.qcount, P.pathSubCap);
+  if (MASKED) wavePush(geom && active, p, M.eye, M.eyeCount, P.pathSubCap);
 }
 template <bool GGX>
 __global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev F, PathBuf P) {
@@ -403,6 +408,11 @@ template <bool GGX>
 __global__ __launch_bounds__(kWave) void init_paths_groups_kernel(SceneDev S, FrameDev F, PathBuf P, GroupDev Gr) {
   BDPT_ONE_WAVE_PER_GROUP();
   initPathsLane<GGX, true>(S, F, P, Gr);
+}
+template <bool GGX>
+__global__ __launch_bounds__(kWave) void init_paths_masked_kernel(SceneDev S, FrameDev F, PathBuf P, MaskDev M) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  initPathsLane<GGX, false, true>(S, F, P, GroupDev{}, M);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -433,6 +443,9 @@ __global__ __launch_bounds__(kWave) void init_paths_groups_kernel(SceneDev S, Fr
 // reference's path pays nothing for it: the eye walk's shading pass adds what the ray found where it ended —
 // environment radiance on a miss, emissive on a hit — to the path's own pixel, in bounce order (a sub-path is shaded
 // by one lane at a time, and init_paths has written the pixel before this launch starts).
+// MASKED (bdpt_execute_masked) is a kernel of its own too: its eye lists (vq < kNumSubQueues) read MaskDev::walkEye, the
+// active valid pixels (under MIS every valid pixel: the splat weights read the eye prefix products), its light lists the
+// valid-pixel queue as before, and EXT terms reach active pixels only.
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kPoolEntries = 128;
 #ifndef BDPT_WALK_ORDER
@@ -463,257 +476,24 @@ BD uint32_t packPath(uint32_t p, int path, int k) { return p | ((uint32_t)path <
 #endif
 constexpr int kWalkStackLds = BDPT_WALK_STACK_LDS;
 constexpr uint32_t kParkedMiss = 1u << 30;
+// The body of both walk kernels (walk_body.inc), included into each so that the plain kernel's code stays what it was.
+// It names S, F, P, head, s_stack, s_pool, the template flags GGX, COUNT, EXT, and MASKED with the MaskDev M.
 template <bool GGX, bool COUNT, bool EXT>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK_WAVES_PER_EU, 8))) void walk_kernel(SceneDev S, FrameDev F, PathBuf P, uint32_t* __restrict__ head) {
   BDPT_ONE_WAVE_PER_GROUP();
   __shared__ int s_stack[kWalkStackLds * kWave];
   __shared__ uint4 s_pool[kPoolEntries];
-  int* stk = s_stack + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63u);
-  const unsigned long long laneBelow = (1ull << lane) - 1ull;
-  const int D = (int)F.p.maxDepth;
-  const bool fromLobe = (F.p.flags & BDPT_PARAM_SPECULAR_FROM_LOBE) != 0;
-  // the eye walk extends vertices 1..D-1 (none when D < 2), the light walk vertices 0..D-1
-  const uint32_t firstV = (D >= 2) ? 0u : kNumSubQueues, numV = 2u * kNumSubQueues - firstV;
-  bool trav = false;   // this lane holds a ray
-  uint32_t id = 0;     // its path id
-  TravState T;
-  travInit(T, mk(0), mk(0), F.p.minT, 1.0e38f);
-  T.cur = kDone;
-  uint32_t nNodes = 0, nTris = 0, nAlpha = 0;
-  uint32_t nEye = 0, nLight = 0, nParked = 0, nReady = 0;  // wave-uniform
-  uint32_t vq = firstV + blockIdx.x % numV, tried = 0, chunkPos = 0, chunkEnd = 0, chunk = BDPT_WALK_CHUNK;
-  bool exhausted = false;
-  const uint32_t wavesPerList = (gridDim.x + numV - 1) / numV;
-  for (;;) {
-    unsigned long long travMask = __ballot(trav);
-    // ---- 1. hit / miss shaders, one parked record per lane ------------------------------------------
-    // (also when nothing else can make progress: the last records of the wave are shaded short-handed)
-    const bool flush = (travMask == 0ull) && nReady == 0 && exhausted && nParked > 0;
-    if (nParked >= (uint32_t)BDPT_WALK_SHADE_MIN || flush) {
-      const uint32_t n = nParked < (uint32_t)kWave ? nParked : (uint32_t)kWave;
-      nParked -= n;
-      const bool act = (uint32_t)lane < n;
-      uint4 rec = make_uint4(0, 0, 0, 0);
-      if (act) rec = s_pool[nParked + (uint32_t)lane];
-      __syncthreads();  // the slots may be overwritten by ready rays below
-      const uint32_t p = rec.x & 0xffffffu;
-      const int path = (int)((rec.x >> 24) & 1u), k = (int)((rec.x >> 25) & 31u);
-      nEye += (uint32_t)__popcll(__ballot(act && path == PATH_EYE));
-      nLight += (uint32_t)__popcll(__ballot(act && path == PATH_LIGHT));
-      bool survive = false;
-      f3 L = mk(0);
-      if (act) {
-        const bool miss = EXT ? (rec.x & kParkedMiss) != 0u : (int)rec.y < 0;
-        const int prim = miss ? -1 : (int)rec.y;
-        const f3 o = ldPlane3(P, path, k, F_POS, p);
-        // what the eye ray that left vertex k found where it ended (EXT): added to the path's pixel below
-        f3 found = mk(0);
-        bool haveFound = false;
-        if (prim >= 0) {
-          const uint32_t seed = (path == PATH_EYE) ? P.seedE[p] : P.seedL[p];
-          const f3 thr = ldPlane3(P, path, k, F_COL, p);
-          Shading sd = shadeHit<false>(S, (uint32_t)prim, __uint_as_float(rec.z), __uint_as_float(rec.w), o);  // V points at WorldRayOrigin()
-          float pdf;
-          bool isSpec;
-          f3 w = sampleBRDF<GGX>(seed, sd.N, sd.N, sd.V, sd.diffuse, sd.specular, sd.roughness, fromLobe, L, pdf, isSpec);
-          Vtx v;
-          v.color = thr * w;
-          v.pos = sd.posW;
-          v.N = sd.N;
-          v.V = sd.V;
-          v.dif = sd.diffuse;
-          v.spec = sd.specular;
-          v.rough = sd.roughness;
-          v.isSpec = isSpec;
-          v.pdf = pdf;
-          storeVtx(P, path, k + 1, p, v);
-          survive = (k + 2 <= D);  // k + 1 < maxK
-          if (EXT && path == PATH_EYE && (F.p.flags & BDPT_PARAM_EMISSIVE_HITS) &&
-              (sd.emissive.x > 0.0f || sd.emissive.y > 0.0f || sd.emissive.z > 0.0f)) {
-            found = thr * sd.emissive;
-            haveFound = true;
-          }
-        } else {
-          if (EXT && path == PATH_EYE && (F.p.flags & BDPT_PARAM_ENV_ON_MISS)) {
-            const f3 dir = mk(__uint_as_float(rec.y), __uint_as_float(rec.z), __uint_as_float(rec.w));
-            const f3 env = F.envMap ? envLookup(F.envMap, F.envW, F.envH, dir) : ld3(F.envColor);
-            found = ldPlane3(P, path, k, F_COL, p) * env;
-            haveFound = true;
-          }
-          Vtx g = zeroVtx();
-          if (path == PATH_EYE && k == 1) {
-            g.pos = o;  // payload still holds initPayload's values (RayPathData.hlsli:69-86)
-          } else {
-            loadSurf(P, path, k, p, g);
-            g.V = ldPlane3(P, path, k, F_V, p);
-            if (path == PATH_LIGHT && k == 0) g.pdf = 0.0f;  // initPayload: pdfForward = 0
-          }
-          g.color = mk(0);
-          storeVtx(P, path, k + 1, p, g);
-          if (path == PATH_EYE) {
-            P.eyeLast[p] = (uint8_t)(k + 1);
-          } else {
-            P.lightLast[p] = (uint8_t)(k + 1);
-            P.lightReal[p] = (uint8_t)k;
-          }
-        }
-        if (EXT && haveFound) {  // path-tracing strategy of k + 1 edges: uniform 1/edges, clamped, no saturate (as NEE terms)
-          f3 term = clampVec(found / (float)(k + 1), F.p.clampUpper);
-          if (isnan3(term)) term = mk(0);
-          float4* out4 = reinterpret_cast<float4*>(F.out);
-          const size_t pix = P.pix[p];
-          float4 acc = out4[pix];
-          acc.x = acc.x + term.x;
-          acc.y = acc.y + term.y;
-          acc.z = acc.z + term.z;
-          acc.w = acc.w + 1.0f;
-          out4[pix] = acc;
-        }
-      }
-      // survivors -> ready rays (origin = the stored vertex k+1, re-read at pick-up)
-      const unsigned long long sm = __ballot(survive);
-      if (survive) {
-        const uint32_t slot = kPoolEntries - 1u - nReady - (uint32_t)__popcll(sm & laneBelow);
-        s_pool[slot] = make_uint4(packPath(p, path, k + 1), __float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z));
-      }
-      nReady += (uint32_t)__popcll(sm);
-      // this wave's later loads of the vertices it just stored must see them (same CU: ordering is enough)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __syncthreads();
-    }
-    // ---- 2. empty lanes take ready rays, then new sub-paths -------------------------------------------
-    const int empty = 64 - __popcll(travMask);
-    if ((empty >= BDPT_WALK_REFILL || travMask == 0ull) && (nReady > 0 || !exhausted)) {
-      const unsigned long long emptyMask = ~travMask;
-      const uint32_t rank = (uint32_t)__popcll(emptyMask & laneBelow);
-      const uint32_t fromReady = ((uint32_t)empty < nReady) ? (uint32_t)empty : nReady;
-      bool got = false;
-      uint32_t nid = 0;
-      f3 dir = mk(0);
-      if (!trav && rank < fromReady) {
-        const uint4 r = s_pool[kPoolEntries - nReady + rank];
-        nid = r.x;
-        dir = mk(__uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
-        got = true;
-      }
-      __syncthreads();  // the pool slots just read may be reused by parked records
-      nReady -= fromReady;
-      uint32_t want = (uint32_t)empty - fromReady;  // lanes still empty: new sub-paths (only reached with nReady == 0)
-      uint32_t taken = fromReady;
-      while (want > 0 && !exhausted) {
-        while (chunkPos >= chunkEnd && !exhausted) {  // wave-uniform loop: take a new chunk
-          const uint32_t nq = P.qcount[(vq % kNumSubQueues) * kCursorStride];
-          uint32_t base = nq;
-          if (__hip_atomic_load(&head[vq * kCursorStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nq) {
-            // A sub-path keeps its lane for up to D rays, so the list is handed out in small pieces (BDPT_WALK_CHUNK):
-            // with 256 per fetch the last pieces kept single waves busy long after the rest of the grid had drained.
-            uint32_t share = (nq / wavesPerList + 15u) & ~15u;
-            chunk = share < 16u ? 16u : (share > (uint32_t)BDPT_WALK_CHUNK ? (uint32_t)BDPT_WALK_CHUNK : share);
-            if (lane == 0) base = atomicAdd(&head[vq * kCursorStride], chunk);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-          }
-          if (base < nq) {
-            chunkPos = base;
-            chunkEnd = (base + chunk < nq) ? base + chunk : nq;
-            tried = 0;
-          } else {
-            vq = (vq + 1 == 2u * kNumSubQueues) ? firstV : vq + 1;
-            if (++tried >= numV) exhausted = true;
-          }
-        }
-        if (exhausted) break;
-        const uint32_t avail = chunkEnd - chunkPos;
-        const uint32_t take = (want < avail) ? want : avail;
-        if (!trav && !got && rank >= taken && rank < taken + take) {
-          const uint32_t p = P.queue[0][(vq % kNumSubQueues) * P.pathSubCap + chunkPos + (rank - taken)];
-          const int path = (int)(vq / kNumSubQueues);
-          const float* rd = P.rayDir + (size_t)(path * 3) * P.Np + p;
-          nid = packPath(p, path, (path == PATH_EYE) ? 1 : 0);
-          dir = mk(rd[0], rd[P.Np], rd[2 * (size_t)P.Np]);
-          got = true;
-        }
-        chunkPos += take;
-        taken += take;
-        want -= take;
-      }
-      if (got) {
-        id = nid;
-        travInit(T, ldPlane3(P, (int)((nid >> 24) & 1u), (int)(nid >> 25), F_POS, nid & 0xffffffu), dir, F.p.minT, 1.0e38f);
-        trav = true;
-      }
-      travMask = __ballot(trav);
-    }
-    if (travMask == 0ull) {
-      if (nParked == 0 && nReady == 0 && exhausted) break;
-      continue;  // parked records are flushed (or ready rays picked up) at the top
-    }
-    // ---- 3. traversal for the lanes that hold a ray
-    bool finished = false;
-#if BDPT_WALK_LEAF_WAIT > 0
-    // node visits in short bursts; a lane that reaches a leaf (or runs out of stack) waits, and the leaves are intersected
-    // once half of the lanes that hold a ray are waiting or no lane can take a node visit (device_trace.hpp, trace_shadow_kernel)
-    if (trav) {
-#pragma unroll 1
-      for (int kk = 0; kk < BDPT_WALK_NODE_BURST && T.cur >= 0; kk++) {
-        if (COUNT) nNodes++;
-        nodeStep<BDPT_WALK_ORDER, kWalkStackLds>(S, T, stk);
-      }
-    }
-    {
-      const unsigned long long waitMask = __ballot(trav && T.cur < 0), nodeMask = __ballot(trav && T.cur >= 0);
-      const int waitNeed = (__popcll(waitMask | nodeMask) * BDPT_LEAF_WAIT_FRAC8 + 7) >> 3;
-      if ((int)__popcll(waitMask) >= waitNeed || nodeMask == 0ull) {
-        if (trav && T.cur < 0) {
-          finished = (T.cur == kDone);
-          if (!finished) {
-            finished = leafStep<0, COUNT>(S, T, nTris, nAlpha);
-            if (!finished) {
-              T.cur = travPop<kWalkStackLds>(S, T, stk);
-              finished = (T.cur == kDone);
-            }
-          }
-        }
-      }
-    }
-#else
-    if (trav) {
-      while (T.cur >= 0) {
-        if (COUNT) nNodes++;
-        nodeStep<BDPT_WALK_ORDER, kWalkStackLds>(S, T, stk);
-      }
-      finished = (T.cur == kDone);
-      if (!finished) {
-        finished = leafStep<0, COUNT>(S, T, nTris, nAlpha);
-        if (!finished) {
-          T.cur = travPop<kWalkStackLds>(S, T, stk);
-          finished = (T.cur == kDone);
-        }
-      }
-    }
-#endif
-    const unsigned long long finMask = __ballot(finished);
-    if (finMask) {
-      if (finished) {
-        const bool miss = T.best.prim < 0;
-        s_pool[nParked + (uint32_t)__popcll(finMask & laneBelow)] =
-            (EXT && miss) ? make_uint4(id | kParkedMiss, __float_as_uint(T.d.x), __float_as_uint(T.d.y), __float_as_uint(T.d.z))
-                          : make_uint4(id, (uint32_t)T.best.prim, __float_as_uint(T.best.u), __float_as_uint(T.best.v));
-        trav = false;
-      }
-      nParked += (uint32_t)__popcll(finMask);
-      __syncthreads();
-    }
-  }
-  if (lane == 0) {
-    if (nEye) atomicAdd(&F.counters->v[blockIdx.x % kCounterShards][C_RAYS_EYE], (unsigned long long)nEye);
-    if (nLight) atomicAdd(&F.counters->v[blockIdx.x % kCounterShards][C_RAYS_LIGHT], (unsigned long long)nLight);
-  }
-  if (COUNT) {
-    waveAddCount(F.counters, C_NODE_CLOSEST, nNodes);
-    waveAddCount(F.counters, C_TRI_CLOSEST, nTris);
-    waveAddCount(F.counters, C_ALPHA_CLOSEST, nAlpha);
-  }
+  constexpr bool MASKED = false;
+  const MaskDev M{};
+#include "walk_body.inc"
+}
+template <bool GGX, bool COUNT, bool EXT>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK_WAVES_PER_EU, 8))) void walk_masked_kernel(SceneDev S, FrameDev F, PathBuf P, uint32_t* __restrict__ head, MaskDev M) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  __shared__ int s_stack[kWalkStackLds * kWave];
+  __shared__ uint4 s_pool[kPoolEntries];
+  constexpr bool MASKED = true;
+#include "walk_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1178,9 +958,12 @@ BD void loadSlotChunk(const PathBuf& P, uint32_t p, int slot0, int n, SlotChunk&
 // with only light k adds +0 for every NEE term of another light; the plane skips those adds, which changes no bit: its sum
 // starts at +0 and only ever adds values >= +0 (clampVec), and x + 0 == x for every such x.  The emission plane (the frame
 // with every intensity zero) adds its +0 terms for real, because it starts from `out`'s start, -0 included.
-template <bool GROUPS>
-BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, float* la, uint32_t p, uint32_t& nSplat) {
+// MASKED (bdpt_execute_masked): a pixel the mask leaves out (`active` false) only lands its splats — its NEE and
+// connection slots were never generated this frame — and its `out` is neither summed nor written.
+template <bool GROUPS, bool MASKED = false>
+BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, float* la, uint32_t p, uint32_t& nSplat, bool active = true) {
   bool pending = false;
+  const bool sums = !MASKED || active;
   const size_t pix = P.pix[p];
   float4* out4 = reinterpret_cast<float4*>(F.out);
   float4 acc = out4[pix];
@@ -1193,7 +976,7 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, floa
     own = (int)Gr.lightIdx[p];
   }
   SlotChunk c;
-  if (!(F.p.flags & BDPT_PARAM_NO_NEE)) {
+  if (sums && !(F.p.flags & BDPT_PARAM_NO_NEE)) {
     uint32_t seed = GROUPS ? P.seedL[p] : 0u;
     for (int t0 = 0; t0 < D; t0 += kGatherChunk) {
       const int n = (D - t0 < kGatherChunk) ? D - t0 : kGatherChunk;
@@ -1219,7 +1002,7 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, floa
         }
     }
   }
-  if (!(F.p.flags & BDPT_PARAM_NO_CONNECT)) {
+  if (sums && !(F.p.flags & BDPT_PARAM_NO_CONNECT)) {
     const int nPairs = (int)numConnectPairs((uint32_t)D);
     bool sat = false;
     float ox = 0.0f, oy = 0.0f, oz = 0.0f;  // the own light plane takes the saturating sequence of `out`
@@ -1260,7 +1043,7 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, floa
     }
     pending = (!sat && nPairs > 0);  // settled by the lazy rounds below
   }
-  out4[pix] = acc;
+  if (sums) out4[pix] = acc;
   if (GROUPS) {
     float4* g4 = reinterpret_cast<float4*>(Gr.planes) + pix;
     for (int k = 0; k < K; k++) g4[(size_t)k * Gr.framePix] = make_float4(la[(3 * k) * kWave], la[(3 * k + 1) * kWave], la[(3 * k + 2) * kWave], acc.w);
@@ -1319,6 +1102,24 @@ __global__ __launch_bounds__(kWave) void gather_groups_kernel(FrameDev F, PathBu
   if (act) {
     p = P.queue[0][i];
     pending = gatherLane<true>(F, P, Gr, s_acc + threadIdx.x, p, nSplat);
+    if (pending) P.lazyCursor[p] = 0;
+  }
+  waveAddCount(F.counters, C_SPLATS, nSplat);
+  wavePush(pending, p, lazyList, lazyCount, P.pathSubCap);
+}
+
+// every valid pixel (its splats land whatever the mask says); the sums and the `out` write of active pixels only
+__global__ __launch_bounds__(kWave) void gather_masked_kernel(FrameDev F, PathBuf P, MaskDev M, uint32_t* __restrict__ lazyList,
+                                                              uint32_t* __restrict__ lazyCount) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  bool act = false;
+  uint32_t i = 0;
+  if (!queueChunk(P.qcount, P.pathSubCap, act, i)) return;
+  uint32_t nSplat = 0, p = 0;
+  bool pending = false;
+  if (act) {
+    p = P.queue[0][i];
+    pending = gatherLane<false, true>(F, P, GroupDev{}, nullptr, p, nSplat, M.mask[P.pix[p]] != 0);
     if (pending) P.lazyCursor[p] = 0;
   }
   waveAddCount(F.counters, C_SPLATS, nSplat);
@@ -1488,6 +1289,24 @@ __global__ void resolve_kernel(const unsigned long long* __restrict__ splat, boo
     }
     const ulonglong2 a = reinterpret_cast<const ulonglong2*>(splat + sidx * 4)[0];
     const ulonglong2 b = reinterpret_cast<const ulonglong2*>(splat + sidx * 4)[1];
+    if (b.y == 0ull) continue;
+    float4 o = out[pix];
+    o.x = saturate(o.x + (float)a.x * 2.3283064365386963e-10f);
+    o.y = saturate(o.y + (float)a.y * 2.3283064365386963e-10f);
+    o.z = saturate(o.z + (float)b.x * 2.3283064365386963e-10f);
+    o.w = saturate(o.w + (float)b.y);
+    out[pix] = o;
+  }
+}
+
+// resolve_kernel of a masked frame (whole frame, SplatLayout = frame order): active pixels only
+__global__ void resolve_masked_kernel(const unsigned long long* __restrict__ splat, float4* __restrict__ out, const uint8_t* __restrict__ mask,
+                                      const uint32_t* __restrict__ pixOf, uint32_t Np) {
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < Np; p += (size_t)gridDim.x * blockDim.x) {
+    const size_t pix = pixOf[p];
+    if (mask[pix] == 0) continue;
+    const ulonglong2 a = reinterpret_cast<const ulonglong2*>(splat + pix * 4)[0];
+    const ulonglong2 b = reinterpret_cast<const ulonglong2*>(splat + pix * 4)[1];
     if (b.y == 0ull) continue;
     float4 o = out[pix];
     o.x = saturate(o.x + (float)a.x * 2.3283064365386963e-10f);
@@ -1841,6 +1660,46 @@ void launchResolveGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr
   if (!P.Np) return;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)P.Np + 255) / 256, 2048);
   hipLaunchKernelGGL(resolve_groups_kernel, dim3(grid), dim3(256), 0, st, F, P.pix, P.Np, Gr);
+}
+void launchInitPathsMasked(const SceneDev& S, const FrameDev& F, const PathBuf& P, const MaskDev& M, hipStream_t st) {
+  if (!P.Np) return;
+  if (F.p.matIndex == 0)
+    launchWave(init_paths_masked_kernel<true>, (uint32_t)(blocksFor(P.Np)), st, S, F, P, M);
+  else
+    launchWave(init_paths_masked_kernel<false>, (uint32_t)(blocksFor(P.Np)), st, S, F, P, M);
+}
+void launchWalkMasked(const SceneDev& S, const FrameDev& F, const PathBuf& P, const MaskDev& M, LaunchGrids& G, int numCUs, hipStream_t st) {
+  if (!P.Np || F.p.maxDepth < 1) return;
+  const bool cnt = (F.p.flags & BDPT_PARAM_COUNTERS) != 0, ggx = F.p.matIndex == 0;
+  const bool ext = (F.p.flags & (BDPT_PARAM_ENV_ON_MISS | BDPT_PARAM_EMISSIVE_HITS)) != 0;
+  uint32_t& g = G.walkMasked[(ext ? 4 : 0) + (ggx ? 2 : 0) + (cnt ? 1 : 0)];
+  const uint32_t need = blocksFor((uint64_t)2 * P.Np);
+#define BDPT_LAUNCH_WALK(GGX, CNT, EXT)                                                                        \
+  {                                                                                                           \
+    if (!g) g = persistentGrid(walk_masked_kernel<GGX, CNT, EXT>, numCUs);                                     \
+    launchWave((walk_masked_kernel<GGX, CNT, EXT>), (uint32_t)(std::min(g, need)), st, S, F, P, P.qhead, M);   \
+  }
+  if (ext) {
+    if (ggx && cnt) BDPT_LAUNCH_WALK(true, true, true)
+    else if (ggx) BDPT_LAUNCH_WALK(true, false, true)
+    else if (cnt) BDPT_LAUNCH_WALK(false, true, true)
+    else BDPT_LAUNCH_WALK(false, false, true)
+  } else {
+    if (ggx && cnt) BDPT_LAUNCH_WALK(true, true, false)
+    else if (ggx) BDPT_LAUNCH_WALK(true, false, false)
+    else if (cnt) BDPT_LAUNCH_WALK(false, true, false)
+    else BDPT_LAUNCH_WALK(false, false, false)
+  }
+#undef BDPT_LAUNCH_WALK
+}
+void launchGatherMasked(const FrameDev& F, const PathBuf& P, const MaskDev& M, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st) {
+  if (!P.Np) return;
+  launchWave(gather_masked_kernel, (uint32_t)(queueGrid(P)), st, F, P, M, lazyList, lazyCount);
+}
+void launchResolveMasked(const FrameDev& F, const PathBuf& P, const MaskDev& M, hipStream_t st) {
+  if (!P.Np) return;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)P.Np + 255) / 256, 2048);
+  hipLaunchKernelGGL(resolve_masked_kernel, dim3(grid), dim3(256), 0, st, F.splat, reinterpret_cast<float4*>(F.out), M.mask, P.pix, P.Np);
 }
 void launchAccumulate(float* last, float* cur, uint32_t accumCount, uint32_t maxAccum, uint64_t numTexels, hipStream_t st) {
   if (!numTexels) return;

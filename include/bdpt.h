@@ -552,6 +552,67 @@ int bdpt_execute(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, fl
  * exchange of tiled rendering has no group planes. */
 int bdpt_execute_light_groups(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, float* out, float* groups, void* stream);
 
+/* Masked frame (region of interest, foveation, adaptive sampling): bdpt_execute for the pixels `mask` selects.  `mask` is
+ * device memory of W x H bytes in frame order; a non-zero byte makes the pixel ACTIVE.  Bit for bit:
+ *   - an active pixel (any G-buffer state) gets exactly what bdpt_execute writes for the same params, G-buffer and scene;
+ *   - an inactive pixel's `out` is not written: its previous bits survive.
+ * Why this holds: every term of pixel p depends only on p's own eye and light subpaths, seeded by initRand(pix,
+ * frameCount) and, for NEE, by seedL; the one exception, light-tracing splats, land on other pixels.  So every valid
+ * pixel still traces its LIGHT subpath and its splats land, and an inactive pixel drops its eye walk, its NEE, connection
+ * and lazy-round rays, its gather and its `out` writes (the emissive / background write included, and the resolve).
+ * MIS: with BDPT_PARAM_MIS_POWER or _LINEAR the splat weight of p's light subpath reads p's EYE prefix products, so then
+ * inactive valid pixels still walk their eye subpaths (and run the MIS prefix pass) and skip only NEE, connections,
+ * gather and lazy rounds; with ENV_ON_MISS / EMISSIVE_HITS also on, their eye walk adds nothing to `out`.
+ * Counters: raysLightExtend, raysSplat, splatsLanded and hintedSplat are bdpt_execute's; raysEyeExtend (MIS off),
+ * raysNee, raysConnect, raysConnectLazy and hintedNee count active pixels only, pixelsValid active valid pixels.  With
+ * MIS off and an all-zero mask the first four are 0; with MIS on raysEyeExtend is bdpt_execute's.
+ * Ordering, stream use, in == NULL and graph capture are those of bdpt_execute; the call allocates nothing beyond what
+ * bdpt_execute does (in == NULL: bdpt_prepare(BDPT_PREPARE_PRIMARY) before a capture).
+ * Errors: a NULL ctx or mask BDPT_E_INVALID; BDPT_PARAM_DEFER_RESOLVE or BDPT_PARAM_DEFER_TAIL BDPT_E_INVALID; no scene
+ * or size BDPT_E_STATE; a context that renders a tile or stripes BDPT_E_INVALID (the eye list is whole-frame). */
+int bdpt_execute_masked(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, const uint8_t* mask, float* out, void* stream);
+
+/* Adaptive sampling: a per-pixel running mean and variance, and the mask of the next masked frame.  All buffers are
+ * caller-owned device memory over the whole frame, in frame order. */
+typedef struct bdpt_adaptive_state {
+  float* mean;      /* RGBA32F running mean (what bdpt_accumulate's lastFrame holds); 16-byte aligned */
+  float* m2;        /* float32 per pixel: summed squared luminance deviations */
+  uint32_t* count;  /* frames folded into each pixel */
+  uint8_t* mask;    /* 1 = render next frame: the mask bdpt_execute_masked reads */
+  uint32_t* active; /* one word: pixels with mask 1 after the last reset / update */
+} bdpt_adaptive_state;
+typedef struct bdpt_adaptive_params {
+  float threshold;     /* relative standard error of the mean at which a pixel has converged */
+  float epsilon;       /* added to the mean luminance in the denominator */
+  uint32_t minSamples; /* >= 2 */
+  uint32_t maxSamples; /* >= minSamples; a pixel at maxSamples has converged */
+  uint32_t blockSize;  /* 1, 2, 4, 8 or 16: pixels are (de)activated per aligned blockSize x blockSize block */
+} bdpt_adaptive_params;
+/* mean = m2 = count = 0, mask = 1 everywhere, *active = W * H. */
+int bdpt_adaptive_reset(bdpt_ctx* ctx, const bdpt_adaptive_state* s, void* stream);
+/* Folds `frame` (RGBA32F, the masked frame's `out`) into the state, decides the next mask and writes the mean back to
+ * `frame`.  fp32 throughout, in exactly this order (no contraction, correctly rounded / and sqrtf):
+ *   lum(v) = (0.2126f*v.x + 0.7152f*v.y) + 0.0722f*v.z
+ *   for every pixel with mask != 0 and count < maxSamples, with n = count, c = frame, a = (float)n, b = (float)(n+1):
+ *     mean' = (a*mean + c)/b                      per channel, all four (bdpt_accumulate's expression: a pixel that is
+ *                                                 always active follows bdpt_accumulate bit for bit)
+ *     m2    = m2 + (lum(c) - lum(mean)) * (lum(c) - lum(mean'))     (mean the old mean)
+ *     mean  = mean';  count = n + 1
+ *   converged = count >= maxSamples, or count >= minSamples and
+ *               sqrtf(m2 / (nf*(nf - 1.0f))) / (lum(mean) + epsilon) <= threshold,  nf = (float)count
+ *               (for every pixel, rendered this frame or not; a NaN comparison is "not converged")
+ *   mask   = 1 for every pixel of an aligned blockSize^2 block that holds any unconverged pixel, else 0 (partial blocks at
+ *            the right and bottom edges count their real pixels only)
+ *   active = the number of pixels with mask 1
+ *   frame  = mean for every pixel, so that the output always shows the accumulated image; an inactive pixel, which the
+ *            next masked frame leaves untouched, keeps showing its mean.
+ * A block that turns inactive never turns active again (its pixels no longer change), so `active` never grows between
+ * resets.  The call neither allocates nor synchronises (read `active` by an async copy) and can be captured; it is ordered
+ * behind the context's previous call.  Errors: a NULL ctx, params, state buffer or frame, a blockSize not in
+ * {1, 2, 4, 8, 16}, minSamples < 2 or maxSamples < minSamples BDPT_E_INVALID; no scene or size BDPT_E_STATE; a tile or
+ * stripes context BDPT_E_INVALID. */
+int bdpt_adaptive_update(bdpt_ctx* ctx, const bdpt_adaptive_params* a, const bdpt_adaptive_state* s, float* frame, void* stream);
+
 /* Second phase of a bdpt_execute issued with BDPT_PARAM_DEFER_TAIL (same params, channels and out). */
 int bdpt_execute_tail(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream);
 
