@@ -1218,9 +1218,8 @@ int frameSetup(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float*
 
 // Connection pairs whose contribution is exactly zero, for the pixels no visible connection has saturated
 // yet (DESIGN.md "Lazy connection rounds"), then the splat fold-in unless the caller defers it.
-// Grp (bdpt_execute_light_groups): the group variants of the lazy check and the resolve.  Msk (bdpt_execute_masked): the
-// masked resolve (the lazy rounds only ever see the active pixels gather handed them).
-int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st, const GroupDev* Grp = nullptr, const MaskDev* Msk = nullptr) {
+// V: the frame's variant (FrameVariant), for the lazy check and the resolve.
+int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st, const FrameVariant& V) {
   const PathBuf& P = c->P;
   const bdpt_params* p = &F.p;
   const int D = (int)p->maxDepth;
@@ -1243,23 +1242,14 @@ int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st, const GroupDe
       stageMark(c, st, "lazy_gen");
       launchTraceShadow(c->S, F, P, RAY_PAIRS, c->grids, c->numCUs, st);
       stageMark(c, st, "lazy_trace");
-      if (Grp)
-        launchLazyCheckGroups(F, P, *Grp, list, P.lazyCount + (size_t)r * kCursorBlock, batch, next,
-                              P.lazyCount + (size_t)(r + 1) * kCursorBlock, st);
-      else
-        launchLazyCheck(F, P, list, P.lazyCount + (size_t)r * kCursorBlock, batch, next, P.lazyCount + (size_t)(r + 1) * kCursorBlock, st);
+      launchLazyCheck(F, P, V, list, P.lazyCount + (size_t)r * kCursorBlock, batch, next, P.lazyCount + (size_t)(r + 1) * kCursorBlock,
+                      st);
     }
     stageMark(c, st, "lazy_check");
   }
-  if (Grp) {
-    launchResolveGroups(F, P, *Grp, st);
-    stageMark(c, st, "resolve_groups");
-  } else if (Msk) {
-    launchResolveMasked(F, P, *Msk, st);
-    stageMark(c, st, "resolve_masked");
-  } else if (!(p->flags & BDPT_PARAM_DEFER_RESOLVE)) {
-    launchResolve(c->splat, false, 0, c->sl, F.out, c->W, c->P.pix, c->P.Np, st);
-    stageMark(c, st, "resolve");
+  if (!(p->flags & BDPT_PARAM_DEFER_RESOLVE)) {  // (refused for group and masked frames)
+    launchFrameResolve(F, P, V, st);
+    stageMark(c, st, V.kind == FrameKind::Groups ? "resolve_groups" : V.kind == FrameKind::Masked ? "resolve_masked" : "resolve");
   }
   HIPCHK(c, hipGetLastError());
   c->lastStream = st;
@@ -1268,29 +1258,19 @@ int connectionTail(bdpt_ctx* c, const FrameDev& F, hipStream_t st, const GroupDe
 }  // namespace
 
 namespace {
-// bdpt_execute, and bdpt_execute_light_groups with Grp set: the same stages and the same rays; the group path swaps in
-// the group variants of init_paths, gather, the lazy check and the resolve, and clears its splat-value planes.
-// bdpt_execute_masked with Msk set: the masked init_paths, walk, gather and resolve, and the generators of eye-side
-// terms (NEE, connections) over the eye list (`PE`: the PathBuf with the eye list as its pixel list).
-int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream, const GroupDev* Grp,
-                 const MaskDev* Msk = nullptr) {
+// bdpt_execute, bdpt_execute_light_groups and bdpt_execute_masked: the same stages and the same rays.  The per-pixel
+// stages take the variant V; a group frame also clears its splat-value planes, and a masked frame runs the generators of
+// eye-side terms (NEE, connections) over its eye list (`PE`: the PathBuf with the eye list as its pixel list).
+int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream, const FrameVariant& V) {
   FrameDev F;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = frameSetup(c, p, in, out, st, F)) return rc;
   const PathBuf& P = c->P;
-  PathBuf eyeP = P;
-  MaskDev M{};
-  if (Msk) {
-    M = *Msk;
-    M.eye = P.queue[2];
-    M.eyeCount = P.lazyCount + kEyeCountBlock * kCursorBlock;
-    const bool misOn = (p->flags & (BDPT_PARAM_MIS_POWER | BDPT_PARAM_MIS_LINEAR)) != 0;
-    M.walkEye = misOn ? P.queue[0] : M.eye;  // under MIS every valid pixel's eye prefix products are read by its splats
-    M.walkEyeCount = misOn ? P.qcount : M.eyeCount;
-    eyeP.queue[0] = M.eye;
-    eyeP.qcount = M.eyeCount;
+  PathBuf PE = P;
+  if (V.kind == FrameKind::Masked) {
+    PE.queue[0] = V.mask.eye;
+    PE.qcount = V.mask.eyeCount;
   }
-  const PathBuf& PE = Msk ? eyeP : P;
   if (!in) {
     // Built-in primary stage: pinhole camera, this frame's jitter and counter, the default constant
     // environment (SharedUtils/ResourceManager.cpp:77-87) — what LightProbeGBufferPass does with its defaults.
@@ -1310,24 +1290,17 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
   if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], st));
   HIPCHK(c, hipMemsetAsync(P.qcount, 0, (size_t)kCursorWords * sizeof(uint32_t), st));
   HIPCHK(c, hipMemsetAsync(c->splat, 0, (size_t)c->sl.owners * c->sl.chunkRows * c->W * 4 * sizeof(unsigned long long), st));
-  if (Grp) HIPCHK(c, hipMemsetAsync(Grp->splat, 0, (size_t)Grp->numLights * Grp->framePix * 4 * sizeof(unsigned long long), st));
+  if (V.kind == FrameKind::Groups)
+    HIPCHK(c, hipMemsetAsync(V.groups.splat, 0, (size_t)V.groups.numLights * V.groups.framePix * 4 * sizeof(unsigned long long), st));
   if (!(p->flags & BDPT_PARAM_KEEP_COUNTERS)) HIPCHK(c, hipMemsetAsync(c->counters, 0, sizeof(DevCounters), st));
   stageMark(c, st, "clear");
 
-  if (Grp)
-    launchInitPathsGroups(c->S, F, P, *Grp, st);
-  else if (Msk)
-    launchInitPathsMasked(c->S, F, P, M, st);
-  else
-    launchInitPaths(c->S, F, P, st);
+  launchInitPaths(c->S, F, P, V, st);
   stageMark(c, st, "init_paths");
 
   // Both walks (eye vertices 2..D, BDPTMain.rt.hlsl:106-112; light vertices 1..D, :138-145) in one persistent
   // launch: traversal and hit/miss shading alternate inside the kernel, lanes re-arm themselves per bounce.
-  if (Msk)
-    launchWalkMasked(c->S, F, P, M, c->grids, c->numCUs, st);
-  else
-    launchWalk(c->S, F, P, c->grids, c->numCUs, st);
+  launchWalk(c->S, F, P, V, c->grids, c->numCUs, st);
   stageMark(c, st, "walk");
 
   // NEE terms (caller's stream) and splat terms (second stream) are generated side by side and traced at once (ray
@@ -1372,12 +1345,7 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
   }
   launchTraceShadow(c->S, F, P, RAY_PAIRS, c->grids, c->numCUs, st);
   stageMark(c, st, "trace_pairs");
-  if (Grp)
-    launchGatherGroups(F, P, *Grp, P.queue[1], P.lazyCount, st);
-  else if (Msk)
-    launchGatherMasked(F, P, M, P.queue[1], P.lazyCount, st);
-  else
-    launchGather(F, P, P.queue[1], P.lazyCount, st);
+  launchGather(F, P, V, P.queue[1], P.lazyCount, st);
   stageMark(c, st, "gather");
   // Everything that touches the splat buffer is enqueued by now: a tiled host may start its exchange here
   // and run the connection tail beside it (BDPT_PARAM_DEFER_TAIL + bdpt_execute_tail).
@@ -1386,7 +1354,7 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
     c->lastStream = st;
     return BDPT_OK;
   }
-  return connectionTail(c, F, st, Grp, Msk);
+  return connectionTail(c, F, st, V);
 }
 
 // the group path's buffers; not while the stream is being captured
@@ -1408,10 +1376,28 @@ int allocLightGroups(bdpt_ctx* c, hipStream_t st) {
   c->groupLightIdx = reinterpret_cast<uint8_t*>(li);
   return BDPT_OK;
 }
+
+// What bdpt_execute_light_groups, bdpt_execute_masked and the adaptive calls refuse alike, as "<what>: ...": the deferred
+// stages (when params are given), a context without scene or size, and one that does not render the whole frame.
+int wholeFrameCheck(bdpt_ctx* c, const bdpt_params* p, const std::string& what) {
+  if (p && (p->flags & (BDPT_PARAM_DEFER_RESOLVE | BDPT_PARAM_DEFER_TAIL))) {
+    fail(c, what + ": BDPT_PARAM_DEFER_RESOLVE and BDPT_PARAM_DEFER_TAIL are not supported");
+    return BDPT_E_INVALID;
+  }
+  if (!c->haveScene || !c->haveSize) {
+    fail(c, what + ": scene and size must be set first");
+    return BDPT_E_STATE;
+  }
+  if (c->stripes.stripeRows != 0 || c->tileRows != c->H) {
+    fail(c, what + ": the context must render the whole frame (no tile, no stripes)");
+    return BDPT_E_INVALID;
+  }
+  return BDPT_OK;
+}
 }  // namespace
 
 int bdpt_execute(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream) {
-  return executeFrame(c, p, in, out, stream, nullptr);
+  return executeFrame(c, p, in, out, stream, FrameVariant{});
 }
 
 int bdpt_execute_light_groups(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, float* groups, void* stream) {
@@ -1420,28 +1406,18 @@ int bdpt_execute_light_groups(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuf
     fail(c, "light groups: groups is NULL");
     return BDPT_E_INVALID;
   }
-  if (p && (p->flags & (BDPT_PARAM_DEFER_RESOLVE | BDPT_PARAM_DEFER_TAIL))) {
-    fail(c, "light groups: BDPT_PARAM_DEFER_RESOLVE and BDPT_PARAM_DEFER_TAIL are not supported");
-    return BDPT_E_INVALID;
-  }
-  if (!c->haveScene || !c->haveSize) {
-    fail(c, "light groups: scene and size must be set first");
-    return BDPT_E_STATE;
-  }
-  if (c->stripes.stripeRows != 0 || c->tileRows != c->H) {
-    fail(c, "light groups: the context must render the whole frame (no tile, no stripes)");
-    return BDPT_E_INVALID;
-  }
+  if (int rc = wholeFrameCheck(c, p, "light groups")) return rc;
   ENTER(c);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = allocLightGroups(c, st)) return rc;
-  GroupDev G{};
-  G.planes = groups;
-  G.splat = c->groupSplat;
-  G.lightIdx = c->groupLightIdx;
-  G.numLights = c->S.numLights;
-  G.framePix = (uint64_t)c->W * c->H;
-  return executeFrame(c, p, in, out, stream, &G);
+  FrameVariant V;
+  V.kind = FrameKind::Groups;
+  V.groups.planes = groups;
+  V.groups.splat = c->groupSplat;
+  V.groups.lightIdx = c->groupLightIdx;
+  V.groups.numLights = c->S.numLights;
+  V.groups.framePix = (uint64_t)c->W * c->H;
+  return executeFrame(c, p, in, out, stream, V);
 }
 
 int bdpt_execute_masked(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, const uint8_t* mask, float* out, void* stream) {
@@ -1450,21 +1426,19 @@ int bdpt_execute_masked(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* i
     fail(c, "execute_masked: mask is NULL");
     return BDPT_E_INVALID;
   }
-  if (p && (p->flags & (BDPT_PARAM_DEFER_RESOLVE | BDPT_PARAM_DEFER_TAIL))) {
-    fail(c, "execute_masked: BDPT_PARAM_DEFER_RESOLVE and BDPT_PARAM_DEFER_TAIL are not supported");
-    return BDPT_E_INVALID;
-  }
-  if (!c->haveScene || !c->haveSize) {
-    fail(c, "execute_masked: scene and size must be set first");
-    return BDPT_E_STATE;
-  }
-  if (c->stripes.stripeRows != 0 || c->tileRows != c->H) {
-    fail(c, "execute_masked: the context must render the whole frame (no tile, no stripes)");
-    return BDPT_E_INVALID;
-  }
-  MaskDev M{};
-  M.mask = mask;  // (the eye list and what the walk reads: executeFrame)
-  return executeFrame(c, p, in, out, stream, nullptr, &M);
+  if (int rc = wholeFrameCheck(c, p, "execute_masked")) return rc;
+  // The eye list: the active valid pixels, which init_paths pushes (where it lives: kEyeCountBlock).  Under MIS the walk's
+  // eye lists stay the valid list: every valid pixel's eye prefix products are read by its splats.
+  const PathBuf& P = c->P;
+  const bool misOn = p && (p->flags & (BDPT_PARAM_MIS_POWER | BDPT_PARAM_MIS_LINEAR)) != 0;
+  FrameVariant V;
+  V.kind = FrameKind::Masked;
+  V.mask.mask = mask;
+  V.mask.eye = P.queue[2];
+  V.mask.eyeCount = P.lazyCount + kEyeCountBlock * kCursorBlock;
+  V.mask.walkEye = misOn ? P.queue[0] : V.mask.eye;
+  V.mask.walkEyeCount = misOn ? P.qcount : V.mask.eyeCount;
+  return executeFrame(c, p, in, out, stream, V);
 }
 
 namespace {
@@ -1474,14 +1448,7 @@ int adaptiveSetup(bdpt_ctx* c, const bdpt_adaptive_state* s, const char* what, A
     fail(c, std::string(what) + ": a state buffer is NULL");
     return BDPT_E_INVALID;
   }
-  if (!c->haveScene || !c->haveSize) {
-    fail(c, std::string(what) + ": scene and size must be set first");
-    return BDPT_E_STATE;
-  }
-  if (c->stripes.stripeRows != 0 || c->tileRows != c->H) {
-    fail(c, std::string(what) + ": the context must render the whole frame (no tile, no stripes)");
-    return BDPT_E_INVALID;
-  }
+  if (int rc = wholeFrameCheck(c, nullptr, what)) return rc;
   if (reinterpret_cast<uintptr_t>(s->mean) % 16 != 0) {
     fail(c, std::string(what) + ": mean must be 16-byte aligned (RGBA32F)");
     return BDPT_E_INVALID;
@@ -1549,7 +1516,7 @@ int bdpt_execute_tail(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in,
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = frameSetup(c, p, in, out, st, F)) return rc;
   stageMark(c, st, "tail_wait");  // stream time between the end of phase 1 and this call (the host's exchange set-up), not a kernel
-  return connectionTail(c, F, st);
+  return connectionTail(c, F, st, FrameVariant{});
 }
 
 // Allocate the optional buffers up front so that no later execute allocates (hipGraph capture, latency).

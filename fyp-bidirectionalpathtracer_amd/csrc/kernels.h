@@ -172,9 +172,9 @@ struct FrameDev {
 };
 
 // Light groups (bdpt_execute_light_groups): one RGBA32F plane per light plus one for emission, from the paths of the
-// plain frame.  Only the group variants of init_paths, gather and lazy_check and the group resolve take it, so the
-// argument layout of every other kernel stays as it is.  Whole-frame contexts only: planes and splat planes are indexed
-// by frame pixel (splat planes in SplatLayout order, which is frame order there).
+// plain frame.  The group instances of init_paths, gather and lazy_check and the group resolve take it (FrameVariant).
+// Whole-frame contexts only: planes and splat planes are indexed by frame pixel (splat planes in SplatLayout order,
+// which is frame order there).
 struct GroupDev {
   float* planes;               // (numLights + 1) planes of W*H float4: plane k < numLights = light k, plane numLights = emission
   unsigned long long* splat;   // numLights splat-value planes of W*H x 4 u64 (r, g, b, unused); counts stay in FrameDev::splat
@@ -184,16 +184,27 @@ struct GroupDev {
 };
 
 // Masked frames (bdpt_execute_masked): only the pixels a caller's mask selects trace eye paths, NEE and connection rays,
-// gather and write `out`; every valid pixel still traces its light subpath and its splats.  Only the masked variants of
-// init_paths, walk, gather and resolve take it, so the argument layout of every other kernel stays as it is; gen_nee,
-// gen_connect and the lazy rounds run unchanged on a PathBuf copy whose queue[0] / qcount name the eye list.
-// Whole-frame contexts only (the mask is indexed by frame pixel).
+// gather and write `out`; every valid pixel still traces its light subpath and its splats.  The masked instances of
+// init_paths, walk and gather and the masked resolve take it (FrameVariant); gen_nee, gen_connect and the lazy rounds
+// run unchanged on a PathBuf copy whose queue[0] / qcount name the eye list.  Whole-frame contexts only (the mask is
+// indexed by frame pixel).
 struct MaskDev {
   const uint8_t* mask;          // W*H bytes, frame order: non-zero = active
   uint32_t* eye;                // eye list: the active valid pixels, sharded as PathBuf::queue[0] (init_paths appends)
   uint32_t* eyeCount;           // its cursor block (kCursorBlock words, zero when init_paths starts)
   const uint32_t* walkEye;      // what the walk's eye lists read: `eye`, or under MIS the valid list (PathBuf::queue[0])
   const uint32_t* walkEyeCount; // and their lengths
+};
+
+// Which frame the per-pixel stages render: bdpt_execute, bdpt_execute_light_groups or bdpt_execute_masked.  Each kind is
+// a template argument of the init_paths, walk, gather and lazy_check kernels, which take what it needs (GroupDev,
+// MaskDev, or an empty struct for the plain frame) as their LAST argument, so the plain instances keep the offsets of
+// their other arguments.  A masked frame runs the plain lazy_check, a group frame the plain walk.
+enum class FrameKind { Plain, Groups, Masked };
+struct FrameVariant {
+  FrameKind kind = FrameKind::Plain;
+  GroupDev groups{};  // kind == Groups
+  MaskDev mask{};     // kind == Masked
 };
 
 struct GBufferDev {
@@ -231,16 +242,22 @@ void launchAlphaRecs(const SceneDev& S, const uint32_t* alphaTris, uint32_t n, f
 void launchHintFill(const SceneDev& S, const GBufferDev& G, hipStream_t st);
 // SceneDev::lightMap of every point / spot light of the scene (res texels per face edge), closest-hit rays from the light
 void launchLightMaps(const SceneDev& S, uint32_t* maps, uint32_t res, hipStream_t st);
-void launchInitPaths(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st);
+// The per-pixel stages of a frame take its variant.  Groups: init_paths also records each pixel's light and starts the
+// background pixels' planes, gather / lazy_check also keep the planes, and the resolve does out and every plane in one
+// pass (out's splat values are the sums of the per-light splat planes: FrameDev::splat then only holds the counts).
+// Masked: init_paths also builds the eye list and writes `out` for active pixels only, the walk's eye lists read
+// MaskDev::walkEye (and it adds ENV_ON_MISS / EMISSIVE_HITS terms to active pixels only), gather runs over every valid
+// pixel but sums and writes only active ones (every pixel's splats still land), and the resolve does active pixels.
+void launchInitPaths(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, hipStream_t st);
 // Persistent-grid sizes of one context's device, filled on first use (occupancy query per kernel variant).
 struct LaunchGrids {
-  uint32_t walk[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // [EXT][GGX][COUNT]
-  uint32_t walkMasked[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for walk_masked_kernel
+  uint32_t walk[16] = {};             // [MASKED][EXT][GGX][COUNT]
   uint32_t shadow[2] = {0, 0};        // [COUNT]
   uint32_t rays[3] = {0, 0, 0};       // [mode] (trace_rays.hip)
 };
 // both random walks of the frame: one persistent launch (trace + hit/miss shading in place)
-void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, LaunchGrids& G, int numCUs, hipStream_t st);
+void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,
+                hipStream_t st);
 void launchMisPrefix(const FrameDev& F, const PathBuf& P, hipStream_t st);
 void launchGenNee(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st);
 void launchGenSplat(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st);
@@ -252,32 +269,18 @@ void launchTraceShadow(const SceneDev& S, const FrameDev& F, const PathBuf& P, i
 // it zero.
 void launchTraceRays(const SceneDev& S, const float4* rays, uint32_t cap, const uint32_t* count, unsigned long long* cursor, int mode,
                      float4* hits, uint8_t* vis, LaunchGrids& G, int numCUs, hipStream_t st);
-void launchGather(const FrameDev& F, const PathBuf& P, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
+void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
-void launchLazyCheck(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch,
-                     uint32_t* nextList, uint32_t* nextCount, hipStream_t st);
+void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,
+                     int batch, uint32_t* nextList, uint32_t* nextCount, hipStream_t st);
 constexpr int kLazyBatchDiv = 8;    // a front round examines ceil(pairs / 8) candidates per pending pixel
 constexpr int kMaxLazyRounds = 8;   // cursor blocks reserved for lazy rounds  // rounds per frame; batch = ceil(pairs / rounds)
 // out[pix] = saturate(out[pix] + splat) for the tile's pixels.  tileLocal: `splat` holds the tile's accumulators in
 // tile-local order (a reduce-scattered chunk); otherwise SplatLayout order, starting at frame row splatRow0 (owners == 1).
 void launchResolve(const unsigned long long* splat, bool tileLocal, uint32_t splatRow0, const SplatLayout& L, float* out, uint32_t W,
                    const uint32_t* pix, uint32_t Np, hipStream_t st);
-// Light-group variants (GroupDev): init_paths that also records each pixel's light and starts the background pixels'
-// planes, gather / lazy_check that also keep the planes, and the resolve of out and every plane in one pass (out's splat
-// values are the sums of the per-light splat planes: FrameDev::splat then only holds the counts).
-void launchInitPathsGroups(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr, hipStream_t st);
-void launchGatherGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
-void launchLazyCheckGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const uint32_t* list, const uint32_t* listCount,
-                           int batch, uint32_t* nextList, uint32_t* nextCount, hipStream_t st);
-void launchResolveGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, hipStream_t st);
-// Masked-frame variants (MaskDev): init_paths that also builds the eye list and writes `out` for active pixels only, the
-// walk whose eye lists read MaskDev::walkEye (and that adds ENV_ON_MISS / EMISSIVE_HITS terms to active pixels only),
-// gather over every valid pixel that sums and writes only active ones (every pixel's splats still land), and the resolve
-// of active pixels.
-void launchInitPathsMasked(const SceneDev& S, const FrameDev& F, const PathBuf& P, const MaskDev& M, hipStream_t st);
-void launchWalkMasked(const SceneDev& S, const FrameDev& F, const PathBuf& P, const MaskDev& M, LaunchGrids& G, int numCUs, hipStream_t st);
-void launchGatherMasked(const FrameDev& F, const PathBuf& P, const MaskDev& M, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
-void launchResolveMasked(const FrameDev& F, const PathBuf& P, const MaskDev& M, hipStream_t st);
+// the frame's own resolve: launchResolve for a plain frame (whole context, SplatLayout order), the group or masked one
+void launchFrameResolve(const FrameDev& F, const PathBuf& P, const FrameVariant& V, hipStream_t st);
 // bdpt_adaptive_update (adaptive.hip; exact arithmetic in include/bdpt.h "Adaptive sampling").  `scratch`: two words of
 // the context, zero when the launch starts; the launch leaves them zero.
 struct AdaptiveDev {

@@ -23,6 +23,7 @@
 #include "kernels.h"
 
 #include <algorithm>
+#include <type_traits>
 
 #include "device_math.hpp"
 #include "device_scene.hpp"
@@ -303,6 +304,20 @@ __global__ __launch_bounds__(kWave) void light_map_kernel(SceneDev S, uint32_t* 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Frame kinds (FrameKind, kernels.h): the last argument of a per-pixel kernel of kind V, and the GroupDev / MaskDev its
+// lane functions take (zero for the other kinds).
+// ------------------------------------------------------------------------------------------------
+struct NoArg {};
+template <FrameKind V>
+using FrameArg = std::conditional_t<V == FrameKind::Groups, GroupDev, std::conditional_t<V == FrameKind::Masked, MaskDev, NoArg>>;
+template <class A>
+BD GroupDev groupOf(const A&) { return GroupDev{}; }
+BD const GroupDev& groupOf(const GroupDev& g) { return g; }
+template <class A>
+BD MaskDev maskOf(const A&) { return MaskDev{}; }
+BD const MaskDev& maskOf(const MaskDev& m) { return m; }
+
+// ------------------------------------------------------------------------------------------------
 // init_paths: eye vertex 1 from the G-buffer, light vertex 0 from sampleLight, valid-pixel queue
 // (BDPTMain.rt.hlsl:51-103, 124-135; sampleLight BDPTUtils.hlsli:140-152)
 // ------------------------------------------------------------------------------------------------
@@ -311,8 +326,8 @@ __global__ __launch_bounds__(kWave) void light_map_kernel(SceneDev S, uint32_t* 
 // MASKED (bdpt_execute_masked): every pixel's paths start as in the plain frame (its light subpath and seedL, which the
 // eye vertex's draws lead to, are needed whatever the mask says), but only active pixels get their `out` write, and the
 // active valid ones also go onto the eye list
-template <bool GGX, bool GROUPS, bool MASKED = false>
-BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const MaskDev& M = MaskDev{}) {
+template <bool GGX, bool GROUPS, bool MASKED>
+BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const MaskDev& M) {
   const uint32_t p = blockIdx.x * kWave + threadIdx.x;
   const bool inTile = p < P.Np;
   const size_t pix = inTile ? P.pix[p] : 0;
@@ -399,20 +414,10 @@ BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, co
   wavePush(geom, p, P.queue[0], P.qcount, P.pathSubCap);
   if (MASKED) wavePush(geom && active, p, M.eye, M.eyeCount, P.pathSubCap);
 }
-template <bool GGX>
-__global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev F, PathBuf P) {
+template <bool GGX, FrameKind V>
+__global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev F, PathBuf P, FrameArg<V> A) {
   BDPT_ONE_WAVE_PER_GROUP();
-  initPathsLane<GGX, false>(S, F, P, GroupDev{});
-}
-template <bool GGX>
-__global__ __launch_bounds__(kWave) void init_paths_groups_kernel(SceneDev S, FrameDev F, PathBuf P, GroupDev Gr) {
-  BDPT_ONE_WAVE_PER_GROUP();
-  initPathsLane<GGX, true>(S, F, P, Gr);
-}
-template <bool GGX>
-__global__ __launch_bounds__(kWave) void init_paths_masked_kernel(SceneDev S, FrameDev F, PathBuf P, MaskDev M) {
-  BDPT_ONE_WAVE_PER_GROUP();
-  initPathsLane<GGX, false, true>(S, F, P, GroupDev{}, M);
+  initPathsLane<GGX, V == FrameKind::Groups, V == FrameKind::Masked>(S, F, P, groupOf(A), maskOf(A));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -443,9 +448,9 @@ __global__ __launch_bounds__(kWave) void init_paths_masked_kernel(SceneDev S, Fr
 // reference's path pays nothing for it: the eye walk's shading pass adds what the ray found where it ended —
 // environment radiance on a miss, emissive on a hit — to the path's own pixel, in bounce order (a sub-path is shaded
 // by one lane at a time, and init_paths has written the pixel before this launch starts).
-// MASKED (bdpt_execute_masked) is a kernel of its own too: its eye lists (vq < kNumSubQueues) read MaskDev::walkEye, the
-// active valid pixels (under MIS every valid pixel: the splat weights read the eye prefix products), its light lists the
-// valid-pixel queue as before, and EXT terms reach active pixels only.
+// MASKED (bdpt_execute_masked) is an instantiation of its own too: its eye lists (vq < kNumSubQueues) read
+// MaskDev::walkEye, the active valid pixels (under MIS every valid pixel: the splat weights read the eye prefix products),
+// its light lists the valid-pixel queue as before, and EXT terms reach active pixels only.
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kPoolEntries = 128;
 #ifndef BDPT_WALK_ORDER
@@ -476,24 +481,265 @@ BD uint32_t packPath(uint32_t p, int path, int k) { return p | ((uint32_t)path <
 #endif
 constexpr int kWalkStackLds = BDPT_WALK_STACK_LDS;
 constexpr uint32_t kParkedMiss = 1u << 30;
-// The body of both walk kernels (walk_body.inc), included into each so that the plain kernel's code stays what it was.
-// It names S, F, P, head, s_stack, s_pool, the template flags GGX, COUNT, EXT, and MASKED with the MaskDev M.
-template <bool GGX, bool COUNT, bool EXT>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK_WAVES_PER_EU, 8))) void walk_kernel(SceneDev S, FrameDev F, PathBuf P, uint32_t* __restrict__ head) {
+// One template for both frames: a MASKED instance takes the MaskDev as its last argument, a plain one an empty struct
+// (M is then all zero).  The body is written here, not in a forced-inline __device__ function: that form compiled to a
+// differently scheduled plain walk.
+template <bool GGX, bool COUNT, bool EXT, bool MASKED>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK_WAVES_PER_EU, 8))) void walk_kernel(
+    SceneDev S, FrameDev F, PathBuf P, uint32_t* __restrict__ head, FrameArg<MASKED ? FrameKind::Masked : FrameKind::Plain> mask) {
   BDPT_ONE_WAVE_PER_GROUP();
   __shared__ int s_stack[kWalkStackLds * kWave];
   __shared__ uint4 s_pool[kPoolEntries];
-  constexpr bool MASKED = false;
-  const MaskDev M{};
-#include "walk_body.inc"
-}
-template <bool GGX, bool COUNT, bool EXT>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK_WAVES_PER_EU, 8))) void walk_masked_kernel(SceneDev S, FrameDev F, PathBuf P, uint32_t* __restrict__ head, MaskDev M) {
-  BDPT_ONE_WAVE_PER_GROUP();
-  __shared__ int s_stack[kWalkStackLds * kWave];
-  __shared__ uint4 s_pool[kPoolEntries];
-  constexpr bool MASKED = true;
-#include "walk_body.inc"
+  const MaskDev& M = maskOf(mask);
+  int* stk = s_stack + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63u);
+  const unsigned long long laneBelow = (1ull << lane) - 1ull;
+  const int D = (int)F.p.maxDepth;
+  const bool fromLobe = (F.p.flags & BDPT_PARAM_SPECULAR_FROM_LOBE) != 0;
+  // the eye walk extends vertices 1..D-1 (none when D < 2), the light walk vertices 0..D-1
+  const uint32_t firstV = (D >= 2) ? 0u : kNumSubQueues, numV = 2u * kNumSubQueues - firstV;
+  bool trav = false;   // this lane holds a ray
+  uint32_t id = 0;     // its path id
+  TravState T;
+  travInit(T, mk(0), mk(0), F.p.minT, 1.0e38f);
+  T.cur = kDone;
+  uint32_t nNodes = 0, nTris = 0, nAlpha = 0;
+  uint32_t nEye = 0, nLight = 0, nParked = 0, nReady = 0;  // wave-uniform
+  uint32_t vq = firstV + blockIdx.x % numV, tried = 0, chunkPos = 0, chunkEnd = 0, chunk = BDPT_WALK_CHUNK;
+  bool exhausted = false;
+  const uint32_t wavesPerList = (gridDim.x + numV - 1) / numV;
+  for (;;) {
+    unsigned long long travMask = __ballot(trav);
+    // ---- 1. hit / miss shaders, one parked record per lane ------------------------------------------
+    // (also when nothing else can make progress: the last records of the wave are shaded short-handed)
+    const bool flush = (travMask == 0ull) && nReady == 0 && exhausted && nParked > 0;
+    if (nParked >= (uint32_t)BDPT_WALK_SHADE_MIN || flush) {
+      const uint32_t n = nParked < (uint32_t)kWave ? nParked : (uint32_t)kWave;
+      nParked -= n;
+      const bool act = (uint32_t)lane < n;
+      uint4 rec = make_uint4(0, 0, 0, 0);
+      if (act) rec = s_pool[nParked + (uint32_t)lane];
+      __syncthreads();  // the slots may be overwritten by ready rays below
+      const uint32_t p = rec.x & 0xffffffu;
+      const int path = (int)((rec.x >> 24) & 1u), k = (int)((rec.x >> 25) & 31u);
+      nEye += (uint32_t)__popcll(__ballot(act && path == PATH_EYE));
+      nLight += (uint32_t)__popcll(__ballot(act && path == PATH_LIGHT));
+      bool survive = false;
+      f3 L = mk(0);
+      if (act) {
+        const bool miss = EXT ? (rec.x & kParkedMiss) != 0u : (int)rec.y < 0;
+        const int prim = miss ? -1 : (int)rec.y;
+        const f3 o = ldPlane3(P, path, k, F_POS, p);
+        // what the eye ray that left vertex k found where it ended (EXT): added to the path's pixel below
+        f3 found = mk(0);
+        bool haveFound = false;
+        if (prim >= 0) {
+          const uint32_t seed = (path == PATH_EYE) ? P.seedE[p] : P.seedL[p];
+          const f3 thr = ldPlane3(P, path, k, F_COL, p);
+          Shading sd = shadeHit<false>(S, (uint32_t)prim, __uint_as_float(rec.z), __uint_as_float(rec.w), o);  // V points at WorldRayOrigin()
+          float pdf;
+          bool isSpec;
+          f3 w = sampleBRDF<GGX>(seed, sd.N, sd.N, sd.V, sd.diffuse, sd.specular, sd.roughness, fromLobe, L, pdf, isSpec);
+          Vtx v;
+          v.color = thr * w;
+          v.pos = sd.posW;
+          v.N = sd.N;
+          v.V = sd.V;
+          v.dif = sd.diffuse;
+          v.spec = sd.specular;
+          v.rough = sd.roughness;
+          v.isSpec = isSpec;
+          v.pdf = pdf;
+          storeVtx(P, path, k + 1, p, v);
+          survive = (k + 2 <= D);  // k + 1 < maxK
+          if (EXT && path == PATH_EYE && (F.p.flags & BDPT_PARAM_EMISSIVE_HITS) &&
+              (sd.emissive.x > 0.0f || sd.emissive.y > 0.0f || sd.emissive.z > 0.0f)) {
+            found = thr * sd.emissive;
+            haveFound = true;
+          }
+        } else {
+          if (EXT && path == PATH_EYE && (F.p.flags & BDPT_PARAM_ENV_ON_MISS)) {
+            const f3 dir = mk(__uint_as_float(rec.y), __uint_as_float(rec.z), __uint_as_float(rec.w));
+            const f3 env = F.envMap ? envLookup(F.envMap, F.envW, F.envH, dir) : ld3(F.envColor);
+            found = ldPlane3(P, path, k, F_COL, p) * env;
+            haveFound = true;
+          }
+          Vtx g = zeroVtx();
+          if (path == PATH_EYE && k == 1) {
+            g.pos = o;  // payload still holds initPayload's values (RayPathData.hlsli:69-86)
+          } else {
+            loadSurf(P, path, k, p, g);
+            g.V = ldPlane3(P, path, k, F_V, p);
+            if (path == PATH_LIGHT && k == 0) g.pdf = 0.0f;  // initPayload: pdfForward = 0
+          }
+          g.color = mk(0);
+          storeVtx(P, path, k + 1, p, g);
+          if (path == PATH_EYE) {
+            P.eyeLast[p] = (uint8_t)(k + 1);
+          } else {
+            P.lightLast[p] = (uint8_t)(k + 1);
+            P.lightReal[p] = (uint8_t)k;
+          }
+        }
+        if (MASKED && haveFound && M.mask[P.pix[p]] == 0) haveFound = false;  // a pixel the mask leaves out: `out` stays as it is
+        if (EXT && haveFound) {  // path-tracing strategy of k + 1 edges: uniform 1/edges, clamped, no saturate (as NEE terms)
+          f3 term = clampVec(found / (float)(k + 1), F.p.clampUpper);
+          if (isnan3(term)) term = mk(0);
+          float4* out4 = reinterpret_cast<float4*>(F.out);
+          const size_t pix = P.pix[p];
+          float4 acc = out4[pix];
+          acc.x = acc.x + term.x;
+          acc.y = acc.y + term.y;
+          acc.z = acc.z + term.z;
+          acc.w = acc.w + 1.0f;
+          out4[pix] = acc;
+        }
+      }
+      // survivors -> ready rays (origin = the stored vertex k+1, re-read at pick-up)
+      const unsigned long long sm = __ballot(survive);
+      if (survive) {
+        const uint32_t slot = kPoolEntries - 1u - nReady - (uint32_t)__popcll(sm & laneBelow);
+        s_pool[slot] = make_uint4(packPath(p, path, k + 1), __float_as_uint(L.x), __float_as_uint(L.y), __float_as_uint(L.z));
+      }
+      nReady += (uint32_t)__popcll(sm);
+      // this wave's later loads of the vertices it just stored must see them (same CU: ordering is enough)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __syncthreads();
+    }
+    // ---- 2. empty lanes take ready rays, then new sub-paths -------------------------------------------
+    const int empty = 64 - __popcll(travMask);
+    if ((empty >= BDPT_WALK_REFILL || travMask == 0ull) && (nReady > 0 || !exhausted)) {
+      const unsigned long long emptyMask = ~travMask;
+      const uint32_t rank = (uint32_t)__popcll(emptyMask & laneBelow);
+      const uint32_t fromReady = ((uint32_t)empty < nReady) ? (uint32_t)empty : nReady;
+      bool got = false;
+      uint32_t nid = 0;
+      f3 dir = mk(0);
+      if (!trav && rank < fromReady) {
+        const uint4 r = s_pool[kPoolEntries - nReady + rank];
+        nid = r.x;
+        dir = mk(__uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
+        got = true;
+      }
+      __syncthreads();  // the pool slots just read may be reused by parked records
+      nReady -= fromReady;
+      uint32_t want = (uint32_t)empty - fromReady;  // lanes still empty: new sub-paths (only reached with nReady == 0)
+      uint32_t taken = fromReady;
+      while (want > 0 && !exhausted) {
+        while (chunkPos >= chunkEnd && !exhausted) {  // wave-uniform loop: take a new chunk
+          const uint32_t* counts = (MASKED && vq < kNumSubQueues) ? M.walkEyeCount : P.qcount;
+          const uint32_t nq = counts[(vq % kNumSubQueues) * kCursorStride];
+          uint32_t base = nq;
+          if (__hip_atomic_load(&head[vq * kCursorStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nq) {
+            // A sub-path keeps its lane for up to D rays, so the list is handed out in small pieces (BDPT_WALK_CHUNK):
+            // with 256 per fetch the last pieces kept single waves busy long after the rest of the grid had drained.
+            uint32_t share = (nq / wavesPerList + 15u) & ~15u;
+            chunk = share < 16u ? 16u : (share > (uint32_t)BDPT_WALK_CHUNK ? (uint32_t)BDPT_WALK_CHUNK : share);
+            if (lane == 0) base = atomicAdd(&head[vq * kCursorStride], chunk);
+            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+          }
+          if (base < nq) {
+            chunkPos = base;
+            chunkEnd = (base + chunk < nq) ? base + chunk : nq;
+            tried = 0;
+          } else {
+            vq = (vq + 1 == 2u * kNumSubQueues) ? firstV : vq + 1;
+            if (++tried >= numV) exhausted = true;
+          }
+        }
+        if (exhausted) break;
+        const uint32_t avail = chunkEnd - chunkPos;
+        const uint32_t take = (want < avail) ? want : avail;
+        if (!trav && !got && rank >= taken && rank < taken + take) {
+          const uint32_t* items = (MASKED && vq < kNumSubQueues) ? M.walkEye : P.queue[0];
+          const uint32_t p = items[(vq % kNumSubQueues) * P.pathSubCap + chunkPos + (rank - taken)];
+          const int path = (int)(vq / kNumSubQueues);
+          const float* rd = P.rayDir + (size_t)(path * 3) * P.Np + p;
+          nid = packPath(p, path, (path == PATH_EYE) ? 1 : 0);
+          dir = mk(rd[0], rd[P.Np], rd[2 * (size_t)P.Np]);
+          got = true;
+        }
+        chunkPos += take;
+        taken += take;
+        want -= take;
+      }
+      if (got) {
+        id = nid;
+        travInit(T, ldPlane3(P, (int)((nid >> 24) & 1u), (int)(nid >> 25), F_POS, nid & 0xffffffu), dir, F.p.minT, 1.0e38f);
+        trav = true;
+      }
+      travMask = __ballot(trav);
+    }
+    if (travMask == 0ull) {
+      if (nParked == 0 && nReady == 0 && exhausted) break;
+      continue;  // parked records are flushed (or ready rays picked up) at the top
+    }
+    // ---- 3. traversal for the lanes that hold a ray
+    bool finished = false;
+#if BDPT_WALK_LEAF_WAIT > 0
+    // node visits in short bursts; a lane that reaches a leaf (or runs out of stack) waits, and the leaves are intersected
+    // once half of the lanes that hold a ray are waiting or no lane can take a node visit (device_trace.hpp, trace_shadow_kernel)
+    if (trav) {
+#pragma unroll 1
+      for (int kk = 0; kk < BDPT_WALK_NODE_BURST && T.cur >= 0; kk++) {
+        if (COUNT) nNodes++;
+        nodeStep<BDPT_WALK_ORDER, kWalkStackLds>(S, T, stk);
+      }
+    }
+    {
+      const unsigned long long waitMask = __ballot(trav && T.cur < 0), nodeMask = __ballot(trav && T.cur >= 0);
+      const int waitNeed = (__popcll(waitMask | nodeMask) * BDPT_LEAF_WAIT_FRAC8 + 7) >> 3;
+      if ((int)__popcll(waitMask) >= waitNeed || nodeMask == 0ull) {
+        if (trav && T.cur < 0) {
+          finished = (T.cur == kDone);
+          if (!finished) {
+            finished = leafStep<0, COUNT>(S, T, nTris, nAlpha);
+            if (!finished) {
+              T.cur = travPop<kWalkStackLds>(S, T, stk);
+              finished = (T.cur == kDone);
+            }
+          }
+        }
+      }
+    }
+#else
+    if (trav) {
+      while (T.cur >= 0) {
+        if (COUNT) nNodes++;
+        nodeStep<BDPT_WALK_ORDER, kWalkStackLds>(S, T, stk);
+      }
+      finished = (T.cur == kDone);
+      if (!finished) {
+        finished = leafStep<0, COUNT>(S, T, nTris, nAlpha);
+        if (!finished) {
+          T.cur = travPop<kWalkStackLds>(S, T, stk);
+          finished = (T.cur == kDone);
+        }
+      }
+    }
+#endif
+    const unsigned long long finMask = __ballot(finished);
+    if (finMask) {
+      if (finished) {
+        const bool miss = T.best.prim < 0;
+        s_pool[nParked + (uint32_t)__popcll(finMask & laneBelow)] =
+            (EXT && miss) ? make_uint4(id | kParkedMiss, __float_as_uint(T.d.x), __float_as_uint(T.d.y), __float_as_uint(T.d.z))
+                          : make_uint4(id, (uint32_t)T.best.prim, __float_as_uint(T.best.u), __float_as_uint(T.best.v));
+        trav = false;
+      }
+      nParked += (uint32_t)__popcll(finMask);
+      __syncthreads();
+    }
+  }
+  if (lane == 0) {
+    if (nEye) atomicAdd(&F.counters->v[blockIdx.x % kCounterShards][C_RAYS_EYE], (unsigned long long)nEye);
+    if (nLight) atomicAdd(&F.counters->v[blockIdx.x % kCounterShards][C_RAYS_LIGHT], (unsigned long long)nLight);
+  }
+  if (COUNT) {
+    waveAddCount(F.counters, C_NODE_CLOSEST, nNodes);
+    waveAddCount(F.counters, C_TRI_CLOSEST, nTris);
+    waveAddCount(F.counters, C_ALPHA_CLOSEST, nAlpha);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -960,8 +1206,8 @@ BD void loadSlotChunk(const PathBuf& P, uint32_t p, int slot0, int n, SlotChunk&
 // with every intensity zero) adds its +0 terms for real, because it starts from `out`'s start, -0 included.
 // MASKED (bdpt_execute_masked): a pixel the mask leaves out (`active` false) only lands its splats — its NEE and
 // connection slots were never generated this frame — and its `out` is neither summed nor written.
-template <bool GROUPS, bool MASKED = false>
-BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, float* la, uint32_t p, uint32_t& nSplat, bool active = true) {
+template <bool GROUPS, bool MASKED>
+BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, float* la, uint32_t p, uint32_t& nSplat, bool active) {
   bool pending = false;
   const bool sums = !MASKED || active;
   const size_t pix = P.pix[p];
@@ -1074,9 +1320,13 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, floa
   return pending;
 }
 
+// every valid pixel; a masked frame (its splats land whatever the mask says) sums and writes `out` of active pixels only
+template <FrameKind V>
 __global__ __launch_bounds__(kWave) void gather_kernel(FrameDev F, PathBuf P, uint32_t* __restrict__ lazyList,
-                                                       uint32_t* __restrict__ lazyCount) {
+                                                       uint32_t* __restrict__ lazyCount, FrameArg<V> A) {
   BDPT_ONE_WAVE_PER_GROUP();
+  constexpr bool GROUPS = V == FrameKind::Groups, MASKED = V == FrameKind::Masked;
+  __shared__ float s_acc[GROUPS ? 3 * BDPT_MAX_LIGHTS * kWave : 1];  // light planes' RGB while a lane sums them (12 KiB)
   bool act = false;
   uint32_t i = 0;
   if (!queueChunk(P.qcount, P.pathSubCap, act, i)) return;
@@ -1084,42 +1334,8 @@ __global__ __launch_bounds__(kWave) void gather_kernel(FrameDev F, PathBuf P, ui
   bool pending = false;
   if (act) {
     p = P.queue[0][i];
-    pending = gatherLane<false>(F, P, GroupDev{}, nullptr, p, nSplat);
-    if (pending) P.lazyCursor[p] = 0;
-  }
-  waveAddCount(F.counters, C_SPLATS, nSplat);
-  wavePush(pending, p, lazyList, lazyCount, P.pathSubCap);
-}
-__global__ __launch_bounds__(kWave) void gather_groups_kernel(FrameDev F, PathBuf P, GroupDev Gr, uint32_t* __restrict__ lazyList,
-                                                              uint32_t* __restrict__ lazyCount) {
-  BDPT_ONE_WAVE_PER_GROUP();
-  __shared__ float s_acc[3 * BDPT_MAX_LIGHTS * kWave];  // light planes' RGB while a lane sums them (12 KiB)
-  bool act = false;
-  uint32_t i = 0;
-  if (!queueChunk(P.qcount, P.pathSubCap, act, i)) return;
-  uint32_t nSplat = 0, p = 0;
-  bool pending = false;
-  if (act) {
-    p = P.queue[0][i];
-    pending = gatherLane<true>(F, P, Gr, s_acc + threadIdx.x, p, nSplat);
-    if (pending) P.lazyCursor[p] = 0;
-  }
-  waveAddCount(F.counters, C_SPLATS, nSplat);
-  wavePush(pending, p, lazyList, lazyCount, P.pathSubCap);
-}
-
-// every valid pixel (its splats land whatever the mask says); the sums and the `out` write of active pixels only
-__global__ __launch_bounds__(kWave) void gather_masked_kernel(FrameDev F, PathBuf P, MaskDev M, uint32_t* __restrict__ lazyList,
-                                                              uint32_t* __restrict__ lazyCount) {
-  BDPT_ONE_WAVE_PER_GROUP();
-  bool act = false;
-  uint32_t i = 0;
-  if (!queueChunk(P.qcount, P.pathSubCap, act, i)) return;
-  uint32_t nSplat = 0, p = 0;
-  bool pending = false;
-  if (act) {
-    p = P.queue[0][i];
-    pending = gatherLane<false, true>(F, P, GroupDev{}, nullptr, p, nSplat, M.mask[P.pix[p]] != 0);
+    pending = gatherLane<GROUPS, MASKED>(F, P, groupOf(A), GROUPS ? s_acc + threadIdx.x : nullptr, p, nSplat,
+                                         !MASKED || maskOf(A).mask[P.pix[p]] != 0);
     if (pending) P.lazyCursor[p] = 0;
   }
   waveAddCount(F.counters, C_SPLATS, nSplat);
@@ -1264,17 +1480,12 @@ BD void lazyCheck(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const
   }
   wavePush(again, p, nextList, nextCount, P.pathSubCap);
 }
+template <FrameKind V>
 __global__ __launch_bounds__(kWave) void lazy_check_kernel(FrameDev F, PathBuf P, const uint32_t* __restrict__ list,
                                                            const uint32_t* __restrict__ listCount, int batch,
-                                                           uint32_t* __restrict__ nextList, uint32_t* __restrict__ nextCount) {
+                                                           uint32_t* __restrict__ nextList, uint32_t* __restrict__ nextCount, FrameArg<V> A) {
   BDPT_ONE_WAVE_PER_GROUP();
-  lazyCheck<false>(F, P, GroupDev{}, list, listCount, batch, nextList, nextCount);
-}
-__global__ __launch_bounds__(kWave) void lazy_check_groups_kernel(FrameDev F, PathBuf P, GroupDev Gr, const uint32_t* __restrict__ list,
-                                                                  const uint32_t* __restrict__ listCount, int batch,
-                                                                  uint32_t* __restrict__ nextList, uint32_t* __restrict__ nextCount) {
-  BDPT_ONE_WAVE_PER_GROUP();
-  lazyCheck<true>(F, P, Gr, list, listCount, batch, nextList, nextCount);
+  lazyCheck<V == FrameKind::Groups>(F, P, groupOf(A), list, listCount, batch, nextList, nextCount);
 }
 
 // out = saturate(out + splat) where at least one splat landed
@@ -1480,13 +1691,44 @@ static inline uint32_t queueGrid(const PathBuf& P) { return (P.pathSubCap / kWav
 // and each starts with oneWavePerGroup(), which makes a launch of any other shape do nothing instead of corrupting.
 // (launchWave and persistentGrid: launch.hpp)
 
+// Run-time flags as template arguments: fn(std::true_type{} or std::false_type{}, ...), one per flag in order.  The
+// parameters convert to bool where a template argument needs one (walk_kernel<GGX, COUNT, EXT, MASKED>).
+template <class Fn>
+static void withFlags(Fn&& fn) {
+  fn();
+}
+template <class Fn, class... Flags>
+static void withFlags(Fn&& fn, bool f, Flags... rest) {
+  if (f)
+    withFlags([&](auto... t) { fn(std::true_type{}, t...); }, rest...);
+  else
+    withFlags([&](auto... t) { fn(std::false_type{}, t...); }, rest...);
+}
+// The frame kind as a template argument: fn(std::integral_constant<FrameKind, kind>{}).
+template <class Fn>
+static void withKind(FrameKind kind, Fn&& fn) {
+  if (kind == FrameKind::Groups)
+    fn(std::integral_constant<FrameKind, FrameKind::Groups>{});
+  else if (kind == FrameKind::Masked)
+    fn(std::integral_constant<FrameKind, FrameKind::Masked>{});
+  else
+    fn(std::integral_constant<FrameKind, FrameKind::Plain>{});
+}
+// what a per-pixel kernel of kind K takes as its last argument
+template <FrameKind K>
+static FrameArg<K> frameArg(const FrameVariant& V) {
+  if constexpr (K == FrameKind::Groups)
+    return V.groups;
+  else if constexpr (K == FrameKind::Masked)
+    return V.mask;
+  else
+    return NoArg{};
+}
+
 void launchGBuffer(const SceneDev& S, const GBufferDev& G, hipStream_t st) {
   const uint32_t Np = G.Np;
   if (!Np) return;
-  if (G.counters)
-    launchWave(gbuffer_kernel<true>, (uint32_t)(blocksFor(Np)), st, S, G);
-  else
-    launchWave(gbuffer_kernel<false>, (uint32_t)(blocksFor(Np)), st, S, G);
+  withFlags([&](auto CNT) { launchWave(gbuffer_kernel<CNT>, blocksFor(Np), st, S, G); }, G.counters != nullptr);
 }
 
 // The 64-byte alpha-test record of every non-opaque triangle (device_scene.hpp alphaTestFails: the triangle's three texture
@@ -1537,38 +1779,28 @@ void launchLightMaps(const SceneDev& S, uint32_t* maps, uint32_t res, hipStream_
   launchWave(light_map_kernel, (uint32_t)((n + kWave - 1) / kWave), st, S, maps, res);
 }
 
-void launchInitPaths(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st) {
+void launchInitPaths(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, hipStream_t st) {
   if (!P.Np) return;
-  if (F.p.matIndex == 0)
-    launchWave(init_paths_kernel<true>, (uint32_t)(blocksFor(P.Np)), st, S, F, P);
-  else
-    launchWave(init_paths_kernel<false>, (uint32_t)(blocksFor(P.Np)), st, S, F, P);
+  withKind(V.kind, [&](auto K) {
+    withFlags([&](auto GGX) { launchWave(init_paths_kernel<GGX, K>, blocksFor(P.Np), st, S, F, P, frameArg<K>(V)); }, F.p.matIndex == 0);
+  });
 }
 
-void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, LaunchGrids& G, int numCUs, hipStream_t st) {
+void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,
+                hipStream_t st) {
   if (!P.Np || F.p.maxDepth < 1) return;
   const bool cnt = (F.p.flags & BDPT_PARAM_COUNTERS) != 0, ggx = F.p.matIndex == 0;
-  const bool ext = (F.p.flags & (BDPT_PARAM_ENV_ON_MISS | BDPT_PARAM_EMISSIVE_HITS)) != 0;
-  uint32_t& g = G.walk[(ext ? 4 : 0) + (ggx ? 2 : 0) + (cnt ? 1 : 0)];
+  const bool ext = (F.p.flags & (BDPT_PARAM_ENV_ON_MISS | BDPT_PARAM_EMISSIVE_HITS)) != 0, masked = V.kind == FrameKind::Masked;
+  uint32_t& g = G.walk[(masked ? 8 : 0) + (ext ? 4 : 0) + (ggx ? 2 : 0) + (cnt ? 1 : 0)];
   // at most two sub-paths per pixel: a small tile does not need the whole persistent grid
   const uint32_t need = blocksFor((uint64_t)2 * P.Np);
-#define BDPT_LAUNCH_WALK(GGX, CNT, EXT)                                                                        \
-  {                                                                                                           \
-    if (!g) g = persistentGrid(walk_kernel<GGX, CNT, EXT>, numCUs);                                            \
-    launchWave((walk_kernel<GGX, CNT, EXT>), (uint32_t)(std::min(g, need)), st, S, F, P, P.qhead); \
-  }
-  if (ext) {
-    if (ggx && cnt) BDPT_LAUNCH_WALK(true, true, true)
-    else if (ggx) BDPT_LAUNCH_WALK(true, false, true)
-    else if (cnt) BDPT_LAUNCH_WALK(false, true, true)
-    else BDPT_LAUNCH_WALK(false, false, true)
-  } else {
-    if (ggx && cnt) BDPT_LAUNCH_WALK(true, true, false)
-    else if (ggx) BDPT_LAUNCH_WALK(true, false, false)
-    else if (cnt) BDPT_LAUNCH_WALK(false, true, false)
-    else BDPT_LAUNCH_WALK(false, false, false)
-  }
-#undef BDPT_LAUNCH_WALK
+  withFlags(
+      [&](auto GGX, auto CNT, auto EXT, auto MASKED) {
+        const auto kernel = walk_kernel<GGX, CNT, EXT, MASKED>;
+        if (!g) g = persistentGrid(kernel, numCUs);
+        launchWave(kernel, std::min(g, need), st, S, F, P, P.qhead, frameArg<MASKED ? FrameKind::Masked : FrameKind::Plain>(V));
+      },
+      ggx, cnt, ext, masked);
 }
 
 void launchMisPrefix(const FrameDev& F, const PathBuf& P, hipStream_t st) {
@@ -1576,28 +1808,23 @@ void launchMisPrefix(const FrameDev& F, const PathBuf& P, hipStream_t st) {
   launchWave(mis_prefix_kernel, (uint32_t)(queueGrid(P)), st, F, P);
 }
 // The three generators only share the ray queues (atomic appends), so the host may launch them on different streams.
-// G lanes per pixel: 8 for contexts sized up to depth 8, else 16 (the ray queues are sized for that shape).
-#define BDPT_LAUNCH_GEN(KERNEL)                                                                   \
-  {                                                                                               \
-    const bool ggx = F.p.matIndex == 0, wide = P.D1 > 9; /* the depth the context is sized for */  \
-    if (ggx && !wide) launchWave(KERNEL<true, 8>, queueGrid(P) * 8, st, S, F, P);     \
-    else if (ggx) launchWave(KERNEL<true, 16>, queueGrid(P) * 16, st, S, F, P);       \
-    else if (!wide) launchWave(KERNEL<false, 8>, queueGrid(P) * 8, st, S, F, P);      \
-    else launchWave(KERNEL<false, 16>, queueGrid(P) * 16, st, S, F, P);               \
-  }
+// G lanes per pixel: 8 for contexts sized up to depth 8, else 16 (the ray queues are sized for that shape; P.D1 is the
+// depth the context is sized for).
 void launchGenNee(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st) {
   if (!P.Np) return;
-  BDPT_LAUNCH_GEN(gen_nee_kernel)
+  withFlags([&](auto GGX, auto WIDE) { launchWave(gen_nee_kernel<GGX, WIDE ? 16 : 8>, queueGrid(P) * (WIDE ? 16 : 8), st, S, F, P); },
+            F.p.matIndex == 0, P.D1 > 9);
 }
 void launchGenSplat(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st) {
   if (!P.Np || (F.p.flags & BDPT_PARAM_NO_SPLAT)) return;
-  BDPT_LAUNCH_GEN(gen_splat_kernel)
+  withFlags([&](auto GGX, auto WIDE) { launchWave(gen_splat_kernel<GGX, WIDE ? 16 : 8>, queueGrid(P) * (WIDE ? 16 : 8), st, S, F, P); },
+            F.p.matIndex == 0, P.D1 > 9);
 }
 void launchGenConnect(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st) {
   if (!P.Np || (F.p.flags & BDPT_PARAM_NO_CONNECT) || F.p.maxDepth < 2) return;
-  BDPT_LAUNCH_GEN(gen_connect_kernel)
+  withFlags([&](auto GGX, auto WIDE) { launchWave(gen_connect_kernel<GGX, WIDE ? 16 : 8>, queueGrid(P) * (WIDE ? 16 : 8), st, S, F, P); },
+            F.p.matIndex == 0, P.D1 > 9);
 }
-#undef BDPT_LAUNCH_GEN
 
 void launchTraceShadow(const SceneDev& S, const FrameDev& F, const PathBuf& P, int cls, LaunchGrids& G, int numCUs, hipStream_t st) {
   if (!P.Np) return;
@@ -1607,30 +1834,31 @@ void launchTraceShadow(const SceneDev& S, const FrameDev& F, const PathBuf& P, i
              P.rayHead + (size_t)cls * kRayCursorBlock};
   uint8_t* vis = P.rayVis + P.rayBase[cls];
   uint32_t& g = G.shadow[cnt ? 1 : 0];
-  if (cnt) {
-    if (!g) g = persistentGrid(trace_shadow_kernel<true>, numCUs);
-    launchWave(trace_shadow_kernel<true>, (uint32_t)(g), st, S, Q, vis, F.counters, F.p.minT);
-  } else {
-    if (!g) g = persistentGrid(trace_shadow_kernel<false>, numCUs);
-    launchWave(trace_shadow_kernel<false>, (uint32_t)(g), st, S, Q, vis, F.counters, F.p.minT);
-  }
+  withFlags(
+      [&](auto CNT) {
+        if (!g) g = persistentGrid(trace_shadow_kernel<CNT>, numCUs);
+        launchWave(trace_shadow_kernel<CNT>, g, st, S, Q, vis, F.counters, F.p.minT);
+      },
+      cnt);
 }
 
-void launchGather(const FrameDev& F, const PathBuf& P, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st) {
+void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st) {
   if (!P.Np) return;
-  launchWave(gather_kernel, (uint32_t)(queueGrid(P)), st, F, P, lazyList, lazyCount);
+  withKind(V.kind, [&](auto K) { launchWave(gather_kernel<K>, queueGrid(P), st, F, P, lazyList, lazyCount, frameArg<K>(V)); });
 }
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st) {
   if (!P.Np) return;
-  if (P.D1 > 9)  // the depth the context is sized for: 16 lanes per pixel, as the generators
-    launchWave(lazy_gen_kernel<16>, (uint32_t)(queueGrid(P) * 16), st, F, P, list, listCount, batch);
-  else
-    launchWave(lazy_gen_kernel<8>, (uint32_t)(queueGrid(P) * 8), st, F, P, list, listCount, batch);
+  // 16 lanes per pixel for contexts sized beyond depth 8, as the generators
+  withFlags([&](auto WIDE) { launchWave(lazy_gen_kernel<WIDE ? 16 : 8>, queueGrid(P) * (WIDE ? 16 : 8), st, F, P, list, listCount, batch); },
+            P.D1 > 9);
 }
-void launchLazyCheck(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch,
-                     uint32_t* nextList, uint32_t* nextCount, hipStream_t st) {
+void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,
+                     int batch, uint32_t* nextList, uint32_t* nextCount, hipStream_t st) {
   if (!P.Np) return;
-  launchWave(lazy_check_kernel, (uint32_t)(queueGrid(P)), st, F, P, list, listCount, batch, nextList, nextCount);
+  if (V.kind == FrameKind::Groups)
+    launchWave(lazy_check_kernel<FrameKind::Groups>, queueGrid(P), st, F, P, list, listCount, batch, nextList, nextCount, V.groups);
+  else  // (a masked frame's lazy rounds only see the active pixels its gather handed them: the plain check)
+    launchWave(lazy_check_kernel<FrameKind::Plain>, queueGrid(P), st, F, P, list, listCount, batch, nextList, nextCount, NoArg{});
 }
 
 void launchResolve(const unsigned long long* splat, bool tileLocal, uint32_t splatRow0, const SplatLayout& L, float* out, uint32_t W,
@@ -1640,66 +1868,15 @@ void launchResolve(const unsigned long long* splat, bool tileLocal, uint32_t spl
   hipLaunchKernelGGL(resolve_kernel, dim3(grid), dim3(256), 0, st, splat, tileLocal, splatRow0, L, reinterpret_cast<float4*>(out), W, pix,
                      Np);
 }
-void launchInitPathsGroups(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr, hipStream_t st) {
-  if (!P.Np) return;
-  if (F.p.matIndex == 0)
-    launchWave(init_paths_groups_kernel<true>, (uint32_t)(blocksFor(P.Np)), st, S, F, P, Gr);
-  else
-    launchWave(init_paths_groups_kernel<false>, (uint32_t)(blocksFor(P.Np)), st, S, F, P, Gr);
-}
-void launchGatherGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st) {
-  if (!P.Np) return;
-  launchWave(gather_groups_kernel, (uint32_t)(queueGrid(P)), st, F, P, Gr, lazyList, lazyCount);
-}
-void launchLazyCheckGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const uint32_t* list, const uint32_t* listCount,
-                           int batch, uint32_t* nextList, uint32_t* nextCount, hipStream_t st) {
-  if (!P.Np) return;
-  launchWave(lazy_check_groups_kernel, (uint32_t)(queueGrid(P)), st, F, P, Gr, list, listCount, batch, nextList, nextCount);
-}
-void launchResolveGroups(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, hipStream_t st) {
+void launchFrameResolve(const FrameDev& F, const PathBuf& P, const FrameVariant& V, hipStream_t st) {
   if (!P.Np) return;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)P.Np + 255) / 256, 2048);
-  hipLaunchKernelGGL(resolve_groups_kernel, dim3(grid), dim3(256), 0, st, F, P.pix, P.Np, Gr);
-}
-void launchInitPathsMasked(const SceneDev& S, const FrameDev& F, const PathBuf& P, const MaskDev& M, hipStream_t st) {
-  if (!P.Np) return;
-  if (F.p.matIndex == 0)
-    launchWave(init_paths_masked_kernel<true>, (uint32_t)(blocksFor(P.Np)), st, S, F, P, M);
+  if (V.kind == FrameKind::Groups)
+    hipLaunchKernelGGL(resolve_groups_kernel, dim3(grid), dim3(256), 0, st, F, P.pix, P.Np, V.groups);
+  else if (V.kind == FrameKind::Masked)
+    hipLaunchKernelGGL(resolve_masked_kernel, dim3(grid), dim3(256), 0, st, F.splat, reinterpret_cast<float4*>(F.out), V.mask.mask, P.pix, P.Np);
   else
-    launchWave(init_paths_masked_kernel<false>, (uint32_t)(blocksFor(P.Np)), st, S, F, P, M);
-}
-void launchWalkMasked(const SceneDev& S, const FrameDev& F, const PathBuf& P, const MaskDev& M, LaunchGrids& G, int numCUs, hipStream_t st) {
-  if (!P.Np || F.p.maxDepth < 1) return;
-  const bool cnt = (F.p.flags & BDPT_PARAM_COUNTERS) != 0, ggx = F.p.matIndex == 0;
-  const bool ext = (F.p.flags & (BDPT_PARAM_ENV_ON_MISS | BDPT_PARAM_EMISSIVE_HITS)) != 0;
-  uint32_t& g = G.walkMasked[(ext ? 4 : 0) + (ggx ? 2 : 0) + (cnt ? 1 : 0)];
-  const uint32_t need = blocksFor((uint64_t)2 * P.Np);
-#define BDPT_LAUNCH_WALK(GGX, CNT, EXT)                                                                        \
-  {                                                                                                           \
-    if (!g) g = persistentGrid(walk_masked_kernel<GGX, CNT, EXT>, numCUs);                                     \
-    launchWave((walk_masked_kernel<GGX, CNT, EXT>), (uint32_t)(std::min(g, need)), st, S, F, P, P.qhead, M);   \
-  }
-  if (ext) {
-    if (ggx && cnt) BDPT_LAUNCH_WALK(true, true, true)
-    else if (ggx) BDPT_LAUNCH_WALK(true, false, true)
-    else if (cnt) BDPT_LAUNCH_WALK(false, true, true)
-    else BDPT_LAUNCH_WALK(false, false, true)
-  } else {
-    if (ggx && cnt) BDPT_LAUNCH_WALK(true, true, false)
-    else if (ggx) BDPT_LAUNCH_WALK(true, false, false)
-    else if (cnt) BDPT_LAUNCH_WALK(false, true, false)
-    else BDPT_LAUNCH_WALK(false, false, false)
-  }
-#undef BDPT_LAUNCH_WALK
-}
-void launchGatherMasked(const FrameDev& F, const PathBuf& P, const MaskDev& M, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st) {
-  if (!P.Np) return;
-  launchWave(gather_masked_kernel, (uint32_t)(queueGrid(P)), st, F, P, M, lazyList, lazyCount);
-}
-void launchResolveMasked(const FrameDev& F, const PathBuf& P, const MaskDev& M, hipStream_t st) {
-  if (!P.Np) return;
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)P.Np + 255) / 256, 2048);
-  hipLaunchKernelGGL(resolve_masked_kernel, dim3(grid), dim3(256), 0, st, F.splat, reinterpret_cast<float4*>(F.out), M.mask, P.pix, P.Np);
+    launchResolve(F.splat, false, 0, F.sl, F.out, F.W, P.pix, P.Np, st);
 }
 void launchAccumulate(float* last, float* cur, uint32_t accumCount, uint32_t maxAccum, uint64_t numTexels, hipStream_t st) {
   if (!numTexels) return;
