@@ -153,6 +153,13 @@ void hostParallelFor(size_t n, const F& f) {
   pool.join();
 }
 
+// The alpha-quad plane of an RGBA8 texture (texture_planes.h alphaQuadRows), rows spread over the host threads
+std::vector<uint32_t> alphaQuadPlane(const bdpt_texture& t) {
+  std::vector<uint32_t> q((size_t)t.width * t.height);
+  hostParallelFor(t.height, [&](size_t y0, size_t y1) { alphaQuadRows(t.rgba8, t.width, t.height, (uint32_t)y0, (uint32_t)y1, q.data()); });
+  return q;
+}
+
 bool fail(bdpt_ctx* c, const std::string& m) {
   if (c) c->err = m;
   return false;
@@ -584,9 +591,19 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
       fail(c, "scene: empty texture");
       return BDPT_E_INVALID;
     }
-    const uint8_t* px;
-    if ((rc = devUpload(c, c->sceneAllocs, &px, t.rgba8, (size_t)t.width * t.height * 4))) return rc;
-    texs[i] = TexDev{px, t.width, t.height, t.srgb, 0};
+    // one spare texel after the last: the row-pair load of the last texel (device_scene.hpp texelRow) stays inside
+    const size_t bytes = (size_t)t.width * t.height * 4;
+    uint8_t* px = nullptr;
+    if ((rc = devAlloc(c, c->sceneAllocs, &px, bytes + 4))) return rc;
+    HIPCHK(c, hipMemset(px + bytes, 0, 4));
+    {
+      std::string e;
+      if (!bvhUploadStaged(px, t.rgba8, bytes, e)) {
+        fail(c, e);
+        return BDPT_E_HIP;
+      }
+    }
+    texs[i] = TexDev{px, t.width, t.height, t.srgb, texPow2Flags(t.width, t.height)};
   }
   if ((rc = devUpload(c, c->sceneAllocs, &c->S.textures, texs.data(), texs.size()))) return rc;
   {
@@ -607,13 +624,30 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
     if (alphaTris.empty()) {
       HIPCHK(c, hipMemset(dAlpha, 0, 4 * sizeof(float4)));
     } else {
+      // an alpha-quad plane for every base-colour texture an alpha test samples (device_scene.hpp alphaQuad): the
+      // materials of the listed triangles (the ids their shading records carry), under the record builder's own rule
+      // (alphaSamplesTexture), so that every mode-2 record alpha_recs_kernel writes has its plane
+      std::vector<uint8_t> alphaMat(d->numMaterials, 0);
+      for (const uint32_t t : alphaTris) alphaMat[d->triMaterial[t]] = 1;
+      std::vector<unsigned long long> quadByTex(std::max<size_t>(d->numTextures, 1), 0ull);
+      for (uint32_t mi = 0; mi < d->numMaterials; mi++) {
+        const bdpt_material& mm = d->materials[mi];
+        if (!alphaMat[mi] || !alphaSamplesTexture(BDPT_FLAG_DIFFUSE_TYPE(mm.flags), mm.texBaseColor) || quadByTex[(size_t)mm.texBaseColor])
+          continue;
+        const std::vector<uint32_t> plane = alphaQuadPlane(d->textures[mm.texBaseColor]);
+        const uint32_t* dPlane = nullptr;
+        if ((rc = devUpload(c, c->sceneAllocs, &dPlane, plane.data(), plane.size()))) return rc;
+        quadByTex[(size_t)mm.texBaseColor] = (unsigned long long)reinterpret_cast<uintptr_t>(dPlane);
+      }
       const uint32_t* dList = nullptr;
+      const unsigned long long* dQuad = nullptr;
       std::vector<void*> scratch;
-      if ((rc = devUpload(c, scratch, &dList, alphaTris.data(), alphaTris.size()))) {
+      if ((rc = devUpload(c, scratch, &dList, alphaTris.data(), alphaTris.size())) ||
+          (rc = devUpload(c, scratch, &dQuad, quadByTex.data(), quadByTex.size()))) {
         freePool(scratch);
         return rc;
       }
-      launchAlphaRecs(c->S, dList, (uint32_t)alphaTris.size(), dAlpha, nullptr);
+      launchAlphaRecs(c->S, dList, (uint32_t)alphaTris.size(), dQuad, dAlpha, nullptr);
       const hipError_t e = hipDeviceSynchronize();
       freePool(scratch);
       HIPCHK(c, e);

@@ -12,23 +12,32 @@ struct f4 {
 BD f4 lerp4(f4 a, f4 b, float s) {
   return f4{a.x + (b.x - a.x) * s, a.y + (b.y - a.y) * s, a.z + (b.z - a.z) * s, a.w + (b.w - a.w) * s};
 }
-BD int wrapi(int i, int n) {
-  int m = i % n;
-  return (m < 0) ? m + n : m;
+// The two texels (ix0, iy) and (ix1, iy) of one row of an RGBA8 texture: one 8-byte load of (ix0, ix0 + 1), which is the
+// pair wherever they are adjacent (every column but the wrap column, where texel ix1 = 0 is loaded on its own).  A global
+// dwordx2 load needs only 4-byte alignment, which every texel has; the texture keeps one spare texel after its last, so
+// the pair load at the very last texel stays inside (api.cpp bdpt_set_scene).  Textures are device allocations: read
+// through global-address-space pointers, not flat ones.
+typedef __attribute__((address_space(1))) const uint32_t gU32;
+typedef __attribute__((address_space(1), aligned(4))) const unsigned long long gU64a4;  // 8 bytes at their real alignment
+BD void texelRow(const uint8_t* px, uint32_t w, int iy, int ix0, int ix1, uint32_t& a, uint32_t& b) {
+  gU32* row = (gU32*)px + (size_t)iy * w;
+  const unsigned long long q = *(gU64a4*)(row + ix0);  // (one 64-bit word: as two 32-bit halves the compiler splits the load)
+  a = (uint32_t)q;
+  b = (uint32_t)(q >> 32);
+  if (ix1 != ix0 + 1) b = row[ix1];
 }
-BD f4 texel(const SceneDev& S, const TexDev& t, int ix, int iy) {
-  const uchar4 p = *reinterpret_cast<const uchar4*>(t.px + ((size_t)iy * t.w + (size_t)ix) * 4);
+BD f4 texel(const SceneDev& S, const TexDev& t, uint32_t p) {  // p: the RGBA8 texel, R in the low byte
   f4 r;
   if (t.srgb) {
-    r.x = S.sc->srgbLut[p.x];
-    r.y = S.sc->srgbLut[p.y];
-    r.z = S.sc->srgbLut[p.z];
+    r.x = S.sc->srgbLut[p & 0xffu];
+    r.y = S.sc->srgbLut[(p >> 8) & 0xffu];
+    r.z = S.sc->srgbLut[(p >> 16) & 0xffu];
   } else {
-    r.x = (float)p.x / 255.0f;
-    r.y = (float)p.y / 255.0f;
-    r.z = (float)p.z / 255.0f;
+    r.x = (float)(p & 0xffu) / 255.0f;
+    r.y = (float)((p >> 8) & 0xffu) / 255.0f;
+    r.z = (float)((p >> 16) & 0xffu) / 255.0f;
   }
-  r.w = (float)p.w / 255.0f;
+  r.w = (float)(p >> 24) / 255.0f;
   return r;
 }
 // linear filter, wrap addressing, mip 0 (sampler: SharedUtils/SceneLoaderWrapper.cpp:65-68)
@@ -37,10 +46,13 @@ BD f4 sampleBilinearT(const SceneDev& S, const TexDev& t, float u, float v) {
   float y = v * (float)t.h - 0.5f;
   float x0 = floorf(x), y0 = floorf(y);
   float fx = x - x0, fy = y - y0;
-  int ix0 = wrapi((int)x0, (int)t.w), iy0 = wrapi((int)y0, (int)t.h);
-  int ix1 = wrapi(ix0 + 1, (int)t.w), iy1 = wrapi(iy0 + 1, (int)t.h);
-  f4 t00 = texel(S, t, ix0, iy0), t10 = texel(S, t, ix1, iy0);
-  f4 t01 = texel(S, t, ix0, iy1), t11 = texel(S, t, ix1, iy1);
+  int ix0 = wrapT((int)x0, (int)t.w, (t.pow2 & kTexPow2W) != 0u), iy0 = wrapT((int)y0, (int)t.h, (t.pow2 & kTexPow2H) != 0u);
+  int ix1 = wrapNext(ix0, (int)t.w), iy1 = wrapNext(iy0, (int)t.h);
+  uint32_t p00, p10, p01, p11;
+  texelRow(t.px, t.w, iy0, ix0, ix1, p00, p10);
+  texelRow(t.px, t.w, iy1, ix0, ix1, p01, p11);
+  f4 t00 = texel(S, t, p00), t10 = texel(S, t, p10);
+  f4 t01 = texel(S, t, p01), t11 = texel(S, t, p11);
   return lerp4(lerp4(t00, t10, fx), lerp4(t01, t11, fx), fy);
 }
 BD f4 sampleBilinear(const SceneDev& S, int texId, float u, float v) { return sampleBilinearT(S, S.textures[texId], u, v); }
@@ -84,11 +96,24 @@ BD MatDev loadMaterial(const SceneDev& S, uint32_t id) {
 
 // BDPT/BDPTUtils.hlsli:115-127.  Everything the any-hit alpha test of a non-opaque triangle reads sits in ONE 64-byte
 // record (built by bdpt_set_scene: the three texture coordinates, the material's threshold and constant alpha, how the base
-// colour is sampled, and the base-colour texture's address and size), so a candidate hit costs one record fetch and four
-// texel fetches instead of the chain shading record -> material -> texture descriptor -> texels.  Same arithmetic as
+// colour is sampled, and the base-colour texture's size and alpha-quad plane), so a candidate hit costs one record fetch and
+// one texel fetch instead of the chain shading record -> material -> texture descriptor -> texels.  Same arithmetic as
 // shadeHit + sampleTexture on the alpha channel (texel alpha = byte / 255, bilinear, wrap).
-//   f4[0] = uv0, uv1   f4[1] = uv2, alphaThreshold, baseColor.a   f4[2] = mode (0 unused, 1 constant, 2 texture), width, height
-//   f4[3] = texel address (two words)
+//   f4[0] = uv0, uv1   f4[1] = uv2, alphaThreshold, baseColor.a
+//   f4[2] = mode (0 unused, 1 constant, 2 texture), width, height, TexDev::pow2 flags   f4[3] = alpha-quad plane address (two words)
+// The alpha-quad plane (texture_planes.h alphaQuadRows) holds per texel (x, y) the alpha bytes of its 2x2 bilinear footprint, wrap
+// already applied: a(x, y), a(x+1, y), a(x, y+1), a(x+1, y+1) from the low byte up.
+BD uint32_t alphaQuad(const float4& a2, const float4& a3, float u, float v, float& fx, float& fy) {
+  const int tw = (int)__float_as_uint(a2.y), th = (int)__float_as_uint(a2.z);
+  const uint32_t pow2 = __float_as_uint(a2.w);
+  gU32* px = (gU32*)(((unsigned long long)__float_as_uint(a3.y) << 32) | (unsigned long long)__float_as_uint(a3.x));
+  const float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
+  const float x0 = floorf(x), y0 = floorf(y);
+  fx = x - x0;
+  fy = y - y0;
+  const int ix0 = wrapT((int)x0, tw, (pow2 & kTexPow2W) != 0u), iy0 = wrapT((int)y0, th, (pow2 & kTexPow2H) != 0u);
+  return px[(size_t)iy0 * tw + (size_t)ix0];
+}
 BD bool alphaTestFails(const SceneDev& S, uint32_t rec, float bu, float bv) {
   const float4* r = S.alphaRecs + (size_t)rec * 4;
   const float4 a0 = r[0], a1 = r[1], a2 = r[2], a3 = r[3];
@@ -105,15 +130,10 @@ BD bool alphaTestFails(const SceneDev& S, uint32_t rec, float bu, float bv) {
     v += a0.w * bu;
     u += a1.x * bv;
     v += a1.y * bv;
-    const int tw = (int)__float_as_uint(a2.y), th = (int)__float_as_uint(a2.z);
-    const uint8_t* px = reinterpret_cast<const uint8_t*>(((unsigned long long)__float_as_uint(a3.y) << 32) | (unsigned long long)__float_as_uint(a3.x));
-    const float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
-    const float x0 = floorf(x), y0 = floorf(y);
-    const float fx = x - x0, fy = y - y0;
-    const int ix0 = wrapi((int)x0, tw), iy0 = wrapi((int)y0, th);
-    const int ix1 = wrapi(ix0 + 1, tw), iy1 = wrapi(iy0 + 1, th);
-    const float t00 = (float)px[((size_t)iy0 * tw + (size_t)ix0) * 4 + 3] / 255.0f, t10 = (float)px[((size_t)iy0 * tw + (size_t)ix1) * 4 + 3] / 255.0f;
-    const float t01 = (float)px[((size_t)iy1 * tw + (size_t)ix0) * 4 + 3] / 255.0f, t11 = (float)px[((size_t)iy1 * tw + (size_t)ix1) * 4 + 3] / 255.0f;
+    float fx, fy;
+    const uint32_t q = alphaQuad(a2, a3, u, v, fx, fy);
+    const float t00 = (float)(q & 0xffu) / 255.0f, t10 = (float)((q >> 8) & 0xffu) / 255.0f;
+    const float t01 = (float)((q >> 16) & 0xffu) / 255.0f, t11 = (float)(q >> 24) / 255.0f;
     const float top = t00 + (t10 - t00) * fx, bot = t01 + (t11 - t01) * fx;
     alpha = top + (bot - top) * fy;
   }
@@ -136,18 +156,11 @@ BD void alphaTexels(const AlphaIn& r, float bu, float bv, bool run, float& fx, f
   v += r.a0.w * bu;
   u += r.a1.x * bv;
   v += r.a1.y * bv;
-  const int tw = (int)__float_as_uint(r.a2.y), th = (int)__float_as_uint(r.a2.z);
-  const uint8_t* px = reinterpret_cast<const uint8_t*>(((unsigned long long)__float_as_uint(r.a3.y) << 32) | (unsigned long long)__float_as_uint(r.a3.x));
-  const float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
-  const float x0 = floorf(x), y0 = floorf(y);
-  fx = x - x0;
-  fy = y - y0;
-  const int ix0 = wrapi((int)x0, tw), iy0 = wrapi((int)y0, th);
-  const int ix1 = wrapi(ix0 + 1, tw), iy1 = wrapi(iy0 + 1, th);
-  t00 = (float)px[((size_t)iy0 * tw + (size_t)ix0) * 4 + 3];
-  t10 = (float)px[((size_t)iy0 * tw + (size_t)ix1) * 4 + 3];
-  t01 = (float)px[((size_t)iy1 * tw + (size_t)ix0) * 4 + 3];
-  t11 = (float)px[((size_t)iy1 * tw + (size_t)ix1) * 4 + 3];
+  const uint32_t q = alphaQuad(r.a2, r.a3, u, v, fx, fy);
+  t00 = (float)(q & 0xffu);
+  t10 = (float)((q >> 8) & 0xffu);
+  t01 = (float)((q >> 16) & 0xffu);
+  t11 = (float)(q >> 24);
 }
 BD bool alphaVerdict(const AlphaIn& r, float fx, float fy, float t00, float t10, float t01, float t11) {
   const uint32_t mode = __float_as_uint(r.a2.x);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/bdpt.h"
+#include "texture_planes.h"
 
 namespace bdpt {
 
@@ -55,9 +56,10 @@ constexpr int NF4 = 6;  // float4s per stored vertex record (96 B; layout in ker
 enum : int { PATH_EYE = 0, PATH_LIGHT = 1 };
 enum : int { RAY_TERMS = 0, RAY_PAIRS = 1 };
 
+// pow2: texPow2Flags (texture_planes.h: bit 0 set when w is a power of two, bit 1 when h is; wrapT wraps by mask there)
 struct TexDev {
   const uint8_t* px;
-  uint32_t w, h, srgb, pad;
+  uint32_t w, h, srgb, pow2;
 };
 
 struct SceneConst {
@@ -237,7 +239,8 @@ void launchBmfr(const BmfrDev& A, uint32_t flags, hipStream_t st);
 // launchers (kernels.hip)
 void launchGBuffer(const SceneDev& S, const GBufferDev& G, hipStream_t st);
 // SceneDev::alphaRecs (4 float4 per non-opaque triangle, in the order of alphaTris) from the shading records and material tables
-void launchAlphaRecs(const SceneDev& S, const uint32_t* alphaTris, uint32_t n, float4* out, hipStream_t st);
+// quadByTex: per texture id the device address of its alpha-quad plane (texture_planes.h alphaQuadRows), 0 where it has none
+void launchAlphaRecs(const SceneDev& S, const uint32_t* alphaTris, uint32_t n, const unsigned long long* quadByTex, float4* out, hipStream_t st);
 // FrameDev::hintPix of EVERY frame pixel (G.Np = W * H; nothing else is written): partial-tile contexts, on a camera change
 void launchHintFill(const SceneDev& S, const GBufferDev& G, hipStream_t st);
 // SceneDev::lightMap of every point / spot light of the scene (res texels per face edge), closest-hit rays from the light

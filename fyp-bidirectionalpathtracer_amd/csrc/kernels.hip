@@ -1732,10 +1732,11 @@ void launchGBuffer(const SceneDev& S, const GBufferDev& G, hipStream_t st) {
 }
 
 // The 64-byte alpha-test record of every non-opaque triangle (device_scene.hpp alphaTestFails: the triangle's three texture
-// coordinates, the material's threshold and constant alpha, how its base colour is given, the texture's size and address)
-// from what is on the device already — the triangle's shading record and the material tables — instead of 64 B per
-// triangle built by the host and copied over (0.32 GB for the 10 M-triangle courtyard).
-__global__ void alpha_recs_kernel(SceneDev S, const uint32_t* __restrict__ alphaTris, uint32_t n, float4* __restrict__ out) {
+// coordinates, the material's threshold and constant alpha, how its base colour is given, the texture's size and its
+// alpha-quad plane, quadByTex[texture id]) from what is on the device already — the triangle's shading record and the
+// material tables — instead of 64 B per triangle built by the host and copied over (0.32 GB for the 10 M-triangle courtyard).
+__global__ void alpha_recs_kernel(SceneDev S, const uint32_t* __restrict__ alphaTris, uint32_t n, const unsigned long long* __restrict__ quadByTex,
+                                  float4* __restrict__ out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t t = alphaTris[i];
@@ -1744,28 +1745,29 @@ __global__ void alpha_recs_kernel(SceneDev S, const uint32_t* __restrict__ alpha
   const uint32_t mid = __float_as_uint(m6.x);
   const bdpt_material& m = S.materials[mid];
   const uint32_t type = BDPT_FLAG_DIFFUSE_TYPE(m.flags);
-  uint32_t mode = 0, tw = 0, th = 0;
+  uint32_t mode = 0, tw = 0, th = 0, pow2 = 0;
   unsigned long long px = 0;
   if (type == BDPT_CHANNEL_UNUSED) {
     mode = 0;
-  } else if (type == BDPT_CHANNEL_CONST || m.texBaseColor < 0) {
+  } else if (!alphaSamplesTexture(type, m.texBaseColor)) {
     mode = 1;
-  } else {
+  } else {  // api.cpp made an alpha-quad plane for this texture under the same alphaSamplesTexture rule
     mode = 2;
     const TexDev td = S.matTex[(size_t)mid * 4];
     tw = td.w;
     th = td.h;
-    px = (unsigned long long)reinterpret_cast<uintptr_t>(td.px);
+    pow2 = td.pow2;
+    px = quadByTex[m.texBaseColor];
   }
   float4* r = out + (size_t)i * 4;
   r[0] = make_float4(a1.z, a1.w, b1.z, b1.w);
   r[1] = make_float4(c1.z, c1.w, m.alphaThreshold, m.baseColor[3]);
-  r[2] = make_float4(__uint_as_float(mode), __uint_as_float(tw), __uint_as_float(th), 0.0f);
+  r[2] = make_float4(__uint_as_float(mode), __uint_as_float(tw), __uint_as_float(th), __uint_as_float(pow2));
   r[3] = make_float4(__uint_as_float((uint32_t)(px & 0xffffffffull)), __uint_as_float((uint32_t)(px >> 32)), 0.0f, 0.0f);
 }
-void launchAlphaRecs(const SceneDev& S, const uint32_t* alphaTris, uint32_t n, float4* out, hipStream_t st) {
+void launchAlphaRecs(const SceneDev& S, const uint32_t* alphaTris, uint32_t n, const unsigned long long* quadByTex, float4* out, hipStream_t st) {
   if (!n) return;
-  hipLaunchKernelGGL(alpha_recs_kernel, dim3((n + 255) / 256), dim3(256), 0, st, S, alphaTris, n, out);
+  hipLaunchKernelGGL(alpha_recs_kernel, dim3((n + 255) / 256), dim3(256), 0, st, S, alphaTris, n, quadByTex, out);
 }
 
 void launchHintFill(const SceneDev& S, const GBufferDev& G, hipStream_t st) {  // G.Np = W * H, G.pix unused
