@@ -299,6 +299,145 @@ class Context:
         hits = out if out.dtype == torch.float32 else out.view(torch.float32)
         return hits[:, :3], hits.view(torch.int32)[:, 3]
 
+    # ---- surface queries (include/bdpt.h "Surface queries") ----
+    def camera_rays(self, gparams, width, height, out=None, stream=None):
+        """bdpt_camera_rays: the G-buffer pass's primary ray of every pixel of a width x height frame (pinhole or thin lens,
+        jitter and frameCount of `gparams`, a GBufferParams), as an (width * height, 8) float32 GPU tensor in the bdpt_ray
+        layout (origin xyz, tmin 0, direction xyz, tmax 1e38), row x + y * width.  `out` takes it preallocated (contiguous,
+        float32, on this context's device).  Enqueued on `stream` without a synchronise."""
+        import torch
+        if not isinstance(gparams, abi.GBufferParams):
+            raise BdptError("camera_rays: gparams must be a GBufferParams")
+        w, h = int(width), int(height)
+        if w <= 0 or h <= 0 or w * h >= 2**32:
+            raise BdptError(f"camera_rays: bad frame size {w} x {h}")
+        n = w * h
+        if out is None:
+            if not torch.cuda.is_available():
+                raise BdptError("camera_rays: no GPU visible to torch (the queries have no CPU fallback)")
+            out = torch.empty((n, 8), dtype=torch.float32, device=torch.device("cuda", self.device))
+        else:
+            self._check_gpu(out, "camera_rays", "out", (n, 8), (torch.float32,))
+        self._check(self._lib.bdpt_camera_rays(self._h, C.byref(gparams), w, h, out.data_ptr(), stream), "bdpt_camera_rays")
+        return out
+
+    def shade_hits(self, rays, hits, normal_map=True, out=None, count=None, stream=None):
+        """bdpt_shade_hits: the pass's shading at each hit, seen from its ray's origin.  `rays` (N, 8) float32 (bdpt_ray),
+        `hits` (N, 4) float32 or int32 (bdpt_hit: t, u, v, prim bits — trace_rays' `out` buffer).  normal_map=True shades as
+        the G-buffer pass does its primary hit, False as the walk does (no normal map).  Returns (N, 24) float32 in the
+        bdpt_surface layout, columns
+            0-2 posW, 3 dist, 4-6 N, 7 linearRoughness, 8-10 V, 11 IoR, 12-14 diffuse, 15 opacity,
+            16-18 specular, 19 material (uint32 bits), 20-22 emissive, 23 prim (int32 bits, -1 = miss);
+        read material and prim through .view(torch.int32) (numpy: .view(np.int32)).  GPU tensors, `out` and `count` as
+        for trace_rays; host arrays are copied, shaded, synchronised and returned as numpy."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.float32, torch.int32)
+        flags = abi.SHADE_NORMAL_MAP if normal_map else 0
+
+        def run(ptrs, n, cnt, res):
+            d = abi.ShadeDesc()
+            d.rays, d.hits, d.numHits, d.flags, d.numHitsDevice, d.surfaces = ptrs[0], ptrs[1], n, flags, cnt, res
+            return self._lib.bdpt_shade_hits(self._h, C.byref(d), stream)
+
+        return self._surface_query("shade_hits", [("rays", rays, 8, f32), ("hits", hits, 4, i32)], (24, i32), run, out, count)
+
+    def sample_bsdf(self, surfaces, seeds, mat_index=0, from_lobe=False, out=None, count=None, stream=None):
+        """bdpt_bsdf_query(SAMPLE): sampleBRDF at each (N, 24) bdpt_surface record (shade_hits' output) with its seed
+        ((N,) uint32 or int32 RNG states, read by value).  mat_index 0 GGX, 1 Lambertian; from_lobe sets
+        BDPT_PARAM_SPECULAR_FROM_LOBE.  Returns (N, 8) float32 in the bdpt_bsdf_sample layout: 0-2 direction, 3 pdf,
+        4-6 weight, 7 specular (uint32 bits, 1 = the specular lobe).  A miss record gives zeros."""
+        import torch
+        i32 = (torch.float32, torch.int32)
+        mat, flags = self._bsdf_mode("sample_bsdf", mat_index, from_lobe)
+
+        def run(ptrs, n, cnt, res):
+            d = abi.BsdfDesc()
+            d.surfaces, d.num, d.mode, d.numDevice, d.matIndex, d.flags = ptrs[0], n, abi.BSDF_SAMPLE, cnt, mat, flags
+            d.seeds, d.samples = ptrs[1], res
+            return self._lib.bdpt_bsdf_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("sample_bsdf", [("surfaces", surfaces, 24, i32), ("seeds", seeds, None, (torch.int32, torch.uint32))],
+                                   (8, i32), run, out, count)
+
+    def eval_bsdf(self, surfaces, dirs, mat_index=0, out=None, count=None, stream=None):
+        """bdpt_bsdf_query(EVAL): evalBRDF at each (N, 24) bdpt_surface record toward dirs (N, 4) float32: L.xyz and w,
+        w != 0 = evaluate the specular lobe (what sample_bsdf's column 7 says).  Returns (N, 4) float32: f.xyz, 0."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.float32, torch.int32)
+        mat, _ = self._bsdf_mode("eval_bsdf", mat_index, False)
+
+        def run(ptrs, n, cnt, res):
+            d = abi.BsdfDesc()
+            d.surfaces, d.num, d.mode, d.numDevice, d.matIndex, d.flags = ptrs[0], n, abi.BSDF_EVAL, cnt, mat, 0
+            d.dirs, d.values = ptrs[1], res
+            return self._lib.bdpt_bsdf_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("eval_bsdf", [("surfaces", surfaces, 24, i32), ("dirs", dirs, 4, f32)], (4, f32), run, out, count)
+
+    @staticmethod
+    def _bsdf_mode(what, mat_index, from_lobe):
+        if mat_index not in (0, 1) or isinstance(mat_index, bool):
+            raise BdptError(f"{what}: mat_index must be 0 (GGX) or 1 (Lambertian), not {mat_index!r}")
+        return int(mat_index), abi.PARAM_SPECULAR_FROM_LOBE if from_lobe else 0
+
+    def _check_gpu(self, t, what, name, shape, dtypes):
+        if not getattr(t, "is_cuda", False) or t.device.index != self.device:
+            raise BdptError(f"{what}: {name} must be a GPU tensor on cuda:{self.device}, not on {getattr(t, 'device', type(t))}")
+        if not t.is_contiguous():
+            raise BdptError(f"{what}: {name} must be contiguous")
+        if t.dtype not in dtypes or tuple(t.shape) != tuple(shape):
+            raise BdptError(f"{what}: {name} must be {tuple(shape)} {'/'.join(str(d) for d in dtypes)}, not "
+                            f"{tuple(t.shape)} {t.dtype}")
+
+    def _surface_query(self, what, inputs, out_spec, run, out, count):
+        """The shared path of the per-item queries.  inputs: (name, value, columns or None for 1-D, allowed torch dtypes),
+        all with one row per item; out_spec: (columns, allowed dtypes; the first is allocated)."""
+        import numpy as np
+        import torch
+        on_gpu = [getattr(v, "is_cuda", False) for _, v, _, _ in inputs]
+        if all(on_gpu):
+            n = int(inputs[0][1].shape[0]) if inputs[0][1].dim() >= 1 else -1
+            if n < 0 or n >= 2**32:
+                raise BdptError(f"{what}: bad item count")
+            for name, v, cols, dts in inputs:
+                self._check_gpu(v, what, name, (n,) if cols is None else (n, cols), dts)
+            if count is not None:
+                self._check_gpu(count, what, "count", (1,), (torch.int32, torch.uint32))
+            if out is None:
+                out = torch.empty((n, out_spec[0]), dtype=out_spec[1][0], device=inputs[0][1].device)
+            else:
+                self._check_gpu(out, what, "out", (n, out_spec[0]), out_spec[1])
+            self._check(run([v.data_ptr() for _, v, _, _ in inputs], n, None if count is None else count.data_ptr(), out.data_ptr()),
+                        "bdpt_" + ("bsdf_query" if "bsdf" in what else what))
+            return out if out.dtype == torch.float32 else out.view(torch.float32)
+        if any(on_gpu):
+            raise BdptError(f"{what}: the inputs must all be GPU tensors or all host arrays")
+        if out is not None or count is not None:
+            raise BdptError(f"{what}: out= and count= go with GPU tensor inputs")
+        np_of = {torch.float32: np.float32, torch.int32: np.int32, torch.uint32: np.uint32}
+        host = []
+        for name, v, cols, dts in inputs:
+            if hasattr(v, "is_cuda") and getattr(v, "device", None) is not None and v.device.type != "cpu":
+                raise BdptError(f"{what}: {name} on {v.device}: neither a GPU tensor nor host memory")
+            a = v.detach().numpy() if hasattr(v, "detach") else v
+            ok_types = {np.dtype(np_of[d]) for d in dts}
+            if not isinstance(a, np.ndarray) or a.dtype not in ok_types or a.shape[1:] != (() if cols is None else (cols,)) \
+                    or a.ndim != (1 if cols is None else 2):
+                raise BdptError(f"{what}: {name} must be {'(N,)' if cols is None else f'(N, {cols})'} "
+                                f"{'/'.join(str(np.dtype(np_of[d])) for d in dts)}")
+            host.append(np.ascontiguousarray(a))
+        if len({a.shape[0] for a in host}) != 1:
+            raise BdptError(f"{what}: the inputs differ in length")
+        if not torch.cuda.is_available():
+            raise BdptError(f"{what}: no GPU visible to torch (the queries have no CPU fallback)")
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            devs = [_host_to_device(a, dev) for a in host]
+            torch.cuda.synchronize(dev)  # the copies are done before the library's stream reads them
+            res = self._surface_query(what, [(nm, d, c, t) for (nm, _, c, t), d in zip(inputs, devs)], out_spec, run, None, None)
+            torch.cuda.synchronize(dev)
+        return res.cpu().numpy()
+
     def set_lights(self, lights, stream=None):
         """bdpt_set_lights: the scene's lights moved (a sequence of abi.Light, as many as the scene has)."""
         arr = (abi.Light * len(lights))(*lights)
@@ -695,6 +834,33 @@ class FramePipeline:
         res = self.ctx.trace_rays(rays, mode, out, count, self._stream_ptr())
         outs = res if isinstance(res, tuple) else (res,)
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (rays, count) + outs)
+        return res
+
+    def camera_rays(self, out=None):
+        """Context.camera_rays with this pipeline's size and gbuffer_params() (the G-buffer pass's next frame: jitter and
+        frame counter), on the pipeline's stream."""
+        res = self.ctx.camera_rays(self.gbuffer_params(), self.W, self.H, out, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (res,))
+        return res
+
+    def shade_hits(self, rays, hits, normal_map=True, out=None, count=None):
+        """Context.shade_hits on this pipeline's stream, ordered after its frames."""
+        res = self.ctx.shade_hits(rays, hits, normal_map, out, count, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (rays, hits, count, res))
+        return res
+
+    def sample_bsdf(self, surfaces, seeds, from_lobe=None, out=None, count=None):
+        """Context.sample_bsdf with the pipeline's BSDF (mat_index; from_lobe defaults to its SPECULAR_FROM_LOBE flag)."""
+        if from_lobe is None:
+            from_lobe = (self.flags & abi.PARAM_SPECULAR_FROM_LOBE) != 0
+        res = self.ctx.sample_bsdf(surfaces, seeds, self.mat_index, from_lobe, out, count, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (surfaces, seeds, count, res))
+        return res
+
+    def eval_bsdf(self, surfaces, dirs, out=None, count=None):
+        """Context.eval_bsdf with the pipeline's BSDF (mat_index) on its stream."""
+        res = self.ctx.eval_bsdf(surfaces, dirs, self.mat_index, out, count, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (surfaces, dirs, count, res))
         return res
 
     def set_lights(self, lights):

@@ -31,6 +31,8 @@ PREPARE_LIGHT_GROUPS = 8
 MEMORY_HOST, MEMORY_DEVICE = 0, 1
 UPDATE_KEEP_LIGHT_MAPS = 1
 TRACE_CLOSEST, TRACE_CLOSEST_CULL_BACK, TRACE_ANY = 0, 1, 2
+SHADE_NORMAL_MAP = 1
+BSDF_SAMPLE, BSDF_EVAL = 0, 1
 
 
 class Material(C.Structure):
@@ -160,6 +162,27 @@ class TraceDesc(C.Structure):
                 ("hits", C.c_void_p), ("visible", C.c_void_p)]
 
 
+class Surface(C.Structure):
+    _fields_ = [("posW", C.c_float * 3), ("dist", C.c_float), ("N", C.c_float * 3), ("linearRoughness", C.c_float),
+                ("V", C.c_float * 3), ("IoR", C.c_float), ("diffuse", C.c_float * 3), ("opacity", C.c_float),
+                ("specular", C.c_float * 3), ("material", C.c_uint32), ("emissive", C.c_float * 3), ("prim", C.c_int32)]
+
+
+class ShadeDesc(C.Structure):
+    _fields_ = [("rays", C.c_void_p), ("hits", C.c_void_p), ("numHits", C.c_uint32), ("flags", C.c_uint32),
+                ("numHitsDevice", C.c_void_p), ("surfaces", C.c_void_p)]
+
+
+class BsdfSample(C.Structure):
+    _fields_ = [("dir", C.c_float * 3), ("pdf", C.c_float), ("weight", C.c_float * 3), ("specular", C.c_uint32)]
+
+
+class BsdfDesc(C.Structure):
+    _fields_ = [("surfaces", C.c_void_p), ("num", C.c_uint32), ("mode", C.c_uint32), ("numDevice", C.c_void_p),
+                ("matIndex", C.c_uint32), ("flags", C.c_uint32), ("seeds", C.c_void_p), ("samples", C.c_void_p),
+                ("dirs", C.c_void_p), ("values", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 PROTOTYPES = {
     "bdpt_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -178,6 +201,9 @@ PROTOTYPES = {
     "bdpt_set_lights": (C.c_int, [C.c_void_p, C.POINTER(Light), C.c_uint32, C.c_void_p]),
     "bdpt_get_refit_info": (C.c_int, [C.c_void_p, C.POINTER(RefitInfo)]),
     "bdpt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(TraceDesc), C.c_void_p]),
+    "bdpt_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(GBufferParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bdpt_shade_hits": (C.c_int, [C.c_void_p, C.POINTER(ShadeDesc), C.c_void_p]),
+    "bdpt_bsdf_query": (C.c_int, [C.c_void_p, C.POINTER(BsdfDesc), C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),
     "bdpt_host_bvh_recs_hash": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -930,6 +930,84 @@ int bdpt_trace_rays(bdpt_ctx* c, const bdpt_trace_desc* d, void* stream) {
   return BDPT_OK;
 }
 
+static_assert(sizeof(bdpt_surface) == 96 && sizeof(bdpt_bsdf_sample) == 32,
+              "shade_hits_kernel writes a surface as six float4, bsdf_query_kernel a sample as two");
+namespace {
+bool aligned(const void* p, uintptr_t a) { return p && (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+}  // namespace
+
+int bdpt_camera_rays(bdpt_ctx* c, const bdpt_gbuffer_params* p, uint32_t width, uint32_t height, bdpt_ray* rays, void* stream) {
+  if (!c || !p) return BDPT_E_INVALID;
+  if (!c->haveCamera) {
+    fail(c, "camera_rays: no camera (bdpt_set_camera first)");
+    return BDPT_E_STATE;
+  }
+  if (!width || !height || (uint64_t)width * height >= (1ull << 32) || !aligned(rays, 16)) {
+    fail(c, "camera_rays: width and height must be > 0 with width * height < 2^32, rays 16-byte aligned");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  launchCameraRays(c->cam, *p, width, height, reinterpret_cast<float4*>(rays), st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
+int bdpt_shade_hits(bdpt_ctx* c, const bdpt_shade_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "shade_hits: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (d->flags & ~BDPT_SHADE_NORMAL_MAP) {
+    fail(c, "shade_hits: unknown flags");
+    return BDPT_E_INVALID;
+  }
+  if (!d->numHits) return BDPT_OK;
+  if (!aligned(d->rays, 16) || !aligned(d->hits, 16) || !aligned(d->surfaces, 16) || (d->numHitsDevice && !aligned(d->numHitsDevice, 4))) {
+    fail(c, "shade_hits: rays, hits or surfaces missing or not aligned (16 bytes; numHitsDevice 4)");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  launchShadeHits(c->S, c->numTriangles, reinterpret_cast<const float4*>(d->rays), reinterpret_cast<const float4*>(d->hits), d->numHits,
+                  d->numHitsDevice, (d->flags & BDPT_SHADE_NORMAL_MAP) != 0, reinterpret_cast<float4*>(d->surfaces), st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
+int bdpt_bsdf_query(bdpt_ctx* c, const bdpt_bsdf_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "bsdf_query: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (d->mode > BDPT_BSDF_EVAL || d->matIndex > 1 || (d->flags & ~BDPT_PARAM_SPECULAR_FROM_LOBE)) {
+    fail(c, "bsdf_query: unknown mode or flags, or matIndex > 1");
+    return BDPT_E_INVALID;
+  }
+  if (!d->num) return BDPT_OK;
+  const bool eval = d->mode == BDPT_BSDF_EVAL;
+  if (!aligned(d->surfaces, 16) || (d->numDevice && !aligned(d->numDevice, 4)) ||
+      (eval ? (!aligned(d->dirs, 16) || !aligned(d->values, 16)) : (!aligned(d->seeds, 4) || !aligned(d->samples, 16)))) {
+    fail(c, "bsdf_query: surfaces, seeds, samples, dirs or values missing or not aligned (16 bytes; seeds and numDevice 4)");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  float4* out = eval ? reinterpret_cast<float4*>(d->values) : reinterpret_cast<float4*>(d->samples);
+  launchBsdfQuery(reinterpret_cast<const float4*>(d->surfaces), d->num, d->numDevice, eval, d->matIndex == 0,
+                  (d->flags & BDPT_PARAM_SPECULAR_FROM_LOBE) != 0, d->seeds, reinterpret_cast<const float4*>(d->dirs), out, st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
 int bdpt_get_refit_info(bdpt_ctx* c, bdpt_refit_info* out) {
   if (!c || !out) return BDPT_E_INVALID;
   if (!c->haveScene) return BDPT_E_STATE;

@@ -285,5 +285,29 @@ BD Shading shadeHit(const SceneDev& S, uint32_t prim, float bu, float bv, f3 cam
   return sd;
 }
 
+// The primary ray of pixel (x, y) of a W x H frame: GBufferRayGen's pinhole / thin-lens camera
+// (CP lightProbeGBuffer.rt.hlsl:110-135).  gbuffer_kernel and camera_rays_kernel (bdpt_camera_rays) both call it, so a
+// caller's camera rays are the G-buffer pass's bit for bit.
+BD void primaryRay(const bdpt_camera& cam, const bdpt_gbuffer_params& gp, uint32_t x, uint32_t y, uint32_t W, uint32_t H, f3& o, f3& d) {
+  const f3 U = ld3(cam.cameraU), V = ld3(cam.cameraV), Wv = ld3(cam.cameraW), camPos = ld3(cam.posW);
+  float pcx = ((float)x + gp.pixelJitter[0]) / (float)W;
+  float pcy = ((float)y + gp.pixelJitter[1]) / (float)H;
+  float ndx = 2.0f * pcx + -1.0f;
+  float ndy = -2.0f * pcy + 1.0f;
+  f3 rayDir = U * ndx + V * ndy + Wv;
+  rayDir = rayDir / length(Wv);
+  f3 focalPoint = camPos + rayDir * gp.focalLen;
+  uint32_t randSeed = initRand(x + y * W, gp.frameCount);
+  float r0 = nextRand(randSeed);
+  float r1 = nextRand(randSeed);
+  float sn, cs;
+  det_sincos2pi(r0, sn, cs);
+  float lr = gp.lensRadius * r1;
+  float lu = cs * lr, lv = sn * lr;
+  f3 randomOrig = camPos + normalize(U) * lu + normalize(V) * lv;
+  o = gp.useThinLens ? randomOrig : camPos;
+  d = normalize(gp.useThinLens ? (focalPoint - randomOrig) : rayDir);
+}
+
 #undef BD
 }  // namespace bdpt

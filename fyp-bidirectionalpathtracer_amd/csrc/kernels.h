@@ -272,6 +272,13 @@ void launchTraceShadow(const SceneDev& S, const FrameDev& F, const PathBuf& P, i
 // it zero.
 void launchTraceRays(const SceneDev& S, const float4* rays, uint32_t cap, const uint32_t* count, unsigned long long* cursor, int mode,
                      float4* hits, uint8_t* vis, LaunchGrids& G, int numCUs, hipStream_t st);
+// surface_query.hip: bdpt_camera_rays (W * H rays), bdpt_shade_hits (six float4 per hit), bdpt_bsdf_query (SAMPLE: two float4
+// per item, EVAL: one); count (optional device word) caps cap
+void launchCameraRays(const bdpt_camera& cam, const bdpt_gbuffer_params& gp, uint32_t W, uint32_t H, float4* rays, hipStream_t st);
+void launchShadeHits(const SceneDev& S, uint32_t numTris, const float4* rays, const float4* hits, uint32_t cap, const uint32_t* count,
+                     bool normalMap, float4* out, hipStream_t st);
+void launchBsdfQuery(const float4* surf, uint32_t cap, const uint32_t* count, bool eval, bool ggx, bool fromLobe, const uint32_t* seeds,
+                     const float4* dirs, float4* out, hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,

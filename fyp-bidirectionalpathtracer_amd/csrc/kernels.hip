@@ -188,24 +188,9 @@ __global__ __launch_bounds__(kWave) void gbuffer_kernel(SceneDev S, GBufferDev G
   const size_t pix = HINT_ONLY ? (size_t)p : (size_t)G.pix[p];
   const uint32_t y = (uint32_t)(pix / G.W), x = (uint32_t)(pix - (size_t)y * G.W);
 
-  const f3 U = ld3(G.cam.cameraU), V = ld3(G.cam.cameraV), Wv = ld3(G.cam.cameraW), camPos = ld3(G.cam.posW);
-  float pcx = ((float)x + G.gp.pixelJitter[0]) / (float)G.W;
-  float pcy = ((float)y + G.gp.pixelJitter[1]) / (float)G.H;
-  float ndx = 2.0f * pcx + -1.0f;
-  float ndy = -2.0f * pcy + 1.0f;
-  f3 rayDir = U * ndx + V * ndy + Wv;
-  rayDir = rayDir / length(Wv);
-  f3 focalPoint = camPos + rayDir * G.gp.focalLen;
-  uint32_t randSeed = initRand(x + y * G.W, G.gp.frameCount);
-  float r0 = nextRand(randSeed);
-  float r1 = nextRand(randSeed);
-  float sn, cs;
-  det_sincos2pi(r0, sn, cs);
-  float lr = G.gp.lensRadius * r1;
-  float lu = cs * lr, lv = sn * lr;
-  f3 randomOrig = camPos + normalize(U) * lu + normalize(V) * lv;
-  f3 o = G.gp.useThinLens ? randomOrig : camPos;
-  f3 d = normalize(G.gp.useThinLens ? (focalPoint - randomOrig) : rayDir);
+  const f3 camPos = ld3(G.cam.posW);
+  f3 o, d;
+  primaryRay(G.cam, G.gp, x, y, G.W, G.H, o, d);
 
   uint32_t nNodes = 0, nTris = 0;
   Hit h = traverse<1, COUNT>(S, o, d, 0.0f, 1e+38f, s_stack + threadIdx.x, nNodes, nTris);

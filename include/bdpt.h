@@ -19,6 +19,10 @@
  *   bdpt_trace_rays                 TraceRay from a caller's own ray-generation shader
  *                                   (CommonPasses/Data/CommonPasses/aoTracing.rt.hlsl:112,
  *                                    lambertianPlusShadows.rt.hlsl:62, simpleDiffuseGI.rt.hlsl:127): ray queries
+ *   bdpt_camera_rays / bdpt_shade_hits / bdpt_bsdf_query
+ *                                   GBufferRayGen's camera, the hit shading (getVertexAttributes,
+ *                                   simplePrepareShadingData) and sampleBRDF / evalBRDF for a caller's own
+ *                                   integrator: surface queries
  *   bdpt_set_environment            the "EnvironmentMap" channel BDPTPass requests (BDPTPass.cpp:29; bound by no shader
  *                                   of the pass in the reference): read only with BDPT_PARAM_ENV_ON_MISS
  *   bdpt_bvh_build_check / _hash, bdpt_host_bvh_*
@@ -431,6 +435,89 @@ typedef struct bdpt_trace_desc {
   uint8_t* visible;              /* BDPT_TRACE_ANY: device, one byte per ray, 1 = unoccluded (ignored otherwise) */
 } bdpt_trace_desc;
 int bdpt_trace_rays(bdpt_ctx* ctx, const bdpt_trace_desc* desc, void* stream);
+
+/* ---- Surface queries: what the pass computes at a hit, for a caller's own integrator ----
+ * bdpt_camera_rays        GBufferRayGen's primary rays (CP lightProbeGBuffer.rt.hlsl:110-135)
+ * bdpt_shade_hits         getVertexAttributes + simplePrepareShadingData (+ applyNormalMap) at a hit: what the G-buffer
+ *                         pass and the walk shade (Falcor ShadingUtils/Raytracing.slang:60-106, BDPT/BDPTUtils.hlsli:2-52)
+ * bdpt_bsdf_query         sampleBRDF / evalBRDF (BDPT/MaterialUtils.hlsli:105-141, 186-329) on shaded records
+ * With bdpt_trace_rays a caller runs camera rays -> trace -> shade -> sample -> trace on the device with the pass's own
+ * arithmetic: each call runs the device function the pass runs, bit for bit (DESIGN.md "Surface queries").
+ * Ordering, capture and counters: as bdpt_trace_rays — enqueued on `stream` behind the context's previous call; no
+ * allocation and no synchronise (one kernel node in a captured graph); bdpt_get_counters and bdpt_get_stage_times are left
+ * alone.  The shading calls see the scene as of the last bdpt_update_geometry enqueued before them.  num == 0 returns
+ * BDPT_OK and does nothing.  Errors are found before anything is enqueued: no camera (bdpt_camera_rays) or no scene
+ * (bdpt_shade_hits, bdpt_bsdf_query) BDPT_E_STATE; a NULL context or desc, a missing or misaligned buffer, unknown flags
+ * or mode, matIndex > 1, a width or height of 0 or width * height >= 2^32 BDPT_E_INVALID.
+ *
+ * bdpt_camera_rays: the G-buffer pass's primary ray of every pixel of a width x height frame, in frame order
+ * (rays[x + y * width]): pinhole, or thin lens with p->useThinLens, pixelJitter and frameCount as in p (the env fields are
+ * ignored); tmin 0, tmax 1e38.  Always the whole frame (the context's size, tile and stripes play no part). */
+int bdpt_camera_rays(bdpt_ctx* ctx, const bdpt_gbuffer_params* p, uint32_t width, uint32_t height, bdpt_ray* rays, void* stream);
+
+/* bdpt_shade_hits: one record per hit.  hits[i] is shaded as seen from rays[i]'s origin (only the origin is read): the
+ * interpolated position and normal, the textured material and, with BDPT_SHADE_NORMAL_MAP, the normal map — the
+ * G-buffer pass's primary-hit shading (shadeHit<true>); without it the walk's (shadeHit<false>).  The ray origin takes the
+ * place of the camera position, as the walk passes WorldRayOrigin(): with pinhole camera rays the records equal the
+ * G-buffer channels before their half rounding.  The BSDF's roughness is linearRoughness * linearRoughness.  A miss
+ * (prim < 0), or a prim that is not a triangle of the scene, writes prim -1, material 0xffffffff and every float 0.  With
+ * numHitsDevice set, hits at or beyond min(*numHitsDevice, numHits) are neither read nor written. */
+typedef struct bdpt_surface {
+  float posW[3];
+  float dist;             /* length(posW - ray origin) */
+  float N[3];             /* shading normal, flipped toward the origin for double-sided materials */
+  float linearRoughness;
+  float V[3];             /* normalize(ray origin - posW) */
+  float IoR;
+  float diffuse[3];
+  float opacity;
+  float specular[3];
+  uint32_t material;      /* material index, 0xffffffff on a miss */
+  float emissive[3];
+  int32_t prim;           /* input triangle index, -1 = miss */
+} bdpt_surface;           /* 96 bytes: six float4 */
+#define BDPT_SHADE_NORMAL_MAP 1u
+typedef struct bdpt_shade_desc {
+  const bdpt_ray* rays;          /* device, 16-byte aligned, numHits records: only the origin is read */
+  const bdpt_hit* hits;          /* device, 16-byte aligned, numHits records (e.g. bdpt_trace_rays' output) */
+  uint32_t numHits;              /* hits to shade; the capacity when numHitsDevice is set */
+  uint32_t flags;                /* BDPT_SHADE_* */
+  const uint32_t* numHitsDevice; /* optional device word: shade min(*numHitsDevice, numHits) hits */
+  bdpt_surface* surfaces;        /* device, 16-byte aligned, one per hit */
+} bdpt_shade_desc;
+int bdpt_shade_hits(bdpt_ctx* ctx, const bdpt_shade_desc* desc, void* stream);
+
+/* bdpt_bsdf_query: the pass's BSDF at shaded records (read: N, V, diffuse, specular, linearRoughness, prim), the GGX model
+ * (matIndex 0) or the Lambertian one (1), as bdpt_params::matIndex selects for the walk.
+ *   BDPT_BSDF_SAMPLE  sampleBRDF(seeds[i], N, N, V, ...): the sampled direction, its pdf, the weight f * cos / pdf and
+ *                     whether the lobe counts as specular (flags BDPT_PARAM_SPECULAR_FROM_LOBE as for the walk; without
+ *                     it never).  The seed is read by value and not advanced.  pdf 0 with
+ *                     a zero weight where the sample lies below the surface.
+ *   BDPT_BSDF_EVAL    evalBRDF(V, L, N, N, ...) toward dirs[i] = (L.xyz, w): w != 0 evaluates the specular lobe (the
+ *                     pass passes the flag its sample returned); values[i] = (f.xyz, 0).
+ * A record with prim < 0 gives all-zero outputs.  With numDevice set, items at or beyond min(*numDevice, num) are neither
+ * read nor written. */
+#define BDPT_BSDF_SAMPLE 0u
+#define BDPT_BSDF_EVAL 1u
+typedef struct bdpt_bsdf_sample {
+  float dir[3];
+  float pdf;
+  float weight[3];
+  uint32_t specular; /* 1: the sampled lobe counts as specular */
+} bdpt_bsdf_sample;  /* 32 bytes */
+typedef struct bdpt_bsdf_desc {
+  const bdpt_surface* surfaces; /* device, 16-byte aligned, num records */
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  uint32_t mode;                /* BDPT_BSDF_* */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  uint32_t matIndex;            /* 0 GGX, 1 Lambertian */
+  uint32_t flags;               /* BDPT_PARAM_SPECULAR_FROM_LOBE or 0 */
+  const uint32_t* seeds;        /* SAMPLE: device, one RNG state per item */
+  bdpt_bsdf_sample* samples;    /* SAMPLE: device, 16-byte aligned, one per item */
+  const float* dirs;            /* EVAL: device, 16-byte aligned, four floats per item */
+  float* values;                /* EVAL: device, 16-byte aligned, four floats per item */
+} bdpt_bsdf_desc;
+int bdpt_bsdf_query(bdpt_ctx* ctx, const bdpt_bsdf_desc* desc, void* stream);
 
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
