@@ -607,6 +607,27 @@ class Context:
                     "bdpt_test_bsdf")
         return out
 
+    def area_light_info(self):
+        """bdpt_get_area_light_info: the emitter table of PARAM_AREA_LIGHTS (made if need be; synchronises)."""
+        info = abi.AreaLightInfo()
+        self._check(self._lib.bdpt_get_area_light_info(self._h, C.byref(info)), "bdpt_get_area_light_info")
+        return info
+
+    def test_area_light_sample(self, mode, states, points=None):
+        """Test hook bdpt_test_area_light_sample: (n, 16) float32 records (include/bdpt.h lists the fields).
+        states: RNG states right after the selection draw; points: (n, 3) receiving points for mode 1."""
+        import numpy as np
+        states = np.ascontiguousarray(states, np.uint32).reshape(-1)
+        n = states.shape[0]
+        pts = None
+        if points is not None:
+            pts = np.ascontiguousarray(points, np.float32).reshape(n, 3)
+        out = np.zeros((n, 16), np.float32)
+        self._check(self._lib.bdpt_test_area_light_sample(self._h, mode, states.ctypes.data,
+                                                          None if pts is None else pts.ctypes.data, n, out.ctypes.data),
+                    "bdpt_test_area_light_sample")
+        return out
+
     def close(self):
         if self._h:
             self._lib.bdpt_destroy(self._h)

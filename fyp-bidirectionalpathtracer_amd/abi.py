@@ -24,10 +24,12 @@ PARAM_DEFER_TAIL = 256
 PARAM_KEEP_COUNTERS = 512
 PARAM_ENV_ON_MISS = 1024
 PARAM_EMISSIVE_HITS = 2048
+PARAM_AREA_LIGHTS = 4096
 PREPARE_PRIMARY = 1
 PREPARE_BMFR = 2
 PREPARE_REFIT = 4
 PREPARE_LIGHT_GROUPS = 8
+PREPARE_AREA_LIGHTS = 16
 MEMORY_HOST, MEMORY_DEVICE = 0, 1
 UPDATE_KEEP_LIGHT_MAPS = 1
 TRACE_CLOSEST, TRACE_CLOSEST_CULL_BACK, TRACE_ANY = 0, 1, 2
@@ -183,6 +185,10 @@ class BsdfDesc(C.Structure):
                 ("dirs", C.c_void_p), ("values", C.c_void_p)]
 
 
+class AreaLightInfo(C.Structure):
+    _fields_ = [("numEmitters", C.c_uint32), ("numTextured", C.c_uint32), ("totalWeight", C.c_float), ("reserved", C.c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol include/*.h declares
 PROTOTYPES = {
     "bdpt_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -253,6 +259,8 @@ PROTOTYPES = {
     "bdpt_test_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
     "bdpt_test_trace_shadow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdpt_test_bsdf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bdpt_get_area_light_info": (C.c_int, [C.c_void_p, C.POINTER(AreaLightInfo)]),
+    "bdpt_test_area_light_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bdpt_scene_create_cornell": (C.c_void_p, []),
     "bdpt_scene_create_atrium": (C.c_void_p, [C.c_uint32, C.c_uint32]),
     "bdpt_scene_create_atrium_uneven": (C.c_void_p, [C.c_uint32, C.c_uint32]),

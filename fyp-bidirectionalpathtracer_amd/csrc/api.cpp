@@ -131,6 +131,16 @@ struct bdpt_ctx {
   // so bdpt_set_scene and bdpt_resize drop them
   unsigned long long* groupSplat = nullptr;
   uint8_t* groupLightIdx = nullptr;
+  // area lights (BDPT_PARAM_AREA_LIGHTS): the emitter table, made by bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) or the first
+  // frame with the switch, in sceneAllocs (a new scene drops it); refreshed on the device by every bdpt_update_geometry.
+  // alphaTris: the non-opaque triangles in ascending order (their alpha-test records' order), kept for the table build.
+  const uint32_t* alphaTris = nullptr;
+  uint32_t numAlphaTris = 0;
+  bool areaReady = false;
+  AreaDev area{};
+  uint32_t areaTextured = 0;
+  float* areaBlockSum = nullptr;     // one float and one word per 64 emitters: the refresh's scratch
+  uint32_t* areaBlockLast = nullptr;
 };
 
 namespace {
@@ -431,6 +441,13 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
   c->refit = RefitDev{};
   c->numUpdates = 0;
   c->lightMaps = nullptr;
+  c->alphaTris = nullptr;
+  c->numAlphaTris = 0;
+  c->areaReady = false;
+  c->area = AreaDev{};
+  c->areaTextured = 0;
+  c->areaBlockSum = nullptr;
+  c->areaBlockLast = nullptr;
   for (float*& p : c->stage) p = nullptr;
   c->stageInFlight = false;
   c->S.stackOvf = c->stackOvf;
@@ -642,11 +659,14 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
       const uint32_t* dList = nullptr;
       const unsigned long long* dQuad = nullptr;
       std::vector<void*> scratch;
-      if ((rc = devUpload(c, scratch, &dList, alphaTris.data(), alphaTris.size())) ||
+      // (the list stays: the emitter table of area lights finds a triangle's alpha-test record in it)
+      if ((rc = devUpload(c, c->sceneAllocs, &dList, alphaTris.data(), alphaTris.size())) ||
           (rc = devUpload(c, scratch, &dQuad, quadByTex.data(), quadByTex.size()))) {
         freePool(scratch);
         return rc;
       }
+      c->alphaTris = dList;
+      c->numAlphaTris = (uint32_t)alphaTris.size();
       launchAlphaRecs(c->S, dList, (uint32_t)alphaTris.size(), dQuad, dAlpha, nullptr);
       const hipError_t e = hipDeviceSynchronize();
       freePool(scratch);
@@ -807,6 +827,61 @@ int stageHostArrays(bdpt_ctx* c, const void* const* arrays, const size_t* bytes,
 void retraceLightMaps(bdpt_ctx* c, hipStream_t st) {
   if (c->hints && c->lightMaps) launchLightMaps(c->S, c->lightMaps, c->S.lightMapRes, st);
 }
+
+// The emitter table of area lights (area_lights.hip); synchronises, so not while capturing.  Triangles the build dropped
+// (alpha clipping) are found through the refit plan's leaves, which is made for that when the scene has any.
+int ensureAreaLights(bdpt_ctx* c, hipStream_t st) {
+  if (c->areaReady) return BDPT_OK;
+  if (streamIsCapturing(st)) {
+    fail(c, "area lights: the emitter table needs bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) before stream capture");
+    return BDPT_E_STATE;
+  }
+  HIPCHK(c, hipDeviceSynchronize());
+  const uint32_t nt = c->numTriangles;
+  const size_t nb = (nt + kWave - 1) / kWave;
+  std::vector<void*> scratch;
+  struct Free {
+    std::vector<void*>& p;
+    ~Free() { freePool(p); }
+  } freeScratch{scratch};
+  uint8_t* referenced = nullptr;
+  int rc;
+  if (c->bvhInfo.numDropped) {
+    if ((rc = ensureRefit(c, st))) return rc;
+    if ((rc = devAlloc(c, scratch, &referenced, nt))) return rc;
+    HIPCHK(c, hipMemset(referenced, 0, nt));
+    launchAreaMarkReferenced(c->refit.nodes, c->refit.numNodes, c->S.recs, referenced, nullptr);
+  }
+  uint32_t *blockCount = nullptr, *blockBase = nullptr, *counts = nullptr;
+  if ((rc = devAlloc(c, scratch, &blockCount, nb)) || (rc = devAlloc(c, scratch, &blockBase, nb)) || (rc = devAlloc(c, scratch, &counts, 2)))
+    return rc;
+  HIPCHK(c, hipMemset(counts, 0, 2 * sizeof(uint32_t)));
+  launchAreaCount(c->S, nt, referenced, blockCount, blockBase, counts, nullptr);
+  uint32_t hc[2] = {0, 0};
+  HIPCHK(c, hipMemcpy(hc, counts, sizeof(hc), hipMemcpyDeviceToHost));
+  AreaDev A{};
+  A.n = hc[0];
+  if (A.n) {
+    const size_t nbe = (A.n + kWave - 1) / kWave;
+    float *cdf = nullptr, *total = nullptr;
+    float4* emit = nullptr;
+    if ((rc = devAlloc(c, c->sceneAllocs, &cdf, A.n)) || (rc = devAlloc(c, c->sceneAllocs, &emit, A.n)) ||
+        (rc = devAlloc(c, c->sceneAllocs, &total, 2)) || (rc = devAlloc(c, c->sceneAllocs, &c->areaBlockSum, nbe)) ||
+        (rc = devAlloc(c, c->sceneAllocs, &c->areaBlockLast, nbe)))
+      return rc;
+    A.cdf = cdf;
+    A.emit = emit;
+    A.total = total;
+    launchAreaCompact(c->S, nt, referenced, blockBase, c->alphaTris, c->numAlphaTris, emit, nullptr);
+    launchAreaRefresh(c->S, A, c->areaBlockSum, c->areaBlockLast, nullptr);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipDeviceSynchronize());
+  c->area = A;
+  c->areaTextured = hc[1];
+  c->areaReady = true;
+  return BDPT_OK;
+}
 }  // namespace
 
 int bdpt_update_geometry(bdpt_ctx* c, const bdpt_geometry_update* u, void* stream) {
@@ -865,6 +940,7 @@ int bdpt_update_geometry(bdpt_ctx* c, const bdpt_geometry_update* u, void* strea
     if (int rc = orderAfterLast(c, st)) return rc;
   }
   launchRefit(c->refit, reinterpret_cast<BvhRec*>(const_cast<uint4*>(c->S.recs)), const_cast<float4*>(c->S.shade), c->S.indices, c->numTriangles, pos, nrm, st);
+  if (c->areaReady) launchAreaRefresh(c->S, c->area, c->areaBlockSum, c->areaBlockLast, st);  // weights and CDF of the new areas
   if (bit) HIPCHK(c, hipMemcpyAsync(const_cast<float*>(c->S.bitangents), bit, nv3 * 4, hipMemcpyDeviceToDevice, st));
   if (!(u->flags & BDPT_UPDATE_KEEP_LIGHT_MAPS)) retraceLightMaps(c, st);
   HIPCHK(c, hipGetLastError());
@@ -1373,10 +1449,25 @@ namespace {
 // bdpt_execute, bdpt_execute_light_groups and bdpt_execute_masked: the same stages and the same rays.  The per-pixel
 // stages take the variant V; a group frame also clears its splat-value planes, and a masked frame runs the generators of
 // eye-side terms (NEE, connections) over its eye list (`PE`: the PathBuf with the eye list as its pixel list).
-int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream, const FrameVariant& V) {
+int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream, const FrameVariant& V0) {
   FrameDev F;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = frameSetup(c, p, in, out, st, F)) return rc;
+  FrameVariant V = V0;
+  if (p->flags & BDPT_PARAM_AREA_LIGHTS) {
+    // (the pdf an area-light vertex needs in the MIS prefix is a design question of its own; group planes have no slot
+    // for the table)
+    if (p->flags & (BDPT_PARAM_MIS_POWER | BDPT_PARAM_MIS_LINEAR)) {
+      fail(c, "execute: BDPT_PARAM_AREA_LIGHTS is not supported with BDPT_PARAM_MIS_POWER / _LINEAR");
+      return BDPT_E_INVALID;
+    }
+    if (V.kind == FrameKind::Groups) {
+      fail(c, "light groups: BDPT_PARAM_AREA_LIGHTS is not supported (the group planes have no slot for area lights)");
+      return BDPT_E_INVALID;
+    }
+    if (int rc = ensureAreaLights(c, st)) return rc;
+    V.area = c->area;  // n == 0 (no emitter): the plain instances
+  }
   const PathBuf& P = c->P;
   PathBuf PE = P;
   if (V.kind == FrameKind::Masked) {
@@ -1422,7 +1513,7 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
   if (mis) {
     launchMisPrefix(F, P, st);
     stageMark(c, st, "mis_prefix");
-    launchGenNee(c->S, F, PE, st);
+    launchGenNee(c->S, F, PE, V.area, st);
     stageMark(c, st, "gen_nee");
     launchGenSplat(c->S, F, P, st);
     stageMark(c, st, "gen_splat");
@@ -1446,7 +1537,7 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
     launchGenConnect(c->S, F, PE, c->walkStream);
     sideEnd(c, c->walkStream);
     HIPCHK(c, hipEventRecord(c->evJoin, c->walkStream));
-    launchGenNee(c->S, F, PE, st);
+    launchGenNee(c->S, F, PE, V.area, st);
     stageMark(c, st, "gen_nee");
     HIPCHK(c, hipStreamWaitEvent(st, c->evSplat, 0));
     stageMark(c, st, "splat_wait");
@@ -1634,7 +1725,7 @@ int bdpt_execute_tail(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in,
 // Allocate the optional buffers up front so that no later execute allocates (hipGraph capture, latency).
 int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
   if (!c) return BDPT_E_INVALID;
-  if ((what & ~BDPT_PREPARE_REFIT) || !what) {
+  if ((what & ~(BDPT_PREPARE_REFIT | BDPT_PREPARE_AREA_LIGHTS)) || !what) {
     if (!c->haveSize) {
       fail(c, "prepare: bdpt_resize must be called first");
       return BDPT_E_STATE;
@@ -1642,6 +1733,10 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
   }
   if ((what & BDPT_PREPARE_REFIT) && !c->haveScene) {
     fail(c, "prepare: BDPT_PREPARE_REFIT needs a scene");
+    return BDPT_E_STATE;
+  }
+  if ((what & BDPT_PREPARE_AREA_LIGHTS) && !c->haveScene) {
+    fail(c, "prepare: BDPT_PREPARE_AREA_LIGHTS needs a scene");
     return BDPT_E_STATE;
   }
   if ((what & BDPT_PREPARE_LIGHT_GROUPS) && !c->haveScene) {
@@ -1657,6 +1752,8 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
     if (int rc = allocBmfrHistory(c)) return rc;
   if (what & BDPT_PREPARE_LIGHT_GROUPS)
     if (int rc = allocLightGroups(c, nullptr)) return rc;
+  if (what & BDPT_PREPARE_AREA_LIGHTS)
+    if (int rc = ensureAreaLights(c, nullptr)) return rc;
   return BDPT_OK;
 }
 
@@ -2098,6 +2195,58 @@ int bdpt_test_trace_shadow(bdpt_ctx* c, const float* rays, uint32_t n, uint8_t* 
     unsigned long long m = 0;
     for (uint32_t sh = 0; sh < kCounterShards; sh++) m = std::max(m, h.v[sh][C_STACK_MAX]);
     *out_max_stack = (uint32_t)m;
+  }
+  return BDPT_OK;
+}
+
+int bdpt_get_area_light_info(bdpt_ctx* c, bdpt_area_light_info* out) {
+  if (!c || !out) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "area_light_info: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  ENTER(c);
+  if (int rc = ensureAreaLights(c, nullptr)) return rc;
+  HIPCHK(c, hipDeviceSynchronize());  // (the last update's refresh)
+  *out = bdpt_area_light_info{};
+  out->numEmitters = c->area.n;
+  out->numTextured = c->areaTextured;
+  if (c->area.n) HIPCHK(c, hipMemcpy(&out->totalWeight, c->area.total, sizeof(float), hipMemcpyDeviceToHost));
+  return BDPT_OK;
+}
+
+int bdpt_test_area_light_sample(bdpt_ctx* c, uint32_t mode, const uint32_t* states, const float* points, uint32_t n, float* out) {
+  if (!c || !states || !out || mode > 1 || (mode == 1 && !points)) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "test_area_light_sample: no scene");
+    return BDPT_E_STATE;
+  }
+  ENTER(c);
+  if (int rc = ensureAreaLights(c, nullptr)) return rc;
+  if (!n) return BDPT_OK;
+  std::vector<void*> pool;
+  const uint32_t* ds = nullptr;
+  const float* dp = nullptr;
+  float* dout = nullptr;
+  int rc;
+  if ((rc = devUpload(c, pool, &ds, states, n)) || (mode == 1 && (rc = devUpload(c, pool, &dp, points, (size_t)n * 3))) ||
+      (rc = devAlloc(c, pool, &dout, (size_t)n * 16))) {
+    freePool(pool);
+    return rc;
+  }
+  hipError_t e = hipDeviceSynchronize();  // (the last update's refresh)
+  if (e == hipSuccess) {
+    if (c->area.n)
+      launchTestAreaSample(c->S, c->area, (int)mode, ds, dp, n, dout, nullptr);
+    else
+      e = hipMemset(dout, 0, (size_t)n * 64);  // no emitter: every output is zero
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 64, hipMemcpyDeviceToHost);
+  freePool(pool);
+  if (e != hipSuccess) {
+    fail(c, hipGetErrorString(e));
+    return BDPT_E_HIP;
   }
   return BDPT_OK;
 }

@@ -198,6 +198,18 @@ struct MaskDev {
   const uint32_t* walkEyeCount; // and their lengths
 };
 
+// Area lights (BDPT_PARAM_AREA_LIGHTS; contract in include/bdpt.h "Area lights"): the scene's emitting triangles in
+// ascending primitive order and their selection CDF, built and refreshed on the device (area_lights.hip).  Only the AREA
+// instances of init_paths and gen_nee take it (last argument), so SceneDev and every other instance stay as they are.
+constexpr uint32_t kNoAlphaRec = 0xFFFFFFFFu;
+struct BvhRefitNode;  // bvh.h
+struct AreaDev {
+  const float* cdf;     // n inclusive prefix sums of the weights (fp32, fixed summation order)
+  const float4* emit;   // per emitter: prim (bits), alpha-test record (bits, kNoAlphaRec when opaque), weight, area
+  const float* total;   // two device words: W = cdf[n - 1], and the last emitter with a positive weight (bits)
+  uint32_t n;           // emitters; 0 = the frame runs the plain instances
+};
+
 // Which frame the per-pixel stages render: bdpt_execute, bdpt_execute_light_groups or bdpt_execute_masked.  Each kind is
 // a template argument of the init_paths, walk, gather and lazy_check kernels, which take what it needs (GroupDev,
 // MaskDev, or an empty struct for the plain frame) as their LAST argument, so the plain instances keep the offsets of
@@ -207,6 +219,7 @@ struct FrameVariant {
   FrameKind kind = FrameKind::Plain;
   GroupDev groups{};  // kind == Groups
   MaskDev mask{};     // kind == Masked
+  AreaDev area{};     // area.n > 0: the AREA instances of init_paths and gen_nee (Plain and Masked kinds)
 };
 
 struct GBufferDev {
@@ -262,7 +275,8 @@ struct LaunchGrids {
 void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,
                 hipStream_t st);
 void launchMisPrefix(const FrameDev& F, const PathBuf& P, hipStream_t st);
-void launchGenNee(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st);
+// A.n > 0: the AREA instance (area-light terms); otherwise the plain one
+void launchGenNee(const SceneDev& S, const FrameDev& F, const PathBuf& P, const AreaDev& A, hipStream_t st);
 void launchGenSplat(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st);
 void launchGenConnect(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st);
 void launchTraceShadow(const SceneDev& S, const FrameDev& F, const PathBuf& P, int rayClass, LaunchGrids& G, int numCUs, hipStream_t st);
@@ -319,5 +333,23 @@ void launchTestTrace(const SceneDev& S, const float* rays, uint32_t n, int mode,
 void launchTestTraceShadow(const SceneDev& S, const float* planes, uint32_t cap, const uint32_t* count, uint32_t* head, uint8_t* vis,
                            DevCounters* counters, float tmin, int numCUs, hipStream_t st);
 void launchTestBsdf(const float* in, uint32_t n, uint32_t matIndex, float* out, hipStream_t st);
+
+// area_lights.hip: the emitter table of BDPT_PARAM_AREA_LIGHTS.
+// Build (bdpt_prepare / first use; may synchronise): launchAreaMarkReferenced sets referenced[t] = 1 for every triangle a
+// leaf of the tree references (only needed when the build dropped triangles; the refit plan names the leaves);
+// launchAreaCount writes per-wave emitter counts of the triangles (referenced may be NULL: all referenced) and scans them
+// into blockBase (exclusive) and counts[0..1] = emitters, textured emitters; launchAreaCompact then writes the emitters'
+// primitives in ascending order.  Refresh (every bdpt_update_geometry; no allocation, no synchronisation):
+// launchAreaRefresh recomputes weights and the CDF from the current shading records.  `blocks` holds one float and one
+// word per 64 emitters (blocksFor(n)).
+void launchAreaMarkReferenced(const BvhRefitNode* nodes, uint32_t numNodes, const uint4* recs, uint8_t* referenced, hipStream_t st);
+void launchAreaCount(const SceneDev& S, uint32_t numTris, const uint8_t* referenced, uint32_t* blockCount, uint32_t* blockBase,
+                     uint32_t* counts, hipStream_t st);
+void launchAreaCompact(const SceneDev& S, uint32_t numTris, const uint8_t* referenced, const uint32_t* blockBase,
+                       const uint32_t* alphaTris, uint32_t numAlphaTris, float4* emit, hipStream_t st);
+void launchAreaRefresh(const SceneDev& S, const AreaDev& A, float* blockSum, uint32_t* blockLast, hipStream_t st);
+// bdpt_test_area_light_sample: mode 0 light-subpath start, mode 1 NEE sample (16 floats per item out; include/bdpt.h)
+void launchTestAreaSample(const SceneDev& S, const AreaDev& A, int mode, const uint32_t* states, const float* points, uint32_t n,
+                          float* out, hipStream_t st);
 
 }  // namespace bdpt

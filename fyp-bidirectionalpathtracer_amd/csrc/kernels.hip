@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "device_area.hpp"
 #include "device_math.hpp"
 #include "device_scene.hpp"
 #include "device_trace.hpp"
@@ -311,8 +312,12 @@ BD const MaskDev& maskOf(const MaskDev& m) { return m; }
 // MASKED (bdpt_execute_masked): every pixel's paths start as in the plain frame (its light subpath and seedL, which the
 // eye vertex's draws lead to, are needed whatever the mask says), but only active pixels get their `out` write, and the
 // active valid ones also go onto the eye list
-template <bool GGX, bool GROUPS, bool MASKED>
-BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const MaskDev& M) {
+// AREA (BDPT_PARAM_AREA_LIGHTS; include/bdpt.h "Area lights"): the emitter table is light numLights of numLights + 1
+// while its W is positive (else the plain arithmetic, bit for bit); a subpath that starts there takes its point, side and
+// cosine direction from the same seed chain (device_area.hpp areaLightStart)
+template <bool GGX, bool GROUPS, bool MASKED, bool AREA = false>
+BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const MaskDev& M,
+                      const AreaDev& A = AreaDev{}) {
   const uint32_t p = blockIdx.x * kWave + threadIdx.x;
   const bool inTile = p < P.Np;
   const size_t pix = inTile ? P.pix[p] : 0;
@@ -365,20 +370,26 @@ BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, co
       rd[2 * (size_t)P.Np] = outDir.z;
 
       // sampleLight (seed continues from seed0: the eye walk never advanced it, quirk 1)
-      const int lightsCount = (int)S.numLights;
+      const float areaW = AREA ? areaTotal(A) : 0.0f;
+      const int lightsCount = (int)S.numLights + ((AREA && areaW > 0.0f) ? 1 : 0);
       int index = (int)(nextRand(seed) * (float)lightsCount);
       if (index > lightsCount - 1) index = lightsCount - 1;
       if (GROUPS) Gr.lightIdx[p] = (uint8_t)index;
-      const bdpt_light& l = S.sc->lights[index];
       f3 lightDir;
-      if (l.type == BDPT_LIGHT_DIRECTIONAL)
-        lightDir = ld3(l.dirW);
-      else
-        lightDir = sampleUnitSphere(seed);
-      lightDir = getCosHemisphereSample(seed, lightDir);
       Vtx lv = zeroVtx();
-      lv.pos = ld3(l.posW);
-      lv.color = ld3(l.intensity);
+      if (AREA && index == (int)S.numLights) {
+        f3 n;
+        lv.pos = areaLightStart(S, A, areaW, seed, n, lightDir, lv.color).pos;
+      } else {
+        const bdpt_light& l = S.sc->lights[index];
+        if (l.type == BDPT_LIGHT_DIRECTIONAL)
+          lightDir = ld3(l.dirW);
+        else
+          lightDir = sampleUnitSphere(seed);
+        lightDir = getCosHemisphereSample(seed, lightDir);
+        lv.pos = ld3(l.posW);
+        lv.color = ld3(l.intensity);
+      }
       lv.pdf = 1.0f / (float)lightsCount;  // lightPath[0].pdfForward, BDPTMain.rt.hlsl:132
       storeVtx(P, PATH_LIGHT, 0, p, lv);
       float* rl = P.rayDir + (size_t)(PATH_LIGHT * 3) * P.Np + p;
@@ -403,6 +414,12 @@ template <bool GGX, FrameKind V>
 __global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev F, PathBuf P, FrameArg<V> A) {
   BDPT_ONE_WAVE_PER_GROUP();
   initPathsLane<GGX, V == FrameKind::Groups, V == FrameKind::Masked>(S, F, P, groupOf(A), maskOf(A));
+}
+// the AREA instances (plain and masked frames; light groups refuse the switch): the emitter table as one more argument
+template <bool GGX, FrameKind V>
+__global__ __launch_bounds__(kWave) void init_paths_area_kernel(SceneDev S, FrameDev F, PathBuf P, FrameArg<V> A, AreaDev E) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  initPathsLane<GGX, false, V == FrameKind::Masked, true>(S, F, P, GroupDev{}, maskOf(A), E);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -879,9 +896,11 @@ BD bool queueGroup(const uint32_t* count, uint32_t subCap, bool& act, uint32_t& 
   return true;
 }
 
-template <bool GGX, int G>
-__global__ __launch_bounds__(kWave) void gen_nee_kernel(SceneDev S, FrameDev F, PathBuf P) {
-  BDPT_ONE_WAVE_PER_GROUP();
+// AREA: the emitter table is light numLights of numLights + 1 while its W is positive; a term that draws it takes its
+// three uniforms from initRand(<state after the term's draw>, kAreaStreamKey), so no other term's draws move, and its
+// shadow ray stops short of the emitter (no occluder hint: those are for point and spot lights)
+template <bool GGX, int G, bool AREA>
+BD void genNeeLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, const AreaDev& A) {
   bool act = false;  // inactive lanes still take part in the wave-collective emitRay
   uint32_t i = 0;
   int t = 0;
@@ -891,7 +910,8 @@ __global__ __launch_bounds__(kWave) void gen_nee_kernel(SceneDev S, FrameDev F, 
   act = act && t < D;
   const uint32_t p = act ? P.queue[0][i] : 0u;
   const int eyeLast = act ? (int)P.eyeLast[p] : 0;
-  const int lightsCount = (int)S.numLights;
+  const float areaW = AREA ? areaTotal(A) : 0.0f;
+  const int lightsCount = (int)S.numLights + ((AREA && areaW > 0.0f) ? 1 : 0);
   // term t uses the (t+1)-th draw after sampleLight: one draw per term, also for vertices that do not exist (App. A item 8)
   uint32_t seed = act ? P.seedL[p] : 0u;
   float r = 0.0f;
@@ -909,12 +929,18 @@ __global__ __launch_bounds__(kWave) void gen_nee_kernel(SceneDev S, FrameDev F, 
     if (GGX) V = ldPlane3(P, PATH_EYE, t + 1, F_V, p);
     const f3 prevColor = (t == 0) ? mk(1.0f) : ldPlane3(P, PATH_EYE, t, F_COL, p);  // cameraPath[t].color; [0] = 1
     f3 lightIntensity;
-    getLightData(S.sc->lights[lightToSample], pos, L, lightIntensity, distToLight);
+    const bool area = AREA && lightToSample == (int)S.numLights;
+    if (area) {
+      areaNee(S, A, areaW, seed, pos, L, distToLight, lightIntensity);
+      distToLight = distToLight * (1.0f - 1e-4f);  // the emitter does not occlude its own sample
+    } else {
+      getLightData(S.sc->lights[lightToSample], pos, L, lightIntensity, distToLight);
+    }
     f3 direct = directIfVisible<GGX>((float)lightsCount, L, lightIntensity, v.N, V, v.dif, v.spec, v.rough);
-    shade = clampVec(applyStrategyWeight(F, P, p, prevColor * direct, t + 2, t + 1, 0), F.p.clampUpper);
+    shade = clampVec(applyStrategyWeight(F, P, p, prevColor * direct, t + 2, t + 1, 0), F.p.clampUpper);  // (NaN -> +0)
     emit = !allZero(shade);
     // the nearest triangle the light sees towards this vertex is tried first: an occluded term adds nothing and needs no ray
-    if (emit && S.sc->lights[lightToSample].type != BDPT_LIGHT_DIRECTIONAL &&
+    if (emit && !area && S.sc->lights[lightToSample].type != BDPT_LIGHT_DIRECTIONAL &&
         recOccludes(S, lightHint(S, lightToSample, ld3(S.sc->lights[lightToSample].posW), pos), pos, L, F.p.minT, distToLight)) {
       emit = false;
       hinted = true;
@@ -925,6 +951,16 @@ __global__ __launch_bounds__(kWave) void gen_nee_kernel(SceneDev S, FrameDev F, 
   waveAddCount(F.counters, C_RAYS_NEE, emit ? 1u : 0u);
   waveAddCount(F.counters, C_HINT_NEE, hinted ? 1u : 0u);
   waveAddCount(F.counters, C_PIX_VALID, firstOfPixel ? 1u : 0u);
+}
+template <bool GGX, int G>
+__global__ __launch_bounds__(kWave) void gen_nee_kernel(SceneDev S, FrameDev F, PathBuf P) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  genNeeLane<GGX, G, false>(S, F, P, AreaDev{});
+}
+template <bool GGX, int G>
+__global__ __launch_bounds__(kWave) void gen_nee_area_kernel(SceneDev S, FrameDev F, PathBuf P, AreaDev A) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  genNeeLane<GGX, G, true>(S, F, P, A);
 }
 
 template <bool GGX, int G>
@@ -1768,6 +1804,16 @@ void launchLightMaps(const SceneDev& S, uint32_t* maps, uint32_t res, hipStream_
 
 void launchInitPaths(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, hipStream_t st) {
   if (!P.Np) return;
+  if (V.area.n && V.kind != FrameKind::Groups) {  // (api.cpp refuses area lights with light groups)
+    const bool masked = V.kind == FrameKind::Masked;
+    withFlags(
+        [&](auto GGX, auto MASKED) {
+          constexpr FrameKind K = MASKED ? FrameKind::Masked : FrameKind::Plain;
+          launchWave(init_paths_area_kernel<GGX, K>, blocksFor(P.Np), st, S, F, P, frameArg<K>(V), V.area);
+        },
+        F.p.matIndex == 0, masked);
+    return;
+  }
   withKind(V.kind, [&](auto K) {
     withFlags([&](auto GGX) { launchWave(init_paths_kernel<GGX, K>, blocksFor(P.Np), st, S, F, P, frameArg<K>(V)); }, F.p.matIndex == 0);
   });
@@ -1797,8 +1843,13 @@ void launchMisPrefix(const FrameDev& F, const PathBuf& P, hipStream_t st) {
 // The three generators only share the ray queues (atomic appends), so the host may launch them on different streams.
 // G lanes per pixel: 8 for contexts sized up to depth 8, else 16 (the ray queues are sized for that shape; P.D1 is the
 // depth the context is sized for).
-void launchGenNee(const SceneDev& S, const FrameDev& F, const PathBuf& P, hipStream_t st) {
+void launchGenNee(const SceneDev& S, const FrameDev& F, const PathBuf& P, const AreaDev& A, hipStream_t st) {
   if (!P.Np) return;
+  if (A.n) {
+    withFlags([&](auto GGX, auto WIDE) { launchWave(gen_nee_area_kernel<GGX, WIDE ? 16 : 8>, queueGrid(P) * (WIDE ? 16 : 8), st, S, F, P, A); },
+              F.p.matIndex == 0, P.D1 > 9);
+    return;
+  }
   withFlags([&](auto GGX, auto WIDE) { launchWave(gen_nee_kernel<GGX, WIDE ? 16 : 8>, queueGrid(P) * (WIDE ? 16 : 8), st, S, F, P); },
             F.p.matIndex == 0, P.D1 > 9);
 }

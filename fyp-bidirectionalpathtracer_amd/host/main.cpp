@@ -39,6 +39,7 @@ struct Options {
   int frames = 8, depth = 3, mat = 0, device = 0, accumLimit = 100, inflight = 1, warmup = 0;
   int gpus = 0, rank = -1, world = 0;  // gpus: ranks as threads of this process; rank / world: this process is one rank
   bool denoise = false, denoiseRegression = false;
+  bool areaLights = false;  // BDPT_PARAM_AREA_LIGHTS: emissive triangles light the scene (NEE and light subpaths)
   float sway = 0.0f;  // > 0: an animated scene — before every frame the vertices move by up to this fraction of the scene's extent
 };
 
@@ -108,7 +109,11 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   }
   // add the passes to the rendering pipeline, as Main.cpp:12-18 does
   pipeline->setPass(0, LightProbeGBufferPass::create());
-  pipeline->setPass(1, BDPTPass::create(ResourceManager::kOutputChannel));
+  {
+    BDPTPass::SharedPtr bdpt = BDPTPass::create(ResourceManager::kOutputChannel);
+    if (o.areaLights) bdpt->setParamFlags(BDPT_PARAM_AREA_LIGHTS);
+    pipeline->setPass(1, bdpt);
+  }
   pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
   pipeline->setPass(3, BlockwiseMultiOrderFeatureRegression::create());
   // the window parameters of Main.cpp:20-25 size the channels (there is no window)
@@ -247,6 +252,7 @@ int main(int argc, char** argv) {
     };
     if (std::strcmp(argv[i], "--denoise") == 0) o.denoise = true;
     else if (std::strcmp(argv[i], "--denoise-regression") == 0) o.denoise = o.denoiseRegression = true;
+    else if (std::strcmp(argv[i], "--area-lights") == 0) o.areaLights = true;
     else if (const char* v = next("--scene")) o.scene = v;
     else if (const char* v = next("--width")) o.W = (uint32_t)std::atoi(v);
     else if (const char* v = next("--height")) o.H = (uint32_t)std::atoi(v);
@@ -270,7 +276,7 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--job-id")) o.jobId = v;  // names THIS run of the job: the id file of another run is not accepted
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
-                           "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--out file.pfm] [--raw file.f32] "
+                           "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
                            "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;

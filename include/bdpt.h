@@ -62,6 +62,12 @@
  *                                   (DenoisePass.h:71) and outside radiance parity
  *   bdpt_camera_view_proj           Camera::calculateCameraParameters' viewProjMat without jitter
  *                                   (Falcor Graphics/Camera/Camera.cpp:60-109), for prevViewProjMat
+ *   BDPT_PARAM_AREA_LIGHTS / bdpt_get_area_light_info / bdpt_test_area_light_sample
+ *                                   the TODO at the start of the light subpath ("Now assume point light source is used,
+ *                                   but we can extend it to area and directional light", BidirectionalPathtracing/Data/
+ *                                   BDPTMain.rt.hlsl:117-120): emissive triangles as one more light of sampleLight's
+ *                                   uniform choice (BDPTUtils.hlsli:140-152), evaluated by ggxDirect / lambertianDirect
+ *                                   (MaterialUtils.hlsli:149-184, 288-307) for next-event estimation
  *   bdpt_get_counters               (none in the reference; replaces nothing — ray tallies
  *                                    needed by the Mrays/s metric)
  *   bdpt_last_error                 Falcor logError / silent no-op conventions
@@ -230,6 +236,40 @@ typedef struct bdpt_params {
  *   EMISSIVE_HITS  a ray leaving eye vertex k that hits an emissive surface adds cameraPath[k].color * emissive / (k + 1) */
 #define BDPT_PARAM_ENV_ON_MISS 1024u
 #define BDPT_PARAM_EMISSIVE_HITS 2048u
+/* Area lights: emissive triangles light the scene through next-event estimation and light subpaths (build definition;
+ * off by default, and off every frame is the frame without it, bit for bit).
+ *   Emitters: the triangles whose material's emissive channel is BDPT_CHANNEL_CONST with a Rec.709 luminance > 0 or
+ *     BDPT_CHANNEL_TEXTURE, except those alpha clipping dropped (bdpt_bvh_info.numDropped), in ascending primitive order.
+ *     Weight w = area * lambda: area = 0.5 |cross(p1 - p0, p2 - p0)| from the current positions (after
+ *     bdpt_update_geometry, the updated ones); lambda = luminance of the emissive constant (CONST) or 1 (TEXTURE: the
+ *     largest luminance a decoded RGBA8 texel has), so the pdf is positive wherever emission can be.  CDF = inclusive fp32
+ *     prefix sums of the weights in a fixed order; W = its last value.  No emitter, or W == 0 (not > 0): the switch changes
+ *     nothing, bit for bit.
+ *   Selection: all emitters together are light numLights; the light count of the whole frame (the uniform choice of
+ *     init_paths and of every NEE term, shadowMult, lightPath[0].pdf) is numLights + 1.  numLights >= 1 stays required.
+ *   A point from uniforms (a, u1, u2): emitter i = the first whose CDF value is > a * W (none, by rounding: the last with
+ *     w > 0); barycentrics b1 = u2 sqrt(u1), b2 = 1 - sqrt(u1) (the point is (1 - b1 - b2) p0 + b1 p1 + b2 p2); position
+ *     and emission Le exactly as the hit shading gives them there (bdpt_shade_hits without the normal map, the same texture
+ *     fetch: NEE and EMISSIVE_HITS read one emission).  Le = 0 where the material is alpha-masked and the alpha test fails
+ *     at the point, or where the geometric normal n_g = normalize(cross(p1 - p0, p2 - p0)) has zero length.  Area pdf
+ *     p_A = w_i / (W * area_i).  Emission is two-sided, as EMISSIVE_HITS and the G-buffer treat it.
+ *   Draws (App. A of SURVEY.md, continued):
+ *     light subpath start (item 5): after the selection draw picks numLights: a, u1, u2, the side s (n = s < 0.5 ? n_g :
+ *       -n_g), then getCosHemisphereSample(seed, n) (two draws); lightPath[0].pos = x, .color = Le * 2 pi / p_A
+ *       (Le |cos| / (p_A p_omega), not divided by the selection probability, as for point lights), .pdf = 1 / (numLights
+ *       + 1); seedL = the state after these draws.
+ *     NEE term t (item 8): its draw r (the (t+1)-th after seedL) is unchanged; when it picks numLights, a, u1, u2 come
+ *       from initRand(<state after r>, 0x41524541u), so no other term's draws move.  L = (x - pos) / d; the light
+ *       intensity ggxDirect / lambertianDirect take is Le |dot(n_g, L)| / (p_A d^2); the shadow ray has tmax = d (1 - 1e-4)
+ *       (the emitter does not occlude its own sample) and no occluder hint.  A term with d^2 == 0 or a non-finite
+ *       intensity is +0.
+ *   Supported with whole-frame, band and stripes contexts, bdpt_execute_masked, DEFER_RESOLVE / DEFER_TAIL and
+ *   EMISSIVE_HITS / ENV_ON_MISS.  BDPT_E_INVALID with BDPT_PARAM_MIS_POWER / _LINEAR (the pdf of an area-light vertex in
+ *   the MIS prefix is a design question of its own) and with bdpt_execute_light_groups (the group planes have no slot for
+ *   it).  The table is made by bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) or by the first frame with the switch (which then
+ *   must not be inside a stream capture: BDPT_E_STATE); bdpt_update_geometry refreshes its weights on its stream without
+ *   allocating or synchronising. */
+#define BDPT_PARAM_AREA_LIGHTS 4096u
 
 /* RayGenCB of lightProbeGBuffer.rt.hlsl:45-52 + the miss shader's env map. */
 typedef struct bdpt_gbuffer_params {
@@ -602,6 +642,7 @@ int bdpt_tile_row_ranges(const bdpt_ctx* ctx, uint32_t* out_first_last, uint32_t
 #define BDPT_PREPARE_BMFR 2u
 #define BDPT_PREPARE_REFIT 4u /* the refit plan and scratch of bdpt_update_geometry now (needs a scene, not a size) */
 #define BDPT_PREPARE_LIGHT_GROUPS 8u /* the per-light splat planes of bdpt_execute_light_groups (needs a scene and a size) */
+#define BDPT_PREPARE_AREA_LIGHTS 16u /* the emitter table of BDPT_PARAM_AREA_LIGHTS (needs a scene, not a size) */
 int bdpt_prepare(bdpt_ctx* ctx, uint32_t what);
 
 /* Primary-visibility pass.  Writes the tile rows of all six channels. */
@@ -801,6 +842,16 @@ int bdpt_enable_stage_timing(bdpt_ctx* ctx, int enable);
 
 int bdpt_sync(bdpt_ctx* ctx, void* stream);
 
+/* The emitter table of BDPT_PARAM_AREA_LIGHTS (made here if need be; synchronises): emitters, of which textured, and W as
+ * of the last bdpt_update_geometry.  No scene BDPT_E_STATE. */
+typedef struct bdpt_area_light_info {
+  uint32_t numEmitters;
+  uint32_t numTextured;
+  float totalWeight; /* W */
+  uint32_t reserved;
+} bdpt_area_light_info;
+int bdpt_get_area_light_info(bdpt_ctx* ctx, bdpt_area_light_info* out);
+
 /* Test hooks through the same library (used by the parity tests; they launch
  * the device functions of the hot path on caller-supplied inputs). */
 /* initRand/nextRand stream: out[i*draws + k] = k-th nextRand seed state for (val0[i], val1[i]). */
@@ -817,6 +868,13 @@ int bdpt_test_trace_shadow(bdpt_ctx* ctx, const float* rays, uint32_t n, uint8_t
  * (N3 V3 L3 dif3 spec3 rough isSpecular seed(bits) pad2); outputs n records of 16 floats
  * (sampleBRDF: weight3 L3 pdf isSpec | evalBRDF: f3 | pad).  matIndex bit 1 = BDPT_PARAM_SPECULAR_FROM_LOBE. */
 int bdpt_test_bsdf(bdpt_ctx* ctx, const float* in, uint32_t n, uint32_t matIndex, float* out);
+/* Area-light known-answer hook: the device functions the AREA instances of init_paths and gen_nee run, on host arrays;
+ * synchronous.  states[i]: the RNG state right after the selection draw.  out: 16 floats per item (integers as bits).
+ *   mode 0 (light subpath start): prim, b1, b2, pos.xyz, side normal n.xyz, direction.xyz, colour.xyz, seedL (the state
+ *          after the draws)
+ *   mode 1 (NEE sample; points[i]: the receiving point, 3 floats): prim, L.xyz, d, intensity.xyz, b1, b2, x.xyz, 0, 0, 0
+ * With no emitter or W == 0 every output is 0.  Errors: mode > 1, a NULL array BDPT_E_INVALID; no scene BDPT_E_STATE. */
+int bdpt_test_area_light_sample(bdpt_ctx* ctx, uint32_t mode, const uint32_t* states, const float* points, uint32_t n, float* out);
 
 #ifdef __cplusplus
 }
