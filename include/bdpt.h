@@ -243,8 +243,13 @@ typedef struct bdpt_params {
  *     Weight w = area * lambda: area = 0.5 |cross(p1 - p0, p2 - p0)| from the current positions (after
  *     bdpt_update_geometry, the updated ones); lambda = luminance of the emissive constant (CONST) or 1 (TEXTURE: the
  *     largest luminance a decoded RGBA8 texel has), so the pdf is positive wherever emission can be.  CDF = inclusive fp32
- *     prefix sums of the weights in a fixed order; W = its last value.  No emitter, or W == 0 (not > 0): the switch changes
- *     nothing, bit for bit.
+ *     prefix sums of the weights in this order: each wave of 64 emitters (emitters 64 j .. 64 j + 63, missing ones weigh
+ *     +0) is scanned Hillis-Steele style (offsets 1, 2, 4, ..., 32: v[l] = v[l] + v[l - o] for l >= o); one wave then
+ *     scans the wave sums (each scan's last value) the same way in chunks of 64 with a running carry (from 0): the prefix
+ *     of wave j is carry for the chunk's first wave, else carry + the in-chunk inclusive value of wave j - 1, and after
+ *     each chunk carry = carry + the chunk's last inclusive value; an emitter's CDF value is its wave's prefix + its
+ *     in-wave value (wave 0: the in-wave value alone).  W = the last CDF value.  No emitter, or W == 0 (not > 0): the
+ *     switch changes nothing, bit for bit.
  *   Selection: all emitters together are light numLights; the light count of the whole frame (the uniform choice of
  *     init_paths and of every NEE term, shadowMult, lightPath[0].pdf) is numLights + 1.  numLights >= 1 stays required.
  *   A point from uniforms (a, u1, u2): emitter i = the first whose CDF value is > a * W (none, by rounding: the last with

@@ -246,6 +246,13 @@ struct oracle_scene {
   std::vector<float> envMap;
   uint32_t envW = 0, envH = 0;
   float envColor[4] = {0, 0, 0, 0};
+  // emitter table of BDPT_PARAM_AREA_LIGHTS (include/bdpt.h "Area lights"), made from the positions the scene was created
+  // with; areaExcluded: the triangles the device build dropped by alpha clipping (oracle_area_exclude)
+  std::vector<uint8_t> areaExcluded;
+  std::vector<uint32_t> areaPrim;
+  std::vector<float> areaWeight, areaArea, areaCdf;
+  uint32_t areaTextured = 0, areaLast = UINT32_MAX;
+  float areaTotal = 0.0f;
 };
 
 namespace {
@@ -650,6 +657,158 @@ inline f3 ggxLighting(f3 H, f3 L, f3 N, float NdotL, float NdotV, float rough, f
   return (D * G) * F / (4 * NdotL * NdotV);
 }
 
+// ----------------------------------------------------------------------------------------------
+// Area lights — a build definition (include/bdpt.h "Area lights"; no counterpart in the reference,
+// whose light subpath starts at a point light only, BDPTMain.rt.hlsl:117-120)
+// ----------------------------------------------------------------------------------------------
+constexpr uint32_t kAreaStreamKey = 0x41524541u;  // "AREA": initRand(state, key) seeds a NEE term's three uniforms
+constexpr int kWave = 64;
+
+// inclusive scan of 64 values in the Hillis-Steele order: offsets 1, 2, 4, ..., 32, v[l] = v[l] + v[l - o]
+void waveScan(float* v) {
+  for (int o = 1; o < kWave; o <<= 1) {
+    float prev[kWave];
+    std::copy(v, v + kWave, prev);
+    for (int l = o; l < kWave; l++) v[l] = prev[l] + prev[l - o];
+  }
+}
+
+// Emitters (ascending primitive order), weights w = area * lambda and the CDF in the summation order of the contract:
+// each 64-emitter wave's inclusive scan; one scan of the wave sums in 64-wide chunks with a running carry
+// (prefix of sum j = carry + inclusive value of sum j - 1 within the chunk, or carry for the chunk's first; carry =
+// carry + the chunk's last inclusive value); then cdf = prefix of the wave + the wave's own scan.
+void buildAreaTable(oracle_scene& s) {
+  s.areaPrim.clear();
+  s.areaTextured = 0;
+  const uint32_t nt = (uint32_t)s.triMat.size();
+  for (uint32_t t = 0; t < nt; t++) {
+    if (!s.areaExcluded.empty() && s.areaExcluded[t]) continue;
+    const bdpt_material& m = s.mats[s.triMat[t]];
+    const uint32_t type = BDPT_FLAG_EMISSIVE_TYPE(m.flags);
+    const bool textured = type == BDPT_CHANNEL_TEXTURE;
+    if (textured || (type == BDPT_CHANNEL_CONST && luminance(ld3(m.emissive)) > 0.0f)) {
+      s.areaPrim.push_back(t);
+      s.areaTextured += textured ? 1u : 0u;
+    }
+  }
+  const size_t n = s.areaPrim.size();
+  const size_t waves = (n + kWave - 1) / kWave;
+  s.areaWeight.assign(n, 0.0f);
+  s.areaArea.assign(n, 0.0f);
+  s.areaCdf.assign(n, 0.0f);
+  s.areaLast = UINT32_MAX;
+  std::vector<float> waveSum(waves, 0.0f);
+  for (size_t b = 0; b < waves; b++) {
+    float v[kWave];
+    for (int l = 0; l < kWave; l++) {
+      const size_t i = b * kWave + (size_t)l;
+      float w = 0.0f;
+      if (i < n) {
+        const uint32_t t = s.areaPrim[i];
+        const f3 p0 = s.pos[s.idx[(size_t)t * 3]], p1 = s.pos[s.idx[(size_t)t * 3 + 1]], p2 = s.pos[s.idx[(size_t)t * 3 + 2]];
+        const float area = 0.5f * length(cross(p1 - p0, p2 - p0));
+        const bdpt_material& m = s.mats[s.triMat[t]];
+        const float lambda = BDPT_FLAG_EMISSIVE_TYPE(m.flags) == BDPT_CHANNEL_TEXTURE ? 1.0f : luminance(ld3(m.emissive));
+        w = area * lambda;
+        s.areaWeight[i] = w;
+        s.areaArea[i] = area;
+        if (w > 0.0f) s.areaLast = (uint32_t)i;
+      }
+      v[l] = w;
+    }
+    waveScan(v);
+    for (int l = 0; l < kWave && b * kWave + (size_t)l < n; l++) s.areaCdf[b * kWave + (size_t)l] = v[l];
+    waveSum[b] = v[kWave - 1];
+  }
+  std::vector<float> prefix(waves, 0.0f);
+  float carry = 0.0f;
+  for (size_t j0 = 0; j0 < waves; j0 += kWave) {
+    float v[kWave];
+    for (int l = 0; l < kWave; l++) v[l] = j0 + (size_t)l < waves ? waveSum[j0 + (size_t)l] : 0.0f;
+    waveScan(v);
+    for (int l = 0; l < kWave && j0 + (size_t)l < waves; l++) prefix[j0 + (size_t)l] = l == 0 ? carry : carry + v[l - 1];
+    carry = carry + v[kWave - 1];
+  }
+  for (size_t i = kWave; i < n; i++) s.areaCdf[i] = prefix[i / kWave] + s.areaCdf[i];
+  s.areaTotal = n ? s.areaCdf[n - 1] : 0.0f;
+}
+
+// emitter i: the first whose CDF value is > a * W (binary search); none (rounding at the top): the last with w > 0
+uint32_t areaPick(const oracle_scene& s, float W, float a) {
+  const float target = a * W;
+  const uint32_t n = (uint32_t)s.areaCdf.size();
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (s.areaCdf[mid] > target)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  return lo < n ? lo : s.areaLast;
+}
+
+struct AreaPoint {
+  uint32_t prim;
+  float b1, b2;
+  f3 pos, ng, Le;
+  float pA;  // area pdf w_i / (W * area_i)
+};
+// the point of uniforms (a, u1, u2): b1 = u2 sqrt(u1), b2 = 1 - sqrt(u1); position and emission of the hit shading there;
+// Le = 0 where the alpha test fails or the geometric normal has zero length
+AreaPoint areaPoint(const oracle_scene& s, float W, float a, float u1, float u2) {
+  const uint32_t i = areaPick(s, W, a);
+  AreaPoint r;
+  r.prim = s.areaPrim[i];
+  const float su = sqrtf(u1);
+  r.b1 = u2 * su;
+  r.b2 = 1.0f - su;
+  const ShadingData sd = prepareShadingData(s, r.prim, r.b1, r.b2, mk(0), false);
+  r.pos = sd.posW;
+  r.Le = sd.emissive;
+  const f3 p0 = s.pos[s.idx[(size_t)r.prim * 3]], p1 = s.pos[s.idx[(size_t)r.prim * 3 + 1]], p2 = s.pos[s.idx[(size_t)r.prim * 3 + 2]];
+  const f3 c = cross(p1 - p0, p2 - p0);
+  const bool flat = !(dot(c, c) > 0.0f);
+  r.ng = flat ? mk(0) : normalize(c);
+  if (flat || (s.triNonOpaque[r.prim] && alphaTestFails(s, r.prim, r.b1, r.b2))) r.Le = mk(0);
+  r.pA = s.areaWeight[i] / (W * s.areaArea[i]);
+  return r;
+}
+
+inline bool finite3(f3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); }
+
+// light subpath start, after the selection draw picked the table: a, u1, u2, the side s, then the cosine direction;
+// colour = Le 2 pi / p_A, +0 where not finite
+AreaPoint areaLightStart(const oracle_scene& s, float W, uint32_t& seed, f3& n, f3& dir, f3& color) {
+  const float a = nextRand(seed);
+  const float u1 = nextRand(seed);
+  const float u2 = nextRand(seed);
+  const float side = nextRand(seed);
+  const AreaPoint x = areaPoint(s, W, a, u1, u2);
+  n = side < 0.5f ? x.ng : -x.ng;
+  dir = getCosHemisphereSample(seed, n);
+  color = x.Le * ((2.0f * kPi) / x.pA);
+  if (!finite3(color)) color = mk(0);
+  return x;
+}
+
+// NEE sample for a receiving point; `state`: the seed after the term's selection draw.  L = (x - pos) / d,
+// intensity = Le |dot(n_g, L)| / (p_A d^2), +0 when d^2 == 0 or not finite
+AreaPoint areaNee(const oracle_scene& s, float W, uint32_t state, f3 pos, f3& L, float& d, f3& intensity) {
+  uint32_t sa = initRand(state, kAreaStreamKey);
+  const float a = nextRand(sa);
+  const float u1 = nextRand(sa);
+  const float u2 = nextRand(sa);
+  const AreaPoint x = areaPoint(s, W, a, u1, u2);
+  const f3 v = x.pos - pos;
+  const float d2 = dot(v, v);
+  d = sqrtf(d2);
+  L = d2 > 0.0f ? v / d : mk(0);
+  intensity = x.Le * (fabsf(dot(x.ng, L)) / (x.pA * d2));
+  if (!(d2 > 0.0f) || !finite3(intensity)) intensity = mk(0);
+  return x;
+}
+
 struct Globals {
   const oracle_scene* s;
   bdpt_camera cam;
@@ -657,7 +816,21 @@ struct Globals {
   uint32_t flags;
   uint32_t W, H;
   int lightsCount;
+  bool area;    // BDPT_PARAM_AREA_LIGHTS with W > 0: the table is light numLights of lightsCount
+  float areaW;
 };
+
+// the light data of a NEE term that drew `lightToSample` (`seed`: the state after that draw); the area light's shadow
+// ray stops short of the emitter: tmax = d (1 - 1e-4)
+void getLightData(const Globals& g, int index, f3 hitPos, f3& toLight, f3& lightIntensity, float& distToLight);
+void neeLightData(const Globals& g, int lightToSample, uint32_t seed, f3 hit, f3& L, f3& lightIntensity, float& distToLight) {
+  if (g.area && lightToSample == (int)g.s->lights.size()) {
+    areaNee(*g.s, g.areaW, seed, hit, L, distToLight, lightIntensity);
+    distToLight = distToLight * (1.0f - 1e-4f);
+  } else {
+    getLightData(g, lightToSample, hit, L, lightIntensity, distToLight);
+  }
+}
 
 // MaterialUtils.hlsli:209-252
 f3 sampleGGXBRDF(uint32_t seed, f3 N, f3 noNormalN, f3 V, f3 dif, f3 spec, float rough, f3& L, float& pdf, bool& isSpecular,
@@ -775,7 +948,7 @@ f3 ggxDirect(const Globals& g, Tally& tl, uint32_t& seed, f3 hit, f3 N, f3 V, f3
   if (lightToSample > g.lightsCount - 1) lightToSample = g.lightsCount - 1;
   float distToLight;
   f3 lightIntensity, L;
-  getLightData(g, lightToSample, hit, L, lightIntensity, distToLight);
+  neeLightData(g, lightToSample, seed, hit, L, lightIntensity, distToLight);
   float NdotL = saturate(dot(N, L));
   bool vis = shadowRayVisibility(g, tl, 3, hit, L, g.p.minT, distToLight);
   float shadowMult = vis ? (float)g.lightsCount : 0.f;
@@ -795,7 +968,7 @@ f3 lambertianDirect(const Globals& g, Tally& tl, uint32_t& seed, f3 hit, f3 norm
   if (lightToSample > g.lightsCount - 1) lightToSample = g.lightsCount - 1;
   float distToLight;
   f3 lightIntensity, toLight;
-  getLightData(g, lightToSample, hit, toLight, lightIntensity, distToLight);
+  neeLightData(g, lightToSample, seed, hit, toLight, lightIntensity, distToLight);
   float LdotN = saturate(dot(norm, toLight));
   bool vis = shadowRayVisibility(g, tl, 3, hit, toLight, g.p.minT, distToLight);
   float shadowMult = (float)g.lightsCount * (vis ? 1.0f : 0.0f);
@@ -1070,14 +1243,19 @@ void bdptPixel(const Globals& g, Tally& tl, oracle_frame* f, uint32_t x, uint32_
   {
     int index = (int)(nextRand(randSeed) * (float)g.lightsCount);
     if (index > g.lightsCount - 1) index = g.lightsCount - 1;
-    const bdpt_light& l = g.s->lights[(size_t)index];
-    lightOrigin = ld3(l.posW);
-    lightIntensity = ld3(l.intensity);
-    if (l.type == BDPT_LIGHT_DIRECTIONAL)
-      lightDir = ld3(l.dirW);
-    else
-      lightDir = sampleUnitSphere(randSeed);
-    lightDir = getCosHemisphereSample(randSeed, lightDir);
+    if (g.area && index == (int)g.s->lights.size()) {  // the emitter table (include/bdpt.h "Area lights")
+      f3 n;
+      lightOrigin = areaLightStart(*g.s, g.areaW, randSeed, n, lightDir, lightIntensity).pos;
+    } else {
+      const bdpt_light& l = g.s->lights[(size_t)index];
+      lightOrigin = ld3(l.posW);
+      lightIntensity = ld3(l.intensity);
+      if (l.type == BDPT_LIGHT_DIRECTIONAL)
+        lightDir = ld3(l.dirW);
+      else
+        lightDir = sampleUnitSphere(randSeed);
+      lightDir = getCosHemisphereSample(randSeed, lightDir);
+    }
   }
   lightPath[0].posW = lightOrigin;
   lightPath[0].color = lightIntensity;
@@ -1354,10 +1532,71 @@ oracle_scene* oracle_scene_create(const bdpt_scene_desc* d) {
     s->triDoubleSided[t] = BDPT_FLAG_DOUBLE_SIDED(m.flags) != 0;
   }
   buildBvh(*s);
+  buildAreaTable(*s);
   return s;
 }
 
 void oracle_scene_destroy(oracle_scene* s) { delete s; }
+
+int oracle_area_exclude(oracle_scene* s, const uint32_t* tris, uint32_t n) {
+  if (!s || (n && !tris)) return -1;
+  const size_t nt = s->triMat.size();
+  for (uint32_t k = 0; k < n; k++)
+    if (tris[k] >= nt) return -1;
+  s->areaExcluded.assign(nt, 0);
+  for (uint32_t k = 0; k < n; k++) s->areaExcluded[tris[k]] = 1;
+  buildAreaTable(*s);
+  return 0;
+}
+
+void oracle_area_light_info(const oracle_scene* s, bdpt_area_light_info* out) {
+  if (!s || !out) return;
+  out->numEmitters = (uint32_t)s->areaPrim.size();
+  out->numTextured = s->areaTextured;
+  out->totalWeight = s->areaTotal;
+  out->reserved = 0;
+}
+
+uint32_t oracle_area_table(const oracle_scene* s, uint32_t* prim, float* weight, float* area, float* cdf) {
+  if (!s) return 0;
+  const size_t n = s->areaPrim.size();
+  if (prim) std::copy(s->areaPrim.begin(), s->areaPrim.end(), prim);
+  if (weight) std::copy(s->areaWeight.begin(), s->areaWeight.end(), weight);
+  if (area) std::copy(s->areaArea.begin(), s->areaArea.end(), area);
+  if (cdf) std::copy(s->areaCdf.begin(), s->areaCdf.end(), cdf);
+  return (uint32_t)n;
+}
+
+void oracle_area_light_sample(const oracle_scene* s, uint32_t mode, const uint32_t* states, const float* points, uint32_t n,
+                              float* out) {
+  if (!s || !states || !out || (mode == 1 && !points) || mode > 1) return;
+  const float W = s->areaTotal;
+  for (uint32_t i = 0; i < n; i++) {
+    float o[16];
+    for (int k = 0; k < 16; k++) o[k] = 0.0f;
+    if (!s->areaPrim.empty() && W > 0.0f) {
+      uint32_t u;
+      if (mode == 0) {
+        uint32_t seed = states[i];
+        f3 nrm, dir, col;
+        const AreaPoint x = areaLightStart(*s, W, seed, nrm, dir, col);
+        const float v[15] = {0.0f, x.b1, x.b2, x.pos.x, x.pos.y, x.pos.z, nrm.x, nrm.y, nrm.z, dir.x, dir.y, dir.z, col.x, col.y, col.z};
+        for (int k = 1; k < 15; k++) o[k] = v[k];
+        memcpy(&o[15], &seed, 4);
+        u = x.prim;
+      } else {
+        f3 L, I;
+        float d;
+        const AreaPoint x = areaNee(*s, W, states[i], ld3(points + (size_t)i * 3), L, d, I);
+        const float v[13] = {0.0f, L.x, L.y, L.z, d, I.x, I.y, I.z, x.b1, x.b2, x.pos.x, x.pos.y, x.pos.z};
+        for (int k = 1; k < 13; k++) o[k] = v[k];
+        u = x.prim;
+      }
+      memcpy(&o[0], &u, 4);
+    }
+    memcpy(out + (size_t)i * 16, o, sizeof(o));
+  }
+}
 
 void oracle_set_environment(oracle_scene* s, const bdpt_environment* env) {
   if (!s) return;
@@ -1393,6 +1632,14 @@ int oracle_bdpt(const oracle_scene* s, const bdpt_camera* cam, const bdpt_params
   g.W = f->width;
   g.H = f->height;
   g.lightsCount = (int)s->lights.size();
+  g.area = false;
+  g.areaW = 0.0f;
+  if (p->flags & BDPT_PARAM_AREA_LIGHTS) {
+    if (p->flags & (BDPT_PARAM_MIS_POWER | BDPT_PARAM_MIS_LINEAR)) return -1;  // BDPT_E_INVALID, as bdpt_execute
+    g.areaW = s->areaTotal;
+    g.area = !s->areaPrim.empty() && g.areaW > 0.0f;
+    if (g.area) g.lightsCount += 1;
+  }
   std::vector<Tally> tallies((size_t)(threads > 1 ? threads : 1));
   parallelRows(f->y0, f->y1, threads, [&](uint32_t y, Tally& tl, int t) {
     if (y == UINT32_MAX) {

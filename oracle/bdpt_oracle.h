@@ -87,6 +87,19 @@ void oracle_bsdf(const float* in, uint32_t n, uint32_t matIndex, float* out);
 void oracle_sincos2pi(const float* u, uint32_t n, float* s, float* c);
 void oracle_half_round(const float* in, uint32_t n, float* out);
 
+/* Area lights (BDPT_PARAM_AREA_LIGHTS, include/bdpt.h "Area lights"): oracle_bdpt honours the switch in p->flags (and
+ * fails with MIS, as bdpt_execute does).  The emitter table is made from the positions the scene was created with.
+ * The oracle cannot know which triangles the device build drops by alpha clipping: oracle_area_exclude lists them
+ * (replacing an earlier list) and remakes the table; -1 on a NULL scene or an index out of range. */
+int oracle_area_exclude(oracle_scene* s, const uint32_t* tris, uint32_t n);
+/* bdpt_get_area_light_info of the oracle's table */
+void oracle_area_light_info(const oracle_scene* s, bdpt_area_light_info* out);
+/* The table: emitter count; each non-NULL array gets that many values (primitive, weight, area, CDF value). */
+uint32_t oracle_area_table(const oracle_scene* s, uint32_t* prim, float* weight, float* area, float* cdf);
+/* bdpt_test_area_light_sample on the oracle's table: modes 0 and 1, 16 floats per item (integers as bits). */
+void oracle_area_light_sample(const oracle_scene* s, uint32_t mode, const uint32_t* states, const float* points, uint32_t n,
+                              float* out);
+
 /* BMFR denoise pass (bmfr_oracle.cpp; DenoisePass.cpp:146-279 + its three shaders).  Channels are
  * float4 per pixel; curNorm / albedo hold the half-precision G-buffer values widened to float. */
 typedef struct oracle_bmfr oracle_bmfr;

@@ -103,8 +103,11 @@ class Vertex:
 
 
 class Renderer:
-    def __init__(self, scene, cam, params, width, height, specular_from_lobe=False, mis=None):
+    def __init__(self, scene, cam, params, width, height, specular_from_lobe=False, mis=None, area=None):
         self.mis = mis  # None: the uniform 1/k the shader applies; "power" / "linear": getWeightPower / getWeightLinear
+        # area: an area_light_numpy.AreaTable — with a positive W it is light numLights of numLights + 1 (BDPT_PARAM_AREA_LIGHTS,
+        # include/bdpt.h "Area lights")
+        self.area = area if area is not None and len(area.prim) and area.W > 0 else None
         self.s, self.W, self.H = scene, width, height
         self.cam_pos = np.array(list(cam.posW), np.float64)
         self.U, self.Vv, self.Wv = (np.array(list(getattr(cam, k)), np.float64) for k in ("cameraU", "cameraV", "cameraW"))
@@ -112,7 +115,8 @@ class Renderer:
         self.mat = int(params.matIndex)
         self.D = int(params.maxDepth)
         self.from_lobe = specular_from_lobe
-        self.nl = len(scene.lights)
+        self.n_point = len(scene.lights)
+        self.nl = self.n_point + (1 if self.area is not None else 0)
 
     # ---- rays
     def visible(self, o, d, tmin, tmax):
@@ -174,7 +178,11 @@ class Renderer:
     def eval_direct(self, seed, v):
         seed, r = hm.next_rand(seed)
         index = min(int(r * self.nl), self.nl - 1)
-        L, inten, dist = self.light_data(index, v.pos)
+        if index == self.n_point:  # the emitter table: its own stream, a shadow ray that stops short of the emitter
+            _, L, d, inten = self.area.nee(seed, v.pos)
+            dist = d * (1.0 - 1e-4)
+        else:
+            L, inten, dist = self.light_data(index, v.pos)
         with np.errstate(invalid="ignore"):
             ndotl = hm.saturate(float(np.dot(v.N, L)))
         vis = self.visible(v.pos, L, float(self.p.minT), dist)
@@ -194,6 +202,9 @@ class Renderer:
     def sample_light(self, seed):
         seed, r = hm.next_rand(seed)
         index = min(int(r * self.nl), self.nl - 1)
+        if index == self.n_point:  # a point on an emitter, its side, a cosine direction about that side
+            x, _, d, color, seed = self.area.light_start(seed)
+            return seed, x["pos"], d, color
         lt = self.s.lights[index]
         origin = np.array(list(lt.posW), np.float64)
         inten = np.array(list(lt.intensity), np.float64)

@@ -45,6 +45,12 @@ def load_oracle(abi):
     lib.oracle_bsdf.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.oracle_sincos2pi.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.oracle_half_round.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.oracle_area_exclude.restype = C.c_int
+    lib.oracle_area_exclude.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.oracle_area_light_info.argtypes = [C.c_void_p, C.POINTER(abi.AreaLightInfo)]
+    lib.oracle_area_table.restype = C.c_uint32
+    lib.oracle_area_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.oracle_area_light_sample.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.oracle_bmfr_create.restype = C.c_void_p
     lib.oracle_bmfr_create.argtypes = [C.c_uint32, C.c_uint32]
     lib.oracle_bmfr_destroy.argtypes = [C.c_void_p]

@@ -7,108 +7,12 @@ import math
 import numpy as np
 import pytest
 
-from area_light_numpy import AREA_KEY, AreaTable
+from area_light_numpy import AREA_KEY
+from area_scenes import AREA, EMISSIVE_HITS, MIS_POWER, NO_CONNECT, NO_NEE, NO_SPLAT, AreaScene
 from hlsl_integrator_numpy import hm_init_rand
 from hlsl_reference_math import next_rand
 
 pytestmark = pytest.mark.gpu
-
-AREA = 4096
-NO_NEE, NO_SPLAT, NO_CONNECT, MIS_POWER, EMISSIVE_HITS = 4, 8, 16, 64, 2048
-
-
-def _flags(dif, spec, emis, alpha=0):
-    return (dif << 3) | (spec << 6) | (emis << 9) | (alpha << 17)
-
-
-def _arr(ptr, n, dtype):
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype).copy()
-
-
-class AreaScene:
-    """A scene description over numpy arrays it keeps alive; the camera is the base scene's."""
-
-    def __init__(self, pkg, base, positions=None, patch_emission=None, extra=True):
-        a = pkg.abi
-        d = base.desc
-        nv, nt = int(d.numVertices), int(d.numTriangles)
-        P = _arr(d.positions, nv * 3, np.float32).reshape(-1, 3)
-        N = _arr(d.normals, nv * 3, np.float32).reshape(-1, 3)
-        T = np.zeros((nv, 3), np.float32) if not d.texcoords else _arr(d.texcoords, nv * 3, np.float32).reshape(-1, 3)
-        I = _arr(d.indices, nt * 3, np.uint32).reshape(-1, 3)
-        M = _arr(d.triMaterial, nt, np.uint32)
-        nm = int(d.numMaterials)
-        mats = [a.Material() for _ in range(nm + 2)]
-        for i in range(nm):
-            C.memmove(C.byref(mats[i]), C.byref(d.materials[i]), C.sizeof(a.Material))
-        if patch_emission is not None:
-            for k in range(3):
-                mats[3].emissive[k] = patch_emission[k]
-        self.textures = []
-        if extra:
-            # textured emitter: a constant sRGB texel; alpha-masked emitter: alpha 255 / 0 in a 2x2 checker of 2x2 blocks
-            tex_e = np.zeros((4, 4, 4), np.uint8)
-            tex_e[...] = (200, 150, 100, 255)
-            tex_a = np.full((4, 4, 4), 128, np.uint8)
-            yy, xx = np.mgrid[0:4, 0:4]
-            tex_a[..., 3] = np.where(((yy // 2) + (xx // 2)) % 2 == 0, 255, 0)
-            self.textures = [(tex_e, True), (tex_a, False)]
-            for m in mats[nm:]:
-                m.baseColor[:] = (0.6, 0.6, 0.6, 1.0)
-                m.specular[:] = (0.0, 1.0, 0.0, 0.0)  # roughness 1, metallic 0
-                m.alphaThreshold, m.IoR = 0.5, 1.5
-                m.texBaseColor = m.texSpecular = m.texEmissive = m.texNormal = -1
-            mats[nm].flags = _flags(1, 1, 2)
-            mats[nm].texEmissive = 0
-            mats[nm + 1].flags = _flags(2, 1, 1, alpha=1)
-            mats[nm + 1].texBaseColor = 1
-            mats[nm + 1].emissive[:] = (2.0, 1.5, 1.0)
-            quads = [((80, 200), (150, 300), 420.0, nm), ((330, 480), (300, 450), 350.0, nm + 1)]
-            for (x0, x1), (z0, z1), y, mid in quads:
-                base_v = P.shape[0]
-                q = np.array([[x0, y, z0], [x1, y, z0], [x1, y, z1], [x0, y, z1]], np.float32)
-                P = np.concatenate([P, q])
-                N = np.concatenate([N, np.tile([[0, -1, 0]], (4, 1)).astype(np.float32)])
-                T = np.concatenate([T, np.array([[0, 0, 0], [1.25, 0, 0], [1.25, 1.25, 0], [0, 1.25, 0]], np.float32)])
-                I = np.concatenate([I, np.array([[0, 1, 2], [0, 2, 3]], np.uint32) + base_v])
-                M = np.concatenate([M, np.array([mid, mid], np.uint32)])
-        else:
-            mats = mats[:nm]
-        # the ceiling patch 10 units lower than the box's 0.1 below the ceiling: the ceiling next to it then sees its top side
-        # from no closer than that, which keeps NEE's 1 / d^2 tail (and so the sample variances the block test relies on) bounded
-        P[np.unique(I[M == 3])] -= np.array([0.0, 10.0, 0.0], np.float32)
-        if positions is not None:
-            P[: positions.shape[0]] = positions
-        self.P, self.N, self.T, self.I, self.M = (np.ascontiguousarray(x) for x in (P, N, T, I, M))
-        self.mats = (a.Material * len(mats))(*mats)
-        self._tex_c = (a.Texture * max(len(self.textures), 1))()
-        for k, (t, srgb) in enumerate(self.textures):
-            self._tex_c[k].rgba8 = t.ctypes.data_as(C.POINTER(C.c_uint8))
-            self._tex_c[k].width, self._tex_c[k].height, self._tex_c[k].srgb = t.shape[1], t.shape[0], int(srgb)
-        light = a.Light()
-        C.memmove(C.byref(light), C.byref(d.lights[0]), C.sizeof(a.Light))
-        light.intensity[0] = light.intensity[1] = light.intensity[2] = 0.0
-        self.lights = (a.Light * 1)(light)
-        self.desc = a.SceneDesc()
-        dd = self.desc
-        dd.numVertices, dd.numTriangles, dd.numMaterials = self.P.shape[0], self.I.shape[0], len(mats)
-        dd.numTextures, dd.numLights = len(self.textures), 1
-        f = C.POINTER(C.c_float)
-        dd.positions, dd.normals, dd.texcoords = (x.ctypes.data_as(f) for x in (self.P, self.N, self.T))
-        dd.bitangents = None
-        dd.indices = self.I.ctypes.data_as(C.POINTER(C.c_uint32))
-        dd.triMaterial = self.M.ctypes.data_as(C.POINTER(C.c_uint32))
-        dd.materials = C.cast(self.mats, C.POINTER(a.Material))
-        dd.textures = C.cast(self._tex_c, C.POINTER(a.Texture)) if self.textures else None
-        dd.lights = C.cast(self.lights, C.POINTER(a.Light))
-        self.base = base
-
-    def camera(self, aspect):
-        return self.base.camera(aspect)
-
-    def table(self):
-        return AreaTable(self.P, self.I, self.M, list(self.mats), self.textures, self.T)
-
 
 @pytest.fixture(scope="module")
 def cornell(pkg):
