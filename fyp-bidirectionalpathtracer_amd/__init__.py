@@ -374,6 +374,61 @@ class Context:
 
         return self._surface_query("eval_bsdf", [("surfaces", surfaces, 24, i32), ("dirs", dirs, 4, f32)], (4, f32), run, out, count)
 
+    # ---- light queries (include/bdpt.h "Light queries") ----
+    def sample_lights(self, surfaces, seeds, mat_index=0, min_t=1e-4, area_lights=False, use_hints=False, out=None,
+                      seeds_out=None, compact=None, count=None, stream=None):
+        """bdpt_light_query(NEE): one next-event sample of the pass per (N, 24) bdpt_surface record and seed ((N,) uint32 or
+        int32 RNG states).  mat_index 0 GGX, 1 Lambertian; min_t is the rays' tmin; area_lights sets BDPT_PARAM_AREA_LIGHTS
+        (the emitter table is one more light while it has weight), use_hints BDPT_LIGHT_USE_HINTS.  Returns (N, 12) float32
+        in the bdpt_light_sample layout: 0-7 the shadow ray (bdpt_ray: origin, tmin, L, distance), 8-10 the unweighted,
+        unclamped value of a visible light, 11 (through .view(torch.int32)) light | status << 16, status bit 0 = the value
+        is non-zero, bit 1 = the occluder hint found the light occluded.  A miss record gives zeros.
+        GPU tensors only: seeds_out (N,) takes the states after the selection draw (it may be `seeds`); compact = (rays (N, 8)
+        float32, items (N,) int32 / uint32, count (1,) int32 / uint32, zeroed by the caller) takes the dense list of rays
+        worth tracing, for trace_rays(rays, "any", count=count).  `out` and `count` as for the other queries."""
+        import torch
+        i32, u32 = (torch.float32, torch.int32), (torch.int32, torch.uint32)
+        mat, _ = self._bsdf_mode("sample_lights", mat_index, False)
+        flags = (abi.PARAM_AREA_LIGHTS if area_lights else 0) | (abi.LIGHT_USE_HINTS if use_hints else 0)
+        extras = [("seeds_out", seeds_out, None, u32)]
+        if compact is not None:
+            if not isinstance(compact, (tuple, list)) or len(compact) != 3 or any(t is None for t in compact):
+                raise BdptError("sample_lights: compact must be (rays, items, count), all three")
+            extras += [("compact rays", compact[0], 8, (torch.float32,)), ("compact items", compact[1], None, u32),
+                       ("compact count", compact[2], 1, u32)]
+        else:
+            compact = (None, None, None)
+
+        def run(ptrs, n, cnt, res):
+            d = abi.LightDesc()
+            d.mode, d.num, d.numDevice, d.matIndex, d.flags, d.minT = abi.LIGHT_NEE, n, cnt, mat, flags, float(min_t)
+            d.surfaces, d.seeds, d.samples = ptrs[0], ptrs[1], res
+            d.seedsOut = None if seeds_out is None else seeds_out.data_ptr()
+            d.compactRays, d.compactItems, d.compactCount = (None if t is None else t.data_ptr() for t in compact)
+            return self._lib.bdpt_light_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("sample_lights", [("surfaces", surfaces, 24, i32), ("seeds", seeds, None, u32)], (12, i32), run,
+                                   out, count, extras=extras, fn="bdpt_light_query")
+
+    def emit_lights(self, seeds, min_t=1e-4, area_lights=False, out=None, seeds_out=None, count=None, stream=None):
+        """bdpt_light_query(EMIT): the start of a light subpath of the pass (sampleLight) per seed ((N,) uint32 or int32 RNG
+        states).  Returns (N, 12) float32 in the bdpt_light_emit layout: 0-7 the ray (bdpt_ray: the light's position or the
+        point on an emitter, tmin = min_t, the sampled direction, 1e38), 8-10 the colour of light vertex 0, 11 the light
+        (uint32 bits).  seeds_out (GPU tensor, (N,)) takes the states after all draws: the pass's seedL."""
+        import torch
+        i32, u32 = (torch.float32, torch.int32), (torch.int32, torch.uint32)
+        flags = abi.PARAM_AREA_LIGHTS if area_lights else 0
+
+        def run(ptrs, n, cnt, res):
+            d = abi.LightDesc()
+            d.mode, d.num, d.numDevice, d.matIndex, d.flags, d.minT = abi.LIGHT_EMIT, n, cnt, 0, flags, float(min_t)
+            d.seeds, d.emits = ptrs[0], res
+            d.seedsOut = None if seeds_out is None else seeds_out.data_ptr()
+            return self._lib.bdpt_light_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("emit_lights", [("seeds", seeds, None, u32)], (12, i32), run, out, count,
+                                   extras=[("seeds_out", seeds_out, None, u32)], fn="bdpt_light_query")
+
     @staticmethod
     def _bsdf_mode(what, mat_index, from_lobe):
         if mat_index not in (0, 1) or isinstance(mat_index, bool):
@@ -389,9 +444,11 @@ class Context:
             raise BdptError(f"{what}: {name} must be {tuple(shape)} {'/'.join(str(d) for d in dtypes)}, not "
                             f"{tuple(t.shape)} {t.dtype}")
 
-    def _surface_query(self, what, inputs, out_spec, run, out, count):
+    def _surface_query(self, what, inputs, out_spec, run, out, count, extras=(), fn=None):
         """The shared path of the per-item queries.  inputs: (name, value, columns or None for 1-D, allowed torch dtypes),
-        all with one row per item; out_spec: (columns, allowed dtypes; the first is allocated)."""
+        all with one row per item; out_spec: (columns, allowed dtypes; the first is allocated).  extras: further outputs of
+        the same form that may be None and go with GPU tensor inputs only (a column count of 1 with a 1-D name "... count":
+        a one-element tensor); fn: the library call's name for error messages."""
         import numpy as np
         import torch
         on_gpu = [getattr(v, "is_cuda", False) for _, v, _, _ in inputs]
@@ -403,17 +460,20 @@ class Context:
                 self._check_gpu(v, what, name, (n,) if cols is None else (n, cols), dts)
             if count is not None:
                 self._check_gpu(count, what, "count", (1,), (torch.int32, torch.uint32))
+            for name, v, cols, dts in extras:
+                if v is not None:
+                    self._check_gpu(v, what, name, (1,) if name.endswith("count") else (n,) if cols is None else (n, cols), dts)
             if out is None:
                 out = torch.empty((n, out_spec[0]), dtype=out_spec[1][0], device=inputs[0][1].device)
             else:
                 self._check_gpu(out, what, "out", (n, out_spec[0]), out_spec[1])
             self._check(run([v.data_ptr() for _, v, _, _ in inputs], n, None if count is None else count.data_ptr(), out.data_ptr()),
-                        "bdpt_" + ("bsdf_query" if "bsdf" in what else what))
+                        fn or "bdpt_" + ("bsdf_query" if "bsdf" in what else what))
             return out if out.dtype == torch.float32 else out.view(torch.float32)
         if any(on_gpu):
             raise BdptError(f"{what}: the inputs must all be GPU tensors or all host arrays")
-        if out is not None or count is not None:
-            raise BdptError(f"{what}: out= and count= go with GPU tensor inputs")
+        if out is not None or count is not None or any(v is not None for _, v, _, _ in extras):
+            raise BdptError(f"{what}: out=, count= and the other output tensors go with GPU tensor inputs")
         np_of = {torch.float32: np.float32, torch.int32: np.int32, torch.uint32: np.uint32}
         host = []
         for name, v, cols, dts in inputs:
@@ -434,7 +494,8 @@ class Context:
         with torch.cuda.device(dev):
             devs = [_host_to_device(a, dev) for a in host]
             torch.cuda.synchronize(dev)  # the copies are done before the library's stream reads them
-            res = self._surface_query(what, [(nm, d, c, t) for (nm, _, c, t), d in zip(inputs, devs)], out_spec, run, None, None)
+            res = self._surface_query(what, [(nm, d, c, t) for (nm, _, c, t), d in zip(inputs, devs)], out_spec, run, None, None,
+                                      fn=fn)
             torch.cuda.synchronize(dev)
         return res.cpu().numpy()
 
@@ -882,6 +943,20 @@ class FramePipeline:
         """Context.eval_bsdf with the pipeline's BSDF (mat_index) on its stream."""
         res = self.ctx.eval_bsdf(surfaces, dirs, self.mat_index, out, count, self._stream_ptr())
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (surfaces, dirs, count, res))
+        return res
+
+    def sample_lights(self, surfaces, seeds, use_hints=False, out=None, seeds_out=None, compact=None, count=None):
+        """Context.sample_lights with the pipeline's BSDF (mat_index), min_t and PARAM_AREA_LIGHTS flag, on its stream."""
+        res = self.ctx.sample_lights(surfaces, seeds, self.mat_index, self.min_t, (self.flags & abi.PARAM_AREA_LIGHTS) != 0, use_hints,
+                                     out, seeds_out, compact, count, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (surfaces, seeds, seeds_out, count, res) + tuple(compact or ()))
+        return res
+
+    def emit_lights(self, seeds, out=None, seeds_out=None, count=None):
+        """Context.emit_lights with the pipeline's min_t and PARAM_AREA_LIGHTS flag, on its stream."""
+        res = self.ctx.emit_lights(seeds, self.min_t, (self.flags & abi.PARAM_AREA_LIGHTS) != 0, out, seeds_out, count,
+                                   self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (seeds, seeds_out, count, res))
         return res
 
     def set_lights(self, lights):

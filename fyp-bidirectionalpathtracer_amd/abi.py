@@ -35,6 +35,9 @@ UPDATE_KEEP_LIGHT_MAPS = 1
 TRACE_CLOSEST, TRACE_CLOSEST_CULL_BACK, TRACE_ANY = 0, 1, 2
 SHADE_NORMAL_MAP = 1
 BSDF_SAMPLE, BSDF_EVAL = 0, 1
+LIGHT_NEE, LIGHT_EMIT = 0, 1
+LIGHT_USE_HINTS = 1
+LIGHT_STATUS_NONZERO, LIGHT_STATUS_HINT_OCCLUDED = 1, 2
 
 
 class Material(C.Structure):
@@ -185,6 +188,21 @@ class BsdfDesc(C.Structure):
                 ("dirs", C.c_void_p), ("values", C.c_void_p)]
 
 
+class LightSample(C.Structure):
+    _fields_ = [("ray", Ray), ("value", C.c_float * 3), ("light", C.c_uint16), ("status", C.c_uint16)]
+
+
+class LightEmit(C.Structure):
+    _fields_ = [("ray", Ray), ("color", C.c_float * 3), ("light", C.c_uint32)]
+
+
+class LightDesc(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("num", C.c_uint32), ("numDevice", C.c_void_p), ("matIndex", C.c_uint32),
+                ("flags", C.c_uint32), ("minT", C.c_float), ("reserved", C.c_uint32), ("surfaces", C.c_void_p),
+                ("seeds", C.c_void_p), ("seedsOut", C.c_void_p), ("samples", C.c_void_p), ("emits", C.c_void_p),
+                ("compactRays", C.c_void_p), ("compactItems", C.c_void_p), ("compactCount", C.c_void_p)]
+
+
 class AreaLightInfo(C.Structure):
     _fields_ = [("numEmitters", C.c_uint32), ("numTextured", C.c_uint32), ("totalWeight", C.c_float), ("reserved", C.c_uint32)]
 
@@ -210,6 +228,7 @@ PROTOTYPES = {
     "bdpt_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(GBufferParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdpt_shade_hits": (C.c_int, [C.c_void_p, C.POINTER(ShadeDesc), C.c_void_p]),
     "bdpt_bsdf_query": (C.c_int, [C.c_void_p, C.POINTER(BsdfDesc), C.c_void_p]),
+    "bdpt_light_query": (C.c_int, [C.c_void_p, C.POINTER(LightDesc), C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),
     "bdpt_host_bvh_recs_hash": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -1084,6 +1084,60 @@ int bdpt_bsdf_query(bdpt_ctx* c, const bdpt_bsdf_desc* d, void* stream) {
   return BDPT_OK;
 }
 
+static_assert(sizeof(bdpt_light_sample) == 48 && sizeof(bdpt_light_emit) == 48 && offsetof(bdpt_light_sample, status) == 46,
+              "the light query kernels write a record as three float4, light and status sharing the last word");
+int bdpt_light_query(bdpt_ctx* c, const bdpt_light_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "light_query: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  const bool emitMode = d->mode == BDPT_LIGHT_EMIT;
+  if (d->mode > BDPT_LIGHT_EMIT || d->matIndex > 1 || (d->flags & ~(BDPT_PARAM_AREA_LIGHTS | BDPT_LIGHT_USE_HINTS))) {
+    fail(c, "light_query: unknown mode or flags, or matIndex > 1");
+    return BDPT_E_INVALID;
+  }
+  const bool compact = d->compactRays || d->compactItems || d->compactCount;
+  if (emitMode && (compact || (d->flags & BDPT_LIGHT_USE_HINTS))) {
+    fail(c, "light_query: compaction and BDPT_LIGHT_USE_HINTS go with BDPT_LIGHT_NEE");
+    return BDPT_E_INVALID;
+  }
+  if (compact && !(d->compactRays && d->compactItems && d->compactCount)) {
+    fail(c, "light_query: compactRays, compactItems and compactCount go together");
+    return BDPT_E_INVALID;
+  }
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->seeds, 4) || (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)) ||
+      (emitMode ? !aligned(d->emits, 16) : (!aligned(d->surfaces, 16) || !aligned(d->samples, 16))) ||
+      (compact && (!aligned(d->compactRays, 16) || !aligned(d->compactItems, 4) || !aligned(d->compactCount, 4)))) {
+    fail(c, "light_query: surfaces, seeds, samples, emits or a compaction buffer missing or not aligned (records 16 bytes, words 4)");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  AreaDev A{};
+  if (d->flags & BDPT_PARAM_AREA_LIGHTS) {
+    if (int rc = ensureAreaLights(c, st)) return rc;
+    A = c->area;  // n == 0 (no emitter): the plain instances
+  }
+  if (int rc = orderAfterLast(c, st)) return rc;
+  LightQueryDev Q{};
+  Q.surf = reinterpret_cast<const float4*>(d->surfaces);
+  Q.seeds = d->seeds;
+  Q.seedsOut = d->seedsOut;
+  Q.out = emitMode ? reinterpret_cast<float4*>(d->emits) : reinterpret_cast<float4*>(d->samples);
+  Q.cap = d->num;
+  Q.count = d->numDevice;
+  Q.minT = d->minT;
+  Q.compactRays = reinterpret_cast<float4*>(d->compactRays);
+  Q.compactItems = d->compactItems;
+  Q.compactCount = d->compactCount;
+  launchLightQuery(c->S, Q, A, emitMode, d->matIndex == 0, (d->flags & BDPT_LIGHT_USE_HINTS) != 0, st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
 int bdpt_get_refit_info(bdpt_ctx* c, bdpt_refit_info* out) {
   if (!c || !out) return BDPT_E_INVALID;
   if (!c->haveScene) return BDPT_E_STATE;

@@ -370,6 +370,41 @@ BD bool recOccludes(const SceneDev& S, uint32_t rec, f3 o, f3 d, float tmin, flo
   if ((k.flags & 1u) && alphaTestFails(S, k.aux, k.u, k.v)) return false;
   return true;
 }
+// The hint of a next-event ray (gen_nee of kernels.hip and the NEE mode of light_query.hip call these two).
+// cube-map texel of direction v (from the light): face = 2 * major axis + (negative ? 1 : 0), the two other components
+// over the major one mapped from [-1, 1] to [0, res)
+BD uint32_t cubeTexel(f3 v, uint32_t res) {
+  const float ax = fabsf(v.x), ay = fabsf(v.y), az = fabsf(v.z);
+  uint32_t face;
+  float ma, uc, vc;
+  if (ax >= ay && ax >= az) {
+    face = v.x < 0.0f ? 1u : 0u;
+    ma = ax;
+    uc = v.y;
+    vc = v.z;
+  } else if (ay >= az) {
+    face = v.y < 0.0f ? 3u : 2u;
+    ma = ay;
+    uc = v.x;
+    vc = v.z;
+  } else {
+    face = v.z < 0.0f ? 5u : 4u;
+    ma = az;
+    uc = v.x;
+    vc = v.y;
+  }
+  if (!(ma > 0.0f)) return kNoHint;  // zero or NaN direction
+  const float fr = (float)res;
+  const float fu = (uc / ma * 0.5f + 0.5f) * fr, fv = (vc / ma * 0.5f + 0.5f) * fr;
+  const uint32_t iu = fu >= fr ? res - 1u : (uint32_t)(fu < 0.0f ? 0.0f : fu), iv = fv >= fr ? res - 1u : (uint32_t)(fv < 0.0f ? 0.0f : fv);
+  return (face * res + iv) * res + iu;
+}
+BD uint32_t lightHint(const SceneDev& S, int light, f3 lightPos, f3 pos) {
+  if (!S.lightMap) return kNoHint;
+  const uint32_t t = cubeTexel(pos - lightPos, S.lightMapRes);
+  if (t == kNoHint) return kNoHint;
+  return S.lightMap[(size_t)light * 6u * S.lightMapRes * S.lightMapRes + t];
+}
 
 BD void addCount(DevCounters* c, int idx, uint32_t n) {
   if (n) atomicAdd(&c->v[blockIdx.x % kCounterShards][idx], (unsigned long long)n);

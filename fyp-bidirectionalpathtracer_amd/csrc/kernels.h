@@ -293,6 +293,22 @@ void launchShadeHits(const SceneDev& S, uint32_t numTris, const float4* rays, co
                      bool normalMap, float4* out, hipStream_t st);
 void launchBsdfQuery(const float4* surf, uint32_t cap, const uint32_t* count, bool eval, bool ggx, bool fromLobe, const uint32_t* seeds,
                      const float4* dirs, float4* out, hipStream_t st);
+// light_query.hip: bdpt_light_query.  NEE: one bdpt_light_sample (three float4) per bdpt_surface record and seed, and with
+// compactRays the rays worth tracing appended to a dense list; EMIT: one bdpt_light_emit (three float4) per seed.
+struct LightQueryDev {
+  const float4* surf;      // NEE: bdpt_surface records (six float4 each)
+  const uint32_t* seeds;   // one RNG state per item
+  uint32_t* seedsOut;      // optional: NEE the state after the selection draw, EMIT the state after all draws (seedL)
+  float4* out;             // three float4 per item
+  uint32_t cap;            // items; the capacity when count is set
+  const uint32_t* count;   // optional device word: min(*count, cap) items
+  float minT;              // tmin of the rays, and of the occluder-hint test
+  float4* compactRays;     // NEE, optional: dense list of the rays with status == NONZERO (capacity cap)
+  uint32_t* compactItems;  //   their item indices
+  uint32_t* compactCount;  //   the list's length (the caller zeroes it)
+};
+// A.n > 0: the AREA instances (the emitter table is light numLights while its W is positive)
+void launchLightQuery(const SceneDev& S, const LightQueryDev& Q, const AreaDev& A, bool emitMode, bool ggx, bool hints, hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,

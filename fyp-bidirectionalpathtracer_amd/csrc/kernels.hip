@@ -233,41 +233,7 @@ __global__ __launch_bounds__(kWave) void gbuffer_kernel(SceneDev S, GBufferDev G
 // A hint only ever picks WHICH triangle is tested first; a ray its hint does not occlude is traced as before, so the
 // image does not depend on the map's resolution, on a stale G-buffer, or on there being hints at all.
 // ------------------------------------------------------------------------------------------------
-// cube-map texel of direction v (from the light): face = 2 * major axis + (negative ? 1 : 0), the two other components
-// over the major one mapped from [-1, 1] to [0, res)
-BD uint32_t cubeTexel(f3 v, uint32_t res) {
-  const float ax = fabsf(v.x), ay = fabsf(v.y), az = fabsf(v.z);
-  uint32_t face;
-  float ma, uc, vc;
-  if (ax >= ay && ax >= az) {
-    face = v.x < 0.0f ? 1u : 0u;
-    ma = ax;
-    uc = v.y;
-    vc = v.z;
-  } else if (ay >= az) {
-    face = v.y < 0.0f ? 3u : 2u;
-    ma = ay;
-    uc = v.x;
-    vc = v.z;
-  } else {
-    face = v.z < 0.0f ? 5u : 4u;
-    ma = az;
-    uc = v.x;
-    vc = v.y;
-  }
-  if (!(ma > 0.0f)) return kNoHint;  // zero or NaN direction
-  const float fr = (float)res;
-  const float fu = (uc / ma * 0.5f + 0.5f) * fr, fv = (vc / ma * 0.5f + 0.5f) * fr;
-  const uint32_t iu = fu >= fr ? res - 1u : (uint32_t)(fu < 0.0f ? 0.0f : fu), iv = fv >= fr ? res - 1u : (uint32_t)(fv < 0.0f ? 0.0f : fv);
-  return (face * res + iv) * res + iu;
-}
-BD uint32_t lightHint(const SceneDev& S, int light, f3 lightPos, f3 pos) {
-  if (!S.lightMap) return kNoHint;
-  const uint32_t t = cubeTexel(pos - lightPos, S.lightMapRes);
-  if (t == kNoHint) return kNoHint;
-  return S.lightMap[(size_t)light * 6u * S.lightMapRes * S.lightMapRes + t];
-}
-
+// (cubeTexel / lightHint, the lookup of a light's cube map: device_trace.hpp, shared with light_query.hip)
 __global__ __launch_bounds__(kWave) void light_map_kernel(SceneDev S, uint32_t* __restrict__ maps, uint32_t res) {
   BDPT_ONE_WAVE_PER_GROUP();
   __shared__ int s_stack[kStackEntries * kWave];

@@ -23,6 +23,9 @@
  *                                   GBufferRayGen's camera, the hit shading (getVertexAttributes,
  *                                   simplePrepareShadingData) and sampleBRDF / evalBRDF for a caller's own
  *                                   integrator: surface queries
+ *   bdpt_light_query                sampleLight (BDPT/BDPTUtils.hlsli:140-152) and the light part of a next-event term
+ *                                   (getLightData, ggxDirect / lambertianDirect) for a caller's own integrator: light
+ *                                   queries
  *   bdpt_set_environment            the "EnvironmentMap" channel BDPTPass requests (BDPTPass.cpp:29; bound by no shader
  *                                   of the pass in the reference): read only with BDPT_PARAM_ENV_ON_MISS
  *   bdpt_bvh_build_check / _hash, bdpt_host_bvh_*
@@ -563,6 +566,93 @@ typedef struct bdpt_bsdf_desc {
   float* values;                /* EVAL: device, 16-byte aligned, four floats per item */
 } bdpt_bsdf_desc;
 int bdpt_bsdf_query(bdpt_ctx* ctx, const bdpt_bsdf_desc* desc, void* stream);
+
+/* ---- Light queries: the pass's light sampling, for a caller's own integrator ----
+ * bdpt_light_query closes the query family: with it a forward path tracer with next-event estimation (NEE: sampling a
+ * light directly from a surface point) is camera rays -> trace -> shade -> light query -> trace(any) -> sample -> trace ...
+ * on one stream, capturable, with no read-back.  Both modes run the device functions the pass runs, bit for bit
+ * (DESIGN.md "Light queries"): the composed calls reproduce bdpt_execute's NEE-only frame.
+ *
+ * Ordering, capture, counters, num == 0 and numDevice: as the surface queries.  The call allocates nothing, with one
+ * exception: with BDPT_PARAM_AREA_LIGHTS in flags the emitter table ("Area lights" above) is made as bdpt_execute makes it,
+ * by bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) or by the first call that needs it, which then must not be inside a stream
+ * capture (BDPT_E_STATE).
+ * lightsCount, the pass's rule: numLights, or numLights + 1 with BDPT_PARAM_AREA_LIGHTS while the table's W > 0 (light
+ * numLights is then the table); with no emitter or W == 0 the flag changes nothing, bit for bit.  matIndex (0 GGX,
+ * 1 Lambertian) and minT play the roles of bdpt_params::matIndex and minT.
+ *
+ * BDPT_LIGHT_NEE: one next-event sample per item, the light part of a NEE term of the pass.  Inputs: surfaces[i] (read:
+ *   posW, N, V, diffuse, specular, linearRoughness, prim; the BSDF's roughness is linearRoughness^2) and the RNG state
+ *   seeds[i].  Draws: r = nextRand(state) picks light min((int)(r * lightsCount), lightsCount - 1); when that is the
+ *   table, a, u1, u2 come from initRand(<state after r>, 0x41524541u) ("Area lights", NEE term).  samples[i]:
+ *     ray     org = posW, tmin = minT, dir = L, tmax = the distance to the light (the table: d (1 - 1e-4))
+ *     value   ggxDirect / lambertianDirect of a VISIBLE light with shadowMult = lightsCount: unweighted and unclamped.
+ *             Throughput, strategy weight and the clamp stay with the caller, in the pass's order:
+ *             clampVec((prevColor * value) / k, clampUpper)
+ *     light   the sampled light (numLights: the table)
+ *     status  BDPT_LIGHT_STATUS_NONZERO: value has a component that is not +-0 (a ray is worth tracing);
+ *             BDPT_LIGHT_STATUS_HINT_OCCLUDED: the occluder hint found the light occluded (no ray is needed)
+ *   A record with prim < 0 gives an all-zero sample and still takes its one draw.  seedsOut[i] (optional; may be seeds) is
+ *   the state after r: chaining it reproduces "term t uses the (t+1)-th draw after seedL".
+ *   BDPT_LIGHT_USE_HINTS: for a point or spot light whose value has a positive component, the nearest triangle the light
+ *   sees towards posW (the context's light cube maps) is tested first, exactly as the pass tests it; on success
+ *   HINT_OCCLUDED is set.  A value that is not +-0 but has no positive component (NaN where dot(N, V) <= 0 under GGX, or a
+ *   negative intensity) keeps NONZERO and is not tried: clampVec turns it into zero whatever the throughput and weight,
+ *   so the pass, which tests its clamped term, never tries it either.
+ *   Directional lights and the table never use hints.  A hint only ever saves a ray: visibility answers do not change.
+ *   Compaction (compactRays, compactItems and compactCount, all or none): every item whose status is exactly NONZERO appends
+ *   its ray to compactRays and its index to compactItems at a position taken from *compactCount (one atomic per wave of 64
+ *   items).  The caller zeroes the word before the call and owns capacity num of both lists; the order inside the lists is
+ *   unspecified.  compactRays / compactCount go straight to bdpt_trace_rays (BDPT_TRACE_ANY, numRaysDevice = compactCount).
+ *   Without compaction the caller traces all num rays and masks by status.
+ *
+ * BDPT_LIGHT_EMIT: the start of a light subpath per item (sampleLight).  Input: seeds[i]; no surfaces.  Draws: the
+ *   selection draw; then sampleUnitSphere (three draws per rejection round; not for directional lights, which start from
+ *   dirW) and getCosHemisphereSample (two draws) around that direction; for the table a, u1, u2, the side and the cosine
+ *   direction ("Area lights", light subpath start: six draws).  emits[i]:
+ *     ray     org = lightPath[0].pos, tmin = minT, dir = the sampled direction, tmax = 1e38
+ *     color   lightPath[0].color: the light's intensity, or Le * 2 pi / p_A for the table
+ *     light   the sampled light
+ *   lightPath[0].pdfForward is 1 / lightsCount and is not stored.  seedsOut[i] (optional) is the state after all draws: the
+ *   pass's seedL.
+ *
+ * Errors (nothing is enqueued): no scene BDPT_E_STATE; a NULL context or desc, an unknown mode or flag, matIndex > 1, a
+ * missing or misaligned buffer (records 16 bytes, words 4), compaction buffers given in part, compaction or hints in EMIT
+ * mode BDPT_E_INVALID. */
+#define BDPT_LIGHT_NEE 0u
+#define BDPT_LIGHT_EMIT 1u
+#define BDPT_LIGHT_USE_HINTS 1u /* flags, beside BDPT_PARAM_AREA_LIGHTS */
+#define BDPT_LIGHT_STATUS_NONZERO 1u
+#define BDPT_LIGHT_STATUS_HINT_OCCLUDED 2u
+typedef struct bdpt_light_sample {
+  bdpt_ray ray;
+  float value[3];
+  uint16_t light;
+  uint16_t status; /* BDPT_LIGHT_STATUS_* */
+} bdpt_light_sample; /* 48 bytes: three float4 */
+typedef struct bdpt_light_emit {
+  bdpt_ray ray;
+  float color[3];
+  uint32_t light;
+} bdpt_light_emit; /* 48 bytes: three float4 */
+typedef struct bdpt_light_desc {
+  uint32_t mode;                /* BDPT_LIGHT_* */
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  uint32_t matIndex;            /* NEE: 0 GGX, 1 Lambertian */
+  uint32_t flags;               /* BDPT_PARAM_AREA_LIGHTS, BDPT_LIGHT_USE_HINTS (NEE) or 0 */
+  float minT;                   /* tmin of the rays and of the hint test (bdpt_params::minT) */
+  uint32_t reserved;
+  const bdpt_surface* surfaces; /* NEE: device, 16-byte aligned, num records */
+  const uint32_t* seeds;        /* device, one RNG state per item */
+  uint32_t* seedsOut;           /* optional: device, one state per item */
+  bdpt_light_sample* samples;   /* NEE: device, 16-byte aligned, one per item */
+  bdpt_light_emit* emits;       /* EMIT: device, 16-byte aligned, one per item */
+  bdpt_ray* compactRays;        /* NEE, optional: device, 16-byte aligned, capacity num */
+  uint32_t* compactItems;       /* NEE, with compactRays: device, capacity num */
+  uint32_t* compactCount;       /* NEE, with compactRays: device word, zeroed by the caller */
+} bdpt_light_desc;
+int bdpt_light_query(bdpt_ctx* ctx, const bdpt_light_desc* desc, void* stream);
 
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
