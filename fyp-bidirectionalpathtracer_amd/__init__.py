@@ -429,6 +429,128 @@ class Context:
         return self._surface_query("emit_lights", [("seeds", seeds, None, u32)], (12, i32), run, out, count,
                                    extras=[("seeds_out", seeds_out, None, u32)], fn="bdpt_light_query")
 
+    # ---- connection queries (include/bdpt.h "Connection queries") ----
+    @staticmethod
+    def _compact_extras(what, compact):
+        import torch
+        u32 = (torch.int32, torch.uint32)
+        if compact is None:
+            return [], (None, None, None)
+        if not isinstance(compact, (tuple, list)) or len(compact) != 3 or any(t is None for t in compact):
+            raise BdptError(f"{what}: compact must be (rays, items, count), all three")
+        return [("compact rays", compact[0], 8, (torch.float32,)), ("compact items", compact[1], None, u32),
+                ("compact count", compact[2], 1, u32)], tuple(compact)
+
+    def _gpu_only(self, what, tensors):
+        for name, t in tensors:
+            if t is not None and not getattr(t, "is_cuda", False):
+                raise BdptError(f"{what}: {name} must be a GPU tensor on cuda:{self.device} (this query takes device memory only)")
+
+    def connect_vertices(self, eye, light, mat_index=0, min_t=1e-4, eye_prev=None, light_prev=None, eye_specular=None,
+                         light_specular=None, out=None, compact=None, count=None, stream=None):
+        """bdpt_connect_query(VERTICES): eye vertex eye[i] against light vertex light[i], both (N, 24) bdpt_surface records
+        (GPU tensors).  eye_prev / light_prev (N, 4) float32: the predecessors' positions (without them the records' V is the
+        outgoing direction); eye_specular / light_specular (N,) uint8: the sampled lobe's specular flag (None = 0).  Returns
+        (N, 12) float32 in the bdpt_connect_sample layout: 0-7 the connection ray (bdpt_ray), 8-10 (fsL * G) * fsE, unweighted
+        and unclamped, 11 (through .view(torch.int32)) the status, bit 0 = the value is non-zero.  compact = (rays (N, 8)
+        float32, items (N,), count (1,), zeroed by the caller) takes the dense list of the non-zero pairs' rays."""
+        import torch
+        i32, f32, u8 = (torch.float32, torch.int32), (torch.float32,), (torch.uint8,)
+        mat, _ = self._bsdf_mode("connect_vertices", mat_index, False)
+        self._gpu_only("connect_vertices", [("eye", eye), ("light", light)])
+        extras = [("eye_prev", eye_prev, 4, f32), ("light_prev", light_prev, 4, f32), ("eye_specular", eye_specular, None, u8),
+                  ("light_specular", light_specular, None, u8)]
+        more, compact = self._compact_extras("connect_vertices", compact)
+
+        def run(ptrs, n, cnt, res):
+            d = abi.ConnectDesc()
+            d.mode, d.num, d.numDevice, d.matIndex, d.minT = abi.CONNECT_VERTICES, n, cnt, mat, float(min_t)
+            d.eye, d.light, d.samples = ptrs[0], ptrs[1], res
+            d.eyePrev, d.lightPrev, d.eyeSpecular, d.lightSpecular = (None if t is None else t.data_ptr()
+                                                                      for t in (eye_prev, light_prev, eye_specular, light_specular))
+            d.compactRays, d.compactItems, d.compactCount = (None if t is None else t.data_ptr() for t in compact)
+            return self._lib.bdpt_connect_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("connect_vertices", [("eye", eye, 24, i32), ("light", light, 24, i32)], (12, i32), run, out, count,
+                                   extras=extras + more, fn="bdpt_connect_query")
+
+    def connect_camera(self, light, width, height, pixel_jitter=(0.0, 0.0), mat_index=0, min_t=1e-4, light_specular=None,
+                       out=None, compact=None, count=None, stream=None):
+        """bdpt_connect_query(CAMERA): light vertex light[i] ((N, 24) bdpt_surface records, GPU tensor; V = the direction to
+        the predecessor) against the context's camera for a width x height frame.  Returns (N, 16) float32 in the
+        bdpt_camera_sample layout: 0-7 the ray to the camera (bdpt_ray), 8-10 f, 11 G, 12 the target pixel x + y * width and
+        13 the status (both through .view(torch.int32); pixel -1 = none; status bit 1 = a pixel, bit 0 = f and G non-zero).
+        compact as for connect_vertices: the rays of the items with a pixel."""
+        import torch
+        i32, u8 = (torch.float32, torch.int32), (torch.uint8,)
+        mat, _ = self._bsdf_mode("connect_camera", mat_index, False)
+        self._gpu_only("connect_camera", [("light", light)])
+        w, h = int(width), int(height)
+        if w <= 0 or h <= 0 or w * h >= 2**32:
+            raise BdptError(f"connect_camera: bad frame size {w} x {h}")
+        if len(pixel_jitter) != 2:
+            raise BdptError("connect_camera: pixel_jitter must be two floats")
+        more, compact = self._compact_extras("connect_camera", compact)
+
+        def run(ptrs, n, cnt, res):
+            d = abi.ConnectDesc()
+            d.mode, d.num, d.numDevice, d.matIndex, d.minT = abi.CONNECT_CAMERA, n, cnt, mat, float(min_t)
+            d.light, d.cameraSamples, d.width, d.height = ptrs[0], res, w, h
+            d.pixelJitter[0], d.pixelJitter[1] = float(pixel_jitter[0]), float(pixel_jitter[1])
+            d.lightSpecular = None if light_specular is None else light_specular.data_ptr()
+            d.compactRays, d.compactItems, d.compactCount = (None if t is None else t.data_ptr() for t in compact)
+            return self._lib.bdpt_connect_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("connect_camera", [("light", light, 24, i32)], (16, i32), run, out, count,
+                                   extras=[("light_specular", light_specular, None, u8)] + more, fn="bdpt_connect_query")
+
+    def splat_add(self, splat, pixels, values, visible=None, items=None, count=None, stream=None):
+        """bdpt_splat_add: entry j adds values[k] ((M, 4) float32, xyz the clamped term) to pixel pixels[k] ((M,) int32 /
+        uint32) of `splat`, k = items[j] ((n,) int32 / uint32) or j, when visible[j] ((n,) uint8) is non-zero or absent and
+        the pixel is below numPixels.  `splat`: a contiguous GPU tensor of numPixels x 4 64-bit words ((P, 4) int64 / uint64),
+        or the (pointer, number of 64-bit words) pair Context.splat_buffer() returns, for a whole-frame context's own
+        buffer.  n = len(items) when given, else M; `count` (1,) caps it on the device.  GPU tensors only; nothing is
+        returned."""
+        import torch
+        u32 = (torch.int32, torch.uint32)
+        own = None
+        if isinstance(splat, tuple):
+            if len(splat) != 2 or not all(isinstance(v, int) and not isinstance(v, bool) for v in splat) or not splat[0] \
+                    or splat[1] % 4 or splat[1] // 4 >= 2**32:
+                raise BdptError("splat_add: a (pointer, words) splat must be what Context.splat_buffer() returns")
+            own, splat = splat, None
+        self._gpu_only("splat_add", [("splat", splat), ("pixels", pixels), ("values", values), ("visible", visible), ("items", items)])
+        for name, t in (("splat", own if splat is None else splat), ("pixels", pixels), ("values", values)):
+            if t is None:
+                raise BdptError(f"splat_add: {name} is required")
+        if pixels.dim() != 1:
+            raise BdptError("splat_add: pixels must be (M,) int32/uint32")
+        m = int(pixels.shape[0])
+        self._check_gpu(pixels, "splat_add", "pixels", (m,), u32)
+        self._check_gpu(values, "splat_add", "values", (m, 4), (torch.float32,))
+        n = m
+        if items is not None:
+            if items.dim() != 1:
+                raise BdptError("splat_add: items must be (n,) int32/uint32")
+            n = int(items.shape[0])
+            self._check_gpu(items, "splat_add", "items", (n,), u32)
+        if visible is not None:
+            self._check_gpu(visible, "splat_add", "visible", (n,), (torch.uint8,))
+        if count is not None:
+            self._check_gpu(count, "splat_add", "count", (1,), u32)
+        if own is None:
+            if splat.dim() != 2 or splat.shape[1] != 4 or splat.shape[0] >= 2**32:
+                raise BdptError("splat_add: splat must be (numPixels, 4) int64/uint64")
+            self._check_gpu(splat, "splat_add", "splat", tuple(splat.shape), (torch.int64, torch.uint64))
+            own = (splat.data_ptr(), 4 * int(splat.shape[0]))
+        d = abi.SplatDesc()
+        d.num, d.numPixels = n, own[1] // 4
+        d.numDevice = None if count is None else count.data_ptr()
+        d.pixels, d.values, d.splat = pixels.data_ptr(), values.data_ptr(), own[0]
+        d.visible = None if visible is None else visible.data_ptr()
+        d.items = None if items is None else items.data_ptr()
+        self._check(self._lib.bdpt_splat_add(self._h, C.byref(d), stream), "bdpt_splat_add")
+
     @staticmethod
     def _bsdf_mode(what, mat_index, from_lobe):
         if mat_index not in (0, 1) or isinstance(mat_index, bool):
@@ -958,6 +1080,28 @@ class FramePipeline:
                                    self._stream_ptr())
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (seeds, seeds_out, count, res))
         return res
+
+    def connect_vertices(self, eye, light, eye_prev=None, light_prev=None, eye_specular=None, light_specular=None, out=None,
+                         compact=None, count=None):
+        """Context.connect_vertices with the pipeline's BSDF (mat_index) and min_t, on its stream."""
+        res = self.ctx.connect_vertices(eye, light, self.mat_index, self.min_t, eye_prev, light_prev, eye_specular, light_specular,
+                                        out, compact, count, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev),
+                        (eye, light, eye_prev, light_prev, eye_specular, light_specular, count, res) + tuple(compact or ()))
+        return res
+
+    def connect_camera(self, light, pixel_jitter=(0.0, 0.0), light_specular=None, out=None, compact=None, count=None):
+        """Context.connect_camera with the pipeline's frame size, BSDF (mat_index) and min_t, on its stream.  pixel_jitter:
+        the bdpt_params::pixelJitter of the frame the splats belong to."""
+        res = self.ctx.connect_camera(light, self.W, self.H, pixel_jitter, self.mat_index, self.min_t, light_specular, out, compact,
+                                      count, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (light, light_specular, count, res) + tuple(compact or ()))
+        return res
+
+    def splat_add(self, splat, pixels, values, visible=None, items=None, count=None):
+        """Context.splat_add on this pipeline's stream."""
+        self.ctx.splat_add(splat, pixels, values, visible, items, count, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (splat, pixels, values, visible, items, count))
 
     def set_lights(self, lights):
         """Move the scene's lights (Context.set_lights on this pipeline's stream); accumulation restarts."""

@@ -38,6 +38,8 @@ BSDF_SAMPLE, BSDF_EVAL = 0, 1
 LIGHT_NEE, LIGHT_EMIT = 0, 1
 LIGHT_USE_HINTS = 1
 LIGHT_STATUS_NONZERO, LIGHT_STATUS_HINT_OCCLUDED = 1, 2
+CONNECT_VERTICES, CONNECT_CAMERA = 0, 1
+CONNECT_STATUS_NONZERO, CONNECT_STATUS_PIXEL = 1, 2
 
 
 class Material(C.Structure):
@@ -203,6 +205,29 @@ class LightDesc(C.Structure):
                 ("compactRays", C.c_void_p), ("compactItems", C.c_void_p), ("compactCount", C.c_void_p)]
 
 
+class ConnectSample(C.Structure):
+    _fields_ = [("ray", Ray), ("value", C.c_float * 3), ("status", C.c_uint32)]
+
+
+class CameraSample(C.Structure):
+    _fields_ = [("ray", Ray), ("f", C.c_float * 3), ("G", C.c_float), ("pixel", C.c_uint32), ("status", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class ConnectDesc(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("num", C.c_uint32), ("numDevice", C.c_void_p), ("matIndex", C.c_uint32),
+                ("flags", C.c_uint32), ("minT", C.c_float), ("reserved", C.c_uint32), ("eye", C.c_void_p), ("light", C.c_void_p),
+                ("eyePrev", C.c_void_p), ("lightPrev", C.c_void_p), ("eyeSpecular", C.c_void_p), ("lightSpecular", C.c_void_p),
+                ("samples", C.c_void_p), ("cameraSamples", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("pixelJitter", C.c_float * 2), ("compactRays", C.c_void_p), ("compactItems", C.c_void_p),
+                ("compactCount", C.c_void_p)]
+
+
+class SplatDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("numPixels", C.c_uint32), ("numDevice", C.c_void_p), ("pixels", C.c_void_p),
+                ("values", C.c_void_p), ("visible", C.c_void_p), ("items", C.c_void_p), ("splat", C.c_void_p)]
+
+
 class AreaLightInfo(C.Structure):
     _fields_ = [("numEmitters", C.c_uint32), ("numTextured", C.c_uint32), ("totalWeight", C.c_float), ("reserved", C.c_uint32)]
 
@@ -229,6 +254,8 @@ PROTOTYPES = {
     "bdpt_shade_hits": (C.c_int, [C.c_void_p, C.POINTER(ShadeDesc), C.c_void_p]),
     "bdpt_bsdf_query": (C.c_int, [C.c_void_p, C.POINTER(BsdfDesc), C.c_void_p]),
     "bdpt_light_query": (C.c_int, [C.c_void_p, C.POINTER(LightDesc), C.c_void_p]),
+    "bdpt_connect_query": (C.c_int, [C.c_void_p, C.POINTER(ConnectDesc), C.c_void_p]),
+    "bdpt_splat_add": (C.c_int, [C.c_void_p, C.POINTER(SplatDesc), C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),
     "bdpt_host_bvh_recs_hash": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

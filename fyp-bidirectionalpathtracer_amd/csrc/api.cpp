@@ -1138,6 +1138,99 @@ int bdpt_light_query(bdpt_ctx* c, const bdpt_light_desc* d, void* stream) {
   return BDPT_OK;
 }
 
+static_assert(sizeof(bdpt_connect_sample) == 48 && sizeof(bdpt_camera_sample) == 64 && offsetof(bdpt_connect_sample, status) == 44 &&
+                  offsetof(bdpt_camera_sample, G) == 44 && offsetof(bdpt_camera_sample, pixel) == 48,
+              "the connection query kernels write a record as three / four float4");
+int bdpt_connect_query(bdpt_ctx* c, const bdpt_connect_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "connect_query: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (d->mode > BDPT_CONNECT_CAMERA || d->matIndex > 1 || d->flags || d->reserved) {
+    fail(c, "connect_query: unknown mode, non-zero flags or reserved, or matIndex > 1");
+    return BDPT_E_INVALID;
+  }
+  const bool camMode = d->mode == BDPT_CONNECT_CAMERA;
+  if (camMode && !c->haveCamera) {
+    fail(c, "connect_query: BDPT_CONNECT_CAMERA without a camera (bdpt_set_camera first)");
+    return BDPT_E_STATE;
+  }
+  if (camMode && (!d->width || !d->height || (uint64_t)d->width * d->height >= (1ull << 32))) {
+    fail(c, "connect_query: width and height must be > 0 with width * height < 2^32");
+    return BDPT_E_INVALID;
+  }
+  const bool compact = d->compactRays || d->compactItems || d->compactCount;
+  if (compact && !(d->compactRays && d->compactItems && d->compactCount)) {
+    fail(c, "connect_query: compactRays, compactItems and compactCount go together");
+    return BDPT_E_INVALID;
+  }
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->light, 16) || (d->numDevice && !aligned(d->numDevice, 4)) ||
+      (camMode ? !aligned(d->cameraSamples, 16)
+               : (!aligned(d->eye, 16) || !aligned(d->samples, 16) || (d->eyePrev && !aligned(d->eyePrev, 16)) ||
+                  (d->lightPrev && !aligned(d->lightPrev, 16)))) ||
+      (compact && (!aligned(d->compactRays, 16) || !aligned(d->compactItems, 4) || !aligned(d->compactCount, 4)))) {
+    fail(c, "connect_query: eye, light, samples, a predecessor or a compaction buffer missing or not aligned (records 16 bytes, words 4)");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  ConnectQueryDev Q{};
+  Q.light = reinterpret_cast<const float4*>(d->light);
+  Q.lightSpecular = d->lightSpecular;
+  if (camMode) {
+    Q.out = reinterpret_cast<float4*>(d->cameraSamples);
+    Q.width = d->width;
+    Q.height = d->height;
+    Q.jitter[0] = d->pixelJitter[0];
+    Q.jitter[1] = d->pixelJitter[1];
+  } else {
+    Q.eye = reinterpret_cast<const float4*>(d->eye);
+    Q.eyePrev = reinterpret_cast<const float4*>(d->eyePrev);
+    Q.lightPrev = reinterpret_cast<const float4*>(d->lightPrev);
+    Q.eyeSpecular = d->eyeSpecular;
+    Q.out = reinterpret_cast<float4*>(d->samples);
+  }
+  Q.cap = d->num;
+  Q.count = d->numDevice;
+  Q.minT = d->minT;
+  Q.compactRays = reinterpret_cast<float4*>(d->compactRays);
+  Q.compactItems = d->compactItems;
+  Q.compactCount = d->compactCount;
+  launchConnectQuery(Q, camMode ? &c->cam : nullptr, d->matIndex == 0, st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
+int bdpt_splat_add(bdpt_ctx* c, const bdpt_splat_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->pixels, 4) || !aligned(d->values, 16) || !aligned(d->splat, 16) || (d->items && !aligned(d->items, 4)) ||
+      (d->numDevice && !aligned(d->numDevice, 4))) {
+    fail(c, "splat_add: pixels, values, splat, items or numDevice missing or not aligned (splat and values 16 bytes, words 4)");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  SplatAddDev A{};
+  A.pixels = d->pixels;
+  A.values = reinterpret_cast<const float4*>(d->values);
+  A.visible = d->visible;
+  A.items = d->items;
+  A.splat = reinterpret_cast<unsigned long long*>(d->splat);
+  A.numPixels = d->numPixels;
+  A.cap = d->num;
+  A.count = d->numDevice;
+  launchSplatAdd(A, st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
 int bdpt_get_refit_info(bdpt_ctx* c, bdpt_refit_info* out) {
   if (!c || !out) return BDPT_E_INVALID;
   if (!c->haveScene) return BDPT_E_STATE;

@@ -309,6 +309,39 @@ struct LightQueryDev {
 };
 // A.n > 0: the AREA instances (the emitter table is light numLights while its W is positive)
 void launchLightQuery(const SceneDev& S, const LightQueryDev& Q, const AreaDev& A, bool emitMode, bool ggx, bool hints, hipStream_t st);
+// connect_query.hip: bdpt_connect_query.  VERTICES: one bdpt_connect_sample (three float4) per pair of bdpt_surface records;
+// CAMERA: one bdpt_camera_sample (four float4) per record; with compactRays the rays worth tracing go to a dense list.
+struct ConnectQueryDev {
+  const float4* eye;             // VERTICES: bdpt_surface records (six float4 each)
+  const float4* light;           // both modes
+  const float4* eyePrev;         // VERTICES, optional: the predecessors' positions (xyz of a float4)
+  const float4* lightPrev;
+  const uint8_t* eyeSpecular;    // optional: bdpt_bsdf_sample::specular of the vertex (NULL = 0)
+  const uint8_t* lightSpecular;
+  float4* out;                   // three (VERTICES) or four (CAMERA) float4 per item
+  uint32_t cap;                  // items; the capacity when count is set
+  const uint32_t* count;         // optional device word: min(*count, cap) items
+  float minT;                    // tmin of the rays
+  uint32_t width, height;        // CAMERA: the frame
+  float jitter[2];               // CAMERA: bdpt_params::pixelJitter
+  float4* compactRays;           // optional: dense list of the rays with NONZERO (VERTICES) / PIXEL (CAMERA), capacity cap
+  uint32_t* compactItems;        //   their item indices
+  uint32_t* compactCount;        //   the list's length (the caller zeroes it)
+};
+// cam: the context's camera for CAMERA mode, nullptr for VERTICES
+void launchConnectQuery(const ConnectQueryDev& Q, const bdpt_camera* cam, bool ggx, hipStream_t st);
+// bdpt_splat_add: entry j adds values[k] to splat[pixels[k]], k = items ? items[j] : j, when visible[j] (or no visible)
+struct SplatAddDev {
+  const uint32_t* pixels;
+  const float4* values;
+  const uint8_t* visible;  // optional
+  const uint32_t* items;   // optional
+  unsigned long long* splat;
+  uint32_t numPixels;
+  uint32_t cap;
+  const uint32_t* count;   // optional device word
+};
+void launchSplatAdd(const SplatAddDev& A, hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,

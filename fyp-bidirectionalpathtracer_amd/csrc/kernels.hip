@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "device_area.hpp"
+#include "device_connect.hpp"  // pairRay, pairValue, splatTarget, splatTerm (shared with connect_query.hip)
 #include "device_math.hpp"
 #include "device_scene.hpp"
 #include "device_trace.hpp"
@@ -940,9 +941,7 @@ __global__ __launch_bounds__(kWave) void gen_splat_kernel(SceneDev S, FrameDev F
   act = act && t < D;
   const uint32_t p = act ? P.queue[0][i] : 0u;
   const int real = act ? (int)P.lightReal[p] : 0;
-  const f3 camPos = ld3(F.cam.posW);
-  const f3 U = ld3(F.cam.cameraU), Vc = ld3(F.cam.cameraV), Wc = ld3(F.cam.cameraW);
-  const f3 cameraN = normalize(Wc);
+  const SplatCam cam = splatCam(F.cam);
   bool emit = false, hinted = false;
   f3 pos = mk(0), dirToCamera = mk(0), shade = mk(0);
   float disToCamera = 0.0f;
@@ -951,38 +950,27 @@ __global__ __launch_bounds__(kWave) void gen_splat_kernel(SceneDev S, FrameDev F
     Vtx lv;
     loadSurf<GGX>(P, PATH_LIGHT, t + 1, p, lv);
     pos = lv.pos;
-    dirToCamera = normalize(camPos - lv.pos);
-    disToCamera = length(camPos - lv.pos);
-    if (dot(cameraN, dirToCamera) < 0) {
-      float d1 = dot(dirToCamera, U) / dot(U, U);
-      float d2 = dot(dirToCamera, Vc) / dot(Vc, Vc);
-      float d3 = dot(dirToCamera, Wc) / dot(Wc, Wc);
-      float nx = d1 / d3, ny = -d2 / d3;
-      float px = nx * 0.5f + 0.5f, py = ny * 0.5f + 0.5f;
-      float fx = rintf(px * (float)F.W - F.p.pixelJitter[0]);
-      float fy = rintf(py * (float)F.H - F.p.pixelJitter[1]);
-      const bool inside = (fx >= 0.0f && fx < (float)F.W && fy >= 0.0f && fy < (float)F.H);
-      // The reference traces this ray whatever the value (its write saturates the target pixel) — but a target outside
-      // the frame has no pixel to write (quirk 8: the out-of-range UAV write is dropped), so such a ray decides nothing
-      // and is not traced.
-      emit = inside;
-      if (inside) {
-        target = (uint32_t)splatIndex(F.sl, F.W, (uint32_t)(int)fx, (uint32_t)(int)fy);
-        float theta1 = saturate(fabsf(dot(dirToCamera, cameraN)));
-        float theta2 = saturate(fabsf(dot(dirToCamera, lv.N)));
-        float invDisToCamera = 1.0f / disToCamera;
-        float Gt = theta1 * theta2 * invDisToCamera * invDisToCamera;
-        f3 vV = mk(0);
-        if (GGX) vV = ldPlane3(P, PATH_LIGHT, t + 1, F_V, p);
-        f3 fr = evalBRDF<GGX>(vV, normalize(camPos - lv.pos), lv.N, lv.N, lv.dif, lv.spec, lv.rough, lv.isSpec);
-        f3 prevColor = ldPlane3(P, PATH_LIGHT, t, F_COL, p);
-        shade = clampVec(applyStrategyWeight(F, P, p, (prevColor * fr) * Gt, t + 2, 0, t + 1), F.p.clampUpper);
-        if (isnan3(shade)) shade = mk(0);
-        // the surface the camera sees through the target pixel is tried first: a hidden vertex lands no splat and needs no ray
-        if (F.hintPix && recOccludes(S, F.hintPix[(size_t)(uint32_t)(int)fy * F.W + (uint32_t)(int)fx], pos, dirToCamera, F.p.minT, disToCamera)) {
-          emit = false;
-          hinted = true;
-        }
+    dirToCamera = normalize(cam.pos - lv.pos);
+    disToCamera = length(cam.pos - lv.pos);
+    float fx = 0.0f, fy = 0.0f;
+    // The reference traces this ray whatever the value (its write saturates the target pixel) — but a target outside
+    // the frame has no pixel to write (quirk 8: the out-of-range UAV write is dropped), so such a ray decides nothing
+    // and is not traced.
+    emit = splatTarget(cam, dirToCamera, F.W, F.H, F.p.pixelJitter[0], F.p.pixelJitter[1], fx, fy);
+    if (emit) {
+      target = (uint32_t)splatIndex(F.sl, F.W, (uint32_t)(int)fx, (uint32_t)(int)fy);
+      f3 vV = mk(0);
+      if (GGX) vV = ldPlane3(P, PATH_LIGHT, t + 1, F_V, p);
+      f3 fr;
+      float Gt;
+      splatTerm<GGX>(cam, lv, vV, dirToCamera, disToCamera, fr, Gt);
+      f3 prevColor = ldPlane3(P, PATH_LIGHT, t, F_COL, p);
+      shade = clampVec(applyStrategyWeight(F, P, p, (prevColor * fr) * Gt, t + 2, 0, t + 1), F.p.clampUpper);
+      if (isnan3(shade)) shade = mk(0);
+      // the surface the camera sees through the target pixel is tried first: a hidden vertex lands no splat and needs no ray
+      if (F.hintPix && recOccludes(S, F.hintPix[(size_t)(uint32_t)(int)fy * F.W + (uint32_t)(int)fx], pos, dirToCamera, F.p.minT, disToCamera)) {
+        emit = false;
+        hinted = true;
       }
     }
   }
@@ -1115,33 +1103,14 @@ __global__ __launch_bounds__(kWave) void gen_connect_kernel(SceneDev S, FrameDev
       }
       const float4 qp = s_light[e][lightLength - 1][0];  // light vertex lightLength - 1 (zero past the end)
       const f3 lprev = mk(qp.x, qp.y, qp.z);
-      const f3 vecAB = le.pos - ev.pos;
-      const float invLengthAB = 1.0f / length(vecAB);
-      const f3 dirG = vecAB * invLengthAB;
-      const float cosA = fabsf(dot(ev.N, dirG));
-      const float cosB = fabsf(dot(le.N, dirG));
-      const float Gt = cosA * cosB * invLengthAB * invLengthAB;
-      const f3 connectDir = normalize(ev.pos - le.pos);
       const f3 woL = normalize(lprev - le.pos);
       f3 cst;
-      const f3 fsL = evalBRDF<GGX>(connectDir, woL, le.N, le.N, le.dif, le.spec, le.rough, le.isSpec);
-      if (allZero(fsL)) {
-        cst = fsL;
-      } else {
-        const f3 fsE = evalBRDF<GGX>(-connectDir, woEs, ev.N, ev.N, ev.dif, ev.spec, ev.rough, ev.isSpec);
-        if (allZero(fsE)) {
-          cst = fsE;
-        } else {
-          const f3 k = (fsL * Gt) * fsE;
-          cst = (aLs * k) * aEs;
-        }
-      }
+      if (pairValue<GGX>(ev, woEs, le, woL, cst)) cst = (aLs * cst) * aEs;  // (a short cut's zero stays as it is)
       shade = clampVec(applyStrategyWeight(F, P, p, cst, totalLength, c, lightLength), F.p.clampUpper);
       if (isnan3(shade)) shade = mk(0);
       if (!allZero(shade)) {
         emit = true;
-        lengthAB = length(le.pos - ev.pos);
-        dirAB = (le.pos - ev.pos) / lengthAB;
+        pairRay(ev.pos, le.pos, dirAB, lengthAB);
       }
     }
     const uint32_t id = emitRay(P, RAY_PAIRS, emit, ev.pos, dirAB, lengthAB, shade);
@@ -1399,8 +1368,7 @@ __global__ __launch_bounds__(kWave) void lazy_gen_kernel(FrameDev F, PathBuf P, 
     if (emit) {
       posA = (cameraLength <= eyeLast) ? ldPlane3(P, PATH_EYE, cameraLength, F_POS, p) : mk(0);
       const f3 posB = (lightLength <= lightLast) ? ldPlane3(P, PATH_LIGHT, lightLength, F_POS, p) : mk(0);
-      lengthAB = length(posB - posA);
-      dirAB = (posB - posA) / lengthAB;
+      pairRay(posA, posB, dirAB, lengthAB);
     }
     const uint32_t id = emitRay(P, RAY_PAIRS, emit, posA, dirAB, lengthAB, mk(0));
     if (emit) P.lazyRay[(size_t)(taken + rank) * P.Np + p] = id;

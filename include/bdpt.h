@@ -26,6 +26,12 @@
  *   bdpt_light_query                sampleLight (BDPT/BDPTUtils.hlsli:140-152) and the light part of a next-event term
  *                                   (getLightData, ggxDirect / lambertianDirect) for a caller's own integrator: light
  *                                   queries
+ *   bdpt_connect_query              the vertex connections (BDPTMain.rt.hlsl:212-233, evalGWithoutV /
+ *                                   getUnweightedContribution BDPTUtils.hlsli:172-224) and the light-tracing splat
+ *                                   (BDPTMain.rt.hlsl:171-208, getLaunchIndexFromDirection BDPTUtils.hlsli:129-138)
+ *                                   for a caller's own integrator: connection queries
+ *   bdpt_splat_add                  the splat's write to the pixel it lands in (BDPTMain.rt.hlsl:186-204) as the
+ *                                   fixed-point sum bdpt_splat_buffer describes below, for a caller's lists
  *   bdpt_set_environment            the "EnvironmentMap" channel BDPTPass requests (BDPTPass.cpp:29; bound by no shader
  *                                   of the pass in the reference): read only with BDPT_PARAM_ENV_ON_MISS
  *   bdpt_bvh_build_check / _hash, bdpt_host_bvh_*
@@ -568,7 +574,8 @@ typedef struct bdpt_bsdf_desc {
 int bdpt_bsdf_query(bdpt_ctx* ctx, const bdpt_bsdf_desc* desc, void* stream);
 
 /* ---- Light queries: the pass's light sampling, for a caller's own integrator ----
- * bdpt_light_query closes the query family: with it a forward path tracer with next-event estimation (NEE: sampling a
+ * bdpt_light_query closes the forward half of the query family ("Connection queries" below has the two bidirectional
+ * strategies): with it a forward path tracer with next-event estimation (NEE: sampling a
  * light directly from a surface point) is camera rays -> trace -> shade -> light query -> trace(any) -> sample -> trace ...
  * on one stream, capturable, with no read-back.  Both modes run the device functions the pass runs, bit for bit
  * (DESIGN.md "Light queries"): the composed calls reproduce bdpt_execute's NEE-only frame.
@@ -653,6 +660,120 @@ typedef struct bdpt_light_desc {
   uint32_t* compactCount;       /* NEE, with compactRays: device word, zeroed by the caller */
 } bdpt_light_desc;
 int bdpt_light_query(bdpt_ctx* ctx, const bdpt_light_desc* desc, void* stream);
+
+/* ---- Connection queries: vertex pairs, camera splats and splat accumulation, for a caller's own integrator ----
+ * The two strategies of the pass that join a light subpath to the eye side.  With the queries above every strategy is a
+ * sequence of calls on one stream: the composed calls reproduce bdpt_execute's connection-only and splat-only frames bit for
+ * bit (DESIGN.md "Connection queries").  Both calls run the device functions the pass runs (csrc/device_connect.hpp).
+ *
+ * Ordering, capture, counters, num == 0 and numDevice: as the surface queries — enqueued on `stream` behind the context's
+ * previous call; no allocation and no synchronise (one kernel node in a captured graph); bdpt_get_counters and
+ * bdpt_get_stage_times are left alone; items at or beyond min(*numDevice, num) are neither read nor written.
+ * matIndex (0 GGX, 1 Lambertian) and minT play the roles of bdpt_params::matIndex and minT; the BSDF's roughness is
+ * linearRoughness^2 as in bdpt_bsdf_query.  Vertices are bdpt_surface records (read: posW, N, diffuse, specular,
+ * linearRoughness, prim, and V where stated; Lambertian reads neither V nor specular).
+ *
+ * BDPT_CONNECT_VERTICES: eye vertex eye[i] against light vertex light[i] (gen_connect's ev and le).
+ *   eyePrev / lightPrev (optional, four floats per item, xyz used): the positions of the two predecessors; the outgoing
+ *     directions are then normalize(prev - posW), as the pass forms woE and woL.  Without them the record's V is used: the
+ *     same bits for a real vertex, not for the walk's ghost vertices (a copy of their predecessor).
+ *   eyeSpecular / lightSpecular (optional bytes): bdpt_bsdf_sample::specular of the sample that left the vertex.  NULL
+ *     means 0, which is what the pass uses without BDPT_PARAM_SPECULAR_FROM_LOBE.
+ *   samples[i]:
+ *     ray     org = eye.posW, tmin = minT, tmax = length(light.posW - eye.posW), dir = (light.posW - eye.posW) / tmax,
+ *             written whatever prim says.  Coincident points give tmax 0 and a NaN direction: bdpt_trace_rays answers
+ *             "miss", i.e. unoccluded for BDPT_TRACE_ANY, as the pass's lazy rounds rely on.
+ *     value   (fsL * G) * fsE with fsL = evalBRDF(connectDir, woL, ...) at the light vertex, fsE = evalBRDF(-connectDir,
+ *             woE, ...) at the eye vertex, connectDir = normalize(eye.posW - light.posW), G = evalGWithoutV.  The pass's
+ *             short cuts are kept: fsL all zero gives fsL, then fsE all zero gives fsE.  All zero when either prim < 0.
+ *             Unweighted and unclamped: the caller applies, in the pass's order,
+ *             clampVec(w((aL * value) * aE), clampUpper), then NaN -> 0.  MIS prefix products are not provided.
+ *     status  BDPT_CONNECT_STATUS_NONZERO: value has a component that is not +-0
+ *
+ * BDPT_CONNECT_CAMERA: light vertex light[i] against the context's camera (gen_splat without the path buffers), for a
+ *   width x height frame with pixelJitter as in bdpt_params — always the whole frame, as bdpt_camera_rays.  Reads V (the
+ *   walk's stored direction to the predecessor) and lightSpecular.  cameraSamples[i]:
+ *     ray     org = posW, dir = normalize(camPos - posW), tmin = minT, tmax = length(camPos - posW)
+ *     f       evalBRDF(V, dir, N, N, ...)
+ *     G       saturate(|dot(dir, cameraN)|) * saturate(|dot(dir, N)|) / tmax^2.  f and G stay apart because the pass forms
+ *             (prevColor * f) * G, which is not prevColor * (f * G) in fp32.
+ *     pixel   x + y * width of the target (getLaunchIndexFromDirection with rintf(p * size - jitter))
+ *     status  BDPT_CONNECT_STATUS_PIXEL: the vertex faces the camera (dot(cameraN, dir) < 0) and the target lies inside the
+ *             frame; otherwise pixel = 0xffffffff and f = G = 0.  BDPT_CONNECT_STATUS_NONZERO (informational): f has a
+ *             non-zero component and G != 0.
+ *   prim < 0 gives an all-zero sample with pixel = 0xffffffff.  There are no occluder hints: those belong to the context's
+ *   own G-buffer pass, and a hint only ever saves a ray.
+ *
+ * Compaction (compactRays, compactItems, compactCount: all or none) works as in bdpt_light_query: VERTICES appends the
+ * items whose status has NONZERO, CAMERA those with PIXEL (the pass traces those whatever their value: a zero-valued splat
+ * still saturates its pixel in the resolve).  One atomic per wave of 64 items; the caller zeroes the word and owns capacity
+ * num of both lists; a position at or beyond num is not written; the order inside the lists is unspecified.
+ *
+ * Errors (nothing is enqueued): no scene, or CAMERA without a camera BDPT_E_STATE; a NULL context or desc, an unknown mode,
+ * non-zero flags or reserved, matIndex > 1, a missing or misaligned buffer (records 16 bytes, words 4), compaction buffers
+ * given in part, CAMERA with a width or height of 0 or width * height >= 2^32 BDPT_E_INVALID. */
+#define BDPT_CONNECT_VERTICES 0u
+#define BDPT_CONNECT_CAMERA 1u
+#define BDPT_CONNECT_STATUS_NONZERO 1u
+#define BDPT_CONNECT_STATUS_PIXEL 2u
+typedef struct bdpt_connect_sample {
+  bdpt_ray ray;
+  float value[3];
+  uint32_t status; /* BDPT_CONNECT_STATUS_NONZERO or 0 */
+} bdpt_connect_sample; /* 48 bytes: three float4 */
+typedef struct bdpt_camera_sample {
+  bdpt_ray ray;
+  float f[3];
+  float G;
+  uint32_t pixel;  /* x + y * width, 0xffffffff = none */
+  uint32_t status; /* BDPT_CONNECT_STATUS_* */
+  uint32_t reserved[2];
+} bdpt_camera_sample; /* 64 bytes: four float4 */
+typedef struct bdpt_connect_desc {
+  uint32_t mode;                     /* BDPT_CONNECT_* */
+  uint32_t num;                      /* items; the capacity when numDevice is set */
+  const uint32_t* numDevice;         /* optional device word: min(*numDevice, num) items */
+  uint32_t matIndex;                 /* 0 GGX, 1 Lambertian */
+  uint32_t flags;                    /* 0 */
+  float minT;                        /* tmin of the rays (bdpt_params::minT) */
+  uint32_t reserved;                 /* 0 */
+  const bdpt_surface* eye;           /* VERTICES: device, 16-byte aligned, num records */
+  const bdpt_surface* light;         /* device, 16-byte aligned, num records */
+  const float* eyePrev;              /* VERTICES, optional: device, 16-byte aligned, four floats per item */
+  const float* lightPrev;            /* VERTICES, optional: device, 16-byte aligned, four floats per item */
+  const uint8_t* eyeSpecular;        /* VERTICES, optional: device, one byte per item */
+  const uint8_t* lightSpecular;      /* optional: device, one byte per item */
+  bdpt_connect_sample* samples;      /* VERTICES: device, 16-byte aligned, one per item */
+  bdpt_camera_sample* cameraSamples; /* CAMERA: device, 16-byte aligned, one per item */
+  uint32_t width, height;            /* CAMERA: the frame */
+  float pixelJitter[2];              /* CAMERA: bdpt_params::pixelJitter */
+  bdpt_ray* compactRays;             /* optional: device, 16-byte aligned, capacity num */
+  uint32_t* compactItems;            /* with compactRays: device, capacity num */
+  uint32_t* compactCount;            /* with compactRays: device word, zeroed by the caller */
+} bdpt_connect_desc;
+int bdpt_connect_query(bdpt_ctx* ctx, const bdpt_connect_desc* desc, void* stream);
+
+/* bdpt_splat_add: the splat half of the pass's gather for a caller's lists.  Entry j (of num, or of min(*numDevice, num))
+ * uses item k = items ? items[j] : j: it reads pixels[k], values[k] (xyz: the clamped term) and visible[j], so CAMERA mode's
+ * compact lists and bdpt_trace_rays' `visible` bytes go in as they are.  An entry lands when visible is NULL or
+ * visible[j] != 0 and pixels[k] < numPixels.  A landed entry adds (uint64_t)(c * 2^32) to word 0 / 1 / 2 of
+ * splat[pixels[k]] for each channel c > 0 (a NaN or non-positive channel adds nothing) and 1 to word 3, with 64-bit atomic
+ * adds: integer sums, so the result is exact and does not depend on the order.  `splat` is a device buffer of uint64[4]
+ * per pixel in frame order: the context's own (bdpt_splat_buffer of a whole-frame context) or the caller's, which
+ * bdpt_resolve(ctx, splat, 0, out) folds in as it does the pass's.  Owner-major (stripes) layouts are not supported.
+ * Ordering, capture, counters, num == 0: as above.  Needs no scene.  Errors (nothing is enqueued): a NULL context or desc, a
+ * missing or misaligned buffer (splat and values 16 bytes, words 4) BDPT_E_INVALID. */
+typedef struct bdpt_splat_desc {
+  uint32_t num;              /* entries; the capacity when numDevice is set */
+  uint32_t numPixels;        /* pixels of `splat` */
+  const uint32_t* numDevice; /* optional device word: min(*numDevice, num) entries */
+  const uint32_t* pixels;    /* device, one target per item (bdpt_camera_sample::pixel) */
+  const float* values;       /* device, 16-byte aligned, four floats per item */
+  const uint8_t* visible;    /* optional: device, one byte per entry */
+  const uint32_t* items;     /* optional: device, one item index per entry */
+  uint64_t* splat;           /* device, 16-byte aligned, uint64[4] per pixel */
+} bdpt_splat_desc;
+int bdpt_splat_add(bdpt_ctx* ctx, const bdpt_splat_desc* desc, void* stream);
 
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
