@@ -684,6 +684,23 @@ class Context:
         self._check(self._lib.bdpt_execute_light_groups(self._h, C.byref(params), C.byref(gbuffer), out_ptr, groups_ptr, stream),
                     "bdpt_execute_light_groups")
 
+    def execute_grouped(self, params, gbuffer, out_ptr, groups_ptr, assignment, num_groups, stream=None):
+        """bdpt_execute_grouped: bdpt_execute into `out_ptr` plus (num_groups + 1) RGBA32F planes of the frame at
+        `groups_ptr` (plane g = the lights `assignment` puts in group g, the last = emission).  `assignment` is a sequence
+        of group indices, one per light, and with PARAM_AREA_LIGHTS one more for the emitter table; the library copies it
+        before it returns (contract in include/bdpt.h "Assignable light groups")."""
+        a = [int(g) for g in assignment]
+        if any(g < 0 or g > 255 for g in a):
+            raise BdptError(f"execute_grouped: group indices must be 0 .. 255, not {a!r}")
+        arr = (C.c_uint8 * max(len(a), 1))(*a)
+        d = abi.LightGroupDesc()
+        d.planes = groups_ptr if isinstance(groups_ptr, (int, type(None))) else groups_ptr.value
+        d.numGroups = int(num_groups)
+        d.numAssigned = len(a)
+        d.groupOf = C.cast(arr, C.POINTER(C.c_uint8))
+        self._check(self._lib.bdpt_execute_grouped(self._h, C.byref(params), C.byref(gbuffer), out_ptr, C.byref(d), stream),
+                    "bdpt_execute_grouped")
+
     def execute_masked(self, params, gbuffer, mask_ptr, out_ptr, stream=None):
         """bdpt_execute_masked: bdpt_execute for the pixels whose byte of `mask_ptr` (W x H uint8, device) is non-zero;
         the others' `out` is left as it is (contract in include/bdpt.h)."""
@@ -856,6 +873,9 @@ class FramePipeline:
     float32 tensor with the frame's planes (plane k = light k, the last = emission) and ``light_groups_accum`` their
     running means, kept by one bdpt_accumulate over all planes with the beauty's counters.  As the beauty's ``output``,
     ``light_groups`` holds the mean too after an accumulating frame.  Whole frames only: not with a tile or stripes.
+    light_groups=<sequence of group indices> (one per light; with flags=PARAM_AREA_LIGHTS one more, for the emitter
+    table) renders through bdpt_execute_grouped instead: the tensors are of shape (max(assignment) + 2, H, W, 4), plane g
+    the lights assigned to group g, the last emission.
 
     adaptive={...} (settings of ADAPTIVE_DEFAULTS; {} for the defaults) makes every frame adaptive: bdpt_execute_masked
     renders the pixels of ``adaptive_state["mask"]`` and bdpt_adaptive_update folds them into the per-pixel running mean
@@ -874,6 +894,16 @@ class FramePipeline:
                                      (tile is not None and (int(tile[0]), int(tile[1])) != (0, int(height)))):
             raise BdptError("adaptive sampling needs a pipeline that renders the whole frame (no tile, no stripes) without "
                             "light groups")
+        self.group_assignment = None
+        if not isinstance(light_groups, bool) and light_groups is not None:
+            self.group_assignment = [int(g) for g in light_groups]
+            want = int(scene.desc.numLights) + (1 if int(flags) & abi.PARAM_AREA_LIGHTS else 0)
+            if len(self.group_assignment) != want:
+                raise BdptError(f"light groups: the assignment needs {want} entries (one per light, and one for the emitter "
+                                f"table with PARAM_AREA_LIGHTS), not {len(self.group_assignment)}")
+            if not self.group_assignment or min(self.group_assignment) < 0 or max(self.group_assignment) > abi.BDPT_MAX_LIGHTS:
+                raise BdptError(f"light groups: group indices must be 0 .. {abi.BDPT_MAX_LIGHTS}, not {self.group_assignment!r}")
+            light_groups = True
         if light_groups and (stripes is not None or (tile is not None and (int(tile[0]), int(tile[1])) != (0, int(height)))):
             raise BdptError("light groups need a pipeline that renders the whole frame (no tile, no stripes)")
         if not torch.cuda.is_available():
@@ -914,7 +944,7 @@ class FramePipeline:
             self.last_frame = torch.zeros(self.H, self.W, 4, dtype=torch.float32, device=self.dev)
             self.light_groups = self.light_groups_accum = None
             if light_groups:
-                k = int(scene.desc.numLights) + 1
+                k = int(scene.desc.numLights) + 1 if self.group_assignment is None else max(self.group_assignment) + 2
                 self.light_groups = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
                 self.light_groups_accum = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
             self.adaptive_state = None
@@ -992,8 +1022,11 @@ class FramePipeline:
             return gp, p
         if self.light_groups is None:
             self.ctx.execute(p, self.gb, C.c_void_p(self.output.data_ptr()), st)
-        else:
+        elif self.group_assignment is None:
             self.ctx.execute_light_groups(p, self.gb, C.c_void_p(self.output.data_ptr()), C.c_void_p(self.light_groups.data_ptr()), st)
+        else:
+            self.ctx.execute_grouped(p, self.gb, C.c_void_p(self.output.data_ptr()), C.c_void_p(self.light_groups.data_ptr()),
+                                     self.group_assignment, self.light_groups.shape[0] - 1, st)
         self.gbuffer_frame += 1
         self.bdpt_frame += 1
         if accumulate:

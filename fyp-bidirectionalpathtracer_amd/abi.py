@@ -30,6 +30,7 @@ PREPARE_BMFR = 2
 PREPARE_REFIT = 4
 PREPARE_LIGHT_GROUPS = 8
 PREPARE_AREA_LIGHTS = 16
+PREPARE_LIGHT_GROUP_TABLE = 32
 MEMORY_HOST, MEMORY_DEVICE = 0, 1
 UPDATE_KEEP_LIGHT_MAPS = 1
 TRACE_CLOSEST, TRACE_CLOSEST_CULL_BACK, TRACE_ANY = 0, 1, 2
@@ -228,6 +229,11 @@ class SplatDesc(C.Structure):
                 ("values", C.c_void_p), ("visible", C.c_void_p), ("items", C.c_void_p), ("splat", C.c_void_p)]
 
 
+class LightGroupDesc(C.Structure):
+    _fields_ = [("planes", C.c_void_p), ("numGroups", C.c_uint32), ("numAssigned", C.c_uint32),
+                ("groupOf", C.POINTER(C.c_uint8)), ("reserved", C.c_uint32 * 2)]
+
+
 class AreaLightInfo(C.Structure):
     _fields_ = [("numEmitters", C.c_uint32), ("numTextured", C.c_uint32), ("totalWeight", C.c_float), ("reserved", C.c_uint32)]
 
@@ -270,6 +276,8 @@ PROTOTYPES = {
     "bdpt_execute_tail": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_execute_light_groups": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
+    "bdpt_execute_grouped": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.POINTER(LightGroupDesc),
+                                       C.c_void_p]),
     "bdpt_execute_masked": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdpt_adaptive_reset": (C.c_int, [C.c_void_p, C.POINTER(AdaptiveState), C.c_void_p]),
     "bdpt_adaptive_update": (C.c_int, [C.c_void_p, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveState), C.c_void_p, C.c_void_p]),

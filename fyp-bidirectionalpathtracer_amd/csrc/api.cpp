@@ -126,10 +126,12 @@ struct bdpt_ctx {
   size_t pinnedBytes = 0;
   hipEvent_t evStage = nullptr, evOrder = nullptr;
   bool stageInFlight = false;
-  // light groups (bdpt_execute_light_groups): the per-light splat-value planes and each pixel's light, made by
-  // bdpt_prepare(BDPT_PREPARE_LIGHT_GROUPS) or the first call; they depend on the scene's light count and the frame size,
-  // so bdpt_set_scene and bdpt_resize drop them
+  // light groups (bdpt_execute_light_groups, bdpt_execute_grouped): the splat-value planes (groupSplatPlanes of them) and
+  // each pixel's light, made by bdpt_prepare(BDPT_PREPARE_LIGHT_GROUPS / _LIGHT_GROUP_TABLE) or by the first call that
+  // needs more planes than there are; they depend on the scene's light count and the frame size, so bdpt_set_scene and
+  // bdpt_resize drop them
   unsigned long long* groupSplat = nullptr;
+  uint32_t groupSplatPlanes = 0;
   uint8_t* groupLightIdx = nullptr;
   // area lights (BDPT_PARAM_AREA_LIGHTS): the emitter table, made by bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) or the first
   // frame with the switch, in sceneAllocs (a new scene drops it); refreshed on the device by every bdpt_update_geometry.
@@ -220,6 +222,7 @@ void freeLightGroups(bdpt_ctx* c) {
   if (c->groupSplat) (void)hipFree(c->groupSplat);
   if (c->groupLightIdx) (void)hipFree(c->groupLightIdx);
   c->groupSplat = nullptr;
+  c->groupSplatPlanes = 0;
   c->groupLightIdx = nullptr;
 }
 
@@ -1596,24 +1599,27 @@ namespace {
 // bdpt_execute, bdpt_execute_light_groups and bdpt_execute_masked: the same stages and the same rays.  The per-pixel
 // stages take the variant V; a group frame also clears its splat-value planes, and a masked frame runs the generators of
 // eye-side terms (NEE, connections) over its eye list (`PE`: the PathBuf with the eye list as its pixel list).
-int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream, const FrameVariant& V0) {
+// groupsTakeArea: a group frame whose caller assigned the emitter table a group (bdpt_execute_grouped)
+int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, void* stream, const FrameVariant& V0,
+                 bool groupsTakeArea = false) {
   FrameDev F;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = frameSetup(c, p, in, out, st, F)) return rc;
   FrameVariant V = V0;
   if (p->flags & BDPT_PARAM_AREA_LIGHTS) {
-    // (the pdf an area-light vertex needs in the MIS prefix is a design question of its own; group planes have no slot
-    // for the table)
+    // (the pdf an area-light vertex needs in the MIS prefix is a design question of its own; the planes of
+    // bdpt_execute_light_groups have no slot for the table: bdpt_execute_grouped assigns it one)
     if (p->flags & (BDPT_PARAM_MIS_POWER | BDPT_PARAM_MIS_LINEAR)) {
       fail(c, "execute: BDPT_PARAM_AREA_LIGHTS is not supported with BDPT_PARAM_MIS_POWER / _LINEAR");
       return BDPT_E_INVALID;
     }
-    if (V.kind == FrameKind::Groups) {
+    if (V.kind == FrameKind::Groups && !groupsTakeArea) {
       fail(c, "light groups: BDPT_PARAM_AREA_LIGHTS is not supported (the group planes have no slot for area lights)");
       return BDPT_E_INVALID;
     }
     if (int rc = ensureAreaLights(c, st)) return rc;
     V.area = c->area;  // n == 0 (no emitter): the plain instances
+    if (V.kind == FrameKind::Groups && V.area.n) V.groups.areaW = V.area.total;
   }
   const PathBuf& P = c->P;
   PathBuf PE = P;
@@ -1641,7 +1647,7 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
   HIPCHK(c, hipMemsetAsync(P.qcount, 0, (size_t)kCursorWords * sizeof(uint32_t), st));
   HIPCHK(c, hipMemsetAsync(c->splat, 0, (size_t)c->sl.owners * c->sl.chunkRows * c->W * 4 * sizeof(unsigned long long), st));
   if (V.kind == FrameKind::Groups)
-    HIPCHK(c, hipMemsetAsync(V.groups.splat, 0, (size_t)V.groups.numLights * V.groups.framePix * 4 * sizeof(unsigned long long), st));
+    HIPCHK(c, hipMemsetAsync(V.groups.splat, 0, (size_t)V.groups.numGroups * V.groups.framePix * 4 * sizeof(unsigned long long), st));
   if (!(p->flags & BDPT_PARAM_KEEP_COUNTERS)) HIPCHK(c, hipMemsetAsync(c->counters, 0, sizeof(DevCounters), st));
   stageMark(c, st, "clear");
 
@@ -1707,22 +1713,27 @@ int executeFrame(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, floa
   return connectionTail(c, F, st, V);
 }
 
-// the group path's buffers; not while the stream is being captured
-int allocLightGroups(bdpt_ctx* c, hipStream_t st) {
-  if (c->groupSplat) return BDPT_OK;
+// the group path's buffers, with at least `planes` splat-value planes; not while the stream is being captured
+int allocLightGroups(bdpt_ctx* c, hipStream_t st, uint32_t planes) {
+  if (c->groupSplat && c->groupSplatPlanes >= planes) return BDPT_OK;
   if (streamIsCapturing(st)) {
-    fail(c, "light groups: the splat planes need bdpt_prepare(BDPT_PREPARE_LIGHT_GROUPS) before stream capture");
+    fail(c, "light groups: the splat planes need bdpt_prepare(BDPT_PREPARE_LIGHT_GROUPS / _LIGHT_GROUP_TABLE) before stream capture");
     return BDPT_E_STATE;
+  }
+  if (c->groupSplat) {  // too few planes for this assignment: frames in flight still use them
+    HIPCHK(c, hipDeviceSynchronize());
+    freeLightGroups(c);
   }
   const size_t n = (size_t)c->W * c->H;
   void *sp = nullptr, *li = nullptr;
-  if (hipMalloc(&sp, std::max<size_t>((size_t)c->S.numLights * n * 4 * sizeof(unsigned long long), 16)) != hipSuccess ||
+  if (hipMalloc(&sp, std::max<size_t>((size_t)planes * n * 4 * sizeof(unsigned long long), 16)) != hipSuccess ||
       hipMalloc(&li, std::max<size_t>(c->P.Np, 16)) != hipSuccess) {
     if (sp) (void)hipFree(sp);
     fail(c, "light groups: hipMalloc of the splat planes failed");
     return BDPT_E_NOMEM;
   }
   c->groupSplat = reinterpret_cast<unsigned long long*>(sp);
+  c->groupSplatPlanes = planes;
   c->groupLightIdx = reinterpret_cast<uint8_t*>(li);
   return BDPT_OK;
 }
@@ -1759,15 +1770,67 @@ int bdpt_execute_light_groups(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuf
   if (int rc = wholeFrameCheck(c, p, "light groups")) return rc;
   ENTER(c);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = allocLightGroups(c, st)) return rc;
-  FrameVariant V;
+  if (int rc = allocLightGroups(c, st, c->S.numLights)) return rc;
+  FrameVariant V;  // the identity assignment: group k = light k
   V.kind = FrameKind::Groups;
   V.groups.planes = groups;
   V.groups.splat = c->groupSplat;
   V.groups.lightIdx = c->groupLightIdx;
   V.groups.numLights = c->S.numLights;
+  V.groups.numGroups = c->S.numLights;
   V.groups.framePix = (uint64_t)c->W * c->H;
+  for (uint32_t i = 0; i < c->S.numLights; i++) V.groups.groupOf[i] = (uint8_t)i;
   return executeFrame(c, p, in, out, stream, V);
+}
+
+int bdpt_execute_grouped(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float* out, const bdpt_light_group_desc* d,
+                         void* stream) {
+  if (!c) return BDPT_E_INVALID;
+  if (!p || !out) {
+    fail(c, "execute_grouped: params or out is NULL");
+    return BDPT_E_INVALID;
+  }
+  if (!d || !d->planes || !d->groupOf) {
+    fail(c, "execute_grouped: the descriptor, its planes or its groupOf is NULL");
+    return BDPT_E_INVALID;
+  }
+  if (int rc = wholeFrameCheck(c, p, "execute_grouped")) return rc;
+  if (d->numGroups < 1 || d->numGroups > BDPT_MAX_LIGHTS + 1) {
+    fail(c, "execute_grouped: numGroups must be 1 .. BDPT_MAX_LIGHTS + 1");
+    return BDPT_E_INVALID;
+  }
+  const bool area = (p->flags & BDPT_PARAM_AREA_LIGHTS) != 0;
+  const uint32_t numLights = c->S.numLights;
+  if (d->numAssigned != numLights + (area ? 1u : 0u)) {
+    fail(c, "execute_grouped: numAssigned must be numLights, or numLights + 1 with BDPT_PARAM_AREA_LIGHTS");
+    return BDPT_E_INVALID;
+  }
+  for (uint32_t i = 0; i < d->numAssigned; i++)
+    if (d->groupOf[i] >= d->numGroups) {
+      fail(c, "execute_grouped: groupOf[" + std::to_string(i) + "] is not below numGroups");
+      return BDPT_E_INVALID;
+    }
+  if (d->reserved[0] || d->reserved[1]) {
+    fail(c, "execute_grouped: reserved must be 0");
+    return BDPT_E_INVALID;
+  }
+  if (area && (p->flags & (BDPT_PARAM_MIS_POWER | BDPT_PARAM_MIS_LINEAR))) {  // (before anything is allocated)
+    fail(c, "execute: BDPT_PARAM_AREA_LIGHTS is not supported with BDPT_PARAM_MIS_POWER / _LINEAR");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = allocLightGroups(c, st, d->numGroups)) return rc;
+  FrameVariant V;
+  V.kind = FrameKind::Groups;
+  V.groups.planes = d->planes;
+  V.groups.splat = c->groupSplat;
+  V.groups.lightIdx = c->groupLightIdx;
+  V.groups.numLights = numLights;
+  V.groups.numGroups = d->numGroups;
+  V.groups.framePix = (uint64_t)c->W * c->H;
+  for (uint32_t i = 0; i < d->numAssigned; i++) V.groups.groupOf[i] = d->groupOf[i];
+  return executeFrame(c, p, in, out, stream, V, true);
 }
 
 int bdpt_execute_masked(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, const uint8_t* mask, float* out, void* stream) {
@@ -1886,7 +1949,7 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
     fail(c, "prepare: BDPT_PREPARE_AREA_LIGHTS needs a scene");
     return BDPT_E_STATE;
   }
-  if ((what & BDPT_PREPARE_LIGHT_GROUPS) && !c->haveScene) {
+  if ((what & (BDPT_PREPARE_LIGHT_GROUPS | BDPT_PREPARE_LIGHT_GROUP_TABLE)) && !c->haveScene) {
     fail(c, "prepare: BDPT_PREPARE_LIGHT_GROUPS needs a scene (the planes are per light)");
     return BDPT_E_STATE;
   }
@@ -1897,8 +1960,8 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
     if (int rc = allocOwnGbuffer(c)) return rc;
   if (what & BDPT_PREPARE_BMFR)  // (whole-frame history also on a band / stripes context: bdpt_bmfr_execute takes whole-frame buffers)
     if (int rc = allocBmfrHistory(c)) return rc;
-  if (what & BDPT_PREPARE_LIGHT_GROUPS)
-    if (int rc = allocLightGroups(c, nullptr)) return rc;
+  if (what & (BDPT_PREPARE_LIGHT_GROUPS | BDPT_PREPARE_LIGHT_GROUP_TABLE))  // (_TABLE: a plane for the emitter table's group too)
+    if (int rc = allocLightGroups(c, nullptr, c->S.numLights + ((what & BDPT_PREPARE_LIGHT_GROUP_TABLE) ? 1u : 0u))) return rc;
   if (what & BDPT_PREPARE_AREA_LIGHTS)
     if (int rc = ensureAreaLights(c, nullptr)) return rc;
   return BDPT_OK;

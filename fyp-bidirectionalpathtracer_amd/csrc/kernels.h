@@ -173,16 +173,21 @@ struct FrameDev {
   const uint32_t* hintPix;
 };
 
-// Light groups (bdpt_execute_light_groups): one RGBA32F plane per light plus one for emission, from the paths of the
-// plain frame.  The group instances of init_paths, gather and lazy_check and the group resolve take it (FrameVariant).
-// Whole-frame contexts only: planes and splat planes are indexed by frame pixel (splat planes in SplatLayout order,
-// which is frame order there).
+// Light groups (bdpt_execute_light_groups, bdpt_execute_grouped): one RGBA32F plane per group of lights plus one for
+// emission, from the paths of the plain frame.  A term's source light (the emitter table is light numLights) decides its
+// plane through `groupOf`; bdpt_execute_light_groups is the identity assignment.  The group instances of init_paths, gather
+// and lazy_check and the group resolve take it (FrameVariant).  The assignment travels by value in the kernel argument, so
+// a captured graph holds it.  Whole-frame contexts only: planes and splat planes are indexed by frame pixel (splat planes
+// in SplatLayout order, which is frame order there).
 struct GroupDev {
-  float* planes;               // (numLights + 1) planes of W*H float4: plane k < numLights = light k, plane numLights = emission
-  unsigned long long* splat;   // numLights splat-value planes of W*H x 4 u64 (r, g, b, unused); counts stay in FrameDev::splat
-  uint8_t* lightIdx;           // tile-local pixel p -> the light its light subpath starts at (init_paths)
+  float* planes;               // (numGroups + 1) planes of W*H float4: plane g < numGroups = group g, plane numGroups = emission
+  unsigned long long* splat;   // numGroups splat-value planes of W*H x 4 u64 (r, g, b, unused); counts stay in FrameDev::splat
+  uint8_t* lightIdx;           // tile-local pixel p -> the light its light subpath starts at (init_paths); numLights = the table
   uint32_t numLights;
+  uint32_t numGroups;
   uint64_t framePix;           // W*H: the stride of both kinds of plane
+  const float* areaW;          // AreaDev::total (the table's W word) of a frame with BDPT_PARAM_AREA_LIGHTS and emitters, else NULL
+  uint8_t groupOf[BDPT_MAX_LIGHTS + 1];  // light -> group; entry numLights = the emitter table
 };
 
 // Masked frames (bdpt_execute_masked): only the pixels a caller's mask selects trace eye paths, NEE and connection rays,
@@ -201,6 +206,7 @@ struct MaskDev {
 // Area lights (BDPT_PARAM_AREA_LIGHTS; contract in include/bdpt.h "Area lights"): the scene's emitting triangles in
 // ascending primitive order and their selection CDF, built and refreshed on the device (area_lights.hip).  Only the AREA
 // instances of init_paths and gen_nee take it (last argument), so SceneDev and every other instance stay as they are.
+// (A group frame's gather re-forms the light count from GroupDev::areaW, the same word.)
 constexpr uint32_t kNoAlphaRec = 0xFFFFFFFFu;
 struct BvhRefitNode;  // bvh.h
 struct AreaDev {
@@ -219,7 +225,7 @@ struct FrameVariant {
   FrameKind kind = FrameKind::Plain;
   GroupDev groups{};  // kind == Groups
   MaskDev mask{};     // kind == Masked
-  AreaDev area{};     // area.n > 0: the AREA instances of init_paths and gen_nee (Plain and Masked kinds)
+  AreaDev area{};     // area.n > 0: the AREA instances of init_paths and gen_nee (every kind)
 };
 
 struct GBufferDev {

@@ -274,8 +274,9 @@ BD const MaskDev& maskOf(const MaskDev& m) { return m; }
 // init_paths: eye vertex 1 from the G-buffer, light vertex 0 from sampleLight, valid-pixel queue
 // (BDPTMain.rt.hlsl:51-103, 124-135; sampleLight BDPTUtils.hlsli:140-152)
 // ------------------------------------------------------------------------------------------------
-// GROUPS (bdpt_execute_light_groups): also the light of each pixel's light subpath, and the planes of the pixels without
-// geometry — the emission plane what `out` gets, a light plane (0, 0, 0, 1): the frame with that background stripped
+// GROUPS (bdpt_execute_light_groups, bdpt_execute_grouped): also the light of each pixel's light subpath (the index, not
+// its group; numLights = the emitter table), and the planes of the pixels without geometry — the emission plane what
+// `out` gets, a group plane (0, 0, 0, 1): the frame with that background stripped
 // MASKED (bdpt_execute_masked): every pixel's paths start as in the plain frame (its light subpath and seedL, which the
 // eye vertex's draws lead to, are needed whatever the mask says), but only active pixels get their `out` write, and the
 // active valid ones also go onto the eye list
@@ -301,8 +302,8 @@ BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, co
       P.eyeLast[p] = 0;
       if (GROUPS) {
         float4* g4 = reinterpret_cast<float4*>(Gr.planes) + pix;
-        for (uint32_t k = 0; k < Gr.numLights; k++) g4[(size_t)k * Gr.framePix] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-        g4[(size_t)Gr.numLights * Gr.framePix] = make_float4(dr, dg, db, 1.0f);
+        for (uint32_t k = 0; k < Gr.numGroups; k++) g4[(size_t)k * Gr.framePix] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+        g4[(size_t)Gr.numGroups * Gr.framePix] = make_float4(dr, dg, db, 1.0f);
       }
     } else {
       float nx, ny, nz, nw, sr, sg, sb, sa, er, eg, eb, ea;
@@ -382,11 +383,11 @@ __global__ __launch_bounds__(kWave) void init_paths_kernel(SceneDev S, FrameDev 
   BDPT_ONE_WAVE_PER_GROUP();
   initPathsLane<GGX, V == FrameKind::Groups, V == FrameKind::Masked>(S, F, P, groupOf(A), maskOf(A));
 }
-// the AREA instances (plain and masked frames; light groups refuse the switch): the emitter table as one more argument
+// the AREA instances (every frame kind): the emitter table as one more argument
 template <bool GGX, FrameKind V>
 __global__ __launch_bounds__(kWave) void init_paths_area_kernel(SceneDev S, FrameDev F, PathBuf P, FrameArg<V> A, AreaDev E) {
   BDPT_ONE_WAVE_PER_GROUP();
-  initPathsLane<GGX, false, V == FrameKind::Masked, true>(S, F, P, GroupDev{}, maskOf(A), E);
+  initPathsLane<GGX, V == FrameKind::Groups, V == FrameKind::Masked, true>(S, F, P, groupOf(A), maskOf(A), E);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1153,13 +1154,16 @@ BD void loadSlotChunk(const PathBuf& P, uint32_t p, int slot0, int n, SlotChunk&
   }
 }
 
-// GROUPS (bdpt_execute_light_groups; contract in include/bdpt.h "Light groups"): the planes as well.  Every term has one
-// source: NEE term t the light gen_nee drew for it (recomputed here from seedL: draw t + 1), connections and splats the
-// pixel's light subpath (GroupDev::lightIdx).  A light plane's RGB lives in LDS (`la`: row (3k + channel) * kWave of the
-// lane's column) while its terms are summed; w is the same in every plane and in `out`, so it is kept once.  The frame
-// with only light k adds +0 for every NEE term of another light; the plane skips those adds, which changes no bit: its sum
-// starts at +0 and only ever adds values >= +0 (clampVec), and x + 0 == x for every such x.  The emission plane (the frame
-// with every intensity zero) adds its +0 terms for real, because it starts from `out`'s start, -0 included.
+// GROUPS (bdpt_execute_light_groups, bdpt_execute_grouped; contract in include/bdpt.h "Light groups"): the planes as well.
+// Every term has one source: NEE term t the light gen_nee / gen_nee_area drew for it (recomputed here from seedL: draw
+// t + 1, over the same lightsCount = numLights + (W > 0) from the table's device word), connections and splats the pixel's
+// light subpath (GroupDev::lightIdx).  GroupDev::groupOf maps the source to its group.  A group plane's RGB lives in LDS
+// (`la`: row (3g + channel) * kWave of the lane's column, 3 * numGroups rows of dynamic LDS) while its terms are summed; w
+// is the same in every plane and in `out`, so it is kept once.  The frame with only group g's sources adds +0 for every
+// NEE term of another group; the plane skips those adds, which changes no bit: its sum starts at +0 and only ever adds
+// values >= +0 (clampVec), and x + 0 == x for every such x.  The terms of several lights of one group are summed in term
+// order, which is that frame's order.  The emission plane (the frame with every source at zero) adds its +0 terms for
+// real, because it starts from `out`'s start, -0 included.
 // MASKED (bdpt_execute_masked): a pixel the mask leaves out (`active` false) only lands its splats — its NEE and
 // connection slots were never generated this frame — and its `out` is neither summed nor written.
 template <bool GROUPS, bool MASKED>
@@ -1170,12 +1174,15 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, floa
   float4* out4 = reinterpret_cast<float4*>(F.out);
   float4 acc = out4[pix];
   const int D = (int)F.p.maxDepth;
-  const int K = GROUPS ? (int)Gr.numLights : 0;
+  const int K = GROUPS ? (int)Gr.numGroups : 0;
   float ex = acc.x, ey = acc.y, ez = acc.z;  // emission plane RGB
-  int own = 0;                               // light plane of the pixel's light subpath
+  int own = 0;                               // group plane of the pixel's light subpath
+  int lightsCount = 0;                       // as gen_nee / gen_nee_area form it
   if (GROUPS) {
     for (int r = 0; r < 3 * K; r++) la[r * kWave] = 0.0f;
-    own = (int)Gr.lightIdx[p];
+    own = (int)Gr.groupOf[Gr.lightIdx[p]];
+    const float areaW = Gr.areaW ? Gr.areaW[0] : 0.0f;
+    lightsCount = (int)Gr.numLights + ((areaW > 0.0f) ? 1 : 0);
   }
   SlotChunk c;
   if (sums && !(F.p.flags & BDPT_PARAM_NO_NEE)) {
@@ -1191,9 +1198,9 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, floa
           acc.z = acc.z + c.cz[j];
           acc.w = acc.w + 1.0f;
           if (GROUPS) {
-            int l = (int)(nextRand(seed) * (float)K);  // gen_nee's lightToSample of term t0 + j
-            if (l > K - 1) l = K - 1;
-            float* a = la + 3 * l * kWave;
+            int l = (int)(nextRand(seed) * (float)lightsCount);  // gen_nee's lightToSample of term t0 + j
+            if (l > lightsCount - 1) l = lightsCount - 1;
+            float* a = la + 3 * (int)Gr.groupOf[l] * kWave;
             a[0] = a[0] + c.cx[j];
             a[kWave] = a[kWave] + c.cy[j];
             a[2 * kWave] = a[2 * kWave] + c.cz[j];
@@ -1207,7 +1214,7 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, floa
   if (sums && !(F.p.flags & BDPT_PARAM_NO_CONNECT)) {
     const int nPairs = (int)numConnectPairs((uint32_t)D);
     bool sat = false;
-    float ox = 0.0f, oy = 0.0f, oz = 0.0f;  // the own light plane takes the saturating sequence of `out`
+    float ox = 0.0f, oy = 0.0f, oz = 0.0f;  // the own group plane takes the saturating sequence of `out`
     if (GROUPS) {
       ox = la[(3 * own) * kWave];
       oy = la[(3 * own + 1) * kWave];
@@ -1262,7 +1269,7 @@ BD bool gatherLane(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, floa
       for (int j = 0; j < kGatherChunk; j++) {
         if (!c.vis[j] || target[j] == kNoRay) continue;  // kNoRay: outside the frame (quirk 8)
         unsigned long long* sp = F.splat + (size_t)target[j] * 4;
-        // GROUPS: the value goes to the splat plane of the pixel's light only (resolve_groups sums the planes for `out`)
+        // GROUPS: the value goes to the splat plane of the pixel's group only (resolve_groups sums the planes for `out`)
         unsigned long long* sv = GROUPS ? Gr.splat + ((size_t)own * Gr.framePix + target[j]) * 4 : sp;
         const unsigned long long qx = toFixed(c.cx[j]), qy = toFixed(c.cy[j]), qz = toFixed(c.cz[j]);
         if (qx) atomicAdd(&sv[0], qx);
@@ -1282,7 +1289,7 @@ __global__ __launch_bounds__(kWave) void gather_kernel(FrameDev F, PathBuf P, ui
                                                        uint32_t* __restrict__ lazyCount, FrameArg<V> A) {
   BDPT_ONE_WAVE_PER_GROUP();
   constexpr bool GROUPS = V == FrameKind::Groups, MASKED = V == FrameKind::Masked;
-  __shared__ float s_acc[GROUPS ? 3 * BDPT_MAX_LIGHTS * kWave : 1];  // light planes' RGB while a lane sums them (12 KiB)
+  extern __shared__ float s_acc[];  // GROUPS: the group planes' RGB while a lane sums them (3 * numGroups * kWave floats)
   bool act = false;
   uint32_t i = 0;
   if (!queueChunk(P.qcount, P.pathSubCap, act, i)) return;
@@ -1419,7 +1426,7 @@ BD void lazyCheck(const FrameDev& F, const PathBuf& P, const GroupDev& Gr, const
       out4[pix] = acc;
       if (GROUPS) {
         float4* g4 = reinterpret_cast<float4*>(Gr.planes) + pix;
-        for (uint32_t k = 0; k <= Gr.numLights; k++) {
+        for (uint32_t k = 0; k <= Gr.numGroups; k++) {
           float4 o = g4[(size_t)k * Gr.framePix];
           o.x = saturate(o.x + 0.0f);
           o.y = saturate(o.y + 0.0f);
@@ -1484,7 +1491,7 @@ __global__ void resolve_masked_kernel(const unsigned long long* __restrict__ spl
 }
 
 // resolve_kernel for `out` and every light-group plane in one pass, where at least one splat landed (count word of
-// FrameDev::splat, shared by all).  `out`'s values are the sums of the light planes' values: integer sums, so equal to
+// FrameDev::splat, shared by all).  `out`'s values are the sums of the group planes' values: integer sums, so equal to
 // what the plain frame's atomics add up to.  The emission plane lands splats of value 0.
 __global__ void resolve_groups_kernel(FrameDev F, const uint32_t* __restrict__ pixOf, uint32_t Np, GroupDev Gr) {
   constexpr float kInvFix = 2.3283064365386963e-10f;
@@ -1497,9 +1504,9 @@ __global__ void resolve_groups_kernel(FrameDev F, const uint32_t* __restrict__ p
     if (cnt == 0ull) continue;
     float4* g4 = reinterpret_cast<float4*>(Gr.planes) + pix;
     unsigned long long tx = 0, ty = 0, tz = 0;
-    for (uint32_t k = 0; k <= Gr.numLights; k++) {
+    for (uint32_t k = 0; k <= Gr.numGroups; k++) {
       unsigned long long vx = 0, vy = 0, vz = 0;
-      if (k < Gr.numLights) {
+      if (k < Gr.numGroups) {
         const unsigned long long* sv = Gr.splat + ((size_t)k * Gr.framePix + sidx) * 4;
         const ulonglong2 a = reinterpret_cast<const ulonglong2*>(sv)[0];
         vx = a.x;
@@ -1738,14 +1745,11 @@ void launchLightMaps(const SceneDev& S, uint32_t* maps, uint32_t res, hipStream_
 
 void launchInitPaths(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, hipStream_t st) {
   if (!P.Np) return;
-  if (V.area.n && V.kind != FrameKind::Groups) {  // (api.cpp refuses area lights with light groups)
-    const bool masked = V.kind == FrameKind::Masked;
-    withFlags(
-        [&](auto GGX, auto MASKED) {
-          constexpr FrameKind K = MASKED ? FrameKind::Masked : FrameKind::Plain;
-          launchWave(init_paths_area_kernel<GGX, K>, blocksFor(P.Np), st, S, F, P, frameArg<K>(V), V.area);
-        },
-        F.p.matIndex == 0, masked);
+  if (V.area.n) {
+    withKind(V.kind, [&](auto K) {
+      withFlags([&](auto GGX) { launchWave(init_paths_area_kernel<GGX, K>, blocksFor(P.Np), st, S, F, P, frameArg<K>(V), V.area); },
+                F.p.matIndex == 0);
+    });
     return;
   }
   withKind(V.kind, [&](auto K) {
@@ -1816,7 +1820,10 @@ void launchTraceShadow(const SceneDev& S, const FrameDev& F, const PathBuf& P, i
 
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st) {
   if (!P.Np) return;
-  withKind(V.kind, [&](auto K) { launchWave(gather_kernel<K>, queueGrid(P), st, F, P, lazyList, lazyCount, frameArg<K>(V)); });
+  // a group frame's LDS: three rows of kWave floats per group (1.5 KiB for two groups, 12.75 KiB for seventeen)
+  // (a scene without lights has no group, but a valid pixel still reads its own group's rows: one group's worth)
+  const size_t lds = V.kind == FrameKind::Groups ? (size_t)3 * std::max(V.groups.numGroups, 1u) * kWave * sizeof(float) : 0;
+  withKind(V.kind, [&](auto K) { launchWaveLds(gather_kernel<K>, queueGrid(P), lds, st, F, P, lazyList, lazyCount, frameArg<K>(V)); });
 }
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st) {
   if (!P.Np) return;

@@ -19,6 +19,12 @@ static void launchWave(K kernel, uint32_t grid, hipStream_t st, Args... args) {
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWave), 0, st, args...);
 }
 
+// the same with `ldsBytes` of dynamic LDS (extern __shared__)
+template <class K, class... Args>
+static void launchWaveLds(K kernel, uint32_t grid, size_t ldsBytes, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWave), ldsBytes, st, args...);
+}
+
 // Persistent grids: as many one-wave workgroups as can be resident (LDS 8 KiB/wave, VGPRs).
 template <class K>
 static uint32_t persistentGrid(K kernel, int numCUs) {

@@ -279,10 +279,10 @@ typedef struct bdpt_params {
  *       intensity is +0.
  *   Supported with whole-frame, band and stripes contexts, bdpt_execute_masked, DEFER_RESOLVE / DEFER_TAIL and
  *   EMISSIVE_HITS / ENV_ON_MISS.  BDPT_E_INVALID with BDPT_PARAM_MIS_POWER / _LINEAR (the pdf of an area-light vertex in
- *   the MIS prefix is a design question of its own) and with bdpt_execute_light_groups (the group planes have no slot for
- *   it).  The table is made by bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) or by the first frame with the switch (which then
- *   must not be inside a stream capture: BDPT_E_STATE); bdpt_update_geometry refreshes its weights on its stream without
- *   allocating or synchronising. */
+ *   the MIS prefix is a design question of its own) and with bdpt_execute_light_groups (its group planes have no slot for
+ *   it: bdpt_execute_grouped assigns the table a group).  The table is made by bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) or
+ *   by the first frame with the switch (which then must not be inside a stream capture: BDPT_E_STATE);
+ *   bdpt_update_geometry refreshes its weights on its stream without allocating or synchronising. */
 #define BDPT_PARAM_AREA_LIGHTS 4096u
 
 /* RayGenCB of lightProbeGBuffer.rt.hlsl:45-52 + the miss shader's env map. */
@@ -859,6 +859,7 @@ int bdpt_tile_row_ranges(const bdpt_ctx* ctx, uint32_t* out_first_last, uint32_t
 #define BDPT_PREPARE_REFIT 4u /* the refit plan and scratch of bdpt_update_geometry now (needs a scene, not a size) */
 #define BDPT_PREPARE_LIGHT_GROUPS 8u /* the per-light splat planes of bdpt_execute_light_groups (needs a scene and a size) */
 #define BDPT_PREPARE_AREA_LIGHTS 16u /* the emitter table of BDPT_PARAM_AREA_LIGHTS (needs a scene, not a size) */
+#define BDPT_PREPARE_LIGHT_GROUP_TABLE 32u /* numLights + 1 splat planes: the most an assignment of bdpt_execute_grouped needs */
 int bdpt_prepare(bdpt_ctx* ctx, uint32_t what);
 
 /* Primary-visibility pass.  Writes the tile rows of all six channels. */
@@ -895,6 +896,49 @@ int bdpt_execute(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, fl
  * or size BDPT_E_STATE; a context that renders a tile or stripes (not the whole frame) BDPT_E_INVALID — the splat
  * exchange of tiled rendering has no group planes. */
 int bdpt_execute_light_groups(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, float* out, float* groups, void* stream);
+
+/* Assignable light groups: the breakdown above with a caller's table from light to group ("key", "fill", "practicals"),
+ * and with the emitter table of BDPT_PARAM_AREA_LIGHTS as one more light, "light numLights".  The cost follows the number
+ * of groups, not of lights: numGroups + 1 planes are written and numGroups splat-value planes cleared.
+ * `planes` is device memory of (numGroups + 1) x W x H RGBA32F planes: plane g < numGroups is group g, plane numGroups is
+ * emission.  `groupOf` is a HOST array of numAssigned bytes, copied before the call returns (a captured graph holds the
+ * copy): groupOf[i] is the group of light i, and with BDPT_PARAM_AREA_LIGHTS groupOf[numLights] that of the emitter table.
+ * Sources of terms: a next-event term belongs to the light drawn for it; a splat and every connection to the light the
+ * pixel's light subpath starts at; either light may be the table.  The G-buffer emissive, the background and the
+ * ENV_ON_MISS / EMISSIVE_HITS terms have no source and go to the emission plane.  Paths, random draws, rays and w never
+ * depend on intensities or on emission.  Hence, bit for bit:
+ *   - `out` and the ray counters are bdpt_execute's for the same params, BDPT_PARAM_AREA_LIGHTS included;
+ *   - every plane's w is out.w;
+ *   - group plane g's RGB is the bdpt_execute frame in which every source outside g contributes exactly +0 — every draw,
+ *     path and ray stays the same — with the G-buffer emissive RGB and the background pixels' diffuse RGB zero and
+ *     ENV_ON_MISS / EMISSIVE_HITS cleared; several lights of one group sum their terms in that frame's order;
+ *   - a group may be empty: its plane is (0, 0, 0, w);
+ *   - the emission plane is the frame in which every source contributes +0;
+ *   - the identity assignment (numGroups = numLights, groupOf[i] = i) without the switch gives
+ *     bdpt_execute_light_groups' planes, `out` and counters.
+ * The area-light switch: without it numAssigned is numLights; with it numAssigned is numLights + 1, and the last entry is
+ * read only while the table's W > 0 — with no emitter or W == 0 the switch changes nothing, as everywhere else (the
+ * entry must still name a group).  The emitter table is made as bdpt_execute makes it (bdpt_prepare(
+ * BDPT_PREPARE_AREA_LIGHTS) or the first frame with the switch).
+ * Ordering, stream use, in == NULL and capture are those of bdpt_execute_light_groups.  The call needs numGroups
+ * splat-value planes (W x H x 32 B each): bdpt_prepare(BDPT_PREPARE_LIGHT_GROUPS) allocates numLights of them,
+ * bdpt_prepare(BDPT_PREPARE_LIGHT_GROUP_TABLE) numLights + 1, the most any assignment needs; a call that finds too few
+ * allocates them (it waits for the device first) and then must not be inside a stream capture (BDPT_E_STATE, nothing
+ * enqueued).
+ * Errors (nothing is enqueued): a NULL ctx, params, out, desc, planes or groupOf BDPT_E_INVALID; numGroups 0 or above
+ * BDPT_MAX_LIGHTS + 1, numAssigned not as stated, an entry >= numGroups, non-zero reserved BDPT_E_INVALID;
+ * BDPT_PARAM_DEFER_RESOLVE / _DEFER_TAIL BDPT_E_INVALID; BDPT_PARAM_AREA_LIGHTS with BDPT_PARAM_MIS_POWER / _LINEAR
+ * BDPT_E_INVALID; a context that renders a tile or stripes BDPT_E_INVALID; no scene or size BDPT_E_STATE.
+ * bdpt_execute_light_groups itself keeps refusing BDPT_PARAM_AREA_LIGHTS (its buffer has no plane for the table). */
+typedef struct bdpt_light_group_desc {
+  float* planes;          /* device: (numGroups + 1) x W x H RGBA32F; plane g < numGroups = group g, plane numGroups = emission */
+  uint32_t numGroups;     /* 1 .. BDPT_MAX_LIGHTS + 1 */
+  uint32_t numAssigned;   /* entries of groupOf: numLights, or numLights + 1 when p->flags has BDPT_PARAM_AREA_LIGHTS */
+  const uint8_t* groupOf; /* HOST array, copied before the call returns: the group of light i; entry numLights = the emitter table */
+  uint32_t reserved[2];   /* 0 */
+} bdpt_light_group_desc;
+int bdpt_execute_grouped(bdpt_ctx* ctx, const bdpt_params* p, const bdpt_gbuffer* in, float* out, const bdpt_light_group_desc* desc,
+                         void* stream);
 
 /* Masked frame (region of interest, foveation, adaptive sampling): bdpt_execute for the pixels `mask` selects.  `mask` is
  * device memory of W x H bytes in frame order; a non-zero byte makes the pixel ACTIVE.  Bit for bit:
