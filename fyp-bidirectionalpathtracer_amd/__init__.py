@@ -219,6 +219,96 @@ class Context:
         u.flags = abi.UPDATE_KEEP_LIGHT_MAPS if keep_light_maps else 0
         self._check(self._lib.bdpt_update_geometry(self._h, C.byref(u), stream), "bdpt_update_geometry")
 
+    def set_skin(self, positions, bone_weights, bone_ids, num_bones, normals=None, bitangents=None):
+        """bdpt_set_skin: the rest pose (numVertices x 3 float32 each; normals / bitangents optional), four weights
+        (float32) and four bone ids (uint16) per vertex, all host arrays, copied before this returns.  Synchronises and
+        allocates; not inside a stream capture.  positions=None drops the skin."""
+        if positions is None:
+            self._check(self._lib.bdpt_set_skin(self._h, None), "bdpt_set_skin")
+            return
+        import numpy as np
+
+        def host(a, dtype):
+            return None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype).reshape(-1)
+
+        p, n, b, w = (host(a, np.float32) for a in (positions, normals, bitangents, bone_weights))
+        ids = host(bone_ids, np.uint16)
+        nv = p.size // 3
+        if p.size != 3 * nv or any(a is not None and a.size != 3 * nv for a in (n, b)) or w.size != 4 * nv or ids.size != 4 * nv:
+            raise BdptError("set_skin: positions, normals and bitangents must be numVertices x 3, weights and ids numVertices x 4")
+        d = abi.SkinDesc()
+        d.numVertices, d.numBones = int(nv), int(num_bones)
+        d.positions, d.boneWeights, d.boneIds = p.ctypes.data, w.ctypes.data, ids.ctypes.data
+        d.normals = None if n is None else n.ctypes.data
+        d.bitangents = None if b is None else b.ctypes.data
+        self._check(self._lib.bdpt_set_skin(self._h, C.byref(d)), "bdpt_set_skin")
+        self._skin_vertices = int(nv)
+
+    def update_skinned(self, bones, normal_bones=None, stream=None, keep_light_maps=False):
+        """bdpt_update_skinned: the frame's bone matrices (numBones x 16 float32, m[4r+c], translation in floats 12..14;
+        normal_bones: their inverse transposes, required iff the skin has normals); the vertices are skinned on the device
+        and the tree refitted.  GPU torch tensors take the device path and numpy arrays / CPU tensors the host path, by
+        the rules of update_geometry.  Nothing is enqueued when an argument is refused."""
+        u = abi.SkinUpdate()
+        arrays = [bones, normal_bones]
+        given = [a for a in arrays if a is not None]
+        on_gpu = [bool(getattr(a, "is_cuda", False)) for a in given]
+        if any(on_gpu):
+            if not all(on_gpu):
+                raise BdptError("update_skinned: bones and normal_bones must both be GPU tensors or both host arrays")
+            for a in given:
+                if a.device.index != self.device:
+                    raise BdptError(f"update_skinned: a tensor on {a.device} for the context of device {self.device}")
+                if not a.is_contiguous() or str(a.dtype) != "torch.float32":
+                    raise BdptError("update_skinned: device inputs must be contiguous float32 tensors")
+            u.memory = abi.MEMORY_DEVICE
+            ptrs = [None if a is None else a.data_ptr() for a in arrays]
+            sizes = [None if a is None else a.numel() for a in arrays]
+        else:
+            import numpy as np
+            u.memory = abi.MEMORY_HOST
+            arrays = [None if a is None else np.ascontiguousarray(a.detach().numpy() if hasattr(a, "detach") else a, np.float32).reshape(-1)
+                      for a in arrays]
+            ptrs = [None if a is None else a.ctypes.data for a in arrays]
+            sizes = [None if a is None else a.size for a in arrays]
+        n = sizes[0] // 16
+        if sizes[0] != 16 * n or (sizes[1] is not None and sizes[1] != 16 * n):
+            raise BdptError("update_skinned: bones and normal_bones must be numBones x 16 each")
+        u.bones, u.normalBones = ptrs
+        u.numBones = int(n)
+        u.flags = abi.UPDATE_KEEP_LIGHT_MAPS if keep_light_maps else 0
+        self._check(self._lib.bdpt_update_skinned(self._h, C.byref(u), stream), "bdpt_update_skinned")
+
+    def skinned_buffers(self):
+        """bdpt_skinned_buffers: the device addresses (int, or None for a stream the skin lacks) of the skinned positions,
+        normals and bitangents; valid until set_skin / set_scene."""
+        p, n, b = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self._lib.bdpt_skinned_buffers(self._h, C.byref(p), C.byref(n), C.byref(b)), "bdpt_skinned_buffers")
+        return p.value, n.value, b.value
+
+    def test_skin_kernel(self, path=abi.SKIN_PATH_AUTO, stream=None):
+        """Test hook bdpt_test_skin_kernel: the skinning kernel alone, with the palette the last host-bone update_skinned
+        staged; path SKIN_PATH_AUTO / _GLOBAL / _LDS."""
+        self._check(self._lib.bdpt_test_skin_kernel(self._h, int(path), stream), "bdpt_test_skin_kernel")
+
+    def read_skinned(self, stream=None):
+        """The skinned streams copied to the host (numVertices x 3 float32 each, None for a stream the skin lacks); waits
+        for `stream`."""
+        import numpy as np
+        self.sync(stream)
+        nv = self._skin_vertices
+        hip = C.CDLL("libamdhip64.so")
+        out = []
+        for ptr in self.skinned_buffers():
+            if ptr is None:
+                out.append(None)
+                continue
+            a = np.empty((nv, 3), np.float32)
+            if hip.hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(ptr), C.c_size_t(a.nbytes), 2) != 0:
+                raise BdptError("read_skinned: hipMemcpy failed")
+            out.append(a)
+        return tuple(out)
+
     def trace_rays(self, rays, mode="closest", out=None, count=None, stream=None):
         """bdpt_trace_rays: closest-hit or any-hit queries of a batch of rays against the scene (semantics: include/bdpt.h
         "Ray queries").  `rays` is (N, 8) float32 in the bdpt_ray layout: origin xyz, tmin, direction xyz, tmax.
@@ -1063,6 +1153,17 @@ class FramePipeline:
         on before the stream has reached the update)."""
         self.ctx.update_geometry(positions, normals, bitangents, self._stream_ptr(), keep_light_maps)
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (positions, normals, bitangents))
+        self.accum_count = 0
+
+    def set_skin(self, positions, bone_weights, bone_ids, num_bones, normals=None, bitangents=None):
+        """Context.set_skin (synchronises: everything this pipeline enqueued has finished when it returns)."""
+        self.ctx.set_skin(positions, bone_weights, bone_ids, num_bones, normals, bitangents)
+
+    def update_skinned(self, bones, normal_bones=None, keep_light_maps=False):
+        """Pose the skinned scene (Context.update_skinned on this pipeline's stream); accumulation restarts, as after
+        update_geometry.  GPU tensors are marked as in use by that stream."""
+        self.ctx.update_skinned(bones, normal_bones, self._stream_ptr(), keep_light_maps)
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (bones, normal_bones))
         self.accum_count = 0
 
     def trace_rays(self, rays, mode="closest", out=None, count=None):

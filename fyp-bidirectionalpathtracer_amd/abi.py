@@ -33,6 +33,11 @@ PREPARE_AREA_LIGHTS = 16
 PREPARE_LIGHT_GROUP_TABLE = 32
 MEMORY_HOST, MEMORY_DEVICE = 0, 1
 UPDATE_KEEP_LIGHT_MAPS = 1
+BDPT_MAX_BONES = 1024
+# csrc/skin.h kSkinLdsBones / kSkinLdsMinVertices: palettes up to this size on skins of at least this many vertices take the
+# kernel's LDS path
+SKIN_LDS_BONES, SKIN_LDS_MIN_VERTICES = 64, 1 << 20
+SKIN_PATH_AUTO, SKIN_PATH_GLOBAL, SKIN_PATH_LDS = 0, 1, 2
 TRACE_CLOSEST, TRACE_CLOSEST_CULL_BACK, TRACE_ANY = 0, 1, 2
 SHADE_NORMAL_MAP = 1
 BSDF_SAMPLE, BSDF_EVAL = 0, 1
@@ -142,6 +147,16 @@ class BvhInfo(C.Structure):
 class GeometryUpdate(C.Structure):
     _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("bitangents", C.c_void_p), ("numVertices", C.c_uint32),
                 ("memory", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SkinDesc(C.Structure):
+    _fields_ = [("numVertices", C.c_uint32), ("numBones", C.c_uint32), ("positions", C.c_void_p), ("normals", C.c_void_p),
+                ("bitangents", C.c_void_p), ("boneWeights", C.c_void_p), ("boneIds", C.c_void_p), ("reserved", C.c_uint32 * 2)]
+
+
+class SkinUpdate(C.Structure):
+    _fields_ = [("bones", C.c_void_p), ("normalBones", C.c_void_p), ("numBones", C.c_uint32), ("memory", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class RefitInfo(C.Structure):
@@ -255,6 +270,11 @@ PROTOTYPES = {
     "bdpt_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(GeometryUpdate), C.c_void_p]),
     "bdpt_set_lights": (C.c_int, [C.c_void_p, C.POINTER(Light), C.c_uint32, C.c_void_p]),
     "bdpt_get_refit_info": (C.c_int, [C.c_void_p, C.POINTER(RefitInfo)]),
+    "bdpt_set_skin": (C.c_int, [C.c_void_p, C.POINTER(SkinDesc)]),
+    "bdpt_update_skinned": (C.c_int, [C.c_void_p, C.POINTER(SkinUpdate), C.c_void_p]),
+    "bdpt_skinned_buffers": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "bdpt_host_skin": (C.c_int, [C.POINTER(SkinDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdpt_test_skin_kernel": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "bdpt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(TraceDesc), C.c_void_p]),
     "bdpt_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(GBufferParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdpt_shade_hits": (C.c_int, [C.c_void_p, C.POINTER(ShadeDesc), C.c_void_p]),

@@ -27,6 +27,7 @@
 #include "bvh.h"
 #include "kernels.h"
 #include "refit.h"
+#include "skin.h"
 #include "scene_bvh.h"
 
 using namespace bdpt;
@@ -143,6 +144,12 @@ struct bdpt_ctx {
   uint32_t areaTextured = 0;
   float* areaBlockSum = nullptr;     // one float and one word per 64 emitters: the refresh's scratch
   uint32_t* areaBlockLast = nullptr;
+  // skinning (bdpt_set_skin): the rest streams, weights, ids, the skinned streams and the device palettes, in skinAllocs
+  // (bdpt_set_skin and bdpt_set_scene drop them).  skinPalette: where host-pointer palettes are staged (bones, normalBones).
+  std::vector<void*> skinAllocs;
+  bool haveSkin = false;
+  SkinDev skin{};
+  float* skinPalette[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -359,6 +366,7 @@ void bdpt_destroy(bdpt_ctx* c) {
   if (c->adaptiveSum) (void)hipFree(c->adaptiveSum);
   freeLightGroups(c);
   freePool(c->sceneAllocs);
+  freePool(c->skinAllocs);
   freePool(c->frameAllocs);
   if (c->evCreated)
     for (int i = 0; i <= kMaxStages; i++) (void)hipEventDestroy(c->ev[i]);
@@ -436,6 +444,10 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
   freePool(c->sceneAllocs);
+  freePool(c->skinAllocs);
+  c->haveSkin = false;
+  c->skin = SkinDev{};
+  c->skinPalette[0] = c->skinPalette[1] = nullptr;
   freeLightGroups(c);
   c->haveScene = false;
   c->S = SceneDev{};
@@ -885,6 +897,20 @@ int ensureAreaLights(bdpt_ctx* c, hipStream_t st) {
   c->areaReady = true;
   return BDPT_OK;
 }
+// What every update ends with, on st: the refit to the device arrays `pos` (and `nrm`), the emitter table's refresh, the
+// bitangent copy, the light maps' re-trace unless kept.
+int updateTail(bdpt_ctx* c, const float* pos, const float* nrm, const float* bit, uint32_t flags, hipStream_t st) {
+  const size_t nv3 = (size_t)c->numVertices * 3;
+  launchRefit(c->refit, reinterpret_cast<BvhRec*>(const_cast<uint4*>(c->S.recs)), const_cast<float4*>(c->S.shade), c->S.indices, c->numTriangles, pos, nrm, st);
+  if (c->areaReady) launchAreaRefresh(c->S, c->area, c->areaBlockSum, c->areaBlockLast, st);  // weights and CDF of the new areas
+  if (bit) HIPCHK(c, hipMemcpyAsync(const_cast<float*>(c->S.bitangents), bit, nv3 * 4, hipMemcpyDeviceToDevice, st));
+  if (!(flags & BDPT_UPDATE_KEEP_LIGHT_MAPS)) retraceLightMaps(c, st);
+  HIPCHK(c, hipGetLastError());
+  c->hintCamValid = false;
+  c->numUpdates++;
+  c->lastStream = st;
+  return BDPT_OK;
+}
 }  // namespace
 
 int bdpt_update_geometry(bdpt_ctx* c, const bdpt_geometry_update* u, void* stream) {
@@ -942,13 +968,215 @@ int bdpt_update_geometry(bdpt_ctx* c, const bdpt_geometry_update* u, void* strea
   } else {
     if (int rc = orderAfterLast(c, st)) return rc;
   }
-  launchRefit(c->refit, reinterpret_cast<BvhRec*>(const_cast<uint4*>(c->S.recs)), const_cast<float4*>(c->S.shade), c->S.indices, c->numTriangles, pos, nrm, st);
-  if (c->areaReady) launchAreaRefresh(c->S, c->area, c->areaBlockSum, c->areaBlockLast, st);  // weights and CDF of the new areas
-  if (bit) HIPCHK(c, hipMemcpyAsync(const_cast<float*>(c->S.bitangents), bit, nv3 * 4, hipMemcpyDeviceToDevice, st));
-  if (!(u->flags & BDPT_UPDATE_KEEP_LIGHT_MAPS)) retraceLightMaps(c, st);
+  return updateTail(c, pos, nrm, bit, u->flags, st);
+}
+
+// ---- skinning: bdpt_set_skin / bdpt_update_skinned (skin.hip) and the same arithmetic on the host ----
+namespace {
+// the checks of a bdpt_skin_desc that need no context; `what` prefixes the message
+int checkSkinDesc(bdpt_ctx* c, const bdpt_skin_desc* d, const char* what) {
+  const std::string w(what);
+  if (!d->positions || !d->boneWeights || !d->boneIds || d->reserved[0] || d->reserved[1] || d->numBones == 0) {
+    fail(c, w + ": positions, boneWeights and boneIds are required, numBones >= 1 and reserved 0");
+    return BDPT_E_INVALID;
+  }
+  if (d->numBones > BDPT_MAX_BONES) {
+    fail(c, w + ": more than BDPT_MAX_BONES bones");
+    return BDPT_E_LIMIT;
+  }
+  std::atomic<int> bad{0};  // 1 = position, 2 = weight, 3 = id
+  hostParallelFor(d->numVertices, [&](size_t v0, size_t v1) {
+    for (size_t v = v0; v < v1; v++) {
+      const float* p = d->positions + v * 3;
+      const float* wt = d->boneWeights + v * 4;
+      if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) bad.store(1);
+      if (!(std::isfinite(wt[0]) && std::isfinite(wt[1]) && std::isfinite(wt[2]) && std::isfinite(wt[3]))) {
+        bad.store(2);
+        continue;
+      }
+      if (skinIsStatic(wt)) continue;  // (its ids are neither checked nor read)
+      for (int k = 0; k < 4; k++)
+        if (d->boneIds[v * 4 + (size_t)k] >= d->numBones) bad.store(3);
+    }
+  });
+  if (bad.load()) {
+    fail(c, w + (bad.load() == 1 ? ": a rest position is not finite" : bad.load() == 2 ? ": a bone weight is not finite" : ": a bone id >= numBones on a vertex with a weight"));
+    return BDPT_E_INVALID;
+  }
+  return BDPT_OK;
+}
+}  // namespace
+
+int bdpt_host_skin(const bdpt_skin_desc* d, const float* bones, const float* normalBones, float* outPositions, float* outNormals,
+                   float* outBitangents) {
+  if (!d || !bones || !outPositions) return BDPT_E_INVALID;
+  if ((d->normals && (!normalBones || !outNormals)) || (d->bitangents && !outBitangents)) return BDPT_E_INVALID;
+  if (int rc = checkSkinDesc(nullptr, d, "host_skin")) return rc;
+  const bool hasN = d->normals != nullptr, hasB = d->bitangents != nullptr;
+  hostParallelFor(d->numVertices, [&](size_t v0, size_t v1) {
+    const float zero[3] = {0.0f, 0.0f, 0.0f};
+    float scratch[3];
+    for (size_t v = v0; v < v1; v++) {
+      const float* w = d->boneWeights + v * 4;
+      const float* p = d->positions + v * 3;
+      const float* n = hasN ? d->normals + v * 3 : zero;
+      const float* b = hasB ? d->bitangents + v * 3 : zero;
+      float* op = outPositions + v * 3;
+      float* on = hasN ? outNormals + v * 3 : scratch;
+      float* ob = hasB ? outBitangents + v * 3 : scratch;
+      if (skinIsStatic(w)) {
+        for (int k = 0; k < 3; k++) {
+          op[k] = p[k];
+          if (hasN) on[k] = n[k];
+          if (hasB) ob[k] = b[k];
+        }
+        continue;
+      }
+      const uint16_t* id = d->boneIds + v * 4;
+      if (hasN && hasB)
+        skinVertex<true, true>(bones, normalBones, id, w, p, n, b, op, on, ob);
+      else if (hasN)
+        skinVertex<true, false>(bones, normalBones, id, w, p, n, b, op, on, ob);
+      else if (hasB)
+        skinVertex<false, true>(bones, normalBones, id, w, p, n, b, op, on, ob);
+      else
+        skinVertex<false, false>(bones, normalBones, id, w, p, n, b, op, on, ob);
+    }
+  });
+  return BDPT_OK;
+}
+
+int bdpt_set_skin(bdpt_ctx* c, const bdpt_skin_desc* d) {
+  if (!c) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "set_skin: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (d) {
+    if (d->numVertices != c->numVertices) {
+      fail(c, "set_skin: numVertices differs from the scene's");
+      return BDPT_E_INVALID;
+    }
+    if (d->bitangents && !c->S.hasBitangents) {
+      fail(c, "set_skin: bitangents given for a scene that has none");
+      return BDPT_E_INVALID;
+    }
+    if (int rc = checkSkinDesc(c, d, "set_skin")) return rc;
+  }
+  ENTER(c);
+  if (streamIsCapturing(c->lastStream)) {
+    fail(c, "set_skin: not inside a stream capture (it allocates and synchronises)");
+    return BDPT_E_STATE;
+  }
+  if (d)
+    if (int rc = ensureRefit(c, c->lastStream)) return rc;  // (before the old skin goes: a failure leaves it in place)
+  HIPCHK(c, hipDeviceSynchronize());
+  std::vector<void*> pool;
+  SkinDev K{};
+  float* palette[2] = {nullptr, nullptr};
+  if (d) {
+    const size_t nv = d->numVertices, nv3 = nv * 3, pal = (size_t)d->numBones * 16;
+    int rc;
+    if ((rc = devUpload(c, pool, &K.restPos, d->positions, nv3)) || (d->normals && (rc = devUpload(c, pool, &K.restNrm, d->normals, nv3))) ||
+        (d->bitangents && (rc = devUpload(c, pool, &K.restBit, d->bitangents, nv3))) || (rc = devUpload(c, pool, &K.weights, d->boneWeights, nv * 4)) ||
+        (rc = devUpload(c, pool, &K.ids, d->boneIds, nv * 4)) || (rc = devAlloc(c, pool, &K.pos, nv3)) ||
+        (d->normals && (rc = devAlloc(c, pool, &K.nrm, nv3))) || (d->bitangents && (rc = devAlloc(c, pool, &K.bit, nv3))) ||
+        (rc = devAlloc(c, pool, &palette[0], pal)) || (d->normals && (rc = devAlloc(c, pool, &palette[1], pal)))) {
+      freePool(pool);
+      return rc;
+    }
+    // until the first update the skinned streams hold the rest pose, the palettes zeros
+    hipError_t e = hipMemcpy(K.pos, K.restPos, nv3 * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && K.nrm) e = hipMemcpy(K.nrm, K.restNrm, nv3 * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && K.bit) e = hipMemcpy(K.bit, K.restBit, nv3 * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemset(palette[0], 0, pal * 4);
+    if (e == hipSuccess && palette[1]) e = hipMemset(palette[1], 0, pal * 4);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+      freePool(pool);
+      fail(c, std::string("set_skin: ") + hipGetErrorString(e));
+      return BDPT_E_HIP;
+    }
+    K.numVertices = d->numVertices;
+    K.numBones = d->numBones;
+  }
+  freePool(c->skinAllocs);
+  c->skinAllocs = std::move(pool);
+  c->skin = K;
+  c->skinPalette[0] = palette[0];
+  c->skinPalette[1] = palette[1];
+  c->haveSkin = d != nullptr;
+  return BDPT_OK;
+}
+
+int bdpt_update_skinned(bdpt_ctx* c, const bdpt_skin_update* u, void* stream) {
+  if (!c || !u) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->haveSkin) {
+    fail(c, c->haveScene ? "update_skinned: no skin (bdpt_set_skin first)" : "update_skinned: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  const SkinDev& K = c->skin;
+  if (!u->bones || (K.nrm && !u->normalBones) || u->numBones != K.numBones || u->memory > BDPT_MEMORY_DEVICE ||
+      (u->flags & ~BDPT_UPDATE_KEEP_LIGHT_MAPS) || u->reserved) {
+    fail(c, u->numBones != K.numBones ? "update_skinned: numBones differs from the skin's"
+                                      : "update_skinned: bones (or normalBones, for a skin with normals) missing, or bad memory / flags / reserved");
+    return BDPT_E_INVALID;
+  }
+  const size_t pal = (size_t)K.numBones * 16;
+  if (u->memory == BDPT_MEMORY_HOST) {
+    bool finite = true;
+    for (size_t i = 0; i < pal; i++) finite = finite && std::isfinite(u->bones[i]) && (!K.nrm || std::isfinite(u->normalBones[i]));
+    if (!finite) {
+      fail(c, "update_skinned: a bone matrix element is not finite");
+      return BDPT_E_INVALID;
+    }
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = ensureRefit(c, st)) return rc;  // (bdpt_set_skin made the plan: nothing to do)
+  const float* bones = u->bones;
+  const float* nbones = K.nrm ? u->normalBones : nullptr;
+  if (u->memory == BDPT_MEMORY_HOST) {
+    if (streamIsCapturing(st)) {
+      fail(c, "update_skinned: host-pointer palettes are staged through pinned memory: not while capturing");
+      return BDPT_E_STATE;
+    }
+    if (int rc = orderAfterLast(c, st)) return rc;
+    const void* arrays[2] = {bones, nbones};
+    const size_t bytes[2] = {pal * 4, pal * 4};
+    if (int rc = stageHostArrays(c, arrays, bytes, 2, c->skinPalette, st)) return rc;
+    bones = c->skinPalette[0];
+    nbones = K.nrm ? c->skinPalette[1] : nullptr;
+  } else {
+    if (int rc = orderAfterLast(c, st)) return rc;
+  }
+  launchSkin(K, bones, nbones, kSkinPathAuto, st);
+  return updateTail(c, K.pos, K.nrm, K.bit, u->flags, st);
+}
+
+int bdpt_skinned_buffers(bdpt_ctx* c, const float** positions, const float** normals, const float** bitangents) {
+  if (!c || !positions || !normals || !bitangents) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->haveSkin) {
+    fail(c, "skinned_buffers: no skin (bdpt_set_skin first)");
+    return BDPT_E_STATE;
+  }
+  *positions = c->skin.pos;
+  *normals = c->skin.nrm;
+  *bitangents = c->skin.bit;
+  return BDPT_OK;
+}
+
+int bdpt_test_skin_kernel(bdpt_ctx* c, uint32_t path, void* stream) {
+  if (!c || path > (uint32_t)kSkinPathLds) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->haveSkin) {
+    fail(c, "test_skin_kernel: no skin (bdpt_set_skin first)");
+    return BDPT_E_STATE;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  launchSkin(c->skin, c->skinPalette[0], c->skin.nrm ? c->skinPalette[1] : nullptr, (int)path, st);
   HIPCHK(c, hipGetLastError());
-  c->hintCamValid = false;
-  c->numUpdates++;
   c->lastStream = st;
   return BDPT_OK;
 }

@@ -414,6 +414,31 @@ bool RayLaunch::setLights(const bdpt_light* lights, uint32_t numLights, const st
   }
   return true;
 }
+bool RayLaunch::setSkin(const bdpt_skin_desc* skin) {
+  if (!mCtx || !mSceneSet) return false;
+  const uint32_t n = (uint32_t)mMore.size() + 1;
+  for (uint32_t s = 0; s < n; s++) {
+    bdpt_ctx* c = s == 0 ? mCtx : mMore[s - 1];
+    if (bdpt_set_skin(c, skin) != BDPT_OK) {
+      std::fprintf(stderr, "[RayLaunch] bdpt_set_skin failed: %s\n", bdpt_last_error(c));
+      return false;
+    }
+  }
+  return true;
+}
+bool RayLaunch::updateSkinned(const bdpt_skin_update& u, const std::vector<hipStream_t>& streams, uint32_t first) {
+  if (!mCtx || !mSceneSet) return false;
+  const uint32_t n = (uint32_t)mMore.size() + 1;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t s = (first + k) % n;
+    bdpt_ctx* c = s == 0 ? mCtx : mMore[s - 1];
+    if (bdpt_update_skinned(c, &u, s < streams.size() ? streams[s] : nullptr) != BDPT_OK) {
+      std::fprintf(stderr, "[RayLaunch] bdpt_update_skinned failed: %s\n", bdpt_last_error(c));
+      return false;
+    }
+  }
+  return true;
+}
 bool RayLaunch::ensureSize(uint32_t w, uint32_t h) {
   if (!mCtx) return false;
   if (w == mW && h == mH && mSizedDepth == mMaxDepth) return true;
@@ -1090,6 +1115,25 @@ bool RenderingPipeline::updateGeometry(const float* positions, const float* norm
   uint32_t first = 0;
   const std::vector<hipStream_t> streams = updateStreams(first);
   if (!rays->updateGeometry(u, streams, first)) return false;
+  mSceneMoved = mSceneUpdated = true;
+  return true;
+}
+bool RenderingPipeline::setSkin(const bdpt_skin_desc* skin) {
+  RayLaunch::SharedPtr rays = mpRays ? mpRays : RayLaunch::create(&mContext);
+  return rays && mpScene && rays->setSkin(skin);
+}
+bool RenderingPipeline::updateSkinned(const float* bones, const float* normalBones, uint32_t numBones, uint32_t memory, bool keepLightMaps) {
+  RayLaunch::SharedPtr rays = mpRays ? mpRays : RayLaunch::create(&mContext);
+  if (!rays || !mpScene || !bones) return false;
+  bdpt_skin_update u{};
+  u.bones = bones;
+  u.normalBones = normalBones;
+  u.numBones = numBones;
+  u.memory = memory;
+  u.flags = keepLightMaps ? BDPT_UPDATE_KEEP_LIGHT_MAPS : 0u;
+  uint32_t first = 0;
+  const std::vector<hipStream_t> streams = updateStreams(first);
+  if (!rays->updateSkinned(u, streams, first)) return false;
   mSceneMoved = mSceneUpdated = true;
   return true;
 }

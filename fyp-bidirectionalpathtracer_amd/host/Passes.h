@@ -25,6 +25,10 @@ class RayLaunch {
   // slot `first`.  false + lastError() when a context refuses it.
   bool updateGeometry(const bdpt_geometry_update& u, const std::vector<hipStream_t>& streams, uint32_t first);
   bool setLights(const bdpt_light* lights, uint32_t numLights, const std::vector<hipStream_t>& streams, uint32_t first);
+  // Skinning (SkinningCache::update in front of the refit): the same skin for every frame slot's context (synchronises;
+  // nullptr drops it), and the same bone palette for each, ordered as updateGeometry's.
+  bool setSkin(const bdpt_skin_desc* skin);
+  bool updateSkinned(const bdpt_skin_update& u, const std::vector<hipStream_t>& streams, uint32_t first);
   void setMaxRecursionDepth(uint32_t d) { mMaxDepth = d; }
   bool readyToRender() const { return mCtx && mSceneSet; }
   // (re)size the per-pixel path state; called by execute when the screen size changed
@@ -259,6 +263,13 @@ class RenderingPipeline {
   bool updateGeometry(const float* positions, const float* normals = nullptr, const float* bitangents = nullptr,
                       uint32_t memory = BDPT_MEMORY_HOST, bool keepLightMaps = false);
   bool setLights(const bdpt_light* lights, uint32_t numLights);
+  // Skinned scenes: setSkin hands every frame slot's context the rest pose, bone weights and ids (host arrays, copied;
+  // call it after initialize(), it synchronises); updateSkinned then poses the scene from a bone palette (numBones x 16
+  // floats, and the inverse transposes when the skin has normals) instead of three vertex streams — skinned on the
+  // device, then refitted as by updateGeometry.  nullptr drops the skin.
+  bool setSkin(const bdpt_skin_desc* skin);
+  bool updateSkinned(const float* bones, const float* normalBones, uint32_t numBones, uint32_t memory = BDPT_MEMORY_HOST,
+                     bool keepLightMaps = false);
   Scene::SharedPtr getScene() const { return mpScene; }
   size_t getPassCount() const { return mActivePasses.size(); }
 

@@ -41,6 +41,7 @@ struct Options {
   bool denoise = false, denoiseRegression = false;
   bool areaLights = false;  // BDPT_PARAM_AREA_LIGHTS: emissive triangles light the scene (NEE and light subpaths)
   float sway = 0.0f;  // > 0: an animated scene — before every frame the vertices move by up to this fraction of the scene's extent
+  float bend = 0.0f;  // > 0: a skinned scene — a small rig along the scene's height, bent by up to this angle (radians) before every frame
 };
 
 // How the ranks of a job stay together: a rank whose set-up fails must not leave its peers waiting in a
@@ -184,8 +185,75 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
       extent = std::max(extent, hi - lo);
     }
   }
+  // --bend: a procedural rig — kBendBones bones stacked along the scene's height, every vertex blended between the two
+  // bones next to it — bent about the scene's foot before every frame (bdpt_set_skin once, then a bone palette per frame
+  // through RenderingPipeline::updateSkinned; the vertices are skinned on the device)
+  constexpr uint32_t kBendBones = 4;
+  std::vector<float> bendBones, bendNormalBones;
+  float bendPivot[3] = {0.0f, 0.0f, 0.0f};
+  bool bendHasNormals = false;
+  if (o.bend > 0.0f && pipeline->getScene()) {
+    const Scene& sc = *pipeline->getScene();
+    const size_t nv = sc.positions.size() / 3;
+    float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
+    for (size_t i = 0; i < nv * 3; i++) {
+      lo[i % 3] = std::min(lo[i % 3], sc.positions[i]);
+      hi[i % 3] = std::max(hi[i % 3], sc.positions[i]);
+    }
+    bendPivot[0] = 0.5f * (lo[0] + hi[0]);
+    bendPivot[1] = lo[1];
+    bendPivot[2] = 0.5f * (lo[2] + hi[2]);
+    std::vector<float> weights(nv * 4, 0.0f);
+    std::vector<uint16_t> ids(nv * 4, 0);
+    const float height = std::max(hi[1] - lo[1], 1e-20f);
+    for (size_t v = 0; v < nv; v++) {
+      const float s = std::min(std::max((sc.positions[v * 3 + 1] - lo[1]) / height, 0.0f), 1.0f) * (float)(kBendBones - 1);
+      const uint32_t k = std::min((uint32_t)s, kBendBones - 2);
+      const float f = s - (float)k;
+      ids[v * 4] = (uint16_t)k;
+      ids[v * 4 + 1] = (uint16_t)(k + 1);
+      weights[v * 4] = 1.0f - f;
+      weights[v * 4 + 1] = f;
+    }
+    bendHasNormals = sc.normals.size() == nv * 3;
+    bdpt_skin_desc sd{};
+    sd.numVertices = (uint32_t)nv;
+    sd.numBones = kBendBones;
+    sd.positions = sc.positions.data();
+    sd.normals = bendHasNormals ? sc.normals.data() : nullptr;
+    sd.bitangents = sc.bitangents.size() == nv * 3 ? sc.bitangents.data() : nullptr;
+    sd.boneWeights = weights.data();
+    sd.boneIds = ids.data();
+    if (!pipeline->setSkin(&sd)) {
+      std::fprintf(stderr, "bdpt_render: setSkin failed\n");
+      env.failLate();
+      return res;
+    }
+    bendBones.assign(kBendBones * 16, 0.0f);
+    bendNormalBones.assign(kBendBones * 16, 0.0f);
+  }
   bool swayOk = true;
   auto frame = [&](int f) {
+    if (!bendBones.empty()) {
+      // bone k turns about the z axis through the pivot by k / (kBendBones - 1) of the frame's angle: p' = (p - c) R + c
+      for (uint32_t k = 0; k < kBendBones; k++) {
+        const float a = o.bend * std::sin(0.7f * (float)(f + 1)) * (float)k / (float)(kBendBones - 1);
+        const float cs = std::cos(a), sn = std::sin(a);
+        float* m = bendBones.data() + k * 16;
+        const float R[9] = {cs, sn, 0.0f, -sn, cs, 0.0f, 0.0f, 0.0f, 1.0f};
+        for (int r = 0; r < 3; r++)
+          for (int c = 0; c < 3; c++) m[4 * r + c] = R[3 * r + c];
+        for (int c = 0; c < 3; c++)
+          m[12 + c] = bendPivot[c] - (bendPivot[0] * R[c] + bendPivot[1] * R[3 + c] + bendPivot[2] * R[6 + c]);
+        m[15] = 1.0f;
+        // (a rotation is its own inverse transpose; the translation plays no part in a normal)
+        float* t = bendNormalBones.data() + k * 16;
+        for (int r = 0; r < 3; r++)
+          for (int c = 0; c < 3; c++) t[4 * r + c] = R[3 * r + c];
+        t[15] = 1.0f;
+      }
+      swayOk = swayOk && pipeline->updateSkinned(bendBones.data(), bendHasNormals ? bendNormalBones.data() : nullptr, kBendBones);
+    }
     if (!base.empty()) {
       moved = base;
       const float a = o.sway * extent * std::sin(0.7f * (float)(f + 1));
@@ -203,7 +271,7 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
   auto t0 = std::chrono::steady_clock::now();
   for (int f = warmup; f < o.frames; f++) frame(f);
   if (!swayOk) {
-    std::fprintf(stderr, "bdpt_render: updateGeometry failed\n");
+    std::fprintf(stderr, "bdpt_render: updateGeometry / updateSkinned failed\n");
     env.failLate();
     return res;
   }
@@ -269,6 +337,7 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--inflight")) o.inflight = std::atoi(v);
     else if (const char* v = next("--warmup")) o.warmup = std::atoi(v);  // of --frames: rendered before the clock starts (first-use allocations)
     else if (const char* v = next("--sway")) o.sway = (float)std::atof(v);
+    else if (const char* v = next("--bend")) o.bend = (float)std::atof(v);
     else if (const char* v = next("--gpus")) o.gpus = std::atoi(v);
     else if (const char* v = next("--rank")) o.rank = std::atoi(v);
     else if (const char* v = next("--world")) o.world = std::atoi(v);
@@ -277,7 +346,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }

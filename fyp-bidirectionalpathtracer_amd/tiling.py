@@ -191,6 +191,21 @@ class TileRenderer:
             keep_for_stream(self.streams[i], (positions, normals, bitangents))  # (read on every slot's stream)
         self.state["accum"] = 0
 
+    def set_skin(self, positions, bone_weights, bone_ids, num_bones, normals=None, bitangents=None):
+        """The same skin for every frame slot's context (Context.set_skin; synchronises)."""
+        for p in self.pipes:
+            p.ctx.set_skin(positions, bone_weights, bone_ids, num_bones, normals, bitangents)
+
+    def update_skinned(self, bones, normal_bones=None, keep_light_maps=False):
+        """The same pose for every frame slot's context (as update_geometry: each on its slot's stream, in frame order);
+        the running mean restarts.  Every rank applies it: skinning and refit are deterministic, the replicas stay equal."""
+        from . import keep_for_stream
+        for k in range(self.inflight):
+            i = (self.state["frame"] + k) % self.inflight
+            self.pipes[i].ctx.update_skinned(bones, normal_bones, C.c_void_p(self.streams[i].cuda_stream), keep_light_maps)
+            keep_for_stream(self.streams[i], (bones, normal_bones))
+        self.state["accum"] = 0
+
     def set_lights(self, lights):
         """Moved lights for every frame slot's context (as update_geometry); the running mean restarts."""
         for k in range(self.inflight):

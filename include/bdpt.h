@@ -407,6 +407,10 @@ int bdpt_set_environment(bdpt_ctx* ctx, const bdpt_environment* env);
  *                         Scene::update); the light count stays.
  * bdpt_get_refit_info     (none in the reference: the DXR driver's structure is opaque) — what a caller needs to decide
  *                         when a rebuild (bdpt_set_scene) pays off.
+ * bdpt_set_skin / bdpt_update_skinned
+ *                         SkinningCache::update (Graphics/Model/SkinningCache.cpp, ComputeSkinning.cs.slang; attached in
+ *                         RtScene.cpp:120) fed by Model::getBoneMatrices / getBoneInvTransposeMatrices: the vertices the
+ *                         refit consumes are skinned on the device from a bone palette (below, "Skinning").
  * Topology, texture coordinates, materials, textures and the light count stay as the last bdpt_set_scene set them.
  * Both calls are enqueued on `stream`.  When the context's previous call used another stream, they first wait (an
  * event) for what that call enqueued, which ends with everything of the context's own second stream; bdpt_gbuffer_execute
@@ -441,6 +445,67 @@ typedef struct bdpt_refit_info {
 int bdpt_update_geometry(bdpt_ctx* ctx, const bdpt_geometry_update* upd, void* stream);
 int bdpt_set_lights(bdpt_ctx* ctx, const bdpt_light* lights, uint32_t numLights, void* stream);
 int bdpt_get_refit_info(bdpt_ctx* ctx, bdpt_refit_info* out); /* synchronises */
+
+/* ---- Skinning: a bone palette per frame instead of three vertex streams ----
+ * bdpt_set_skin gives the context the rest pose, four bone ids and four weights per vertex; bdpt_update_skinned then
+ * takes the frame's bone matrices (a few KB), skins every vertex on the device into the context's own skinned streams
+ * and does what bdpt_update_geometry does with them: the refit, the area-light table's refresh when there is a table, the
+ * bitangent copy, the light maps' re-trace unless BDPT_UPDATE_KEEP_LIGHT_MAPS.  Ordering is bdpt_update_geometry's.
+ *
+ * Arithmetic: fp32, no contraction, exactly in this order (getBlendedBoneMat, mul(float4(pos, 1), boneMat),
+ * mul(normal, invTransposeBoneMat) and mul(bitangent, (float3x3)boneMat) of the shader).  A matrix is 16 floats m[4r+c]:
+ * the memory of the glm::mat4 getBoneMatrices hands over, translation in floats 12..14.  With the ids i0..i3 and the
+ * weights w0..w3 of a vertex, M the `bones` and the rest position p, normal n, bitangent b:
+ *   B[e]    = ((M[i0][e]*w0 + M[i1][e]*w1) + M[i2][e]*w2) + M[i3][e]*w3        T[e]: the same sum over `normalBones`
+ *   pos'[c] = ((p.x*B[c] + p.y*B[4+c]) + p.z*B[8+c]) + B[12+c]
+ *   n'[c]   = (n.x*T[c] + n.y*T[4+c]) + n.z*T[8+c]                             (not normalised, as in the shader)
+ *   b'[c]   = (b.x*B[c] + b.y*B[4+c]) + b.z*B[8+c]
+ * A vertex whose four weights are all zero (either sign) is static: its outputs are its rest values bit for bit, and its
+ * ids are neither checked nor read (the flattened static part of a scene).  Weights are not renormalised.  The previous
+ * frame's positions (gSkinnedPrevPositions, for motion vectors) are out of scope: nothing here keeps them.
+ *
+ * bdpt_set_skin synchronises and allocates everything a skinned update needs (rest streams, weights, ids, the skinned
+ * streams, the device palette, and the refit plan as bdpt_prepare(BDPT_PREPARE_REFIT) does); not inside a stream capture
+ * (BDPT_E_STATE).  After it a BDPT_MEMORY_DEVICE bdpt_update_skinned neither allocates nor synchronises and can be
+ * captured into a hipGraph; its palettes must stay valid until the stream reaches the update, and their finiteness is the
+ * caller's responsibility.  BDPT_MEMORY_HOST palettes are checked for finiteness and staged before the call returns;
+ * inside a capture they give BDPT_E_STATE.  bdpt_update_geometry stays usable on a skinned context: it overwrites the
+ * pose and leaves the rest pose alone.  A NULL desc drops the skin; bdpt_set_scene drops it too.
+ * Errors (nothing is enqueued, the scene and the skin stay as they were): no scene, or bdpt_update_skinned /
+ * bdpt_skinned_buffers without a skin BDPT_E_STATE; a NULL argument, numVertices or numBones not matching, numBones of 0,
+ * a non-zero reserved, unknown flags or memory, bitangents for a scene without any, normalBones missing when the skin has
+ * normals, a rest position, a weight or a host bone element that is not finite, an id >= numBones on a non-static vertex
+ * BDPT_E_INVALID; numBones above BDPT_MAX_BONES BDPT_E_LIMIT. */
+#define BDPT_MAX_BONES 1024
+typedef struct bdpt_skin_desc { /* all HOST pointers, copied before the call returns */
+  uint32_t numVertices;         /* must equal the scene's */
+  uint32_t numBones;            /* 1 .. BDPT_MAX_BONES */
+  const float* positions;       /* rest pose, numVertices x 3, required, finite */
+  const float* normals;         /* rest pose; NULL = a skinned update leaves normals alone */
+  const float* bitangents;      /* rest pose; NULL = left alone; only for a scene that has them */
+  const float* boneWeights;     /* numVertices x 4 */
+  const uint16_t* boneIds;      /* numVertices x 4 */
+  uint32_t reserved[2];         /* 0 */
+} bdpt_skin_desc;
+int bdpt_set_skin(bdpt_ctx* ctx, const bdpt_skin_desc* desc);
+typedef struct bdpt_skin_update {
+  const float* bones;       /* numBones x 16 floats */
+  const float* normalBones; /* numBones x 16: the inverse transposes; required iff the skin has normals */
+  uint32_t numBones;        /* must equal the skin's */
+  uint32_t memory;          /* BDPT_MEMORY_HOST / BDPT_MEMORY_DEVICE */
+  uint32_t flags;           /* BDPT_UPDATE_KEEP_LIGHT_MAPS or 0 */
+  uint32_t reserved;        /* 0 */
+} bdpt_skin_update;
+int bdpt_update_skinned(bdpt_ctx* ctx, const bdpt_skin_update* upd, void* stream);
+/* device pointers of the context's skinned streams (NULL for a stream the skin lacks); valid until bdpt_set_skin /
+ * bdpt_set_scene.  They hold the pose of the last bdpt_update_skinned once its stream has reached it. */
+int bdpt_skinned_buffers(bdpt_ctx* ctx, const float** positions, const float** normals, const float** bitangents);
+/* host-only, no context: the same arithmetic on the CPU, the same code as the kernel's (tests, callers that want the
+ * pose on the host).  outNormals / outBitangents are required iff the desc has the stream; normalBones iff it has normals.
+ * BDPT_E_INVALID / BDPT_E_LIMIT as above (the checks of the desc, NULL arguments, ids); the palettes' finiteness is not
+ * checked. */
+int bdpt_host_skin(const bdpt_skin_desc* desc, const float* bones, const float* normalBones, float* outPositions, float* outNormals,
+                   float* outBitangents);
 
 /* ---- Ray queries: a caller's own rays against the scene ----
  * bdpt_trace_rays         TraceRay from a caller's own ray-generation shader: ambient occlusion
@@ -1135,6 +1200,12 @@ int bdpt_test_bsdf(bdpt_ctx* ctx, const float* in, uint32_t n, uint32_t matIndex
  *   mode 1 (NEE sample; points[i]: the receiving point, 3 floats): prim, L.xyz, d, intensity.xyz, b1, b2, x.xyz, 0, 0, 0
  * With no emitter or W == 0 every output is 0.  Errors: mode > 1, a NULL array BDPT_E_INVALID; no scene BDPT_E_STATE. */
 int bdpt_test_area_light_sample(bdpt_ctx* ctx, uint32_t mode, const uint32_t* states, const float* points, uint32_t n, float* out);
+/* Skinning measurement hook: the skinning kernel of bdpt_update_skinned alone, enqueued on `stream` behind the context's
+ * previous call, with the context's device palette as the last BDPT_MEMORY_HOST update staged it (no refit: the scene is
+ * left as it was, the skinned streams are rewritten).  path 0: the path bdpt_update_skinned takes, 1: the global-memory
+ * gather, 2: the LDS-staged palette (where the palette is small enough for it, else the gather).  Errors: no skin
+ * BDPT_E_STATE, path > 2 BDPT_E_INVALID. */
+int bdpt_test_skin_kernel(bdpt_ctx* ctx, uint32_t path, void* stream);
 
 #ifdef __cplusplus
 }
