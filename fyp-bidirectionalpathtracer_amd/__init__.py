@@ -431,6 +431,26 @@ class Context:
 
         return self._surface_query("shade_hits", [("rays", rays, 8, f32), ("hits", hits, 4, i32)], (24, i32), run, out, count)
 
+    def keep_pose(self, stream=None):
+        """bdpt_keep_pose: the current pose becomes the previous one (after prepare(motion=True)).  Once per frame, before
+        that frame's updates — also in a frame without an update.  Enqueued on `stream` without a synchronise."""
+        self._check(self._lib.bdpt_keep_pose(self._h, stream), "bdpt_keep_pose")
+
+    def motion_query(self, hits, out=None, count=None, stream=None):
+        """bdpt_motion_query: where each hit's surface point was in the previous pose.  `hits` (N, 4) float32 or int32
+        (bdpt_hit: t, u, v, prim bits — trace_rays' `out` buffer).  Returns (N, 4) float32: (previous position, 1), zeros
+        for a miss or a prim outside the scene.  GPU tensors, `out` and `count` as for trace_rays; host arrays are copied,
+        queried, synchronised and returned as numpy."""
+        import torch
+
+        def run(ptrs, n, cnt, res):
+            d = abi.MotionDesc()
+            d.hits, d.num, d.reserved, d.numDevice, d.prevPositions = ptrs[0], n, 0, cnt, res
+            return self._lib.bdpt_motion_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("motion_query", [("hits", hits, 4, (torch.float32, torch.int32))], (4, (torch.float32,)), run, out,
+                                   count)
+
     def sample_bsdf(self, surfaces, seeds, mat_index=0, from_lobe=False, out=None, count=None, stream=None):
         """bdpt_bsdf_query(SAMPLE): sampleBRDF at each (N, 24) bdpt_surface record (shade_hits' output) with its seed
         ((N,) uint32 or int32 RNG states, read by value).  mat_index 0 GGX, 1 Lambertian; from_lobe sets
@@ -765,6 +785,12 @@ class Context:
         self._check(self._lib.bdpt_gbuffer_execute(self._h, C.byref(gparams), C.byref(gbuffer), stream),
                     "bdpt_gbuffer_execute")
 
+    def gbuffer_execute_motion(self, gparams, gbuffer, prev_position_ptr, stream=None):
+        """bdpt_gbuffer_execute plus the PrevWorldPosition channel (W x H float4 at `prev_position_ptr`): where each pixel's
+        surface point was in the previous pose (after prepare(motion=True))."""
+        self._check(self._lib.bdpt_gbuffer_execute_motion(self._h, C.byref(gparams), C.byref(gbuffer), prev_position_ptr, stream),
+                    "bdpt_gbuffer_execute_motion")
+
     def execute(self, params, gbuffer, out_ptr, stream=None):
         self._check(self._lib.bdpt_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_execute")
 
@@ -813,8 +839,9 @@ class Context:
         self._check(self._lib.bdpt_execute_tail(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream),
                     "bdpt_execute_tail")
 
-    def prepare(self, what):
-        self._check(self._lib.bdpt_prepare(self._h, int(what)), "bdpt_prepare")
+    def prepare(self, what=0, motion=False):
+        """bdpt_prepare(what); motion=True adds PREPARE_MOTION (the previous pose of keep_pose; needs a scene)."""
+        self._check(self._lib.bdpt_prepare(self._h, int(what) | (abi.PREPARE_MOTION if motion else 0)), "bdpt_prepare")
 
     def splat_buffer(self):
         p = C.c_void_p()
@@ -835,6 +862,11 @@ class Context:
     def bmfr_execute(self, params, gbuffer, noisy_ptr, stream=None):
         self._check(self._lib.bdpt_bmfr_execute(self._h, C.byref(params), C.byref(gbuffer), noisy_ptr, stream),
                     "bdpt_bmfr_execute")
+
+    def bmfr_execute_motion(self, params, gbuffer, prev_position_ptr, noisy_ptr, stream=None):
+        """bdpt_bmfr_execute reprojecting through the PrevWorldPosition channel at `prev_position_ptr` (W x H float4)."""
+        self._check(self._lib.bdpt_bmfr_execute_motion(self._h, C.byref(params), C.byref(gbuffer), prev_position_ptr, noisy_ptr,
+                                                       stream), "bdpt_bmfr_execute_motion")
 
     def bmfr_reset(self):
         self._check(self._lib.bdpt_bmfr_reset(self._h), "bdpt_bmfr_reset")
@@ -973,10 +1005,16 @@ class FramePipeline:
     pass: render_frame's ``accumulate`` has no effect.  active_pixels() reads how many pixels the next frame renders (0:
     the image has converged); adaptive_reset() starts over (after a camera, scene or light change).  Whole frames only,
     and not with light_groups.
+
+    motion=True keeps the previous pose (Context.prepare(motion=True)): every G-buffer pass also writes ``prev_position``
+    ((H, W, 4) float32: where each pixel's surface point was at the previous frame's G-buffer pass, for
+    Context.bmfr_execute_motion), and render_frame ends its G-buffer stage with keep_pose, so that the updates a caller
+    issues between two render_frame calls are measured against the pose the earlier frame rendered, and a frame without
+    an update gets zero motion.
     """
 
     def __init__(self, scene, width, height, max_depth=3, mat_index=0, device=0, tile=None, clamp_upper=0.9, min_t=1e-4,
-                 accum_limit=100, flags=0, stripes=None, light_groups=False, adaptive=None):
+                 accum_limit=100, flags=0, stripes=None, light_groups=False, adaptive=None, motion=False):
         import torch
         self.torch = torch
         self.adaptive_params = None if adaptive is None else adaptive_params(adaptive)
@@ -1037,6 +1075,10 @@ class FramePipeline:
                 k = int(scene.desc.numLights) + 1 if self.group_assignment is None else max(self.group_assignment) + 2
                 self.light_groups = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
                 self.light_groups_accum = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
+            self.prev_position = None
+            if motion:
+                self.ctx.prepare(motion=True)
+                self.prev_position = torch.zeros(self.H, self.W, 4, dtype=torch.float32, device=self.dev)
             self.adaptive_state = None
             if adaptive is not None:
                 self.adaptive_state = {
@@ -1100,7 +1142,10 @@ class FramePipeline:
         """One pipeline frame.  Returns the bdpt_params used (for the oracle to mirror)."""
         st = self._stream_ptr()
         gp = self.gbuffer_params()
-        if gbuffer:
+        if gbuffer and self.prev_position is not None:
+            self.ctx.gbuffer_execute_motion(gp, self.gb, C.c_void_p(self.prev_position.data_ptr()), st)
+            self.ctx.keep_pose(st)  # (the start of the next step: before the updates the caller issues for it)
+        elif gbuffer:
             self.ctx.gbuffer_execute(gp, self.gb, st)
         p = self.bdpt_params(extra_flags)
         if self.adaptive_state is not None:
@@ -1236,6 +1281,12 @@ class FramePipeline:
         """Context.splat_add on this pipeline's stream."""
         self.ctx.splat_add(splat, pixels, values, visible, items, count, self._stream_ptr())
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (splat, pixels, values, visible, items, count))
+
+    def motion_query(self, hits, out=None, count=None):
+        """Context.motion_query on this pipeline's stream."""
+        res = self.ctx.motion_query(hits, out, count, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (hits, count, res))
+        return res
 
     def set_lights(self, lights):
         """Move the scene's lights (Context.set_lights on this pipeline's stream); accumulation restarts."""

@@ -31,6 +31,7 @@ PREPARE_REFIT = 4
 PREPARE_LIGHT_GROUPS = 8
 PREPARE_AREA_LIGHTS = 16
 PREPARE_LIGHT_GROUP_TABLE = 32
+PREPARE_MOTION = 64
 MEMORY_HOST, MEMORY_DEVICE = 0, 1
 UPDATE_KEEP_LIGHT_MAPS = 1
 BDPT_MAX_BONES = 1024
@@ -196,6 +197,11 @@ class ShadeDesc(C.Structure):
                 ("numHitsDevice", C.c_void_p), ("surfaces", C.c_void_p)]
 
 
+class MotionDesc(C.Structure):
+    _fields_ = [("hits", C.c_void_p), ("num", C.c_uint32), ("reserved", C.c_uint32), ("numDevice", C.c_void_p),
+                ("prevPositions", C.c_void_p)]
+
+
 class BsdfSample(C.Structure):
     _fields_ = [("dir", C.c_float * 3), ("pdf", C.c_float), ("weight", C.c_float * 3), ("specular", C.c_uint32)]
 
@@ -279,6 +285,8 @@ PROTOTYPES = {
     "bdpt_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(GBufferParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdpt_shade_hits": (C.c_int, [C.c_void_p, C.POINTER(ShadeDesc), C.c_void_p]),
     "bdpt_bsdf_query": (C.c_int, [C.c_void_p, C.POINTER(BsdfDesc), C.c_void_p]),
+    "bdpt_keep_pose": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bdpt_motion_query": (C.c_int, [C.c_void_p, C.POINTER(MotionDesc), C.c_void_p]),
     "bdpt_light_query": (C.c_int, [C.c_void_p, C.POINTER(LightDesc), C.c_void_p]),
     "bdpt_connect_query": (C.c_int, [C.c_void_p, C.POINTER(ConnectDesc), C.c_void_p]),
     "bdpt_splat_add": (C.c_int, [C.c_void_p, C.POINTER(SplatDesc), C.c_void_p]),
@@ -292,6 +300,7 @@ PROTOTYPES = {
     "bdpt_msaa_jitter": (None, [C.c_uint32, C.POINTER(C.c_float)]),
     "bdpt_resize": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, Tile, C.c_uint32]),
     "bdpt_gbuffer_execute": (C.c_int, [C.c_void_p, C.POINTER(GBufferParams), C.POINTER(GBuffer), C.c_void_p]),
+    "bdpt_gbuffer_execute_motion": (C.c_int, [C.c_void_p, C.POINTER(GBufferParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_execute": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_execute_tail": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_execute_light_groups": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(GBuffer), C.c_void_p, C.c_void_p,
@@ -315,6 +324,7 @@ PROTOTYPES = {
     "bdpt_set_splat_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "bdpt_resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdpt_bmfr_execute": (C.c_int, [C.c_void_p, C.POINTER(BmfrParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "bdpt_bmfr_execute_motion": (C.c_int, [C.c_void_p, C.POINTER(BmfrParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdpt_bmfr_reset": (C.c_int, [C.c_void_p]),
     "bdpt_bmfr_history_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "bdpt_bmfr_save_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),

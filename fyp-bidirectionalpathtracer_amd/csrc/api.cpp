@@ -150,6 +150,9 @@ struct bdpt_ctx {
   bool haveSkin = false;
   SkinDev skin{};
   float* skinPalette[2] = {nullptr, nullptr};
+  // motion (bdpt_prepare(BDPT_PREPARE_MOTION)): the previous pose, three float4 per primitive, in sceneAllocs (a new scene
+  // drops it); bdpt_keep_pose copies the current corners into it
+  float4* prevPose = nullptr;
 };
 
 namespace {
@@ -463,6 +466,7 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
   c->areaTextured = 0;
   c->areaBlockSum = nullptr;
   c->areaBlockLast = nullptr;
+  c->prevPose = nullptr;
   for (float*& p : c->stage) p = nullptr;
   c->stageInFlight = false;
   c->S.stackOvf = c->stackOvf;
@@ -1692,12 +1696,9 @@ int resizeRows(bdpt_ctx* c, uint32_t width, uint32_t height, uint32_t maxDepth) 
 }
 }  // namespace
 
-int bdpt_gbuffer_execute(bdpt_ctx* c, const bdpt_gbuffer_params* gp, const bdpt_gbuffer* out, void* stream) {
-  if (!c || !gp || !out) return BDPT_E_INVALID;
-  if (!c->haveScene || !c->haveCamera || !c->haveSize) {
-    fail(c, "gbuffer_execute: scene, camera and size must be set first");
-    return BDPT_E_STATE;
-  }
+namespace {
+// bdpt_gbuffer_execute (prevPosition == NULL) and bdpt_gbuffer_execute_motion
+int gbufferRun(bdpt_ctx* c, const bdpt_gbuffer_params* gp, const bdpt_gbuffer* out, float* prevPosition, void* stream) {
   if (!out->worldPosition || !out->worldNormal || !out->materialDiffuse || !out->materialSpecRough ||
       !out->materialExtraParams || !out->emissive) {
     fail(c, "gbuffer_execute: all six channels are required");
@@ -1723,7 +1724,100 @@ int bdpt_gbuffer_execute(bdpt_ctx* c, const bdpt_gbuffer_params* gp, const bdpt_
     c->hintCam = c->cam;
     c->hintCamValid = true;
   }
-  launchGBuffer(c->S, G, st);
+  if (prevPosition) {
+    MotionDev M{};
+    M.prevPose = c->prevPose;
+    M.prevPosition = reinterpret_cast<float4*>(prevPosition);
+    launchGBufferMotion(c->S, G, M, st);
+  } else {
+    launchGBuffer(c->S, G, st);
+  }
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+}  // namespace
+
+int bdpt_gbuffer_execute(bdpt_ctx* c, const bdpt_gbuffer_params* gp, const bdpt_gbuffer* out, void* stream) {
+  if (!c || !gp || !out) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->haveCamera || !c->haveSize) {
+    fail(c, "gbuffer_execute: scene, camera and size must be set first");
+    return BDPT_E_STATE;
+  }
+  return gbufferRun(c, gp, out, nullptr, stream);
+}
+
+// ---- motion: the previous pose (motion.hip) and the calls that read it ----
+namespace {
+int allocPrevPose(bdpt_ctx* c) {
+  if (c->prevPose) return BDPT_OK;
+  if (streamIsCapturing(c->lastStream)) {
+    fail(c, "prepare: BDPT_PREPARE_MOTION allocates and synchronises: not inside a stream capture");
+    return BDPT_E_STATE;
+  }
+  float4* pose = nullptr;
+  if (int rc = devAlloc(c, c->sceneAllocs, &pose, (size_t)c->numTriangles * 3)) return rc;
+  HIPCHK(c, hipDeviceSynchronize());  // (updates in flight on any stream: the first previous pose is the current one)
+  launchKeepPose(c->S.shade, c->numTriangles, pose, nullptr);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipDeviceSynchronize());
+  c->prevPose = pose;
+  return BDPT_OK;
+}
+}  // namespace
+
+int bdpt_keep_pose(bdpt_ctx* c, void* stream) {
+  if (!c) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->prevPose) {
+    fail(c, c->haveScene ? "keep_pose: no previous pose (bdpt_prepare(BDPT_PREPARE_MOTION) first)" : "keep_pose: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  launchKeepPose(c->S.shade, c->numTriangles, c->prevPose, st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
+int bdpt_gbuffer_execute_motion(bdpt_ctx* c, const bdpt_gbuffer_params* gp, const bdpt_gbuffer* out, float* prevPosition, void* stream) {
+  if (!c || !gp || !out) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->haveCamera || !c->haveSize) {
+    fail(c, "gbuffer_execute_motion: scene, camera and size must be set first");
+    return BDPT_E_STATE;
+  }
+  if (!c->prevPose) {
+    fail(c, "gbuffer_execute_motion: no previous pose (bdpt_prepare(BDPT_PREPARE_MOTION) first)");
+    return BDPT_E_STATE;
+  }
+  if (!aligned(prevPosition, 16)) {
+    fail(c, "gbuffer_execute_motion: prevPosition missing or not 16-byte aligned");
+    return BDPT_E_INVALID;
+  }
+  return gbufferRun(c, gp, out, prevPosition, stream);
+}
+
+int bdpt_motion_query(bdpt_ctx* c, const bdpt_motion_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->prevPose) {
+    fail(c, c->haveScene ? "motion_query: no previous pose (bdpt_prepare(BDPT_PREPARE_MOTION) first)" : "motion_query: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (d->reserved) {
+    fail(c, "motion_query: reserved must be 0");
+    return BDPT_E_INVALID;
+  }
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->hits, 16) || !aligned(d->prevPositions, 16) || (d->numDevice && !aligned(d->numDevice, 4))) {
+    fail(c, "motion_query: hits or prevPositions missing or not aligned (16 bytes; numDevice 4)");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  launchMotionQuery(c->prevPose, c->numTriangles, reinterpret_cast<const float4*>(d->hits), d->num, d->numDevice,
+                    reinterpret_cast<float4*>(d->prevPositions), st);
   HIPCHK(c, hipGetLastError());
   c->lastStream = st;
   return BDPT_OK;
@@ -2163,7 +2257,7 @@ int bdpt_execute_tail(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in,
 // Allocate the optional buffers up front so that no later execute allocates (hipGraph capture, latency).
 int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
   if (!c) return BDPT_E_INVALID;
-  if ((what & ~(BDPT_PREPARE_REFIT | BDPT_PREPARE_AREA_LIGHTS)) || !what) {
+  if ((what & ~(BDPT_PREPARE_REFIT | BDPT_PREPARE_AREA_LIGHTS | BDPT_PREPARE_MOTION)) || !what) {
     if (!c->haveSize) {
       fail(c, "prepare: bdpt_resize must be called first");
       return BDPT_E_STATE;
@@ -2175,6 +2269,10 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
   }
   if ((what & BDPT_PREPARE_AREA_LIGHTS) && !c->haveScene) {
     fail(c, "prepare: BDPT_PREPARE_AREA_LIGHTS needs a scene");
+    return BDPT_E_STATE;
+  }
+  if ((what & BDPT_PREPARE_MOTION) && !c->haveScene) {
+    fail(c, "prepare: BDPT_PREPARE_MOTION needs a scene");
     return BDPT_E_STATE;
   }
   if ((what & (BDPT_PREPARE_LIGHT_GROUPS | BDPT_PREPARE_LIGHT_GROUP_TABLE)) && !c->haveScene) {
@@ -2192,12 +2290,15 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
     if (int rc = allocLightGroups(c, nullptr, c->S.numLights + ((what & BDPT_PREPARE_LIGHT_GROUP_TABLE) ? 1u : 0u))) return rc;
   if (what & BDPT_PREPARE_AREA_LIGHTS)
     if (int rc = ensureAreaLights(c, nullptr)) return rc;
+  if (what & BDPT_PREPARE_MOTION)
+    if (int rc = allocPrevPose(c)) return rc;
   return BDPT_OK;
 }
 
 // BlockwiseMultiOrderFeatureRegression::execute (DenoisePass.cpp:146-204)
-int bdpt_bmfr_execute(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, float* noisy, void* stream) {
-  if (!c || !p || !g || !noisy) return BDPT_E_INVALID;
+namespace {
+// bdpt_bmfr_execute (prevPosition == NULL) and bdpt_bmfr_execute_motion
+int bmfrRun(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, const float* prevPosition, float* noisy, void* stream) {
   if (!c->haveSize) {
     fail(c, "bmfr: bdpt_resize must be called first");
     return BDPT_E_STATE;
@@ -2238,6 +2339,7 @@ int bdpt_bmfr_execute(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer
   A.prevFilteredW = c->bmfrFiltered[w];
   A.accept = c->bmfrAccept;
   A.prevPixel = c->bmfrPrevPixel;
+  A.prevPos = reinterpret_cast<const float4*>(prevPosition);
   if (!(p->flags & BDPT_BMFR_POSTPROCESS))  // no new filtered frame this time: keep the old one on the read side next frame
     HIPCHK(c, hipMemcpyAsync(c->bmfrFiltered[w], c->bmfrFiltered[r], n * sizeof(float4), hipMemcpyDeviceToDevice, st));
   launchBmfr(A, p->flags, st);
@@ -2245,6 +2347,22 @@ int bdpt_bmfr_execute(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer
   c->bmfrRead = w;
   c->lastStream = st;
   return BDPT_OK;
+}
+}  // namespace
+
+int bdpt_bmfr_execute(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, float* noisy, void* stream) {
+  if (!c || !p || !g || !noisy) return BDPT_E_INVALID;
+  return bmfrRun(c, p, g, nullptr, noisy, stream);
+}
+
+int bdpt_bmfr_execute_motion(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, const float* prevPosition, float* noisy,
+                             void* stream) {
+  if (!c || !p || !g || !noisy) return BDPT_E_INVALID;
+  if (!aligned(prevPosition, 16)) {
+    fail(c, "bmfr_execute_motion: prevPosition missing or not 16-byte aligned");
+    return BDPT_E_INVALID;
+  }
+  return bmfrRun(c, p, g, prevPosition, noisy, stream);
 }
 
 int bdpt_bmfr_reset(bdpt_ctx* c) {

@@ -56,6 +56,10 @@ BD float addRandom(float value, uint32_t id, uint32_t sub, uint32_t featureBuffe
 
 }  // namespace
 
+// MOTION (bdpt_bmfr_execute_motion): the reprojection and the position test use q = A.prevPos[i], where the pixel's surface
+// point was in the previous frame, instead of its current position cp; everything else, the history write included, is
+// the plain instance's.
+template <bool MOTION>
 __global__ __launch_bounds__(256) void bmfr_preprocess_kernel(BmfrDev A) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const uint32_t n = A.W * A.H;
@@ -63,6 +67,7 @@ __global__ __launch_bounds__(256) void bmfr_preprocess_kernel(BmfrDev A) {
   const int W = (int)A.W, H = (int)A.H;
   const int x = (int)(i % A.W), y = (int)(i / A.W);
   const float4 cp = A.curPos[i];
+  const float4 q = MOTION ? A.prevPos[i] : cp;
   const float4 cn = loadHalf4(A.curNorm, i);
   float4 cur = A.noisy[i];
   const float posx = (float)x + 0.5f, posy = (float)y + 0.5f;
@@ -77,7 +82,7 @@ __global__ __launch_bounds__(256) void bmfr_preprocess_kernel(BmfrDev A) {
     if (A.frame > 0) {
       float c[4];
 #pragma unroll
-      for (int r = 0; r < 4; r++) c[r] = ((A.m[4 * r] * cp.x + A.m[4 * r + 1] * cp.y) + A.m[4 * r + 2] * cp.z) + A.m[4 * r + 3];
+      for (int r = 0; r < 4; r++) c[r] = ((A.m[4 * r] * q.x + A.m[4 * r + 1] * q.y) + A.m[4 * r + 2] * q.z) + A.m[4 * r + 3];
       float ux = c[0] / c[3], uy = c[1] / c[3];
       ux = (ux + 1.0f) / 2.0f;
       uy = (1 - uy) / 2.0f;
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(256) void bmfr_preprocess_kernel(BmfrDev A) {
           if (sx >= 0 && sy >= 0 && sx < W && sy < H) {
             const size_t j = (size_t)sy * W + sx;
             const float4 pp = A.prevPosR[j];
-            const float dx = pp.x - cp.x, dy = pp.y - cp.y, dz = pp.z - cp.z;
+            const float dx = pp.x - q.x, dy = pp.y - q.y, dz = pp.z - q.z;
             const float pd = (dx * dx + dy * dy) + dz * dz;
             if (pd < 0.01f) {
               const float4 pn = A.prevNormR[j];
@@ -407,7 +412,10 @@ void launchBmfr(const BmfrDev& A, uint32_t flags, hipStream_t st) {
   const uint32_t n = A.W * A.H;
   if (!n) return;
   const dim3 grid((n + 255u) / 256u), block(256);
-  hipLaunchKernelGGL(bmfr_preprocess_kernel, grid, block, 0, st, A);
+  if (A.prevPos)
+    hipLaunchKernelGGL(bmfr_preprocess_kernel<true>, grid, block, 0, st, A);
+  else
+    hipLaunchKernelGGL(bmfr_preprocess_kernel<false>, grid, block, 0, st, A);
   if (flags & BDPT_BMFR_REGRESSION) {
     const int bw = ((int)A.W + 31) / 32, bh = ((int)A.H + 31) / 32;
     int w = bw + 1;

@@ -252,11 +252,27 @@ struct BmfrDev {
   float4 *prevPosW, *prevNormW, *prevNoisyW, *prevFilteredW;
   uint8_t* accept;             // BMFR_AcceptedBools
   uint32_t* prevPixel;         // BMFR_PrevFramePixel, RG16Float
+  const float4* prevPos;       // bdpt_bmfr_execute_motion: where each pixel's surface point was last frame; NULL = curPos
 };
 void launchBmfr(const BmfrDev& A, uint32_t flags, hipStream_t st);
 
+// Motion (motion.hip, device_motion.hpp; contract in include/bdpt.h "Motion"): the previous pose, three float4 per
+// primitive (the corners p0, p1, p2 in primitive order, w unused), and the G-buffer channel made from it.  Only the MOTION
+// instance of gbuffer_kernel takes it (last argument), so SceneDev, GBufferDev and every other instance stay as they are.
+struct MotionDev {
+  const float4* prevPose;  // 3 per primitive
+  float4* prevPosition;    // W*H texels, frame order: (where the pixel's surface point was, 1), zeros on a miss
+};
+// prevPose <- the corner positions of the current shading records (words r0.xyz, r2.xyz, r4.xyz)
+void launchKeepPose(const float4* shade, uint32_t numTris, float4* prevPose, hipStream_t st);
+// bdpt_motion_query: out[i] = (prevPosAtHit(hits[i]), 1), zeros for a miss or a prim outside the scene; count caps cap
+void launchMotionQuery(const float4* prevPose, uint32_t numTris, const float4* hits, uint32_t cap, const uint32_t* count, float4* out,
+                       hipStream_t st);
+
 // launchers (kernels.hip)
 void launchGBuffer(const SceneDev& S, const GBufferDev& G, hipStream_t st);
+// bdpt_gbuffer_execute_motion: launchGBuffer plus M.prevPosition (G.counters unused)
+void launchGBufferMotion(const SceneDev& S, const GBufferDev& G, const MotionDev& M, hipStream_t st);
 // SceneDev::alphaRecs (4 float4 per non-opaque triangle, in the order of alphaTris) from the shading records and material tables
 // quadByTex: per texture id the device address of its alpha-quad plane (texture_planes.h alphaQuadRows), 0 where it has none
 void launchAlphaRecs(const SceneDev& S, const uint32_t* alphaTris, uint32_t n, const unsigned long long* quadByTex, float4* out, hipStream_t st);

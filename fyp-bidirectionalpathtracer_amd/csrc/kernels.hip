@@ -28,6 +28,7 @@
 #include "device_area.hpp"
 #include "device_connect.hpp"  // pairRay, pairValue, splatTarget, splatTerm (shared with connect_query.hip)
 #include "device_math.hpp"
+#include "device_motion.hpp"
 #include "device_scene.hpp"
 #include "device_trace.hpp"
 #include "launch.hpp"
@@ -181,8 +182,11 @@ BD f3 envLookup(const float* envMap, uint32_t envW, uint32_t envH, f3 d) {
 // HINT_ONLY: the primary ray of EVERY frame pixel (G.Np = W * H, no pixel list), and only its occluder-hint word is
 // written — what a context that renders a band or one rank's stripes runs when the camera has moved, so that its
 // light-tracing rays, which may aim at any pixel of the frame, find a hint outside its own rows too.
-template <bool COUNT, bool HINT_ONLY = false>
-__global__ __launch_bounds__(kWave) void gbuffer_kernel(SceneDev S, GBufferDev G) {
+// MOTION (bdpt_gbuffer_execute_motion): one more channel, the hit point's place in the previous pose (device_motion.hpp);
+// the instance takes the MotionDev as its last argument, the others an empty struct, as the frame kinds below do.
+struct NoArg {};
+template <bool COUNT, bool HINT_ONLY = false, bool MOTION = false>
+__global__ __launch_bounds__(kWave) void gbuffer_kernel(SceneDev S, GBufferDev G, std::conditional_t<MOTION, MotionDev, NoArg> M) {
   BDPT_ONE_WAVE_PER_GROUP();
   __shared__ int s_stack[kStackEntries * kWave];
   const uint32_t p = blockIdx.x * kWave + threadIdx.x;
@@ -212,7 +216,12 @@ __global__ __launch_bounds__(kWave) void gbuffer_kernel(SceneDev S, GBufferDev G
     packHalf4(G.gb.materialSpecRough, pix, 0, 0, 0, 0);
     packHalf4(G.gb.materialExtraParams, pix, 0, 0, 0, 0);
     packHalf4(G.gb.emissive, pix, 0, 0, 0, 0);
+    if constexpr (MOTION) M.prevPosition[pix] = make_float4(0, 0, 0, 0);
     return;
+  }
+  if constexpr (MOTION) {
+    const f3 q = prevPosAtHit(M, (uint32_t)h.prim, h.u, h.v);
+    M.prevPosition[pix] = make_float4(q.x, q.y, q.z, 1.0f);
   }
   Shading sd = shadeHit<true>(S, (uint32_t)h.prim, h.u, h.v, camPos);
   oP[pix] = make_float4(sd.posW.x, sd.posW.y, sd.posW.z, 1.0f);
@@ -260,7 +269,6 @@ __global__ __launch_bounds__(kWave) void light_map_kernel(SceneDev S, uint32_t* 
 // Frame kinds (FrameKind, kernels.h): the last argument of a per-pixel kernel of kind V, and the GroupDev / MaskDev its
 // lane functions take (zero for the other kinds).
 // ------------------------------------------------------------------------------------------------
-struct NoArg {};
 template <FrameKind V>
 using FrameArg = std::conditional_t<V == FrameKind::Groups, GroupDev, std::conditional_t<V == FrameKind::Masked, MaskDev, NoArg>>;
 template <class A>
@@ -1690,7 +1698,11 @@ static FrameArg<K> frameArg(const FrameVariant& V) {
 void launchGBuffer(const SceneDev& S, const GBufferDev& G, hipStream_t st) {
   const uint32_t Np = G.Np;
   if (!Np) return;
-  withFlags([&](auto CNT) { launchWave(gbuffer_kernel<CNT>, blocksFor(Np), st, S, G); }, G.counters != nullptr);
+  withFlags([&](auto CNT) { launchWave(gbuffer_kernel<CNT>, blocksFor(Np), st, S, G, NoArg{}); }, G.counters != nullptr);
+}
+void launchGBufferMotion(const SceneDev& S, const GBufferDev& G, const MotionDev& M, hipStream_t st) {
+  if (!G.Np) return;
+  launchWave(gbuffer_kernel<false, false, true>, blocksFor(G.Np), st, S, G, M);
 }
 
 // The 64-byte alpha-test record of every non-opaque triangle (device_scene.hpp alphaTestFails: the triangle's three texture
@@ -1734,7 +1746,7 @@ void launchAlphaRecs(const SceneDev& S, const uint32_t* alphaTris, uint32_t n, c
 
 void launchHintFill(const SceneDev& S, const GBufferDev& G, hipStream_t st) {  // G.Np = W * H, G.pix unused
   if (!G.Np || !G.hintPix) return;
-  launchWave(gbuffer_kernel<false, true>, (uint32_t)(blocksFor(G.Np)), st, S, G);
+  launchWave(gbuffer_kernel<false, true>, (uint32_t)(blocksFor(G.Np)), st, S, G, NoArg{});
 }
 
 void launchLightMaps(const SceneDev& S, uint32_t* maps, uint32_t res, hipStream_t st) {

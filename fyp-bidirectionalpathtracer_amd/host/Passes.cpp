@@ -387,6 +387,36 @@ void RayLaunch::setScene(Scene::SharedPtr pScene) {
       std::fprintf(stderr, "[RayLaunch] bdpt_set_scene failed: %s\n", bdpt_last_error(c));
       mSceneSet = false;
     }
+  if (mSceneSet && mMotion) prepareMotion();  // (a new scene dropped the previous pose)
+}
+bool RayLaunch::prepareMotion() {
+  const uint32_t n = (uint32_t)mMore.size() + 1;
+  for (uint32_t s = 0; s < n; s++) {
+    bdpt_ctx* c = s == 0 ? mCtx : mMore[s - 1];
+    if (bdpt_prepare(c, BDPT_PREPARE_MOTION) != BDPT_OK) {
+      std::fprintf(stderr, "[RayLaunch] bdpt_prepare(BDPT_PREPARE_MOTION) failed: %s\n", bdpt_last_error(c));
+      return false;
+    }
+  }
+  return true;
+}
+bool RayLaunch::requestMotion() {
+  if (!mCtx) return false;
+  mMotion = true;
+  return mSceneSet ? prepareMotion() : true;
+}
+bool RayLaunch::keepPose(const std::vector<hipStream_t>& streams, uint32_t first) {
+  if (!mCtx || !mSceneSet || !mMotion) return false;
+  const uint32_t n = (uint32_t)mMore.size() + 1;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t s = (first + k) % n;
+    bdpt_ctx* c = s == 0 ? mCtx : mMore[s - 1];
+    if (bdpt_keep_pose(c, s < streams.size() ? streams[s] : nullptr) != BDPT_OK) {
+      std::fprintf(stderr, "[RayLaunch] bdpt_keep_pose failed: %s\n", bdpt_last_error(c));
+      return false;
+    }
+  }
+  return true;
 }
 bool RayLaunch::updateGeometry(const bdpt_geometry_update& u, const std::vector<hipStream_t>& streams, uint32_t first) {
   if (!mCtx || !mSceneSet) return false;
@@ -561,7 +591,12 @@ void LightProbeGBufferPass::execute(RenderContext* pRenderContext) {
     cam->setJitter(0, 0);
   }
   mFrameCount++;
-  if (bdpt_gbuffer_execute(mpRays->ctx(), &gp, &gb, pRenderContext->getStream()) != BDPT_OK)
+  // a pass asked for the PrevWorldPosition channel (the motion-aware denoiser): the same pass, one more channel
+  Texture::SharedPtr prevPos = mpRays->motion() ? mpResManager->getTexture("PrevWorldPosition") : nullptr;
+  const int rc = prevPos && prevPos->getFormat() == ResourceFormat::RGBA32Float
+                     ? bdpt_gbuffer_execute_motion(mpRays->ctx(), &gp, &gb, (float*)prevPos->getDevicePointer(), pRenderContext->getStream())
+                     : bdpt_gbuffer_execute(mpRays->ctx(), &gp, &gb, pRenderContext->getStream());
+  if (rc != BDPT_OK)
     std::fprintf(stderr, "[LightProbeGBufferPass] %s\n", mpRays->lastError());
 }
 
@@ -724,6 +759,10 @@ bool BlockwiseMultiOrderFeatureRegression::initialize(RenderContext* pRenderCont
   mpResManager->requestTextureResources({"WorldPosition", "WorldNormal", "MaterialDiffuse"});  // the three feature buffers
   mpRays = RayLaunch::create(pRenderContext);
   setGuiSize(ivec2{250, 135});
+  if (mpRays && mMotion) {
+    mpResManager->requestTextureResource("PrevWorldPosition");  // RGBA32F, rendered by the G-buffer pass
+    if (!mpRays->requestMotion()) return false;
+  }
   return mpRays != nullptr;
 }
 void BlockwiseMultiOrderFeatureRegression::initScene(RenderContext*, Scene::SharedPtr pScene) {
@@ -772,7 +811,10 @@ void BlockwiseMultiOrderFeatureRegression::execute(RenderContext* pRenderContext
     gb.materialDiffuse = mFullAlb;
     noisy = mFullNoisy;
   }
-  if (bdpt_bmfr_execute(mpRays->ctx(), &p, &gb, noisy, pRenderContext->getStream()) != BDPT_OK) {
+  Texture::SharedPtr prevPos = (mMotion && !mpRays->tiled()) ? mpResManager->getTexture("PrevWorldPosition") : nullptr;
+  const int rc = prevPos ? bdpt_bmfr_execute_motion(mpRays->ctx(), &p, &gb, (const float*)prevPos->getDevicePointer(), noisy, pRenderContext->getStream())
+                         : bdpt_bmfr_execute(mpRays->ctx(), &p, &gb, noisy, pRenderContext->getStream());
+  if (rc != BDPT_OK) {
     std::fprintf(stderr, "[BMFR] %s\n", mpRays->lastError());
     return;
   }
@@ -991,6 +1033,7 @@ void RenderingPipeline::renderFrame() {
     for (auto& p : mActivePasses)
       if (p) p->onExecute(&mContext);
     mFrameIndex++;
+    keepPose();
     return;
   }
   // this frame's slot: its stream (in order behind the frame that used the slot before), channels and launcher context
@@ -1007,6 +1050,16 @@ void RenderingPipeline::renderFrame() {
     if (ordered) (void)hipEventRecord(mOrderEvents[i], mSlotStreams[slot]);
   }
   mFrameIndex++;
+  keepPose();
+}
+// A pass asked for motion: the pose this frame rendered becomes the previous pose, once per frame, here at the frame's end
+// — which is before the next frame's updates, also when there are none (an object that stops gets zero motion).
+void RenderingPipeline::keepPose() {
+  RayLaunch::SharedPtr rays = mpRays ? mpRays : RayLaunch::create(&mContext);
+  if (!rays || !rays->motion() || !rays->readyToRender()) return;
+  uint32_t first = 0;
+  const std::vector<hipStream_t> streams = updateStreams(first);
+  (void)rays->keepPose(streams, first);
 }
 // ---- checkpoints (byte helpers: top of the file)
 

@@ -29,6 +29,12 @@ class RayLaunch {
   // nullptr drops it), and the same bone palette for each, ordered as updateGeometry's.
   bool setSkin(const bdpt_skin_desc* skin);
   bool updateSkinned(const bdpt_skin_update& u, const std::vector<hipStream_t>& streams, uint32_t first);
+  // Motion (include/bdpt.h "Motion"): a pass that wants the PrevWorldPosition channel asks for the previous pose; every
+  // frame slot's context then prepares it with its scene (bdpt_prepare(BDPT_PREPARE_MOTION)), and keepPose makes the
+  // current pose the previous one on each, ordered as updateGeometry's.
+  bool requestMotion();
+  bool motion() const { return mMotion; }
+  bool keepPose(const std::vector<hipStream_t>& streams, uint32_t first);
   void setMaxRecursionDepth(uint32_t d) { mMaxDepth = d; }
   bool readyToRender() const { return mCtx && mSceneSet; }
   // (re)size the per-pixel path state; called by execute when the screen size changed
@@ -63,6 +69,8 @@ class RayLaunch {
   int mDevice = 0;
   Scene::SharedPtr mpScene;
   bool mSceneSet = false;
+  bool mMotion = false;
+  bool prepareMotion();
   uint32_t mW = 0, mH = 0, mMaxDepth = 8, mSizedDepth = 0;
 };
 
@@ -170,6 +178,11 @@ class BlockwiseMultiOrderFeatureRegression : public RenderPass {
     return SharedPtr(new BlockwiseMultiOrderFeatureRegression(bufferToDenoise));
   }
   uint32_t getAccumCount() const { return mAccumCount; }
+  // Motion-aware reprojection for animated scenes (bdpt_bmfr_execute_motion): the pass requests the PrevWorldPosition
+  // channel, which the G-buffer pass then renders, and the pipeline keeps the previous pose once per frame.  Call before
+  // the pipeline's initialize().  Whole-frame pipelines only: a tiled pipeline runs the plain call (the channel is not
+  // part of its all-gather).  Default off: the reference's static-scene behaviour.
+  void setMotion(bool on) { mMotion = on; }
   ~BlockwiseMultiOrderFeatureRegression() override { freeGather(); }
 
  protected:
@@ -203,6 +216,7 @@ class BlockwiseMultiOrderFeatureRegression : public RenderPass {
   bool mBMFR_postprocess = true;
   bool mBMFR_regression = false;
   bool mBMFR_removeFeatures = true;
+  bool mMotion = false;
   uint32_t mAccumCount = 0;
   // tiled: this rank's packed rows of the four channels, all ranks' (after the all-gather), and the whole-frame copies
   uint8_t *mPackedMine = nullptr, *mPackedAll = nullptr;
@@ -287,6 +301,7 @@ class RenderingPipeline {
   RayLaunch::SharedPtr mpRays;             // kept to switch the launcher's slot
   bool inFlightActive();
   std::vector<hipStream_t> updateStreams(uint32_t& first);
+  void keepPose();
   bool mSceneMoved = false;    // the next frame delivers the refresh notification
   bool mSceneUpdated = false;  // since initialize(): no checkpoint
   uint32_t mTileRank = 0, mTileWorld = 0;  // world 0: not tiled

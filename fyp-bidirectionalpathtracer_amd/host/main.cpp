@@ -41,6 +41,7 @@ struct Options {
   bool denoise = false, denoiseRegression = false;
   bool areaLights = false;  // BDPT_PARAM_AREA_LIGHTS: emissive triangles light the scene (NEE and light subpaths)
   float sway = 0.0f;  // > 0: an animated scene — before every frame the vertices move by up to this fraction of the scene's extent
+  bool noMotion = false;  // --sway / --bend with --denoise: keep the denoiser's static-scene reprojection (for comparison)
   float bend = 0.0f;  // > 0: a skinned scene — a small rig along the scene's height, bent by up to this angle (radians) before every frame
 };
 
@@ -116,7 +117,12 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
     pipeline->setPass(1, bdpt);
   }
   pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
-  pipeline->setPass(3, BlockwiseMultiOrderFeatureRegression::create());
+  {
+    BlockwiseMultiOrderFeatureRegression::SharedPtr bmfr = BlockwiseMultiOrderFeatureRegression::create();
+    // an animated scene under the denoiser: reproject through the previous pose (whole-frame pipelines)
+    bmfr->setMotion(o.denoise && (o.sway > 0.0f || o.bend > 0.0f) && !o.noMotion && !tiled);
+    pipeline->setPass(3, bmfr);
+  }
   // the window parameters of Main.cpp:20-25 size the channels (there is no window)
   SampleConfig config;
   config.windowDesc.resizableWindow = true;
@@ -292,6 +298,7 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
                 o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
     if (tiled) std::printf(", %u GPU%s (interleaved stripes of %u rows, RCCL reduce-scatter + all-gather)", world, world == 1 ? "" : "s",
                            bdpt_stripe_rows(o.H, world));
+    if (o.denoise && (o.sway > 0.0f || o.bend > 0.0f) && !o.noMotion && !tiled) std::printf(", denoiser history reprojected through the previous pose");
     std::printf("\n");
     writePfm(o.out.c_str(), img, o.W, o.H);
   }
@@ -338,6 +345,7 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--warmup")) o.warmup = std::atoi(v);  // of --frames: rendered before the clock starts (first-use allocations)
     else if (const char* v = next("--sway")) o.sway = (float)std::atof(v);
     else if (const char* v = next("--bend")) o.bend = (float)std::atof(v);
+    else if (std::strcmp(argv[i], "--no-motion") == 0) o.noMotion = true;
     else if (const char* v = next("--gpus")) o.gpus = std::atoi(v);
     else if (const char* v = next("--rank")) o.rank = std::atoi(v);
     else if (const char* v = next("--world")) o.world = std::atoi(v);
@@ -346,7 +354,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }

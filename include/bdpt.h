@@ -462,7 +462,8 @@ int bdpt_get_refit_info(bdpt_ctx* ctx, bdpt_refit_info* out); /* synchronises */
  *   b'[c]   = (b.x*B[c] + b.y*B[4+c]) + b.z*B[8+c]
  * A vertex whose four weights are all zero (either sign) is static: its outputs are its rest values bit for bit, and its
  * ids are neither checked nor read (the flattened static part of a scene).  Weights are not renormalised.  The previous
- * frame's positions (gSkinnedPrevPositions, for motion vectors) are out of scope: nothing here keeps them.
+ * frame's positions (gSkinnedPrevPositions, for motion vectors) are kept by bdpt_keep_pose ("Motion", after the surface queries), for every
+ * kind of update, not by the skinning kernel.
  *
  * bdpt_set_skin synchronises and allocates everything a skinned update needs (rest streams, weights, ids, the skinned
  * streams, the device palette, and the refit plan as bdpt_prepare(BDPT_PREPARE_REFIT) does); not inside a stream capture
@@ -637,6 +638,53 @@ typedef struct bdpt_bsdf_desc {
   float* values;                /* EVAL: device, 16-byte aligned, four floats per item */
 } bdpt_bsdf_desc;
 int bdpt_bsdf_query(bdpt_ctx* ctx, const bdpt_bsdf_desc* desc, void* stream);
+
+/* ---- Motion: where a surface point was in the previous frame ----
+ * bdpt_keep_pose                 gSkinnedPrevPositions of SkinningCache (ComputeSkinning.cs.slang): the pose before this
+ *                                frame's updates, kept on the device — here for bdpt_update_geometry and
+ *                                bdpt_update_skinned alike, per triangle corner.
+ * bdpt_gbuffer_execute_motion    bdpt_gbuffer_execute plus one RGBA32F channel: the hit point's position in that pose.
+ * bdpt_motion_query              the same for a caller's bdpt_hit records.
+ * bdpt_bmfr_execute_motion       bdpt_bmfr_execute reprojecting through that channel ("BMFR denoiser" below).
+ * The reference has no counterpart past the first: its BMFR reprojects the current position, so a moving surface
+ * restarts at 1 spp every frame.  Every existing call keeps its bits; all of this is behind these entry points.
+ *
+ * bdpt_prepare(BDPT_PREPARE_MOTION) (needs a scene, not a size; allocates and synchronises, so not inside a stream capture:
+ * BDPT_E_STATE) allocates the previous pose — three float4 per primitive, the corners p0, p1, p2 in primitive order, 48 B
+ * per primitive — and fills it from the current shading records: previous == current.  bdpt_set_scene drops it.
+ *
+ * bdpt_keep_pose copies the current corner positions into the previous pose: one streaming kernel, enqueued on `stream`
+ * behind the context's previous call (the event rule of bdpt_update_geometry); no allocation, no synchronise, one kernel
+ * node in a captured graph; it always runs (a replayed graph replays it).  A caller calls it once per frame BEFORE that
+ * frame's updates — also in a frame without an update: that is how an object that stops gets zero motion.  Updates
+ * themselves do not touch the previous pose: two updates without a bdpt_keep_pose between them leave it alone.
+ *
+ * The previous position of a hit (prim, u, v) with the previous-pose corners p0, p1, p2, per component, fp32, no
+ * contraction, exactly in this order (the arithmetic of the G-buffer's WorldPosition on the current corners, so an
+ * unmoved scene gives WorldPosition's bits):
+ *   b0 = 1 - u - v          prev = ((0 + p0*b0) + p1*u) + p2*v
+ *
+ * bdpt_gbuffer_execute_motion: bdpt_gbuffer_execute, and prevPosition (device, 16-byte aligned, width x height float4
+ * texels in frame order) written for the context's tile pixels: (prev.xyz, 1) at a hit, (0, 0, 0, 0) at a miss, as
+ * WorldPosition.  The six channels and the occluder hints get the bits bdpt_gbuffer_execute gives.
+ *
+ * bdpt_motion_query: prevPositions[i] = (prev.xyz, 1) for hits[i]; a prim < 0 or one that is not a triangle of the scene
+ * writes zeros; with numDevice set, items at or beyond min(*numDevice, num) are neither read nor written.  Ordering,
+ * capture and counters as the surface queries: stream-ordered behind the context's previous call, no allocation, no
+ * synchronise, bdpt_get_counters and bdpt_get_stage_times left alone; num == 0 returns BDPT_OK and does nothing.
+ *
+ * Errors (nothing is enqueued): no scene, or no bdpt_prepare(BDPT_PREPARE_MOTION) since the last bdpt_set_scene,
+ * BDPT_E_STATE (bdpt_gbuffer_execute_motion also without camera or size); a NULL context, params, channels or desc, a
+ * missing or misaligned buffer, a non-zero reserved BDPT_E_INVALID. */
+int bdpt_keep_pose(bdpt_ctx* ctx, void* stream);
+typedef struct bdpt_motion_desc {
+  const bdpt_hit* hits;      /* device, 16-byte aligned, num records (e.g. bdpt_trace_rays' output) */
+  uint32_t num;              /* items; the capacity when numDevice is set */
+  uint32_t reserved;         /* 0 */
+  const uint32_t* numDevice; /* optional device word: min(*numDevice, num) items */
+  float* prevPositions;      /* device, 16-byte aligned, one float4 per item */
+} bdpt_motion_desc;
+int bdpt_motion_query(bdpt_ctx* ctx, const bdpt_motion_desc* desc, void* stream);
 
 /* ---- Light queries: the pass's light sampling, for a caller's own integrator ----
  * bdpt_light_query closes the forward half of the query family ("Connection queries" below has the two bidirectional
@@ -925,10 +973,13 @@ int bdpt_tile_row_ranges(const bdpt_ctx* ctx, uint32_t* out_first_last, uint32_t
 #define BDPT_PREPARE_LIGHT_GROUPS 8u /* the per-light splat planes of bdpt_execute_light_groups (needs a scene and a size) */
 #define BDPT_PREPARE_AREA_LIGHTS 16u /* the emitter table of BDPT_PARAM_AREA_LIGHTS (needs a scene, not a size) */
 #define BDPT_PREPARE_LIGHT_GROUP_TABLE 32u /* numLights + 1 splat planes: the most an assignment of bdpt_execute_grouped needs */
+#define BDPT_PREPARE_MOTION 64u /* the previous pose of bdpt_keep_pose, filled from the current one (needs a scene, not a size) */
 int bdpt_prepare(bdpt_ctx* ctx, uint32_t what);
 
 /* Primary-visibility pass.  Writes the tile rows of all six channels. */
 int bdpt_gbuffer_execute(bdpt_ctx* ctx, const bdpt_gbuffer_params* p, const bdpt_gbuffer* out, void* stream);
+/* The same plus the PrevWorldPosition channel ("Motion" above). */
+int bdpt_gbuffer_execute_motion(bdpt_ctx* ctx, const bdpt_gbuffer_params* p, const bdpt_gbuffer* out, float* prevPosition, void* stream);
 
 /* The BDPT pass.  `out` is the full-frame RGBA32F "PipelineOutput" channel;
  * only the tile rows are written (cleared to 0 first, as getClearedTexture does,
@@ -1120,6 +1171,17 @@ typedef struct bdpt_bmfr_params {
  * bdpt_tile_unpack; host/Passes.cpp BlockwiseMultiOrderFeatureRegression::execute) and every rank filters the same
  * whole frame. */
 int bdpt_bmfr_execute(bdpt_ctx* ctx, const bdpt_bmfr_params* p, const bdpt_gbuffer* features, float* noisy, void* stream);
+
+/* bdpt_bmfr_execute for scenes whose geometry moves.  prevPosition (device, 16-byte aligned, whole-frame float4 texels:
+ * bdpt_gbuffer_execute_motion's channel; NULL: BDPT_E_INVALID) says where each pixel's surface point was in the previous
+ * frame.  With q = prevPosition[i] and cp = features->worldPosition[i], the preprocess stage projects q (not cp) with
+ * prevViewProj and accepts a history tap when |tap position - q|^2 < 0.01 (not cp).  Everything else is
+ * bdpt_bmfr_execute's: the normal test against the current normal, the weights, the blend, the accept masks, the history
+ * write (which stores the CURRENT position cp), regression and postprocess (which read `features`), history allocation,
+ * whole-frame buffers, the history blob.  With prevPosition equal to worldPosition the call is bdpt_bmfr_execute bit for
+ * bit.  Rotating surfaces still fail the normal test: normals are not reprojected. */
+int bdpt_bmfr_execute_motion(bdpt_ctx* ctx, const bdpt_bmfr_params* p, const bdpt_gbuffer* features, const float* prevPosition,
+                             float* noisy, void* stream);
 
 /* Forget the history (BlockwiseMultiOrderFeatureRegression::resize / initScene set mAccumCount = 0). */
 int bdpt_bmfr_reset(bdpt_ctx* ctx);
