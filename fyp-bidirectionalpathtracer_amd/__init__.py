@@ -323,71 +323,24 @@ class Context:
 
         numpy arrays and CPU tensors are copied to the device, traced, synchronised and returned as numpy arrays; no host
         address ever reaches the library.  Anything else is refused before the library is called."""
+        import numpy as np
+        import torch
         if mode not in _TRACE_MODES:
             raise BdptError(f"trace_rays: mode must be one of {sorted(_TRACE_MODES)}, not {mode!r}")
-        if getattr(rays, "is_cuda", False):
-            return self._trace_rays_device(rays, _TRACE_MODES[mode], out, count, stream)
-        if out is not None or count is not None:
-            raise BdptError("trace_rays: out= and count= go with GPU tensor rays")
-        if hasattr(rays, "is_cuda") and getattr(rays, "device", None) is not None and rays.device.type != "cpu":
-            raise BdptError(f"trace_rays: rays on {rays.device}: neither a GPU tensor nor host memory")
-        import numpy as np
-        host = rays.detach().numpy() if hasattr(rays, "detach") else rays
-        if not isinstance(host, np.ndarray) or host.dtype != np.float32 or host.ndim != 2 or host.shape[1] != 8:
-            raise BdptError("trace_rays: rays must be an (N, 8) float32 array")
-        import torch
-        if not torch.cuda.is_available():
-            raise BdptError("trace_rays: no GPU visible to torch (the queries have no CPU fallback)")
-        dev = torch.device("cuda", self.device)
-        with torch.cuda.device(dev):
-            d = _host_to_device(np.ascontiguousarray(host), dev)
-            torch.cuda.synchronize(dev)  # the copy is done before the library's stream reads it
-            res = self._trace_rays_device(d, _TRACE_MODES[mode], None, None, stream)
-            torch.cuda.synchronize(dev)
-        if isinstance(res, tuple):
-            return tuple(r.cpu().numpy() for r in res)
-        return res.cpu().numpy()
+        closest = _TRACE_MODES[mode] != abi.TRACE_ANY
 
-    def _trace_rays_device(self, rays, mode, out, count, stream):
-        import torch
+        def run(ptrs, n, cnt, res):
+            d = abi.TraceDesc()
+            d.rays, d.numRays, d.mode, d.numRaysDevice = ptrs[0], n, _TRACE_MODES[mode], cnt
+            d.hits, d.visible = (res, None) if closest else (None, res)
+            return self._lib.bdpt_trace_rays(self._h, C.byref(d), stream)
 
-        def on_device(t, what):
-            if not getattr(t, "is_cuda", False) or t.device.index != self.device:
-                raise BdptError(f"trace_rays: {what} must be a GPU tensor on cuda:{self.device}, not on {getattr(t, 'device', type(t))}")
-            if not t.is_contiguous():
-                raise BdptError(f"trace_rays: {what} must be contiguous")
-
-        on_device(rays, "rays")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-            raise BdptError(f"trace_rays: rays must be (N, 8) float32, not {tuple(rays.shape)} {rays.dtype}")
-        n = int(rays.shape[0])
-        if n >= 2**32:
-            raise BdptError("trace_rays: more than 2^32 - 1 rays")
-        if count is not None:
-            on_device(count, "count")
-            if count.dtype not in (torch.int32, torch.uint32) or count.numel() != 1:
-                raise BdptError("trace_rays: count must be a 1-element int32 or uint32 tensor")
-        closest = mode != abi.TRACE_ANY
-        if out is None:
-            out = torch.empty((n, 4) if closest else (n,), dtype=torch.float32 if closest else torch.uint8, device=rays.device)
-        else:
-            on_device(out, "out")
-            if closest and (out.dtype not in (torch.float32, torch.int32) or tuple(out.shape) != (n, 4)):
-                raise BdptError(f"trace_rays: out must be ({n}, 4) float32 or int32 for a closest-hit mode")
-            if not closest and (out.dtype != torch.uint8 or tuple(out.shape) != (n,)):
-                raise BdptError(f"trace_rays: out must be ({n},) uint8 for mode 'any'")
-        d = abi.TraceDesc()
-        d.rays, d.numRays, d.mode = rays.data_ptr(), n, mode
-        d.numRaysDevice = None if count is None else count.data_ptr()
-        if closest:
-            d.hits = out.data_ptr()
-        else:
-            d.visible = out.data_ptr()
-        self._check(self._lib.bdpt_trace_rays(self._h, C.byref(d), stream), "bdpt_trace_rays")
+        res = self._surface_query("trace_rays", [("rays", rays, 8, (torch.float32,))],
+                                  (4, (torch.float32, torch.int32)) if closest else (None, (torch.uint8,)), run, out, count,
+                                  any_count_shape=True)
         if not closest:
-            return out
-        hits = out if out.dtype == torch.float32 else out.view(torch.float32)
-        return hits[:, :3], hits.view(torch.int32)[:, 3]
+            return res
+        return res[:, :3], res.view(np.int32 if isinstance(res, np.ndarray) else torch.int32)[:, 3]
 
     # ---- surface queries (include/bdpt.h "Surface queries", DESIGN.md) ----
     def camera_rays(self, gparams, width, height, out=None, stream=None):
@@ -676,11 +629,12 @@ class Context:
             raise BdptError(f"{what}: {name} must be {tuple(shape)} {'/'.join(str(d) for d in dtypes)}, not "
                             f"{tuple(t.shape)} {t.dtype}")
 
-    def _surface_query(self, what, inputs, out_spec, run, out, count, extras=(), fn=None):
+    def _surface_query(self, what, inputs, out_spec, run, out, count, extras=(), fn=None, any_count_shape=False):
         """The shared path of the per-item queries.  inputs: (name, value, columns or None for 1-D, allowed torch dtypes),
-        all with one row per item; out_spec: (columns, allowed dtypes; the first is allocated).  extras: further outputs of
-        the same form that may be None and go with GPU tensor inputs only (a column count of 1 with a 1-D name "... count":
-        a one-element tensor); fn: the library call's name for error messages."""
+        all with one row per item; out_spec: (columns or None for 1-D, allowed dtypes; the first is allocated).  extras:
+        further outputs of the same form that may be None and go with GPU tensor inputs only (a column count of 1 with a 1-D
+        name "... count": a one-element tensor); fn: the library call's name for error messages; any_count_shape: `count`
+        may be a one-element tensor of any shape (trace_rays), not only (1,)."""
         import numpy as np
         import torch
         on_gpu = [getattr(v, "is_cuda", False) for _, v, _, _ in inputs]
@@ -691,17 +645,19 @@ class Context:
             for name, v, cols, dts in inputs:
                 self._check_gpu(v, what, name, (n,) if cols is None else (n, cols), dts)
             if count is not None:
-                self._check_gpu(count, what, "count", (1,), (torch.int32, torch.uint32))
+                one = any_count_shape and getattr(count, "is_cuda", False) and count.numel() == 1
+                self._check_gpu(count, what, "count", tuple(count.shape) if one else (1,), (torch.int32, torch.uint32))
             for name, v, cols, dts in extras:
                 if v is not None:
                     self._check_gpu(v, what, name, (1,) if name.endswith("count") else (n,) if cols is None else (n, cols), dts)
+            out_shape = (n,) if out_spec[0] is None else (n, out_spec[0])
             if out is None:
-                out = torch.empty((n, out_spec[0]), dtype=out_spec[1][0], device=inputs[0][1].device)
+                out = torch.empty(out_shape, dtype=out_spec[1][0], device=inputs[0][1].device)
             else:
-                self._check_gpu(out, what, "out", (n, out_spec[0]), out_spec[1])
+                self._check_gpu(out, what, "out", out_shape, out_spec[1])
             self._check(run([v.data_ptr() for _, v, _, _ in inputs], n, None if count is None else count.data_ptr(), out.data_ptr()),
                         fn or "bdpt_" + ("bsdf_query" if "bsdf" in what else what))
-            return out if out.dtype == torch.float32 else out.view(torch.float32)
+            return out.view(torch.float32) if out.dtype == torch.int32 else out
         if any(on_gpu):
             raise BdptError(f"{what}: the inputs must all be GPU tensors or all host arrays")
         if out is not None or count is not None or any(v is not None for _, v, _, _ in extras):

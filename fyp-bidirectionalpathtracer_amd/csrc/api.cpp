@@ -1,5 +1,5 @@
-// api.cpp — the C ABI of include/bdpt.h: context, scene upload + BVH build, per-tile path
-// buffers, stage launches.  Workspaces are sized by bdpt_set_scene / bdpt_resize / bdpt_prepare, so
+// api.cpp — the C ABI of include/bdpt.h but its per-item queries (api_query.cpp): context, scene upload + BVH build,
+// per-tile path buffers, stage launches.  Workspaces are sized by bdpt_set_scene / bdpt_resize / bdpt_prepare, so
 // bdpt_gbuffer_execute, bdpt_execute and bdpt_bmfr_execute neither allocate nor synchronise and can be
 // captured into a hipGraph.  The one exception is spelled out in bdpt.h: bdpt_execute(in = NULL) and
 // bdpt_bmfr_execute allocate their optional buffers on first use when bdpt_prepare was not called, and
@@ -21,19 +21,15 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/bdpt.h"
 #include <new>
 
-#include "bvh.h"
-#include "kernels.h"
-#include "refit.h"
-#include "skin.h"
+#include "context.hpp"
+#include "launch.hpp"
 #include "scene_bvh.h"
 
 using namespace bdpt;
 
 namespace {
-constexpr int kMaxStages = 64;
 // path-queue counters, their fetch cursors, then the shadow sub-queue counters and cursors
 // (every cursor is sharded: kNumSubQueues words, each on its own 128-byte line — atomics to one line serialise)
 constexpr size_t kCountBlocks = 1;  // lengths of the valid-pixel lists
@@ -47,113 +43,6 @@ constexpr size_t kEyeCountBlock = kLazyBlocks - 1;
 static_assert(kEyeCountBlock > (size_t)kMaxLazyRounds, "the eye list's cursor block must be one no lazy round uses");
 constexpr size_t kCursorWords = (kCountBlocks + kHeadBlocks + kLazyBlocks) * kCursorBlock + 4 * kRayCursorBlock;  // + ray count / head blocks of two classes
 }
-
-struct bdpt_ctx {
-  int device = 0;
-  int numCUs = 256;
-  std::string err;
-  // scene
-  bool haveScene = false, haveCamera = false, haveSize = false;
-  SceneDev S{};
-  std::vector<void*> sceneAllocs;
-  bdpt_bvh_info bvhInfo{};
-  bdpt_camera cam{};
-  bdpt_environment env{};  // bdpt_set_environment: what BDPT_PARAM_ENV_ON_MISS looks up (none: black)
-  // frame
-  uint32_t W = 0, H = 0, maxDepth = 0;
-  // the tile: which frame rows this context renders (a contiguous band, or the stripes of one owner) and where
-  // splat accumulators live (SplatLayout); rows in ascending order
-  std::vector<std::pair<uint32_t, uint32_t>> rowRanges;  // [first, last) runs of rows
-  uint32_t tileRows = 0;
-  SplatLayout sl{1, 1, 0};
-  bdpt_stripes stripes{0, 1, 0};  // stripeRows == 0: contiguous band (bdpt_resize)
-  PathBuf P{};
-  std::vector<void*> frameAllocs;
-  unsigned long long* splat = nullptr;     // buffer in use (own or caller-provided)
-  unsigned long long* ownSplat = nullptr;
-  DevCounters* counters = nullptr;
-  hipStream_t lastStream = nullptr;
-  // stage timing
-  bool timing = false;
-  hipEvent_t ev[kMaxStages + 1]{};
-  const char* stageNames[kMaxStages]{};
-  int numStages = 0;
-  bool evCreated = false;
-  // kernels on the context's second stream (the splat and connection generators): their own event pairs, so that a
-  // kernel's time is the kernel's and the caller's stream shows the WAIT for it as a stage of its own
-  static constexpr int kMaxSideStages = 4;
-  hipEvent_t sideEv[2 * kMaxSideStages]{};
-  const char* sideNames[kMaxSideStages]{};
-  int numSideStages = 0;
-  int lazyRounds = 3;
-  LaunchGrids grids{};  // persistent-grid sizes for this context's device
-  int* stackOvf = nullptr;      // overflow rows of the persistent kernels' traversal stacks (kernels.h kStackLds)
-  uint32_t stackOvfStride = 0;  // lanes per row: every wave a persistent grid can hold
-  unsigned long long* rayCursor = nullptr;  // fetch cursor and done count of bdpt_trace_rays (each launch leaves them zero)
-  unsigned long long* adaptiveSum = nullptr;  // active-pixel sum and done count of bdpt_adaptive_update (each launch leaves them zero)
-  // channels of the built-in primary stage (bdpt_execute with in == NULL): bdpt_prepare or first use
-  bdpt_gbuffer ownGb{};
-  // BMFR history (bdpt_prepare or the first bdpt_bmfr_execute): [2] = ping-pong pair
-  float4* bmfrPos[2] = {nullptr, nullptr};
-  float4* bmfrNorm[2] = {nullptr, nullptr};
-  float4* bmfrNoisy[2] = {nullptr, nullptr};
-  float4* bmfrFiltered[2] = {nullptr, nullptr};
-  uint8_t* bmfrAccept = nullptr;
-  uint32_t* bmfrPrevPixel = nullptr;
-  int bmfrRead = 0;  // which half holds the previous frame
-  // the splat and NEE generators run beside the connection generator on this stream (fork/join with events; capture-safe)
-  hipStream_t walkStream = nullptr;
-  hipEvent_t evFork = nullptr, evJoin = nullptr, evSplat = nullptr;
-  // occluder hints (kernels.hip "Occluder hints"): the primary-visibility triangle of every frame pixel, written by this
-  // context's G-buffer pass and read by its light-tracing generator.  BDPT_NO_HINTS (environment) switches both kinds off.
-  uint32_t* hintPix = nullptr;
-  bool hints = true;
-  // a context that renders only part of the frame fills the hints of ALL frame pixels when its camera changes (its
-  // light-tracing rays aim anywhere); its own rows are refreshed by every G-buffer pass
-  bdpt_camera hintCam{};
-  bool hintCamValid = false;
-  // refit (bdpt_update_geometry / bdpt_set_lights): the plan and its scratch are made on first use or by
-  // bdpt_prepare(BDPT_PREPARE_REFIT) and live in sceneAllocs (a new scene drops them)
-  uint32_t numVertices = 0, numTriangles = 0;
-  uint32_t* lightMaps = nullptr;  // = S.lightMap (writable)
-  bool refitReady = false;
-  BvhRefitPlan refitPlan;  // (host copy: the SAH of bdpt_get_refit_info walks it)
-  RefitDev refit{};
-  uint32_t numUpdates = 0;
-  float* stage[3] = {nullptr, nullptr, nullptr};  // device copies of host-pointer inputs: positions, normals, bitangents
-  // host-pointer inputs go through pinned memory (copied before the call returns); evStage marks the end of the copy
-  // that last read it
-  void* pinned = nullptr;
-  size_t pinnedBytes = 0;
-  hipEvent_t evStage = nullptr, evOrder = nullptr;
-  bool stageInFlight = false;
-  // light groups (bdpt_execute_light_groups, bdpt_execute_grouped): the splat-value planes (groupSplatPlanes of them) and
-  // each pixel's light, made by bdpt_prepare(BDPT_PREPARE_LIGHT_GROUPS / _LIGHT_GROUP_TABLE) or by the first call that
-  // needs more planes than there are; they depend on the scene's light count and the frame size, so bdpt_set_scene and
-  // bdpt_resize drop them
-  unsigned long long* groupSplat = nullptr;
-  uint32_t groupSplatPlanes = 0;
-  uint8_t* groupLightIdx = nullptr;
-  // area lights (BDPT_PARAM_AREA_LIGHTS): the emitter table, made by bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) or the first
-  // frame with the switch, in sceneAllocs (a new scene drops it); refreshed on the device by every bdpt_update_geometry.
-  // alphaTris: the non-opaque triangles in ascending order (their alpha-test records' order), kept for the table build.
-  const uint32_t* alphaTris = nullptr;
-  uint32_t numAlphaTris = 0;
-  bool areaReady = false;
-  AreaDev area{};
-  uint32_t areaTextured = 0;
-  float* areaBlockSum = nullptr;     // one float and one word per 64 emitters: the refresh's scratch
-  uint32_t* areaBlockLast = nullptr;
-  // skinning (bdpt_set_skin): the rest streams, weights, ids, the skinned streams and the device palettes, in skinAllocs
-  // (bdpt_set_skin and bdpt_set_scene drop them).  skinPalette: where host-pointer palettes are staged (bones, normalBones).
-  std::vector<void*> skinAllocs;
-  bool haveSkin = false;
-  SkinDev skin{};
-  float* skinPalette[2] = {nullptr, nullptr};
-  // motion (bdpt_prepare(BDPT_PREPARE_MOTION)): the previous pose, three float4 per primitive, in sceneAllocs (a new scene
-  // drops it); bdpt_keep_pose copies the current corners into it
-  float4* prevPose = nullptr;
-};
 
 namespace {
 
@@ -181,19 +70,6 @@ std::vector<uint32_t> alphaQuadPlane(const bdpt_texture& t) {
   hostParallelFor(t.height, [&](size_t y0, size_t y1) { alphaQuadRows(t.rgba8, t.width, t.height, (uint32_t)y0, (uint32_t)y1, q.data()); });
   return q;
 }
-
-bool fail(bdpt_ctx* c, const std::string& m) {
-  if (c) c->err = m;
-  return false;
-}
-#define HIPCHK(ctx, expr)                                                                       \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) {                                                                     \
-      fail(ctx, std::string(#expr) + ": " + hipGetErrorString(e_));                             \
-      return BDPT_E_HIP;                                                                        \
-    }                                                                                           \
-  } while (0)
 
 template <class T>
 int devAlloc(bdpt_ctx* c, std::vector<void*>& pool, T** out, size_t count) {
@@ -235,10 +111,6 @@ void freeLightGroups(bdpt_ctx* c) {
   c->groupSplatPlanes = 0;
   c->groupLightIdx = nullptr;
 }
-
-// Every entry point that launches or allocates starts here: the context's device becomes current, so one
-// host thread can hold contexts on several GPUs.
-#define ENTER(ctx) HIPCHK(ctx, hipSetDevice((ctx)->device))
 
 bool streamIsCapturing(hipStream_t st) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -317,7 +189,110 @@ void sideEnd(bdpt_ctx* c, hipStream_t side) {
   c->numSideStages++;
 }
 
+// refit (refit.hip, bvh.h "refit"): the plan (a top-down pass over the records, read back once) and the refit's scratch;
+// not while capturing
+int ensureRefit(bdpt_ctx* c, hipStream_t st) {
+  if (c->refitReady) return BDPT_OK;
+  if (streamIsCapturing(st)) {
+    fail(c, "update: the first update needs bdpt_prepare(BDPT_PREPARE_REFIT) before stream capture");
+    return BDPT_E_STATE;
+  }
+  HIPCHK(c, hipDeviceSynchronize());
+  BvhRefitPlan plan;
+  {
+    std::vector<BvhRec> recs(c->S.numRecs);
+    HIPCHK(c, hipMemcpy(recs.data(), c->S.recs, recs.size() * sizeof(BvhRec), hipMemcpyDeviceToHost));
+    std::string err;
+    if (!bvhRefitMakePlan(recs.data(), recs.size(), plan, err)) {
+      fail(c, err);
+      return BDPT_E_HIP;
+    }
+  }
+  const size_t nn = std::max<size_t>(plan.nodes.size(), 1);
+  RefitDev R{};
+  const BvhRefitNode* dNodes = nullptr;
+  const uint32_t* dOrder = nullptr;
+  int rc;
+  if ((rc = devUpload(c, c->sceneAllocs, &dNodes, plan.nodes.data(), plan.nodes.size())) ||
+      (rc = devUpload(c, c->sceneAllocs, &dOrder, plan.levelOrder.data(), plan.levelOrder.size())) ||
+      (rc = devAlloc(c, c->sceneAllocs, &R.box, nn * 6)) || (rc = devAlloc(c, c->sceneAllocs, &R.childArea, nn * 4)) ||
+      (rc = devAlloc(c, c->sceneAllocs, &R.partial, (size_t)kRefitPartials * 6)) || (rc = devAlloc(c, c->sceneAllocs, &R.pad, 1)))
+    return rc;
+  R.nodes = dNodes;
+  R.levelOrder = dOrder;
+  R.levelStart = plan.levelStart;
+  R.numNodes = (uint32_t)plan.nodes.size();
+  c->refit = std::move(R);
+  c->refitPlan = std::move(plan);
+  c->refitReady = true;
+  return BDPT_OK;
+}
+
 }  // namespace
+
+// (declared in context.hpp)
+int bdpt::orderAfterLast(bdpt_ctx* c, hipStream_t st) {
+  if (c->lastStream != st) {
+    HIPCHK(c, hipEventRecord(c->evOrder, c->lastStream));
+    HIPCHK(c, hipStreamWaitEvent(st, c->evOrder, 0));
+  }
+  return BDPT_OK;
+}
+
+// (declared in context.hpp)  Triangles the build dropped (alpha clipping) are found through the
+// refit plan's leaves, which is made for that when the scene has any.
+int bdpt::ensureAreaLights(bdpt_ctx* c, hipStream_t st) {
+  if (c->areaReady) return BDPT_OK;
+  if (streamIsCapturing(st)) {
+    fail(c, "area lights: the emitter table needs bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) before stream capture");
+    return BDPT_E_STATE;
+  }
+  HIPCHK(c, hipDeviceSynchronize());
+  const uint32_t nt = c->numTriangles;
+  const size_t nb = wavesFor(nt);
+  std::vector<void*> scratch;
+  struct Free {
+    std::vector<void*>& p;
+    ~Free() { freePool(p); }
+  } freeScratch{scratch};
+  uint8_t* referenced = nullptr;
+  int rc;
+  if (c->bvhInfo.numDropped) {
+    if ((rc = ensureRefit(c, st))) return rc;
+    if ((rc = devAlloc(c, scratch, &referenced, nt))) return rc;
+    HIPCHK(c, hipMemset(referenced, 0, nt));
+    launchAreaMarkReferenced(c->refit.nodes, c->refit.numNodes, c->S.recs, referenced, nullptr);
+  }
+  uint32_t *blockCount = nullptr, *blockBase = nullptr, *counts = nullptr;
+  if ((rc = devAlloc(c, scratch, &blockCount, nb)) || (rc = devAlloc(c, scratch, &blockBase, nb)) || (rc = devAlloc(c, scratch, &counts, 2)))
+    return rc;
+  HIPCHK(c, hipMemset(counts, 0, 2 * sizeof(uint32_t)));
+  launchAreaCount(c->S, nt, referenced, blockCount, blockBase, counts, nullptr);
+  uint32_t hc[2] = {0, 0};
+  HIPCHK(c, hipMemcpy(hc, counts, sizeof(hc), hipMemcpyDeviceToHost));
+  AreaDev A{};
+  A.n = hc[0];
+  if (A.n) {
+    const size_t nbe = wavesFor(A.n);
+    float *cdf = nullptr, *total = nullptr;
+    float4* emit = nullptr;
+    if ((rc = devAlloc(c, c->sceneAllocs, &cdf, A.n)) || (rc = devAlloc(c, c->sceneAllocs, &emit, A.n)) ||
+        (rc = devAlloc(c, c->sceneAllocs, &total, 2)) || (rc = devAlloc(c, c->sceneAllocs, &c->areaBlockSum, nbe)) ||
+        (rc = devAlloc(c, c->sceneAllocs, &c->areaBlockLast, nbe)))
+      return rc;
+    A.cdf = cdf;
+    A.emit = emit;
+    A.total = total;
+    launchAreaCompact(c->S, nt, referenced, blockBase, c->alphaTris, c->numAlphaTris, emit, nullptr);
+    launchAreaRefresh(c->S, A, c->areaBlockSum, c->areaBlockLast, nullptr);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipDeviceSynchronize());
+  c->area = A;
+  c->areaTextured = hc[1];
+  c->areaReady = true;
+  return BDPT_OK;
+}
 
 extern "C" {
 
@@ -770,51 +745,6 @@ int bdpt_set_environment(bdpt_ctx* c, const bdpt_environment* env) {
 
 // ---- animated scenes: refit in place (refit.hip, bvh.h "refit") ----
 namespace {
-// the plan (a top-down pass over the records, read back once) and the refit's scratch; not while capturing
-int ensureRefit(bdpt_ctx* c, hipStream_t st) {
-  if (c->refitReady) return BDPT_OK;
-  if (streamIsCapturing(st)) {
-    fail(c, "update: the first update needs bdpt_prepare(BDPT_PREPARE_REFIT) before stream capture");
-    return BDPT_E_STATE;
-  }
-  HIPCHK(c, hipDeviceSynchronize());
-  BvhRefitPlan plan;
-  {
-    std::vector<BvhRec> recs(c->S.numRecs);
-    HIPCHK(c, hipMemcpy(recs.data(), c->S.recs, recs.size() * sizeof(BvhRec), hipMemcpyDeviceToHost));
-    std::string err;
-    if (!bvhRefitMakePlan(recs.data(), recs.size(), plan, err)) {
-      fail(c, err);
-      return BDPT_E_HIP;
-    }
-  }
-  const size_t nn = std::max<size_t>(plan.nodes.size(), 1);
-  RefitDev R{};
-  const BvhRefitNode* dNodes = nullptr;
-  const uint32_t* dOrder = nullptr;
-  int rc;
-  if ((rc = devUpload(c, c->sceneAllocs, &dNodes, plan.nodes.data(), plan.nodes.size())) ||
-      (rc = devUpload(c, c->sceneAllocs, &dOrder, plan.levelOrder.data(), plan.levelOrder.size())) ||
-      (rc = devAlloc(c, c->sceneAllocs, &R.box, nn * 6)) || (rc = devAlloc(c, c->sceneAllocs, &R.childArea, nn * 4)) ||
-      (rc = devAlloc(c, c->sceneAllocs, &R.partial, (size_t)kRefitPartials * 6)) || (rc = devAlloc(c, c->sceneAllocs, &R.pad, 1)))
-    return rc;
-  R.nodes = dNodes;
-  R.levelOrder = dOrder;
-  R.levelStart = plan.levelStart;
-  R.numNodes = (uint32_t)plan.nodes.size();
-  c->refit = std::move(R);
-  c->refitPlan = std::move(plan);
-  c->refitReady = true;
-  return BDPT_OK;
-}
-// the update is ordered after everything this context enqueued before (its last stream joins its side stream)
-int orderAfterLast(bdpt_ctx* c, hipStream_t st) {
-  if (c->lastStream != st) {
-    HIPCHK(c, hipEventRecord(c->evOrder, c->lastStream));
-    HIPCHK(c, hipStreamWaitEvent(st, c->evOrder, 0));
-  }
-  return BDPT_OK;
-}
 // host arrays -> pinned memory (now) -> device copies (on st); arrays[k] may be null
 int stageHostArrays(bdpt_ctx* c, const void* const* arrays, const size_t* bytes, int n, float** dst, hipStream_t st) {
   size_t total = 0;
@@ -847,60 +777,6 @@ void retraceLightMaps(bdpt_ctx* c, hipStream_t st) {
   if (c->hints && c->lightMaps) launchLightMaps(c->S, c->lightMaps, c->S.lightMapRes, st);
 }
 
-// The emitter table of area lights (area_lights.hip); synchronises, so not while capturing.  Triangles the build dropped
-// (alpha clipping) are found through the refit plan's leaves, which is made for that when the scene has any.
-int ensureAreaLights(bdpt_ctx* c, hipStream_t st) {
-  if (c->areaReady) return BDPT_OK;
-  if (streamIsCapturing(st)) {
-    fail(c, "area lights: the emitter table needs bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) before stream capture");
-    return BDPT_E_STATE;
-  }
-  HIPCHK(c, hipDeviceSynchronize());
-  const uint32_t nt = c->numTriangles;
-  const size_t nb = (nt + kWave - 1) / kWave;
-  std::vector<void*> scratch;
-  struct Free {
-    std::vector<void*>& p;
-    ~Free() { freePool(p); }
-  } freeScratch{scratch};
-  uint8_t* referenced = nullptr;
-  int rc;
-  if (c->bvhInfo.numDropped) {
-    if ((rc = ensureRefit(c, st))) return rc;
-    if ((rc = devAlloc(c, scratch, &referenced, nt))) return rc;
-    HIPCHK(c, hipMemset(referenced, 0, nt));
-    launchAreaMarkReferenced(c->refit.nodes, c->refit.numNodes, c->S.recs, referenced, nullptr);
-  }
-  uint32_t *blockCount = nullptr, *blockBase = nullptr, *counts = nullptr;
-  if ((rc = devAlloc(c, scratch, &blockCount, nb)) || (rc = devAlloc(c, scratch, &blockBase, nb)) || (rc = devAlloc(c, scratch, &counts, 2)))
-    return rc;
-  HIPCHK(c, hipMemset(counts, 0, 2 * sizeof(uint32_t)));
-  launchAreaCount(c->S, nt, referenced, blockCount, blockBase, counts, nullptr);
-  uint32_t hc[2] = {0, 0};
-  HIPCHK(c, hipMemcpy(hc, counts, sizeof(hc), hipMemcpyDeviceToHost));
-  AreaDev A{};
-  A.n = hc[0];
-  if (A.n) {
-    const size_t nbe = (A.n + kWave - 1) / kWave;
-    float *cdf = nullptr, *total = nullptr;
-    float4* emit = nullptr;
-    if ((rc = devAlloc(c, c->sceneAllocs, &cdf, A.n)) || (rc = devAlloc(c, c->sceneAllocs, &emit, A.n)) ||
-        (rc = devAlloc(c, c->sceneAllocs, &total, 2)) || (rc = devAlloc(c, c->sceneAllocs, &c->areaBlockSum, nbe)) ||
-        (rc = devAlloc(c, c->sceneAllocs, &c->areaBlockLast, nbe)))
-      return rc;
-    A.cdf = cdf;
-    A.emit = emit;
-    A.total = total;
-    launchAreaCompact(c->S, nt, referenced, blockBase, c->alphaTris, c->numAlphaTris, emit, nullptr);
-    launchAreaRefresh(c->S, A, c->areaBlockSum, c->areaBlockLast, nullptr);
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipDeviceSynchronize());
-  c->area = A;
-  c->areaTextured = hc[1];
-  c->areaReady = true;
-  return BDPT_OK;
-}
 // What every update ends with, on st: the refit to the device arrays `pos` (and `nrm`), the emitter table's refresh, the
 // bitangent copy, the light maps' re-trace unless kept.
 int updateTail(bdpt_ctx* c, const float* pos, const float* nrm, const float* bit, uint32_t flags, hipStream_t st) {
@@ -1213,259 +1089,6 @@ int bdpt_set_lights(bdpt_ctx* c, const bdpt_light* lights, uint32_t numLights, v
   return BDPT_OK;
 }
 
-static_assert(sizeof(bdpt_ray) == 32 && sizeof(bdpt_hit) == 16, "trace_rays_kernel reads a ray as two float4 and writes a hit as one");
-int bdpt_trace_rays(bdpt_ctx* c, const bdpt_trace_desc* d, void* stream) {
-  if (!c || !d) return BDPT_E_INVALID;
-  if (!c->haveScene) {
-    fail(c, "trace_rays: no scene (bdpt_set_scene first)");
-    return BDPT_E_STATE;
-  }
-  if (d->mode > BDPT_TRACE_ANY) {
-    fail(c, "trace_rays: unknown mode");
-    return BDPT_E_INVALID;
-  }
-  if (!d->numRays) return BDPT_OK;
-  const auto aligned = [](const void* p, uintptr_t a) { return p && (reinterpret_cast<uintptr_t>(p) % a) == 0; };
-  if (!aligned(d->rays, 16) || (d->numRaysDevice && !aligned(d->numRaysDevice, 4)) ||
-      (d->mode == BDPT_TRACE_ANY ? !d->visible : !aligned(d->hits, 16))) {
-    fail(c, "trace_rays: rays, hits or visible missing or not aligned (rays and hits 16 bytes, numRaysDevice 4)");
-    return BDPT_E_INVALID;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = orderAfterLast(c, st)) return rc;
-  launchTraceRays(c->S, reinterpret_cast<const float4*>(d->rays), d->numRays, d->numRaysDevice, c->rayCursor, (int)d->mode,
-                  reinterpret_cast<float4*>(d->hits), d->visible, c->grids, c->numCUs, st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
-}
-
-static_assert(sizeof(bdpt_surface) == 96 && sizeof(bdpt_bsdf_sample) == 32,
-              "shade_hits_kernel writes a surface as six float4, bsdf_query_kernel a sample as two");
-namespace {
-bool aligned(const void* p, uintptr_t a) { return p && (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-}  // namespace
-
-int bdpt_camera_rays(bdpt_ctx* c, const bdpt_gbuffer_params* p, uint32_t width, uint32_t height, bdpt_ray* rays, void* stream) {
-  if (!c || !p) return BDPT_E_INVALID;
-  if (!c->haveCamera) {
-    fail(c, "camera_rays: no camera (bdpt_set_camera first)");
-    return BDPT_E_STATE;
-  }
-  if (!width || !height || (uint64_t)width * height >= (1ull << 32) || !aligned(rays, 16)) {
-    fail(c, "camera_rays: width and height must be > 0 with width * height < 2^32, rays 16-byte aligned");
-    return BDPT_E_INVALID;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = orderAfterLast(c, st)) return rc;
-  launchCameraRays(c->cam, *p, width, height, reinterpret_cast<float4*>(rays), st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
-}
-
-int bdpt_shade_hits(bdpt_ctx* c, const bdpt_shade_desc* d, void* stream) {
-  if (!c || !d) return BDPT_E_INVALID;
-  if (!c->haveScene) {
-    fail(c, "shade_hits: no scene (bdpt_set_scene first)");
-    return BDPT_E_STATE;
-  }
-  if (d->flags & ~BDPT_SHADE_NORMAL_MAP) {
-    fail(c, "shade_hits: unknown flags");
-    return BDPT_E_INVALID;
-  }
-  if (!d->numHits) return BDPT_OK;
-  if (!aligned(d->rays, 16) || !aligned(d->hits, 16) || !aligned(d->surfaces, 16) || (d->numHitsDevice && !aligned(d->numHitsDevice, 4))) {
-    fail(c, "shade_hits: rays, hits or surfaces missing or not aligned (16 bytes; numHitsDevice 4)");
-    return BDPT_E_INVALID;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = orderAfterLast(c, st)) return rc;
-  launchShadeHits(c->S, c->numTriangles, reinterpret_cast<const float4*>(d->rays), reinterpret_cast<const float4*>(d->hits), d->numHits,
-                  d->numHitsDevice, (d->flags & BDPT_SHADE_NORMAL_MAP) != 0, reinterpret_cast<float4*>(d->surfaces), st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
-}
-
-int bdpt_bsdf_query(bdpt_ctx* c, const bdpt_bsdf_desc* d, void* stream) {
-  if (!c || !d) return BDPT_E_INVALID;
-  if (!c->haveScene) {
-    fail(c, "bsdf_query: no scene (bdpt_set_scene first)");
-    return BDPT_E_STATE;
-  }
-  if (d->mode > BDPT_BSDF_EVAL || d->matIndex > 1 || (d->flags & ~BDPT_PARAM_SPECULAR_FROM_LOBE)) {
-    fail(c, "bsdf_query: unknown mode or flags, or matIndex > 1");
-    return BDPT_E_INVALID;
-  }
-  if (!d->num) return BDPT_OK;
-  const bool eval = d->mode == BDPT_BSDF_EVAL;
-  if (!aligned(d->surfaces, 16) || (d->numDevice && !aligned(d->numDevice, 4)) ||
-      (eval ? (!aligned(d->dirs, 16) || !aligned(d->values, 16)) : (!aligned(d->seeds, 4) || !aligned(d->samples, 16)))) {
-    fail(c, "bsdf_query: surfaces, seeds, samples, dirs or values missing or not aligned (16 bytes; seeds and numDevice 4)");
-    return BDPT_E_INVALID;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = orderAfterLast(c, st)) return rc;
-  float4* out = eval ? reinterpret_cast<float4*>(d->values) : reinterpret_cast<float4*>(d->samples);
-  launchBsdfQuery(reinterpret_cast<const float4*>(d->surfaces), d->num, d->numDevice, eval, d->matIndex == 0,
-                  (d->flags & BDPT_PARAM_SPECULAR_FROM_LOBE) != 0, d->seeds, reinterpret_cast<const float4*>(d->dirs), out, st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
-}
-
-static_assert(sizeof(bdpt_light_sample) == 48 && sizeof(bdpt_light_emit) == 48 && offsetof(bdpt_light_sample, status) == 46,
-              "the light query kernels write a record as three float4, light and status sharing the last word");
-int bdpt_light_query(bdpt_ctx* c, const bdpt_light_desc* d, void* stream) {
-  if (!c || !d) return BDPT_E_INVALID;
-  if (!c->haveScene) {
-    fail(c, "light_query: no scene (bdpt_set_scene first)");
-    return BDPT_E_STATE;
-  }
-  const bool emitMode = d->mode == BDPT_LIGHT_EMIT;
-  if (d->mode > BDPT_LIGHT_EMIT || d->matIndex > 1 || (d->flags & ~(BDPT_PARAM_AREA_LIGHTS | BDPT_LIGHT_USE_HINTS))) {
-    fail(c, "light_query: unknown mode or flags, or matIndex > 1");
-    return BDPT_E_INVALID;
-  }
-  const bool compact = d->compactRays || d->compactItems || d->compactCount;
-  if (emitMode && (compact || (d->flags & BDPT_LIGHT_USE_HINTS))) {
-    fail(c, "light_query: compaction and BDPT_LIGHT_USE_HINTS go with BDPT_LIGHT_NEE");
-    return BDPT_E_INVALID;
-  }
-  if (compact && !(d->compactRays && d->compactItems && d->compactCount)) {
-    fail(c, "light_query: compactRays, compactItems and compactCount go together");
-    return BDPT_E_INVALID;
-  }
-  if (!d->num) return BDPT_OK;
-  if (!aligned(d->seeds, 4) || (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)) ||
-      (emitMode ? !aligned(d->emits, 16) : (!aligned(d->surfaces, 16) || !aligned(d->samples, 16))) ||
-      (compact && (!aligned(d->compactRays, 16) || !aligned(d->compactItems, 4) || !aligned(d->compactCount, 4)))) {
-    fail(c, "light_query: surfaces, seeds, samples, emits or a compaction buffer missing or not aligned (records 16 bytes, words 4)");
-    return BDPT_E_INVALID;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  AreaDev A{};
-  if (d->flags & BDPT_PARAM_AREA_LIGHTS) {
-    if (int rc = ensureAreaLights(c, st)) return rc;
-    A = c->area;  // n == 0 (no emitter): the plain instances
-  }
-  if (int rc = orderAfterLast(c, st)) return rc;
-  LightQueryDev Q{};
-  Q.surf = reinterpret_cast<const float4*>(d->surfaces);
-  Q.seeds = d->seeds;
-  Q.seedsOut = d->seedsOut;
-  Q.out = emitMode ? reinterpret_cast<float4*>(d->emits) : reinterpret_cast<float4*>(d->samples);
-  Q.cap = d->num;
-  Q.count = d->numDevice;
-  Q.minT = d->minT;
-  Q.compactRays = reinterpret_cast<float4*>(d->compactRays);
-  Q.compactItems = d->compactItems;
-  Q.compactCount = d->compactCount;
-  launchLightQuery(c->S, Q, A, emitMode, d->matIndex == 0, (d->flags & BDPT_LIGHT_USE_HINTS) != 0, st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
-}
-
-static_assert(sizeof(bdpt_connect_sample) == 48 && sizeof(bdpt_camera_sample) == 64 && offsetof(bdpt_connect_sample, status) == 44 &&
-                  offsetof(bdpt_camera_sample, G) == 44 && offsetof(bdpt_camera_sample, pixel) == 48,
-              "the connection query kernels write a record as three / four float4");
-int bdpt_connect_query(bdpt_ctx* c, const bdpt_connect_desc* d, void* stream) {
-  if (!c || !d) return BDPT_E_INVALID;
-  if (!c->haveScene) {
-    fail(c, "connect_query: no scene (bdpt_set_scene first)");
-    return BDPT_E_STATE;
-  }
-  if (d->mode > BDPT_CONNECT_CAMERA || d->matIndex > 1 || d->flags || d->reserved) {
-    fail(c, "connect_query: unknown mode, non-zero flags or reserved, or matIndex > 1");
-    return BDPT_E_INVALID;
-  }
-  const bool camMode = d->mode == BDPT_CONNECT_CAMERA;
-  if (camMode && !c->haveCamera) {
-    fail(c, "connect_query: BDPT_CONNECT_CAMERA without a camera (bdpt_set_camera first)");
-    return BDPT_E_STATE;
-  }
-  if (camMode && (!d->width || !d->height || (uint64_t)d->width * d->height >= (1ull << 32))) {
-    fail(c, "connect_query: width and height must be > 0 with width * height < 2^32");
-    return BDPT_E_INVALID;
-  }
-  const bool compact = d->compactRays || d->compactItems || d->compactCount;
-  if (compact && !(d->compactRays && d->compactItems && d->compactCount)) {
-    fail(c, "connect_query: compactRays, compactItems and compactCount go together");
-    return BDPT_E_INVALID;
-  }
-  if (!d->num) return BDPT_OK;
-  if (!aligned(d->light, 16) || (d->numDevice && !aligned(d->numDevice, 4)) ||
-      (camMode ? !aligned(d->cameraSamples, 16)
-               : (!aligned(d->eye, 16) || !aligned(d->samples, 16) || (d->eyePrev && !aligned(d->eyePrev, 16)) ||
-                  (d->lightPrev && !aligned(d->lightPrev, 16)))) ||
-      (compact && (!aligned(d->compactRays, 16) || !aligned(d->compactItems, 4) || !aligned(d->compactCount, 4)))) {
-    fail(c, "connect_query: eye, light, samples, a predecessor or a compaction buffer missing or not aligned (records 16 bytes, words 4)");
-    return BDPT_E_INVALID;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = orderAfterLast(c, st)) return rc;
-  ConnectQueryDev Q{};
-  Q.light = reinterpret_cast<const float4*>(d->light);
-  Q.lightSpecular = d->lightSpecular;
-  if (camMode) {
-    Q.out = reinterpret_cast<float4*>(d->cameraSamples);
-    Q.width = d->width;
-    Q.height = d->height;
-    Q.jitter[0] = d->pixelJitter[0];
-    Q.jitter[1] = d->pixelJitter[1];
-  } else {
-    Q.eye = reinterpret_cast<const float4*>(d->eye);
-    Q.eyePrev = reinterpret_cast<const float4*>(d->eyePrev);
-    Q.lightPrev = reinterpret_cast<const float4*>(d->lightPrev);
-    Q.eyeSpecular = d->eyeSpecular;
-    Q.out = reinterpret_cast<float4*>(d->samples);
-  }
-  Q.cap = d->num;
-  Q.count = d->numDevice;
-  Q.minT = d->minT;
-  Q.compactRays = reinterpret_cast<float4*>(d->compactRays);
-  Q.compactItems = d->compactItems;
-  Q.compactCount = d->compactCount;
-  launchConnectQuery(Q, camMode ? &c->cam : nullptr, d->matIndex == 0, st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
-}
-
-int bdpt_splat_add(bdpt_ctx* c, const bdpt_splat_desc* d, void* stream) {
-  if (!c || !d) return BDPT_E_INVALID;
-  if (!d->num) return BDPT_OK;
-  if (!aligned(d->pixels, 4) || !aligned(d->values, 16) || !aligned(d->splat, 16) || (d->items && !aligned(d->items, 4)) ||
-      (d->numDevice && !aligned(d->numDevice, 4))) {
-    fail(c, "splat_add: pixels, values, splat, items or numDevice missing or not aligned (splat and values 16 bytes, words 4)");
-    return BDPT_E_INVALID;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = orderAfterLast(c, st)) return rc;
-  SplatAddDev A{};
-  A.pixels = d->pixels;
-  A.values = reinterpret_cast<const float4*>(d->values);
-  A.visible = d->visible;
-  A.items = d->items;
-  A.splat = reinterpret_cast<unsigned long long*>(d->splat);
-  A.numPixels = d->numPixels;
-  A.cap = d->num;
-  A.count = d->numDevice;
-  launchSplatAdd(A, st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
-}
-
 int bdpt_get_refit_info(bdpt_ctx* c, bdpt_refit_info* out) {
   if (!c || !out) return BDPT_E_INVALID;
   if (!c->haveScene) return BDPT_E_STATE;
@@ -1615,7 +1238,7 @@ int resizeRows(bdpt_ctx* c, uint32_t width, uint32_t height, uint32_t maxDepth) 
   if ((rc = devAlloc(c, c->frameAllocs, &P.lightReal, np))) return rc;
   // a path queue = kNumSubQueues lists; workgroup b appends to list b % kNumSubQueues
   // (+ one workgroup's worth of slack)
-  P.pathSubCap = (uint32_t)((((np + kWave - 1) / kWave + kNumSubQueues - 1) / kNumSubQueues + 1) * kWave);
+  P.pathSubCap = (uint32_t)((((uint64_t)wavesFor(np) + kNumSubQueues - 1) / kNumSubQueues + 1) * kWave);
   const size_t qcap = (size_t)P.pathSubCap * kNumSubQueues;
   for (int q = 0; q < 3; q++)
     if ((rc = devAlloc(c, c->frameAllocs, &P.queue[q], qcap))) return rc;
@@ -1629,7 +1252,7 @@ int resizeRows(bdpt_ctx* c, uint32_t width, uint32_t height, uint32_t maxDepth) 
     const uint32_t D = std::max<uint32_t>(maxDepth, 1);
     const uint64_t slots = (uint64_t)2 * D + numConnectPairs(D);
     // workgroup b appends to sub-queue b % kNumSubQueues: size each for the workgroups it serves
-    const uint64_t blocks = (np + kWave - 1) / kWave;
+    const uint64_t blocks = wavesFor(np);
     // Producer workgroup b appends to ray sub-queue b % kNumRaySubQueues.  Generators run G lanes per pixel (8, or 16
     // when the context is sized for depth > 8: G x queueGrid workgroups of 64 / G pixels), lazy_gen one lane per pixel:
     // size every sub-queue for the workgroups it can serve under either launch shape.
@@ -1796,31 +1419,6 @@ int bdpt_gbuffer_execute_motion(bdpt_ctx* c, const bdpt_gbuffer_params* gp, cons
     return BDPT_E_INVALID;
   }
   return gbufferRun(c, gp, out, prevPosition, stream);
-}
-
-int bdpt_motion_query(bdpt_ctx* c, const bdpt_motion_desc* d, void* stream) {
-  if (!c || !d) return BDPT_E_INVALID;
-  if (!c->haveScene || !c->prevPose) {
-    fail(c, c->haveScene ? "motion_query: no previous pose (bdpt_prepare(BDPT_PREPARE_MOTION) first)" : "motion_query: no scene (bdpt_set_scene first)");
-    return BDPT_E_STATE;
-  }
-  if (d->reserved) {
-    fail(c, "motion_query: reserved must be 0");
-    return BDPT_E_INVALID;
-  }
-  if (!d->num) return BDPT_OK;
-  if (!aligned(d->hits, 16) || !aligned(d->prevPositions, 16) || (d->numDevice && !aligned(d->numDevice, 4))) {
-    fail(c, "motion_query: hits or prevPositions missing or not aligned (16 bytes; numDevice 4)");
-    return BDPT_E_INVALID;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = orderAfterLast(c, st)) return rc;
-  launchMotionQuery(c->prevPose, c->numTriangles, reinterpret_cast<const float4*>(d->hits), d->num, d->numDevice,
-                    reinterpret_cast<float4*>(d->prevPositions), st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
 }
 
 namespace {

@@ -1,0 +1,232 @@
+// api_query.cpp — the per-item queries of the C ABI (include/bdpt.h): bdpt_trace_rays, bdpt_camera_rays, bdpt_shade_hits,
+// bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add and bdpt_motion_query, on a caller's arrays in
+// device memory.  Every one checks its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags
+// and what goes together (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call
+// enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
+// first use of the emitter table), so all can be captured into a hipGraph.
+#include <cstddef>
+#include <string>
+
+#include "context.hpp"
+
+using namespace bdpt;
+
+namespace {
+
+int refuse(bdpt_ctx* c, int code, const char* what, const char* why) {
+  fail(c, std::string(what) + ": " + why);
+  return code;
+}
+int needScene(bdpt_ctx* c, const char* what) {
+  return c->haveScene ? BDPT_OK : refuse(c, BDPT_E_STATE, what, "no scene (bdpt_set_scene first)");
+}
+int needCamera(bdpt_ctx* c, const char* what) {
+  return c->haveCamera ? BDPT_OK : refuse(c, BDPT_E_STATE, what, "no camera (bdpt_set_camera first)");
+}
+bool frameSizeOk(uint32_t width, uint32_t height) { return width && height && (uint64_t)width * height < (1ull << 32); }
+
+// The three pointers of a compacted ray list: `on` when any is set, and then `whole` (all three are: checked before an
+// empty call returns) and `aligned` (checked with the other pointers).
+struct CompactArgs {
+  bool on, whole, aligned;
+  CompactList list;
+};
+CompactArgs compactArgs(bdpt_ray* rays, uint32_t* items, uint32_t* count) {
+  return {rays || items || count, rays && items && count, aligned(rays, 16) && aligned(items, 4) && aligned(count, 4),
+          CompactList{reinterpret_cast<float4*>(rays), items, count}};
+}
+int needWholeCompact(bdpt_ctx* c, const char* what, const CompactArgs& k) {
+  return !k.on || k.whole ? BDPT_OK : refuse(c, BDPT_E_INVALID, what, "compactRays, compactItems and compactCount go together");
+}
+
+// The accepted call: launch(st) on the caller's stream, ordered after the context's last call.
+template <class Launch>
+int enqueueQuery(bdpt_ctx* c, void* stream, Launch&& launch) {
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  launch(st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
+const float4* f4(const void* p) { return reinterpret_cast<const float4*>(p); }
+float4* f4(void* p) { return reinterpret_cast<float4*>(p); }
+
+}  // namespace
+
+extern "C" {
+
+static_assert(sizeof(bdpt_ray) == 32 && sizeof(bdpt_hit) == 16, "trace_rays_kernel reads a ray as two float4 and writes a hit as one");
+int bdpt_trace_rays(bdpt_ctx* c, const bdpt_trace_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "trace_rays")) return rc;
+  if (d->mode > BDPT_TRACE_ANY) return refuse(c, BDPT_E_INVALID, "trace_rays", "unknown mode");
+  if (!d->numRays) return BDPT_OK;
+  if (!aligned(d->rays, 16) || (d->numRaysDevice && !aligned(d->numRaysDevice, 4)) ||
+      (d->mode == BDPT_TRACE_ANY ? !d->visible : !aligned(d->hits, 16)))
+    return refuse(c, BDPT_E_INVALID, "trace_rays", "rays, hits or visible missing or not aligned (rays and hits 16 bytes, numRaysDevice 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    launchTraceRays(c->S, f4(d->rays), d->numRays, d->numRaysDevice, c->rayCursor, (int)d->mode, f4(d->hits), d->visible, c->grids,
+                    c->numCUs, st);
+  });
+}
+
+static_assert(sizeof(bdpt_surface) == 96 && sizeof(bdpt_bsdf_sample) == 32,
+              "shade_hits_kernel writes a surface as six float4, bsdf_query_kernel a sample as two");
+int bdpt_camera_rays(bdpt_ctx* c, const bdpt_gbuffer_params* p, uint32_t width, uint32_t height, bdpt_ray* rays, void* stream) {
+  if (!c || !p) return BDPT_E_INVALID;
+  if (int rc = needCamera(c, "camera_rays")) return rc;
+  if (!frameSizeOk(width, height) || !aligned(rays, 16))
+    return refuse(c, BDPT_E_INVALID, "camera_rays", "width and height must be > 0 with width * height < 2^32, rays 16-byte aligned");
+  return enqueueQuery(c, stream, [&](hipStream_t st) { launchCameraRays(c->cam, *p, width, height, f4(rays), st); });
+}
+
+int bdpt_shade_hits(bdpt_ctx* c, const bdpt_shade_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "shade_hits")) return rc;
+  if (d->flags & ~BDPT_SHADE_NORMAL_MAP) return refuse(c, BDPT_E_INVALID, "shade_hits", "unknown flags");
+  if (!d->numHits) return BDPT_OK;
+  if (!aligned(d->rays, 16) || !aligned(d->hits, 16) || !aligned(d->surfaces, 16) || (d->numHitsDevice && !aligned(d->numHitsDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "shade_hits", "rays, hits or surfaces missing or not aligned (16 bytes; numHitsDevice 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    launchShadeHits(c->S, c->numTriangles, f4(d->rays), f4(d->hits), d->numHits, d->numHitsDevice, (d->flags & BDPT_SHADE_NORMAL_MAP) != 0,
+                    f4(d->surfaces), st);
+  });
+}
+
+int bdpt_bsdf_query(bdpt_ctx* c, const bdpt_bsdf_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "bsdf_query")) return rc;
+  if (d->mode > BDPT_BSDF_EVAL || d->matIndex > 1 || (d->flags & ~BDPT_PARAM_SPECULAR_FROM_LOBE))
+    return refuse(c, BDPT_E_INVALID, "bsdf_query", "unknown mode or flags, or matIndex > 1");
+  if (!d->num) return BDPT_OK;
+  const bool eval = d->mode == BDPT_BSDF_EVAL;
+  if (!aligned(d->surfaces, 16) || (d->numDevice && !aligned(d->numDevice, 4)) ||
+      (eval ? (!aligned(d->dirs, 16) || !aligned(d->values, 16)) : (!aligned(d->seeds, 4) || !aligned(d->samples, 16))))
+    return refuse(c, BDPT_E_INVALID, "bsdf_query", "surfaces, seeds, samples, dirs or values missing or not aligned (16 bytes; seeds and numDevice 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    launchBsdfQuery(f4(d->surfaces), d->num, d->numDevice, eval, d->matIndex == 0, (d->flags & BDPT_PARAM_SPECULAR_FROM_LOBE) != 0, d->seeds,
+                    f4(d->dirs), eval ? f4(d->values) : f4(d->samples), st);
+  });
+}
+
+static_assert(sizeof(bdpt_light_sample) == 48 && sizeof(bdpt_light_emit) == 48 && offsetof(bdpt_light_sample, status) == 46,
+              "the light query kernels write a record as three float4, light and status sharing the last word");
+int bdpt_light_query(bdpt_ctx* c, const bdpt_light_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "light_query")) return rc;
+  const bool emitMode = d->mode == BDPT_LIGHT_EMIT;
+  if (d->mode > BDPT_LIGHT_EMIT || d->matIndex > 1 || (d->flags & ~(BDPT_PARAM_AREA_LIGHTS | BDPT_LIGHT_USE_HINTS)))
+    return refuse(c, BDPT_E_INVALID, "light_query", "unknown mode or flags, or matIndex > 1");
+  const CompactArgs k = compactArgs(d->compactRays, d->compactItems, d->compactCount);
+  if (emitMode && (k.on || (d->flags & BDPT_LIGHT_USE_HINTS)))
+    return refuse(c, BDPT_E_INVALID, "light_query", "compaction and BDPT_LIGHT_USE_HINTS go with BDPT_LIGHT_NEE");
+  if (int rc = needWholeCompact(c, "light_query", k)) return rc;
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->seeds, 4) || (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)) ||
+      (emitMode ? !aligned(d->emits, 16) : (!aligned(d->surfaces, 16) || !aligned(d->samples, 16))) || (k.on && !k.aligned))
+    return refuse(c, BDPT_E_INVALID, "light_query",
+                  "surfaces, seeds, samples, emits or a compaction buffer missing or not aligned (records 16 bytes, words 4)");
+  AreaDev A{};
+  // The table's first build synchronises the device, so it comes before enqueueQuery orders the call after the last one;
+  // it needs the context's device current, hence an ENTER of its own (enqueueQuery's second one changes nothing).
+  if (d->flags & BDPT_PARAM_AREA_LIGHTS) {
+    ENTER(c);
+    if (int rc = ensureAreaLights(c, reinterpret_cast<hipStream_t>(stream))) return rc;
+    A = c->area;  // n == 0 (no emitter): the plain instances
+  }
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    LightQueryDev Q{};
+    Q.surf = f4(d->surfaces);
+    Q.seeds = d->seeds;
+    Q.seedsOut = d->seedsOut;
+    Q.out = emitMode ? f4(d->emits) : f4(d->samples);
+    Q.range = {d->num, d->numDevice, d->minT};
+    Q.compact = k.list;
+    launchLightQuery(c->S, Q, A, emitMode, d->matIndex == 0, (d->flags & BDPT_LIGHT_USE_HINTS) != 0, st);
+  });
+}
+
+static_assert(sizeof(bdpt_connect_sample) == 48 && sizeof(bdpt_camera_sample) == 64 && offsetof(bdpt_connect_sample, status) == 44 &&
+                  offsetof(bdpt_camera_sample, G) == 44 && offsetof(bdpt_camera_sample, pixel) == 48,
+              "the connection query kernels write a record as three / four float4");
+int bdpt_connect_query(bdpt_ctx* c, const bdpt_connect_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "connect_query")) return rc;
+  if (d->mode > BDPT_CONNECT_CAMERA || d->matIndex > 1 || d->flags || d->reserved)
+    return refuse(c, BDPT_E_INVALID, "connect_query", "unknown mode, non-zero flags or reserved, or matIndex > 1");
+  const bool camMode = d->mode == BDPT_CONNECT_CAMERA;
+  if (camMode) {
+    if (int rc = needCamera(c, "connect_query: BDPT_CONNECT_CAMERA")) return rc;
+    if (!frameSizeOk(d->width, d->height))
+      return refuse(c, BDPT_E_INVALID, "connect_query", "width and height must be > 0 with width * height < 2^32");
+  }
+  const CompactArgs k = compactArgs(d->compactRays, d->compactItems, d->compactCount);
+  if (int rc = needWholeCompact(c, "connect_query", k)) return rc;
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->light, 16) || (d->numDevice && !aligned(d->numDevice, 4)) ||
+      (camMode ? !aligned(d->cameraSamples, 16)
+               : (!aligned(d->eye, 16) || !aligned(d->samples, 16) || (d->eyePrev && !aligned(d->eyePrev, 16)) ||
+                  (d->lightPrev && !aligned(d->lightPrev, 16)))) ||
+      (k.on && !k.aligned))
+    return refuse(c, BDPT_E_INVALID, "connect_query",
+                  "eye, light, samples, a predecessor or a compaction buffer missing or not aligned (records 16 bytes, words 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    ConnectQueryDev Q{};
+    Q.light = f4(d->light);
+    Q.lightSpecular = d->lightSpecular;
+    if (camMode) {
+      Q.out = f4(d->cameraSamples);
+      Q.width = d->width;
+      Q.height = d->height;
+      Q.jitter[0] = d->pixelJitter[0];
+      Q.jitter[1] = d->pixelJitter[1];
+    } else {
+      Q.eye = f4(d->eye);
+      Q.eyePrev = f4(d->eyePrev);
+      Q.lightPrev = f4(d->lightPrev);
+      Q.eyeSpecular = d->eyeSpecular;
+      Q.out = f4(d->samples);
+    }
+    Q.range = {d->num, d->numDevice, d->minT};
+    Q.compact = k.list;
+    launchConnectQuery(Q, camMode ? &c->cam : nullptr, d->matIndex == 0, st);
+  });
+}
+
+int bdpt_splat_add(bdpt_ctx* c, const bdpt_splat_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->pixels, 4) || !aligned(d->values, 16) || !aligned(d->splat, 16) || (d->items && !aligned(d->items, 4)) ||
+      (d->numDevice && !aligned(d->numDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "splat_add", "pixels, values, splat, items or numDevice missing or not aligned (splat and values 16 bytes, words 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    SplatAddDev A{};
+    A.pixels = d->pixels;
+    A.values = f4(d->values);
+    A.visible = d->visible;
+    A.items = d->items;
+    A.splat = reinterpret_cast<unsigned long long*>(d->splat);
+    A.numPixels = d->numPixels;
+    A.cap = d->num;
+    A.count = d->numDevice;
+    launchSplatAdd(A, st);
+  });
+}
+
+int bdpt_motion_query(bdpt_ctx* c, const bdpt_motion_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "motion_query")) return rc;
+  if (!c->prevPose) return refuse(c, BDPT_E_STATE, "motion_query", "no previous pose (bdpt_prepare(BDPT_PREPARE_MOTION) first)");
+  if (d->reserved) return refuse(c, BDPT_E_INVALID, "motion_query", "reserved must be 0");
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->hits, 16) || !aligned(d->prevPositions, 16) || (d->numDevice && !aligned(d->numDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "motion_query", "hits or prevPositions missing or not aligned (16 bytes; numDevice 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    launchMotionQuery(c->prevPose, c->numTriangles, f4(d->hits), d->num, d->numDevice, f4(d->prevPositions), st);
+  });
+}
+
+}  // extern "C"

@@ -209,8 +209,6 @@ __global__ __launch_bounds__(kWave) void test_area_kernel(SceneDev S, AreaDev A,
   for (int k = 0; k < 16; k++) out[(size_t)i * 16 + k] = o[k];
 }
 
-uint32_t wavesFor(uint64_t n) { return (uint32_t)((n + kWave - 1) / kWave); }
-
 }  // namespace
 
 void launchAreaMarkReferenced(const BvhRefitNode* nodes, uint32_t numNodes, const uint4* recs, uint8_t* referenced, hipStream_t st) {

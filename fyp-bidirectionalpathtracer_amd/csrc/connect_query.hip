@@ -12,23 +12,15 @@
 // count returns, except in the COMPACT instances, where it stays for the wave's ballot (a wave wholly past it returns).
 #include "kernels.h"
 
-#include <type_traits>
-
 #include "device_connect.hpp"
 #include "device_math.hpp"
+#include "device_query.hpp"
 #include "device_trace.hpp"  // BDPT_ONE_WAVE_PER_GROUP
 #include "launch.hpp"
 
 namespace bdpt {
 
 namespace {
-// The number of items a launch covers: min(*count, cap), or cap without a device word (wave-uniform).
-__device__ __forceinline__ uint32_t itemCount(uint32_t cap, const uint32_t* count) {
-  if (!count) return cap;
-  const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)*count);
-  return c < cap ? c : cap;
-}
-
 // the fields of a bdpt_surface record the BSDF reads (the names pairValue / splatTerm expect)
 struct SurfVtx {
   f3 pos, N, dif, spec;
@@ -65,32 +57,14 @@ __device__ __forceinline__ f3 outgoing(const float4* rec, const float4* prev, ui
   const float4 v = rec[2];
   return mk(v.x, v.y, v.z);
 }
-
-// one ballot + popcount prefix and one atomic per wave, as emitRay appends to the pass's ray queue
-__device__ __forceinline__ void compactAppend(const ConnectQueryDev& Q, bool emit, uint32_t i, float4 q0, float4 q1) {
-  const unsigned long long mask = __ballot(emit);
-  if (mask == 0ull) return;
-  const int lane = (int)(threadIdx.x & 63u);
-  const int leader = __ffsll((long long)mask) - 1;
-  uint32_t base = 0;
-  if (lane == leader) base = atomicAdd(Q.compactCount, (uint32_t)__popcll(mask));
-  base = (uint32_t)__shfl((int)base, leader);
-  const uint32_t at = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-  if (emit && at < Q.cap) {  // (at < cap always when the caller zeroed the word: never write past the lists)
-    Q.compactRays[(size_t)at * 2] = q0;
-    Q.compactRays[(size_t)at * 2 + 1] = q1;
-    Q.compactItems[at] = i;
-  }
-}
 }  // namespace
 
 // bdpt_connect_sample: three float4 per item, (org, tmin) (dir, tmax) (value, status)
 template <bool GGX, bool COMPACT>
 __global__ __launch_bounds__(kWave) void connect_vertices_kernel(ConnectQueryDev Q) {
   BDPT_ONE_WAVE_PER_GROUP();
-  const uint32_t i = blockIdx.x * kWave + threadIdx.x;
-  const uint32_t n = itemCount(Q.cap, Q.count);
-  if (COMPACT ? (blockIdx.x * kWave >= n) : (i >= n)) return;  // (COMPACT: wave-uniform)
+  uint32_t i, n;
+  if (queryLanePast<COMPACT>(Q.range.cap, Q.range.count, i, n)) return;
   bool emit = false;
   float4 q0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q1 = q0;
   if (i < n) {
@@ -105,23 +79,22 @@ __global__ __launch_bounds__(kWave) void connect_vertices_kernel(ConnectQueryDev
     if (__float_as_int(er[5].w) >= 0 && __float_as_int(lr[5].w) >= 0)
       pairValue<GGX>(ev, outgoing<GGX>(er, Q.eyePrev, i, ev.pos), le, outgoing<GGX>(lr, Q.lightPrev, i, le.pos), value);
     emit = !allZero(value);
-    q0 = make_float4(ev.pos.x, ev.pos.y, ev.pos.z, Q.minT);
+    q0 = make_float4(ev.pos.x, ev.pos.y, ev.pos.z, Q.range.minT);
     q1 = make_float4(dirAB.x, dirAB.y, dirAB.z, lengthAB);
     float4* o = Q.out + (size_t)i * 3;
     o[0] = q0;
     o[1] = q1;
     o[2] = make_float4(value.x, value.y, value.z, __uint_as_float(emit ? BDPT_CONNECT_STATUS_NONZERO : 0u));
   }
-  if (COMPACT) compactAppend(Q, emit, i, q0, q1);
+  if (COMPACT) compactAppend(Q.compact, Q.range.cap, emit, i, q0, q1);
 }
 
 // bdpt_camera_sample: four float4 per item, (org, tmin) (dir, tmax) (f, G) (pixel, status, 0, 0)
 template <bool GGX, bool COMPACT>
 __global__ __launch_bounds__(kWave) void connect_camera_kernel(ConnectQueryDev Q, bdpt_camera camera) {
   BDPT_ONE_WAVE_PER_GROUP();
-  const uint32_t i = blockIdx.x * kWave + threadIdx.x;
-  const uint32_t n = itemCount(Q.cap, Q.count);
-  if (COMPACT ? (blockIdx.x * kWave >= n) : (i >= n)) return;  // (COMPACT: wave-uniform)
+  uint32_t i, n;
+  if (queryLanePast<COMPACT>(Q.range.cap, Q.range.count, i, n)) return;
   bool emit = false;
   float4 q0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q1 = q0;
   if (i < n) {
@@ -148,7 +121,7 @@ __global__ __launch_bounds__(kWave) void connect_camera_kernel(ConnectQueryDev Q
         q2 = make_float4(fr.x, fr.y, fr.z, Gt);
         emit = true;  // the pass traces it whatever its value: a zero-valued splat still saturates its pixel
       }
-      q0 = make_float4(lv.pos.x, lv.pos.y, lv.pos.z, Q.minT);
+      q0 = make_float4(lv.pos.x, lv.pos.y, lv.pos.z, Q.range.minT);
       q1 = make_float4(dirToCamera.x, dirToCamera.y, dirToCamera.z, disToCamera);
     }
     float4* o = Q.out + (size_t)i * 4;
@@ -157,15 +130,15 @@ __global__ __launch_bounds__(kWave) void connect_camera_kernel(ConnectQueryDev Q
     o[2] = q2;
     o[3] = make_float4(__uint_as_float(pixel), __uint_as_float(status), 0.0f, 0.0f);
   }
-  if (COMPACT) compactAppend(Q, emit, i, q0, q1);
+  if (COMPACT) compactAppend(Q.compact, Q.range.cap, emit, i, q0, q1);
 }
 
 // Entry j uses item k = items ? items[j] : j: pixels[k], values[k], visible[j].  64-bit vector atomics on integers: the
 // sums are exact whatever the order.
 __global__ __launch_bounds__(kWave) void splat_add_kernel(SplatAddDev A) {
   BDPT_ONE_WAVE_PER_GROUP();
-  const uint32_t j = blockIdx.x * kWave + threadIdx.x;
-  if (j >= itemCount(A.cap, A.count)) return;
+  uint32_t j;
+  if (queryLanePast(A.cap, A.count, j)) return;
   if (A.visible && A.visible[j] == 0) return;
   const uint32_t k = A.items ? A.items[j] : j;
   const uint32_t pix = A.pixels[k];
@@ -181,21 +154,11 @@ __global__ __launch_bounds__(kWave) void splat_add_kernel(SplatAddDev A) {
   atomicAdd(&sp[3], 1ull);
 }
 
-namespace {
-template <class Fn>
-void withFlag(bool f, Fn&& fn) {
-  if (f)
-    fn(std::true_type{});
-  else
-    fn(std::false_type{});
-}
-}  // namespace
-
 void launchConnectQuery(const ConnectQueryDev& Q, const bdpt_camera* cam, bool ggx, hipStream_t st) {
-  if (!Q.cap) return;
-  const uint32_t g = (uint32_t)(((uint64_t)Q.cap + kWave - 1) / kWave);
+  if (!Q.range.cap) return;
+  const uint32_t g = wavesFor(Q.range.cap);
   withFlag(ggx, [&](auto GGX) {
-    withFlag(Q.compactRays != nullptr, [&](auto COMPACT) {
+    withFlag(Q.compact.rays != nullptr, [&](auto COMPACT) {
       if (cam)
         launchWave(connect_camera_kernel<GGX, COMPACT>, g, st, Q, *cam);
       else
@@ -206,7 +169,7 @@ void launchConnectQuery(const ConnectQueryDev& Q, const bdpt_camera* cam, bool g
 
 void launchSplatAdd(const SplatAddDev& A, hipStream_t st) {
   if (!A.cap) return;
-  launchWave(splat_add_kernel, (uint32_t)(((uint64_t)A.cap + kWave - 1) / kWave), st, A);
+  launchWave(splat_add_kernel, wavesFor(A.cap), st, A);
 }
 
 }  // namespace bdpt

@@ -315,6 +315,17 @@ void launchShadeHits(const SceneDev& S, uint32_t numTris, const float4* rays, co
                      bool normalMap, float4* out, hipStream_t st);
 void launchBsdfQuery(const float4* surf, uint32_t cap, const uint32_t* count, bool eval, bool ggx, bool fromLobe, const uint32_t* seeds,
                      const float4* dirs, float4* out, hipStream_t st);
+// What the per-item queries share (device_query.hpp reads them): the items of a launch and the dense ray list.
+struct QueryRange {
+  uint32_t cap;           // items; the capacity when count is set
+  const uint32_t* count;  // optional device word: min(*count, cap) items
+  float minT;             // tmin of the rays
+};
+struct CompactList {
+  float4* rays;     // optional: dense list of the rays worth tracing (capacity: the query's cap)
+  uint32_t* items;  //   their item indices
+  uint32_t* count;  //   the list's length (the caller zeroes it)
+};
 // light_query.hip: bdpt_light_query.  NEE: one bdpt_light_sample (three float4) per bdpt_surface record and seed, and with
 // compactRays the rays worth tracing appended to a dense list; EMIT: one bdpt_light_emit (three float4) per seed.
 struct LightQueryDev {
@@ -322,12 +333,8 @@ struct LightQueryDev {
   const uint32_t* seeds;   // one RNG state per item
   uint32_t* seedsOut;      // optional: NEE the state after the selection draw, EMIT the state after all draws (seedL)
   float4* out;             // three float4 per item
-  uint32_t cap;            // items; the capacity when count is set
-  const uint32_t* count;   // optional device word: min(*count, cap) items
-  float minT;              // tmin of the rays, and of the occluder-hint test
-  float4* compactRays;     // NEE, optional: dense list of the rays with status == NONZERO (capacity cap)
-  uint32_t* compactItems;  //   their item indices
-  uint32_t* compactCount;  //   the list's length (the caller zeroes it)
+  QueryRange range;        // minT: also of the occluder-hint test
+  CompactList compact;     // NEE, optional: the rays with status == NONZERO
 };
 // A.n > 0: the AREA instances (the emitter table is light numLights while its W is positive)
 void launchLightQuery(const SceneDev& S, const LightQueryDev& Q, const AreaDev& A, bool emitMode, bool ggx, bool hints, hipStream_t st);
@@ -341,14 +348,10 @@ struct ConnectQueryDev {
   const uint8_t* eyeSpecular;    // optional: bdpt_bsdf_sample::specular of the vertex (NULL = 0)
   const uint8_t* lightSpecular;
   float4* out;                   // three (VERTICES) or four (CAMERA) float4 per item
-  uint32_t cap;                  // items; the capacity when count is set
-  const uint32_t* count;         // optional device word: min(*count, cap) items
-  float minT;                    // tmin of the rays
+  QueryRange range;
   uint32_t width, height;        // CAMERA: the frame
   float jitter[2];               // CAMERA: bdpt_params::pixelJitter
-  float4* compactRays;           // optional: dense list of the rays with NONZERO (VERTICES) / PIXEL (CAMERA), capacity cap
-  uint32_t* compactItems;        //   their item indices
-  uint32_t* compactCount;        //   the list's length (the caller zeroes it)
+  CompactList compact;           // optional: the rays with NONZERO (VERTICES) / PIXEL (CAMERA)
 };
 // cam: the context's camera for CAMERA mode, nullptr for VERTICES
 void launchConnectQuery(const ConnectQueryDev& Q, const bdpt_camera* cam, bool ggx, hipStream_t st);
@@ -412,7 +415,7 @@ void launchTestBsdf(const float* in, uint32_t n, uint32_t matIndex, float* out, 
 // into blockBase (exclusive) and counts[0..1] = emitters, textured emitters; launchAreaCompact then writes the emitters'
 // primitives in ascending order.  Refresh (every bdpt_update_geometry; no allocation, no synchronisation):
 // launchAreaRefresh recomputes weights and the CDF from the current shading records.  `blocks` holds one float and one
-// word per 64 emitters (blocksFor(n)).
+// word per 64 emitters (wavesFor(n)).
 void launchAreaMarkReferenced(const BvhRefitNode* nodes, uint32_t numNodes, const uint4* recs, uint8_t* referenced, hipStream_t st);
 void launchAreaCount(const SceneDev& S, uint32_t numTris, const uint8_t* referenced, uint32_t* blockCount, uint32_t* blockBase,
                      uint32_t* counts, hipStream_t st);

@@ -1646,7 +1646,6 @@ __global__ void test_bsdf_kernel(const float* in, uint32_t n, bool fromLobe, flo
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static inline uint32_t blocksFor(uint64_t n) { return (uint32_t)((n + kWave - 1) / kWave); }
 // grid of a dense kernel over a sharded path queue: every (list, chunk) pair gets a workgroup
 static inline uint32_t queueGrid(const PathBuf& P) { return (P.pathSubCap / kWave) * kNumSubQueues; }
 
@@ -1698,11 +1697,11 @@ static FrameArg<K> frameArg(const FrameVariant& V) {
 void launchGBuffer(const SceneDev& S, const GBufferDev& G, hipStream_t st) {
   const uint32_t Np = G.Np;
   if (!Np) return;
-  withFlags([&](auto CNT) { launchWave(gbuffer_kernel<CNT>, blocksFor(Np), st, S, G, NoArg{}); }, G.counters != nullptr);
+  withFlags([&](auto CNT) { launchWave(gbuffer_kernel<CNT>, wavesFor(Np), st, S, G, NoArg{}); }, G.counters != nullptr);
 }
 void launchGBufferMotion(const SceneDev& S, const GBufferDev& G, const MotionDev& M, hipStream_t st) {
   if (!G.Np) return;
-  launchWave(gbuffer_kernel<false, false, true>, blocksFor(G.Np), st, S, G, M);
+  launchWave(gbuffer_kernel<false, false, true>, wavesFor(G.Np), st, S, G, M);
 }
 
 // The 64-byte alpha-test record of every non-opaque triangle (device_scene.hpp alphaTestFails: the triangle's three texture
@@ -1746,26 +1745,26 @@ void launchAlphaRecs(const SceneDev& S, const uint32_t* alphaTris, uint32_t n, c
 
 void launchHintFill(const SceneDev& S, const GBufferDev& G, hipStream_t st) {  // G.Np = W * H, G.pix unused
   if (!G.Np || !G.hintPix) return;
-  launchWave(gbuffer_kernel<false, true>, (uint32_t)(blocksFor(G.Np)), st, S, G, NoArg{});
+  launchWave(gbuffer_kernel<false, true>, wavesFor(G.Np), st, S, G, NoArg{});
 }
 
 void launchLightMaps(const SceneDev& S, uint32_t* maps, uint32_t res, hipStream_t st) {
   const uint64_t n = (uint64_t)6 * res * res * S.numLights;
   if (!n) return;
-  launchWave(light_map_kernel, (uint32_t)((n + kWave - 1) / kWave), st, S, maps, res);
+  launchWave(light_map_kernel, wavesFor(n), st, S, maps, res);
 }
 
 void launchInitPaths(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, hipStream_t st) {
   if (!P.Np) return;
   if (V.area.n) {
     withKind(V.kind, [&](auto K) {
-      withFlags([&](auto GGX) { launchWave(init_paths_area_kernel<GGX, K>, blocksFor(P.Np), st, S, F, P, frameArg<K>(V), V.area); },
+      withFlags([&](auto GGX) { launchWave(init_paths_area_kernel<GGX, K>, wavesFor(P.Np), st, S, F, P, frameArg<K>(V), V.area); },
                 F.p.matIndex == 0);
     });
     return;
   }
   withKind(V.kind, [&](auto K) {
-    withFlags([&](auto GGX) { launchWave(init_paths_kernel<GGX, K>, blocksFor(P.Np), st, S, F, P, frameArg<K>(V)); }, F.p.matIndex == 0);
+    withFlags([&](auto GGX) { launchWave(init_paths_kernel<GGX, K>, wavesFor(P.Np), st, S, F, P, frameArg<K>(V)); }, F.p.matIndex == 0);
   });
 }
 
@@ -1776,7 +1775,7 @@ void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const Fr
   const bool ext = (F.p.flags & (BDPT_PARAM_ENV_ON_MISS | BDPT_PARAM_EMISSIVE_HITS)) != 0, masked = V.kind == FrameKind::Masked;
   uint32_t& g = G.walk[(masked ? 8 : 0) + (ext ? 4 : 0) + (ggx ? 2 : 0) + (cnt ? 1 : 0)];
   // at most two sub-paths per pixel: a small tile does not need the whole persistent grid
-  const uint32_t need = blocksFor((uint64_t)2 * P.Np);
+  const uint32_t need = wavesFor((uint64_t)2 * P.Np);
   withFlags(
       [&](auto GGX, auto CNT, auto EXT, auto MASKED) {
         const auto kernel = walk_kernel<GGX, CNT, EXT, MASKED>;
@@ -1928,11 +1927,11 @@ void launchTestRng(const uint32_t* v0, const uint32_t* v1, uint32_t n, uint32_t 
 void launchTestTrace(const SceneDev& S, const float* rays, uint32_t n, int mode, int32_t* prim, float* tuv, hipStream_t st) {
   if (!n) return;
   if (mode == 0)
-    launchWave(test_trace_kernel<0>, (uint32_t)(blocksFor(n)), st, S, rays, n, prim, tuv);
+    launchWave(test_trace_kernel<0>, wavesFor(n), st, S, rays, n, prim, tuv);
   else if (mode == 1)
-    launchWave(test_trace_kernel<1>, (uint32_t)(blocksFor(n)), st, S, rays, n, prim, tuv);
+    launchWave(test_trace_kernel<1>, wavesFor(n), st, S, rays, n, prim, tuv);
   else
-    launchWave(test_trace_kernel<2>, (uint32_t)(blocksFor(n)), st, S, rays, n, prim, tuv);
+    launchWave(test_trace_kernel<2>, wavesFor(n), st, S, rays, n, prim, tuv);
 }
 // The persistent any-hit kernel over a caller's ray list (planes ox oy oz dx dy dz tmax of stride `cap`, one sub-queue):
 // visibility bytes and, through `counters`, the visit tallies and the deepest stack.

@@ -1,7 +1,9 @@
-// launch.hpp — host-side launch helpers of the one-wave-per-workgroup kernels (kernels.hip, trace_rays.hip).
+// launch.hpp — host-side launch helpers of the one-wave-per-workgroup kernels (every .hip file but bvh_device.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -10,6 +12,18 @@ namespace bdpt {
 #ifndef PERCU
 #define PERCU 24
 #endif
+
+// one-wave workgroups that cover n lanes
+static inline uint32_t wavesFor(uint64_t n) { return (uint32_t)((n + kWave - 1) / kWave); }
+
+// fn(std::true_type{}) or fn(std::false_type{}): a run-time switch as a template argument of the kernel
+template <class Fn>
+static void withFlag(bool f, Fn&& fn) {
+  if (f)
+    fn(std::true_type{});
+  else
+    fn(std::false_type{});
+}
 
 // ONE WORKGROUP = ONE WAVE (kernels.hip, above its launchers, lists what relies on it).  The kernels declared
 // __launch_bounds__(kWave) are launched through launchWave() only — there is no block size to get wrong — and each

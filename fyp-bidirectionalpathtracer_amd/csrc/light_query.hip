@@ -11,10 +11,9 @@
 // returns, except in the COMPACT instances, where it stays for the wave's ballot (a wave wholly past the count returns).
 #include "kernels.h"
 
-#include <type_traits>
-
 #include "device_area.hpp"
 #include "device_math.hpp"
+#include "device_query.hpp"
 #include "device_scene.hpp"
 #include "device_trace.hpp"  // BDPT_ONE_WAVE_PER_GROUP, recOccludes, lightHint
 #include "launch.hpp"
@@ -22,13 +21,6 @@
 namespace bdpt {
 
 namespace {
-// The number of items a launch covers: min(*count, cap), or cap without a device word (wave-uniform).
-__device__ __forceinline__ uint32_t itemCount(uint32_t cap, const uint32_t* count) {
-  if (!count) return cap;
-  const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)*count);
-  return c < cap ? c : cap;
-}
-
 // the light count of the pass: the emitter table is light numLights of numLights + 1 while its W is positive
 template <bool AREA>
 __device__ __forceinline__ int lightsCountOf(const SceneDev& S, const AreaDev& A, float& areaW) {
@@ -41,9 +33,8 @@ __device__ __forceinline__ int lightsCountOf(const SceneDev& S, const AreaDev& A
 // gen_nee's loadSurf<false> leaves them zero).
 template <bool GGX, bool AREA, bool HINTS, bool COMPACT>
 __device__ __forceinline__ void lightNeeLane(const SceneDev& S, const LightQueryDev& Q, const AreaDev& A) {
-  const uint32_t i = blockIdx.x * kWave + threadIdx.x;
-  const uint32_t n = itemCount(Q.cap, Q.count);
-  if (COMPACT ? (blockIdx.x * kWave >= n) : (i >= n)) return;  // (COMPACT: wave-uniform)
+  uint32_t i, n;
+  if (queryLanePast<COMPACT>(Q.range.cap, Q.range.count, i, n)) return;
   const bool act = i < n;
   bool emit = false;
   float4 q0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q1 = q0;
@@ -84,10 +75,10 @@ __device__ __forceinline__ void lightNeeLane(const SceneDev& S, const LightQuery
       // intensity) whatever the throughput and weight: such a value is not ±0, so it keeps bit 0, but no hint is tried.
       const bool positive = value.x > 0.0f || value.y > 0.0f || value.z > 0.0f;
       if (HINTS && positive && !area && S.sc->lights[lightToSample].type != BDPT_LIGHT_DIRECTIONAL &&
-          recOccludes(S, lightHint(S, lightToSample, ld3(S.sc->lights[lightToSample].posW), pos), pos, L, Q.minT, distToLight))
+          recOccludes(S, lightHint(S, lightToSample, ld3(S.sc->lights[lightToSample].posW), pos), pos, L, Q.range.minT, distToLight))
         status |= BDPT_LIGHT_STATUS_HINT_OCCLUDED;
       emit = status == BDPT_LIGHT_STATUS_NONZERO;
-      q0 = make_float4(pos.x, pos.y, pos.z, Q.minT);
+      q0 = make_float4(pos.x, pos.y, pos.z, Q.range.minT);
       q1 = make_float4(L.x, L.y, L.z, distToLight);
       q2 = make_float4(value.x, value.y, value.z, __uint_as_float((uint32_t)lightToSample | (status << 16)));
     }
@@ -96,29 +87,14 @@ __device__ __forceinline__ void lightNeeLane(const SceneDev& S, const LightQuery
     o[1] = q1;
     o[2] = q2;
   }
-  if (COMPACT) {
-    // one ballot + popcount prefix and one atomic per wave, as emitRay appends to the pass's ray queue
-    const unsigned long long mask = __ballot(emit);
-    if (mask == 0ull) return;
-    const int lane = (int)(threadIdx.x & 63u);
-    const int leader = __ffsll((long long)mask) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(Q.compactCount, (uint32_t)__popcll(mask));
-    base = (uint32_t)__shfl((int)base, leader);
-    const uint32_t at = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    if (emit && at < Q.cap) {  // (at < cap always when the caller zeroed the word: never write past the lists)
-      Q.compactRays[(size_t)at * 2] = q0;
-      Q.compactRays[(size_t)at * 2 + 1] = q1;
-      Q.compactItems[at] = i;
-    }
-  }
+  if (COMPACT) compactAppend(Q.compact, Q.range.cap, emit, i, q0, q1);
 }
 
 // bdpt_light_emit: three float4 per item, (org, tmin) (dir, 1e38) (colour, light); seedsOut = the pass's seedL
 template <bool AREA>
 __device__ __forceinline__ void lightEmitLane(const SceneDev& S, const LightQueryDev& Q, const AreaDev& A) {
-  const uint32_t i = blockIdx.x * kWave + threadIdx.x;
-  if (i >= itemCount(Q.cap, Q.count)) return;
+  uint32_t i;
+  if (queryLanePast(Q.range.cap, Q.range.count, i)) return;
   float areaW;
   const int lightsCount = lightsCountOf<AREA>(S, A, areaW);
   uint32_t seed = Q.seeds[i];
@@ -140,7 +116,7 @@ __device__ __forceinline__ void lightEmitLane(const SceneDev& S, const LightQuer
   }
   if (Q.seedsOut) Q.seedsOut[i] = seed;
   float4* o = Q.out + (size_t)i * 3;
-  o[0] = make_float4(pos.x, pos.y, pos.z, Q.minT);
+  o[0] = make_float4(pos.x, pos.y, pos.z, Q.range.minT);
   o[1] = make_float4(lightDir.x, lightDir.y, lightDir.z, 1e+38f);
   o[2] = make_float4(color.x, color.y, color.z, __uint_as_float((uint32_t)index));
 }
@@ -166,19 +142,9 @@ __global__ __launch_bounds__(kWave) void light_emit_area_kernel(SceneDev S, Ligh
   lightEmitLane<true>(S, Q, A);
 }
 
-namespace {
-template <class Fn>
-void withFlag(bool f, Fn&& fn) {
-  if (f)
-    fn(std::true_type{});
-  else
-    fn(std::false_type{});
-}
-}  // namespace
-
 void launchLightQuery(const SceneDev& S, const LightQueryDev& Q, const AreaDev& A, bool emitMode, bool ggx, bool hints, hipStream_t st) {
-  if (!Q.cap) return;
-  const uint32_t g = (uint32_t)(((uint64_t)Q.cap + kWave - 1) / kWave);
+  if (!Q.range.cap) return;
+  const uint32_t g = wavesFor(Q.range.cap);
   if (emitMode) {
     if (A.n)
       launchWave(light_emit_area_kernel, g, st, S, Q, A);
@@ -188,7 +154,7 @@ void launchLightQuery(const SceneDev& S, const LightQueryDev& Q, const AreaDev& 
   }
   withFlag(ggx, [&](auto GGX) {
     withFlag(hints, [&](auto HINTS) {
-      withFlag(Q.compactRays != nullptr, [&](auto COMPACT) {
+      withFlag(Q.compact.rays != nullptr, [&](auto COMPACT) {
         if (A.n)
           launchWave(light_nee_area_kernel<GGX, HINTS, COMPACT>, g, st, S, Q, A);
         else

@@ -11,6 +11,7 @@
 
 #include "device_math.hpp"
 #include "device_motion.hpp"
+#include "device_query.hpp"
 #include "device_trace.hpp"  // BDPT_ONE_WAVE_PER_GROUP
 #include "launch.hpp"
 
@@ -32,13 +33,8 @@ __global__ __launch_bounds__(kWave) void keep_pose_kernel(const float4* __restri
 __global__ __launch_bounds__(kWave) void motion_query_kernel(MotionDev M, uint32_t numTris, const float4* __restrict__ hits, uint32_t cap,
                                                              const uint32_t* count, float4* __restrict__ out) {
   BDPT_ONE_WAVE_PER_GROUP();
-  const uint32_t i = blockIdx.x * kWave + threadIdx.x;
-  uint32_t n = cap;
-  if (count) {  // (wave-uniform)
-    const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)*count);
-    n = c < cap ? c : cap;
-  }
-  if (i >= n) return;
+  uint32_t i;
+  if (queryLanePast(cap, count, i)) return;
   const float4 h = hits[i];
   const int prim = __float_as_int(h.w);
   if (prim < 0 || (uint32_t)prim >= numTris) {
@@ -48,8 +44,6 @@ __global__ __launch_bounds__(kWave) void motion_query_kernel(MotionDev M, uint32
   const f3 q = prevPosAtHit(M, (uint32_t)prim, h.y, h.z);
   out[i] = make_float4(q.x, q.y, q.z, 1.0f);
 }
-
-static uint32_t wavesFor(uint64_t n) { return (uint32_t)((n + kWave - 1) / kWave); }
 
 void launchKeepPose(const float4* shade, uint32_t numTris, float4* prevPose, hipStream_t st) {
   if (!numTris) return;

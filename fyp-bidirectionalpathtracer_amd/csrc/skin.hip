@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kWave) void skin_lds_kernel(SkinDev K, const float*
 
 template <bool N, bool B>
 static void launchSkinT(const SkinDev& K, const float* bones, const float* nbones, bool lds, hipStream_t st) {
-  const uint32_t chunks = (K.numVertices + kWave - 1) / kWave;
+  const uint32_t chunks = wavesFor(K.numVertices);
   if (lds)
     launchWave(skin_lds_kernel<N, B>, (chunks + kSkinLdsChunks - 1) / kSkinLdsChunks, st, K, bones, nbones);
   else

@@ -8,6 +8,7 @@
 #include "kernels.h"
 
 #include "device_math.hpp"
+#include "device_query.hpp"
 #include "device_scene.hpp"
 #include "device_trace.hpp"  // BDPT_ONE_WAVE_PER_GROUP
 #include "launch.hpp"
@@ -27,13 +28,6 @@ __global__ __launch_bounds__(kWave) void camera_rays_kernel(bdpt_camera cam, bdp
   rays[(size_t)i * 2 + 1] = make_float4(d.x, d.y, d.z, 1e+38f);
 }
 
-// The number of items a launch covers: min(*count, cap), or cap without a device word (wave-uniform).
-__device__ __forceinline__ uint32_t itemCount(uint32_t cap, const uint32_t* count) {
-  if (!count) return cap;
-  const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)*count);
-  return c < cap ? c : cap;
-}
-
 // bdpt_surface: six float4 per hit, (posW, dist) (N, linearRoughness) (V, IoR) (diffuse, opacity) (specular, material)
 // (emissive, prim).  A miss, or a prim outside the scene, writes prim -1, material 0xffffffff and zeros.
 template <bool NMAP>
@@ -41,8 +35,8 @@ __global__ __launch_bounds__(kWave) void shade_hits_kernel(SceneDev S, uint32_t 
                                                            const float4* __restrict__ hits, uint32_t cap, const uint32_t* count,
                                                            float4* __restrict__ out) {
   BDPT_ONE_WAVE_PER_GROUP();
-  const uint32_t i = blockIdx.x * kWave + threadIdx.x;
-  if (i >= itemCount(cap, count)) return;
+  uint32_t i;
+  if (queryLanePast(cap, count, i)) return;
   const float4 org = rays[(size_t)i * 2], h = hits[i];
   const int prim = __float_as_int(h.w);
   float4* o = out + (size_t)i * 6;
@@ -75,8 +69,8 @@ __global__ __launch_bounds__(kWave) void bsdf_query_kernel(const float4* __restr
                                                            bool fromLobe, const uint32_t* __restrict__ seeds,
                                                            const float4* __restrict__ dirs, float4* __restrict__ out) {
   BDPT_ONE_WAVE_PER_GROUP();
-  const uint32_t i = blockIdx.x * kWave + threadIdx.x;
-  if (i >= itemCount(cap, count)) return;
+  uint32_t i;
+  if (queryLanePast(cap, count, i)) return;
   const float4* r = surf + (size_t)i * 6;
   const int prim = __float_as_int(r[5].w);
   const float4 n = r[1], v = r[2], dif = r[3], spec = r[4];
@@ -97,35 +91,26 @@ __global__ __launch_bounds__(kWave) void bsdf_query_kernel(const float4* __restr
   }
 }
 
-static uint32_t gridFor(uint32_t n) { return (uint32_t)(((uint64_t)n + kWave - 1) / kWave); }
-
 void launchCameraRays(const bdpt_camera& cam, const bdpt_gbuffer_params& gp, uint32_t W, uint32_t H, float4* rays, hipStream_t st) {
   const uint32_t n = W * H;
   if (!n) return;
-  launchWave(camera_rays_kernel, gridFor(n), st, cam, gp, W, H, rays);
+  launchWave(camera_rays_kernel, wavesFor(n), st, cam, gp, W, H, rays);
 }
 
 void launchShadeHits(const SceneDev& S, uint32_t numTris, const float4* rays, const float4* hits, uint32_t cap, const uint32_t* count,
                      bool normalMap, float4* out, hipStream_t st) {
   if (!cap) return;
-  if (normalMap)
-    launchWave(shade_hits_kernel<true>, gridFor(cap), st, S, numTris, rays, hits, cap, count, out);
-  else
-    launchWave(shade_hits_kernel<false>, gridFor(cap), st, S, numTris, rays, hits, cap, count, out);
+  withFlag(normalMap, [&](auto NMAP) { launchWave(shade_hits_kernel<NMAP>, wavesFor(cap), st, S, numTris, rays, hits, cap, count, out); });
 }
 
 void launchBsdfQuery(const float4* surf, uint32_t cap, const uint32_t* count, bool eval, bool ggx, bool fromLobe, const uint32_t* seeds,
                      const float4* dirs, float4* out, hipStream_t st) {
   if (!cap) return;
-  const uint32_t g = gridFor(cap);
-  if (ggx && !eval)
-    launchWave(bsdf_query_kernel<true, false>, g, st, surf, cap, count, fromLobe, seeds, dirs, out);
-  else if (ggx)
-    launchWave(bsdf_query_kernel<true, true>, g, st, surf, cap, count, fromLobe, seeds, dirs, out);
-  else if (!eval)
-    launchWave(bsdf_query_kernel<false, false>, g, st, surf, cap, count, fromLobe, seeds, dirs, out);
-  else
-    launchWave(bsdf_query_kernel<false, true>, g, st, surf, cap, count, fromLobe, seeds, dirs, out);
+  withFlag(ggx, [&](auto GGX) {
+    withFlag(eval, [&](auto EVAL) {
+      launchWave(bsdf_query_kernel<GGX, EVAL>, wavesFor(cap), st, surf, cap, count, fromLobe, seeds, dirs, out);
+    });
+  });
 }
 
 }  // namespace bdpt

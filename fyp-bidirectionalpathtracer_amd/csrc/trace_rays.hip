@@ -12,6 +12,7 @@
 #include "kernels.h"
 
 #include "device_math.hpp"
+#include "device_query.hpp"
 #include "device_scene.hpp"
 #include "device_trace.hpp"
 #include "launch.hpp"
@@ -28,11 +29,7 @@ __global__ __launch_bounds__(kWave) void trace_rays_kernel(SceneDev S, const flo
   __shared__ int s_stack[kStackLds * kWave];
   int* stk = s_stack + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63u);
-  uint32_t n = cap;
-  if (count) {
-    const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)*count);
-    n = c < cap ? c : cap;
-  }
+  const uint32_t n = itemCount(cap, count);
   // rays per atomic: up to kFetchChunk, no more than a fair share per wave (a short list still spreads over the grid)
   const uint32_t share = (n / gridDim.x + kWave - 1) & ~(uint32_t)(kWave - 1);
   const uint32_t chunk = share < (uint32_t)kWave ? (uint32_t)kWave : (share > kFetchChunk ? kFetchChunk : share);
@@ -120,18 +117,12 @@ __global__ __launch_bounds__(kWave) void trace_rays_kernel(SceneDev S, const flo
 void launchTraceRays(const SceneDev& S, const float4* rays, uint32_t cap, const uint32_t* count, unsigned long long* cursor, int mode,
                      float4* hits, uint8_t* vis, LaunchGrids& G, int numCUs, hipStream_t st) {
   if (!cap) return;
-  const uint32_t need = (uint32_t)(((uint64_t)cap + kWave - 1) / kWave);
+  static constexpr decltype(&trace_rays_kernel<0>) kByMode[3] = {trace_rays_kernel<0>, trace_rays_kernel<1>, trace_rays_kernel<2>};
+  const auto kernel = kByMode[mode];
   uint32_t& g = G.rays[mode];
-  if (mode == 0) {
-    if (!g) g = persistentGrid(trace_rays_kernel<0>, numCUs);
-    launchWave(trace_rays_kernel<0>, g < need ? g : need, st, S, rays, cap, count, cursor, hits, vis);
-  } else if (mode == 1) {
-    if (!g) g = persistentGrid(trace_rays_kernel<1>, numCUs);
-    launchWave(trace_rays_kernel<1>, g < need ? g : need, st, S, rays, cap, count, cursor, hits, vis);
-  } else {
-    if (!g) g = persistentGrid(trace_rays_kernel<2>, numCUs);
-    launchWave(trace_rays_kernel<2>, g < need ? g : need, st, S, rays, cap, count, cursor, hits, vis);
-  }
+  if (!g) g = persistentGrid(kernel, numCUs);
+  const uint32_t need = wavesFor(cap);
+  launchWave(kernel, g < need ? g : need, st, S, rays, cap, count, cursor, hits, vis);
 }
 
 }  // namespace bdpt

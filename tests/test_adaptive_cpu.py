@@ -4,41 +4,23 @@ that nothing a GPU would need is involved."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
+
+from binding_fakes import RecordingLib, context_without_device, header_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _header_layout():
-    """sizeof / offsetof of the two adaptive structures as a C compiler lays out include/bdpt.h."""
-    src = r'''
-#include <stddef.h>
-#include <stdio.h>
-#include "bdpt.h"
-#define F(T, m) printf(#T "." #m " %zu\n", offsetof(T, m));
-int main(void) {
-  printf("bdpt_adaptive_state %zu\nbdpt_adaptive_params %zu\n", sizeof(bdpt_adaptive_state), sizeof(bdpt_adaptive_params));
-  F(bdpt_adaptive_state, mean) F(bdpt_adaptive_state, m2) F(bdpt_adaptive_state, count) F(bdpt_adaptive_state, mask)
-  F(bdpt_adaptive_state, active)
-  F(bdpt_adaptive_params, threshold) F(bdpt_adaptive_params, epsilon) F(bdpt_adaptive_params, minSamples)
-  F(bdpt_adaptive_params, maxSamples) F(bdpt_adaptive_params, blockSize)
-  return 0;
+STRUCTS = {
+    "bdpt_adaptive_state": ["mean", "m2", "count", "mask", "active"],
+    "bdpt_adaptive_params": ["threshold", "epsilon", "minSamples", "maxSamples", "blockSize"],
 }
-'''
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        open(c, "w").write(src)
-        subprocess.run(["g++", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-o", exe, c], check=True)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    return dict(re.findall(r"^(\S+) (.+)$", out, flags=re.M))
 
 
 def test_adaptive_structs_match_the_header(pkg):
     a = pkg.abi
-    lay = _header_layout()
+    lay = header_layout(STRUCTS, lang="c++")
     assert int(lay["bdpt_adaptive_state"]) == C.sizeof(a.AdaptiveState) == 40
     assert int(lay["bdpt_adaptive_params"]) == C.sizeof(a.AdaptiveParams) == 20
     for cls, cname in ((a.AdaptiveState, "bdpt_adaptive_state"), (a.AdaptiveParams, "bdpt_adaptive_params")):
@@ -81,33 +63,14 @@ def test_adaptive_params_refuses_bad_settings(pkg, bad, match):
         pkg.adaptive_params(bad)
 
 
-class _RecordingLib:
-    """Stands in for libbdpt_amd.so: records what the adaptive entry points are handed."""
-
-    def __init__(self):
-        self.calls = []
-
-    def bdpt_adaptive_update(self, h, params, state, frame, stream):
-        p = params._obj
-        self.calls.append(("update", p.threshold, p.epsilon, p.minSamples, p.maxSamples, p.blockSize, state._obj.mean, frame))
-        return 0
-
-    def bdpt_adaptive_reset(self, h, state, stream):
-        self.calls.append(("reset", state._obj.mask))
-        return 0
-
-    def bdpt_execute_masked(self, h, params, gb, mask, out, stream):
-        self.calls.append(("masked", mask, out))
-        return 0
-
-    def bdpt_last_error(self, h):
-        return b"recorded"
-
-
 def _fake_context(pkg):
-    ctx = pkg.Context.__new__(pkg.Context)
-    ctx._lib, ctx._h, ctx.device = _RecordingLib(), C.c_void_p(1), 0
-    return ctx
+    """a Context whose library records what the adaptive entry points are handed"""
+    return context_without_device(pkg, RecordingLib({
+        "bdpt_adaptive_update": lambda p, state, frame, stream: ("update", p.threshold, p.epsilon, p.minSamples, p.maxSamples,
+                                                                 p.blockSize, state.mean, frame),
+        "bdpt_adaptive_reset": lambda state, stream: ("reset", state.mask),
+        "bdpt_execute_masked": lambda params, gb, mask, out, stream: ("masked", mask, out),
+    }, last_error=b"recorded"))
 
 
 def test_context_passes_dict_params_and_pointers(pkg):

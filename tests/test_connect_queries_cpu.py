@@ -2,17 +2,11 @@
 constants against include/bdpt.h, and the Python binding's argument checks against a fake library, so that nothing a GPU
 would need is involved."""
 import ctypes as C
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from test_trace_rays_cpu import FakeGpuTensor
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from binding_fakes import FakeGpuTensor, RecordingLib, context_without_device, desc_fields, header_layout
 
 STRUCTS = {
     "bdpt_connect_sample": ("ConnectSample", ["ray", "value", "status"]),
@@ -25,25 +19,9 @@ STRUCTS = {
 CONSTS = ["BDPT_CONNECT_VERTICES", "BDPT_CONNECT_CAMERA", "BDPT_CONNECT_STATUS_NONZERO", "BDPT_CONNECT_STATUS_PIXEL"]
 
 
-def _header_layout():
-    """sizeof / offsetof of the new structures and the constants as a C compiler reads include/bdpt.h."""
-    lines = []
-    for cname, (_, fields) in STRUCTS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f in fields]
-    lines += [f'printf("{c} %u\\n", (unsigned){c});' for c in CONSTS]
-    src = ('#include <stddef.h>\n#include <stdio.h>\n#include "bdpt.h"\nint main(void) {\n' + "\n".join(lines) + '\nreturn 0;\n}\n')
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        open(c, "w").write(src)
-        subprocess.run(["gcc", "-x", "c", "-I", os.path.join(ROOT, "include"), "-o", exe, c], check=True)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    return dict(re.findall(r"^(\S+) (.+)$", out, flags=re.M))
-
-
 def test_connect_structs_match_the_header(pkg):
     a = pkg.abi
-    lay = _header_layout()
+    lay = header_layout({c: f for c, (_, f) in STRUCTS.items()}, {c: [c] for c in CONSTS})
     assert int(lay["bdpt_connect_sample"]) == C.sizeof(a.ConnectSample) == 48  # three float4
     assert int(lay["bdpt_camera_sample"]) == C.sizeof(a.CameraSample) == 64    # four float4
     for cname, (pyname, fields) in STRUCTS.items():
@@ -65,31 +43,10 @@ def test_the_prototypes_are_declared(pkg):
     assert a.PROTOTYPES["bdpt_splat_add"] == (C.c_int, [C.c_void_p, C.POINTER(a.SplatDesc), C.c_void_p])
 
 
-class _RecordingLib:
-    """Stands in for libbdpt_amd.so: records what the two entry points are handed."""
-
-    def __init__(self):
-        self.calls = []
-
-    def _record(self, desc):
-        d = desc._obj
-        self.calls.append({n: (list(getattr(d, n)) if n == "pixelJitter" else getattr(d, n)) for n, _ in d._fields_})
-        return 0
-
-    def bdpt_connect_query(self, h, desc, stream):
-        return self._record(desc)
-
-    def bdpt_splat_add(self, h, desc, stream):
-        return self._record(desc)
-
-    def bdpt_last_error(self, h):
-        return b""
-
-
 def _context_without_device(pkg, device=0):
-    ctx = pkg.Context.__new__(pkg.Context)
-    ctx._lib, ctx._h, ctx.device = _RecordingLib(), C.c_void_p(1), device
-    return ctx
+    """a Context whose library records what the two entry points are handed"""
+    record = lambda d, stream: desc_fields(d)  # noqa: E731
+    return context_without_device(pkg, RecordingLib({"bdpt_connect_query": record, "bdpt_splat_add": record}), device)
 
 
 def test_good_calls_reach_the_library(pkg):

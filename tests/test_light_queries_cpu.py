@@ -2,17 +2,12 @@
 include/bdpt.h, and the Python binding's argument checks against a fake library, so that nothing a GPU would need is
 involved."""
 import ctypes as C
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from test_trace_rays_cpu import FakeGpuTensor, _FakeOut, _NullContext
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from binding_fakes import (FakeGpuTensor, RecordingLib, _FakeOut, _NullContext, context_without_device, desc_fields,
+                           header_layout)
 
 STRUCTS = {
     "bdpt_light_sample": ("LightSample", ["ray", "value", "light", "status"]),
@@ -24,25 +19,9 @@ CONSTS = ["BDPT_LIGHT_NEE", "BDPT_LIGHT_EMIT", "BDPT_LIGHT_USE_HINTS", "BDPT_LIG
           "BDPT_PARAM_AREA_LIGHTS"]
 
 
-def _header_layout():
-    """sizeof / offsetof of the new structures and the constants as a C compiler reads include/bdpt.h."""
-    lines = []
-    for cname, (_, fields) in STRUCTS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f in fields]
-    lines += [f'printf("{c} %u\\n", (unsigned){c});' for c in CONSTS]
-    src = ('#include <stddef.h>\n#include <stdio.h>\n#include "bdpt.h"\nint main(void) {\n' + "\n".join(lines) + '\nreturn 0;\n}\n')
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        open(c, "w").write(src)
-        subprocess.run(["gcc", "-x", "c", "-I", os.path.join(ROOT, "include"), "-o", exe, c], check=True)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    return dict(re.findall(r"^(\S+) (.+)$", out, flags=re.M))
-
-
 def test_light_structs_match_the_header(pkg):
     a = pkg.abi
-    lay = _header_layout()
+    lay = header_layout({c: f for c, (_, f) in STRUCTS.items()}, {c: [c] for c in CONSTS})
     assert int(lay["bdpt_light_sample"]) == C.sizeof(a.LightSample) == 48  # three float4
     assert int(lay["bdpt_light_emit"]) == C.sizeof(a.LightEmit) == 48
     for cname, (pyname, fields) in STRUCTS.items():
@@ -64,25 +43,9 @@ def test_the_prototype_is_declared(pkg):
     assert a.PROTOTYPES["bdpt_light_query"] == (C.c_int, [C.c_void_p, C.POINTER(a.LightDesc), C.c_void_p])
 
 
-class _RecordingLib:
-    """Stands in for libbdpt_amd.so: records what bdpt_light_query is handed."""
-
-    def __init__(self):
-        self.calls = []
-
-    def bdpt_light_query(self, h, desc, stream):
-        d = desc._obj
-        self.calls.append({n: getattr(d, n) for n, _ in d._fields_})
-        return 0
-
-    def bdpt_last_error(self, h):
-        return b""
-
-
 def _context_without_device(pkg, device=0):
-    ctx = pkg.Context.__new__(pkg.Context)
-    ctx._lib, ctx._h, ctx.device = _RecordingLib(), C.c_void_p(1), device
-    return ctx
+    """a Context whose library records what bdpt_light_query is handed"""
+    return context_without_device(pkg, RecordingLib({"bdpt_light_query": lambda d, stream: desc_fields(d)}), device)
 
 
 def test_good_calls_reach_the_library(pkg):

@@ -3,33 +3,18 @@ bdpt_motion_query, bdpt_bmfr_execute_motion): the library's symbols, the ctypes 
 codes that need no GPU, and the C++ host's channel and switch.  The kernels are tested on the GPU by tests/test_motion.py."""
 import ctypes as C
 import os
-import re
 import subprocess
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from binding_fakes import header_layout
 
 FIELDS = ["hits", "num", "reserved", "numDevice", "prevPositions"]
 SYMBOLS = ["bdpt_keep_pose", "bdpt_gbuffer_execute_motion", "bdpt_motion_query", "bdpt_bmfr_execute_motion"]
 
 
-def _header_layout():
-    """sizeof / offsetof of bdpt_motion_desc, and the untouched bdpt_bmfr_params, as a C compiler reads include/bdpt.h"""
-    lines = ['printf("bdpt_motion_desc %zu\\n", sizeof(bdpt_motion_desc));', 'printf("bdpt_bmfr_params %zu\\n", sizeof(bdpt_bmfr_params));']
-    lines += [f'printf("bdpt_motion_desc.{f} %zu\\n", offsetof(bdpt_motion_desc, {f}));' for f in FIELDS]
-    src = ('#include <stddef.h>\n#include <stdio.h>\n#include "bdpt.h"\nint main(void) {\n' + "\n".join(lines) +
-           '\nprintf("consts %u\\n", BDPT_PREPARE_MOTION);\nreturn 0;\n}\n')
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        open(c, "w").write(src)
-        subprocess.run(["gcc", "-x", "c", "-I", os.path.join(ROOT, "include"), "-o", exe, c], check=True)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    return dict(re.findall(r"^(\S+) (.+)$", out, flags=re.M))
-
-
 def test_motion_symbols_and_struct_match_the_header(pkg):
     a, lib = pkg.abi, pkg.load_library()
-    lay = _header_layout()
+    lay = header_layout({"bdpt_motion_desc": FIELDS, "bdpt_bmfr_params": []}, {"consts": ["BDPT_PREPARE_MOTION"]})
     assert int(lay["bdpt_motion_desc"]) == C.sizeof(a.MotionDesc) == 32
     assert [n for n, _ in a.MotionDesc._fields_] == FIELDS
     for f in FIELDS:

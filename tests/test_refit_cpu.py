@@ -8,6 +8,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import binding_fakes as fakes
+from binding_fakes import RecordingLib, context_without_device
+
 
 def positions_of(desc):
     return np.ctypeslib.as_array(desc.positions, shape=(desc.numVertices, 3)).copy()
@@ -183,28 +186,10 @@ def test_new_entry_points_have_their_declared_layouts(pkg):
     assert (pkg.abi.MEMORY_HOST, pkg.abi.MEMORY_DEVICE) == (0, 1)
 
 
-class _RecordingLib:
-    """Stands in for the library behind a Context: records what bdpt_update_geometry was handed."""
-
-    def __init__(self):
-        self.calls = []
-
-    def bdpt_update_geometry(self, h, u, stream):
-        g = u._obj
-        self.calls.append((g.memory, g.positions, g.normals, g.numVertices))
-        return 0
-
-    def bdpt_last_error(self, h):
-        return b""
-
-    def bdpt_destroy(self, h):
-        pass
-
-
 def _context_without_device(pkg, device=0):
-    ctx = pkg.Context.__new__(pkg.Context)
-    ctx._lib, ctx._h, ctx.device = _RecordingLib(), C.c_void_p(1), device
-    return ctx
+    """a Context whose library records what bdpt_update_geometry was handed"""
+    return context_without_device(pkg, RecordingLib({"bdpt_update_geometry": lambda g, stream: (g.memory, g.positions, g.normals,
+                                                                                                g.numVertices)}), device)
 
 
 def test_update_geometry_never_hands_host_memory_to_the_device_path(pkg):
@@ -226,22 +211,8 @@ def test_update_geometry_never_hands_host_memory_to_the_device_path(pkg):
     with pytest.raises(pkg.BdptError):
         ctx.update_geometry(np.ones(10, np.float32))  # not numVertices x 3
 
-    class FakeGpuTensor:  # what a GPU tensor looks like to the binding
-        is_cuda = True
-
-        def __init__(self, index):
-            self.device = torch.device("cuda", index)
-
-        def is_contiguous(self):
-            return True
-
-        dtype = torch.float32
-
-        def numel(self):
-            return 12
-
-        def data_ptr(self):
-            return 0x1000
+    def FakeGpuTensor(index):  # four positions in GPU memory
+        return fakes.FakeGpuTensor((4, 3), torch.float32, index, ptr=0x1000)
 
     with pytest.raises(pkg.BdptError):
         ctx.update_geometry(FakeGpuTensor(1))  # another GPU's memory

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 import skin_numpy as sn
+import binding_fakes as fakes
+from binding_fakes import RecordingLib, context_without_device
 
 
 def _soup_rig(pkg, seed, num_triangles, num_bones, **kw):
@@ -136,33 +138,17 @@ def test_host_skin_error_codes(pkg):
         assert call(sn.skin_desc(a, P, W2, I, 4, N, B)) == -1
 
 
-class _RecordingLib:
-    """Stands in for the library behind a Context: records what bdpt_update_skinned and bdpt_set_skin were handed."""
-
-    def __init__(self):
-        self.calls = []
-        self.skins = []
-
-    def bdpt_update_skinned(self, h, u, stream):
-        g = u._obj
-        self.calls.append((g.memory, g.bones, g.normalBones, g.numBones, g.flags))
-        return 0
-
-    def bdpt_set_skin(self, h, d):
-        self.skins.append(None if d is None else (d._obj.numVertices, d._obj.numBones, d._obj.normals, d._obj.bitangents))
-        return 0
-
-    def bdpt_last_error(self, h):
-        return b""
-
-    def bdpt_destroy(self, h):
-        pass
-
-
 def _context_without_device(pkg, device=0):
-    ctx = pkg.Context.__new__(pkg.Context)
-    ctx._lib, ctx._h, ctx.device = _RecordingLib(), C.c_void_p(1), device
-    return ctx
+    """a Context whose library records what bdpt_update_skinned (.calls) and bdpt_set_skin (.skins) were handed"""
+    lib = RecordingLib({"bdpt_update_skinned": lambda g, stream: (g.memory, g.bones, g.normalBones, g.numBones, g.flags)})
+    lib.skins = []
+
+    def set_skin(h, d):
+        lib.skins.append(None if d is None else (d._obj.numVertices, d._obj.numBones, d._obj.normals, d._obj.bitangents))
+        return 0
+
+    lib.bdpt_set_skin = set_skin
+    return context_without_device(pkg, lib, device)
 
 
 def test_update_skinned_picks_the_host_or_the_device_path(pkg):
@@ -182,22 +168,8 @@ def test_update_skinned_picks_the_host_or_the_device_path(pkg):
     with pytest.raises(pkg.BdptError):
         ctx.update_skinned(np.ones(20, np.float32))  # not numBones x 16
 
-    class FakeGpuTensor:  # what a GPU tensor looks like to the binding
-        is_cuda = True
-        dtype = torch.float32
-
-        def __init__(self, index, contiguous=True):
-            self.device = torch.device("cuda", index)
-            self._c = contiguous
-
-        def is_contiguous(self):
-            return self._c
-
-        def numel(self):
-            return 48
-
-        def data_ptr(self):
-            return 0x2000
+    def FakeGpuTensor(index, contiguous=True):  # a palette of three bones in GPU memory
+        return fakes.FakeGpuTensor((3, 16), torch.float32, index, contiguous, ptr=0x2000)
 
     with pytest.raises(pkg.BdptError):
         ctx.update_skinned(FakeGpuTensor(1))  # another GPU's memory

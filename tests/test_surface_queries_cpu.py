@@ -2,17 +2,11 @@
 against include/bdpt.h, and the Python binding's argument checks against a fake library, so that nothing a GPU would need
 is involved."""
 import ctypes as C
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from test_trace_rays_cpu import FakeGpuTensor, _FakeOut, _NullContext
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from binding_fakes import FakeGpuTensor, RecordingLib, _FakeOut, _NullContext, context_without_device, header_layout
 
 STRUCTS = {
     "bdpt_surface": ("Surface", ["posW", "dist", "N", "linearRoughness", "V", "IoR", "diffuse", "opacity", "specular", "material",
@@ -24,25 +18,9 @@ STRUCTS = {
 }
 
 
-def _header_layout():
-    """sizeof / offsetof of the new structures as a C compiler lays out include/bdpt.h."""
-    lines = []
-    for cname, (_, fields) in STRUCTS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f in fields]
-    src = ('#include <stddef.h>\n#include <stdio.h>\n#include "bdpt.h"\nint main(void) {\n' + "\n".join(lines) +
-           '\nprintf("consts %u %u %u\\n", BDPT_SHADE_NORMAL_MAP, BDPT_BSDF_SAMPLE, BDPT_BSDF_EVAL);\nreturn 0;\n}\n')
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        open(c, "w").write(src)
-        subprocess.run(["gcc", "-x", "c", "-I", os.path.join(ROOT, "include"), "-o", exe, c], check=True)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    return dict(re.findall(r"^(\S+) (.+)$", out, flags=re.M))
-
-
 def test_surface_structs_match_the_header(pkg):
     a = pkg.abi
-    lay = _header_layout()
+    lay = header_layout({c: f for c, (_, f) in STRUCTS.items()}, {"consts": ["BDPT_SHADE_NORMAL_MAP", "BDPT_BSDF_SAMPLE", "BDPT_BSDF_EVAL"]})
     assert int(lay["bdpt_surface"]) == C.sizeof(a.Surface) == 96
     assert int(lay["bdpt_bsdf_sample"]) == C.sizeof(a.BsdfSample) == 32
     for cname, (pyname, fields) in STRUCTS.items():
@@ -56,36 +34,16 @@ def test_surface_structs_match_the_header(pkg):
         assert n in a.PROTOTYPES
 
 
-class _RecordingLib:
-    """Stands in for libbdpt_amd.so: records what the three entry points are handed."""
-
-    def __init__(self):
-        self.calls = []
-
-    def bdpt_camera_rays(self, h, gp, w, hh, rays, stream):
-        self.calls.append(dict(fn="camera_rays", w=w, h=hh, rays=rays))
-        return 0
-
-    def bdpt_shade_hits(self, h, desc, stream):
-        d = desc._obj
-        self.calls.append(dict(fn="shade_hits", rays=d.rays, hits=d.hits, n=d.numHits, flags=d.flags, count=d.numHitsDevice,
-                               out=d.surfaces))
-        return 0
-
-    def bdpt_bsdf_query(self, h, desc, stream):
-        d = desc._obj
-        self.calls.append(dict(fn="bsdf", surfaces=d.surfaces, n=d.num, mode=d.mode, count=d.numDevice, mat=d.matIndex,
-                               flags=d.flags, seeds=d.seeds, samples=d.samples, dirs=d.dirs, values=d.values))
-        return 0
-
-    def bdpt_last_error(self, h):
-        return b""
-
-
 def _context_without_device(pkg, device=0):
-    ctx = pkg.Context.__new__(pkg.Context)
-    ctx._lib, ctx._h, ctx.device = _RecordingLib(), C.c_void_p(1), device
-    return ctx
+    """a Context whose library records what the three entry points are handed"""
+    return context_without_device(pkg, RecordingLib({
+        "bdpt_camera_rays": lambda gp, w, hh, rays, stream: dict(fn="camera_rays", w=w, h=hh, rays=rays),
+        "bdpt_shade_hits": lambda d, stream: dict(fn="shade_hits", rays=d.rays, hits=d.hits, n=d.numHits, flags=d.flags,
+                                                  count=d.numHitsDevice, out=d.surfaces),
+        "bdpt_bsdf_query": lambda d, stream: dict(fn="bsdf", surfaces=d.surfaces, n=d.num, mode=d.mode, count=d.numDevice,
+                                                  mat=d.matIndex, flags=d.flags, seeds=d.seeds, samples=d.samples, dirs=d.dirs,
+                                                  values=d.values),
+    }), device)
 
 
 def test_good_calls_reach_the_library(pkg):

@@ -1,45 +1,23 @@
 """CPU checks of bdpt_trace_rays' interface: the ctypes structures against include/bdpt.h, and the Python binding's
 argument checks (Context.trace_rays) against a fake library, so that nothing a GPU would need is involved."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from binding_fakes import FakeGpuTensor, RecordingLib, _FakeOut, _NullContext, context_without_device, header_layout
 
-
-def _header_layout():
-    """sizeof / offsetof of the three structures as a C compiler lays out include/bdpt.h."""
-    src = r'''
-#include <stddef.h>
-#include <stdio.h>
-#include "bdpt.h"
-#define F(T, m) printf(#T "." #m " %zu\n", offsetof(T, m));
-int main(void) {
-  printf("bdpt_ray %zu\nbdpt_hit %zu\nbdpt_trace_desc %zu\n", sizeof(bdpt_ray), sizeof(bdpt_hit), sizeof(bdpt_trace_desc));
-  F(bdpt_ray, org) F(bdpt_ray, tmin) F(bdpt_ray, dir) F(bdpt_ray, tmax)
-  F(bdpt_hit, t) F(bdpt_hit, u) F(bdpt_hit, v) F(bdpt_hit, prim)
-  F(bdpt_trace_desc, rays) F(bdpt_trace_desc, numRays) F(bdpt_trace_desc, mode) F(bdpt_trace_desc, numRaysDevice)
-  F(bdpt_trace_desc, hits) F(bdpt_trace_desc, visible)
-  printf("modes %u %u %u\n", BDPT_TRACE_CLOSEST, BDPT_TRACE_CLOSEST_CULL_BACK, BDPT_TRACE_ANY);
-  return 0;
+STRUCTS = {
+    "bdpt_ray": ["org", "tmin", "dir", "tmax"],
+    "bdpt_hit": ["t", "u", "v", "prim"],
+    "bdpt_trace_desc": ["rays", "numRays", "mode", "numRaysDevice", "hits", "visible"],
 }
-'''
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        open(c, "w").write(src)
-        subprocess.run(["g++", "-x", "c++", "-I", os.path.join(ROOT, "include"), "-o", exe, c], check=True)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    return dict(re.findall(r"^(\S+) (.+)$", out, flags=re.M))
 
 
 def test_trace_structs_match_the_header(pkg):
     a = pkg.abi
-    lay = _header_layout()
+    lay = header_layout(STRUCTS, {"modes": ["BDPT_TRACE_CLOSEST", "BDPT_TRACE_CLOSEST_CULL_BACK", "BDPT_TRACE_ANY"]},
+                        lang="c++")
     assert int(lay["bdpt_ray"]) == C.sizeof(a.Ray) == 32
     assert int(lay["bdpt_hit"]) == C.sizeof(a.Hit) == 16
     assert int(lay["bdpt_trace_desc"]) == C.sizeof(a.TraceDesc)
@@ -50,54 +28,10 @@ def test_trace_structs_match_the_header(pkg):
     assert "bdpt_trace_rays" in a.PROTOTYPES
 
 
-class _RecordingLib:
-    """Stands in for libbdpt_amd.so: records what bdpt_trace_rays is handed."""
-
-    def __init__(self):
-        self.calls = []
-
-    def bdpt_trace_rays(self, h, desc, stream):
-        d = desc._obj
-        self.calls.append(dict(rays=d.rays, numRays=d.numRays, mode=d.mode, count=d.numRaysDevice, hits=d.hits,
-                               visible=d.visible))
-        return 0
-
-    def bdpt_last_error(self, h):
-        return b""
-
-
 def _context_without_device(pkg, device=0):
-    ctx = pkg.Context.__new__(pkg.Context)
-    ctx._lib, ctx._h, ctx.device = _RecordingLib(), C.c_void_p(1), device
-    return ctx
-
-
-class FakeGpuTensor:
-    """What a GPU tensor looks like to the binding (no GPU needed)."""
-    is_cuda = True
-
-    def __init__(self, shape, dtype, index=0, contiguous=True, ptr=0x10000):
-        import torch
-        self.shape, self.dtype, self.device = tuple(shape), dtype, torch.device("cuda", index)
-        self._contiguous, self._ptr = contiguous, ptr
-
-    def is_contiguous(self):
-        return self._contiguous
-
-    def dim(self):
-        return len(self.shape)
-
-    def numel(self):
-        return int(np.prod(self.shape))
-
-    def data_ptr(self):
-        return self._ptr
-
-    def view(self, dtype):
-        return self
-
-    def __getitem__(self, k):
-        return self
+    """a Context whose library records what bdpt_trace_rays is handed"""
+    return context_without_device(pkg, RecordingLib({"bdpt_trace_rays": lambda d, stream: dict(
+        rays=d.rays, numRays=d.numRays, mode=d.mode, count=d.numRaysDevice, hits=d.hits, visible=d.visible)}), device)
 
 
 def test_host_rays_never_reach_the_library_as_device_pointers(pkg, monkeypatch):
@@ -134,25 +68,6 @@ def test_host_rays_never_reach_the_library_as_device_pointers(pkg, monkeypatch):
     assert len(ctx._lib.calls) == 2
 
 
-class _NullContext:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-class _FakeOut(FakeGpuTensor):
-    def __init__(self, shape, dtype):
-        super().__init__(shape, dtype, ptr=0x90000)
-
-    def cpu(self):
-        return self
-
-    def numpy(self):
-        return np.zeros(self.shape, np.uint8)
-
-
 def test_bad_arguments_are_refused_before_the_library(pkg):
     import torch
     ctx = _context_without_device(pkg)
@@ -165,6 +80,9 @@ def test_bad_arguments_are_refused_before_the_library(pkg):
     ctx.trace_rays(good, mode="closest_cull_back", out=FakeGpuTensor((64, 4), torch.int32, ptr=0x30000),
                    count=FakeGpuTensor((1,), torch.uint32, ptr=0x50000))
     assert ctx._lib.calls[-1]["mode"] == pkg.abi.TRACE_CLOSEST_CULL_BACK
+    for shape in ((), (1, 1)):  # any one-element count, not only (1,)
+        ctx.trace_rays(good, out=FakeGpuTensor((64, 4), torch.float32), count=FakeGpuTensor(shape, torch.int32, ptr=0x50000))
+        assert ctx._lib.calls[-1]["count"] == 0x50000
     calls = len(ctx._lib.calls)
     bad = [
         dict(rays=FakeGpuTensor((64, 8), torch.float32, index=1)),                         # another GPU

@@ -89,7 +89,8 @@ def main():
         # a moved scene: the previous pose stays the scene as loaded
         P = np.ctypeslib.as_array(d.positions, shape=(int(d.numVertices), 3)).astype(np.float32)
         ext = float(np.max(P.max(axis=0) - P.min(axis=0)))
-        moved = torch.from_numpy(P + np.float32(0.002 * ext) * np.sin(P[:, [1, 2, 0]] * np.float32(40.0 / ext))).cuda()
+        moved = P + np.float32(0.002 * ext) * np.sin(P[:, [1, 2, 0]] * np.float32(40.0 / ext))
+        moved = torch.from_numpy(np.ascontiguousarray(moved, dtype=np.float32)).cuda()  # (the fancy index is not C-ordered)
         pipe.ctx.update_geometry(moved, stream=sp, keep_light_maps=True)
         gp = pipe.gbuffer_params()
         prev = C.c_void_p(pipe.prev_position.data_ptr())
