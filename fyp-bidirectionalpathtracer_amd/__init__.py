@@ -126,6 +126,17 @@ def camera_view_proj(pos, target, up, focal_length_mm=21.0, frame_height_mm=24.0
     return list(out)
 
 
+def view_proj_of_camera(cam, near=0.1, far=1000.0):
+    """camera_view_proj for an abi.Camera as bdpt_camera_look_at makes it: looking along cameraW with cameraV up,
+    tan(fovY / 2) = |cameraV| / |cameraW|, aspect = |cameraU| / |cameraV|."""
+    import math
+    length = lambda v: math.sqrt(sum(float(x) * float(x) for x in v))
+    pos = [float(x) for x in cam.posW]
+    u, v, w = length(cam.cameraU), length(cam.cameraV), length(cam.cameraW)
+    return camera_view_proj(pos, [pos[i] + float(cam.cameraW[i]) for i in range(3)], list(cam.cameraV), 12.0 * w / v, 24.0, u / v,
+                            near, far)
+
+
 def msaa_jitter(counter_before_increment):
     j = (C.c_float * 2)()
     load_library().bdpt_msaa_jitter(counter_before_increment & 0xFFFFFFFF, j)
@@ -714,10 +725,12 @@ class Context:
 
     def resize(self, width, height, y0, y1, max_depth):
         self._check(self._lib.bdpt_resize(self._h, width, height, Tile(y0, y1), max_depth), "bdpt_resize")
+        self._frame = (int(height), int(width))
 
     def resize_stripes(self, width, height, stripe_rows, num_owners, owner, max_depth):
         self._check(self._lib.bdpt_resize_stripes(self._h, width, height, Stripes(stripe_rows, num_owners, owner), max_depth),
                     "bdpt_resize_stripes")
+        self._frame = (int(height), int(width))
 
     def tile_info(self):
         info = TileInfo()
@@ -826,6 +839,55 @@ class Context:
 
     def bmfr_reset(self):
         self._check(self._lib.bdpt_bmfr_reset(self._h), "bdpt_bmfr_reset")
+
+    def bmfr_planes_prepare(self, n):
+        """bdpt_bmfr_planes_prepare: allocate the plane history of bmfr_execute_planes for `n` planes and reset it."""
+        self._check(self._lib.bdpt_bmfr_planes_prepare(self._h, int(n)), "bdpt_bmfr_planes_prepare")
+
+    def bmfr_planes_reset(self):
+        self._check(self._lib.bdpt_bmfr_planes_reset(self._h), "bdpt_bmfr_planes_reset")
+
+    def bmfr_execute_planes(self, params, gbuffer, planes, prev_position=None, stream=None):
+        """bdpt_bmfr_execute_planes: denoise the images of `planes` in place, each to the bits bmfr_execute would give it on
+        a context of its own, with the geometry tests and the fit's factorisation done once (contract in include/bdpt.h
+        "Denoised planes").  `planes`: a (P, H, W, 4) float32 GPU tensor or a sequence of (H, W, 4) float32 GPU tensors, all
+        of one shape, P = 1 .. abi.BMFR_MAX_PLANES; list position k owns history slot k.  `prev_position`: an (H, W, 4)
+        float32 GPU tensor, the channel of bmfr_execute_motion, or None."""
+        import torch
+        what = "bmfr_execute_planes"
+        if getattr(planes, "is_cuda", False) and hasattr(planes, "dim"):
+            if planes.dim() != 4 or planes.shape[3] != 4:
+                raise BdptError(f"{what}: planes must be (P, H, W, 4) float32, not {tuple(planes.shape)} {planes.dtype}")
+            self._check_gpu(planes, what, "planes", tuple(planes.shape), (torch.float32,))
+            count, frame = int(planes.shape[0]), tuple(planes.shape[1:])
+            stride = frame[0] * frame[1] * 16
+            ptrs = [planes.data_ptr() + k * stride for k in range(count)]
+        else:
+            try:
+                items = list(planes)
+            except TypeError:
+                raise BdptError(f"{what}: planes must be a (P, H, W, 4) GPU tensor or a sequence of (H, W, 4) GPU tensors") from None
+            count = len(items)
+            frame = tuple(getattr(items[0], "shape", ())) if items else ()
+            if count and (len(frame) != 3 or frame[2] != 4):
+                raise BdptError(f"{what}: planes[0] must be (H, W, 4) float32, not {frame}")
+            for k, t in enumerate(items):
+                self._check_gpu(t, what, f"planes[{k}]", frame, (torch.float32,))
+            ptrs = [t.data_ptr() for t in items]
+        if not 1 <= count <= abi.BMFR_MAX_PLANES:
+            raise BdptError(f"{what}: 1 .. {abi.BMFR_MAX_PLANES} planes, not {count}")
+        size = getattr(self, "_frame", None)  # (set by resize / resize_stripes)
+        if size is not None and frame != size + (4,):
+            raise BdptError(f"{what}: the planes must be whole frames, {size + (4,)}, not {frame}")
+        if prev_position is not None:
+            self._check_gpu(prev_position, what, "prev_position", frame, (torch.float32,))
+        arr = (C.c_void_p * count)(*ptrs)
+        d = abi.BmfrPlanesDesc()
+        d.planes = C.cast(arr, C.POINTER(C.c_void_p))
+        d.numPlanes = count
+        d.prevPosition = None if prev_position is None else prev_position.data_ptr()
+        self._check(self._lib.bdpt_bmfr_execute_planes(self._h, C.byref(params), C.byref(gbuffer), C.byref(d), stream),
+                    "bdpt_bmfr_execute_planes")
 
     def counters(self):
         c = Counters()
@@ -967,12 +1029,23 @@ class FramePipeline:
     Context.bmfr_execute_motion), and render_frame ends its G-buffer stage with keep_pose, so that the updates a caller
     issues between two render_frame calls are measured against the pose the earlier frame rendered, and a frame without
     an update gets zero motion.
+
+    denoise_groups=<BMFR_* flags> (with light_groups) denoises the planes after every render_frame with one
+    Context.bmfr_execute_planes: ``light_groups_denoised`` ((planes + 1, H, W, 4) float32) holds the denoised copies of the
+    ``light_groups`` planes and, last, that of ``output``; the rendered tensors stay as they are.  Entry k is what
+    bdpt_bmfr_execute gives that image on a context of its own.  The pipeline keeps the previous frame's view-projection
+    (view_proj_of_camera of ``cam``) for prevViewProj, counts the denoiser's frames from 0 (``last_denoise_params``: the
+    BmfrParams of the last frame; denoise_reset() starts over) and passes ``prev_position`` when motion=True.  Relighting
+    is a torch expression over the tensor: ``(gains[:, None, None, None] * pipe.light_groups_denoised[:-1]).sum(0)``.
     """
 
     def __init__(self, scene, width, height, max_depth=3, mat_index=0, device=0, tile=None, clamp_upper=0.9, min_t=1e-4,
-                 accum_limit=100, flags=0, stripes=None, light_groups=False, adaptive=None, motion=False):
+                 accum_limit=100, flags=0, stripes=None, light_groups=False, adaptive=None, motion=False, denoise_groups=None):
         import torch
         self.torch = torch
+        if denoise_groups is not None and (light_groups is None or light_groups is False):
+            raise BdptError("denoise_groups needs light_groups: it denoises the light-group planes")
+        self.denoise_flags = None if denoise_groups is None else int(denoise_groups)
         self.adaptive_params = None if adaptive is None else adaptive_params(adaptive)
         if adaptive is not None and (light_groups or stripes is not None or
                                      (tile is not None and (int(tile[0]), int(tile[1])) != (0, int(height)))):
@@ -1031,6 +1104,10 @@ class FramePipeline:
                 k = int(scene.desc.numLights) + 1 if self.group_assignment is None else max(self.group_assignment) + 2
                 self.light_groups = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
                 self.light_groups_accum = torch.zeros(k, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
+            self.light_groups_denoised = None
+            if self.denoise_flags is not None:
+                self.light_groups_denoised = torch.zeros(k + 1, self.H, self.W, 4, dtype=torch.float32, device=self.dev)
+                self.ctx.bmfr_planes_prepare(k + 1)
             self.prev_position = None
             if motion:
                 self.ctx.prepare(motion=True)
@@ -1057,6 +1134,9 @@ class FramePipeline:
         self.env_color = (0.5, 0.5, 0.8, 1.0)  # SharedUtils/ResourceManager.cpp:77-87 default environment
         self.use_jitter = True
         self.last_params = None
+        self.denoise_frame = 0
+        self.last_denoise_params = None
+        self._prev_view_proj = None
 
     @property
     def output(self):
@@ -1133,8 +1213,34 @@ class FramePipeline:
             else:
                 self.ctx.accumulate_tile(C.c_void_p(self.last_frame.data_ptr()), C.c_void_p(self.output.data_ptr()), n,
                                          self.accum_limit, st)
+        if self.light_groups_denoised is not None:
+            self._denoise_groups(st)
         self.last_params = (gp, p)
         return gp, p
+
+    def _denoise_groups(self, st):
+        """light_groups_denoised <- the frame's planes and output, denoised by one bmfr_execute_planes (the call is in/out:
+        copies first)."""
+        k = self.light_groups.shape[0]
+        self.light_groups_denoised[:k].copy_(self.light_groups)
+        self.light_groups_denoised[k].copy_(self.output)
+        bp = abi.BmfrParams()
+        bp.frameNumber, bp.flags = self.denoise_frame & 0xFFFFFFFF, self.denoise_flags
+        vp = self._prev_view_proj if self._prev_view_proj is not None else [float(i % 5 == 0) for i in range(16)]
+        for i in range(16):
+            bp.prevViewProj[i] = vp[i]
+        self.ctx.bmfr_execute_planes(bp, self.gb, self.light_groups_denoised, self.prev_position, st)
+        self._prev_view_proj = view_proj_of_camera(self.cam)
+        self.denoise_frame += 1
+        self.last_denoise_params = bp
+
+    def denoise_reset(self):
+        """Forget the denoiser's history of the planes (after a cut): the next frame is its frame 0."""
+        if self.light_groups_denoised is None:
+            raise BdptError("denoise_reset: the pipeline does not denoise (FramePipeline(..., light_groups=..., denoise_groups=flags))")
+        self.ctx.bmfr_planes_reset()
+        self.denoise_frame = 0
+        self._prev_view_proj = None
 
     def active_pixels(self):
         """Adaptive pipelines: pixels the next frame renders (the `active` word; waits for the pipeline's stream)."""

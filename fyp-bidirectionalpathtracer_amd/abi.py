@@ -250,6 +250,14 @@ class SplatDesc(C.Structure):
                 ("values", C.c_void_p), ("visible", C.c_void_p), ("items", C.c_void_p), ("splat", C.c_void_p)]
 
 
+BMFR_MAX_PLANES = BDPT_MAX_LIGHTS + 2
+
+
+class BmfrPlanesDesc(C.Structure):
+    _fields_ = [("planes", C.POINTER(C.c_void_p)), ("numPlanes", C.c_uint32), ("reserved", C.c_uint32),
+                ("prevPosition", C.c_void_p)]
+
+
 class LightGroupDesc(C.Structure):
     _fields_ = [("planes", C.c_void_p), ("numGroups", C.c_uint32), ("numAssigned", C.c_uint32),
                 ("groupOf", C.POINTER(C.c_uint8)), ("reserved", C.c_uint32 * 2)]
@@ -329,6 +337,9 @@ PROTOTYPES = {
     "bdpt_bmfr_history_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "bdpt_bmfr_save_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "bdpt_bmfr_load_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "bdpt_bmfr_execute_planes": (C.c_int, [C.c_void_p, C.POINTER(BmfrParams), C.POINTER(GBuffer), C.POINTER(BmfrPlanesDesc), C.c_void_p]),
+    "bdpt_bmfr_planes_prepare": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "bdpt_bmfr_planes_reset": (C.c_int, [C.c_void_p]),
     "bdpt_tile_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bdpt_tile_unpack": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bdpt_camera_view_proj": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,

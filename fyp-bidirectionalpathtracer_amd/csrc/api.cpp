@@ -112,6 +112,23 @@ void freeLightGroups(bdpt_ctx* c) {
   c->groupLightIdx = nullptr;
 }
 
+void freeBmfrPlanes(bdpt_ctx* c) {
+  for (int k = 0; k < 2; k++) {
+    if (c->planesPos[k]) (void)hipFree(c->planesPos[k]);
+    if (c->planesNorm[k]) (void)hipFree(c->planesNorm[k]);
+    c->planesPos[k] = c->planesNorm[k] = nullptr;
+  }
+  if (c->planesNoisy) (void)hipFree(c->planesNoisy);
+  if (c->planesFiltered) (void)hipFree(c->planesFiltered);
+  if (c->planesAccept) (void)hipFree(c->planesAccept);
+  if (c->planesPrevPixel) (void)hipFree(c->planesPrevPixel);
+  c->planesNoisy = c->planesFiltered = nullptr;
+  c->planesAccept = nullptr;
+  c->planesPrevPixel = nullptr;
+  c->planesSlots = 0;
+  c->planesRead = 0;
+}
+
 bool streamIsCapturing(hipStream_t st) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess) return false;
@@ -343,6 +360,7 @@ void bdpt_destroy(bdpt_ctx* c) {
   if (c->rayCursor) (void)hipFree(c->rayCursor);
   if (c->adaptiveSum) (void)hipFree(c->adaptiveSum);
   freeLightGroups(c);
+  freeBmfrPlanes(c);
   freePool(c->sceneAllocs);
   freePool(c->skinAllocs);
   freePool(c->frameAllocs);
@@ -1208,6 +1226,7 @@ int resizeRows(bdpt_ctx* c, uint32_t width, uint32_t height, uint32_t maxDepth) 
   HIPCHK(c, hipDeviceSynchronize());
   freePool(c->frameAllocs);
   freeLightGroups(c);
+  freeBmfrPlanes(c);
   for (int k = 0; k < 2; k++) c->bmfrPos[k] = c->bmfrNorm[k] = c->bmfrNoisy[k] = c->bmfrFiltered[k] = nullptr;
   c->ownGb = bdpt_gbuffer{};
   c->bmfrAccept = nullptr;  // history goes with the frame (BlockwiseMultiOrderFeatureRegression::resize)
@@ -2018,6 +2037,143 @@ int bdpt_bmfr_load_history(bdpt_ctx* c, const void* blob, uint64_t bytes) {
   const int r = c->bmfrRead;
   float4* dst[4] = {c->bmfrPos[r], c->bmfrNorm[r], c->bmfrNoisy[r], c->bmfrFiltered[r]};
   for (int k = 0; k < 4; k++) HIPCHK(c, hipMemcpy(dst[k], static_cast<const uint8_t*>(blob) + k * plane, plane, hipMemcpyHostToDevice));
+  return BDPT_OK;
+}
+
+// ---- bdpt_bmfr_execute_planes: the plane history and the call (contract in include/bdpt.h "Denoised planes") ----
+namespace {
+// history for at least `slots` planes; (re)allocating waits for the device and resets.  Not while `st` is being captured.
+int allocBmfrPlanes(bdpt_ctx* c, hipStream_t st, uint32_t slots) {
+  if (c->planesAccept && c->planesSlots >= slots) return BDPT_OK;
+  if (streamIsCapturing(st)) {
+    fail(c, "bmfr planes: the history needs bdpt_bmfr_planes_prepare before stream capture");
+    return BDPT_E_STATE;
+  }
+  HIPCHK(c, hipDeviceSynchronize());  // frames in flight still use the old history
+  freeBmfrPlanes(c);
+  const size_t n = std::max<size_t>((size_t)c->W * c->H, 1);
+  void* a[8]{};
+  const size_t bytes[8] = {n * sizeof(float4), n * sizeof(float4), n * sizeof(float4), n * sizeof(float4),
+                           2 * n * sizeof(float4) * slots, 2 * n * sizeof(float4) * slots, std::max<size_t>(n, 16), n * sizeof(uint32_t)};
+  for (int k = 0; k < 8; k++)
+    if (hipMalloc(&a[k], bytes[k]) != hipSuccess) {
+      for (int j = 0; j < k; j++) (void)hipFree(a[j]);
+      fail(c, "bmfr planes: hipMalloc of the plane history failed");
+      return BDPT_E_NOMEM;
+    }
+  c->planesPos[0] = static_cast<float4*>(a[0]);
+  c->planesPos[1] = static_cast<float4*>(a[1]);
+  c->planesNorm[0] = static_cast<float4*>(a[2]);
+  c->planesNorm[1] = static_cast<float4*>(a[3]);
+  c->planesNoisy = static_cast<float4*>(a[4]);
+  c->planesFiltered = static_cast<float4*>(a[5]);
+  c->planesAccept = static_cast<uint8_t*>(a[6]);
+  c->planesPrevPixel = static_cast<uint32_t*>(a[7]);
+  c->planesSlots = slots;
+  return bdpt_bmfr_planes_reset(c);
+}
+}  // namespace
+
+int bdpt_bmfr_planes_prepare(bdpt_ctx* c, uint32_t numPlanes) {
+  if (!c) return BDPT_E_INVALID;
+  if (!c->haveSize) {
+    fail(c, "bmfr_planes_prepare: bdpt_resize must be called first");
+    return BDPT_E_STATE;
+  }
+  if (numPlanes < 1 || numPlanes > BDPT_BMFR_MAX_PLANES) {
+    fail(c, "bmfr_planes_prepare: numPlanes must be 1 .. BDPT_BMFR_MAX_PLANES");
+    return BDPT_E_INVALID;
+  }
+  ENTER(c);
+  if (c->planesAccept && c->planesSlots >= numPlanes) return bdpt_bmfr_planes_reset(c);
+  return allocBmfrPlanes(c, nullptr, numPlanes);
+}
+
+int bdpt_bmfr_planes_reset(bdpt_ctx* c) {
+  if (!c) return BDPT_E_INVALID;
+  if (!c->planesAccept) return BDPT_OK;  // nothing allocated yet
+  ENTER(c);
+  const size_t n = (size_t)c->W * c->H;
+  for (int k = 0; k < 2; k++) {
+    HIPCHK(c, hipMemset(c->planesPos[k], 0, n * sizeof(float4)));
+    HIPCHK(c, hipMemset(c->planesNorm[k], 0, n * sizeof(float4)));
+  }
+  HIPCHK(c, hipMemset(c->planesNoisy, 0, 2 * n * sizeof(float4) * c->planesSlots));
+  HIPCHK(c, hipMemset(c->planesFiltered, 0, 2 * n * sizeof(float4) * c->planesSlots));
+  HIPCHK(c, hipMemset(c->planesAccept, 0, n));
+  HIPCHK(c, hipMemset(c->planesPrevPixel, 0, n * sizeof(uint32_t)));
+  c->planesRead = 0;
+  return BDPT_OK;
+}
+
+int bdpt_bmfr_execute_planes(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, const bdpt_bmfr_planes_desc* d, void* stream) {
+  if (!c || !p || !g || !d) return BDPT_E_INVALID;
+  if (!c->haveSize) {
+    fail(c, "bmfr planes: bdpt_resize must be called first");
+    return BDPT_E_STATE;
+  }
+  if (!g->worldPosition || !g->worldNormal || !g->materialDiffuse) {
+    fail(c, "bmfr planes: WorldPosition, WorldNormal and MaterialDiffuse are required");
+    return BDPT_E_INVALID;
+  }
+  if (d->numPlanes < 1 || d->numPlanes > BDPT_BMFR_MAX_PLANES || d->reserved != 0 || !d->planes) {
+    fail(c, "bmfr planes: numPlanes must be 1 .. BDPT_BMFR_MAX_PLANES, reserved 0 and planes set");
+    return BDPT_E_INVALID;
+  }
+  if (d->prevPosition && !aligned(d->prevPosition, 16)) {
+    fail(c, "bmfr planes: prevPosition not 16-byte aligned");
+    return BDPT_E_INVALID;
+  }
+  const size_t n = (size_t)c->W * c->H;
+  BmfrPlanesDev B{};
+  B.numPlanes = d->numPlanes;
+  for (uint32_t k = 0; k < d->numPlanes; k++) {  // (the caller's array is copied here)
+    if (!aligned(d->planes[k], 16)) {
+      fail(c, "bmfr planes: plane " + std::to_string(k) + " missing or not 16-byte aligned");
+      return BDPT_E_INVALID;
+    }
+    B.planes[k] = reinterpret_cast<float4*>(d->planes[k]);
+  }
+  for (uint32_t k = 0; k < d->numPlanes; k++)
+    for (uint32_t j = 0; j < k; j++) {
+      const uintptr_t a = reinterpret_cast<uintptr_t>(B.planes[k]), b = reinterpret_cast<uintptr_t>(B.planes[j]);
+      if (a < b + n * sizeof(float4) && b < a + n * sizeof(float4)) {
+        fail(c, "bmfr planes: planes " + std::to_string(j) + " and " + std::to_string(k) + " overlap");
+        return BDPT_E_INVALID;
+      }
+    }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = allocBmfrPlanes(c, st, d->numPlanes)) return rc;
+  BmfrDev& A = B.g;
+  A.W = c->W;
+  A.H = c->H;
+  A.frame = p->frameNumber;
+  A.full = (p->flags & BDPT_BMFR_FULL_FRAME) ? 1u : 0u;
+  A.doPre = (p->flags & BDPT_BMFR_PREPROCESS) ? 1u : 0u;
+  for (int k = 0; k < 16; k++) A.m[k] = p->prevViewProj[k];
+  A.curPos = reinterpret_cast<const float4*>(g->worldPosition);
+  A.curNorm = g->worldNormal;
+  A.albedo = g->materialDiffuse;
+  const int r = c->planesRead, w = 1 - r;
+  A.prevPosR = c->planesPos[r];
+  A.prevNormR = c->planesNorm[r];
+  A.prevPosW = c->planesPos[w];
+  A.prevNormW = c->planesNorm[w];
+  A.accept = c->planesAccept;
+  A.prevPixel = c->planesPrevPixel;
+  A.prevPos = reinterpret_cast<const float4*>(d->prevPosition);
+  B.read = (uint32_t)r;
+  B.histNoisy = c->planesNoisy;
+  B.histFiltered = c->planesFiltered;
+  if (!(p->flags & BDPT_BMFR_POSTPROCESS))  // as bmfrRun: the old filtered frames stay on the read side next frame
+    for (uint32_t k = 0; k < d->numPlanes; k++)
+      HIPCHK(c, hipMemcpyAsync(c->planesFiltered + (2 * (size_t)k + w) * n, c->planesFiltered + (2 * (size_t)k + r) * n, n * sizeof(float4),
+                               hipMemcpyDeviceToDevice, st));
+  launchBmfrPlanes(B, p->flags, st);
+  HIPCHK(c, hipGetLastError());
+  c->planesRead = w;
+  c->lastStream = st;
   return BDPT_OK;
 }
 

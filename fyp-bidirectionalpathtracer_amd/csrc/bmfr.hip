@@ -431,5 +431,496 @@ void launchBmfr(const BmfrDev& A, uint32_t flags, hipStream_t st) {
   if (flags & BDPT_BMFR_POSTPROCESS) hipLaunchKernelGGL(bmfr_postprocess_kernel, grid, block, 0, st, A);
 }
 
+// ---- Planes (bdpt_bmfr_execute_planes; DESIGN.md "Denoised light groups") ----
+// numPlanes images over one G-buffer, each left with the bits the three kernels above give it alone.  Whatever reads
+// positions and normals only is done once: the reprojection, the tap tests, accept, prevPixel and the position / normal
+// history; feature scaling and the Householder reflectors of the ten feature columns; the postprocess taps and weights.
+// Whatever reads a colour is done per plane, with the single-image kernels' expressions in their order.
+
+namespace {
+
+BD float4* planeHist(float4* base, const BmfrPlanesDev& B, uint32_t k, uint32_t side) {
+  return base + (size_t)(2u * k + side) * ((size_t)B.g.W * B.g.H);
+}
+
+}  // namespace
+
+template <bool MOTION>
+__global__ __launch_bounds__(256) void bmfr_planes_preprocess_kernel(BmfrPlanesDev B) {
+  const BmfrDev& A = B.g;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t n = A.W * A.H;
+  if (i >= n) return;
+  const int W = (int)A.W, H = (int)A.H;
+  const int x = (int)(i % A.W), y = (int)(i / A.W);
+  const float4 cp = A.curPos[i];
+  const float4 q = MOTION ? A.prevPos[i] : cp;
+  const float4 cn = loadHalf4(A.curNorm, i);
+  const float posx = (float)x + 0.5f, posy = (float)y + 0.5f;
+  const float texCx = posx / (float)W;
+  const bool process = A.doPre && (A.full || !(texCx > 0.5f));
+  // geometry: bmfr_preprocess_kernel's tests, once
+  float pfx = posx, pfy = posy;
+  uint32_t storeAccept = 0;
+  float totalWeight = 0;
+  float wts[4] = {0, 0, 0, 0};
+  uint32_t tap[4] = {0, 0, 0, 0};
+  bool outside = false;
+  if (process && A.frame > 0) {
+    float c[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) c[r] = ((A.m[4 * r] * q.x + A.m[4 * r + 1] * q.y) + A.m[4 * r + 2] * q.z) + A.m[4 * r + 3];
+    float ux = c[0] / c[3], uy = c[1] / c[3];
+    ux = (ux + 1.0f) / 2.0f;
+    uy = (1 - uy) / 2.0f;
+    if (ux > 1.0f || ux < 0.0f || uy > 1.0f || uy < 0.0f) {
+      outside = true;
+    } else {
+      pfx = ux * (float)A.W - 0.5f;
+      pfy = uy * (float)A.H - 0.5f;
+      const int ipx = (int)pfx, ipy = (int)pfy;
+      const float fx = pfx - (float)ipx, fy = pfy - (float)ipy;
+      const float ox = 1.0f - fx, oy = 1.0f - fy;
+      wts[0] = ox * oy;
+      wts[1] = fx * oy;
+      wts[2] = ox * fy;
+      wts[3] = fx * fy;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int sx = ipx + (k & 1), sy = ipy + (k >> 1);
+        if (sx >= 0 && sy >= 0 && sx < W && sy < H) {
+          const uint32_t j = (uint32_t)sy * A.W + (uint32_t)sx;
+          const float4 pp = A.prevPosR[j];
+          const float dx = pp.x - q.x, dy = pp.y - q.y, dz = pp.z - q.z;
+          const float pd = (dx * dx + dy * dy) + dz * dz;
+          if (pd < 0.01f) {
+            const float4 pn = A.prevNormR[j];
+            const float ex = pn.x - cn.x, ey = pn.y - cn.y, ez = pn.z - cn.z;
+            const float nd = (ex * ex + ey * ey) + ez * ez;
+            if (nd < 1.0f) {
+              storeAccept |= 1u << k;
+              tap[k] = j;
+              totalWeight += wts[k];
+            }
+          }
+        }
+      }
+    }
+  }
+  if (process) {
+    if (outside) {
+      A.accept[i] = 0;
+    } else {
+      A.accept[i] = (uint8_t)storeAccept;
+      A.prevPixel[i] = (uint32_t)f32_to_f16(pfx) | ((uint32_t)f32_to_f16(pfy) << 16);  // RG16Float
+    }
+  }
+  A.prevNormW[i] = cn;
+  A.prevPosW[i] = cp;
+  // colours: per plane, from the plane's own history
+  for (uint32_t p = 0; p < B.numPlanes; p++) {
+    float4 cur = B.planes[p][i];
+    if (process) {
+      if (outside) {
+        cur.w = 1.0f;
+      } else {
+        const float4* prevNoisyR = planeHist(B.histNoisy, B, p, B.read);
+        float blendAlpha = 1.0f;
+        float pr = 0, pg = 0, pb = 0, sampleSpp = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if (storeAccept & (1u << k)) {
+            const float4 pd4 = prevNoisyR[tap[k]];
+            sampleSpp += wts[k] * pd4.w;
+            pr += wts[k] * pd4.x;
+            pg += wts[k] * pd4.y;
+            pb += wts[k] * pd4.z;
+          }
+        if (totalWeight > 0.0f) {
+          pr /= totalWeight;
+          pg /= totalWeight;
+          pb /= totalWeight;
+          sampleSpp /= totalWeight;
+          blendAlpha = 1.0f / (sampleSpp + 1.0f);
+          blendAlpha = blendAlpha > 0.2f ? blendAlpha : 0.2f;
+        }
+        float newSpp = 1.0f;
+        if (blendAlpha < 1.0f) newSpp += sampleSpp;
+        cur = make_float4(blendAlpha * cur.x + (1.0f - blendAlpha) * pr, blendAlpha * cur.y + (1.0f - blendAlpha) * pg,
+                          blendAlpha * cur.z + (1.0f - blendAlpha) * pb, newSpp);
+      }
+      B.planes[p][i] = cur;
+    }
+    planeHist(B.histNoisy, B, p, 1u - B.read)[i] = cur;
+  }
+}
+
+// blockTree<0> for N columns at once: column c's partial sums in sumN[c * kLocal ..]; every column keeps blockTree's pairing
+// (v[t] += v[t + stride], then v[0] + v[1]), the N * stride additions of a level are spread over the whole workgroup, and
+// the columns share the level's barrier
+template <int N>
+BD void blockTreeSumN(const float (&v)[N], float (&r)[N], float* sumN, int tid) {
+#pragma unroll
+  for (int c = 0; c < N; c++) sumN[c * kLocal + tid] = v[c];
+  __syncthreads();
+#pragma unroll
+  for (int stride = 128; stride >= 2; stride >>= 1) {
+#pragma unroll
+    for (int item = tid; item < N * stride; item += kLocal) {
+      const int at = (item / stride) * kLocal + item % stride;
+      const float a = sumN[at], b = sumN[at + stride];
+      sumN[at] = a + b;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int c = 0; c < N; c++) {
+    const float a = sumN[c * kLocal], b = sumN[c * kLocal + 1];
+    r[c] = a + b;
+  }
+  __syncthreads();
+}
+
+// K: planes whose colour columns are carried through the ten steps together (3 K columns per tree pass); a workgroup
+// takes its planes K at a time
+template <bool IGNORE_LD, int K>
+__global__ __launch_bounds__(256) void bmfr_planes_fit_kernel(BmfrPlanesDev B, int horizontalBlocks) {
+  constexpr int kCols = 3 * K;
+  __shared__ float outS[kFeatures * kBlockPixels];  // the feature columns; after the factorisation column c = reflector c
+  __shared__ float sumN[kCols * kLocal];            // (the feature trees use its first kLocal words)
+  __shared__ float rfeat[kFeatures][kFeatures];     // R of the features: rmat[.][0..9] of bmfr_fit_kernel
+  __shared__ float rcol[kCols][kFeatures];          // rmat[.][10..12] of the planes in flight, one row per colour column
+  __shared__ float stepUls[kFeatures];
+  __shared__ int stepFirst[kFeatures];  // firstUpd of the step; -1: the step was skipped (rank dropped)
+  __shared__ float bcast[2];
+  const BmfrDev& A = B.g;
+  const int tid = (int)threadIdx.x, group = (int)blockIdx.x;
+  const int W = (int)A.W, H = (int)A.H;
+  const uint32_t frame = A.frame;
+  const int offx = kBlockOffsets[frame % 16u][0], offy = kBlockOffsets[frame % 16u][1];
+  const int bx = (group % horizontalBlocks) * kBlockEdge + offx, by = (group / horizontalBlocks) * kBlockEdge + offy;
+  float tmp[kSub][kFeatures];
+  uint32_t pix[kSub];  // the (mirrored) pixel each row loads; ~0u: outside the texture, loads give 0
+#define OUT(index, buf) outS[(buf) * kBlockPixels + (index)]
+#pragma unroll
+  for (int s = 0; s < kSub; s++) {
+    const int index = s * kLocal + tid;
+    const int ux = mirror(bx + index % kBlockEdge, W), uy = mirror(by + index / kBlockEdge, H);
+    const bool inside = ux >= 0 && uy >= 0 && ux < W && uy < H;
+    const size_t i = inside ? (size_t)uy * W + ux : 0;
+    pix[s] = inside ? (uint32_t)i : ~0u;
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 p = inside ? A.curPos[i] : zero;
+    const float4 nrm = inside ? loadHalf4(A.curNorm, i) : zero;
+    tmp[s][0] = 1.0f;
+    tmp[s][1] = nrm.x;
+    tmp[s][2] = nrm.y;
+    tmp[s][3] = nrm.z;
+    tmp[s][4] = p.x;
+    tmp[s][5] = p.y;
+    tmp[s][6] = p.z;
+    tmp[s][7] = p.x * p.x;
+    tmp[s][8] = p.y * p.y;
+    tmp[s][9] = p.z * p.z;
+  }
+#pragma unroll
+  for (int fb = kFeaturesNotScaled; fb < kFeatures; fb++) {
+    float mx = tmp[0][fb], mn = tmp[0][fb];
+#pragma unroll
+    for (int s = 1; s < kSub; s++) {
+      mx = fmaxf(tmp[s][fb], mx);
+      mn = fminf(tmp[s][fb], mn);
+    }
+    const float blockMax = blockTree<1>(mx, sumN, tid);
+    const float blockMin = blockTree<2>(mn, sumN, tid);
+    const bool wide = blockMax - blockMin > 1.0f;
+#pragma unroll
+    for (int s = 0; s < kSub; s++) tmp[s][fb] = wide ? (tmp[s][fb] - blockMin) / (blockMax - blockMin) : tmp[s][fb] - blockMin;
+  }
+#pragma unroll
+  for (int fb = 0; fb < kFeatures; fb++)
+#pragma unroll
+    for (int s = 0; s < kSub; s++) OUT(s * kLocal + tid, fb) = tmp[s][fb];
+  __syncthreads();
+
+  // bmfr_fit_kernel's factorisation of the feature columns; each step leaves what a colour column needs from it
+  float u[kSub];
+  float uLengthSquared = 0.0f;
+  int limit = 0;
+  for (int col = 0; col < kFeatures; col++) {
+    const int firstRow = IGNORE_LD ? limit + 1 : col + 1;
+    float acc = 0.0f;
+#pragma unroll
+    for (int s = 0; s < kSub; s++) {
+      const int index = s * kLocal + tid;
+      const float v = OUT(index, col);
+      u[s] = v;
+      if (index >= firstRow) acc += v * v;
+    }
+    float vecLength = blockTree<0>(acc, sumN, tid);
+    const int pivot = IGNORE_LD ? limit : col;
+    float rValue = 0.0f;
+    if (tid < pivot) {
+      rValue = u[0];
+    } else if (tid == pivot) {
+      float uls = vecLength;
+      vecLength = sqrtf(vecLength + u[0] * u[0]);
+      u[0] -= vecLength;
+      uls += u[0] * u[0];
+      rValue = vecLength;
+      bcast[0] = vecLength;
+      bcast[1] = uls;
+      OUT(tid, col) = u[0];  // the reflector stays in its column; the R value it replaces is in rfeat
+    }
+    if (tid == 0) stepFirst[col] = -1;
+    __syncthreads();
+    vecLength = bcast[0];
+    uLengthSquared = bcast[1];
+    if (IGNORE_LD) {
+      if (vecLength > 0.01f) {
+        limit++;
+        if (tid < kFeatures) rfeat[tid][col] = rValue;
+      } else {
+        if (tid < kFeatures) rfeat[tid][col] = 0.0f;
+        __syncthreads();
+        continue;
+      }
+      if (uLengthSquared < 0.001f) {
+        __syncthreads();
+        continue;
+      }
+    } else {
+      if (tid < kFeatures) rfeat[tid][col] = rValue;
+    }
+    const int firstUpd = IGNORE_LD ? limit - 1 : col;
+    if (tid == 0) {
+      stepFirst[col] = firstUpd;
+      stepUls[col] = uLengthSquared;
+    }
+    for (int fb = col + 1; fb < kFeatures; fb++) {
+      float cache[kSub];
+      float dot = 0.0f;
+#pragma unroll
+      for (int s = 0; s < kSub; s++) {
+        const int index = s * kLocal + tid;
+        if (index >= firstUpd) {
+          float v = OUT(index, fb);
+          if (!IGNORE_LD && col == 0) v = addRandom(v, (uint32_t)tid, (uint32_t)s, (uint32_t)fb, frame);
+          cache[s] = v;
+          dot += v * u[s];
+        }
+      }
+      const float dotV = blockTree<0>(dot, sumN, tid);
+#pragma unroll
+      for (int s = 0; s < kSub; s++) {
+        const int index = s * kLocal + tid;
+        if (index >= firstUpd) OUT(index, fb) = cache[s] - 2.0f * u[s] * dotV / uLengthSquared;
+      }
+    }
+    __syncthreads();
+  }
+
+  for (uint32_t p0 = 0; p0 < B.numPlanes; p0 += K) {
+    // the demodulated colours of planes p0 .. p0 + K - 1 (rows of a thread are its own: registers, not LDS)
+    float cv[kCols][kSub];
+    float spp[K][kSub];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      const bool live = p0 + k < B.numPlanes;
+      const float4* noisyW = planeHist(B.histNoisy, B, live ? p0 + k : p0, 1u - B.read);  // bmfr_fit_kernel reads prevNoisyW
+#pragma unroll
+      for (int s = 0; s < kSub; s++) {
+        const bool inside = live && pix[s] != ~0u;
+        const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const float4 alb = inside ? loadHalf4(A.albedo, pix[s]) : zero;
+        const float4 c = inside ? noisyW[pix[s]] : zero;
+        cv[3 * k][s] = alb.x < 0.01f ? 0.0f : c.x / alb.x;
+        cv[3 * k + 1][s] = alb.y < 0.01f ? 0.0f : c.y / alb.y;
+        cv[3 * k + 2][s] = alb.z < 0.01f ? 0.0f : c.z / alb.z;
+        spp[k][s] = c.w;
+      }
+    }
+    for (int col = 0; col < kFeatures; col++) {
+      const int firstUpd = stepFirst[col];
+      if (firstUpd < 0) continue;
+      const float uls = stepUls[col];
+#pragma unroll
+      for (int s = 0; s < kSub; s++) u[s] = OUT(s * kLocal + tid, col);
+      float dot[kCols], dotV[kCols];
+#pragma unroll
+      for (int c = 0; c < kCols; c++) {
+        dot[c] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < kSub; s++)
+          if (s * kLocal + tid >= firstUpd) dot[c] += cv[c][s] * u[s];
+      }
+      blockTreeSumN<kCols>(dot, dotV, sumN, tid);
+#pragma unroll
+      for (int c = 0; c < kCols; c++)
+#pragma unroll
+        for (int s = 0; s < kSub; s++)
+          if (s * kLocal + tid >= firstUpd) cv[c][s] = cv[c][s] - 2.0f * u[s] * dotV[c] / uls;
+    }
+    if (tid < kFeatures) {
+#pragma unroll
+      for (int c = 0; c < kCols; c++) rcol[c][tid] = cv[c][0];
+    }
+    __syncthreads();
+    // back substitution: bmfr_fit_kernel's, one lane per colour column (the channels never mix)
+    if (tid < kCols) {
+      float* rc = rcol[tid];
+      if (IGNORE_LD) {
+        int lim = limit - 1;
+        for (int i = kFeatures - 1; i >= 0; i--) {
+          if (lim >= 0 && rfeat[lim][i] != 0.0f) {
+            rc[i] = rc[lim] / rfeat[lim][i];
+            lim--;
+          } else {
+            rc[i] = 0.0f;
+          }
+          for (int rowId = lim; rowId >= 0; rowId--) rc[rowId] -= rc[i] * rfeat[rowId][i];
+        }
+      } else {
+        for (int i = kFeatures - 1; i >= 0; i--) {
+          rc[i] /= rfeat[i][i];
+          for (int rowId = i - 1; rowId >= 0; rowId--) rc[rowId] -= rc[i] * rfeat[rowId][i];
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      if (p0 + k >= B.numPlanes) break;
+      float4* out = B.planes[p0 + k];
+#pragma unroll
+      for (int s = 0; s < kSub; s++) {
+        const int index = s * kLocal + tid;
+        float r = 0.0f, g = 0.0f, b = 0.0f;
+#pragma unroll
+        for (int col = 0; col < kFeatures; col++) {
+          const float t = tmp[s][col];
+          r += rcol[3 * k][col] * t;
+          g += rcol[3 * k + 1][col] * t;
+          b += rcol[3 * k + 2][col] * t;
+        }
+        const int ux = bx + index % kBlockEdge, uy = by + index / kBlockEdge;
+        if (ux < 0 || uy < 0 || ux >= W || uy >= H) continue;
+        const size_t i = (size_t)uy * W + ux;
+        const float4 alb = loadHalf4(A.albedo, i);
+        out[i] = make_float4(alb.x * (r < 0.0f ? 0.0f : r), alb.y * (g < 0.0f ? 0.0f : g), alb.z * (b < 0.0f ? 0.0f : b), alb.w * spp[k][s]);
+      }
+    }
+    __syncthreads();  // rcol is rewritten by the next K planes
+  }
+#undef OUT
+}
+
+__global__ __launch_bounds__(256) void bmfr_planes_postprocess_kernel(BmfrPlanesDev B) {
+  const BmfrDev& A = B.g;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t n = A.W * A.H;
+  if (i >= n) return;
+  const int W = (int)A.W, H = (int)A.H;
+  const int x = (int)(i % A.W);
+  const float texCx = ((float)x + 0.5f) / (float)W;
+  const bool passThrough = !A.full && texCx > 0.5f;
+  // geometry: the accepted taps and their weights, once
+  float wts[4] = {0, 0, 0, 0};
+  uint32_t tap[4] = {~0u, ~0u, ~0u, ~0u};  // ~0u: outside the frame, the tap reads 0
+  uint32_t accept = 0;
+  float totalWeight = 0.0f;
+  if (!passThrough && A.frame > 0) {
+    accept = A.accept[i];
+    if (accept > 0) {
+      const uint32_t pw = A.prevPixel[i];
+      const float pfx = f16_to_f32((uint16_t)(pw & 0xffffu)), pfy = f16_to_f32((uint16_t)(pw >> 16));
+      const int ipx = (int)pfx, ipy = (int)pfy;
+      const float fx = pfx - (float)ipx, fy = pfy - (float)ipy;
+      const float ox = 1.0f - fx, oy = 1.0f - fy;
+      wts[0] = ox * oy;
+      wts[1] = fx * oy;
+      wts[2] = ox * fy;
+      wts[3] = fx * fy;
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (accept & (1u << k)) {
+          totalWeight += wts[k];
+          const int sx = ipx + (k & 1), sy = ipy + (k >> 1);
+          if (sx >= 0 && sy >= 0 && sx < W && sy < H) tap[k] = (uint32_t)sy * A.W + (uint32_t)sx;
+        }
+    }
+  }
+  for (uint32_t p = 0; p < B.numPlanes; p++) {
+    const float4 f = B.planes[p][i];
+    float4 res;
+    if (passThrough) {
+      res = f;
+    } else {
+      const float4* prevFilteredR = planeHist(B.histFiltered, B, p, B.read);
+      float prev[3] = {0, 0, 0};
+      float blendAlpha = 1.0f;
+      if (accept > 0) {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if (accept & (1u << k)) {
+            float4 pv = make_float4(0, 0, 0, 0);
+            if (tap[k] != ~0u) pv = prevFilteredR[tap[k]];
+            prev[0] += wts[k] * pv.x;
+            prev[1] += wts[k] * pv.y;
+            prev[2] += wts[k] * pv.z;
+          }
+        if (totalWeight > 0.0f) {
+          blendAlpha = 1.0f / f.w;
+          blendAlpha = blendAlpha > 0.1f ? blendAlpha : 0.1f;
+          prev[0] /= totalWeight;
+          prev[1] /= totalWeight;
+          prev[2] /= totalWeight;
+        }
+      }
+      res = make_float4(blendAlpha * f.x + (1.0f - blendAlpha) * prev[0], blendAlpha * f.y + (1.0f - blendAlpha) * prev[1],
+                        blendAlpha * f.z + (1.0f - blendAlpha) * prev[2], 1.0f);
+    }
+    B.planes[p][i] = res;
+    planeHist(B.histFiltered, B, p, 1u - B.read)[i] = res;
+  }
+}
+
+namespace {
+template <int K>
+void launchPlanesFit(const BmfrPlanesDev& B, uint32_t flags, int w, int h, hipStream_t st) {
+  if (flags & BDPT_BMFR_KEEP_LD_FEATURES)
+    hipLaunchKernelGGL((bmfr_planes_fit_kernel<false, K>), dim3((uint32_t)(w * h)), dim3(256), 0, st, B, w);
+  else
+    hipLaunchKernelGGL((bmfr_planes_fit_kernel<true, K>), dim3((uint32_t)(w * h)), dim3(256), 0, st, B, w);
+}
+}  // namespace
+
+void launchBmfrPlanes(const BmfrPlanesDev& B, uint32_t flags, hipStream_t st) {
+  const BmfrDev& A = B.g;
+  const uint32_t n = A.W * A.H;
+  if (!n || !B.numPlanes) return;
+  const dim3 grid((n + 255u) / 256u), block(256);
+  if (A.prevPos)
+    hipLaunchKernelGGL(bmfr_planes_preprocess_kernel<true>, grid, block, 0, st, B);
+  else
+    hipLaunchKernelGGL(bmfr_planes_preprocess_kernel<false>, grid, block, 0, st, B);
+  if (flags & BDPT_BMFR_REGRESSION) {
+    const int bw = ((int)A.W + 31) / 32, bh = ((int)A.H + 31) / 32;
+    int w = bw + 1;
+    const int h = bh + 1;
+    if (!A.full) w /= 2;
+    if (w * h > 0) {
+      // K = planes per pass over the ten steps (kBmfrPlanesK at most); fewer planes than that take the narrower instance
+      if (B.numPlanes == 1)
+        launchPlanesFit<1>(B, flags, w, h, st);
+      else if (B.numPlanes == 2)
+        launchPlanesFit<2>(B, flags, w, h, st);
+      else
+        launchPlanesFit<4>(B, flags, w, h, st);
+    }
+  }
+  if (flags & BDPT_BMFR_POSTPROCESS) hipLaunchKernelGGL(bmfr_planes_postprocess_kernel, grid, block, 0, st, B);
+}
+
 #undef BD
 }  // namespace bdpt

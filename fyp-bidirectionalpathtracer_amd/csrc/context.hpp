@@ -70,6 +70,16 @@ struct bdpt_ctx {
   uint8_t* bmfrAccept = nullptr;
   uint32_t* bmfrPrevPixel = nullptr;
   int bmfrRead = 0;  // which half holds the previous frame
+  // the plane history of bdpt_bmfr_execute_planes (bdpt_bmfr_planes_prepare or the first call that needs more slots),
+  // apart from the history above: position / normal pairs, accept and prevPixel once, noisy and filtered pairs per slot
+  // (side s of slot k at [(2 * k + s) * W * H]).  Own allocations, not frameAllocs: growing frees them.
+  float4* planesPos[2] = {nullptr, nullptr};
+  float4* planesNorm[2] = {nullptr, nullptr};
+  float4 *planesNoisy = nullptr, *planesFiltered = nullptr;
+  uint8_t* planesAccept = nullptr;
+  uint32_t* planesPrevPixel = nullptr;
+  uint32_t planesSlots = 0;
+  int planesRead = 0;
   // the splat and NEE generators run beside the connection generator on this stream (fork/join with events; capture-safe)
   hipStream_t walkStream = nullptr;
   hipEvent_t evFork = nullptr, evJoin = nullptr, evSplat = nullptr;

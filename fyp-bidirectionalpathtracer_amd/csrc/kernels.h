@@ -256,6 +256,19 @@ struct BmfrDev {
 };
 void launchBmfr(const BmfrDev& A, uint32_t flags, hipStream_t st);
 
+// bdpt_bmfr_execute_planes (bmfr.hip "Planes"): numPlanes images over one G-buffer.  g carries what the images share (frame,
+// flags, matrix, features, the position / normal history, accept, prevPixel, prevPos); its noisy, prevNoisy* and
+// prevFiltered* stay NULL.  Plane k's noisy and filtered history: side s of slot k at hist*[(2 * k + s) * W * H]; `read` is
+// the side that holds the previous frame.  The pointers travel by value in the kernel argument.
+struct BmfrPlanesDev {
+  BmfrDev g;
+  uint32_t numPlanes, read;
+  float4* planes[BDPT_BMFR_MAX_PLANES];
+  float4 *histNoisy, *histFiltered;
+};
+// one launch per stage whatever numPlanes is
+void launchBmfrPlanes(const BmfrPlanesDev& B, uint32_t flags, hipStream_t st);
+
 // Motion (motion.hip, device_motion.hpp; contract in include/bdpt.h "Motion"): the previous pose, three float4 per
 // primitive (the corners p0, p1, p2 in primitive order, w unused), and the G-buffer channel made from it.  Only the MOTION
 // instance of gbuffer_kernel takes it (last argument), so SceneDev, GBufferDev and every other instance stay as they are.

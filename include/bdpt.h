@@ -1196,6 +1196,47 @@ int bdpt_bmfr_history_bytes(const bdpt_ctx* ctx, uint64_t* out_bytes);
 int bdpt_bmfr_save_history(bdpt_ctx* ctx, void* host_blob, uint64_t bytes);
 int bdpt_bmfr_load_history(bdpt_ctx* ctx, const void* host_blob, uint64_t bytes);
 
+/* ---- Denoised planes: several images over one G-buffer (light-group planes, for relighting) with one fit ----
+ * bdpt_bmfr_execute_planes denoises numPlanes whole-frame images that share `features` in one call: the reprojection
+ * and its geometry tests, the feature scaling and the Householder factorisation of the ten feature columns of every
+ * block are done once, the colour work per plane.
+ *
+ * Contract.  After the call planes[k] holds exactly the bits bdpt_bmfr_execute (with prevPosition set:
+ * bdpt_bmfr_execute_motion) would have left in it on a context of its own that was fed planes[k], the same `features`
+ * and the same params on every frame since its reset — for every flag combination bdpt_bmfr_execute accepts (regression
+ * off, BDPT_BMFR_KEEP_LD_FEATURES, BDPT_BMFR_FULL_FRAME, stages switched off).  List position k owns history slot k.
+ * Colours, w / spp, sampleSpp and both blend factors are computed per plane from that plane's own history; only what
+ * reads positions and normals alone is shared.
+ *
+ * History.  The plane history is apart from the single-image history: position and normal ping-pong pairs, the accept
+ * mask and prevPixel once, noisy and filtered ping-pong pairs per slot.  bdpt_bmfr_execute, _motion, _reset,
+ * _history_bytes, _save_history and _load_history keep their bits and their state whatever is called here, and the blob
+ * functions cover the single-image history only: the plane history is not checkpointed.  bdpt_resize drops it, as it
+ * drops the other.
+ *   bdpt_bmfr_planes_prepare(n)  allocates the history for n planes (if fewer are there) and resets it.
+ *   bdpt_bmfr_planes_reset       forgets it (BDPT_OK when there is none).
+ * A call that needs more planes than are allocated waits for the device, reallocates and resets the plane history
+ * (inside a stream capture: BDPT_E_STATE, as the other first-use allocations); one with fewer uses the first numPlanes
+ * slots.  Stream capture follows bdpt_bmfr_execute's rule: history prepared beforehand, the ping-pong side chosen on the
+ * host at capture time.
+ *
+ * Errors, nothing enqueued on any: no size BDPT_E_STATE; a NULL ctx, params, features or desc, missing feature channels,
+ * numPlanes outside 1 .. BDPT_BMFR_MAX_PLANES, non-zero reserved, a NULL or misaligned plane or a misaligned
+ * prevPosition, two planes whose byte ranges overlap BDPT_E_INVALID.  As bdpt_bmfr_execute, the call takes WHOLE-FRAME
+ * buffers also on a band or stripes context. */
+#define BDPT_BMFR_MAX_PLANES (BDPT_MAX_LIGHTS + 2) /* 16 groups + emission + the frame itself */
+typedef struct bdpt_bmfr_planes_desc {
+  float* const* planes;      /* HOST array of numPlanes device pointers; each a whole-frame RGBA32F image, 16-byte aligned,
+                                in/out; the array is copied before the call returns (as groupOf is) */
+  uint32_t numPlanes;        /* 1 .. BDPT_BMFR_MAX_PLANES */
+  uint32_t reserved;         /* 0 */
+  const float* prevPosition; /* optional: bdpt_bmfr_execute_motion's channel; NULL = bdpt_bmfr_execute's reprojection */
+} bdpt_bmfr_planes_desc;
+int bdpt_bmfr_execute_planes(bdpt_ctx* ctx, const bdpt_bmfr_params* p, const bdpt_gbuffer* features,
+                             const bdpt_bmfr_planes_desc* desc, void* stream);
+int bdpt_bmfr_planes_prepare(bdpt_ctx* ctx, uint32_t numPlanes); /* allocate + reset the plane history */
+int bdpt_bmfr_planes_reset(bdpt_ctx* ctx);
+
 /* Rows of a tile as one contiguous run, and back: `frame` is a whole-frame buffer of `bytesPerPixel` (4, 8 or 16) bytes
  * per pixel, `packed` holds rows of `width` pixels.
  * bdpt_tile_pack:   packed[i] = frame[pixel i of this context's tile] (its rows in ascending order: the order of a
