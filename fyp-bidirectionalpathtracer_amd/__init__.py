@@ -808,9 +808,12 @@ class Context:
         self._check(self._lib.bdpt_execute_tail(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream),
                     "bdpt_execute_tail")
 
-    def prepare(self, what=0, motion=False):
-        """bdpt_prepare(what); motion=True adds PREPARE_MOTION (the previous pose of keep_pose; needs a scene)."""
-        self._check(self._lib.bdpt_prepare(self._h, int(what) | (abi.PREPARE_MOTION if motion else 0)), "bdpt_prepare")
+    def prepare(self, what=0, motion=False, refit_pieces=False):
+        """bdpt_prepare(what); motion=True adds PREPARE_MOTION (the previous pose of keep_pose; needs a scene),
+        refit_pieces=True adds PREPARE_REFIT_PIECES (later updates refit split / clipped references by their piece; needs
+        a scene that has not been updated yet)."""
+        what = int(what) | (abi.PREPARE_MOTION if motion else 0) | (abi.PREPARE_REFIT_PIECES if refit_pieces else 0)
+        self._check(self._lib.bdpt_prepare(self._h, what), "bdpt_prepare")
 
     def splat_buffer(self):
         p = C.c_void_p()

@@ -32,6 +32,7 @@ PREPARE_LIGHT_GROUPS = 8
 PREPARE_AREA_LIGHTS = 16
 PREPARE_LIGHT_GROUP_TABLE = 32
 PREPARE_MOTION = 64
+PREPARE_REFIT_PIECES = 128
 MEMORY_HOST, MEMORY_DEVICE = 0, 1
 UPDATE_KEEP_LIGHT_MAPS = 1
 BDPT_MAX_BONES = 1024
@@ -299,6 +300,7 @@ PROTOTYPES = {
     "bdpt_connect_query": (C.c_int, [C.c_void_p, C.POINTER(ConnectDesc), C.c_void_p]),
     "bdpt_splat_add": (C.c_int, [C.c_void_p, C.POINTER(SplatDesc), C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bdpt_host_bvh_refit_pieces": (C.c_int, [C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),
     "bdpt_host_bvh_recs_hash": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "bdpt_host_bvh_refit_info": (C.c_int, [C.c_void_p, C.POINTER(RefitInfo)]),

@@ -245,6 +245,29 @@ int ensureRefit(bdpt_ctx* c, hipStream_t st) {
   return BDPT_OK;
 }
 
+// bdpt_prepare(BDPT_PREPARE_REFIT_PIECES): the plan as above, then the regions of the tree AS BUILT (bvh.h "piece-tight
+// refit", refit.hip k_refit_regions); from then on launchRefit runs its piece-tight instance
+int ensureRefitPieces(bdpt_ctx* c) {
+  if (c->refitReady && c->refit.region) return BDPT_OK;
+  if (c->numUpdates) {
+    fail(c, "prepare: BDPT_PREPARE_REFIT_PIECES derives the regions from the tree as built: not after an update (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (streamIsCapturing(c->lastStream)) {
+    fail(c, "prepare: BDPT_PREPARE_REFIT_PIECES allocates and synchronises: not inside a stream capture");
+    return BDPT_E_STATE;
+  }
+  if (int rc = ensureRefit(c, nullptr)) return rc;
+  float* region = nullptr;
+  if (int rc = devAlloc(c, c->sceneAllocs, &region, (size_t)c->S.numRecs * kPieceFloats)) return rc;
+  HIPCHK(c, hipDeviceSynchronize());
+  launchRefitRegions(c->refit, reinterpret_cast<const BvhRec*>(c->S.recs), region, nullptr);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipDeviceSynchronize());
+  c->refit.region = region;
+  return BDPT_OK;
+}
+
 }  // namespace
 
 // (declared in context.hpp)
@@ -1874,13 +1897,13 @@ int bdpt_execute_tail(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in,
 // Allocate the optional buffers up front so that no later execute allocates (hipGraph capture, latency).
 int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
   if (!c) return BDPT_E_INVALID;
-  if ((what & ~(BDPT_PREPARE_REFIT | BDPT_PREPARE_AREA_LIGHTS | BDPT_PREPARE_MOTION)) || !what) {
+  if ((what & ~(BDPT_PREPARE_REFIT | BDPT_PREPARE_AREA_LIGHTS | BDPT_PREPARE_MOTION | BDPT_PREPARE_REFIT_PIECES)) || !what) {
     if (!c->haveSize) {
       fail(c, "prepare: bdpt_resize must be called first");
       return BDPT_E_STATE;
     }
   }
-  if ((what & BDPT_PREPARE_REFIT) && !c->haveScene) {
+  if ((what & (BDPT_PREPARE_REFIT | BDPT_PREPARE_REFIT_PIECES)) && !c->haveScene) {
     fail(c, "prepare: BDPT_PREPARE_REFIT needs a scene");
     return BDPT_E_STATE;
   }
@@ -1897,8 +1920,11 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
     return BDPT_E_STATE;
   }
   ENTER(c);
-  if (what & BDPT_PREPARE_REFIT)
+  if (what & BDPT_PREPARE_REFIT_PIECES) {  // (implies BDPT_PREPARE_REFIT)
+    if (int rc = ensureRefitPieces(c)) return rc;
+  } else if (what & BDPT_PREPARE_REFIT) {
     if (int rc = ensureRefit(c, nullptr)) return rc;
+  }
   if (what & BDPT_PREPARE_PRIMARY)
     if (int rc = allocOwnGbuffer(c)) return rc;
   if (what & BDPT_PREPARE_BMFR)  // (whole-frame history also on a band / stripes context: bdpt_bmfr_execute takes whole-frame buffers)

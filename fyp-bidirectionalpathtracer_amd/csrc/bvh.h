@@ -467,6 +467,123 @@ BVH_HD inline float bvhPadOf(const float* lo, const float* hi, bool any) {
   return 2e-5f * diag + 1e-30f;
 }
 
+// ---- piece-tight refit (BDPT_PREPARE_REFIT_PIECES): a split or clipped reference bounded by its piece ----
+// A reference stands for a piece of its triangle, and a per-vertex update maps the triangle affinely: the piece keeps its
+// footprint in the triangle's barycentric plane (P = v0 + u e1 + v e2) however the vertices move.  Once, from the tree as
+// built, every triangle record gets a region of that plane that contains its piece — the hexagon
+//   umin <= u <= umax,  vmin <= v <= vmax,  smin <= u + v <= smax
+// around (triangle) n (decoded box of the leaf child the record belongs to): the piece lies in both.  A refit then bounds
+// the reference by the hexagon's corners mapped through the moved v0, e1, e2, intersected with the whole triangle's box.
+// Six floats per record: umin, umax, vmin, vmax, smin, smax, each widened outward by kPieceMargin and clamped to [0, 1].
+// The margin: a hit's (u, v) comes out of the fp32 ray / triangle test with a few ulps of error, and the hexagon's bounds
+// lose at most one fp32 rounding (6e-8) when they are stored; 1e-5 is two orders above either, and no more than half the
+// pad (2e-5 of the scene diagonal) in world units for the largest triangle a scene can hold.  The boxes also keep the
+// refit's `pad`, as every box does.  A reference that is its whole triangle lies inside its leaf's box with `pad` to
+// spare, so its region comes out as all of [0, 1] ("whole") and it takes the plain refit's box: a tree without pieces
+// gets the plain refit's records.  (That needs `pad` to exceed an ulp of the coordinates — a scene nearer to the origin
+// than some 300 of its diagonals — which is the regime in which the build's own pad means anything.)
+constexpr int kPieceFloats = 6;
+constexpr double kPieceMargin = 1e-5;
+constexpr int kPiecePolyMax = 12;  // a triangle cut by six half-planes: at most nine vertices
+BVH_HD inline bool bvhPieceIsWhole(const float* g) {
+  return g[0] <= 0.0f && g[1] >= 1.0f && g[2] <= 0.0f && g[3] >= 1.0f && g[4] <= 0.0f && g[5] >= 1.0f;
+}
+// The region of the triangle (v0, e1, e2) inside the box [blo, bhi]: the triangle {(0,0), (1,0), (0,1)} clipped in (u, v)
+// against the six half-planes lo_a <= v0_a + u e1_a + v e2_a <= hi_a in double precision (Sutherland-Hodgman, as the
+// alpha clipper's polygons).  Nothing left (numerically), or anything not finite: the whole triangle.
+BVH_HD inline void bvhPieceRegion(const float* v0, const float* e1, const float* e2, const float* blo, const float* bhi, float* g) {
+  double pu[kPiecePolyMax], pv[kPiecePolyMax], qu[kPiecePolyMax], qv[kPiecePolyMax];
+  int n = 3;
+  pu[0] = 0.0, pv[0] = 0.0;
+  pu[1] = 1.0, pv[1] = 0.0;
+  pu[2] = 0.0, pv[2] = 1.0;
+  for (int h = 0; h < 6 && n > 0; h++) {
+    const int a = h >> 1;
+    // inside: f(u, v) >= 0
+    const double sg = (h & 1) ? -1.0 : 1.0;
+    const double c0 = sg * ((double)v0[a] - (double)((h & 1) ? bhi[a] : blo[a])), cu = sg * (double)e1[a], cv = sg * (double)e2[a];
+    int m = 0;
+    for (int i = 0; i < n; i++) {
+      const int j = i + 1 == n ? 0 : i + 1;
+      const double fi = c0 + pu[i] * cu + pv[i] * cv, fj = c0 + pu[j] * cu + pv[j] * cv;
+      const bool ini = fi >= 0.0, inj = fj >= 0.0;
+      if (ini && m < kPiecePolyMax) {
+        qu[m] = pu[i];
+        qv[m] = pv[i];
+        m++;
+      }
+      if (ini != inj && m < kPiecePolyMax) {
+        const double t = fi / (fi - fj);
+        qu[m] = pu[i] + t * (pu[j] - pu[i]);
+        qv[m] = pv[i] + t * (pv[j] - pv[i]);
+        m++;
+      }
+    }
+    n = m;
+    for (int i = 0; i < n; i++) {
+      pu[i] = qu[i];
+      pv[i] = qv[i];
+    }
+  }
+  double r[6] = {1e30, -1e30, 1e30, -1e30, 1e30, -1e30};
+  for (int i = 0; i < n; i++) {
+    const double s = pu[i] + pv[i];
+    r[0] = pu[i] < r[0] ? pu[i] : r[0];
+    r[1] = r[1] < pu[i] ? pu[i] : r[1];
+    r[2] = pv[i] < r[2] ? pv[i] : r[2];
+    r[3] = r[3] < pv[i] ? pv[i] : r[3];
+    r[4] = s < r[4] ? s : r[4];
+    r[5] = r[5] < s ? s : r[5];
+  }
+  bool ok = n > 0;
+  for (int i = 0; i < 6; i++) ok = ok && r[i] >= -1e30 && r[i] <= 1e30;  // (false for a NaN)
+  for (int i = 0; i < 6; i++) {
+    double x = ok ? r[i] + ((i & 1) ? kPieceMargin : -kPieceMargin) : ((i & 1) ? 1.0 : 0.0);
+    x = x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x);
+    g[i] = (float)x;
+  }
+}
+// Corner i (0..7) of the hexagon g: (u, max(vmin, smin - u)) and (u, min(vmax, smax - u)) for u = umin, umax, then
+// (max(umin, smin - v), v) and (min(umax, smax - v), v) for v = vmin, vmax.  Every vertex of the hexagon lies on a u or a v
+// bound, so these eight contain them all.  A range that rounding leaves empty still gives both of its ends: that only
+// loosens the box.
+BVH_HD inline void bvhPieceCorner(const float* g, int i, float& u, float& v) {
+  const float fixed = g[((i >> 2) << 1) + ((i >> 1) & 1)];  // umin, umax, vmin, vmax for i >> 1 = 0..3
+  const float olo = g[i & 4 ? 0 : 2], ohi = g[i & 4 ? 1 : 3];  // the other coordinate's own bounds
+  float other;
+  if (i & 1) {
+    const float t = g[5] - fixed;
+    other = ohi < t ? ohi : t;
+  } else {
+    const float t = g[4] - fixed;
+    other = olo < t ? t : olo;
+  }
+  u = i & 4 ? other : fixed;
+  v = i & 4 ? fixed : other;
+}
+// The box of the eight corners mapped through (v0 + u e1) + v e2 in fp32, in corner order, intersected with the box
+// (lo, hi) it is handed (the five-point box of the whole triangle), which it overwrites.
+BVH_HD inline void bvhPieceBox(const float* v0, const float* e1, const float* e2, const float* g, float* lo, float* hi) {
+  const float gg[6] = {g[0], g[1], g[2], g[3], g[4], g[5]};
+  float l[3] = {1e30f, 1e30f, 1e30f}, h[3] = {-1e30f, -1e30f, -1e30f};
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int i = 0; i < 8; i++) {
+    float u, v;
+    bvhPieceCorner(gg, i, u, v);
+    for (int a = 0; a < 3; a++) {
+      const float p = (v0[a] + u * e1[a]) + v * e2[a];
+      l[a] = p < l[a] ? p : l[a];
+      h[a] = h[a] < p ? p : h[a];
+    }
+  }
+  for (int a = 0; a < 3; a++) {
+    lo[a] = lo[a] < l[a] ? l[a] : lo[a];
+    hi[a] = h[a] < hi[a] ? h[a] : hi[a];
+  }
+}
+
 // ---- refit (bdpt_update_geometry): new vertex positions, the same tree ----
 // Everything in the records that derives from positions is rewritten in place; the layout, every record index, leaf bits,
 // childBase, child offsets and the prim / flags / aux words of the triangles stay.  A reference is bounded by its whole
@@ -492,8 +609,11 @@ bool bvhRefitMakePlan(const BvhRec* recs, size_t numRecs, BvhRefitPlan& plan, st
 // One node of one level.  box: 6 floats (exact lo, hi) per plan node, read for interior children, written for this one;
 // childArea: 4 per plan node (BvhBox::area of each child's exact box, 0 for an unused slot).  The leaf children's
 // triangle records are rewritten here too (v0, e1, e2 from prim and the indices).
-BVH_HD inline void bvhRefitNode(const BvhRefitNode& nd, uint32_t self, BvhRec* recs, const float* pos, const uint32_t* idx, float* box, float* childArea,
-                                float pad) {
+// PIECES: `region` holds six floats per record (bvhPieceRegion, below "piece-tight refit"); a reference whose region is
+// not the whole triangle is bounded by the region's mapped corners instead.  The plain refit is the instance without.
+template <bool PIECES>
+BVH_HD inline void bvhRefitNodeT(const BvhRefitNode& nd, uint32_t self, BvhRec* recs, const float* pos, const uint32_t* idx, float* box, float* childArea,
+                                 float pad, const float* region) {
   float lo[4][3], hi[4][3];
   for (int k = 0; k < 4; k++) {
     if (k >= (int)nd.nk) {
@@ -516,6 +636,10 @@ BVH_HD inline void bvhRefitNode(const BvhRefitNode& nd, uint32_t self, BvhRec* r
         const float* pc = pos + (size_t)idx[(size_t)t * 3 + 2] * 3;
         float v0[3], e1[3], e2[3], tl[3], th[3];
         bvhTriGeom(pa, pb, pc, v0, e1, e2, tl, th);
+        if constexpr (PIECES) {
+          const float* g = region + (size_t)(at + j) * kPieceFloats;
+          if (!bvhPieceIsWhole(g)) bvhPieceBox(v0, e1, e2, g, tl, th);
+        }
         for (int a = 0; a < 3; a++) {
           __builtin_memcpy(&r.w[a], &v0[a], 4);
           __builtin_memcpy(&r.w[4 + a], &e1[a], 4);
@@ -551,11 +675,53 @@ BVH_HD inline void bvhRefitNode(const BvhRefitNode& nd, uint32_t self, BvhRec* r
   BvhRec& r = recs[nd.rec];
   for (int i = 0; i < 10; i++) r.w[i] = i == 3 ? (w[3] | (r.w[3] & 0xff000000u)) : w[i];
 }
+BVH_HD inline void bvhRefitNode(const BvhRefitNode& nd, uint32_t self, BvhRec* recs, const float* pos, const uint32_t* idx, float* box, float* childArea,
+                                float pad) {
+  bvhRefitNodeT<false>(nd, self, recs, pos, idx, box, childArea, pad, nullptr);
+}
+BVH_HD inline void bvhRefitNodePieces(const BvhRefitNode& nd, uint32_t self, BvhRec* recs, const float* pos, const uint32_t* idx, float* box,
+                                      float* childArea, float pad, const float* region) {
+  bvhRefitNodeT<true>(nd, self, recs, pos, idx, box, childArea, pad, region);
+}
+// The regions of one plan node's leaf children, from the records AS BUILT: the child's box decoded from the node's origin,
+// scale exponents and plane bytes (bvhDecodePlane's arithmetic), every one of its references clipped to it.  Writes
+// region[kPieceFloats * record] of the triangle records; node records' slots are never read.
+BVH_HD inline void bvhPieceRegionsOfNode(const BvhRefitNode& nd, const BvhRec* recs, float* region) {
+  const BvhRec& n = recs[nd.rec];
+  for (int k = 0; k < (int)nd.nk; k++) {
+    const uint32_t kd = nd.kid[k];
+    if (!(kd & kRefitLeaf)) continue;
+    float blo[3], bhi[3];
+    for (int a = 0; a < 3; a++) {
+      float org, sc;
+      __builtin_memcpy(&org, &n.w[a], 4);
+      const uint32_t sb = ((n.w[3] >> (8 * a)) & 0xffu) << 23;
+      __builtin_memcpy(&sc, &sb, 4);
+      blo[a] = org + (float)((n.w[4 + a] >> (8 * k)) & 0xffu) * sc;
+      bhi[a] = org + (float)((n.w[7 + a] >> (8 * k)) & 0xffu) * sc;
+    }
+    const uint32_t at = n.w[10] + ((n.w[11] >> (8 * k)) & 0xffu);
+    for (uint32_t j = 0; j < (kd & ~kRefitLeaf); j++) {
+      const BvhRec& r = recs[at + j];
+      float v0[3], e1[3], e2[3];
+      for (int a = 0; a < 3; a++) {
+        __builtin_memcpy(&v0[a], &r.w[a], 4);
+        __builtin_memcpy(&e1[a], &r.w[4 + a], 4);
+        __builtin_memcpy(&e2[a], &r.w[8 + a], 4);
+      }
+      bvhPieceRegion(v0, e1, e2, blo, bhi, region + (size_t)(at + j) * kPieceFloats);
+    }
+  }
+}
+// Every node's regions on the host (the definition the device's k_refit_regions matches bit for bit).  region: sized by
+// it, kPieceFloats per record, zero where no triangle record lies.
+void bvhPieceRegionsHost(const BvhRec* recs, size_t numRecs, const BvhRefitPlan& plan, std::vector<float>& region, int threads = 0);
 // The SAH cost of a refitted tree with the formula of the build (bvh_build.cpp sahCost, bvh_device.hip k_sah_terms /
 // k_sah_sum): float terms, summed in double in node order in blocks of 65536 nodes, the block sums in block order.
 float bvhRefitSah(const BvhRefitPlan& plan, const float* rootBox, const float* childArea);
 // The whole refit on the host (the definition the device refit matches bit for bit).  box / childArea: sized by it.
+// pieces: the regions of bvhPieceRegionsHost for the piece-tight refit, null for the plain one.
 void bvhRefitHost(BvhRec* recs, const BvhRefitPlan& plan, const float* positions, const uint32_t* indices, uint32_t numTris,
-                  std::vector<float>& box, std::vector<float>& childArea, int threads = 0);
+                  std::vector<float>& box, std::vector<float>& childArea, int threads = 0, const float* pieces = nullptr);
 
 }  // namespace bdpt

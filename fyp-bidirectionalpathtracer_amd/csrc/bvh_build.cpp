@@ -1430,8 +1430,16 @@ float bvhRefitSah(const BvhRefitPlan& plan, const float* rootBox, const float* c
   return (float)cost + kCostTraverse;
 }
 
+void bvhPieceRegionsHost(const BvhRec* recs, size_t numRecs, const BvhRefitPlan& plan, std::vector<float>& region, int threads) {
+  if (threads <= 0) threads = bvhBuildThreads();
+  region.assign(numRecs * kPieceFloats, 0.0f);
+  parallelFor(plan.nodes.size(), threads, [&](size_t i0, size_t i1, int) {
+    for (size_t i = i0; i < i1; i++) bvhPieceRegionsOfNode(plan.nodes[i], recs, region.data());
+  });
+}
+
 void bvhRefitHost(BvhRec* recs, const BvhRefitPlan& plan, const float* positions, const uint32_t* indices, uint32_t numTris,
-                  std::vector<float>& box, std::vector<float>& childArea, int threads) {
+                  std::vector<float>& box, std::vector<float>& childArea, int threads, const float* pieces) {
   if (threads <= 0) threads = bvhBuildThreads();
   float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};  // the scene box over every input triangle
   for (uint32_t t = 0; t < numTris; t++) {
@@ -1451,7 +1459,10 @@ void bvhRefitHost(BvhRec* recs, const BvhRefitPlan& plan, const float* positions
     parallelFor(n, threads, [&](size_t i0, size_t i1, int) {
       for (size_t i = i0; i < i1; i++) {
         const uint32_t self = plan.levelOrder[a + i];
-        bvhRefitNode(plan.nodes[self], self, recs, positions, indices, box.data(), childArea.data(), pad);
+        if (pieces)
+          bvhRefitNodePieces(plan.nodes[self], self, recs, positions, indices, box.data(), childArea.data(), pad, pieces);
+        else
+          bvhRefitNode(plan.nodes[self], self, recs, positions, indices, box.data(), childArea.data(), pad);
       }
     });
   }

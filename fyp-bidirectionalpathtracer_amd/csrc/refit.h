@@ -19,9 +19,13 @@ struct RefitDev {
   float* partial;    // 6 * kRefitPartials
   float* pad;        // 1
   uint32_t numNodes;
+  const float* region;  // kPieceFloats per record (launchRefitRegions): the piece-tight refit; null: the plain one
 };
 // refits `recs` to `positions` (device, 3 floats per vertex) and rewrites the shading records' positions and, when
 // `normals` is given, normals; enqueued on `st`, allocates nothing
 void launchRefit(const RefitDev& R, BvhRec* recs, float4* shade, const uint32_t* indices, uint32_t numTris, const float* positions, const float* normals,
                  hipStream_t st);
+// bdpt_prepare(BDPT_PREPARE_REFIT_PIECES): the regions (bvh.h "piece-tight refit") of the records AS BUILT into `region`,
+// kPieceFloats per record; enqueued on `st`
+void launchRefitRegions(const RefitDev& R, const BvhRec* recs, float* region, hipStream_t st);
 }  // namespace bdpt

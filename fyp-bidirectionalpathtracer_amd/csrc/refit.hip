@@ -9,6 +9,8 @@
 //   2. one launch per level of the plan, deepest first: a thread per node rewrites its leaf children's triangle records,
 //      takes the union of its children's exact boxes and quantises (min / max only: no order dependence)
 //   3. the shading records (positions, normals when given)
+// With regions (bdpt_prepare(BDPT_PREPARE_REFIT_PIECES), made once by k_refit_regions from the tree as built) step 2 runs
+// its piece-tight instance: a split or clipped reference is bounded by its piece, not by its whole triangle.
 // Nothing here allocates or synchronises: the plan and the scratch are the caller's (api.cpp), so an update with
 // device-pointer inputs can be captured into a hipGraph.
 #include <hip/hip_runtime.h>
@@ -90,6 +92,27 @@ __global__ __launch_bounds__(256) void k_refit_level(const BvhRefitNode* __restr
   bvhRefitNode(nodes[self], self, recs, pos, idx, box, childArea, pad[0]);
 }
 
+// the piece-tight instance (bvh.h "piece-tight refit"): the same node function with the regions; fixed-size loops only,
+// no scratch
+__global__ __launch_bounds__(256) void k_refit_level_pieces(const BvhRefitNode* __restrict__ nodes, const uint32_t* __restrict__ order, uint32_t n,
+                                                           BvhRec* recs, const float* __restrict__ pos, const uint32_t* __restrict__ idx, float* box,
+                                                           float* __restrict__ childArea, const float* __restrict__ pad,
+                                                           const float* __restrict__ region) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t self = order[i];
+  bvhRefitNodePieces(nodes[self], self, recs, pos, idx, box, childArea, pad[0], region);
+}
+
+// the regions, once per scene: a thread per plan node, a loop over its leaf children (the clipper's polygons live in
+// scratch: this kernel runs once)
+__global__ __launch_bounds__(256) void k_refit_regions(const BvhRefitNode* __restrict__ nodes, uint32_t n, const BvhRec* __restrict__ recs,
+                                                      float* __restrict__ region) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bvhPieceRegionsOfNode(nodes[i], recs, region);
+}
+
 // positions (and normals) of the 112-byte shading records (api.cpp setSceneImpl): three (position, normal, uv) vertices
 // + material id; the uvs and the material id stay
 __global__ __launch_bounds__(256) void k_refit_shade(float4* __restrict__ shade, const uint32_t* __restrict__ idx, const float* __restrict__ pos,
@@ -121,9 +144,18 @@ void launchRefit(const RefitDev& R, BvhRec* recs, float4* shade, const uint32_t*
   hipLaunchKernelGGL(k_refit_pad, dim3(1), dim3(kBoxBlock), 0, st, R.partial, blocks, numTris, R.pad);
   for (size_t l = 0; l + 1 < R.levelStart.size(); l++) {
     const uint32_t a = R.levelStart[l], n = R.levelStart[l + 1] - a;
-    if (n) hipLaunchKernelGGL(k_refit_level, dim3((n + 255) / 256), dim3(256), 0, st, R.nodes, R.levelOrder + a, n, recs, positions, indices, R.box, R.childArea, R.pad);
+    if (!n) continue;
+    if (R.region)
+      hipLaunchKernelGGL(k_refit_level_pieces, dim3((n + 255) / 256), dim3(256), 0, st, R.nodes, R.levelOrder + a, n, recs, positions, indices, R.box,
+                         R.childArea, R.pad, R.region);
+    else
+      hipLaunchKernelGGL(k_refit_level, dim3((n + 255) / 256), dim3(256), 0, st, R.nodes, R.levelOrder + a, n, recs, positions, indices, R.box, R.childArea, R.pad);
   }
   if (numTris) hipLaunchKernelGGL(k_refit_shade, dim3((numTris + 255) / 256), dim3(256), 0, st, shade, indices, positions, normals, numTris);
+}
+
+void launchRefitRegions(const RefitDev& R, const BvhRec* recs, float* region, hipStream_t st) {
+  if (R.numNodes) hipLaunchKernelGGL(k_refit_regions, dim3((R.numNodes + 255) / 256), dim3(256), 0, st, R.nodes, R.numNodes, recs, region);
 }
 
 }  // namespace bdpt

@@ -149,6 +149,8 @@ struct HostScene {
   BvhRefitPlan plan;
   std::vector<BvhRec> builtRecs;
   std::vector<float> box, childArea;
+  // bdpt_host_bvh_refit_pieces: the regions of the tree as built (empty: the plain refit)
+  std::vector<float> pieces;
 };
 
 inline float clampedRcpHost(float d) {
@@ -588,25 +590,46 @@ int bdpt_host_bvh_trace(void* h, const float* rays, uint32_t n, int mode, int br
 }
 
 // ---- host refit hooks (bdpt_update_geometry's definition on the CPU) --------------------------------------------
+namespace {
+// the plan of a handle's tree as built, and a copy of its records, on first use
+int hostRefitPlan(HostScene& S) {
+  Bvh& bvh = S.sb.bvh;
+  if (bvh.recs.empty()) return BDPT_E_STATE;
+  if (!S.builtRecs.empty()) return BDPT_OK;
+  // the tree walk of bdpt_host_bvh_trace reads nodes / tris: they are decoded back from the refitted records
+  // (plan order = node order, packBvh).  A plan of another size would leave that walk on the old tree: refused.
+  std::string err;
+  if (!bvhRefitMakePlan(bvh.recs.data(), bvh.recs.size(), S.plan, err)) return BDPT_E_INVALID;
+  if (bvh.nodes.size() != S.plan.nodes.size()) {
+    S.plan = BvhRefitPlan{};
+    return BDPT_E_STATE;
+  }
+  S.builtRecs.assign(bvh.recs.begin(), bvh.recs.end());
+  return BDPT_OK;
+}
+}  // namespace
+
+int bdpt_host_bvh_refit_pieces(void* h) try {
+  if (!h) return BDPT_E_INVALID;
+  HostScene& S = *static_cast<HostScene*>(h);
+  if (S.refitted) return BDPT_E_STATE;  // the regions come from the boxes as built, and those are gone
+  if (int rc = hostRefitPlan(S)) return rc;
+  bvhPieceRegionsHost(S.sb.bvh.recs.data(), S.sb.bvh.recs.size(), S.plan, S.pieces);
+  return BDPT_OK;
+} catch (const std::bad_alloc&) {
+  return BDPT_E_NOMEM;
+} catch (...) {
+  return BDPT_E_INVALID;
+}
+
 int bdpt_host_bvh_refit(void* h, const float* positions) try {
   if (!h || !positions) return BDPT_E_INVALID;
   HostScene& S = *static_cast<HostScene*>(h);
   Bvh& bvh = S.sb.bvh;
   const bdpt_scene_desc* d = S.d;
-  if (bvh.recs.empty()) return BDPT_E_STATE;
-  if (!S.refitted) {
-    // the tree walk of bdpt_host_bvh_trace reads nodes / tris: they are decoded back from the refitted records below
-    // (plan order = node order, packBvh).  A plan of another size would leave that walk on the old tree: refused.
-    std::string err;
-    if (!bvhRefitMakePlan(bvh.recs.data(), bvh.recs.size(), S.plan, err)) return BDPT_E_INVALID;
-    if (bvh.nodes.size() != S.plan.nodes.size()) {
-      S.plan = BvhRefitPlan{};
-      return BDPT_E_STATE;
-    }
-    S.builtRecs.assign(bvh.recs.begin(), bvh.recs.end());
-    S.refitted = true;
-  }
-  bvhRefitHost(bvh.recs.data(), S.plan, positions, d->indices, d->numTriangles, S.box, S.childArea);
+  if (int rc = hostRefitPlan(S)) return rc;
+  S.refitted = true;
+  bvhRefitHost(bvh.recs.data(), S.plan, positions, d->indices, d->numTriangles, S.box, S.childArea, 0, S.pieces.empty() ? nullptr : S.pieces.data());
   for (size_t w = 0; w < S.plan.nodes.size(); w++) {
     const BvhRefitNode& pn = S.plan.nodes[w];
     const BvhRec& r = bvh.recs[pn.rec];
@@ -704,6 +727,17 @@ int bdpt_host_bvh_refit_check(void* h, char* msg, uint32_t msgCap) try {
         std::memcpy(v0, &t.w[0], 12);
         std::memcpy(e1, &t.w[4], 12);
         std::memcpy(e2, &t.w[8], 12);
+        if (!S.pieces.empty()) {  // the piece refit: the reference's eight mapped corners instead of its triangle
+          for (int i = 0; i < 8; i++) {
+            float u, v;
+            bvhPieceCorner(S.pieces.data() + (size_t)(at + j) * kPieceFloats, i, u, v);
+            for (int a = 0; a < 3; a++) {
+              const float q = (v0[a] + u * e1[a]) + v * e2[a];
+              if (!(q >= c.lo[a] && q <= c.hi[a])) return say("a piece of triangle " + std::to_string(t.w[3]) + " outside an ancestor box");
+            }
+          }
+          continue;
+        }
         for (int a = 0; a < 3; a++) {
           const float p[3] = {v0[a], v0[a] + e1[a], v0[a] + e2[a]};
           for (float q : p)

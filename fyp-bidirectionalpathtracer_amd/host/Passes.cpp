@@ -388,6 +388,23 @@ void RayLaunch::setScene(Scene::SharedPtr pScene) {
       mSceneSet = false;
     }
   if (mSceneSet && mMotion) prepareMotion();  // (a new scene dropped the previous pose)
+  if (mSceneSet && mTightRefit) prepareTightRefit();  // (... and the piece regions)
+}
+bool RayLaunch::prepareTightRefit() {
+  const uint32_t n = (uint32_t)mMore.size() + 1;
+  for (uint32_t s = 0; s < n; s++) {
+    bdpt_ctx* c = s == 0 ? mCtx : mMore[s - 1];
+    if (bdpt_prepare(c, BDPT_PREPARE_REFIT_PIECES) != BDPT_OK) {
+      std::fprintf(stderr, "[RayLaunch] bdpt_prepare(BDPT_PREPARE_REFIT_PIECES) failed: %s\n", bdpt_last_error(c));
+      return false;
+    }
+  }
+  return true;
+}
+bool RayLaunch::requestTightRefit() {
+  if (!mCtx) return false;
+  mTightRefit = true;
+  return mSceneSet ? prepareTightRefit() : true;
 }
 bool RayLaunch::prepareMotion() {
   const uint32_t n = (uint32_t)mMore.size() + 1;
@@ -1174,6 +1191,10 @@ bool RenderingPipeline::updateGeometry(const float* positions, const float* norm
 bool RenderingPipeline::setSkin(const bdpt_skin_desc* skin) {
   RayLaunch::SharedPtr rays = mpRays ? mpRays : RayLaunch::create(&mContext);
   return rays && mpScene && rays->setSkin(skin);
+}
+bool RenderingPipeline::setTightRefit() {
+  RayLaunch::SharedPtr rays = mpRays ? mpRays : RayLaunch::create(&mContext);
+  return rays && rays->requestTightRefit();
 }
 bool RenderingPipeline::updateSkinned(const float* bones, const float* normalBones, uint32_t numBones, uint32_t memory, bool keepLightMaps) {
   RayLaunch::SharedPtr rays = mpRays ? mpRays : RayLaunch::create(&mContext);

@@ -35,6 +35,9 @@ class RayLaunch {
   bool requestMotion();
   bool motion() const { return mMotion; }
   bool keepPose(const std::vector<hipStream_t>& streams, uint32_t first);
+  // Piece-tight refit (include/bdpt.h "Animated scenes"): every frame slot's context prepares it with its scene
+  // (bdpt_prepare(BDPT_PREPARE_REFIT_PIECES)), before the scene's first update; later updates then refit by pieces.
+  bool requestTightRefit();
   void setMaxRecursionDepth(uint32_t d) { mMaxDepth = d; }
   bool readyToRender() const { return mCtx && mSceneSet; }
   // (re)size the per-pixel path state; called by execute when the screen size changed
@@ -71,6 +74,8 @@ class RayLaunch {
   bool mSceneSet = false;
   bool mMotion = false;
   bool prepareMotion();
+  bool mTightRefit = false;
+  bool prepareTightRefit();
   uint32_t mW = 0, mH = 0, mMaxDepth = 8, mSizedDepth = 0;
 };
 
@@ -284,6 +289,10 @@ class RenderingPipeline {
   bool setSkin(const bdpt_skin_desc* skin);
   bool updateSkinned(const float* bones, const float* normalBones, uint32_t numBones, uint32_t memory = BDPT_MEMORY_HOST,
                      bool keepLightMaps = false);
+  // Opt-in: split and alpha-clipped references are refitted by their piece instead of by their whole triangle (a tree that
+  // stays close to its built quality under updateGeometry / updateSkinned).  Call it after initialize() and before the
+  // scene's first update; it synchronises.
+  bool setTightRefit();
   Scene::SharedPtr getScene() const { return mpScene; }
   size_t getPassCount() const { return mActivePasses.size(); }
 

@@ -42,6 +42,7 @@ struct Options {
   bool areaLights = false;  // BDPT_PARAM_AREA_LIGHTS: emissive triangles light the scene (NEE and light subpaths)
   float sway = 0.0f;  // > 0: an animated scene — before every frame the vertices move by up to this fraction of the scene's extent
   bool noMotion = false;  // --sway / --bend with --denoise: keep the denoiser's static-scene reprojection (for comparison)
+  bool tightRefit = false;  // --sway / --bend: refit split and alpha-clipped references by their piece (BDPT_PREPARE_REFIT_PIECES)
   float bend = 0.0f;  // > 0: a skinned scene — a small rig along the scene's height, bent by up to this angle (radians) before every frame
 };
 
@@ -175,6 +176,11 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
     return res;
   }
 
+  if (o.tightRefit && (o.sway > 0.0f || o.bend > 0.0f) && !pipeline->setTightRefit()) {
+    std::fprintf(stderr, "bdpt_render: setTightRefit failed\n");
+    env.failLate();
+    return res;
+  }
   int warmup = o.warmup;
   if (warmup < 0 || warmup >= o.frames) warmup = 0;
   // --sway: a smooth displacement of every vertex before every frame (bdpt_update_geometry through the pipeline)
@@ -299,6 +305,7 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
     if (tiled) std::printf(", %u GPU%s (interleaved stripes of %u rows, RCCL reduce-scatter + all-gather)", world, world == 1 ? "" : "s",
                            bdpt_stripe_rows(o.H, world));
     if (o.denoise && (o.sway > 0.0f || o.bend > 0.0f) && !o.noMotion && !tiled) std::printf(", denoiser history reprojected through the previous pose");
+    if (o.tightRefit && (o.sway > 0.0f || o.bend > 0.0f)) std::printf(", references refitted by their pieces");
     std::printf("\n");
     writePfm(o.out.c_str(), img, o.W, o.H);
   }
@@ -346,6 +353,7 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--sway")) o.sway = (float)std::atof(v);
     else if (const char* v = next("--bend")) o.bend = (float)std::atof(v);
     else if (std::strcmp(argv[i], "--no-motion") == 0) o.noMotion = true;
+    else if (std::strcmp(argv[i], "--tight-refit") == 0) o.tightRefit = true;
     else if (const char* v = next("--gpus")) o.gpus = std::atoi(v);
     else if (const char* v = next("--rank")) o.rank = std::atoi(v);
     else if (const char* v = next("--world")) o.world = std::atoi(v);
@@ -354,7 +362,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }

@@ -422,7 +422,22 @@ int bdpt_set_environment(bdpt_ctx* ctx, const bdpt_environment* env);
  * After the first update, or after bdpt_prepare(BDPT_PREPARE_REFIT), a device-pointer update neither allocates nor
  * synchronises, so it can be captured into a hipGraph.
  * Errors: no scene BDPT_E_STATE; numVertices or the light count not the scene's BDPT_E_INVALID; more than
- * BDPT_MAX_LIGHTS lights BDPT_E_LIMIT. */
+ * BDPT_MAX_LIGHTS lights BDPT_E_LIMIT.
+ *
+ * Piece-tight refit (opt-in, per context): bdpt_prepare(BDPT_PREPARE_REFIT_PIECES).  The plain refit bounds every
+ * reference by its whole triangle, which gives away what spatial pre-splitting and alpha clipping bought at build time.
+ * A reference stands for a piece of its triangle, and a per-vertex update maps a triangle affinely, so the piece keeps
+ * its footprint in the triangle's barycentric plane.  The prepare derives, once, from the tree as built, a small
+ * barycentric region per reference that contains its piece (DESIGN.md "Refit"); from then on every bdpt_update_geometry
+ * and bdpt_update_skinned of the context bounds a reference by that region under the moved corners.  It implies
+ * BDPT_PREPARE_REFIT, needs a scene and no update since bdpt_set_scene (after one the built boxes are gone), allocates
+ * (24 bytes per record of the tree) and synchronises: BDPT_E_STATE without a scene, after an update, or inside a stream
+ * capture.  bdpt_set_scene drops it.  Updates still neither allocate nor synchronise with device pointers and stay
+ * capturable; bdpt_get_refit_info reports the tighter tree's cost.  Guarantees:
+ *   - every query answers exactly as it does on a tree built at the new positions: images are bit-identical, as for the
+ *     plain refit;
+ *   - the records are a pure function of the built tree and the current positions;
+ *   - a tree without split or clipped references gets exactly the plain refit's records. */
 #define BDPT_MEMORY_HOST 0u
 #define BDPT_MEMORY_DEVICE 1u
 typedef struct bdpt_geometry_update {
@@ -927,8 +942,12 @@ int bdpt_host_bvh_trace(void* handle, const float* rays, uint32_t n, int mode, i
  * words 10-11 and the leaf bits of every node and prim / flags / aux of every triangle unchanged, every triangle inside
  * every decoded ancestor box (BDPT_E_INVALID + msg otherwise).  _recs_hash: FNV-1a over the handle's records (as
  * bdpt_bvh_recs_hash); bdpt_ctx_recs_hash: the same over a context's records (synchronises).  _refit_info: as
- * bdpt_get_refit_info. */
+ * bdpt_get_refit_info.  _refit_pieces: derives the piece regions of the handle's tree as built
+ * (BDPT_PREPARE_REFIT_PIECES on the host) and makes later _refit calls use them; BDPT_E_STATE after a refit,
+ * BDPT_E_INVALID for NULL.  In that mode _refit_check checks, in place of every triangle, every reference's eight mapped
+ * region corners inside every decoded ancestor box. */
 int bdpt_host_bvh_refit(void* handle, const float* positions);
+int bdpt_host_bvh_refit_pieces(void* handle);
 int bdpt_host_bvh_refit_check(void* handle, char* msg, uint32_t msgCap);
 int bdpt_host_bvh_recs_hash(void* handle, uint64_t* out_hash);
 int bdpt_host_bvh_refit_info(void* handle, bdpt_refit_info* out);
@@ -974,6 +993,7 @@ int bdpt_tile_row_ranges(const bdpt_ctx* ctx, uint32_t* out_first_last, uint32_t
 #define BDPT_PREPARE_AREA_LIGHTS 16u /* the emitter table of BDPT_PARAM_AREA_LIGHTS (needs a scene, not a size) */
 #define BDPT_PREPARE_LIGHT_GROUP_TABLE 32u /* numLights + 1 splat planes: the most an assignment of bdpt_execute_grouped needs */
 #define BDPT_PREPARE_MOTION 64u /* the previous pose of bdpt_keep_pose, filled from the current one (needs a scene, not a size) */
+#define BDPT_PREPARE_REFIT_PIECES 128u /* BDPT_PREPARE_REFIT plus the piece regions: later updates refit by pieces ("Animated scenes"; needs a scene, no update yet) */
 int bdpt_prepare(bdpt_ctx* ctx, uint32_t what);
 
 /* Primary-visibility pass.  Writes the tile rows of all six channels. */

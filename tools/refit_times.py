@@ -13,7 +13,16 @@
 The sway: a small smooth displacement (0.5 % of the scene extent at most) of the foliage vertices (those of alpha-mode
 materials; in a scene without any, its upper half) over 30 frames, ending where it started.
 
-  python tools/refit_times.py [--configs 2,4] [--frames 5]
+With --pieces, in the same run, the piece-tight refit (bdpt_prepare(BDPT_PREPARE_REFIT_PIECES)) on the rebuilt tree:
+
+  pieces.prepare_ms / table_bytes   the prepare after BDPT_PREPARE_REFIT (wall, synchronised: the regions alone) and the
+                                    region table (24 B per record)
+  pieces.update_ms                  device-pointer updates, light maps re-traced / kept, as update_ms above (the plain
+                                    figures to compare with are update_ms.device_* of the same line)
+  pieces.sah_ratio, trees.after_sway_pieces
+                                    the same 30-update sway as above, refitted by pieces
+
+  python tools/refit_times.py [--configs 2,4] [--frames 5] [--pieces]
 """
 import argparse
 import ctypes as C
@@ -33,6 +42,7 @@ def main():
     ap.add_argument("--configs", default="2,4")
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--pieces", action="store_true")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as ge
@@ -90,27 +100,32 @@ def main():
         poses_dev = [torch.from_numpy(pose(t)).cuda() for t in (3, 7)]
         poses_host = [pose(t) for t in (3, 7)]
         pipe.ctx.prepare(pkg.abi.PREPARE_REFIT)
-        upd = {}
-        for mem in ("device", "host"):
-            for keep in (False, True):
-                ms, wall = [], []
-                for r in range(2 + args.reps):
-                    p = (poses_dev if mem == "device" else poses_host)[r % 2]
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    t0 = time.perf_counter()
-                    e0.record(st)
-                    pipe.ctx.update_geometry(p, stream=C.c_void_p(st.cuda_stream), keep_light_maps=keep)
-                    e1.record(st)
-                    t1 = time.perf_counter()
-                    torch.cuda.synchronize()
-                    if r >= 2:
-                        ms.append(e0.elapsed_time(e1))
-                        wall.append((t1 - t0) * 1e3)
-                k = f"{mem}_{'keep_maps' if keep else 'retrace_maps'}"
-                upd[k] = {"device_ms": round(statistics.median(ms), 3)}
-                if mem == "host":
-                    upd[k]["call_wall_ms"] = round(statistics.median(wall), 3)
+
+        def update_times(mems):
+            upd = {}
+            for mem in mems:
+                for keep in (False, True):
+                    ms, wall = [], []
+                    for r in range(2 + args.reps):
+                        p = (poses_dev if mem == "device" else poses_host)[r % 2]
+                        torch.cuda.synchronize()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        t0 = time.perf_counter()
+                        e0.record(st)
+                        pipe.ctx.update_geometry(p, stream=C.c_void_p(st.cuda_stream), keep_light_maps=keep)
+                        e1.record(st)
+                        t1 = time.perf_counter()
+                        torch.cuda.synchronize()
+                        if r >= 2:
+                            ms.append(e0.elapsed_time(e1))
+                            wall.append((t1 - t0) * 1e3)
+                    k = f"{mem}_{'keep_maps' if keep else 'retrace_maps'}"
+                    upd[k] = {"device_ms": round(statistics.median(ms), 3)}
+                    if mem == "host":
+                        upd[k]["call_wall_ms"] = round(statistics.median(wall), 3)
+            return upd
+
+        upd = update_times(("device", "host"))
         out["update_ms"] = upd
         for t in range(30):  # the sway, light maps kept (the per-frame animation setting)
             pipe.update_geometry(torch.from_numpy(pose(t + 1)).cuda(), keep_light_maps=True)
@@ -131,6 +146,23 @@ def main():
         trees["rebuilt"] = frames()
         out["trees"] = trees
         out["refit_over_set_scene"] = round(upd["device_keep_maps"]["device_ms"] / (out["set_scene_s"] * 1e3), 5)
+        if args.pieces:  # the rebuilt tree has seen no update: the regions come from it
+            pipe.ctx.prepare(pkg.abi.PREPARE_REFIT)  # (the plan, as for the plain refit: not part of the figure)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pipe.ctx.prepare(refit_pieces=True)
+            torch.cuda.synchronize()
+            bi = pipe.ctx.bvh_info()
+            pc = {"prepare_ms": round((time.perf_counter() - t0) * 1e3, 3), "table_bytes": 24 * (int(bi.numNodes) + int(bi.numReferences) + 4)}
+            pc["update_ms"] = update_times(("device",))
+            for t in range(30):
+                pipe.update_geometry(torch.from_numpy(pose(t + 1)).cuda(), keep_light_maps=True)
+            torch.cuda.synchronize()
+            trees["after_sway_pieces"] = frames()
+            info = pipe.ctx.refit_info()
+            pc["sah_ratio"] = round(info.sahCost / info.sahCostBuilt, 4)
+            pc["refit_over_set_scene"] = round(pc["update_ms"]["device_keep_maps"]["device_ms"] / (out["set_scene_s"] * 1e3), 5)
+            out["pieces"] = pc
         print(json.dumps(out), flush=True)
         pipe.close()
         scene.close()
