@@ -112,23 +112,6 @@ void freeLightGroups(bdpt_ctx* c) {
   c->groupLightIdx = nullptr;
 }
 
-void freeBmfrPlanes(bdpt_ctx* c) {
-  for (int k = 0; k < 2; k++) {
-    if (c->planesPos[k]) (void)hipFree(c->planesPos[k]);
-    if (c->planesNorm[k]) (void)hipFree(c->planesNorm[k]);
-    c->planesPos[k] = c->planesNorm[k] = nullptr;
-  }
-  if (c->planesNoisy) (void)hipFree(c->planesNoisy);
-  if (c->planesFiltered) (void)hipFree(c->planesFiltered);
-  if (c->planesAccept) (void)hipFree(c->planesAccept);
-  if (c->planesPrevPixel) (void)hipFree(c->planesPrevPixel);
-  c->planesNoisy = c->planesFiltered = nullptr;
-  c->planesAccept = nullptr;
-  c->planesPrevPixel = nullptr;
-  c->planesSlots = 0;
-  c->planesRead = 0;
-}
-
 bool streamIsCapturing(hipStream_t st) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess) return false;
@@ -155,37 +138,67 @@ int allocOwnGbuffer(bdpt_ctx* c) {
   return BDPT_OK;
 }
 
-int allocBmfrHistory(bdpt_ctx* c) {
-  if (c->bmfrAccept) return BDPT_OK;
+// ---- the denoiser's history (context.hpp BmfrHistory) ----
+// the calls that allocate one ahead of a stream capture, as the refusal inside a capture names them
+constexpr const char* kBmfrPrepare = "bdpt_prepare(BDPT_PREPARE_BMFR)";
+constexpr const char* kBmfrPlanesPrepare = "bdpt_bmfr_planes_prepare";
+// (the device is idle, or the caller has synchronised it)
+void freeBmfrHistory(BmfrHistory& h) {
+  for (void* p : {(void*)h.pos[0], (void*)h.pos[1], (void*)h.norm[0], (void*)h.norm[1], (void*)h.noisy, (void*)h.filtered, (void*)h.accept,
+                  (void*)h.prevPixel})
+    if (p) (void)hipFree(p);
+  h = BmfrHistory{};
+}
+
+int resetBmfrHistory(bdpt_ctx* c, BmfrHistory& h) {
+  if (!h.accept) return BDPT_OK;  // nothing allocated yet
+  ENTER(c);
   const size_t n = (size_t)c->W * c->H;
-  const size_t mark = c->frameAllocs.size();
-  float4 *pos[2]{}, *norm[2]{}, *noisy[2]{}, *filt[2]{};
-  uint8_t* accept = nullptr;
-  uint32_t* prevPixel = nullptr;
-  int rc = BDPT_OK;
-  for (int k = 0; k < 2 && !rc; k++) {
-    if ((rc = devAlloc(c, c->frameAllocs, &pos[k], n)) || (rc = devAlloc(c, c->frameAllocs, &norm[k], n)) ||
-        (rc = devAlloc(c, c->frameAllocs, &noisy[k], n)) || (rc = devAlloc(c, c->frameAllocs, &filt[k], n)))
-      break;
-  }
-  if (!rc) rc = devAlloc(c, c->frameAllocs, &accept, n);
-  if (!rc) rc = devAlloc(c, c->frameAllocs, &prevPixel, n);
-  if (rc) {
-    while (c->frameAllocs.size() > mark) {
-      (void)hipFree(c->frameAllocs.back());
-      c->frameAllocs.pop_back();
-    }
-    return rc;
-  }
   for (int k = 0; k < 2; k++) {
-    c->bmfrPos[k] = pos[k];
-    c->bmfrNorm[k] = norm[k];
-    c->bmfrNoisy[k] = noisy[k];
-    c->bmfrFiltered[k] = filt[k];
+    HIPCHK(c, hipMemset(h.pos[k], 0, n * sizeof(float4)));
+    HIPCHK(c, hipMemset(h.norm[k], 0, n * sizeof(float4)));
   }
-  c->bmfrAccept = accept;
-  c->bmfrPrevPixel = prevPixel;
-  return bdpt_bmfr_reset(c);
+  HIPCHK(c, hipMemset(h.noisy, 0, 2 * n * sizeof(float4) * h.slots));
+  HIPCHK(c, hipMemset(h.filtered, 0, 2 * n * sizeof(float4) * h.slots));
+  HIPCHK(c, hipMemset(h.accept, 0, n));
+  HIPCHK(c, hipMemset(h.prevPixel, 0, n * sizeof(uint32_t)));
+  h.read = 0;
+  return BDPT_OK;
+}
+
+// History for at least `slots` images.  (Re)allocating resets; replacing a smaller history waits for the device first
+// (frames in flight still use it), the first allocation frees nothing and does not wait.  Not while `st` is being
+// captured: the message names `who` and the call (`prepare`) that allocates ahead of the capture.
+int ensureBmfrHistory(bdpt_ctx* c, BmfrHistory& h, uint32_t slots, hipStream_t st, const char* who, const char* prepare) {
+  if (h.accept && h.slots >= slots) return BDPT_OK;
+  if (streamIsCapturing(st)) {
+    fail(c, std::string(who) + ": the history needs " + prepare + " before stream capture");
+    return BDPT_E_STATE;
+  }
+  if (h.accept) {
+    HIPCHK(c, hipDeviceSynchronize());
+    freeBmfrHistory(h);
+  }
+  const size_t n = std::max<size_t>((size_t)c->W * c->H, 1);
+  void* a[8]{};
+  const size_t bytes[8] = {n * sizeof(float4), n * sizeof(float4), n * sizeof(float4), n * sizeof(float4),
+                           2 * n * sizeof(float4) * slots, 2 * n * sizeof(float4) * slots, std::max<size_t>(n, 16), n * sizeof(uint32_t)};
+  for (int k = 0; k < 8; k++)
+    if (hipMalloc(&a[k], bytes[k]) != hipSuccess) {
+      for (int j = 0; j < k; j++) (void)hipFree(a[j]);
+      fail(c, std::string(who) + ": hipMalloc of the history failed");
+      return BDPT_E_NOMEM;
+    }
+  h.pos[0] = static_cast<float4*>(a[0]);
+  h.pos[1] = static_cast<float4*>(a[1]);
+  h.norm[0] = static_cast<float4*>(a[2]);
+  h.norm[1] = static_cast<float4*>(a[3]);
+  h.noisy = static_cast<float4*>(a[4]);
+  h.filtered = static_cast<float4*>(a[5]);
+  h.accept = static_cast<uint8_t*>(a[6]);
+  h.prevPixel = static_cast<uint32_t*>(a[7]);
+  h.slots = slots;
+  return resetBmfrHistory(c, h);
 }
 
 void stageMark(bdpt_ctx* c, hipStream_t st, const char* name) {
@@ -383,7 +396,8 @@ void bdpt_destroy(bdpt_ctx* c) {
   if (c->rayCursor) (void)hipFree(c->rayCursor);
   if (c->adaptiveSum) (void)hipFree(c->adaptiveSum);
   freeLightGroups(c);
-  freeBmfrPlanes(c);
+  freeBmfrHistory(c->bmfr);
+  freeBmfrHistory(c->bmfrPlanes);
   freePool(c->sceneAllocs);
   freePool(c->skinAllocs);
   freePool(c->frameAllocs);
@@ -1249,11 +1263,9 @@ int resizeRows(bdpt_ctx* c, uint32_t width, uint32_t height, uint32_t maxDepth) 
   HIPCHK(c, hipDeviceSynchronize());
   freePool(c->frameAllocs);
   freeLightGroups(c);
-  freeBmfrPlanes(c);
-  for (int k = 0; k < 2; k++) c->bmfrPos[k] = c->bmfrNorm[k] = c->bmfrNoisy[k] = c->bmfrFiltered[k] = nullptr;
+  freeBmfrHistory(c->bmfr);
+  freeBmfrHistory(c->bmfrPlanes);
   c->ownGb = bdpt_gbuffer{};
-  c->bmfrAccept = nullptr;  // history goes with the frame (BlockwiseMultiOrderFeatureRegression::resize)
-  c->bmfrPrevPixel = nullptr;
   c->haveSize = false;
   c->W = width;
   c->H = height;
@@ -1928,7 +1940,7 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
   if (what & BDPT_PREPARE_PRIMARY)
     if (int rc = allocOwnGbuffer(c)) return rc;
   if (what & BDPT_PREPARE_BMFR)  // (whole-frame history also on a band / stripes context: bdpt_bmfr_execute takes whole-frame buffers)
-    if (int rc = allocBmfrHistory(c)) return rc;
+    if (int rc = ensureBmfrHistory(c, c->bmfr, 1, nullptr, "bmfr", kBmfrPrepare)) return rc;
   if (what & (BDPT_PREPARE_LIGHT_GROUPS | BDPT_PREPARE_LIGHT_GROUP_TABLE))  // (_TABLE: a plane for the emitter table's group too)
     if (int rc = allocLightGroups(c, nullptr, c->S.numLights + ((what & BDPT_PREPARE_LIGHT_GROUP_TABLE) ? 1u : 0u))) return rc;
   if (what & BDPT_PREPARE_AREA_LIGHTS)
@@ -1940,26 +1952,24 @@ int bdpt_prepare(bdpt_ctx* c, uint32_t what) {
 
 // BlockwiseMultiOrderFeatureRegression::execute (DenoisePass.cpp:146-204)
 namespace {
-// bdpt_bmfr_execute (prevPosition == NULL) and bdpt_bmfr_execute_motion
-int bmfrRun(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, const float* prevPosition, float* noisy, void* stream) {
+// what every denoise entry point checks first
+int bmfrCheck(bdpt_ctx* c, const bdpt_gbuffer* g, const char* who) {
   if (!c->haveSize) {
-    fail(c, "bmfr: bdpt_resize must be called first");
+    fail(c, std::string(who) + ": bdpt_resize must be called first");
     return BDPT_E_STATE;
   }
   if (!g->worldPosition || !g->worldNormal || !g->materialDiffuse) {
-    fail(c, "bmfr: WorldPosition, WorldNormal and MaterialDiffuse are required");
+    fail(c, std::string(who) + ": WorldPosition, WorldNormal and MaterialDiffuse are required");
     return BDPT_E_INVALID;
   }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return BDPT_OK;
+}
+
+// One denoise of `count` images (checked by the entry point; its array is copied here) on history h, which holds at least
+// `count` slots: enqueues the pass on st and flips the history.
+int bmfrRun(bdpt_ctx* c, BmfrHistory& h, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, const float* prevPosition, float* const* planes,
+            uint32_t count, hipStream_t st) {
   const size_t n = (size_t)c->W * c->H;
-  if (!c->bmfrAccept) {  // bdpt_prepare(BDPT_PREPARE_BMFR) was not called: allocate now, unless capturing
-    if (streamIsCapturing(st)) {
-      fail(c, "bmfr: the history needs bdpt_prepare(BDPT_PREPARE_BMFR) before stream capture");
-      return BDPT_E_STATE;
-    }
-    if (int rc = allocBmfrHistory(c)) return rc;
-  }
   BmfrDev A{};
   A.W = c->W;
   A.H = c->H;
@@ -1970,32 +1980,43 @@ int bmfrRun(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, const
   A.curPos = reinterpret_cast<const float4*>(g->worldPosition);
   A.curNorm = g->worldNormal;
   A.albedo = g->materialDiffuse;
-  A.noisy = reinterpret_cast<float4*>(noisy);
-  const int r = c->bmfrRead, w = 1 - r;
-  A.prevPosR = c->bmfrPos[r];
-  A.prevNormR = c->bmfrNorm[r];
-  A.prevNoisyR = c->bmfrNoisy[r];
-  A.prevFilteredR = c->bmfrFiltered[r];
-  A.prevPosW = c->bmfrPos[w];
-  A.prevNormW = c->bmfrNorm[w];
-  A.prevNoisyW = c->bmfrNoisy[w];
-  A.prevFilteredW = c->bmfrFiltered[w];
-  A.accept = c->bmfrAccept;
-  A.prevPixel = c->bmfrPrevPixel;
+  const int r = h.read, w = 1 - r;
+  A.prevPosR = h.pos[r];
+  A.prevNormR = h.norm[r];
+  A.prevPosW = h.pos[w];
+  A.prevNormW = h.norm[w];
+  A.accept = h.accept;
+  A.prevPixel = h.prevPixel;
   A.prevPos = reinterpret_cast<const float4*>(prevPosition);
-  if (!(p->flags & BDPT_BMFR_POSTPROCESS))  // no new filtered frame this time: keep the old one on the read side next frame
-    HIPCHK(c, hipMemcpyAsync(c->bmfrFiltered[w], c->bmfrFiltered[r], n * sizeof(float4), hipMemcpyDeviceToDevice, st));
+  A.numPlanes = count;
+  A.read = (uint32_t)r;
+  for (uint32_t k = 0; k < count; k++) A.planes[k] = reinterpret_cast<float4*>(planes[k]);
+  A.histNoisy = h.noisy;
+  A.histFiltered = h.filtered;
+  if (!(p->flags & BDPT_BMFR_POSTPROCESS))  // no new filtered frames this time: the old ones stay on the read side next frame
+    for (uint32_t k = 0; k < count; k++)
+      HIPCHK(c, hipMemcpyAsync(h.filtered + (2 * (size_t)k + w) * n, h.filtered + (2 * (size_t)k + r) * n, n * sizeof(float4),
+                               hipMemcpyDeviceToDevice, st));
   launchBmfr(A, p->flags, st);
   HIPCHK(c, hipGetLastError());
-  c->bmfrRead = w;
+  h.read = w;
   c->lastStream = st;
   return BDPT_OK;
+}
+
+// bdpt_bmfr_execute (prevPosition == NULL) and bdpt_bmfr_execute_motion
+int bmfrSingle(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, const float* prevPosition, float* noisy, void* stream) {
+  if (int rc = bmfrCheck(c, g, "bmfr")) return rc;
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = ensureBmfrHistory(c, c->bmfr, 1, st, "bmfr", kBmfrPrepare)) return rc;
+  return bmfrRun(c, c->bmfr, p, g, prevPosition, &noisy, 1, st);
 }
 }  // namespace
 
 int bdpt_bmfr_execute(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, float* noisy, void* stream) {
   if (!c || !p || !g || !noisy) return BDPT_E_INVALID;
-  return bmfrRun(c, p, g, nullptr, noisy, stream);
+  return bmfrSingle(c, p, g, nullptr, noisy, stream);
 }
 
 int bdpt_bmfr_execute_motion(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, const float* prevPosition, float* noisy,
@@ -2005,44 +2026,32 @@ int bdpt_bmfr_execute_motion(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_
     fail(c, "bmfr_execute_motion: prevPosition missing or not 16-byte aligned");
     return BDPT_E_INVALID;
   }
-  return bmfrRun(c, p, g, prevPosition, noisy, stream);
+  return bmfrSingle(c, p, g, prevPosition, noisy, stream);
 }
 
 int bdpt_bmfr_reset(bdpt_ctx* c) {
   if (!c) return BDPT_E_INVALID;
-  if (!c->bmfrAccept) return BDPT_OK;  // nothing allocated yet
-  ENTER(c);
-  const size_t n = (size_t)c->W * c->H;
-  for (int k = 0; k < 2; k++) {
-    HIPCHK(c, hipMemset(c->bmfrPos[k], 0, n * sizeof(float4)));
-    HIPCHK(c, hipMemset(c->bmfrNorm[k], 0, n * sizeof(float4)));
-    HIPCHK(c, hipMemset(c->bmfrNoisy[k], 0, n * sizeof(float4)));
-    HIPCHK(c, hipMemset(c->bmfrFiltered[k], 0, n * sizeof(float4)));
-  }
-  HIPCHK(c, hipMemset(c->bmfrAccept, 0, n));
-  HIPCHK(c, hipMemset(c->bmfrPrevPixel, 0, n * sizeof(uint32_t)));
-  c->bmfrRead = 0;
-  return BDPT_OK;
+  return resetBmfrHistory(c, c->bmfr);
 }
 
-// [pos | norm | noisy | filtered] of the read side, W * H float4 each
+// [pos | norm | noisy | filtered] of the read side (slot 0 of the single-image history), W * H float4 each
 int bdpt_bmfr_history_bytes(const bdpt_ctx* c, uint64_t* out_bytes) {
   if (!c || !out_bytes) return BDPT_E_INVALID;
-  *out_bytes = (c->haveSize && c->bmfrAccept) ? (uint64_t)c->W * c->H * sizeof(float4) * 4 : 0;
+  *out_bytes = (c->haveSize && c->bmfr.accept) ? (uint64_t)c->W * c->H * sizeof(float4) * 4 : 0;
   return BDPT_OK;
 }
 int bdpt_bmfr_save_history(bdpt_ctx* c, void* blob, uint64_t bytes) {
   if (!c || !blob) return BDPT_E_INVALID;
-  if (!c->haveSize || !c->bmfrAccept) {
+  if (!c->haveSize || !c->bmfr.accept) {
     fail(c, "bmfr_save_history: no history (the denoiser has not run on this context)");
     return BDPT_E_STATE;
   }
-  const size_t plane = (size_t)c->W * c->H * sizeof(float4);
+  const size_t n = (size_t)c->W * c->H, plane = n * sizeof(float4);
   if (bytes < 4 * plane) return BDPT_E_INVALID;
   ENTER(c);
   HIPCHK(c, hipStreamSynchronize(c->lastStream));
-  const int r = c->bmfrRead;
-  const float4* src[4] = {c->bmfrPos[r], c->bmfrNorm[r], c->bmfrNoisy[r], c->bmfrFiltered[r]};
+  const BmfrHistory& h = c->bmfr;
+  const float4* src[4] = {h.pos[h.read], h.norm[h.read], h.noisy + h.read * n, h.filtered + h.read * n};
   for (int k = 0; k < 4; k++) HIPCHK(c, hipMemcpy(static_cast<uint8_t*>(blob) + k * plane, src[k], plane, hipMemcpyDeviceToHost));
   return BDPT_OK;
 }
@@ -2052,54 +2061,21 @@ int bdpt_bmfr_load_history(bdpt_ctx* c, const void* blob, uint64_t bytes) {
     fail(c, "bmfr_load_history: bdpt_resize must be called first");
     return BDPT_E_STATE;
   }
-  const size_t plane = (size_t)c->W * c->H * sizeof(float4);
+  const size_t n = (size_t)c->W * c->H, plane = n * sizeof(float4);
   if (bytes != 4 * plane) {
     fail(c, "bmfr_load_history: the blob was written for another frame size");
     return BDPT_E_INVALID;
   }
   ENTER(c);
-  if (int rc = allocBmfrHistory(c)) return rc;  // (resets: read side 0)
+  if (int rc = ensureBmfrHistory(c, c->bmfr, 1, nullptr, "bmfr", kBmfrPrepare)) return rc;  // (a new one is reset: read side 0)
   HIPCHK(c, hipStreamSynchronize(c->lastStream));
-  const int r = c->bmfrRead;
-  float4* dst[4] = {c->bmfrPos[r], c->bmfrNorm[r], c->bmfrNoisy[r], c->bmfrFiltered[r]};
+  const BmfrHistory& h = c->bmfr;
+  float4* dst[4] = {h.pos[h.read], h.norm[h.read], h.noisy + h.read * n, h.filtered + h.read * n};
   for (int k = 0; k < 4; k++) HIPCHK(c, hipMemcpy(dst[k], static_cast<const uint8_t*>(blob) + k * plane, plane, hipMemcpyHostToDevice));
   return BDPT_OK;
 }
 
-// ---- bdpt_bmfr_execute_planes: the plane history and the call (contract in include/bdpt.h "Denoised planes") ----
-namespace {
-// history for at least `slots` planes; (re)allocating waits for the device and resets.  Not while `st` is being captured.
-int allocBmfrPlanes(bdpt_ctx* c, hipStream_t st, uint32_t slots) {
-  if (c->planesAccept && c->planesSlots >= slots) return BDPT_OK;
-  if (streamIsCapturing(st)) {
-    fail(c, "bmfr planes: the history needs bdpt_bmfr_planes_prepare before stream capture");
-    return BDPT_E_STATE;
-  }
-  HIPCHK(c, hipDeviceSynchronize());  // frames in flight still use the old history
-  freeBmfrPlanes(c);
-  const size_t n = std::max<size_t>((size_t)c->W * c->H, 1);
-  void* a[8]{};
-  const size_t bytes[8] = {n * sizeof(float4), n * sizeof(float4), n * sizeof(float4), n * sizeof(float4),
-                           2 * n * sizeof(float4) * slots, 2 * n * sizeof(float4) * slots, std::max<size_t>(n, 16), n * sizeof(uint32_t)};
-  for (int k = 0; k < 8; k++)
-    if (hipMalloc(&a[k], bytes[k]) != hipSuccess) {
-      for (int j = 0; j < k; j++) (void)hipFree(a[j]);
-      fail(c, "bmfr planes: hipMalloc of the plane history failed");
-      return BDPT_E_NOMEM;
-    }
-  c->planesPos[0] = static_cast<float4*>(a[0]);
-  c->planesPos[1] = static_cast<float4*>(a[1]);
-  c->planesNorm[0] = static_cast<float4*>(a[2]);
-  c->planesNorm[1] = static_cast<float4*>(a[3]);
-  c->planesNoisy = static_cast<float4*>(a[4]);
-  c->planesFiltered = static_cast<float4*>(a[5]);
-  c->planesAccept = static_cast<uint8_t*>(a[6]);
-  c->planesPrevPixel = static_cast<uint32_t*>(a[7]);
-  c->planesSlots = slots;
-  return bdpt_bmfr_planes_reset(c);
-}
-}  // namespace
-
+// ---- bdpt_bmfr_execute_planes (contract in include/bdpt.h "Denoised planes") ----
 int bdpt_bmfr_planes_prepare(bdpt_ctx* c, uint32_t numPlanes) {
   if (!c) return BDPT_E_INVALID;
   if (!c->haveSize) {
@@ -2111,37 +2087,18 @@ int bdpt_bmfr_planes_prepare(bdpt_ctx* c, uint32_t numPlanes) {
     return BDPT_E_INVALID;
   }
   ENTER(c);
-  if (c->planesAccept && c->planesSlots >= numPlanes) return bdpt_bmfr_planes_reset(c);
-  return allocBmfrPlanes(c, nullptr, numPlanes);
+  if (c->bmfrPlanes.accept && c->bmfrPlanes.slots >= numPlanes) return resetBmfrHistory(c, c->bmfrPlanes);
+  return ensureBmfrHistory(c, c->bmfrPlanes, numPlanes, nullptr, "bmfr planes", kBmfrPlanesPrepare);
 }
 
 int bdpt_bmfr_planes_reset(bdpt_ctx* c) {
   if (!c) return BDPT_E_INVALID;
-  if (!c->planesAccept) return BDPT_OK;  // nothing allocated yet
-  ENTER(c);
-  const size_t n = (size_t)c->W * c->H;
-  for (int k = 0; k < 2; k++) {
-    HIPCHK(c, hipMemset(c->planesPos[k], 0, n * sizeof(float4)));
-    HIPCHK(c, hipMemset(c->planesNorm[k], 0, n * sizeof(float4)));
-  }
-  HIPCHK(c, hipMemset(c->planesNoisy, 0, 2 * n * sizeof(float4) * c->planesSlots));
-  HIPCHK(c, hipMemset(c->planesFiltered, 0, 2 * n * sizeof(float4) * c->planesSlots));
-  HIPCHK(c, hipMemset(c->planesAccept, 0, n));
-  HIPCHK(c, hipMemset(c->planesPrevPixel, 0, n * sizeof(uint32_t)));
-  c->planesRead = 0;
-  return BDPT_OK;
+  return resetBmfrHistory(c, c->bmfrPlanes);
 }
 
 int bdpt_bmfr_execute_planes(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_gbuffer* g, const bdpt_bmfr_planes_desc* d, void* stream) {
   if (!c || !p || !g || !d) return BDPT_E_INVALID;
-  if (!c->haveSize) {
-    fail(c, "bmfr planes: bdpt_resize must be called first");
-    return BDPT_E_STATE;
-  }
-  if (!g->worldPosition || !g->worldNormal || !g->materialDiffuse) {
-    fail(c, "bmfr planes: WorldPosition, WorldNormal and MaterialDiffuse are required");
-    return BDPT_E_INVALID;
-  }
+  if (int rc = bmfrCheck(c, g, "bmfr planes")) return rc;
   if (d->numPlanes < 1 || d->numPlanes > BDPT_BMFR_MAX_PLANES || d->reserved != 0 || !d->planes) {
     fail(c, "bmfr planes: numPlanes must be 1 .. BDPT_BMFR_MAX_PLANES, reserved 0 and planes set");
     return BDPT_E_INVALID;
@@ -2151,56 +2108,23 @@ int bdpt_bmfr_execute_planes(bdpt_ctx* c, const bdpt_bmfr_params* p, const bdpt_
     return BDPT_E_INVALID;
   }
   const size_t n = (size_t)c->W * c->H;
-  BmfrPlanesDev B{};
-  B.numPlanes = d->numPlanes;
-  for (uint32_t k = 0; k < d->numPlanes; k++) {  // (the caller's array is copied here)
+  for (uint32_t k = 0; k < d->numPlanes; k++) {
     if (!aligned(d->planes[k], 16)) {
       fail(c, "bmfr planes: plane " + std::to_string(k) + " missing or not 16-byte aligned");
       return BDPT_E_INVALID;
     }
-    B.planes[k] = reinterpret_cast<float4*>(d->planes[k]);
-  }
-  for (uint32_t k = 0; k < d->numPlanes; k++)
     for (uint32_t j = 0; j < k; j++) {
-      const uintptr_t a = reinterpret_cast<uintptr_t>(B.planes[k]), b = reinterpret_cast<uintptr_t>(B.planes[j]);
+      const uintptr_t a = reinterpret_cast<uintptr_t>(d->planes[k]), b = reinterpret_cast<uintptr_t>(d->planes[j]);
       if (a < b + n * sizeof(float4) && b < a + n * sizeof(float4)) {
         fail(c, "bmfr planes: planes " + std::to_string(j) + " and " + std::to_string(k) + " overlap");
         return BDPT_E_INVALID;
       }
     }
+  }
   ENTER(c);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = allocBmfrPlanes(c, st, d->numPlanes)) return rc;
-  BmfrDev& A = B.g;
-  A.W = c->W;
-  A.H = c->H;
-  A.frame = p->frameNumber;
-  A.full = (p->flags & BDPT_BMFR_FULL_FRAME) ? 1u : 0u;
-  A.doPre = (p->flags & BDPT_BMFR_PREPROCESS) ? 1u : 0u;
-  for (int k = 0; k < 16; k++) A.m[k] = p->prevViewProj[k];
-  A.curPos = reinterpret_cast<const float4*>(g->worldPosition);
-  A.curNorm = g->worldNormal;
-  A.albedo = g->materialDiffuse;
-  const int r = c->planesRead, w = 1 - r;
-  A.prevPosR = c->planesPos[r];
-  A.prevNormR = c->planesNorm[r];
-  A.prevPosW = c->planesPos[w];
-  A.prevNormW = c->planesNorm[w];
-  A.accept = c->planesAccept;
-  A.prevPixel = c->planesPrevPixel;
-  A.prevPos = reinterpret_cast<const float4*>(d->prevPosition);
-  B.read = (uint32_t)r;
-  B.histNoisy = c->planesNoisy;
-  B.histFiltered = c->planesFiltered;
-  if (!(p->flags & BDPT_BMFR_POSTPROCESS))  // as bmfrRun: the old filtered frames stay on the read side next frame
-    for (uint32_t k = 0; k < d->numPlanes; k++)
-      HIPCHK(c, hipMemcpyAsync(c->planesFiltered + (2 * (size_t)k + w) * n, c->planesFiltered + (2 * (size_t)k + r) * n, n * sizeof(float4),
-                               hipMemcpyDeviceToDevice, st));
-  launchBmfrPlanes(B, p->flags, st);
-  HIPCHK(c, hipGetLastError());
-  c->planesRead = w;
-  c->lastStream = st;
-  return BDPT_OK;
+  if (int rc = ensureBmfrHistory(c, c->bmfrPlanes, d->numPlanes, st, "bmfr planes", kBmfrPlanesPrepare)) return rc;
+  return bmfrRun(c, c->bmfrPlanes, p, g, d->prevPosition, d->planes, d->numPlanes, st);
 }
 
 int bdpt_tile_pack(bdpt_ctx* c, const void* frame, void* packed, uint32_t bytesPerPixel, void* stream) {

@@ -15,6 +15,20 @@
 
 namespace bdpt {
 constexpr int kMaxStages = 64;
+
+// What the denoiser keeps between frames for `slots` images over one G-buffer: position / normal ping-pong pairs, accept
+// and prevPixel once, noisy and filtered pairs per slot (side s of slot k at [(2 * k + s) * W * H]).  Own allocations, not
+// frameAllocs: growing frees them; bdpt_resize and bdpt_destroy drop them (the history goes with the frame,
+// BlockwiseMultiOrderFeatureRegression::resize).
+struct BmfrHistory {
+  float4* pos[2] = {nullptr, nullptr};
+  float4* norm[2] = {nullptr, nullptr};
+  float4 *noisy = nullptr, *filtered = nullptr;
+  uint8_t* accept = nullptr;  // set: the history is allocated
+  uint32_t* prevPixel = nullptr;
+  uint32_t slots = 0;
+  int read = 0;  // which side holds the previous frame
+};
 }  // namespace bdpt
 
 struct bdpt_ctx {
@@ -62,24 +76,10 @@ struct bdpt_ctx {
   unsigned long long* adaptiveSum = nullptr;  // active-pixel sum and done count of bdpt_adaptive_update (each launch leaves them zero)
   // channels of the built-in primary stage (bdpt_execute with in == NULL): bdpt_prepare or first use
   bdpt_gbuffer ownGb{};
-  // BMFR history (bdpt_prepare or the first bdpt_bmfr_execute): [2] = ping-pong pair
-  float4* bmfrPos[2] = {nullptr, nullptr};
-  float4* bmfrNorm[2] = {nullptr, nullptr};
-  float4* bmfrNoisy[2] = {nullptr, nullptr};
-  float4* bmfrFiltered[2] = {nullptr, nullptr};
-  uint8_t* bmfrAccept = nullptr;
-  uint32_t* bmfrPrevPixel = nullptr;
-  int bmfrRead = 0;  // which half holds the previous frame
-  // the plane history of bdpt_bmfr_execute_planes (bdpt_bmfr_planes_prepare or the first call that needs more slots),
-  // apart from the history above: position / normal pairs, accept and prevPixel once, noisy and filtered pairs per slot
-  // (side s of slot k at [(2 * k + s) * W * H]).  Own allocations, not frameAllocs: growing frees them.
-  float4* planesPos[2] = {nullptr, nullptr};
-  float4* planesNorm[2] = {nullptr, nullptr};
-  float4 *planesNoisy = nullptr, *planesFiltered = nullptr;
-  uint8_t* planesAccept = nullptr;
-  uint32_t* planesPrevPixel = nullptr;
-  uint32_t planesSlots = 0;
-  int planesRead = 0;
+  // BMFR history, two of them and apart: bmfr for bdpt_bmfr_execute / _motion (one slot; bdpt_prepare(BDPT_PREPARE_BMFR)
+  // or the first call), bmfrPlanes for bdpt_bmfr_execute_planes (bdpt_bmfr_planes_prepare or the first call that needs
+  // more slots)
+  bdpt::BmfrHistory bmfr, bmfrPlanes;
   // the splat and NEE generators run beside the connection generator on this stream (fork/join with events; capture-safe)
   hipStream_t walkStream = nullptr;
   hipEvent_t evFork = nullptr, evJoin = nullptr, evSplat = nullptr;

@@ -238,8 +238,12 @@ struct GBufferDev {
   uint32_t* hintPix;    // FrameDev::hintPix, written here (may be NULL)
 };
 
-// BMFR denoise pass (bmfr.hip).  History buffers come in ping-pong pairs: R = previous frame (read), W = this
-// frame (written), so the reference's post-pass blits (DenoisePass.cpp:180-182, 194) cost no extra copy.
+// BMFR denoise pass (bmfr.hip): numPlanes images over one G-buffer (one for bdpt_bmfr_execute / _motion).  History buffers
+// come in ping-pong pairs: R = previous frame (read), W = this frame (written), so the reference's post-pass blits
+// (DenoisePass.cpp:180-182, 194) cost no extra copy.  The images share frame, flags, matrix, features, the position / normal
+// history, accept, prevPixel and prevPos.  Plane k's noisy and filtered history: side s of slot k at
+// hist*[(2 * k + s) * W * H]; `read` is the side that holds the previous frame.  The pointers travel by value in the kernel
+// argument.
 struct BmfrDev {
   uint32_t W, H, frame;
   uint32_t full, doPre;
@@ -247,27 +251,17 @@ struct BmfrDev {
   const float4* curPos;        // WorldPosition
   const uint16_t* curNorm;     // WorldNormal (half4)
   const uint16_t* albedo;      // MaterialDiffuse (half4)
-  float4* noisy;               // channel being denoised, in/out
-  const float4 *prevPosR, *prevNormR, *prevNoisyR, *prevFilteredR;
-  float4 *prevPosW, *prevNormW, *prevNoisyW, *prevFilteredW;
+  const float4 *prevPosR, *prevNormR;
+  float4 *prevPosW, *prevNormW;
   uint8_t* accept;             // BMFR_AcceptedBools
   uint32_t* prevPixel;         // BMFR_PrevFramePixel, RG16Float
-  const float4* prevPos;       // bdpt_bmfr_execute_motion: where each pixel's surface point was last frame; NULL = curPos
-};
-void launchBmfr(const BmfrDev& A, uint32_t flags, hipStream_t st);
-
-// bdpt_bmfr_execute_planes (bmfr.hip "Planes"): numPlanes images over one G-buffer.  g carries what the images share (frame,
-// flags, matrix, features, the position / normal history, accept, prevPixel, prevPos); its noisy, prevNoisy* and
-// prevFiltered* stay NULL.  Plane k's noisy and filtered history: side s of slot k at hist*[(2 * k + s) * W * H]; `read` is
-// the side that holds the previous frame.  The pointers travel by value in the kernel argument.
-struct BmfrPlanesDev {
-  BmfrDev g;
+  const float4* prevPos;       // where each pixel's surface point was last frame (PrevWorldPosition); NULL = curPos
   uint32_t numPlanes, read;
-  float4* planes[BDPT_BMFR_MAX_PLANES];
+  float4* planes[BDPT_BMFR_MAX_PLANES];  // the channels being denoised, in/out
   float4 *histNoisy, *histFiltered;
 };
 // one launch per stage whatever numPlanes is
-void launchBmfrPlanes(const BmfrPlanesDev& B, uint32_t flags, hipStream_t st);
+void launchBmfr(const BmfrDev& A, uint32_t flags, hipStream_t st);
 
 // Motion (motion.hip, device_motion.hpp; contract in include/bdpt.h "Motion"): the previous pose, three float4 per
 // primitive (the corners p0, p1, p2 in primitive order, w unused), and the G-buffer channel made from it.  Only the MOTION

@@ -1219,7 +1219,8 @@ int bdpt_bmfr_load_history(bdpt_ctx* ctx, const void* host_blob, uint64_t bytes)
 /* ---- Denoised planes: several images over one G-buffer (light-group planes, for relighting) with one fit ----
  * bdpt_bmfr_execute_planes denoises numPlanes whole-frame images that share `features` in one call: the reprojection
  * and its geometry tests, the feature scaling and the Householder factorisation of the ten feature columns of every
- * block are done once, the colour work per plane.
+ * block are done once, the colour work per plane.  bdpt_bmfr_execute and bdpt_bmfr_execute_motion are the one-plane case
+ * of the same code, on a history of their own.
  *
  * Contract.  After the call planes[k] holds exactly the bits bdpt_bmfr_execute (with prevPosition set:
  * bdpt_bmfr_execute_motion) would have left in it on a context of its own that was fed planes[k], the same `features`
@@ -1228,11 +1229,11 @@ int bdpt_bmfr_load_history(bdpt_ctx* ctx, const void* host_blob, uint64_t bytes)
  * Colours, w / spp, sampleSpp and both blend factors are computed per plane from that plane's own history; only what
  * reads positions and normals alone is shared.
  *
- * History.  The plane history is apart from the single-image history: position and normal ping-pong pairs, the accept
- * mask and prevPixel once, noisy and filtered ping-pong pairs per slot.  bdpt_bmfr_execute, _motion, _reset,
- * _history_bytes, _save_history and _load_history keep their bits and their state whatever is called here, and the blob
- * functions cover the single-image history only: the plane history is not checkpointed.  bdpt_resize drops it, as it
- * drops the other.
+ * History.  The plane history is apart from the single-image history and laid out like it, which is the one-slot case:
+ * position and normal ping-pong pairs, the accept mask and prevPixel once, noisy and filtered ping-pong pairs per slot.
+ * bdpt_bmfr_execute, _motion, _reset, _history_bytes, _save_history and _load_history keep their bits and their state
+ * whatever is called here, and the blob functions cover the single-image history only: the plane history is not
+ * checkpointed.  bdpt_resize drops it, as it drops the other.
  *   bdpt_bmfr_planes_prepare(n)  allocates the history for n planes (if fewer are there) and resets it.
  *   bdpt_bmfr_planes_reset       forgets it (BDPT_OK when there is none).
  * A call that needs more planes than are allocated waits for the device, reallocates and resets the plane history

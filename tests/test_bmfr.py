@@ -390,3 +390,65 @@ def test_bmfr_large_frame_numbers_match_oracle(pkg, ob, keep_ld):
         gpu, ref = run.frame(_params(pkg, frame, flags), g)
         _assert_same(gpu, ref, f"frame {frame}")
     run.close()
+
+
+@pytest.mark.gpu
+def test_bmfr_execute_captured_in_a_hip_graph(pkg):
+    """33x31: after bdpt_prepare(BDPT_PREPARE_BMFR), two frames' worth of one bdpt_bmfr_execute each captured into one graph
+    (one stream, no branches) replay to the bits of the same two calls made eagerly on a second context; without the
+    prepare the captured call is refused with BDPT_E_STATE and enqueues nothing."""
+    import torch
+    import test_bmfr_cross_check as xc
+    A, lib = pkg.abi, pkg.load_library()
+    W, H = 33, 31
+    flags = A.BMFR_PREPROCESS | A.BMFR_REGRESSION | A.BMFR_POSTPROCESS | A.BMFR_FULL_FRAME
+    frames = []
+    for k in range(2):
+        g, vp = xc.sequence_gbuffer(pkg, W, H, k)
+        t = (torch.from_numpy(g[0]).cuda(), torch.from_numpy(g[1].astype(np.float16)).cuda(),
+             torch.from_numpy(g[2].astype(np.float16)).cuda(), torch.from_numpy(g[3]).cuda())
+        gb = A.GBuffer()
+        gb.worldPosition, gb.worldNormal, gb.materialDiffuse = [x.data_ptr() for x in t[:3]]
+        frames.append((_params(pkg, k, flags, vp), gb, t))
+    eager, cap = pkg.Context(0), pkg.Context(0)
+    for c in (eager, cap):
+        c.resize(W, H, 0, H, 1)
+    want = []
+    for p, gb, t in frames:
+        img = t[3].clone()
+        eager.bmfr_execute(p, gb, C.c_void_p(img.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        want.append(img.cpu().numpy())
+    assert not np.array_equal(want[1], frames[1][2][3].cpu().numpy())
+    images = [t[3].clone() for _, _, t in frames]
+    side = torch.cuda.Stream()
+    sp = C.c_void_p(side.cuda_stream)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        graph.capture_begin()
+        images[0].add_(0.0)  # something to capture: the refused call below enqueues nothing
+        p, gb, _ = frames[0]
+        rc = lib.bdpt_bmfr_execute(cap._h, C.byref(p), C.byref(gb), C.c_void_p(images[0].data_ptr()), sp)
+        graph.capture_end()
+    assert rc == -2, rc  # BDPT_E_STATE: not prepared
+    assert b"bdpt_prepare(BDPT_PREPARE_BMFR)" in lib.bdpt_last_error(cap._h)
+    del graph
+    cap.prepare(A.PREPARE_BMFR)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        graph.capture_begin()
+        rcs = [lib.bdpt_bmfr_execute(cap._h, C.byref(p), C.byref(gb), C.c_void_p(img.data_ptr()), sp)
+               for (p, gb, _), img in zip(frames, images)]
+        graph.capture_end()
+    assert rcs == [0, 0], rcs
+    torch.cuda.synchronize()
+    for (_, _, t), img in zip(frames, images):
+        assert torch.equal(img, t[3])  # captured, not run
+    graph.replay()
+    torch.cuda.synchronize()
+    for k, img in enumerate(images):
+        _assert_same(img.cpu().numpy(), want[k], f"replayed frame {k}")
+    del graph
+    eager.close()
+    cap.close()

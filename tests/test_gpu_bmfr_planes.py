@@ -130,10 +130,12 @@ def test_planes_133x77_matches_oracle(pkg, ob, keep_ld):
     _check_against_oracles(pkg, ob, 133, 77, _flags(pkg.abi, True, keep_ld), 4, 2)
 
 
-def _check_against_contexts(pkg, W, H, count, frames, params_of, gbuffer_of, prev_of=None, w_per_plane=False):
-    """the planes call against `count` contexts running bdpt_bmfr_execute (_motion with prev_of) on one image each"""
+def _check_against_contexts(pkg, W, H, count, frames, params_of, gbuffer_of, prev_of=None, w_per_plane=False, ob=None):
+    """the planes call against `count` contexts running bdpt_bmfr_execute (_motion with prev_of) on one image each; with
+    `ob` also against one OracleBmfr per plane, as _check_against_oracles"""
     run = PlanesRun(pkg, W, H)
     refs = [PlanesRun(pkg, W, H) for _ in range(count)]
+    oracles = [ob.OracleBmfr(pkg.abi, W, H) for _ in range(count)] if ob is not None else []
     changed = False
     for k in range(frames):
         g, p = gbuffer_of(k), params_of(k)
@@ -143,17 +145,22 @@ def _check_against_contexts(pkg, W, H, count, frames, params_of, gbuffer_of, pre
         for j, ref in enumerate(refs):
             want = ref.single(p, g, images[j].copy(), prev)
             _assert_same(got[j], want, f"frame {k} plane {j}")
+        for j, orc in enumerate(oracles):
+            ref = images[j].copy()
+            orc.execute(p, g[0], g[1], g[2], ref)
+            _assert_same(got[j], ref, f"frame {k} plane {j} against the oracle")
         changed = changed or not np.array_equal(got[0], images[0])
     assert changed, "the call left every frame as it was"
-    for r in refs + [run]:
+    for r in refs + [run] + oracles:
         r.close()
 
 
 # ---- 3. stage switches
 @pytest.mark.parametrize("off", ["regression", "preprocess", "postprocess"])
-def test_planes_stage_switches(pkg, off):
-    """33x31, three planes, four frames with one stage off, against three contexts running bdpt_bmfr_execute.  With the
-    preprocess stage off w is the caller's, and differs per plane here."""
+def test_planes_stage_switches(pkg, ob, off):
+    """33x31, three planes, four frames with one stage off, against three contexts running bdpt_bmfr_execute and against
+    three oracles (the contexts run the K = 1 instance of the kernels the planes call runs: the oracle is the independent
+    side).  With the preprocess stage off w is the caller's, and differs per plane here."""
     import test_bmfr_cross_check as xc
     A = pkg.abi
     W, H = 33, 31
@@ -163,7 +170,7 @@ def test_planes_stage_switches(pkg, off):
     flags = _flags(A, True, False, stages)
     seq = [xc.sequence_gbuffer(pkg, W, H, k) for k in range(4)]
     _check_against_contexts(pkg, W, H, 3, 4, lambda k: _params(pkg, k, flags, seq[k][1]), lambda k: seq[k][0],
-                            w_per_plane=off == "preprocess")
+                            w_per_plane=off == "preprocess", ob=ob)
 
 
 # ---- 4. motion

@@ -1,5 +1,7 @@
 """Cost of denoising P planes with one bdpt_bmfr_execute_planes against P bdpt_bmfr_execute calls on P contexts (one
-stream), at 1920x1080 on the 262 k-triangle atrium's G-buffer.  One BDPT frame with light groups is rendered once; plane k
+stream), at 1920x1080 on the 262 k-triangle atrium's G-buffer.  Both forms run the same kernels: the "separate" baseline
+is the one-plane instance run P times, so at P = 1 the two forms are one and the same work, and for P >= 2 the ratio shows
+what sharing the reprojection and the factorisation among the planes saves.  One BDPT frame with light groups is rendered once; plane k
 is that frame's plane k % 4 (three lights + emission) scaled by 1 + k / 8, copied fresh before every timed call.  Both
 forms run alternately, --reps times each after --warmup, on frames 1, 2, ... of a still camera (every pixel reprojects),
 timed by torch.cuda events around the call(s) on the stream.  The default flags plus regression (preprocess + regression +
