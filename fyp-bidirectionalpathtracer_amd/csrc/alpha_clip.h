@@ -14,12 +14,14 @@
 
 #include "../../include/bdpt.h"
 #include "bvh.h"
+#include "bvh_refs.h"
 
 namespace bdpt {
 
 class AlphaClipper : public BvhRefClipper {
  public:
   AlphaClipper(const bdpt_scene_desc* d);
+  AlphaClipper(const AlphaClipper&) = delete;  // (passMasks_ points into masks_)
   // 0: both outcomes occur (or could not be decided), 1: the test always passes, 2: it always fails
   int classify(uint32_t tri) const;
   bool clip(uint32_t tri, double (*poly)[2], int& n) const override;
@@ -31,17 +33,13 @@ class AlphaClipper : public BvhRefClipper {
   struct Mask {
     int w = 0, h = 0;
     std::vector<uint32_t> mayPass, mayFail;  // summed-area tables, (w + 1) x (h + 1): cells a sample may pass / fail in
-    uint32_t count(const std::vector<uint32_t>& sat, long x0, long x1, long y0, long y1) const;
   };
-  struct MatInfo {
-    int mask = -1;        // index into masks, -1: no texture decides
-    int verdict = 0;      // for mask < 0: 1 always passes, 2 always fails
-  };
-  bool cellRect(uint32_t tri, const double (*poly)[2], int n, const Mask*& m, long& x0, long& x1, long& y0, long& y1, double& margin,
-                double uv[3][2]) const;
+  BvhClipView view() const;  // the tables below as bvh_refs.h reads them
   const bdpt_scene_desc* d_;
-  std::vector<MatInfo> mats_;
+  std::vector<int32_t> matMask_;     // per material: index into masks_, -1: no texture decides
+  std::vector<int32_t> matVerdict_;  // for matMask_ < 0: 1 always passes, 2 always fails
   std::vector<Mask> masks_;
+  std::vector<BvhClipMask> passMasks_;  // masks_[i] as {w, h, mayPass}
 };
 
 }  // namespace bdpt

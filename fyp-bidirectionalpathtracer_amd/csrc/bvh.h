@@ -207,8 +207,9 @@ BVH_HD inline double bvhCbrt(double x) {
   __builtin_memcpy(&s2, &p, 8);
   return t * s2;
 }
-// What a clipper decides with, as plain tables — for an implementation of the same decisions somewhere else (the device:
-// bvh_device.hip runs alpha_clip.cpp's clip() from these).  All pointers stay the clipper's / the scene's.
+// What a clipper decides with, as plain tables — for the same decisions somewhere else (the device: bvh_device.hip runs
+// bvh_refs.h's bvhClipPoly, the text of alpha_clip.cpp's clip(), on copies of these).  All pointers stay the clipper's /
+// the scene's.
 struct BvhClipTables {
   const uint32_t* triMaterial = nullptr;  // per triangle
   const uint32_t* indices = nullptr;      // 3 per triangle
@@ -240,7 +241,6 @@ constexpr uint32_t kBvhLeafMax = BDPT_LEAF_MAX;   // references per leaf, at mos
 constexpr int kBvhBinaryMaxDepth = kBvhMaxStack;  // depth budget of the binary tree: a two-wide path stacks one reference per level
 struct BvhBox {
   float lo[3], hi[3];
-  // (host-side helpers; the device code of bvh_device.hip spells the same arithmetic out itself)
   void reset() {
     lo[0] = lo[1] = lo[2] = 1e30f;
     hi[0] = hi[1] = hi[2] = -1e30f;

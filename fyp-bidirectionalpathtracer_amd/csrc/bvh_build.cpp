@@ -7,6 +7,7 @@
 // partition is the same serial std::partition on the same range, the four-wide collapse only looks at the tree's
 // shape, and the one floating-point sum (the SAH cost) is taken in node order by one thread.
 #include "bvh.h"
+#include "bvh_refs.h"
 
 #include <algorithm>
 #include <atomic>
@@ -363,192 +364,21 @@ void buildSubtree(const BuildData& B, BigVec<TmpNode>& nodes, uint32_t root, uin
 // rounding of the device's triangle test, as it does for whole triangles).  For non-opaque triangles the caller's
 // BvhRefClipper shrinks a piece to where the alpha test can pass, or drops it.
 // ------------------------------------------------------------------------------------------------
-struct Piece {
-  double b[kBvhPolyMax][2];
-  int n;
-  Box box;
-  uint32_t splits;
-};
-
-inline float floatDown(double x) {
-  float f = (float)x;
-  if ((double)f > x) f = std::nextafterf(f, -INFINITY);
-  return f;
-}
-inline float floatUp(double x) {
-  float f = (float)x;
-  if ((double)f < x) f = std::nextafterf(f, INFINITY);
-  return f;
-}
-
-Box polyBox(const BvhTri& r, const double (*b)[2], int n) {
-  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-  for (int k = 0; k < n; k++)
-    for (int a = 0; a < 3; a++) {
-      const double p = (double)r.v0[a] + b[k][0] * (double)r.e1[a] + b[k][1] * (double)r.e2[a];
-      lo[a] = std::min(lo[a], p);
-      hi[a] = std::max(hi[a], p);
-    }
-  Box bx;
-  for (int a = 0; a < 3; a++) {
-    bx.lo[a] = floatDown(lo[a]);
-    bx.hi[a] = floatUp(hi[a]);
-  }
-  return bx;
-}
-
-// Sutherland-Hodgman against the closed half-plane A + B bu + C bv <= 0
-int clipHalfPlane(const double (*in)[2], int n, double A, double B, double C, double (*out)[2]) {
-  int m = 0;
-  for (int k = 0; k < n; k++) {
-    const double* p = in[k];
-    const double* q = in[(k + 1) % n];
-    const double fp = A + B * p[0] + C * p[1], fq = A + B * q[0] + C * q[1];
-    if (fp <= 0.0 && m < kBvhPolyMax) {
-      out[m][0] = p[0];
-      out[m][1] = p[1];
-      m++;
-    }
-    if (((fp < 0.0 && fq > 0.0) || (fp > 0.0 && fq < 0.0)) && m < kBvhPolyMax) {
-      const double t = fp / (fp - fq);
-      out[m][0] = p[0] + t * (q[0] - p[0]);
-      out[m][1] = p[1] + t * (q[1] - p[1]);
-      m++;
-    }
-  }
-  return m;
-}
-
-struct SplitGrid {  // spatial-median planes of the scene box on a 2^30 grid per axis
-  double lo[3], ext[3];
-  // most important plane strictly inside [a, b] on `axis`: its importance (bit position, higher = nearer the root) or -1
-  int plane(int axis, float a, float b, double& coord) const {
-    if (!(ext[axis] > 0.0) || !(b > a)) return -1;
-    const double s = 1073741824.0 / ext[axis];
-    double ua = std::floor(((double)a - lo[axis]) * s), ub = std::floor(((double)b - lo[axis]) * s);
-    ua = std::min(std::max(ua, 0.0), 1073741823.0);
-    ub = std::min(std::max(ub, 0.0), 1073741823.0);
-    const uint32_t ia = (uint32_t)ua, ib = (uint32_t)ub;
-    if (ia == ib) return -1;
-    const uint32_t diff = ia ^ ib;
-    const int h = 31 - __builtin_clz(diff);
-    const uint32_t pl = (ib >> h) << h;
-    coord = lo[axis] + (double)pl / s;
-    if (!(coord > (double)a && coord < (double)b)) return -1;  // (rounding at the ends of the interval)
-    return h;
-  }
-  int dominant(const Box& bx, int& axis, double& coord) const {
-    int best = -1;
-    float bestExt = -1.0f;
-    for (int a = 0; a < 3; a++) {
-      double c;
-      const int h = plane(a, bx.lo[a], bx.hi[a], c);
-      const float e = bx.hi[a] - bx.lo[a];
-      if (h > best || (h == best && h >= 0 && e > bestExt)) {
-        best = h;
-        bestExt = e;
-        axis = a;
-        coord = c;
-      }
-    }
-    return best;
-  }
-};
-
-double splitPriority(const SplitGrid& G, const BvhTri& r, const Box& bx, double polyShare) {
-  int axis = 0;
-  double c = 0;
-  const int h = G.dominant(bx, axis, c);
-  if (h < 0) return 0.0;
-  const double cx = (double)r.e1[1] * r.e2[2] - (double)r.e1[2] * r.e2[1], cy = (double)r.e1[2] * r.e2[0] - (double)r.e1[0] * r.e2[2],
-               cz = (double)r.e1[0] * r.e2[1] - (double)r.e1[1] * r.e2[0];
-  const double ideal = (std::fabs(cx) + std::fabs(cy) + std::fabs(cz)) * polyShare;
-  const double dx = (double)bx.hi[0] - bx.lo[0], dy = (double)bx.hi[1] - bx.lo[1], dz = (double)bx.hi[2] - bx.lo[2];
-  const double gain = 2.0 * (dx * dy + dy * dz + dz * dx) - ideal;
-  if (!(gain > 0.0)) return 0.0;
-  return bvhCbrt(std::ldexp(gain, h - 30));
-}
-
-double polyArea2(const double (*b)[2], int n) {  // twice the area in barycentric units (the whole triangle: 1)
-  double s = 0;
-  for (int k = 0; k < n; k++) {
-    const double* p = b[k];
-    const double* q = b[(k + 1) % n];
-    s += p[0] * q[1] - q[0] * p[1];
-  }
-  return std::fabs(s);
-}
-
-inline Box intersectBox(const Box& a, const Box& b) {
-  Box r;
-  for (int k = 0; k < 3; k++) {
-    r.lo[k] = std::max(a.lo[k], b.lo[k]);
-    r.hi[k] = std::min(a.hi[k], b.hi[k]);
-    if (r.hi[k] < r.lo[k]) r.hi[k] = r.lo[k];  // (outward rounding of two disjoint-by-an-ulp intervals)
-  }
-  return r;
-}
-
+// The arithmetic of all this — clipping, boxes, the split grid, priorities, bvhSplitTriangle — is bvh_refs.h, the one text
+// the device builder (bvh_device.hip) compiles too; what follows here only loads, calls and stores.
 struct RefOut {
   std::vector<Box> boxes;
   std::vector<uint32_t> tri;
-};
-
-// All references of one triangle, appended to `out` in a fixed order.  Returns the number appended.
-uint32_t splitTriangle(const SplitGrid& G, const BvhTri& r, uint32_t t, const Piece& whole, const BvhRefClipper* clipper, RefOut& out) {
-  std::vector<Piece> todo{whole};
-  uint32_t made = 0;
-  while (!todo.empty()) {
-    Piece pc = todo.back();
-    todo.pop_back();
-    for (int guard = 0;; guard++) {
-      int axis = 0;
-      double c = 0;
-      if (pc.splits == 0 || guard > 96 || pc.n + 2 > kBvhPolyMax || G.dominant(pc.box, axis, c) < 0) {
-        out.boxes.push_back(pc.box);
-        out.tri.push_back(t);
-        made++;
-        break;
-      }
-      const double A = (double)r.v0[axis] - c, B = (double)r.e1[axis], C = (double)r.e2[axis];
-      Piece lo, hi;
-      lo.n = clipHalfPlane(pc.b, pc.n, A, B, C, lo.b);
-      hi.n = clipHalfPlane(pc.b, pc.n, -A, -B, -C, hi.b);
-      bool haveLo = lo.n >= 3 && polyArea2(lo.b, lo.n) > 0.0, haveHi = hi.n >= 3 && polyArea2(hi.b, hi.n) > 0.0;
-      if (clipper) {
-        if (haveLo) haveLo = clipper->clip(t, lo.b, lo.n) && lo.n >= 3;
-        if (haveHi) haveHi = clipper->clip(t, hi.b, hi.n) && hi.n >= 3;
-      }
-      if (haveLo) lo.box = intersectBox(polyBox(r, lo.b, lo.n), pc.box);
-      if (haveHi) hi.box = intersectBox(polyBox(r, hi.b, hi.n), pc.box);
-      if (!haveLo && !haveHi) {
-        if (!clipper) {  // (a sliver the clip lost to rounding: keep the piece as it was)
-          out.boxes.push_back(pc.box);
-          out.tri.push_back(t);
-          made++;
-        }
-        break;
-      }
-      if (!haveLo || !haveHi) {  // the polygon lies on one side of the plane although its box straddles it: shrink and go on
-        const uint32_t s = pc.splits;
-        pc = haveLo ? lo : hi;
-        pc.splits = s;
-        continue;
-      }
-      const uint32_t rest = pc.splits - 1;
-      const double wl = ((double)lo.box.hi[0] - lo.box.lo[0]) + ((double)lo.box.hi[1] - lo.box.lo[1]) + ((double)lo.box.hi[2] - lo.box.lo[2]);
-      const double wh = ((double)hi.box.hi[0] - hi.box.lo[0]) + ((double)hi.box.hi[1] - hi.box.lo[1]) + ((double)hi.box.hi[2] - hi.box.lo[2]);
-      uint32_t sl = (wl + wh > 0.0) ? (uint32_t)std::floor((double)rest * wl / (wl + wh) + 0.5) : rest / 2;
-      if (sl > rest) sl = rest;
-      lo.splits = sl;
-      hi.splits = rest - sl;
-      todo.push_back(hi);
-      pc = lo;
-      guard = 0;
+  void push(const float* lo, const float* hi, uint32_t t) {
+    Box bx;
+    for (int a = 0; a < 3; a++) {
+      bx.lo[a] = lo[a];
+      bx.hi[a] = hi[a];
     }
+    boxes.push_back(bx);
+    tri.push_back(t);
   }
-  return made;
-}
+};
 
 }  // namespace
 
@@ -643,24 +473,11 @@ void buildBvh(const float* positions, const uint32_t* indices, uint32_t nTris, c
         const float* b = positions + (size_t)indices[t * 3 + 1] * 3;
         const float* c = positions + (size_t)indices[t * 3 + 2] * 3;
         BvhTri r;
-        float p1[3], p2[3];
-        for (int k = 0; k < 3; k++) {
-          r.v0[k] = a[k];
-          r.e1[k] = b[k] - a[k];
-          r.e2[k] = c[k] - a[k];
-          p1[k] = r.v0[k] + r.e1[k];
-          p2[k] = r.v0[k] + r.e2[k];
-        }
+        Box bx;
+        bvhTriGeom(a, b, c, r.v0, r.e1, r.e2, bx.lo, bx.hi);
         r.prim = (uint32_t)t;
         r.flags = triFlags ? triFlags[t] : 0u;
         r.aux = triAux ? triAux[t] : 0u;
-        Box bx;
-        bx.reset();
-        bx.grow(r.v0);
-        bx.grow(p1);
-        bx.grow(p2);
-        bx.grow(b);
-        bx.grow(c);
         if (!recsElsewhere) {
           recs[t] = r;
           triBox[t] = bx;
@@ -682,7 +499,7 @@ void buildBvh(const float* positions, const uint32_t* indices, uint32_t nTris, c
 
   // ---- references (see "References" above): the whole triangle, shrunk by the clipper where it is non-opaque,
   // then split s_t times
-  SplitGrid G;
+  BvhSplitGrid G;
   for (int a = 0; a < 3; a++) {
     G.lo[a] = nTris ? (double)scene.lo[a] : 0.0;
     G.ext[a] = nTris ? (double)scene.hi[a] - (double)scene.lo[a] : 0.0;
@@ -692,7 +509,7 @@ void buildBvh(const float* positions, const uint32_t* indices, uint32_t nTris, c
     std::vector<float> areas;
     areas.reserve(nTris);
     for (uint32_t t = 0; t < nTris; t++)
-      if (!(recs[t].flags & kTriNonOpaque)) areas.push_back(triBox[t].area());
+      if (!(recs[t].flags & kTriNonOpaque)) areas.push_back(bvhBoxArea(triBox[t].lo, triBox[t].hi));  // (the area bvhRefDecide compares against it)
     if (!areas.empty()) {
       std::nth_element(areas.begin(), areas.begin() + areas.size() / 2, areas.end());
       outlierArea = (float)BDPT_SPLIT_OUTLIER * areas[areas.size() / 2];
@@ -704,54 +521,14 @@ void buildBvh(const float* positions, const uint32_t* indices, uint32_t nTris, c
   BigVec<float> capOf(nHere);    // splits a triangle may get at most
   BigVec<uint8_t> state(nHere);  // 0 = plain reference (triBox), 1 = shrunk by the clipper, 2 = dropped
   BigVec<uint32_t> splits(nHere);
-  parallelFor(nHere, threads, [&](size_t t0, size_t t1, int) {
-    for (size_t t = t0; t < t1; t++) {
-      prio[t] = 0.0;
-      capOf[t] = (float)BDPT_SPLIT_MAX_PER_TRI;
-      state[t] = 0;
-      splits[t] = 0;
-    }
-  });
   const bool anySplit = budgetOpaque > 0.0f || budgetAlpha > 0.0f;
-  // the whole triangle as a piece, shrunk by the clipper where it is non-opaque; false: nothing of it can be hit.
-  // (Recomputed where it is needed again instead of kept: a piece is ~400 bytes and a scene may hold millions.)
-  auto wholePiece = [&](size_t t, Piece& pc, bool& shrunk) {
-    const BvhTri& r = recs[t];
-    pc.n = 3;
-    pc.b[0][0] = 0.0;
-    pc.b[0][1] = 0.0;
-    pc.b[1][0] = 1.0;
-    pc.b[1][1] = 0.0;
-    pc.b[2][0] = 0.0;
-    pc.b[2][1] = 1.0;
-    pc.splits = 0;
-    pc.box = triBox[t];
-    shrunk = false;
-    if (!((r.flags & kTriNonOpaque) != 0 && opt.clipper != nullptr)) return true;
-    if (!opt.clipper->clip((uint32_t)t, pc.b, pc.n) || pc.n < 3) return false;
-    shrunk = !(pc.n == 3 && pc.b[0][0] == 0.0 && pc.b[0][1] == 0.0 && pc.b[1][0] == 1.0 && pc.b[1][1] == 0.0 && pc.b[2][0] == 0.0 && pc.b[2][1] == 1.0);
-    if (shrunk) pc.box = intersectBox(polyBox(r, pc.b, pc.n), triBox[t]);
-    return true;
-  };
   // pass 1: what the clipper leaves of every non-opaque triangle, and every triangle's priority
   constexpr size_t kRefChunk = 8192;
   parallelChunks(nHere, threads, kRefChunk, [&](size_t, size_t t0, size_t t1) {
     for (size_t t = t0; t < t1; t++) {
-      const BvhTri& r = recs[t];
-      Piece pc;
-      bool shrunk = false;
-      if (!wholePiece(t, pc, shrunk)) {
-        state[t] = 2;
-        continue;
-      }
-      state[t] = shrunk ? 1 : 0;
-      const float budget = (r.flags & kTriNonOpaque) ? budgetAlpha : budgetOpaque;
-      if (budget > 0.0f && ((r.flags & kTriNonOpaque) || pc.box.area() >= outlierArea)) {
-        prio[t] = splitPriority(G, r, pc.box, shrunk ? polyArea2(pc.b, pc.n) : 1.0);
-        // an opaque outlier is cut down to about the size of its neighbours, not further
-        if (!(r.flags & kTriNonOpaque) && outlierArea > 0.0f)
-          capOf[t] = std::min((float)BDPT_SPLIT_MAX_PER_TRI, std::floor((float)BDPT_SPLIT_OUTLIER * pc.box.area() / outlierArea));
-      }
+      auto clip = [&](double (*poly)[2], int& n) { return opt.clipper->clip((uint32_t)t, poly, n); };
+      bvhRefDecide(G, recs[t], triBox[t].lo, triBox[t].hi, opt.clipper != nullptr, clip, budgetOpaque, budgetAlpha, outlierArea, state[t], prio[t], capOf[t]);
+      splits[t] = 0;
     }
   });
   // split counts per class: the largest D with sum floor(D p_t) <= budget (integer sums: thread-count independent)
@@ -795,22 +572,11 @@ void buildBvh(const float* positions, const uint32_t* indices, uint32_t nTris, c
         for (uint64_t v : part) s += v;
         return s;
       };
-      double dLo = 0.0, dHi = ((double)BDPT_SPLIT_MAX_PER_TRI + 1.0) / pmax;  // at dHi the largest priority is capped
-      if (total(dHi) <= budget) {
-        dLo = dHi;
-      } else {
-        for (int it = 0; it < 40; it++) {
-          const double mid = 0.5 * (dLo + dHi);
-          if (total(mid) <= budget)
-            dLo = mid;
-          else
-            dHi = mid;
-        }
-      }
+      const double D = bvhSplitScale(pmax, budget, total);
       parallelFor(nTris, threads, [&](size_t t0, size_t t1, int) {
         for (size_t t = t0; t < t1; t++)
           if (state[t] != 2 && (((recs[t].flags & kTriNonOpaque) != 0) == (cls == 1)))
-            splits[t] = (uint32_t)std::min<double>(std::floor(dLo * prio[t]), (double)capOf[t]);
+            splits[t] = (uint32_t)std::min<double>(std::floor(D * prio[t]), (double)capOf[t]);
       });
     }
   }
@@ -851,24 +617,27 @@ void buildBvh(const float* positions, const uint32_t* indices, uint32_t nTris, c
     std::vector<RefOut> part((nTris + kRefChunk - 1) / kRefChunk);  // one per chunk, appended in chunk order below
     parallelChunks(nTris, threads, kRefChunk, [&](size_t ci, size_t t0, size_t t1) {
       RefOut& o = part[ci];
+      BigVec<BvhPiece> stack;  // the chunk's split stack: sized to a triangle's split count before it is split
       for (size_t t = t0; t < t1; t++) {
         if (state[t] == 2) continue;
         if (splits[t] == 0 && state[t] == 0) {
-          o.boxes.push_back(triBox[t]);
-          o.tri.push_back((uint32_t)t);
+          o.push(triBox[t].lo, triBox[t].hi, (uint32_t)t);
           continue;
         }
-        Piece pc;
+        // (the whole piece is recomputed here instead of kept since pass 1: a piece is ~400 bytes and a scene may hold millions)
+        const bool alpha = (recs[t].flags & kTriNonOpaque) != 0 && opt.clipper != nullptr;
+        auto clip = [&](double (*poly)[2], int& n) { return opt.clipper->clip((uint32_t)t, poly, n); };
+        auto emit = [&](const BvhPiece& p) { o.push(p.lo, p.hi, (uint32_t)t); };
+        BvhPiece pc;
         bool shrunk = false;
-        if (!wholePiece(t, pc, shrunk)) continue;  // (cannot happen: pass 1 kept it)
+        if (!bvhWholePiece(recs[t], triBox[t].lo, triBox[t].hi, alpha, clip, pc, shrunk)) continue;  // (cannot happen: pass 1 kept it)
         if (splits[t] == 0) {
-          o.boxes.push_back(pc.box);
-          o.tri.push_back((uint32_t)t);
+          emit(pc);
           continue;
         }
         pc.splits = splits[t];
-        const bool alpha = (recs[t].flags & kTriNonOpaque) != 0 && opt.clipper != nullptr;
-        splitTriangle(G, recs[t], (uint32_t)t, pc, alpha ? opt.clipper : nullptr, o);
+        if (stack.size() < splits[t]) stack.resize(splits[t]);
+        bvhSplitTriangle(G, recs[t], pc, alpha, stack.data(), clip, emit);
       }
     });
     std::vector<size_t> at(part.size() + 1, 0);

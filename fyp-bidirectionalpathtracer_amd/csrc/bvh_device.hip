@@ -9,7 +9,9 @@
 //   buildBinaryTreeOnDevice  the binned-SAH binary tree over them
 //   packOnDevice             the four-wide collapse (collapseOnDevice), child boxes quantised, nodes + leaf triangles packed
 //                            into the record array the kernels traverse
-// (on the host: the triangle records, before all of it).
+// (the triangle records, before all of it, are made on the device too unless BDPT_UPLOAD_TRI_RECS hands the host's over).
+// The reference stage has no arithmetic of its own: both builders compile bvh_refs.h.  The tree stage is a different
+// algorithm for the same result:
 //
 // The tree is level-synchronous: every level is a handful of launches —
 //   bounds   node box + centroid box per active node ("slot")   (ordered-uint atomics; a block first reduces the
@@ -39,6 +41,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "bvh_refs.h"
 
 namespace bdpt {
 
@@ -949,38 +952,22 @@ __global__ void k_write_recs(const BvhWideNode* __restrict__ wide, uint32_t nWid
 }
 
 // ------------------------------------------------------------------------------------------------
-// References on the device: bvh_build.cpp's wholePiece + splitTriangle and alpha_clip.cpp's clip(), one thread per
-// triangle — the same double-precision operations in the same order (no contraction: the Makefile's -ffp-contract=off),
-// so the same pieces, the same boxes, in the same order.
+// References on the device, one thread per triangle.  What a thread computes — the whole piece, the alpha clip, priority
+// and cap, bvhSplitTriangle — is bvh_refs.h, the text the host builder compiles too (no contraction on either side: the
+// Makefile's -ffp-contract=off): the same pieces, the same boxes, in the same order.  The kernels load, call and store.
 // ------------------------------------------------------------------------------------------------
-struct DevPiece {
-  double b[kBvhPolyMax][2];
-  int n;
-  uint32_t splits;
-  float lo[3], hi[3];
-};
-struct DevMask {
-  int32_t w, h;
-  const uint32_t* mayPass;
-};
 struct RefArgs {
   const BvhTri* triRecs;
   const BvhBox* triBox;
   const uint32_t* splits;
   const uint8_t* state;
   uint32_t numTris;
-  double gridLo[3], gridExt[3];
+  BvhSplitGrid grid;
   int haveClipper;
-  const uint32_t* triMaterial;
-  const uint32_t* indices;
-  const float* texcoords;  // may be null
-  const int32_t* matMask;
-  const int32_t* matVerdict;
-  const DevMask* masks;
+  BvhClipView clip;  // (with haveClipper) the clipper's tables, in device memory
 };
 
-// buildBvh "Triangle records" (bvh_build.cpp) on the device: v0, e1 = v1 - v0, e2 = v2 - v0, ids; the box of the five
-// points the host takes (v0, v0 + e1, v0 + e2, v1, v2), with its min / max spelled as BvhBox::grow spells them.
+// buildBvh "Triangle records" (bvh_build.cpp) on the device
 __global__ void k_tri_recs(const float* __restrict__ pos, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ flags,
                            const uint32_t* __restrict__ aux, uint32_t n, BvhTri* __restrict__ recs, BvhBox* __restrict__ boxes) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -990,21 +977,7 @@ __global__ void k_tri_recs(const float* __restrict__ pos, const uint32_t* __rest
   const float* c = pos + (size_t)idx[(size_t)t * 3 + 2] * 3;
   BvhTri r;
   BvhBox bx;
-  for (int k = 0; k < 3; k++) {
-    const float va = a[k], vb = b[k], vc = c[k];
-    r.v0[k] = va;
-    r.e1[k] = vb - va;
-    r.e2[k] = vc - va;
-    const float p1 = r.v0[k] + r.e1[k], p2 = r.v0[k] + r.e2[k];
-    float lo = 1e30f, hi = -1e30f;
-    const float pts[5] = {va, p1, p2, vb, vc};
-    for (int j = 0; j < 5; j++) {
-      lo = pts[j] < lo ? pts[j] : lo;
-      hi = hi < pts[j] ? pts[j] : hi;
-    }
-    bx.lo[k] = lo;
-    bx.hi[k] = hi;
-  }
+  bvhTriGeom(a, b, c, r.v0, r.e1, r.e2, bx.lo, bx.hi);
   r.prim = t;
   r.flags = flags ? flags[t] : 0u;
   r.aux = aux ? aux[t] : 0u;
@@ -1012,251 +985,7 @@ __global__ void k_tri_recs(const float* __restrict__ pos, const uint32_t* __rest
   boxes[t] = bx;
 }
 
-BDV float floatDownD(double x) {
-  float f = (float)x;
-  if ((double)f > x) {  // nextafterf(f, -inf)
-    const uint32_t u = __float_as_uint(f);
-    f = (f == 0.0f) ? -__uint_as_float(1u) : __uint_as_float((u & 0x80000000u) ? u + 1u : u - 1u);
-  }
-  return f;
-}
-BDV float floatUpD(double x) {
-  float f = (float)x;
-  if ((double)f < x) {  // nextafterf(f, +inf)
-    const uint32_t u = __float_as_uint(f);
-    f = (f == 0.0f) ? __uint_as_float(1u) : __uint_as_float((u & 0x80000000u) ? u - 1u : u + 1u);
-  }
-  return f;
-}
-BDV double dmin(double a, double b) { return b < a ? b : a; }  // std::min(a, b)
-BDV double dmax(double a, double b) { return a < b ? b : a; }  // std::max(a, b)
-
-// Sutherland-Hodgman against the closed half-plane A + B bu + C bv <= 0 (clipHalfPlane)
-__device__ int devClipHalfPlane(const double (*in)[2], int n, double A, double B, double C, double (*out)[2]) {
-  int m = 0;
-  for (int k = 0; k < n; k++) {
-    const double* p = in[k];
-    const double* q = in[(k + 1) % n];
-    const double fp = A + B * p[0] + C * p[1], fq = A + B * q[0] + C * q[1];
-    if (fp <= 0.0 && m < kBvhPolyMax) {
-      out[m][0] = p[0];
-      out[m][1] = p[1];
-      m++;
-    }
-    if (((fp < 0.0 && fq > 0.0) || (fp > 0.0 && fq < 0.0)) && m < kBvhPolyMax) {
-      const double t = fp / (fp - fq);
-      out[m][0] = p[0] + t * (q[0] - p[0]);
-      out[m][1] = p[1] + t * (q[1] - p[1]);
-      m++;
-    }
-  }
-  return m;
-}
-__device__ int devClipInPlace(double (*poly)[2], int n, double A, double B, double C) {
-  double out[kBvhPolyMax][2];
-  const int m = devClipHalfPlane(poly, n, A, B, C, out);
-  for (int k = 0; k < m; k++) {
-    poly[k][0] = out[k][0];
-    poly[k][1] = out[k][1];
-  }
-  return m;
-}
-__device__ double devPolyArea2(const double (*b)[2], int n) {
-  double s = 0;
-  for (int k = 0; k < n; k++) {
-    const double* p = b[k];
-    const double* q = b[(k + 1) % n];
-    s += p[0] * q[1] - q[0] * p[1];
-  }
-  return fabs(s);
-}
-// intersectBox(polyBox(r, b, n), outer)
-__device__ void devPolyBoxIn(const BvhTri& r, const double (*b)[2], int n, const float* outerLo, const float* outerHi, float* lo, float* hi) {
-  double dlo[3] = {1e300, 1e300, 1e300}, dhi[3] = {-1e300, -1e300, -1e300};
-  for (int k = 0; k < n; k++)
-    for (int a = 0; a < 3; a++) {
-      const double p = (double)r.v0[a] + b[k][0] * (double)r.e1[a] + b[k][1] * (double)r.e2[a];
-      dlo[a] = dmin(dlo[a], p);
-      dhi[a] = dmax(dhi[a], p);
-    }
-  for (int a = 0; a < 3; a++) {
-    const float pl = floatDownD(dlo[a]), ph = floatUpD(dhi[a]);
-    lo[a] = pl < outerLo[a] ? outerLo[a] : pl;  // std::max(a.lo, b.lo)
-    hi[a] = outerHi[a] < ph ? outerHi[a] : ph;  // std::min(a.hi, b.hi)
-    if (hi[a] < lo[a]) hi[a] = lo[a];
-  }
-}
-// SplitGrid::plane
-__device__ int devPlane(const RefArgs& A, int axis, float a, float b, double& coord) {
-  if (!(A.gridExt[axis] > 0.0) || !(b > a)) return -1;
-  const double s = 1073741824.0 / A.gridExt[axis];
-  double ua = floor(((double)a - A.gridLo[axis]) * s), ub = floor(((double)b - A.gridLo[axis]) * s);
-  ua = dmin(dmax(ua, 0.0), 1073741823.0);
-  ub = dmin(dmax(ub, 0.0), 1073741823.0);
-  const uint32_t ia = (uint32_t)ua, ib = (uint32_t)ub;
-  if (ia == ib) return -1;
-  const uint32_t diff = ia ^ ib;
-  const int h = 31 - __clz((int)diff);
-  const uint32_t pl = (ib >> h) << h;
-  coord = A.gridLo[axis] + (double)pl / s;
-  if (!(coord > (double)a && coord < (double)b)) return -1;
-  return h;
-}
-__device__ int devDominant(const RefArgs& A, const float* lo, const float* hi, int& axis, double& coord) {
-  int best = -1;
-  float bestExt = -1.0f;
-  for (int a = 0; a < 3; a++) {
-    double c = 0.0;
-    const int h = devPlane(A, a, lo[a], hi[a], c);
-    const float e = hi[a] - lo[a];
-    if (h > best || (h == best && h >= 0 && e > bestExt)) {
-      best = h;
-      bestExt = e;
-      axis = a;
-      coord = c;
-    }
-  }
-  return best;
-}
-BDV long long devFloorDiv(long long a, long long n) {
-  long long q = a / n;
-  if ((a % n) != 0 && ((a < 0) != (n < 0))) q--;
-  return q;
-}
-// AlphaClipper::Mask::count over mayPass
-__device__ uint32_t devCount(const DevMask& m, long long x0, long long x1, long long y0, long long y1) {
-  if (x1 < x0 || y1 < y0) return 0;
-  const size_t W1 = (size_t)m.w + 1;
-  const uint32_t* sat = m.mayPass;
-  long long xs[2][2], ys[2][2];
-  int nx = 0, ny = 0;
-  {
-    const long long s = devFloorDiv(x0, m.w) * m.w, a = x0 - s, b = x1 - s;
-    if (b < m.w) {
-      xs[nx][0] = a, xs[nx][1] = b, nx++;
-    } else {
-      xs[nx][0] = a, xs[nx][1] = m.w - 1, nx++;
-      xs[nx][0] = 0, xs[nx][1] = (b - m.w) < (long long)(m.w - 1) ? (b - m.w) : (long long)(m.w - 1), nx++;
-    }
-  }
-  {
-    const long long s = devFloorDiv(y0, m.h) * m.h, a = y0 - s, b = y1 - s;
-    if (b < m.h) {
-      ys[ny][0] = a, ys[ny][1] = b, ny++;
-    } else {
-      ys[ny][0] = a, ys[ny][1] = m.h - 1, ny++;
-      ys[ny][0] = 0, ys[ny][1] = (b - m.h) < (long long)(m.h - 1) ? (b - m.h) : (long long)(m.h - 1), ny++;
-    }
-  }
-  uint32_t c = 0;
-  for (int i = 0; i < nx; i++)
-    for (int j = 0; j < ny; j++) {
-      const long long xa = xs[i][0], xb = xs[i][1], ya = ys[j][0], yb = ys[j][1];
-      c += sat[((size_t)yb + 1) * W1 + (size_t)xb + 1] - sat[(size_t)ya * W1 + (size_t)xb + 1] - sat[((size_t)yb + 1) * W1 + (size_t)xa] +
-           sat[(size_t)ya * W1 + (size_t)xa];
-    }
-  return c;
-}
-// AlphaClipper::clip
-__device__ bool devClip(const RefArgs& A, uint32_t tri, double (*poly)[2], int& n) {
-  const uint32_t mat = A.triMaterial[tri];
-  const int32_t mask = A.matMask[mat];
-  if (mask < 0) return A.matVerdict[mat] != 2;
-  // cellRect
-  if (!A.texcoords) return true;
-  const DevMask m = A.masks[mask];
-  double uv[3][2], big = 0.0;
-  for (int k = 0; k < 3; k++) {
-    const uint32_t vi = A.indices[(size_t)tri * 3 + (size_t)k];
-    uv[k][0] = (double)A.texcoords[(size_t)vi * 3];
-    uv[k][1] = (double)A.texcoords[(size_t)vi * 3 + 1];
-    if (!isfinite(uv[k][0]) || !isfinite(uv[k][1])) return true;
-    big = dmax(big, dmax(fabs(uv[k][0]), fabs(uv[k][1])));
-  }
-  if (big > 4096.0) return true;
-  const double margin = 0.5 + 1e-5 * (big + 1.0) * (double)(m.w < m.h ? m.h : m.w);
-  double xa = 1e300, xb = -1e300, ya = 1e300, yb = -1e300;
-  for (int k = 0; k < n; k++) {
-    const double b0 = 1.0 - poly[k][0] - poly[k][1];
-    const double u = uv[0][0] * b0 + uv[1][0] * poly[k][0] + uv[2][0] * poly[k][1];
-    const double v = uv[0][1] * b0 + uv[1][1] * poly[k][0] + uv[2][1] * poly[k][1];
-    const double x = u * (double)m.w - 0.5, y = v * (double)m.h - 0.5;
-    xa = dmin(xa, x);
-    xb = dmax(xb, x);
-    ya = dmin(ya, y);
-    yb = dmax(yb, y);
-  }
-  long long x0 = (long long)floor(xa - margin), x1 = (long long)floor(xb + margin);
-  long long y0 = (long long)floor(ya - margin), y1 = (long long)floor(yb + margin);
-  const bool fullX = x1 - x0 + 1 >= m.w, fullY = y1 - y0 + 1 >= m.h;
-  if (fullX) x0 = 0, x1 = m.w - 1;
-  if (fullY) y0 = 0, y1 = m.h - 1;
-  if (devCount(m, x0, x1, y0, y1) == 0) return false;
-  const double du1 = uv[1][0] - uv[0][0], du2 = uv[2][0] - uv[0][0], dv1 = uv[1][1] - uv[0][1], dv2 = uv[2][1] - uv[0][1];
-  if (!fullX) {
-    long long a = x0, b = x1;  // firstCol
-    while (a < b) {
-      const long long mid = a + (b - a) / 2;
-      if (devCount(m, x0, mid, y0, y1) > 0)
-        b = mid;
-      else
-        a = mid + 1;
-    }
-    const long long c0 = a;
-    a = x0, b = x1;  // lastCol
-    while (a < b) {
-      const long long mid = a + (b - a + 1) / 2;
-      if (devCount(m, mid, x1, y0, y1) > 0)
-        a = mid;
-      else
-        b = mid - 1;
-    }
-    const long long c1 = a;
-    const double uLo = ((double)c0 + 0.5 - margin) / (double)m.w, uHi = ((double)c1 + 1.5 + margin) / (double)m.w;
-    if (c0 > x0) n = devClipInPlace(poly, n, uLo - uv[0][0], -du1, -du2);
-    if (n >= 3 && c1 < x1) n = devClipInPlace(poly, n, uv[0][0] - uHi, du1, du2);
-  }
-  if (n >= 3 && !fullY) {
-    long long a = y0, b = y1;  // firstRow
-    while (a < b) {
-      const long long mid = a + (b - a) / 2;
-      if (devCount(m, x0, x1, y0, mid) > 0)
-        b = mid;
-      else
-        a = mid + 1;
-    }
-    const long long r0 = a;
-    a = y0, b = y1;  // lastRow
-    while (a < b) {
-      const long long mid = a + (b - a + 1) / 2;
-      if (devCount(m, x0, x1, mid, y1) > 0)
-        a = mid;
-      else
-        b = mid - 1;
-    }
-    const long long r1 = a;
-    const double vLo = ((double)r0 + 0.5 - margin) / (double)m.h, vHi = ((double)r1 + 1.5 + margin) / (double)m.h;
-    if (r0 > y0) n = devClipInPlace(poly, n, vLo - uv[0][1], -dv1, -dv2);
-    if (n >= 3 && r1 < y1) n = devClipInPlace(poly, n, uv[0][1] - vHi, dv1, dv2);
-  }
-  return n >= 3;
-}
-
 // ---- pass 1 of bvh_build.cpp and its split counts on the device (BvhRefInput::splits == null) ----
-// splitPriority
-__device__ double devSplitPriority(const RefArgs& A, const BvhTri& r, const float* lo, const float* hi, double polyShare) {
-  int axis = 0;
-  double c = 0;
-  const int h = devDominant(A, lo, hi, axis, c);
-  if (h < 0) return 0.0;
-  const double cx = (double)r.e1[1] * r.e2[2] - (double)r.e1[2] * r.e2[1], cy = (double)r.e1[2] * r.e2[0] - (double)r.e1[0] * r.e2[2],
-               cz = (double)r.e1[0] * r.e2[1] - (double)r.e1[1] * r.e2[0];
-  const double ideal = (fabs(cx) + fabs(cy) + fabs(cz)) * polyShare;
-  const double dx = (double)hi[0] - lo[0], dy = (double)hi[1] - lo[1], dz = (double)hi[2] - lo[2];
-  const double gain = 2.0 * (dx * dy + dy * dz + dz * dx) - ideal;
-  if (!(gain > 0.0)) return 0.0;
-  return bvhCbrt(ldexp(gain, h - 30));
-}
 // what the clipper leaves of every triangle, its priority and the most splits it may get
 __global__ __launch_bounds__(64) void k_prio(RefArgs A, float budgetOpaque, float budgetAlpha, float outlierArea, uint8_t* __restrict__ state,
                                              double* __restrict__ prio, float* __restrict__ capOf, uint32_t* __restrict__ splits) {
@@ -1264,38 +993,15 @@ __global__ __launch_bounds__(64) void k_prio(RefArgs A, float budgetOpaque, floa
   if (t >= A.numTris) return;
   const BvhTri r = A.triRecs[t];
   const BvhBox tb = A.triBox[t];
-  double b[kBvhPolyMax][2];
-  int n = 3;
-  b[0][0] = 0.0;
-  b[0][1] = 0.0;
-  b[1][0] = 1.0;
-  b[1][1] = 0.0;
-  b[2][0] = 0.0;
-  b[2][1] = 1.0;
-  float lo[3] = {tb.lo[0], tb.lo[1], tb.lo[2]}, hi[3] = {tb.hi[0], tb.hi[1], tb.hi[2]};
-  bool shrunk = false;
+  auto clip = [&](double (*poly)[2], int& n) { return bvhClipPoly(A.clip, t, poly, n); };
+  uint8_t st;
+  double p;
+  float cap;
+  bvhRefDecide(A.grid, r, tb.lo, tb.hi, A.haveClipper != 0, clip, budgetOpaque, budgetAlpha, outlierArea, st, p, cap);
+  state[t] = st;
+  prio[t] = p;
+  capOf[t] = cap;
   splits[t] = 0;
-  prio[t] = 0.0;
-  capOf[t] = (float)BDPT_SPLIT_MAX_PER_TRI;
-  const bool nonOpaque = (r.flags & kTriNonOpaque) != 0;
-  if (nonOpaque && A.haveClipper) {
-    if (!devClip(A, t, b, n) || n < 3) {
-      state[t] = 2;
-      return;
-    }
-    shrunk = !(n == 3 && b[0][0] == 0.0 && b[0][1] == 0.0 && b[1][0] == 1.0 && b[1][1] == 0.0 && b[2][0] == 0.0 && b[2][1] == 1.0);
-    if (shrunk) devPolyBoxIn(r, b, n, tb.lo, tb.hi, lo, hi);
-  }
-  state[t] = shrunk ? 1 : 0;
-  const float budget = nonOpaque ? budgetAlpha : budgetOpaque;
-  const float area = areaOf(lo, hi);
-  if (budget > 0.0f && (nonOpaque || area >= outlierArea)) {
-    prio[t] = devSplitPriority(A, r, lo, hi, shrunk ? devPolyArea2(b, n) : 1.0);
-    if (!nonOpaque && outlierArea > 0.0f) {
-      const float f = floorf((float)BDPT_SPLIT_OUTLIER * area / outlierArea);
-      capOf[t] = f < (float)BDPT_SPLIT_MAX_PER_TRI ? f : (float)BDPT_SPLIT_MAX_PER_TRI;  // std::min(MAX, f)
-    }
-  }
 }
 BDV bool inClass(const RefArgs& A, const uint8_t* state, uint32_t t, int cls) {
   return state[t] != 2 && (((A.triRecs[t].flags & kTriNonOpaque) != 0) == (cls == 1));
@@ -1374,7 +1080,7 @@ __global__ void k_ref_caps(RefArgs A, uint32_t* __restrict__ capRefs, uint32_t* 
 }
 // pass 2 of bvh_build.cpp for triangle t: its references' boxes into boxes[slotAt[t] ...], their number into made[t]
 __global__ __launch_bounds__(64) void k_make_refs(RefArgs A, const uint32_t* __restrict__ slotAt, const uint32_t* __restrict__ stackAt,
-                                                  DevPiece* __restrict__ stacks, BvhBox* __restrict__ boxes, uint32_t* __restrict__ made) {
+                                                  BvhPiece* __restrict__ stacks, BvhBox* __restrict__ boxes, uint32_t* __restrict__ made) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= A.numTris) return;
   const uint32_t st = A.state[t];
@@ -1392,30 +1098,9 @@ __global__ __launch_bounds__(64) void k_make_refs(RefArgs A, const uint32_t* __r
   }
   const BvhTri r = A.triRecs[t];
   const bool alpha = (r.flags & kTriNonOpaque) != 0 && A.haveClipper;
-  // wholePiece
-  DevPiece pc;
-  pc.n = 3;
-  pc.b[0][0] = 0.0;
-  pc.b[0][1] = 0.0;
-  pc.b[1][0] = 1.0;
-  pc.b[1][1] = 0.0;
-  pc.b[2][0] = 0.0;
-  pc.b[2][1] = 1.0;
-  for (int a = 0; a < 3; a++) {
-    pc.lo[a] = tb.lo[a];
-    pc.hi[a] = tb.hi[a];
-  }
-  if (alpha) {
-    if (!devClip(A, t, pc.b, pc.n) || pc.n < 3) {  // (cannot happen: pass 1 kept it)
-      made[t] = 0;
-      return;
-    }
-    const bool shrunk =
-        !(pc.n == 3 && pc.b[0][0] == 0.0 && pc.b[0][1] == 0.0 && pc.b[1][0] == 1.0 && pc.b[1][1] == 0.0 && pc.b[2][0] == 0.0 && pc.b[2][1] == 1.0);
-    if (shrunk) devPolyBoxIn(r, pc.b, pc.n, tb.lo, tb.hi, pc.lo, pc.hi);
-  }
+  auto clip = [&](double (*poly)[2], int& n) { return bvhClipPoly(A.clip, t, poly, n); };
   uint32_t m = 0;
-  auto emit = [&](const DevPiece& p) {
+  auto emit = [&](const BvhPiece& p) {
     BvhBox bx;
     for (int a = 0; a < 3; a++) {
       bx.lo[a] = p.lo[a];
@@ -1423,57 +1108,17 @@ __global__ __launch_bounds__(64) void k_make_refs(RefArgs A, const uint32_t* __r
     }
     out[m++] = bx;
   };
-  if (nSplits == 0) {
-    emit(pc);
-    made[t] = m;
+  BvhPiece pc;
+  bool shrunk = false;
+  if (!bvhWholePiece(r, tb.lo, tb.hi, alpha, clip, pc, shrunk)) {  // (cannot happen: pass 1 kept it)
+    made[t] = 0;
     return;
   }
-  pc.splits = nSplits;
-  // splitTriangle
-  DevPiece* const stack = stacks + stackAt[t];
-  uint32_t sp = 0;
-  for (;;) {
-    for (int guard = 0;; guard++) {
-      int axis = 0;
-      double c = 0;
-      if (pc.splits == 0 || guard > 96 || pc.n + 2 > kBvhPolyMax || devDominant(A, pc.lo, pc.hi, axis, c) < 0) {
-        emit(pc);
-        break;
-      }
-      const double PA = (double)r.v0[axis] - c, PB = (double)r.e1[axis], PC = (double)r.e2[axis];
-      DevPiece lo, hi;
-      lo.n = devClipHalfPlane(pc.b, pc.n, PA, PB, PC, lo.b);
-      hi.n = devClipHalfPlane(pc.b, pc.n, -PA, -PB, -PC, hi.b);
-      bool haveLo = lo.n >= 3 && devPolyArea2(lo.b, lo.n) > 0.0, haveHi = hi.n >= 3 && devPolyArea2(hi.b, hi.n) > 0.0;
-      if (alpha) {
-        if (haveLo) haveLo = devClip(A, t, lo.b, lo.n) && lo.n >= 3;
-        if (haveHi) haveHi = devClip(A, t, hi.b, hi.n) && hi.n >= 3;
-      }
-      if (haveLo) devPolyBoxIn(r, lo.b, lo.n, pc.lo, pc.hi, lo.lo, lo.hi);
-      if (haveHi) devPolyBoxIn(r, hi.b, hi.n, pc.lo, pc.hi, hi.lo, hi.hi);
-      if (!haveLo && !haveHi) {
-        if (!alpha) emit(pc);  // (a sliver the clip lost to rounding: keep the piece as it was)
-        break;
-      }
-      if (!haveLo || !haveHi) {
-        const uint32_t s = pc.splits;
-        pc = haveLo ? lo : hi;
-        pc.splits = s;
-        continue;
-      }
-      const uint32_t rest = pc.splits - 1;
-      const double wl = ((double)lo.hi[0] - lo.lo[0]) + ((double)lo.hi[1] - lo.lo[1]) + ((double)lo.hi[2] - lo.lo[2]);
-      const double wh = ((double)hi.hi[0] - hi.lo[0]) + ((double)hi.hi[1] - hi.lo[1]) + ((double)hi.hi[2] - hi.lo[2]);
-      uint32_t sl = (wl + wh > 0.0) ? (uint32_t)floor((double)rest * wl / (wl + wh) + 0.5) : rest / 2;
-      if (sl > rest) sl = rest;
-      lo.splits = sl;
-      hi.splits = rest - sl;
-      stack[sp++] = hi;
-      pc = lo;
-      guard = 0;
-    }
-    if (sp == 0) break;
-    pc = stack[--sp];
+  if (nSplits == 0) {
+    emit(pc);
+  } else {
+    pc.splits = nSplits;
+    bvhSplitTriangle(A.grid, r, pc, alpha, stacks + stackAt[t], clip, emit);
   }
   made[t] = m;
 }
@@ -2400,8 +2045,8 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
   A.state = dState;
   A.numTris = nT;
   for (int a = 0; a < 3; a++) {
-    A.gridLo[a] = in.gridLo[a];
-    A.gridExt[a] = in.gridExt[a];
+    A.grid.lo[a] = in.gridLo[a];
+    A.grid.ext[a] = in.gridExt[a];
   }
   if (in.clipper) {
     BvhClipTables tb;
@@ -2412,7 +2057,7 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
     uint32_t *dMat = nullptr, *dIdx = nullptr;
     float* dTex = nullptr;
     int32_t *dMask = nullptr, *dVerdict = nullptr;
-    DevMask* dMasks = nullptr;
+    BvhClipMask* dMasks = nullptr;
     if (dIdxAll && tb.indices == in.indices)
       dIdx = dIdxAll;  // (already here)
     else if (!upload(&dIdx, tb.indices, (size_t)nT * 3))
@@ -2421,20 +2066,15 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
         !upload(&dVerdict, tb.matVerdict.data(), tb.matVerdict.size()))
       return false;
     if (tb.texcoords && !upload(&dTex, tb.texcoords, (size_t)tb.numVertices * 3)) return false;
-    std::vector<DevMask> masks;
+    std::vector<BvhClipMask> masks;
     for (const BvhClipTables::Mask& m : tb.masks) {
       uint32_t* dSat = nullptr;
       if (!upload(&dSat, m.mayPass, ((size_t)m.w + 1) * ((size_t)m.h + 1))) return false;
-      masks.push_back(DevMask{m.w, m.h, dSat});
+      masks.push_back(BvhClipMask{m.w, m.h, dSat});
     }
     if (!upload(&dMasks, masks.data(), masks.size())) return false;
     A.haveClipper = 1;
-    A.triMaterial = dMat;
-    A.indices = dIdx;
-    A.texcoords = dTex;
-    A.matMask = dMask;
-    A.matVerdict = dVerdict;
-    A.masks = dMasks;
+    A.clip = BvhClipView{dMat, dIdx, dTex, dMask, dVerdict, dMasks};
   }
   lap("refs upload");
   hipStream_t st = nullptr;
@@ -2466,23 +2106,12 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
         if (hipMemcpy(&v, dSum, 8, hipMemcpyDeviceToHost) != hipSuccess) failed = true;
         return v;
       };
-      double dLo = 0.0, dHi = ((double)BDPT_SPLIT_MAX_PER_TRI + 1.0) / pmax;  // at dHi the largest priority is capped
-      if (total(dHi) <= budget) {
-        dLo = dHi;
-      } else {
-        for (int it = 0; it < 40; it++) {
-          const double mid = 0.5 * (dLo + dHi);
-          if (total(mid) <= budget)
-            dLo = mid;
-          else
-            dHi = mid;
-        }
-      }
+      const double D = bvhSplitScale(pmax, budget, total);
       if (failed) {
         err = "device reference maker: split counts failed";
         return false;
       }
-      hipLaunchKernelGGL(k_split_assign, grid, blk, 0, st, A, dState, prio, capOf, cls, dLo, dSplits);
+      hipLaunchKernelGGL(k_split_assign, grid, blk, 0, st, A, dState, prio, capOf, cls, D, dSplits);
     }
     lap("refs decide");
   }
@@ -2512,7 +2141,7 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
     if (in.numDroppedOut) *in.numDroppedOut = (uint32_t)sum[0];
   }
   BvhBox* boxes = nullptr;
-  DevPiece* stacks = nullptr;
+  BvhPiece* stacks = nullptr;
   if (!devAllocT(pool, &boxes, totalSlots, err) || !devAllocT(pool, &stacks, totalStack, err)) return false;
   if (plain)
     hipLaunchKernelGGL(k_plain_refs, grid, blk, 0, st, A, slotAt, boxes, made);

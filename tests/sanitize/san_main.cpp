@@ -1,6 +1,7 @@
 // CPU-only sanitizer run (AddressSanitizer + UBSan; GPU sanitizers are not available on the pool): the host-side
 // C++ that never touches the device — scene factories, scene loader, BVH builder — and the oracle, driven the way
 // the tests drive them.  Built and run by tests/test_sanitizers.py.
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "../../fyp-bidirectionalpathtracer_amd/csrc/bvh.h"
+#include "../../fyp-bidirectionalpathtracer_amd/csrc/bvh_refs.h"
 #include "../../include/bdpt.h"
 #include "../../include/bdpt_scene.h"
 #include "../../oracle/bdpt_oracle.h"
@@ -138,6 +140,47 @@ int main(int argc, char** argv) {
       rc |= 1;
     }
     bdpt_scene_destroy(sc);
+  }
+  {  // the builders' outward rounding (bvh_refs.h: the next float on the bits, for the host and the device alike) against
+     // std::nextafterf: the edges, then a million random doubles of every float magnitude, denormals included
+    auto down = [](double x) {
+      float f = (float)x;
+      if ((double)f > x) f = std::nextafterf(f, -INFINITY);
+      return f;
+    };
+    auto up = [](double x) {
+      float f = (float)x;
+      if ((double)f < x) f = std::nextafterf(f, INFINITY);
+      return f;
+    };
+    uint64_t tried = 0, wrong = 0;
+    auto check = [&](double x) {
+      const float d0 = down(x), d1 = bdpt::bvhFloatDown(x), u0 = up(x), u1 = bdpt::bvhFloatUp(x);
+      tried++;
+      if (std::memcmp(&d0, &d1, 4) != 0 || std::memcmp(&u0, &u1, 4) != 0 || !((double)d1 <= x && x <= (double)u1)) wrong++;
+    };
+    const float tiny = std::nextafterf(0.0f, 1.0f);  // the smallest denormal
+    for (double x : {0.0, 1e-300, 4.9e-324, 1e-60, 0.4 * (double)tiny, 0.5 * (double)tiny, 0.6 * (double)tiny})  // +-0 and what rounds to it
+      for (double sgn : {1.0, -1.0}) check(sgn * x);
+    for (float f : {tiny, 2.0f * tiny, 12345.0f * tiny, 0.5f * FLT_MIN, std::nextafterf(FLT_MIN, 0.0f), FLT_MIN, 1.0f, std::nextafterf(1.0f, 0.0f), 0.1f,
+                    16777216.0f, 3.0e38f, FLT_MAX})
+      for (float sgn : {1.0f, -1.0f}) {
+        const double x = (double)(sgn * f);
+        check(x);  // a float, and one double ulp either side of it
+        check(std::nextafter(x, -INFINITY));
+        check(std::nextafter(x, INFINITY));
+        check(0.5 * (x + (double)std::nextafterf(sgn * f, 0.0f)));  // halfway to its neighbour
+      }
+    uint64_t st = 0x9e3779b97f4a7c15ull;
+    auto rnd = [&]() { return st = st * 6364136223846793005ull + 1442695040888963407ull; };
+    for (int i = 0; i < 1000000; i++) {
+      const double m = 1.0 + (double)(rnd() >> 11) / 9007199254740992.0;  // [1, 2), all 52 mantissa bits
+      const int e = (int)((rnd() >> 33) % 279u) - 151;                    // 2^-151 (below the denormals) .. 2^127
+      const double x = std::ldexp((rnd() >> 63) ? -m : m, e);
+      if (std::fabs(x) <= (double)FLT_MAX) check(x);
+    }
+    std::printf("outward rounding: %llu values, %llu differ from nextafterf\n", (unsigned long long)tried, (unsigned long long)wrong);
+    if (wrong || tried < 900000) rc |= 1;
   }
   {  // scene loader on a small OBJ + MTL + PPM
     std::ofstream(tmp + "/san.mtl") << "newmtl a\nKd 0.5 0.6 0.7\nKs 0.1 0.1 0.1\nNs 0.4\nmap_Kd san.ppm\nnewmtl b.DoubleSided\nKe 1 1 1\n";

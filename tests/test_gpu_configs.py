@@ -525,6 +525,16 @@ def _many_cards_scene(pkg, n_cards, tex, uv_scale, rng, threshold=0.5, jitter=0.
     return d, [tex, pos, nrm, uv, idx, tri_mat, mats, texs, lights]
 
 
+def _blob_texture(rng):
+    """64 x 64 texels, alpha 255 inside twelve random discs and 0 outside."""
+    blobs = np.zeros((64, 64, 4), np.uint8)
+    yy, xx = np.mgrid[0:64, 0:64]
+    for _ in range(12):
+        cx, cy, r = rng.uniform(0, 64, 3)
+        blobs[..., 3] = np.maximum(blobs[..., 3], np.where((xx - cx) ** 2 + (yy - cy) ** 2 < (4 + r / 8) ** 2, 255, 0))
+    return blobs
+
+
 def test_device_builder_on_adversarial_inputs(pkg, monkeypatch):
     """The device build against the host build (packed records + summary, bdpt_bvh_recs_hash) where the code paths fork:
     reference counts on either side of the one-wave-per-node bound (1024) and of the wave sort's bound (2048), every
@@ -552,11 +562,8 @@ def test_device_builder_on_adversarial_inputs(pkg, monkeypatch):
     cases.append(("line 3000", soup(3000, lambda m: np.stack([rng.uniform(-5, 5, m), np.zeros(m), np.zeros(m)], 1), size=0.0), {}))
     cases.append(("plane 3000", soup(3000, lambda m: np.stack([rng.uniform(-5, 5, m), rng.uniform(-5, 5, m), np.full(m, 2.0)], 1), size=0.0), {}))
     cases.append(("24 decades", soup(6000, lambda m: np.exp(rng.uniform(-27, 27, (m, 3))) * rng.choice([-1.0, 1.0], (m, 3)), size=1e-3), {}))
-    blobs = np.zeros((64, 64, 4), np.uint8)
+    blobs = _blob_texture(rng)
     yy, xx = np.mgrid[0:64, 0:64]
-    for _ in range(12):
-        cx, cy, r = rng.uniform(0, 64, 3)
-        blobs[..., 3] = np.maximum(blobs[..., 3], np.where((xx - cx) ** 2 + (yy - cy) ** 2 < (4 + r / 8) ** 2, 255, 0))
     checker = np.zeros((16, 16, 4), np.uint8)
     checker[..., 3] = np.where((xx[:16, :16] + yy[:16, :16]) % 2 == 0, 255, 0)
     dot = np.zeros((32, 32, 4), np.uint8)
@@ -587,3 +594,38 @@ def test_device_builder_on_adversarial_inputs(pkg, monkeypatch):
         for k in env:
             monkeypatch.delenv(k)
         sc.close()
+
+
+def test_device_reference_maker_forks(pkg, monkeypatch):
+    """The two forks of the device reference maker that no other test takes, against the host build (packed records +
+    summary, bdpt_bvh_recs_hash): BDPT_HOST_PRIORITIES (the host decides what the clipper leaves, the priorities and the split
+    counts, and uploads state and counts: k_prio and the split-count kernels are skipped) and BDPT_UPLOAD_TRI_RECS (the
+    host's triangle records and boxes are uploaded: k_tri_recs is skipped), next to the default path.  400 alpha-masked
+    blob cards tiled 3.7 times plus the opaque floor, opaque budget 2 (the floor is an outlier and is split), alpha budget
+    16: references must outnumber the kept triangles, so nothing passes by never splitting.  A card tiled 3.7 times sees
+    every texel of a texture that has any passing cell, so no triangle of that scene can be dropped, whatever the seed; the
+    same cards over half a period of the same texture supply the dropped triangles, and both scenes go through all three
+    paths."""
+    lib = pkg.load_library()
+    rng = np.random.default_rng(5)
+    blobs = _blob_texture(rng)
+    monkeypatch.setenv("BDPT_SPLIT_BUDGET", "2")
+    monkeypatch.setenv("BDPT_SPLIT_BUDGET_ALPHA", "16")
+    for uv_scale, drops in ((3.7, False), (0.5, True)):
+        d, keep = _many_cards_scene(pkg, 400, blobs, uv_scale, rng)
+
+        def build(dev):
+            h = C.c_uint64()
+            info = pkg.abi.BvhInfo()
+            assert lib.bdpt_bvh_recs_hash(C.byref(d), dev, C.byref(h), C.byref(info)) == 0, (uv_scale, dev)
+            return (h.value, info.numNodes, info.maxDepth, info.maxStack, info.sahCost, info.numReferences, info.numDropped, info.reserved)
+        host = build(-1)
+        assert host[5] > d.numTriangles - host[6], (uv_scale, host)  # pieces were split off
+        assert (host[6] > 0) == drops, (uv_scale, host)              # the clipper dropped triangles
+        for fork in (None, "BDPT_HOST_PRIORITIES", "BDPT_UPLOAD_TRI_RECS"):
+            if fork:
+                monkeypatch.setenv(fork, "1")
+            assert build(0) == host, (uv_scale, fork)
+            if fork:
+                monkeypatch.delenv(fork)
+        del keep
