@@ -417,6 +417,25 @@ void bdpt_destroy(bdpt_ctx* c) {
 
 const char* bdpt_last_error(const bdpt_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
+// The scene's acceleration structure built on `device` (bvh_device.hip: references, binary tree, collapse and packed
+// records — the records the host code produces, bit for bit).  The one place that reads the build's measurement knobs,
+// at every call: BDPT_HOST_PRIORITIES (the host decides what the clipper leaves, priorities and split counts),
+// BDPT_UPLOAD_TRI_RECS (the host's triangle records and boxes are uploaded).
+static void buildSceneBvhOnDevice(const bdpt_scene_desc* d, int device, bool classify, SceneBvh& sb, std::string& error) {
+  struct Build {
+    BvhDeviceBuild* b;
+    ~Build() { bvhDeviceBuildEnd(b); }
+  } build{bvhDeviceBuildBegin(device)};
+  BvhBackend be;
+  be.user = build.b;
+  be.makeRefs = makeReferencesOnDevice;
+  be.buildTree = buildBinaryTreeOnDevice;
+  be.pack = packOnDevice;
+  be.hostPriorities = std::getenv("BDPT_HOST_PRIORITIES") != nullptr;
+  be.uploadTriRecs = std::getenv("BDPT_UPLOAD_TRI_RECS") != nullptr;
+  buildSceneBvh(d, 0, -1.0f, -1.0f, classify, sb, &be, &error);
+}
+
 static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
   if (!c || !d) return BDPT_E_INVALID;
   if (!d->positions || !d->normals || !d->indices || !d->triMaterial || !d->materials || !d->numMaterials) {
@@ -584,15 +603,8 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
   // traversal flags, alpha classification, spatial pre-splitting and the tree itself: scene_bvh.cpp
   SceneBvh sb;
   try {
-    // the binary tree is built, and the records are quantised and packed, on this context's device (bvh_device.hip):
-    // the records the host code produces, bit for bit
     std::string treeError;
-    struct Build {
-      BvhDeviceBuild* b;
-      ~Build() { bvhDeviceBuildEnd(b); }
-    } build{bvhDeviceBuildBegin(c->device, std::getenv("BDPT_HOST_COLLAPSE") == nullptr)};  // (measurement knob: the collapse on the host)
-    buildSceneBvh(d, 0, -1.0f, -1.0f, std::getenv("BDPT_NO_ALPHA_CLASSIFY") == nullptr, sb, buildBinaryTreeOnDevice, build.b, &treeError, packOnDevice, makeReferencesOnDevice,
-                  std::getenv("BDPT_HOST_COLLAPSE") == nullptr, std::getenv("BDPT_HOST_PRIORITIES") == nullptr);
+    buildSceneBvhOnDevice(d, c->device, std::getenv("BDPT_NO_ALPHA_CLASSIFY") == nullptr, sb, treeError);
     if (sb.bvh.deviceRecs) c->sceneAllocs.push_back(sb.bvh.deviceRecs);  // (the context's from here on)
     if (!treeError.empty()) {
       fail(c, "scene: " + treeError);
@@ -2223,14 +2235,17 @@ int bdpt_accumulate_tile(bdpt_ctx* c, float* lastFrame, float* curFrame, uint32_
 // use for the binary tree: device >= 0 the device implementation on that device, < 0 the host code (the default).
 int bdpt_test_tree_builder(int device) {
   static BvhDeviceBuild* sBuild = nullptr;
-  bvhSetDefaultTreeBuilder(nullptr, nullptr);
+  bvhSetDefaultBackend(BvhBackend());
   if (sBuild) bvhDeviceBuildEnd(sBuild);
   sBuild = nullptr;
   if (device < 0) return BDPT_OK;
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || device >= count) return BDPT_E_HIP;
   sBuild = bvhDeviceBuildBegin(device);
-  bvhSetDefaultTreeBuilder(buildBinaryTreeOnDevice, sBuild);
+  BvhBackend treeOnly;
+  treeOnly.user = sBuild;
+  treeOnly.buildTree = buildBinaryTreeOnDevice;
+  bvhSetDefaultBackend(treeOnly);
   return BDPT_OK;
 }
 
@@ -2251,12 +2266,7 @@ int bdpt_bvh_recs_hash(const bdpt_scene_desc* d, int device, uint64_t* out_hash,
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device >= count) return BDPT_E_HIP;
     std::string error;
-    struct Build {
-      BvhDeviceBuild* b;
-      ~Build() { bvhDeviceBuildEnd(b); }
-    } build{bvhDeviceBuildBegin(device, std::getenv("BDPT_HOST_COLLAPSE") == nullptr)};
-    buildSceneBvh(d, 0, -1.0f, -1.0f, true, sb, buildBinaryTreeOnDevice, build.b, &error, packOnDevice, makeReferencesOnDevice, std::getenv("BDPT_HOST_COLLAPSE") == nullptr,
-                  std::getenv("BDPT_HOST_PRIORITIES") == nullptr);
+    buildSceneBvhOnDevice(d, device, true, sb, error);
     if (!sb.bvh.deviceRecs && !sb.bvh.recs.empty() && error.empty()) {  // (nothing to build a tree over: the host's one empty node)
       recs = sb.bvh.recs.data();
       numRecs = sb.bvh.recs.size();

@@ -157,7 +157,7 @@ struct Bvh {
   uint32_t numDropped = 0;   // input triangles with no reference at all (the clipper found nothing that can be hit)
   uint32_t numNodes = 0;     // four-wide nodes and references (= nodes.size(), tris.size() when the host code packed)
   uint32_t numRefs = 0;
-  // With BvhBuildOptions::packer: the packed records are built in device memory and nodes / tris / refBox / recs stay empty.
+  // With BvhBackend::pack: the packed records are built in device memory and nodes / tris / refBox / recs stay empty.
   void* deviceRecs = nullptr;  // hipMalloc'ed, the caller's to free
   size_t deviceNumRecs = 0;    // (including the kBvhPadRecs pad records)
 };
@@ -278,13 +278,40 @@ struct BvhBuildNode {  // (no member initialisers: arrays of these are sized wit
   uint32_t depth;
 };
 static_assert(sizeof(BvhBuildNode) == 44, "binary node");
-// Builds the binary tree over refs[0, n) — binned SAH, stable partitions, median fallback: the decisions, the order of the
-// references and the tree of bvh_build.cpp's host code, bit for bit — somewhere else (bdpt_set_scene plugs in the device
-// implementation, bvh_device.hip).  `refs` stays as it is; order[i] is the reference (its index = its id) at position i
-// of the leaf order the nodes' ranges speak of.  nodes[0] is the root; children come after their parents.  false + err
-// on failure.
+// ---- the stages of buildBvh that can run somewhere else (bdpt_set_scene: on the device, bvh_device.hip) ----
+// Each produces what the host code of bvh_build.cpp produces, bit for bit, and hands it to the next one of the same `user`
+// where it works.  false + err on failure.
+//
+// Makes the references (bvh_build.cpp "References": every triangle's whole piece, shrunk by the clipper, split `splits`
+// times, every piece clipped again) in the host code's order and keeps them, the triangle of each and the triangle
+// records for the two stages below.
+struct BvhRefInput {
+  const BvhTri* triRecs;   // one per input triangle; null with triBox: made from positions / indices / triFlags / triAux
+  const BvhBox* triBox;    // where the maker works (buildBvh "Triangle records": plain fp32 arithmetic, bit-identical)
+  bool uploadTriRecs;      // the two arrays above are there and are the ones to use
+  const uint32_t* splits;  // split count per triangle; null: the maker also decides what the clipper leaves of every
+  const uint8_t* state;    // triangle (state: 0 = plain reference (triBox), 1 = shrunk by the clipper, 2 = dropped), its split
+  uint32_t numTris;        // priority and the split counts that meet the budgets below (bvh_build.cpp pass 1 + "split counts")
+  float budgetOpaque, budgetAlpha;  // extra references per triangle of the class, on average (0: the class is not split)
+  float outlierArea;                // opaque triangles below this box area are never split
+  uint32_t* numDroppedOut;          // (with splits == null) receives the number of dropped triangles
+  double gridLo[3], gridExt[3];      // the scene box: the split planes are its spatial medians
+  const BvhRefClipper* clipper;      // for the non-opaque triangles; may be null
+  const float* positions;            // buildBvh's inputs: (12 numVertices + 20 numTris) bytes to hand over instead of
+  const uint32_t* indices;           // the 72 numTris of triRecs + triBox
+  const uint32_t* triFlags;          // may be null (all 0)
+  const uint32_t* triAux;            // may be null (all 0)
+  uint32_t numVertices;
+};
+using BvhRefMaker = bool (*)(void* user, const BvhRefInput& in, uint32_t& numRefs, std::string& err);
+// Builds the binary tree over n references — binned SAH, stable partitions, median fallback: the decisions, the order of
+// the references and the tree of bvh_build.cpp's host code.  nodes[0] is the root; children come after their parents.
+//   refs != null (no BvhRefMaker in the backend): refs[0, n) stay as they are; order[i] is the reference (its index = its
+//     id) at position i of the leaf order the nodes' ranges speak of, and `nodes` is the whole tree.
+//   refs == null: the references the BvhRefMaker of the same `user` kept; order and tree stay there for the BvhPacker,
+//     `order` comes back empty and `nodes` holds the root alone.
 using BvhTreeBuilder = bool (*)(void* user, const BvhBuildRef* refs, uint32_t n, BigVec<uint32_t>& order, BigVec<BvhBuildNode>& nodes, std::string& err);
-// After the collapse (host): the four-wide nodes as lists of binary nodes, and where each one's index goes in its parent.
+// After the collapse: the four-wide nodes as lists of binary nodes, and where each one's index goes in its parent.
 struct BvhWideNode {
   uint32_t src;      // binary node this wide node covers
   uint32_t kids[4];  // the binary nodes that became its (up to 4) children
@@ -295,53 +322,35 @@ struct BvhSlot {
   int32_t node, idx;  // wide node and child slot that refer to this wide node (-1: the root)
 };
 struct Bvh;
+// Everything after the binary tree — the four-wide collapse, the child boxes quantised, nodes and leaf triangles packed
+// into the device's record array — from what the two stages above of the same `user` left behind.  Fills out.deviceRecs /
+// out.deviceNumRecs (the caller owns the allocation: hipFree) and out.numNodes / maxDepth / maxStack / sahCost.
 struct BvhPackInput {
-  const BvhTri* triRecs;  // one per input triangle
-  uint32_t numTris;
-  const uint32_t* refTri;  // the triangle of every reference, by reference id (null: the BvhRefMaker of this build kept it, and triRecs)
-  uint32_t numRefs;
-  const BvhWideNode* wide;  // null: the collapse has not happened — the packer does it from the tree of this build and fills
-  const BvhSlot* slots;     // out.numNodes / maxDepth / maxStack / sahCost as well
-  size_t numWide;
+  uint32_t numTris, numRefs;
   float pad;  // what every child box is padded by before it is quantised
 };
-// Makes the references (bvh_build.cpp "References": every triangle's whole piece, shrunk by the clipper, split `splits`
-// times, every piece clipped again) somewhere else, in the host code's order, and keeps them there for the
-// BvhTreeBuilder of the same `user` (which is then called with refs = null) and the BvhPacker.
-struct BvhRefInput {
-  const BvhTri* triRecs;   // one per input triangle
-  const BvhBox* triBox;
-  const uint32_t* splits;  // split count per triangle; null: the maker also decides what the clipper leaves of every
-  const uint8_t* state;    // triangle (state: 0 = plain reference (triBox), 1 = shrunk by the clipper, 2 = dropped), its split
-  uint32_t numTris;        // priority and the split counts that meet the budgets below (bvh_build.cpp pass 1 + "split counts")
-  float budgetOpaque, budgetAlpha;  // extra references per triangle of the class, on average (0: the class is not split)
-  float outlierArea;                // opaque triangles below this box area are never split
-  uint32_t* numDroppedOut;          // (with splits == null) receives the number of dropped triangles
-  double gridLo[3], gridExt[3];      // the scene box: the split planes are its spatial medians
-  const BvhRefClipper* clipper;      // for the non-opaque triangles; may be null
-  // What triRecs / triBox were made from (buildBvh's inputs; numVertices 0: not given).  A maker that works on another
-  // device can make the two arrays there from these — (12 numVertices + 20 numTris) bytes to hand over instead of
-  // 72 numTris — with the loop of buildBvh "Triangle records", which is plain fp32 arithmetic (bit-identical).
-  const float* positions = nullptr;
-  const uint32_t* indices = nullptr;
-  const uint32_t* triFlags = nullptr;  // may be null (all 0)
-  const uint32_t* triAux = nullptr;    // may be null (all 0)
-  uint32_t numVertices = 0;
-};
-using BvhRefMaker = bool (*)(void* user, const BvhRefInput& in, uint32_t& numRefs, std::string& err);
-// Quantises the child boxes and packs nodes and leaf triangles into the device's record array — what the host code does
-// between "collapse" and the upload — from the order and the nodes the BvhTreeBuilder of the same `user` left behind.
-// Fills out.deviceRecs / out.deviceNumRecs (the caller owns the allocation: hipFree) and nothing else.
 using BvhPacker = bool (*)(void* user, const BvhPackInput& in, Bvh& out, std::string& err);
-// Test hook: the tree builder (and packer) buildBvh uses when its options name none (null = the host code).
-// bdpt_test_tree_builder (api.cpp) points it at the device implementation so that the host-only hash / check hooks can be
-// run over a device-built tree and compared with the host-built one.
-void bvhSetDefaultTreeBuilder(BvhTreeBuilder f, void* user);
+// Where the stages run.  Two shapes besides the empty one (all host code) are legal, and buildBvh refuses any other:
+//   buildTree alone             host references, host collapse, host pack (the test hook bdpt_test_tree_builder)
+//   makeRefs, buildTree, pack   the whole pipeline (bdpt_set_scene)
+struct BvhBackend {
+  void* user = nullptr;  // handed to every stage
+  BvhRefMaker makeRefs = nullptr;
+  BvhTreeBuilder buildTree = nullptr;
+  BvhPacker pack = nullptr;
+  // The whole pipeline's two forks (measurement knobs of bdpt_set_scene, BDPT_HOST_PRIORITIES / BDPT_UPLOAD_TRI_RECS):
+  bool hostPriorities = false;  // the host decides what the clipper leaves, the priorities and the split counts (BvhRefInput::splits / state)
+  bool uploadTriRecs = false;   // the host's triangle records and boxes are uploaded (BvhRefInput::uploadTriRecs)
+};
+// Test hook: the backend buildBvh uses when its options name none (default: the empty one, all host code).
+// bdpt_test_tree_builder (api.cpp) sets the tree-only shape with the device implementation so that the host-only hash /
+// check hooks can be run over a device-built tree and compared with the host-built one.
+void bvhSetDefaultBackend(const BvhBackend& b);
 
 // The device implementation (bvh_device.hip).  One BvhDeviceBuild per build: the stages hand their results to one another
-// in device memory through it (`user` of both functions).
+// in device memory through it (`user` of the three functions).
 struct BvhDeviceBuild;
-BvhDeviceBuild* bvhDeviceBuildBegin(int device, bool collapseOnDevice = false);
+BvhDeviceBuild* bvhDeviceBuildBegin(int device);
 void bvhDeviceBuildEnd(BvhDeviceBuild* b);
 // pageable host memory -> the current device through pinned staging buffers and a few copy threads (bvh_device.hip)
 bool bvhUploadStaged(void* dst, const void* src, size_t bytes, std::string& err);
@@ -358,14 +367,9 @@ struct BvhBuildOptions {
   float splitBudget = -1.0f;      // < 0: the build default (BDPT_SPLIT_BUDGET)
   float splitBudgetAlpha = -1.0f; // < 0: the build default (BDPT_SPLIT_BUDGET_ALPHA)
   const BvhRefClipper* clipper = nullptr;  // applied to the pieces of triangles flagged kTriNonOpaque
-  uint32_t numVertices = 0;                // vertices `positions` holds (0: unknown; only a plugged-in reference maker asks)
-  BvhTreeBuilder treeBuilder = nullptr;    // null: the host code builds the binary tree
-  bool prioritiesInRefMaker = false;       // (with a refMaker) it also classifies, rates and assigns the split counts (BvhRefInput::splits = null)
-  BvhRefMaker refMaker = nullptr;          // (with a treeBuilder and a packer only) null: the host code makes the references
-  bool collapseInPacker = false;           // (with refMaker, treeBuilder and packer) the packer also does the four-wide collapse (in.wide = null) and fills the summary
-  BvhPacker packer = nullptr;              // (with a treeBuilder only) null: the host code quantises and packs; else Bvh::deviceRecs is the result
-  void* treeBuilderUser = nullptr;
-  std::string* error = nullptr;            // receives the tree builder's message when it fails (the build then has no nodes)
+  uint32_t numVertices = 0;                // vertices `positions` holds (0: unknown; only a backend's reference maker asks)
+  const BvhBackend* backend = nullptr;     // null: the default backend (bvhSetDefaultBackend; all host code unless a test set one)
+  std::string* error = nullptr;            // receives the message when a backend's stage fails or the backend's shape is illegal (the build is empty then)
 };
 
 // positions: 3 floats per vertex; indices: 3 per triangle; triFlags: per triangle (may be null).

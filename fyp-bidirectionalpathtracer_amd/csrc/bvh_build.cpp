@@ -15,7 +15,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <future>
 #include <chrono>
 #include <mutex>
 #include <thread>
@@ -380,14 +379,491 @@ struct RefOut {
   }
 };
 
+
+// ------------------------------------------------------------------------------------------------
+// The stages of buildBvh, in the order it runs them.
+// ------------------------------------------------------------------------------------------------
+struct Laps {  // BDPT_BUILD_VERBOSE: what every stage took
+  const bool verbose = std::getenv("BDPT_BUILD_VERBOSE") != nullptr;
+  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+  void lap(const char* what) {
+    if (!verbose) return;
+    const auto t = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[bvh] %-12s %.3f s\n", what, std::chrono::duration<double>(t - last).count());
+    last = t;
+  }
+};
+
+// Triangle records exactly as the device intersects them — the "actual" triangle is (v0, v0+e1, v0+e2) in fp32, so
+// bounds are taken from those points — and what derives from the scene's box.
+struct Triangles {
+  BigVec<BvhTri> recs;  // (both empty when the backend makes them where it works: `keep` = false)
+  BigVec<Box> box;
+  BvhSplitGrid grid;  // the scene box: the split planes are its spatial medians
+  float pad;          // what every box is padded by
+};
+void makeTriangles(const float* positions, const uint32_t* indices, uint32_t nTris, const uint32_t* triFlags, const uint32_t* triAux, bool keep, int threads,
+                   Triangles& T) {
+  T.recs.resize(keep ? nTris : 0);  // (every field of every record is written by the loop below)
+  T.box.resize(keep ? nTris : 0);
+  Box scene;
+  scene.reset();
+  std::vector<Box> part((size_t)threads);
+  for (Box& b : part) b.reset();
+  parallelFor(nTris, threads, [&](size_t t0, size_t t1, int th) {
+    Box acc;
+    acc.reset();
+    for (size_t t = t0; t < t1; t++) {
+      const float* a = positions + (size_t)indices[t * 3] * 3;
+      const float* b = positions + (size_t)indices[t * 3 + 1] * 3;
+      const float* c = positions + (size_t)indices[t * 3 + 2] * 3;
+      BvhTri r;
+      Box bx;
+      bvhTriGeom(a, b, c, r.v0, r.e1, r.e2, bx.lo, bx.hi);
+      r.prim = (uint32_t)t;
+      r.flags = triFlags ? triFlags[t] : 0u;
+      r.aux = triAux ? triAux[t] : 0u;
+      if (keep) {
+        T.recs[t] = r;
+        T.box[t] = bx;
+      }
+      acc.grow(bx);
+    }
+    part[(size_t)th].grow(acc);
+  });
+  for (const Box& b : part) scene.grow(b);
+  float diag = 0.0f;
+  if (nTris) {
+    float dx = scene.hi[0] - scene.lo[0], dy = scene.hi[1] - scene.lo[1], dz = scene.hi[2] - scene.lo[2];
+    diag = std::sqrt(dx * dx + dy * dy + dz * dz);
+  }
+  // Slab tests run in fp32 on boxes that must never reject a hit the triangle test accepts:
+  // pad every box by a small fraction of the scene diagonal (covers rounding in both tests).
+  T.pad = 2e-5f * diag + 1e-30f;
+  for (int a = 0; a < 3; a++) {
+    T.grid.lo[a] = nTris ? (double)scene.lo[a] : 0.0;
+    T.grid.ext[a] = nTris ? (double)scene.hi[a] - (double)scene.lo[a] : 0.0;
+  }
+}
+
+struct Budgets {
+  float opaque, alpha;  // extra references per triangle of the class, on average
+  float outlierArea;    // opaque triangles below this box area are never split
+};
+float outlierAreaOf(const Triangles& T, uint32_t nTris, float budgetOpaque) {
+  if (!(budgetOpaque > 0.0f) || !nTris) return 0.0f;
+  std::vector<float> areas;
+  areas.reserve(nTris);
+  for (uint32_t t = 0; t < nTris; t++)
+    if (!(T.recs[t].flags & kTriNonOpaque)) areas.push_back(bvhBoxArea(T.box[t].lo, T.box[t].hi));  // (the area bvhRefDecide compares against it)
+  if (areas.empty()) return 0.0f;
+  std::nth_element(areas.begin(), areas.begin() + areas.size() / 2, areas.end());
+  return (float)BDPT_SPLIT_OUTLIER * areas[areas.size() / 2];
+}
+
+// The reference decision (see "References" above): what the clipper leaves of every non-opaque triangle, every triangle's
+// priority, and from those the split counts per class.
+struct RefDecision {
+  BigVec<uint8_t> state;  // 0 = plain reference (the triangle's box), 1 = shrunk by the clipper, 2 = dropped
+  BigVec<uint32_t> splits;
+  uint32_t dropped = 0;
+};
+constexpr size_t kRefChunk = 8192;
+void decideReferences(const Triangles& T, uint32_t nTris, const BvhRefClipper* clipper, const Budgets& budgets, int threads, RefDecision& D) {
+  const BigVec<BvhTri>& recs = T.recs;
+  // (sized without being touched, filled side by side: 130 MB of one-thread value-initialisation at 10 M triangles otherwise)
+  BigVec<double> prio(nTris);
+  BigVec<float> capOf(nTris);  // splits a triangle may get at most
+  BigVec<uint8_t>& state = D.state;
+  BigVec<uint32_t>& splits = D.splits;
+  state.resize(nTris);
+  splits.resize(nTris);
+  // pass 1: what the clipper leaves of every non-opaque triangle, and every triangle's priority
+  parallelChunks(nTris, threads, kRefChunk, [&](size_t, size_t t0, size_t t1) {
+    for (size_t t = t0; t < t1; t++) {
+      auto clip = [&](double (*poly)[2], int& n) { return clipper->clip((uint32_t)t, poly, n); };
+      bvhRefDecide(T.grid, recs[t], T.box[t].lo, T.box[t].hi, clipper != nullptr, clip, budgets.opaque, budgets.alpha, budgets.outlierArea, state[t], prio[t],
+                   capOf[t]);
+      splits[t] = 0;
+    }
+  });
+  // split counts per class: the largest D with sum floor(D p_t) <= budget (integer sums: thread-count independent)
+  for (int cls = 0; cls < 2 && nTris; cls++) {
+    const float budgetF = cls ? budgets.alpha : budgets.opaque;
+    if (!(budgetF > 0.0f)) continue;
+    auto member = [&](size_t t) { return state[t] != 2 && (((recs[t].flags & kTriNonOpaque) != 0) == (cls == 1)); };
+    uint64_t members = 0;
+    double pmax = 0.0;
+    {  // (a count and a maximum: what the threads find does not depend on how the range was shared out)
+      std::vector<uint64_t> pm((size_t)threads, 0);
+      std::vector<double> px((size_t)threads, 0.0);
+      parallelFor(nTris, threads, [&](size_t t0, size_t t1, int th) {
+        uint64_t m = 0;
+        double x = 0.0;
+        for (size_t t = t0; t < t1; t++)
+          if (member(t)) {
+            m++;
+            x = std::max(x, prio[t]);
+          }
+        pm[(size_t)th] = m;
+        px[(size_t)th] = x;
+      });
+      for (int th = 0; th < threads; th++) {
+        members += pm[(size_t)th];
+        pmax = std::max(pmax, px[(size_t)th]);
+      }
+    }
+    const uint64_t budget = (uint64_t)((double)members * (double)budgetF);
+    if (!members || !budget || !(pmax > 0.0)) continue;
+    auto total = [&](double scale) {
+      std::vector<uint64_t> part((size_t)threads, 0);
+      parallelFor(nTris, threads, [&](size_t t0, size_t t1, int th) {
+        uint64_t acc = 0;
+        for (size_t t = t0; t < t1; t++)
+          if (member(t)) acc += (uint64_t)std::min<double>(std::floor(scale * prio[t]), (double)capOf[t]);
+        part[(size_t)th] = acc;
+      });
+      uint64_t s = 0;
+      for (uint64_t v : part) s += v;
+      return s;
+    };
+    const double scale = bvhSplitScale(pmax, budget, total);
+    parallelFor(nTris, threads, [&](size_t t0, size_t t1, int) {
+      for (size_t t = t0; t < t1; t++)
+        if (member(t)) splits[t] = (uint32_t)std::min<double>(std::floor(scale * prio[t]), (double)capOf[t]);
+    });
+  }
+  D.dropped = 0;
+  for (uint32_t t = 0; t < nTris; t++) D.dropped += state[t] == 2 ? 1u : 0u;
+}
+
+// pass 2: the references, triangle order (chunks are contiguous triangle ranges, appended in order), as the 40-byte
+// records the tree is built over (box, centre, reference index) + the triangle every reference belongs to
+void makeReferences(const Triangles& T, uint32_t nTris, const BvhRefClipper* clipper, const RefDecision& D, int threads, BigVec<Ref>& refs,
+                    BigVec<uint32_t>& refTri) {
+  const BigVec<BvhTri>& recs = T.recs;
+  const BigVec<Box>& triBox = T.box;
+  std::vector<RefOut> part((nTris + kRefChunk - 1) / kRefChunk);  // one per chunk, appended in chunk order below
+  parallelChunks(nTris, threads, kRefChunk, [&](size_t ci, size_t t0, size_t t1) {
+    RefOut& o = part[ci];
+    BigVec<BvhPiece> stack;  // the chunk's split stack: sized to a triangle's split count before it is split
+    for (size_t t = t0; t < t1; t++) {
+      const uint32_t splits = D.splits[t];
+      if (D.state[t] == 2) continue;
+      if (splits == 0 && D.state[t] == 0) {
+        o.push(triBox[t].lo, triBox[t].hi, (uint32_t)t);
+        continue;
+      }
+      // (the whole piece is recomputed here instead of kept since pass 1: a piece is ~400 bytes and a scene may hold millions)
+      const bool alpha = (recs[t].flags & kTriNonOpaque) != 0 && clipper != nullptr;
+      auto clip = [&](double (*poly)[2], int& n) { return clipper->clip((uint32_t)t, poly, n); };
+      auto emit = [&](const BvhPiece& p) { o.push(p.lo, p.hi, (uint32_t)t); };
+      BvhPiece pc;
+      bool shrunk = false;
+      if (!bvhWholePiece(recs[t], triBox[t].lo, triBox[t].hi, alpha, clip, pc, shrunk)) continue;  // (cannot happen: pass 1 kept it)
+      if (splits == 0) {
+        emit(pc);
+        continue;
+      }
+      pc.splits = splits;
+      if (stack.size() < splits) stack.resize(splits);
+      bvhSplitTriangle(T.grid, recs[t], pc, alpha, stack.data(), clip, emit);
+    }
+  });
+  std::vector<size_t> at(part.size() + 1, 0);
+  for (size_t ci = 0; ci < part.size(); ci++) at[ci + 1] = at[ci] + part[ci].tri.size();
+  refs.resize(at.back());
+  refTri.resize(at.back());
+  parallelChunks(part.size(), threads, 16, [&](size_t, size_t c0, size_t c1) {  // every chunk knows where it lands
+    for (size_t ci = c0; ci < c1; ci++) {
+      const RefOut& o = part[ci];
+      for (size_t j = 0; j < o.tri.size(); j++) {
+        Ref& r = refs[at[ci] + j];
+        for (int k = 0; k < 3; k++) {  // (+ 0.0f: -0 becomes +0, so that no minimum or maximum depends on the order in which equal zeros meet)
+          r.box.lo[k] = o.boxes[j].lo[k] + 0.0f;
+          r.box.hi[k] = o.boxes[j].hi[k] + 0.0f;
+          r.cent[k] = 0.5f * (r.box.lo[k] + r.box.hi[k]) + 0.0f;
+        }
+        r.id = (uint32_t)(at[ci] + j);
+        refTri[at[ci] + j] = o.tri[j];
+      }
+      RefOut().boxes.swap(part[ci].boxes);  // (release as we go: the pieces are as large as the result)
+      RefOut().tri.swap(part[ci].tri);
+    }
+  });
+}
+
+// The binary tree over refs[0, n), which it permutes into the leaf order.  Few references or one thread: one depth-first
+// pass.  Else phase 1: one thread splits the top of the tree (large nodes share their scans among all threads) and defers
+// every subtree of at most `grain` references.  Phase 2: the deferred subtrees are built concurrently, largest first,
+// each into its own node list.  Phase 3: the lists are appended; children stay after parents.
+void buildBinaryTree(BigVec<Ref>& refs, uint32_t n, int threads, Laps& laps, BigVec<TmpNode>& tmp) {
+  BigVec<Ref> scratch(n);  // every partition scatters through the node's own range of it
+  const BuildData B{refs, scratch};
+  tmp.reserve((size_t)n / 2 + 16);
+  tmp.push_back(makeTmpNode(0, n, 0));
+  if (threads <= 1 || n < (1u << 15)) {
+    buildSubtree(B, tmp, 0, 0, 1, nullptr);
+    return;
+  }
+  const uint32_t grain = std::max<uint32_t>(4096, n / (uint32_t)(threads * 8));
+  std::vector<uint32_t> deferred;
+  buildSubtree(B, tmp, 0, grain, threads, &deferred);
+  laps.lap("top");
+  std::sort(deferred.begin(), deferred.end(), [&](uint32_t a, uint32_t b) {
+    return tmp[a].count > tmp[b].count || (tmp[a].count == tmp[b].count && a < b);
+  });
+  std::vector<BigVec<TmpNode>> local(deferred.size());
+  parallelChunks(deferred.size(), threads, 1, [&](size_t j, size_t, size_t) {
+    BigVec<TmpNode>& L = local[j];
+    L.reserve((size_t)tmp[deferred[j]].count / 2 + 4);
+    L.push_back(tmp[deferred[j]]);
+    buildSubtree(B, L, 0, 0, 1, nullptr);
+  });
+  laps.lap("subtrees");
+  // the lists are appended in the order of `deferred` (children stay after parents); every list knows where it
+  // lands, so the copies run side by side
+  std::vector<size_t> at(deferred.size() + 1);
+  at[0] = tmp.size();
+  for (size_t j = 0; j < deferred.size(); j++) at[j + 1] = at[j] + local[j].size() - 1;
+  tmp.resize(at.back());
+  parallelChunks(deferred.size(), threads, 1, [&](size_t j, size_t, size_t) {
+    const BigVec<TmpNode>& L = local[j];
+    const int32_t off = (int32_t)at[j] - 1;  // local index i >= 1 -> off + i
+    TmpNode rootNode = L[0];
+    if (rootNode.left >= 0) {
+      rootNode.left += off;
+      rootNode.right += off;
+    }
+    tmp[deferred[j]] = rootNode;
+    for (size_t i = 1; i < L.size(); i++) {
+      TmpNode nd = L[i];
+      if (nd.left >= 0) {
+        nd.left += off;
+        nd.right += off;
+      }
+      tmp[at[j] + i - 1] = nd;
+    }
+  });
+}
+
+// Leaf-ordered triangle list and reference boxes; `order` (a backend's tree builder left `refs` as they were): the
+// reference at every position, null: `refs` are in leaf order themselves.
+void gatherLeaves(const BigVec<Ref>& refs, const uint32_t* order, const BigVec<uint32_t>& refTri, const BigVec<BvhTri>& recs, int threads, Bvh& out) {
+  const size_t n = refs.size();
+  out.tris.resize(n);
+  out.refBox.resize(n * 6);
+  parallelFor(n, threads, [&](size_t a, size_t b, int) {
+    for (size_t i = a; i < b; i++) {
+      const Ref& r = order ? refs[order[i]] : refs[i];
+      out.tris[i] = recs[refTri[r.id]];
+      for (int k = 0; k < 3; k++) {
+        out.refBox[i * 6 + (size_t)k] = r.box.lo[k];
+        out.refBox[i * 6 + 3 + (size_t)k] = r.box.hi[k];
+      }
+    }
+  });
+}
+
+// ---- the binary tree collapsed into four-wide nodes ----
+using Wide = BvhWideNode;  // (src: tmp index of the subtree root this node covers; kids: tmp indices of the up to 4 children)
+struct WideTree {
+  std::vector<Wide> wide;
+  std::vector<BvhSlot> slots;  // per wide node: where its index must be written
+  uint32_t depth = 0, stack = 0;
+};
+struct Collapser {
+  struct Job {
+    uint32_t src, depth, stackAbove;
+    int32_t slotNode, slotIdx;
+  };
+  const BigVec<TmpNode>& tmp;
+  // Binary height of every subtree: the stack need of a subtree left two-wide is its height, so a
+  // node at stack level u may widen to k children only while u + (k-1) + max child height stays
+  // within the device stack.  Shallow subtrees (most of the nodes) become four-wide; only the few
+  // deep, skinny paths of a SAH tree keep two-wide nodes.
+  std::vector<uint16_t> height;
+  std::vector<uint32_t> subtreeNodes;  // binary nodes in the subtree (itself included)
+  explicit Collapser(const BigVec<TmpNode>& t) : tmp(t), height(t.size(), 0), subtreeNodes(t.size(), 1) {
+    for (size_t i = tmp.size(); i-- > 0;)  // children are always created after their parent
+      if (tmp[i].left >= 0) {
+        height[i] = (uint16_t)(1 + std::max(height[(size_t)tmp[i].left], height[(size_t)tmp[i].right]));
+        subtreeNodes[i] = 1 + subtreeNodes[(size_t)tmp[i].left] + subtreeNodes[(size_t)tmp[i].right];
+      }
+  }
+  // One subtree, depth first, appended to W; `defer` (may be null) receives the jobs of subtrees of at most
+  // kCollapseGrain binary nodes instead of descending into them.
+  void run(Job rootJob, WideTree& W, std::vector<Job>* defer) const {
+    std::vector<Job> jobs;
+    jobs.push_back(rootJob);
+    while (!jobs.empty()) {
+      Job j = jobs.back();
+      jobs.pop_back();
+      Wide w;
+      w.src = j.src;
+      w.depth = j.depth;
+      w.nk = 0;
+      if (tmp[j.src].left < 0) {  // root is a single leaf
+        w.kids[w.nk++] = j.src;
+      } else {
+        w.kids[w.nk++] = (uint32_t)tmp[j.src].left;
+        w.kids[w.nk++] = (uint32_t)tmp[j.src].right;
+        while (w.nk < 4) {
+          int best = -1;
+          float bestArea = -1.0f;
+          for (int k = 0; k < w.nk; k++)
+            if (tmp[w.kids[k]].left >= 0) {
+              float ar = tmp[w.kids[k]].box.area();
+              if (ar > bestArea) {
+                bestArea = ar;
+                best = k;
+              }
+            }
+          if (best < 0) break;
+          // stack need if we widen: j.stackAbove + nk (= (nk+1)-1) + tallest remaining child
+          const uint32_t t = w.kids[best];
+          uint32_t tallest = std::max<uint32_t>(height[(size_t)tmp[t].left], height[(size_t)tmp[t].right]);
+          for (int k = 0; k < w.nk; k++)
+            if (k != best) tallest = std::max<uint32_t>(tallest, height[w.kids[k]]);
+          if (j.stackAbove + (uint32_t)w.nk + tallest > (uint32_t)kBvhMaxStack) break;
+          w.kids[best] = (uint32_t)tmp[t].left;
+          w.kids[w.nk++] = (uint32_t)tmp[t].right;
+        }
+      }
+      const uint32_t self = (uint32_t)W.wide.size();
+      W.wide.push_back(w);
+      W.slots.push_back(BvhSlot{j.slotNode, j.slotIdx});
+      W.depth = std::max(W.depth, j.depth);
+      const uint32_t need = j.stackAbove + (uint32_t)(w.nk - 1);
+      W.stack = std::max(W.stack, need);
+      for (int k = w.nk - 1; k >= 0; k--)
+        if (tmp[w.kids[k]].left >= 0) {
+          const Job child{w.kids[k], j.depth + 1, need, (int32_t)self, k};
+          if (defer && subtreeNodes[w.kids[k]] <= kCollapseGrain)
+            defer->push_back(child);
+          else
+            jobs.push_back(child);
+        }
+    }
+  }
+};
+// The top of the tree by one thread; the subtrees below kCollapseGrain nodes side by side, each into its own list,
+// appended in the order they were met.  The grain is a constant, so the node order does not depend on the thread count.
+void collapseTree(const BigVec<TmpNode>& tmp, int threads, WideTree& W) {
+  using Job = Collapser::Job;
+  const Collapser C(tmp);
+  std::vector<Job> deferred;
+  C.run(Job{0, 0, 0, -1, -1}, W, tmp.size() > 4 * (size_t)kCollapseGrain ? &deferred : nullptr);
+  if (deferred.empty()) return;
+  std::vector<WideTree> local(deferred.size());
+  parallelChunks(deferred.size(), threads, 1, [&](size_t j, size_t, size_t) {
+    WideTree& L = local[j];
+    L.wide.reserve(C.subtreeNodes[deferred[j].src] / 2 + 4);
+    L.slots.reserve(C.subtreeNodes[deferred[j].src] / 2 + 4);
+    C.run(deferred[j], L, nullptr);  // (slots[0], a node of the top part, is a global index already)
+  });
+  std::vector<size_t> at(deferred.size() + 1);
+  at[0] = W.wide.size();
+  for (size_t j = 0; j < deferred.size(); j++) at[j + 1] = at[j] + local[j].wide.size();
+  W.wide.resize(at.back());
+  W.slots.resize(at.back());
+  parallelChunks(deferred.size(), threads, 1, [&](size_t j, size_t, size_t) {
+    const WideTree& L = local[j];
+    std::copy(L.wide.begin(), L.wide.end(), W.wide.begin() + (long)at[j]);
+    W.slots[at[j]] = L.slots[0];
+    for (size_t i = 1; i < L.slots.size(); i++) W.slots[at[j] + i] = BvhSlot{L.slots[i].node + (int32_t)at[j], L.slots[i].idx};
+  });
+  for (const WideTree& L : local) {
+    W.depth = std::max(W.depth, L.depth);
+    W.stack = std::max(W.stack, L.stack);
+  }
+}
+
+// The SAH cost: blocks of kCostBlock nodes summed in node order side by side, the block sums added in block order — the
+// rounding depends on neither the thread count nor on who builds the tree.
+float sahCost(const BigVec<TmpNode>& tmp, const std::vector<Wide>& wide, int threads) {
+  const float rootArea = tmp[0].box.area();
+  constexpr size_t kCostBlock = (size_t)1 << 16;
+  std::vector<double> part((wide.size() + kCostBlock - 1) / kCostBlock, 0.0);
+  if (rootArea > 0)
+    parallelChunks(wide.size(), threads, kCostBlock, [&](size_t ci, size_t w0, size_t w1) {
+      double cost = 0.0;
+      for (size_t wi = w0; wi < w1; wi++)
+        for (int k = 0; k < wide[wi].nk; k++) {
+          const TmpNode& c = tmp[wide[wi].kids[k]];
+          cost += (c.left < 0 ? kCostTri * c.count : kCostTraverse) * c.box.area() / rootArea;
+        }
+      part[ci] = cost;
+    });
+  double cost = 0.0;
+  for (double v : part) cost += v;
+  return (float)cost + kCostTraverse;
+}
+
+// Child boxes padded, then quantised (bvh.h bvhQuantiseNode: the device build and the refits run the same code).
+void quantiseNodes(const BigVec<TmpNode>& tmp, const WideTree& W, float pad, int threads, BigVec<BvhNode>& nodes) {
+  nodes.resize(W.wide.size());
+  parallelFor(W.wide.size(), threads, [&](size_t w0, size_t w1, int) {
+    for (size_t wi = w0; wi < w1; wi++) {
+      const Wide& w = W.wide[wi];
+      BvhNode nd;
+      std::memset(&nd, 0, sizeof(nd));
+      float clo[4][3], chi[4][3];
+      for (int k = 0; k < w.nk; k++)
+        for (int a = 0; a < 3; a++) {
+          clo[k][a] = tmp[w.kids[k]].box.lo[a] - pad;
+          chi[k][a] = tmp[w.kids[k]].box.hi[a] + pad;
+        }
+      uint32_t q[10];
+      bvhQuantiseNode(clo, chi, w.nk, q);
+      std::memcpy(nd.origin, &q[0], 12);
+      for (int a = 0; a < 3; a++) {
+        const uint32_t sb = ((q[3] >> (8 * a)) & 0xffu) << 23;
+        std::memcpy(&nd.scale[a], &sb, 4);
+      }
+      std::memcpy(nd.lo, &q[4], 12);
+      std::memcpy(nd.hi, &q[7], 12);
+      for (int k = 0; k < 4; k++) nd.child[k] = -1;
+      for (int k = 0; k < w.nk; k++) {
+        const TmpNode& c = tmp[w.kids[k]];
+        if (c.left < 0) nd.child[k] = -1 - (int32_t)((c.first << 3) | (c.count - 1));  // leaf reference; interior ones are patched below
+      }
+      nodes[wi] = nd;
+    }
+  });
+  for (size_t wi = 1; wi < W.wide.size(); wi++) nodes[(size_t)W.slots[wi].node].child[W.slots[wi].idx] = (int32_t)wi;
+}
+
+// Nothing to build a tree over: one node without children.
+void emptyTree(Bvh& out) {
+  BvhNode nd;
+  std::memset(&nd, 0, sizeof(nd));
+  for (int a = 0; a < 3; a++)
+    for (int c = 0; c < 4; c++) {
+      nd.lo[a][c] = 255;
+      nd.hi[a][c] = 0;
+    }
+  for (int c = 0; c < 4; c++) nd.child[c] = -1;
+  nd.scale[0] = nd.scale[1] = nd.scale[2] = 1.0f;
+  out.nodes.push_back(nd);
+  out.numNodes = 1;
+  packBvh(out, 1);
+}
+
+float budgetOr(float asked, const char* env, float dflt) {
+  if (asked >= 0.0f) return asked;
+  if (const char* e = std::getenv(env)) {
+    const float v = (float)std::atof(e);
+    if (v >= 0.0f && v <= 64.0f) return v;
+  }
+  return dflt;
+}
+
+BvhBackend gDefaultBackend;
+
 }  // namespace
 
-static BvhTreeBuilder gDefaultTreeBuilder = nullptr;
-static void* gDefaultTreeBuilderUser = nullptr;
-void bvhSetDefaultTreeBuilder(BvhTreeBuilder f, void* user) {
-  gDefaultTreeBuilder = f;
-  gDefaultTreeBuilderUser = user;
-}
+void bvhSetDefaultBackend(const BvhBackend& b) { gDefaultBackend = b; }
 
 int bvhBuildThreads() {
   if (const char* e = std::getenv("BDPT_BUILD_THREADS")) {
@@ -416,191 +892,51 @@ void buildBvh(const float* positions, const uint32_t* indices, uint32_t n, const
 
 void buildBvh(const float* positions, const uint32_t* indices, uint32_t nTris, const uint32_t* triFlags, Bvh& out,
               const BvhBuildOptions& opt, const uint32_t* triAux) {
-  int threads = opt.threads;
-  if (threads <= 0) threads = bvhBuildThreads();
-  const bool verbose = std::getenv("BDPT_BUILD_VERBOSE") != nullptr;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto tStart = now();
-  auto lap = [&](const char* what) {
-    if (!verbose) return;
-    auto t = now();
-    std::fprintf(stderr, "[bvh] %-12s %.3f s\n", what, std::chrono::duration<double>(t - tStart).count());
-    tStart = t;
+  const int threads = opt.threads > 0 ? opt.threads : bvhBuildThreads();
+  Laps laps;
+  out = Bvh();
+  auto fail = [&](const std::string& err, const char* what) {
+    if (opt.error) *opt.error = err.empty() ? what : err;
   };
-  out.nodes.clear();
-  out.tris.clear();
-  out.refBox.clear();
-  out.maxDepth = 0;
-  out.sahCost = 0.0f;
-  out.numDropped = 0;
-  out.numNodes = 0;
-  out.numRefs = 0;
-  out.deviceRecs = nullptr;
-  out.deviceNumRecs = 0;
+  // where the stages run: all here, the binary tree alone on the backend, or references, tree and everything after it
+  const BvhBackend be = opt.backend ? *opt.backend : gDefaultBackend;
+  const bool whole = be.makeRefs && be.buildTree && be.pack;
+  if (!whole && (be.makeRefs || be.pack)) return fail("", "build backend: a reference maker and a packer need each other and a tree builder");
+  Budgets budgets;
+  budgets.opaque = budgetOr(opt.splitBudget, "BDPT_SPLIT_BUDGET", (float)BDPT_SPLIT_BUDGET);
+  budgets.alpha = budgetOr(opt.splitBudgetAlpha, "BDPT_SPLIT_BUDGET_ALPHA", (float)BDPT_SPLIT_BUDGET_ALPHA);
+  // the backend does all of the reference stage, pass 1 and the split counts included ...
+  const bool decideThere = whole && !be.hostPriorities;
+  // ... and then makes the triangle records and their boxes where it works, from positions + indices: this side only
+  // needs the scene's box, not 72 bytes per triangle written and page-faulted in (0.05-0.15 s of a 10 M-triangle bdpt_set_scene)
+  const bool recsThere = decideThere && !be.uploadTriRecs && opt.numVertices != 0 && !(budgets.opaque > 0.0f);
 
-  auto budgetDefault = [](const char* env, float dflt) {
-    if (const char* e = std::getenv(env)) {
-      const float v = (float)std::atof(e);
-      if (v >= 0.0f && v <= 64.0f) return v;
-    }
-    return dflt;
-  };
-  const float budgetOpaque = opt.splitBudget >= 0.0f ? opt.splitBudget : budgetDefault("BDPT_SPLIT_BUDGET", (float)BDPT_SPLIT_BUDGET);
-  const float budgetAlpha = opt.splitBudgetAlpha >= 0.0f ? opt.splitBudgetAlpha : budgetDefault("BDPT_SPLIT_BUDGET_ALPHA", (float)BDPT_SPLIT_BUDGET_ALPHA);
-  // (a plugged-in reference maker — bdpt_set_scene: the device — may do all of the reference stage, pass 1 and the split counts, itself)
-  const BvhRefMaker refMaker = (opt.treeBuilder && opt.packer) ? opt.refMaker : nullptr;
-  const bool decideElsewhere = refMaker && opt.prioritiesInRefMaker;
-  // ... and then makes the triangle records and their boxes where it works, from positions + indices (BvhRefInput), and
-  // the packer of the same pipeline reads them there: this side only needs the scene's box, not 72 bytes per triangle
-  // written and page-faulted in (0.05-0.15 s of a 10 M-triangle bdpt_set_scene).
-  const bool recsElsewhere = decideElsewhere && opt.collapseInPacker && opt.numVertices != 0 && !(budgetOpaque > 0.0f) &&
-                             std::getenv("BDPT_UPLOAD_TRI_RECS") == nullptr;
+  Triangles T;
+  makeTriangles(positions, indices, nTris, triFlags, triAux, !recsThere, threads, T);
+  budgets.outlierArea = outlierAreaOf(T, nTris, budgets.opaque);
+  RefDecision D;
+  if (!decideThere) decideReferences(T, nTris, opt.clipper, budgets, threads, D);
+  laps.lap("priorities");
 
-  // Triangle records exactly as the device intersects them: the "actual" triangle is
-  // (v0, v0+e1, v0+e2) in fp32, so bounds are taken from those points.
-  BigVec<BvhTri> recs(recsElsewhere ? 0 : nTris);  // (every field of every record is written by the loop below)
-  BigVec<Box> triBox(recsElsewhere ? 0 : nTris);
-  Box scene;
-  scene.reset();
-  {
-    std::vector<Box> part((size_t)threads);
-    for (Box& b : part) b.reset();
-    parallelFor(nTris, threads, [&](size_t t0, size_t t1, int th) {
-      Box acc;
-      acc.reset();
-      for (size_t t = t0; t < t1; t++) {
-        const float* a = positions + (size_t)indices[t * 3] * 3;
-        const float* b = positions + (size_t)indices[t * 3 + 1] * 3;
-        const float* c = positions + (size_t)indices[t * 3 + 2] * 3;
-        BvhTri r;
-        Box bx;
-        bvhTriGeom(a, b, c, r.v0, r.e1, r.e2, bx.lo, bx.hi);
-        r.prim = (uint32_t)t;
-        r.flags = triFlags ? triFlags[t] : 0u;
-        r.aux = triAux ? triAux[t] : 0u;
-        if (!recsElsewhere) {
-          recs[t] = r;
-          triBox[t] = bx;
-        }
-        acc.grow(bx);
-      }
-      part[(size_t)th].grow(acc);
-    });
-    for (const Box& b : part) scene.grow(b);
-  }
-  float diag = 0.0f;
-  if (nTris) {
-    float dx = scene.hi[0] - scene.lo[0], dy = scene.hi[1] - scene.lo[1], dz = scene.hi[2] - scene.lo[2];
-    diag = std::sqrt(dx * dx + dy * dy + dz * dz);
-  }
-  // Slab tests run in fp32 on boxes that must never reject a hit the triangle test accepts:
-  // pad every box by a small fraction of the scene diagonal (covers rounding in both tests).
-  const float pad = 2e-5f * diag + 1e-30f;
-
-  // ---- references (see "References" above): the whole triangle, shrunk by the clipper where it is non-opaque,
-  // then split s_t times
-  BvhSplitGrid G;
-  for (int a = 0; a < 3; a++) {
-    G.lo[a] = nTris ? (double)scene.lo[a] : 0.0;
-    G.ext[a] = nTris ? (double)scene.hi[a] - (double)scene.lo[a] : 0.0;
-  }
-  float outlierArea = 0.0f;  // opaque triangles below this box area are never split
-  if (budgetOpaque > 0.0f && nTris) {
-    std::vector<float> areas;
-    areas.reserve(nTris);
-    for (uint32_t t = 0; t < nTris; t++)
-      if (!(recs[t].flags & kTriNonOpaque)) areas.push_back(bvhBoxArea(triBox[t].lo, triBox[t].hi));  // (the area bvhRefDecide compares against it)
-    if (!areas.empty()) {
-      std::nth_element(areas.begin(), areas.begin() + areas.size() / 2, areas.end());
-      outlierArea = (float)BDPT_SPLIT_OUTLIER * areas[areas.size() / 2];
-    }
-  }
-  const size_t nHere = decideElsewhere ? 0 : nTris;
-  // (sized without being touched, filled side by side: 130 MB of one-thread value-initialisation at 10 M triangles otherwise)
-  BigVec<double> prio(nHere);
-  BigVec<float> capOf(nHere);    // splits a triangle may get at most
-  BigVec<uint8_t> state(nHere);  // 0 = plain reference (triBox), 1 = shrunk by the clipper, 2 = dropped
-  BigVec<uint32_t> splits(nHere);
-  const bool anySplit = budgetOpaque > 0.0f || budgetAlpha > 0.0f;
-  // pass 1: what the clipper leaves of every non-opaque triangle, and every triangle's priority
-  constexpr size_t kRefChunk = 8192;
-  parallelChunks(nHere, threads, kRefChunk, [&](size_t, size_t t0, size_t t1) {
-    for (size_t t = t0; t < t1; t++) {
-      auto clip = [&](double (*poly)[2], int& n) { return opt.clipper->clip((uint32_t)t, poly, n); };
-      bvhRefDecide(G, recs[t], triBox[t].lo, triBox[t].hi, opt.clipper != nullptr, clip, budgetOpaque, budgetAlpha, outlierArea, state[t], prio[t], capOf[t]);
-      splits[t] = 0;
-    }
-  });
-  // split counts per class: the largest D with sum floor(D p_t) <= budget (integer sums: thread-count independent)
-  if (anySplit && nTris && !decideElsewhere) {
-    for (int cls = 0; cls < 2; cls++) {
-      const float budgetF = cls ? budgetAlpha : budgetOpaque;
-      if (!(budgetF > 0.0f)) continue;
-      uint64_t members = 0;
-      double pmax = 0.0;
-      {  // (a count and a maximum: what the threads find does not depend on how the range was shared out)
-        std::vector<uint64_t> pm((size_t)threads, 0);
-        std::vector<double> px((size_t)threads, 0.0);
-        parallelFor(nTris, threads, [&](size_t t0, size_t t1, int th) {
-          uint64_t m = 0;
-          double x = 0.0;
-          for (size_t t = t0; t < t1; t++)
-            if (state[t] != 2 && (((recs[t].flags & kTriNonOpaque) != 0) == (cls == 1))) {
-              m++;
-              x = std::max(x, prio[t]);
-            }
-          pm[(size_t)th] = m;
-          px[(size_t)th] = x;
-        });
-        for (int th = 0; th < threads; th++) {
-          members += pm[(size_t)th];
-          pmax = std::max(pmax, px[(size_t)th]);
-        }
-      }
-      const uint64_t budget = (uint64_t)((double)members * (double)budgetF);
-      if (!members || !budget || !(pmax > 0.0)) continue;
-      auto total = [&](double D) {
-        std::vector<uint64_t> part((size_t)threads, 0);
-        parallelFor(nTris, threads, [&](size_t t0, size_t t1, int th) {
-          uint64_t acc = 0;
-          for (size_t t = t0; t < t1; t++)
-            if (state[t] != 2 && (((recs[t].flags & kTriNonOpaque) != 0) == (cls == 1)))
-              acc += (uint64_t)std::min<double>(std::floor(D * prio[t]), (double)capOf[t]);
-          part[(size_t)th] = acc;
-        });
-        uint64_t s = 0;
-        for (uint64_t v : part) s += v;
-        return s;
-      };
-      const double D = bvhSplitScale(pmax, budget, total);
-      parallelFor(nTris, threads, [&](size_t t0, size_t t1, int) {
-        for (size_t t = t0; t < t1; t++)
-          if (state[t] != 2 && (((recs[t].flags & kTriNonOpaque) != 0) == (cls == 1)))
-            splits[t] = (uint32_t)std::min<double>(std::floor(D * prio[t]), (double)capOf[t]);
-      });
-    }
-  }
-  lap("priorities");
-  // pass 2: the references, triangle order (chunks are contiguous triangle ranges, appended in order), as the
-  // 40-byte records the tree is built over (box, centre, reference index) + the triangle every reference belongs to
-  BigVec<Ref> refs;
+  BigVec<Ref> refs;  // (stay empty when the backend makes them: it keeps them for its tree builder and its packer)
   BigVec<uint32_t> refTri;
-  // (a plugged-in reference maker — bdpt_set_scene: the device — makes the same references in the same order and keeps them)
-  uint32_t madeElsewhere = 0, droppedElsewhere = 0;
-  if (refMaker) {
-    BvhRefInput in;
-    in.triRecs = recsElsewhere ? nullptr : recs.data();
-    in.triBox = recsElsewhere ? nullptr : triBox.data();
-    in.splits = decideElsewhere ? nullptr : splits.data();
-    in.state = decideElsewhere ? nullptr : state.data();
-    in.budgetOpaque = budgetOpaque;
-    in.budgetAlpha = budgetAlpha;
-    in.outlierArea = outlierArea;
-    in.numDroppedOut = &droppedElsewhere;
+  uint32_t n = 0;  // references from here on
+  std::string err;
+  if (whole) {
+    BvhRefInput in{};
+    in.triRecs = recsThere ? nullptr : T.recs.data();
+    in.triBox = recsThere ? nullptr : T.box.data();
+    in.uploadTriRecs = be.uploadTriRecs || opt.numVertices == 0;
+    in.splits = decideThere ? nullptr : D.splits.data();
+    in.state = decideThere ? nullptr : D.state.data();
     in.numTris = nTris;
+    in.budgetOpaque = budgets.opaque;
+    in.budgetAlpha = budgets.alpha;
+    in.outlierArea = budgets.outlierArea;
+    in.numDroppedOut = decideThere ? &D.dropped : nullptr;
     for (int a = 0; a < 3; a++) {
-      in.gridLo[a] = G.lo[a];
-      in.gridExt[a] = G.ext[a];
+      in.gridLo[a] = T.grid.lo[a];
+      in.gridExt[a] = T.grid.ext[a];
     }
     in.clipper = opt.clipper;
     in.positions = positions;
@@ -608,402 +944,53 @@ void buildBvh(const float* positions, const uint32_t* indices, uint32_t nTris, c
     in.triFlags = triFlags;
     in.triAux = triAux;
     in.numVertices = opt.numVertices;
-    std::string err;
-    if (!refMaker(opt.treeBuilderUser, in, madeElsewhere, err)) {
-      if (opt.error) *opt.error = err.empty() ? "reference maker failed" : err;
-      return;
-    }
+    if (!be.makeRefs(be.user, in, n, err)) return fail(err, "reference maker failed");
   } else {
-    std::vector<RefOut> part((nTris + kRefChunk - 1) / kRefChunk);  // one per chunk, appended in chunk order below
-    parallelChunks(nTris, threads, kRefChunk, [&](size_t ci, size_t t0, size_t t1) {
-      RefOut& o = part[ci];
-      BigVec<BvhPiece> stack;  // the chunk's split stack: sized to a triangle's split count before it is split
-      for (size_t t = t0; t < t1; t++) {
-        if (state[t] == 2) continue;
-        if (splits[t] == 0 && state[t] == 0) {
-          o.push(triBox[t].lo, triBox[t].hi, (uint32_t)t);
-          continue;
-        }
-        // (the whole piece is recomputed here instead of kept since pass 1: a piece is ~400 bytes and a scene may hold millions)
-        const bool alpha = (recs[t].flags & kTriNonOpaque) != 0 && opt.clipper != nullptr;
-        auto clip = [&](double (*poly)[2], int& n) { return opt.clipper->clip((uint32_t)t, poly, n); };
-        auto emit = [&](const BvhPiece& p) { o.push(p.lo, p.hi, (uint32_t)t); };
-        BvhPiece pc;
-        bool shrunk = false;
-        if (!bvhWholePiece(recs[t], triBox[t].lo, triBox[t].hi, alpha, clip, pc, shrunk)) continue;  // (cannot happen: pass 1 kept it)
-        if (splits[t] == 0) {
-          emit(pc);
-          continue;
-        }
-        pc.splits = splits[t];
-        if (stack.size() < splits[t]) stack.resize(splits[t]);
-        bvhSplitTriangle(G, recs[t], pc, alpha, stack.data(), clip, emit);
-      }
-    });
-    std::vector<size_t> at(part.size() + 1, 0);
-    for (size_t ci = 0; ci < part.size(); ci++) at[ci + 1] = at[ci] + part[ci].tri.size();
-    refs.resize(at.back());
-    refTri.resize(at.back());
-    parallelChunks(part.size(), threads, 16, [&](size_t, size_t c0, size_t c1) {  // every chunk knows where it lands
-      for (size_t ci = c0; ci < c1; ci++) {
-        const RefOut& o = part[ci];
-        for (size_t j = 0; j < o.tri.size(); j++) {
-          Ref& r = refs[at[ci] + j];
-          for (int k = 0; k < 3; k++) {  // (+ 0.0f: -0 becomes +0, so that no minimum or maximum depends on the order in which equal zeros meet)
-            r.box.lo[k] = o.boxes[j].lo[k] + 0.0f;
-            r.box.hi[k] = o.boxes[j].hi[k] + 0.0f;
-            r.cent[k] = 0.5f * (r.box.lo[k] + r.box.hi[k]) + 0.0f;
-          }
-          r.id = (uint32_t)(at[ci] + j);
-          refTri[at[ci] + j] = o.tri[j];
-        }
-        RefOut().boxes.swap(part[ci].boxes);  // (release as we go: the pieces are as large as the result)
-        RefOut().tri.swap(part[ci].tri);
-      }
-    });
+    makeReferences(T, nTris, opt.clipper, D, threads, refs, refTri);
+    n = (uint32_t)refs.size();
   }
-  if (decideElsewhere) {
-    out.numDropped = droppedElsewhere;
-  } else {
-    uint32_t dropped = 0;
-    for (uint32_t t = 0; t < nTris; t++) dropped += state[t] == 2 ? 1u : 0u;
-    out.numDropped = dropped;
-  }
-  const uint32_t n = refMaker ? madeElsewhere : (uint32_t)refs.size();  // references from here on
-  if (verbose) std::fprintf(stderr, "[bvh] %u triangles -> %u references (%u dropped)\n", nTris, n, out.numDropped);
-  BigVec<TmpNode> tmp;
-  BigVec<uint32_t> order;  // filled by a plugged-in tree builder: the leaf order as reference ids (the host code permutes `refs` itself)
-  const BvhTreeBuilder treeBuilder = opt.treeBuilder ? opt.treeBuilder : gDefaultTreeBuilder;
-  void* const treeBuilderUser = opt.treeBuilder ? opt.treeBuilderUser : gDefaultTreeBuilderUser;
-  const bool plugged = treeBuilder && n > 0;
-  const BvhPacker packer = (plugged && opt.treeBuilder) ? opt.packer : nullptr;
-  BigVec<Ref> scratch(plugged ? 0 : n);  // every partition scatters through the node's own range of it
-  const BuildData B{refs, scratch};
-  lap("records");
-  if (plugged) {
-    // the binary tree is built elsewhere (bdpt_set_scene: on the device, bvh_device.hip) — the same decisions, the same
-    // order of the references, the same tree as the host code below; children come after their parents there too
-    std::string err;
-    if (!treeBuilder(treeBuilderUser, refMaker ? nullptr : refs.data(), n, order, tmp, err) || tmp.empty() || (!refMaker && order.size() != n)) {
-      if (opt.error) *opt.error = err.empty() ? "tree builder failed" : err;
-      out.nodes.clear();
-      out.tris.clear();
-      out.refBox.clear();
-      out.recs.clear();
-      return;
-    }
-    lap("device tree");
-  } else if (threads <= 1 || n < (1u << 15)) {
-    // The host code.  Phase 1: one thread splits the top of the tree (large nodes share their scans among all threads)
-    // and defers every subtree of at most `grain` triangles.  Phase 2: the deferred subtrees are built concurrently,
-    // largest first, each into its own node list.  Phase 3: the lists are appended; children stay after parents.
-    tmp.reserve((size_t)n / 2 + 16);
-    tmp.push_back(makeTmpNode(0, n, 0));
-    buildSubtree(B, tmp, 0, 0, 1, nullptr);
-  } else {
-    tmp.reserve((size_t)n / 2 + 16);
-    tmp.push_back(makeTmpNode(0, n, 0));
-    const uint32_t grain = std::max<uint32_t>(4096, n / (uint32_t)(threads * 8));
-    std::vector<uint32_t> deferred;
-    buildSubtree(B, tmp, 0, grain, threads, &deferred);
-    lap("top");
-    std::sort(deferred.begin(), deferred.end(), [&](uint32_t a, uint32_t b) {
-      return tmp[a].count > tmp[b].count || (tmp[a].count == tmp[b].count && a < b);
-    });
-    std::vector<BigVec<TmpNode>> local(deferred.size());
-    std::atomic<size_t> next{0};
-    auto worker = [&] {
-      for (;;) {
-        const size_t j = next.fetch_add(1);
-        if (j >= deferred.size()) return;
-        BigVec<TmpNode>& L = local[j];
-        L.reserve((size_t)tmp[deferred[j]].count / 2 + 4);
-        L.push_back(tmp[deferred[j]]);
-        buildSubtree(B, L, 0, 0, 1, nullptr);
-      }
-    };
-    {
-      WorkerScope pool;
-      for (int t = 1; t < threads; t++) pool.spawn(worker);
-      worker();
-      pool.join();
-    }
-    lap("subtrees");
-    // the lists are appended in the order of `deferred` (children stay after parents); every list knows where it
-    // lands, so the copies run side by side
-    std::vector<size_t> at(deferred.size() + 1);
-    at[0] = tmp.size();
-    for (size_t j = 0; j < deferred.size(); j++) at[j + 1] = at[j] + local[j].size() - 1;
-    tmp.resize(at.back());
-    parallelChunks(deferred.size(), threads, 1, [&](size_t j, size_t, size_t) {
-      const BigVec<TmpNode>& L = local[j];
-      const int32_t off = (int32_t)at[j] - 1;  // local index i >= 1 -> off + i
-      TmpNode rootNode = L[0];
-      if (rootNode.left >= 0) {
-        rootNode.left += off;
-        rootNode.right += off;
-      }
-      tmp[deferred[j]] = rootNode;
-      for (size_t i = 1; i < L.size(); i++) {
-        TmpNode nd = L[i];
-        if (nd.left >= 0) {
-          nd.left += off;
-          nd.right += off;
-        }
-        tmp[at[j] + i - 1] = nd;
-      }
-    });
-  }
-
-  lap("append");
+  out.numDropped = D.dropped;
   out.numRefs = n;
-  if (packer && refMaker && opt.collapseInPacker) {
-    // everything from here on — collapse, quantisation, packing, the summary — happens where the tree is (bvh_device.hip)
-    BvhPackInput in;
-    in.triRecs = recs.data();
-    in.numTris = nTris;
-    in.refTri = nullptr;
-    in.numRefs = n;
-    in.wide = nullptr;
-    in.slots = nullptr;
-    in.numWide = 0;
-    in.pad = pad;
-    std::string err;
-    if (!packer(treeBuilderUser, in, out, err)) {
-      if (opt.error) *opt.error = err.empty() ? "packer failed" : err;
-      out.deviceRecs = nullptr;
-      out.deviceNumRecs = 0;
-    }
-    lap("device collapse + pack");
-    return;
-  }
-  // Leaf-ordered triangle list (a packer gathers it on the device).
-  out.tris.resize(packer ? 0 : n);
-  out.refBox.resize(packer ? 0 : (size_t)n * 6);
-  if (!packer) parallelFor(n, threads, [&](size_t a, size_t b, int) {
-    for (size_t i = a; i < b; i++) {
-      const Ref& r = plugged ? refs[order[i]] : refs[i];
-      out.tris[i] = recs[refTri[r.id]];
-      for (int k = 0; k < 3; k++) {
-        out.refBox[i * 6 + (size_t)k] = r.box.lo[k];
-        out.refBox[i * 6 + 3 + (size_t)k] = r.box.hi[k];
-      }
-    }
-  });
+  if (laps.verbose) std::fprintf(stderr, "[bvh] %u triangles -> %u references (%u dropped)\n", nTris, n, out.numDropped);
+  laps.lap("records");
 
-  // ---- collapse the binary tree into four-wide nodes and quantise the child boxes ----------------
-  auto leafRef = [](uint32_t first, uint32_t count) -> int32_t { return -1 - (int32_t)((first << 3) | (count - 1)); };
-  using Wide = BvhWideNode;  // (src: tmp index of the subtree root this node covers; kids: tmp indices of the up to 4 children)
-  if (n == 0) {
-    BvhNode nd;
-    std::memset(&nd, 0, sizeof(nd));
-    for (int a = 0; a < 3; a++)
-      for (int c = 0; c < 4; c++) {
-        nd.lo[a][c] = 255;
-        nd.hi[a][c] = 0;
-      }
-    for (int c = 0; c < 4; c++) nd.child[c] = -1;
-    nd.scale[0] = nd.scale[1] = nd.scale[2] = 1.0f;
-    out.nodes.push_back(nd);
-    out.numNodes = 1;
-    packBvh(out, 1);
-    return;
+  // the binary tree: on the backend the same decisions, the same order of the references, the same tree as the host code
+  BigVec<TmpNode> tmp;
+  BigVec<uint32_t> order;  // filled by a backend's tree builder that was handed `refs`: the leaf order as reference ids (the host code permutes `refs` itself)
+  const bool treeThere = be.buildTree && n > 0;
+  if (treeThere) {
+    if (!be.buildTree(be.user, whole ? nullptr : refs.data(), n, order, tmp, err) || tmp.empty() || (!whole && order.size() != n))
+      return fail(err, "tree builder failed");
+    laps.lap("device tree");
+  } else {
+    buildBinaryTree(refs, n, threads, laps, tmp);
   }
-  // Binary height of every subtree: the stack need of a subtree left two-wide is its height, so a
-  // node at stack level u may widen to k children only while u + (k-1) + max child height stays
-  // within the device stack.  Shallow subtrees (most of the nodes) become four-wide; only the few
-  // deep, skinny paths of a SAH tree keep two-wide nodes.
-  std::vector<uint16_t> height(tmp.size(), 0);
-  std::vector<uint32_t> subtreeNodes(tmp.size(), 1);  // binary nodes in the subtree (itself included)
-  for (size_t t = tmp.size(); t-- > 0;)  // children are always created after their parent
-    if (tmp[t].left >= 0) {
-      height[t] = (uint16_t)(1 + std::max(height[(size_t)tmp[t].left], height[(size_t)tmp[t].right]));
-      subtreeNodes[t] = 1 + subtreeNodes[(size_t)tmp[t].left] + subtreeNodes[(size_t)tmp[t].right];
-    }
-  std::vector<Wide> wide;
-  std::vector<BvhSlot> slots;  // per wide node: where its index must be written
-  uint32_t wDepth = 0, wStack = 0;
-  {
-    struct Job {
-      uint32_t src, depth, stackAbove;
-      int32_t slotNode, slotIdx;
-    };
-    // One subtree, depth first, appended to (W, SL); `defer` (may be null) receives the jobs of subtrees of at most
-    // kCollapseGrain binary nodes instead of descending into them.
-    auto collapse = [&](Job rootJob, std::vector<Wide>& W, std::vector<BvhSlot>& SL, std::vector<Job>* defer, uint32_t& dMax,
-                        uint32_t& sMax) {
-      std::vector<Job> jobs;
-      jobs.push_back(rootJob);
-      while (!jobs.empty()) {
-        Job j = jobs.back();
-        jobs.pop_back();
-        Wide w;
-        w.src = j.src;
-        w.depth = j.depth;
-        w.nk = 0;
-        if (tmp[j.src].left < 0) {  // root is a single leaf
-          w.kids[w.nk++] = j.src;
-        } else {
-          w.kids[w.nk++] = (uint32_t)tmp[j.src].left;
-          w.kids[w.nk++] = (uint32_t)tmp[j.src].right;
-          while (w.nk < 4) {
-            int best = -1;
-            float bestArea = -1.0f;
-            for (int k = 0; k < w.nk; k++)
-              if (tmp[w.kids[k]].left >= 0) {
-                float ar = tmp[w.kids[k]].box.area();
-                if (ar > bestArea) {
-                  bestArea = ar;
-                  best = k;
-                }
-              }
-            if (best < 0) break;
-            // stack need if we widen: j.stackAbove + nk (= (nk+1)-1) + tallest remaining child
-            const uint32_t t = w.kids[best];
-            uint32_t tallest = std::max<uint32_t>(height[(size_t)tmp[t].left], height[(size_t)tmp[t].right]);
-            for (int k = 0; k < w.nk; k++)
-              if (k != best) tallest = std::max<uint32_t>(tallest, height[w.kids[k]]);
-            if (j.stackAbove + (uint32_t)w.nk + tallest > (uint32_t)kBvhMaxStack) break;
-            w.kids[best] = (uint32_t)tmp[t].left;
-            w.kids[w.nk++] = (uint32_t)tmp[t].right;
-          }
-        }
-        const uint32_t self = (uint32_t)W.size();
-        W.push_back(w);
-        SL.push_back(BvhSlot{j.slotNode, j.slotIdx});
-        dMax = std::max(dMax, j.depth);
-        const uint32_t need = j.stackAbove + (uint32_t)(w.nk - 1);
-        sMax = std::max(sMax, need);
-        for (int k = w.nk - 1; k >= 0; k--)
-          if (tmp[w.kids[k]].left >= 0) {
-            const Job child{w.kids[k], j.depth + 1, need, (int32_t)self, k};
-            if (defer && subtreeNodes[w.kids[k]] <= kCollapseGrain)
-              defer->push_back(child);
-            else
-              jobs.push_back(child);
-          }
-      }
-    };
-    // The top of the tree by one thread; the subtrees below kCollapseGrain nodes side by side, each into its own list,
-    // appended in the order they were met.  The grain is a constant, so the node order does not depend on the thread count.
-    std::vector<Job> deferred;
-    collapse(Job{0, 0, 0, -1, -1}, wide, slots, tmp.size() > 4 * (size_t)kCollapseGrain ? &deferred : nullptr, wDepth, wStack);
-    if (!deferred.empty()) {
-      struct Local {
-        std::vector<Wide> w;
-        std::vector<BvhSlot> sl;
-        uint32_t dMax = 0, sMax = 0;
-      };
-      std::vector<Local> local(deferred.size());
-      parallelChunks(deferred.size(), threads, 1, [&](size_t j, size_t, size_t) {
-        Local& L = local[j];
-        L.w.reserve(subtreeNodes[deferred[j].src] / 2 + 4);
-        L.sl.reserve(subtreeNodes[deferred[j].src] / 2 + 4);
-        Job r = deferred[j];
-        const int32_t parentNode = r.slotNode, parentIdx = r.slotIdx;
-        r.slotNode = -2;  // marks the list's root: its slot is a node of the top part
-        collapse(r, L.w, L.sl, nullptr, L.dMax, L.sMax);
-        L.sl[0] = BvhSlot{parentNode, parentIdx};
-      });
-      std::vector<size_t> at(deferred.size() + 1);
-      at[0] = wide.size();
-      for (size_t j = 0; j < deferred.size(); j++) at[j + 1] = at[j] + local[j].w.size();
-      wide.resize(at.back());
-      slots.resize(at.back());
-      parallelChunks(deferred.size(), threads, 1, [&](size_t j, size_t, size_t) {
-        const Local& L = local[j];
-        std::copy(L.w.begin(), L.w.end(), wide.begin() + (long)at[j]);
-        slots[at[j]] = L.sl[0];  // (a node of the top part: global index already)
-        for (size_t i = 1; i < L.sl.size(); i++) slots[at[j] + i] = BvhSlot{L.sl[i].node + (int32_t)at[j], L.sl[i].idx};
-      });
-      for (const Local& L : local) {
-        wDepth = std::max(wDepth, L.dMax);
-        wStack = std::max(wStack, L.sMax);
-      }
-    }
-  }
-  lap("collapse");
-  out.maxDepth = wDepth;
-  out.maxStack = wStack;
-  out.numNodes = (uint32_t)wide.size();
-  const float rootArea = tmp[0].box.area();
-  auto sahCost = [&] {
-    // blocks of kCostBlock nodes summed in node order side by side, the block sums added in block order: the rounding
-    // depends on neither the thread count nor on who builds the tree
-    constexpr size_t kCostBlock = (size_t)1 << 16;
-    std::vector<double> part((wide.size() + kCostBlock - 1) / kCostBlock, 0.0);
-    if (rootArea > 0)
-      parallelChunks(wide.size(), threads, kCostBlock, [&](size_t ci, size_t w0, size_t w1) {
-        double cost = 0.0;
-        for (size_t wi = w0; wi < w1; wi++)
-          for (int k = 0; k < wide[wi].nk; k++) {
-            const TmpNode& c = tmp[wide[wi].kids[k]];
-            cost += (c.left < 0 ? kCostTri * c.count : kCostTraverse) * c.box.area() / rootArea;
-          }
-        part[ci] = cost;
-      });
-    double cost = 0.0;
-    for (double v : part) cost += v;
-    return (float)cost + kCostTraverse;
-  };
-  if (packer) {
-    // quantisation and packing happen where the tree was built; the host keeps only the summary
-    BvhPackInput in;
-    in.triRecs = recs.data();
-    in.numTris = nTris;
-    in.refTri = refMaker ? nullptr : refTri.data();
-    in.numRefs = n;
-    in.wide = wide.data();
-    in.slots = slots.data();
-    in.numWide = wide.size();
-    in.pad = pad;
-    std::string err;
-    std::future<float> cost = std::async(std::launch::async, sahCost);  // (the host's one job meanwhile)
-    const bool ok = packer(treeBuilderUser, in, out, err);
-    out.sahCost = cost.get();
-    if (!ok) {
-      if (opt.error) *opt.error = err.empty() ? "packer failed" : err;
+  laps.lap("append");
+
+  if (whole && treeThere) {
+    // collapse, quantisation, packing, the summary: where the tree is
+    const BvhPackInput in{nTris, n, T.pad};
+    if (!be.pack(be.user, in, out, err)) {
+      fail(err, "packer failed");
       out.deviceRecs = nullptr;
       out.deviceNumRecs = 0;
     }
-    lap("device pack");
+    laps.lap("device collapse + pack");
     return;
   }
-  out.nodes.resize(wide.size());
-  parallelFor(wide.size(), threads, [&](size_t w0, size_t w1, int) {
-  for (size_t wi = w0; wi < w1; wi++) {
-    const Wide& w = wide[wi];
-    BvhNode nd;
-    std::memset(&nd, 0, sizeof(nd));
-    // child boxes padded, then quantised (bvh.h bvhQuantiseNode: the device build and the refits run the same code)
-    float clo[4][3], chi[4][3];
-    for (int k = 0; k < w.nk; k++)
-      for (int a = 0; a < 3; a++) {
-        clo[k][a] = tmp[w.kids[k]].box.lo[a] - pad;
-        chi[k][a] = tmp[w.kids[k]].box.hi[a] + pad;
-      }
-    uint32_t q[10];
-    bvhQuantiseNode(clo, chi, w.nk, q);
-    std::memcpy(nd.origin, &q[0], 12);
-    for (int a = 0; a < 3; a++) {
-      const uint32_t sb = ((q[3] >> (8 * a)) & 0xffu) << 23;
-      std::memcpy(&nd.scale[a], &sb, 4);
-    }
-    std::memcpy(nd.lo, &q[4], 12);
-    std::memcpy(nd.hi, &q[7], 12);
-    for (int k = 0; k < 4; k++) nd.child[k] = -1;
-    for (int k = 0; k < w.nk; k++) {
-      const TmpNode& c = tmp[w.kids[k]];
-      if (c.left < 0) nd.child[k] = leafRef(c.first, c.count);  // interior refs are patched below
-    }
-    out.nodes[wi] = nd;
-  }
-  });
-  for (size_t wi = 1; wi < wide.size(); wi++) out.nodes[(size_t)slots[wi].node].child[slots[wi].idx] = (int32_t)wi;
-  out.sahCost = sahCost();
-  lap("quantise");
+  if (n == 0) return emptyTree(out);
+  gatherLeaves(refs, treeThere ? order.data() : nullptr, refTri, T.recs, threads, out);
+  WideTree W;
+  collapseTree(tmp, threads, W);
+  laps.lap("collapse");
+  out.maxDepth = W.depth;
+  out.maxStack = W.stack;
+  out.numNodes = (uint32_t)W.wide.size();
+  quantiseNodes(tmp, W, T.pad, threads, out.nodes);
+  out.sahCost = sahCost(tmp, W.wide, threads);
+  laps.lap("quantise");
   if (!packBvh(out, threads)) out.recs.clear();  // (leaves of at most 8 triangles always fit: 3 x 8 < 256)
-  lap("pack");
+  laps.lap("pack");
 }
 
 bool packBvh(Bvh& bvh, int threads) {

@@ -9,7 +9,7 @@
 //   buildBinaryTreeOnDevice  the binned-SAH binary tree over them
 //   packOnDevice             the four-wide collapse (collapseOnDevice), child boxes quantised, nodes + leaf triangles packed
 //                            into the record array the kernels traverse
-// (the triangle records, before all of it, are made on the device too unless BDPT_UPLOAD_TRI_RECS hands the host's over).
+// (the triangle records, before all of it, are made on the device too unless BvhRefInput::uploadTriRecs hands the host's over).
 // The reference stage has no arithmetic of its own: both builders compile bvh_refs.h.  The tree stage is a different
 // algorithm for the same result:
 //
@@ -105,7 +105,6 @@ struct BvhDeviceBuild {
   uint32_t* refTri = nullptr;     // ... the triangle of each, and the triangle records (for the packer)
   BvhTri* triRecs = nullptr;
   uint32_t numTris = 0;
-  bool collapseHere = false;          // the four-wide collapse happens on the device too: the tree is not read back
   std::vector<uint32_t> levelStart;   // first node of every level of the binary tree, then numNodes (for the collapse)
   void releaseTree() {
     if (nodes) (void)hipFree(nodes);
@@ -126,10 +125,9 @@ struct BvhDeviceBuild {
     arena.release();
   }
 };
-BvhDeviceBuild* bvhDeviceBuildBegin(int device, bool collapseOnDevice) {
+BvhDeviceBuild* bvhDeviceBuildBegin(int device) {
   BvhDeviceBuild* b = new BvhDeviceBuild();
   b->device = device;
-  b->collapseHere = collapseOnDevice;
   return b;
 }
 void bvhDeviceBuildEnd(BvhDeviceBuild* b) {
@@ -1531,6 +1529,26 @@ bool uploadStagedImpl(void* dst, const void* src, size_t bytes, std::string& err
   return e == hipSuccess ? true : bad(e);
 }
 
+// What a stage of the device build reports with: its errors under its name, its BDPT_BUILD_VERBOSE laps.
+struct DeviceStage {
+  const char* name;
+  std::string& err;
+  const bool verbose = std::getenv("BDPT_BUILD_VERBOSE") != nullptr;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  bool ok(hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    err = std::string(name) + ": " + what + ": " + hipGetErrorString(e);
+    return false;
+  }
+  void lap(const char* what) {
+    if (!verbose) return;
+    (void)hipDeviceSynchronize();
+    const auto t1 = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[bvh]   device %-10s %.3f s\n", what, std::chrono::duration<double>(t1 - t0).count());
+    t0 = t1;
+  }
+};
+
 template <class T>
 bool devAllocT(BvhDeviceArena& pool, T** p, size_t count, std::string& err) {
   void* q = pool.alloc(count * sizeof(T));
@@ -1565,11 +1583,7 @@ bool allocLevel(BvhDeviceArena& pool, Level& L, size_t cap, std::string& err) {
 
 // The collapse of this build's tree (see the kernels above): wide nodes and slots in device memory, the summary to `out`.
 bool collapseOnDevice(BvhDeviceBuild* build, BvhDeviceArena& pool, BvhWideNode** dWideOut, BvhSlot** dSlotsOut, uint32_t* nWideOut, Bvh& out, std::string& err) {
-  auto ok = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    err = std::string("device collapse: ") + what + ": " + hipGetErrorString(e);
-    return false;
-  };
+  DeviceStage dev{"device collapse", err};
   hipStream_t st = nullptr;
   const dim3 blk(256);
   auto gridFor = [](size_t m) { return dim3((unsigned)((m + 255) / 256)); };
@@ -1602,10 +1616,10 @@ bool collapseOnDevice(BvhDeviceBuild* build, BvhDeviceArena& pool, BvhWideNode**
   {  // the root job
     const uint32_t zero = 0, top = WF_TOP;
     const int32_t minus = -1;
-    if (!ok(hipMemsetAsync(counters, 0, 8, st), "memset") || !ok(hipMemcpy(W.src, &zero, 4, hipMemcpyHostToDevice), "root") ||
-        !ok(hipMemcpy(W.depth, &zero, 4, hipMemcpyHostToDevice), "root") || !ok(hipMemcpy(W.above, &zero, 4, hipMemcpyHostToDevice), "root") ||
-        !ok(hipMemcpy(W.parent, &minus, 4, hipMemcpyHostToDevice), "root") || !ok(hipMemcpy(W.kIdx, &minus, 4, hipMemcpyHostToDevice), "root") ||
-        !ok(hipMemcpy(W.flags, &top, 4, hipMemcpyHostToDevice), "root"))
+    if (!dev.ok(hipMemsetAsync(counters, 0, 8, st), "memset") || !dev.ok(hipMemcpy(W.src, &zero, 4, hipMemcpyHostToDevice), "root") ||
+        !dev.ok(hipMemcpy(W.depth, &zero, 4, hipMemcpyHostToDevice), "root") || !dev.ok(hipMemcpy(W.above, &zero, 4, hipMemcpyHostToDevice), "root") ||
+        !dev.ok(hipMemcpy(W.parent, &minus, 4, hipMemcpyHostToDevice), "root") || !dev.ok(hipMemcpy(W.kIdx, &minus, 4, hipMemcpyHostToDevice), "root") ||
+        !dev.ok(hipMemcpy(W.flags, &top, 4, hipMemcpyHostToDevice), "root"))
       return false;
   }
   std::vector<uint32_t> wl{0, 1};  // breadth-first ranges of the wide levels: [wl[i], wl[i + 1])
@@ -1614,7 +1628,7 @@ bool collapseOnDevice(BvhDeviceBuild* build, BvhDeviceArena& pool, BvhWideNode**
     hipLaunchKernelGGL(k_wide_expand, gridFor(s1 - s0), blk, 0, st, W, s0, s1, nodes, hgt, counters, counters + 1);
     scan.run(W.nInterior + s0, s1 - s0, at, st);
     uint32_t nNext = 0;
-    if (!ok(hipMemcpy(&nNext, at + (s1 - s0), 4, hipMemcpyDeviceToHost), "level")) return false;
+    if (!dev.ok(hipMemcpy(&nNext, at + (s1 - s0), 4, hipMemcpyDeviceToHost), "level")) return false;
     if (nNext == 0) break;
     if ((size_t)s1 + nNext > capWide || wl.size() > 4096) {
       err = "device collapse: node count out of bounds";
@@ -1626,7 +1640,7 @@ bool collapseOnDevice(BvhDeviceBuild* build, BvhDeviceArena& pool, BvhWideNode**
   const uint32_t nWide = wl.back();
   for (size_t l = wl.size() - 1; l-- > 0;) hipLaunchKernelGGL(k_wide_sizes, gridFor(wl[l + 1] - wl[l]), blk, 0, st, W, wl[l], wl[l + 1]);
   uint32_t numTop = 0;
-  if (!ok(hipMemcpy(&numTop, W.sizeTop, 4, hipMemcpyDeviceToHost), "sizes")) return false;
+  if (!dev.ok(hipMemcpy(&numTop, W.sizeTop, 4, hipMemcpyDeviceToHost), "sizes")) return false;
   uint32_t *defCountByIdx = nullptr, *defBaseByIdx = nullptr, *rankOf = nullptr, *sizeByRank = nullptr, *offByRank = nullptr;
   if (!devAllocT(pool, &defCountByIdx, (size_t)numTop + 1, err) || !devAllocT(pool, &defBaseByIdx, (size_t)numTop + 1, err) || !devAllocT(pool, &rankOf, nWide, err) ||
       !devAllocT(pool, &sizeByRank, (size_t)nWide + 1, err) || !devAllocT(pool, &offByRank, (size_t)nWide + 1, err))
@@ -1634,7 +1648,7 @@ bool collapseOnDevice(BvhDeviceBuild* build, BvhDeviceArena& pool, BvhWideNode**
   for (size_t l = 0; l + 1 < wl.size(); l++) hipLaunchKernelGGL(k_wide_number_top, gridFor(wl[l + 1] - wl[l]), blk, 0, st, W, wl[l], wl[l + 1], defCountByIdx);
   scan.run(defCountByIdx, numTop, defBaseByIdx, st);
   uint32_t numDef = 0;
-  if (!ok(hipMemcpy(&numDef, defBaseByIdx + numTop, 4, hipMemcpyDeviceToHost), "deferred")) return false;
+  if (!dev.ok(hipMemcpy(&numDef, defBaseByIdx + numTop, 4, hipMemcpyDeviceToHost), "deferred")) return false;
   if (numDef > 0) {
     hipLaunchKernelGGL(k_wide_def_rank, gridFor(nWide), blk, 0, st, W, nWide, defBaseByIdx, rankOf, sizeByRank);
     scan.run(sizeByRank, numDef, offByRank, st);
@@ -1651,17 +1665,17 @@ bool collapseOnDevice(BvhDeviceBuild* build, BvhDeviceArena& pool, BvhWideNode**
   hipLaunchKernelGGL(k_wide_emit, gridFor(nWide), blk, 0, st, W, nWide, dWide, dSlots);
   BvhBuildNode root;
   uint32_t hc[2] = {0, 0};
-  if (!ok(hipMemcpy(&root, nodes, sizeof(root), hipMemcpyDeviceToHost), "root") || !ok(hipMemcpy(hc, counters, 8, hipMemcpyDeviceToHost), "summary")) return false;
+  if (!dev.ok(hipMemcpy(&root, nodes, sizeof(root), hipMemcpyDeviceToHost), "root") || !dev.ok(hipMemcpy(hc, counters, 8, hipMemcpyDeviceToHost), "summary")) return false;
   const float rootArea = root.box.area();
   double cost = 0.0;
   if (rootArea > 0) {
     hipLaunchKernelGGL(k_sah_terms, gridFor(nWide), blk, 0, st, dWide, nWide, nodes, rootArea, term);
     hipLaunchKernelGGL(k_sah_sum, dim3(nBlocks), dim3(64), 0, st, term, nWide, part);
     std::vector<double> hp(nBlocks);
-    if (!ok(hipMemcpy(hp.data(), part, (size_t)nBlocks * 8, hipMemcpyDeviceToHost), "cost")) return false;
+    if (!dev.ok(hipMemcpy(hp.data(), part, (size_t)nBlocks * 8, hipMemcpyDeviceToHost), "cost")) return false;
     for (double v : hp) cost += v;
   }
-  if (!ok(hipGetLastError(), "launch") || !ok(hipDeviceSynchronize(), "synchronise")) return false;
+  if (!dev.ok(hipGetLastError(), "launch") || !dev.ok(hipDeviceSynchronize(), "synchronise")) return false;
   out.maxDepth = hc[0];
   out.maxStack = hc[1];
   out.numNodes = nWide;
@@ -1687,17 +1701,9 @@ bool buildBinaryTreeOnDevice(void* user, const BvhBuildRef* refs, uint32_t n, Bi
     err = "device tree builder: no such device";
     return false;
   }
-  const bool verbose = std::getenv("BDPT_BUILD_VERBOSE") != nullptr;
-  auto t0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!verbose) return;
-    (void)hipDeviceSynchronize();
-    const auto t1 = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[bvh]   device %-10s %.3f s\n", what, std::chrono::duration<double>(t1 - t0).count());
-    t0 = t1;
-  };
+  DeviceStage dev{"device tree builder", err};
   // BDPT_BUILD_VERBOSE=2: synchronise after every stage and report where the levels' time goes
-  const bool stages = verbose && std::atoi(std::getenv("BDPT_BUILD_VERBOSE")) >= 2;
+  const bool stages = dev.verbose && std::atoi(std::getenv("BDPT_BUILD_VERBOSE")) >= 2;
   enum { S_BOUNDS, S_PREPARE, S_SMALL, S_BIN, S_DECIDE, S_FLAGS, S_SCAN, S_NLEFT, S_MEDIAN, S_CHILDREN, S_SCATTER, S_COUNT };
   static const char* const stageName[S_COUNT] = {"bounds", "prepare", "small", "bin", "decide", "flags", "scan", "nleft+read", "median", "children", "scatter"};
   double stageTime[S_COUNT] = {};
@@ -1718,11 +1724,6 @@ bool buildBinaryTreeOnDevice(void* user, const BvhBuildRef* refs, uint32_t n, Bi
     }
   } takenRefs;
   hipStream_t st = nullptr;  // the default stream: the build is a blocking call of set-up, not of the frame
-  auto ok = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    err = std::string("device tree builder: ") + what + ": " + hipGetErrorString(e);
-    return false;
-  };
   const size_t cap = n;                  // active slots per level: disjoint non-empty ranges
   const size_t maxNodes = 2 * (size_t)n;  // a binary tree over n references has at most 2n - 1 nodes
   BvhBuildRef *rA = nullptr, *rB = nullptr;
@@ -1750,9 +1751,9 @@ bool buildBinaryTreeOnDevice(void* user, const BvhBuildRef* refs, uint32_t n, Bi
     return false;
   scan.capTiles = (uint32_t)((std::max<size_t>(n, cap) + kScanTile - 1) / kScanTile) + 1;
   if (!devAllocT(pool, &scan.sums, scan.capTiles, err) || !devAllocT(pool, &scan.total, 1, err)) return false;
-  lap("alloc");
-  if (refs && !ok(hipMemcpy(rA, refs, (size_t)n * sizeof(BvhBuildRef), hipMemcpyHostToDevice), "upload")) return false;
-  lap("upload");
+  dev.lap("alloc");
+  if (refs && !dev.ok(hipMemcpy(rA, refs, (size_t)n * sizeof(BvhBuildRef), hipMemcpyHostToDevice), "upload")) return false;
+  dev.lap("upload");
 
   const dim3 blk(256);
   auto gridFor = [](size_t m) { return dim3((unsigned)((m + 255) / 256)); };
@@ -1770,7 +1771,7 @@ bool buildBinaryTreeOnDevice(void* user, const BvhBuildRef* refs, uint32_t n, Bi
     }
     Level& Lc = L[cur];
     Level& Ln = L[cur ^ 1];
-    if (!ok(hipMemsetAsync(C, 0, sizeof(Counters), st), "memset")) return false;
+    if (!dev.ok(hipMemsetAsync(C, 0, sizeof(Counters), st), "memset")) return false;
     if (stages) {
       (void)hipDeviceSynchronize();
       ts = std::chrono::steady_clock::now();
@@ -1792,7 +1793,7 @@ bool buildBinaryTreeOnDevice(void* user, const BvhBuildRef* refs, uint32_t n, Bi
     stage(S_SCAN);
     hipLaunchKernelGGL(k_nleft, gridFor(nA), blk, 0, st, Lc, nA, S, C);
     Counters hc;
-    if (!ok(hipMemcpy(&hc, C, sizeof(hc), hipMemcpyDeviceToHost), "counters")) return false;
+    if (!dev.ok(hipMemcpy(&hc, C, sizeof(hc), hipMemcpyDeviceToHost), "counters")) return false;
     stage(S_NLEFT);
     if (hc.numMedianNew > 0) {
       // median fallback: every such slot's pivot (by one wave's ranking, or by a radix select), then the flags again
@@ -1802,10 +1803,10 @@ bool buildBinaryTreeOnDevice(void* user, const BvhBuildRef* refs, uint32_t n, Bi
         if (!selHist && (!devAllocT(pool, &selHist, (size_t)capBig * 256, err) || !devAllocT(pool, &selHi, capBig, err) || !devAllocT(pool, &selLo, capBig, err) ||
                          !devAllocT(pool, &selK, capBig, err)))
           return false;
-        if (!ok(hipMemsetAsync(bigCount, 0, 4, st), "memset") || !ok(hipMemsetAsync(selHist, 0, (size_t)capBig * 256 * 4, st), "memset")) return false;
+        if (!dev.ok(hipMemsetAsync(bigCount, 0, 4, st), "memset") || !dev.ok(hipMemsetAsync(selHist, 0, (size_t)capBig * 256 * 4, st), "memset")) return false;
         hipLaunchKernelGGL(k_median_list_big, gridFor(nA), blk, 0, st, Lc, nA, bigList, bigCount, selHi, selLo, selK);
         uint32_t m = 0;
-        if (!ok(hipMemcpy(&m, bigCount, 4, hipMemcpyDeviceToHost), "list")) return false;
+        if (!dev.ok(hipMemcpy(&m, bigCount, 4, hipMemcpyDeviceToHost), "list")) return false;
         for (int pass = 7; pass >= 0 && m > 0; pass--) {
           hipLaunchKernelGGL(k_sel_hist, gridFor(n), blk, 0, st, rA, ofA, n, Lc, pass, selHi, selLo, selHist);
           hipLaunchKernelGGL(k_sel_pick, gridFor(m), blk, 0, st, m, pass, selHi, selLo, selK, selHist, Lc, bigList);
@@ -1820,7 +1821,7 @@ bool buildBinaryTreeOnDevice(void* user, const BvhBuildRef* refs, uint32_t n, Bi
     hipLaunchKernelGGL(k_split_flags, gridFor(nA), blk, 0, st, Lc, nA, G);
     scan.run(G, nA, R, st);
     uint32_t numSplit = 0;
-    if (!ok(hipMemcpy(&numSplit, R + nA, 4, hipMemcpyDeviceToHost), "split count")) return false;
+    if (!dev.ok(hipMemcpy(&numSplit, R + nA, 4, hipMemcpyDeviceToHost), "split count")) return false;
     if ((size_t)numNodes + 2 * (size_t)numSplit > maxNodes || 2 * (size_t)numSplit > cap) {
       err = "device tree builder: node count out of bounds";
       return false;
@@ -1837,10 +1838,10 @@ bool buildBinaryTreeOnDevice(void* user, const BvhBuildRef* refs, uint32_t n, Bi
     if (numSplit > 0) build->levelStart.push_back(numNodes);
     nA = 2 * numSplit;
     cur ^= 1;
-    if (!ok(hipGetLastError(), "launch")) return false;
+    if (!dev.ok(hipGetLastError(), "launch")) return false;
   }
-  if (!ok(hipDeviceSynchronize(), "synchronise")) return false;
-  lap("levels");
+  if (!dev.ok(hipDeviceSynchronize(), "synchronise")) return false;
+  dev.lap("levels");
   if (stages)
     for (int i = 0; i < S_COUNT; i++) std::fprintf(stderr, "[bvh]   device stage %-10s %.4f s\n", stageName[i], stageTime[i]);
   // back to the host: the leaf order and the tree, in the host's formats (the boxes of the references are the caller's own)
@@ -1862,22 +1863,22 @@ bool buildBinaryTreeOnDevice(void* user, const BvhBuildRef* refs, uint32_t n, Bi
   BvhBuildNode* const dNodes = build->nodes;
   hipLaunchKernelGGL(k_order, gridFor(n), blk, 0, st, rA, n, dOrder);
   hipLaunchKernelGGL(k_pack_nodes, gridFor(numNodes), blk, 0, st, T, numNodes, dNodes);
-  if (!ok(hipDeviceSynchronize(), "pack")) return false;
-  order.resize(refs ? n : 0);  // (references that never left the device: the packer reads the order there)
-  const bool keepHere = build->collapseHere && !refs;  // the collapse happens here too: only the root goes back (a tree was built)
-  nodes.resize(keepHere ? 1 : numNodes);
-  if ((refs && !downloadStaged(order.data(), dOrder, (size_t)n * 4, err)) ||
-      !downloadStaged(nodes.data(), dNodes, (size_t)(keepHere ? 1 : numNodes) * sizeof(BvhBuildNode), err))
+  if (!dev.ok(hipDeviceSynchronize(), "pack")) return false;
+  // the caller's references: the order and the whole tree go back.  References that never left the device: the packer
+  // reads both here and collapses the tree here, so only the root goes back (a tree was built)
+  order.resize(refs ? n : 0);
+  nodes.resize(refs ? numNodes : 1);
+  if ((refs && !downloadStaged(order.data(), dOrder, (size_t)n * 4, err)) || !downloadStaged(nodes.data(), dNodes, nodes.size() * sizeof(BvhBuildNode), err))
     return false;
-  lap("download");
+  dev.lap("download");
   return true;
 }
 
-// The BvhPacker bdpt_set_scene plugs into buildBvh (after buildBinaryTreeOnDevice of the same build).
+// The BvhPacker bdpt_set_scene plugs into buildBvh: after makeReferencesOnDevice and buildBinaryTreeOnDevice of the same
+// build, from the triangle records, the references' triangles, the order and the tree they kept.
 bool packOnDevice(void* user, const BvhPackInput& in, Bvh& out, std::string& err) {
   BvhDeviceBuild* const build = static_cast<BvhDeviceBuild*>(user);
-  const bool collapse = in.wide == nullptr;  // the four-wide collapse has not happened yet: it happens here
-  if (!build || !build->nodes || !build->order || build->numRefs != in.numRefs || (!collapse && (in.numWide == 0 || in.numWide > 0x7fffffffull))) {
+  if (!build || !build->nodes || !build->order || build->numRefs != in.numRefs) {
     err = "device packer: no tree of this build in device memory";
     return false;
   }
@@ -1885,60 +1886,33 @@ bool packOnDevice(void* user, const BvhPackInput& in, Bvh& out, std::string& err
     err = "device packer: no such device";
     return false;
   }
-  const bool verbose = std::getenv("BDPT_BUILD_VERBOSE") != nullptr;
-  auto t0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!verbose) return;
-    (void)hipDeviceSynchronize();
-    const auto t1 = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[bvh]   device %-10s %.3f s\n", what, std::chrono::duration<double>(t1 - t0).count());
-    t0 = t1;
-  };
+  DeviceStage dev{"device packer", err};
   BvhDeviceArena& pool = build->arena;
   BvhDeviceArenaScope scratch{pool};
-  auto ok = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    err = std::string("device packer: ") + what + ": " + hipGetErrorString(e);
+  if (!build->refTri || !build->triRecs || build->numMadeRefs != in.numRefs || build->numTris != in.numTris) {
+    err = "device packer: no references of this build in device memory";
     return false;
-  };
-  uint32_t nWide = (uint32_t)in.numWide;
-  BvhTri* dTri = nullptr;
-  uint32_t *dRefTri = nullptr, *dBlock = nullptr, *dBase = nullptr, *dPos = nullptr;
+  }
+  uint32_t nWide = 0;
+  uint32_t *dBlock = nullptr, *dBase = nullptr, *dPos = nullptr;
   BvhWideNode* dWide = nullptr;
   BvhSlot* dSlots = nullptr;
   BvhRec* dTmp = nullptr;
   Scan scan;
-  const bool kept = in.refTri == nullptr;  // the reference maker of this build kept refTri and the triangle records
-  if (kept && (!build->refTri || !build->triRecs || build->numMadeRefs != in.numRefs || build->numTris != in.numTris)) {
-    err = "device packer: no references of this build in device memory";
-    return false;
-  }
-  if (kept) {
-    dTri = build->triRecs;
-    dRefTri = build->refTri;
-  }
-  if (collapse) {
-    if (!collapseOnDevice(build, pool, &dWide, &dSlots, &nWide, out, err)) return false;
-    lap("collapse");
-  }
-  if ((!kept && (!devAllocT(pool, &dTri, in.numTris, err) || !devAllocT(pool, &dRefTri, in.numRefs, err))) || (!collapse && !devAllocT(pool, &dWide, nWide, err)) ||
-      (!collapse && !devAllocT(pool, &dSlots, nWide, err)) || !devAllocT(pool, &dTmp, nWide, err) || !devAllocT(pool, &dBlock, (size_t)nWide + 1, err) ||
-      !devAllocT(pool, &dBase, (size_t)nWide + 1, err) || !devAllocT(pool, &dPos, nWide, err))
+  if (!collapseOnDevice(build, pool, &dWide, &dSlots, &nWide, out, err)) return false;
+  dev.lap("collapse");
+  if (!devAllocT(pool, &dTmp, nWide, err) || !devAllocT(pool, &dBlock, (size_t)nWide + 1, err) || !devAllocT(pool, &dBase, (size_t)nWide + 1, err) ||
+      !devAllocT(pool, &dPos, nWide, err))
     return false;
   scan.capTiles = (nWide + kScanTile - 1) / kScanTile + 1;
   if (!devAllocT(pool, &scan.sums, scan.capTiles, err) || !devAllocT(pool, &scan.total, 1, err)) return false;
-  if ((!kept && (!ok(hipMemcpy(dTri, in.triRecs, (size_t)in.numTris * sizeof(BvhTri), hipMemcpyHostToDevice), "upload") ||
-                 !ok(hipMemcpy(dRefTri, in.refTri, (size_t)in.numRefs * 4, hipMemcpyHostToDevice), "upload"))) ||
-      (!collapse && (!ok(hipMemcpy(dWide, in.wide, (size_t)nWide * sizeof(BvhWideNode), hipMemcpyHostToDevice), "upload") ||
-                     !ok(hipMemcpy(dSlots, in.slots, (size_t)nWide * sizeof(BvhSlot), hipMemcpyHostToDevice), "upload"))))
-    return false;
-  lap("pack upload");
+  dev.lap("pack upload");
   hipStream_t st = nullptr;
   const dim3 blk(256), grid((nWide + 255) / 256);
   hipLaunchKernelGGL(k_quantise, grid, blk, 0, st, dWide, nWide, build->nodes, in.pad, dTmp, dBlock);
   scan.run(dBlock, nWide, dBase, st);
   uint32_t total = 0;
-  if (!ok(hipMemcpy(&total, dBase + nWide, 4, hipMemcpyDeviceToHost), "block sizes")) return false;
+  if (!dev.ok(hipMemcpy(&total, dBase + nWide, 4, hipMemcpyDeviceToHost), "block sizes")) return false;
   const uint64_t next = 1ull + total;
   if (next >= 0x7fffffffull || total < nWide - 1) {  // (the 32-bit sum wrapped, or the format's 2^31 records are not enough)
     err = "bvh does not fit the packed record format (2^31 records)";
@@ -1951,17 +1925,17 @@ bool packOnDevice(void* user, const BvhPackInput& in, Bvh& out, std::string& err
     return false;
   }
   BvhRec* const dRecs = static_cast<BvhRec*>(q);
-  bool good = ok(hipMemsetAsync(dRecs + next, 0, kBvhPadRecs * sizeof(BvhRec), st), "memset");
+  bool good = dev.ok(hipMemsetAsync(dRecs + next, 0, kBvhPadRecs * sizeof(BvhRec), st), "memset");
   if (good) {
     hipLaunchKernelGGL(k_node_pos, grid, blk, 0, st, dSlots, nWide, dTmp, dBase, dPos);
-    hipLaunchKernelGGL(k_write_recs, grid, blk, 0, st, dWide, nWide, build->nodes, dTmp, dBase, dPos, build->order, dRefTri, dTri, dRecs);
-    good = ok(hipGetLastError(), "launch") && ok(hipDeviceSynchronize(), "synchronise");
+    hipLaunchKernelGGL(k_write_recs, grid, blk, 0, st, dWide, nWide, build->nodes, dTmp, dBase, dPos, build->order, build->refTri, build->triRecs, dRecs);
+    good = dev.ok(hipGetLastError(), "launch") && dev.ok(hipDeviceSynchronize(), "synchronise");
   }
   if (!good) {
     (void)hipFree(dRecs);
     return false;
   }
-  lap("pack");
+  dev.lap("pack");
   build->release();
   out.deviceRecs = dRecs;
   out.deviceNumRecs = numRecs;
@@ -1983,27 +1957,18 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
   build->release();
   numRefs = 0;
   if (in.numTris == 0) return true;
-  const bool verbose = std::getenv("BDPT_BUILD_VERBOSE") != nullptr;
-  auto t0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!verbose) return;
-    (void)hipDeviceSynchronize();
-    const auto t1 = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[bvh]   device %-10s %.3f s\n", what, std::chrono::duration<double>(t1 - t0).count());
-    t0 = t1;
-  };
+  DeviceStage dev{"device reference maker", err};
   BvhDeviceArena& pool = build->arena;
   BvhDeviceArenaScope scratch{pool};
-  auto ok = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    err = std::string("device reference maker: ") + what + ": " + hipGetErrorString(e);
-    return false;
-  };
   auto upload = [&](auto** dst, const auto* src, size_t count) {
     if (!devAllocT(pool, dst, count, err)) return false;
     return count == 0 || uploadStagedImpl(*dst, src, count * sizeof(**dst), err);
   };
   const uint32_t nT = in.numTris;
+  if (in.uploadTriRecs ? (!in.triRecs || !in.triBox) : (!in.positions || !in.indices || !in.numVertices)) {
+    err = "device reference maker: neither triangle records nor what they are made of were handed over";
+    return false;
+  }
   RefArgs A{};
   {  // the triangle records stay for the packer
     void* q = nullptr;
@@ -2020,8 +1985,7 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
   uint8_t* dState = nullptr;
   uint32_t* dIdxAll = nullptr;  // the index list, shared with the clipper's tables below when they name the same array
   const bool decideHere = in.splits == nullptr;  // classification, priorities and split counts happen here too
-  // BDPT_UPLOAD_TRI_RECS (measurement knob): hand the host's records and boxes over instead of making them here
-  if (in.positions && in.indices && in.numVertices && nT && std::getenv("BDPT_UPLOAD_TRI_RECS") == nullptr) {
+  if (!in.uploadTriRecs) {
     // records and boxes made here from what they are made of: 12 B per vertex + 20 B per triangle cross the bus
     // instead of 72 B per triangle
     float* dPos = nullptr;
@@ -2032,10 +1996,7 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
     if (!devAllocT(pool, &dTriBox, nT, err)) return false;
     hipLaunchKernelGGL(k_tri_recs, dim3((nT + 255) / 256), dim3(256), 0, nullptr, dPos, dIdxAll, dFlags, dAux, nT, build->triRecs, dTriBox);
   } else {
-    if (!in.triRecs || !in.triBox) {
-      err = "device reference maker: neither triangle records nor what they are made of were handed over";
-      return false;
-    }
+    // (measurement knob, or a caller that does not know how many vertices there are: the host's records and boxes)
     if (!uploadStagedImpl(build->triRecs, in.triRecs, (size_t)nT * sizeof(BvhTri), err)) return false;
     if (!upload(&dTriBox, in.triBox, nT)) return false;
   }
@@ -2076,7 +2037,7 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
     A.haveClipper = 1;
     A.clip = BvhClipView{dMat, dIdx, dTex, dMask, dVerdict, dMasks};
   }
-  lap("refs upload");
+  dev.lap("refs upload");
   hipStream_t st = nullptr;
   const dim3 blk(256), grid((nT + 255) / 256);
   unsigned long long* dSum = nullptr;
@@ -2090,9 +2051,9 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
       const float budgetF = cls ? in.budgetAlpha : in.budgetOpaque;
       if (!(budgetF > 0.0f)) continue;
       unsigned long long stats[2] = {0, 0};
-      if (!ok(hipMemsetAsync(dSum, 0, 16, st), "memset")) return false;
+      if (!dev.ok(hipMemsetAsync(dSum, 0, 16, st), "memset")) return false;
       hipLaunchKernelGGL(k_class_stats, grid, blk, 0, st, A, dState, prio, cls, dSum);
-      if (!ok(hipMemcpy(stats, dSum, 16, hipMemcpyDeviceToHost), "class")) return false;
+      if (!dev.ok(hipMemcpy(stats, dSum, 16, hipMemcpyDeviceToHost), "class")) return false;
       const uint64_t members = stats[0];
       double pmax;
       std::memcpy(&pmax, &stats[1], 8);
@@ -2113,7 +2074,7 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
       }
       hipLaunchKernelGGL(k_split_assign, grid, blk, 0, st, A, dState, prio, capOf, cls, D, dSplits);
     }
-    lap("refs decide");
+    dev.lap("refs decide");
   }
   uint32_t *capRefs = nullptr, *capStack = nullptr, *slotAt = nullptr, *stackAt = nullptr, *made = nullptr, *refAt = nullptr;
   Scan scan;
@@ -2126,13 +2087,13 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
   scan.run(capRefs, nT, slotAt, st);
   scan.run(capStack, nT, stackAt, st);
   uint32_t totalSlots = 0, totalStack = 0;
-  if (!ok(hipMemcpy(&totalSlots, slotAt + nT, 4, hipMemcpyDeviceToHost), "caps") || !ok(hipMemcpy(&totalStack, stackAt + nT, 4, hipMemcpyDeviceToHost), "caps")) return false;
+  if (!dev.ok(hipMemcpy(&totalSlots, slotAt + nT, 4, hipMemcpyDeviceToHost), "caps") || !dev.ok(hipMemcpy(&totalStack, stackAt + nT, 4, hipMemcpyDeviceToHost), "caps")) return false;
   bool plain = true;  // nothing to split, nothing shrunk
   {  // (the scans are 32-bit: make sure they did not wrap)
     unsigned long long sum[3] = {0, 0, 0};
-    if (!ok(hipMemsetAsync(dSum, 0, 24, st), "memset")) return false;
+    if (!dev.ok(hipMemsetAsync(dSum, 0, 24, st), "memset")) return false;
     hipLaunchKernelGGL(k_ref_summary, grid, blk, 0, st, nT, A.state, A.splits, dSum);
-    if (!ok(hipMemcpy(sum, dSum, 24, hipMemcpyDeviceToHost), "summary")) return false;
+    if (!dev.ok(hipMemcpy(sum, dSum, 24, hipMemcpyDeviceToHost), "summary")) return false;
     if (sum[1] != totalSlots || sum[1] >= 0x7fffffffull) {
       err = "bvh does not fit the packed record format (2^31 records)";
       return false;
@@ -2149,8 +2110,8 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
     hipLaunchKernelGGL(k_make_refs, dim3((nT + 63) / 64), dim3(64), 0, st, A, slotAt, stackAt, stacks, boxes, made);
   scan.run(made, nT, refAt, st);
   uint32_t total = 0;
-  if (!ok(hipMemcpy(&total, refAt + nT, 4, hipMemcpyDeviceToHost), "count")) return false;
-  lap("refs make");
+  if (!dev.ok(hipMemcpy(&total, refAt + nT, 4, hipMemcpyDeviceToHost), "count")) return false;
+  dev.lap("refs make");
   if (total > 0) {
     void *q0 = nullptr, *q1 = nullptr;
     if (hipMalloc(&q0, (size_t)total * sizeof(BvhBuildRef)) != hipSuccess || hipMalloc(&q1, (size_t)total * 4) != hipSuccess) {
@@ -2162,10 +2123,10 @@ bool makeReferencesOnDevice(void* user, const BvhRefInput& in, uint32_t& numRefs
     build->refTri = static_cast<uint32_t*>(q1);
     hipLaunchKernelGGL(k_compact_refs, grid, blk, 0, st, nT, slotAt, made, refAt, boxes, build->refs, build->refTri);
   }
-  if (!ok(hipGetLastError(), "launch") || !ok(hipDeviceSynchronize(), "synchronise")) return false;
+  if (!dev.ok(hipGetLastError(), "launch") || !dev.ok(hipDeviceSynchronize(), "synchronise")) return false;
   build->numMadeRefs = total;
   numRefs = total;
-  lap("refs compact");
+  dev.lap("refs compact");
   return true;
 }
 

@@ -35,7 +35,7 @@ void hostFor(size_t n, int threads, const F& f) {
 }  // namespace
 
 void buildSceneBvh(const bdpt_scene_desc* d, int threads, float splitBudget, float splitBudgetAlpha, bool classify, SceneBvh& out,
-                   BvhTreeBuilder treeBuilder, void* treeBuilderUser, std::string* error, BvhPacker packer, BvhRefMaker refMaker, bool collapseInPacker, bool prioritiesInRefMaker) {
+                   const BvhBackend* backend, std::string* error) {
   if (threads <= 0) threads = bvhBuildThreads();
   const bool verbose = std::getenv("BDPT_BUILD_VERBOSE") != nullptr;
   auto tLap = std::chrono::steady_clock::now();
@@ -89,12 +89,7 @@ void buildSceneBvh(const bdpt_scene_desc* d, int threads, float splitBudget, flo
   opt.splitBudgetAlpha = splitBudgetAlpha;
   opt.clipper = classify ? out.clipper.get() : nullptr;
   opt.numVertices = d->numVertices;
-  opt.treeBuilder = treeBuilder;
-  opt.treeBuilderUser = treeBuilderUser;
-  opt.packer = packer;
-  opt.refMaker = refMaker;
-  opt.collapseInPacker = collapseInPacker;
-  opt.prioritiesInRefMaker = prioritiesInRefMaker;
+  opt.backend = backend;
   opt.error = error;
   lap("aux");
   buildBvh(d->positions, d->indices, n, out.triFlags.data(), out.bvh, opt, out.triAux.data());

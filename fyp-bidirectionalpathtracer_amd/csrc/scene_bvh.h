@@ -23,10 +23,10 @@ struct SceneBvh {
 
 // threads / budgets as BvhBuildOptions (negative budgets: build defaults); classify = false keeps the reference's
 // per-material opacity (every triangle of an alpha-mode material is tested, nothing is dropped or clipped).
-// refMaker / treeBuilder / packer (may be null: host code) make the references, build the binary tree and pack the records — bdpt_set_scene passes the
-// device implementations; when one fails *error says why (no nodes / no device records then).
+// backend (null: the default one, host code): where the references are made, the binary tree is built and the records are
+// packed — bdpt_set_scene passes the device implementations; when a stage fails *error says why (no nodes / no device
+// records then).
 void buildSceneBvh(const bdpt_scene_desc* d, int threads, float splitBudget, float splitBudgetAlpha, bool classify, SceneBvh& out,
-                   BvhTreeBuilder treeBuilder = nullptr, void* treeBuilderUser = nullptr, std::string* error = nullptr, BvhPacker packer = nullptr,
-                   BvhRefMaker refMaker = nullptr, bool collapseInPacker = false, bool prioritiesInRefMaker = false);
+                   const BvhBackend* backend = nullptr, std::string* error = nullptr);
 
 }  // namespace bdpt

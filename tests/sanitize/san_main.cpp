@@ -141,6 +141,42 @@ int main(int argc, char** argv) {
     }
     bdpt_scene_destroy(sc);
   }
+  {  // buildBvh's backend (bvh.h BvhBackend) on a dozen triangles: a shape that is not legal — a pack stage without a
+     // reference maker — is refused with a message before any stage runs; the tree-only shape with a tree builder that
+     // fails ends with that stage's message; either way the result is empty
+    std::vector<float> pos;
+    std::vector<uint32_t> idx;
+    for (uint32_t t = 0; t < 12; t++) {
+      const float x = (float)t;
+      pos.insert(pos.end(), {x, 0.0f, 0.0f, x + 0.5f, 1.0f, 0.0f, x, 0.0f, 1.0f});
+      idx.insert(idx.end(), {3 * t, 3 * t + 1, 3 * t + 2});
+    }
+    static int calls;
+    calls = 0;
+    const bdpt::BvhTreeBuilder mustNotRun = [](void*, const bdpt::BvhBuildRef*, uint32_t, bdpt::BigVec<uint32_t>&, bdpt::BigVec<bdpt::BvhBuildNode>&, std::string&) -> bool { std::abort(); };
+    const bdpt::BvhPacker mustNotPack = [](void*, const bdpt::BvhPackInput&, bdpt::Bvh&, std::string&) -> bool { std::abort(); };
+    const bdpt::BvhTreeBuilder failing = [](void*, const bdpt::BvhBuildRef* refs, uint32_t n, bdpt::BigVec<uint32_t>&, bdpt::BigVec<bdpt::BvhBuildNode>&, std::string&) -> bool {
+      calls += (refs && n == 12) ? 1 : 100;  // the tree-only shape hands the host's references over
+      return false;
+    };
+    for (int which = 0; which < 2; which++) {
+      bdpt::BvhBackend be;
+      be.buildTree = which == 0 ? mustNotRun : failing;
+      be.pack = which == 0 ? mustNotPack : nullptr;
+      std::string error;
+      bdpt::BvhBuildOptions opt;
+      opt.threads = 2;
+      opt.backend = &be;
+      opt.error = &error;
+      bdpt::Bvh bvh;
+      bvh.nodes.resize(3);  // (what an earlier build left must go as well)
+      bdpt::buildBvh(pos.data(), idx.data(), 12, nullptr, bvh, opt);
+      const bool empty = bvh.nodes.empty() && bvh.tris.empty() && bvh.recs.empty() && !bvh.deviceRecs;
+      const bool message = which == 0 ? !error.empty() : error == "tree builder failed";
+      std::printf("backend shape %d: \"%s\", %s, %d tree builder calls\n", which, error.c_str(), empty ? "empty" : "NOT EMPTY", calls);
+      if (!empty || !message || calls != which) rc |= 1;
+    }
+  }
   {  // the builders' outward rounding (bvh_refs.h: the next float on the bits, for the host and the device alike) against
      // std::nextafterf: the edges, then a million random doubles of every float magnitude, denormals included
     auto down = [](double x) {

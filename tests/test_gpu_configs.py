@@ -600,11 +600,11 @@ def test_device_reference_maker_forks(pkg, monkeypatch):
     """The two forks of the device reference maker that no other test takes, against the host build (packed records +
     summary, bdpt_bvh_recs_hash): BDPT_HOST_PRIORITIES (the host decides what the clipper leaves, the priorities and the split
     counts, and uploads state and counts: k_prio and the split-count kernels are skipped) and BDPT_UPLOAD_TRI_RECS (the
-    host's triangle records and boxes are uploaded: k_tri_recs is skipped), next to the default path.  400 alpha-masked
-    blob cards tiled 3.7 times plus the opaque floor, opaque budget 2 (the floor is an outlier and is split), alpha budget
-    16: references must outnumber the kept triangles, so nothing passes by never splitting.  A card tiled 3.7 times sees
+    host's triangle records and boxes are uploaded: k_tri_recs is skipped), each alone and both together, next to the
+    default path.  400 alpha-masked blob cards tiled 3.7 times plus the opaque floor, opaque budget 2 (the floor is an
+    outlier and is split), alpha budget 16: references must outnumber the kept triangles, so nothing passes by never splitting.  A card tiled 3.7 times sees
     every texel of a texture that has any passing cell, so no triangle of that scene can be dropped, whatever the seed; the
-    same cards over half a period of the same texture supply the dropped triangles, and both scenes go through all three
+    same cards over half a period of the same texture supply the dropped triangles, and both scenes go through all four
     paths."""
     lib = pkg.load_library()
     rng = np.random.default_rng(5)
@@ -622,10 +622,10 @@ def test_device_reference_maker_forks(pkg, monkeypatch):
         host = build(-1)
         assert host[5] > d.numTriangles - host[6], (uv_scale, host)  # pieces were split off
         assert (host[6] > 0) == drops, (uv_scale, host)              # the clipper dropped triangles
-        for fork in (None, "BDPT_HOST_PRIORITIES", "BDPT_UPLOAD_TRI_RECS"):
-            if fork:
+        for forks in ((), ("BDPT_HOST_PRIORITIES",), ("BDPT_UPLOAD_TRI_RECS",), ("BDPT_HOST_PRIORITIES", "BDPT_UPLOAD_TRI_RECS")):
+            for fork in forks:
                 monkeypatch.setenv(fork, "1")
-            assert build(0) == host, (uv_scale, fork)
-            if fork:
+            assert build(0) == host, (uv_scale, forks)
+            for fork in forks:
                 monkeypatch.delenv(fork)
         del keep
