@@ -320,6 +320,107 @@ class Context:
             out.append(a)
         return tuple(out)
 
+    def set_morph(self, target_start, vertex, d_positions, d_normals=None, d_bitangents=None, positions=None, normals=None,
+                  bitangents=None):
+        """bdpt_set_morph: morph targets as sparse deltas, all host arrays, copied before this returns.  target_start
+        (numTargets + 1, uint32): target t owns entries [target_start[t], target_start[t + 1]); vertex (uint32, per
+        entry, strictly ascending inside a target); d_positions / d_normals / d_bitangents: entries x 3 float32.
+        positions / normals / bitangents: the base pose (numVertices x 3), for a context without a skin only (with a skin
+        the base is its rest pose).  Synchronises and allocates; not inside a stream capture.  target_start=None drops
+        the morph."""
+        if target_start is None:
+            self._check(self._lib.bdpt_set_morph(self._h, None), "bdpt_set_morph")
+            return
+        import numpy as np
+
+        def host(a, dtype):
+            return None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype).reshape(-1)
+
+        ts, vx = host(target_start, np.uint32), host(vertex, np.uint32)
+        dp, dn, db, p, n, b = (host(a, np.float32) for a in (d_positions, d_normals, d_bitangents, positions, normals, bitangents))
+        if ts.size < 2 or vx is None or dp is None or int(ts[-1]) != vx.size or any(a is not None and a.size != 3 * vx.size for a in (dp, dn, db)):
+            raise BdptError("set_morph: target_start must hold numTargets + 1 offsets ending at the entry count, vertex one id per "
+                            "entry, the deltas entries x 3 each")
+        given = [a for a in (p, n, b) if a is not None]
+        if any(a.size % 3 or a.size != given[0].size for a in given) or (given and p is None):
+            raise BdptError("set_morph: positions, normals and bitangents must be numVertices x 3 each, and positions among them")
+        d = abi.MorphDesc()
+        nv = p.size // 3 if p is not None else getattr(self, "_skin_vertices", 0)
+        d.numVertices, d.numTargets = int(nv), int(ts.size - 1)
+        d.targetStart, d.vertex = ts.ctypes.data, vx.ctypes.data
+        for field, a in (("dPositions", dp), ("dNormals", dn), ("dBitangents", db), ("positions", p), ("normals", n), ("bitangents", b)):
+            setattr(d, field, None if a is None else a.ctypes.data)
+        self._check(self._lib.bdpt_set_morph(self._h, C.byref(d)), "bdpt_set_morph")
+        self._morph_vertices = int(nv)
+
+    def update_morphed(self, weights, bones=None, normal_bones=None, stream=None, keep_light_maps=False):
+        """bdpt_update_morphed: the frame's morph weights (numTargets float32) and, for a context with a skin, its bone
+        matrices (as update_skinned); the vertices are morphed and skinned on the device and the tree refitted.  GPU
+        torch tensors take the device path and numpy arrays / CPU tensors the host path, by the rules of
+        update_geometry, weights and palettes alike.  Nothing is enqueued when an argument is refused."""
+        u = abi.MorphUpdate()
+        if weights is None:
+            raise BdptError("update_morphed: weights are required")
+        arrays = [weights, bones, normal_bones]
+        given = [a for a in arrays if a is not None]
+        on_gpu = [bool(getattr(a, "is_cuda", False)) for a in given]
+        if any(on_gpu):
+            if not all(on_gpu):
+                raise BdptError("update_morphed: weights, bones and normal_bones must all be GPU tensors or all host arrays")
+            for a in given:
+                if a.device.index != self.device:
+                    raise BdptError(f"update_morphed: a tensor on {a.device} for the context of device {self.device}")
+                if not a.is_contiguous() or str(a.dtype) != "torch.float32":
+                    raise BdptError("update_morphed: device inputs must be contiguous float32 tensors")
+            u.memory = abi.MEMORY_DEVICE
+            ptrs = [None if a is None else a.data_ptr() for a in arrays]
+            sizes = [None if a is None else a.numel() for a in arrays]
+        else:
+            import numpy as np
+            u.memory = abi.MEMORY_HOST
+            arrays = [None if a is None else np.ascontiguousarray(a.detach().numpy() if hasattr(a, "detach") else a, np.float32).reshape(-1)
+                      for a in arrays]
+            ptrs = [None if a is None else a.ctypes.data for a in arrays]
+            sizes = [None if a is None else a.size for a in arrays]
+        nb = 0 if sizes[1] is None else sizes[1] // 16
+        if sizes[0] == 0 or (sizes[1] is not None and sizes[1] != 16 * nb) or (sizes[2] is not None and sizes[2] != 16 * nb):
+            raise BdptError("update_morphed: weights must be numTargets floats, bones and normal_bones numBones x 16 each "
+                            "(normal_bones only with bones)")
+        u.weights, u.bones, u.normalBones = ptrs
+        u.numTargets, u.numBones = int(sizes[0]), int(nb)
+        u.flags = abi.UPDATE_KEEP_LIGHT_MAPS if keep_light_maps else 0
+        self._check(self._lib.bdpt_update_morphed(self._h, C.byref(u), stream), "bdpt_update_morphed")
+
+    def morphed_buffers(self):
+        """bdpt_morphed_buffers: the device addresses (int, or None for a stream the base lacks) of the positions, normals
+        and bitangents a morphed update writes; valid until set_morph / set_skin / set_scene."""
+        p, n, b = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self._lib.bdpt_morphed_buffers(self._h, C.byref(p), C.byref(n), C.byref(b)), "bdpt_morphed_buffers")
+        return p.value, n.value, b.value
+
+    def test_morph_kernel(self, path=abi.MORPH_PATH_AUTO, stream=None):
+        """Test hook bdpt_test_morph_kernel: the morph kernel alone, with the weights and palettes the last host-pointer
+        update_morphed staged; path MORPH_PATH_AUTO / _GLOBAL / _LDS."""
+        self._check(self._lib.bdpt_test_morph_kernel(self._h, int(path), stream), "bdpt_test_morph_kernel")
+
+    def read_morphed(self, stream=None):
+        """The streams a morphed update writes copied to the host (numVertices x 3 float32 each, None for a stream the
+        base lacks); waits for `stream`."""
+        import numpy as np
+        self.sync(stream)
+        nv = self._morph_vertices
+        hip = C.CDLL("libamdhip64.so")
+        out = []
+        for ptr in self.morphed_buffers():
+            if ptr is None:
+                out.append(None)
+                continue
+            a = np.empty((nv, 3), np.float32)
+            if hip.hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(ptr), C.c_size_t(a.nbytes), 2) != 0:
+                raise BdptError("read_morphed: hipMemcpy failed")
+            out.append(a)
+        return tuple(out)
+
     def trace_rays(self, rays, mode="closest", out=None, count=None, stream=None):
         """bdpt_trace_rays: closest-hit or any-hit queries of a batch of rays against the scene (semantics: include/bdpt.h
         "Ray queries").  `rays` is (N, 8) float32 in the bdpt_ray layout: origin xyz, tmin, direction xyz, tmax.
@@ -1274,6 +1375,18 @@ class FramePipeline:
         update_geometry.  GPU tensors are marked as in use by that stream."""
         self.ctx.update_skinned(bones, normal_bones, self._stream_ptr(), keep_light_maps)
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (bones, normal_bones))
+        self.accum_count = 0
+
+    def set_morph(self, target_start, vertex, d_positions, d_normals=None, d_bitangents=None, positions=None, normals=None,
+                  bitangents=None):
+        """Context.set_morph (synchronises: everything this pipeline enqueued has finished when it returns)."""
+        self.ctx.set_morph(target_start, vertex, d_positions, d_normals, d_bitangents, positions, normals, bitangents)
+
+    def update_morphed(self, weights, bones=None, normal_bones=None, keep_light_maps=False):
+        """Morph (and pose) the scene (Context.update_morphed on this pipeline's stream); accumulation restarts, as after
+        update_geometry.  GPU tensors are marked as in use by that stream."""
+        self.ctx.update_morphed(weights, bones, normal_bones, self._stream_ptr(), keep_light_maps)
+        keep_for_stream(self.torch.cuda.current_stream(self.dev), (weights, bones, normal_bones))
         self.accum_count = 0
 
     def trace_rays(self, rays, mode="closest", out=None, count=None):

@@ -36,10 +36,13 @@ PREPARE_REFIT_PIECES = 128
 MEMORY_HOST, MEMORY_DEVICE = 0, 1
 UPDATE_KEEP_LIGHT_MAPS = 1
 BDPT_MAX_BONES = 1024
+MAX_MORPH_TARGETS = 1024
 # csrc/skin.h kSkinLdsBones / kSkinLdsMinVertices: palettes up to this size on skins of at least this many vertices take the
 # kernel's LDS path
 SKIN_LDS_BONES, SKIN_LDS_MIN_VERTICES = 64, 1 << 20
 SKIN_PATH_AUTO, SKIN_PATH_GLOBAL, SKIN_PATH_LDS = 0, 1, 2
+# bdpt_test_morph_kernel: the same paths, chosen by the same rule (csrc/morph.h launchMorph)
+MORPH_PATH_AUTO, MORPH_PATH_GLOBAL, MORPH_PATH_LDS = 0, 1, 2
 TRACE_CLOSEST, TRACE_CLOSEST_CULL_BACK, TRACE_ANY = 0, 1, 2
 SHADE_NORMAL_MAP = 1
 BSDF_SAMPLE, BSDF_EVAL = 0, 1
@@ -159,6 +162,17 @@ class SkinDesc(C.Structure):
 class SkinUpdate(C.Structure):
     _fields_ = [("bones", C.c_void_p), ("normalBones", C.c_void_p), ("numBones", C.c_uint32), ("memory", C.c_uint32),
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MorphDesc(C.Structure):
+    _fields_ = [("numVertices", C.c_uint32), ("numTargets", C.c_uint32), ("targetStart", C.c_void_p), ("vertex", C.c_void_p),
+                ("dPositions", C.c_void_p), ("dNormals", C.c_void_p), ("dBitangents", C.c_void_p), ("positions", C.c_void_p),
+                ("normals", C.c_void_p), ("bitangents", C.c_void_p), ("reserved", C.c_uint32 * 2)]
+
+
+class MorphUpdate(C.Structure):
+    _fields_ = [("weights", C.c_void_p), ("bones", C.c_void_p), ("normalBones", C.c_void_p), ("numTargets", C.c_uint32),
+                ("numBones", C.c_uint32), ("memory", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class RefitInfo(C.Structure):
@@ -290,6 +304,12 @@ PROTOTYPES = {
     "bdpt_skinned_buffers": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "bdpt_host_skin": (C.c_int, [C.POINTER(SkinDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdpt_test_skin_kernel": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bdpt_set_morph": (C.c_int, [C.c_void_p, C.POINTER(MorphDesc)]),
+    "bdpt_update_morphed": (C.c_int, [C.c_void_p, C.POINTER(MorphUpdate), C.c_void_p]),
+    "bdpt_morphed_buffers": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "bdpt_host_morph": (C.c_int, [C.POINTER(MorphDesc), C.POINTER(SkinDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "bdpt_test_morph_kernel": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "bdpt_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(TraceDesc), C.c_void_p]),
     "bdpt_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(GBufferParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdpt_shade_hits": (C.c_int, [C.c_void_p, C.POINTER(ShadeDesc), C.c_void_p]),

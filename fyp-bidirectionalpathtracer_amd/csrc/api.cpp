@@ -104,6 +104,13 @@ void freePool(std::vector<void*>& pool) {
   pool.clear();
 }
 // (the device is idle, or the caller has synchronised it)
+void dropMorph(bdpt_ctx* c) {
+  freePool(c->morphAllocs);
+  c->haveMorph = false;
+  c->morph = MorphDev{};
+  c->morphWeights = nullptr;
+}
+// (the device is idle, or the caller has synchronised it)
 void freeLightGroups(bdpt_ctx* c) {
   if (c->groupSplat) (void)hipFree(c->groupSplat);
   if (c->groupLightIdx) (void)hipFree(c->groupLightIdx);
@@ -400,6 +407,7 @@ void bdpt_destroy(bdpt_ctx* c) {
   freeBmfrHistory(c->bmfrPlanes);
   freePool(c->sceneAllocs);
   freePool(c->skinAllocs);
+  freePool(c->morphAllocs);
   freePool(c->frameAllocs);
   if (c->evCreated)
     for (int i = 0; i <= kMaxStages; i++) (void)hipEventDestroy(c->ev[i]);
@@ -500,6 +508,7 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
   c->haveSkin = false;
   c->skin = SkinDev{};
   c->skinPalette[0] = c->skinPalette[1] = nullptr;
+  dropMorph(c);
   freeLightGroups(c);
   c->haveScene = false;
   c->S = SceneDev{};
@@ -1047,6 +1056,7 @@ int bdpt_set_skin(bdpt_ctx* c, const bdpt_skin_desc* d) {
     K.numVertices = d->numVertices;
     K.numBones = d->numBones;
   }
+  dropMorph(c);  // (its base and its outputs were this skin's, or it had none: scene, skin, morph is the order)
   freePool(c->skinAllocs);
   c->skinAllocs = std::move(pool);
   c->skin = K;
@@ -1123,6 +1133,281 @@ int bdpt_test_skin_kernel(bdpt_ctx* c, uint32_t path, void* stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = orderAfterLast(c, st)) return rc;
   launchSkin(c->skin, c->skinPalette[0], c->skin.nrm ? c->skinPalette[1] : nullptr, (int)path, st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
+
+// ---- morph targets: bdpt_set_morph / bdpt_update_morphed (morph.hip) and the same arithmetic on the host ----
+namespace {
+// The checks of a bdpt_morph_desc.  haveSkin: the base is a skin's rest pose, which has normals / bitangents where
+// skinN / skinB; `what` prefixes the message.
+int checkMorphDesc(bdpt_ctx* c, const bdpt_morph_desc* d, bool haveSkin, bool skinN, bool skinB, const char* what) {
+  const std::string w(what);
+  if (!d->targetStart || !d->vertex || !d->dPositions || d->reserved[0] || d->reserved[1] || d->numTargets == 0) {
+    fail(c, w + ": targetStart, vertex and dPositions are required, numTargets >= 1 and reserved 0");
+    return BDPT_E_INVALID;
+  }
+  if (d->numTargets > BDPT_MAX_MORPH_TARGETS) {
+    fail(c, w + ": more than BDPT_MAX_MORPH_TARGETS targets");
+    return BDPT_E_LIMIT;
+  }
+  if (haveSkin) {
+    if (d->positions || d->normals || d->bitangents) {
+      fail(c, w + ": the base is the skin's rest pose: positions, normals and bitangents must be NULL");
+      return BDPT_E_INVALID;
+    }
+  } else if (!d->positions) {
+    fail(c, w + ": positions (the base pose) are required without a skin");
+    return BDPT_E_INVALID;
+  }
+  if ((d->dNormals && !(haveSkin ? skinN : d->normals != nullptr)) || (d->dBitangents && !(haveSkin ? skinB : d->bitangents != nullptr))) {
+    fail(c, w + ": deltas for a stream the base lacks");
+    return BDPT_E_INVALID;
+  }
+  if (d->targetStart[0] != 0) {
+    fail(c, w + ": targetStart[0] is not 0");
+    return BDPT_E_INVALID;
+  }
+  for (uint32_t t = 0; t < d->numTargets; t++)
+    if (d->targetStart[t + 1] < d->targetStart[t]) {
+      fail(c, w + ": targetStart decreases");
+      return BDPT_E_INVALID;
+    }
+  const size_t ne = d->targetStart[d->numTargets];
+  if (ne >= ((size_t)1 << 31)) {
+    fail(c, w + ": 2^31 entries or more");
+    return BDPT_E_LIMIT;
+  }
+  for (uint32_t t = 0; t < d->numTargets; t++)
+    for (size_t e = d->targetStart[t]; e < d->targetStart[t + 1]; e++)
+      if (d->vertex[e] >= d->numVertices || (e > d->targetStart[t] && d->vertex[e] <= d->vertex[e - 1])) {
+        fail(c, w + ": a vertex id >= numVertices, or ids not strictly ascending within a target");
+        return BDPT_E_INVALID;
+      }
+  std::atomic<int> bad{0};
+  const float* deltas[3] = {d->dPositions, d->dNormals, d->dBitangents};
+  const float* base[3] = {d->positions, d->normals, d->bitangents};
+  for (int k = 0; k < 3; k++) {
+    if (deltas[k])
+      hostParallelFor(ne * 3, [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; i++)
+          if (!std::isfinite(deltas[k][i])) bad.store(1);
+      });
+    if (base[k])
+      hostParallelFor((size_t)d->numVertices * 3, [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; i++)
+          if (!std::isfinite(base[k][i])) bad.store(2);
+      });
+  }
+  if (bad.load()) {
+    fail(c, w + (bad.load() == 1 ? ": a delta is not finite" : ": a base value is not finite"));
+    return BDPT_E_INVALID;
+  }
+  return BDPT_OK;
+}
+}  // namespace
+
+int bdpt_host_morph(const bdpt_morph_desc* d, const bdpt_skin_desc* skin, const float* weights, const float* bones, const float* normalBones,
+                    float* outPositions, float* outNormals, float* outBitangents) {
+  if (!d || !weights || !outPositions) return BDPT_E_INVALID;
+  if (skin) {
+    if (skin->numVertices != d->numVertices || !bones || (skin->normals && !normalBones)) return BDPT_E_INVALID;
+    if (int rc = checkSkinDesc(nullptr, skin, "host_morph")) return rc;
+  } else if (bones || normalBones) {
+    return BDPT_E_INVALID;
+  }
+  if (int rc = checkMorphDesc(nullptr, d, skin != nullptr, skin && skin->normals, skin && skin->bitangents, "host_morph")) return rc;
+  const float* baseP = skin ? skin->positions : d->positions;
+  const float* baseN = skin ? skin->normals : d->normals;
+  const float* baseB = skin ? skin->bitangents : d->bitangents;
+  const bool hasN = baseN != nullptr, hasB = baseB != nullptr;
+  if ((hasN && !outNormals) || (hasB && !outBitangents)) return BDPT_E_INVALID;
+  for (uint32_t t = 0; t < d->numTargets; t++)
+    if (!std::isfinite(weights[t])) return BDPT_E_INVALID;
+  const MorphCsr m = morphBuildCsr(d->numVertices, d->numTargets, d->targetStart, d->vertex, d->dPositions, d->dNormals, d->dBitangents);
+  const float* dN = d->dNormals ? m.dNrm.data() : nullptr;
+  const float* dB = d->dBitangents ? m.dBit.data() : nullptr;
+  hostParallelFor(d->numVertices, [&](size_t v0, size_t v1) {
+    float scratch[3];
+    for (size_t v = v0; v < v1; v++) {
+      float p[3], n[3] = {0.0f, 0.0f, 0.0f}, b[3] = {0.0f, 0.0f, 0.0f};
+      for (int k = 0; k < 3; k++) {
+        p[k] = baseP[v * 3 + k];
+        if (hasN) n[k] = baseN[v * 3 + k];
+        if (hasB) b[k] = baseB[v * 3 + k];
+      }
+      morphVertex(m.target.data(), m.dPos.data(), dN, dB, weights, m.start[v], m.start[v + 1], p, n, b);
+      float* op = outPositions + v * 3;
+      float* on = hasN ? outNormals + v * 3 : scratch;
+      float* ob = hasB ? outBitangents + v * 3 : scratch;
+      const float* w = skin ? skin->boneWeights + v * 4 : nullptr;
+      if (!skin || skinIsStatic(w)) {
+        for (int k = 0; k < 3; k++) {
+          op[k] = p[k];
+          if (hasN) on[k] = n[k];
+          if (hasB) ob[k] = b[k];
+        }
+        continue;
+      }
+      const uint16_t* id = skin->boneIds + v * 4;
+      if (hasN && hasB)
+        skinVertex<true, true>(bones, normalBones, id, w, p, n, b, op, on, ob);
+      else if (hasN)
+        skinVertex<true, false>(bones, normalBones, id, w, p, n, b, op, on, ob);
+      else if (hasB)
+        skinVertex<false, true>(bones, normalBones, id, w, p, n, b, op, on, ob);
+      else
+        skinVertex<false, false>(bones, normalBones, id, w, p, n, b, op, on, ob);
+    }
+  });
+  return BDPT_OK;
+}
+
+int bdpt_set_morph(bdpt_ctx* c, const bdpt_morph_desc* d) {
+  if (!c) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "set_morph: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  if (d) {
+    if (d->numVertices != c->numVertices) {
+      fail(c, "set_morph: numVertices differs from the scene's");
+      return BDPT_E_INVALID;
+    }
+    if ((d->bitangents || d->dBitangents) && !c->S.hasBitangents) {
+      fail(c, "set_morph: bitangents given for a scene that has none");
+      return BDPT_E_INVALID;
+    }
+    if (int rc = checkMorphDesc(c, d, c->haveSkin, c->skin.nrm != nullptr, c->skin.bit != nullptr, "set_morph")) return rc;
+  }
+  ENTER(c);
+  if (streamIsCapturing(c->lastStream)) {
+    fail(c, "set_morph: not inside a stream capture (it allocates and synchronises)");
+    return BDPT_E_STATE;
+  }
+  if (d)
+    if (int rc = ensureRefit(c, c->lastStream)) return rc;  // (before the old morph goes: a failure leaves it in place)
+  HIPCHK(c, hipDeviceSynchronize());
+  std::vector<void*> pool;
+  MorphDev M{};
+  float* weights = nullptr;
+  if (d) {
+    const MorphCsr m = morphBuildCsr(d->numVertices, d->numTargets, d->targetStart, d->vertex, d->dPositions, d->dNormals, d->dBitangents);
+    const size_t nv3 = (size_t)d->numVertices * 3;
+    int rc;
+    if ((rc = devUpload(c, pool, &M.start, m.start.data(), m.start.size())) || (rc = devUpload(c, pool, &M.target, m.target.data(), m.target.size())) ||
+        (rc = devUpload(c, pool, &M.dPos, m.dPos.data(), m.dPos.size())) ||
+        (d->dNormals && (rc = devUpload(c, pool, &M.dNrm, m.dNrm.data(), m.dNrm.size()))) ||
+        (d->dBitangents && (rc = devUpload(c, pool, &M.dBit, m.dBit.data(), m.dBit.size()))) ||
+        (rc = devUpload(c, pool, &M.active, m.active.data(), m.active.size())) || (rc = devAlloc(c, pool, &weights, d->numTargets)) ||
+        (d->positions && ((rc = devUpload(c, pool, &M.basePos, d->positions, nv3)) || (rc = devAlloc(c, pool, &M.pos, nv3)))) ||
+        (d->normals && ((rc = devUpload(c, pool, &M.baseNrm, d->normals, nv3)) || (rc = devAlloc(c, pool, &M.nrm, nv3)))) ||
+        (d->bitangents && ((rc = devUpload(c, pool, &M.baseBit, d->bitangents, nv3)) || (rc = devAlloc(c, pool, &M.bit, nv3))))) {
+      freePool(pool);
+      return rc;
+    }
+    // until the first update the morphed streams hold the base, the weights zeros
+    hipError_t e = hipMemset(weights, 0, (size_t)d->numTargets * 4);
+    if (e == hipSuccess && M.pos) e = hipMemcpy(M.pos, M.basePos, nv3 * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && M.nrm) e = hipMemcpy(M.nrm, M.baseNrm, nv3 * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && M.bit) e = hipMemcpy(M.bit, M.baseBit, nv3 * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+      freePool(pool);
+      fail(c, std::string("set_morph: ") + hipGetErrorString(e));
+      return BDPT_E_HIP;
+    }
+    M.numVertices = d->numVertices;
+    M.numTargets = d->numTargets;
+    M.numActive = (uint32_t)m.active.size();
+  }
+  dropMorph(c);
+  c->morphAllocs = std::move(pool);
+  c->morph = M;
+  c->morphWeights = weights;
+  c->haveMorph = d != nullptr;
+  return BDPT_OK;
+}
+
+int bdpt_update_morphed(bdpt_ctx* c, const bdpt_morph_update* u, void* stream) {
+  if (!c || !u) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->haveMorph) {
+    fail(c, c->haveScene ? "update_morphed: no morph (bdpt_set_morph first)" : "update_morphed: no scene (bdpt_set_scene first)");
+    return BDPT_E_STATE;
+  }
+  const MorphDev& M = c->morph;
+  const SkinDev* K = c->haveSkin ? &c->skin : nullptr;
+  const bool needN = K && K->nrm;
+  if (!u->weights || u->numTargets != M.numTargets || u->numBones != (K ? K->numBones : 0u) || (u->bones != nullptr) != (K != nullptr) ||
+      (u->normalBones != nullptr) != needN || u->memory > BDPT_MEMORY_DEVICE || (u->flags & ~BDPT_UPDATE_KEEP_LIGHT_MAPS) || u->reserved[0] ||
+      u->reserved[1]) {
+    fail(c, u->numTargets != M.numTargets ? "update_morphed: numTargets differs from the morph's"
+            : u->numBones != (K ? K->numBones : 0u)
+                ? "update_morphed: numBones differs from the skin's (0 without a skin)"
+                : "update_morphed: weights missing, palettes missing with a skin or given without one, or bad memory / flags / reserved");
+    return BDPT_E_INVALID;
+  }
+  const size_t pal = K ? (size_t)K->numBones * 16 : 0;
+  if (u->memory == BDPT_MEMORY_HOST) {
+    bool finite = true;
+    for (uint32_t t = 0; t < M.numTargets; t++) finite = finite && std::isfinite(u->weights[t]);
+    for (size_t i = 0; i < pal; i++) finite = finite && std::isfinite(u->bones[i]) && (!needN || std::isfinite(u->normalBones[i]));
+    if (!finite) {
+      fail(c, "update_morphed: a weight or a bone matrix element is not finite");
+      return BDPT_E_INVALID;
+    }
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = ensureRefit(c, st)) return rc;  // (bdpt_set_morph made the plan: nothing to do)
+  const float* weights = u->weights;
+  const float* bones = u->bones;
+  const float* nbones = u->normalBones;
+  if (u->memory == BDPT_MEMORY_HOST) {
+    if (streamIsCapturing(st)) {
+      fail(c, "update_morphed: host-pointer weights and palettes are staged through pinned memory: not while capturing");
+      return BDPT_E_STATE;
+    }
+    if (int rc = orderAfterLast(c, st)) return rc;
+    const void* arrays[3] = {weights, bones, nbones};
+    const size_t bytes[3] = {(size_t)M.numTargets * 4, pal * 4, pal * 4};
+    float* dst[3] = {c->morphWeights, c->skinPalette[0], c->skinPalette[1]};
+    if (int rc = stageHostArrays(c, arrays, bytes, 3, dst, st)) return rc;
+    weights = c->morphWeights;
+    bones = K ? c->skinPalette[0] : nullptr;
+    nbones = needN ? c->skinPalette[1] : nullptr;
+  } else {
+    if (int rc = orderAfterLast(c, st)) return rc;
+  }
+  launchMorph(M, K, weights, bones, nbones, kSkinPathAuto, st);
+  if (K) return updateTail(c, K->pos, K->nrm, K->bit, u->flags, st);
+  return updateTail(c, M.pos, M.nrm, M.bit, u->flags, st);
+}
+
+int bdpt_morphed_buffers(bdpt_ctx* c, const float** positions, const float** normals, const float** bitangents) {
+  if (!c || !positions || !normals || !bitangents) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->haveMorph) {
+    fail(c, "morphed_buffers: no morph (bdpt_set_morph first)");
+    return BDPT_E_STATE;
+  }
+  *positions = c->haveSkin ? c->skin.pos : c->morph.pos;
+  *normals = c->haveSkin ? c->skin.nrm : c->morph.nrm;
+  *bitangents = c->haveSkin ? c->skin.bit : c->morph.bit;
+  return BDPT_OK;
+}
+
+int bdpt_test_morph_kernel(bdpt_ctx* c, uint32_t path, void* stream) {
+  if (!c || path > (uint32_t)kSkinPathLds) return BDPT_E_INVALID;
+  if (!c->haveScene || !c->haveMorph) {
+    fail(c, "test_morph_kernel: no morph (bdpt_set_morph first)");
+    return BDPT_E_STATE;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  const SkinDev* K = c->haveSkin ? &c->skin : nullptr;
+  launchMorph(c->morph, K, c->morphWeights, K ? c->skinPalette[0] : nullptr, K && K->nrm ? c->skinPalette[1] : nullptr, (int)path, st);
   HIPCHK(c, hipGetLastError());
   c->lastStream = st;
   return BDPT_OK;

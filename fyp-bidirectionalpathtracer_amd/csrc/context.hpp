@@ -10,6 +10,7 @@
 #include "../../include/bdpt.h"
 #include "bvh.h"
 #include "kernels.h"
+#include "morph.h"
 #include "refit.h"
 #include "skin.h"
 
@@ -129,6 +130,13 @@ struct bdpt_ctx {
   bool haveSkin = false;
   bdpt::SkinDev skin{};
   float* skinPalette[2] = {nullptr, nullptr};
+  // morph targets (bdpt_set_morph): the vertex-major entries, the active-vertex list, without a skin the base and the
+  // morphed streams, and the device weights, in morphAllocs (bdpt_set_morph, bdpt_set_skin and bdpt_set_scene drop
+  // them).  morphWeights: where host-pointer weights are staged.
+  std::vector<void*> morphAllocs;
+  bool haveMorph = false;
+  bdpt::MorphDev morph{};
+  float* morphWeights = nullptr;
   // motion (bdpt_prepare(BDPT_PREPARE_MOTION)): the previous pose, three float4 per primitive, in sceneAllocs (a new scene
   // drops it); bdpt_keep_pose copies the current corners into it
   float4* prevPose = nullptr;

@@ -206,6 +206,22 @@ class TileRenderer:
             keep_for_stream(self.streams[i], (bones, normal_bones))
         self.state["accum"] = 0
 
+    def set_morph(self, target_start, vertex, d_positions, d_normals=None, d_bitangents=None, positions=None, normals=None,
+                  bitangents=None):
+        """The same morph targets for every frame slot's context (Context.set_morph; synchronises)."""
+        for p in self.pipes:
+            p.ctx.set_morph(target_start, vertex, d_positions, d_normals, d_bitangents, positions, normals, bitangents)
+
+    def update_morphed(self, weights, bones=None, normal_bones=None, keep_light_maps=False):
+        """The same weights and pose for every frame slot's context (as update_skinned: each on its slot's stream, in frame
+        order); the running mean restarts.  Every rank applies it: the replicas stay equal."""
+        from . import keep_for_stream
+        for k in range(self.inflight):
+            i = (self.state["frame"] + k) % self.inflight
+            self.pipes[i].ctx.update_morphed(weights, bones, normal_bones, C.c_void_p(self.streams[i].cuda_stream), keep_light_maps)
+            keep_for_stream(self.streams[i], (weights, bones, normal_bones))
+        self.state["accum"] = 0
+
     def set_lights(self, lights):
         """Moved lights for every frame slot's context (as update_geometry); the running mean restarts."""
         for k in range(self.inflight):

@@ -523,6 +523,81 @@ int bdpt_skinned_buffers(bdpt_ctx* ctx, const float** positions, const float** n
 int bdpt_host_skin(const bdpt_skin_desc* desc, const float* bones, const float* normalBones, float* outPositions, float* outNormals,
                    float* outBitangents);
 
+/* ---- Morph targets: blend-shape weights ahead of skinning and the refit ----
+ * bdpt_set_morph gives the context per-target sparse vertex deltas; bdpt_update_morphed then takes the frame's weights
+ * (one float per target) and, for a context with a skin, the frame's bone palettes, forms every vertex's morphed values,
+ * skins them in the same registers where there is a skin, and does what bdpt_update_geometry does with the result: the
+ * refit, the area-light table's refresh, the bitangent copy, the light maps' re-trace unless
+ * BDPT_UPDATE_KEEP_LIGHT_MAPS.  Ordering is bdpt_update_geometry's.  The order of set-up calls is scene, skin, morph:
+ * bdpt_set_skin (a NULL desc included) and bdpt_set_scene drop the morph.
+ *
+ * Base pose.  With a skin the base is the skin's rest pose: positions, normals and bitangents of the desc must be NULL,
+ * and dNormals / dBitangents are allowed only for streams the skin has.  Without a skin `positions` is required;
+ * normals / bitangents are optional, NULL meaning that an update leaves that stream alone, as bdpt_update_geometry
+ * does, and the matching delta array must then be NULL too.
+ *
+ * Arithmetic: fp32, no contraction, exactly in this order.  For vertex v, every morphed stream and every component c:
+ *   x = base[v][c]
+ *   for every target t in ascending order that has an entry e for v and whose weight is not zero (either sign):
+ *     x = x + weights[t] * d[e][c]                    (one rounding for the product, one for the sum)
+ * A zero weight skips the term by definition (x + 0*d would turn a -0.0 into +0.0), so a vertex without entries, or
+ * with only zero-weight entries, keeps its base bits exactly.  With a skin the morphed position / normal / bitangent
+ * then take the place of the rest values in the skinning arithmetic above, which is unchanged; a static vertex (all four
+ * bone weights zero) outputs its morphed values.  Nothing is renormalised.  Hence with a skin and all weights zero
+ * bdpt_update_morphed leaves exactly the streams and records bdpt_update_skinned leaves for the same palettes.
+ *
+ * bdpt_set_morph synchronises and allocates everything a morphed update needs (the vertex-major copy of the entries,
+ * the device weights, without a skin the base and the morphed streams, which hold the base until the first update, and
+ * the refit plan); not inside a stream capture (BDPT_E_STATE).  After it a BDPT_MEMORY_DEVICE bdpt_update_morphed
+ * neither allocates nor synchronises and can be captured into a hipGraph; weights and palettes must stay valid until the
+ * stream reaches the update, and their finiteness is the caller's responsibility.  BDPT_MEMORY_HOST weights and palettes
+ * are checked for finiteness and staged before the call returns; inside a capture they give BDPT_E_STATE.
+ * bdpt_update_skinned and bdpt_update_geometry stay usable and unchanged on a context that has a morph; the former
+ * ignores the morph.  With a skin the outputs are the skin's own skinned streams, so bdpt_skinned_buffers and
+ * bdpt_morphed_buffers agree.
+ * Errors (nothing is enqueued; scene, skin and morph stay as they were): no scene, bdpt_update_morphed /
+ * bdpt_morphed_buffers without a morph, bdpt_set_morph inside a capture BDPT_E_STATE; a NULL argument, numVertices /
+ * numTargets / numBones not matching, numTargets of 0, a non-zero reserved, unknown flags or memory, targetStart[0] != 0
+ * or targetStart decreasing, a vertex id >= numVertices or ids not strictly ascending within a target, a delta, base value
+ * or host weight (or host bone element) that is not finite, base pointers given with a skin or positions missing without
+ * one, deltas for a stream the base lacks, bitangents for a scene without any, palettes missing with a skin or given
+ * without one BDPT_E_INVALID; numTargets above BDPT_MAX_MORPH_TARGETS, 2^31 entries or more BDPT_E_LIMIT. */
+#define BDPT_MAX_MORPH_TARGETS 1024
+typedef struct bdpt_morph_desc { /* all HOST pointers, copied before the call returns */
+  uint32_t numVertices;          /* must equal the scene's */
+  uint32_t numTargets;           /* 1 .. BDPT_MAX_MORPH_TARGETS */
+  const uint32_t* targetStart;   /* numTargets + 1, non-decreasing, [0] = 0: target t owns entries [targetStart[t], targetStart[t+1]) */
+  const uint32_t* vertex;        /* per entry: vertex id, strictly ascending inside a target */
+  const float* dPositions;       /* per entry x 3, required, finite */
+  const float* dNormals;         /* per entry x 3, or NULL: normals are not morphed */
+  const float* dBitangents;      /* per entry x 3, or NULL; only for a scene that has bitangents */
+  const float* positions;        /* base pose, numVertices x 3: required without a skin, NULL with one */
+  const float* normals;          /* base pose or NULL */
+  const float* bitangents;       /* base pose or NULL */
+  uint32_t reserved[2];          /* 0 */
+} bdpt_morph_desc;
+int bdpt_set_morph(bdpt_ctx* ctx, const bdpt_morph_desc* desc); /* NULL desc drops the morph */
+typedef struct bdpt_morph_update {
+  const float* weights;     /* numTargets */
+  const float* bones;       /* required iff the context has a skin, else NULL: as bdpt_skin_update */
+  const float* normalBones; /* required iff that skin has normals, else NULL */
+  uint32_t numTargets;      /* must equal the morph's */
+  uint32_t numBones;        /* must equal the skin's; 0 without a skin */
+  uint32_t memory;          /* BDPT_MEMORY_HOST / BDPT_MEMORY_DEVICE, of weights and palettes alike */
+  uint32_t flags;           /* BDPT_UPDATE_KEEP_LIGHT_MAPS or 0 */
+  uint32_t reserved[2];     /* 0 */
+} bdpt_morph_update;
+int bdpt_update_morphed(bdpt_ctx* ctx, const bdpt_morph_update* upd, void* stream);
+/* device pointers of the streams a morphed update writes (with a skin: the skinned streams; NULL for a stream the base
+ * lacks); valid until bdpt_set_morph / bdpt_set_skin / bdpt_set_scene. */
+int bdpt_morphed_buffers(bdpt_ctx* ctx, const float** positions, const float** normals, const float** bitangents);
+/* host-only, no context: the same arithmetic on the CPU, the same code as the kernel's.  `skin`: the skin whose rest pose
+ * is the base (the desc's base pointers NULL, bones required, normalBones iff it has normals), or NULL (the desc's own
+ * base; bones and normalBones NULL).  outNormals / outBitangents are required iff the base has the stream.  The same desc
+ * checks and codes as above; weights are checked for finiteness, palettes are not. */
+int bdpt_host_morph(const bdpt_morph_desc* desc, const bdpt_skin_desc* skin, const float* weights, const float* bones,
+                    const float* normalBones, float* outPositions, float* outNormals, float* outBitangents);
+
 /* ---- Ray queries: a caller's own rays against the scene ----
  * bdpt_trace_rays         TraceRay from a caller's own ray-generation shader: ambient occlusion
  *                         (CommonPasses/Data/CommonPasses/aoTracing.rt.hlsl:112), shadow rays
@@ -1330,6 +1405,12 @@ int bdpt_test_area_light_sample(bdpt_ctx* ctx, uint32_t mode, const uint32_t* st
  * gather, 2: the LDS-staged palette (where the palette is small enough for it, else the gather).  Errors: no skin
  * BDPT_E_STATE, path > 2 BDPT_E_INVALID. */
 int bdpt_test_skin_kernel(bdpt_ctx* ctx, uint32_t path, void* stream);
+/* Morph measurement hook: the morph kernel of bdpt_update_morphed alone, enqueued on `stream` behind the context's
+ * previous call, with the context's device weights and palettes as the last BDPT_MEMORY_HOST update staged them (no
+ * refit: the scene is left as it was, the output streams are rewritten).  path as bdpt_test_skin_kernel's: 0 the path
+ * bdpt_update_morphed takes, 1 the global-memory palette gather, 2 the LDS-staged palette (with a skin whose palette is
+ * small enough for it, else the gather).  Errors: no morph BDPT_E_STATE, path > 2 BDPT_E_INVALID. */
+int bdpt_test_morph_kernel(bdpt_ctx* ctx, uint32_t path, void* stream);
 
 #ifdef __cplusplus
 }
