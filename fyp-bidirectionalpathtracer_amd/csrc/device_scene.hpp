@@ -26,12 +26,18 @@ BD void texelRow(const uint8_t* px, uint32_t w, int iy, int ix0, int ix1, uint32
   b = (uint32_t)(q >> 32);
   if (ix1 != ix0 + 1) b = row[ix1];
 }
-BD f4 texel(const SceneDev& S, const TexDev& t, uint32_t p) {  // p: the RGBA8 texel, R in the low byte
+// The sRGB decode table comes in as `srgb`, a pointer type of the caller's choosing: SceneConst::srgbLut in global memory
+// (globalSrgb) for every kernel but the walk, which serves the lookups from its own copy in LDS (ldsF32*: twelve fully
+// divergent 4-byte loads per bilinear sample either way, but an LDS read does not queue at the CU's vector-memory address unit).
+typedef __attribute__((address_space(3))) const float ldsF32;
+BD const float* globalSrgb(const SceneDev& S) { return S.sc->srgbLut; }
+template <class Lut>
+BD f4 texel(Lut srgb, const TexDev& t, uint32_t p) {  // p: the RGBA8 texel, R in the low byte
   f4 r;
   if (t.srgb) {
-    r.x = S.sc->srgbLut[p & 0xffu];
-    r.y = S.sc->srgbLut[(p >> 8) & 0xffu];
-    r.z = S.sc->srgbLut[(p >> 16) & 0xffu];
+    r.x = srgb[p & 0xffu];
+    r.y = srgb[(p >> 8) & 0xffu];
+    r.z = srgb[(p >> 16) & 0xffu];
   } else {
     r.x = (float)(p & 0xffu) / 255.0f;
     r.y = (float)((p >> 8) & 0xffu) / 255.0f;
@@ -41,7 +47,8 @@ BD f4 texel(const SceneDev& S, const TexDev& t, uint32_t p) {  // p: the RGBA8 t
   return r;
 }
 // linear filter, wrap addressing, mip 0 (sampler: SharedUtils/SceneLoaderWrapper.cpp:65-68)
-BD f4 sampleBilinearT(const SceneDev& S, const TexDev& t, float u, float v) {
+template <class Lut>
+BD f4 sampleBilinearT(Lut srgb, const TexDev& t, float u, float v) {
   float x = u * (float)t.w - 0.5f;
   float y = v * (float)t.h - 0.5f;
   float x0 = floorf(x), y0 = floorf(y);
@@ -51,22 +58,17 @@ BD f4 sampleBilinearT(const SceneDev& S, const TexDev& t, float u, float v) {
   uint32_t p00, p10, p01, p11;
   texelRow(t.px, t.w, iy0, ix0, ix1, p00, p10);
   texelRow(t.px, t.w, iy1, ix0, ix1, p01, p11);
-  f4 t00 = texel(S, t, p00), t10 = texel(S, t, p10);
-  f4 t01 = texel(S, t, p01), t11 = texel(S, t, p11);
+  f4 t00 = texel(srgb, t, p00), t10 = texel(srgb, t, p10);
+  f4 t01 = texel(srgb, t, p01), t11 = texel(srgb, t, p11);
   return lerp4(lerp4(t00, t10, fx), lerp4(t01, t11, fx), fy);
 }
-BD f4 sampleBilinear(const SceneDev& S, int texId, float u, float v) { return sampleBilinearT(S, S.textures[texId], u, v); }
-// Falcor ShadingUtils/Shading.slang:88-94
-BD f4 sampleTexture(const SceneDev& S, int texId, float u, float v, f4 factor, uint32_t mode) {
+// Falcor ShadingUtils/Shading.slang:88-94, with the texture's descriptor already fetched (SceneDev::matTex: fetched beside
+// the material record, not after it)
+template <class Lut>
+BD f4 sampleTextureT(Lut srgb, const TexDev& t, int texId, float u, float v, f4 factor, uint32_t mode) {
   if (mode == BDPT_CHANNEL_UNUSED) return f4{0, 0, 0, 0};
   if (mode == BDPT_CHANNEL_CONST || texId < 0) return factor;
-  return sampleBilinear(S, texId, u, v);
-}
-// the same with the texture's descriptor already fetched (SceneDev::matTex: fetched beside the material record, not after it)
-BD f4 sampleTextureT(const SceneDev& S, const TexDev& t, int texId, float u, float v, f4 factor, uint32_t mode) {
-  if (mode == BDPT_CHANNEL_UNUSED) return f4{0, 0, 0, 0};
-  if (mode == BDPT_CHANNEL_CONST || texId < 0) return factor;
-  return sampleBilinearT(S, t, u, v);
+  return sampleBilinearT(srgb, t, u, v);
 }
 
 struct MatDev {
@@ -205,9 +207,9 @@ struct Shading {
 };
 // getVertexAttributes (Falcor ShadingUtils/Raytracing.slang:60-106) + simplePrepareShadingData
 // (BDPT/BDPTUtils.hlsli:2-52); NMAP adds applyNormalMap for the primary hit
-// (Falcor ShadingUtils/Shading.slang:135-157, 189-259).
-template <bool NMAP>
-BD Shading shadeHit(const SceneDev& S, uint32_t prim, float bu, float bv, f3 camPosW) {
+// (Falcor ShadingUtils/Shading.slang:135-157, 189-259).  `srgb`: where texel() reads the sRGB table.
+template <bool NMAP, class Lut>
+BD Shading shadeHitLut(const SceneDev& S, Lut srgb, uint32_t prim, float bu, float bv, f3 camPosW) {
   const float4* r = S.shade + (size_t)prim * kShadeRecF4;
   const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4], r5 = r[5], r6 = r[6];
   const float b0 = 1.0f - bu - bv;
@@ -232,12 +234,12 @@ BD Shading shadeHit(const SceneDev& S, uint32_t prim, float bu, float bv, f3 cam
   // the descriptors of the material's base, specular and emissive textures, fetched beside the material record
   const TexDev tBase = S.matTex[(size_t)matId * 4], tSpec = S.matTex[(size_t)matId * 4 + 1], tEmis = S.matTex[(size_t)matId * 4 + 2];
   Shading sd;
-  f4 base = sampleTextureT(S, tBase, m.texBase, u, v, m.baseColor, BDPT_FLAG_DIFFUSE_TYPE(m.flags));
+  f4 base = sampleTextureT(srgb, tBase, m.texBase, u, v, m.baseColor, BDPT_FLAG_DIFFUSE_TYPE(m.flags));
   sd.opacity = m.baseColor.w;
   sd.posW = posW;
   sd.V = normalize(camPosW - posW);
   sd.N = normalize(normalW);
-  f4 spec = sampleTextureT(S, tSpec, m.texSpec, u, v, m.specular, BDPT_FLAG_SPECULAR_TYPE(m.flags));
+  f4 spec = sampleTextureT(srgb, tSpec, m.texSpec, u, v, m.specular, BDPT_FLAG_SPECULAR_TYPE(m.flags));
   f3 baseRgb = mk(base.x, base.y, base.z);
   if (BDPT_FLAG_SHADING_MODEL(m.flags) == BDPT_SHADING_MODEL_METAL_ROUGH) {
     sd.diffuse = lerp3(baseRgb, mk(0), spec.z);
@@ -250,7 +252,7 @@ BD Shading shadeHit(const SceneDev& S, uint32_t prim, float bu, float bv, f3 cam
   }
   sd.linearRoughness = maxf(0.08f, sd.linearRoughness);
   sd.roughness = sd.linearRoughness * sd.linearRoughness;
-  f4 em = sampleTextureT(S, tEmis, m.texEmis, u, v, f4{m.emissive.x, m.emissive.y, m.emissive.z, 1.0f}, BDPT_FLAG_EMISSIVE_TYPE(m.flags));
+  f4 em = sampleTextureT(srgb, tEmis, m.texEmis, u, v, f4{m.emissive.x, m.emissive.y, m.emissive.z, 1.0f}, BDPT_FLAG_EMISSIVE_TYPE(m.flags));
   sd.emissive = mk(em.x, em.y, em.z);
   sd.IoR = m.IoR;
   const bool doubleSided = BDPT_FLAG_DOUBLE_SIDED(m.flags) != 0;
@@ -267,7 +269,7 @@ BD Shading shadeHit(const SceneDev& S, uint32_t prim, float bu, float bv, f3 cam
       bitW = normalize(bitW);
       f3 B = normalize(bitW - sd.N * dot(bitW, sd.N));
       f3 T = normalize(cross(B, sd.N));
-      f4 mp = sampleBilinear(S, m.texNorm, u, v);
+      f4 mp = sampleBilinearT(srgb, S.textures[m.texNorm], u, v);
       f3 mapN;
       if (mapType == BDPT_NORMAL_MAP_RGB) {
         mapN = normalize(mk(mp.x, mp.y, mp.z) * 2.0f - mk(1.0f));
@@ -283,6 +285,10 @@ BD Shading shadeHit(const SceneDev& S, uint32_t prim, float bu, float bv, f3 cam
   float NdotV = dot(sd.N, sd.V);
   if (NdotV <= 0.0f && doubleSided) sd.N = -sd.N;
   return sd;
+}
+template <bool NMAP>
+BD Shading shadeHit(const SceneDev& S, uint32_t prim, float bu, float bv, f3 camPosW) {
+  return shadeHitLut<NMAP>(S, globalSrgb(S), prim, bu, bv, camPosW);
 }
 
 // The primary ray of pixel (x, y) of a W x H frame: GBufferRayGen's pinhole / thin-lens camera

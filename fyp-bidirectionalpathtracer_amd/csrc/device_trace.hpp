@@ -435,6 +435,35 @@ BD void waveAddCount(DevCounters* c, int idx, uint32_t n) {
 #ifndef BDPT_NODE_BURST
 #define BDPT_NODE_BURST 3
 #endif
+// Up to BURST node visits of the lane's ray (has: the lane holds one) with KL stack rows in LDS.  A visit raises sp by at
+// most three, and nodeStep's unchecked form writes rows sp .. sp + 2 (ORDER 0 and 1) or sp .. sp + 3 (ORDER 2: four
+// unconditional stores, the last of them a scratch slot above the new sp) — hence its own guards sp <= KL - 3 / KL - 4.  So
+// a lane that starts a burst at sp <= KL - kMargin, kMargin = 3 * BURST (+ 1 for ORDER 2), starts its last visit at
+// sp <= KL - 3 (KL - 4) and never touches row KL.  While that holds for every lane of the wave — one wave-uniform test per
+// burst — the visits run as with every row in LDS, without nodeStep's per-visit overflow tests (which cost the walk 2 % of
+// its time when they ran at every visit: profiles/README.md).  maxSp: deepest stack seen (COUNT).
+template <int ORDER, int KL, int BURST, bool COUNT>
+BD void nodeBurst(const SceneDev& S, TravState& T, int* stk, bool has, uint32_t& nNodes, int& maxSp) {
+  static_assert(ORDER >= 0 && ORDER <= 2, "the margin below is worked out for nodeStep's three child orders");
+  constexpr int kMargin = 3 * BURST + (ORDER == 2 ? 1 : 0);
+  if (KL < kStackEntries && __ballot(has && T.sp > KL - kMargin) != 0ull) {
+    if (has) {
+#pragma unroll 1
+      for (int k = 0; k < BURST && T.cur >= 0; k++) {
+        if (COUNT) nNodes++;
+        nodeStep<ORDER, KL>(S, T, stk);
+        if (COUNT) maxSp = T.sp > maxSp ? T.sp : maxSp;
+      }
+    }
+  } else if (has) {
+#pragma unroll 1
+    for (int k = 0; k < BURST && T.cur >= 0; k++) {
+      if (COUNT) nNodes++;
+      nodeStep<ORDER, kStackEntries>(S, T, stk);
+      if (COUNT) maxSp = T.sp > maxSp ? T.sp : maxSp;
+    }
+  }
+}
 #ifndef BDPT_REFILL_IDLE
 #define BDPT_REFILL_IDLE 16
 #endif
@@ -520,14 +549,7 @@ __global__ __launch_bounds__(kWave) void trace_shadow_kernel(SceneDev S, RayQueu
     // nine tenths of the work — ran with a third of the lanes; a leaf phase after every node visit (if-if) or by
     // majority vote (round 1) paid a 65-instruction triangle test for a handful of lanes per iteration.  Measured on
     // the bench frame: any-hit tracing 7.9 -> 6.7 ms, walk 7.4 -> 6.5 ms (profiles/README.md).
-    if (has) {
-#pragma unroll 1
-      for (int k = 0; k < BDPT_NODE_BURST && T.cur >= 0; k++) {
-        if (COUNT) nNodes++;
-        nodeStep<0, kStackLds>(S, T, stk);
-        if (COUNT) maxSp = T.sp > maxSp ? T.sp : maxSp;
-      }
-    }
+    nodeBurst<0, kStackLds, BDPT_NODE_BURST, COUNT>(S, T, stk, has, nNodes, maxSp);
     const unsigned long long waitMask = __ballot(has && T.cur < 0), nodeMask = __ballot(has && T.cur >= 0);
     const int waitNeed = (__popcll(waitMask | nodeMask) * BDPT_LEAF_WAIT_FRAC8 + 7) >> 3;
     if ((int)__popcll(waitMask) >= waitNeed || nodeMask == 0ull) {

@@ -21,13 +21,20 @@ constexpr int kStackEntries = KSTACK;  // per-lane traversal stack capacity (the
 #define BDPT_STACK_LDS 24
 #endif
 constexpr int kStackLds = BDPT_STACK_LDS < KSTACK ? BDPT_STACK_LDS : KSTACK;
+// The walk kernel keeps BDPT_WALK_STACK_LDS rows in LDS and the rest in the same overflow area: four rows of a wave are
+// exactly the 1 KiB its sRGB table takes (kernels.hip walk_kernel), so its LDS footprint stays 10 KiB per wave.
+#ifndef BDPT_WALK_STACK_LDS
+#define BDPT_WALK_STACK_LDS 28
+#endif
+constexpr int kWalkStackLds = BDPT_WALK_STACK_LDS < KSTACK ? BDPT_WALK_STACK_LDS : KSTACK;
 constexpr int kMaxPersistentPerCU = 32;  // resident one-wave workgroups per CU a persistent grid may use (8 per SIMD)
 // Rows of the per-context stack overflow area (SceneDev::stackOvf).  INVARIANT the area relies on: it is indexed by
 // workgroup and lane only, so no two persistent traversal launches of one context may be resident at once — every
 // launchWalk / launchTraceShadow of a context goes to the caller's stream, the context's second stream only runs
 // generators (api.cpp bdpt_execute, evFork / evJoin), the test hooks synchronise the device first, and launchTraceRays
 // (bdpt_trace_rays) goes to the caller's stream ordered behind everything the context's previous call enqueued.
-constexpr int kStackOvfRows = KSTACK - kStackLds;
+// Rows: what the kernel with the fewest LDS rows needs (each indexes its own entry - rows-in-LDS from row 0).
+constexpr int kStackOvfRows = KSTACK - (kStackLds < kWalkStackLds ? kStackLds : kWalkStackLds);
 constexpr int kShadeRecF4 = 7;  // float4s per triangle shading record (7 used = 112 B)
 constexpr uint32_t kNoRay = 0xFFFFFFFFu;
 // Hot single-word atomics top out near 90 M/s on this chip (MI355X_MICROARCH.md "dequeue"), so
@@ -80,7 +87,7 @@ struct SceneDev {
   uint32_t hasBitangents;
   uint32_t numRecs;
   const float4* alphaRecs;  // 4 per non-opaque triangle (device_scene.hpp alphaTestFails), indexed by BvhTri::aux
-  int* stackOvf;            // overflow rows of the persistent kernels' stacks: [entry - kStackLds][workgroup * 64 + lane]
+  int* stackOvf;            // overflow rows of the persistent kernels' stacks: [entry - rows in LDS][workgroup * 64 + lane]
   uint32_t stackOvfStride;  // lanes per row
   // occluder hints for next-event rays (kernels.hip "Occluder hints"): per point / spot light a cube map of the record
   // index of the nearest triangle in each direction from the light; [light][face][v][u], kNoHint where nothing is seen

@@ -454,10 +454,6 @@ BD uint32_t packPath(uint32_t p, int path, int k) { return p | ((uint32_t)path <
 #ifndef BDPT_WALK_WAVES_PER_EU
 #define BDPT_WALK_WAVES_PER_EU 4
 #endif
-#ifndef BDPT_WALK_STACK_LDS
-#define BDPT_WALK_STACK_LDS kStackEntries
-#endif
-constexpr int kWalkStackLds = BDPT_WALK_STACK_LDS;
 constexpr uint32_t kParkedMiss = 1u << 30;
 // One template for both frames: a MASKED instance takes the MaskDev as its last argument, a plain one an empty struct
 // (M is then all zero).  The body is written here, not in a forced-inline __device__ function: that form compiled to a
@@ -468,6 +464,12 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK
   BDPT_ONE_WAVE_PER_GROUP();
   __shared__ int s_stack[kWalkStackLds * kWave];
   __shared__ uint4 s_pool[kPoolEntries];
+  // the sRGB decode table (SceneConst::srgbLut), which shadeHit's texel lookups read from here
+  __shared__ float s_srgb[256];
+#pragma unroll
+  for (int i = 0; i < 256; i += kWave) s_srgb[i + (int)threadIdx.x] = S.sc->srgbLut[i + (int)threadIdx.x];
+  __syncthreads();
+  ldsF32* const srgb = (ldsF32*)s_srgb;
   const MaskDev& M = maskOf(mask);
   int* stk = s_stack + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63u);
@@ -514,7 +516,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK
         if (prim >= 0) {
           const uint32_t seed = (path == PATH_EYE) ? P.seedE[p] : P.seedL[p];
           const f3 thr = ldPlane3(P, path, k, F_COL, p);
-          Shading sd = shadeHit<false>(S, (uint32_t)prim, __uint_as_float(rec.z), __uint_as_float(rec.w), o);  // V points at WorldRayOrigin()
+          Shading sd = shadeHitLut<false>(S, srgb, (uint32_t)prim, __uint_as_float(rec.z), __uint_as_float(rec.w), o);  // V points at WorldRayOrigin()
           float pdf;
           bool isSpec;
           f3 w = sampleBRDF<GGX>(seed, sd.N, sd.N, sd.V, sd.diffuse, sd.specular, sd.roughness, fromLobe, L, pdf, isSpec);
@@ -657,12 +659,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK
 #if BDPT_WALK_LEAF_WAIT > 0
     // node visits in short bursts; a lane that reaches a leaf (or runs out of stack) waits, and the leaves are intersected
     // once half of the lanes that hold a ray are waiting or no lane can take a node visit (device_trace.hpp, trace_shadow_kernel)
-    if (trav) {
-#pragma unroll 1
-      for (int kk = 0; kk < BDPT_WALK_NODE_BURST && T.cur >= 0; kk++) {
-        if (COUNT) nNodes++;
-        nodeStep<BDPT_WALK_ORDER, kWalkStackLds>(S, T, stk);
-      }
+    {
+      int maxSp = 0;
+      nodeBurst<BDPT_WALK_ORDER, kWalkStackLds, BDPT_WALK_NODE_BURST, COUNT>(S, T, stk, trav, nNodes, maxSp);
     }
     {
       const unsigned long long waitMask = __ballot(trav && T.cur < 0), nodeMask = __ballot(trav && T.cur >= 0);

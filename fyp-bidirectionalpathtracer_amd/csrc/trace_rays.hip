@@ -70,9 +70,10 @@ __global__ __launch_bounds__(kWave) void trace_rays_kernel(SceneDev S, const flo
     if (__ballot(has) == 0ull) break;  // exhausted and every lane retired
 #if BDPT_LEAF_WAIT > 0
     // deferred leaves, as trace_shadow_kernel: node bursts; leaves once BDPT_LEAF_WAIT_FRAC8 eighths of the lanes wait at one
-    if (has) {
-#pragma unroll 1
-      for (int k = 0; k < BDPT_NODE_BURST && T.cur >= 0; k++) nodeStep<(MODE != 2) ? 1 : 0, kStackLds>(S, T, stk);
+    {
+      uint32_t nNodes = 0;
+      int maxSp = 0;
+      nodeBurst<(MODE != 2) ? 1 : 0, kStackLds, BDPT_NODE_BURST, false>(S, T, stk, has, nNodes, maxSp);
     }
     const unsigned long long waitMask = __ballot(has && T.cur < 0), nodeMask = __ballot(has && T.cur >= 0);
     const int waitNeed = (__popcll(waitMask | nodeMask) * BDPT_LEAF_WAIT_FRAC8 + 7) >> 3;

@@ -9,6 +9,19 @@ import json
 import sys
 
 
+def cut_args(name):
+    """the kernel's name without its argument list: cut at the first "(" outside the template arguments"""
+    depth = 0
+    for i, ch in enumerate(name):
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif ch == "(" and depth == 0 and not name.startswith("(anonymous namespace)", i):
+            return name[:i]
+    return name
+
+
 def load(d, counter):
     f = (glob.glob(d + "/*counter_collection.csv") + glob.glob(d + "/*/*counter_collection.csv"))[0]
     tot = collections.defaultdict(float)
@@ -17,7 +30,7 @@ def load(d, counter):
         if r["Counter_Name"] != counter:
             continue
         k = r["Kernel_Name"]
-        k = k[:k.index("(")] if "(" in k else k
+        k = cut_args(k)
         tot[k] += float(r["Counter_Value"]) * 1024.0
         n[k].add(r["Dispatch_Id"])
     return tot, {k: len(v) for k, v in n.items()}

@@ -17,8 +17,21 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def cut_args(name):
+    """the kernel's name without its argument list: cut at the first "(" outside the template arguments"""
+    depth = 0
+    for i, ch in enumerate(name):
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif ch == "(" and depth == 0 and not name.startswith("(anonymous namespace)", i):
+            return name[:i]
+    return name
+
+
 def short(name):
-    name = name[:name.index("(")] if "(" in name else name
+    name = cut_args(name)
     return name.replace("void ", "").replace("bdpt::", "")
 
 

@@ -12,8 +12,21 @@ import csv
 import sys
 
 
+def cut_args(name):
+    """the kernel's name without its argument list: cut at the first "(" outside the template arguments"""
+    depth = 0
+    for i, ch in enumerate(name):
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif ch == "(" and depth == 0 and not name.startswith("(anonymous namespace)", i):
+            return name[:i]
+    return name
+
+
 def short(name):
-    name = name[:name.index("(")] if "(" in name else name
+    name = cut_args(name)
     name = name.replace("void ", "").replace("bdpt::", "")
     return name[:name.index("<")] if "<" in name else name
 
