@@ -541,7 +541,7 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
   };
   lap("validate");
   // Beside the build, on a thread of its own: the per-primitive shading records (3 x (position, normal, uv) + material id,
-  // 112 B) and the uploads that depend on nothing the build produces — while the build's device stages run the host is
+  // 112 B in a 128-byte slot) and the uploads that depend on nothing the build produces — while the build's device stages run the host is
   // idle, and while its host stages run the copy engine is.
   struct SideUploads {
     std::vector<void*> pool;
@@ -1582,7 +1582,6 @@ int resizeRows(bdpt_ctx* c, uint32_t width, uint32_t height, uint32_t maxDepth) 
   }
   if ((rc = devAlloc(c, c->frameAllocs, &P.v, (size_t)2 * P.D1 * NF4 * 4 * np))) return rc;
   if ((rc = devAlloc(c, c->frameAllocs, &P.rayDir, (size_t)6 * np))) return rc;
-  if ((rc = devAlloc(c, c->frameAllocs, &P.seedE, np))) return rc;
   if ((rc = devAlloc(c, c->frameAllocs, &P.seedL, np))) return rc;
   if ((rc = devAlloc(c, c->frameAllocs, &P.eyeLast, np))) return rc;
   if ((rc = devAlloc(c, c->frameAllocs, &P.lightLast, np))) return rc;

@@ -35,7 +35,7 @@ constexpr int kMaxPersistentPerCU = 32;  // resident one-wave workgroups per CU 
 // (bdpt_trace_rays) goes to the caller's stream ordered behind everything the context's previous call enqueued.
 // Rows: what the kernel with the fewest LDS rows needs (each indexes its own entry - rows-in-LDS from row 0).
 constexpr int kStackOvfRows = KSTACK - (kStackLds < kWalkStackLds ? kStackLds : kWalkStackLds);
-constexpr int kShadeRecF4 = 7;  // float4s per triangle shading record (7 used = 112 B)
+constexpr int kShadeRecF4 = 8;  // float4s per triangle shading record: 7 used (112 B), the eighth zero, so that a record is one 128-byte line
 constexpr uint32_t kNoRay = 0xFFFFFFFFu;
 // Hot single-word atomics top out near 90 M/s on this chip (MI355X_MICROARCH.md "dequeue"), so
 // producer and consumer cursors of every queue are sharded over sub-queues, the any-hit trace kernel
@@ -119,8 +119,9 @@ struct PathBuf {
   float* v;            // vertex records: ((path*D1 + k)*Np + p) * NF4 float4s
   float* rayDir;       // planes: (path*3 + axis)*Np + p
   const uint32_t* pix; // tile-local pixel p -> full-frame pixel index y*W + x (the tile's rows, row-major)
-  uint32_t* seedE;     // RNG state the eye walk draws from at every bounce (initRand of the pixel, quirk 1)
-  uint32_t* seedL;     // RNG state after sampleLight
+  // RNG state after sampleLight, where gen_nee's, the gather's and light_query's draws start.  The walks do not read it: the
+  // state a sub-path draws from travels in q0.w of its vertex records (kernels.hip "Path vertices"), the eye walk's too
+  uint32_t* seedL;
   uint8_t* eyeLast;    // last stored eye vertex (ghost included); 0 = pixel has no geometry
   uint8_t* lightLast;  // last stored light vertex (ghost included)
   uint8_t* lightReal;  // number of light vertices produced by hits (takeContribution, BDPTMain.rt.hlsl:144)

@@ -73,20 +73,25 @@ BD bool queueChunk(const uint32_t* count, uint32_t subCap, bool& act, uint32_t& 
 // by pixel.  A lane owns a sub-path, so it reads and writes whole records: six 16-byte accesses that use
 // every byte of the lines they touch, whatever pixel the lane holds (the walk kernel's lanes hold unrelated
 // pixels; the dense kernels' lanes hold consecutive ones and so cover 6 KiB contiguously per wave).
-//   q0 = pos.xyz, roughness   q1 = N.xyz, isSpecular   q2 = diffuse.xyz, pdfForward
-//   q3 = specular.xyz, -      q4 = colour.xyz, -       q5 = V.xyz, -
+//   q0 = colour.xyz, seed     q1 = pos.xyz, roughness  q2 = N.xyz, isSpecular
+//   q3 = diffuse.xyz, pdfForward   q4 = specular.xyz, -   q5 = V.xyz, -
+// q0 and q1 are what the walk's shading pass reads of vertex k (throughput, RNG state, ray origin): bytes 0..31 of a
+// record, which a 96-byte stride from a 128-byte-aligned base never splits over two 128-byte lines.  seed is the state
+// every bounce of the sub-path draws from by value (quirk 1: constant along it; initRand of the pixel on the eye side,
+// PathBuf::seedL on the light side); init_paths writes it with eye vertex 1 and light vertex 0, the walk copies it into
+// vertex k + 1, a ghost vertex stores 0.
 // ------------------------------------------------------------------------------------------------
 constexpr int kVtxQ = NF4;
 BD float4* vtxPtr(const PathBuf& P, int path, int k, uint32_t p) {
   return reinterpret_cast<float4*>(P.v) + ((size_t)(path * (int)P.D1 + k) * P.Np + p) * kVtxQ;
 }
-BD constexpr int fieldQ(int f) { return f == F_POS ? 0 : f == F_N ? 1 : f == F_DIF ? 2 : f == F_SPEC ? 3 : f == F_COL ? 4 : 5; }
+BD constexpr int fieldQ(int f) { return f == F_COL ? 0 : f == F_POS ? 1 : f == F_N ? 2 : f == F_DIF ? 3 : f == F_SPEC ? 4 : 5; }
 BD f3 ldPlane3(const PathBuf& P, int path, int k, int f, uint32_t p) {
   const float4 q = vtxPtr(P, path, k, p)[fieldQ(f)];
   return f3{q.x, q.y, q.z};
 }
-BD float ldPlane1(const PathBuf& P, int path, int k, int f, uint32_t p) {  // F_ROUGH, F_ISSPEC, F_PDF: .w of q0, q1, q2
-  const int q = (f == F_ROUGH) ? 0 : (f == F_ISSPEC ? 1 : 2);
+BD float ldPlane1(const PathBuf& P, int path, int k, int f, uint32_t p) {  // F_ROUGH, F_ISSPEC, F_PDF: .w of q1, q2, q3
+  const int q = (f == F_ROUGH) ? 1 : (f == F_ISSPEC ? 2 : 3);
   return reinterpret_cast<const float*>(vtxPtr(P, path, k, p))[q * 4 + 3];
 }
 
@@ -95,6 +100,7 @@ struct Vtx {
   float rough;
   bool isSpec;
   float pdf;
+  uint32_t seed;  // RNG state of the sub-path (walk_kernel draws from it); 0 in a ghost vertex
 };
 BD Vtx zeroVtx() {
   Vtx v;
@@ -102,13 +108,14 @@ BD Vtx zeroVtx() {
   v.rough = 0.0f;
   v.isSpec = false;
   v.pdf = 0.0f;
+  v.seed = 0u;
   return v;
 }
 BD void storeVtx(const PathBuf& P, int path, int k, uint32_t p, const Vtx& v) {
   float4* r = vtxPtr(P, path, k, p);
-  const float4 q0 = make_float4(v.pos.x, v.pos.y, v.pos.z, v.rough), q1 = make_float4(v.N.x, v.N.y, v.N.z, v.isSpec ? 1.0f : 0.0f),
-               q2 = make_float4(v.dif.x, v.dif.y, v.dif.z, v.pdf), q3 = make_float4(v.spec.x, v.spec.y, v.spec.z, 0.0f),
-               q4 = make_float4(v.color.x, v.color.y, v.color.z, 0.0f), q5 = make_float4(v.V.x, v.V.y, v.V.z, 0.0f);
+  const float4 q0 = make_float4(v.color.x, v.color.y, v.color.z, __uint_as_float(v.seed)), q1 = make_float4(v.pos.x, v.pos.y, v.pos.z, v.rough),
+               q2 = make_float4(v.N.x, v.N.y, v.N.z, v.isSpec ? 1.0f : 0.0f), q3 = make_float4(v.dif.x, v.dif.y, v.dif.z, v.pdf),
+               q4 = make_float4(v.spec.x, v.spec.y, v.spec.z, 0.0f), q5 = make_float4(v.V.x, v.V.y, v.V.z, 0.0f);
   r[0] = q0;
   r[1] = q1;
   r[2] = q2;
@@ -120,16 +127,16 @@ BD void storeVtx(const PathBuf& P, int path, int k, uint32_t p, const Vtx& v) {
 template <bool GGX = true>
 BD void loadSurf(const PathBuf& P, int path, int k, uint32_t p, Vtx& v) {
   const float4* r = vtxPtr(P, path, k, p);
-  const float4 q0 = r[0], q1 = r[1], q2 = r[2];
-  v.pos = mk(q0.x, q0.y, q0.z);
-  v.N = mk(q1.x, q1.y, q1.z);
-  v.dif = mk(q2.x, q2.y, q2.z);
-  v.pdf = q2.w;
+  const float4 q1 = r[1], q2 = r[2], q3 = r[3];
+  v.pos = mk(q1.x, q1.y, q1.z);
+  v.N = mk(q2.x, q2.y, q2.z);
+  v.dif = mk(q3.x, q3.y, q3.z);
+  v.pdf = q3.w;
   if (GGX) {
-    const float4 q3 = r[3];
-    v.spec = mk(q3.x, q3.y, q3.z);
-    v.rough = q0.w;
-    v.isSpec = q1.w != 0.0f;
+    const float4 q4 = r[4];
+    v.spec = mk(q4.x, q4.y, q4.z);
+    v.rough = q1.w;
+    v.isSpec = q2.w != 0.0f;
   } else {
     v.spec = mk(0);
     v.rough = 0.0f;
@@ -323,7 +330,7 @@ BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, co
       const float roughness = sa * sa;
       const f3 V = normalize(camPos - worldPos);
       uint32_t seed = initRand((uint32_t)pix, F.p.frameCount);
-      P.seedE[p] = seed;  // every eye bounce draws from this state by value (quirk 1)
+      const uint32_t seedEye = seed;  // every eye bounce draws from this state by value (quirk 1)
       f3 outDir;
       float pdf;
       bool isSpec;
@@ -339,6 +346,7 @@ BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, co
       v.rough = roughness;
       v.isSpec = isSpec;
       v.pdf = pdf;
+      v.seed = seedEye;
       storeVtx(P, PATH_EYE, 1, p, v);
       float* rd = P.rayDir + (size_t)(PATH_EYE * 3) * P.Np + p;
       rd[0] = outDir.x;
@@ -367,6 +375,7 @@ BD void initPathsLane(const SceneDev& S, const FrameDev& F, const PathBuf& P, co
         lv.color = ld3(l.intensity);
       }
       lv.pdf = 1.0f / (float)lightsCount;  // lightPath[0].pdfForward, BDPTMain.rt.hlsl:132
+      lv.seed = seed;                      // = seedL below: the state every light bounce draws from
       storeVtx(P, PATH_LIGHT, 0, p, lv);
       float* rl = P.rayDir + (size_t)(PATH_LIGHT * 3) * P.Np + p;
       rl[0] = lightDir.x;
@@ -509,13 +518,16 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK
       if (act) {
         const bool miss = EXT ? (rec.x & kParkedMiss) != 0u : (int)rec.y < 0;
         const int prim = miss ? -1 : (int)rec.y;
-        const f3 o = ldPlane3(P, path, k, F_POS, p);
+        // colour + seed and pos of vertex k: q0, q1 of its record, two adjacent 16-byte loads within one 128-byte line
+        const float4* rk = vtxPtr(P, path, k, p);
+        const float4 qc = rk[0], qp = rk[1];
+        const f3 o = mk(qp.x, qp.y, qp.z);
         // what the eye ray that left vertex k found where it ended (EXT): added to the path's pixel below
         f3 found = mk(0);
         bool haveFound = false;
         if (prim >= 0) {
-          const uint32_t seed = (path == PATH_EYE) ? P.seedE[p] : P.seedL[p];
-          const f3 thr = ldPlane3(P, path, k, F_COL, p);
+          const uint32_t seed = __float_as_uint(qc.w);
+          const f3 thr = mk(qc.x, qc.y, qc.z);
           Shading sd = shadeHitLut<false>(S, srgb, (uint32_t)prim, __uint_as_float(rec.z), __uint_as_float(rec.w), o);  // V points at WorldRayOrigin()
           float pdf;
           bool isSpec;
@@ -530,6 +542,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK
           v.rough = sd.roughness;
           v.isSpec = isSpec;
           v.pdf = pdf;
+          v.seed = seed;
           storeVtx(P, path, k + 1, p, v);
           survive = (k + 2 <= D);  // k + 1 < maxK
           if (EXT && path == PATH_EYE && (F.p.flags & BDPT_PARAM_EMISSIVE_HITS) &&
@@ -541,7 +554,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK
           if (EXT && path == PATH_EYE && (F.p.flags & BDPT_PARAM_ENV_ON_MISS)) {
             const f3 dir = mk(__uint_as_float(rec.y), __uint_as_float(rec.z), __uint_as_float(rec.w));
             const f3 env = F.envMap ? envLookup(F.envMap, F.envW, F.envH, dir) : ld3(F.envColor);
-            found = ldPlane3(P, path, k, F_COL, p) * env;
+            found = mk(qc.x, qc.y, qc.z) * env;
             haveFound = true;
           }
           Vtx g = zeroVtx();
@@ -1005,7 +1018,7 @@ template <bool GGX, int G>
 __global__ __launch_bounds__(kWave) void gen_connect_kernel(SceneDev S, FrameDev F, PathBuf P) {
   BDPT_ONE_WAVE_PER_GROUP();
   constexpr int kPix = kWave / G;
-  __shared__ float4 s_light[kPix][G][4];       // q0..q3 of light vertex g (zeros past the end of the sub-path)
+  __shared__ float4 s_light[kPix][G][4];       // q1..q4 of light vertex g: pos, N, diffuse, specular (zeros past the end of the sub-path)
   __shared__ float4 s_eyePos[kPix][G];         // position of eye vertex g + 1 (zero past the end)
   __shared__ uint8_t s_pair[G * (G - 1) / 2];  // pair ordinal -> (cameraLength << 4) | lightLength, for this launch's depth
   bool act = false;
@@ -1033,10 +1046,10 @@ __global__ __launch_bounds__(kWave) void gen_connect_kernel(SceneDev S, FrameDev
     float4 l0 = make_float4(0, 0, 0, 0), l1 = l0, l2 = l0, l3 = l0;
     if (act && g <= lightLast && g < D) {
       const float4* r = vtxPtr(P, PATH_LIGHT, g, p);
-      l0 = r[0];
-      l1 = r[1];
-      l2 = r[2];
-      if (GGX) l3 = r[3];
+      l0 = r[1];
+      l1 = r[2];
+      l2 = r[3];
+      if (GGX) l3 = r[4];
     }
     s_light[e][g][0] = l0;
     s_light[e][g][1] = l1;

@@ -17,7 +17,7 @@
 
 namespace bdpt {
 
-// 48 of a record's 112 bytes are read (r0, r2, r4), 48 written; w of the copies is 0
+// 48 of a record's 128 bytes are read (r0, r2, r4), 48 written; w of the copies is 0
 __global__ __launch_bounds__(kWave) void keep_pose_kernel(const float4* __restrict__ shade, uint32_t numTris, float4* __restrict__ prevPose) {
   BDPT_ONE_WAVE_PER_GROUP();
   const uint32_t i = blockIdx.x * kWave + threadIdx.x;

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void k_refit_regions(const BvhRefitNode* __res
   bvhPieceRegionsOfNode(nodes[i], recs, region);
 }
 
-// positions (and normals) of the 112-byte shading records (api.cpp setSceneImpl): three (position, normal, uv) vertices
+// positions (and normals) of the 128-byte shading records (api.cpp setSceneImpl): three (position, normal, uv) vertices
 // + material id; the uvs and the material id stay
 __global__ __launch_bounds__(256) void k_refit_shade(float4* __restrict__ shade, const uint32_t* __restrict__ idx, const float* __restrict__ pos,
                                                     const float* __restrict__ nrm, uint32_t numTris) {
