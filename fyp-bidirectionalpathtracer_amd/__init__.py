@@ -193,6 +193,29 @@ class Context:
     def set_camera(self, cam):
         self._check(self._lib.bdpt_set_camera(self._h, C.byref(cam)), "bdpt_set_camera")
 
+    def _update_inputs(self, what, names, arrays):
+        """(memory, pointers, sizes, keep) of an update's optional arrays: GPU torch tensors as they are, numpy arrays and
+        CPU tensors as contiguous float32 copies, which `keep` holds until the call has returned.  `names` lists the
+        arguments for the message of a mixture."""
+        given = [a for a in arrays if a is not None]
+        on_gpu = [bool(getattr(a, "is_cuda", False)) for a in given]
+        if any(on_gpu):
+            if not all(on_gpu):
+                every = "both" if len(arrays) == 2 else "all"
+                raise BdptError(f"{what}: {names} must {every} be GPU tensors or {every} host arrays")
+            for a in given:
+                if a.device.index != self.device:
+                    raise BdptError(f"{what}: a tensor on {a.device} for the context of device {self.device}")
+                if not a.is_contiguous() or str(a.dtype) != "torch.float32":
+                    raise BdptError(f"{what}: device inputs must be contiguous float32 tensors")
+            return (abi.MEMORY_DEVICE, [None if a is None else a.data_ptr() for a in arrays],
+                    [None if a is None else a.numel() for a in arrays], arrays)
+        import numpy as np
+        # (a CPU torch tensor is host memory: its numpy view, never its address as a device pointer)
+        keep = [None if a is None else np.ascontiguousarray(a.detach().numpy() if hasattr(a, "detach") else a, np.float32).reshape(-1)
+                for a in arrays]
+        return abi.MEMORY_HOST, [None if a is None else a.ctypes.data for a in keep], [None if a is None else a.size for a in keep], keep
+
     def update_geometry(self, positions, normals=None, bitangents=None, stream=None, keep_light_maps=False):
         """bdpt_update_geometry: new vertex positions (and normals / bitangents) for the scene, the tree refitted in place.
         GPU torch tensors take the device path: all of them must be contiguous float32 tensors on this context's device,
@@ -200,28 +223,7 @@ class Context:
         arrays and CPU torch tensors take the host path: checked for finiteness and copied before this returns.  All
         arrays are numVertices x 3 float32.  Nothing is enqueued when an argument is refused."""
         u = abi.GeometryUpdate()
-        arrays = [positions, normals, bitangents]
-        given = [a for a in arrays if a is not None]
-        on_gpu = [bool(getattr(a, "is_cuda", False)) for a in given]
-        if any(on_gpu):
-            if not all(on_gpu):
-                raise BdptError("update_geometry: positions, normals and bitangents must all be GPU tensors or all host arrays")
-            for a in given:
-                if a.device.index != self.device:
-                    raise BdptError(f"update_geometry: a tensor on {a.device} for the context of device {self.device}")
-                if not a.is_contiguous() or str(a.dtype) != "torch.float32":
-                    raise BdptError("update_geometry: device inputs must be contiguous float32 tensors")
-            u.memory = abi.MEMORY_DEVICE
-            ptrs = [None if a is None else a.data_ptr() for a in arrays]
-            sizes = [None if a is None else a.numel() for a in arrays]
-        else:
-            import numpy as np
-            u.memory = abi.MEMORY_HOST
-            # (a CPU torch tensor is host memory: its numpy view, never its address as a device pointer)
-            arrays = [None if a is None else np.ascontiguousarray(a.detach().numpy() if hasattr(a, "detach") else a, np.float32).reshape(-1)
-                      for a in arrays]
-            ptrs = [None if a is None else a.ctypes.data for a in arrays]
-            sizes = [None if a is None else a.size for a in arrays]
+        u.memory, ptrs, sizes, _keep = self._update_inputs("update_geometry", "positions, normals and bitangents", [positions, normals, bitangents])
         n = sizes[0] // 3
         if sizes[0] != 3 * n or any(m is not None and m != 3 * n for m in sizes[1:]):
             raise BdptError("update_geometry: positions, normals and bitangents must be numVertices x 3 each")
@@ -261,27 +263,7 @@ class Context:
         and the tree refitted.  GPU torch tensors take the device path and numpy arrays / CPU tensors the host path, by
         the rules of update_geometry.  Nothing is enqueued when an argument is refused."""
         u = abi.SkinUpdate()
-        arrays = [bones, normal_bones]
-        given = [a for a in arrays if a is not None]
-        on_gpu = [bool(getattr(a, "is_cuda", False)) for a in given]
-        if any(on_gpu):
-            if not all(on_gpu):
-                raise BdptError("update_skinned: bones and normal_bones must both be GPU tensors or both host arrays")
-            for a in given:
-                if a.device.index != self.device:
-                    raise BdptError(f"update_skinned: a tensor on {a.device} for the context of device {self.device}")
-                if not a.is_contiguous() or str(a.dtype) != "torch.float32":
-                    raise BdptError("update_skinned: device inputs must be contiguous float32 tensors")
-            u.memory = abi.MEMORY_DEVICE
-            ptrs = [None if a is None else a.data_ptr() for a in arrays]
-            sizes = [None if a is None else a.numel() for a in arrays]
-        else:
-            import numpy as np
-            u.memory = abi.MEMORY_HOST
-            arrays = [None if a is None else np.ascontiguousarray(a.detach().numpy() if hasattr(a, "detach") else a, np.float32).reshape(-1)
-                      for a in arrays]
-            ptrs = [None if a is None else a.ctypes.data for a in arrays]
-            sizes = [None if a is None else a.size for a in arrays]
+        u.memory, ptrs, sizes, _keep = self._update_inputs("update_skinned", "bones and normal_bones", [bones, normal_bones])
         n = sizes[0] // 16
         if sizes[0] != 16 * n or (sizes[1] is not None and sizes[1] != 16 * n):
             raise BdptError("update_skinned: bones and normal_bones must be numBones x 16 each")
@@ -305,18 +287,23 @@ class Context:
     def read_skinned(self, stream=None):
         """The skinned streams copied to the host (numVertices x 3 float32 each, None for a stream the skin lacks); waits
         for `stream`."""
+        return self._read_streams("read_skinned", self.skinned_buffers, "_skin_vertices", stream)
+
+    def _read_streams(self, what, buffers, vertices, stream):
+        """read_skinned / read_morphed: the device streams `buffers()` names copied to the host, getattr(self, vertices)
+        x 3 float32 each; waits for `stream`."""
         import numpy as np
         self.sync(stream)
-        nv = self._skin_vertices
+        nv = getattr(self, vertices)
         hip = C.CDLL("libamdhip64.so")
         out = []
-        for ptr in self.skinned_buffers():
+        for ptr in buffers():
             if ptr is None:
                 out.append(None)
                 continue
             a = np.empty((nv, 3), np.float32)
             if hip.hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(ptr), C.c_size_t(a.nbytes), 2) != 0:
-                raise BdptError("read_skinned: hipMemcpy failed")
+                raise BdptError(f"{what}: hipMemcpy failed")
             out.append(a)
         return tuple(out)
 
@@ -361,27 +348,7 @@ class Context:
         u = abi.MorphUpdate()
         if weights is None:
             raise BdptError("update_morphed: weights are required")
-        arrays = [weights, bones, normal_bones]
-        given = [a for a in arrays if a is not None]
-        on_gpu = [bool(getattr(a, "is_cuda", False)) for a in given]
-        if any(on_gpu):
-            if not all(on_gpu):
-                raise BdptError("update_morphed: weights, bones and normal_bones must all be GPU tensors or all host arrays")
-            for a in given:
-                if a.device.index != self.device:
-                    raise BdptError(f"update_morphed: a tensor on {a.device} for the context of device {self.device}")
-                if not a.is_contiguous() or str(a.dtype) != "torch.float32":
-                    raise BdptError("update_morphed: device inputs must be contiguous float32 tensors")
-            u.memory = abi.MEMORY_DEVICE
-            ptrs = [None if a is None else a.data_ptr() for a in arrays]
-            sizes = [None if a is None else a.numel() for a in arrays]
-        else:
-            import numpy as np
-            u.memory = abi.MEMORY_HOST
-            arrays = [None if a is None else np.ascontiguousarray(a.detach().numpy() if hasattr(a, "detach") else a, np.float32).reshape(-1)
-                      for a in arrays]
-            ptrs = [None if a is None else a.ctypes.data for a in arrays]
-            sizes = [None if a is None else a.size for a in arrays]
+        u.memory, ptrs, sizes, _keep = self._update_inputs("update_morphed", "weights, bones and normal_bones", [weights, bones, normal_bones])
         nb = 0 if sizes[1] is None else sizes[1] // 16
         if sizes[0] == 0 or (sizes[1] is not None and sizes[1] != 16 * nb) or (sizes[2] is not None and sizes[2] != 16 * nb):
             raise BdptError("update_morphed: weights must be numTargets floats, bones and normal_bones numBones x 16 each "
@@ -406,20 +373,7 @@ class Context:
     def read_morphed(self, stream=None):
         """The streams a morphed update writes copied to the host (numVertices x 3 float32 each, None for a stream the
         base lacks); waits for `stream`."""
-        import numpy as np
-        self.sync(stream)
-        nv = self._morph_vertices
-        hip = C.CDLL("libamdhip64.so")
-        out = []
-        for ptr in self.morphed_buffers():
-            if ptr is None:
-                out.append(None)
-                continue
-            a = np.empty((nv, 3), np.float32)
-            if hip.hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(ptr), C.c_size_t(a.nbytes), 2) != 0:
-                raise BdptError("read_morphed: hipMemcpy failed")
-            out.append(a)
-        return tuple(out)
+        return self._read_streams("read_morphed", self.morphed_buffers, "_morph_vertices", stream)
 
     def trace_rays(self, rays, mode="closest", out=None, count=None, stream=None):
         """bdpt_trace_rays: closest-hit or any-hit queries of a batch of rays against the scene (semantics: include/bdpt.h

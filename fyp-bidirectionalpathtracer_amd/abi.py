@@ -41,7 +41,7 @@ MAX_MORPH_TARGETS = 1024
 # kernel's LDS path
 SKIN_LDS_BONES, SKIN_LDS_MIN_VERTICES = 64, 1 << 20
 SKIN_PATH_AUTO, SKIN_PATH_GLOBAL, SKIN_PATH_LDS = 0, 1, 2
-# bdpt_test_morph_kernel: the same paths, chosen by the same rule (csrc/morph.h launchMorph)
+# bdpt_test_morph_kernel: the same paths, chosen by the same rule (csrc/morph.h launchDeform)
 MORPH_PATH_AUTO, MORPH_PATH_GLOBAL, MORPH_PATH_LDS = 0, 1, 2
 TRACE_CLOSEST, TRACE_CLOSEST_CULL_BACK, TRACE_ANY = 0, 1, 2
 SHADE_NORMAL_MAP = 1

@@ -927,7 +927,8 @@ int bdpt_update_geometry(bdpt_ctx* c, const bdpt_geometry_update* u, void* strea
   return updateTail(c, pos, nrm, bit, u->flags, st);
 }
 
-// ---- skinning: bdpt_set_skin / bdpt_update_skinned (skin.hip) and the same arithmetic on the host ----
+// ---- skinning and morph targets: bdpt_set_skin / bdpt_set_morph, one deformation pass behind bdpt_update_skinned and
+// bdpt_update_morphed (deform.hip), and the same arithmetic on the host ----
 namespace {
 // the checks of a bdpt_skin_desc that need no context; `what` prefixes the message
 int checkSkinDesc(bdpt_ctx* c, const bdpt_skin_desc* d, const char* what) {
@@ -961,6 +962,113 @@ int checkSkinDesc(bdpt_ctx* c, const bdpt_skin_desc* d, const char* what) {
   }
   return BDPT_OK;
 }
+
+// The vertex loop of bdpt_host_skin and bdpt_host_morph: the base (with a skin, its rest pose), morphed if `m`, then
+// skinned, or copied for a static vertex and without a skin.
+void hostDeform(size_t numVertices, const float* baseP, const float* baseN, const float* baseB, const MorphCsr* m, const float* weights,
+                const bdpt_skin_desc* skin, const float* bones, const float* normalBones, float* outP, float* outN, float* outB) {
+  const float* dN = m && !m->dNrm.empty() ? m->dNrm.data() : nullptr;
+  const float* dB = m && !m->dBit.empty() ? m->dBit.data() : nullptr;
+  withFlag(baseN != nullptr, [&](auto hasN) {
+    withFlag(baseB != nullptr, [&](auto hasB) {
+      constexpr bool N = decltype(hasN)::value, B = decltype(hasB)::value;
+      hostParallelFor(numVertices, [&](size_t v0, size_t v1) {
+        for (size_t v = v0; v < v1; v++) {
+          const size_t o = v * 3;
+          float p[3], n[3] = {0.0f, 0.0f, 0.0f}, b[3] = {0.0f, 0.0f, 0.0f};
+          for (int k = 0; k < 3; k++) {
+            p[k] = baseP[o + k];
+            if (N) n[k] = baseN[o + k];
+            if (B) b[k] = baseB[o + k];
+          }
+          if (m) morphVertex(m->target.data(), m->dPos.data(), dN, dB, weights, m->start[v], m->start[v + 1], p, n, b);
+          const float* w = skin ? skin->boneWeights + v * 4 : nullptr;
+          if (skin && !skinIsStatic(w)) {
+            skinVertex<N, B>(bones, normalBones, skin->boneIds + v * 4, w, p, n, b, outP + o, N ? outN + o : nullptr, B ? outB + o : nullptr);
+            continue;
+          }
+          for (int k = 0; k < 3; k++) {
+            outP[o + k] = p[k];
+            if (N) outN[o + k] = n[k];
+            if (B) outB[o + k] = b[k];
+          }
+        }
+      });
+    });
+  });
+}
+
+// the context's deformed streams: the skin's with a skin, the morph's without
+struct DeformOut {
+  float *pos, *nrm, *bit;
+};
+DeformOut deformOut(const bdpt_ctx* c) {
+  return c->haveSkin ? DeformOut{c->skin.pos, c->skin.nrm, c->skin.bit} : DeformOut{c->morph.pos, c->morph.nrm, c->morph.bit};
+}
+int deformedBuffers(const bdpt_ctx* c, const float** positions, const float** normals, const float** bitangents) {
+  const DeformOut o = deformOut(c);
+  *positions = o.pos;
+  *normals = o.nrm;
+  *bitangents = o.bit;
+  return BDPT_OK;
+}
+
+// What bdpt_update_skinned (weights null) and bdpt_update_morphed do with arguments that passed their checks: the
+// finiteness scan of host inputs, their staging, the deformation pass and the refit.  `what` prefixes the messages.
+int updateDeformed(bdpt_ctx* c, const char* what, const float* weights, const float* bones, const float* nbones, uint32_t memory, uint32_t flags,
+                   void* stream) {
+  const std::string w(what);
+  const MorphDev* M = weights ? &c->morph : nullptr;
+  const SkinDev* K = c->haveSkin ? &c->skin : nullptr;
+  const size_t nw = M ? M->numTargets : 0, pal = K ? (size_t)K->numBones * 16 : 0;
+  const bool host = memory == BDPT_MEMORY_HOST;
+  if (host) {
+    bool finite = true;
+    for (size_t t = 0; t < nw; t++) finite = finite && std::isfinite(weights[t]);
+    for (size_t i = 0; i < pal; i++) finite = finite && std::isfinite(bones[i]) && (!nbones || std::isfinite(nbones[i]));
+    if (!finite) {
+      fail(c, w + (M ? ": a weight or a bone matrix element is not finite" : ": a bone matrix element is not finite"));
+      return BDPT_E_INVALID;
+    }
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = ensureRefit(c, st)) return rc;  // (bdpt_set_skin / bdpt_set_morph made the plan: nothing to do)
+  if (host && streamIsCapturing(st)) {
+    fail(c, w + ": host-pointer " + (M ? "weights and palettes" : "palettes") + " are staged through pinned memory: not while capturing");
+    return BDPT_E_STATE;
+  }
+  if (int rc = orderAfterLast(c, st)) return rc;
+  if (host) {
+    const void* arrays[3] = {weights, bones, nbones};
+    const size_t bytes[3] = {nw * 4, pal * 4, pal * 4};
+    float* dst[3] = {c->morphWeights, c->skinPalette[0], c->skinPalette[1]};
+    if (int rc = stageHostArrays(c, arrays, bytes, 3, dst, st)) return rc;
+    if (weights) weights = dst[0];
+    if (bones) bones = dst[1];
+    if (nbones) nbones = dst[2];
+  }
+  launchDeform(M, weights, K, bones, nbones, kSkinPathAuto, st);
+  const DeformOut o = deformOut(c);
+  return updateTail(c, o.pos, o.nrm, o.bit, flags, st);
+}
+
+// bdpt_test_skin_kernel and bdpt_test_morph_kernel: the pass alone, with the palettes (and weights) of the last update
+int testDeformKernel(bdpt_ctx* c, bool morph, uint32_t path, void* stream) {
+  if (!c || path > (uint32_t)kSkinPathLds) return BDPT_E_INVALID;
+  if (!c->haveScene || !(morph ? c->haveMorph : c->haveSkin)) {
+    fail(c, morph ? "test_morph_kernel: no morph (bdpt_set_morph first)" : "test_skin_kernel: no skin (bdpt_set_skin first)");
+    return BDPT_E_STATE;
+  }
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = orderAfterLast(c, st)) return rc;
+  // (skinPalette[k] is null where the context has no skin, or its skin no normals)
+  launchDeform(morph ? &c->morph : nullptr, c->morphWeights, c->haveSkin ? &c->skin : nullptr, c->skinPalette[0], c->skinPalette[1], (int)path, st);
+  HIPCHK(c, hipGetLastError());
+  c->lastStream = st;
+  return BDPT_OK;
+}
 }  // namespace
 
 int bdpt_host_skin(const bdpt_skin_desc* d, const float* bones, const float* normalBones, float* outPositions, float* outNormals,
@@ -968,37 +1076,7 @@ int bdpt_host_skin(const bdpt_skin_desc* d, const float* bones, const float* nor
   if (!d || !bones || !outPositions) return BDPT_E_INVALID;
   if ((d->normals && (!normalBones || !outNormals)) || (d->bitangents && !outBitangents)) return BDPT_E_INVALID;
   if (int rc = checkSkinDesc(nullptr, d, "host_skin")) return rc;
-  const bool hasN = d->normals != nullptr, hasB = d->bitangents != nullptr;
-  hostParallelFor(d->numVertices, [&](size_t v0, size_t v1) {
-    const float zero[3] = {0.0f, 0.0f, 0.0f};
-    float scratch[3];
-    for (size_t v = v0; v < v1; v++) {
-      const float* w = d->boneWeights + v * 4;
-      const float* p = d->positions + v * 3;
-      const float* n = hasN ? d->normals + v * 3 : zero;
-      const float* b = hasB ? d->bitangents + v * 3 : zero;
-      float* op = outPositions + v * 3;
-      float* on = hasN ? outNormals + v * 3 : scratch;
-      float* ob = hasB ? outBitangents + v * 3 : scratch;
-      if (skinIsStatic(w)) {
-        for (int k = 0; k < 3; k++) {
-          op[k] = p[k];
-          if (hasN) on[k] = n[k];
-          if (hasB) ob[k] = b[k];
-        }
-        continue;
-      }
-      const uint16_t* id = d->boneIds + v * 4;
-      if (hasN && hasB)
-        skinVertex<true, true>(bones, normalBones, id, w, p, n, b, op, on, ob);
-      else if (hasN)
-        skinVertex<true, false>(bones, normalBones, id, w, p, n, b, op, on, ob);
-      else if (hasB)
-        skinVertex<false, true>(bones, normalBones, id, w, p, n, b, op, on, ob);
-      else
-        skinVertex<false, false>(bones, normalBones, id, w, p, n, b, op, on, ob);
-    }
-  });
+  hostDeform(d->numVertices, d->positions, d->normals, d->bitangents, nullptr, nullptr, d, bones, normalBones, outPositions, outNormals, outBitangents);
   return BDPT_OK;
 }
 
@@ -1079,36 +1157,7 @@ int bdpt_update_skinned(bdpt_ctx* c, const bdpt_skin_update* u, void* stream) {
                                       : "update_skinned: bones (or normalBones, for a skin with normals) missing, or bad memory / flags / reserved");
     return BDPT_E_INVALID;
   }
-  const size_t pal = (size_t)K.numBones * 16;
-  if (u->memory == BDPT_MEMORY_HOST) {
-    bool finite = true;
-    for (size_t i = 0; i < pal; i++) finite = finite && std::isfinite(u->bones[i]) && (!K.nrm || std::isfinite(u->normalBones[i]));
-    if (!finite) {
-      fail(c, "update_skinned: a bone matrix element is not finite");
-      return BDPT_E_INVALID;
-    }
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = ensureRefit(c, st)) return rc;  // (bdpt_set_skin made the plan: nothing to do)
-  const float* bones = u->bones;
-  const float* nbones = K.nrm ? u->normalBones : nullptr;
-  if (u->memory == BDPT_MEMORY_HOST) {
-    if (streamIsCapturing(st)) {
-      fail(c, "update_skinned: host-pointer palettes are staged through pinned memory: not while capturing");
-      return BDPT_E_STATE;
-    }
-    if (int rc = orderAfterLast(c, st)) return rc;
-    const void* arrays[2] = {bones, nbones};
-    const size_t bytes[2] = {pal * 4, pal * 4};
-    if (int rc = stageHostArrays(c, arrays, bytes, 2, c->skinPalette, st)) return rc;
-    bones = c->skinPalette[0];
-    nbones = K.nrm ? c->skinPalette[1] : nullptr;
-  } else {
-    if (int rc = orderAfterLast(c, st)) return rc;
-  }
-  launchSkin(K, bones, nbones, kSkinPathAuto, st);
-  return updateTail(c, K.pos, K.nrm, K.bit, u->flags, st);
+  return updateDeformed(c, "update_skinned", nullptr, u->bones, K.nrm ? u->normalBones : nullptr, u->memory, u->flags, stream);
 }
 
 int bdpt_skinned_buffers(bdpt_ctx* c, const float** positions, const float** normals, const float** bitangents) {
@@ -1117,28 +1166,12 @@ int bdpt_skinned_buffers(bdpt_ctx* c, const float** positions, const float** nor
     fail(c, "skinned_buffers: no skin (bdpt_set_skin first)");
     return BDPT_E_STATE;
   }
-  *positions = c->skin.pos;
-  *normals = c->skin.nrm;
-  *bitangents = c->skin.bit;
-  return BDPT_OK;
+  return deformedBuffers(c, positions, normals, bitangents);
 }
 
-int bdpt_test_skin_kernel(bdpt_ctx* c, uint32_t path, void* stream) {
-  if (!c || path > (uint32_t)kSkinPathLds) return BDPT_E_INVALID;
-  if (!c->haveScene || !c->haveSkin) {
-    fail(c, "test_skin_kernel: no skin (bdpt_set_skin first)");
-    return BDPT_E_STATE;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = orderAfterLast(c, st)) return rc;
-  launchSkin(c->skin, c->skinPalette[0], c->skin.nrm ? c->skinPalette[1] : nullptr, (int)path, st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
-}
+int bdpt_test_skin_kernel(bdpt_ctx* c, uint32_t path, void* stream) { return testDeformKernel(c, false, path, stream); }
+int bdpt_test_morph_kernel(bdpt_ctx* c, uint32_t path, void* stream) { return testDeformKernel(c, true, path, stream); }
 
-// ---- morph targets: bdpt_set_morph / bdpt_update_morphed (morph.hip) and the same arithmetic on the host ----
 namespace {
 // The checks of a bdpt_morph_desc.  haveSkin: the base is a skin's rest pose, which has normals / bitangents where
 // skinN / skinB; `what` prefixes the message.
@@ -1221,46 +1254,11 @@ int bdpt_host_morph(const bdpt_morph_desc* d, const bdpt_skin_desc* skin, const 
   const float* baseP = skin ? skin->positions : d->positions;
   const float* baseN = skin ? skin->normals : d->normals;
   const float* baseB = skin ? skin->bitangents : d->bitangents;
-  const bool hasN = baseN != nullptr, hasB = baseB != nullptr;
-  if ((hasN && !outNormals) || (hasB && !outBitangents)) return BDPT_E_INVALID;
+  if ((baseN && !outNormals) || (baseB && !outBitangents)) return BDPT_E_INVALID;
   for (uint32_t t = 0; t < d->numTargets; t++)
     if (!std::isfinite(weights[t])) return BDPT_E_INVALID;
   const MorphCsr m = morphBuildCsr(d->numVertices, d->numTargets, d->targetStart, d->vertex, d->dPositions, d->dNormals, d->dBitangents);
-  const float* dN = d->dNormals ? m.dNrm.data() : nullptr;
-  const float* dB = d->dBitangents ? m.dBit.data() : nullptr;
-  hostParallelFor(d->numVertices, [&](size_t v0, size_t v1) {
-    float scratch[3];
-    for (size_t v = v0; v < v1; v++) {
-      float p[3], n[3] = {0.0f, 0.0f, 0.0f}, b[3] = {0.0f, 0.0f, 0.0f};
-      for (int k = 0; k < 3; k++) {
-        p[k] = baseP[v * 3 + k];
-        if (hasN) n[k] = baseN[v * 3 + k];
-        if (hasB) b[k] = baseB[v * 3 + k];
-      }
-      morphVertex(m.target.data(), m.dPos.data(), dN, dB, weights, m.start[v], m.start[v + 1], p, n, b);
-      float* op = outPositions + v * 3;
-      float* on = hasN ? outNormals + v * 3 : scratch;
-      float* ob = hasB ? outBitangents + v * 3 : scratch;
-      const float* w = skin ? skin->boneWeights + v * 4 : nullptr;
-      if (!skin || skinIsStatic(w)) {
-        for (int k = 0; k < 3; k++) {
-          op[k] = p[k];
-          if (hasN) on[k] = n[k];
-          if (hasB) ob[k] = b[k];
-        }
-        continue;
-      }
-      const uint16_t* id = skin->boneIds + v * 4;
-      if (hasN && hasB)
-        skinVertex<true, true>(bones, normalBones, id, w, p, n, b, op, on, ob);
-      else if (hasN)
-        skinVertex<true, false>(bones, normalBones, id, w, p, n, b, op, on, ob);
-      else if (hasB)
-        skinVertex<false, true>(bones, normalBones, id, w, p, n, b, op, on, ob);
-      else
-        skinVertex<false, false>(bones, normalBones, id, w, p, n, b, op, on, ob);
-    }
-  });
+  hostDeform(d->numVertices, baseP, baseN, baseB, &m, weights, skin, bones, normalBones, outPositions, outNormals, outBitangents);
   return BDPT_OK;
 }
 
@@ -1348,41 +1346,7 @@ int bdpt_update_morphed(bdpt_ctx* c, const bdpt_morph_update* u, void* stream) {
                 : "update_morphed: weights missing, palettes missing with a skin or given without one, or bad memory / flags / reserved");
     return BDPT_E_INVALID;
   }
-  const size_t pal = K ? (size_t)K->numBones * 16 : 0;
-  if (u->memory == BDPT_MEMORY_HOST) {
-    bool finite = true;
-    for (uint32_t t = 0; t < M.numTargets; t++) finite = finite && std::isfinite(u->weights[t]);
-    for (size_t i = 0; i < pal; i++) finite = finite && std::isfinite(u->bones[i]) && (!needN || std::isfinite(u->normalBones[i]));
-    if (!finite) {
-      fail(c, "update_morphed: a weight or a bone matrix element is not finite");
-      return BDPT_E_INVALID;
-    }
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = ensureRefit(c, st)) return rc;  // (bdpt_set_morph made the plan: nothing to do)
-  const float* weights = u->weights;
-  const float* bones = u->bones;
-  const float* nbones = u->normalBones;
-  if (u->memory == BDPT_MEMORY_HOST) {
-    if (streamIsCapturing(st)) {
-      fail(c, "update_morphed: host-pointer weights and palettes are staged through pinned memory: not while capturing");
-      return BDPT_E_STATE;
-    }
-    if (int rc = orderAfterLast(c, st)) return rc;
-    const void* arrays[3] = {weights, bones, nbones};
-    const size_t bytes[3] = {(size_t)M.numTargets * 4, pal * 4, pal * 4};
-    float* dst[3] = {c->morphWeights, c->skinPalette[0], c->skinPalette[1]};
-    if (int rc = stageHostArrays(c, arrays, bytes, 3, dst, st)) return rc;
-    weights = c->morphWeights;
-    bones = K ? c->skinPalette[0] : nullptr;
-    nbones = needN ? c->skinPalette[1] : nullptr;
-  } else {
-    if (int rc = orderAfterLast(c, st)) return rc;
-  }
-  launchMorph(M, K, weights, bones, nbones, kSkinPathAuto, st);
-  if (K) return updateTail(c, K->pos, K->nrm, K->bit, u->flags, st);
-  return updateTail(c, M.pos, M.nrm, M.bit, u->flags, st);
+  return updateDeformed(c, "update_morphed", u->weights, u->bones, u->normalBones, u->memory, u->flags, stream);
 }
 
 int bdpt_morphed_buffers(bdpt_ctx* c, const float** positions, const float** normals, const float** bitangents) {
@@ -1391,26 +1355,7 @@ int bdpt_morphed_buffers(bdpt_ctx* c, const float** positions, const float** nor
     fail(c, "morphed_buffers: no morph (bdpt_set_morph first)");
     return BDPT_E_STATE;
   }
-  *positions = c->haveSkin ? c->skin.pos : c->morph.pos;
-  *normals = c->haveSkin ? c->skin.nrm : c->morph.nrm;
-  *bitangents = c->haveSkin ? c->skin.bit : c->morph.bit;
-  return BDPT_OK;
-}
-
-int bdpt_test_morph_kernel(bdpt_ctx* c, uint32_t path, void* stream) {
-  if (!c || path > (uint32_t)kSkinPathLds) return BDPT_E_INVALID;
-  if (!c->haveScene || !c->haveMorph) {
-    fail(c, "test_morph_kernel: no morph (bdpt_set_morph first)");
-    return BDPT_E_STATE;
-  }
-  ENTER(c);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = orderAfterLast(c, st)) return rc;
-  const SkinDev* K = c->haveSkin ? &c->skin : nullptr;
-  launchMorph(c->morph, K, c->morphWeights, K ? c->skinPalette[0] : nullptr, K && K->nrm ? c->skinPalette[1] : nullptr, (int)path, st);
-  HIPCHK(c, hipGetLastError());
-  c->lastStream = st;
-  return BDPT_OK;
+  return deformedBuffers(c, positions, normals, bitangents);
 }
 
 int bdpt_set_lights(bdpt_ctx* c, const bdpt_light* lights, uint32_t numLights, void* stream) {

@@ -1,6 +1,6 @@
 // morph.h — morph targets (bdpt_set_morph / bdpt_update_morphed / bdpt_host_morph): the per-vertex arithmetic, shared by
-// the device kernel (morph.hip) and the host entry point (api.cpp), the vertex-major layout both read, and the launcher
-// api.cpp drives.  The arithmetic is the contract of include/bdpt.h "Morph targets": fp32, no contraction
+// the device kernels (deform.hip) and the host entry point (api.cpp), the vertex-major layout both read, and the launcher
+// of the deformation pass, which api.cpp drives.  The arithmetic is the contract of include/bdpt.h "Morph targets": fp32, no contraction
 // (-ffp-contract=off on both sides), one product and one sum per term, terms in ascending target order, a term whose
 // weight is zero (either sign) skipped.  Plain C++ apart from the __host__ __device__ markers (texture_planes.h BDPT_HD).
 #pragma once
@@ -102,13 +102,12 @@ struct MorphDev {
   uint32_t numTargets;
   uint32_t numActive;
 };
-// One morph pass with `weights` (device, numTargets floats), enqueued on `st`, allocates nothing.  K: the context's skin
-// or null.  With a skin every vertex is morphed and skinned in registers into the skin's streams with the palettes
-// `bones` / `normalBones` (as launchSkin's); without one the active vertices are morphed into the morph's own streams.
-// `path`: as launchSkin's, and by the same rule (the palette gather is the same access): kSkinPathAuto stages palettes of
-// at most kSkinLdsBones bones in LDS on skins of at least kSkinLdsMinVertices vertices; kSkinPathGlobal / kSkinPathLds
-// force a path (kSkinPathLds falls back to global above kSkinLdsBones, and without a skin there is nothing to stage).
-void launchMorph(const MorphDev& M, const SkinDev* K, const float* weights, const float* bones, const float* normalBones, int path,
-                 hipStream_t st);
+// One deformation pass (deform.hip), enqueued on `st`, allocates nothing.  M: the context's morph or null, with `weights`
+// (device, numTargets floats); K: its skin or null, with the palettes `bones` / `normalBones` (device, numBones x 16
+// floats; normalBones only read when the skin has normals).  With a skin every vertex is (morphed and) skinned in
+// registers into the skin's streams; without one the morph's active vertices are morphed into the morph's own streams.
+// `path`: kSkinPath* of skin.h, and without a skin there is nothing to stage.
+void launchDeform(const MorphDev* M, const float* weights, const SkinDev* K, const float* bones, const float* normalBones, int path,
+                  hipStream_t st);
 }  // namespace bdpt
 #endif

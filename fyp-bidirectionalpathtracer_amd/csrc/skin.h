@@ -1,5 +1,5 @@
 // skin.h — skinning (bdpt_set_skin / bdpt_update_skinned / bdpt_host_skin): the per-vertex arithmetic, shared by the
-// device kernel (skin.hip) and the host entry point (api.cpp), and the launcher api.cpp drives.
+// device kernels (deform.hip) and the host entry point (api.cpp), and the skin as the kernels see it.
 // The arithmetic is the contract of include/bdpt.h "Skinning": fp32, no contraction (-ffp-contract=off on both sides),
 // every sum in the order written here.  Plain C++ apart from the __host__ __device__ markers (texture_planes.h BDPT_HD).
 #pragma once
@@ -46,7 +46,7 @@ BDPT_HD void skinVertex(const float* bones, const float* normalBones, const uint
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 namespace bdpt {
-// The LDS path of the kernel (skin.hip, DESIGN.md "Skinning"): palettes of at most kSkinLdsBones bones are staged in LDS
+// The LDS path of the kernels (deform.hip, DESIGN.md "Skinning"): palettes of at most kSkinLdsBones bones are staged in LDS
 // by each workgroup when the skin has at least kSkinLdsMinVertices vertices (fewer leave the chip short of workgroups:
 // measured, the gather from global memory wins below about 0.75 M vertices and loses from about 1.25 M on).  Everything
 // else gathers from global memory.
@@ -66,11 +66,8 @@ struct SkinDev {
   uint32_t numVertices;
   uint32_t numBones;
 };
+// how launchDeform (morph.h) gathers the palettes: kSkinPathAuto picks by palette size and vertex count; the other two
+// force a path (kSkinPathLds falls back to global above kSkinLdsBones)
 enum : int { kSkinPathAuto = 0, kSkinPathGlobal = 1, kSkinPathLds = 2 };
-// One skinning pass of K into its skinned streams with the palettes `bones` / `normalBones` (device, numBones x 16
-// floats; normalBones only read when the skin has normals); enqueued on `st`, allocates nothing.  `path`: kSkinPathAuto
-// picks by palette size and vertex count; the other two force a path (kSkinPathLds falls back to global above
-// kSkinLdsBones).
-void launchSkin(const SkinDev& K, const float* bones, const float* normalBones, int path, hipStream_t st);
 }  // namespace bdpt
 #endif

@@ -1,4 +1,4 @@
-"""GPU tests of morph targets: bdpt_set_morph / bdpt_update_morphed (csrc/morph.hip in front of the device refit).
+"""GPU tests of morph targets: bdpt_set_morph / bdpt_update_morphed (csrc/deform.hip in front of the device refit).
 Everything is compared bit for bit: the morphed (and skinned) streams with the numpy float32 restatement of
 tests/morph_numpy.py, the refitted records with the host refit of the restated positions, frames with the oracle rendering
 the description that holds the restated arrays and with a context given them through bdpt_update_geometry — as
@@ -49,7 +49,8 @@ def atrium(pkg):
 @pytest.mark.parametrize("num_targets", [1, 3, 1024])
 def test_kernel_equals_the_restatement(pkg, atrium, num_targets, skinned):
     """Host weights, then device weights of another pose, the kernel alone with what the host update staged; then
-    positions only, and positions plus normals.  Before the first update read_morphed returns the base."""
+    positions only, positions plus normals, and positions plus bitangents.  Before the first update read_morphed returns
+    the base."""
     scene, r = atrium
     d = scene.desc
     nv = int(d.numVertices)
@@ -58,7 +59,7 @@ def test_kernel_equals_the_restatement(pkg, atrium, num_targets, skinned):
     ctx.set_scene(d)
     (b0, n0), (b1, n1) = r["poses"]
     w0, w1 = mn.make_weights(0, num_targets), mn.make_weights(1, num_targets)
-    for streams in ("pnb", "p", "pn"):
+    for streams in ("pnb", "p", "pn", "pb"):
         N = r["N"] if "n" in streams else None
         B = r["B"] if "b" in streams else None
         t = mn.only(tg, N is not None, B is not None)
@@ -85,7 +86,7 @@ def test_kernel_equals_the_restatement(pkg, atrium, num_targets, skinned):
             ctx.test_morph_kernel(path)
             _assert_streams(ctx, first, f"{streams}: forced path {path}")
             ctx.update_morphed(tw, *tp)
-    assert ctx.refit_info().numUpdates == 12
+    assert ctx.refit_info().numUpdates == 16
     ctx.close()
 
 

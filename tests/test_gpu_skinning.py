@@ -1,4 +1,4 @@
-"""GPU tests of skinning: bdpt_set_skin / bdpt_update_skinned (csrc/skin.hip in front of the device refit).  Everything is
+"""GPU tests of skinning: bdpt_set_skin / bdpt_update_skinned (csrc/deform.hip in front of the device refit).  Everything is
 compared bit for bit: the skinned streams with the numpy float32 restatement of tests/skin_numpy.py, the refitted records
 with the host refit of the restated positions, frames with the oracle rendering the description that holds the restated
 arrays — as tests/test_gpu_refit.py does for bdpt_update_geometry."""
@@ -43,7 +43,7 @@ def _assert_streams(ctx, r, bones, nbones, label, normals=True, bitangents=True)
 @pytest.mark.parametrize("num_bones", [1, 3, 64, 65, 1024])
 def test_kernel_equals_the_restatement(pkg, num_bones):
     """Scene.atrium(4, 30000): bitangents and a ragged last wave.  Host bones, then device bones of another pose; then a
-    skin without normals and bitangents."""
+    skin without normals and bitangents, one without bitangents, and one without normals on both paths."""
     assert pkg.abi.SKIN_LDS_BONES == 64
     scene = pkg.Scene.atrium(4, 30000)
     d = scene.desc
@@ -76,6 +76,14 @@ def test_kernel_equals_the_restatement(pkg, num_bones):
     _set_skin(ctx, r, num_bones, normals=True, bitangents=False)
     ctx.update_skinned(bones, nbones)
     _assert_streams(ctx, r, bones, nbones, "no bitangents", bitangents=False)
+    _set_skin(ctx, r, num_bones, normals=False, bitangents=True)
+    ctx.update_skinned(bones)
+    _assert_streams(ctx, r, bones, None, "no normals", normals=False)
+    for path in (pkg.abi.SKIN_PATH_GLOBAL, pkg.abi.SKIN_PATH_LDS):
+        ctx.update_skinned(tb)
+        _assert_streams(ctx, r, bones2, None, "no normals, device bones", normals=False)
+        ctx.test_skin_kernel(path)
+        _assert_streams(ctx, r, bones, None, f"no normals, forced path {path}", normals=False)
     ctx.close()
     scene.close()
 
