@@ -30,7 +30,7 @@ constexpr int kDone = (int)0x80000000;  // traversal cursor value: stack exhaust
 
 struct TravState {
   f3 o, d, idir;  // idir clamped to +-1e30 so slab arithmetic never produces inf - inf
-  uint32_t neg;   // bit a set when d[a] < 0: near plane of axis a is the box's hi plane
+  uint32_t neg;   // bit a: the sign bit of d[a], which idir[a] carries too: near plane of axis a is the box's hi plane
   float tmin, tmax;
   int cur, sp;
   Hit best;
@@ -46,7 +46,9 @@ BD void travInit(TravState& T, f3 o, f3 d, float tmin, float tmax) {
   T.o = o;
   T.d = d;
   T.idir = mk(clampedRcp(d.x), clampedRcp(d.y), clampedRcp(d.z));
-  T.neg = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
+  // Near and far planes go by the sign idir carries, d's sign bit, not by d < 0: -0.0 has idir = -1e30, and with the lo
+  // plane taken as its near plane tn = +huge and tf = -huge rejected every box.  For every other d the two agree.
+  T.neg = (__float_as_uint(d.x) >> 31) | ((__float_as_uint(d.y) >> 31) << 1) | ((__float_as_uint(d.z) >> 31) << 2);
   T.tmin = tmin;
   T.tmax = tmax;
   T.sp = 0;

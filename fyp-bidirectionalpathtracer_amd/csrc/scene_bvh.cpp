@@ -185,7 +185,7 @@ HostHit traceHost(const HostScene& S, int mode, const float* ray, uint64_t& nNod
   if (bvh.tris.empty()) return best;
   const float idir[3] = {clampedRcpHost(d.x), clampedRcpHost(d.y), clampedRcpHost(d.z)};
   const float org[3] = {o.x, o.y, o.z};
-  const bool neg[3] = {d.x < 0.0f, d.y < 0.0f, d.z < 0.0f};
+  const bool neg[3] = {std::signbit(d.x), std::signbit(d.y), std::signbit(d.z)};  // the sign idir carries (travInit): -0.0 too
   int32_t stack[128];
   int sp = 0;
   int32_t cur = 0;

@@ -611,6 +611,15 @@ int bdpt_host_morph(const bdpt_morph_desc* desc, const bdpt_skin_desc* skin, con
  *   - alpha-masked materials run the any-hit alpha test; triangles the build dropped as never visible are never hit;
  *   - a miss writes prim = -1 and t = u = v = 0; a ray with a NaN or zero direction, a NaN origin or tmax <= tmin misses;
  *   - with numRaysDevice set, rays at or beyond min(*numRaysDevice, numRays) are neither read nor written.
+ * Ray contract (what a caller may send; DESIGN.md "Ray queries" has the measurements):
+ *   - signed zeros in a direction are equivalent: (-0, -1, -0), the ray along -N of an axis-aligned wall, finds what
+ *     (0, -1, 0) finds;
+ *   - a direction component of magnitude below 1e-30 is treated as zero by the tree walk (its reciprocal is clamped to
+ *     +-1e30): scale such directions up, and tmin / tmax down, before the call;
+ *   - the answers are those of a linear scan over all triangles (hit on a shared vertex or edge, t == tmax, t == tmin,
+ *     tmax = inf and negative tmin included) while the build's pad, 2e-5 of the scene's diagonal, exceeds an ulp of the
+ *     coordinates: a scene nearer to the origin than some 300 of its diagonals.  Farther out a ray that grazes a
+ *     triangle's vertex or edge can miss it: move the scene (and the rays) to the origin first.
  * Ordering: the call is enqueued on `stream`.  When the context's previous call used another stream, it first waits (an
  * event) for what that call enqueued, as bdpt_update_geometry does; it sees the scene as of the last update enqueued
  * before it.  Later calls of the context on the same stream are ordered behind it; work on further streams is ordered by
