@@ -715,7 +715,17 @@ int bdpt_shade_hits(bdpt_ctx* ctx, const bdpt_shade_desc* desc, void* stream);
  *   BDPT_BSDF_EVAL    evalBRDF(V, L, N, N, ...) toward dirs[i] = (L.xyz, w): w != 0 evaluates the specular lobe (the
  *                     pass passes the flag its sample returned); values[i] = (f.xyz, 0).
  * A record with prim < 0 gives all-zero outputs.  With numDevice set, items at or beyond min(*numDevice, num) are neither
- * read nor written. */
+ * read nor written.
+ * Record contract (tests/edge_records.py has the families, DESIGN.md "Surface queries" the measurements): every float
+ * field may be degenerate or non-finite; none reaches an address, and the outputs are those of the fp32 arithmetic as
+ * written, bit for bit the CPU oracle's.  N and V are used as given (a non-unit N scales the cosines).  Under GGX a V in
+ * or below the tangent plane (saturate(N.V) = 0) makes the specular lobe's weight and f NaN (0 / 0) and leaves the diffuse
+ * lobe alone; a linearRoughness whose fourth power underflows to 0 (below some 5e-12) gives the specular sample pdf 0 with
+ * a NaN weight; dirs[i] == -V evaluates the specular lobe as NaN where N.L > 0 (the half vector is normalize(0)); N.L == 0
+ * counts as below the surface (f = 0; a sample: pdf 0, weight 0).  A NaN or infinite colour channel stays in its channel
+ * of f; in a sample it also reaches probDiffuse, and a NaN probDiffuse picks the specular lobe.  The caller's
+ * clampVec(x, clampUpper) turns a NaN, a negative number and -inf into +0 and +inf into clampUpper, so such a weight
+ * ends a path or saturates it; it cannot poison a sum. */
 #define BDPT_BSDF_SAMPLE 0u
 #define BDPT_BSDF_EVAL 1u
 typedef struct bdpt_bsdf_sample {
@@ -835,6 +845,24 @@ int bdpt_motion_query(bdpt_ctx* ctx, const bdpt_motion_desc* desc, void* stream)
  *   lightPath[0].pdfForward is 1 / lightsCount and is not stored.  seedsOut[i] (optional) is the state after all draws: the
  *   pass's seedL.
  *
+ * Record contract (tests/edge_records.py, DESIGN.md "Light queries"): the floats of a record and of a light may be
+ * degenerate or non-finite; the scene has at least one light, and the light index, a draw in [0, 1) times lightsCount
+ * clamped to lightsCount - 1, is in range whatever the record holds.  The outputs are the fp32 arithmetic's, bit for bit
+ * the CPU oracle's:
+ *   - a point within sqrt(1e-5) of a point or spot light (getLightData's switch), or so far that the squared distance
+ *     overflows: dir is NaN and value is 0 (status 0), tmax the distance (0 at the light itself, inf beyond 1.8e19);
+ *   - cosTheta == cosOpeningAngle is inside the cone; penumbraAngle > 0 scales by saturate((delta - p) / p), so a penumbra
+ *     at or above openingAngle gives 0; acos is taken of cosTheta clamped to [-1, 1] (a build definition: HLSL leaves acos
+ *     outside the interval to the driver), so a dirW longer than 1 widens the cone's bright core, never makes a NaN;
+ *   - a zero dirW: a spot light sees cosTheta 0 everywhere; a directional light gives a NaN direction and value 0, and in
+ *     EMIT a zero direction;
+ *   - N.L <= 0, V below the surface or V == -L under GGX: value NaN (0 / 0) or 0; status NONZERO for the NaN, and no hint;
+ *   - intensities pass through: negative ones give negative values, inf gives inf or NaN, none gets a hint unless some
+ *     component is positive.
+ *   A hint is looked up only for a value with a positive component, which implies a finite direction and distance: the
+ *   cube map is indexed by a finite, non-zero posW - lightPos.  clampVec (see bdpt_bsdf_query) makes +0 of every NaN and
+ *   negative value.
+ *
  * Errors (nothing is enqueued): no scene BDPT_E_STATE; a NULL context or desc, an unknown mode or flag, matIndex > 1, a
  * missing or misaligned buffer (records 16 bytes, words 4), compaction buffers given in part, compaction or hints in EMIT
  * mode BDPT_E_INVALID. */
@@ -920,6 +948,19 @@ int bdpt_light_query(bdpt_ctx* ctx, const bdpt_light_desc* desc, void* stream);
  * items whose status has NONZERO, CAMERA those with PIXEL (the pass traces those whatever their value: a zero-valued splat
  * still saturates its pixel in the resolve).  One atomic per wave of 64 items; the caller zeroes the word and owns capacity
  * num of both lists; a position at or beyond num is not written; the order inside the lists is unspecified.
+ *
+ * Record contract (tests/edge_records.py, DESIGN.md "Connection queries"): every float of a record may be degenerate or
+ * non-finite; the outputs are the fp32 arithmetic's, bit for bit the CPU oracle's.
+ *   VERTICES: coincident points give tmax 0, a NaN direction and a NaN value (status NONZERO; the caller's clamp drops
+ *   it) unless a cosine test made it 0 first; points closer than 1e-19 (invLengthAB^2 overflows) give inf or NaN, farther
+ *   than 1.8e19 (length^2 overflows) tmax inf, a zero direction and 0 (Lambertian) or NaN (GGX, 0 / 0), as do two normals
+ *   perpendicular to the connection; a predecessor equal to its vertex gives a NaN outgoing direction: NaN under GGX where
+ *   that vertex's specular flag is set, else its diffuse lobe (a NaN passes the cosine test), as for Lambertian.
+ *   CAMERA: the pixel is written only after 0 <= rintf(p * size - jitter) < size held for both coordinates, which fails
+ *   for NaN and +-inf: pixel is below width * height or 0xffffffff, whatever the record holds.  rintf rounds a tie to the
+ *   even pixel; -0.0 is pixel 0; a vertex in the camera plane or behind it (dot(cameraN, dir) >= 0), at the camera (a NaN
+ *   direction) or beyond 1.8e19 (a zero direction) has no pixel.  f may be NaN with a pixel (GGX, V below the surface):
+ *   the pass's NaN -> 0 and bdpt_splat_add's "c > 0" both drop it, and the splat still counts.
  *
  * Errors (nothing is enqueued): no scene, or CAMERA without a camera BDPT_E_STATE; a NULL context or desc, an unknown mode,
  * non-zero flags or reserved, matIndex > 1, a missing or misaligned buffer (records 16 bytes, words 4), compaction buffers

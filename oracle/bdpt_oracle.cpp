@@ -822,6 +822,7 @@ struct Globals {
 
 // the light data of a NEE term that drew `lightToSample` (`seed`: the state after that draw); the area light's shadow
 // ray stops short of the emitter: tmax = d (1 - 1e-4)
+void getLightData(const bdpt_light& l, f3 hitPos, f3& toLight, f3& lightIntensity, float& distToLight);
 void getLightData(const Globals& g, int index, f3 hitPos, f3& toLight, f3& lightIntensity, float& distToLight);
 void neeLightData(const Globals& g, int lightToSample, uint32_t seed, f3 hit, f3& L, f3& lightIntensity, float& distToLight) {
   if (g.area && lightToSample == (int)g.s->lights.size()) {
@@ -900,8 +901,7 @@ f3 evalBRDF(const Globals& g, f3 V, f3 L, f3 N, f3 noNormalN, f3 dif, f3 spec, f
 }
 
 // F/ShadingUtils/Lights.slang:54-102 + BDPT/MaterialUtils.hlsli:67-85
-void getLightData(const Globals& g, int index, f3 hitPos, f3& toLight, f3& lightIntensity, float& distToLight) {
-  const bdpt_light& l = g.s->lights[(size_t)index];
+void getLightData(const bdpt_light& l, f3 hitPos, f3& toLight, f3& lightIntensity, float& distToLight) {
   f3 lpos = ld3(l.posW), ldir = ld3(l.dirW), lint = ld3(l.intensity);
   f3 lsL, lsPos, lsDiffuse;
   if (l.type == BDPT_LIGHT_DIRECTIONAL) {
@@ -929,6 +929,16 @@ void getLightData(const Globals& g, int index, f3 hitPos, f3& toLight, f3& light
   distToLight = length(lsPos - hitPos);
 }
 
+void getLightData(const Globals& g, int index, f3 hitPos, f3& toLight, f3& lightIntensity, float& distToLight) {
+  getLightData(g.s->lights[(size_t)index], hitPos, toLight, lightIntensity, distToLight);
+}
+// the uniform light choice of ggxDirect / lambertianDirect / sampleLight (MaterialUtils.hlsli:151, 290; BDPTUtils.hlsli:142)
+inline int drawLight(int lightsCount, uint32_t& seed) {
+  int index = (int)(nextRand(seed) * (float)lightsCount);
+  if (index > lightsCount - 1) index = lightsCount - 1;
+  return index;
+}
+
 struct Tally {
   uint64_t rays[6] = {0, 0, 0, 0, 0, 0};  // primary, eye, light, nee, splat, connect
   uint64_t nodeC = 0, triC = 0, nodeS = 0, triS = 0, valid = 0, splats = 0;
@@ -942,16 +952,9 @@ bool shadowRayVisibility(const Globals& g, Tally& tl, int stage, f3 origin, f3 d
   return h.prim < 0;
 }
 
-// MaterialUtils.hlsli:149-184
-f3 ggxDirect(const Globals& g, Tally& tl, uint32_t& seed, f3 hit, f3 N, f3 V, f3 dif, f3 spec, float rough) {
-  int lightToSample = (int)(nextRand(seed) * (float)g.lightsCount);
-  if (lightToSample > g.lightsCount - 1) lightToSample = g.lightsCount - 1;
-  float distToLight;
-  f3 lightIntensity, L;
-  neeLightData(g, lightToSample, seed, hit, L, lightIntensity, distToLight);
+// MaterialUtils.hlsli:160-184: ggxDirect from its shadow term on (shadowMult = lightsCount for a visible light, else 0)
+f3 ggxDirectTerm(float shadowMult, f3 L, f3 lightIntensity, f3 N, f3 V, f3 dif, f3 spec, float rough) {
   float NdotL = saturate(dot(N, L));
-  bool vis = shadowRayVisibility(g, tl, 3, hit, L, g.p.minT, distToLight);
-  float shadowMult = vis ? (float)g.lightsCount : 0.f;
   f3 H = normalize(V + L);
   float NdotH = saturate(dot(N, H));
   float LdotH = saturate(dot(L, H));
@@ -962,17 +965,30 @@ f3 ggxDirect(const Globals& g, Tally& tl, uint32_t& seed, f3 hit, f3 N, f3 V, f3
   f3 ggxTerm = (D * G) * F / (4 * NdotV);
   return (shadowMult * lightIntensity) * (ggxTerm + (NdotL * dif) / kPi);
 }
+// MaterialUtils.hlsli:149-184
+f3 ggxDirect(const Globals& g, Tally& tl, uint32_t& seed, f3 hit, f3 N, f3 V, f3 dif, f3 spec, float rough) {
+  int lightToSample = drawLight(g.lightsCount, seed);
+  float distToLight;
+  f3 lightIntensity, L;
+  neeLightData(g, lightToSample, seed, hit, L, lightIntensity, distToLight);
+  bool vis = shadowRayVisibility(g, tl, 3, hit, L, g.p.minT, distToLight);
+  float shadowMult = vis ? (float)g.lightsCount : 0.f;
+  return ggxDirectTerm(shadowMult, L, lightIntensity, N, V, dif, spec, rough);
+}
+// MaterialUtils.hlsli:296-307: lambertianDirect from its shadow term on
+f3 lambertianDirectTerm(float shadowMult, f3 toLight, f3 lightIntensity, f3 norm, f3 difColor) {
+  float LdotN = saturate(dot(norm, toLight));
+  return (((shadowMult * LdotN) * lightIntensity) * difColor) / kPi;
+}
 // MaterialUtils.hlsli:288-307
 f3 lambertianDirect(const Globals& g, Tally& tl, uint32_t& seed, f3 hit, f3 norm, f3 difColor) {
-  int lightToSample = (int)(nextRand(seed) * (float)g.lightsCount);
-  if (lightToSample > g.lightsCount - 1) lightToSample = g.lightsCount - 1;
+  int lightToSample = drawLight(g.lightsCount, seed);
   float distToLight;
   f3 lightIntensity, toLight;
   neeLightData(g, lightToSample, seed, hit, toLight, lightIntensity, distToLight);
-  float LdotN = saturate(dot(norm, toLight));
   bool vis = shadowRayVisibility(g, tl, 3, hit, toLight, g.p.minT, distToLight);
   float shadowMult = (float)g.lightsCount * (vis ? 1.0f : 0.0f);
-  return (((shadowMult * LdotN) * lightIntensity) * difColor) / kPi;
+  return lambertianDirectTerm(shadowMult, toLight, lightIntensity, norm, difColor);
 }
 
 // BDPT/RayPathData.hlsli:1-45
@@ -1097,6 +1113,21 @@ inline float evalGWithoutV(const PathVertex& a, const PathVertex& b) {
   float cosB = fabsf(dot(b.N, dirAB));
   return cosA * cosB * invLengthAB * invLengthAB;
 }
+// BDPT/BDPTUtils.hlsli:200-222: the two BRDFs of a connection and (fsL * G) * fsE; woE / woL are the directions from the
+// two end vertices to their predecessors.  False where the shader returns early (fsL, then fsE, all zero): value is that zero.
+inline bool pairValue(const Globals& g, const PathVertex& cameraEndV, f3 woE, const PathVertex& lightEndV, f3 woL, float G, f3& value) {
+  f3 connectDir = normalize(cameraEndV.posW - lightEndV.posW);
+  f3 wi = connectDir;
+  f3 fsL = evalBRDF(g, wi, woL, lightEndV.N, lightEndV.N, lightEndV.dif, lightEndV.spec, lightEndV.rough, lightEndV.isSpecular);
+  value = fsL;
+  if (fsL.x == 0 && fsL.y == 0 && fsL.z == 0) return false;
+  wi = -connectDir;
+  f3 fsE = evalBRDF(g, wi, woE, cameraEndV.N, cameraEndV.N, cameraEndV.dif, cameraEndV.spec, cameraEndV.rough, cameraEndV.isSpecular);
+  value = fsE;
+  if (fsE.x == 0 && fsE.y == 0 && fsE.z == 0) return false;
+  value = (fsL * G) * fsE;
+  return true;
+}
 // BDPT/BDPTUtils.hlsli:186-224 (aL indexes the LIGHT path with cameraIndex-1, sic :198)
 f3 getUnweightedContribution(const Globals& g, const PathVertex* cameraPath, const PathVertex* lightPath, uint32_t cameraIndex,
                              uint32_t lightIndex, float G) {
@@ -1105,16 +1136,10 @@ f3 getUnweightedContribution(const Globals& g, const PathVertex* cameraPath, con
   const PathVertex& lightEndV = lightPath[lightIndex];
   f3 aE = cameraPath[cameraIndex - 1].color;
   f3 aL = lightPath[cameraIndex - 1].color;
-  f3 connectDir = normalize(cameraEndV.posW - lightEndV.posW);
-  f3 wi = connectDir;
-  f3 wo = normalize(lightPath[lightIndex - 1].posW - lightEndV.posW);
-  f3 fsL = evalBRDF(g, wi, wo, lightEndV.N, lightEndV.N, lightEndV.dif, lightEndV.spec, lightEndV.rough, lightEndV.isSpecular);
-  if (fsL.x == 0 && fsL.y == 0 && fsL.z == 0) return fsL;
-  wi = -connectDir;
-  wo = normalize(cameraPath[cameraIndex - 1].posW - cameraEndV.posW);
-  f3 fsE = evalBRDF(g, wi, wo, cameraEndV.N, cameraEndV.N, cameraEndV.dif, cameraEndV.spec, cameraEndV.rough, cameraEndV.isSpecular);
-  if (fsE.x == 0 && fsE.y == 0 && fsE.z == 0) return fsE;
-  f3 cst = (fsL * G) * fsE;
+  f3 woL = normalize(lightPath[lightIndex - 1].posW - lightEndV.posW);
+  f3 woE = normalize(cameraPath[cameraIndex - 1].posW - cameraEndV.posW);
+  f3 cst;
+  if (!pairValue(g, cameraEndV, woE, lightEndV, woL, G, cst)) return cst;
   return (aL * cst) * aE;
 }
 
@@ -1160,6 +1185,15 @@ inline bool getLaunchIndexFromDirection(const Globals& g, f3 dir, int& ix, int& 
   ix = (int)fx;
   iy = (int)fy;
   return true;
+}
+
+// BDPTMain.rt.hlsl:186-196: the geometry term of a light-tracing splat and connectToCamera (MaterialUtils.hlsli:10-13)
+inline void splatTerm(const Globals& g, const PathVertex& lv, f3 cameraN, f3 dirToCamera, float disToCamera, f3& fr, float& G) {
+  float theta1 = saturate(fabsf(dot(dirToCamera, cameraN)));
+  float theta2 = saturate(fabsf(dot(dirToCamera, lv.N)));
+  float invDisToCamera = 1.0f / disToCamera;
+  G = theta1 * theta2 * invDisToCamera * invDisToCamera;
+  fr = evalBRDF(g, lv.V, dirToCamera, lv.N, lv.N, lv.dif, lv.spec, lv.rough, lv.isSpecular);
 }
 
 inline uint64_t toFixed(float c) {  // c in [0, clampUpper<=1]; 2^-32 units
@@ -1241,8 +1275,7 @@ void bdptPixel(const Globals& g, Tally& tl, oracle_frame* f, uint32_t x, uint32_
   // sampleLight, BDPT/BDPTUtils.hlsli:140-152
   f3 lightOrigin, lightDir, lightIntensity;
   {
-    int index = (int)(nextRand(randSeed) * (float)g.lightsCount);
-    if (index > g.lightsCount - 1) index = g.lightsCount - 1;
+    int index = drawLight(g.lightsCount, randSeed);
     if (g.area && index == (int)g.s->lights.size()) {  // the emitter table (include/bdpt.h "Area lights")
       f3 n;
       lightOrigin = areaLightStart(*g.s, g.areaW, randSeed, n, lightDir, lightIntensity).pos;
@@ -1302,7 +1335,6 @@ void bdptPixel(const Globals& g, Tally& tl, oracle_frame* f, uint32_t x, uint32_
   // light tracing, :171-208.  Build definition (quirk 6): fixed-point sums in a separate buffer.
   for (uint32_t i = 0; doSplat && i < D && takeContribution[i + 1]; i++) {
     f3 lastHitPos = lightPath[i + 1].posW;
-    f3 lastHitN = lightPath[i + 1].N;
     f3 cameraN = normalize(ld3(g.cam.cameraW));
     f3 dirToCamera = normalize(camPos - lastHitPos);
     float disToCamera = length(camPos - lastHitPos);
@@ -1311,13 +1343,9 @@ void bdptPixel(const Globals& g, Tally& tl, oracle_frame* f, uint32_t x, uint32_
       if (vis) {
         int ix, iy;
         bool inside = getLaunchIndexFromDirection(g, dirToCamera, ix, iy);
-        float theta1 = saturate(fabsf(dot(dirToCamera, cameraN)));
-        float theta2 = saturate(fabsf(dot(dirToCamera, lastHitN)));
-        float invDisToCamera = 1.0f / disToCamera;
-        float G = theta1 * theta2 * invDisToCamera * invDisToCamera;
-        const PathVertex& lv = lightPath[i + 1];
-        // connectToCamera, MaterialUtils.hlsli:10-13
-        f3 fr = evalBRDF(g, lv.V, normalize(camPos - lv.posW), lv.N, lv.N, lv.dif, lv.spec, lv.rough, lv.isSpecular);
+        f3 fr;
+        float G;
+        splatTerm(g, lightPath[i + 1], cameraN, dirToCamera, disToCamera, fr, G);  // (lastHitPos is its posW)
         f3 shade = (lightPath[i].color * fr) * G;
         shade = clampVec(g, applyStrategyWeight(g, cameraPath, lightPath, shade, i + 2, 0, i + 1));
         bool colorsNan = isnan3(shade);
@@ -1750,6 +1778,131 @@ void oracle_bsdf(const float* in, uint32_t n, uint32_t matIndex, float* out) {
     o[9] = fr.y;
     o[10] = fr.z;
     o[11] = o[12] = o[13] = o[14] = o[15] = 0.0f;
+  }
+}
+
+// ---- per-record hooks mirroring the NEE mode of bdpt_light_query and the two modes of bdpt_connect_query (include/bdpt.h):
+// loops over the functions bdptPixel calls, on bdpt_surface records, writing the queries' output records.
+namespace {
+struct SurfRec {
+  f3 posW, N, V, dif, spec;
+  float linearRoughness;
+  int32_t prim;
+};
+SurfRec loadSurf(const bdpt_surface* s) {
+  SurfRec r;
+  r.posW = ld3(s->posW);
+  r.N = ld3(s->N);
+  r.V = ld3(s->V);
+  r.dif = ld3(s->diffuse);
+  r.spec = ld3(s->specular);
+  r.linearRoughness = s->linearRoughness;
+  r.prim = s->prim;
+  return r;
+}
+// The vertex a record stands for.  The Lambertian model reads neither specular nor roughness nor the flag.
+PathVertex vertexOf(const SurfRec& r, bool ggx, bool isSpecular) {
+  PathVertex v = vinit();
+  v.posW = r.posW;
+  v.N = r.N;
+  v.V = r.V;
+  v.dif = r.dif;
+  if (ggx) {
+    v.spec = r.spec;
+    v.rough = r.linearRoughness * r.linearRoughness;
+    v.isSpecular = isSpecular;
+  }
+  return v;
+}
+void storeRay(bdpt_ray* o, f3 org, float tmin, f3 dir, float tmax) {
+  float* f = reinterpret_cast<float*>(o);
+  f[0] = org.x, f[1] = org.y, f[2] = org.z, f[3] = tmin;
+  f[4] = dir.x, f[5] = dir.y, f[6] = dir.z, f[7] = tmax;
+}
+bool allZero(f3 a) { return a.x == 0.0f && a.y == 0.0f && a.z == 0.0f; }
+}  // namespace
+
+void oracle_light_nee(const bdpt_light* lights, uint32_t numLights, const bdpt_surface* surfaces, const uint32_t* seeds, uint32_t n,
+                      uint32_t matIndex, float minT, bdpt_light_sample* samples, uint32_t* seedsOut) {
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t seed = seeds[i];
+    const int lightToSample = drawLight((int)numLights, seed);  // the term's one draw, also for a record that is a miss
+    if (seedsOut) seedsOut[i] = seed;
+    memset(&samples[i], 0, sizeof(samples[i]));
+    const SurfRec r = loadSurf(&surfaces[i]);
+    if (r.prim < 0) continue;
+    f3 L, lightIntensity;
+    float distToLight;
+    getLightData(lights[lightToSample], r.posW, L, lightIntensity, distToLight);
+    const float rough = r.linearRoughness * r.linearRoughness;
+    const f3 value = matIndex == 0 ? ggxDirectTerm((float)numLights, L, lightIntensity, r.N, r.V, r.dif, r.spec, rough)
+                                   : lambertianDirectTerm((float)numLights * 1.0f, L, lightIntensity, r.N, r.dif);
+    storeRay(&samples[i].ray, r.posW, minT, L, distToLight);
+    samples[i].value[0] = value.x, samples[i].value[1] = value.y, samples[i].value[2] = value.z;
+    samples[i].light = (uint16_t)lightToSample;
+    samples[i].status = allZero(value) ? 0u : BDPT_LIGHT_STATUS_NONZERO;
+  }
+}
+
+void oracle_connect_vertices(const bdpt_surface* eye, const bdpt_surface* light, const float* eyePrev, const float* lightPrev,
+                             const uint8_t* eyeSpecular, const uint8_t* lightSpecular, uint32_t n, uint32_t matIndex, float minT,
+                             bdpt_connect_sample* samples) {
+  Globals g;
+  memset(&g, 0, sizeof(g));
+  g.p.matIndex = matIndex;
+  const bool ggx = matIndex == 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const SurfRec er = loadSurf(&eye[i]), lr = loadSurf(&light[i]);
+    const PathVertex ev = vertexOf(er, ggx, eyeSpecular && eyeSpecular[i] != 0);
+    const PathVertex lv = vertexOf(lr, ggx, lightSpecular && lightSpecular[i] != 0);
+    // the pair's ray, as bdptPixel forms it (:222-223), whatever prim says
+    const float lengthAB = length(lv.posW - ev.posW);
+    const f3 dirAB = (lv.posW - ev.posW) / lengthAB;
+    f3 value = mk(0);
+    if (er.prim >= 0 && lr.prim >= 0) {
+      // the directions to the predecessors: normalize(prev - posW) as getUnweightedContribution forms them, or the record's V
+      const f3 woE = eyePrev ? normalize(ld3(eyePrev + (size_t)i * 4) - ev.posW) : ev.V;
+      const f3 woL = lightPrev ? normalize(ld3(lightPrev + (size_t)i * 4) - lv.posW) : lv.V;
+      pairValue(g, ev, woE, lv, woL, evalGWithoutV(ev, lv), value);
+    }
+    storeRay(&samples[i].ray, ev.posW, minT, dirAB, lengthAB);
+    samples[i].value[0] = value.x, samples[i].value[1] = value.y, samples[i].value[2] = value.z;
+    samples[i].status = allZero(value) ? 0u : BDPT_CONNECT_STATUS_NONZERO;
+  }
+}
+
+void oracle_connect_camera(const bdpt_camera* cam, uint32_t width, uint32_t height, const float* pixelJitter, const bdpt_surface* light,
+                           const uint8_t* lightSpecular, uint32_t n, uint32_t matIndex, float minT, bdpt_camera_sample* samples) {
+  Globals g;
+  memset(&g, 0, sizeof(g));
+  g.cam = *cam;
+  g.W = width;
+  g.H = height;
+  g.p.matIndex = matIndex;
+  g.p.pixelJitter[0] = pixelJitter[0];
+  g.p.pixelJitter[1] = pixelJitter[1];
+  const bool ggx = matIndex == 0;
+  const f3 camPos = ld3(cam->posW);
+  const f3 cameraN = normalize(ld3(cam->cameraW));
+  for (uint32_t i = 0; i < n; i++) {
+    memset(&samples[i], 0, sizeof(samples[i]));
+    samples[i].pixel = 0xffffffffu;
+    const SurfRec lr = loadSurf(&light[i]);
+    if (lr.prim < 0) continue;
+    PathVertex lv = vertexOf(lr, ggx, lightSpecular && lightSpecular[i] != 0);
+    if (!ggx) lv.V = mk(0);  // (never read)
+    const f3 dirToCamera = normalize(camPos - lv.posW);
+    const float disToCamera = length(camPos - lv.posW);
+    storeRay(&samples[i].ray, lv.posW, minT, dirToCamera, disToCamera);
+    int ix, iy;
+    if (!(dot(cameraN, dirToCamera) < 0) || !getLaunchIndexFromDirection(g, dirToCamera, ix, iy)) continue;
+    f3 fr;
+    float G;
+    splatTerm(g, lv, cameraN, dirToCamera, disToCamera, fr, G);
+    samples[i].f[0] = fr.x, samples[i].f[1] = fr.y, samples[i].f[2] = fr.z;
+    samples[i].G = G;
+    samples[i].pixel = (uint32_t)ix + (uint32_t)iy * width;
+    samples[i].status = BDPT_CONNECT_STATUS_PIXEL | ((!allZero(fr) && G != 0.0f) ? BDPT_CONNECT_STATUS_NONZERO : 0u);
   }
 }
 

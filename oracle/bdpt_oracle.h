@@ -84,6 +84,17 @@ void oracle_rng(const uint32_t* val0, const uint32_t* val1, uint32_t n, uint32_t
 void oracle_trace(const oracle_scene* s, const float* rays, uint32_t n, int mode, uint32_t flags,
                   int32_t* out_prim, float* out_tuv);
 void oracle_bsdf(const float* in, uint32_t n, uint32_t matIndex, float* out);
+/* Per-record hooks mirroring bdpt_light_query (BDPT_LIGHT_NEE, no emitter table, no hints) and bdpt_connect_query (both
+ * modes) of include/bdpt.h: loops over the functions the frame's pixel loop calls, on the queries' input records, writing
+ * the queries' output records (host memory).  lights: numLights >= 1 records.  seedsOut, the predecessors and the specular
+ * bytes are optional, with the queries' meaning of NULL. */
+void oracle_light_nee(const bdpt_light* lights, uint32_t numLights, const bdpt_surface* surfaces, const uint32_t* seeds, uint32_t n,
+                      uint32_t matIndex, float minT, bdpt_light_sample* samples, uint32_t* seedsOut);
+void oracle_connect_vertices(const bdpt_surface* eye, const bdpt_surface* light, const float* eyePrev, const float* lightPrev,
+                             const uint8_t* eyeSpecular, const uint8_t* lightSpecular, uint32_t n, uint32_t matIndex, float minT,
+                             bdpt_connect_sample* samples);
+void oracle_connect_camera(const bdpt_camera* cam, uint32_t width, uint32_t height, const float* pixelJitter, const bdpt_surface* light,
+                           const uint8_t* lightSpecular, uint32_t n, uint32_t matIndex, float minT, bdpt_camera_sample* samples);
 void oracle_sincos2pi(const float* u, uint32_t n, float* s, float* c);
 void oracle_half_round(const float* in, uint32_t n, float* out);
 

@@ -140,3 +140,43 @@ def eval_brdf(mat_index, v, l, n, dif, spec, rough, is_specular):
     ndotv = saturate(float(np.dot(n, v)))
     val, _ = ggx_lighting(h, l, n, ndotl, ndotv, rough, spec)
     return val
+
+
+FLT_MIN = 1.17549435e-38  # the smallest normal fp32 number
+FLT_MAX = 3.40282347e+38
+
+
+def cos_margin(a, b):
+    """|dot(a, b)| in units of |a| |b|: the distance of a dot product from 0 (0 where a vector is 0, NaN where one is NaN)"""
+    with np.errstate(all="ignore"):
+        d = abs(float(np.dot(a, b)))
+        scale = float(np.linalg.norm(a)) * float(np.linalg.norm(b))
+        return d / scale if (scale > 0 and math.isfinite(scale)) else d
+
+
+def fp32_range_margin(*values):
+    """Half the margin (i.e. "inside it") when a value this reading meets is finite and not 0 but outside fp32's normal
+    range — fp32 then over- or underflows where float64 does not, the boundary being the format's own — else inf."""
+    for x in values:
+        x = abs(float(x))
+        if x != 0 and math.isfinite(x) and (x < FLT_MIN or x > FLT_MAX):
+            return 0.5e-6
+    return float("inf")
+
+
+def brdf_margins(mat_index, seed, n, v, l_query, dif, spec, rough, l_sampled):
+    """The distance of every comparison sampleBRDF / evalBRDF met from its boundary, in the units of the compared
+    quantity: the lobe choice (|rand - probDiffuse|), dot(N, L) <= 0 of the sampled and of the queried direction, and
+    N.V against 0 (its saturate, behind which 0 / 0 waits).  A dot product's unit is the product of its vectors' lengths
+    (that is what its rounding error scales with), so its margin is the cosine's.  A NaN margin is no boundary at all: the
+    comparison goes the same way in every precision.  `fp32_range`: fp32_range_margin of roughness^2 and roughness^2 / 2, which fp32 holds
+    only above FLT_MIN (below it the fp32 arithmetic underflows where this reading does not)."""
+    inf = float("inf")
+    if mat_index == 1:
+        return dict(lobe=inf, ndotl_sample=inf, ndotl_eval=inf, ndotv=inf, fp32_range=inf)
+    _, r = next_rand(seed)
+    with np.errstate(all="ignore"):
+        a2 = float(rough) * float(rough)
+        return dict(lobe=abs(r - prob_diffuse(dif, spec)), ndotl_sample=cos_margin(n, l_sampled),
+                    ndotl_eval=cos_margin(n, l_query), ndotv=cos_margin(n, v),
+                    fp32_range=fp32_range_margin(a2, a2 / 2))

@@ -43,6 +43,11 @@ def load_oracle(abi):
     lib.oracle_rng.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.oracle_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.oracle_bsdf.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.oracle_light_nee.argtypes = [C.POINTER(abi.Light), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float,
+                                     C.c_void_p, C.c_void_p]
+    lib.oracle_connect_vertices.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
+    lib.oracle_connect_camera.argtypes = [C.POINTER(abi.Camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                          C.c_uint32, C.c_float, C.c_void_p]
     lib.oracle_sincos2pi.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.oracle_half_round.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.oracle_area_exclude.restype = C.c_int
@@ -64,6 +69,45 @@ def load_oracle(abi):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _records(a, width):
+    a = np.ascontiguousarray(a, np.float32)
+    assert a.ndim == 2 and a.shape[1] == width
+    return a
+
+
+def light_nee(abi, lights, surfaces, seeds, mat_index, min_t):
+    """oracle_light_nee: lights a ctypes array of abi.Light, surfaces (n, 24) float32, seeds (n,) uint32.
+    -> (samples (n, 12) float32 in the bdpt_light_sample layout, the states after the selection draw)"""
+    lib = load_oracle(abi)
+    surfaces, seeds = _records(surfaces, 24), np.ascontiguousarray(seeds, np.uint32)
+    out, after = np.zeros((len(seeds), 12), np.float32), np.zeros(len(seeds), np.uint32)
+    lib.oracle_light_nee(lights, len(lights), _p(surfaces), _p(seeds), len(seeds), mat_index, min_t, _p(out), _p(after))
+    return out, after
+
+
+def connect_vertices(abi, eye, light, mat_index, min_t, eye_prev=None, light_prev=None, eye_specular=None, light_specular=None):
+    """oracle_connect_vertices -> (n, 12) float32 in the bdpt_connect_sample layout"""
+    lib = load_oracle(abi)
+    eye, light = _records(eye, 24), _records(light, 24)
+    opt = [None if a is None else np.ascontiguousarray(a, t) for a, t in
+           ((eye_prev, np.float32), (light_prev, np.float32), (eye_specular, np.uint8), (light_specular, np.uint8))]
+    out = np.zeros((len(eye), 12), np.float32)
+    lib.oracle_connect_vertices(_p(eye), _p(light), *[None if a is None else _p(a) for a in opt], len(eye), mat_index, min_t, _p(out))
+    return out
+
+
+def connect_camera(abi, cam, width, height, jitter, light, mat_index, min_t, light_specular=None):
+    """oracle_connect_camera -> (n, 16) float32 in the bdpt_camera_sample layout"""
+    lib = load_oracle(abi)
+    light = _records(light, 24)
+    spec = None if light_specular is None else np.ascontiguousarray(light_specular, np.uint8)
+    jit = np.array(jitter, np.float32)
+    out = np.zeros((len(light), 16), np.float32)
+    lib.oracle_connect_camera(C.byref(cam), width, height, _p(jit), _p(light), None if spec is None else _p(spec), len(light), mat_index,
+                              min_t, _p(out))
+    return out
 
 
 class OracleRender:
