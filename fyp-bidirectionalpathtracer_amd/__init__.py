@@ -680,6 +680,56 @@ class Context:
         d.items = None if items is None else items.data_ptr()
         self._check(self._lib.bdpt_splat_add(self._h, C.byref(d), stream), "bdpt_splat_add")
 
+    # ---- walk queries (include/bdpt.h "Walk queries") ----
+    def walk(self, starts, seeds, steps, mat_index=0, min_t=1e-4, from_lobe=False, seed_per_step=False, first=None,
+             first_specular=None, alive=None, out=None, samples=None, hits=None, count=None, stream=None):
+        """bdpt_walk_query: one subpath per item, up to `steps` bounces (1 .. 16) in one launch — the loop trace_rays("closest")
+        -> shade_hits(normal_map=False) -> sample_bsdf -> next ray, bit for bit.  GPU tensors only.
+        starts (N, 12) float32 in the bdpt_walk_start layout, which is emit_lights' output: 0-7 the first ray (bdpt_ray; step 0
+        takes its tmin and tmax, later steps min_t and 1e38), 8-10 the colour the walk starts with, 11 not read.  seeds (N,)
+        uint32 / int32 RNG states, read by value at every step; with seed_per_step (steps, N), one state per step.
+        first (N, 24) bdpt_surface records: the vertex the walk leaves (its position is the first ray's origin, and a ghost
+        at step 0 copies it); first_specular (N,) uint8 its specular byte; alive (N,) uint8, 0 = the item has no path.
+        Returns (vertices (steps, N, 24) float32 bdpt_surface records, info (steps, N, 4) float32: 0-2 the path colour at
+        the vertex, 3 (through .view(torch.int32)) the status, abi.WALK_STATUS_STORED | _REAL | _SPECULAR); out= takes that
+        pair preallocated.  samples (steps, N, 8) and hits (steps, N, 4), when given, take the sample drawn at each real
+        vertex and the hit that made it.  `count` (1,) caps the items on the device; the plane stride stays N."""
+        import torch
+        f32, i32, u32, u8 = (torch.float32,), (torch.float32, torch.int32), (torch.int32, torch.uint32), (torch.uint8,)
+        mat, flags = self._bsdf_mode("walk", mat_index, from_lobe)
+        if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= abi.BDPT_MAX_DEPTH:
+            raise BdptError(f"walk: steps must be an integer in 1 .. {abi.BDPT_MAX_DEPTH}, not {steps!r}")
+        self._gpu_only("walk", [("starts", starts), ("seeds", seeds), ("first", first), ("first_specular", first_specular),
+                                ("alive", alive), ("samples", samples), ("hits", hits), ("count", count)])
+        if starts is None or seeds is None:
+            raise BdptError("walk: starts and seeds are required")
+        n = int(starts.shape[0]) if starts.dim() >= 1 else -1
+        if n < 0 or steps * n >= 2**32:
+            raise BdptError("walk: bad item count")
+        self._check_gpu(starts, "walk", "starts", (n, 12), i32)
+        self._check_gpu(seeds, "walk", "seeds", (steps, n) if seed_per_step else (n,), u32)
+        for name, t, shape, dts in (("first", first, (n, 24), i32), ("first_specular", first_specular, (n,), u8),
+                                    ("alive", alive, (n,), u8), ("samples", samples, (steps, n, 8), i32),
+                                    ("hits", hits, (steps, n, 4), i32), ("count", count, (1,), u32)):
+            if t is not None:
+                self._check_gpu(t, "walk", name, shape, dts)
+        if out is None:
+            out = (torch.empty((steps, n, 24), dtype=torch.float32, device=starts.device),
+                   torch.empty((steps, n, 4), dtype=torch.float32, device=starts.device))
+        elif not isinstance(out, (tuple, list)) or len(out) != 2 or any(t is None for t in out):
+            raise BdptError("walk: out must be (vertices, info), both")
+        self._gpu_only("walk", [("out vertices", out[0]), ("out info", out[1])])
+        self._check_gpu(out[0], "walk", "out vertices", (steps, n, 24), i32)
+        self._check_gpu(out[1], "walk", "out info", (steps, n, 4), i32)
+        d = abi.WalkDesc()
+        d.num, d.steps, d.matIndex, d.minT = n, steps, mat, float(min_t)
+        d.flags = flags | (abi.WALK_SEED_PER_STEP if seed_per_step else 0)
+        d.starts, d.seeds, d.vertices, d.info = starts.data_ptr(), seeds.data_ptr(), out[0].data_ptr(), out[1].data_ptr()
+        d.numDevice, d.first, d.firstSpecular, d.alive, d.samples, d.hits = (
+            None if t is None else t.data_ptr() for t in (count, first, first_specular, alive, samples, hits))
+        self._check(self._lib.bdpt_walk_query(self._h, C.byref(d), stream), "bdpt_walk_query")
+        return tuple(t.view(torch.float32) if t.dtype == torch.int32 else t for t in out)
+
     @staticmethod
     def _bsdf_mode(what, mat_index, from_lobe):
         if mat_index not in (0, 1) or isinstance(mat_index, bool):
@@ -1413,6 +1463,15 @@ class FramePipeline:
         """Context.splat_add on this pipeline's stream."""
         self.ctx.splat_add(splat, pixels, values, visible, items, count, self._stream_ptr())
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (splat, pixels, values, visible, items, count))
+
+    def walk(self, starts, seeds, steps, seed_per_step=False, first=None, first_specular=None, alive=None, out=None, samples=None,
+             hits=None, count=None):
+        """Context.walk with the pipeline's BSDF (mat_index), min_t and SPECULAR_FROM_LOBE flag, on its stream."""
+        res = self.ctx.walk(starts, seeds, steps, self.mat_index, self.min_t, (self.flags & abi.PARAM_SPECULAR_FROM_LOBE) != 0,
+                            seed_per_step, first, first_specular, alive, out, samples, hits, count, self._stream_ptr())
+        keep_for_stream(self.torch.cuda.current_stream(self.dev),
+                        (starts, seeds, first, first_specular, alive, samples, hits, count) + tuple(res))
+        return res
 
     def motion_query(self, hits, out=None, count=None):
         """Context.motion_query on this pipeline's stream."""

@@ -51,6 +51,8 @@ LIGHT_USE_HINTS = 1
 LIGHT_STATUS_NONZERO, LIGHT_STATUS_HINT_OCCLUDED = 1, 2
 CONNECT_VERTICES, CONNECT_CAMERA = 0, 1
 CONNECT_STATUS_NONZERO, CONNECT_STATUS_PIXEL = 1, 2
+WALK_SEED_PER_STEP = 1
+WALK_STATUS_STORED, WALK_STATUS_REAL, WALK_STATUS_SPECULAR = 1, 2, 4
 
 
 class Material(C.Structure):
@@ -265,6 +267,21 @@ class SplatDesc(C.Structure):
                 ("values", C.c_void_p), ("visible", C.c_void_p), ("items", C.c_void_p), ("splat", C.c_void_p)]
 
 
+class WalkStart(C.Structure):
+    _fields_ = [("ray", Ray), ("color", C.c_float * 3), ("unused", C.c_uint32)]
+
+
+class WalkInfo(C.Structure):
+    _fields_ = [("color", C.c_float * 3), ("status", C.c_uint32)]
+
+
+class WalkDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("steps", C.c_uint32), ("numDevice", C.c_void_p), ("matIndex", C.c_uint32),
+                ("flags", C.c_uint32), ("minT", C.c_float), ("reserved", C.c_uint32), ("starts", C.c_void_p), ("seeds", C.c_void_p),
+                ("first", C.c_void_p), ("firstSpecular", C.c_void_p), ("alive", C.c_void_p), ("vertices", C.c_void_p),
+                ("info", C.c_void_p), ("samples", C.c_void_p), ("hits", C.c_void_p)]
+
+
 BMFR_MAX_PLANES = BDPT_MAX_LIGHTS + 2
 
 
@@ -319,6 +336,7 @@ PROTOTYPES = {
     "bdpt_light_query": (C.c_int, [C.c_void_p, C.POINTER(LightDesc), C.c_void_p]),
     "bdpt_connect_query": (C.c_int, [C.c_void_p, C.POINTER(ConnectDesc), C.c_void_p]),
     "bdpt_splat_add": (C.c_int, [C.c_void_p, C.POINTER(SplatDesc), C.c_void_p]),
+    "bdpt_walk_query": (C.c_int, [C.c_void_p, C.POINTER(WalkDesc), C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit_pieces": (C.c_int, [C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),

@@ -1,5 +1,5 @@
 // api_query.cpp — the per-item queries of the C ABI (include/bdpt.h): bdpt_trace_rays, bdpt_camera_rays, bdpt_shade_hits,
-// bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add and bdpt_motion_query, on a caller's arrays in
+// bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query and bdpt_motion_query, on a caller's arrays in
 // device memory.  Every one checks its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags
 // and what goes together (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call
 // enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
@@ -213,6 +213,41 @@ int bdpt_splat_add(bdpt_ctx* c, const bdpt_splat_desc* d, void* stream) {
     A.cap = d->num;
     A.count = d->numDevice;
     launchSplatAdd(A, st);
+  });
+}
+
+static_assert(sizeof(bdpt_walk_start) == 48 && sizeof(bdpt_walk_start) == sizeof(bdpt_light_emit) &&
+                  offsetof(bdpt_walk_start, color) == offsetof(bdpt_light_emit, color) && sizeof(bdpt_walk_info) == 16 &&
+                  offsetof(bdpt_walk_info, status) == 12,
+              "walk_query_kernel reads a start as three float4 (bdpt_light_emit's layout) and writes an info record as one");
+int bdpt_walk_query(bdpt_ctx* c, const bdpt_walk_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "walk_query")) return rc;
+  if (!d->steps || d->steps > BDPT_MAX_DEPTH || d->matIndex > 1 || (d->flags & ~(BDPT_PARAM_SPECULAR_FROM_LOBE | BDPT_WALK_SEED_PER_STEP)) ||
+      d->reserved || (uint64_t)d->steps * d->num >= (1ull << 32))
+    return refuse(c, BDPT_E_INVALID, "walk_query",
+                  "steps outside 1 .. BDPT_MAX_DEPTH, matIndex > 1, unknown flags, non-zero reserved, or steps * num >= 2^32");
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->starts, 16) || !aligned(d->seeds, 4) || !aligned(d->vertices, 16) || !aligned(d->info, 16) ||
+      (d->first && !aligned(d->first, 16)) || (d->samples && !aligned(d->samples, 16)) || (d->hits && !aligned(d->hits, 16)) ||
+      (d->numDevice && !aligned(d->numDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "walk_query",
+                  "starts, seeds, vertices, info, first, samples or hits missing or not aligned (records 16 bytes, words 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    WalkQueryDev Q{};
+    Q.starts = f4(d->starts);
+    Q.seeds = d->seeds;
+    Q.first = f4(d->first);
+    Q.firstSpecular = d->firstSpecular;
+    Q.alive = d->alive;
+    Q.vertices = f4(d->vertices);
+    Q.info = f4(d->info);
+    Q.samples = f4(d->samples);
+    Q.hits = f4(d->hits);
+    Q.range = {d->num, d->numDevice, d->minT};
+    Q.steps = d->steps;
+    Q.seedPerStep = (d->flags & BDPT_WALK_SEED_PER_STEP) ? 1u : 0u;
+    launchWalkQuery(c->S, Q, d->matIndex == 0, (d->flags & BDPT_PARAM_SPECULAR_FROM_LOBE) != 0, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 

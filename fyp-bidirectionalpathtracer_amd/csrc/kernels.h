@@ -307,6 +307,7 @@ struct LaunchGrids {
   uint32_t walk[16] = {};             // [MASKED][EXT][GGX][COUNT]
   uint32_t shadow[2] = {0, 0};        // [COUNT]
   uint32_t rays[3] = {0, 0, 0};       // [mode] (trace_rays.hip)
+  uint32_t walkQuery[2] = {0, 0};     // [GGX] (walk_query.hip)
 };
 // both random walks of the frame: one persistent launch (trace + hit/miss shading in place)
 void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,
@@ -382,6 +383,25 @@ struct SplatAddDev {
   const uint32_t* count;   // optional device word
 };
 void launchSplatAdd(const SplatAddDev& A, hipStream_t st);
+// walk_query.hip: bdpt_walk_query.  One subpath per item, up to `steps` bounces: plane s of item i is element s * cap + i
+// of vertices (six float4), info (one), samples (two) and hits (one).
+struct WalkQueryDev {
+  const float4* starts;          // three float4 per item: (org, tmin) (dir, tmax) (colour, unused)
+  const uint32_t* seeds;         // cap states, or steps x cap with seedPerStep
+  const float4* first;           // optional: bdpt_surface records, the predecessor a step-0 ghost copies (its posW is the origin)
+  const uint8_t* firstSpecular;  // optional
+  const uint8_t* alive;          // optional: 0 = no path
+  float4* vertices;
+  float4* info;
+  float4* samples;               // optional
+  float4* hits;                  // optional
+  QueryRange range;              // minT: tmin of the rays after step 0
+  uint32_t steps;
+  uint32_t seedPerStep;
+};
+// `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
+void launchWalkQuery(const SceneDev& S, const WalkQueryDev& Q, bool ggx, bool fromLobe, unsigned long long* cursor, LaunchGrids& G,
+                     int numCUs, hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,

@@ -32,6 +32,8 @@
  *                                   for a caller's own integrator: connection queries
  *   bdpt_splat_add                  the splat's write to the pixel it lands in (BDPTMain.rt.hlsl:186-204) as the
  *                                   fixed-point sum bdpt_splat_buffer describes below, for a caller's lists
+ *   bdpt_walk_query                 shootRay and the walks' closest-hit and miss shaders (BDPTMain.rt.hlsl:106-145,
+ *                                   BDPT/globalIlluminationRay.hlsli:1-45) for a caller's own integrator: walk queries
  *   bdpt_set_environment            the "EnvironmentMap" channel BDPTPass requests (BDPTPass.cpp:29; bound by no shader
  *                                   of the pass in the reference): read only with BDPT_PARAM_ENV_ON_MISS
  *   bdpt_bvh_build_check / _hash, bdpt_host_bvh_*
@@ -1027,6 +1029,81 @@ typedef struct bdpt_splat_desc {
   uint64_t* splat;           /* device, 16-byte aligned, uint64[4] per pixel */
 } bdpt_splat_desc;
 int bdpt_splat_add(bdpt_ctx* ctx, const bdpt_splat_desc* desc, void* stream);
+
+/* ---- Walk queries: whole subpaths from one persistent kernel, for a caller's own integrator ----
+ * bdpt_walk_query walks one subpath per item for up to `steps` bounces in one launch: shootRay and the closest-hit
+ * shader of the reference's two walks (BDPT/BDPTMain.rt.hlsl:106-145, BDPT/globalIlluminationRay.hlsli:1-45).  It is the
+ * loop bdpt_trace_rays(BDPT_TRACE_CLOSEST) -> bdpt_shade_hits (without BDPT_SHADE_NORMAL_MAP) -> bdpt_bsdf_query(SAMPLE)
+ * -> select the hits, multiply the colours, build the next rays, bit for bit, run with the device functions those calls
+ * and the pass run, without a launch and a trip through memory per stage and bounce (DESIGN.md "Walk queries").
+ *
+ * State of item i: `payload`, a bdpt_surface, starting as first[i], or without `first` as posW = starts[i].ray.org with
+ * every other word 0; `pspec`, starting as firstSpecular[i] != 0 (NULL: 0); `pcolor`, starting as starts[i].color; the
+ * direction L, starting as starts[i].ray.dir; `live`, starting as alive ? alive[i] != 0 : true.
+ * Step s = 0 .. steps-1 runs while `live` holds:
+ *   - the ray is (payload.posW, L), traced as BDPT_TRACE_CLOSEST traces it; step 0 takes tmin and tmax from starts[i].ray,
+ *     later steps minT and 1e38;
+ *   - a hit is shaded as bdpt_shade_hits shades it without the normal map, seen from the ray's origin, and the record is
+ *     sampled as bdpt_bsdf_query(SAMPLE) samples it with matIndex and the BDPT_PARAM_SPECULAR_FROM_LOBE bit of `flags`.
+ *     The seed is read by value and never advanced: every step uses seeds[i] (the reference's quirk, which the pass
+ *     keeps); with BDPT_WALK_SEED_PER_STEP step s uses seeds[s * num + i], so a caller can decorrelate the bounces.  Then
+ *     payload = the record, pspec = the sample's specular word, pcolor = pcolor * weight, L = the sampled direction, and
+ *     the vertex is REAL;
+ *   - a miss — everything bdpt_trace_rays calls a miss: a NaN or zero direction, a NaN origin, tmax <= tmin — sets
+ *     pcolor = +0 and makes the vertex a ghost: payload and pspec stay as they were, and the walk ends after this step
+ *     (RayMiss: the ghost and the last direction are what a caller needs for an environment term);
+ *   - vertex s is written: vertices[s * num + i] = payload with prim = max(prim, 0), info.color = pcolor, info.status =
+ *     STORED, plus REAL for a real vertex, plus SPECULAR where pspec is set.  A real vertex writes the sample drawn at it
+ *     to `samples` and (t, u, v, prim) to `hits`; a ghost writes zeros to both, with hits.prim = -1.
+ * Steps after the walk has ended, and every step of an item that is not alive, write an all-zero record with prim = -1,
+ * colour +0 and status 0, and fill a given `samples` and `hits` as for a ghost.
+ *
+ * bdpt_light_query(BDPT_LIGHT_EMIT)'s output goes in as `starts` unchanged for a light walk (the last word is not read).
+ * An eye walk starts from the G-buffer vertex as `first`, with its first sample's direction and weight in `starts`; or
+ * straight from bdpt_camera_rays with a colour of 1 (step 0 then takes the camera ray's tmin and tmax), in which case the
+ * primary hit is shaded without the normal map, unlike the G-buffer pass's.
+ *
+ * Ordering, capture, counters and numDevice: as the surface queries — enqueued on `stream` behind the context's previous
+ * call, which also keeps bdpt_trace_rays' INVARIANT (no two persistent traversal kernels of one context resident at
+ * once); no allocation and no synchronise (one kernel node in a captured graph); bdpt_get_counters and
+ * bdpt_get_stage_times are left alone; items at or beyond min(*numDevice, num) are neither read nor written, and the plane
+ * stride stays num.  Nothing a caller supplies reaches an address: prim comes from the traversal only, `first` is copied.
+ * The ray and record contracts of bdpt_trace_rays and bdpt_bsdf_query hold for every step.
+ * Errors (nothing is enqueued): no scene BDPT_E_STATE; a NULL context or desc, steps of 0 or above BDPT_MAX_DEPTH,
+ * matIndex > 1, unknown flags, a non-zero reserved, steps * num >= 2^32 BDPT_E_INVALID; then num == 0 returns BDPT_OK
+ * and does nothing; then a missing or misaligned buffer (records 16 bytes, words 4) BDPT_E_INVALID. */
+#define BDPT_WALK_SEED_PER_STEP 1u   /* flags, beside BDPT_PARAM_SPECULAR_FROM_LOBE */
+#define BDPT_WALK_STATUS_STORED 1u   /* the vertex exists: a real vertex or a ghost */
+#define BDPT_WALK_STATUS_REAL 2u     /* made by a hit */
+#define BDPT_WALK_STATUS_SPECULAR 4u /* the specular byte the pass keeps for this vertex */
+typedef struct bdpt_walk_start {
+  bdpt_ray ray;
+  float color[3];
+  uint32_t unused; /* not read (bdpt_light_emit::light) */
+} bdpt_walk_start; /* 48 bytes: bdpt_light_emit's layout */
+typedef struct bdpt_walk_info {
+  float color[3];
+  uint32_t status; /* BDPT_WALK_STATUS_* */
+} bdpt_walk_info;  /* 16 bytes */
+typedef struct bdpt_walk_desc {
+  uint32_t num;                  /* items; the capacity when numDevice is set */
+  uint32_t steps;                /* 1 .. BDPT_MAX_DEPTH */
+  const uint32_t* numDevice;     /* optional device word: min(*numDevice, num) items */
+  uint32_t matIndex;             /* 0 GGX, 1 Lambertian */
+  uint32_t flags;                /* BDPT_PARAM_SPECULAR_FROM_LOBE, BDPT_WALK_SEED_PER_STEP or 0 */
+  float minT;                    /* tmin of the rays after step 0 (bdpt_params::minT) */
+  uint32_t reserved;             /* 0 */
+  const bdpt_walk_start* starts; /* device, 16-byte aligned, num records */
+  const uint32_t* seeds;         /* device, num RNG states, or steps x num with BDPT_WALK_SEED_PER_STEP */
+  const bdpt_surface* first;     /* optional: device, 16-byte aligned, num records: the predecessor a step-0 ghost copies */
+  const uint8_t* firstSpecular;  /* optional: device, one byte per item (NULL = 0) */
+  const uint8_t* alive;          /* optional: device, one byte per item, 0 = the item has no path */
+  bdpt_surface* vertices;        /* device, 16-byte aligned, steps x num records, [s * num + i] */
+  bdpt_walk_info* info;          /* device, 16-byte aligned, steps x num records */
+  bdpt_bsdf_sample* samples;     /* optional: device, 16-byte aligned, steps x num records */
+  bdpt_hit* hits;                /* optional: device, 16-byte aligned, steps x num records */
+} bdpt_walk_desc;
+int bdpt_walk_query(bdpt_ctx* ctx, const bdpt_walk_desc* desc, void* stream);
 
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
