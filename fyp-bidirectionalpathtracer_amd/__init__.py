@@ -1076,6 +1076,17 @@ class Context:
                     "bdpt_test_area_light_sample")
         return out
 
+    def test_alpha(self, variant, prim, uv):
+        """Test hook bdpt_test_alpha: the any-hit alpha verdict of each (prim, u, v) -> (n,) bool, True where the candidate is
+        ignored.  variant 0: alphaTestFails; 1 and 2: the first and the second slot of alphaTestFails2 (include/bdpt.h)."""
+        import numpy as np
+        prim = np.ascontiguousarray(prim, np.uint32).reshape(-1)
+        uv = np.ascontiguousarray(uv, np.float32).reshape(prim.shape[0], 2)
+        out = np.zeros(prim.shape[0], np.uint8)
+        self._check(self._lib.bdpt_test_alpha(self._h, variant, prim.ctypes.data, uv.ctypes.data, prim.shape[0], out.ctypes.data),
+                    "bdpt_test_alpha")
+        return out != 0
+
     def close(self):
         if self._h:
             self._lib.bdpt_destroy(self._h)

@@ -396,6 +396,7 @@ PROTOTYPES = {
     "bdpt_test_bsdf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bdpt_get_area_light_info": (C.c_int, [C.c_void_p, C.POINTER(AreaLightInfo)]),
     "bdpt_test_area_light_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bdpt_test_alpha": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bdpt_scene_create_cornell": (C.c_void_p, []),
     "bdpt_scene_create_atrium": (C.c_void_p, [C.c_uint32, C.c_uint32]),
     "bdpt_scene_create_atrium_uneven": (C.c_void_p, [C.c_uint32, C.c_uint32]),

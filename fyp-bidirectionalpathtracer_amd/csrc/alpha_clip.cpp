@@ -1,5 +1,6 @@
 // alpha_clip.cpp — see alpha_clip.h.
 #include "alpha_clip.h"
+#include "texture_planes.h"
 
 #include <algorithm>
 #include <cmath>
@@ -119,7 +120,7 @@ bool AlphaClipper::testFails(uint32_t tri, float bu, float bv) const {
     const float x = u * (float)tw - 0.5f, y = v * (float)th - 0.5f;
     const float x0 = std::floor(x), y0 = std::floor(y);
     const float fx = x - x0, fy = y - y0;
-    const int ix0 = wrapHost((int)x0, tw), iy0 = wrapHost((int)y0, th);
+    const int ix0 = wrapHost(texelFloorInt(x0), tw), iy0 = wrapHost(texelFloorInt(y0), th);
     const int ix1 = wrapHost(ix0 + 1, tw), iy1 = wrapHost(iy0 + 1, th);
     const uint8_t* px = t.rgba8;
     const float t00 = (float)px[((size_t)iy0 * tw + (size_t)ix0) * 4 + 3] / 255.0f, t10 = (float)px[((size_t)iy0 * tw + (size_t)ix1) * 4 + 3] / 255.0f;

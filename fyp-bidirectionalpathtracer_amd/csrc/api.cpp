@@ -2750,6 +2750,39 @@ int bdpt_test_area_light_sample(bdpt_ctx* c, uint32_t mode, const uint32_t* stat
   return BDPT_OK;
 }
 
+int bdpt_test_alpha(bdpt_ctx* c, uint32_t variant, const uint32_t* prim, const float* uv, uint32_t n, uint8_t* out_fails) {
+  if (!c || !prim || !uv || !out_fails || variant > 2) return BDPT_E_INVALID;
+  if (!c->haveScene) {
+    fail(c, "test_alpha: no scene");
+    return BDPT_E_STATE;
+  }
+  ENTER(c);
+  for (uint32_t i = 0; i < n; i++)
+    if (prim[i] >= c->numTriangles) {
+      fail(c, "test_alpha: a prim is not a triangle of the scene");
+      return BDPT_E_INVALID;
+    }
+  if (!n) return BDPT_OK;
+  std::vector<void*> pool;
+  const uint32_t* dp = nullptr;
+  const float* duv = nullptr;
+  uint8_t* dout = nullptr;
+  int rc;
+  if ((rc = devUpload(c, pool, &dp, prim, n)) || (rc = devUpload(c, pool, &duv, uv, (size_t)n * 2)) || (rc = devAlloc(c, pool, &dout, (size_t)n))) {
+    freePool(pool);
+    return rc;
+  }
+  launchTestAlpha(c->S, c->alphaTris, c->alphaTris ? c->numAlphaTris : 0u, variant, dp, duv, n, dout, nullptr);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out_fails, dout, (size_t)n, hipMemcpyDeviceToHost);
+  freePool(pool);
+  if (e != hipSuccess) {
+    fail(c, hipGetErrorString(e));
+    return BDPT_E_HIP;
+  }
+  return BDPT_OK;
+}
+
 int bdpt_test_bsdf(bdpt_ctx* c, const float* in, uint32_t n, uint32_t matIndex, float* out) {
   if (!c || !in || !out) return BDPT_E_INVALID;
   ENTER(c);

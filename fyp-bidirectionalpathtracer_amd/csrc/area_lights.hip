@@ -92,6 +92,20 @@ __global__ __launch_bounds__(kWave) void area_count_scan_kernel(const uint32_t* 
   }
 }
 
+// A triangle's alpha-test record: its place in the ascending list of non-opaque triangles (api.cpp alphaTris), kNoAlphaRec
+// for an opaque one
+BD uint32_t alphaRecOf(const uint32_t* __restrict__ alphaTris, uint32_t numAlphaTris, uint32_t t) {
+  uint32_t lo = 0, hi = numAlphaTris;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (alphaTris[mid] < t)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return (lo < numAlphaTris && alphaTris[lo] == t) ? lo : kNoAlphaRec;
+}
+
 __global__ __launch_bounds__(kWave) void area_compact_kernel(SceneDev S, uint32_t numTris, const uint8_t* __restrict__ referenced,
                                                              const uint32_t* __restrict__ blockBase, const uint32_t* __restrict__ alphaTris,
                                                              uint32_t numAlphaTris, float4* __restrict__ emit) {
@@ -103,17 +117,7 @@ __global__ __launch_bounds__(kWave) void area_compact_kernel(SceneDev S, uint32_
   if (!e) return;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t at = blockBase[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  // the triangle's alpha-test record: its place in the ascending list of non-opaque triangles (api.cpp alphaTris)
-  uint32_t lo = 0, hi = numAlphaTris;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (alphaTris[mid] < t)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  const uint32_t rec = (lo < numAlphaTris && alphaTris[lo] == t) ? lo : kNoAlphaRec;
-  emit[at] = make_float4(__uint_as_float(t), __uint_as_float(rec), 0.0f, 0.0f);
+  emit[at] = make_float4(__uint_as_float(t), __uint_as_float(alphaRecOf(alphaTris, numAlphaTris, t)), 0.0f, 0.0f);
 }
 
 // weights w = area * lambda from the current shading records, and each wave's inclusive scan of them
@@ -209,6 +213,30 @@ __global__ __launch_bounds__(kWave) void test_area_kernel(SceneDev S, AreaDev A,
   for (int k = 0; k < 16; k++) out[(size_t)i * 16 + k] = o[k];
 }
 
+// bdpt_test_alpha: the alpha verdict of (prim, u, v) from the device functions the traversal calls.  variant 0:
+// alphaTestFails; 1: alphaTestFails2 with the item in slot 0 and the next item (the first after the last) in slot 1;
+// 2: the slots swapped and the partner's `need` off.  An opaque triangle has no record and passes.
+__global__ __launch_bounds__(kWave) void test_alpha_kernel(SceneDev S, const uint32_t* __restrict__ alphaTris, uint32_t numAlphaTris,
+                                                           uint32_t variant, const uint32_t* __restrict__ prim,
+                                                           const float* __restrict__ uv, uint32_t n, uint8_t* __restrict__ out) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  const uint32_t i = blockIdx.x * kWave + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t j = (i + 1 == n) ? 0u : i + 1;
+  const uint32_t rec = alphaRecOf(alphaTris, numAlphaTris, prim[i]), other = alphaRecOf(alphaTris, numAlphaTris, prim[j]);
+  const float u = uv[(size_t)i * 2], v = uv[(size_t)i * 2 + 1], pu = uv[(size_t)j * 2], pv = uv[(size_t)j * 2 + 1];
+  bool fails = false, partner = false;
+  if (rec != kNoAlphaRec) {
+    if (variant == 0)
+      fails = alphaTestFails(S, rec, u, v);
+    else if (variant == 1)
+      alphaTestFails2(S, true, rec, u, v, other != kNoAlphaRec, other, pu, pv, fails, partner);
+    else
+      alphaTestFails2(S, false, other, pu, pv, true, rec, u, v, partner, fails);
+  }
+  out[i] = fails ? 1 : 0;
+}
+
 }  // namespace
 
 void launchAreaMarkReferenced(const BvhRefitNode* nodes, uint32_t numNodes, const uint4* recs, uint8_t* referenced, hipStream_t st) {
@@ -238,6 +266,12 @@ void launchTestAreaSample(const SceneDev& S, const AreaDev& A, int mode, const u
                           float* out, hipStream_t st) {
   if (!n) return;
   launchWave(test_area_kernel, wavesFor(n), st, S, A, mode, states, points, n, out);
+}
+
+void launchTestAlpha(const SceneDev& S, const uint32_t* alphaTris, uint32_t numAlphaTris, uint32_t variant, const uint32_t* prim,
+                     const float* uv, uint32_t n, uint8_t* out, hipStream_t st) {
+  if (!n) return;
+  launchWave(test_alpha_kernel, wavesFor(n), st, S, alphaTris, numAlphaTris, variant, prim, uv, n, out);
 }
 
 #undef BD

@@ -460,5 +460,8 @@ void launchAreaRefresh(const SceneDev& S, const AreaDev& A, float* blockSum, uin
 // bdpt_test_area_light_sample: mode 0 light-subpath start, mode 1 NEE sample (16 floats per item out; include/bdpt.h)
 void launchTestAreaSample(const SceneDev& S, const AreaDev& A, int mode, const uint32_t* states, const float* points, uint32_t n,
                           float* out, hipStream_t st);
+// bdpt_test_alpha: one lane per (prim, u, v); variant 0 alphaTestFails, 1 and 2 the two slots of alphaTestFails2 (include/bdpt.h)
+void launchTestAlpha(const SceneDev& S, const uint32_t* alphaTris, uint32_t numAlphaTris, uint32_t variant, const uint32_t* prim,
+                     const float* uv, uint32_t n, uint8_t* out, hipStream_t st);
 
 }  // namespace bdpt

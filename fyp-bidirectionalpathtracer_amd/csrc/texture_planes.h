@@ -21,6 +21,16 @@ BDPT_HD uint32_t texPow2Flags(uint32_t w, uint32_t h) {
   return ((w & (w - 1u)) == 0u ? kTexPow2W : 0u) | ((h & (h - 1u)) == 0u ? kTexPow2H : 0u);
 }
 
+// The samplers' float -> int outside the int range (include/bdpt.h "Surface queries"): saturating, NaN -> 0 — what the
+// device's convert instruction does with the plain cast of device_scene.hpp.  Host restatements of the samplers
+// (alpha_clip.cpp; the CPU oracle has its own copy) convert with this, because the plain cast is undefined there in C++.
+BDPT_HD int texelFloorInt(float x0) {
+  if (!(x0 == x0)) return 0;
+  if (x0 >= 2147483648.0f) return INT32_MAX;
+  if (x0 <= -2147483648.0f) return INT32_MIN;
+  return (int)x0;
+}
+
 // wrap addressing: i mod n in [0, n)
 BDPT_HD int wrapi(int i, int n) {
   int m = i % n;

@@ -682,7 +682,28 @@ int bdpt_camera_rays(bdpt_ctx* ctx, const bdpt_gbuffer_params* p, uint32_t width
  * place of the camera position, as the walk passes WorldRayOrigin(): with pinhole camera rays the records equal the
  * G-buffer channels before their half rounding.  The BSDF's roughness is linearRoughness * linearRoughness.  A miss
  * (prim < 0), or a prim that is not a triangle of the scene, writes prim -1, material 0xffffffff and every float 0.  With
- * numHitsDevice set, hits at or beyond min(*numHitsDevice, numHits) are neither read nor written. */
+ * numHitsDevice set, hits at or beyond min(*numHitsDevice, numHits) are neither read nor written.
+ * Hit contract (tests/edge_surfaces.py has the families, DESIGN.md "Edge-case surfaces" the measurements): prim decides
+ * every address; u and v may be anything a float holds — on a corner or an edge, outside the triangle, NaN or infinite —
+ * and the record is that of the fp32 arithmetic as written, bit for bit the CPU oracle's.  The scene's texcoords need not
+ * be finite either (bdpt_set_scene checks positions only; an infinite or NaN texcoord makes every UV of its triangle but
+ * the one at its own corner NaN).
+ *   Texture addressing: a sample at (u, v) of a w x h texture blends the texels around x = u * w - 0.5, y = v * h - 0.5:
+ *     (int)floorf(x) and its successor under wrap addressing, fraction x - floorf(x), likewise in y.  The float -> int
+ *     conversion is the hardware's (v_cvt_i32_f32): exact inside the int range, INT_MAX at and above 2^31, INT_MIN at and
+ *     below -2^31, 0 for NaN; the oracle and every host restatement (csrc/texture_planes.h texelFloorInt) convert the same
+ *     way.  So a texel index is inside the texture whatever the coordinate.  From |x| = 2^23 on the fraction is 0; an
+ *     infinite or NaN x makes the fraction, and with it every texture-derived field, NaN (linearRoughness then is 0.08:
+ *     maxf(0.08, NaN)).  The any-hit alpha test samples the same way; a NaN alpha is not below any threshold: it passes.
+ *   Channel types: the type fields of bdpt_material::flags are 3 bits wide (the normal map's 2).  Every diffuse, specular or
+ *     emissive type other than UNUSED (0) and CONST (1) samples the channel's texture at the hit's UV when the texture id is
+ *     >= 0 and takes the constant factor when it is -1 (the rule of sampleTexture); the alpha test follows the same rule.
+ *     Every shading model other than METAL_ROUGH decodes as SPEC_GLOSS; every normal-map type other than UNUSED and RGB as RG.
+ *   Degenerate frames: an interpolated normal of length 0 (or one whose squared length under- or overflows fp32) gives a NaN
+ *     N; an origin at posW a NaN V; dot(N, V) == 0 flips the normal of a double-sided material (the test is <=); a NaN
+ *     dot(N, V) does not.  With BDPT_SHADE_NORMAL_MAP a bitangent parallel to N, or of length 0, gives a NaN N; a map texel
+ *     whose decoded normal is 0 likewise.  A scene without bitangents, or a material whose texNormal is -1, is shaded
+ *     without the map whatever its map type. */
 typedef struct bdpt_surface {
   float posW[3];
   float dist;             /* length(posW - ray origin) */
@@ -1526,6 +1547,12 @@ int bdpt_test_bsdf(bdpt_ctx* ctx, const float* in, uint32_t n, uint32_t matIndex
  *   mode 1 (NEE sample; points[i]: the receiving point, 3 floats): prim, L.xyz, d, intensity.xyz, b1, b2, x.xyz, 0, 0, 0
  * With no emitter or W == 0 every output is 0.  Errors: mode > 1, a NULL array BDPT_E_INVALID; no scene BDPT_E_STATE. */
 int bdpt_test_area_light_sample(bdpt_ctx* ctx, uint32_t mode, const uint32_t* states, const float* points, uint32_t n, float* out);
+/* Alpha-test known-answer hook: the any-hit alpha verdict of candidate (prim[i], uv[2i], uv[2i+1]) from the device functions
+ * the traversal calls, one lane per item, on host arrays; synchronous.  out_fails[i] = 1 where the candidate is ignored; an
+ * opaque triangle passes.  variant 0: alphaTestFails; 1: alphaTestFails2 with the item in the first slot and item i + 1
+ * (item 0 after the last) in the second; 2: the item in the second slot, the partner in the first with its test switched
+ * off.  Errors: a NULL array, variant > 2 or a prim >= numTriangles BDPT_E_INVALID; no scene BDPT_E_STATE. */
+int bdpt_test_alpha(bdpt_ctx* ctx, uint32_t variant, const uint32_t* prim, const float* uv, uint32_t n, uint8_t* out_fails);
 /* Skinning measurement hook: the skinning kernel of bdpt_update_skinned alone, enqueued on `stream` behind the context's
  * previous call, with the context's device palette as the last BDPT_MEMORY_HOST update staged it (no refit: the scene is
  * left as it was, the skinned streams are rewritten).  path 0: the path bdpt_update_skinned takes, 1: the global-memory

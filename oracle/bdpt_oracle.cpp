@@ -287,13 +287,21 @@ inline int wrapi(int i, int n) {
 inline f4 lerp4(f4 a, f4 b, float s) {
   return f4{a.x + (b.x - a.x) * s, a.y + (b.y - a.y) * s, a.z + (b.z - a.z) * s, a.w + (b.w - a.w) * s};
 }
+// float -> int as the samplers define it outside the int range (include/bdpt.h "Surface queries"): saturating, NaN -> 0.
+// (A plain cast is undefined there; the device's convert instruction saturates.)
+inline int satInt(float x) {
+  if (!(x == x)) return 0;
+  if (x >= 2147483648.0f) return INT32_MAX;
+  if (x <= -2147483648.0f) return INT32_MIN;
+  return (int)x;
+}
 f4 sampleBilinear(const oracle_scene& s, int texId, float u, float v) {
   const Tex& t = s.tex[(size_t)texId];
   float x = u * (float)t.w - 0.5f;
   float y = v * (float)t.h - 0.5f;
   float x0 = floorf(x), y0 = floorf(y);
   float fx = x - x0, fy = y - y0;
-  int ix0 = wrapi((int)x0, (int)t.w), iy0 = wrapi((int)y0, (int)t.h);
+  int ix0 = wrapi(satInt(x0), (int)t.w), iy0 = wrapi(satInt(y0), (int)t.h);
   int ix1 = wrapi(ix0 + 1, (int)t.w), iy1 = wrapi(iy0 + 1, (int)t.h);
   f4 t00 = texel(s, t, ix0, iy0), t10 = texel(s, t, ix1, iy0);
   f4 t01 = texel(s, t, ix0, iy1), t11 = texel(s, t, ix1, iy1);
@@ -342,7 +350,8 @@ bool alphaTestFails(const oracle_scene& s, uint32_t tri, float bu, float bv) {
   const bdpt_material& m = s.mats[s.triMat[tri]];
   float u = 0, v = 0;
   uint32_t mode = BDPT_FLAG_DIFFUSE_TYPE(m.flags);
-  if (mode == BDPT_CHANNEL_TEXTURE && m.texBaseColor >= 0 && s.hasUv) {
+  // the rule of sampleTexture: every type but UNUSED and CONST samples a present texture at the hit's UV
+  if (mode != BDPT_CHANNEL_UNUSED && mode != BDPT_CHANNEL_CONST && m.texBaseColor >= 0 && s.hasUv) {
     float b[3] = {1.0f - bu - bv, bu, bv};
     for (int i = 0; i < 3; i++) {
       uint32_t vi = s.idx[(size_t)tri * 3 + i];
@@ -1746,6 +1755,42 @@ void oracle_trace(const oracle_scene* s, const float* rays, uint32_t n, int mode
       out_tuv[(size_t)i * 3 + 2] = h.prim < 0 ? 0.0f : h.v;
     }
   }
+}
+
+void oracle_shade_hits(const oracle_scene* s, const bdpt_ray* rays, const bdpt_hit* hits, uint32_t n, uint32_t flags,
+                       bdpt_surface* out) {
+  const uint32_t numTris = (uint32_t)(s->idx.size() / 3);
+  for (uint32_t i = 0; i < n; i++) {
+    const float* r = reinterpret_cast<const float*>(&rays[i]);
+    const float* h = reinterpret_cast<const float*>(&hits[i]);
+    int32_t prim;
+    memcpy(&prim, h + 3, 4);
+    bdpt_surface& o = out[i];
+    memset(&o, 0, sizeof(o));
+    if (prim < 0 || (uint32_t)prim >= numTris) {  // bdpt_shade_hits' miss rule
+      o.material = 0xffffffffu;
+      o.prim = -1;
+      continue;
+    }
+    const f3 ro = ld3(r);
+    const ShadingData sd = prepareShadingData(*s, (uint32_t)prim, h[1], h[2], ro, (flags & BDPT_SHADE_NORMAL_MAP) != 0);
+    o.posW[0] = sd.posW.x, o.posW[1] = sd.posW.y, o.posW[2] = sd.posW.z;
+    o.dist = length(sd.posW - ro);
+    o.N[0] = sd.N.x, o.N[1] = sd.N.y, o.N[2] = sd.N.z;
+    o.linearRoughness = sd.linearRoughness;
+    o.V[0] = sd.V.x, o.V[1] = sd.V.y, o.V[2] = sd.V.z;
+    o.IoR = sd.IoR;
+    o.diffuse[0] = sd.diffuse.x, o.diffuse[1] = sd.diffuse.y, o.diffuse[2] = sd.diffuse.z;
+    o.opacity = sd.opacity;
+    o.specular[0] = sd.specular.x, o.specular[1] = sd.specular.y, o.specular[2] = sd.specular.z;
+    o.material = s->triMat[(size_t)prim];
+    o.emissive[0] = sd.emissive.x, o.emissive[1] = sd.emissive.y, o.emissive[2] = sd.emissive.z;
+    o.prim = prim;
+  }
+}
+
+void oracle_alpha_test(const oracle_scene* s, const uint32_t* prim, const float* uv, uint32_t n, uint8_t* fails) {
+  for (uint32_t i = 0; i < n; i++) fails[i] = alphaTestFails(*s, prim[i], uv[(size_t)i * 2], uv[(size_t)i * 2 + 1]) ? 1 : 0;
 }
 
 void oracle_bsdf(const float* in, uint32_t n, uint32_t matIndex, float* out) {

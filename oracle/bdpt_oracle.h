@@ -84,6 +84,13 @@ void oracle_rng(const uint32_t* val0, const uint32_t* val1, uint32_t n, uint32_t
 void oracle_trace(const oracle_scene* s, const float* rays, uint32_t n, int mode, uint32_t flags,
                   int32_t* out_prim, float* out_tuv);
 void oracle_bsdf(const float* in, uint32_t n, uint32_t matIndex, float* out);
+/* bdpt_shade_hits (include/bdpt.h "Surface queries") on host arrays: a loop over prepareShadingData with rays[i]'s origin as
+ * the camera position, flags BDPT_SHADE_*, and the query's miss rule (prim < 0 or not a triangle of the scene). */
+void oracle_shade_hits(const oracle_scene* s, const bdpt_ray* rays, const bdpt_hit* hits, uint32_t n, uint32_t flags,
+                       bdpt_surface* out);
+/* The any-hit alpha test of candidate i: triangle prim[i] (any triangle of the scene; the caller asks only about non-opaque
+ * ones) at barycentrics uv[2i], uv[2i+1].  fails[i] = 1 where the candidate is ignored. */
+void oracle_alpha_test(const oracle_scene* s, const uint32_t* prim, const float* uv, uint32_t n, uint8_t* fails);
 /* Per-record hooks mirroring bdpt_light_query (BDPT_LIGHT_NEE, no emitter table, no hints) and bdpt_connect_query (both
  * modes) of include/bdpt.h: loops over the functions the frame's pixel loop calls, on the queries' input records, writing
  * the queries' output records (host memory).  lights: numLights >= 1 records.  seedsOut, the predecessors and the specular

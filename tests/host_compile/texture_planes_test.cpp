@@ -4,6 +4,7 @@
 //   texture_planes_test wrap N IN OUT     IN: int32 coordinates    OUT: per coordinate int32 wrapT(i, N, pow2), wrapNext(that, N),
 //                                         pow2 from texPow2Flags(N, N)
 //   texture_planes_test flags             prints "w h flags" for a list of sides
+//   texture_planes_test floor IN OUT      IN: float32 values x0 = floorf(x)    OUT: per value int32 texelFloorInt(x0)
 //   texture_planes_test rule              prints "type tex alphaSamplesTexture" for every 3-bit diffuse type
 #include <cstdio>
 #include <cstdlib>
@@ -56,6 +57,16 @@ int main(int argc, char** argv) {
       out[2 * i + 1] = wrapNext(out[2 * i], n);
     }
     writeAll(argv[4], out.data(), out.size() * 4);
+    return 0;
+  }
+  if (argc >= 4 && !std::strcmp(argv[1], "floor")) {
+    const std::vector<unsigned char> in = readAll(argv[2]);
+    const size_t m = in.size() / 4;
+    std::vector<float> x(m);
+    std::vector<int32_t> out(m);
+    std::memcpy(x.data(), in.data(), m * 4);
+    for (size_t i = 0; i < m; i++) out[i] = texelFloorInt(x[i]);
+    writeAll(argv[3], out.data(), out.size() * 4);
     return 0;
   }
   if (argc >= 2 && !std::strcmp(argv[1], "flags")) {

@@ -43,6 +43,8 @@ def load_oracle(abi):
     lib.oracle_rng.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.oracle_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.oracle_bsdf.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.oracle_shade_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.oracle_alpha_test.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.oracle_light_nee.argtypes = [C.POINTER(abi.Light), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float,
                                      C.c_void_p, C.c_void_p]
     lib.oracle_connect_vertices.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
@@ -108,6 +110,25 @@ def connect_camera(abi, cam, width, height, jitter, light, mat_index, min_t, lig
     lib.oracle_connect_camera(C.byref(cam), width, height, _p(jit), _p(light), None if spec is None else _p(spec), len(light), mat_index,
                               min_t, _p(out))
     return out
+
+
+def shade_hits(abi, scene, rays, hits, flags):
+    """oracle_shade_hits: rays (n, 8) float32 (bdpt_ray), hits (n, 4) float32 (bdpt_hit: t, u, v, prim bits) -> (n, 24) float32
+    in the bdpt_surface layout"""
+    lib = load_oracle(abi)
+    rays, hits = _records(rays, 8), _records(hits, 4)
+    out = np.zeros((len(hits), 24), np.float32)
+    lib.oracle_shade_hits(scene, _p(rays), _p(hits), len(hits), flags, _p(out))
+    return out
+
+
+def alpha_test(abi, scene, prim, uv):
+    """oracle_alpha_test: prim (n,) uint32, uv (n, 2) float32 barycentrics -> (n,) bool, True where the candidate is ignored"""
+    lib = load_oracle(abi)
+    prim, uv = np.ascontiguousarray(prim, np.uint32), _records(uv, 2)
+    fails = np.zeros(len(prim), np.uint8)
+    lib.oracle_alpha_test(scene, _p(prim), _p(uv), len(prim), _p(fails))
+    return fails != 0
 
 
 class OracleRender:

@@ -53,12 +53,20 @@ def new_indices(x0, n):
     return ix0, ix1
 
 
+def floor_int(x0):
+    """The samplers' (int)floorf(x) as include/bdpt.h "Surface queries" defines it outside the int range: saturating, NaN -> 0
+    (csrc/texture_planes.h texelFloorInt; a plain astype(int32) is as undefined there as the C cast)."""
+    x0 = np.asarray(x0, np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isnan(x0), 0.0, np.clip(x0, -2.0 ** 31, 2.0 ** 31 - 1)).astype(np.int64).astype(np.int32)
+
+
 def coords(rng, n):
     """Integer floors (int)floorf(u * n - 0.5f) for UVs inside, near and far outside [0, 1], negative ones included."""
     u = np.concatenate([rng.uniform(0, 1, 4000), rng.uniform(-3, 4, 4000), rng.uniform(-1e4, 1e4, 2000),
                         np.array([0.0, 1.0, -1.0, 0.5 / n, 1 - 0.5 / n, -0.5 / n, 2.0, -2.0])]).astype(np.float32)
     x = u * np.float32(n) - np.float32(0.5)
-    x0 = np.floor(x).astype(np.int32)
+    x0 = floor_int(np.floor(x))
     edge = np.array([-(2 ** 31), 2 ** 31 - 1, -(2 ** 31) + 1, -n, -n - 1, n, n - 1, 0, -1], dtype=np.int64)
     return np.concatenate([x0, edge.astype(np.int32)]).astype(np.int32)
 
@@ -95,12 +103,12 @@ def sample(tex, srgb, u, v, new):
     x0, y0 = np.floor(x), np.floor(y)
     fx, fy = x - x0, y - y0
     if not new:
-        ix0, ix1 = old_indices(x0.astype(np.int32), w)
-        iy0, iy1 = old_indices(y0.astype(np.int32), h)
+        ix0, ix1 = old_indices(floor_int(x0), w)
+        iy0, iy1 = old_indices(floor_int(y0), h)
         t = [decode(tex[iy, ix], srgb) for iy, ix in ((iy0, ix0), (iy0, ix1), (iy1, ix0), (iy1, ix1))]
     else:
-        ix0, ix1 = new_indices(x0.astype(np.int32), w)
-        iy0, iy1 = new_indices(y0.astype(np.int32), h)
+        ix0, ix1 = new_indices(floor_int(x0), w)
+        iy0, iy1 = new_indices(floor_int(y0), h)
         flat = np.concatenate([tex.reshape(-1, 4), np.zeros((1, 4), np.uint8)])  # the texture's spare texel
         t = []
         for iy in (iy0, iy1):
@@ -144,8 +152,8 @@ def test_alpha_quad_plane_equals_four_byte_loads(w, h):
     n = 5000
     u = np.concatenate([rng.uniform(0, 1, n), rng.uniform(-4, 5, n), rng.uniform(-2e3, 2e3, n)]).astype(np.float32)
     v = np.concatenate([rng.uniform(0, 1, n), rng.uniform(-4, 5, n), rng.uniform(-2e3, 2e3, n)]).astype(np.float32)
-    x0 = np.floor(u * np.float32(w) - np.float32(0.5)).astype(np.int32)
-    y0 = np.floor(v * np.float32(h) - np.float32(0.5)).astype(np.int32)
+    x0 = floor_int(np.floor(u * np.float32(w) - np.float32(0.5)))
+    y0 = floor_int(np.floor(v * np.float32(h) - np.float32(0.5)))
     ix0, ix1 = old_indices(x0, w)
     iy0, iy1 = old_indices(y0, h)
     old = [tex[iy, ix, 3] for iy, ix in ((iy0, ix0), (iy0, ix1), (iy1, ix0), (iy1, ix1))]
@@ -170,6 +178,34 @@ def test_cpp_wrap_equals_remainder(harness, tmp_path, n):
     o0, o1 = old_indices(x0, n)
     np.testing.assert_array_equal(got[:, 0], o0)
     np.testing.assert_array_equal(got[:, 1], o1)
+
+
+FLOOR_EDGES = np.array([0.0, -0.0, 1.0, -1.0, 2147483520.0, 2147483648.0, 2147483904.0, -2147483520.0, -2147483648.0, -2147483904.0,
+                        1e12, -1e12, 3e38, -3e38, np.inf, -np.inf, np.nan, 16777216.0, -16777217.0], np.float32)
+
+
+def test_cpp_float_to_int_saturates(harness, tmp_path):
+    """texelFloorInt (the host spelling of the samplers' conversion) and floor_int above: the cast inside the int range,
+    INT_MAX / INT_MIN beyond it, 0 for NaN; and the wrapped index of each is inside the texture for every side."""
+    x0 = np.concatenate([FLOOR_EDGES, np.floor(np.random.default_rng(5).uniform(-3e9, 3e9, 2000)).astype(np.float32)])
+    fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
+    x0.tofile(fin)
+    r = subprocess.run([harness, "floor", str(fin), str(fout)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = np.fromfile(fout, dtype=np.int32)
+    np.testing.assert_array_equal(got, floor_int(x0))
+    expect = {2147483520.0: 2147483520, 2147483648.0: 2 ** 31 - 1, 2147483904.0: 2 ** 31 - 1, -2147483648.0: -2 ** 31, -2147483904.0: -2 ** 31,
+              1e12: 2 ** 31 - 1, -3e38: -2 ** 31, np.inf: 2 ** 31 - 1, -np.inf: -2 ** 31}
+    for v, e in expect.items():
+        assert got[np.flatnonzero(x0 == np.float32(v))[0]] == e, v
+    assert got[np.flatnonzero(np.isnan(x0))[0]] == 0
+    inside = np.abs(x0.astype(np.float64)) < 2.0 ** 31
+    np.testing.assert_array_equal(got[inside], x0[inside].astype(np.int64))
+    for n in SIDES:
+        o0, _ = old_indices(got, n)
+        n0, _ = new_indices(got, n)
+        np.testing.assert_array_equal(o0, n0)
+        assert ((n0 >= 0) & (n0 < n)).all()
 
 
 def test_cpp_pow2_flags(harness):
