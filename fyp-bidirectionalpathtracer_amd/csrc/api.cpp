@@ -475,12 +475,12 @@ static int setSceneImpl(bdpt_ctx* c, const bdpt_scene_desc* d) {
           }
           // (a box with a NaN or an infinity in it has no place in a tree built by comparing and sorting boxes)
           const float* p = d->positions + (size_t)vi * 3;
-          if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2])) && bad.load() == 0) bad.store(3);
+          if (!(bvhCoordInRange(p[0]) && bvhCoordInRange(p[1]) && bvhCoordInRange(p[2])) && bad.load() == 0) bad.store(3);
         }
       }
     });
     if (bad.load() == 3) {
-      fail(c, "scene: a triangle has a vertex position that is not finite");
+      fail(c, "scene: a triangle has a vertex position that is not finite or lies beyond 2^60");
       return BDPT_E_INVALID;
     }
     if (bad.load() == 1) {
@@ -888,13 +888,13 @@ int bdpt_update_geometry(bdpt_ctx* c, const bdpt_geometry_update* u, void* strea
     std::atomic<int> bad{0};
     hostParallelFor(nv3, [&](size_t i0, size_t i1) {
       for (size_t i = i0; i < i1; i++)
-        if (!std::isfinite(u->positions[i])) {
+        if (!bvhCoordInRange(u->positions[i])) {  // (bvh.h kBvhMaxCoord; false for a NaN)
           bad.store(1);
           return;
         }
     });
     if (bad.load()) {
-      fail(c, "update: a vertex position is not finite");
+      fail(c, "update: a vertex position is not finite or lies beyond 2^60");
       return BDPT_E_INVALID;
     }
   }

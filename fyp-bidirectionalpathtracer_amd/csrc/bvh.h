@@ -422,11 +422,13 @@ BVH_HD inline void bvhQuantiseNode(const float (*clo)[3], const float (*chi)[3],
         lo4 |= 255u << (8 * k);
         continue;
       }
-      int ql = (int)floorf((clo[k][a] - blo[a]) / sc);
-      ql = ql < 0 ? 0 : (ql > 255 ? 255 : ql);
+      // clamped as floats, then converted: the plain cast of an infinity or a NaN (boxes of positions that overflowed) is
+      // undefined on the host and saturates on the device (NaN -> 0); this is the device's answer on both
+      const float fl = floorf((clo[k][a] - blo[a]) / sc);
+      int ql = !(fl > 0.0f) ? 0 : (fl > 255.0f ? 255 : (int)fl);
       while (ql > 0 && blo[a] + (float)ql * sc > clo[k][a]) ql--;
-      int qh = (int)ceilf((chi[k][a] - blo[a]) / sc);
-      qh = qh < 0 ? 0 : (qh > 255 ? 255 : qh);
+      const float fh = ceilf((chi[k][a] - blo[a]) / sc);
+      int qh = !(fh > 0.0f) ? 0 : (fh > 255.0f ? 255 : (int)fh);
       while (qh < 255 && blo[a] + (float)qh * sc < chi[k][a]) qh++;
       lo4 |= (uint32_t)ql << (8 * k);
       hi4 |= (uint32_t)qh << (8 * k);
@@ -461,14 +463,37 @@ BVH_HD inline float bvhBoxArea(const float* lo, const float* hi) {  // BvhBox::a
   if (dx < 0 || dy < 0 || dz < 0) return 0.0f;
   return 2.0f * (dx * dy + dy * dz + dz * dx);
 }
-// buildBvh's pad from the scene box (the union of the five-point boxes of ALL input triangles)
+// Positions the build and the refit are defined for: every |coordinate| <= kBvhMaxCoord = 2^60 (1.15e18).  Up to there no
+// box extent, squared diagonal or box area leaves the fp32 range (3 (2^61)^2 < 2^128), so the pad and the SAH cost stay
+// finite; bdpt_set_scene and the host-memory updates refuse anything beyond with BDPT_E_INVALID, as they refuse what is
+// not finite.  (Device-memory updates are not inspected: beyond the range the pad overflows and every box is NaN — the
+// records still hold no address that derives from a position.)
+constexpr float kBvhMaxCoord = 1152921504606846976.0f;
+BVH_HD inline bool bvhCoordInRange(float x) { return fabsf(x) <= kBvhMaxCoord; }  // (false for a NaN)
+// buildBvh's pad from the scene box (the union of the five-point boxes of ALL input triangles): what every child box is
+// widened by before it is quantised.  Two terms, the larger one counts:
+//   2e-5 of the diagonal   the rounding of the slab test and of the ray / triangle test, both relative to the distances
+//                          inside the scene;
+//   2^-21 of the largest |coordinate| of the box (at least four ulps of any coordinate)   what is rounded at the size of
+//                          the coordinates themselves: the padded plane lo - pad (half an ulp), bvhQuantiseNode's outward
+//                          check origin + q scale, which rounds to fp32 while the slab test works on the difference
+//                          (origin - ray origin) + q scale without that rounding (half an ulp), and the corners of a
+//                          piece box (v0 + u e1) + v e2 (two roundings, one ulp): two ulps, doubled.
+// The second term only counts for a scene farther from the origin than 42 of its diagonals; nearer, the pad and every
+// record keep the bits of the first term alone.
 BVH_HD inline float bvhPadOf(const float* lo, const float* hi, bool any) {
-  float diag = 0.0f;
+  float diag = 0.0f, big = 0.0f;
   if (any) {
     const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
     diag = sqrtf(dx * dx + dy * dy + dz * dz);
+    for (int a = 0; a < 3; a++) {
+      const float l = fabsf(lo[a]), h = fabsf(hi[a]);
+      big = big < l ? l : big;
+      big = big < h ? h : big;
+    }
   }
-  return 2e-5f * diag + 1e-30f;
+  const float rel = 2e-5f * diag + 1e-30f, ulps = 4.76837158203125e-07f * big;
+  return rel < ulps ? ulps : rel;
 }
 
 // ---- piece-tight refit (BDPT_PREPARE_REFIT_PIECES): a split or clipped reference bounded by its piece ----
@@ -484,8 +509,8 @@ BVH_HD inline float bvhPadOf(const float* lo, const float* hi, bool any) {
 // pad (2e-5 of the scene diagonal) in world units for the largest triangle a scene can hold.  The boxes also keep the
 // refit's `pad`, as every box does.  A reference that is its whole triangle lies inside its leaf's box with `pad` to
 // spare, so its region comes out as all of [0, 1] ("whole") and it takes the plain refit's box: a tree without pieces
-// gets the plain refit's records.  (That needs `pad` to exceed an ulp of the coordinates — a scene nearer to the origin
-// than some 300 of its diagonals — which is the regime in which the build's own pad means anything.)
+// gets the plain refit's records.  (That needs `pad` to exceed an ulp of the coordinates, which bvhPadOf's
+// second term sees to at any distance from the origin.)
 constexpr int kPieceFloats = 6;
 constexpr double kPieceMargin = 1e-5;
 constexpr int kPiecePolyMax = 12;  // a triangle cut by six half-planes: at most nine vertices

@@ -432,14 +432,10 @@ void makeTriangles(const float* positions, const uint32_t* indices, uint32_t nTr
     part[(size_t)th].grow(acc);
   });
   for (const Box& b : part) scene.grow(b);
-  float diag = 0.0f;
-  if (nTris) {
-    float dx = scene.hi[0] - scene.lo[0], dy = scene.hi[1] - scene.lo[1], dz = scene.hi[2] - scene.lo[2];
-    diag = std::sqrt(dx * dx + dy * dy + dz * dz);
-  }
   // Slab tests run in fp32 on boxes that must never reject a hit the triangle test accepts:
-  // pad every box by a small fraction of the scene diagonal (covers rounding in both tests).
-  T.pad = 2e-5f * diag + 1e-30f;
+  // pad every box by a small fraction of the scene diagonal, or by a few ulps of the coordinates where those are
+  // larger (bvh.h bvhPadOf, which the refits share: covers rounding in both tests).
+  T.pad = bvhPadOf(scene.lo, scene.hi, nTris != 0);
   for (int a = 0; a < 3; a++) {
     T.grid.lo[a] = nTris ? (double)scene.lo[a] : 0.0;
     T.grid.ext[a] = nTris ? (double)scene.hi[a] - (double)scene.lo[a] : 0.0;

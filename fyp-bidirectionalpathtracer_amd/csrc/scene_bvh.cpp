@@ -497,6 +497,17 @@ int bdpt_bvh_build_hash(const bdpt_scene_desc* d, int threads, uint64_t* out_has
 
 void* bdpt_host_bvh_create(const bdpt_scene_desc* d, int threads, float splitBudget, float splitBudgetAlpha, int classify, bdpt_bvh_info* info) {
   if (!d || !d->positions || !d->indices || !d->triMaterial || !d->materials) return nullptr;
+  for (size_t i = 0; i < (size_t)d->numTriangles * 3; i++) {  // bdpt_set_scene's check: the vertices triangles use (bvh.h kBvhMaxCoord)
+    if (d->indices[i] >= d->numVertices) return nullptr;
+    const float* p = d->positions + (size_t)d->indices[i] * 3;
+    if (!(bvhCoordInRange(p[0]) && bvhCoordInRange(p[1]) && bvhCoordInRange(p[2]))) {
+      if (info) {  // (the only refusal that leaves a trace: numTriangles = 0, reserved = 1 + the triangle)
+        std::memset(info, 0, sizeof(*info));
+        info->reserved = 1u + (uint32_t)(i / 3);
+      }
+      return nullptr;
+    }
+  }
   HostScene* S = nullptr;
   try {
     S = new HostScene();

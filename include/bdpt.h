@@ -391,7 +391,8 @@ const char* bdpt_last_error(const bdpt_ctx* ctx);
 
 /* Copies the scene and builds its acceleration structure on the context's device (what the reference leaves to the DXR
  * driver: Falcor RtModel.cpp:181-254, RtScene.cpp:220-308).  The caller keeps its arrays.  BDPT_E_INVALID for indices or
- * material ids out of range and for a triangle with a vertex position that is not finite; BDPT_E_NOMEM when host or
+ * material ids out of range and for a triangle with a vertex position that is not finite or beyond 2^60 in magnitude
+ * ("Animated scenes", Range); BDPT_E_NOMEM when host or
  * device memory runs out during the build; BDPT_E_LIMIT past 2^28 triangles / 2^31 records. */
 int bdpt_set_scene(bdpt_ctx* ctx, const bdpt_scene_desc* scene);
 int bdpt_get_bvh_info(const bdpt_ctx* ctx, bdpt_bvh_info* out);
@@ -418,8 +419,8 @@ int bdpt_set_environment(bdpt_ctx* ctx, const bdpt_environment* env);
  * event) for what that call enqueued, which ends with everything of the context's own second stream; bdpt_gbuffer_execute
  * and bdpt_execute calls enqueued after them on the same stream see the new scene.  Work on further streams is ordered by
  * the caller, as for the other calls of this interface.
- * Host inputs (BDPT_MEMORY_HOST) are checked and copied before the call returns: a position that is not finite gives
- * BDPT_E_INVALID and leaves the scene as it was.  Device inputs (BDPT_MEMORY_DEVICE) must stay valid until the stream
+ * Host inputs (BDPT_MEMORY_HOST) are checked and copied before the call returns: a position that is not finite, or
+ * beyond 2^60 (below, "Range"), gives BDPT_E_INVALID and leaves the scene as it was.  Device inputs (BDPT_MEMORY_DEVICE) must stay valid until the stream
  * reaches the update, and their finiteness is the caller's responsibility.
  * After the first update, or after bdpt_prepare(BDPT_PREPARE_REFIT), a device-pointer update neither allocates nor
  * synchronises, so it can be captured into a hipGraph.
@@ -439,7 +440,34 @@ int bdpt_set_environment(bdpt_ctx* ctx, const bdpt_environment* env);
  *   - every query answers exactly as it does on a tree built at the new positions: images are bit-identical, as for the
  *     plain refit;
  *   - the records are a pure function of the built tree and the current positions;
- *   - a tree without split or clipped references gets exactly the plain refit's records. */
+ *   - a tree without split or clipped references gets exactly the plain refit's records.
+ *
+ * What poses an update may bring (bones that scale an axis to zero or mirror, morphs that close a mesh, a world whose
+ * origin is not the model's), and the rules that make "exactly as on a tree built at the new positions" — and, for the
+ * host tests, "exactly as a linear scan over the posed triangles" — hold for them, plain and by pieces:
+ *   - Range.  Every |coordinate| <= 2^60 (1.15e18): up to there no box extent, squared diagonal or box area overflows, and
+ *     bdpt_get_refit_info stays finite.  bdpt_set_scene and host-memory updates answer BDPT_E_INVALID beyond it, as for a
+ *     position that is not finite.  Device-memory updates are not inspected: beyond the range the pad overflows and every
+ *     box is NaN; no address in the tree derives from a position, so queries then miss, nothing else.
+ *   - Far from the origin.  Every box is padded by the larger of 2e-5 of the scene's diagonal and 2^-21 of its largest
+ *     |coordinate| (four ulps): the roundings that happen at the size of the coordinates (the padded planes, the
+ *     quantiser's outward check, the corners of a piece box) add up to two ulps.  The second term counts from 42
+ *     diagonals away from the origin; nearer, every record keeps the bits of the first alone.  At 1e7 extents the whole
+ *     scene is a few fp32 values and nothing can be hit.
+ *   - What the fp32 ray / triangle test itself cannot see is seen by nobody: scaled by 1e13 a scene keeps a few of its
+ *     hits (products of three edge-sized factors overflow), from 1e15 on none, and none below 1e-20.
+ *   - Zero direction components are exact in scenes no wider than 2^35 (3.4e10): the slab test multiplies a node's scale
+ *     by the clamped reciprocal 1e30, which overflows for a node wider than 6.8e10; such rays may miss there.
+ *   - Ill-conditioned hits (a documented limit).  With c = |e1 . (d x e2)| / (|e1| |e2| |d|), the (u, v) of a hit carry
+ *     an error of about 4 eps / c of an edge.  Below c = 2^-6 — a needle (edges parallel up to rounding: the determinant
+ *     is rounding noise, not zero), a sliver, or a ray inside a triangle's plane — the point a linear scan reports can lie
+ *     outside the padded box of the triangle it reports, and a tree, built or refitted, may answer with another triangle
+ *     or a miss.  Which of these a walk gives depends on the order in which it shrinks its interval, so on such a ray two
+ *     walks of the same records — the device's kernels and the host hook's walk — may differ from one another too (one
+ *     ray of 4096 on the courtyard's oblique plane does).  tests/edge_poses.py states the criterion in float64 and the tests count the rays it excuses (a
+ *     flattened scene: 1.6 % of the closest hits).  Storing e1 = e2 = 0 for needles (sine of the corner below
+ *     8 eps) ends these on flattened poses, but changes the records of every scene that holds a needle — the atrium has
+ *     34, the tips of its cone caps — so it waits for a change that may move those hashes (DESIGN.md "Refit"). */
 #define BDPT_MEMORY_HOST 0u
 #define BDPT_MEMORY_DEVICE 1u
 typedef struct bdpt_geometry_update {
