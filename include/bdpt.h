@@ -1381,6 +1381,18 @@ int bdpt_adaptive_reset(bdpt_ctx* ctx, const bdpt_adaptive_state* s, void* strea
  *   active = the number of pixels with mask 1
  *   frame  = mean for every pixel, so that the output always shows the accumulated image; an inactive pixel, which the
  *            next masked frame leaves untouched, keeps showing its mean.
+ * The edges, all of them the lines above taken literally:
+ *   - mask: any non-zero byte is "render"; the update itself writes 0 and 1 only.
+ *   - counts: the test count < maxSamples and the increment are exact in 32 bits (maxSamples up to 2^32 - 1); only the
+ *     casts a, b and nf round, to nearest even from 2^24 + 1 on.  A pixel whose count is already beyond maxSamples is left
+ *     alone and is converged.
+ *   - the comparison is made as written, whatever its sides are.  A quotient that is negative because
+ *     lum(mean) + epsilon < 0 is <= a threshold >= 0: converged.  lum(mean) + epsilon == 0 gives +inf (not converged
+ *     unless the threshold is +inf) or, with m2 == 0, NaN.  m2 < 0 (rounding of a pixel whose frames agree to an ulp, or a
+ *     caller's state) makes sqrtf NaN: not converged before maxSamples.  A NaN threshold never converges before
+ *     maxSamples; nor does a negative one, but for a negative quotient below it; a threshold of 0 or -0.0 converges
+ *     exactly where the quotient is 0 or negative; +inf converges every quotient but NaN at minSamples.
+ *   - non-finite frames, means and m2 propagate by IEEE rules; which NaN a NaN is, is not promised.
  * A block that turns inactive never turns active again (its pixels no longer change), so `active` never grows between
  * resets.  The call neither allocates nor synchronises (read `active` by an async copy) and can be captured; it is ordered
  * behind the context's previous call.  Errors: a NULL ctx, params, state buffer or frame, a blockSize not in
@@ -1404,7 +1416,14 @@ int bdpt_set_splat_buffer(bdpt_ctx* ctx, uint64_t* device_ptr, uint64_t num_u64)
 
 /* out[tile rows] = saturate(out + splat) where the splat count is non-zero.
  * `splat` may be the context's own buffer or a reduced copy holding at least the
- * tile rows at the same full-frame indexing (splat_row0 = first row it holds). */
+ * tile rows at the same full-frame indexing (splat_row0 = first row it holds).
+ * fp32, per channel, in exactly this order:
+ *   v     = (float)word * 2^-32f    the conversion of the 64-bit word rounds ONCE, to nearest even (never through a
+ *                                   double: 2^63 + 2^39 + 1 becomes 2^63 + 2^40); the scaling is exact
+ *   out.c = saturate(out.c + v)     saturate(x) = min(max(x, 0), 1) with saturate(NaN) = +0 and saturate(-0) = +0
+ *   out.w = saturate(out.w + (float)count)
+ * Whatever `out` holds is used as it is (negative, beyond 1, infinite, NaN): the result is in [0, 1] and never a NaN.
+ * A pixel whose count word is 0 is neither read nor written, whatever its colour words hold. */
 int bdpt_resolve(bdpt_ctx* ctx, const uint64_t* splat, uint32_t splat_row0, float* out, void* stream);
 
 /* The same for a buffer that holds the tile's accumulators in tile-local order (4 uint64 per tile pixel): one
@@ -1412,7 +1431,11 @@ int bdpt_resolve(bdpt_ctx* ctx, const uint64_t* splat, uint32_t splat_row0, floa
 int bdpt_resolve_tile(bdpt_ctx* ctx, const uint64_t* tile_splat, float* out, void* stream);
 
 /* Running mean of accumulate.ps.hlsl:28-42 over `numTexels` RGBA32F texels:
- *   cur = accumCount < maxAccumCount ? (accumCount*last + cur)/(accumCount+1) : last;  last = cur. */
+ *   cur = accumCount < maxAccumCount ? (accumCount*last + cur)/(accumCount+1) : last;  last = cur.
+ * fp32 in that order (product, sum, correctly rounded quotient; no contraction; subnormals kept), with
+ * a = (float)accumCount and b = (float)(accumCount + 1), casts that round to nearest even from 2^24 + 1 on.  IEEE
+ * throughout: 0 * inf is NaN (count 0 does not hide a non-finite `last`), a * last may overflow to an infinity where the
+ * mean itself is finite, and which NaN a NaN result is, is not promised. */
 int bdpt_accumulate(bdpt_ctx* ctx, float* lastFrame, float* curFrame, uint32_t accumCount, uint32_t maxAccumCount,
                     uint64_t numTexels, void* stream);
 

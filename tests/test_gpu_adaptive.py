@@ -6,6 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from edge_images import _lum, np_update  # noqa: F401  (the float32 restatement lives with the other readings)
+
 pytestmark = pytest.mark.gpu
 
 RAY_KEYS = ("raysPrimary", "raysEyeExtend", "raysLightExtend", "raysNee", "raysSplat", "raysConnect", "pixelsValid",
@@ -179,34 +181,6 @@ def test_masked_cornell_frame_against_oracle(pkg, ob):
 
 
 # ---- (5) the update against numpy ------------------------------------------------------------------------------------
-def _lum(v):
-    return (f32(0.2126) * v[..., 0] + f32(0.7152) * v[..., 1]) + f32(0.0722) * v[..., 2]
-
-
-def np_update(mean, m2, count, mask, frame, threshold, epsilon, mn, mx, B):
-    """include/bdpt.h "Adaptive sampling", restated in float32."""
-    H, W = count.shape
-    upd = (mask != 0) & (count < mx)
-    a = count.astype(f32)[..., None]
-    b = (count + 1).astype(f32)[..., None]
-    new = (a * mean + frame) / b
-    lc, lo, ln = _lum(frame), _lum(mean), _lum(new)
-    m2n = m2 + (lc - lo) * (lc - ln)
-    mean = np.where(upd[..., None], new, mean).astype(f32)
-    m2 = np.where(upd, m2n, m2).astype(f32)
-    count = np.where(upd, count + 1, count).astype(np.uint32)
-    nf = count.astype(f32)
-    with np.errstate(all="ignore"):
-        rel = np.sqrt(m2 / (nf * (nf - f32(1.0)))) / (_lum(mean) + f32(epsilon))
-    conv = (count >= mx) | ((count >= mn) & (rel <= f32(threshold)))
-    Hb, Wb = (H + B - 1) // B, (W + B - 1) // B
-    unc = np.zeros((Hb * B, Wb * B), bool)
-    unc[:H, :W] = ~conv
-    blk = unc.reshape(Hb, B, Wb, B).any(axis=(1, 3))
-    newmask = np.kron(blk, np.ones((B, B), bool))[:H, :W].astype(np.uint8)
-    return mean, m2, count, newmask, int(newmask.sum()), mean.copy()
-
-
 def _state(torch, mean, m2, count, mask):
     d = {"mean": torch.tensor(mean, device="cuda"), "m2": torch.tensor(m2, device="cuda"),
          "count": torch.tensor(count.view(np.int32), device="cuda"), "mask": torch.tensor(mask, device="cuda"),
