@@ -19,6 +19,7 @@ __all__ = ["abi", "tiling", "Scene", "Context", "FramePipeline", "load_library",
 GBUFFER_CHANNELS = ("WorldPosition", "WorldNormal", "MaterialDiffuse", "MaterialSpecRough", "MaterialExtraParams",
                     "Emissive")
 OUTPUT_CHANNEL = "PipelineOutput"  # ResourceManager::kOutputChannel, SharedUtils/ResourceManager.cpp:22
+AO_CHANNEL = "AmbientOcclusion"  # the channel FramePipeline.ambient_occlusion and bdpt_render --ao write
 
 
 class BdptError(RuntimeError):
@@ -141,6 +142,18 @@ def msaa_jitter(counter_before_increment):
     j = (C.c_float * 2)()
     load_library().bdpt_msaa_jitter(counter_before_increment & 0xFFFFFFFF, j)
     return float(j[0]), float(j[1])
+
+
+def ao_default_radius(scene_desc):
+    """The AO pass's radius for a newly loaded scene, max(0.1, scene radius * 0.05) (CommonPasses/AmbientOcclusionPass.cpp:62),
+    with the scene radius half the length of the bounding box's half extent (Falcor Graphics/Scene/Scene.cpp:92, Utils/AABB.h:113),
+    in fp32 as the host's Scene::getRadius computes it."""
+    import numpy as np
+    f = np.float32
+    p = np.ctypeslib.as_array(scene_desc.positions, (int(scene_desc.numVertices), 3))
+    e = (p.max(axis=0).astype(f) - p.min(axis=0).astype(f)) * f(0.5)
+    radius = np.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2], dtype=f) * f(0.5)
+    return float(max(f(0.1), radius * f(0.05)))
 
 
 def keep_for_stream(stream, arrays):
@@ -730,6 +743,41 @@ class Context:
         self._check(self._lib.bdpt_walk_query(self._h, C.byref(d), stream), "bdpt_walk_query")
         return tuple(t.view(torch.float32) if t.dtype == torch.int32 else t for t in out)
 
+    # ---- ambient occlusion (include/bdpt.h "Ambient occlusion") ----
+    @staticmethod
+    def _ao_samples(what, samples):
+        if isinstance(samples, bool) or not isinstance(samples, int) or not 1 <= samples <= abi.AO_MAX_SAMPLES:
+            raise BdptError(f"{what}: samples must be an integer in 1 .. {abi.AO_MAX_SAMPLES}, not {samples!r}")
+        return samples
+
+    def ambient_occlusion(self, surfaces, seeds, samples, radius, min_t=1e-4, alive=None, out=None, counts=None, seeds_out=None,
+                          count=None, stream=None):
+        """bdpt_ao_query: `samples` (1 .. 64) cosine-weighted any-hit rays per (N, 24) bdpt_surface record (posW, N and prim
+        are read) inside (min_t, radius), in one launch — the loop sample_bsdf(mat_index=1) -> rays -> trace_rays("any") ->
+        count, bit for bit.  seeds (N,) uint32 / int32 RNG states; each sample takes two draws.  Returns (N,) float32: the
+        share of unoccluded samples; a miss record (prim < 0), or an item whose `alive` byte is 0, gives 1 without a draw.
+        GPU tensors only: alive (N,) uint8; counts (N,) takes the unoccluded samples (for exact accumulation over frames);
+        seeds_out (N,) the states after 2 * samples draws (it may be `seeds`).  `out` and `count` as for the other queries."""
+        import torch
+        records, words = (torch.float32, torch.int32), (torch.int32, torch.uint32)  # the dtypes a record / a 32-bit word may have
+        samples = self._ao_samples("ambient_occlusion", samples)
+        extras = [("alive", alive, None, (torch.uint8,)), ("counts", counts, None, words), ("seeds_out", seeds_out, None, words)]
+
+        def run(ptrs, n, cnt, res):
+            d = abi.AoDesc()
+            d.num, d.samples, d.numDevice, d.radius, d.minT = n, samples, cnt, float(radius), float(min_t)
+            d.surfaces, d.seeds, d.ao = ptrs[0], ptrs[1], res
+            d.alive, d.counts, d.seedsOut = (None if t is None else t.data_ptr() for t in (alive, counts, seeds_out))
+            return self._lib.bdpt_ao_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("ambient_occlusion", [("surfaces", surfaces, 24, records), ("seeds", seeds, None, words)],
+                                   (None, (torch.float32,)), run, out, count, extras=extras, fn="bdpt_ao_query")
+
+    def ao_execute(self, params, gbuffer, out_ptr, stream=None):
+        """bdpt_ao_execute: the reference's AO pass on the context's tile pixels — abi.AoParams (frameCount, radius, minT,
+        samples), the full-frame G-buffer, and the full-frame RGBA32F image at `out_ptr`, which gets (ao, ao, ao, 1)."""
+        self._check(self._lib.bdpt_ao_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_ao_execute")
+
     @staticmethod
     def _bsdf_mode(what, mat_index, from_lobe):
         if mat_index not in (0, 1) or isinstance(mat_index, bool):
@@ -1249,6 +1297,9 @@ class FramePipeline:
         self.gb = GBuffer(*[self.channels[n].data_ptr() for n in GBUFFER_CHANNELS])
         self.gbuffer_frame = 0xdeadbeef
         self.bdpt_frame = 0x1337
+        self.ao_frame = 0  # CommonPasses/AmbientOcclusionPass.h:54
+        self.last_ao_params = None
+        self._ao_radius = None  # the pass's default radius for the scene, made on first use
         self.accum_count = 0
         self.env_color = (0.5, 0.5, 0.8, 1.0)  # SharedUtils/ResourceManager.cpp:77-87 default environment
         self.use_jitter = True
@@ -1489,6 +1540,30 @@ class FramePipeline:
         res = self.ctx.motion_query(hits, out, count, self._stream_ptr())
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (hits, count, res))
         return res
+
+    def ambient_occlusion(self, samples=1, radius=None):
+        """The reference's AmbientOcclusionPass on this pipeline's G-buffer as it stands (render_frame, or a gbuffer_execute
+        of the caller's, fills it) and stream: Context.ao_execute with the pass's frame counter (from 0, one per call:
+        CommonPasses/AmbientOcclusionPass.h:54, .cpp:86), the pipeline's min_t and `samples` rays per pixel (1 .. 64; the pass's
+        default 1).  radius=None is the pass's default for the scene, ao_default_radius.  Returns the (H, W, 4) float32
+        channel "AmbientOcclusion" ((ao, ao, ao, 1); a tile or stripes pipeline writes its own rows), also in ``channels``;
+        ``last_ao_params`` keeps the abi.AoParams used."""
+        p = abi.AoParams()
+        p.samples = Context._ao_samples("ambient_occlusion", samples)
+        if radius is None:
+            if self._ao_radius is None:  # once per pipeline, as the pass's initScene: the scene's vertices as loaded
+                self._ao_radius = ao_default_radius(self.scene.desc)
+            radius = self._ao_radius
+        p.radius = float(radius)
+        p.minT, p.frameCount = self.min_t, self.ao_frame & 0xFFFFFFFF
+        if AO_CHANNEL not in self.channels:
+            with self.torch.cuda.device(self.dev):
+                self.channels[AO_CHANNEL] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
+        out = self.channels[AO_CHANNEL]
+        self.ctx.ao_execute(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
+        self.ao_frame += 1
+        self.last_ao_params = p
+        return out
 
     def set_lights(self, lights):
         """Move the scene's lights (Context.set_lights on this pipeline's stream); accumulation restarts."""

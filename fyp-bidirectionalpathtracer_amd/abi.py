@@ -53,6 +53,7 @@ CONNECT_VERTICES, CONNECT_CAMERA = 0, 1
 CONNECT_STATUS_NONZERO, CONNECT_STATUS_PIXEL = 1, 2
 WALK_SEED_PER_STEP = 1
 WALK_STATUS_STORED, WALK_STATUS_REAL, WALK_STATUS_SPECULAR = 1, 2, 4
+AO_MAX_SAMPLES = 64
 
 
 class Material(C.Structure):
@@ -282,6 +283,17 @@ class WalkDesc(C.Structure):
                 ("info", C.c_void_p), ("samples", C.c_void_p), ("hits", C.c_void_p)]
 
 
+class AoDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("samples", C.c_uint32), ("numDevice", C.c_void_p), ("radius", C.c_float), ("minT", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32), ("surfaces", C.c_void_p), ("seeds", C.c_void_p), ("alive", C.c_void_p),
+                ("ao", C.c_void_p), ("counts", C.c_void_p), ("seedsOut", C.c_void_p)]
+
+
+class AoParams(C.Structure):
+    _fields_ = [("frameCount", C.c_uint32), ("radius", C.c_float), ("minT", C.c_float), ("samples", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 BMFR_MAX_PLANES = BDPT_MAX_LIGHTS + 2
 
 
@@ -337,6 +349,8 @@ PROTOTYPES = {
     "bdpt_connect_query": (C.c_int, [C.c_void_p, C.POINTER(ConnectDesc), C.c_void_p]),
     "bdpt_splat_add": (C.c_int, [C.c_void_p, C.POINTER(SplatDesc), C.c_void_p]),
     "bdpt_walk_query": (C.c_int, [C.c_void_p, C.POINTER(WalkDesc), C.c_void_p]),
+    "bdpt_ao_query": (C.c_int, [C.c_void_p, C.POINTER(AoDesc), C.c_void_p]),
+    "bdpt_ao_execute": (C.c_int, [C.c_void_p, C.POINTER(AoParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit_pieces": (C.c_int, [C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),

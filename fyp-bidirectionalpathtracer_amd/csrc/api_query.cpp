@@ -1,8 +1,8 @@
 // api_query.cpp — the per-item queries of the C ABI (include/bdpt.h): bdpt_trace_rays, bdpt_camera_rays, bdpt_shade_hits,
-// bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query and bdpt_motion_query, on a caller's arrays in
-// device memory.  Every one checks its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags
-// and what goes together (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call
-// enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
+// bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query, bdpt_ao_query and bdpt_motion_query, on a
+// caller's arrays in device memory, and bdpt_ao_execute, the same kernel on the tile's G-buffer pixels.  Every one checks
+// its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags and what goes together
+// (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
 // first use of the emitter table), so all can be captured into a hipGraph.
 #include <cstddef>
 #include <string>
@@ -248,6 +248,52 @@ int bdpt_walk_query(bdpt_ctx* c, const bdpt_walk_desc* d, void* stream) {
     Q.steps = d->steps;
     Q.seedPerStep = (d->flags & BDPT_WALK_SEED_PER_STEP) ? 1u : 0u;
     launchWalkQuery(c->S, Q, d->matIndex == 0, (d->flags & BDPT_PARAM_SPECULAR_FROM_LOBE) != 0, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+int bdpt_ao_query(bdpt_ctx* c, const bdpt_ao_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "ao_query")) return rc;
+  if (!d->samples || d->samples > BDPT_AO_MAX_SAMPLES || d->flags || d->reserved)
+    return refuse(c, BDPT_E_INVALID, "ao_query", "samples outside 1 .. BDPT_AO_MAX_SAMPLES, or non-zero flags or reserved");
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->surfaces, 16) || !aligned(d->seeds, 4) || !aligned(d->ao, 4) || (d->counts && !aligned(d->counts, 4)) ||
+      (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "ao_query", "surfaces, seeds, ao, counts, seedsOut or numDevice missing or not aligned (records 16 bytes, words 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    AoDev A{};
+    A.surf = f4(d->surfaces);
+    A.seeds = d->seeds;
+    A.alive = d->alive;
+    A.ao = d->ao;
+    A.counts = d->counts;
+    A.seedsOut = d->seedsOut;
+    A.range = {d->num, d->numDevice, d->minT};
+    A.radius = d->radius;
+    A.samples = d->samples;
+    launchAo(c->S, A, false, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+int bdpt_ao_execute(bdpt_ctx* c, const bdpt_ao_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
+  if (!c || !p || !gb) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "ao_execute")) return rc;
+  if (!c->haveSize) return refuse(c, BDPT_E_STATE, "ao_execute", "no size (bdpt_resize first)");
+  if (!p->samples || p->samples > BDPT_AO_MAX_SAMPLES || p->reserved)
+    return refuse(c, BDPT_E_INVALID, "ao_execute", "samples outside 1 .. BDPT_AO_MAX_SAMPLES, or non-zero reserved");
+  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(out, 16))
+    return refuse(c, BDPT_E_INVALID, "ao_execute", "worldPosition, worldNormal or out missing or not aligned (16 bytes; worldNormal 8)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    AoDev A{};
+    A.gbPosition = f4(gb->worldPosition);
+    A.gbNormal = gb->worldNormal;
+    A.pix = c->P.pix;
+    A.out = f4(out);
+    A.range = {c->P.Np, nullptr, p->minT};
+    A.radius = p->radius;
+    A.samples = p->samples;
+    A.frameCount = p->frameCount;
+    launchAo(c->S, A, true, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 

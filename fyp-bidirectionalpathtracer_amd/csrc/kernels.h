@@ -308,6 +308,7 @@ struct LaunchGrids {
   uint32_t shadow[2] = {0, 0};        // [COUNT]
   uint32_t rays[3] = {0, 0, 0};       // [mode] (trace_rays.hip)
   uint32_t walkQuery[2] = {0, 0};     // [GGX] (walk_query.hip)
+  uint32_t ao[2] = {0, 0};            // [G-buffer source] (ao.hip)
 };
 // both random walks of the frame: one persistent launch (trace + hit/miss shading in place)
 void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,
@@ -402,6 +403,26 @@ struct WalkQueryDev {
 // `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
 void launchWalkQuery(const SceneDev& S, const WalkQueryDev& Q, bool ggx, bool fromLobe, unsigned long long* cursor, LaunchGrids& G,
                      int numCUs, hipStream_t st);
+// ao.hip: bdpt_ao_query (items are bdpt_surface records) and bdpt_ao_execute (items are the tile's pixels, read from the
+// G-buffer).  `samples` any-hit rays per alive item from its position inside (range.minT, radius).
+struct AoDev {
+  const float4* surf;        // query: bdpt_surface records (six float4 each; posW, N and prim are read)
+  const uint32_t* seeds;     // query: one RNG state per item
+  const uint8_t* alive;      // query, optional: 0 = the item is dead
+  float* ao;                 // query: count / samples per item
+  uint32_t* counts;          // query, optional: unoccluded samples per item
+  uint32_t* seedsOut;        // query, optional: the state after 2 * samples draws (a dead item's: unchanged)
+  const float4* gbPosition;  // execute: WorldPosition of the full frame (w != 0: geometry)
+  const uint16_t* gbNormal;  // execute: WorldNormal (half4) of the full frame
+  const uint32_t* pix;       // execute: the tile's pixels (PathBuf::pix); the seed is initRand(pix, frameCount)
+  float4* out;               // execute: full-frame RGBA32F, (ao, ao, ao, 1) at the tile's pixels
+  QueryRange range;          // execute: cap = the tile's pixel count, no device word
+  float radius;              // tmax of the rays
+  uint32_t samples;          // 1 .. 64
+  uint32_t frameCount;       // execute
+};
+// `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
+void launchAo(const SceneDev& S, const AoDev& A, bool gbuffer, unsigned long long* cursor, LaunchGrids& G, int numCUs, hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,

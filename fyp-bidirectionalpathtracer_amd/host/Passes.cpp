@@ -618,6 +618,57 @@ void LightProbeGBufferPass::execute(RenderContext* pRenderContext) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// AmbientOcclusionPass (CommonPasses/AmbientOcclusionPass.cpp:32-96)
+// ------------------------------------------------------------------------------------------------
+bool AmbientOcclusionPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
+  mpResManager = pResManager;
+  // default-format requests: behind a G-buffer pass they lose against its formats, as in the reference (.cpp:38-40)
+  mPositionIndex = mpResManager->requestTextureResource("WorldPosition");
+  mNormalIndex = mpResManager->requestTextureResource("WorldNormal");
+  mOutputIndex = mpResManager->requestTextureResource(mOutputTexName);
+  mpRays = RayLaunch::create(pRenderContext);
+  if (!mpRays) return false;
+  if (mpScene) mpRays->setScene(mpScene);
+  return true;
+}
+void AmbientOcclusionPass::initScene(RenderContext*, Scene::SharedPtr pScene) {
+  mpScene = pScene;
+  if (!mpScene) return;
+  if (mpRays) mpRays->setScene(mpScene);
+  const float r = mpScene->getRadius() * 0.05f;  // .cpp:62: the default radius of a newly loaded scene
+  mAORadius = r > 0.1f ? r : 0.1f;
+}
+void AmbientOcclusionPass::renderGui(Gui* pGui) {
+  int dirty = 0;
+  dirty |= (int)pGui->addFloatVar("AO radius", mAORadius, 1e-4f, 1e38f, mAORadius * 0.01f);
+  dirty |= (int)pGui->addIntVar("Num AO Rays", mNumRaysPerPixel, 1, (int)BDPT_AO_MAX_SAMPLES);
+  if (dirty) setRefreshFlag();
+}
+void AmbientOcclusionPass::execute(RenderContext* pRenderContext) {
+  Texture::SharedPtr pDstTex = mpResManager->getClearedTexture(mOutputTexName, vec4{0.0f, 0.0f, 0.0f, 0.0f});
+  if (!pDstTex || !mpRays || !mpRays->readyToRender()) return;  // silent no-op, .cpp:82
+  Texture::SharedPtr pos = mpResManager->getTexture("WorldPosition"), nrm = mpResManager->getTexture("WorldNormal");
+  if (!pos || !nrm || pos->getFormat() != ResourceFormat::RGBA32Float || nrm->getFormat() != ResourceFormat::RGBA16Float ||
+      pDstTex->getFormat() != ResourceFormat::RGBA32Float) {
+    std::fprintf(stderr, "[AmbientOcclusionPass] needs WorldPosition (RGBA32F) and WorldNormal (RGBA16F) of a G-buffer pass and an RGBA32F output\n");
+    return;
+  }
+  if (!mpRays->ensureSize(pDstTex->getWidth(), pDstTex->getHeight())) return;
+  bdpt_gbuffer gb;
+  std::memset(&gb, 0, sizeof(gb));
+  gb.worldPosition = (float*)pos->getDevicePointer();
+  gb.worldNormal = (uint16_t*)nrm->getDevicePointer();
+  bdpt_ao_params p;
+  std::memset(&p, 0, sizeof(p));
+  p.frameCount = mFrameCount++;  // .cpp:86
+  p.radius = mAORadius;
+  p.minT = mpResManager->getMinTDist();
+  p.samples = (uint32_t)mNumRaysPerPixel;
+  if (bdpt_ao_execute(mpRays->ctx(), &p, &gb, (float*)pDstTex->getDevicePointer(), pRenderContext->getStream()) != BDPT_OK)
+    std::fprintf(stderr, "[AmbientOcclusionPass] %s\n", mpRays->lastError());
+}
+
+// ------------------------------------------------------------------------------------------------
 // BDPTPass (BidirectionalPathtracing/Passes/BDPTPass.cpp:23-107)
 // ------------------------------------------------------------------------------------------------
 bool BDPTPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
@@ -1097,6 +1148,20 @@ bool LightProbeGBufferPass::loadState(RenderContext*, const uint8_t* data, size_
   if (size != 16) return false;
   if (get32(data + 4) != ((mUseThinLens ? 1u : 0u) | (mUseJitter ? 2u : 0u))) return false;
   if (mUseThinLens && (get32(data + 8) != floatBits(mFStop) || get32(data + 12) != floatBits(mFocalLength))) return false;
+  mFrameCount = get32(data);
+  return true;
+}
+void AmbientOcclusionPass::saveState(RenderContext*, std::vector<uint8_t>& out) {
+  put32(out, mFrameCount);
+  put32(out, (uint32_t)mNumRaysPerPixel);
+  put32(out, floatBits(mAORadius));
+  put32(out, floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f));
+}
+bool AmbientOcclusionPass::loadState(RenderContext*, const uint8_t* data, size_t size) {
+  if (size != 16) return false;
+  if (get32(data + 4) != (uint32_t)mNumRaysPerPixel || get32(data + 8) != floatBits(mAORadius) ||
+      get32(data + 12) != floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f))
+    return false;
   mFrameCount = get32(data);
   return true;
 }

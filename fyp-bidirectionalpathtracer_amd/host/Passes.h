@@ -3,6 +3,7 @@
 //   LightProbeGBufferPass   CommonPasses/LightProbeGBufferPass.{h,cpp}
 //   BDPTPass                BidirectionalPathtracing/Passes/BDPTPass.{h,cpp}
 //   SimpleAccumulationPass  CommonPasses/SimpleAccumulationPass.{h,cpp}
+// the framework's ambient occlusion pass, AmbientOcclusionPass (CommonPasses/AmbientOcclusionPass.{h,cpp}),
 // plus RayLaunch, the thin launch wrapper they hold (SharedUtils/RayLaunch.h:85-135): here it owns
 // one bdpt_ctx and forwards to the C ABI of include/bdpt.h instead of building a DXR state object.
 #pragma once
@@ -171,6 +172,33 @@ class SimpleAccumulationPass : public RenderPass {
   uint32_t mAccumCount = 0;
   int32_t mCountLimit = 100;
   const int32_t mMaxCountLimit = 10000;
+};
+
+// Ray traced ambient occlusion (CommonPasses/AmbientOcclusionPass.{h,cpp}): WorldPosition and WorldNormal in, the output
+// channel out, the reference's GUI state and defaults.  Its ray generation shader is bdpt_ao_execute.
+class AmbientOcclusionPass : public RenderPass {
+ public:
+  using SharedPtr = std::shared_ptr<AmbientOcclusionPass>;
+  static SharedPtr create(const std::string& outBuf = ResourceManager::kOutputChannel) { return SharedPtr(new AmbientOcclusionPass(outBuf)); }
+
+ protected:
+  AmbientOcclusionPass(const std::string& outBuf) : RenderPass("Ambient Occlusion Rays", "Ambient Occlusion Options") { mOutputTexName = outBuf; }
+  bool initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) override;
+  void initScene(RenderContext* pRenderContext, Scene::SharedPtr pScene) override;
+  void renderGui(Gui* pGui) override;
+  void execute(RenderContext* pRenderContext) override;
+  bool requiresScene() override { return true; }
+  bool usesRayTracing() override { return true; }
+  void saveState(RenderContext* pRenderContext, std::vector<uint8_t>& out) override;
+  bool loadState(RenderContext* pRenderContext, const uint8_t* data, size_t size) override;
+
+  RayLaunch::SharedPtr mpRays;
+  Scene::SharedPtr mpScene;
+  float mAORadius = 0.0f;        // AmbientOcclusionPass.h:53; initScene sets the scene's default
+  uint32_t mFrameCount = 0;      // AmbientOcclusionPass.h:54
+  int32_t mNumRaysPerPixel = 1;  // AmbientOcclusionPass.h:55
+  int32_t mPositionIndex = -1, mNormalIndex = -1, mOutputIndex = -1;
+  std::string mOutputTexName;
 };
 
 // BMFR denoiser pass (BidirectionalPathtracing/Passes/DenoisePass.{h,cpp}): same channels, switches and defaults

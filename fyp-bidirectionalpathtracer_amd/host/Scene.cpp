@@ -60,6 +60,18 @@ void Scene::addQuad(float3 a, float3 b, float3 c, float3 d, uint32_t material) {
   addTriangle(i0, i2, i3, material);
 }
 
+float Scene::getRadius() const {
+  if (positions.size() < 3) return 0.0f;
+  float lo[3] = {positions[0], positions[1], positions[2]}, hi[3] = {positions[0], positions[1], positions[2]};
+  for (size_t i = 3; i + 2 < positions.size(); i += 3)
+    for (int k = 0; k < 3; k++) {
+      lo[k] = positions[i + k] < lo[k] ? positions[i + k] : lo[k];
+      hi[k] = positions[i + k] > hi[k] ? positions[i + k] : hi[k];
+    }
+  const float ex = (hi[0] - lo[0]) * 0.5f, ey = (hi[1] - lo[1]) * 0.5f, ez = (hi[2] - lo[2]) * 0.5f;
+  return std::sqrt(ex * ex + ey * ey + ez * ez) * 0.5f;
+}
+
 void Scene::addDefaultLightIfNone() {
   if (!lights.empty()) return;
   bdpt_light l{};

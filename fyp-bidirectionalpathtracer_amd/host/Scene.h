@@ -85,6 +85,9 @@ class Scene {
   uint32_t getTriangleCount() const { return (uint32_t)(indices.size() / 3); }
   uint32_t getVertexCount() const { return (uint32_t)(positions.size() / 3); }
   uint32_t getLightCount() const { return (uint32_t)lights.size(); }
+  // Scene::getRadius (Falcor Graphics/Scene/Scene.cpp:92): half the length of the bounding box's half extent
+  // (Utils/AABB.h:113), of the positions as loaded.
+  float getRadius() const;
   Camera::SharedPtr getActiveCamera() const { return mCamera; }
   void setActiveCamera(Camera::SharedPtr c) { mCamera = c; }
   // SceneLoaderWrapper.cpp:71-78: a scene without lights gets this directional light.

@@ -1,6 +1,8 @@
 // main.cpp — headless counterpart of BidirectionalPathtracing/Main.cpp:9-29: the same pipeline
 // (G-buffer pass -> BDPT pass -> accumulation pass -> BMFR denoiser, which is off unless --denoise /
 // --denoise-regression tick its boxes), run for a number of frames, output written as a PFM image.
+// `--ao N` runs the G-buffer pass and the ambient occlusion pass instead (CommonPasses/AmbientOcclusionPass.cpp) and
+// writes the AO channel.
 //
 // Multi-GPU: `--gpus N` runs N such pipelines, one per GPU, each on a host thread of its own
 // with its own RCCL communicator (ncclCommInitAll); `--rank R --world N --id-file F` is the same for one PROCESS per
@@ -43,6 +45,9 @@ struct Options {
   float sway = 0.0f;  // > 0: an animated scene — before every frame the vertices move by up to this fraction of the scene's extent
   bool noMotion = false;  // --sway / --bend with --denoise: keep the denoiser's static-scene reprojection (for comparison)
   bool tightRefit = false;  // --sway / --bend: refit split and alpha-clipped references by their piece (BDPT_PREPARE_REFIT_PIECES)
+  int ao = -1;             // --ao N: render the G-buffer and the ambient occlusion pass (N rays per pixel) instead of the BDPT pipeline
+  float aoRadius = 0.0f;   // --ao-radius R (with --ao, > 0); not given: the pass's default for the scene
+  bool aoRadiusSet = false;
   float bend = 0.0f;  // > 0: a skinned scene — a small rig along the scene's height, bent by up to this angle (radians) before every frame
 };
 
@@ -112,13 +117,14 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   }
   // add the passes to the rendering pipeline, as Main.cpp:12-18 does
   pipeline->setPass(0, LightProbeGBufferPass::create());
-  {
+  const size_t numPasses = o.ao >= 0 ? 2 : 4;
+  if (o.ao >= 0) {  // --ao: the G-buffer and the ambient occlusion pass, which writes the output channel
+    pipeline->setPass(1, AmbientOcclusionPass::create(ResourceManager::kOutputChannel));
+  } else {
     BDPTPass::SharedPtr bdpt = BDPTPass::create(ResourceManager::kOutputChannel);
     if (o.areaLights) bdpt->setParamFlags(BDPT_PARAM_AREA_LIGHTS);
     pipeline->setPass(1, bdpt);
-  }
-  pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
-  {
+    pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
     BlockwiseMultiOrderFeatureRegression::SharedPtr bmfr = BlockwiseMultiOrderFeatureRegression::create();
     // an animated scene under the denoiser: reproject through the previous pose (whole-frame pipelines)
     bmfr->setMotion(o.denoise && (o.sway > 0.0f || o.bend > 0.0f) && !o.noMotion && !tiled);
@@ -136,7 +142,7 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
     std::fprintf(stderr, "bdpt_render: bad tiling (rank %u of %u)\n", rank, world);
     return false;
   }
-  if (!pipeline->initialize(pScene) || pipeline->getPassCount() != 4) {
+  if (!pipeline->initialize(pScene) || pipeline->getPassCount() != numPasses) {
     std::fprintf(stderr, "pipeline initialisation failed (no GPU?)\n");
     return false;
   }
@@ -151,6 +157,8 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   gui.overrides["Max frames to accumulate"] = o.accumLimit;
   if (o.denoise) gui.overrides["Ignore the denoise stage"] = 1;  // the check box's label while it is off (DenoisePass.cpp:139)
   if (o.denoiseRegression) gui.overrides["Skip Regression"] = 1;
+  if (o.ao >= 0) gui.overrides["Num AO Rays"] = o.ao;
+  if (o.ao >= 0 && o.aoRadiusSet) gui.overrides["AO radius"] = o.aoRadius;
   pipeline->applyGui(&gui);
   if (!o.resume.empty() && !pipeline->loadCheckpoint(o.resume)) {  // continue an earlier run's frame sequence
     std::fprintf(stderr, "bdpt_render: cannot resume from %s (missing, or written for other passes / another frame size)\n", o.resume.c_str());
@@ -300,8 +308,12 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
   if (writer) {
     double mean = 0;
     for (size_t i = 0; i < img.size(); i += 4) mean += img[i] + img[i + 1] + img[i + 2];
-    std::printf("%s %ux%u depth %d mat %d: %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H, o.depth, o.mat,
-                o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
+    if (o.ao >= 0)
+      std::printf("%s %ux%u ambient occlusion, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean ao %.6f", o.scene.c_str(), o.W, o.H,
+                  o.ao, o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
+    else
+      std::printf("%s %ux%u depth %d mat %d: %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H, o.depth, o.mat,
+                  o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
     if (tiled) std::printf(", %u GPU%s (interleaved stripes of %u rows, RCCL reduce-scatter + all-gather)", world, world == 1 ? "" : "s",
                            bdpt_stripe_rows(o.H, world));
     if (o.denoise && (o.sway > 0.0f || o.bend > 0.0f) && !o.noMotion && !tiled) std::printf(", denoiser history reprojected through the previous pose");
@@ -352,6 +364,8 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--warmup")) o.warmup = std::atoi(v);  // of --frames: rendered before the clock starts (first-use allocations)
     else if (const char* v = next("--sway")) o.sway = (float)std::atof(v);
     else if (const char* v = next("--bend")) o.bend = (float)std::atof(v);
+    else if (const char* v = next("--ao")) o.ao = std::max(0, std::atoi(v));
+    else if (const char* v = next("--ao-radius")) o.aoRadius = (float)std::atof(v), o.aoRadiusSet = true;
     else if (std::strcmp(argv[i], "--no-motion") == 0) o.noMotion = true;
     else if (std::strcmp(argv[i], "--tight-refit") == 0) o.tightRefit = true;
     else if (const char* v = next("--gpus")) o.gpus = std::atoi(v);
@@ -362,10 +376,25 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }
+  }
+  if (o.ao >= 0 && (o.ao < 1 || o.ao > (int)BDPT_AO_MAX_SAMPLES || o.gpus > 0 || o.world > 0 || (o.aoRadiusSet && !(o.aoRadius > 0.0f)))) {
+    std::fprintf(stderr, "bdpt_render: --ao N needs N in 1 .. %u rays per pixel, --ao-radius R > 0 when given, and one GPU (no --gpus / --world)\n",
+                 BDPT_AO_MAX_SAMPLES);
+    return 2;
+  }
+  // --ao replaces the BDPT, accumulation and denoise passes: the switches only they read are refused, not ignored
+  if (o.ao >= 0 && (o.denoise || o.areaLights || o.noMotion)) {
+    std::fprintf(stderr, "bdpt_render: --ao N renders the G-buffer and the ambient occlusion pass only: not with --denoise, --denoise-regression, "
+                         "--area-lights or --no-motion\n");
+    return 2;
+  }
+  if (o.ao < 0 && o.aoRadiusSet) {
+    std::fprintf(stderr, "bdpt_render: --ao-radius R goes with --ao N\n");
+    return 2;
   }
   if (o.gpus < 0 || o.gpus > 64 || (o.gpus > 0 && o.world > 0)) {
     std::fprintf(stderr, "bdpt_render: --gpus N (ranks as threads) or --rank R --world N --id-file F (one process per rank), not both\n");

@@ -1154,6 +1154,72 @@ typedef struct bdpt_walk_desc {
 } bdpt_walk_desc;
 int bdpt_walk_query(bdpt_ctx* ctx, const bdpt_walk_desc* desc, void* stream);
 
+/* ---- Ambient occlusion: S cosine-weighted any-hit rays per item inside a radius, from one persistent kernel ----
+ * bdpt_ao_query is the reference's AO ray generation shader on a caller's items
+ * (CommonPasses/Data/CommonPasses/aoTracing.rt.hlsl:74-122); bdpt_ao_execute is its pass on the G-buffer
+ * (CommonPasses/AmbientOcclusionPass.cpp:76-96).  It is the loop, per sample, bdpt_bsdf_query(SAMPLE, matIndex 1) -> build
+ * the rays -> bdpt_trace_rays(BDPT_TRACE_ANY) -> add the visibility bytes, bit for bit, run with the device functions
+ * those calls run, without two launches and a trip through memory per sample (DESIGN.md "Ambient occlusion").
+ *
+ * Item i is alive iff surfaces[i].prim >= 0 and (alive == NULL or alive[i] != 0).  For an alive item:
+ *   s = seeds[i]; count = 0;
+ *   for k = 0 .. samples-1: dir = getCosHemisphereSample(s, N) — two draws, s advances (the Lambertian sampleBRDF's
+ *     direction: BDPT/MaterialUtils.hlsli:41-54); the ray is org = posW, tmin = minT, dir, tmax = radius, traced as
+ *     BDPT_TRACE_ANY traces it (the alpha test included, a hit needs tmin < t < tmax); count += 1 when it is unoccluded;
+ *   ao[i] = (float)count / (float)samples, a correctly rounded fp32 division (aoTracing.rt.hlsl:121); counts[i] = count;
+ *   seedsOut[i] = s, the state after exactly 2 * samples draws.
+ * A dead item gives ao = 1, counts = samples and seedsOut = seeds[i] with no draw (the shader's background branch,
+ * aoTracing.rt.hlsl:88-91).  seedsOut may be `seeds`.  `counts` lets a caller accumulate over frames exactly.
+ * radius and minT are not validated; they follow the ray contract of bdpt_trace_rays: radius <= minT, or a NaN in
+ * either, makes every ray a miss, so ao = 1.
+ * Record contract: only posW, N and prim are read, and prim only for its sign: it reaches no address.  N need not be
+ * unit, finite or non-zero, posW need not be finite: the direction is that of the fp32 arithmetic as written
+ * (bdpt_bsdf_query's record contract), and a zero or NaN direction or a NaN origin is a miss under the ray contract, so a
+ * record with N = 0, a NaN in N or a NaN in posW gives ao = 1 after its 2 * samples draws.  A normal so short that a
+ * component of the direction falls below 1e-30 comes under that rule of the ray contract.  ao is always in [0, 1].
+ *
+ * bdpt_ao_execute runs the same for the context's tile pixels (rows or stripes), reading the FULL-FRAME G-buffer
+ * channels worldPosition and worldNormal and writing `out` (full-frame RGBA32F, addressed as bdpt_execute addresses it)
+ * at the tile's pixels only: pixel (x, y) has seed initRand(x + y * width, frameCount, 16) with the full frame's width
+ * and the absolute y (aoTracing.rt.hlsl:82), so tiles reproduce the whole frame; it is alive iff worldPosition.w != 0;
+ * N is the half-decoded xyz of worldNormal; out = (ao, ao, ao, 1).  It needs a scene and a size, not a camera.
+ *
+ * Ordering, capture, counters and numDevice: as the surface queries — enqueued on `stream` behind the context's previous
+ * call, which also keeps bdpt_trace_rays' INVARIANT (no two persistent traversal kernels of one context resident at
+ * once); no allocation and no synchronise (exactly one kernel node in a captured graph); bdpt_get_counters and
+ * bdpt_get_stage_times are left alone; items at or beyond min(*numDevice, num) are neither read nor written.  Nothing a
+ * caller supplies reaches an address.
+ * Errors (nothing is enqueued), in this order: a NULL context, desc / params or gbuffer BDPT_E_INVALID; no scene
+ * (bdpt_ao_execute: or no size) BDPT_E_STATE; samples outside 1 .. BDPT_AO_MAX_SAMPLES (the reference's GUI range,
+ * AmbientOcclusionPass.cpp:69; 0 would be 0 / 0), non-zero flags or reserved BDPT_E_INVALID; then num == 0 returns BDPT_OK
+ * and does nothing; then a missing or misaligned buffer BDPT_E_INVALID: records and `out` 16 bytes, worldNormal 8, words
+ * (seeds, ao, counts, seedsOut, numDevice) 4; a NULL `out` is found here. */
+#define BDPT_AO_MAX_SAMPLES 64u
+typedef struct bdpt_ao_desc {
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  uint32_t samples;             /* 1 .. BDPT_AO_MAX_SAMPLES rays per item */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  float radius;                 /* tmax of the rays */
+  float minT;                   /* tmin of the rays (bdpt_params::minT) */
+  uint32_t flags;               /* 0 */
+  uint32_t reserved;            /* 0 */
+  const bdpt_surface* surfaces; /* device, 16-byte aligned, num records: posW, N and prim are read */
+  const uint32_t* seeds;        /* device, num RNG states */
+  const uint8_t* alive;         /* optional: device, one byte per item, 0 = the item is dead */
+  float* ao;                    /* device, num floats */
+  uint32_t* counts;             /* optional: device, num words: the unoccluded samples */
+  uint32_t* seedsOut;           /* optional: device, num RNG states (may be `seeds`) */
+} bdpt_ao_desc;
+int bdpt_ao_query(bdpt_ctx* ctx, const bdpt_ao_desc* desc, void* stream);
+typedef struct bdpt_ao_params {
+  uint32_t frameCount; /* starts at 0 and grows by one per frame (AmbientOcclusionPass.h:54, .cpp:86) */
+  float radius;        /* the pass's default: max(0.1, scene radius * 0.05) (AmbientOcclusionPass.cpp:62) */
+  float minT;
+  uint32_t samples;    /* 1 .. BDPT_AO_MAX_SAMPLES; the pass's default is 1 (AmbientOcclusionPass.h:55) */
+  uint32_t reserved;   /* 0 */
+} bdpt_ao_params;
+int bdpt_ao_execute(bdpt_ctx* ctx, const bdpt_ao_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
+
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
  * a split triangle covering it, every child box containing its subtree's pieces, depth within the traversal stack.
