@@ -20,6 +20,7 @@ GBUFFER_CHANNELS = ("WorldPosition", "WorldNormal", "MaterialDiffuse", "Material
                     "Emissive")
 OUTPUT_CHANNEL = "PipelineOutput"  # ResourceManager::kOutputChannel, SharedUtils/ResourceManager.cpp:22
 AO_CHANNEL = "AmbientOcclusion"  # the channel FramePipeline.ambient_occlusion and bdpt_render --ao write
+GI_CHANNEL = "DiffuseGI"  # the channel FramePipeline.diffuse_gi and bdpt_render --gi write
 
 
 class BdptError(RuntimeError):
@@ -778,6 +779,45 @@ class Context:
         samples), the full-frame G-buffer, and the full-frame RGBA32F image at `out_ptr`, which gets (ao, ao, ao, 1)."""
         self._check(self._lib.bdpt_ao_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_ao_execute")
 
+    # ---- diffuse GI (include/bdpt.h "Diffuse GI", DESIGN.md) ----
+    def diffuse_gi(self, surfaces, seeds, indirect=True, cosine=True, view_pos=None, normal_map=True, min_t=1e-4, alive=None,
+                   out=None, hits=None, status=None, seeds_out=None, count=None, stream=None):
+        """bdpt_gi_query: the reference's one-bounce path tracer per (N, 24) bdpt_surface record (posW, N, diffuse and prim
+        are read), in one launch — the loop light_query -> trace_rays("any") -> sample_bsdf(mat_index=1) ->
+        trace_rays("closest") -> shade_hits -> light_query -> trace_rays("any") and the shader's arithmetic, bit for bit.
+        seeds (N,) uint32 / int32 RNG states: one draw, with `indirect` three.  cosine=False samples the hemisphere
+        uniformly.  view_pos (three floats): the bounce hit is shaded as seen from there (the reference's behaviour, with
+        the camera position), None: from the item's posW; normal_map as shade_hits'.  Returns (N, 4) float32 (colour, 1);
+        a miss record (prim < 0), or an item whose `alive` byte is 0, gives (diffuse, 1) without a draw.  GPU tensors
+        only: alive (N,) uint8; hits (N, 4) the bounce ray's hit; status (N,) abi.GI_STATUS_* bits; seeds_out (N,) the
+        states after the draws (it may be `seeds`).  `out` and `count` as for the other queries."""
+        import torch
+        records, words = (torch.float32, torch.int32), (torch.int32, torch.uint32)  # the dtypes a record / a 32-bit word may have
+        extras = [("alive", alive, None, (torch.uint8,)), ("hits", hits, 4, records), ("status", status, None, words),
+                  ("seeds_out", seeds_out, None, words)]
+        if view_pos is not None and len(view_pos) != 3:
+            raise BdptError("diffuse_gi: view_pos must be three floats or None")
+
+        def run(ptrs, n, cnt, res):
+            d = abi.GiDesc()
+            d.num, d.numDevice, d.minT = n, cnt, float(min_t)
+            d.flags = (abi.GI_INDIRECT if indirect else 0) | (0 if cosine else abi.GI_UNIFORM) | \
+                (abi.GI_SHADE_FROM_VIEW if view_pos is not None else 0)
+            d.shadeFlags = abi.SHADE_NORMAL_MAP if normal_map else 0
+            for k in range(3):
+                d.viewPos[k] = float(view_pos[k]) if view_pos is not None else 0.0
+            d.surfaces, d.seeds, d.color = ptrs[0], ptrs[1], res
+            d.alive, d.hits, d.status, d.seedsOut = (None if t is None else t.data_ptr() for t in (alive, hits, status, seeds_out))
+            return self._lib.bdpt_gi_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("diffuse_gi", [("surfaces", surfaces, 24, records), ("seeds", seeds, None, words)],
+                                   (4, (torch.float32,)), run, out, count, extras=extras, fn="bdpt_gi_query")
+
+    def gi_execute(self, params, gbuffer, out_ptr, stream=None):
+        """bdpt_gi_execute: the reference's SimpleDiffuseGIPass on the context's tile pixels — abi.GiParams (frameCount, minT,
+        flags), the full-frame G-buffer, and the full-frame RGBA32F image at `out_ptr`, which gets (colour, 1)."""
+        self._check(self._lib.bdpt_gi_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_gi_execute")
+
     @staticmethod
     def _bsdf_mode(what, mat_index, from_lobe):
         if mat_index not in (0, 1) or isinstance(mat_index, bool):
@@ -1300,6 +1340,8 @@ class FramePipeline:
         self.ao_frame = 0  # CommonPasses/AmbientOcclusionPass.h:54
         self.last_ao_params = None
         self._ao_radius = None  # the pass's default radius for the scene, made on first use
+        self.gi_frame = 0x1337  # CommonPasses/SimpleDiffuseGIPass.h:62
+        self.last_gi_params = None
         self.accum_count = 0
         self.env_color = (0.5, 0.5, 0.8, 1.0)  # SharedUtils/ResourceManager.cpp:77-87 default environment
         self.use_jitter = True
@@ -1563,6 +1605,25 @@ class FramePipeline:
         self.ctx.ao_execute(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
         self.ao_frame += 1
         self.last_ao_params = p
+        return out
+
+    def diffuse_gi(self, indirect=True, cosine=True):
+        """The reference's SimpleDiffuseGIPass on this pipeline's G-buffer as it stands (render_frame, or a gbuffer_execute
+        of the caller's, fills it) and stream: Context.gi_execute with the pass's frame counter (from 0x1337, one per call:
+        CommonPasses/SimpleDiffuseGIPass.h:62, .cpp:100), the pipeline's min_t, camera and environment (Context.set_environment),
+        and the pass's two switches (its defaults: indirect rays, cosine sampling).  Returns the (H, W, 4) float32 channel
+        "DiffuseGI" ((colour, 1); a tile or stripes pipeline writes its own rows), also in ``channels``; ``last_gi_params``
+        keeps the abi.GiParams used."""
+        p = abi.GiParams()
+        p.flags = (abi.GI_INDIRECT if indirect else 0) | (0 if cosine else abi.GI_UNIFORM)
+        p.minT, p.frameCount = self.min_t, self.gi_frame & 0xFFFFFFFF
+        if GI_CHANNEL not in self.channels:
+            with self.torch.cuda.device(self.dev):
+                self.channels[GI_CHANNEL] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
+        out = self.channels[GI_CHANNEL]
+        self.ctx.gi_execute(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
+        self.gi_frame += 1
+        self.last_gi_params = p
         return out
 
     def set_lights(self, lights):

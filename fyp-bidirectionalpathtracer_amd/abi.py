@@ -54,6 +54,8 @@ CONNECT_STATUS_NONZERO, CONNECT_STATUS_PIXEL = 1, 2
 WALK_SEED_PER_STEP = 1
 WALK_STATUS_STORED, WALK_STATUS_REAL, WALK_STATUS_SPECULAR = 1, 2, 4
 AO_MAX_SAMPLES = 64
+GI_INDIRECT, GI_UNIFORM, GI_SHADE_FROM_VIEW = 1, 2, 4
+GI_STATUS_DIRECT_OCCLUDED, GI_STATUS_BOUNCE_HIT, GI_STATUS_BOUNCE_OCCLUDED = 1, 2, 4
 
 
 class Material(C.Structure):
@@ -294,6 +296,16 @@ class AoParams(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class GiDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("flags", C.c_uint32), ("numDevice", C.c_void_p), ("shadeFlags", C.c_uint32), ("minT", C.c_float),
+                ("viewPos", C.c_float * 3), ("reserved", C.c_uint32), ("surfaces", C.c_void_p), ("seeds", C.c_void_p),
+                ("alive", C.c_void_p), ("color", C.c_void_p), ("hits", C.c_void_p), ("status", C.c_void_p), ("seedsOut", C.c_void_p)]
+
+
+class GiParams(C.Structure):
+    _fields_ = [("frameCount", C.c_uint32), ("minT", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 BMFR_MAX_PLANES = BDPT_MAX_LIGHTS + 2
 
 
@@ -351,6 +363,8 @@ PROTOTYPES = {
     "bdpt_walk_query": (C.c_int, [C.c_void_p, C.POINTER(WalkDesc), C.c_void_p]),
     "bdpt_ao_query": (C.c_int, [C.c_void_p, C.POINTER(AoDesc), C.c_void_p]),
     "bdpt_ao_execute": (C.c_int, [C.c_void_p, C.POINTER(AoParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "bdpt_gi_query": (C.c_int, [C.c_void_p, C.POINTER(GiDesc), C.c_void_p]),
+    "bdpt_gi_execute": (C.c_int, [C.c_void_p, C.POINTER(GiParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit_pieces": (C.c_int, [C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),

@@ -1,6 +1,7 @@
 // api_query.cpp — the per-item queries of the C ABI (include/bdpt.h): bdpt_trace_rays, bdpt_camera_rays, bdpt_shade_hits,
-// bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query, bdpt_ao_query and bdpt_motion_query, on a
-// caller's arrays in device memory, and bdpt_ao_execute, the same kernel on the tile's G-buffer pixels.  Every one checks
+// bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query, bdpt_ao_query, bdpt_gi_query and
+// bdpt_motion_query, on a caller's arrays in device memory, and bdpt_ao_execute and bdpt_gi_execute, the same kernels on the
+// tile's G-buffer pixels.  Every one checks
 // its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags and what goes together
 // (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
 // first use of the emitter table), so all can be captured into a hipGraph.
@@ -294,6 +295,71 @@ int bdpt_ao_execute(bdpt_ctx* c, const bdpt_ao_params* p, const bdpt_gbuffer* gb
     A.samples = p->samples;
     A.frameCount = p->frameCount;
     launchAo(c->S, A, true, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+namespace {
+// the context's environment (bdpt_set_environment), as the walk's miss branch reads it
+void giEnvironment(const bdpt_ctx* c, GiDev& Q) {
+  Q.envMap = c->env.envMap;
+  Q.envW = c->env.width;
+  Q.envH = c->env.height;
+  for (int k = 0; k < 3; k++) Q.envColor[k] = c->env.color[k];
+}
+}  // namespace
+
+static_assert(sizeof(bdpt_gi_desc) == 96 && offsetof(bdpt_gi_desc, surfaces) == 40 && sizeof(bdpt_gi_params) == 16,
+              "abi.GiDesc and abi.GiParams restate these layouts");
+int bdpt_gi_query(bdpt_ctx* c, const bdpt_gi_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "gi_query")) return rc;
+  if ((d->flags & ~(BDPT_GI_INDIRECT | BDPT_GI_UNIFORM | BDPT_GI_SHADE_FROM_VIEW)) || (d->shadeFlags & ~BDPT_SHADE_NORMAL_MAP) || d->reserved)
+    return refuse(c, BDPT_E_INVALID, "gi_query", "unknown flags or shadeFlags, or non-zero reserved");
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->surfaces, 16) || !aligned(d->seeds, 4) || !aligned(d->color, 16) || (d->hits && !aligned(d->hits, 16)) ||
+      (d->status && !aligned(d->status, 4)) || (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "gi_query",
+                  "surfaces, seeds, color, hits, status, seedsOut or numDevice missing or not aligned (records 16 bytes, words 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    GiDev Q{};
+    Q.surf = f4(d->surfaces);
+    Q.seeds = d->seeds;
+    Q.alive = d->alive;
+    Q.color = f4(d->color);
+    Q.hits = f4(d->hits);
+    Q.status = d->status;
+    Q.seedsOut = d->seedsOut;
+    Q.range = {d->num, d->numDevice, d->minT};
+    Q.flags = d->flags;
+    for (int k = 0; k < 3; k++) Q.viewPos[k] = d->viewPos[k];
+    giEnvironment(c, Q);
+    launchGi(c->S, Q, false, (d->shadeFlags & BDPT_SHADE_NORMAL_MAP) != 0, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+int bdpt_gi_execute(bdpt_ctx* c, const bdpt_gi_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
+  if (!c || !p || !gb) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "gi_execute")) return rc;
+  if (!c->haveSize) return refuse(c, BDPT_E_STATE, "gi_execute", "no size (bdpt_resize first)");
+  if (int rc = needCamera(c, "gi_execute")) return rc;
+  if ((p->flags & ~(BDPT_GI_INDIRECT | BDPT_GI_UNIFORM)) || p->reserved)
+    return refuse(c, BDPT_E_INVALID, "gi_execute", "flags other than BDPT_GI_INDIRECT | BDPT_GI_UNIFORM, or non-zero reserved");
+  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(gb->materialDiffuse, 8) || !aligned(out, 16))
+    return refuse(c, BDPT_E_INVALID, "gi_execute",
+                  "worldPosition, worldNormal, materialDiffuse or out missing or not aligned (16 bytes; the half channels 8)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    GiDev Q{};
+    Q.gbPosition = f4(gb->worldPosition);
+    Q.gbNormal = gb->worldNormal;
+    Q.gbDiffuse = gb->materialDiffuse;
+    Q.pix = c->P.pix;
+    Q.out = f4(out);
+    Q.range = {c->P.Np, nullptr, p->minT};
+    Q.flags = p->flags | BDPT_GI_SHADE_FROM_VIEW;  // prepareShadingData shades from gCamera.posW
+    Q.frameCount = p->frameCount;
+    for (int k = 0; k < 3; k++) Q.viewPos[k] = c->cam.posW[k];
+    giEnvironment(c, Q);
+    launchGi(c->S, Q, true, true, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 

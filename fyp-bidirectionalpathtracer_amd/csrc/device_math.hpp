@@ -188,6 +188,18 @@ BD f3 getCosHemisphereSample(uint32_t& seed, f3 hitNorm) {  // MaterialUtils.hls
   det_sincos2pi(r1, sn, cs);
   return tangent * (r * cs) + bitangent * (r * sn) + hitNorm * sqrtf(maxf(0.0f, 1.0f - r0));
 }
+// CommonPasses simpleDiffuseGIUtils.hlsli:130-143: getCosHemisphereSample's frame and angle with r = sqrt(max(0, 1 - r0^2))
+// and height r0
+BD f3 getUniformHemisphereSample(uint32_t& seed, f3 hitNorm) {
+  float r0 = nextRand(seed);
+  float r1 = nextRand(seed);
+  f3 bitangent = getPerpendicularVector(hitNorm);
+  f3 tangent = cross(bitangent, hitNorm);
+  float r = sqrtf(maxf(0.0f, 1.0f - r0 * r0));
+  float sn, cs;
+  det_sincos2pi(r1, sn, cs);
+  return tangent * (r * cs) + bitangent * (r * sn) + hitNorm * r0;
+}
 BD f3 sampleUnitSphere(uint32_t& seed) {  // MaterialUtils.hlsli:56-63
   f3 p = mk(2.0f, 2.0f, 2.0f);
   while (length(p) > 1.0f) {

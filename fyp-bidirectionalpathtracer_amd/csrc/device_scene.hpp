@@ -315,5 +315,32 @@ BD void primaryRay(const bdpt_camera& cam, const bdpt_gbuffer_params& gp, uint32
   d = normalize(gp.useThinLens ? (focalPoint - randomOrig) : rayDir);
 }
 
+// The environment toward a direction: what the G-buffer pass's PrimaryMiss, the walk's miss branch and the diffuse GI
+// kernel's IndirectMiss (gi.hip) all call.
+BD float atan2_WAR(float y, float x) {  // CP lightProbeGBufferUtils.hlsli:45-58
+  if (x > 0.f)
+    return det_atan(y / x);
+  else if (x < 0.f && y >= 0.f)
+    return det_atan(y / x) + kPi;
+  else if (x < 0.f && y < 0.f)
+    return det_atan(y / x) - kPi;
+  else if (x == 0.f && y > 0.f)
+    return kPi / 2.f;
+  else if (x == 0.f && y < 0.f)
+    return -kPi / 2.f;
+  return 0.f;
+}
+
+// lat-long lookup of PrimaryMiss (CP lightProbeGBuffer.rt.hlsl:63-74): texel of the RGBA32F map, 0 outside
+BD f3 envLookup(const float* envMap, uint32_t envW, uint32_t envH, f3 d) {
+  const f3 pd = normalize(d);
+  const float u = (1.f + atan2_WAR(pd.x, -pd.z) * kInvPi) * 0.5f;
+  const float v = det_acos(pd.y) * kInvPi;
+  const uint32_t ex = (uint32_t)(u * (float)envW), ey = (uint32_t)(v * (float)envH);
+  f3 c = mk(0);
+  if (ex < envW && ey < envH) c = ld3(envMap + ((size_t)ey * envW + ex) * 4);
+  return c;
+}
+
 #undef BD
 }  // namespace bdpt

@@ -309,6 +309,7 @@ struct LaunchGrids {
   uint32_t rays[3] = {0, 0, 0};       // [mode] (trace_rays.hip)
   uint32_t walkQuery[2] = {0, 0};     // [GGX] (walk_query.hip)
   uint32_t ao[2] = {0, 0};            // [G-buffer source] (ao.hip)
+  uint32_t gi[3] = {0, 0, 0};         // [records, records + normal map, G-buffer] (gi.hip)
 };
 // both random walks of the frame: one persistent launch (trace + hit/miss shading in place)
 void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,
@@ -423,6 +424,33 @@ struct AoDev {
 };
 // `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
 void launchAo(const SceneDev& S, const AoDev& A, bool gbuffer, unsigned long long* cursor, LaunchGrids& G, int numCUs, hipStream_t st);
+// gi.hip: bdpt_gi_query (items are bdpt_surface records) and bdpt_gi_execute (items are the tile's pixels, read from the
+// G-buffer).  Per alive item a direct any-hit ray, and with BDPT_GI_INDIRECT a closest-hit bounce ray and an any-hit ray
+// from its hit.
+struct GiDev {
+  const float4* surf;         // query: bdpt_surface records (six float4 each; posW, N, diffuse and prim are read)
+  const uint32_t* seeds;      // query: one RNG state per item
+  const uint8_t* alive;       // query, optional: 0 = the item is dead
+  float4* color;              // query: (colour, 1) per item
+  float4* hits;               // query, optional: the bounce ray's bdpt_hit
+  uint32_t* status;           // query, optional: BDPT_GI_STATUS_*
+  uint32_t* seedsOut;         // query, optional: the state after 1 or 3 draws (a dead item's: unchanged)
+  const float4* gbPosition;   // execute: WorldPosition of the full frame (w != 0: geometry)
+  const uint16_t* gbNormal;   // execute: WorldNormal (half4) of the full frame
+  const uint16_t* gbDiffuse;  // execute: MaterialDiffuse (half4) of the full frame
+  const uint32_t* pix;        // execute: the tile's pixels (PathBuf::pix); the seed is initRand(pix, frameCount)
+  float4* out;                // execute: full-frame RGBA32F, (colour, 1) at the tile's pixels
+  QueryRange range;           // execute: cap = the tile's pixel count, no device word
+  uint32_t flags;             // BDPT_GI_INDIRECT | BDPT_GI_UNIFORM | BDPT_GI_SHADE_FROM_VIEW
+  uint32_t frameCount;        // execute
+  float viewPos[3];           // BDPT_GI_SHADE_FROM_VIEW: where the bounce hit is shaded from
+  const float* envMap;        // the context's environment (bdpt_set_environment): RGBA32F map, or null: envColor
+  uint32_t envW, envH;
+  float envColor[3];
+};
+// `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
+void launchGi(const SceneDev& S, const GiDev& Q, bool gbuffer, bool normalMap, unsigned long long* cursor, LaunchGrids& G, int numCUs,
+              hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,

@@ -161,31 +161,7 @@ BD void packHalf4(uint16_t* base, size_t idx, float a, float b, float c, float d
 // ------------------------------------------------------------------------------------------------
 // G-buffer pass: GBufferRayGen + PrimaryClosestHit/AnyHit/Miss (CP lightProbeGBuffer.rt.hlsl:63-159)
 // ------------------------------------------------------------------------------------------------
-BD float atan2_WAR(float y, float x) {  // CP lightProbeGBufferUtils.hlsli:45-58
-  if (x > 0.f)
-    return det_atan(y / x);
-  else if (x < 0.f && y >= 0.f)
-    return det_atan(y / x) + kPi;
-  else if (x < 0.f && y < 0.f)
-    return det_atan(y / x) - kPi;
-  else if (x == 0.f && y > 0.f)
-    return kPi / 2.f;
-  else if (x == 0.f && y < 0.f)
-    return -kPi / 2.f;
-  return 0.f;
-}
-
-// lat-long lookup of PrimaryMiss (CP lightProbeGBuffer.rt.hlsl:63-74): texel of the RGBA32F map, 0 outside
-BD f3 envLookup(const float* envMap, uint32_t envW, uint32_t envH, f3 d) {
-  const f3 pd = normalize(d);
-  const float u = (1.f + atan2_WAR(pd.x, -pd.z) * kInvPi) * 0.5f;
-  const float v = det_acos(pd.y) * kInvPi;
-  const uint32_t ex = (uint32_t)(u * (float)envW), ey = (uint32_t)(v * (float)envH);
-  f3 c = mk(0);
-  if (ex < envW && ey < envH) c = ld3(envMap + ((size_t)ey * envW + ex) * 4);
-  return c;
-}
-
+// (atan2_WAR and envLookup, the lat-long lookup of PrimaryMiss: device_scene.hpp, shared with gi.hip)
 // HINT_ONLY: the primary ray of EVERY frame pixel (G.Np = W * H, no pixel list), and only its occluder-hint word is
 // written — what a context that renders a band or one rank's stripes runs when the camera has moved, so that its
 // light-tracing rays, which may aim at any pixel of the frame, find a hint outside its own rows too.

@@ -669,6 +669,68 @@ void AmbientOcclusionPass::execute(RenderContext* pRenderContext) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// SimpleDiffuseGIPass (CommonPasses/SimpleDiffuseGIPass.cpp:38-117)
+// ------------------------------------------------------------------------------------------------
+bool SimpleDiffuseGIPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
+  mpResManager = pResManager;
+  // default-format requests: behind a G-buffer pass they lose against its formats, as in the reference (.cpp:47-51)
+  mpResManager->requestTextureResources({"WorldPosition", "WorldNormal", "MaterialDiffuse"});
+  mpResManager->requestTextureResource(mOutputBuf);
+  mpResManager->requestTextureResource(ResourceManager::kEnvironmentMap);
+  mpRays = RayLaunch::create(pRenderContext);
+  if (!mpRays) return false;
+  if (mpScene) mpRays->setScene(mpScene);
+  return true;
+}
+void SimpleDiffuseGIPass::initScene(RenderContext*, Scene::SharedPtr pScene) {
+  mpScene = pScene;
+  if (mpRays) mpRays->setScene(mpScene);
+}
+void SimpleDiffuseGIPass::renderGui(Gui* pGui) {
+  int dirty = 0;  // the three check boxes of .cpp:81-84, under the labels they show while ticked and while not
+  dirty |= (int)pGui->addCheckBox(mDoDirectShadows ? "Shooting direct shadow rays" : "No direct shadow rays", mDoDirectShadows);
+  dirty |= (int)pGui->addCheckBox(mDoIndirectGI ? "Shooting global illumination rays" : "Skipping global illumination", mDoIndirectGI);
+  dirty |= (int)pGui->addCheckBox(mDoCosSampling ? "Use cosine sampling" : "Use uniform sampling", mDoCosSampling);
+  if (dirty) setRefreshFlag();
+}
+void SimpleDiffuseGIPass::execute(RenderContext* pRenderContext) {
+  Texture::SharedPtr pDstTex = mpResManager->getClearedTexture(mOutputBuf, vec4{0.0f, 0.0f, 0.0f, 0.0f});
+  if (!pDstTex || !mpRays || !mpRays->readyToRender()) return;  // silent no-op, .cpp:95
+  Texture::SharedPtr pos = mpResManager->getTexture("WorldPosition"), nrm = mpResManager->getTexture("WorldNormal"),
+                     dif = mpResManager->getTexture("MaterialDiffuse");
+  if (!pos || !nrm || !dif || pos->getFormat() != ResourceFormat::RGBA32Float || nrm->getFormat() != ResourceFormat::RGBA16Float ||
+      dif->getFormat() != ResourceFormat::RGBA16Float || pDstTex->getFormat() != ResourceFormat::RGBA32Float) {
+    std::fprintf(stderr, "[SimpleDiffuseGIPass] needs WorldPosition (RGBA32F), WorldNormal and MaterialDiffuse (RGBA16F) of a G-buffer pass "
+                         "and an RGBA32F output\n");
+    return;
+  }
+  if (!mpRays->ensureSize(pDstTex->getWidth(), pDstTex->getHeight())) return;
+  bdpt_set_camera(mpRays->ctx(), &mpScene->getActiveCamera()->getData());  // the hit is shaded from gCamera.posW
+  {  // the "EnvironmentMap" channel indirect rays that miss look up (.cpp:111-113)
+    Texture::SharedPtr env = mpResManager->getTexture(ResourceManager::kEnvironmentMap);
+    bdpt_environment e{};
+    if (env && env->getFormat() == ResourceFormat::RGBA32Float) {
+      e.envMap = (const float*)env->getDevicePointer();
+      e.width = env->getWidth();
+      e.height = env->getHeight();
+    }
+    bdpt_set_environment(mpRays->ctx(), &e);
+  }
+  bdpt_gbuffer gb;
+  std::memset(&gb, 0, sizeof(gb));
+  gb.worldPosition = (float*)pos->getDevicePointer();
+  gb.worldNormal = (uint16_t*)nrm->getDevicePointer();
+  gb.materialDiffuse = (uint16_t*)dif->getDevicePointer();
+  bdpt_gi_params p;
+  std::memset(&p, 0, sizeof(p));
+  p.frameCount = mFrameCount++;  // .cpp:100
+  p.minT = mpResManager->getMinTDist();
+  p.flags = (mDoIndirectGI ? BDPT_GI_INDIRECT : 0u) | (mDoCosSampling ? 0u : BDPT_GI_UNIFORM);  // mDoDirectShadows: never read by the shader
+  if (bdpt_gi_execute(mpRays->ctx(), &p, &gb, (float*)pDstTex->getDevicePointer(), pRenderContext->getStream()) != BDPT_OK)
+    std::fprintf(stderr, "[SimpleDiffuseGIPass] %s\n", mpRays->lastError());
+}
+
+// ------------------------------------------------------------------------------------------------
 // BDPTPass (BidirectionalPathtracing/Passes/BDPTPass.cpp:23-107)
 // ------------------------------------------------------------------------------------------------
 bool BDPTPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
@@ -1161,6 +1223,19 @@ bool AmbientOcclusionPass::loadState(RenderContext*, const uint8_t* data, size_t
   if (size != 16) return false;
   if (get32(data + 4) != (uint32_t)mNumRaysPerPixel || get32(data + 8) != floatBits(mAORadius) ||
       get32(data + 12) != floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f))
+    return false;
+  mFrameCount = get32(data);
+  return true;
+}
+void SimpleDiffuseGIPass::saveState(RenderContext*, std::vector<uint8_t>& out) {
+  put32(out, mFrameCount);
+  put32(out, (mDoIndirectGI ? 1u : 0u) | (mDoCosSampling ? 2u : 0u));
+  put32(out, floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f));
+}
+bool SimpleDiffuseGIPass::loadState(RenderContext*, const uint8_t* data, size_t size) {
+  if (size != 12) return false;
+  if (get32(data + 4) != ((mDoIndirectGI ? 1u : 0u) | (mDoCosSampling ? 2u : 0u)) ||
+      get32(data + 8) != floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f))
     return false;
   mFrameCount = get32(data);
   return true;

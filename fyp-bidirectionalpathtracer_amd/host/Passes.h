@@ -4,6 +4,7 @@
 //   BDPTPass                BidirectionalPathtracing/Passes/BDPTPass.{h,cpp}
 //   SimpleAccumulationPass  CommonPasses/SimpleAccumulationPass.{h,cpp}
 // the framework's ambient occlusion pass, AmbientOcclusionPass (CommonPasses/AmbientOcclusionPass.{h,cpp}),
+// its one-bounce path tracer, SimpleDiffuseGIPass (CommonPasses/SimpleDiffuseGIPass.{h,cpp}),
 // plus RayLaunch, the thin launch wrapper they hold (SharedUtils/RayLaunch.h:85-135): here it owns
 // one bdpt_ctx and forwards to the C ABI of include/bdpt.h instead of building a DXR state object.
 #pragma once
@@ -199,6 +200,35 @@ class AmbientOcclusionPass : public RenderPass {
   int32_t mNumRaysPerPixel = 1;  // AmbientOcclusionPass.h:55
   int32_t mPositionIndex = -1, mNormalIndex = -1, mOutputIndex = -1;
   std::string mOutputTexName;
+};
+
+// One-bounce diffuse global illumination (CommonPasses/SimpleDiffuseGIPass.{h,cpp}): WorldPosition, WorldNormal, MaterialDiffuse
+// and the environment map in, the output channel out, the reference's three switches and defaults.  Its ray generation
+// shader with its hit groups is bdpt_gi_execute.
+class SimpleDiffuseGIPass : public RenderPass {
+ public:
+  using SharedPtr = std::shared_ptr<SimpleDiffuseGIPass>;
+  static SharedPtr create(const std::string& outBuf) { return SharedPtr(new SimpleDiffuseGIPass(outBuf)); }
+
+ protected:
+  SimpleDiffuseGIPass(const std::string& outBuf) : RenderPass("Simple Diffuse GI Ray", "Simple Diffuse GI Options"), mOutputBuf(outBuf) {}
+  bool initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) override;
+  void initScene(RenderContext* pRenderContext, Scene::SharedPtr pScene) override;
+  void renderGui(Gui* pGui) override;
+  void execute(RenderContext* pRenderContext) override;
+  bool requiresScene() override { return true; }
+  bool usesRayTracing() override { return true; }
+  bool usesEnvironmentMap() override { return true; }
+  void saveState(RenderContext* pRenderContext, std::vector<uint8_t>& out) override;
+  bool loadState(RenderContext* pRenderContext, const uint8_t* data, size_t size) override;
+
+  RayLaunch::SharedPtr mpRays;
+  Scene::SharedPtr mpScene;
+  std::string mOutputBuf;
+  bool mDoIndirectGI = true;        // SimpleDiffuseGIPass.h:57
+  bool mDoCosSampling = true;       // SimpleDiffuseGIPass.h:58
+  bool mDoDirectShadows = true;     // SimpleDiffuseGIPass.h:59: sets gDirectShadow, which the shader does not declare
+  uint32_t mFrameCount = 0x1337u;   // SimpleDiffuseGIPass.h:62
 };
 
 // BMFR denoiser pass (BidirectionalPathtracing/Passes/DenoisePass.{h,cpp}): same channels, switches and defaults

@@ -24,5 +24,6 @@ using bdpt::ResourceFormat;
 using bdpt::ResourceManager;
 using bdpt::SampleConfig;
 using bdpt::Scene;
+using bdpt::SimpleDiffuseGIPass;
 using bdpt::SimpleAccumulationPass;
 using bdpt::Texture;

@@ -2,7 +2,8 @@
 // (G-buffer pass -> BDPT pass -> accumulation pass -> BMFR denoiser, which is off unless --denoise /
 // --denoise-regression tick its boxes), run for a number of frames, output written as a PFM image.
 // `--ao N` runs the G-buffer pass and the ambient occlusion pass instead (CommonPasses/AmbientOcclusionPass.cpp) and
-// writes the AO channel.
+// writes the AO channel; `--gi` runs the G-buffer pass, the one-bounce diffuse GI pass (CommonPasses/SimpleDiffuseGIPass.cpp)
+// and the accumulation pass, so that --frames N converges.
 //
 // Multi-GPU: `--gpus N` runs N such pipelines, one per GPU, each on a host thread of its own
 // with its own RCCL communicator (ncclCommInitAll); `--rank R --world N --id-file F` is the same for one PROCESS per
@@ -48,6 +49,9 @@ struct Options {
   int ao = -1;             // --ao N: render the G-buffer and the ambient occlusion pass (N rays per pixel) instead of the BDPT pipeline
   float aoRadius = 0.0f;   // --ao-radius R (with --ao, > 0); not given: the pass's default for the scene
   bool aoRadiusSet = false;
+  bool gi = false;            // --gi: render the G-buffer, the diffuse GI pass and the accumulation pass instead of the BDPT pipeline
+  bool giDirectOnly = false;  // --gi-direct-only: untick "Shooting global illumination rays"
+  bool giUniform = false;     // --gi-uniform: untick "Use cosine sampling"
   float bend = 0.0f;  // > 0: a skinned scene — a small rig along the scene's height, bent by up to this angle (radians) before every frame
 };
 
@@ -117,9 +121,12 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   }
   // add the passes to the rendering pipeline, as Main.cpp:12-18 does
   pipeline->setPass(0, LightProbeGBufferPass::create());
-  const size_t numPasses = o.ao >= 0 ? 2 : 4;
+  const size_t numPasses = o.ao >= 0 ? 2 : o.gi ? 3 : 4;
   if (o.ao >= 0) {  // --ao: the G-buffer and the ambient occlusion pass, which writes the output channel
     pipeline->setPass(1, AmbientOcclusionPass::create(ResourceManager::kOutputChannel));
+  } else if (o.gi) {  // --gi: the G-buffer, the diffuse GI pass into the output channel, and the accumulation pass over it
+    pipeline->setPass(1, SimpleDiffuseGIPass::create(ResourceManager::kOutputChannel));
+    pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
   } else {
     BDPTPass::SharedPtr bdpt = BDPTPass::create(ResourceManager::kOutputChannel);
     if (o.areaLights) bdpt->setParamFlags(BDPT_PARAM_AREA_LIGHTS);
@@ -159,6 +166,8 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   if (o.denoiseRegression) gui.overrides["Skip Regression"] = 1;
   if (o.ao >= 0) gui.overrides["Num AO Rays"] = o.ao;
   if (o.ao >= 0 && o.aoRadiusSet) gui.overrides["AO radius"] = o.aoRadius;
+  if (o.gi && o.giDirectOnly) gui.overrides["Shooting global illumination rays"] = 0;  // the check boxes' labels while they are on
+  if (o.gi && o.giUniform) gui.overrides["Use cosine sampling"] = 0;                   // (SimpleDiffuseGIPass.cpp:82-84)
   pipeline->applyGui(&gui);
   if (!o.resume.empty() && !pipeline->loadCheckpoint(o.resume)) {  // continue an earlier run's frame sequence
     std::fprintf(stderr, "bdpt_render: cannot resume from %s (missing, or written for other passes / another frame size)\n", o.resume.c_str());
@@ -308,7 +317,11 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
   if (writer) {
     double mean = 0;
     for (size_t i = 0; i < img.size(); i += 4) mean += img[i] + img[i + 1] + img[i + 2];
-    if (o.ao >= 0)
+    if (o.gi)
+      std::printf("%s %ux%u diffuse GI (%s%s): %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
+                  o.giDirectOnly ? "direct only" : "one bounce", o.giUniform ? ", uniform sampling" : ", cosine sampling", o.frames - warmup, res.ms,
+                  res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
+    else if (o.ao >= 0)
       std::printf("%s %ux%u ambient occlusion, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean ao %.6f", o.scene.c_str(), o.W, o.H,
                   o.ao, o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
     else
@@ -366,6 +379,9 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--bend")) o.bend = (float)std::atof(v);
     else if (const char* v = next("--ao")) o.ao = std::max(0, std::atoi(v));
     else if (const char* v = next("--ao-radius")) o.aoRadius = (float)std::atof(v), o.aoRadiusSet = true;
+    else if (std::strcmp(argv[i], "--gi") == 0) o.gi = true;
+    else if (std::strcmp(argv[i], "--gi-direct-only") == 0) o.giDirectOnly = true;
+    else if (std::strcmp(argv[i], "--gi-uniform") == 0) o.giUniform = true;
     else if (std::strcmp(argv[i], "--no-motion") == 0) o.noMotion = true;
     else if (std::strcmp(argv[i], "--tight-refit") == 0) o.tightRefit = true;
     else if (const char* v = next("--gpus")) o.gpus = std::atoi(v);
@@ -376,7 +392,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }
@@ -394,6 +410,20 @@ int main(int argc, char** argv) {
   }
   if (o.ao < 0 && o.aoRadiusSet) {
     std::fprintf(stderr, "bdpt_render: --ao-radius R goes with --ao N\n");
+    return 2;
+  }
+  if (o.gi && (o.ao >= 0 || o.gpus > 0 || o.world > 0)) {
+    std::fprintf(stderr, "bdpt_render: --gi renders on one GPU (no --gpus / --world) and not together with --ao N\n");
+    return 2;
+  }
+  // --gi replaces the BDPT and denoise passes: the switches only they read are refused, not ignored
+  if (o.gi && (o.denoise || o.areaLights || o.noMotion)) {
+    std::fprintf(stderr, "bdpt_render: --gi renders the G-buffer, the diffuse GI pass and the accumulation pass only: not with --denoise, "
+                         "--denoise-regression, --area-lights or --no-motion\n");
+    return 2;
+  }
+  if (!o.gi && (o.giDirectOnly || o.giUniform)) {
+    std::fprintf(stderr, "bdpt_render: --gi-direct-only and --gi-uniform go with --gi\n");
     return 2;
   }
   if (o.gpus < 0 || o.gpus > 64 || (o.gpus > 0 && o.world > 0)) {

@@ -1220,6 +1220,100 @@ typedef struct bdpt_ao_params {
 } bdpt_ao_params;
 int bdpt_ao_execute(bdpt_ctx* ctx, const bdpt_ao_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
 
+/* ---- Diffuse GI: direct light plus one diffuse bounce per item, up to three rays, from one persistent kernel ----
+ * bdpt_gi_query is the reference's one-bounce path tracer on a caller's items, the ray generation shader
+ * SimpleDiffuseGIRayGen with its IndirectMiss / IndirectClosestHit pair
+ * (CommonPasses/Data/CommonPasses/simpleDiffuseGI.rt.hlsl:61-108, 133-198); bdpt_gi_execute is its pass on the G-buffer
+ * (CommonPasses/SimpleDiffuseGIPass.cpp:89-117).  It is the loop bdpt_light_query(NEE) -> bdpt_trace_rays(ANY) ->
+ * bdpt_bsdf_query(SAMPLE) -> bdpt_trace_rays(CLOSEST) -> bdpt_shade_hits -> bdpt_light_query(NEE) -> bdpt_trace_rays(ANY)
+ * and the arithmetic between them, bit for bit, run with the device functions those calls run, in one launch
+ * (DESIGN.md "Diffuse GI").  kPi below is fp32 M_PI.
+ *
+ * Item i is alive iff surfaces[i].prim >= 0 and (alive == NULL or alive[i] != 0).  With s = seeds[i]:
+ *   dead:  color = (diffuse.rgb, 1) (the shader's background branch, .hlsl:146-152), no draw, seedsOut = s, status = 0,
+ *          hit = (0, 0, 0, -1).
+ *   alive: (ray1, value1) = NEE(record, s): one draw, s advances: exactly bdpt_light_query(BDPT_LIGHT_NEE, matIndex 1,
+ *            flags 0) on (record, s): the light choice, getLightData, value = (((lightsCount * LdotN) * I) * diffuse) / kPi
+ *            with lightsCount = numLights (.hlsl:155-170)
+ *          direct = term(value1, ray1); color = direct
+ *          with BDPT_GI_INDIRECT:
+ *            dir   = BDPT_GI_UNIFORM ? getUniformHemisphereSample(s, N) : getCosHemisphereSample(s, N), two draws
+ *                    (.hlsl:176-180, simpleDiffuseGIUtils.hlsli:114-143)
+ *            NdotL = saturate(dot(N, dir))
+ *            hit   = the closest hit of (posW, minT, dir, 1e38) as BDPT_TRACE_CLOSEST answers it (alpha test included)
+ *            miss: bounce = the context's environment toward dir (bdpt_set_environment: the map's lat-long texel, else the
+ *                  constant colour; none = black) (IndirectMiss, .hlsl:61-73)
+ *            hit:  rec = the hit shaded as bdpt_shade_hits shades it with `shadeFlags`, seen from `viewPos` with
+ *                  BDPT_GI_SHADE_FROM_VIEW, else from the item's posW;
+ *                  t = s, a copy (the payload's seed: the item's own state does not advance);
+ *                  (ray2, value2) = NEE(rec, t); bounce = term(value2, ray2) (IndirectClosestHit, .hlsl:85-108)
+ *            prob  = BDPT_GI_UNIFORM ? 1.0f / (2.0f * kPi) : NdotL / kPi
+ *            color = direct + (((NdotL * bounce) * diffuse) / kPi) / prob, as written, nothing cancelled (.hlsl:189-192):
+ *                    with cosine sampling NdotL = 0 gives 0 / 0 = NaN, as the shader does
+ *          seedsOut = s (one draw without BDPT_GI_INDIRECT, three with); out = (color, 1)
+ *   term(value, ray) = value when every component of value is +-0 (no ray is traced), else +0 when the ray is occluded as
+ *                      BDPT_TRACE_ANY answers it, else value.
+ * Build definitions: an occluded light contributes exactly +0 (directIfVisible's rule; the shader's 0 * inf would be NaN).
+ * prob for uniform sampling is the fp32 expression above.  Falcor's prepareShadingData in getHitShadingData shades from
+ * gCamera.posW, not from the ray origin, which decides the flip of double-sided normals: BDPT_GI_SHADE_FROM_VIEW is the
+ * reference's behaviour, and bdpt_gi_execute always uses it with the context's camera position and shadeFlags =
+ * BDPT_SHADE_NORMAL_MAP (full prepareShadingData applies the normal map).  mDoDirectShadows writes gDirectShadow, which
+ * the shader never declares (SimpleDiffuseGIPass.cpp:103): it has no effect, and none here.  The emitter table and
+ * occluder hints are not part of this call.
+ * status bits: BDPT_GI_STATUS_DIRECT_OCCLUDED ray1 was traced and occluded; BDPT_GI_STATUS_BOUNCE_HIT the bounce ray hit;
+ * BDPT_GI_STATUS_BOUNCE_OCCLUDED ray2 was traced and occluded.  hits[i] is the bdpt_hit of the bounce ray, (0, 0, 0, -1)
+ * when there is none or it missed.
+ * Record contract: posW, N, diffuse and prim are read, prim for its sign only: nothing a caller supplies reaches an
+ * address.  The floats may be degenerate or non-finite; the results are those of the fp32 arithmetic as written, and a
+ * zero or NaN direction or a NaN origin is a miss under the ray contract of bdpt_trace_rays, so such a bounce sees the
+ * environment.
+ *
+ * bdpt_gi_execute runs the same for the context's tile pixels (rows or stripes), reading the FULL-FRAME G-buffer
+ * channels worldPosition, worldNormal and materialDiffuse (halves decoded to fp32) and writing `out` (full-frame
+ * RGBA32F) at the tile's pixels only: pixel (x, y) has seed initRand(x + y * width, frameCount, 16) with the full
+ * frame's width and the absolute y (.hlsl:149); it is alive iff worldPosition.w != 0.  It needs a scene, a size and a
+ * camera.
+ *
+ * Ordering, capture, counters and numDevice: as bdpt_ao_query — enqueued on `stream` behind the context's previous call,
+ * which also keeps bdpt_trace_rays' INVARIANT; no allocation and no synchronise (exactly one kernel node in a captured
+ * graph); bdpt_get_counters and bdpt_get_stage_times are left alone; items at or beyond min(*numDevice, num) are neither
+ * read nor written.
+ * Errors (nothing is enqueued), in this order: a NULL context, desc / params or gbuffer BDPT_E_INVALID; no scene
+ * (bdpt_gi_execute: or no size, or no camera) BDPT_E_STATE; unknown flags (bdpt_gi_params: anything but INDIRECT |
+ * UNIFORM), unknown shadeFlags or non-zero reserved BDPT_E_INVALID; then num == 0 returns BDPT_OK and does nothing; then
+ * a missing or misaligned buffer BDPT_E_INVALID: records, color, hits and `out` 16 bytes, worldNormal and materialDiffuse
+ * 8, words (seeds, status, seedsOut, numDevice) 4. */
+#define BDPT_GI_INDIRECT 1u        /* gDoIndirectGI */
+#define BDPT_GI_UNIFORM 2u         /* !gCosSampling */
+#define BDPT_GI_SHADE_FROM_VIEW 4u /* bdpt_gi_query: shade the bounce hit as seen from viewPos */
+#define BDPT_GI_STATUS_DIRECT_OCCLUDED 1u
+#define BDPT_GI_STATUS_BOUNCE_HIT 2u
+#define BDPT_GI_STATUS_BOUNCE_OCCLUDED 4u
+typedef struct bdpt_gi_desc {
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  uint32_t flags;               /* BDPT_GI_* */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  uint32_t shadeFlags;          /* BDPT_SHADE_* for the bounce hit */
+  float minT;                   /* tmin of every ray (bdpt_params::minT) */
+  float viewPos[3];             /* read with BDPT_GI_SHADE_FROM_VIEW */
+  uint32_t reserved;            /* 0 */
+  const bdpt_surface* surfaces; /* device, 16-byte aligned, num records: posW, N, diffuse and prim are read */
+  const uint32_t* seeds;        /* device, num RNG states */
+  const uint8_t* alive;         /* optional: device, one byte per item, 0 = the item is dead */
+  float* color;                 /* device, 16-byte aligned, num float4 */
+  bdpt_hit* hits;               /* optional: device, 16-byte aligned, num records: the bounce ray's hit */
+  uint32_t* status;             /* optional: device, num words of BDPT_GI_STATUS_* */
+  uint32_t* seedsOut;           /* optional: device, num RNG states (may be `seeds`) */
+} bdpt_gi_desc;
+int bdpt_gi_query(bdpt_ctx* ctx, const bdpt_gi_desc* desc, void* stream);
+typedef struct bdpt_gi_params {
+  uint32_t frameCount; /* starts at 0x1337 and grows by one per frame (SimpleDiffuseGIPass.h:62, .cpp:100) */
+  float minT;
+  uint32_t flags;      /* BDPT_GI_INDIRECT | BDPT_GI_UNIFORM; the pass's defaults: INDIRECT, cosine (SimpleDiffuseGIPass.h:57-59) */
+  uint32_t reserved;   /* 0 */
+} bdpt_gi_params;
+int bdpt_gi_execute(bdpt_ctx* ctx, const bdpt_gi_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
+
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
  * a split triangle covering it, every child box containing its subtree's pieces, depth within the traversal stack.
