@@ -6,22 +6,23 @@
 // loop a caller otherwise runs per sample: bdpt_bsdf_query(SAMPLE, Lambertian) -> glue that builds the rays ->
 // bdpt_trace_rays(BDPT_TRACE_ANY) -> a count add.
 //
-// Built on trace_rays_kernel<BDPT_TRACE_ANY> (trace_rays.hip): one wave per workgroup, 64 traversal slots refilled from
-// the ITEM list by ballot + popcount prefix with one atomic per chunk, node bursts with deferred leaves, kStackLds stack
-// rows in LDS and the rest in the context's overflow area, the context's ray cursor with its reset protocol.  What differs
-// is what a finished lane does: a lane owns its item for all S rays.  When its ray is answered it adds to its count, draws
-// the next direction (getCosHemisphereSample, the Lambertian sampleBRDF's direction) and starts that ray in its own slot;
-// after sample S-1 it retires with one store per output.  No output atomics and no per-ray memory traffic: every output
-// word has one writer, whatever the order the lanes run in.  Dead items never take a slot: their outputs are written at
-// fetch.  Across the traversal a lane keeps its item, k, count, the RNG state and N; the origin lives in the traversal
-// state (TravState::o).  BDPT_AO_RELOAD_N re-reads N from the record at every regeneration instead (DESIGN.md "Ambient
-// occlusion" has both resource usages and timings).
+// The loop is the item loop of device_item_loop.hpp (refill, nodePhase, leafPhase, parkedDue), kept here as the kernel's
+// own text with any-hit rays: through the helpers the kernel computes the same but compiles to other code, which
+// measured slower (DESIGN.md "The shared item loop"); with this text its device code is what it was before the helpers
+// existed.  A change to the fetch or to the leaf schedule is made there and here.  Cursor release and launch are shared.
+// What is its own is what an answered lane does: a lane owns its item for all S rays.  When its ray is answered it adds
+// to its count, draws the next direction (getCosHemisphereSample, the Lambertian sampleBRDF's direction) and starts
+// that ray in its own slot; after sample S-1 it retires with one store per output.  No output atomics and no per-ray
+// memory traffic: every output word has one writer, whatever the order the lanes run in.  Dead items never take a
+// slot: their outputs are written at fetch.  Across the traversal a lane keeps its item, k, count, the RNG state and
+// N; the origin lives in the traversal state (TravState::o).  BDPT_AO_RELOAD_N re-reads N from the record at every
+// regeneration instead (DESIGN.md "Ambient occlusion" has both resource usages and timings).
 #include "kernels.h"
 
+#include "device_item_loop.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_scene.hpp"
-#include "device_trace.hpp"
 #include "launch.hpp"
 
 namespace bdpt {
@@ -88,7 +89,7 @@ __device__ __forceinline__ void aoStore(const AoDev& A, uint32_t i, uint32_t cou
 
 }  // namespace
 
-// cursor: as trace_rays_kernel (both words zero when a launch starts and when it ends).
+// cursor: as releaseCursor has it (both words zero when a launch starts and when it ends).
 template <int SRC>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_AO_WAVES_PER_EU, 8))) void ao_kernel(
     SceneDev S, AoDev A, unsigned long long* cursor) {
@@ -96,6 +97,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_AO_W
   __shared__ int s_stack[kStackLds * kWave];
   int* stk = s_stack + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63u);
+  // refill (device_item_loop.hpp), as this kernel's own text: see the head of the file
   const uint32_t n = itemCount(A.range.cap, A.range.count);
   const uint32_t share = (n / gridDim.x + kWave - 1) & ~(uint32_t)(kWave - 1);
   const uint32_t chunk = share < (uint32_t)kWave ? (uint32_t)kWave : (share > kFetchChunk ? kFetchChunk : share);
@@ -152,6 +154,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_AO_W
       if (exhausted) break;  // every lane retired and nothing left to take
       continue;              // (a chunk of dead items: take the next)
     }
+    // nodePhase<0>, leafPhase<BDPT_TRACE_ANY> and parkedDue<BDPT_AO_GEN_MIN>, as this kernel's own text
 #if BDPT_LEAF_WAIT > 0
     {
       uint32_t nNodes = 0;
@@ -160,13 +163,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_AO_W
     }
     const unsigned long long waitMask = __ballot(has && !parked && T.cur < 0), nodeMask = __ballot(has && !parked && T.cur >= 0);
     const int waitNeed = (__popcll(waitMask | nodeMask) * BDPT_LEAF_WAIT_FRAC8 + 7) >> 3;
-    const bool leafPhase = (int)__popcll(waitMask) >= waitNeed || nodeMask == 0ull;
+    const bool leavesDue = (int)__popcll(waitMask) >= waitNeed || nodeMask == 0ull;
 #else
     if (has && !parked)
       while (T.cur >= 0) nodeStep<0, kStackLds>(S, T, stk);
-    const bool leafPhase = true;
+    const bool leavesDue = true;
 #endif
-    if (leafPhase && has && !parked && T.cur < 0) {
+    if (leavesDue && has && !parked && T.cur < 0) {
       bool finished = (T.cur == kDone);
       if (!finished) {
         finished = leafStep<BDPT_TRACE_ANY, false>(S, T, nTris, nAlpha);
@@ -178,7 +181,6 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_AO_W
       parked = finished;
     }
 #if BDPT_AO_GEN_MIN > 1
-    // the parked lanes, together, once enough of them wait or nothing else can make progress
     const unsigned long long parkedMask = __ballot(parked);
     const bool genPhase = (int)__popcll(parkedMask) >= BDPT_AO_GEN_MIN || (parkedMask != 0ull && __ballot(has && !parked) == 0ull);
 #else
@@ -204,24 +206,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_AO_W
       }
     }
   }
-  // the last wave to finish leaves the cursor at zero for the next launch (trace_rays_kernel)
-  if (lane == 0) {
-    __threadfence();
-    if (atomicAdd(&cursor[1], 1ull) == (unsigned long long)gridDim.x - 1ull) {
-      cursor[0] = 0ull;
-      cursor[1] = 0ull;
-    }
-  }
+  releaseCursor(cursor, lane);
 }
 
 void launchAo(const SceneDev& S, const AoDev& A, bool gbuffer, unsigned long long* cursor, LaunchGrids& G, int numCUs, hipStream_t st) {
   if (!A.range.cap) return;
   withFlag(gbuffer, [&](auto GB) {
-    const auto kernel = ao_kernel<GB ? AO_SRC_GBUFFER : AO_SRC_SURFACES>;
-    uint32_t& g = G.ao[GB ? 1 : 0];
-    if (!g) g = persistentGrid(kernel, numCUs);
-    const uint32_t need = wavesFor(A.range.cap);
-    launchWave(kernel, g < need ? g : need, st, S, A, cursor);
+    launchPersistent(ao_kernel<GB ? AO_SRC_GBUFFER : AO_SRC_SURFACES>, G.ao[GB ? 1 : 0], A.range.cap, numCUs, st, S, A, cursor);
   });
 }
 

@@ -7,10 +7,11 @@
 // bdpt_trace_rays(ANY) -> bdpt_bsdf_query(SAMPLE) -> bdpt_trace_rays(CLOSEST) -> bdpt_shade_hits -> bdpt_light_query(NEE)
 // -> bdpt_trace_rays(ANY) with glue between them.
 //
-// Built on walk_query_kernel and ao_kernel: one wave per workgroup, 64 traversal slots refilled from the ITEM list by
-// ballot + popcount prefix with one atomic per chunk, node bursts with deferred leaves, kStackLds stack rows in LDS and the
-// rest in the context's overflow area, the context's ray cursor with its reset protocol.  A lane owns its item through
-// its rays, phase by phase:
+// Built on the item loop of device_item_loop.hpp: nodePhase, parkedDue and releaseCursor are called; the fetch (refill)
+// and the leaf step are kept as the kernel's own text, the leaf step because it serves two ray types, and both because
+// with them the device code is what it was before the helpers existed, and through the helpers it measured 1.3 % slower
+// (DESIGN.md "The shared item loop").  A change to the fetch is made there and here.  A lane owns its item through its
+// rays, phase by phase:
 //   phase 0  the any-hit ray toward the light chosen for the item            -> direct
 //   phase 1  the closest-hit bounce ray (BDPT_GI_INDIRECT)                   -> environment, or the shaded hit's NEE term
 //   phase 2  the any-hit ray from the bounce hit toward its light            -> bounce
@@ -31,10 +32,10 @@
 // bounce direction is drawn; diffuse is re-read from the record when the item retires.
 #include "kernels.h"
 
+#include "device_item_loop.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_scene.hpp"
-#include "device_trace.hpp"
 #include "launch.hpp"
 
 namespace bdpt {
@@ -157,7 +158,7 @@ __device__ __forceinline__ void giRetire(const GiDev& Q, uint32_t i, bool indire
 
 }  // namespace
 
-// cursor: as trace_rays_kernel (both words zero when a launch starts and when it ends).
+// cursor: as releaseCursor has it (both words zero when a launch starts and when it ends).
 template <int SRC, bool NMAP>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_GI_WAVES_PER_EU, 8))) void gi_kernel(
     SceneDev S, GiDev Q, unsigned long long* cursor) {
@@ -165,6 +166,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_GI_W
   __shared__ int s_stack[kStackLds * kWave];
   int* stk = s_stack + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63u);
+  // refill (device_item_loop.hpp), as this kernel's own text: see the head of the file
   const uint32_t n = itemCount(Q.range.cap, Q.range.count);
   const uint32_t share = (n / gridDim.x + kWave - 1) & ~(uint32_t)(kWave - 1);
   const uint32_t chunk = share < (uint32_t)kWave ? (uint32_t)kWave : (share > kFetchChunk ? kFetchChunk : share);
@@ -236,21 +238,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_GI_W
       if (exhausted) break;  // every lane retired and nothing left to take
       continue;              // (a chunk of dead items: take the next)
     }
-#if BDPT_LEAF_WAIT > 0
-    {
-      uint32_t nNodes = 0;
-      int maxSp = 0;
-      nodeBurst<1, kStackLds, BDPT_NODE_BURST, false>(S, T, stk, has && !parked, nNodes, maxSp);
-    }
-    const unsigned long long waitMask = __ballot(has && !parked && T.cur < 0), nodeMask = __ballot(has && !parked && T.cur >= 0);
-    const int waitNeed = (__popcll(waitMask | nodeMask) * BDPT_LEAF_WAIT_FRAC8 + 7) >> 3;
-    const bool leafPhase = (int)__popcll(waitMask) >= waitNeed || nodeMask == 0ull;
-#else
-    if (has && !parked)
-      while (T.cur >= 0) nodeStep<1, kStackLds>(S, T, stk);
-    const bool leafPhase = true;
-#endif
-    if (leafPhase) {
+    const bool leavesDue = nodePhase<1>(S, T, stk, has && !parked);
+    if (leavesDue) {
       // the any-hit lanes' leaves, then the closest-hit lanes' (a branch no lane of the wave takes is jumped over)
       const bool atLeaf = has && !parked && T.cur < 0;
       bool finished = atLeaf && T.cur == kDone;
@@ -298,11 +287,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_GI_W
         T.cur = kDone;
       }
     }
-    // the lanes whose bounce ray hit, together, once enough of them wait or nothing else can make progress
-    const unsigned long long parkedMask = __ballot(parked);
-    const bool shadePhase =
-        (int)__popcll(parkedMask) >= BDPT_GI_SHADE_MIN || (parkedMask != 0ull && __ballot(has && !parked) == 0ull);
-    if (shadePhase && parked) {
+    // the lanes whose bounce ray hit, together (parkedDue)
+    if (parkedDue<BDPT_GI_SHADE_MIN>(parked, has && !parked) && parked) {
       // IndirectClosestHit (.hlsl:85-108): the hit as bdpt_shade_hits shades it, then its NEE term on a copy of the state
       parked = false;
       giStoreHit(Q, rid, T.best);
@@ -317,32 +303,18 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_GI_W
       phase = 2u;
     }
   }
-  // the last wave to finish leaves the cursor at zero for the next launch (trace_rays_kernel)
-  if (lane == 0) {
-    __threadfence();
-    if (atomicAdd(&cursor[1], 1ull) == (unsigned long long)gridDim.x - 1ull) {
-      cursor[0] = 0ull;
-      cursor[1] = 0ull;
-    }
-  }
+  releaseCursor(cursor, lane);
 }
 
 void launchGi(const SceneDev& S, const GiDev& Q, bool gbuffer, bool normalMap, unsigned long long* cursor, LaunchGrids& G, int numCUs,
               hipStream_t st) {
   if (!Q.range.cap) return;
-  const uint32_t need = wavesFor(Q.range.cap);
   if (gbuffer) {  // the pass: full prepareShadingData, so always with the normal map
-    const auto kernel = gi_kernel<GI_SRC_GBUFFER, true>;
-    uint32_t& g = G.gi[2];
-    if (!g) g = persistentGrid(kernel, numCUs);
-    launchWave(kernel, g < need ? g : need, st, S, Q, cursor);
+    launchPersistent(gi_kernel<GI_SRC_GBUFFER, true>, G.gi[2], Q.range.cap, numCUs, st, S, Q, cursor);
     return;
   }
   withFlag(normalMap, [&](auto NMAP) {
-    const auto kernel = gi_kernel<GI_SRC_SURFACES, NMAP>;
-    uint32_t& g = G.gi[NMAP ? 1 : 0];
-    if (!g) g = persistentGrid(kernel, numCUs);
-    launchWave(kernel, g < need ? g : need, st, S, Q, cursor);
+    launchPersistent(gi_kernel<GI_SRC_SURFACES, NMAP>, G.gi[NMAP ? 1 : 0], Q.range.cap, numCUs, st, S, Q, cursor);
   });
 }
 

@@ -49,4 +49,13 @@ static uint32_t persistentGrid(K kernel, int numCUs) {
   return (uint32_t)(perCU * numCUs);
 }
 
+// A persistent kernel over a list of up to `cap` items: its resident grid (asked once per kernel and kept in the
+// context's `gridSlot`, a LaunchGrids word), no larger than the waves the items can fill.
+template <class K, class... Args>
+static void launchPersistent(K kernel, uint32_t& gridSlot, uint32_t cap, int numCUs, hipStream_t st, Args... args) {
+  if (!gridSlot) gridSlot = persistentGrid(kernel, numCUs);
+  const uint32_t need = wavesFor(cap);
+  launchWave(kernel, gridSlot < need ? gridSlot : need, st, args...);
+}
+
 }  // namespace bdpt

@@ -4,21 +4,20 @@
 // bdpt_bsdf_query(SAMPLE) and glue that selects the hits, multiplies the colours and builds the next rays — i.e. shootRay /
 // the closest-hit shader of the reference's walks (BDPT/BDPTMain.rt.hlsl:106-145, BDPT/globalIlluminationRay.hlsli:1-45).
 //
-// Built on trace_rays_kernel<BDPT_TRACE_CLOSEST> (trace_rays.hip): one wave per workgroup, 64 traversal slots refilled from
-// the item list by ballot + popcount prefix with one atomic per chunk, node bursts with deferred leaves, kStackLds stack
-// rows in LDS and the rest in the context's overflow area, the context's ray cursor with its reset protocol.  What differs
-// is what a finished lane does: it shades the hit (shadeHit<false>, seen from the ray's origin, as shade_hits_kernel),
-// samples the record (sampleBRDF on the stored words, as bsdf_query_kernel), writes vertex `step` and, while steps remain,
-// starts the next ray in its own slot; it retires when its walk has ended, after writing the steps that do not exist.
-// Finished lanes wait until BDPT_WALKQ_SHADE_MIN of them can be shaded together.  Between bounces a lane keeps its item, its step, the running
-// colour and the specular bit; origin and direction live in the traversal state.  A ghost re-reads the record it copies
-// from the lane's own previous plane (step 0: from `first`), so the 24-word payload is not held across the traversal.
+// Built on the item loop of device_item_loop.hpp (fetch, node and leaf phases, parking, cursor release) with closest-hit
+// rays.  What is its own is what an answered lane does: it shades the hit (shadeHit<false>, seen from the ray's origin,
+// as shade_hits_kernel), samples the record (sampleBRDF on the stored words, as bsdf_query_kernel), writes vertex `step`
+// and, while steps remain, starts the next ray in its own slot; it retires when its walk has ended, after writing the
+// steps that do not exist.  Finished lanes wait until BDPT_WALKQ_SHADE_MIN of them can be shaded together.  Between
+// bounces a lane keeps its item, its step, the running colour and the specular bit; origin and direction live in the
+// traversal state.  A ghost re-reads the record it copies from the lane's own previous plane (step 0: from `first`), so
+// the 24-word payload is not held across the traversal.
 #include "kernels.h"
 
+#include "device_item_loop.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_scene.hpp"
-#include "device_trace.hpp"
 #include "launch.hpp"
 
 namespace bdpt {
@@ -66,7 +65,7 @@ __device__ __forceinline__ void walkWriteNone(const WalkQueryDev& Q, uint32_t fr
 #endif
 // starts[3i] = (org, tmin), starts[3i+1] = (dir, tmax), starts[3i+2] = (colour, unused) (bdpt_walk_start); plane s of item i
 // at s * cap + i: vertices six float4 (bdpt_surface), info (colour, status), samples two float4, hits one.
-// cursor: as trace_rays_kernel (both words zero when a launch starts and when it ends).
+// cursor: as releaseCursor has it (both words zero when a launch starts and when it ends).
 template <bool GGX>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALKQ_WAVES_PER_EU, 8))) void walk_query_kernel(
     SceneDev S, WalkQueryDev Q, bool fromLobe, unsigned long long* cursor) {
@@ -75,88 +74,32 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK
   int* stk = s_stack + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63u);
   const uint32_t cap = Q.range.cap;
-  const uint32_t n = itemCount(cap, Q.range.count);
-  const uint32_t share = (n / gridDim.x + kWave - 1) & ~(uint32_t)(kWave - 1);
-  const uint32_t chunk = share < (uint32_t)kWave ? (uint32_t)kWave : (share > kFetchChunk ? kFetchChunk : share);
-  bool has = false, exhausted = false, parked = false;
-  uint32_t rid = 0, step = 0, chunkPos = 0, chunkEnd = 0;
-  uint32_t nTris = 0, nAlpha = 0;  // (leafStep's tallies: not kept)
+  ItemFeed F = feedInit(itemCount(cap, Q.range.count));
+  bool has = false, parked = false;
+  uint32_t rid = 0, step = 0;
   f3 pcolor = mk(0);
   bool pspec = false;
   TravState T;
   T.cur = kDone;
-  for (;;) {
-    const unsigned long long idleMask = __ballot(!has);
-    const int idle = __popcll(idleMask);
-    if (!exhausted && idle >= kRefillIdle) {
-      if (chunkPos >= chunkEnd) {  // wave-uniform: take a new chunk
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(cursor, (unsigned long long)chunk);
-        base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
-               (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-        if (base < n) {
-          chunkPos = (uint32_t)base;
-          chunkEnd = (base + chunk < n) ? (uint32_t)(base + chunk) : n;
-        } else {
-          exhausted = true;
-        }
-      }
-      if (!exhausted) {
-        const uint32_t avail = chunkEnd - chunkPos;
-        const uint32_t take = ((uint32_t)idle < avail) ? (uint32_t)idle : avail;
-        const uint32_t rank = (uint32_t)__popcll(idleMask & ((1ull << lane) - 1ull));
-        if (!has && rank < take) {
-          rid = chunkPos + rank;
-          if (Q.alive && Q.alive[rid] == 0) {
-            walkWriteNone(Q, 0u, rid);  // no path: the lane stays idle
-          } else {
-            const float4 a = Q.starts[(size_t)rid * 3], b = Q.starts[(size_t)rid * 3 + 1], c = Q.starts[(size_t)rid * 3 + 2];
-            float4 org = a;
-            if (Q.first) org = Q.first[(size_t)rid * 6];
-            pcolor = mk(c.x, c.y, c.z);
-            pspec = Q.firstSpecular ? Q.firstSpecular[rid] != 0 : false;
-            step = 0;
-            travInit(T, mk(org.x, org.y, org.z), mk(b.x, b.y, b.z), a.w, b.w);
-            has = true;
-          }
-        }
-        chunkPos += take;
-      }
+  while (refill(F, cursor, lane, has, [&](uint32_t item) {
+    rid = item;
+    if (Q.alive && Q.alive[rid] == 0) {
+      walkWriteNone(Q, 0u, rid);  // no path: the lane stays idle
+    } else {
+      const float4 a = Q.starts[(size_t)rid * 3], b = Q.starts[(size_t)rid * 3 + 1], c = Q.starts[(size_t)rid * 3 + 2];
+      float4 org = a;
+      if (Q.first) org = Q.first[(size_t)rid * 6];
+      pcolor = mk(c.x, c.y, c.z);
+      pspec = Q.firstSpecular ? Q.firstSpecular[rid] != 0 : false;
+      step = 0;
+      travInit(T, mk(org.x, org.y, org.z), mk(b.x, b.y, b.z), a.w, b.w);
+      has = true;
     }
-    if (__ballot(has) == 0ull) {
-      if (exhausted) break;  // every lane retired and nothing left to take
-      continue;              // (a chunk of items without a path: take the next)
-    }
-#if BDPT_LEAF_WAIT > 0
-    {
-      uint32_t nNodes = 0;
-      int maxSp = 0;
-      nodeBurst<1, kStackLds, BDPT_NODE_BURST, false>(S, T, stk, has && !parked, nNodes, maxSp);
-    }
-    const unsigned long long waitMask = __ballot(has && !parked && T.cur < 0), nodeMask = __ballot(has && !parked && T.cur >= 0);
-    const int waitNeed = (__popcll(waitMask | nodeMask) * BDPT_LEAF_WAIT_FRAC8 + 7) >> 3;
-    const bool leafPhase = (int)__popcll(waitMask) >= waitNeed || nodeMask == 0ull;
-#else
-    if (has && !parked)
-      while (T.cur >= 0) nodeStep<1, kStackLds>(S, T, stk);
-    const bool leafPhase = true;
-#endif
-    if (leafPhase && has && !parked && T.cur < 0) {
-      bool finished = (T.cur == kDone);
-      if (!finished) {
-        finished = leafStep<BDPT_TRACE_CLOSEST, false>(S, T, nTris, nAlpha);
-        if (!finished) {
-          T.cur = travPop<kStackLds>(S, T, stk);
-          finished = (T.cur == kDone);
-        }
-      }
-      parked = finished;
-    }
-    // the parked lanes, together, once enough of them wait or nothing else can make progress: vertex `step` of their item
-    const unsigned long long parkedMask = __ballot(parked);
-    const bool shadePhase =
-        (int)__popcll(parkedMask) >= BDPT_WALKQ_SHADE_MIN || (parkedMask != 0ull && __ballot(has && !parked) == 0ull);
-    if (shadePhase && parked) {
+  })) {
+    const bool leavesDue = nodePhase<1>(S, T, stk, has && !parked);
+    if (leavesDue && has && !parked && T.cur < 0) parked = leafPhase<BDPT_TRACE_CLOSEST>(S, T, stk);
+    // the parked lanes, together (parkedDue): vertex `step` of their item
+    if (parkedDue<BDPT_WALKQ_SHADE_MIN>(parked, has && !parked) && parked) {
       parked = false;
       const size_t at = (size_t)step * cap + rid;
       float4* o = Q.vertices + at * 6;
@@ -230,25 +173,14 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_WALK
       }
     }
   }
-  // the last wave to finish leaves the cursor at zero for the next launch (trace_rays_kernel)
-  if (lane == 0) {
-    __threadfence();
-    if (atomicAdd(&cursor[1], 1ull) == (unsigned long long)gridDim.x - 1ull) {
-      cursor[0] = 0ull;
-      cursor[1] = 0ull;
-    }
-  }
+  releaseCursor(cursor, lane);
 }
 
 void launchWalkQuery(const SceneDev& S, const WalkQueryDev& Q, bool ggx, bool fromLobe, unsigned long long* cursor, LaunchGrids& G,
                      int numCUs, hipStream_t st) {
   if (!Q.range.cap) return;
   withFlag(ggx, [&](auto GGX) {
-    const auto kernel = walk_query_kernel<GGX>;
-    uint32_t& g = G.walkQuery[GGX ? 1 : 0];
-    if (!g) g = persistentGrid(kernel, numCUs);
-    const uint32_t need = wavesFor(Q.range.cap);
-    launchWave(kernel, g < need ? g : need, st, S, Q, fromLobe, cursor);
+    launchPersistent(walk_query_kernel<GGX>, G.walkQuery[GGX ? 1 : 0], Q.range.cap, numCUs, st, S, Q, fromLobe, cursor);
   });
 }
 
