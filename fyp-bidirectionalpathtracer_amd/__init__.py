@@ -21,6 +21,7 @@ GBUFFER_CHANNELS = ("WorldPosition", "WorldNormal", "MaterialDiffuse", "Material
 OUTPUT_CHANNEL = "PipelineOutput"  # ResourceManager::kOutputChannel, SharedUtils/ResourceManager.cpp:22
 AO_CHANNEL = "AmbientOcclusion"  # the channel FramePipeline.ambient_occlusion and bdpt_render --ao write
 GI_CHANNEL = "DiffuseGI"  # the channel FramePipeline.diffuse_gi and bdpt_render --gi write
+DIRECT_CHANNEL = "DirectLighting"  # the channel FramePipeline.direct_lighting and bdpt_render --direct write
 
 
 class BdptError(RuntimeError):
@@ -818,6 +819,61 @@ class Context:
         flags), the full-frame G-buffer, and the full-frame RGBA32F image at `out_ptr`, which gets (colour, 1)."""
         self._check(self._lib.bdpt_gi_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_gi_execute")
 
+    # ---- direct lighting (include/bdpt.h "Direct lighting", DESIGN.md) ----
+    def direct_lighting(self, surfaces, *, alive=None, min_t, use_hints=False, visible=False, traced=False, out=None, count=None,
+                        stream=None):
+        """bdpt_direct_query: the reference's Lambertian-plus-shadows pass per (N, 24) bdpt_surface record (posW, N, diffuse,
+        specular and prim are read): every light of the scene, at most one any-hit ray each, in one launch — the loop, per
+        light, set_lights([light]) -> sample_lights(mat_index=1) -> trace_rays("any") -> accumulate, bit for bit.  No seeds:
+        nothing is drawn.  use_hints tries the lights' occluder hints first (the same answer, fewer traversals).  Returns
+        (N, 4) float32 (colour, 1); a miss record (prim < 0), or an item whose `alive` byte is 0, gives (diffuse, or specular
+        where diffuse is black, 1).  visible / traced: False (not wanted), True (allocated) or an (N,) int32 / uint32 GPU
+        tensor: per item bit k = light k was added unshadowed / a ray or hint test was spent on light k; with either the
+        result is a tuple (colour, visible if wanted, traced if wanted).  GPU tensors only for alive, visible and traced.
+        `out` and `count` as for the other queries."""
+        import torch
+        records, words = (torch.float32, torch.int32), (torch.int32, torch.uint32)  # the dtypes a record / a 32-bit word may have
+        masks = []
+        for name, m in (("visible", visible), ("traced", traced)):
+            if m is True:
+                if not getattr(surfaces, "is_cuda", False) or surfaces.dim() < 1:
+                    raise BdptError(f"direct_lighting: {name}=True goes with GPU tensor inputs")
+                m = torch.empty((int(surfaces.shape[0]),), dtype=torch.int32, device=surfaces.device)
+            elif m is False:
+                m = None
+            elif m is None or isinstance(m, (bool, int, float)):
+                raise BdptError(f"direct_lighting: {name} must be False, True or a GPU tensor, not {m!r}")
+            masks.append(m)
+        extras = [("alive", alive, None, (torch.uint8,)), ("visible", masks[0], None, words), ("traced", masks[1], None, words)]
+
+        def run(ptrs, n, cnt, res):
+            d = abi.DirectDesc()
+            d.num, d.numDevice, d.minT, d.flags = n, cnt, float(min_t), abi.DIRECT_USE_HINTS if use_hints else 0
+            d.surfaces, d.color = ptrs[0], res
+            d.alive, d.visible, d.traced = (None if t is None else t.data_ptr() for t in (alive, masks[0], masks[1]))
+            return self._lib.bdpt_direct_query(self._h, C.byref(d), stream)
+
+        color = self._surface_query("direct_lighting", [("surfaces", surfaces, 24, records)], (4, (torch.float32,)), run, out, count,
+                                    extras=extras, fn="bdpt_direct_query")
+        wanted = [m for m in masks if m is not None]
+        return (color, *wanted) if wanted else color
+
+    def direct_execute(self, gbuffer, out, *, min_t, use_hints=False, stream=None):
+        """bdpt_direct_execute: the reference's LambertianPlusShadowPass on the context's tile pixels — the full-frame G-buffer
+        (abi.GBuffer) and the full-frame (H, W, 4) float32 GPU image `out`, which gets (colour, 1) at the tile's pixels."""
+        import torch
+        if not isinstance(gbuffer, abi.GBuffer):
+            raise BdptError("direct_execute: gbuffer must be an abi.GBuffer")
+        frame = getattr(self, "_frame", None)
+        if frame is None:
+            raise BdptError("direct_execute: no frame size (resize first)")
+        self._check_gpu(out, "direct_execute", "out", frame + (4,), (torch.float32,))
+        p = abi.DirectParams()
+        p.minT, p.flags = float(min_t), abi.DIRECT_USE_HINTS if use_hints else 0
+        self._check(self._lib.bdpt_direct_execute(self._h, C.byref(p), C.byref(gbuffer), C.c_void_p(out.data_ptr()), stream),
+                    "bdpt_direct_execute")
+        return p
+
     @staticmethod
     def _bsdf_mode(what, mat_index, from_lobe):
         if mat_index not in (0, 1) or isinstance(mat_index, bool):
@@ -1340,6 +1396,7 @@ class FramePipeline:
         self.ao_frame = 0  # CommonPasses/AmbientOcclusionPass.h:54
         self.last_ao_params = None
         self._ao_radius = None  # the pass's default radius for the scene, made on first use
+        self.last_direct_params = None
         self.gi_frame = 0x1337  # CommonPasses/SimpleDiffuseGIPass.h:62
         self.last_gi_params = None
         self.accum_count = 0
@@ -1624,6 +1681,21 @@ class FramePipeline:
         self.ctx.gi_execute(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
         self.gi_frame += 1
         self.last_gi_params = p
+        return out
+
+    def direct_lighting(self, use_hints=False):
+        """The reference's LambertianPlusShadowPass on this pipeline's G-buffer as it stands (render_frame, or a gbuffer_execute
+        of the caller's, fills it) and stream: Context.direct_execute with the pipeline's min_t.  There is no frame counter:
+        the pass draws nothing, so one call is converged direct lighting.  use_hints tries the lights' occluder hints first
+        (the same image).  Returns the (H, W, 4) float32 channel "DirectLighting" ((colour, 1); a tile or stripes pipeline
+        writes its own rows), also in ``channels``; ``last_direct_params`` keeps the abi.DirectParams used."""
+        if not isinstance(use_hints, bool):
+            raise BdptError(f"direct_lighting: use_hints must be a bool, not {use_hints!r}")
+        if DIRECT_CHANNEL not in self.channels:
+            with self.torch.cuda.device(self.dev):
+                self.channels[DIRECT_CHANNEL] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
+        out = self.channels[DIRECT_CHANNEL]
+        self.last_direct_params = self.ctx.direct_execute(self.gb, out, min_t=self.min_t, use_hints=use_hints, stream=self._stream_ptr())
         return out
 
     def set_lights(self, lights):

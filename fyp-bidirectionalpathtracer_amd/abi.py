@@ -56,6 +56,7 @@ WALK_STATUS_STORED, WALK_STATUS_REAL, WALK_STATUS_SPECULAR = 1, 2, 4
 AO_MAX_SAMPLES = 64
 GI_INDIRECT, GI_UNIFORM, GI_SHADE_FROM_VIEW = 1, 2, 4
 GI_STATUS_DIRECT_OCCLUDED, GI_STATUS_BOUNCE_HIT, GI_STATUS_BOUNCE_OCCLUDED = 1, 2, 4
+DIRECT_USE_HINTS = 1
 
 
 class Material(C.Structure):
@@ -306,6 +307,16 @@ class GiParams(C.Structure):
     _fields_ = [("frameCount", C.c_uint32), ("minT", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DirectDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("flags", C.c_uint32), ("numDevice", C.c_void_p), ("minT", C.c_float), ("reserved", C.c_uint32),
+                ("surfaces", C.c_void_p), ("alive", C.c_void_p), ("color", C.c_void_p), ("visible", C.c_void_p),
+                ("traced", C.c_void_p)]
+
+
+class DirectParams(C.Structure):
+    _fields_ = [("minT", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 BMFR_MAX_PLANES = BDPT_MAX_LIGHTS + 2
 
 
@@ -365,6 +376,8 @@ PROTOTYPES = {
     "bdpt_ao_execute": (C.c_int, [C.c_void_p, C.POINTER(AoParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_gi_query": (C.c_int, [C.c_void_p, C.POINTER(GiDesc), C.c_void_p]),
     "bdpt_gi_execute": (C.c_int, [C.c_void_p, C.POINTER(GiParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "bdpt_direct_query": (C.c_int, [C.c_void_p, C.POINTER(DirectDesc), C.c_void_p]),
+    "bdpt_direct_execute": (C.c_int, [C.c_void_p, C.POINTER(DirectParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit_pieces": (C.c_int, [C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),

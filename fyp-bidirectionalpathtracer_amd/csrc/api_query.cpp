@@ -1,7 +1,7 @@
 // api_query.cpp — the per-item queries of the C ABI (include/bdpt.h): bdpt_trace_rays, bdpt_camera_rays, bdpt_shade_hits,
-// bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query, bdpt_ao_query, bdpt_gi_query and
-// bdpt_motion_query, on a caller's arrays in device memory, and bdpt_ao_execute and bdpt_gi_execute, the same kernels on the
-// tile's G-buffer pixels.  Every one checks
+// bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query, bdpt_ao_query, bdpt_gi_query,
+// bdpt_direct_query and bdpt_motion_query, on a caller's arrays in device memory, and bdpt_ao_execute, bdpt_gi_execute and
+// bdpt_direct_execute, the same kernels on the tile's G-buffer pixels.  Every one checks
 // its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags and what goes together
 // (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
 // first use of the emitter table), so all can be captured into a hipGraph.
@@ -360,6 +360,56 @@ int bdpt_gi_execute(bdpt_ctx* c, const bdpt_gi_params* p, const bdpt_gbuffer* gb
     for (int k = 0; k < 3; k++) Q.viewPos[k] = c->cam.posW[k];
     giEnvironment(c, Q);
     launchGi(c->S, Q, true, true, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+static_assert(sizeof(bdpt_direct_desc) == 64 && offsetof(bdpt_direct_desc, surfaces) == 24 && sizeof(bdpt_direct_params) == 16,
+              "abi.DirectDesc and abi.DirectParams restate these layouts");
+int bdpt_direct_query(bdpt_ctx* c, const bdpt_direct_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "direct_query")) return rc;
+  if ((d->flags & ~BDPT_DIRECT_USE_HINTS) || d->reserved)
+    return refuse(c, BDPT_E_INVALID, "direct_query",
+                  "flags other than BDPT_DIRECT_USE_HINTS (the emitter table is not part of this call), or non-zero reserved");
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->surfaces, 16) || !aligned(d->color, 16) || (d->visible && !aligned(d->visible, 4)) ||
+      (d->traced && !aligned(d->traced, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "direct_query",
+                  "surfaces, color, visible, traced or numDevice missing or not aligned (records 16 bytes, words 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    DirectDev Q{};
+    Q.surf = f4(d->surfaces);
+    Q.alive = d->alive;
+    Q.color = f4(d->color);
+    Q.visible = d->visible;
+    Q.traced = d->traced;
+    Q.range = {d->num, d->numDevice, d->minT};
+    launchDirect(c->S, Q, false, (d->flags & BDPT_DIRECT_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+int bdpt_direct_execute(bdpt_ctx* c, const bdpt_direct_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
+  if (!c || !p || !gb) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "direct_execute")) return rc;
+  if (!c->haveSize) return refuse(c, BDPT_E_STATE, "direct_execute", "no size (bdpt_resize first)");
+  if ((p->flags & ~BDPT_DIRECT_USE_HINTS) || p->reserved[0] || p->reserved[1])
+    return refuse(c, BDPT_E_INVALID, "direct_execute",
+                  "flags other than BDPT_DIRECT_USE_HINTS (the emitter table is not part of this call), or non-zero reserved");
+  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(gb->materialDiffuse, 8) ||
+      !aligned(gb->materialSpecRough, 8) || !aligned(out, 16))
+    return refuse(c, BDPT_E_INVALID, "direct_execute",
+                  "worldPosition, worldNormal, materialDiffuse, materialSpecRough or out missing or not aligned (16 bytes; the half "
+                  "channels 8)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    DirectDev Q{};
+    Q.gbPosition = f4(gb->worldPosition);
+    Q.gbNormal = gb->worldNormal;
+    Q.gbDiffuse = gb->materialDiffuse;
+    Q.gbSpecRough = gb->materialSpecRough;
+    Q.pix = c->P.pix;
+    Q.out = f4(out);
+    Q.range = {c->P.Np, nullptr, p->minT};
+    launchDirect(c->S, Q, true, (p->flags & BDPT_DIRECT_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 

@@ -310,6 +310,7 @@ struct LaunchGrids {
   uint32_t walkQuery[2] = {0, 0};     // [GGX] (walk_query.hip)
   uint32_t ao[2] = {0, 0};            // [G-buffer source] (ao.hip)
   uint32_t gi[3] = {0, 0, 0};         // [records, records + normal map, G-buffer] (gi.hip)
+  uint32_t direct[4] = {0, 0, 0, 0};  // [G-buffer source][HINTS] (direct.hip)
 };
 // both random walks of the frame: one persistent launch (trace + hit/miss shading in place)
 void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,
@@ -451,6 +452,25 @@ struct GiDev {
 // `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
 void launchGi(const SceneDev& S, const GiDev& Q, bool gbuffer, bool normalMap, unsigned long long* cursor, LaunchGrids& G, int numCUs,
               hipStream_t st);
+// direct.hip: bdpt_direct_query (items are bdpt_surface records) and bdpt_direct_execute (items are the tile's pixels, read
+// from the G-buffer).  Per alive item and light of the scene at most one any-hit ray; no RNG state.
+struct DirectDev {
+  const float4* surf;           // query: bdpt_surface records (six float4 each; posW, N, diffuse, specular and prim are read)
+  const uint8_t* alive;         // query, optional: 0 = the item is dead
+  float4* color;                // query: (colour, 1) per item
+  uint32_t* visible;            // query, optional: bit k = light k's term was added with s_k = 1
+  uint32_t* traced;             // query, optional: bit k = a ray or a hint test was spent on light k
+  const float4* gbPosition;     // execute: WorldPosition of the full frame (w != 0: geometry)
+  const uint16_t* gbNormal;     // execute: WorldNormal (half4) of the full frame
+  const uint16_t* gbDiffuse;    // execute: MaterialDiffuse (half4) of the full frame
+  const uint16_t* gbSpecRough;  // execute: MaterialSpecRough (half4) of the full frame
+  const uint32_t* pix;          // execute: the tile's pixels (PathBuf::pix)
+  float4* out;                  // execute: full-frame RGBA32F, (colour, 1) at the tile's pixels
+  QueryRange range;             // execute: cap = the tile's pixel count, no device word
+};
+// `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
+void launchDirect(const SceneDev& S, const DirectDev& Q, bool gbuffer, bool hints, unsigned long long* cursor, LaunchGrids& G, int numCUs,
+                  hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,

@@ -731,6 +731,50 @@ void SimpleDiffuseGIPass::execute(RenderContext* pRenderContext) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// LambertianPlusShadowPass (CommonPasses/LambertianPlusShadowPass.cpp:33-83)
+// ------------------------------------------------------------------------------------------------
+bool LambertianPlusShadowPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
+  mpResManager = pResManager;
+  // default-format requests: behind a G-buffer pass they lose against its formats, as in the reference (.cpp:39-43)
+  mpResManager->requestTextureResources({"WorldPosition", "WorldNormal", "MaterialDiffuse", "MaterialSpecRough"});
+  mpResManager->requestTextureResource(ResourceManager::kOutputChannel);
+  mpRays = RayLaunch::create(pRenderContext);
+  if (!mpRays) return false;
+  if (mpScene) mpRays->setScene(mpScene);
+  return true;
+}
+void LambertianPlusShadowPass::initScene(RenderContext*, Scene::SharedPtr pScene) {
+  mpScene = pScene;
+  if (mpRays) mpRays->setScene(mpScene);
+}
+void LambertianPlusShadowPass::execute(RenderContext* pRenderContext) {
+  Texture::SharedPtr pDstTex = mpResManager->getClearedTexture(ResourceManager::kOutputChannel, vec4{0.0f, 0.0f, 0.0f, 0.0f});
+  if (!pDstTex || !mpRays || !mpRays->readyToRender()) return;  // silent no-op, .cpp:70
+  Texture::SharedPtr pos = mpResManager->getTexture("WorldPosition"), nrm = mpResManager->getTexture("WorldNormal"),
+                     dif = mpResManager->getTexture("MaterialDiffuse"), spec = mpResManager->getTexture("MaterialSpecRough");
+  if (!pos || !nrm || !dif || !spec || pos->getFormat() != ResourceFormat::RGBA32Float || nrm->getFormat() != ResourceFormat::RGBA16Float ||
+      dif->getFormat() != ResourceFormat::RGBA16Float || spec->getFormat() != ResourceFormat::RGBA16Float ||
+      pDstTex->getFormat() != ResourceFormat::RGBA32Float) {
+    std::fprintf(stderr, "[LambertianPlusShadowPass] needs WorldPosition (RGBA32F), WorldNormal, MaterialDiffuse and MaterialSpecRough "
+                         "(RGBA16F) of a G-buffer pass and an RGBA32F output\n");
+    return;
+  }
+  if (!mpRays->ensureSize(pDstTex->getWidth(), pDstTex->getHeight())) return;
+  bdpt_gbuffer gb;
+  std::memset(&gb, 0, sizeof(gb));
+  gb.worldPosition = (float*)pos->getDevicePointer();
+  gb.worldNormal = (uint16_t*)nrm->getDevicePointer();
+  gb.materialDiffuse = (uint16_t*)dif->getDevicePointer();
+  gb.materialSpecRough = (uint16_t*)spec->getDevicePointer();
+  bdpt_direct_params p;
+  std::memset(&p, 0, sizeof(p));
+  p.minT = mpResManager->getMinTDist();  // gMinT, .cpp:74
+  p.flags = mUseHints ? BDPT_DIRECT_USE_HINTS : 0u;
+  if (bdpt_direct_execute(mpRays->ctx(), &p, &gb, (float*)pDstTex->getDevicePointer(), pRenderContext->getStream()) != BDPT_OK)
+    std::fprintf(stderr, "[LambertianPlusShadowPass] %s\n", mpRays->lastError());
+}
+
+// ------------------------------------------------------------------------------------------------
 // BDPTPass (BidirectionalPathtracing/Passes/BDPTPass.cpp:23-107)
 // ------------------------------------------------------------------------------------------------
 bool BDPTPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
@@ -1239,6 +1283,12 @@ bool SimpleDiffuseGIPass::loadState(RenderContext*, const uint8_t* data, size_t 
     return false;
   mFrameCount = get32(data);
   return true;
+}
+void LambertianPlusShadowPass::saveState(RenderContext*, std::vector<uint8_t>& out) {  // no counter: only what the image depends on
+  put32(out, floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f));
+}
+bool LambertianPlusShadowPass::loadState(RenderContext*, const uint8_t* data, size_t size) {
+  return size == 4 && get32(data) == floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f);
 }
 void BDPTPass::saveState(RenderContext*, std::vector<uint8_t>& out) {
   put32(out, mFrameCount);

@@ -5,6 +5,7 @@
 //   SimpleAccumulationPass  CommonPasses/SimpleAccumulationPass.{h,cpp}
 // the framework's ambient occlusion pass, AmbientOcclusionPass (CommonPasses/AmbientOcclusionPass.{h,cpp}),
 // its one-bounce path tracer, SimpleDiffuseGIPass (CommonPasses/SimpleDiffuseGIPass.{h,cpp}),
+// its direct lighting pass, LambertianPlusShadowPass (CommonPasses/LambertianPlusShadowPass.{h,cpp}),
 // plus RayLaunch, the thin launch wrapper they hold (SharedUtils/RayLaunch.h:85-135): here it owns
 // one bdpt_ctx and forwards to the C ABI of include/bdpt.h instead of building a DXR state object.
 #pragma once
@@ -229,6 +230,31 @@ class SimpleDiffuseGIPass : public RenderPass {
   bool mDoCosSampling = true;       // SimpleDiffuseGIPass.h:58
   bool mDoDirectShadows = true;     // SimpleDiffuseGIPass.h:59: sets gDirectShadow, which the shader does not declare
   uint32_t mFrameCount = 0x1337u;   // SimpleDiffuseGIPass.h:62
+};
+
+// Direct lighting from every light with one shadow ray each (CommonPasses/LambertianPlusShadowPass.{h,cpp}): WorldPosition,
+// WorldNormal, MaterialDiffuse and MaterialSpecRough in, the output channel out; no GUI state and no frame counter, as in the
+// reference (nothing is drawn).  Its ray generation shader with its shadow hit group is bdpt_direct_execute.
+class LambertianPlusShadowPass : public RenderPass {
+ public:
+  using SharedPtr = std::shared_ptr<LambertianPlusShadowPass>;
+  static SharedPtr create() { return SharedPtr(new LambertianPlusShadowPass()); }
+  // BDPT_DIRECT_USE_HINTS: the lights' occluder hints are tried before a traversal (the same image); not in the reference
+  void setUseHints(bool on) { mUseHints = on; }
+
+ protected:
+  LambertianPlusShadowPass() : RenderPass("Lambertian Plus Shadows", "Lambertian Plus Shadow Options") {}
+  bool initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) override;
+  void initScene(RenderContext* pRenderContext, Scene::SharedPtr pScene) override;
+  void execute(RenderContext* pRenderContext) override;
+  bool requiresScene() override { return true; }
+  bool usesRayTracing() override { return true; }
+  void saveState(RenderContext* pRenderContext, std::vector<uint8_t>& out) override;
+  bool loadState(RenderContext* pRenderContext, const uint8_t* data, size_t size) override;
+
+  RayLaunch::SharedPtr mpRays;
+  Scene::SharedPtr mpScene;
+  bool mUseHints = false;
 };
 
 // BMFR denoiser pass (BidirectionalPathtracing/Passes/DenoisePass.{h,cpp}): same channels, switches and defaults

@@ -14,6 +14,7 @@ using bdpt::BlockwiseMultiOrderFeatureRegression;
 using bdpt::Camera;
 using bdpt::Gui;
 using bdpt::KeyboardEvent;
+using bdpt::LambertianPlusShadowPass;
 using bdpt::LightProbeGBufferPass;
 using bdpt::MouseEvent;
 using bdpt::RayLaunch;

@@ -3,7 +3,8 @@
 // --denoise-regression tick its boxes), run for a number of frames, output written as a PFM image.
 // `--ao N` runs the G-buffer pass and the ambient occlusion pass instead (CommonPasses/AmbientOcclusionPass.cpp) and
 // writes the AO channel; `--gi` runs the G-buffer pass, the one-bounce diffuse GI pass (CommonPasses/SimpleDiffuseGIPass.cpp)
-// and the accumulation pass, so that --frames N converges.
+// and the accumulation pass, so that --frames N converges; `--direct` runs the G-buffer pass and the direct lighting pass
+// (CommonPasses/LambertianPlusShadowPass.cpp: every light, one shadow ray each, no draw) and writes its image.
 //
 // Multi-GPU: `--gpus N` runs N such pipelines, one per GPU, each on a host thread of its own
 // with its own RCCL communicator (ncclCommInitAll); `--rank R --world N --id-file F` is the same for one PROCESS per
@@ -52,6 +53,8 @@ struct Options {
   bool gi = false;            // --gi: render the G-buffer, the diffuse GI pass and the accumulation pass instead of the BDPT pipeline
   bool giDirectOnly = false;  // --gi-direct-only: untick "Shooting global illumination rays"
   bool giUniform = false;     // --gi-uniform: untick "Use cosine sampling"
+  bool direct = false;       // --direct: render the G-buffer and the direct lighting pass (every light, one shadow ray each) instead of the BDPT pipeline
+  bool directHints = false;  // --direct-hints: the lights' occluder hints are tried before a traversal (the same image)
   float bend = 0.0f;  // > 0: a skinned scene — a small rig along the scene's height, bent by up to this angle (radians) before every frame
 };
 
@@ -121,8 +124,12 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   }
   // add the passes to the rendering pipeline, as Main.cpp:12-18 does
   pipeline->setPass(0, LightProbeGBufferPass::create());
-  const size_t numPasses = o.ao >= 0 ? 2 : o.gi ? 3 : 4;
-  if (o.ao >= 0) {  // --ao: the G-buffer and the ambient occlusion pass, which writes the output channel
+  const size_t numPasses = (o.ao >= 0 || o.direct) ? 2 : o.gi ? 3 : 4;
+  if (o.direct) {  // --direct: the G-buffer and the direct lighting pass, which writes the output channel (nothing to accumulate: no draw)
+    LambertianPlusShadowPass::SharedPtr lambert = LambertianPlusShadowPass::create();
+    lambert->setUseHints(o.directHints);
+    pipeline->setPass(1, lambert);
+  } else if (o.ao >= 0) {  // --ao: the G-buffer and the ambient occlusion pass, which writes the output channel
     pipeline->setPass(1, AmbientOcclusionPass::create(ResourceManager::kOutputChannel));
   } else if (o.gi) {  // --gi: the G-buffer, the diffuse GI pass into the output channel, and the accumulation pass over it
     pipeline->setPass(1, SimpleDiffuseGIPass::create(ResourceManager::kOutputChannel));
@@ -317,7 +324,11 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
   if (writer) {
     double mean = 0;
     for (size_t i = 0; i < img.size(); i += 4) mean += img[i] + img[i + 1] + img[i + 2];
-    if (o.gi)
+    if (o.direct)
+      std::printf("%s %ux%u direct lighting%s: %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
+                  o.directHints ? ", occluder hints" : "", o.frames - warmup, res.ms, res.ms / (o.frames - warmup),
+                  mean / (3.0 * (double)(img.size() / 4)));
+    else if (o.gi)
       std::printf("%s %ux%u diffuse GI (%s%s): %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
                   o.giDirectOnly ? "direct only" : "one bounce", o.giUniform ? ", uniform sampling" : ", cosine sampling", o.frames - warmup, res.ms,
                   res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
@@ -382,6 +393,8 @@ int main(int argc, char** argv) {
     else if (std::strcmp(argv[i], "--gi") == 0) o.gi = true;
     else if (std::strcmp(argv[i], "--gi-direct-only") == 0) o.giDirectOnly = true;
     else if (std::strcmp(argv[i], "--gi-uniform") == 0) o.giUniform = true;
+    else if (std::strcmp(argv[i], "--direct") == 0) o.direct = true;
+    else if (std::strcmp(argv[i], "--direct-hints") == 0) o.directHints = true;
     else if (std::strcmp(argv[i], "--no-motion") == 0) o.noMotion = true;
     else if (std::strcmp(argv[i], "--tight-refit") == 0) o.tightRefit = true;
     else if (const char* v = next("--gpus")) o.gpus = std::atoi(v);
@@ -392,7 +405,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] [--direct [--direct-hints]] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }
@@ -424,6 +437,20 @@ int main(int argc, char** argv) {
   }
   if (!o.gi && (o.giDirectOnly || o.giUniform)) {
     std::fprintf(stderr, "bdpt_render: --gi-direct-only and --gi-uniform go with --gi\n");
+    return 2;
+  }
+  if (o.direct && (o.ao >= 0 || o.gi || o.gpus > 0 || o.world > 0)) {
+    std::fprintf(stderr, "bdpt_render: --direct renders on one GPU (no --gpus / --world) and not together with --ao N or --gi\n");
+    return 2;
+  }
+  // --direct replaces the BDPT, accumulation and denoise passes: the switches only they read are refused, not ignored
+  if (o.direct && (o.denoise || o.areaLights || o.noMotion)) {
+    std::fprintf(stderr, "bdpt_render: --direct renders the G-buffer and the direct lighting pass only: not with --denoise, "
+                         "--denoise-regression, --area-lights or --no-motion\n");
+    return 2;
+  }
+  if (!o.direct && o.directHints) {
+    std::fprintf(stderr, "bdpt_render: --direct-hints goes with --direct\n");
     return 2;
   }
   if (o.gpus < 0 || o.gpus > 64 || (o.gpus > 0 && o.world > 0)) {

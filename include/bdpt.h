@@ -1314,6 +1314,82 @@ typedef struct bdpt_gi_params {
 } bdpt_gi_params;
 int bdpt_gi_execute(bdpt_ctx* ctx, const bdpt_gi_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
 
+/* ---- Direct lighting: every light of the scene at every item, at most one any-hit ray each, from one persistent kernel ----
+ * bdpt_direct_query is the reference's Lambertian-plus-shadows ray generation shader on a caller's items
+ * (CommonPasses/Data/CommonPasses/lambertianPlusShadows.rt.hlsl:51-149); bdpt_direct_execute is its pass on the G-buffer
+ * (CommonPasses/LambertianPlusShadowPass.cpp:64-83).  It is the only pass with no random draw: every light is evaluated
+ * at every item, so one call is converged direct lighting, and there are no seeds in or out.  It replaces the loop, per
+ * light, bdpt_set_lights(a one-light table) -> bdpt_light_query(NEE, matIndex 1) -> bdpt_trace_rays(BDPT_TRACE_ANY) -> an
+ * accumulate, run with the device functions those calls run, in one launch (DESIGN.md "Direct lighting").
+ *
+ * Item i is alive iff surfaces[i].prim >= 0 and (alive == NULL or alive[i] != 0).
+ *   dif   = diffuse;  if (dot(dif, dif) < 0.00001f) dif = specular                       (.hlsl:109-114)
+ *   dead:   color = (dif, 1) (after the fallback), visible = 0, traced = 0               (.hlsl:117, 120)
+ *   alive:  sum = (0, 0, 0)
+ *           for k = 0 .. numLights-1, in this order:
+ *             (L, I, dist) = getLightData(light k, posW)       Falcor ShadingUtils/Lights.slang:54-102, as every pass here
+ *             LdotN = saturate(dot(N, L))                      NaN saturates to 0
+ *             s_k   = 1.0f if the ray org = posW, tmin = minT, dir = L, tmax = dist is unoccluded as BDPT_TRACE_ANY
+ *                     answers it (the alpha test included, a hit needs tmin < t < tmax), else 0.0f
+ *             sum  += (s_k * LdotN) * I                                                   (.hlsl:140)
+ *           color = (sum * (dif / 3.141592f), 1)    the shader's literal, not fp32 M_PI   (.hlsl:144)
+ * A ray is not traced when it cannot change a bit of the result: when LdotN == 0 (which covers a NaN direction and a
+ * point sitting at the light), or when every component of I is +-0 (as outside a spot light's cone).  In both cases
+ * (0 * LdotN) * I and (1 * LdotN) * I are the same bits; the term is added as written with s_k = 1, so a non-finite
+ * intensity gives the shader's NaN or inf.  bdpt_gi_query's rule "an occluded light contributes exactly +0" deliberately
+ * does NOT apply here: this shader multiplies by its shadow factor, and so does the query: an occluded light of infinite
+ * intensity gives 0 * inf = NaN.
+ * Build definition: the shader's payload is an `int hitDist` initialised to maxT + 1.0f (.hlsl:60-75), which read as
+ * written answers "visible iff no accepted hit" for 0 <= dist < 2^24 and otherwise leaves the answer to a float-to-int
+ * conversion.  The build defines visibility as "no accepted hit in (minT, dist)" for every dist.
+ *
+ * Outputs: color (num float4) is required.  visible[i] (optional): bit k is set iff light k's term was added with
+ * s_k = 1 — the ray was traced and unoccluded, or no ray was needed — so color can be recomputed under changed
+ * intensities without tracing again.  traced[i] (optional): bit k is set iff a ray or a hint test was spent on light k.
+ * BDPT_DIRECT_USE_HINTS: for a point or spot light whose term LdotN * I has a positive component, the nearest triangle
+ * the light sees toward the item (the context's light cube map, as BDPT_LIGHT_USE_HINTS of bdpt_light_query) is tested
+ * first; when it occludes the segment the term is settled with s_k = 0 and no traversal.  A hint only ever saves a
+ * traversal: color, visible and traced are bit-identical with and without the flag.
+ * The emitter table (BDPT_PARAM_AREA_LIGHTS) is not part of this call: the reference's pass has none, and sampling it
+ * needs a draw; the flag is BDPT_E_INVALID.  Lights are those of the scene as bdpt_set_lights last left them.
+ * Record contract: posW, N, diffuse, specular and prim are read, prim for its sign only: nothing a caller supplies
+ * reaches an address.  The floats may be degenerate or non-finite; the results are those of the fp32 arithmetic as written,
+ * and a zero or NaN direction or a NaN origin is a miss (s_k = 1) under the ray contract of bdpt_trace_rays.
+ *
+ * bdpt_direct_execute runs the same for the context's tile pixels (rows or stripes), reading the FULL-FRAME G-buffer
+ * channels worldPosition, worldNormal, materialDiffuse and materialSpecRough (halves decoded to fp32) and writing `out`
+ * (full-frame RGBA32F) at the tile's pixels only; a pixel is alive iff worldPosition.w != 0.  It needs a scene and a
+ * size, not a camera.
+ *
+ * Ordering, capture, counters and numDevice: as bdpt_gi_query — enqueued on `stream` behind the context's previous call,
+ * which also keeps bdpt_trace_rays' INVARIANT; no allocation and no synchronise (exactly one kernel node in a captured
+ * graph); bdpt_get_counters and bdpt_get_stage_times are left alone; items at or beyond min(*numDevice, num) are neither
+ * read nor written.
+ * Errors (nothing is enqueued), in this order: a NULL context, desc / params or gbuffer BDPT_E_INVALID; no scene
+ * (bdpt_direct_execute: or no size) BDPT_E_STATE; flags other than BDPT_DIRECT_USE_HINTS (BDPT_PARAM_AREA_LIGHTS among
+ * them) or non-zero reserved BDPT_E_INVALID; then num == 0 returns BDPT_OK and does nothing; then a missing or misaligned
+ * buffer BDPT_E_INVALID: records, color and `out` 16 bytes, the half channels 8, words (visible, traced, numDevice) 4. */
+#define BDPT_DIRECT_USE_HINTS 1u
+typedef struct bdpt_direct_desc {
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  uint32_t flags;               /* BDPT_DIRECT_USE_HINTS or 0 */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  float minT;                   /* tmin of every ray (bdpt_params::minT) */
+  uint32_t reserved;            /* 0 */
+  const bdpt_surface* surfaces; /* device, 16-byte aligned, num records: posW, N, diffuse, specular and prim are read */
+  const uint8_t* alive;         /* optional: device, one byte per item, 0 = the item is dead */
+  float* color;                 /* device, 16-byte aligned, num float4 */
+  uint32_t* visible;            /* optional: device, num words, bit k: light k was added with s_k = 1 */
+  uint32_t* traced;             /* optional: device, num words, bit k: a ray or a hint test was spent on light k */
+} bdpt_direct_desc;
+int bdpt_direct_query(bdpt_ctx* ctx, const bdpt_direct_desc* desc, void* stream);
+typedef struct bdpt_direct_params {
+  float minT;
+  uint32_t flags;       /* BDPT_DIRECT_USE_HINTS or 0 */
+  uint32_t reserved[2]; /* 0 */
+} bdpt_direct_params;
+int bdpt_direct_execute(bdpt_ctx* ctx, const bdpt_direct_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
+
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
  * a split triangle covering it, every child box containing its subtree's pieces, depth within the traversal stack.
