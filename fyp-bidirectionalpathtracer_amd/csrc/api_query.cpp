@@ -8,22 +8,12 @@
 #include <cstddef>
 #include <string>
 
-#include "context.hpp"
+#include "api_common.hpp"
 
 using namespace bdpt;
 
 namespace {
 
-int refuse(bdpt_ctx* c, int code, const char* what, const char* why) {
-  fail(c, std::string(what) + ": " + why);
-  return code;
-}
-int needScene(bdpt_ctx* c, const char* what) {
-  return c->haveScene ? BDPT_OK : refuse(c, BDPT_E_STATE, what, "no scene (bdpt_set_scene first)");
-}
-int needCamera(bdpt_ctx* c, const char* what) {
-  return c->haveCamera ? BDPT_OK : refuse(c, BDPT_E_STATE, what, "no camera (bdpt_set_camera first)");
-}
 bool frameSizeOk(uint32_t width, uint32_t height) { return width && height && (uint64_t)width * height < (1ull << 32); }
 
 // The three pointers of a compacted ray list: `on` when any is set, and then `whole` (all three are: checked before an
@@ -69,7 +59,7 @@ int bdpt_trace_rays(bdpt_ctx* c, const bdpt_trace_desc* d, void* stream) {
       (d->mode == BDPT_TRACE_ANY ? !d->visible : !aligned(d->hits, 16)))
     return refuse(c, BDPT_E_INVALID, "trace_rays", "rays, hits or visible missing or not aligned (rays and hits 16 bytes, numRaysDevice 4)");
   return enqueueQuery(c, stream, [&](hipStream_t st) {
-    launchTraceRays(c->S, f4(d->rays), d->numRays, d->numRaysDevice, c->rayCursor, (int)d->mode, f4(d->hits), d->visible, c->grids,
+    launchTraceRays(c->scene.S, f4(d->rays), d->numRays, d->numRaysDevice, c->rayCursor, (int)d->mode, f4(d->hits), d->visible, c->grids,
                     c->numCUs, st);
   });
 }
@@ -92,7 +82,7 @@ int bdpt_shade_hits(bdpt_ctx* c, const bdpt_shade_desc* d, void* stream) {
   if (!aligned(d->rays, 16) || !aligned(d->hits, 16) || !aligned(d->surfaces, 16) || (d->numHitsDevice && !aligned(d->numHitsDevice, 4)))
     return refuse(c, BDPT_E_INVALID, "shade_hits", "rays, hits or surfaces missing or not aligned (16 bytes; numHitsDevice 4)");
   return enqueueQuery(c, stream, [&](hipStream_t st) {
-    launchShadeHits(c->S, c->numTriangles, f4(d->rays), f4(d->hits), d->numHits, d->numHitsDevice, (d->flags & BDPT_SHADE_NORMAL_MAP) != 0,
+    launchShadeHits(c->scene.S, c->scene.numTriangles, f4(d->rays), f4(d->hits), d->numHits, d->numHitsDevice, (d->flags & BDPT_SHADE_NORMAL_MAP) != 0,
                     f4(d->surfaces), st);
   });
 }
@@ -136,7 +126,7 @@ int bdpt_light_query(bdpt_ctx* c, const bdpt_light_desc* d, void* stream) {
   if (d->flags & BDPT_PARAM_AREA_LIGHTS) {
     ENTER(c);
     if (int rc = ensureAreaLights(c, reinterpret_cast<hipStream_t>(stream))) return rc;
-    A = c->area;  // n == 0 (no emitter): the plain instances
+    A = c->scene.area;  // n == 0 (no emitter): the plain instances
   }
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     LightQueryDev Q{};
@@ -146,7 +136,7 @@ int bdpt_light_query(bdpt_ctx* c, const bdpt_light_desc* d, void* stream) {
     Q.out = emitMode ? f4(d->emits) : f4(d->samples);
     Q.range = {d->num, d->numDevice, d->minT};
     Q.compact = k.list;
-    launchLightQuery(c->S, Q, A, emitMode, d->matIndex == 0, (d->flags & BDPT_LIGHT_USE_HINTS) != 0, st);
+    launchLightQuery(c->scene.S, Q, A, emitMode, d->matIndex == 0, (d->flags & BDPT_LIGHT_USE_HINTS) != 0, st);
   });
 }
 
@@ -248,7 +238,7 @@ int bdpt_walk_query(bdpt_ctx* c, const bdpt_walk_desc* d, void* stream) {
     Q.range = {d->num, d->numDevice, d->minT};
     Q.steps = d->steps;
     Q.seedPerStep = (d->flags & BDPT_WALK_SEED_PER_STEP) ? 1u : 0u;
-    launchWalkQuery(c->S, Q, d->matIndex == 0, (d->flags & BDPT_PARAM_SPECULAR_FROM_LOBE) != 0, c->rayCursor, c->grids, c->numCUs, st);
+    launchWalkQuery(c->scene.S, Q, d->matIndex == 0, (d->flags & BDPT_PARAM_SPECULAR_FROM_LOBE) != 0, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 
@@ -272,14 +262,14 @@ int bdpt_ao_query(bdpt_ctx* c, const bdpt_ao_desc* d, void* stream) {
     A.range = {d->num, d->numDevice, d->minT};
     A.radius = d->radius;
     A.samples = d->samples;
-    launchAo(c->S, A, false, c->rayCursor, c->grids, c->numCUs, st);
+    launchAo(c->scene.S, A, false, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 
 int bdpt_ao_execute(bdpt_ctx* c, const bdpt_ao_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
   if (!c || !p || !gb) return BDPT_E_INVALID;
   if (int rc = needScene(c, "ao_execute")) return rc;
-  if (!c->haveSize) return refuse(c, BDPT_E_STATE, "ao_execute", "no size (bdpt_resize first)");
+  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "ao_execute", "no size (bdpt_resize first)");
   if (!p->samples || p->samples > BDPT_AO_MAX_SAMPLES || p->reserved)
     return refuse(c, BDPT_E_INVALID, "ao_execute", "samples outside 1 .. BDPT_AO_MAX_SAMPLES, or non-zero reserved");
   if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(out, 16))
@@ -288,13 +278,13 @@ int bdpt_ao_execute(bdpt_ctx* c, const bdpt_ao_params* p, const bdpt_gbuffer* gb
     AoDev A{};
     A.gbPosition = f4(gb->worldPosition);
     A.gbNormal = gb->worldNormal;
-    A.pix = c->P.pix;
+    A.pix = c->frame.P.pix;
     A.out = f4(out);
-    A.range = {c->P.Np, nullptr, p->minT};
+    A.range = {c->frame.P.Np, nullptr, p->minT};
     A.radius = p->radius;
     A.samples = p->samples;
     A.frameCount = p->frameCount;
-    launchAo(c->S, A, true, c->rayCursor, c->grids, c->numCUs, st);
+    launchAo(c->scene.S, A, true, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 
@@ -333,14 +323,14 @@ int bdpt_gi_query(bdpt_ctx* c, const bdpt_gi_desc* d, void* stream) {
     Q.flags = d->flags;
     for (int k = 0; k < 3; k++) Q.viewPos[k] = d->viewPos[k];
     giEnvironment(c, Q);
-    launchGi(c->S, Q, false, (d->shadeFlags & BDPT_SHADE_NORMAL_MAP) != 0, c->rayCursor, c->grids, c->numCUs, st);
+    launchGi(c->scene.S, Q, false, (d->shadeFlags & BDPT_SHADE_NORMAL_MAP) != 0, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 
 int bdpt_gi_execute(bdpt_ctx* c, const bdpt_gi_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
   if (!c || !p || !gb) return BDPT_E_INVALID;
   if (int rc = needScene(c, "gi_execute")) return rc;
-  if (!c->haveSize) return refuse(c, BDPT_E_STATE, "gi_execute", "no size (bdpt_resize first)");
+  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "gi_execute", "no size (bdpt_resize first)");
   if (int rc = needCamera(c, "gi_execute")) return rc;
   if ((p->flags & ~(BDPT_GI_INDIRECT | BDPT_GI_UNIFORM)) || p->reserved)
     return refuse(c, BDPT_E_INVALID, "gi_execute", "flags other than BDPT_GI_INDIRECT | BDPT_GI_UNIFORM, or non-zero reserved");
@@ -352,14 +342,14 @@ int bdpt_gi_execute(bdpt_ctx* c, const bdpt_gi_params* p, const bdpt_gbuffer* gb
     Q.gbPosition = f4(gb->worldPosition);
     Q.gbNormal = gb->worldNormal;
     Q.gbDiffuse = gb->materialDiffuse;
-    Q.pix = c->P.pix;
+    Q.pix = c->frame.P.pix;
     Q.out = f4(out);
-    Q.range = {c->P.Np, nullptr, p->minT};
+    Q.range = {c->frame.P.Np, nullptr, p->minT};
     Q.flags = p->flags | BDPT_GI_SHADE_FROM_VIEW;  // prepareShadingData shades from gCamera.posW
     Q.frameCount = p->frameCount;
     for (int k = 0; k < 3; k++) Q.viewPos[k] = c->cam.posW[k];
     giEnvironment(c, Q);
-    launchGi(c->S, Q, true, true, c->rayCursor, c->grids, c->numCUs, st);
+    launchGi(c->scene.S, Q, true, true, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 
@@ -384,14 +374,14 @@ int bdpt_direct_query(bdpt_ctx* c, const bdpt_direct_desc* d, void* stream) {
     Q.visible = d->visible;
     Q.traced = d->traced;
     Q.range = {d->num, d->numDevice, d->minT};
-    launchDirect(c->S, Q, false, (d->flags & BDPT_DIRECT_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
+    launchDirect(c->scene.S, Q, false, (d->flags & BDPT_DIRECT_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 
 int bdpt_direct_execute(bdpt_ctx* c, const bdpt_direct_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
   if (!c || !p || !gb) return BDPT_E_INVALID;
   if (int rc = needScene(c, "direct_execute")) return rc;
-  if (!c->haveSize) return refuse(c, BDPT_E_STATE, "direct_execute", "no size (bdpt_resize first)");
+  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "direct_execute", "no size (bdpt_resize first)");
   if ((p->flags & ~BDPT_DIRECT_USE_HINTS) || p->reserved[0] || p->reserved[1])
     return refuse(c, BDPT_E_INVALID, "direct_execute",
                   "flags other than BDPT_DIRECT_USE_HINTS (the emitter table is not part of this call), or non-zero reserved");
@@ -406,23 +396,23 @@ int bdpt_direct_execute(bdpt_ctx* c, const bdpt_direct_params* p, const bdpt_gbu
     Q.gbNormal = gb->worldNormal;
     Q.gbDiffuse = gb->materialDiffuse;
     Q.gbSpecRough = gb->materialSpecRough;
-    Q.pix = c->P.pix;
+    Q.pix = c->frame.P.pix;
     Q.out = f4(out);
-    Q.range = {c->P.Np, nullptr, p->minT};
-    launchDirect(c->S, Q, true, (p->flags & BDPT_DIRECT_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
+    Q.range = {c->frame.P.Np, nullptr, p->minT};
+    launchDirect(c->scene.S, Q, true, (p->flags & BDPT_DIRECT_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 
 int bdpt_motion_query(bdpt_ctx* c, const bdpt_motion_desc* d, void* stream) {
   if (!c || !d) return BDPT_E_INVALID;
   if (int rc = needScene(c, "motion_query")) return rc;
-  if (!c->prevPose) return refuse(c, BDPT_E_STATE, "motion_query", "no previous pose (bdpt_prepare(BDPT_PREPARE_MOTION) first)");
+  if (!c->scene.prevPose) return refuse(c, BDPT_E_STATE, "motion_query", "no previous pose (bdpt_prepare(BDPT_PREPARE_MOTION) first)");
   if (d->reserved) return refuse(c, BDPT_E_INVALID, "motion_query", "reserved must be 0");
   if (!d->num) return BDPT_OK;
   if (!aligned(d->hits, 16) || !aligned(d->prevPositions, 16) || (d->numDevice && !aligned(d->numDevice, 4)))
     return refuse(c, BDPT_E_INVALID, "motion_query", "hits or prevPositions missing or not aligned (16 bytes; numDevice 4)");
   return enqueueQuery(c, stream, [&](hipStream_t st) {
-    launchMotionQuery(c->prevPose, c->numTriangles, f4(d->hits), d->num, d->numDevice, f4(d->prevPositions), st);
+    launchMotionQuery(c->scene.prevPose, c->scene.numTriangles, f4(d->hits), d->num, d->numDevice, f4(d->prevPositions), st);
   });
 }
 

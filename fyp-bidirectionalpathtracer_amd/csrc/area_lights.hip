@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kWave) void area_count_scan_kernel(const uint32_t* 
   }
 }
 
-// A triangle's alpha-test record: its place in the ascending list of non-opaque triangles (api.cpp alphaTris), kNoAlphaRec
+// A triangle's alpha-test record: its place in the ascending list of non-opaque triangles (api_scene.cpp alphaTris), kNoAlphaRec
 // for an opaque one
 BD uint32_t alphaRecOf(const uint32_t* __restrict__ alphaTris, uint32_t numAlphaTris, uint32_t t) {
   uint32_t lo = 0, hi = numAlphaTris;

@@ -343,7 +343,7 @@ struct BvhBackend {
   bool uploadTriRecs = false;   // the host's triangle records and boxes are uploaded (BvhRefInput::uploadTriRecs)
 };
 // Test hook: the backend buildBvh uses when its options name none (default: the empty one, all host code).
-// bdpt_test_tree_builder (api.cpp) sets the tree-only shape with the device implementation so that the host-only hash /
+// bdpt_test_tree_builder (api_test.cpp) sets the tree-only shape with the device implementation so that the host-only hash /
 // check hooks can be run over a device-built tree and compared with the host-built one.
 void bvhSetDefaultBackend(const BvhBackend& b);
 

@@ -15,7 +15,7 @@ BD f4 lerp4(f4 a, f4 b, float s) {
 // The two texels (ix0, iy) and (ix1, iy) of one row of an RGBA8 texture: one 8-byte load of (ix0, ix0 + 1), which is the
 // pair wherever they are adjacent (every column but the wrap column, where texel ix1 = 0 is loaded on its own).  A global
 // dwordx2 load needs only 4-byte alignment, which every texel has; the texture keeps one spare texel after its last, so
-// the pair load at the very last texel stays inside (api.cpp bdpt_set_scene).  Textures are device allocations: read
+// the pair load at the very last texel stays inside (api_scene.cpp bdpt_set_scene).  Textures are device allocations: read
 // through global-address-space pointers, not flat ones.
 typedef __attribute__((address_space(1))) const uint32_t gU32;
 typedef __attribute__((address_space(1), aligned(4))) const unsigned long long gU64a4;  // 8 bytes at their real alignment

@@ -1,4 +1,4 @@
-// kernels.h — device-side views and launch entry points shared by kernels.hip and api.cpp.
+// kernels.h — device-side views and launch entry points shared by kernels.hip and the entry points (api*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,7 +31,7 @@ constexpr int kMaxPersistentPerCU = 32;  // resident one-wave workgroups per CU 
 // Rows of the per-context stack overflow area (SceneDev::stackOvf).  INVARIANT the area relies on: it is indexed by
 // workgroup and lane only, so no two persistent traversal launches of one context may be resident at once — every
 // launchWalk / launchTraceShadow of a context goes to the caller's stream, the context's second stream only runs
-// generators (api.cpp bdpt_execute, evFork / evJoin), the test hooks synchronise the device first, and launchTraceRays
+// generators (api_frame.cpp bdpt_execute, evFork / evJoin), the test hooks synchronise the device first, and launchTraceRays
 // (bdpt_trace_rays) goes to the caller's stream ordered behind everything the context's previous call enqueued.
 // Rows: what the kernel with the fewest LDS rows needs (each indexes its own entry - rows-in-LDS from row 0).
 constexpr int kStackOvfRows = KSTACK - (kStackLds < kWalkStackLds ? kStackLds : kWalkStackLds);

@@ -1712,7 +1712,7 @@ __global__ void alpha_recs_kernel(SceneDev S, const uint32_t* __restrict__ alpha
     mode = 0;
   } else if (!alphaSamplesTexture(type, m.texBaseColor)) {
     mode = 1;
-  } else {  // api.cpp made an alpha-quad plane for this texture under the same alphaSamplesTexture rule
+  } else {  // api_scene.cpp made an alpha-quad plane for this texture under the same alphaSamplesTexture rule
     mode = 2;
     const TexDev td = S.matTex[(size_t)mid * 4];
     tw = td.w;

@@ -1,6 +1,6 @@
 // morph.h — morph targets (bdpt_set_morph / bdpt_update_morphed / bdpt_host_morph): the per-vertex arithmetic, shared by
-// the device kernels (deform.hip) and the host entry point (api.cpp), the vertex-major layout both read, and the launcher
-// of the deformation pass, which api.cpp drives.  The arithmetic is the contract of include/bdpt.h "Morph targets": fp32, no contraction
+// the device kernels (deform.hip) and the host entry point (api_deform.cpp), the vertex-major layout both read, and the launcher
+// of the deformation pass, which api_deform.cpp drives.  The arithmetic is the contract of include/bdpt.h "Morph targets": fp32, no contraction
 // (-ffp-contract=off on both sides), one product and one sum per term, terms in ascending target order, a term whose
 // weight is zero (either sign) skipped.  Plain C++ apart from the __host__ __device__ markers (texture_planes.h BDPT_HD).
 #pragma once
@@ -82,7 +82,7 @@ inline MorphCsr morphBuildCsr(uint32_t numVertices, uint32_t numTargets, const u
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 namespace bdpt {
-// A context's morph, all in device memory (api.cpp bdpt_set_morph).  With a skin the base is the skin's rest pose and the
+// A context's morph, all in device memory (api_deform.cpp bdpt_set_morph).  With a skin the base is the skin's rest pose and the
 // outputs are the skin's skinned streams: basePos .. bit are null.  Without one, baseNrm / baseBit and nrm / bit are null
 // for a stream the morph lacks, and the outputs hold the base from bdpt_set_morph on.
 struct MorphDev {

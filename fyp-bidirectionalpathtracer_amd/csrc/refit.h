@@ -1,4 +1,4 @@
-// refit.h — the device refit of bdpt_update_geometry (refit.hip), as api.cpp drives it.
+// refit.h — the device refit of bdpt_update_geometry (refit.hip), as api_deform.cpp drives it.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -11,7 +11,7 @@
 //   3. the shading records (positions, normals when given)
 // With regions (bdpt_prepare(BDPT_PREPARE_REFIT_PIECES), made once by k_refit_regions from the tree as built) step 2 runs
 // its piece-tight instance: a split or clipped reference is bounded by its piece, not by its whole triangle.
-// Nothing here allocates or synchronises: the plan and the scratch are the caller's (api.cpp), so an update with
+// Nothing here allocates or synchronises: the plan and the scratch are the caller's (api_deform.cpp), so an update with
 // device-pointer inputs can be captured into a hipGraph.
 #include <hip/hip_runtime.h>
 
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void k_refit_regions(const BvhRefitNode* __res
   bvhPieceRegionsOfNode(nodes[i], recs, region);
 }
 
-// positions (and normals) of the 128-byte shading records (api.cpp setSceneImpl): three (position, normal, uv) vertices
+// positions (and normals) of the 128-byte shading records (api_scene.cpp sideUploads): three (position, normal, uv) vertices
 // + material id; the uvs and the material id stay
 __global__ __launch_bounds__(256) void k_refit_shade(float4* __restrict__ shade, const uint32_t* __restrict__ idx, const float* __restrict__ pos,
                                                     const float* __restrict__ nrm, uint32_t numTris) {

@@ -1,5 +1,5 @@
 // scene_bvh.h — from a scene description to the acceleration structure bdpt_set_scene uploads: per-triangle traversal
-// flags, the alpha classification of alpha_clip.h, and the build.  Shared by bdpt_set_scene (api.cpp) and the
+// flags, the alpha classification of alpha_clip.h, and the build.  Shared by bdpt_set_scene (api_scene.cpp) and the
 // host-side trace hook (bdpt_host_bvh_*), which walks the same tree on the CPU so that the builder can be tested
 // and its trees compared without a GPU.
 #pragma once

@@ -1,5 +1,5 @@
 // skin.h — skinning (bdpt_set_skin / bdpt_update_skinned / bdpt_host_skin): the per-vertex arithmetic, shared by the
-// device kernels (deform.hip) and the host entry point (api.cpp), and the skin as the kernels see it.
+// device kernels (deform.hip) and the host entry point (api_deform.cpp), and the skin as the kernels see it.
 // The arithmetic is the contract of include/bdpt.h "Skinning": fp32, no contraction (-ffp-contract=off on both sides),
 // every sum in the order written here.  Plain C++ apart from the __host__ __device__ markers (texture_planes.h BDPT_HD).
 #pragma once
@@ -52,7 +52,7 @@ namespace bdpt {
 // else gathers from global memory.
 constexpr uint32_t kSkinLdsBones = 64;
 constexpr uint32_t kSkinLdsMinVertices = 1u << 20;
-// A context's skin, all in device memory (api.cpp bdpt_set_skin).  normals / bitangents (rest and skinned) are null for a
+// A context's skin, all in device memory (api_deform.cpp bdpt_set_skin).  normals / bitangents (rest and skinned) are null for a
 // stream the skin lacks.
 struct SkinDev {
   const float* restPos;

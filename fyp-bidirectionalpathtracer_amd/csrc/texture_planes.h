@@ -1,4 +1,4 @@
-// texture_planes.h — texel addressing shared by the device samplers (device_scene.hpp) and the host set-up (api.cpp):
+// texture_planes.h — texel addressing shared by the device samplers (device_scene.hpp) and the host set-up (api_scene.cpp):
 // wrap addressing, the power-of-two flags of TexDev, which alpha-test records sample a texture, and the alpha-quad plane.
 // Plain C++ apart from the __host__ __device__ markers, so a host-only harness can compile it as it is.
 #pragma once
@@ -45,7 +45,7 @@ BDPT_HD int wrapNext(int i, int n) { return (i + 1 == n) ? 0 : i + 1; }
 // Whether the alpha test of a non-opaque triangle samples its material's base-colour texture (alpha record mode 2):
 // the rule of sampleTexture — every diffuse channel type other than UNUSED and CONST samples, when there is a
 // texture.  The record builder (kernels.hip alpha_recs_kernel) and the choice of textures that get an alpha-quad plane
-// (api.cpp) both use it, so every mode-2 record has a plane.
+// (api_scene.cpp) both use it, so every mode-2 record has a plane.
 BDPT_HD bool alphaSamplesTexture(uint32_t diffuseType, int texBaseColor) {
   return diffuseType != BDPT_CHANNEL_UNUSED && diffuseType != BDPT_CHANNEL_CONST && texBaseColor >= 0;
 }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/variants.sh "<flags1>" "<flags2>" ... — rebuild kernels.hip (EXTRA) and bvh_build.cpp (the -D flags among them:
 # HOSTEXTRA) with each set of flags ON THE GPU BOX and print
-# the bench frame's stage times; restores the default build at the end.  (api.cpp sees the kernel flags too: sizes in
+# the bench frame's stage times; restores the default build at the end.  (api*.cpp see the kernel flags too: sizes in
 # kernels.h that both sides use — the stack overflow area — depend on them.)
 cd fyp-bidirectionalpathtracer_amd/csrc
 for v in "$@"; do
