@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void bmfr_preprocess_kernel(BmfrDev A) {
     } else {
       pfx = ux * (float)A.W - 0.5f;
       pfy = uy * (float)A.H - 0.5f;
-      const int ipx = (int)pfx, ipy = (int)pfy;
+      const int ipx = ftoi(pfx), ipy = ftoi(pfy);  // pfx is a NaN for ux = 0/0, which passes the test above
       const float fx = pfx - (float)ipx, fy = pfy - (float)ipy;
       const float ox = 1.0f - fx, oy = 1.0f - fy;
       wts[0] = ox * oy;
@@ -486,7 +486,7 @@ __global__ __launch_bounds__(256) void bmfr_postprocess_kernel(BmfrDev A) {
     if (accept > 0) {
       const uint32_t pw = A.prevPixel[i];
       const float pfx = f16_to_f32((uint16_t)(pw & 0xffffu)), pfy = f16_to_f32((uint16_t)(pw >> 16));
-      const int ipx = (int)pfx, ipy = (int)pfy;
+      const int ipx = ftoi(pfx), ipy = ftoi(pfy);
       const float fx = pfx - (float)ipx, fy = pfy - (float)ipy;
       const float ox = 1.0f - fx, oy = 1.0f - fy;
       wts[0] = ox * oy;

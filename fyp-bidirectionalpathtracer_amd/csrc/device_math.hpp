@@ -47,6 +47,13 @@ BD float clampUp(float x, float hi) {
   float y = (x > 0.0f) ? x : 0.0f;
   return (y < hi) ? y : hi;
 }
+// HLSL int(float), D3D's ftoi: toward zero, NaN -> 0, out of range saturates ((int) of either is undefined in C++).
+BD int ftoi(float f) {
+  if (f != f) return 0;
+  if (f >= 2147483648.0f) return 2147483647;
+  if (f <= -2147483648.0f) return -2147483647 - 1;
+  return (int)f;
+}
 BD bool isnan3(f3 a) { return (a.x != a.x) || (a.y != a.y) || (a.z != a.z); }
 BD bool allZero(f3 a) { return a.x == 0.0f && a.y == 0.0f && a.z == 0.0f; }
 BD f3 lerp3(f3 a, f3 b, float s) { return a + (b - a) * s; }

@@ -1699,7 +1699,15 @@ typedef struct bdpt_bmfr_params {
  * The filter's blocks need their neighbours, so ALL FOUR buffers must hold the WHOLE frame, also when the context
  * renders only a band or the stripes of one rank: a tiled host gathers them first (bdpt_tile_pack -> all-gather ->
  * bdpt_tile_unpack; host/Passes.cpp BlockwiseMultiOrderFeatureRegression::execute) and every rank filters the same
- * whole frame. */
+ * whole frame.
+ * Non-finite and background texels follow the shaders under D3D rules: max / min return the operand that is not a NaN,
+ * int() of a float rounds toward zero, gives 0 for a NaN and saturates, a load outside a texture is 0.  So a texel whose
+ * reprojection is 0/0 (a worldPosition of (0,0,0) seen from a previous camera at the origin) passes the "outside" test and
+ * tests the four taps around pixel (0,0) with NaN weights; a NaN position or normal fails every tap test and leaves that
+ * texel's colour as it came; in the regression a NaN feature does not decide its block's range, the default QR drops the
+ * column that holds it and leaves the NaN to its own texel, while an infinite feature, any non-finite feature under
+ * BDPT_BMFR_KEEP_LD_FEATURES, or a non-finite colour (its own channel) makes the whole block NaN.  Where an input makes a
+ * result a NaN, a NaN is promised, not which one. */
 int bdpt_bmfr_execute(bdpt_ctx* ctx, const bdpt_bmfr_params* p, const bdpt_gbuffer* features, float* noisy, void* stream);
 
 /* bdpt_bmfr_execute for scenes whose geometry moves.  prevPosition (device, 16-byte aligned, whole-frame float4 texels:

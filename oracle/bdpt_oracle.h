@@ -126,6 +126,9 @@ void oracle_bmfr_destroy(oracle_bmfr* b);
 void oracle_bmfr_reset(oracle_bmfr* b);
 int oracle_bmfr_execute(oracle_bmfr* b, const bdpt_bmfr_params* p, const float* curPos, const float* curNorm,
                         const float* albedo, float* noisy);
+/* bdpt_bmfr_execute_motion: prevPos (float4 per pixel; null = oracle_bmfr_execute) is what preprocess reprojects and compares. */
+int oracle_bmfr_execute_motion(oracle_bmfr* b, const bdpt_bmfr_params* p, const float* curPos, const float* curNorm,
+                               const float* albedo, const float* prevPos, float* noisy);
 /* Test hook: copies out BMFR_PrevNoisy (float4), the accept bools and prev_frame_pixel_f (float2); null skips one. */
 void oracle_bmfr_state(const oracle_bmfr* b, float* prevNoisy, uint32_t* accept, float* prevPixel);
 

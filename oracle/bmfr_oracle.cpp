@@ -15,7 +15,9 @@
 //   * regressionCP.hlsl reads gCurNoisy while other groups write it (mirrored border pixels): reads
 //     come from the copy DenoisePass.cpp:180 blits to BMFR_PrevNoisy just before the dispatch;
 //   * out-of-range texel reads return 0 (D3D semantics), out-of-range writes are dropped;
-//   * mul(float4(p,1), prevViewProjMat) is evaluated as ((m0*x + m1*y) + m2*z) + m3.
+//   * mul(float4(p,1), prevViewProjMat) is evaluated as ((m0*x + m1*y) + m2*z) + m3;
+//   * max / min return the operand that is not a NaN, and int() of a float is ftoi: toward zero, NaN -> 0,
+//     saturating (D3D; std::max keeps or drops a NaN by operand order, and (int) of a NaN is undefined in C++).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -55,6 +57,16 @@ inline float addRandom(float value, uint32_t id, uint32_t sub, uint32_t featureB
   return value + 0.01f * 2 *
                      (hashRandom(id + sub * kLocal + featureBuffer * kBlockEdge * kBlockEdge + frame * kBufferCount * kBlockEdge * kBlockEdge) -
                       0.5f);
+}
+// D3D max / min: a NaN operand is dropped (both NaN: NaN)
+inline float d3dMax(float a, float b) { return (b > a) ? b : ((a == a) ? a : b); }
+inline float d3dMin(float a, float b) { return (b < a) ? b : ((a == a) ? a : b); }
+// D3D ftoi: round toward zero, NaN -> 0, out of range saturates
+inline int ftoi(float f) {
+  if (f != f) return 0;
+  if (f >= 2147483648.0f) return INT32_MAX;
+  if (f <= -2147483648.0f) return INT32_MIN;
+  return (int)f;
 }
 // the shader's parallel reduction: v[i] (op)= v[i+128], +64, ... +2, then v[0] (op) v[1]
 template <class Op>
@@ -104,8 +116,10 @@ void oracle_bmfr_state(const oracle_bmfr* b, float* prevNoisy, uint32_t* accept,
   if (prevPixel) std::memcpy(prevPixel, b->prevPixel.data(), b->prevPixel.size() * 4);
 }
 
-// preprocess.ps.hlsl:33-165
-static void preprocess(oracle_bmfr& B, const bdpt_bmfr_params& P, const float* curPos, const float* curNorm, float* noisy) {
+// preprocess.ps.hlsl:33-165.  prevPos (bdpt_bmfr_execute_motion; null: curPos): where each pixel's surface point was in
+// the previous frame, which is what is reprojected and what the taps' positions are compared with.
+static void preprocess(oracle_bmfr& B, const bdpt_bmfr_params& P, const float* curPos, const float* curNorm, const float* prevPos, float* noisy) {
+  const float* rp = prevPos ? prevPos : curPos;
   const int W = (int)B.W, H = (int)B.H;
   const bool full = (P.flags & BDPT_BMFR_FULL_FRAME) != 0;
   const float* m = P.prevViewProj;
@@ -117,7 +131,7 @@ static void preprocess(oracle_bmfr& B, const bdpt_bmfr_params& P, const float* c
       const float posx = (float)x + 0.5f, posy = (float)y + 0.5f;
       const float texCx = posx / (float)W;
       if (!full && texCx > 0.5f) continue;  // "Denoise only half image for comparison"
-      const float wx = curPos[i * 4], wy = curPos[i * 4 + 1], wz = curPos[i * 4 + 2];
+      const float wx = rp[i * 4], wy = rp[i * 4 + 1], wz = rp[i * 4 + 2];
       const float nx = curNorm[i * 4], ny = curNorm[i * 4 + 1], nz = curNorm[i * 4 + 2];
       const float cr = noisy[i * 4], cg = noisy[i * 4 + 1], cb = noisy[i * 4 + 2];
       float pfx = posx, pfy = posy;
@@ -137,7 +151,7 @@ static void preprocess(oracle_bmfr& B, const bdpt_bmfr_params& P, const float* c
         }
         pfx = ux * (float)(uint32_t)W - 0.5f;
         pfy = uy * (float)(uint32_t)H - 0.5f;
-        const int ipx = (int)pfx, ipy = (int)pfy;
+        const int ipx = ftoi(pfx), ipy = ftoi(pfy);
         const float fx = pfx - (float)ipx, fy = pfy - (float)ipy;
         const float ox = 1.0f - fx, oy = 1.0f - fy;
         const float wts[4] = {ox * oy, fx * oy, ox * fy, fx * fy};
@@ -169,7 +183,7 @@ static void preprocess(oracle_bmfr& B, const bdpt_bmfr_params& P, const float* c
           pb /= totalWeight;
           sampleSpp /= totalWeight;
           blendAlpha = 1.0f / (sampleSpp + 1.0f);
-          blendAlpha = std::max(blendAlpha, 0.2f);
+          blendAlpha = d3dMax(blendAlpha, 0.2f);  // preprocess.ps.hlsl:148
         }
       }
       float newSpp = 1.0f;
@@ -228,16 +242,16 @@ static void fitBlock(const oracle_bmfr& B, const bdpt_bmfr_params& P, int group,
   for (int fb = kFeaturesNotScaled; fb < kFeatures; fb++) {
     for (int t = 0; t < kLocal; t++) {
       float mx = tmp(t, fb);
-      for (int s = 1; s < kSub; s++) mx = std::max(tmp(s * kLocal + t, fb), mx);
+      for (int s = 1; s < kSub; s++) mx = d3dMax(tmp(s * kLocal + t, fb), mx);
       sumVec[t] = mx;
     }
-    const float blockMax = treeReduce(sumVec, [](float a, float b) { return std::max(a, b); });
+    const float blockMax = treeReduce(sumVec, d3dMax);
     for (int t = 0; t < kLocal; t++) {
       float mn = tmp(t, fb);
-      for (int s = 1; s < kSub; s++) mn = std::min(tmp(s * kLocal + t, fb), mn);
+      for (int s = 1; s < kSub; s++) mn = d3dMin(tmp(s * kLocal + t, fb), mn);
       sumVec[t] = mn;
     }
-    const float blockMin = treeReduce(sumVec, [](float a, float b) { return std::min(a, b); });
+    const float blockMin = treeReduce(sumVec, d3dMin);
     for (int index = 0; index < kBlockPixels; index++) {
       const float v = (blockMax - blockMin > 1.0f) ? (tmp(index, fb) - blockMin) / (blockMax - blockMin) : tmp(index, fb) - blockMin;
       out(index, fb) = v;
@@ -424,7 +438,7 @@ static void postprocess(oracle_bmfr& B, const bdpt_bmfr_params& P, const float* 
         const uint32_t accept = B.accept[i];
         if (accept > 0) {
           const float pfx = B.prevPixel[i * 2], pfy = B.prevPixel[i * 2 + 1];
-          const int ipx = (int)pfx, ipy = (int)pfy;
+          const int ipx = ftoi(pfx), ipy = ftoi(pfy);
           const float fx = pfx - (float)ipx, fy = pfy - (float)ipy;
           const float ox = 1.0f - fx, oy = 1.0f - fy;
           float totalWeight = 0.0f;
@@ -437,7 +451,7 @@ static void postprocess(oracle_bmfr& B, const bdpt_bmfr_params& P, const float* 
             }
           if (totalWeight > 0.0f) {
             blendAlpha = 1.0f / spp;
-            blendAlpha = std::max(blendAlpha, 0.1f);
+            blendAlpha = d3dMax(blendAlpha, 0.1f);  // postprocess.ps.hlsl:81
             for (int c = 0; c < 3; c++) prev[c] /= totalWeight;
           }
         }
@@ -447,11 +461,12 @@ static void postprocess(oracle_bmfr& B, const bdpt_bmfr_params& P, const float* 
     }
 }
 
-// DenoisePass.cpp:146-204
-int oracle_bmfr_execute(oracle_bmfr* b, const bdpt_bmfr_params* p, const float* curPos, const float* curNorm, const float* albedo, float* noisy) {
+// DenoisePass.cpp:146-204; prevPos as in preprocess (null: bdpt_bmfr_execute)
+int oracle_bmfr_execute_motion(oracle_bmfr* b, const bdpt_bmfr_params* p, const float* curPos, const float* curNorm, const float* albedo,
+                               const float* prevPos, float* noisy) {
   if (!b || !p || !curPos || !curNorm || !albedo || !noisy) return -1;
   const size_t n4 = (size_t)b->W * b->H * 4;
-  if (p->flags & BDPT_BMFR_PREPROCESS) preprocess(*b, *p, curPos, curNorm, noisy);
+  if (p->flags & BDPT_BMFR_PREPROCESS) preprocess(*b, *p, curPos, curNorm, prevPos, noisy);
   std::memcpy(b->prevNoisy.data(), noisy, n4 * 4);
   std::memcpy(b->prevNorm.data(), curNorm, n4 * 4);
   std::memcpy(b->prevPos.data(), curPos, n4 * 4);
@@ -468,6 +483,10 @@ int oracle_bmfr_execute(oracle_bmfr* b, const bdpt_bmfr_params* p, const float* 
     std::memcpy(b->prevFiltered.data(), b->accumulated.data(), n4 * 4);
   }
   return 0;
+}
+
+int oracle_bmfr_execute(oracle_bmfr* b, const bdpt_bmfr_params* p, const float* curPos, const float* curNorm, const float* albedo, float* noisy) {
+  return oracle_bmfr_execute_motion(b, p, curPos, curNorm, albedo, nullptr, noisy);
 }
 
 }  // extern "C"

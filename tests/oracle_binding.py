@@ -65,6 +65,8 @@ def load_oracle(abi):
     lib.oracle_bmfr_execute.restype = C.c_int
     lib.oracle_bmfr_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.oracle_bmfr_execute.argtypes = [C.c_void_p, C.POINTER(abi.BmfrParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.oracle_bmfr_execute_motion.restype = C.c_int
+    lib.oracle_bmfr_execute_motion.argtypes = [C.c_void_p, C.POINTER(abi.BmfrParams)] + [C.c_void_p] * 5
     _lib = lib
     return lib
 
@@ -199,11 +201,13 @@ class OracleBmfr:
     def reset(self):
         self.lib.oracle_bmfr_reset(self.h)
 
-    def execute(self, params, cur_pos, cur_norm, albedo, noisy):
-        """All arrays float32 [H*W, 4], C-contiguous; `noisy` is updated in place."""
-        for a in (cur_pos, cur_norm, albedo, noisy):
+    def execute(self, params, cur_pos, cur_norm, albedo, noisy, prev_pos=None):
+        """All arrays float32 [H*W, 4], C-contiguous; `noisy` is updated in place.  prev_pos: bdpt_bmfr_execute_motion's
+        channel."""
+        for a in (cur_pos, cur_norm, albedo, noisy) + (() if prev_pos is None else (prev_pos,)):
             assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"] and a.size == self.W * self.H * 4
-        rc = self.lib.oracle_bmfr_execute(self.h, C.byref(params), _p(cur_pos), _p(cur_norm), _p(albedo), _p(noisy))
+        rc = self.lib.oracle_bmfr_execute_motion(self.h, C.byref(params), _p(cur_pos), _p(cur_norm), _p(albedo),
+                                                 None if prev_pos is None else _p(prev_pos), _p(noisy))
         assert rc == 0
         return noisy
 
