@@ -22,6 +22,7 @@ OUTPUT_CHANNEL = "PipelineOutput"  # ResourceManager::kOutputChannel, SharedUtil
 AO_CHANNEL = "AmbientOcclusion"  # the channel FramePipeline.ambient_occlusion and bdpt_render --ao write
 GI_CHANNEL = "DiffuseGI"  # the channel FramePipeline.diffuse_gi and bdpt_render --gi write
 DIRECT_CHANNEL = "DirectLighting"  # the channel FramePipeline.direct_lighting and bdpt_render --direct write
+SKY_CHANNEL = "SkyLighting"  # the channel FramePipeline.sky_lighting and bdpt_render --sky write
 
 
 class BdptError(RuntimeError):
@@ -181,6 +182,11 @@ def _host_to_device(array, device):
 
 class Context:
     """One bdpt_ctx = one GPU (one ctx per GPU, not thread-safe)."""
+
+    # set_environment calls made through this object, and the count at the last env_prepare: FramePipeline.sky_lighting
+    # prepares again when they differ.  Only calls are counted: a map rewritten in place is the caller's to prepare again.
+    _env_serial = 0
+    _env_prepared = None
 
     def __init__(self, device=0):
         self._lib = load_library()
@@ -780,6 +786,103 @@ class Context:
         samples), the full-frame G-buffer, and the full-frame RGBA32F image at `out_ptr`, which gets (ao, ao, ao, 1)."""
         self._check(self._lib.bdpt_ao_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_ao_execute")
 
+    # ---- environment lighting (include/bdpt.h "Environment lighting", DESIGN.md) ----
+    @staticmethod
+    def _sky_samples(what, samples):
+        if isinstance(samples, bool) or not isinstance(samples, int) or not 1 <= samples <= abi.SKY_MAX_SAMPLES:
+            raise BdptError(f"{what}: samples must be an integer in 1 .. {abi.SKY_MAX_SAMPLES}, not {samples!r}")
+        return samples
+
+    def env_prepare(self, stream=None):
+        """bdpt_env_prepare: build the sampling table of the map set_environment bound (the first call for a map size
+        allocates: not inside a capture).  set_environment drops the table; the environment queries need it.  The table
+        is a snapshot of the map's contents: a caller who rewrites the map in place (an animated probe) calls this again."""
+        self._check(self._lib.bdpt_env_prepare(self._h, stream), "bdpt_env_prepare")
+        self._env_prepared = self._env_serial
+
+    def env_info(self):
+        """bdpt_get_env_info (synchronises): abi.EnvInfo — width, height, total, max, the scan chunk sizes, the table's bytes
+        and device addresses."""
+        info = abi.EnvInfo()
+        self._check(self._lib.bdpt_get_env_info(self._h, C.byref(info)), "bdpt_get_env_info")
+        return info
+
+    def env_table(self):
+        """Test hook bdpt_test_env_table (synchronises): the table as numpy (cdf (H, W) uint32, rowCdf (H,) uint64)."""
+        import numpy as np
+        info = self.env_info()
+        cdf, row = np.zeros((info.height, info.width), np.uint32), np.zeros(info.height, np.uint64)
+        self._check(self._lib.bdpt_test_env_table(self._h, cdf.ctypes.data, row.ctypes.data), "bdpt_test_env_table")
+        return cdf, row
+
+    def env_sample(self, surfaces, seeds, mat_index=1, min_t=1e-4, out=None, seeds_out=None, compact=None, count=None, stream=None):
+        """bdpt_env_query(SAMPLE): one importance sample of the environment map per (N, 24) bdpt_surface record and seed ((N,)
+        uint32 / int32 RNG states; four draws each).  Returns (N, 20) float32 in the bdpt_env_sample layout: 0-7 the shadow
+        ray (origin, tmin, direction, 1e38), 8-10 the texel's radiance, 11 the solid-angle pdf, 12-14 the unweighted,
+        unclamped value of a visible environment (mat_index 1 Lambertian, 0 GGX), 15 the texel y * W + x and 16 the status
+        (both through .view(torch.int32); status bit 0 = the value is non-zero).  A miss record gives zeros.  GPU tensors
+        only: seeds_out (N,) takes the states after the four draws (it may be `seeds`); compact = (rays (N, 8) float32,
+        items (N,), count (1,), zeroed by the caller) takes the dense list of the non-zero items' rays, for
+        trace_rays(rays, "any", count=count).  `out` and `count` as for the other queries."""
+        import torch
+        i32, u32 = (torch.float32, torch.int32), (torch.int32, torch.uint32)
+        mat, _ = self._bsdf_mode("env_sample", mat_index, False)
+        more, compact = self._compact_extras("env_sample", compact)
+
+        def run(ptrs, n, cnt, res):
+            d = abi.EnvDesc()
+            d.mode, d.num, d.numDevice, d.matIndex, d.minT = abi.ENV_SAMPLE, n, cnt, mat, float(min_t)
+            d.surfaces, d.seeds, d.samples = ptrs[0], ptrs[1], res
+            d.seedsOut = None if seeds_out is None else seeds_out.data_ptr()
+            d.compactRays, d.compactItems, d.compactCount = (None if t is None else t.data_ptr() for t in compact)
+            return self._lib.bdpt_env_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("env_sample", [("surfaces", surfaces, 24, i32), ("seeds", seeds, None, u32)], (20, i32), run, out,
+                                   count, extras=[("seeds_out", seeds_out, None, u32)] + more, fn="bdpt_env_query")
+
+    def env_eval(self, dirs, out=None, count=None, stream=None):
+        """bdpt_env_query(EVAL): the environment toward (N, 4) float32 directions (xyz read), for MIS against env_sample.
+        Returns (N, 8) float32 in the bdpt_env_eval layout: 0-2 the radiance (the G-buffer miss shader's lookup), 3 the
+        sampler's solid-angle pdf, 4 (through .view(torch.int32)) the texel, -1 = outside the map."""
+        import torch
+
+        def run(ptrs, n, cnt, res):
+            d = abi.EnvDesc()
+            d.mode, d.num, d.numDevice, d.dirs, d.evals = abi.ENV_EVAL, n, cnt, ptrs[0], res
+            return self._lib.bdpt_env_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("env_eval", [("dirs", dirs, 4, (torch.float32,))], (8, (torch.float32, torch.int32)), run, out, count,
+                                   fn="bdpt_env_query")
+
+    def sky_lighting(self, surfaces, seeds, samples, clamp=float(3.4028234663852886e38), min_t=1e-4, alive=None, out=None, counts=None,
+                     seeds_out=None, count=None, stream=None):
+        """bdpt_sky_query: `samples` (1 .. 64) importance-sampled any-hit rays toward the environment map per (N, 24)
+        bdpt_surface record (posW, N, diffuse and prim are read), in one launch — the loop env_sample(mat_index=1) -> clamp ->
+        trace_rays("any") on the non-zero terms -> ordered add, bit for bit.  seeds (N,) uint32 / int32 RNG states; each
+        sample takes four draws.  `clamp` bounds every component of a sample's value.  Returns (N, 4) float32: (the mean of
+        the visible terms, 1); a miss record (prim < 0), or an item whose `alive` byte is 0, gives (diffuse, 1) without a
+        draw.  GPU tensors only: alive (N,) uint8; counts (N,) takes the samples traced and found unoccluded; seeds_out (N,)
+        the states after 4 * samples draws (it may be `seeds`).  `out` and `count` as for the other queries."""
+        import torch
+        records, words = (torch.float32, torch.int32), (torch.int32, torch.uint32)
+        samples = self._sky_samples("sky_lighting", samples)
+        extras = [("alive", alive, None, (torch.uint8,)), ("counts", counts, None, words), ("seeds_out", seeds_out, None, words)]
+
+        def run(ptrs, n, cnt, res):
+            d = abi.SkyDesc()
+            d.num, d.samples, d.numDevice, d.clampUpper, d.minT = n, samples, cnt, float(clamp), float(min_t)
+            d.surfaces, d.seeds, d.color = ptrs[0], ptrs[1], res
+            d.alive, d.counts, d.seedsOut = (None if t is None else t.data_ptr() for t in (alive, counts, seeds_out))
+            return self._lib.bdpt_sky_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("sky_lighting", [("surfaces", surfaces, 24, records), ("seeds", seeds, None, words)],
+                                   (4, (torch.float32,)), run, out, count, extras=extras, fn="bdpt_sky_query")
+
+    def sky_execute(self, params, gbuffer, out_ptr, stream=None):
+        """bdpt_sky_execute: sky lighting on the context's tile pixels — abi.SkyParams (frameCount, clampUpper, minT, samples),
+        the full-frame G-buffer, and the full-frame RGBA32F image at `out_ptr`, which gets (colour, 1)."""
+        self._check(self._lib.bdpt_sky_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_sky_execute")
+
     # ---- diffuse GI (include/bdpt.h "Diffuse GI", DESIGN.md) ----
     def diffuse_gi(self, surfaces, seeds, indirect=True, cosine=True, view_pos=None, normal_map=True, min_t=1e-4, alive=None,
                    out=None, hits=None, status=None, seeds_out=None, count=None, stream=None):
@@ -971,6 +1074,7 @@ class Context:
         for i in range(4):
             e.color[i] = float(color[i])
         self._check(self._lib.bdpt_set_environment(self._h, C.byref(e)), "bdpt_set_environment")
+        self._env_serial += 1  # (the library dropped the sampling table: env_prepare again)
 
     def resize(self, width, height, y0, y1, max_depth):
         self._check(self._lib.bdpt_resize(self._h, width, height, Tile(y0, y1), max_depth), "bdpt_resize")
@@ -1397,6 +1501,8 @@ class FramePipeline:
         self.last_ao_params = None
         self._ao_radius = None  # the pass's default radius for the scene, made on first use
         self.last_direct_params = None
+        self.sky_frame = 0
+        self.last_sky_params = None
         self.gi_frame = 0x1337  # CommonPasses/SimpleDiffuseGIPass.h:62
         self.last_gi_params = None
         self.accum_count = 0
@@ -1662,6 +1768,30 @@ class FramePipeline:
         self.ctx.ao_execute(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
         self.ao_frame += 1
         self.last_ao_params = p
+        return out
+
+    def sky_lighting(self, samples=1, clamp=float(3.4028234663852886e38)):
+        """Sky lighting on this pipeline's G-buffer as it stands and stream: Context.sky_execute with the pass's frame
+        counter (from 0, one per call, as ambient_occlusion keeps its own), the pipeline's min_t, `samples` table-sampled rays
+        per pixel (1 .. 64) and `clamp` as the bound of a sample's value.  The environment is the map given to
+        ``ctx.set_environment``; its sampling table is prepared on first use and again whenever the environment was set anew
+        through ``ctx.set_environment``.  The map's contents are not watched: after rewriting the map in place, call
+        ``ctx.env_prepare`` (or set the environment again).
+        Returns the (H, W, 4) float32 channel "SkyLighting" ((colour, 1); a tile or stripes pipeline writes its own rows),
+        also in ``channels``; ``last_sky_params`` keeps the abi.SkyParams used."""
+        p = abi.SkyParams()
+        p.samples = Context._sky_samples("sky_lighting", samples)
+        p.clampUpper = float(clamp)
+        p.minT, p.frameCount = self.min_t, self.sky_frame & 0xFFFFFFFF
+        if self.ctx._env_prepared != self.ctx._env_serial:
+            self.ctx.env_prepare(self._stream_ptr())
+        if SKY_CHANNEL not in self.channels:
+            with self.torch.cuda.device(self.dev):
+                self.channels[SKY_CHANNEL] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
+        out = self.channels[SKY_CHANNEL]
+        self.ctx.sky_execute(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
+        self.sky_frame += 1
+        self.last_sky_params = p
         return out
 
     def diffuse_gi(self, indirect=True, cosine=True):

@@ -317,6 +317,53 @@ class DirectParams(C.Structure):
     _fields_ = [("minT", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+ENV_MAX_DIM = 16384
+ENV_SAMPLE, ENV_EVAL = 0, 1
+ENV_STATUS_NONZERO = 1
+SKY_MAX_SAMPLES = 64
+ENV_NO_TEXEL = 0xFFFFFFFF
+# texels per pass of the table's row scan and rows per pass of its marginal scan (csrc/env_light.h; bdpt_get_env_info
+# reports them): sizes just past them cross a carry
+ENV_ROW_SCAN_CHUNK, ENV_MARGINAL_CHUNK = 64, 64
+
+
+class EnvInfo(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("total", C.c_uint64), ("max", C.c_float),
+                ("rowScanChunk", C.c_uint32), ("marginalChunk", C.c_uint32), ("reserved", C.c_uint32), ("tableBytes", C.c_uint64),
+                ("cdf", C.c_void_p), ("rowCdf", C.c_void_p)]
+
+
+class EnvSample(C.Structure):
+    _fields_ = [("ray", Ray), ("radiance", C.c_float * 3), ("pdf", C.c_float), ("value", C.c_float * 3), ("texel", C.c_uint32),
+                ("status", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class EnvEval(C.Structure):
+    _fields_ = [("radiance", C.c_float * 3), ("pdf", C.c_float), ("texel", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class EnvHostSample(C.Structure):
+    _fields_ = [("dir", C.c_float * 3), ("pdf", C.c_float), ("radiance", C.c_float * 3), ("texel", C.c_uint32)]
+
+
+class EnvDesc(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("num", C.c_uint32), ("numDevice", C.c_void_p), ("matIndex", C.c_uint32), ("flags", C.c_uint32),
+                ("minT", C.c_float), ("reserved", C.c_uint32), ("surfaces", C.c_void_p), ("seeds", C.c_void_p), ("seedsOut", C.c_void_p),
+                ("samples", C.c_void_p), ("dirs", C.c_void_p), ("evals", C.c_void_p), ("compactRays", C.c_void_p),
+                ("compactItems", C.c_void_p), ("compactCount", C.c_void_p)]
+
+
+class SkyDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("samples", C.c_uint32), ("numDevice", C.c_void_p), ("clampUpper", C.c_float), ("minT", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32), ("surfaces", C.c_void_p), ("seeds", C.c_void_p), ("alive", C.c_void_p),
+                ("color", C.c_void_p), ("counts", C.c_void_p), ("seedsOut", C.c_void_p)]
+
+
+class SkyParams(C.Structure):
+    _fields_ = [("frameCount", C.c_uint32), ("clampUpper", C.c_float), ("minT", C.c_float), ("samples", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 BMFR_MAX_PLANES = BDPT_MAX_LIGHTS + 2
 
 
@@ -378,6 +425,17 @@ PROTOTYPES = {
     "bdpt_gi_execute": (C.c_int, [C.c_void_p, C.POINTER(GiParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_direct_query": (C.c_int, [C.c_void_p, C.POINTER(DirectDesc), C.c_void_p]),
     "bdpt_direct_execute": (C.c_int, [C.c_void_p, C.POINTER(DirectParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "bdpt_env_prepare": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bdpt_get_env_info": (C.c_int, [C.c_void_p, C.POINTER(EnvInfo)]),
+    "bdpt_env_query": (C.c_int, [C.c_void_p, C.POINTER(EnvDesc), C.c_void_p]),
+    "bdpt_sky_query": (C.c_int, [C.c_void_p, C.POINTER(SkyDesc), C.c_void_p]),
+    "bdpt_sky_execute": (C.c_int, [C.c_void_p, C.POINTER(SkyParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "bdpt_host_env_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "bdpt_host_env_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                        C.c_void_p]),
+    "bdpt_host_env_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bdpt_test_env_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdpt_test_host_env_search": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bdpt_host_bvh_refit": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdpt_host_bvh_refit_pieces": (C.c_int, [C.c_void_p]),
     "bdpt_host_bvh_refit_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),

@@ -25,6 +25,7 @@ void bdpt::dropBmfrHistory(BmfrHistory& h) {
     if (p) (void)hipFree(p);
   h = BmfrHistory{};
 }
+void bdpt::dropEnv(EnvState& e) { e = EnvState{}; }
 void bdpt::dropScene(bdpt_ctx* c) {
   dropLightGroups(c->groups);
   c->scene = SceneState{};
@@ -93,6 +94,7 @@ void bdpt_destroy(bdpt_ctx* c) {
   (void)hipDeviceSynchronize();
   dropFrame(c);
   dropScene(c);
+  dropEnv(c->envTable);
   if (c->stackOvf) (void)hipFree(c->stackOvf);
   if (c->rayCursor) (void)hipFree(c->rayCursor);
   if (c->adaptiveSum) (void)hipFree(c->adaptiveSum);

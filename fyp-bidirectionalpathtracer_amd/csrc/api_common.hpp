@@ -100,6 +100,7 @@ void dropMorph(MorphState& m);
 void dropSkin(SkinState& k);  // and its morph
 void dropLightGroups(LightGroups& g);
 void dropBmfrHistory(BmfrHistory& h);
+void dropEnv(EnvState& e);
 void dropScene(bdpt_ctx* c);  // and its skin, its morph, the light groups
 void dropFrame(bdpt_ctx* c);  // and both histories, the light groups
 // the call is ordered after everything this context enqueued before (its last stream joins its side stream)

@@ -1,8 +1,8 @@
 // api_query.cpp — the per-item queries of the C ABI (include/bdpt.h): bdpt_trace_rays, bdpt_camera_rays, bdpt_shade_hits,
 // bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query, bdpt_ao_query, bdpt_gi_query,
-// bdpt_direct_query and bdpt_motion_query, on a caller's arrays in device memory, and bdpt_ao_execute, bdpt_gi_execute and
-// bdpt_direct_execute, the same kernels on the tile's G-buffer pixels.  Every one checks
-// its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags and what goes together
+// bdpt_direct_query, bdpt_env_query, bdpt_sky_query and bdpt_motion_query, on a caller's arrays in device memory, and
+// bdpt_ao_execute, bdpt_gi_execute, bdpt_direct_execute and bdpt_sky_execute, the same kernels on the tile's G-buffer
+// pixels.  Every one checks its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags and what goes together
 // (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
 // first use of the emitter table), so all can be captured into a hipGraph.
 #include <cstddef>
@@ -400,6 +400,104 @@ int bdpt_direct_execute(bdpt_ctx* c, const bdpt_direct_params* p, const bdpt_gbu
     Q.out = f4(out);
     Q.range = {c->frame.P.Np, nullptr, p->minT};
     launchDirect(c->scene.S, Q, true, (p->flags & BDPT_DIRECT_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+namespace {
+int needEnvTable(bdpt_ctx* c, const char* what) {
+  if (c->envTable.ready) return BDPT_OK;
+  return refuse(c, BDPT_E_STATE, what,
+                c->env.envMap ? "no sampling table for the environment map (bdpt_env_prepare first, and again after bdpt_set_environment)"
+                              : "no environment map (bdpt_set_environment with a map, then bdpt_env_prepare)");
+}
+}  // namespace
+
+static_assert(sizeof(bdpt_env_sample) == 80 && offsetof(bdpt_env_sample, radiance) == 32 && offsetof(bdpt_env_sample, value) == 48 &&
+                  offsetof(bdpt_env_sample, texel) == 60 && offsetof(bdpt_env_sample, status) == 64 && sizeof(bdpt_env_eval) == 32 &&
+                  offsetof(bdpt_env_eval, texel) == 16,
+              "the environment query kernels write a sample as five float4 and an evaluation as two");
+static_assert(sizeof(bdpt_env_desc) == 104 && sizeof(bdpt_env_info) == 56 && sizeof(bdpt_sky_desc) == 80 && sizeof(bdpt_sky_params) == 20,
+              "abi.EnvDesc, abi.EnvInfo, abi.SkyDesc and abi.SkyParams restate these layouts");
+int bdpt_env_query(bdpt_ctx* c, const bdpt_env_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needEnvTable(c, "env_query")) return rc;
+  const bool evalMode = d->mode == BDPT_ENV_EVAL;
+  if (d->mode > BDPT_ENV_EVAL || d->matIndex > 1 || d->flags || d->reserved)
+    return refuse(c, BDPT_E_INVALID, "env_query", "unknown mode, non-zero flags or reserved, or matIndex > 1");
+  const CompactArgs k = compactArgs(d->compactRays, d->compactItems, d->compactCount);
+  if (evalMode && k.on) return refuse(c, BDPT_E_INVALID, "env_query", "compaction goes with BDPT_ENV_SAMPLE");
+  if (int rc = needWholeCompact(c, "env_query", k)) return rc;
+  if (!d->num) return BDPT_OK;
+  if ((d->numDevice && !aligned(d->numDevice, 4)) ||
+      (evalMode ? (!aligned(d->dirs, 16) || !aligned(d->evals, 16))
+                : (!aligned(d->surfaces, 16) || !aligned(d->seeds, 4) || !aligned(d->samples, 16) || (d->seedsOut && !aligned(d->seedsOut, 4)))) ||
+      (k.on && !k.aligned))
+    return refuse(c, BDPT_E_INVALID, "env_query",
+                  "surfaces, seeds, samples, dirs, evals or a compaction buffer missing or not aligned (records 16 bytes, words 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    EnvQueryDev Q{};
+    Q.table = c->envTable.table;
+    Q.surf = f4(d->surfaces);
+    Q.seeds = d->seeds;
+    Q.seedsOut = d->seedsOut;
+    Q.dirs = f4(d->dirs);
+    Q.out = evalMode ? f4(d->evals) : f4(d->samples);
+    Q.range = {d->num, d->numDevice, d->minT};
+    Q.compact = k.list;
+    launchEnvQuery(Q, evalMode, d->matIndex == 0, st);
+  });
+}
+
+int bdpt_sky_query(bdpt_ctx* c, const bdpt_sky_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "sky_query")) return rc;
+  if (int rc = needEnvTable(c, "sky_query")) return rc;
+  if (!d->samples || d->samples > BDPT_SKY_MAX_SAMPLES || d->flags || d->reserved)
+    return refuse(c, BDPT_E_INVALID, "sky_query", "samples outside 1 .. BDPT_SKY_MAX_SAMPLES, or non-zero flags or reserved");
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->surfaces, 16) || !aligned(d->seeds, 4) || !aligned(d->color, 16) || (d->counts && !aligned(d->counts, 4)) ||
+      (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "sky_query",
+                  "surfaces, seeds, color, counts, seedsOut or numDevice missing or not aligned (records 16 bytes, words 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    SkyDev Q{};
+    Q.table = c->envTable.table;
+    Q.surf = f4(d->surfaces);
+    Q.seeds = d->seeds;
+    Q.alive = d->alive;
+    Q.color = f4(d->color);
+    Q.counts = d->counts;
+    Q.seedsOut = d->seedsOut;
+    Q.range = {d->num, d->numDevice, d->minT};
+    Q.clampUpper = d->clampUpper;
+    Q.samples = d->samples;
+    launchSky(c->scene.S, Q, false, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+int bdpt_sky_execute(bdpt_ctx* c, const bdpt_sky_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
+  if (!c || !p || !gb) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "sky_execute")) return rc;
+  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "sky_execute", "no size (bdpt_resize first)");
+  if (int rc = needEnvTable(c, "sky_execute")) return rc;
+  if (!p->samples || p->samples > BDPT_SKY_MAX_SAMPLES || p->reserved)
+    return refuse(c, BDPT_E_INVALID, "sky_execute", "samples outside 1 .. BDPT_SKY_MAX_SAMPLES, or non-zero reserved");
+  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(gb->materialDiffuse, 8) || !aligned(out, 16))
+    return refuse(c, BDPT_E_INVALID, "sky_execute",
+                  "worldPosition, worldNormal, materialDiffuse or out missing or not aligned (16 bytes; the half channels 8)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    SkyDev Q{};
+    Q.table = c->envTable.table;
+    Q.gbPosition = f4(gb->worldPosition);
+    Q.gbNormal = gb->worldNormal;
+    Q.gbDiffuse = gb->materialDiffuse;
+    Q.pix = c->frame.P.pix;
+    Q.out = f4(out);
+    Q.range = {c->frame.P.Np, nullptr, p->minT};
+    Q.clampUpper = p->clampUpper;
+    Q.samples = p->samples;
+    Q.frameCount = p->frameCount;
+    launchSky(c->scene.S, Q, true, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 

@@ -2,7 +2,8 @@
 // is derived from them, in named stages), camera and environment, the emitter table of area lights, and the BVH's summary
 // and hashes.  bdpt_set_scene, ensureAreaLights' first build and the hashes allocate and synchronise the device: not
 // inside a stream capture.  bdpt_set_scene is not transactional: validation refuses with the old scene in place, any
-// later failure leaves the context without a scene.  bdpt_set_camera and bdpt_set_environment only store their argument.
+// later failure leaves the context without a scene.  bdpt_set_camera and bdpt_set_environment only store their argument
+// (the latter drops the sampling table bdpt_env_prepare made for the old map).
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -441,8 +442,77 @@ int bdpt_set_camera(bdpt_ctx* c, const bdpt_camera* cam) {
 int bdpt_set_environment(bdpt_ctx* c, const bdpt_environment* env) {
   if (!c) return BDPT_E_INVALID;
   if (env && env->envMap && (!env->width || !env->height)) return refuse(c, BDPT_E_INVALID, "environment", "a map needs a width and a height");
+  if (!c->envTable.allocs.ptrs.empty()) {  // a sampling table made for the old map goes with it (it may still be read)
+    ENTER(c);
+    HIPCHK(c, hipDeviceSynchronize());
+  }
+  dropEnv(c->envTable);
   c->env = env ? *env : bdpt_environment{};
   if (!c->env.envMap) c->env.width = c->env.height = 0;
+  return BDPT_OK;
+}
+
+// The sampling table of the bound map (env_light.hip): allocated on first use or when the size changes (not while
+// capturing), rebuilt by three stream-ordered launches on every call.
+int bdpt_env_prepare(bdpt_ctx* c, void* stream) {
+  if (!c) return BDPT_E_INVALID;
+  if (!c->env.envMap) return refuse(c, BDPT_E_STATE, "env_prepare", "no environment map (bdpt_set_environment with a map first)");
+  const uint32_t W = c->env.width, H = c->env.height;
+  if (W > kEnvMaxDim || H > kEnvMaxDim) return refuse(c, BDPT_E_LIMIT, "env_prepare", "the map exceeds BDPT_ENV_MAX_DIM in width or height");
+  if (!aligned(c->env.envMap, 16)) return refuse(c, BDPT_E_INVALID, "env_prepare", "the map must be 16-byte aligned");
+  ENTER(c);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  EnvState& E = c->envTable;
+  if (E.allocs.ptrs.empty() || E.table.W != W || E.table.H != H) {
+    if (streamIsCapturing(st)) return refuse(c, BDPT_E_STATE, "env_prepare", "the first call for a map size allocates: not inside a stream capture");
+    HIPCHK(c, hipDeviceSynchronize());
+    dropEnv(E);
+    EnvState fresh;
+    uint32_t* cdf = nullptr;
+    uint64_t* rowCdf = nullptr;
+    int rc;
+    if ((rc = devAlloc(c, fresh.allocs, &cdf, (size_t)W * H)) || (rc = devAlloc(c, fresh.allocs, &rowCdf, (size_t)H)) ||
+        (rc = devAlloc(c, fresh.allocs, &fresh.maxBits, (size_t)4)))
+      return rc;
+    HIPCHK(c, hipMemset(fresh.maxBits, 0, 16));
+    fresh.table = EnvTable{c->env.envMap, W, H, cdf, rowCdf};
+    fresh.bytes = (uint64_t)W * H * sizeof(uint32_t) + (uint64_t)H * sizeof(uint64_t) + 16;
+    E = std::move(fresh);
+  }
+  E.table.map = c->env.envMap;
+  if (int rc = orderAfterLast(c, st)) return rc;
+  E.ready = false;
+  launchEnvTable(E.table.map, W, H, const_cast<uint32_t*>(E.table.cdf), const_cast<uint64_t*>(E.table.rowCdf), E.maxBits, st);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) {
+    // a launch that failed midway may have left the maximum's word non-zero: the table goes, the next call builds afresh
+    fail(c, std::string("env_prepare: ") + hipGetErrorString(e));
+    (void)hipDeviceSynchronize();
+    dropEnv(E);
+    return BDPT_E_HIP;
+  }
+  c->lastStream = st;
+  E.ready = true;
+  return BDPT_OK;
+}
+
+int bdpt_get_env_info(bdpt_ctx* c, bdpt_env_info* out) {
+  if (!c || !out) return BDPT_E_INVALID;
+  if (!c->envTable.ready) return refuse(c, BDPT_E_STATE, "get_env_info", "no sampling table (bdpt_env_prepare first)");
+  ENTER(c);
+  HIPCHK(c, hipDeviceSynchronize());
+  const EnvState& E = c->envTable;
+  *out = bdpt_env_info{};
+  out->width = E.table.W;
+  out->height = E.table.H;
+  uint32_t bits = 0;
+  HIPCHK(c, hipMemcpy(&out->total, E.table.rowCdf + (E.table.H - 1), sizeof(uint64_t), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&bits, E.maxBits + 1, sizeof(bits), hipMemcpyDeviceToHost));
+  std::memcpy(&out->max, &bits, sizeof(bits));
+  out->rowScanChunk = kEnvRowScanChunk;
+  out->marginalChunk = kEnvMarginalChunk;
+  out->tableBytes = E.bytes;
+  out->cdf = E.table.cdf;
+  out->rowCdf = E.table.rowCdf;
   return BDPT_OK;
 }
 

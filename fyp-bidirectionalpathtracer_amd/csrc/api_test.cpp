@@ -212,4 +212,16 @@ int bdpt_test_bsdf(bdpt_ctx* c, const float* in, uint32_t n, uint32_t matIndex, 
   return BDPT_OK;
 }
 
+// Test hook: the sampling table of bdpt_env_prepare, read back
+int bdpt_test_env_table(bdpt_ctx* c, uint32_t* cdf, uint64_t* rowCdf) {
+  if (!c || !cdf || !rowCdf) return BDPT_E_INVALID;
+  if (!c->envTable.ready) return refuse(c, BDPT_E_STATE, "test_env_table", "no sampling table (bdpt_env_prepare first)");
+  ENTER(c);
+  HIPCHK(c, hipDeviceSynchronize());
+  const EnvTable& T = c->envTable.table;
+  HIPCHK(c, hipMemcpy(cdf, T.cdf, (size_t)T.W * T.H * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(rowCdf, T.rowCdf, (size_t)T.H * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return BDPT_OK;
+}
+
 }  // extern "C"

@@ -3,7 +3,8 @@
 //                dropping a scene drops its skin, dropping a skin drops its morph
 //   FrameState   what bdpt_resize / bdpt_resize_stripes replace
 //   LightGroups  sized by the scene's lights and by the frame: both drops drop them
-//   bdpt_ctx     the three, and what lives as long as the context (device, streams, events, cursors, staging, timing)
+//   EnvState     what bdpt_set_environment replaces: the sampling table bdpt_env_prepare made for the map
+//   bdpt_ctx     these, and what lives as long as the context (device, streams, events, cursors, staging, timing)
 // Every default is a member initialiser, so a drop is "free what the struct owns, then x = X{}" (api.cpp dropScene,
 // dropSkin, dropMorph, dropFrame, dropLightGroups: the only places that reset a field).  Internal to the library.
 #pragma once
@@ -15,6 +16,7 @@
 
 #include "../../include/bdpt.h"
 #include "bvh.h"
+#include "env_light.h"
 #include "kernels.h"
 #include "morph.h"
 #include "refit.h"
@@ -158,12 +160,23 @@ struct LightGroups {
   uint32_t planes = 0;
   uint8_t* lightIdx = nullptr;
 };
+
+// The sampling table of the environment map (bdpt_env_prepare): made for the map bdpt_set_environment bound, so that call
+// drops it (dropEnv), as bdpt_destroy does.  The map itself stays the caller's.
+struct EnvState {
+  DevPool allocs;
+  bool ready = false;
+  EnvTable table{};             // the snapshot of the map, and cdf / rowCdf (in `allocs`)
+  uint32_t* maxBits = nullptr;  // two words (in `allocs`): [0] the running maximum, zero between builds; [1] the bits of m
+  uint64_t bytes = 0;           // what `allocs` holds
+};
 }  // namespace bdpt
 
 struct bdpt_ctx {
   bdpt::SceneState scene;
   bdpt::FrameState frame;
   bdpt::LightGroups groups;
+  bdpt::EnvState envTable;
   // ---- from bdpt_create to bdpt_destroy ----
   int device = 0;
   int numCUs = 256;

@@ -731,6 +731,72 @@ void SimpleDiffuseGIPass::execute(RenderContext* pRenderContext) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// SkyLightingPass (include/bdpt.h "Environment lighting"; shaped like AmbientOcclusionPass above)
+// ------------------------------------------------------------------------------------------------
+bool SkyLightingPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
+  mpResManager = pResManager;
+  mpResManager->requestTextureResources({"WorldPosition", "WorldNormal", "MaterialDiffuse"});
+  mpResManager->requestTextureResource(mOutputBuf);
+  mpResManager->requestTextureResource(ResourceManager::kEnvironmentMap);
+  mpRays = RayLaunch::create(pRenderContext);
+  if (!mpRays) return false;
+  if (mpScene) mpRays->setScene(mpScene);
+  return true;
+}
+void SkyLightingPass::initScene(RenderContext*, Scene::SharedPtr pScene) {
+  mpScene = pScene;
+  if (mpRays) mpRays->setScene(mpScene);
+}
+void SkyLightingPass::renderGui(Gui* pGui) {
+  int dirty = 0;
+  dirty |= (int)pGui->addIntVar("Num Sky Rays", mNumRaysPerPixel, 1, (int)BDPT_SKY_MAX_SAMPLES);
+  dirty |= (int)pGui->addFloatVar("Sky clamp", mClampUpper, 0.0f, 3.402823466e+38f, 0.1f);
+  if (dirty) setRefreshFlag();
+}
+void SkyLightingPass::execute(RenderContext* pRenderContext) {
+  Texture::SharedPtr pDstTex = mpResManager->getClearedTexture(mOutputBuf, vec4{0.0f, 0.0f, 0.0f, 0.0f});
+  if (!pDstTex || !mpRays || !mpRays->readyToRender()) return;
+  Texture::SharedPtr pos = mpResManager->getTexture("WorldPosition"), nrm = mpResManager->getTexture("WorldNormal"),
+                     dif = mpResManager->getTexture("MaterialDiffuse"), env = mpResManager->getTexture(ResourceManager::kEnvironmentMap);
+  if (!pos || !nrm || !dif || !env || pos->getFormat() != ResourceFormat::RGBA32Float || nrm->getFormat() != ResourceFormat::RGBA16Float ||
+      dif->getFormat() != ResourceFormat::RGBA16Float || env->getFormat() != ResourceFormat::RGBA32Float ||
+      pDstTex->getFormat() != ResourceFormat::RGBA32Float) {
+    std::fprintf(stderr, "[SkyLightingPass] needs WorldPosition (RGBA32F), WorldNormal and MaterialDiffuse (RGBA16F) of a G-buffer pass, an "
+                         "RGBA32F environment map and an RGBA32F output\n");
+    return;
+  }
+  if (!mpRays->ensureSize(pDstTex->getWidth(), pDstTex->getHeight())) return;
+  hipStream_t stream = pRenderContext->getStream();
+  const float* map = (const float*)env->getDevicePointer();
+  if (map != mPreparedMap || env->getWidth() != mPreparedW || env->getHeight() != mPreparedH) {  // a new probe: bind it, make its table
+    bdpt_environment e{};
+    e.envMap = map;
+    e.width = env->getWidth();
+    e.height = env->getHeight();
+    if (bdpt_set_environment(mpRays->ctx(), &e) != BDPT_OK || bdpt_env_prepare(mpRays->ctx(), stream) != BDPT_OK) {
+      std::fprintf(stderr, "[SkyLightingPass] %s\n", mpRays->lastError());
+      return;
+    }
+    mPreparedMap = map;
+    mPreparedW = e.width;
+    mPreparedH = e.height;
+  }
+  bdpt_gbuffer gb;
+  std::memset(&gb, 0, sizeof(gb));
+  gb.worldPosition = (float*)pos->getDevicePointer();
+  gb.worldNormal = (uint16_t*)nrm->getDevicePointer();
+  gb.materialDiffuse = (uint16_t*)dif->getDevicePointer();
+  bdpt_sky_params p;
+  std::memset(&p, 0, sizeof(p));
+  p.frameCount = mFrameCount++;
+  p.clampUpper = mClampUpper;
+  p.minT = mpResManager->getMinTDist();
+  p.samples = (uint32_t)mNumRaysPerPixel;
+  if (bdpt_sky_execute(mpRays->ctx(), &p, &gb, (float*)pDstTex->getDevicePointer(), stream) != BDPT_OK)
+    std::fprintf(stderr, "[SkyLightingPass] %s\n", mpRays->lastError());
+}
+
+// ------------------------------------------------------------------------------------------------
 // LambertianPlusShadowPass (CommonPasses/LambertianPlusShadowPass.cpp:33-83)
 // ------------------------------------------------------------------------------------------------
 bool LambertianPlusShadowPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
@@ -1280,6 +1346,20 @@ bool SimpleDiffuseGIPass::loadState(RenderContext*, const uint8_t* data, size_t 
   if (size != 12) return false;
   if (get32(data + 4) != ((mDoIndirectGI ? 1u : 0u) | (mDoCosSampling ? 2u : 0u)) ||
       get32(data + 8) != floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f))
+    return false;
+  mFrameCount = get32(data);
+  return true;
+}
+void SkyLightingPass::saveState(RenderContext*, std::vector<uint8_t>& out) {
+  put32(out, mFrameCount);
+  put32(out, (uint32_t)mNumRaysPerPixel);
+  put32(out, floatBits(mClampUpper));
+  put32(out, floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f));
+}
+bool SkyLightingPass::loadState(RenderContext*, const uint8_t* data, size_t size) {
+  if (size != 16) return false;
+  if (get32(data + 4) != (uint32_t)mNumRaysPerPixel || get32(data + 8) != floatBits(mClampUpper) ||
+      get32(data + 12) != floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f))
     return false;
   mFrameCount = get32(data);
   return true;

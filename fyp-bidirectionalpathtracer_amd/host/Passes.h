@@ -232,6 +232,40 @@ class SimpleDiffuseGIPass : public RenderPass {
   uint32_t mFrameCount = 0x1337u;   // SimpleDiffuseGIPass.h:62
 };
 
+// Sky lighting: importance-sampled shadow rays toward the environment map (no pass of the reference: it is shaped like the
+// AO pass above).  WorldPosition, WorldNormal, MaterialDiffuse and the environment map in, the output channel out.  The
+// map's sampling table is prepared when the map bound to the pass's context changes.  Its kernel is bdpt_sky_execute.
+class SkyLightingPass : public RenderPass {
+ public:
+  using SharedPtr = std::shared_ptr<SkyLightingPass>;
+  static SharedPtr create(const std::string& outBuf = ResourceManager::kOutputChannel) { return SharedPtr(new SkyLightingPass(outBuf)); }
+  void setClamp(float hi) { mClampUpper = hi; }
+  // The table is a snapshot of the map's contents, made again when the map's address or size changes.  A host that
+  // rewrites the map in place calls this, and the next frame prepares the table anew.
+  void environmentChanged() { mPreparedMap = nullptr; }
+
+ protected:
+  SkyLightingPass(const std::string& outBuf) : RenderPass("Sky Lighting Rays", "Sky Lighting Options"), mOutputBuf(outBuf) {}
+  bool initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) override;
+  void initScene(RenderContext* pRenderContext, Scene::SharedPtr pScene) override;
+  void renderGui(Gui* pGui) override;
+  void execute(RenderContext* pRenderContext) override;
+  bool requiresScene() override { return true; }
+  bool usesRayTracing() override { return true; }
+  bool usesEnvironmentMap() override { return true; }
+  void saveState(RenderContext* pRenderContext, std::vector<uint8_t>& out) override;
+  bool loadState(RenderContext* pRenderContext, const uint8_t* data, size_t size) override;
+
+  RayLaunch::SharedPtr mpRays;
+  Scene::SharedPtr mpScene;
+  std::string mOutputBuf;
+  float mClampUpper = 3.402823466e+38f;  // no clamp
+  uint32_t mFrameCount = 0;
+  int32_t mNumRaysPerPixel = 1;
+  const float* mPreparedMap = nullptr;  // the map the context's table was made for, and its size
+  uint32_t mPreparedW = 0, mPreparedH = 0;
+};
+
 // Direct lighting from every light with one shadow ray each (CommonPasses/LambertianPlusShadowPass.{h,cpp}): WorldPosition,
 // WorldNormal, MaterialDiffuse and MaterialSpecRough in, the output channel out; no GUI state and no frame counter, as in the
 // reference (nothing is drawn).  Its ray generation shader with its shadow hit group is bdpt_direct_execute.

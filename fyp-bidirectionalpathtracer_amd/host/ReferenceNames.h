@@ -27,4 +27,5 @@ using bdpt::SampleConfig;
 using bdpt::Scene;
 using bdpt::SimpleDiffuseGIPass;
 using bdpt::SimpleAccumulationPass;
+using bdpt::SkyLightingPass;
 using bdpt::Texture;

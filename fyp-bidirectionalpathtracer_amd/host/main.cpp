@@ -2,7 +2,8 @@
 // (G-buffer pass -> BDPT pass -> accumulation pass -> BMFR denoiser, which is off unless --denoise /
 // --denoise-regression tick its boxes), run for a number of frames, output written as a PFM image.
 // `--ao N` runs the G-buffer pass and the ambient occlusion pass instead (CommonPasses/AmbientOcclusionPass.cpp) and
-// writes the AO channel; `--gi` runs the G-buffer pass, the one-bounce diffuse GI pass (CommonPasses/SimpleDiffuseGIPass.cpp)
+// writes the AO channel; `--sky N` (with `--env FILE`) runs the G-buffer pass, the sky lighting pass and the accumulation pass;
+// `--gi` runs the G-buffer pass, the one-bounce diffuse GI pass (CommonPasses/SimpleDiffuseGIPass.cpp)
 // and the accumulation pass, so that --frames N converges; `--direct` runs the G-buffer pass and the direct lighting pass
 // (CommonPasses/LambertianPlusShadowPass.cpp: every light, one shadow ray each, no draw) and writes its image.
 //
@@ -50,6 +51,9 @@ struct Options {
   int ao = -1;             // --ao N: render the G-buffer and the ambient occlusion pass (N rays per pixel) instead of the BDPT pipeline
   float aoRadius = 0.0f;   // --ao-radius R (with --ao, > 0); not given: the pass's default for the scene
   bool aoRadiusSet = false;
+  int sky = -1;               // --sky N: render the G-buffer, the sky lighting pass (N rays per pixel) and the accumulation pass; needs --env
+  float skyClamp = 0.0f;      // --sky-clamp C (with --sky, > 0): the bound of a sample's value; not given: none
+  bool skyClampSet = false;
   bool gi = false;            // --gi: render the G-buffer, the diffuse GI pass and the accumulation pass instead of the BDPT pipeline
   bool giDirectOnly = false;  // --gi-direct-only: untick "Shooting global illumination rays"
   bool giUniform = false;     // --gi-uniform: untick "Use cosine sampling"
@@ -124,13 +128,18 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   }
   // add the passes to the rendering pipeline, as Main.cpp:12-18 does
   pipeline->setPass(0, LightProbeGBufferPass::create());
-  const size_t numPasses = (o.ao >= 0 || o.direct) ? 2 : o.gi ? 3 : 4;
+  const size_t numPasses = (o.ao >= 0 || o.direct) ? 2 : (o.gi || o.sky >= 0) ? 3 : 4;
   if (o.direct) {  // --direct: the G-buffer and the direct lighting pass, which writes the output channel (nothing to accumulate: no draw)
     LambertianPlusShadowPass::SharedPtr lambert = LambertianPlusShadowPass::create();
     lambert->setUseHints(o.directHints);
     pipeline->setPass(1, lambert);
   } else if (o.ao >= 0) {  // --ao: the G-buffer and the ambient occlusion pass, which writes the output channel
     pipeline->setPass(1, AmbientOcclusionPass::create(ResourceManager::kOutputChannel));
+  } else if (o.sky >= 0) {  // --sky: the G-buffer, the sky lighting pass into the output channel, and the accumulation pass over it
+    SkyLightingPass::SharedPtr sky = SkyLightingPass::create(ResourceManager::kOutputChannel);
+    if (o.skyClampSet) sky->setClamp(o.skyClamp);
+    pipeline->setPass(1, sky);
+    pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
   } else if (o.gi) {  // --gi: the G-buffer, the diffuse GI pass into the output channel, and the accumulation pass over it
     pipeline->setPass(1, SimpleDiffuseGIPass::create(ResourceManager::kOutputChannel));
     pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
@@ -173,6 +182,7 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   if (o.denoiseRegression) gui.overrides["Skip Regression"] = 1;
   if (o.ao >= 0) gui.overrides["Num AO Rays"] = o.ao;
   if (o.ao >= 0 && o.aoRadiusSet) gui.overrides["AO radius"] = o.aoRadius;
+  if (o.sky >= 0) gui.overrides["Num Sky Rays"] = o.sky;
   if (o.gi && o.giDirectOnly) gui.overrides["Shooting global illumination rays"] = 0;  // the check boxes' labels while they are on
   if (o.gi && o.giUniform) gui.overrides["Use cosine sampling"] = 0;                   // (SimpleDiffuseGIPass.cpp:82-84)
   pipeline->applyGui(&gui);
@@ -332,6 +342,9 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
       std::printf("%s %ux%u diffuse GI (%s%s): %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
                   o.giDirectOnly ? "direct only" : "one bounce", o.giUniform ? ", uniform sampling" : ", cosine sampling", o.frames - warmup, res.ms,
                   res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
+    else if (o.sky >= 0)
+      std::printf("%s %ux%u sky lighting, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
+                  o.sky, o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
     else if (o.ao >= 0)
       std::printf("%s %ux%u ambient occlusion, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean ao %.6f", o.scene.c_str(), o.W, o.H,
                   o.ao, o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
@@ -390,6 +403,8 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--bend")) o.bend = (float)std::atof(v);
     else if (const char* v = next("--ao")) o.ao = std::max(0, std::atoi(v));
     else if (const char* v = next("--ao-radius")) o.aoRadius = (float)std::atof(v), o.aoRadiusSet = true;
+    else if (const char* v = next("--sky")) o.sky = std::max(0, std::atoi(v));
+    else if (const char* v = next("--sky-clamp")) o.skyClamp = (float)std::atof(v), o.skyClampSet = true;
     else if (std::strcmp(argv[i], "--gi") == 0) o.gi = true;
     else if (std::strcmp(argv[i], "--gi-direct-only") == 0) o.giDirectOnly = true;
     else if (std::strcmp(argv[i], "--gi-uniform") == 0) o.giUniform = true;
@@ -405,7 +420,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] [--direct [--direct-hints]] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] [--direct [--direct-hints]] [--sky N [--sky-clamp C]] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }
@@ -451,6 +466,25 @@ int main(int argc, char** argv) {
   }
   if (!o.direct && o.directHints) {
     std::fprintf(stderr, "bdpt_render: --direct-hints goes with --direct\n");
+    return 2;
+  }
+  if (o.sky >= 0 && (o.sky < 1 || o.sky > (int)BDPT_SKY_MAX_SAMPLES || o.gpus > 0 || o.world > 0 || (o.skyClampSet && !(o.skyClamp > 0.0f)))) {
+    std::fprintf(stderr, "bdpt_render: --sky N needs N in 1 .. %u rays per pixel, --sky-clamp C > 0 when given, and one GPU (no --gpus / --world)\n",
+                 BDPT_SKY_MAX_SAMPLES);
+    return 2;
+  }
+  if (o.sky >= 0 && (o.envFile.empty() || o.envFile == "Black")) {
+    std::fprintf(stderr, "bdpt_render: --sky N samples an environment map: it needs --env FILE\n");
+    return 2;
+  }
+  // --sky replaces the BDPT and denoise passes: the switches only they read are refused, not ignored
+  if (o.sky >= 0 && (o.ao >= 0 || o.gi || o.direct || o.denoise || o.areaLights || o.noMotion)) {
+    std::fprintf(stderr, "bdpt_render: --sky N renders the G-buffer, the sky lighting pass and the accumulation pass only: not with --ao N, --gi, "
+                         "--direct, --denoise, --denoise-regression, --area-lights or --no-motion\n");
+    return 2;
+  }
+  if (o.sky < 0 && o.skyClampSet) {
+    std::fprintf(stderr, "bdpt_render: --sky-clamp C goes with --sky N\n");
     return 2;
   }
   if (o.gpus < 0 || o.gpus > 64 || (o.gpus > 0 && o.world > 0)) {

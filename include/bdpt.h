@@ -398,7 +398,9 @@ int bdpt_set_scene(bdpt_ctx* ctx, const bdpt_scene_desc* scene);
 int bdpt_get_bvh_info(const bdpt_ctx* ctx, bdpt_bvh_info* out);
 int bdpt_set_camera(bdpt_ctx* ctx, const bdpt_camera* cam);
 /* ResourceManager's "EnvironmentMap" channel as the BDPT pass would bind it (BDPTPass.cpp:29 requests it; no shader of
- * the pass reads it in the reference).  NULL = none (black).  Only read with BDPT_PARAM_ENV_ON_MISS. */
+ * the pass reads it in the reference).  NULL = none (black).  Only read with BDPT_PARAM_ENV_ON_MISS, by bdpt_gi_query /
+ * bdpt_gi_execute, and by the calls of "Environment lighting", whose sampling table (bdpt_env_prepare) this call drops: it
+ * synchronises the device when there is one to drop. */
 int bdpt_set_environment(bdpt_ctx* ctx, const bdpt_environment* env);
 
 /* ---- Animated scenes: new vertex positions and lights between frames, without a rebuild ----
@@ -1389,6 +1391,194 @@ typedef struct bdpt_direct_params {
   uint32_t reserved[2]; /* 0 */
 } bdpt_direct_params;
 int bdpt_direct_execute(bdpt_ctx* ctx, const bdpt_direct_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
+
+/* ---- Environment lighting: a sampling table over the bound map, a sample / eval query, and a fused sky pass ----
+ * The map of bdpt_set_environment is otherwise seen only by rays that happen to leave the scene (the G-buffer's miss
+ * shader, BDPT_PARAM_ENV_ON_MISS, the diffuse GI kernel's IndirectMiss).  bdpt_env_prepare builds a discrete distribution
+ * over its texels, bdpt_env_query samples it (next-event estimation) and evaluates directions against it (MIS for a
+ * caller's BSDF-sampled miss), bdpt_sky_query / bdpt_sky_execute are the fused loop sample -> any-hit ray -> ordered add.
+ * bdpt_execute does not change: environment NEE inside the BDPT frame is not part of this.  All arithmetic below is
+ * csrc/env_light.h, one text compiled for the host (bdpt_host_env_*) and for the device, fp32 / fp64 as written, without
+ * contraction; the table is exact in integers, so nothing depends on summation order.
+ *
+ * Table, for the W x H RGBA32F map, 1 <= W, H <= BDPT_ENV_MAX_DIM (beyond: BDPT_E_LIMIT):
+ *   clean(c)  = c > 0 ? min(c, FLT_MAX) : 0                       NaN and negative channels count as 0
+ *   lum(x, y) = (clean(r) * 0.2126f + clean(g) * 0.7152f) + clean(b) * 0.0722f (`luminance`); when a channel is positive
+ *               and the sum rounds to 0 (subnormal channels), lum is the smallest subnormal: any positive channel gives lum > 0
+ *   sinRow(y) = the sine of det_sincos2pi(((y + 0.5f) / H) * 0.5f), positive for every row
+ *   f(x, y)   = min(lum * sinRow, FLT_MAX), and the smallest subnormal when lum > 0 and the product rounds to 0
+ *   m         = max f over the map (order-free; on the device an unsigned atomicMax on the float's bits)
+ *   q(x, y)   = f > 0 ? 1 + (uint32_t)(((double)f / (double)m) * 65535.0) : 0, in [0, 65536]: no lit texel is unreachable
+ *   cdf[y][x] = inclusive prefix sum of q along row y (uint32; a row total is at most 2^30)
+ *   rowCdf[y] = inclusive prefix sum of the row totals (uint64); total = rowCdf[H - 1] <= 2^44
+ * Sample, envSample(state): exactly four draws r1 .. r4 of nextRand, in that order, whatever happens.
+ *   total == 0: every output is zero.  Otherwise
+ *   t  = min((uint64_t)((double)r1 * (double)total), total - 1);        y = the first row with rowCdf[y] > t
+ *   t2 = min((uint32_t)((double)r2 * (double)rowTotal), rowTotal - 1);  x = the first column with cdf[y][x] > t2
+ *   u = ((float)x + r3) / W, v = ((float)y + r4) / H; (s, c) = det_sincos2pi(u), (st, ct) = det_sincos2pi(v * 0.5f)
+ *   dir = (-st * s, ct, st * c) — the inverse of envLookup's u = (1 + atan2_WAR(x, -z) / pi) / 2, v = acos(y) / pi
+ *   radiance = the texel's rgb as stored; texel = y * W + x
+ *   pdf = the solid-angle density (q / total) * (W * H) / (2 pi^2 st), evaluated as
+ *         p = (float)((double)q / (double)total); pdf = ((p * (float)W) * (float)H) / ((2.0f * (kPi * kPi)) * st),
+ *         and 0 when st <= 0.  Accuracy: within 1e-4 relative of the float64 reading of the formula wherever sin(pi v) is above
+ *         2^-8; nearer a pole fp32 cannot hold it: v, a number up to 1 with two roundings behind it, is off by up to 1.2e-7,
+ *         its sine by pi times that, which is more than 1e-4 of a sine below 3.7e-3.  The sin-weighted table puts under 1 %
+ *         of any map's samples there (tests/test_env_cpu.py asserts the share).
+ *   Build definition: a draw has 24 bits, so it picks among at most 2^24 targets: a row or a texel whose probability is
+ *   below 2^-24 may never be drawn, although its pdf is positive.
+ * Eval, envEval(dir): the texel and radiance are exactly envLookup's — the same normalize, atan2_WAR, det_acos and
+ *   truncation (the device's conversion: NaN and negatives 0), zero outside the map; pdf is the formula above with
+ *   st = sqrtf(max(0, 1 - pd.y * pd.y)), pd the normalised direction, evaluated as sqrtf(pd.x * pd.x + pd.z * pd.z): the
+ *   same quantity without the cancellation, which below st = 0.03 would cost more than the 1e-4 by which the two pdfs may
+ *   differ (a unit vector's y alone holds the polar angle only to sqrt(1e-7) near the poles).  Outside the map: radiance 0, pdf 0, texel 0xFFFFFFFF
+ *   (u reaches 1 for directions with x = +0, z > 0).  A NaN or zero direction (its normalisation is NaN) looks up
+ *   texel (W / 2, 0), as envLookup does: every comparison of atan2_WAR fails, so u = 0.5, and the NaN v converts to row 0;
+ *   its pdf is 0.
+ *
+ * bdpt_env_prepare snapshots the map bound by bdpt_set_environment (the map stays caller memory and is read by every later
+ * query; the table is the context's).  It needs a map: a constant colour or no environment gives BDPT_E_STATE.  It allocates
+ * on first use and when the size changes, so that call must not be inside a stream capture (BDPT_E_STATE there), as the
+ * emitter table's first build; a repeat call with the same size allocates nothing, does not synchronise and can be captured
+ * (three kernel nodes): the re-prepare after an animated probe.  bdpt_set_environment and bdpt_destroy
+ * drop the table: the calls below then return BDPT_E_STATE until bdpt_env_prepare ran again.  bdpt_get_env_info
+ * synchronises (it reads total and m back).
+ *
+ * bdpt_env_query, per item i < min(*numDevice, num):
+ *   BDPT_ENV_SAMPLE  in: surfaces[i], seeds[i]; out: samples[i] (five float4), seedsOut[i] (optional, may be `seeds`): the
+ *     state after the four draws.  ray = (posW, minT, dir, 1e38); radiance, pdf, texel as above;
+ *     value = the unweighted contribution of a visible environment, +0 when pdf == 0: with matIndex 1
+ *       (((NdotL * radiance) * diffuse) / kPi) / pdf, NdotL = saturate(dot(N, dir)); with matIndex 0 the pass's GGX term
+ *       directIfVisible(lightsCount 1, L = dir, intensity = radiance) / pdf — (D G F / (4 NdotV) + NdotL diffuse / kPi) times
+ *       radiance, the device function next-event estimation runs.  Throughput, weight and clamp stay with the caller.
+ *     status = BDPT_ENV_STATUS_NONZERO when value has a component that is not +-0.  A record with prim < 0 gives an
+ *     all-zero sample and still takes its four draws.  With compactRays / compactItems / compactCount (all three, as
+ *     bdpt_light_query) the rays of the NONZERO items go to a dense list for bdpt_trace_rays(BDPT_TRACE_ANY).
+ *   BDPT_ENV_EVAL    in: dirs[i] (float4, xyz read); out: evals[i] (two float4): radiance, pdf, texel.
+ * Record contract: posW, N, V, linearRoughness, diffuse, specular and prim (its sign) are read; floats may be degenerate or
+ * not finite, the outputs are those of the fp32 arithmetic as written.  Nothing a caller supplies reaches an address: a
+ * texel index comes only from the table search, bounded by W and H whatever the table holds, or from envLookup's
+ * bounds-checked truncation.
+ *
+ * bdpt_sky_query: item i alive iff surfaces[i].prim >= 0 and (alive == NULL or alive[i] != 0).  For an alive item
+ *   s = seeds[i]; sum = 0; count = 0
+ *   for k = 0 .. samples-1 (1 .. BDPT_SKY_MAX_SAMPLES):
+ *     (ray, radiance, pdf) = envSample(s)                                           four draws
+ *     value = clampVec((((NdotL * radiance) * diffuse) / kPi) / pdf, clampUpper), +0 when pdf == 0
+ *     term  = value when every component is +-0 (no ray is traced); else +0 when the ray is occluded as BDPT_TRACE_ANY
+ *             answers it; else value, and count += 1
+ *     sum += term                                                                   in k order
+ *   color[i] = (sum / (float)samples, 1); counts[i] = count; seedsOut[i] = s
+ * A dead item gets color = (diffuse.rgb, 1) — the G-buffer's environment colour on a miss, as bdpt_gi_query — counts 0 and
+ * its seed unchanged: no draw.  This equals the composed loop bdpt_env_query(SAMPLE, matIndex 1) -> clamp ->
+ * bdpt_trace_rays(ANY) on the non-zero terms -> ordered add, bit for bit.  Only posW, N, diffuse and prim are read.
+ * bdpt_sky_execute runs the same for the context's tile pixels with the seed initRand(x + y * width, frameCount, 16), the
+ * full-frame worldPosition, worldNormal and materialDiffuse channels, alive iff worldPosition.w != 0 — bdpt_gi_execute's
+ * rules, so tiles reproduce the whole frame.  It needs a scene, a size and a prepared table, no camera.
+ *
+ * Ordering, capture, counters and numDevice: as bdpt_light_query and bdpt_ao_query (one kernel node per query).
+ * Errors (nothing is enqueued), in this order: a NULL context, desc / params or gbuffer BDPT_E_INVALID; no scene
+ * (bdpt_sky_*), no size (bdpt_sky_execute), no prepared table — none yet, or dropped by bdpt_set_environment — BDPT_E_STATE;
+ * unknown mode or flags, matIndex > 1, samples outside 1 .. BDPT_SKY_MAX_SAMPLES, non-zero reserved, a partial compaction
+ * triple, compaction with BDPT_ENV_EVAL BDPT_E_INVALID; then num == 0 returns BDPT_OK; then a missing or misaligned buffer
+ * BDPT_E_INVALID: records and `out` 16 bytes, the half channels 8, words 4. */
+#define BDPT_ENV_MAX_DIM 16384u
+#define BDPT_ENV_SAMPLE 0u
+#define BDPT_ENV_EVAL 1u
+#define BDPT_ENV_STATUS_NONZERO 1u
+#define BDPT_SKY_MAX_SAMPLES 64u
+typedef struct bdpt_env_info {
+  uint32_t width, height;
+  uint64_t total;           /* rowCdf[H - 1] */
+  float max;                /* m */
+  uint32_t rowScanChunk;    /* texels per pass of the row scan */
+  uint32_t marginalChunk;   /* rows per pass of the marginal scan */
+  uint32_t reserved;
+  uint64_t tableBytes;      /* device bytes the table holds */
+  const uint32_t* cdf;      /* device addresses of the table (stable across a re-prepare of the same size) */
+  const uint64_t* rowCdf;
+} bdpt_env_info; /* 56 bytes */
+int bdpt_env_prepare(bdpt_ctx* ctx, void* stream);
+int bdpt_get_env_info(bdpt_ctx* ctx, bdpt_env_info* out); /* synchronises */
+typedef struct bdpt_env_sample {
+  bdpt_ray ray;       /* org = posW, tmin = minT, dir, tmax = 1e38 */
+  float radiance[3];  /* the chosen texel's rgb */
+  float pdf;          /* solid angle */
+  float value[3];
+  uint32_t texel;     /* y * W + x */
+  uint32_t status;    /* BDPT_ENV_STATUS_NONZERO or 0 */
+  uint32_t reserved[3];
+} bdpt_env_sample; /* 80 bytes: five float4 */
+typedef struct bdpt_env_eval {
+  float radiance[3];
+  float pdf;
+  uint32_t texel;     /* 0xFFFFFFFF: outside the map */
+  uint32_t reserved[3];
+} bdpt_env_eval; /* 32 bytes: two float4 */
+typedef struct bdpt_env_desc {
+  uint32_t mode;                /* BDPT_ENV_SAMPLE or BDPT_ENV_EVAL */
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  uint32_t matIndex;            /* SAMPLE: 0 GGX, 1 Lambertian */
+  uint32_t flags;               /* 0 */
+  float minT;                   /* SAMPLE: tmin of the rays */
+  uint32_t reserved;            /* 0 */
+  const bdpt_surface* surfaces; /* SAMPLE: device, 16-byte aligned, num records */
+  const uint32_t* seeds;        /* SAMPLE: device, num RNG states */
+  uint32_t* seedsOut;           /* SAMPLE, optional: device, num RNG states (may be `seeds`) */
+  bdpt_env_sample* samples;     /* SAMPLE: device, 16-byte aligned, num records */
+  const float* dirs;            /* EVAL: device, 16-byte aligned, num float4 (xyz read) */
+  bdpt_env_eval* evals;         /* EVAL: device, 16-byte aligned, num records */
+  bdpt_ray* compactRays;        /* SAMPLE, optional, all three or none: as bdpt_light_desc */
+  uint32_t* compactItems;
+  uint32_t* compactCount;
+} bdpt_env_desc;
+int bdpt_env_query(bdpt_ctx* ctx, const bdpt_env_desc* desc, void* stream);
+typedef struct bdpt_sky_desc {
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  uint32_t samples;             /* 1 .. BDPT_SKY_MAX_SAMPLES */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  float clampUpper;             /* upper bound of every component of a sample's value (clampVec) */
+  float minT;                   /* tmin of the rays */
+  uint32_t flags;               /* 0 */
+  uint32_t reserved;            /* 0 */
+  const bdpt_surface* surfaces; /* device, 16-byte aligned, num records: posW, N, diffuse and prim are read */
+  const uint32_t* seeds;        /* device, num RNG states */
+  const uint8_t* alive;         /* optional: device, one byte per item, 0 = the item is dead */
+  float* color;                 /* device, 16-byte aligned, num float4 */
+  uint32_t* counts;             /* optional: device, num words: the samples traced and found unoccluded */
+  uint32_t* seedsOut;           /* optional: device, num RNG states (may be `seeds`) */
+} bdpt_sky_desc;
+int bdpt_sky_query(bdpt_ctx* ctx, const bdpt_sky_desc* desc, void* stream);
+typedef struct bdpt_sky_params {
+  uint32_t frameCount;
+  float clampUpper;
+  float minT;
+  uint32_t samples;  /* 1 .. BDPT_SKY_MAX_SAMPLES */
+  uint32_t reserved; /* 0 */
+} bdpt_sky_params;
+int bdpt_sky_execute(bdpt_ctx* ctx, const bdpt_sky_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
+/* Host twins (no GPU, no context): csrc/env_light.h on the CPU.  bdpt_host_env_table fills q (optional), cdf (W * H words),
+ * rowCdf (H words) and *outMax (optional) for a host map; BDPT_E_LIMIT past BDPT_ENV_MAX_DIM.  bdpt_host_env_sample runs
+ * envSample for n states (seedsOut optional, may be `seeds`); bdpt_host_env_eval runs envEval for n float4 directions. */
+typedef struct bdpt_env_host_sample {
+  float dir[3];
+  float pdf;
+  float radiance[3];
+  uint32_t texel;
+} bdpt_env_host_sample; /* 32 bytes */
+int bdpt_host_env_table(const float* map, uint32_t width, uint32_t height, uint32_t* q, uint32_t* cdf, uint64_t* rowCdf, float* outMax);
+int bdpt_host_env_sample(const float* map, uint32_t width, uint32_t height, const uint32_t* cdf, const uint64_t* rowCdf,
+                         const uint32_t* seeds, uint32_t n, bdpt_env_host_sample* out, uint32_t* seedsOut);
+int bdpt_host_env_eval(const float* map, uint32_t width, uint32_t height, const uint32_t* cdf, const uint64_t* rowCdf, const float* dirs,
+                       uint32_t n, bdpt_env_eval* out);
+/* Test hook: the context's table read back to host memory (cdf: W * H words, rowCdf: H words); synchronises. */
+int bdpt_test_env_table(bdpt_ctx* ctx, uint32_t* cdf, uint64_t* rowCdf);
+/* Host-only test hook: the table search of envSample (csrc/env_light.h envSearch) for n pairs of draws given directly, so
+ * that a test can aim at every boundary of both tables (through seeds the second draw is a function of the first):
+ * texels[i] = y * W + x for draws r1[i], r2[i] in [0, 1) (any other value, a NaN included: BDPT_E_INVALID, nothing is
+ * written).  BDPT_E_STATE when the tables' total is 0. */
+int bdpt_test_host_env_search(uint32_t width, uint32_t height, const uint32_t* cdf, const uint64_t* rowCdf, const float* r1, const float* r2,
+                              uint32_t n, uint32_t* texels);
 
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
