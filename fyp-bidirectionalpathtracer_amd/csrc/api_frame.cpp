@@ -319,6 +319,11 @@ int frameSetup(bdpt_ctx* c, const bdpt_params* p, const bdpt_gbuffer* in, float*
   if (!c->scene.have || !c->haveCamera || !c->frame.have) return refuse(c, BDPT_E_STATE, "execute", "scene, camera and size must be set first");
   if (p->maxDepth > c->frame.maxDepth) return refuse(c, BDPT_E_LIMIT, "execute", "params.maxDepth exceeds the depth given to bdpt_resize");
   if (p->matIndex > 1) return refuse(c, BDPT_E_INVALID, "execute", "matIndex must be 0 (GGX) or 1 (Lambertian)");
+  // clampVec(x, hi) returns hi itself for a NaN or negative hi, and a light-tracing term c in [0, hi] lands as
+  // (uint64_t)(c * 2^32) (toFixed, device_math.hpp), a conversion that is defined only below 2^64 (include/bdpt.h, bdpt_params)
+  if (!(p->clampUpper >= 0.0f)) return refuse(c, BDPT_E_INVALID, "execute", "clampUpper must be a number >= 0");
+  if (!(p->flags & BDPT_PARAM_NO_SPLAT) && p->clampUpper > BDPT_MAX_CLAMP_UPPER_SPLAT)
+    return refuse(c, BDPT_E_LIMIT, "execute", "clampUpper exceeds BDPT_MAX_CLAMP_UPPER_SPLAT in a frame with light-tracing splats");
   if (!in->worldPosition || !in->worldNormal || !in->materialDiffuse || !in->materialSpecRough || !in->emissive) {
     fail(c, "execute: G-buffer channels missing");
     return BDPT_E_INVALID;

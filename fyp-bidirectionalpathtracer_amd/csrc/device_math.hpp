@@ -362,6 +362,8 @@ BD f3 directIfVisible(float lightsCount, f3 L, f3 lightIntensity, f3 N, f3 V, f3
 
 BD f3 clampVec(f3 v, float hi) { return mk(clampUp(v.x, hi), clampUp(v.y, hi), clampUp(v.z, hi)); }  // MaterialUtils.hlsli:15-18
 
+// c in [0, BDPT_MAX_CLAMP_UPPER_SPLAT]: the frame entry points refuse a clampUpper outside it (include/bdpt.h, bdpt_params), since
+// the conversion of a NaN, a negative number or 2^64 and more is undefined in C++ and differs between host and device
 BD uint64_t toFixed(float c) { return (uint64_t)(c * 4294967296.0f); }
 
 #undef BD

@@ -210,10 +210,22 @@ typedef struct bdpt_params {
   float refractiveIndex; /* gRefractiveIndex — read by no shader, kept for layout */
   uint32_t maxDepth;     /* gMaxDepth */
   float emitMult;        /* gEmitMult — read by no shader */
-  float clampUpper;      /* gClampUpper, default 0.9 */
+  float clampUpper;      /* gClampUpper, default 0.9; a number >= 0, see BDPT_MAX_CLAMP_UPPER_SPLAT */
   float pixelJitter[2];  /* gPixelJitter = kMSAA[(frame+1)%8]/16 + 0.5 */
   uint32_t flags;        /* BDPT_PARAM_* */
 } bdpt_params;
+
+/* clampUpper.  The reference clamps every term to [0, gClampUpper] (clampVec, MaterialUtils.hlsli:15-18) and its UI keeps the
+ * bound in [0.001, 1] (BDPTPass.cpp:64).  Here light-tracing terms are summed in 2^-32 fixed point (quirk 6): a term c lands as (uint64_t)(c * 2^32),
+ * which is defined for 0 <= c < 2^32 only (beyond it the host conversion and the device's differ, and neither saturates).
+ * So every frame entry point (bdpt_execute, _tail, _masked, _light_groups, _grouped) refuses
+ *   - a clampUpper that is NaN or negative: BDPT_E_INVALID (clampVec would return the bound itself for every term);
+ *   - a clampUpper above BDPT_MAX_CLAMP_UPPER_SPLAT = 2^32 - 256, the largest float below 2^32, unless the frame has no
+ *     light-tracing stage (BDPT_PARAM_NO_SPLAT): BDPT_E_LIMIT.  NEE and connection terms are float sums and take any bound,
+ *     +inf included.
+ * Within the limit the accumulators are exact sums modulo 2^64 in any order; they stay below 2^64, and so mean what they
+ * say, while (splats landing on one pixel) * clampUpper < 2^32. */
+#define BDPT_MAX_CLAMP_UPPER_SPLAT 4294967040.0f
 
 #define BDPT_PARAM_COUNTERS 1u      /* also tally node / triangle visits (slower; not for timing).  Ray tallies are always on. */
 #define BDPT_PARAM_DEFER_RESOLVE 2u /* leave splats in the splat buffer; caller runs bdpt_resolve */
@@ -1063,7 +1075,8 @@ int bdpt_connect_query(bdpt_ctx* ctx, const bdpt_connect_desc* desc, void* strea
  * uses item k = items ? items[j] : j: it reads pixels[k], values[k] (xyz: the clamped term) and visible[j], so CAMERA mode's
  * compact lists and bdpt_trace_rays' `visible` bytes go in as they are.  An entry lands when visible is NULL or
  * visible[j] != 0 and pixels[k] < numPixels.  A landed entry adds (uint64_t)(c * 2^32) to word 0 / 1 / 2 of
- * splat[pixels[k]] for each channel c > 0 (a NaN or non-positive channel adds nothing) and 1 to word 3, with 64-bit atomic
+ * splat[pixels[k]] for each channel c > 0 (a NaN or non-positive channel adds nothing; a channel above
+ * BDPT_MAX_CLAMP_UPPER_SPLAT is the caller's error: its conversion is undefined) and 1 to word 3, with 64-bit atomic
  * adds: integer sums, so the result is exact and does not depend on the order.  `splat` is a device buffer of uint64[4]
  * per pixel in frame order: the context's own (bdpt_splat_buffer of a whole-frame context) or the caller's, which
  * bdpt_resolve(ctx, splat, 0, out) folds in as it does the pass's.  Owner-major (stripes) layouts are not supported.

@@ -958,6 +958,7 @@ bool shadowRayVisibility(const Globals& g, Tally& tl, int stage, f3 origin, f3 d
   Ray r{origin, direction, minT, maxT};
   tl.rays[stage]++;
   Hit h = traceRay(*g.s, r, 2, g.flags, &tl.nodeS, &tl.triS);
+  if ((g.flags & ORACLE_TERMS_ALL_VISIBLE) && (stage == 3 || stage == 4)) return true;  // cross-check hook, see bdpt_oracle.h
   return h.prim < 0;
 }
 
@@ -1205,7 +1206,7 @@ inline void splatTerm(const Globals& g, const PathVertex& lv, f3 cameraN, f3 dir
   fr = evalBRDF(g, lv.V, dirToCamera, lv.N, lv.N, lv.dif, lv.spec, lv.rough, lv.isSpecular);
 }
 
-inline uint64_t toFixed(float c) {  // c in [0, clampUpper<=1]; 2^-32 units
+inline uint64_t toFixed(float c) {  // c in [0, clampUpper <= BDPT_MAX_CLAMP_UPPER_SPLAT] (oracle_bdpt refuses others); 2^-32 units
   return (uint64_t)(c * 4294967296.0f);
 }
 
@@ -1661,6 +1662,8 @@ int oracle_bdpt(const oracle_scene* s, const bdpt_camera* cam, const bdpt_params
                 bdpt_counters* counters) {
   if (!s || !cam || !p || !f) return -1;
   if (s->lights.empty() || p->maxDepth > BDPT_MAX_DEPTH) return -2;
+  if (!(p->clampUpper >= 0.0f)) return BDPT_E_INVALID;  // as bdpt_execute: toFixed below is defined for [0, 2^32) only
+  if (!(p->flags & BDPT_PARAM_NO_SPLAT) && p->clampUpper > BDPT_MAX_CLAMP_UPPER_SPLAT) return BDPT_E_LIMIT;
   Globals g;
   g.s = s;
   g.cam = *cam;

@@ -47,6 +47,9 @@ void oracle_set_environment(oracle_scene* s, const bdpt_environment* env);
  * the far surface itself occludes them is decided by the last bit of the arithmetic; with this flag the
  * connection sums can be compared with an implementation in another precision. */
 #define ORACLE_CONNECT_ALL_VISIBLE 2u
+/* The same hook for the next-event and light-tracing shadow rays (tests/test_edge_scenes_cpu.py): a light that lies ON a
+ * surface, or a camera on one, ends every such ray on that surface, the same last-bit decision. */
+#define ORACLE_TERMS_ALL_VISIBLE 4u
 
 typedef struct oracle_frame {
   uint32_t width, height;

@@ -14,6 +14,13 @@ pixel at a time, brute-force ray/triangle tests, constant-colour materials only 
 What the shader leaves to the driver is defined as the oracle defines it: a hit needs
 tmin < t < tmax, the closest hit wins with ties to the lowest primitive; cross-pixel splats are returned as a
 list instead of racing on gOutput, and out-of-frame splat targets are dropped.
+
+For the edge-case scenes (tests/test_edge_scenes_cpu.py): the path arrays hold maxDepth + 2 vertices where the shader's hold
+9 (the build's depths beyond 8, include/bdpt.h BDPT_MAX_DEPTH); BDPT_PARAM_ENV_ON_MISS under a constant environment is read
+from include/bdpt.h (a build definition: the shader's miss returns black); Renderer.risky collects, per pixel, the decisions
+whose quantity lies within a margin of a discontinuity (the light pick, the rintf tie of a splat target, a shadow ray whose
+answer changes when tmin and tmax move by T_MARGIN, the lobe choice); Renderer.nan_terms counts the terms that are NaN before
+clampVec; Semantics switches single rules of the reading off, for the positive controls.
 """
 import math
 
@@ -23,6 +30,23 @@ import hlsl_reference_math as hm
 
 M_PI = hm.M_PI
 M_1_PI = hm.M_1_PI
+MARGIN = 1e-6    # light pick, rintf tie, lobe choice
+T_MARGIN = 1e-4  # relative change of a shadow ray's tmin and tmax that must not change its answer
+
+
+class Semantics:
+    """The rules of BDPTMain.rt.hlsl:160-233 a positive control can switch off:
+      saturate_per_write   every connection write saturates gOutput (:230)
+      d3d_clamp            clampVec's clamp is min(max(x, 0), hi) with D3D's NaN rule (the other operand wins), so a NaN channel
+                           becomes +0 and colorsNan (:165, :197, :228) never fires; False: an IEEE clamp that keeps NaN in the
+                           light-tracing stage, after which colorsNan zeroes all three channels
+      zero_pairs_write     a visible connection whose contribution is all zero still writes (+0, +0, +0, 1) (:230)"""
+
+    def __init__(self, saturate_per_write=True, d3d_clamp=True, zero_pairs_write=True):
+        self.saturate_per_write, self.d3d_clamp, self.zero_pairs_write = saturate_per_write, d3d_clamp, zero_pairs_write
+
+
+D3D = Semantics()
 
 
 def norm(v):
@@ -103,7 +127,12 @@ class Vertex:
 
 
 class Renderer:
-    def __init__(self, scene, cam, params, width, height, specular_from_lobe=False, mis=None, area=None):
+    def __init__(self, scene, cam, params, width, height, specular_from_lobe=False, mis=None, area=None, env_color=None, sem=D3D,
+                 margins=False):
+        self.margins = margins  # probe every shadow ray's answer at tmin, tmax -+ T_MARGIN too (two more scans per ray)
+        self.env_color = None if env_color is None else np.array(env_color[:3], np.float64)  # BDPT_PARAM_ENV_ON_MISS, constant
+        self.sem = sem
+        self.risky, self.nan_terms, self.terms_all_visible = [], 0, False
         self.mis = mis  # None: the uniform 1/k the shader applies; "power" / "linear": getWeightPower / getWeightLinear
         # area: an area_light_numpy.AreaTable — with a positive W it is light numLights of numLights + 1 (BDPT_PARAM_AREA_LIGHTS,
         # include/bdpt.h "Area lights")
@@ -122,20 +151,32 @@ class Renderer:
     def visible(self, o, d, tmin, tmax):
         if not (np.isfinite(o).all() and np.isfinite(d).all() and tmax > tmin):
             return True  # no triangle can satisfy tmin < t < tmax: the miss shader runs
-        return self.s.intersect(o, d, tmin, tmax) is None
+        ans = self.s.intersect(o, d, tmin, tmax) is None
+        if not self.margins:
+            return ans
+        wide = self.s.intersect(o, d, tmin * (1.0 - T_MARGIN), tmax * (1.0 + T_MARGIN)) is None
+        narrow = self.s.intersect(o, d, tmin * (1.0 + T_MARGIN), tmax * (1.0 - T_MARGIN)) is None
+        if wide != ans or narrow != ans:
+            self.risky.append("t")
+        return ans
 
     def shoot(self, pl):
         """shootRay + closest-hit / miss shader on the payload dict."""
         hit = None
         if np.isfinite(pl["o"]).all() and np.isfinite(pl["d"]).all():
             hit = self.s.intersect(pl["o"], pl["d"], float(self.p.minT), 1.0e38)
+        pl["extra"] = None
         if hit is None:
+            if self.env_color is not None:
+                pl["extra"] = self.env_color
             pl["color"] = np.zeros(3)
             pl["terminated"] = True
             return
         prim, t, u, v = hit
         pos, n, vv, dif, spec, rough = self.s.shading(prim, u, v, pl["o"], pl["d"], t)
-        w, l, pdf, lobe, _ = hm.sample_brdf(self.mat, pl["seed"], n, vv, dif, spec, rough)  # seed passed BY VALUE
+        w, l, pdf, lobe, margin = hm.sample_brdf(self.mat, pl["seed"], n, vv, dif, spec, rough)  # seed passed BY VALUE
+        if margin < MARGIN:
+            self.risky.append("lobe")
         pl["color"] = pl["color"] * w
         pl.update(o=pos, d=l, pos=pos, N=n, V=vv, dif=dif, spec=spec, rough=rough, pdf=pdf,
                   is_spec=(lobe and self.from_lobe) if self.mat == 0 else False)
@@ -144,7 +185,7 @@ class Renderer:
     def payload(o, d, color, seed):
         z = np.zeros(3)
         return dict(o=o, d=d, seed=seed, color=color, pos=o, N=z, V=z, dif=z, spec=z, rough=0.0, is_spec=False, pdf=0.0,
-                    terminated=False)
+                    terminated=False, extra=None)
 
     @staticmethod
     def vertex_of(pl):
@@ -175,9 +216,15 @@ class Renderer:
             to_light = L / np.linalg.norm(L)
         return to_light, diffuse, float(np.linalg.norm(ls_pos - hit))
 
+    def pick(self, r):
+        x = r * self.nl
+        if self.nl > 1 and abs(x - round(x)) < MARGIN and 0 < round(x) < self.nl:
+            self.risky.append("light")
+        return min(int(x), self.nl - 1)
+
     def eval_direct(self, seed, v):
         seed, r = hm.next_rand(seed)
-        index = min(int(r * self.nl), self.nl - 1)
+        index = self.pick(r)
         if index == self.n_point:  # the emitter table: its own stream, a shadow ray that stops short of the emitter
             _, L, d, inten = self.area.nee(seed, v.pos)
             dist = d * (1.0 - 1e-4)
@@ -185,7 +232,7 @@ class Renderer:
             L, inten, dist = self.light_data(index, v.pos)
         with np.errstate(invalid="ignore"):
             ndotl = hm.saturate(float(np.dot(v.N, L)))
-        vis = self.visible(v.pos, L, float(self.p.minT), dist)
+        vis = self.terms_all_visible or self.visible(v.pos, L, float(self.p.minT), dist)
         shadow = float(self.nl) if vis else 0.0
         if self.mat == 1:
             return seed, shadow * ndotl * inten * v.dif / M_PI
@@ -201,7 +248,7 @@ class Renderer:
 
     def sample_light(self, seed):
         seed, r = hm.next_rand(seed)
-        index = min(int(r * self.nl), self.nl - 1)
+        index = self.pick(r)
         if index == self.n_point:  # a point on an emitter, its side, a cosine direction about that side
             x, _, d, color, seed = self.area.light_start(seed)
             return seed, x["pos"], d, color
@@ -221,9 +268,13 @@ class Renderer:
         return seed, origin, d, inten
 
     # ---- helpers of the contribution loops
-    def clamp_vec(self, c):
+    def clamp_vec(self, c, d3d=True):
         # HLSL clamp = min(max(x, lo), hi) with the "other operand wins over NaN" rule: clamp(NaN) = lo
-        return np.fmin(np.fmax(c, 0.0), float(self.p.clampUpper))
+        self.nan_terms += int(np.isnan(c).any())
+        with np.errstate(invalid="ignore"):
+            if not d3d:
+                return np.minimum(np.maximum(c, 0.0), float(self.p.clampUpper))
+            return np.fmin(np.fmax(c, 0.0), float(self.p.clampUpper))
 
     def pixel_of(self, d):
         d1 = np.dot(d, self.U) / np.dot(self.U, self.U)
@@ -234,6 +285,8 @@ class Renderer:
         fx, fy = cx * self.W - self.p.pixelJitter[0], cy * self.H - self.p.pixelJitter[1]
         # HLSL round() = round half to even; uint() of a negative value is out of range -> dropped here
         ix, iy = np.rint(fx), np.rint(fy)
+        if abs(abs(fx - ix) - 0.5) < MARGIN or abs(abs(fy - iy) - 0.5) < MARGIN:
+            self.risky.append("rint")
         if not (np.isfinite(ix) and np.isfinite(iy)) or ix < 0 or iy < 0 or ix >= self.W or iy >= self.H:
             return None
         return int(ix), int(iy)
@@ -288,9 +341,12 @@ class Renderer:
 
     # ---- the ray-generation shader for one pixel
     def pixel(self, x, y, world_pos, world_norm, dif4, spec4, emissive4, nee=True, splat=True, connect=True,
-              connect_all_visible=False):
-        """-> (rgba written to this pixel, [(target x, target y, rgb)] splats); inputs are the G-buffer texels."""
+              connect_all_visible=False, terms_all_visible=False):
+        """-> (rgba written to this pixel, [(target x, target y, rgb)] splats); inputs are the G-buffer texels.
+        connect_all_visible / terms_all_visible: the oracle's ORACLE_CONNECT_ALL_VISIBLE / ORACLE_TERMS_ALL_VISIBLE hooks."""
         D, minT = self.D, float(self.p.minT)
+        self.terms_all_visible = terms_all_visible
+        self.risky = []
         if world_pos[3] == 0.0:
             return np.array([dif4[0], dif4[1], dif4[2], 1.0]), []
         out = np.zeros(4)  # getClearedTexture: the channel starts at 0 (BDPTPass.cpp:73)
@@ -299,20 +355,24 @@ class Renderer:
         dif, spec = dif4[:3].astype(np.float64), spec4[:3].astype(np.float64)
         V = norm(self.cam_pos - wp)
         seed = hm_init_rand(x + y * self.W, int(self.p.frameCount))
-        cam = [Vertex() for _ in range(9)]
-        lig = [Vertex() for _ in range(9)]
+        cam = [Vertex() for _ in range(max(9, D + 2))]
+        lig = [Vertex() for _ in range(max(9, D + 2))]
         cam[0].pos, cam[0].N, cam[0].color, cam[0].pdf = self.cam_pos, norm(self.Wv), np.ones(3), 1.0
         w, out_dir, pdf, lobe, _ = hm.sample_brdf(self.mat, seed, wn, V, dif, spec, rough)
         cam[1] = Vertex(w, wp, wn, V, dif, spec, rough, (lobe and self.from_lobe) if self.mat == 0 else False, pdf)
         pl = self.payload(wp, out_dir, w, seed)
         depth = 1
+        walk_terms = []  # BDPT_PARAM_ENV_ON_MISS (include/bdpt.h): what the ray that left eye vertex `depth` found, weighted 1 / edges
         while depth < D and not pl["terminated"]:
             self.shoot(pl)
+            if pl["extra"] is not None:
+                c = self.clamp_vec((cam[depth].color * pl["extra"]) / (depth + 1))
+                walk_terms.append(np.zeros(3) if np.isnan(c).any() else c)
             cam[depth + 1] = self.vertex_of(pl)
             depth += 1
         seed = pl["seed"]
         seed, l_origin, l_dir, l_int = self.sample_light(seed)
-        take = [True] * 9
+        take = [True] * len(lig)
         lig[0].pos, lig[0].color, lig[0].pdf = l_origin, l_int, 1.0 / self.nl
         lp = self.payload(l_origin, l_dir, l_int, seed)
         depth = 0
@@ -324,6 +384,8 @@ class Renderer:
         seed = lp["seed"]
         if (emissive4[:3] > 0.0).any():
             out = out + emissive4.astype(np.float64)
+        for c in walk_terms:  # after the pixel's own emissive term, before the NEE terms, in bounce order, without saturate
+            out = out + np.append(c, 1.0)
         for i in range(D if nee else 0):
             seed, direct = self.eval_direct(seed, cam[i + 1])
             c = self.clamp_vec(self.weighted(cam[i].color * direct, i + 2, cam, lig, i + 1, 0))
@@ -335,7 +397,7 @@ class Renderer:
             last_pos, last_n = lig[i + 1].pos, lig[i + 1].N
             to_cam = norm(self.cam_pos - last_pos)
             dist = float(np.linalg.norm(self.cam_pos - last_pos))
-            if float(np.dot(cam_n, to_cam)) < 0 and self.visible(last_pos, to_cam, minT, dist):
+            if float(np.dot(cam_n, to_cam)) < 0 and (self.terms_all_visible or self.visible(last_pos, to_cam, minT, dist)):
                 target = self.pixel_of(to_cam)
                 t1 = hm.saturate(abs(float(np.dot(to_cam, cam_n))))
                 t2 = hm.saturate(abs(float(np.dot(to_cam, last_n))))
@@ -343,14 +405,14 @@ class Renderer:
                 g = t1 * t2 * inv * inv
                 v = lig[i + 1]
                 f = hm.eval_brdf(self.mat, v.V, norm(self.cam_pos - v.pos), v.N, v.dif, v.spec, v.rough, v.is_spec)
-                c = self.clamp_vec(self.weighted((lig[i].color * f) * g, i + 2, cam, lig, 0, i + 1))
+                c = self.clamp_vec(self.weighted((lig[i].color * f) * g, i + 2, cam, lig, 0, i + 1), self.sem.d3d_clamp)
                 if target is not None:
                     splats.append((target[0], target[1], np.zeros(3) if np.isnan(c).any() else c))
             i += 1
         for total in range(2, (D + 1) if connect else 2):
             for cl in range(1, D):
                 ll = total - cl
-                if ll < 0 or ll > 8:
+                if ll < 0 or ll >= len(lig):
                     continue  # uint underflow / out-of-range index in the shader: skipped
                 g = self.g_without_v(cam[cl], lig[ll])
                 a, b = cam[cl].pos, lig[ll].pos
@@ -359,7 +421,11 @@ class Renderer:
                     d = (b - a) / np.float64(length)
                 if connect_all_visible or self.visible(a, d, minT, length):
                     c = self.clamp_vec(self.weighted(self.contribution(cam, lig, cl, ll, g), total, cam, lig, cl, ll))
-                    out = np.fmin(np.fmax(out + np.append(np.zeros(3) if np.isnan(c).any() else c, 1.0), 0.0), 1.0)  # saturate
+                    if not self.sem.zero_pairs_write and not c.any():
+                        continue
+                    out = out + np.append(np.zeros(3) if np.isnan(c).any() else c, 1.0)
+                    if self.sem.saturate_per_write:
+                        out = np.fmin(np.fmax(out, 0.0), 1.0)  # saturate
         return out, splats
 
 

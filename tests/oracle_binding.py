@@ -8,6 +8,7 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_PATH = os.path.join(_ROOT, "oracle", "liboracle.so")
 ORACLE_BRUTE_FORCE = 1
 ORACLE_CONNECT_ALL_VISIBLE = 2
+ORACLE_TERMS_ALL_VISIBLE = 4
 
 
 class OracleFrame(C.Structure):
