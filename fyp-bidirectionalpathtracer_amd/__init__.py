@@ -883,6 +883,65 @@ class Context:
         the full-frame G-buffer, and the full-frame RGBA32F image at `out_ptr`, which gets (colour, 1)."""
         self._check(self._lib.bdpt_sky_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_sky_execute")
 
+    # ---- MIS sky lighting (include/bdpt.h "Environment lighting", DESIGN.md "MIS sky lighting") ----
+    @staticmethod
+    def _sky_techniques(what, techniques):
+        if isinstance(techniques, bool) or not isinstance(techniques, int) or not 1 <= techniques <= 3:
+            raise BdptError(f"{what}: techniques must be 1 (table samples), 2 (BSDF samples) or 3 (both), not {techniques!r}")
+        return techniques
+
+    def bsdf_pdf(self, surfaces, dirs, mat_index=0, out=None, count=None, stream=None):
+        """bdpt_bsdf_pdf_query: the BSDF of each (N, 24) bdpt_surface record toward dirs (N, 4) float32 (xyz = L, used as
+        given), for MIS.  Returns (N, 4) float32: 0-2 the unweighted BSDF times cosine that next-event estimation uses, 3 the
+        solid-angle density with which sample_bsdf draws L (mat_index 0 GGX: the mixture of its two lobes; 1 Lambertian).  A
+        miss record gives zeros."""
+        import torch
+        f32, i32 = (torch.float32,), (torch.float32, torch.int32)
+        mat, _ = self._bsdf_mode("bsdf_pdf", mat_index, False)
+
+        def run(ptrs, n, cnt, res):
+            d = abi.BsdfPdfDesc()
+            d.num, d.matIndex, d.numDevice, d.surfaces, d.dirs, d.values = n, mat, cnt, ptrs[0], ptrs[1], res
+            return self._lib.bdpt_bsdf_pdf_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("bsdf_pdf", [("surfaces", surfaces, 24, i32), ("dirs", dirs, 4, f32)], (4, f32), run, out, count,
+                                   fn="bdpt_bsdf_pdf_query")
+
+    def sky_lighting_mis(self, surfaces, seeds, samples, mat_index=0, techniques=3, clamp=float(3.4028234663852886e38), min_t=1e-4,
+                         alive=None, out=None, counts=None, seeds_out=None, count=None, stream=None):
+        """bdpt_sky_mis_query: sky lighting with multiple importance sampling.  Per (N, 24) bdpt_surface record and sample
+        one any-hit ray toward a direction drawn from the environment map's table (techniques bit 0) and one toward a
+        direction drawn from the BSDF (bit 1; mat_index 0 GGX, 1 Lambertian), each weighted by the balance heuristic, in one
+        launch — the loop env_sample -> bsdf_pdf -> sample_bsdf -> env_eval -> bsdf_pdf -> trace_rays("any") twice -> ordered
+        adds, bit for bit.  With one technique it is the plain estimator.  seeds (N,) uint32 / int32 RNG states: four draws
+        per table sample, three per BSDF sample.  `clamp` bounds every component of a term.  Returns (N, 4) float32: (the sum
+        of the visible terms over `samples`, 1); a miss record, or an item whose `alive` byte is 0, gives (diffuse, 1) without
+        a draw.  GPU tensors only: alive (N,) uint8; counts (N,) takes the terms traced and found unoccluded (0 .. 2 *
+        samples); seeds_out (N,) the states after the draws (it may be `seeds`).  `out` and `count` as for the other queries."""
+        import torch
+        records, words = (torch.float32, torch.int32), (torch.int32, torch.uint32)
+        samples = self._sky_samples("sky_lighting_mis", samples)
+        mat, _ = self._bsdf_mode("sky_lighting_mis", mat_index, False)
+        techniques = self._sky_techniques("sky_lighting_mis", techniques)
+        extras = [("alive", alive, None, (torch.uint8,)), ("counts", counts, None, words), ("seeds_out", seeds_out, None, words)]
+
+        def run(ptrs, n, cnt, res):
+            d = abi.SkyMisDesc()
+            d.num, d.samples, d.numDevice, d.clampUpper, d.minT = n, samples, cnt, float(clamp), float(min_t)
+            d.matIndex, d.techniques = mat, techniques
+            d.surfaces, d.seeds, d.color = ptrs[0], ptrs[1], res
+            d.alive, d.counts, d.seedsOut = (None if t is None else t.data_ptr() for t in (alive, counts, seeds_out))
+            return self._lib.bdpt_sky_mis_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("sky_lighting_mis", [("surfaces", surfaces, 24, records), ("seeds", seeds, None, words)],
+                                   (4, (torch.float32,)), run, out, count, extras=extras, fn="bdpt_sky_mis_query")
+
+    def sky_mis_execute(self, params, gbuffer, out_ptr, stream=None):
+        """bdpt_sky_mis_execute: MIS sky lighting on the context's tile pixels — abi.SkyMisParams (frameCount, clampUpper,
+        minT, samples, matIndex, techniques), the full-frame G-buffer, and the full-frame RGBA32F image at `out_ptr`, which
+        gets (colour, 1).  matIndex 0 needs a camera."""
+        self._check(self._lib.bdpt_sky_mis_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_sky_mis_execute")
+
     # ---- diffuse GI (include/bdpt.h "Diffuse GI", DESIGN.md) ----
     def diffuse_gi(self, surfaces, seeds, indirect=True, cosine=True, view_pos=None, normal_map=True, min_t=1e-4, alive=None,
                    out=None, hits=None, status=None, seeds_out=None, count=None, stream=None):
@@ -1770,26 +1829,34 @@ class FramePipeline:
         self.last_ao_params = p
         return out
 
-    def sky_lighting(self, samples=1, clamp=float(3.4028234663852886e38)):
+    def sky_lighting(self, samples=1, clamp=float(3.4028234663852886e38), mis=False, mat_index=1):
         """Sky lighting on this pipeline's G-buffer as it stands and stream: Context.sky_execute with the pass's frame
         counter (from 0, one per call, as ambient_occlusion keeps its own), the pipeline's min_t, `samples` table-sampled rays
-        per pixel (1 .. 64) and `clamp` as the bound of a sample's value.  The environment is the map given to
+        per pixel (1 .. 64) and `clamp` as the bound of a sample's value.  With ``mis`` it is Context.sky_mis_execute: per
+        sample a table-sampled and a BSDF-sampled ray, combined by the balance heuristic, for the Lambertian surface
+        (``mat_index`` 1) or the pass's GGX material (0: MaterialSpecRough and the pipeline's camera are read as well);
+        ``mat_index`` 0 without ``mis`` is refused.  The environment is the map given to
         ``ctx.set_environment``; its sampling table is prepared on first use and again whenever the environment was set anew
         through ``ctx.set_environment``.  The map's contents are not watched: after rewriting the map in place, call
         ``ctx.env_prepare`` (or set the environment again).
         Returns the (H, W, 4) float32 channel "SkyLighting" ((colour, 1); a tile or stripes pipeline writes its own rows),
-        also in ``channels``; ``last_sky_params`` keeps the abi.SkyParams used."""
-        p = abi.SkyParams()
+        also in ``channels``; ``last_sky_params`` keeps the abi.SkyParams (abi.SkyMisParams with ``mis``) used."""
+        mat_index, _ = Context._bsdf_mode("sky_lighting", mat_index, False)
+        if not mis and mat_index != 1:
+            raise BdptError("sky_lighting: mat_index 0 (GGX) goes with mis=True (the plain pass is Lambertian)")
+        p = abi.SkyMisParams() if mis else abi.SkyParams()
         p.samples = Context._sky_samples("sky_lighting", samples)
         p.clampUpper = float(clamp)
         p.minT, p.frameCount = self.min_t, self.sky_frame & 0xFFFFFFFF
+        if mis:
+            p.matIndex, p.techniques = mat_index, abi.SKY_MIS_TABLE | abi.SKY_MIS_BSDF
         if self.ctx._env_prepared != self.ctx._env_serial:
             self.ctx.env_prepare(self._stream_ptr())
         if SKY_CHANNEL not in self.channels:
             with self.torch.cuda.device(self.dev):
                 self.channels[SKY_CHANNEL] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
         out = self.channels[SKY_CHANNEL]
-        self.ctx.sky_execute(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
+        (self.ctx.sky_mis_execute if mis else self.ctx.sky_execute)(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
         self.sky_frame += 1
         self.last_sky_params = p
         return out

@@ -364,6 +364,26 @@ class SkyParams(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+SKY_MIS_TABLE, SKY_MIS_BSDF = 1, 2  # bdpt_sky_mis_desc::techniques
+
+
+class BsdfPdfDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("matIndex", C.c_uint32), ("numDevice", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("surfaces", C.c_void_p), ("dirs", C.c_void_p), ("values", C.c_void_p)]
+
+
+class SkyMisDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("samples", C.c_uint32), ("numDevice", C.c_void_p), ("clampUpper", C.c_float), ("minT", C.c_float),
+                ("matIndex", C.c_uint32), ("techniques", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("surfaces", C.c_void_p), ("seeds", C.c_void_p), ("alive", C.c_void_p), ("color", C.c_void_p), ("counts", C.c_void_p),
+                ("seedsOut", C.c_void_p)]
+
+
+class SkyMisParams(C.Structure):
+    _fields_ = [("frameCount", C.c_uint32), ("clampUpper", C.c_float), ("minT", C.c_float), ("samples", C.c_uint32),
+                ("matIndex", C.c_uint32), ("techniques", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 BMFR_MAX_PLANES = BDPT_MAX_LIGHTS + 2
 
 
@@ -430,6 +450,9 @@ PROTOTYPES = {
     "bdpt_env_query": (C.c_int, [C.c_void_p, C.POINTER(EnvDesc), C.c_void_p]),
     "bdpt_sky_query": (C.c_int, [C.c_void_p, C.POINTER(SkyDesc), C.c_void_p]),
     "bdpt_sky_execute": (C.c_int, [C.c_void_p, C.POINTER(SkyParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "bdpt_bsdf_pdf_query": (C.c_int, [C.c_void_p, C.POINTER(BsdfPdfDesc), C.c_void_p]),
+    "bdpt_sky_mis_query": (C.c_int, [C.c_void_p, C.POINTER(SkyMisDesc), C.c_void_p]),
+    "bdpt_sky_mis_execute": (C.c_int, [C.c_void_p, C.POINTER(SkyMisParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_host_env_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "bdpt_host_env_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                         C.c_void_p]),

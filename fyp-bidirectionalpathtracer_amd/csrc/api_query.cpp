@@ -1,7 +1,8 @@
 // api_query.cpp — the per-item queries of the C ABI (include/bdpt.h): bdpt_trace_rays, bdpt_camera_rays, bdpt_shade_hits,
 // bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query, bdpt_ao_query, bdpt_gi_query,
-// bdpt_direct_query, bdpt_env_query, bdpt_sky_query and bdpt_motion_query, on a caller's arrays in device memory, and
-// bdpt_ao_execute, bdpt_gi_execute, bdpt_direct_execute and bdpt_sky_execute, the same kernels on the tile's G-buffer
+// bdpt_direct_query, bdpt_env_query, bdpt_sky_query, bdpt_bsdf_pdf_query, bdpt_sky_mis_query and bdpt_motion_query, on a
+// caller's arrays in device memory, and bdpt_ao_execute, bdpt_gi_execute, bdpt_direct_execute, bdpt_sky_execute and
+// bdpt_sky_mis_execute, the same kernels on the tile's G-buffer
 // pixels.  Every one checks its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags and what goes together
 // (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
 // first use of the emitter table), so all can be captured into a hipGraph.
@@ -498,6 +499,93 @@ int bdpt_sky_execute(bdpt_ctx* c, const bdpt_sky_params* p, const bdpt_gbuffer* 
     Q.samples = p->samples;
     Q.frameCount = p->frameCount;
     launchSky(c->scene.S, Q, true, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+static_assert(sizeof(bdpt_bsdf_pdf_desc) == 48 && offsetof(bdpt_bsdf_pdf_desc, surfaces) == 24 && sizeof(bdpt_sky_mis_desc) == 88 &&
+                  offsetof(bdpt_sky_mis_desc, surfaces) == 40 && sizeof(bdpt_sky_mis_params) == 32,
+              "abi.BsdfPdfDesc, abi.SkyMisDesc and abi.SkyMisParams restate these layouts");
+int bdpt_bsdf_pdf_query(bdpt_ctx* c, const bdpt_bsdf_pdf_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "bsdf_pdf_query")) return rc;
+  if (d->matIndex > 1 || d->flags || d->reserved)
+    return refuse(c, BDPT_E_INVALID, "bsdf_pdf_query", "matIndex > 1, or non-zero flags or reserved");
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->surfaces, 16) || !aligned(d->dirs, 16) || !aligned(d->values, 16) || (d->numDevice && !aligned(d->numDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "bsdf_pdf_query", "surfaces, dirs or values missing or not aligned (16 bytes; numDevice 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    launchBsdfPdfQuery(f4(d->surfaces), d->num, d->numDevice, d->matIndex == 0, f4(d->dirs), f4(d->values), st);
+  });
+}
+
+namespace {
+bool skyMisModeOk(uint32_t samples, uint32_t matIndex, uint32_t techniques) {
+  return samples && samples <= BDPT_SKY_MAX_SAMPLES && matIndex <= 1 && techniques >= 1 && techniques <= 3;
+}
+}  // namespace
+
+int bdpt_sky_mis_query(bdpt_ctx* c, const bdpt_sky_mis_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "sky_mis_query")) return rc;
+  if (int rc = needEnvTable(c, "sky_mis_query")) return rc;
+  if (!skyMisModeOk(d->samples, d->matIndex, d->techniques) || d->flags || d->reserved)
+    return refuse(c, BDPT_E_INVALID, "sky_mis_query",
+                  "samples outside 1 .. BDPT_SKY_MAX_SAMPLES, matIndex > 1, techniques outside 1 .. 3, or non-zero flags or reserved");
+  if (!d->num) return BDPT_OK;
+  if (!aligned(d->surfaces, 16) || !aligned(d->seeds, 4) || !aligned(d->color, 16) || (d->counts && !aligned(d->counts, 4)) ||
+      (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
+    return refuse(c, BDPT_E_INVALID, "sky_mis_query",
+                  "surfaces, seeds, color, counts, seedsOut or numDevice missing or not aligned (records 16 bytes, words 4)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    SkyMisDev Q{};
+    Q.table = c->envTable.table;
+    Q.surf = f4(d->surfaces);
+    Q.seeds = d->seeds;
+    Q.alive = d->alive;
+    Q.color = f4(d->color);
+    Q.counts = d->counts;
+    Q.seedsOut = d->seedsOut;
+    Q.range = {d->num, d->numDevice, d->minT};
+    Q.clampUpper = d->clampUpper;
+    Q.samples = d->samples;
+    Q.techniques = d->techniques;
+    launchSkyMis(c->scene.S, Q, false, d->matIndex == 0, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+int bdpt_sky_mis_execute(bdpt_ctx* c, const bdpt_sky_mis_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
+  if (!c || !p || !gb) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "sky_mis_execute")) return rc;
+  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "sky_mis_execute", "no size (bdpt_resize first)");
+  if (int rc = needEnvTable(c, "sky_mis_execute")) return rc;
+  const bool ggx = p->matIndex == 0;  // V comes from the camera
+  if (ggx)
+    if (int rc = needCamera(c, "sky_mis_execute: matIndex 0")) return rc;
+  if (!skyMisModeOk(p->samples, p->matIndex, p->techniques) || p->reserved[0] || p->reserved[1])
+    return refuse(c, BDPT_E_INVALID, "sky_mis_execute",
+                  "samples outside 1 .. BDPT_SKY_MAX_SAMPLES, matIndex > 1, techniques outside 1 .. 3, or non-zero reserved");
+  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(gb->materialDiffuse, 8) ||
+      (ggx && !aligned(gb->materialSpecRough, 8)) || !aligned(out, 16))
+    return refuse(c, BDPT_E_INVALID, "sky_mis_execute",
+                  "worldPosition, worldNormal, materialDiffuse, materialSpecRough (matIndex 0) or out missing or not aligned (16 bytes; "
+                  "the half channels 8)");
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    SkyMisDev Q{};
+    Q.table = c->envTable.table;
+    Q.gbPosition = f4(gb->worldPosition);
+    Q.gbNormal = gb->worldNormal;
+    Q.gbDiffuse = gb->materialDiffuse;
+    Q.gbSpecRough = gb->materialSpecRough;
+    Q.pix = c->frame.P.pix;
+    Q.out = f4(out);
+    Q.range = {c->frame.P.Np, nullptr, p->minT};
+    if (ggx)
+      for (int k = 0; k < 3; k++) Q.camPos[k] = c->cam.posW[k];
+    Q.clampUpper = p->clampUpper;
+    Q.samples = p->samples;
+    Q.techniques = p->techniques;
+    Q.frameCount = p->frameCount;
+    launchSkyMis(c->scene.S, Q, true, ggx, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 

@@ -1,5 +1,5 @@
 // device_item_loop.hpp — the persistent item loop of the query kernels (trace_rays.hip, walk_query.hip, ao.hip, gi.hip,
-// sky.hip).
+// sky.hip, sky_mis.hip).
 //
 // Each of those kernels is one wave per workgroup with 64 traversal slots, kStackLds stack rows in LDS and the rest in the
 // context's overflow area, and this loop:

@@ -1,8 +1,9 @@
-// env_light.h — environment lighting (bdpt_env_prepare / bdpt_env_query / bdpt_sky_query / bdpt_host_env_*): the sampling
-// table's per-texel arithmetic, the sampler, its pdf and the evaluation of a direction, shared by the device kernels
-// (env_light.hip, sky.hip) and the host entry points (env_host.cpp).  The arithmetic is the contract of include/bdpt.h
-// "Environment lighting": fp32 and fp64 as written, no contraction (-ffp-contract=off on both sides), every operation in
-// the order written here.  Plain C++ apart from the __host__ __device__ markers (texture_planes.h BDPT_HD).
+// env_light.h — environment lighting (bdpt_env_prepare / bdpt_env_query / bdpt_sky_query / bdpt_sky_mis_query /
+// bdpt_host_env_*): the sampling table's per-texel arithmetic, the sampler, its pdf and the evaluation of a direction, shared
+// by the device kernels (env_light.hip, sky.hip, sky_mis.hip) and the host entry points (env_host.cpp).  The arithmetic is
+// the contract of include/bdpt.h "Environment lighting": fp32 and fp64 as written, no contraction (-ffp-contract=off on both
+// sides), every operation in the order written here.  Plain C++ apart from the __host__ __device__ markers
+// (texture_planes.h BDPT_HD).
 //
 // det_sincos2pi, det_acos, det_atan, atan2_WAR, normalize and nextRand are the texts of device_math.hpp / device_scene.hpp,
 // which are device-only; they are restated here (namespace envl) so that the host runs them too.  tests/test_gpu_env.py
@@ -297,5 +298,34 @@ struct SkyDev {
 };
 // `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
 void launchSky(const SceneDev& S, const SkyDev& Q, bool gbuffer, unsigned long long* cursor, LaunchGrids& G, int numCUs, hipStream_t st);
+// bdpt_bsdf_pdf_query (env_light.hip): out[i] = (fcos, pdf) of bdpt_surface record i toward dirs[i].xyz (device_bsdf_pdf.hpp);
+// count (optional device word) caps cap
+void launchBsdfPdfQuery(const float4* surf, uint32_t cap, const uint32_t* count, bool ggx, const float4* dirs, float4* out, hipStream_t st);
+// sky_mis.hip: bdpt_sky_mis_query and bdpt_sky_mis_execute.  Per alive item and sample one table-sampled and one BSDF-sampled
+// any-hit ray (`techniques` bit 0 / bit 1), weighted by the balance heuristic when both are on.
+struct SkyMisDev {
+  EnvTable table;
+  const float4* surf;           // query: bdpt_surface records (posW, N, V, linearRoughness, diffuse, specular and prim are read)
+  const uint32_t* seeds;        // query: one RNG state per item
+  const uint8_t* alive;         // query, optional: 0 = the item is dead
+  float4* color;                // query: (colour, 1) per item
+  uint32_t* counts;             // query, optional: traced and unoccluded terms per item (0 .. 2 * samples)
+  uint32_t* seedsOut;           // query, optional: the state after (4 | 3 | 7) * samples draws (a dead item's: unchanged)
+  const float4* gbPosition;     // execute: WorldPosition of the full frame (w != 0: geometry)
+  const uint16_t* gbNormal;     // execute: WorldNormal (half4) of the full frame
+  const uint16_t* gbDiffuse;    // execute: MaterialDiffuse (half4) of the full frame
+  const uint16_t* gbSpecRough;  // execute, GGX: MaterialSpecRough (half4): specular = rgb, rough = a * a
+  const uint32_t* pix;          // execute: the tile's pixels (PathBuf::pix); the seed is initRand(pix, frameCount)
+  float4* out;                  // execute: full-frame RGBA32F, (colour, 1) at the tile's pixels
+  QueryRange range;             // execute: cap = the tile's pixel count, no device word
+  float camPos[3];              // execute, GGX: V = normalize(camPos - posW)
+  float clampUpper;
+  uint32_t samples;             // 1 .. 64
+  uint32_t techniques;          // bit 0: table samples, bit 1: BSDF samples
+  uint32_t frameCount;          // execute
+};
+// `cursor`: as launchSky
+void launchSkyMis(const SceneDev& S, const SkyMisDev& Q, bool gbuffer, bool ggx, unsigned long long* cursor, LaunchGrids& G, int numCUs,
+                  hipStream_t st);
 }  // namespace bdpt
 #endif

@@ -1,4 +1,5 @@
-// env_light.hip — the environment map's sampling table on the device (bdpt_env_prepare) and bdpt_env_query.
+// env_light.hip — the environment map's sampling table on the device (bdpt_env_prepare), bdpt_env_query and
+// bdpt_bsdf_pdf_query.
 //
 // The table is a discrete distribution over the texels of the lat-long map, exact in integers (include/bdpt.h
 // "Environment lighting"; the per-texel arithmetic is env_light.h, which bdpt_host_env_table runs on the CPU).  Three
@@ -14,9 +15,11 @@
 //
 // bdpt_env_query has no traversal, so no persistent grid: one lane per item on a dense grid of one-wave workgroups, as
 // light_query.hip.  The sampler and the evaluation are env_light.h's; the value is written with the device functions the
-// pass runs (saturate, directIfVisible).
+// pass runs (saturate, directIfVisible).  bdpt_bsdf_pdf_query (bsdf_pdf_kernel, beside the sample kernel) is the same kind
+// of launch: the BSDF's fcos and sampling density toward a caller's direction (device_bsdf_pdf.hpp), for MIS.
 #include "kernels.h"
 
+#include "device_bsdf_pdf.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_trace.hpp"  // BDPT_ONE_WAVE_PER_GROUP
@@ -175,6 +178,25 @@ __global__ __launch_bounds__(kWave) void env_sample_kernel(EnvQueryDev Q) {
   envSampleLane<GGX, COMPACT>(Q);
 }
 
+// bdpt_bsdf_pdf_query: one float4 per item, (fcos, pdf) of the record toward dirs[i].xyz (bsdfFcosPdf); zeros for a record
+// with prim < 0.  Reads the record's N, V, linearRoughness, diffuse, specular and prim only.
+template <bool GGX>
+__global__ __launch_bounds__(kWave) void bsdf_pdf_kernel(const float4* __restrict__ surf, uint32_t cap, const uint32_t* count,
+                                                         const float4* __restrict__ dirs, float4* __restrict__ out) {
+  BDPT_ONE_WAVE_PER_GROUP();
+  uint32_t i;
+  if (queryLanePast(cap, count, i)) return;
+  const float4* r = surf + (size_t)i * 6;
+  f3 fcos = mk(0);
+  float pdf = 0.0f;
+  if (__float_as_int(r[5].w) >= 0) {
+    const float4 n = r[1], v = r[2], dif = r[3], spec = r[4], l = dirs[i];
+    bsdfFcosPdf<GGX>(mk(l.x, l.y, l.z), mk(n.x, n.y, n.z), mk(v.x, v.y, v.z), mk(dif.x, dif.y, dif.z), mk(spec.x, spec.y, spec.z),
+                     n.w * n.w, fcos, pdf);
+  }
+  out[i] = make_float4(fcos.x, fcos.y, fcos.z, pdf);
+}
+
 // bdpt_env_eval: two float4 per item, (radiance, pdf) (texel, 0, 0, 0)
 __global__ __launch_bounds__(kWave) void env_eval_kernel(EnvQueryDev Q) {
   BDPT_ONE_WAVE_PER_GROUP();
@@ -198,6 +220,11 @@ void launchEnvQuery(const EnvQueryDev& Q, bool evalMode, bool ggx, hipStream_t s
   withFlag(ggx, [&](auto GGX) {
     withFlag(Q.compact.rays != nullptr, [&](auto COMPACT) { launchWave(env_sample_kernel<GGX, COMPACT>, g, st, Q); });
   });
+}
+
+void launchBsdfPdfQuery(const float4* surf, uint32_t cap, const uint32_t* count, bool ggx, const float4* dirs, float4* out, hipStream_t st) {
+  if (!cap) return;
+  withFlag(ggx, [&](auto GGX) { launchWave(bsdf_pdf_kernel<GGX>, wavesFor(cap), st, surf, cap, count, dirs, out); });
 }
 
 }  // namespace bdpt

@@ -312,6 +312,7 @@ struct LaunchGrids {
   uint32_t gi[3] = {0, 0, 0};         // [records, records + normal map, G-buffer] (gi.hip)
   uint32_t direct[4] = {0, 0, 0, 0};  // [G-buffer source][HINTS] (direct.hip)
   uint32_t sky[2] = {0, 0};           // [G-buffer source] (sky.hip)
+  uint32_t skyMis[4] = {0, 0, 0, 0};  // [G-buffer source][GGX] (sky_mis.hip)
 };
 // both random walks of the frame: one persistent launch (trace + hit/miss shading in place)
 void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,

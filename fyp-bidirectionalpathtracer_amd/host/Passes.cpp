@@ -736,6 +736,7 @@ void SimpleDiffuseGIPass::execute(RenderContext* pRenderContext) {
 bool SkyLightingPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
   mpResManager = pResManager;
   mpResManager->requestTextureResources({"WorldPosition", "WorldNormal", "MaterialDiffuse"});
+  if (mUseMis && mMatIndex == 0) mpResManager->requestTextureResource("MaterialSpecRough");
   mpResManager->requestTextureResource(mOutputBuf);
   mpResManager->requestTextureResource(ResourceManager::kEnvironmentMap);
   mpRays = RayLaunch::create(pRenderContext);
@@ -751,6 +752,8 @@ void SkyLightingPass::renderGui(Gui* pGui) {
   int dirty = 0;
   dirty |= (int)pGui->addIntVar("Num Sky Rays", mNumRaysPerPixel, 1, (int)BDPT_SKY_MAX_SAMPLES);
   dirty |= (int)pGui->addFloatVar("Sky clamp", mClampUpper, 0.0f, 3.402823466e+38f, 0.1f);
+  dirty |= (int)pGui->addCheckBox(mUseMis ? "Table and BSDF samples (MIS)" : "Table samples only", mUseMis);
+  if (mUseMis) dirty |= (int)pGui->addIntVar("Sky material (0 GGX, 1 Lambertian)", mMatIndex, 0, 1);
   if (dirty) setRefreshFlag();
 }
 void SkyLightingPass::execute(RenderContext* pRenderContext) {
@@ -786,6 +789,30 @@ void SkyLightingPass::execute(RenderContext* pRenderContext) {
   gb.worldPosition = (float*)pos->getDevicePointer();
   gb.worldNormal = (uint16_t*)nrm->getDevicePointer();
   gb.materialDiffuse = (uint16_t*)dif->getDevicePointer();
+  if (mUseMis) {
+    const bool ggx = mMatIndex == 0;
+    if (ggx) {  // the GGX material reads MaterialSpecRough, and V from the scene's camera
+      Texture::SharedPtr spec = mpResManager->getTexture("MaterialSpecRough");
+      Camera::SharedPtr cam = mpScene ? mpScene->getActiveCamera() : nullptr;
+      if (!spec || spec->getFormat() != ResourceFormat::RGBA16Float || !cam) {
+        std::fprintf(stderr, "[SkyLightingPass] the GGX material needs MaterialSpecRough (RGBA16F) of a G-buffer pass and a camera\n");
+        return;
+      }
+      gb.materialSpecRough = (uint16_t*)spec->getDevicePointer();
+      bdpt_set_camera(mpRays->ctx(), &cam->getData());
+    }
+    bdpt_sky_mis_params m;
+    std::memset(&m, 0, sizeof(m));
+    m.frameCount = mFrameCount++;
+    m.clampUpper = mClampUpper;
+    m.minT = mpResManager->getMinTDist();
+    m.samples = (uint32_t)mNumRaysPerPixel;
+    m.matIndex = ggx ? 0u : 1u;
+    m.techniques = BDPT_SKY_MIS_TABLE | BDPT_SKY_MIS_BSDF;
+    if (bdpt_sky_mis_execute(mpRays->ctx(), &m, &gb, (float*)pDstTex->getDevicePointer(), stream) != BDPT_OK)
+      std::fprintf(stderr, "[SkyLightingPass] %s\n", mpRays->lastError());
+    return;
+  }
   bdpt_sky_params p;
   std::memset(&p, 0, sizeof(p));
   p.frameCount = mFrameCount++;

@@ -234,12 +234,17 @@ class SimpleDiffuseGIPass : public RenderPass {
 
 // Sky lighting: importance-sampled shadow rays toward the environment map (no pass of the reference: it is shaped like the
 // AO pass above).  WorldPosition, WorldNormal, MaterialDiffuse and the environment map in, the output channel out.  The
-// map's sampling table is prepared when the map bound to the pass's context changes.  Its kernel is bdpt_sky_execute.
+// map's sampling table is prepared when the map bound to the pass's context changes.  Its kernel is bdpt_sky_execute; with
+// MIS on it is bdpt_sky_mis_execute (a table-sampled and a BSDF-sampled ray per sample, balance heuristic), for the
+// Lambertian surface or, with material 0, the pass's GGX material: MaterialSpecRough and the scene's camera then go in too.
+// MIS and the material are the host program's configuration, like the clamp: the checkpoint record does not hold them.
 class SkyLightingPass : public RenderPass {
  public:
   using SharedPtr = std::shared_ptr<SkyLightingPass>;
   static SharedPtr create(const std::string& outBuf = ResourceManager::kOutputChannel) { return SharedPtr(new SkyLightingPass(outBuf)); }
   void setClamp(float hi) { mClampUpper = hi; }
+  void setMis(bool on) { mUseMis = on; }
+  void setMaterial(int matIndex) { mMatIndex = matIndex; }  // 0 GGX (with MIS only), 1 Lambertian
   // The table is a snapshot of the map's contents, made again when the map's address or size changes.  A host that
   // rewrites the map in place calls this, and the next frame prepares the table anew.
   void environmentChanged() { mPreparedMap = nullptr; }
@@ -260,6 +265,8 @@ class SkyLightingPass : public RenderPass {
   Scene::SharedPtr mpScene;
   std::string mOutputBuf;
   float mClampUpper = 3.402823466e+38f;  // no clamp
+  bool mUseMis = false;
+  int32_t mMatIndex = 1;
   uint32_t mFrameCount = 0;
   int32_t mNumRaysPerPixel = 1;
   const float* mPreparedMap = nullptr;  // the map the context's table was made for, and its size

@@ -54,6 +54,8 @@ struct Options {
   int sky = -1;               // --sky N: render the G-buffer, the sky lighting pass (N rays per pixel) and the accumulation pass; needs --env
   float skyClamp = 0.0f;      // --sky-clamp C (with --sky, > 0): the bound of a sample's value; not given: none
   bool skyClampSet = false;
+  bool skyMis = false;        // --sky-mis (with --sky): a table-sampled and a BSDF-sampled ray per sample, balance heuristic
+  bool skyGgx = false;        // --sky-ggx (with --sky-mis): the pass's GGX material instead of the Lambertian surface
   bool gi = false;            // --gi: render the G-buffer, the diffuse GI pass and the accumulation pass instead of the BDPT pipeline
   bool giDirectOnly = false;  // --gi-direct-only: untick "Shooting global illumination rays"
   bool giUniform = false;     // --gi-uniform: untick "Use cosine sampling"
@@ -138,6 +140,8 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   } else if (o.sky >= 0) {  // --sky: the G-buffer, the sky lighting pass into the output channel, and the accumulation pass over it
     SkyLightingPass::SharedPtr sky = SkyLightingPass::create(ResourceManager::kOutputChannel);
     if (o.skyClampSet) sky->setClamp(o.skyClamp);
+    sky->setMis(o.skyMis);
+    sky->setMaterial(o.skyGgx ? 0 : 1);
     pipeline->setPass(1, sky);
     pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
   } else if (o.gi) {  // --gi: the G-buffer, the diffuse GI pass into the output channel, and the accumulation pass over it
@@ -343,8 +347,8 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
                   o.giDirectOnly ? "direct only" : "one bounce", o.giUniform ? ", uniform sampling" : ", cosine sampling", o.frames - warmup, res.ms,
                   res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
     else if (o.sky >= 0)
-      std::printf("%s %ux%u sky lighting, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
-                  o.sky, o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
+      std::printf("%s %ux%u sky lighting%s, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
+                  o.skyMis ? (o.skyGgx ? " (MIS, GGX; two rays a sample)" : " (MIS; two rays a sample)") : "", o.sky, o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
     else if (o.ao >= 0)
       std::printf("%s %ux%u ambient occlusion, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean ao %.6f", o.scene.c_str(), o.W, o.H,
                   o.ao, o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
@@ -405,6 +409,8 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--ao-radius")) o.aoRadius = (float)std::atof(v), o.aoRadiusSet = true;
     else if (const char* v = next("--sky")) o.sky = std::max(0, std::atoi(v));
     else if (const char* v = next("--sky-clamp")) o.skyClamp = (float)std::atof(v), o.skyClampSet = true;
+    else if (std::strcmp(argv[i], "--sky-mis") == 0) o.skyMis = true;
+    else if (std::strcmp(argv[i], "--sky-ggx") == 0) o.skyGgx = true;
     else if (std::strcmp(argv[i], "--gi") == 0) o.gi = true;
     else if (std::strcmp(argv[i], "--gi-direct-only") == 0) o.giDirectOnly = true;
     else if (std::strcmp(argv[i], "--gi-uniform") == 0) o.giUniform = true;
@@ -420,7 +426,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] [--direct [--direct-hints]] [--sky N [--sky-clamp C]] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] [--direct [--direct-hints]] [--sky N [--sky-clamp C] [--sky-mis [--sky-ggx]]] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }
@@ -485,6 +491,10 @@ int main(int argc, char** argv) {
   }
   if (o.sky < 0 && o.skyClampSet) {
     std::fprintf(stderr, "bdpt_render: --sky-clamp C goes with --sky N\n");
+    return 2;
+  }
+  if ((o.skyMis && o.sky < 0) || (o.skyGgx && !o.skyMis)) {
+    std::fprintf(stderr, "bdpt_render: --sky-mis goes with --sky N, and --sky-ggx with --sky-mis\n");
     return 2;
   }
   if (o.gpus < 0 || o.gpus > 64 || (o.gpus > 0 && o.world > 0)) {

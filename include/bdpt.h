@@ -1570,6 +1570,94 @@ typedef struct bdpt_sky_params {
   uint32_t reserved; /* 0 */
 } bdpt_sky_params;
 int bdpt_sky_execute(bdpt_ctx* ctx, const bdpt_sky_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
+/* MIS sky lighting: the BSDF's density toward a given direction, and the fused pass with table samples and BSDF samples
+ * combined by the balance heuristic, for the pass's GGX material or the Lambertian one.  bdpt_sky_query above stays as it is.
+ *
+ * bdpt_bsdf_pdf_query, per item i < min(*numDevice, num): in surfaces[i], dirs[i] (float4, xyz = L, used as given);
+ * out values[i] = (fcos.xyz, pdf): fcos the unweighted BSDF times cosine that next-event estimation uses, pdf the
+ * solid-angle density with which bdpt_bsdf_query(BDPT_BSDF_SAMPLE) draws L; rough = linearRoughness^2 as there.  Built from
+ * the pass's device functions, fp32 as written, without contraction:
+ *   matIndex 1: NdotL = saturate(dot(N, L)); fcos = (NdotL * diffuse) / kPi; pdf = NdotL * kInvPi (sampleBRDF's expression)
+ *   matIndex 0: fcos = directIfVisible(lightsCount 1, L, intensity (1, 1, 1)) = D G F / (4 NdotV) + NdotL diffuse / kPi;
+ *               pdf = 0 when dot(N, L) <= 0, otherwise pdfD + pdfS with pd = probabilityToSampleDiffuse(diffuse, specular),
+ *               pdfD = (NdotL * kInvPi) * pd, H = normalize(V + L), NdotH = saturate(dot(N, H)), LdotH = saturate(dot(L, H)),
+ *               pdfS = (ggxNormalDistribution(NdotH, rough) * NdotH / (4 * LdotH)) * (1.0f - pd): the one-sample mixture of
+ *               sampleBRDF's two lobes.
+ * A record with prim < 0 gives zeros.  numDevice, stream ordering, capture (one kernel node), the error order and the
+ * record contract are bdpt_bsdf_query's: N, V, linearRoughness, diffuse, specular and prim (its sign) are read, floats may be
+ * degenerate or not finite, the outputs are those of the fp32 arithmetic as written, nothing a caller supplies reaches an
+ * address.  flags and reserved must be 0.
+ *
+ * bdpt_sky_mis_query: item i alive as for bdpt_sky_query.  techniques: bit 0 table samples, bit 1 BSDF samples (1, 2 or 3).
+ * For an alive item
+ *   s = seeds[i]; sum = 0; count = 0
+ *   for k = 0 .. samples-1 (1 .. BDPT_SKY_MAX_SAMPLES):
+ *     bit 0 set, the table-sampled term L_k:
+ *       e = envSample(s)                                                              four draws
+ *       (fcos, pB) = the function above toward e.dir; with bit 1 clear pB counts as +0
+ *       termL = e.pdf == 0 ? +0 : clampVec((fcos * e.radiance) / (e.pdf + pB), clampUpper)
+ *     bit 1 set, the BSDF-sampled term B_k:
+ *       b = sampleBRDF(s by value, N, N, V, ...): what bdpt_bsdf_query(BDPT_BSDF_SAMPLE, flags 0) returns for state s;
+ *       then s advances by exactly three draws, for either material (the samplers take two or three)
+ *       ev = envEval(b.dir); (fcos, pB) toward b.dir; with bit 0 clear ev.pdf counts as +0
+ *       termB = b.pdf == 0 ? +0 : clampVec((fcos * ev.radiance) / (ev.pdf + pB), clampUpper)
+ *     each term, in the order L_0, B_0, L_1, B_1, ...: all +-0: added at once, no ray is traced; else the ray
+ *       (posW, minT, dir, 1e38) is traced as BDPT_TRACE_ANY traces it: occluded adds +0, unoccluded adds the term and
+ *       count += 1
+ *   color[i] = (sum / (float)samples, 1); counts[i] = count, 0 .. 2 * samples; seedsOut[i] = s after 4, 3 or 7 draws a sample
+ * A dead item is handled as by bdpt_sky_query.  This is the balance heuristic with one sample per technique; with one
+ * technique it is the plain estimator, so techniques 1 with matIndex 0 is the GGX variant of bdpt_sky_query.  The call
+ * equals the composed loop bdpt_env_query(SAMPLE) -> bdpt_bsdf_pdf_query -> bdpt_bsdf_query(SAMPLE) -> bdpt_env_query(EVAL)
+ * -> bdpt_bsdf_pdf_query -> elementwise fp32 arithmetic -> bdpt_trace_rays(ANY) twice -> ordered adds, bit for bit.
+ * bdpt_sky_mis_execute runs the same for the context's tile pixels: seeds initRand(x + y * width, frameCount, 16); the
+ * full-frame worldPosition, worldNormal and materialDiffuse, and for matIndex 0 materialSpecRough (specular = rgb, rough =
+ * a * a) with V = normalize(camera position - posW), as the frame's first vertex; alive iff worldPosition.w != 0.  Tiles
+ * and stripes reproduce the whole frame.
+ * Errors, in this order: a NULL context, desc / params or gbuffer BDPT_E_INVALID; no scene, no size (execute), no prepared
+ * table, no camera (execute with matIndex 0) BDPT_E_STATE; samples outside 1 .. BDPT_SKY_MAX_SAMPLES, matIndex > 1,
+ * techniques outside 1 .. 3, non-zero flags or reserved BDPT_E_INVALID; then num == 0 returns BDPT_OK; then a missing or
+ * misaligned buffer BDPT_E_INVALID. */
+#define BDPT_SKY_MIS_TABLE 1u
+#define BDPT_SKY_MIS_BSDF 2u
+typedef struct bdpt_bsdf_pdf_desc {
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  uint32_t matIndex;            /* 0 GGX, 1 Lambertian */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  uint32_t flags;               /* 0 */
+  uint32_t reserved;            /* 0 */
+  const bdpt_surface* surfaces; /* device, 16-byte aligned, num records */
+  const float* dirs;            /* device, 16-byte aligned, num float4 (xyz = L) */
+  float* values;                /* device, 16-byte aligned, num float4: (fcos, pdf) */
+} bdpt_bsdf_pdf_desc; /* 48 bytes */
+int bdpt_bsdf_pdf_query(bdpt_ctx* ctx, const bdpt_bsdf_pdf_desc* desc, void* stream);
+typedef struct bdpt_sky_mis_desc {
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  uint32_t samples;             /* 1 .. BDPT_SKY_MAX_SAMPLES */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  float clampUpper;             /* upper bound of every component of a term (clampVec) */
+  float minT;                   /* tmin of the rays */
+  uint32_t matIndex;            /* 0 GGX, 1 Lambertian */
+  uint32_t techniques;          /* BDPT_SKY_MIS_TABLE | BDPT_SKY_MIS_BSDF: 1, 2 or 3 */
+  uint32_t flags;               /* 0 */
+  uint32_t reserved;            /* 0 */
+  const bdpt_surface* surfaces; /* device, 16-byte aligned, num records */
+  const uint32_t* seeds;        /* device, num RNG states */
+  const uint8_t* alive;         /* optional: device, one byte per item, 0 = the item is dead */
+  float* color;                 /* device, 16-byte aligned, num float4 */
+  uint32_t* counts;             /* optional: device, num words: the terms traced and found unoccluded */
+  uint32_t* seedsOut;           /* optional: device, num RNG states (may be `seeds`) */
+} bdpt_sky_mis_desc; /* 88 bytes */
+int bdpt_sky_mis_query(bdpt_ctx* ctx, const bdpt_sky_mis_desc* desc, void* stream);
+typedef struct bdpt_sky_mis_params {
+  uint32_t frameCount;
+  float clampUpper;
+  float minT;
+  uint32_t samples;     /* 1 .. BDPT_SKY_MAX_SAMPLES */
+  uint32_t matIndex;    /* 0 GGX (needs a camera), 1 Lambertian */
+  uint32_t techniques;  /* 1, 2 or 3 */
+  uint32_t reserved[2]; /* 0 */
+} bdpt_sky_mis_params; /* 32 bytes */
+int bdpt_sky_mis_execute(bdpt_ctx* ctx, const bdpt_sky_mis_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
 /* Host twins (no GPU, no context): csrc/env_light.h on the CPU.  bdpt_host_env_table fills q (optional), cdf (W * H words),
  * rowCdf (H words) and *outMax (optional) for a host map; BDPT_E_LIMIT past BDPT_ENV_MAX_DIM.  bdpt_host_env_sample runs
  * envSample for n states (seedsOut optional, may be `seeds`); bdpt_host_env_eval runs envEval for n float4 directions. */
