@@ -758,6 +758,14 @@ class Context:
             raise BdptError(f"{what}: samples must be an integer in 1 .. {abi.AO_MAX_SAMPLES}, not {samples!r}")
         return samples
 
+    @staticmethod
+    def _item_extras(alive, counts, seeds_out):
+        """The optional GPU tensors of a per-item lighting query, as _surface_query's extras: alive (N,) uint8, counts and
+        seeds_out (N,) 32-bit words."""
+        import torch
+        words = (torch.int32, torch.uint32)
+        return [("alive", alive, None, (torch.uint8,)), ("counts", counts, None, words), ("seeds_out", seeds_out, None, words)]
+
     def ambient_occlusion(self, surfaces, seeds, samples, radius, min_t=1e-4, alive=None, out=None, counts=None, seeds_out=None,
                           count=None, stream=None):
         """bdpt_ao_query: `samples` (1 .. 64) cosine-weighted any-hit rays per (N, 24) bdpt_surface record (posW, N and prim
@@ -769,7 +777,7 @@ class Context:
         import torch
         records, words = (torch.float32, torch.int32), (torch.int32, torch.uint32)  # the dtypes a record / a 32-bit word may have
         samples = self._ao_samples("ambient_occlusion", samples)
-        extras = [("alive", alive, None, (torch.uint8,)), ("counts", counts, None, words), ("seeds_out", seeds_out, None, words)]
+        extras = self._item_extras(alive, counts, seeds_out)
 
         def run(ptrs, n, cnt, res):
             d = abi.AoDesc()
@@ -866,7 +874,7 @@ class Context:
         import torch
         records, words = (torch.float32, torch.int32), (torch.int32, torch.uint32)
         samples = self._sky_samples("sky_lighting", samples)
-        extras = [("alive", alive, None, (torch.uint8,)), ("counts", counts, None, words), ("seeds_out", seeds_out, None, words)]
+        extras = self._item_extras(alive, counts, seeds_out)
 
         def run(ptrs, n, cnt, res):
             d = abi.SkyDesc()
@@ -923,7 +931,7 @@ class Context:
         samples = self._sky_samples("sky_lighting_mis", samples)
         mat, _ = self._bsdf_mode("sky_lighting_mis", mat_index, False)
         techniques = self._sky_techniques("sky_lighting_mis", techniques)
-        extras = [("alive", alive, None, (torch.uint8,)), ("counts", counts, None, words), ("seeds_out", seeds_out, None, words)]
+        extras = self._item_extras(alive, counts, seeds_out)
 
         def run(ptrs, n, cnt, res):
             d = abi.SkyMisDesc()
@@ -1805,6 +1813,13 @@ class FramePipeline:
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (hits, count, res))
         return res
 
+    def _pass_channel(self, name):
+        """The (H, W, 4) float32 channel a lighting pass writes, allocated (zeros) on first use."""
+        if name not in self.channels:
+            with self.torch.cuda.device(self.dev):
+                self.channels[name] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
+        return self.channels[name]
+
     def ambient_occlusion(self, samples=1, radius=None):
         """The reference's AmbientOcclusionPass on this pipeline's G-buffer as it stands (render_frame, or a gbuffer_execute
         of the caller's, fills it) and stream: Context.ao_execute with the pass's frame counter (from 0, one per call:
@@ -1820,10 +1835,7 @@ class FramePipeline:
             radius = self._ao_radius
         p.radius = float(radius)
         p.minT, p.frameCount = self.min_t, self.ao_frame & 0xFFFFFFFF
-        if AO_CHANNEL not in self.channels:
-            with self.torch.cuda.device(self.dev):
-                self.channels[AO_CHANNEL] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
-        out = self.channels[AO_CHANNEL]
+        out = self._pass_channel(AO_CHANNEL)
         self.ctx.ao_execute(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
         self.ao_frame += 1
         self.last_ao_params = p
@@ -1852,10 +1864,7 @@ class FramePipeline:
             p.matIndex, p.techniques = mat_index, abi.SKY_MIS_TABLE | abi.SKY_MIS_BSDF
         if self.ctx._env_prepared != self.ctx._env_serial:
             self.ctx.env_prepare(self._stream_ptr())
-        if SKY_CHANNEL not in self.channels:
-            with self.torch.cuda.device(self.dev):
-                self.channels[SKY_CHANNEL] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
-        out = self.channels[SKY_CHANNEL]
+        out = self._pass_channel(SKY_CHANNEL)
         (self.ctx.sky_mis_execute if mis else self.ctx.sky_execute)(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
         self.sky_frame += 1
         self.last_sky_params = p
@@ -1871,10 +1880,7 @@ class FramePipeline:
         p = abi.GiParams()
         p.flags = (abi.GI_INDIRECT if indirect else 0) | (0 if cosine else abi.GI_UNIFORM)
         p.minT, p.frameCount = self.min_t, self.gi_frame & 0xFFFFFFFF
-        if GI_CHANNEL not in self.channels:
-            with self.torch.cuda.device(self.dev):
-                self.channels[GI_CHANNEL] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
-        out = self.channels[GI_CHANNEL]
+        out = self._pass_channel(GI_CHANNEL)
         self.ctx.gi_execute(p, self.gb, C.c_void_p(out.data_ptr()), self._stream_ptr())
         self.gi_frame += 1
         self.last_gi_params = p
@@ -1888,10 +1894,7 @@ class FramePipeline:
         writes its own rows), also in ``channels``; ``last_direct_params`` keeps the abi.DirectParams used."""
         if not isinstance(use_hints, bool):
             raise BdptError(f"direct_lighting: use_hints must be a bool, not {use_hints!r}")
-        if DIRECT_CHANNEL not in self.channels:
-            with self.torch.cuda.device(self.dev):
-                self.channels[DIRECT_CHANNEL] = self.torch.zeros(self.H, self.W, 4, dtype=self.torch.float32, device=self.dev)
-        out = self.channels[DIRECT_CHANNEL]
+        out = self._pass_channel(DIRECT_CHANNEL)
         self.last_direct_params = self.ctx.direct_execute(self.gb, out, min_t=self.min_t, use_hints=use_hints, stream=self._stream_ptr())
         return out
 

@@ -16,10 +16,12 @@
 // memory traffic: every output word has one writer, whatever the order the lanes run in.  Dead items never take a
 // slot: their outputs are written at fetch.  Across the traversal a lane keeps its item, k, count, the RNG state and
 // N; the origin lives in the traversal state (TravState::o).  BDPT_AO_RELOAD_N re-reads N from the record at every
-// regeneration instead (DESIGN.md "Ambient occlusion" has both resource usages and timings).
+// regeneration instead (DESIGN.md "Ambient occlusion" has both resource usages and timings).  The item itself, a record
+// or a G-buffer pixel, is read through device_item_source.hpp.
 #include "kernels.h"
 
 #include "device_item_loop.hpp"
+#include "device_item_source.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_scene.hpp"
@@ -46,39 +48,13 @@ namespace bdpt {
 #define BDPT_AO_WAVES_PER_EU 5
 #endif
 
-enum : int { AO_SRC_SURFACES = 0, AO_SRC_GBUFFER = 1 };
-
 namespace {
-
-// item `i`: whether it is alive, its position and its normal (only N with `onlyN`)
-template <int SRC>
-__device__ __forceinline__ bool aoLoad(const AoDev& A, uint32_t i, bool onlyN, f3& pos, f3& N) {
-  if (SRC == AO_SRC_SURFACES) {
-    const float4* r = A.surf + (size_t)i * 6;
-    const float4 q1 = r[1];
-    N = mk(q1.x, q1.y, q1.z);
-    if (onlyN) return true;
-    if (A.alive && A.alive[i] == 0) return false;
-    if (__float_as_int(r[5].w) < 0) return false;
-    const float4 q0 = r[0];
-    pos = mk(q0.x, q0.y, q0.z);
-    return true;
-  } else {
-    const uint32_t fp = A.pix[i];
-    const uint2 raw = reinterpret_cast<const uint2*>(A.gbNormal)[fp];  // half4: N.xyz, distance
-    N = mk(f16_to_f32((uint16_t)(raw.x & 0xffffu)), f16_to_f32((uint16_t)(raw.x >> 16)), f16_to_f32((uint16_t)(raw.y & 0xffffu)));
-    if (onlyN) return true;
-    const float4 wp = A.gbPosition[fp];
-    pos = mk(wp.x, wp.y, wp.z);
-    return wp.w != 0.0f;  // aoTracing.rt.hlsl:91 (the background branch otherwise)
-  }
-}
 
 // the outputs of item `i`: ao = count / S, correctly rounded (aoTracing.rt.hlsl:121)
 template <int SRC>
 __device__ __forceinline__ void aoStore(const AoDev& A, uint32_t i, uint32_t count, uint32_t seed) {
   const float ao = (float)count / (float)A.samples;
-  if (SRC == AO_SRC_SURFACES) {
+  if (SRC == ITEM_SRC_SURFACES) {
     A.ao[i] = ao;
     if (A.counts) A.counts[i] = count;
     if (A.seedsOut) A.seedsOut[i] = seed;
@@ -131,10 +107,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_AO_W
         const uint32_t rank = (uint32_t)__popcll(idleMask & ((1ull << lane) - 1ull));
         if (!has && rank < take) {
           rid = chunkPos + rank;
-          // the item's RNG state: the caller's, or the pass's initRand(pixel, frameCount, 16) (aoTracing.rt.hlsl:82)
-          seed = (SRC == AO_SRC_SURFACES) ? A.seeds[rid] : initRand(A.pix[rid], A.frameCount);
-          f3 pos = mk(0), N = mk(0);
-          if (!aoLoad<SRC>(A, rid, false, pos, N)) {
+          seed = itemSeed<SRC>(A, rid);
+          f3 pos = mk(0);
+          const f3 N = itemNormal<SRC>(A, rid);
+          if (!itemAlive<SRC>(A, rid, pos)) {
             aoStore<SRC>(A, rid, A.samples, seed);  // the background branch: ao = 1, no draw; the lane stays idle
           } else {
             k = 0;
@@ -192,8 +168,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_AO_W
       k++;
       if (k < A.samples) {
 #if BDPT_AO_RELOAD_N
-        f3 pos = mk(0), N = mk(0);
-        aoLoad<SRC>(A, rid, true, pos, N);
+        const f3 N = itemNormal<SRC>(A, rid);
 #else
         const f3 N = keptN;
 #endif
@@ -212,7 +187,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_AO_W
 void launchAo(const SceneDev& S, const AoDev& A, bool gbuffer, unsigned long long* cursor, LaunchGrids& G, int numCUs, hipStream_t st) {
   if (!A.range.cap) return;
   withFlag(gbuffer, [&](auto GB) {
-    launchPersistent(ao_kernel<GB ? AO_SRC_GBUFFER : AO_SRC_SURFACES>, G.ao[GB ? 1 : 0], A.range.cap, numCUs, st, S, A, cursor);
+    launchPersistent(ao_kernel<GB ? ITEM_SRC_GBUFFER : ITEM_SRC_SURFACES>, G.ao[GB ? 1 : 0], A.range.cap, numCUs, st, S, A, cursor);
   });
 }
 

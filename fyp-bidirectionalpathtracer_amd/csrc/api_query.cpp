@@ -7,6 +7,7 @@
 // (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
 // first use of the emitter table), so all can be captured into a hipGraph.
 #include <cstddef>
+#include <initializer_list>
 #include <string>
 
 #include "api_common.hpp"
@@ -45,6 +46,49 @@ int enqueueQuery(bdpt_ctx* c, void* stream, Launch&& launch) {
 
 const float4* f4(const void* p) { return reinterpret_cast<const float4*>(p); }
 float4* f4(void* p) { return reinterpret_cast<float4*>(p); }
+
+// What the five fused lighting calls share (ao, gi, direct, sky, sky_mis; the fields are device_item_source.hpp's).
+int needFrame(bdpt_ctx* c, const char* what) {
+  return c->frame.have ? BDPT_OK : refuse(c, BDPT_E_STATE, what, "no size (bdpt_resize first)");
+}
+// The pointers of an *_execute call: worldPosition, worldNormal, `out`, and the other half channels the call reads.
+int checkGbuffer(bdpt_ctx* c, const char* what, const bdpt_gbuffer* gb, const float* out, bool diffuse, bool specRough) {
+  if (aligned(gb->worldPosition, 16) && aligned(gb->worldNormal, 8) && (!diffuse || aligned(gb->materialDiffuse, 8)) &&
+      (!specRough || aligned(gb->materialSpecRough, 8)) && aligned(out, 16))
+    return BDPT_OK;
+  const std::string why = std::string("worldPosition, worldNormal, ") + (diffuse ? "materialDiffuse, " : "") +
+                          (specRough ? "materialSpecRough, " : "") + "or out missing or not aligned (16 bytes; the half channels 8)";
+  return refuse(c, BDPT_E_INVALID, what, why.c_str());
+}
+// The pointers of a *_query call, each with its alignment (records and float4 results 16 bytes, words 4); an optional one
+// may be null.  `names`: how the refusal lists them.
+struct PtrArg { const void* p; uintptr_t align; bool optional = false; };
+int checkRecords(bdpt_ctx* c, const char* what, const char* names, std::initializer_list<PtrArg> ptrs) {
+  bool ok = true;
+  for (const PtrArg& a : ptrs) ok = ok && ((a.optional && !a.p) || aligned(a.p, a.align));
+  if (ok) return BDPT_OK;
+  return refuse(c, BDPT_E_INVALID, what, (std::string(names) + " missing or not aligned (records 16 bytes, words 4)").c_str());
+}
+// The common fields of AoDev, GiDev, DirectDev, SkyDev or SkyMisDev: from a query descriptor (SEEDED: it has RNG states) ...
+template <bool SEEDED, class Dev, class Desc>
+void fillRecords(Dev& Q, const Desc* d) {
+  Q.surf = f4(d->surfaces);
+  Q.alive = d->alive;
+  Q.range = {d->num, d->numDevice, d->minT};
+  if constexpr (SEEDED) {
+    Q.seeds = d->seeds;
+    Q.seedsOut = d->seedsOut;
+  }
+}
+// ... and from the tile's G-buffer pixels
+template <class Dev>
+void fillGbuffer(Dev& Q, const bdpt_ctx* c, const bdpt_gbuffer* gb, float* out, float minT) {
+  Q.gbPosition = f4(gb->worldPosition);
+  Q.gbNormal = gb->worldNormal;
+  Q.pix = c->frame.P.pix;
+  Q.out = f4(out);
+  Q.range = {c->frame.P.Np, nullptr, minT};
+}
 
 }  // namespace
 
@@ -249,18 +293,14 @@ int bdpt_ao_query(bdpt_ctx* c, const bdpt_ao_desc* d, void* stream) {
   if (!d->samples || d->samples > BDPT_AO_MAX_SAMPLES || d->flags || d->reserved)
     return refuse(c, BDPT_E_INVALID, "ao_query", "samples outside 1 .. BDPT_AO_MAX_SAMPLES, or non-zero flags or reserved");
   if (!d->num) return BDPT_OK;
-  if (!aligned(d->surfaces, 16) || !aligned(d->seeds, 4) || !aligned(d->ao, 4) || (d->counts && !aligned(d->counts, 4)) ||
-      (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
-    return refuse(c, BDPT_E_INVALID, "ao_query", "surfaces, seeds, ao, counts, seedsOut or numDevice missing or not aligned (records 16 bytes, words 4)");
+  if (int rc = checkRecords(c, "ao_query", "surfaces, seeds, ao, counts, seedsOut or numDevice",
+                            {{d->surfaces, 16}, {d->seeds, 4}, {d->ao, 4}, {d->counts, 4, true}, {d->seedsOut, 4, true}, {d->numDevice, 4, true}}))
+    return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     AoDev A{};
-    A.surf = f4(d->surfaces);
-    A.seeds = d->seeds;
-    A.alive = d->alive;
+    fillRecords<true>(A, d);
     A.ao = d->ao;
     A.counts = d->counts;
-    A.seedsOut = d->seedsOut;
-    A.range = {d->num, d->numDevice, d->minT};
     A.radius = d->radius;
     A.samples = d->samples;
     launchAo(c->scene.S, A, false, c->rayCursor, c->grids, c->numCUs, st);
@@ -270,18 +310,13 @@ int bdpt_ao_query(bdpt_ctx* c, const bdpt_ao_desc* d, void* stream) {
 int bdpt_ao_execute(bdpt_ctx* c, const bdpt_ao_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
   if (!c || !p || !gb) return BDPT_E_INVALID;
   if (int rc = needScene(c, "ao_execute")) return rc;
-  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "ao_execute", "no size (bdpt_resize first)");
+  if (int rc = needFrame(c, "ao_execute")) return rc;
   if (!p->samples || p->samples > BDPT_AO_MAX_SAMPLES || p->reserved)
     return refuse(c, BDPT_E_INVALID, "ao_execute", "samples outside 1 .. BDPT_AO_MAX_SAMPLES, or non-zero reserved");
-  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(out, 16))
-    return refuse(c, BDPT_E_INVALID, "ao_execute", "worldPosition, worldNormal or out missing or not aligned (16 bytes; worldNormal 8)");
+  if (int rc = checkGbuffer(c, "ao_execute", gb, out, false, false)) return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     AoDev A{};
-    A.gbPosition = f4(gb->worldPosition);
-    A.gbNormal = gb->worldNormal;
-    A.pix = c->frame.P.pix;
-    A.out = f4(out);
-    A.range = {c->frame.P.Np, nullptr, p->minT};
+    fillGbuffer(A, c, gb, out, p->minT);
     A.radius = p->radius;
     A.samples = p->samples;
     A.frameCount = p->frameCount;
@@ -307,20 +342,16 @@ int bdpt_gi_query(bdpt_ctx* c, const bdpt_gi_desc* d, void* stream) {
   if ((d->flags & ~(BDPT_GI_INDIRECT | BDPT_GI_UNIFORM | BDPT_GI_SHADE_FROM_VIEW)) || (d->shadeFlags & ~BDPT_SHADE_NORMAL_MAP) || d->reserved)
     return refuse(c, BDPT_E_INVALID, "gi_query", "unknown flags or shadeFlags, or non-zero reserved");
   if (!d->num) return BDPT_OK;
-  if (!aligned(d->surfaces, 16) || !aligned(d->seeds, 4) || !aligned(d->color, 16) || (d->hits && !aligned(d->hits, 16)) ||
-      (d->status && !aligned(d->status, 4)) || (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
-    return refuse(c, BDPT_E_INVALID, "gi_query",
-                  "surfaces, seeds, color, hits, status, seedsOut or numDevice missing or not aligned (records 16 bytes, words 4)");
+  if (int rc = checkRecords(c, "gi_query", "surfaces, seeds, color, hits, status, seedsOut or numDevice",
+                            {{d->surfaces, 16}, {d->seeds, 4}, {d->color, 16}, {d->hits, 16, true}, {d->status, 4, true},
+                             {d->seedsOut, 4, true}, {d->numDevice, 4, true}}))
+    return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     GiDev Q{};
-    Q.surf = f4(d->surfaces);
-    Q.seeds = d->seeds;
-    Q.alive = d->alive;
+    fillRecords<true>(Q, d);
     Q.color = f4(d->color);
     Q.hits = f4(d->hits);
     Q.status = d->status;
-    Q.seedsOut = d->seedsOut;
-    Q.range = {d->num, d->numDevice, d->minT};
     Q.flags = d->flags;
     for (int k = 0; k < 3; k++) Q.viewPos[k] = d->viewPos[k];
     giEnvironment(c, Q);
@@ -331,21 +362,15 @@ int bdpt_gi_query(bdpt_ctx* c, const bdpt_gi_desc* d, void* stream) {
 int bdpt_gi_execute(bdpt_ctx* c, const bdpt_gi_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
   if (!c || !p || !gb) return BDPT_E_INVALID;
   if (int rc = needScene(c, "gi_execute")) return rc;
-  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "gi_execute", "no size (bdpt_resize first)");
+  if (int rc = needFrame(c, "gi_execute")) return rc;
   if (int rc = needCamera(c, "gi_execute")) return rc;
   if ((p->flags & ~(BDPT_GI_INDIRECT | BDPT_GI_UNIFORM)) || p->reserved)
     return refuse(c, BDPT_E_INVALID, "gi_execute", "flags other than BDPT_GI_INDIRECT | BDPT_GI_UNIFORM, or non-zero reserved");
-  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(gb->materialDiffuse, 8) || !aligned(out, 16))
-    return refuse(c, BDPT_E_INVALID, "gi_execute",
-                  "worldPosition, worldNormal, materialDiffuse or out missing or not aligned (16 bytes; the half channels 8)");
+  if (int rc = checkGbuffer(c, "gi_execute", gb, out, true, false)) return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     GiDev Q{};
-    Q.gbPosition = f4(gb->worldPosition);
-    Q.gbNormal = gb->worldNormal;
+    fillGbuffer(Q, c, gb, out, p->minT);
     Q.gbDiffuse = gb->materialDiffuse;
-    Q.pix = c->frame.P.pix;
-    Q.out = f4(out);
-    Q.range = {c->frame.P.Np, nullptr, p->minT};
     Q.flags = p->flags | BDPT_GI_SHADE_FROM_VIEW;  // prepareShadingData shades from gCamera.posW
     Q.frameCount = p->frameCount;
     for (int k = 0; k < 3; k++) Q.viewPos[k] = c->cam.posW[k];
@@ -363,18 +388,15 @@ int bdpt_direct_query(bdpt_ctx* c, const bdpt_direct_desc* d, void* stream) {
     return refuse(c, BDPT_E_INVALID, "direct_query",
                   "flags other than BDPT_DIRECT_USE_HINTS (the emitter table is not part of this call), or non-zero reserved");
   if (!d->num) return BDPT_OK;
-  if (!aligned(d->surfaces, 16) || !aligned(d->color, 16) || (d->visible && !aligned(d->visible, 4)) ||
-      (d->traced && !aligned(d->traced, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
-    return refuse(c, BDPT_E_INVALID, "direct_query",
-                  "surfaces, color, visible, traced or numDevice missing or not aligned (records 16 bytes, words 4)");
+  if (int rc = checkRecords(c, "direct_query", "surfaces, color, visible, traced or numDevice",
+                            {{d->surfaces, 16}, {d->color, 16}, {d->visible, 4, true}, {d->traced, 4, true}, {d->numDevice, 4, true}}))
+    return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     DirectDev Q{};
-    Q.surf = f4(d->surfaces);
-    Q.alive = d->alive;
+    fillRecords<false>(Q, d);
     Q.color = f4(d->color);
     Q.visible = d->visible;
     Q.traced = d->traced;
-    Q.range = {d->num, d->numDevice, d->minT};
     launchDirect(c->scene.S, Q, false, (d->flags & BDPT_DIRECT_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
@@ -382,24 +404,16 @@ int bdpt_direct_query(bdpt_ctx* c, const bdpt_direct_desc* d, void* stream) {
 int bdpt_direct_execute(bdpt_ctx* c, const bdpt_direct_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
   if (!c || !p || !gb) return BDPT_E_INVALID;
   if (int rc = needScene(c, "direct_execute")) return rc;
-  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "direct_execute", "no size (bdpt_resize first)");
+  if (int rc = needFrame(c, "direct_execute")) return rc;
   if ((p->flags & ~BDPT_DIRECT_USE_HINTS) || p->reserved[0] || p->reserved[1])
     return refuse(c, BDPT_E_INVALID, "direct_execute",
                   "flags other than BDPT_DIRECT_USE_HINTS (the emitter table is not part of this call), or non-zero reserved");
-  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(gb->materialDiffuse, 8) ||
-      !aligned(gb->materialSpecRough, 8) || !aligned(out, 16))
-    return refuse(c, BDPT_E_INVALID, "direct_execute",
-                  "worldPosition, worldNormal, materialDiffuse, materialSpecRough or out missing or not aligned (16 bytes; the half "
-                  "channels 8)");
+  if (int rc = checkGbuffer(c, "direct_execute", gb, out, true, true)) return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     DirectDev Q{};
-    Q.gbPosition = f4(gb->worldPosition);
-    Q.gbNormal = gb->worldNormal;
+    fillGbuffer(Q, c, gb, out, p->minT);
     Q.gbDiffuse = gb->materialDiffuse;
     Q.gbSpecRough = gb->materialSpecRough;
-    Q.pix = c->frame.P.pix;
-    Q.out = f4(out);
-    Q.range = {c->frame.P.Np, nullptr, p->minT};
     launchDirect(c->scene.S, Q, true, (p->flags & BDPT_DIRECT_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
@@ -456,20 +470,15 @@ int bdpt_sky_query(bdpt_ctx* c, const bdpt_sky_desc* d, void* stream) {
   if (!d->samples || d->samples > BDPT_SKY_MAX_SAMPLES || d->flags || d->reserved)
     return refuse(c, BDPT_E_INVALID, "sky_query", "samples outside 1 .. BDPT_SKY_MAX_SAMPLES, or non-zero flags or reserved");
   if (!d->num) return BDPT_OK;
-  if (!aligned(d->surfaces, 16) || !aligned(d->seeds, 4) || !aligned(d->color, 16) || (d->counts && !aligned(d->counts, 4)) ||
-      (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
-    return refuse(c, BDPT_E_INVALID, "sky_query",
-                  "surfaces, seeds, color, counts, seedsOut or numDevice missing or not aligned (records 16 bytes, words 4)");
+  if (int rc = checkRecords(c, "sky_query", "surfaces, seeds, color, counts, seedsOut or numDevice",
+                            {{d->surfaces, 16}, {d->seeds, 4}, {d->color, 16}, {d->counts, 4, true}, {d->seedsOut, 4, true}, {d->numDevice, 4, true}}))
+    return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     SkyDev Q{};
     Q.table = c->envTable.table;
-    Q.surf = f4(d->surfaces);
-    Q.seeds = d->seeds;
-    Q.alive = d->alive;
+    fillRecords<true>(Q, d);
     Q.color = f4(d->color);
     Q.counts = d->counts;
-    Q.seedsOut = d->seedsOut;
-    Q.range = {d->num, d->numDevice, d->minT};
     Q.clampUpper = d->clampUpper;
     Q.samples = d->samples;
     launchSky(c->scene.S, Q, false, c->rayCursor, c->grids, c->numCUs, st);
@@ -479,22 +488,16 @@ int bdpt_sky_query(bdpt_ctx* c, const bdpt_sky_desc* d, void* stream) {
 int bdpt_sky_execute(bdpt_ctx* c, const bdpt_sky_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
   if (!c || !p || !gb) return BDPT_E_INVALID;
   if (int rc = needScene(c, "sky_execute")) return rc;
-  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "sky_execute", "no size (bdpt_resize first)");
+  if (int rc = needFrame(c, "sky_execute")) return rc;
   if (int rc = needEnvTable(c, "sky_execute")) return rc;
   if (!p->samples || p->samples > BDPT_SKY_MAX_SAMPLES || p->reserved)
     return refuse(c, BDPT_E_INVALID, "sky_execute", "samples outside 1 .. BDPT_SKY_MAX_SAMPLES, or non-zero reserved");
-  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(gb->materialDiffuse, 8) || !aligned(out, 16))
-    return refuse(c, BDPT_E_INVALID, "sky_execute",
-                  "worldPosition, worldNormal, materialDiffuse or out missing or not aligned (16 bytes; the half channels 8)");
+  if (int rc = checkGbuffer(c, "sky_execute", gb, out, true, false)) return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     SkyDev Q{};
     Q.table = c->envTable.table;
-    Q.gbPosition = f4(gb->worldPosition);
-    Q.gbNormal = gb->worldNormal;
+    fillGbuffer(Q, c, gb, out, p->minT);
     Q.gbDiffuse = gb->materialDiffuse;
-    Q.pix = c->frame.P.pix;
-    Q.out = f4(out);
-    Q.range = {c->frame.P.Np, nullptr, p->minT};
     Q.clampUpper = p->clampUpper;
     Q.samples = p->samples;
     Q.frameCount = p->frameCount;
@@ -532,20 +535,15 @@ int bdpt_sky_mis_query(bdpt_ctx* c, const bdpt_sky_mis_desc* d, void* stream) {
     return refuse(c, BDPT_E_INVALID, "sky_mis_query",
                   "samples outside 1 .. BDPT_SKY_MAX_SAMPLES, matIndex > 1, techniques outside 1 .. 3, or non-zero flags or reserved");
   if (!d->num) return BDPT_OK;
-  if (!aligned(d->surfaces, 16) || !aligned(d->seeds, 4) || !aligned(d->color, 16) || (d->counts && !aligned(d->counts, 4)) ||
-      (d->seedsOut && !aligned(d->seedsOut, 4)) || (d->numDevice && !aligned(d->numDevice, 4)))
-    return refuse(c, BDPT_E_INVALID, "sky_mis_query",
-                  "surfaces, seeds, color, counts, seedsOut or numDevice missing or not aligned (records 16 bytes, words 4)");
+  if (int rc = checkRecords(c, "sky_mis_query", "surfaces, seeds, color, counts, seedsOut or numDevice",
+                            {{d->surfaces, 16}, {d->seeds, 4}, {d->color, 16}, {d->counts, 4, true}, {d->seedsOut, 4, true}, {d->numDevice, 4, true}}))
+    return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     SkyMisDev Q{};
     Q.table = c->envTable.table;
-    Q.surf = f4(d->surfaces);
-    Q.seeds = d->seeds;
-    Q.alive = d->alive;
+    fillRecords<true>(Q, d);
     Q.color = f4(d->color);
     Q.counts = d->counts;
-    Q.seedsOut = d->seedsOut;
-    Q.range = {d->num, d->numDevice, d->minT};
     Q.clampUpper = d->clampUpper;
     Q.samples = d->samples;
     Q.techniques = d->techniques;
@@ -556,7 +554,7 @@ int bdpt_sky_mis_query(bdpt_ctx* c, const bdpt_sky_mis_desc* d, void* stream) {
 int bdpt_sky_mis_execute(bdpt_ctx* c, const bdpt_sky_mis_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
   if (!c || !p || !gb) return BDPT_E_INVALID;
   if (int rc = needScene(c, "sky_mis_execute")) return rc;
-  if (!c->frame.have) return refuse(c, BDPT_E_STATE, "sky_mis_execute", "no size (bdpt_resize first)");
+  if (int rc = needFrame(c, "sky_mis_execute")) return rc;
   if (int rc = needEnvTable(c, "sky_mis_execute")) return rc;
   const bool ggx = p->matIndex == 0;  // V comes from the camera
   if (ggx)
@@ -564,21 +562,13 @@ int bdpt_sky_mis_execute(bdpt_ctx* c, const bdpt_sky_mis_params* p, const bdpt_g
   if (!skyMisModeOk(p->samples, p->matIndex, p->techniques) || p->reserved[0] || p->reserved[1])
     return refuse(c, BDPT_E_INVALID, "sky_mis_execute",
                   "samples outside 1 .. BDPT_SKY_MAX_SAMPLES, matIndex > 1, techniques outside 1 .. 3, or non-zero reserved");
-  if (!aligned(gb->worldPosition, 16) || !aligned(gb->worldNormal, 8) || !aligned(gb->materialDiffuse, 8) ||
-      (ggx && !aligned(gb->materialSpecRough, 8)) || !aligned(out, 16))
-    return refuse(c, BDPT_E_INVALID, "sky_mis_execute",
-                  "worldPosition, worldNormal, materialDiffuse, materialSpecRough (matIndex 0) or out missing or not aligned (16 bytes; "
-                  "the half channels 8)");
+  if (int rc = checkGbuffer(c, "sky_mis_execute", gb, out, true, ggx)) return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     SkyMisDev Q{};
     Q.table = c->envTable.table;
-    Q.gbPosition = f4(gb->worldPosition);
-    Q.gbNormal = gb->worldNormal;
+    fillGbuffer(Q, c, gb, out, p->minT);
     Q.gbDiffuse = gb->materialDiffuse;
     Q.gbSpecRough = gb->materialSpecRough;
-    Q.pix = c->frame.P.pix;
-    Q.out = f4(out);
-    Q.range = {c->frame.P.Np, nullptr, p->minT};
     if (ggx)
       for (int k = 0; k < 3; k++) Q.camPos[k] = c->cam.posW[k];
     Q.clampUpper = p->clampUpper;

@@ -23,9 +23,11 @@
 // Across a traversal a lane keeps its item, k, the two masks (one register), the answer, the sum, and with
 // BDPT_DIRECT_KEEP_TERM N, LdotN and I of the ray in flight; without it N is re-read from the record and getLightData runs
 // again for light k when the answer comes (same inputs, same bits).  The diffuse colour is read when the item retires.
+// The item itself, a record or a G-buffer pixel, is read and written through device_item_source.hpp.
 #include "kernels.h"
 
 #include "device_item_loop.hpp"
+#include "device_item_source.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_scene.hpp"
@@ -55,66 +57,30 @@ namespace bdpt {
 #define BDPT_DIRECT_WAVES_PER_EU 5
 #endif
 
-enum : int { DIRECT_SRC_SURFACES = 0, DIRECT_SRC_GBUFFER = 1 };
-
 namespace {
-
-__device__ __forceinline__ f3 directHalf3(const uint16_t* base, uint32_t at) {  // xyz of a half4 channel, as gi.hip decodes one
-  const uint2 raw = reinterpret_cast<const uint2*>(base)[at];
-  return mk(f16_to_f32((uint16_t)(raw.x & 0xffffu)), f16_to_f32((uint16_t)(raw.x >> 16)), f16_to_f32((uint16_t)(raw.y & 0xffffu)));
-}
 
 // item `i`: the colour the sum is multiplied by: diffuse, or specular where diffuse is (nearly) black
 // (lambertianPlusShadows.rt.hlsl:109-114)
 template <int SRC>
 __device__ __forceinline__ f3 directAlbedo(const DirectDev& Q, uint32_t i) {
-  f3 dif, spec;
-  if (SRC == DIRECT_SRC_SURFACES) {
-    const float4 q3 = Q.surf[(size_t)i * 6 + 3], q4 = Q.surf[(size_t)i * 6 + 4];
-    dif = mk(q3.x, q3.y, q3.z);
+  f3 dif = itemDiffuse<SRC>(Q, i), spec;
+  if (SRC == ITEM_SRC_SURFACES) {
+    const float4 q4 = Q.surf[(size_t)i * 6 + 4];
     spec = mk(q4.x, q4.y, q4.z);
   } else {
-    dif = directHalf3(Q.gbDiffuse, Q.pix[i]);
-    spec = directHalf3(Q.gbSpecRough, Q.pix[i]);
+    spec = itemHalf3(Q.gbSpecRough, Q.pix[i]);
   }
   if (dot(dif, dif) < 0.00001f) dif = spec;
   return dif;
-}
-template <int SRC>
-__device__ __forceinline__ f3 directNormal(const DirectDev& Q, uint32_t i) {
-  if (SRC == DIRECT_SRC_SURFACES) {
-    const float4 q1 = Q.surf[(size_t)i * 6 + 1];
-    return mk(q1.x, q1.y, q1.z);
-  }
-  return directHalf3(Q.gbNormal, Q.pix[i]);
-}
-// item `i`: whether it is alive, and then its position
-template <int SRC>
-__device__ __forceinline__ bool directLoad(const DirectDev& Q, uint32_t i, f3& pos) {
-  if (SRC == DIRECT_SRC_SURFACES) {
-    const float4* r = Q.surf + (size_t)i * 6;
-    if (Q.alive && Q.alive[i] == 0) return false;
-    if (__float_as_int(r[5].w) < 0) return false;
-    const float4 q0 = r[0];
-    pos = mk(q0.x, q0.y, q0.z);
-    return true;
-  } else {
-    const float4 wp = Q.gbPosition[Q.pix[i]];
-    pos = mk(wp.x, wp.y, wp.z);
-    return wp.w != 0.0f;  // lambertianPlusShadows.rt.hlsl:117 (the background branch otherwise)
-  }
 }
 
 // the outputs of item `i`; masks: bits 0-15 `visible`, bits 16-31 `traced`
 template <int SRC>
 __device__ __forceinline__ void directStore(const DirectDev& Q, uint32_t i, f3 color, uint32_t masks) {
-  const float4 c = make_float4(color.x, color.y, color.z, 1.0f);
-  if (SRC == DIRECT_SRC_SURFACES) {
-    Q.color[i] = c;
+  itemStoreColor<SRC>(Q, i, color);
+  if (SRC == ITEM_SRC_SURFACES) {
     if (Q.visible) Q.visible[i] = masks & 0xffffu;
     if (Q.traced) Q.traced[i] = masks >> 16;
-  } else {
-    Q.out[Q.pix[i]] = c;
   }
 }
 
@@ -144,7 +110,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_DIRE
   T.best.prim = -1;
   while (refill(F, cursor, lane, has, [&](uint32_t item) {
     f3 pos = mk(0);
-    if (!directLoad<SRC>(Q, item, pos)) {
+    if (!itemAlive<SRC>(Q, item, pos)) {
       directStore<SRC>(Q, item, directAlbedo<SRC>(Q, item), 0u);  // the background branch: (colour, 1); the lane stays idle
       return;
     }
@@ -154,7 +120,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_DIRE
     sum = mk(0);
     T.o = pos;  // the origin of every ray of the item
 #if BDPT_DIRECT_KEEP_TERM
-    keptN = directNormal<SRC>(Q, item);
+    keptN = itemNormal<SRC>(Q, item);
 #endif
     flying = false;
     answer = -1;
@@ -172,7 +138,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_DIRE
 #if BDPT_DIRECT_KEEP_TERM
       const f3 N = keptN;
 #else
-      const f3 N = directNormal<SRC>(Q, rid);
+      const f3 N = itemNormal<SRC>(Q, rid);
 #endif
       while (k < numLights) {
         const bdpt_light& lt = S.sc->lights[k];
@@ -229,7 +195,7 @@ void launchDirect(const SceneDev& S, const DirectDev& Q, bool gbuffer, bool hint
   if (!Q.range.cap) return;
   withFlag(gbuffer, [&](auto GB) {
     withFlag(hints, [&](auto HINTS) {
-      launchPersistent(direct_kernel<GB ? DIRECT_SRC_GBUFFER : DIRECT_SRC_SURFACES, HINTS>, G.direct[(GB ? 2 : 0) + (HINTS ? 1 : 0)],
+      launchPersistent(direct_kernel<GB ? ITEM_SRC_GBUFFER : ITEM_SRC_SURFACES, HINTS>, G.direct[(GB ? 2 : 0) + (HINTS ? 1 : 0)],
                        Q.range.cap, numCUs, st, S, Q, cursor);
     });
   });

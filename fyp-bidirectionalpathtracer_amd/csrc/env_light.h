@@ -278,20 +278,20 @@ struct EnvQueryDev {
 void launchEnvQuery(const EnvQueryDev& Q, bool evalMode, bool ggx, hipStream_t st);
 // sky.hip: bdpt_sky_query (items are bdpt_surface records) and bdpt_sky_execute (items are the tile's pixels, read from the
 // G-buffer).  `samples` table-sampled any-hit rays per alive item.
-struct SkyDev {
+struct SkyDev {  // fields without a comment: the item source (device_item_source.hpp)
   EnvTable table;
-  const float4* surf;         // query: bdpt_surface records (six float4 each; posW, N, diffuse and prim are read)
-  const uint32_t* seeds;      // query: one RNG state per item
-  const uint8_t* alive;       // query, optional: 0 = the item is dead
-  float4* color;              // query: (colour, 1) per item
+  const float4* surf;         // posW, N, diffuse and prim are read
+  const uint32_t* seeds;
+  const uint8_t* alive;
+  float4* color;
   uint32_t* counts;           // query, optional: traced and unoccluded samples per item
   uint32_t* seedsOut;         // query, optional: the state after 4 * samples draws (a dead item's: unchanged)
-  const float4* gbPosition;   // execute: WorldPosition of the full frame (w != 0: geometry)
-  const uint16_t* gbNormal;   // execute: WorldNormal (half4) of the full frame
-  const uint16_t* gbDiffuse;  // execute: MaterialDiffuse (half4) of the full frame
-  const uint32_t* pix;        // execute: the tile's pixels (PathBuf::pix); the seed is initRand(pix, frameCount)
-  float4* out;                // execute: full-frame RGBA32F, (colour, 1) at the tile's pixels
-  QueryRange range;           // execute: cap = the tile's pixel count, no device word
+  const float4* gbPosition;
+  const uint16_t* gbNormal;
+  const uint16_t* gbDiffuse;
+  const uint32_t* pix;
+  float4* out;
+  QueryRange range;
   float clampUpper;
   uint32_t samples;           // 1 .. 64
   uint32_t frameCount;        // execute
@@ -303,21 +303,21 @@ void launchSky(const SceneDev& S, const SkyDev& Q, bool gbuffer, unsigned long l
 void launchBsdfPdfQuery(const float4* surf, uint32_t cap, const uint32_t* count, bool ggx, const float4* dirs, float4* out, hipStream_t st);
 // sky_mis.hip: bdpt_sky_mis_query and bdpt_sky_mis_execute.  Per alive item and sample one table-sampled and one BSDF-sampled
 // any-hit ray (`techniques` bit 0 / bit 1), weighted by the balance heuristic when both are on.
-struct SkyMisDev {
+struct SkyMisDev {  // fields without a comment: the item source (device_item_source.hpp)
   EnvTable table;
-  const float4* surf;           // query: bdpt_surface records (posW, N, V, linearRoughness, diffuse, specular and prim are read)
-  const uint32_t* seeds;        // query: one RNG state per item
-  const uint8_t* alive;         // query, optional: 0 = the item is dead
-  float4* color;                // query: (colour, 1) per item
+  const float4* surf;           // posW, N, V, linearRoughness, diffuse, specular and prim are read
+  const uint32_t* seeds;
+  const uint8_t* alive;
+  float4* color;
   uint32_t* counts;             // query, optional: traced and unoccluded terms per item (0 .. 2 * samples)
   uint32_t* seedsOut;           // query, optional: the state after (4 | 3 | 7) * samples draws (a dead item's: unchanged)
-  const float4* gbPosition;     // execute: WorldPosition of the full frame (w != 0: geometry)
-  const uint16_t* gbNormal;     // execute: WorldNormal (half4) of the full frame
-  const uint16_t* gbDiffuse;    // execute: MaterialDiffuse (half4) of the full frame
-  const uint16_t* gbSpecRough;  // execute, GGX: MaterialSpecRough (half4): specular = rgb, rough = a * a
-  const uint32_t* pix;          // execute: the tile's pixels (PathBuf::pix); the seed is initRand(pix, frameCount)
-  float4* out;                  // execute: full-frame RGBA32F, (colour, 1) at the tile's pixels
-  QueryRange range;             // execute: cap = the tile's pixel count, no device word
+  const float4* gbPosition;
+  const uint16_t* gbNormal;
+  const uint16_t* gbDiffuse;
+  const uint16_t* gbSpecRough;  // GGX only: specular = rgb, rough = a * a
+  const uint32_t* pix;
+  float4* out;
+  QueryRange range;
   float camPos[3];              // execute, GGX: V = normalize(camPos - posW)
   float clampUpper;
   uint32_t samples;             // 1 .. 64

@@ -29,10 +29,12 @@
 //
 // Across traversals a lane keeps its item, its phase and status bits, the RNG state, NdotL, `direct` and `pend` (the value
 // the ray in flight gates); origin and direction live in the traversal state (TravState::o, ::d).  N is used up when the
-// bounce direction is drawn; diffuse is re-read from the record when the item retires.
+// bounce direction is drawn; diffuse is re-read from the record when the item retires.  The item itself, a record or a
+// G-buffer pixel, is read and written through device_item_source.hpp (itemLoad: position and normal in one body).
 #include "kernels.h"
 
 #include "device_item_loop.hpp"
+#include "device_item_source.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_scene.hpp"
@@ -63,57 +65,15 @@ namespace bdpt {
 #define BDPT_GI_RELOAD_DIFFUSE 1
 #endif
 
-enum : int { GI_SRC_SURFACES = 0, GI_SRC_GBUFFER = 1 };
-
 namespace {
-
-__device__ __forceinline__ void giHalf3(const uint16_t* base, uint32_t at, f3& v) {  // xyz of a half4 channel, as ao.hip decodes WorldNormal
-  const uint2 raw = reinterpret_cast<const uint2*>(base)[at];
-  v = mk(f16_to_f32((uint16_t)(raw.x & 0xffffu)), f16_to_f32((uint16_t)(raw.x >> 16)), f16_to_f32((uint16_t)(raw.y & 0xffffu)));
-}
-
-// item `i`: its diffuse colour
-template <int SRC>
-__device__ __forceinline__ f3 giDiffuse(const GiDev& Q, uint32_t i) {
-  f3 d;
-  if (SRC == GI_SRC_SURFACES) {
-    const float4 q3 = Q.surf[(size_t)i * 6 + 3];
-    d = mk(q3.x, q3.y, q3.z);
-  } else {
-    giHalf3(Q.gbDiffuse, Q.pix[i], d);
-  }
-  return d;
-}
-// item `i`: whether it is alive, and then its position and normal
-template <int SRC>
-__device__ __forceinline__ bool giLoad(const GiDev& Q, uint32_t i, f3& pos, f3& N) {
-  if (SRC == GI_SRC_SURFACES) {
-    const float4* r = Q.surf + (size_t)i * 6;
-    if (Q.alive && Q.alive[i] == 0) return false;
-    if (__float_as_int(r[5].w) < 0) return false;
-    const float4 q0 = r[0], q1 = r[1];
-    pos = mk(q0.x, q0.y, q0.z);
-    N = mk(q1.x, q1.y, q1.z);
-    return true;
-  } else {
-    const uint32_t fp = Q.pix[i];
-    const float4 wp = Q.gbPosition[fp];
-    pos = mk(wp.x, wp.y, wp.z);
-    giHalf3(Q.gbNormal, fp, N);
-    return wp.w != 0.0f;  // simpleDiffuseGI.rt.hlsl:152 (the background branch otherwise)
-  }
-}
 
 // the outputs of item `i`
 template <int SRC>
 __device__ __forceinline__ void giStore(const GiDev& Q, uint32_t i, f3 color, uint32_t status, uint32_t seed) {
-  const float4 c = make_float4(color.x, color.y, color.z, 1.0f);
-  if (SRC == GI_SRC_SURFACES) {
-    Q.color[i] = c;
+  itemStoreColor<SRC>(Q, i, color);
+  if (SRC == ITEM_SRC_SURFACES) {
     if (Q.status) Q.status[i] = status;
     if (Q.seedsOut) Q.seedsOut[i] = seed;
-  } else {
-    Q.out[Q.pix[i]] = c;
   }
 }
 // the bounce ray's bdpt_hit as trace_rays_kernel writes one; giStoreNoHit: there was no bounce ray
@@ -204,19 +164,18 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_GI_W
         const uint32_t rank = (uint32_t)__popcll(idleMask & ((1ull << lane) - 1ull));
         if (!has && rank < take) {
           rid = chunkPos + rank;
-          // the item's RNG state: the caller's, or the pass's initRand(pixel, frameCount, 16) (simpleDiffuseGI.rt.hlsl:149)
-          seed = (SRC == GI_SRC_SURFACES) ? Q.seeds[rid] : initRand(Q.pix[rid], Q.frameCount);
+          seed = itemSeed<SRC>(Q, rid);
           f3 pos = mk(0), N = mk(0);
-          if (!giLoad<SRC>(Q, rid, pos, N)) {
+          if (!itemLoad<SRC, true>(Q, rid, pos, N)) {
             // the background branch: the diffuse channel holds the colour, no draw; the lane stays idle
-            giStore<SRC>(Q, rid, giDiffuse<SRC>(Q, rid), 0u, seed);
+            giStore<SRC>(Q, rid, itemDiffuse<SRC>(Q, rid), 0u, seed);
             giStoreNoHit(Q, rid);
           } else {
             phase = 0;
             status = 0;
             f3 L;
             float dist;
-            const f3 dif = giDiffuse<SRC>(Q, rid);
+            const f3 dif = itemDiffuse<SRC>(Q, rid);
 #if !BDPT_GI_RELOAD_DIFFUSE
             keptDif = dif;
 #endif
@@ -278,7 +237,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_GI_W
       }
       if (retire) {
 #if BDPT_GI_RELOAD_DIFFUSE
-        const f3 dif = indirect ? giDiffuse<SRC>(Q, rid) : mk(0);
+        const f3 dif = indirect ? itemDiffuse<SRC>(Q, rid) : mk(0);
 #else
         const f3 dif = keptDif;
 #endif
@@ -310,11 +269,11 @@ void launchGi(const SceneDev& S, const GiDev& Q, bool gbuffer, bool normalMap, u
               hipStream_t st) {
   if (!Q.range.cap) return;
   if (gbuffer) {  // the pass: full prepareShadingData, so always with the normal map
-    launchPersistent(gi_kernel<GI_SRC_GBUFFER, true>, G.gi[2], Q.range.cap, numCUs, st, S, Q, cursor);
+    launchPersistent(gi_kernel<ITEM_SRC_GBUFFER, true>, G.gi[2], Q.range.cap, numCUs, st, S, Q, cursor);
     return;
   }
   withFlag(normalMap, [&](auto NMAP) {
-    launchPersistent(gi_kernel<GI_SRC_SURFACES, NMAP>, G.gi[NMAP ? 1 : 0], Q.range.cap, numCUs, st, S, Q, cursor);
+    launchPersistent(gi_kernel<ITEM_SRC_SURFACES, NMAP>, G.gi[NMAP ? 1 : 0], Q.range.cap, numCUs, st, S, Q, cursor);
   });
 }
 

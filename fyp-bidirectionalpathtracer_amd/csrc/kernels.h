@@ -409,18 +409,18 @@ void launchWalkQuery(const SceneDev& S, const WalkQueryDev& Q, bool ggx, bool fr
                      int numCUs, hipStream_t st);
 // ao.hip: bdpt_ao_query (items are bdpt_surface records) and bdpt_ao_execute (items are the tile's pixels, read from the
 // G-buffer).  `samples` any-hit rays per alive item from its position inside (range.minT, radius).
-struct AoDev {
-  const float4* surf;        // query: bdpt_surface records (six float4 each; posW, N and prim are read)
-  const uint32_t* seeds;     // query: one RNG state per item
-  const uint8_t* alive;      // query, optional: 0 = the item is dead
+struct AoDev {  // fields without a comment: the item source (device_item_source.hpp)
+  const float4* surf;        // posW, N and prim are read
+  const uint32_t* seeds;
+  const uint8_t* alive;
   float* ao;                 // query: count / samples per item
   uint32_t* counts;          // query, optional: unoccluded samples per item
   uint32_t* seedsOut;        // query, optional: the state after 2 * samples draws (a dead item's: unchanged)
-  const float4* gbPosition;  // execute: WorldPosition of the full frame (w != 0: geometry)
-  const uint16_t* gbNormal;  // execute: WorldNormal (half4) of the full frame
-  const uint32_t* pix;       // execute: the tile's pixels (PathBuf::pix); the seed is initRand(pix, frameCount)
-  float4* out;               // execute: full-frame RGBA32F, (ao, ao, ao, 1) at the tile's pixels
-  QueryRange range;          // execute: cap = the tile's pixel count, no device word
+  const float4* gbPosition;
+  const uint16_t* gbNormal;
+  const uint32_t* pix;
+  float4* out;               // execute: (ao, ao, ao, 1) at the tile's pixels
+  QueryRange range;
   float radius;              // tmax of the rays
   uint32_t samples;          // 1 .. 64
   uint32_t frameCount;       // execute
@@ -430,20 +430,20 @@ void launchAo(const SceneDev& S, const AoDev& A, bool gbuffer, unsigned long lon
 // gi.hip: bdpt_gi_query (items are bdpt_surface records) and bdpt_gi_execute (items are the tile's pixels, read from the
 // G-buffer).  Per alive item a direct any-hit ray, and with BDPT_GI_INDIRECT a closest-hit bounce ray and an any-hit ray
 // from its hit.
-struct GiDev {
-  const float4* surf;         // query: bdpt_surface records (six float4 each; posW, N, diffuse and prim are read)
-  const uint32_t* seeds;      // query: one RNG state per item
-  const uint8_t* alive;       // query, optional: 0 = the item is dead
-  float4* color;              // query: (colour, 1) per item
+struct GiDev {  // fields without a comment: the item source (device_item_source.hpp)
+  const float4* surf;         // posW, N, diffuse and prim are read
+  const uint32_t* seeds;
+  const uint8_t* alive;
+  float4* color;
   float4* hits;               // query, optional: the bounce ray's bdpt_hit
   uint32_t* status;           // query, optional: BDPT_GI_STATUS_*
   uint32_t* seedsOut;         // query, optional: the state after 1 or 3 draws (a dead item's: unchanged)
-  const float4* gbPosition;   // execute: WorldPosition of the full frame (w != 0: geometry)
-  const uint16_t* gbNormal;   // execute: WorldNormal (half4) of the full frame
-  const uint16_t* gbDiffuse;  // execute: MaterialDiffuse (half4) of the full frame
-  const uint32_t* pix;        // execute: the tile's pixels (PathBuf::pix); the seed is initRand(pix, frameCount)
-  float4* out;                // execute: full-frame RGBA32F, (colour, 1) at the tile's pixels
-  QueryRange range;           // execute: cap = the tile's pixel count, no device word
+  const float4* gbPosition;
+  const uint16_t* gbNormal;
+  const uint16_t* gbDiffuse;
+  const uint32_t* pix;
+  float4* out;
+  QueryRange range;
   uint32_t flags;             // BDPT_GI_INDIRECT | BDPT_GI_UNIFORM | BDPT_GI_SHADE_FROM_VIEW
   uint32_t frameCount;        // execute
   float viewPos[3];           // BDPT_GI_SHADE_FROM_VIEW: where the bounce hit is shaded from
@@ -456,19 +456,19 @@ void launchGi(const SceneDev& S, const GiDev& Q, bool gbuffer, bool normalMap, u
               hipStream_t st);
 // direct.hip: bdpt_direct_query (items are bdpt_surface records) and bdpt_direct_execute (items are the tile's pixels, read
 // from the G-buffer).  Per alive item and light of the scene at most one any-hit ray; no RNG state.
-struct DirectDev {
-  const float4* surf;           // query: bdpt_surface records (six float4 each; posW, N, diffuse, specular and prim are read)
-  const uint8_t* alive;         // query, optional: 0 = the item is dead
-  float4* color;                // query: (colour, 1) per item
+struct DirectDev {  // fields without a comment: the item source (device_item_source.hpp)
+  const float4* surf;           // posW, N, diffuse, specular and prim are read
+  const uint8_t* alive;
+  float4* color;
   uint32_t* visible;            // query, optional: bit k = light k's term was added with s_k = 1
   uint32_t* traced;             // query, optional: bit k = a ray or a hint test was spent on light k
-  const float4* gbPosition;     // execute: WorldPosition of the full frame (w != 0: geometry)
-  const uint16_t* gbNormal;     // execute: WorldNormal (half4) of the full frame
-  const uint16_t* gbDiffuse;    // execute: MaterialDiffuse (half4) of the full frame
-  const uint16_t* gbSpecRough;  // execute: MaterialSpecRough (half4) of the full frame
-  const uint32_t* pix;          // execute: the tile's pixels (PathBuf::pix)
-  float4* out;                  // execute: full-frame RGBA32F, (colour, 1) at the tile's pixels
-  QueryRange range;             // execute: cap = the tile's pixel count, no device word
+  const float4* gbPosition;
+  const uint16_t* gbNormal;
+  const uint16_t* gbDiffuse;
+  const uint16_t* gbSpecRough;
+  const uint32_t* pix;
+  float4* out;
+  QueryRange range;
 };
 // `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
 void launchDirect(const SceneDev& S, const DirectDev& Q, bool gbuffer, bool hints, unsigned long long* cursor, LaunchGrids& G, int numCUs,

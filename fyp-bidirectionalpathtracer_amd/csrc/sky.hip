@@ -12,9 +12,11 @@
 // atomics, every word has one writer, whatever the order the lanes run in.  Dead items never take a slot: their outputs
 // are written at fetch.  Across the traversal a lane keeps its item, k, count, the RNG state, the sum and the term its
 // ray gates; N and diffuse are re-read from the record when it regenerates, the origin lives in the traversal state.
+// The item itself, a record or a G-buffer pixel, is read and written through device_item_source.hpp.
 #include "kernels.h"
 
 #include "device_item_loop.hpp"
+#include "device_item_source.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_scene.hpp"
@@ -29,55 +31,15 @@ namespace bdpt {
 #define BDPT_SKY_WAVES_PER_EU 4
 #endif
 
-enum : int { SKY_SRC_SURFACES = 0, SKY_SRC_GBUFFER = 1 };
-
 namespace {
 
-__device__ __forceinline__ f3 skyHalf3(const uint16_t* base, uint32_t at) {  // xyz of a half4 channel, as gi.hip's giHalf3
-  const uint2 raw = reinterpret_cast<const uint2*>(base)[at];
-  return mk(f16_to_f32((uint16_t)(raw.x & 0xffffu)), f16_to_f32((uint16_t)(raw.x >> 16)), f16_to_f32((uint16_t)(raw.y & 0xffffu)));
-}
-
-// item `i`: its normal and diffuse colour
-template <int SRC>
-__device__ __forceinline__ void skyShading(const SkyDev& Q, uint32_t i, f3& N, f3& dif) {
-  if (SRC == SKY_SRC_SURFACES) {
-    const float4* r = Q.surf + (size_t)i * 6;
-    const float4 q1 = r[1], q3 = r[3];
-    N = mk(q1.x, q1.y, q1.z);
-    dif = mk(q3.x, q3.y, q3.z);
-  } else {
-    const uint32_t fp = Q.pix[i];
-    N = skyHalf3(Q.gbNormal, fp);
-    dif = skyHalf3(Q.gbDiffuse, fp);
-  }
-}
-// item `i`: whether it is alive, and then its position
-template <int SRC>
-__device__ __forceinline__ bool skyAlive(const SkyDev& Q, uint32_t i, f3& pos) {
-  if (SRC == SKY_SRC_SURFACES) {
-    const float4* r = Q.surf + (size_t)i * 6;
-    if (Q.alive && Q.alive[i] == 0) return false;
-    if (__float_as_int(r[5].w) < 0) return false;
-    const float4 q0 = r[0];
-    pos = mk(q0.x, q0.y, q0.z);
-    return true;
-  } else {
-    const float4 wp = Q.gbPosition[Q.pix[i]];
-    pos = mk(wp.x, wp.y, wp.z);
-    return wp.w != 0.0f;
-  }
-}
 // the outputs of item `i`
 template <int SRC>
 __device__ __forceinline__ void skyStore(const SkyDev& Q, uint32_t i, f3 color, uint32_t count, uint32_t seed) {
-  const float4 c = make_float4(color.x, color.y, color.z, 1.0f);
-  if (SRC == SKY_SRC_SURFACES) {
-    Q.color[i] = c;
+  itemStoreColor<SRC>(Q, i, color);
+  if (SRC == ITEM_SRC_SURFACES) {
     if (Q.counts) Q.counts[i] = count;
     if (Q.seedsOut) Q.seedsOut[i] = seed;
-  } else {
-    Q.out[Q.pix[i]] = c;
   }
 }
 
@@ -85,8 +47,7 @@ __device__ __forceinline__ void skyStore(const SkyDev& Q, uint32_t i, f3 color, 
 // other one starts its ray from `pos` and is kept in `pend`.  Returns whether a ray is in flight; false: k == samples.
 template <int SRC>
 __device__ __forceinline__ bool skyNext(const SkyDev& Q, uint32_t i, f3 pos, uint32_t& k, uint32_t& seed, f3& sum, f3& pend, TravState& T) {
-  f3 N, dif;
-  skyShading<SRC>(Q, i, N, dif);
+  const f3 N = itemNormal<SRC>(Q, i), dif = itemDiffuse<SRC>(Q, i);
   while (k < Q.samples) {
     k++;
     const EnvSample e = envSample(Q.table, seed);
@@ -125,13 +86,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_SKY_
   T.cur = kDone;
   while (refill(F, cursor, lane, has, [&](uint32_t item) {
     rid = item;
-    // the item's RNG state: the caller's, or the pass's initRand(pixel, frameCount, 16)
-    seed = (SRC == SKY_SRC_SURFACES) ? Q.seeds[rid] : initRand(Q.pix[rid], Q.frameCount);
+    seed = itemSeed<SRC>(Q, rid);
     f3 pos = mk(0);
-    if (!skyAlive<SRC>(Q, rid, pos)) {
-      f3 N, dif;
-      skyShading<SRC>(Q, rid, N, dif);
-      skyStore<SRC>(Q, rid, dif, 0u, seed);  // the background: the diffuse channel holds the colour, no draw; the lane stays idle
+    if (!itemAlive<SRC>(Q, rid, pos)) {
+      skyStore<SRC>(Q, rid, itemDiffuse<SRC>(Q, rid), 0u, seed);  // the background: the diffuse channel holds the colour, no draw; the lane stays idle
     } else {
       k = 0;
       count = 0;
@@ -162,7 +120,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_SKY_
 void launchSky(const SceneDev& S, const SkyDev& Q, bool gbuffer, unsigned long long* cursor, LaunchGrids& G, int numCUs, hipStream_t st) {
   if (!Q.range.cap) return;
   withFlag(gbuffer, [&](auto GB) {
-    launchPersistent(sky_kernel<GB ? SKY_SRC_GBUFFER : SKY_SRC_SURFACES>, G.sky[GB ? 1 : 0], Q.range.cap, numCUs, st, S, Q, cursor);
+    launchPersistent(sky_kernel<GB ? ITEM_SRC_GBUFFER : ITEM_SRC_SURFACES>, G.sky[GB ? 1 : 0], Q.range.cap, numCUs, st, S, Q, cursor);
   });
 }
 

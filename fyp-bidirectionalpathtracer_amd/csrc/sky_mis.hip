@@ -13,11 +13,13 @@
 // After the last term the lane retires with one store per output: no output atomics, every word has one writer.  Dead
 // items never take a slot: their outputs are written at fetch.  Across the traversal a lane keeps its item, the term index,
 // count, the RNG state, the sum and the term its ray gates; N, V, the colours and the roughness are re-read when it
-// regenerates, the origin lives in the traversal state.
+// regenerates, the origin lives in the traversal state.  The item itself, a record or a G-buffer pixel, is read and
+// written through device_item_source.hpp; the GGX reads (V, specular, roughness) are this file's.
 #include "kernels.h"
 
 #include "device_bsdf_pdf.hpp"
 #include "device_item_loop.hpp"
+#include "device_item_source.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_scene.hpp"
@@ -40,8 +42,6 @@ namespace bdpt {
 #define BDPT_SKY_MIS_REGEN_MIN 32
 #endif
 
-enum : int { SKY_MIS_SRC_SURFACES = 0, SKY_MIS_SRC_GBUFFER = 1 };
-
 namespace {
 
 struct SkyMisShading {
@@ -49,20 +49,6 @@ struct SkyMisShading {
   float rough;
 };
 
-__device__ __forceinline__ f3 skyMisHalf3(const uint16_t* base, uint32_t at) {  // xyz of a half4 channel, as sky.hip's skyHalf3
-  const uint2 raw = reinterpret_cast<const uint2*>(base)[at];
-  return mk(f16_to_f32((uint16_t)(raw.x & 0xffffu)), f16_to_f32((uint16_t)(raw.x >> 16)), f16_to_f32((uint16_t)(raw.y & 0xffffu)));
-}
-
-// item `i`: its diffuse colour (what a dead item's output takes)
-template <int SRC>
-__device__ __forceinline__ f3 skyMisDiffuse(const SkyMisDev& Q, uint32_t i) {
-  if (SRC == SKY_MIS_SRC_SURFACES) {
-    const float4 q3 = Q.surf[(size_t)i * 6 + 3];
-    return mk(q3.x, q3.y, q3.z);
-  }
-  return skyMisHalf3(Q.gbDiffuse, Q.pix[i]);
-}
 // item `i` at `pos`: what its BSDF reads.  The Lambertian instances read N and diffuse only.
 template <int SRC, bool GGX>
 __device__ __forceinline__ SkyMisShading skyMisShading(const SkyMisDev& Q, uint32_t i, f3 pos) {
@@ -70,57 +56,31 @@ __device__ __forceinline__ SkyMisShading skyMisShading(const SkyMisDev& Q, uint3
   sd.V = mk(0);
   sd.spec = mk(0);
   sd.rough = 0.0f;
-  if (SRC == SKY_MIS_SRC_SURFACES) {
+  sd.N = itemNormal<SRC>(Q, i);
+  sd.dif = itemDiffuse<SRC>(Q, i);
+  if (!GGX) return sd;
+  if (SRC == ITEM_SRC_SURFACES) {
     const float4* r = Q.surf + (size_t)i * 6;
-    const float4 q1 = r[1], q3 = r[3];
-    sd.N = mk(q1.x, q1.y, q1.z);
-    sd.dif = mk(q3.x, q3.y, q3.z);
-    if (GGX) {
-      const float4 q2 = r[2], q4 = r[4];
-      sd.V = mk(q2.x, q2.y, q2.z);
-      sd.spec = mk(q4.x, q4.y, q4.z);
-      sd.rough = q1.w * q1.w;
-    }
-  } else {
-    const uint32_t fp = Q.pix[i];
-    sd.N = skyMisHalf3(Q.gbNormal, fp);
-    sd.dif = skyMisHalf3(Q.gbDiffuse, fp);
-    if (GGX) {  // as init_paths_kernel reads the pixel
-      const uint2 raw = reinterpret_cast<const uint2*>(Q.gbSpecRough)[fp];
-      sd.spec = mk(f16_to_f32((uint16_t)(raw.x & 0xffffu)), f16_to_f32((uint16_t)(raw.x >> 16)), f16_to_f32((uint16_t)(raw.y & 0xffffu)));
-      const float a = f16_to_f32((uint16_t)(raw.y >> 16));
-      sd.rough = a * a;
-      sd.V = normalize(ld3(Q.camPos) - pos);
-    }
+    const float4 q1 = r[1], q2 = r[2], q4 = r[4];
+    sd.V = mk(q2.x, q2.y, q2.z);
+    sd.spec = mk(q4.x, q4.y, q4.z);
+    sd.rough = q1.w * q1.w;
+  } else {  // as init_paths_kernel reads the pixel
+    const uint2 raw = reinterpret_cast<const uint2*>(Q.gbSpecRough)[Q.pix[i]];
+    sd.spec = mk(f16_to_f32((uint16_t)(raw.x & 0xffffu)), f16_to_f32((uint16_t)(raw.x >> 16)), f16_to_f32((uint16_t)(raw.y & 0xffffu)));
+    const float a = f16_to_f32((uint16_t)(raw.y >> 16));
+    sd.rough = a * a;
+    sd.V = normalize(ld3(Q.camPos) - pos);
   }
   return sd;
-}
-// item `i`: whether it is alive, and then its position
-template <int SRC>
-__device__ __forceinline__ bool skyMisAlive(const SkyMisDev& Q, uint32_t i, f3& pos) {
-  if (SRC == SKY_MIS_SRC_SURFACES) {
-    const float4* r = Q.surf + (size_t)i * 6;
-    if (Q.alive && Q.alive[i] == 0) return false;
-    if (__float_as_int(r[5].w) < 0) return false;
-    const float4 q0 = r[0];
-    pos = mk(q0.x, q0.y, q0.z);
-    return true;
-  } else {
-    const float4 wp = Q.gbPosition[Q.pix[i]];
-    pos = mk(wp.x, wp.y, wp.z);
-    return wp.w != 0.0f;
-  }
 }
 // the outputs of item `i`
 template <int SRC>
 __device__ __forceinline__ void skyMisStore(const SkyMisDev& Q, uint32_t i, f3 color, uint32_t count, uint32_t seed) {
-  const float4 c = make_float4(color.x, color.y, color.z, 1.0f);
-  if (SRC == SKY_MIS_SRC_SURFACES) {
-    Q.color[i] = c;
+  itemStoreColor<SRC>(Q, i, color);
+  if (SRC == ITEM_SRC_SURFACES) {
     if (Q.counts) Q.counts[i] = count;
     if (Q.seedsOut) Q.seedsOut[i] = seed;
-  } else {
-    Q.out[Q.pix[i]] = c;
   }
 }
 
@@ -194,12 +154,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(BDPT_SKY_
   T.cur = kDone;
   while (refill(F, cursor, lane, has, [&](uint32_t item) {
     rid = item;
-    // the item's RNG state: the caller's, or the pass's initRand(pixel, frameCount, 16)
-    seed = (SRC == SKY_MIS_SRC_SURFACES) ? Q.seeds[rid] : initRand(Q.pix[rid], Q.frameCount);
+    seed = itemSeed<SRC>(Q, rid);
     f3 pos = mk(0);
-    if (!skyMisAlive<SRC>(Q, rid, pos)) {
+    if (!itemAlive<SRC>(Q, rid, pos)) {
       // the background: the diffuse channel holds the colour, no draw; the lane stays idle
-      skyMisStore<SRC>(Q, rid, skyMisDiffuse<SRC>(Q, rid), 0u, seed);
+      skyMisStore<SRC>(Q, rid, itemDiffuse<SRC>(Q, rid), 0u, seed);
     } else {
       h = 0;
       count = 0;
@@ -234,7 +193,7 @@ void launchSkyMis(const SceneDev& S, const SkyMisDev& Q, bool gbuffer, bool ggx,
   if (!Q.range.cap) return;
   withFlag(gbuffer, [&](auto GB) {
     withFlag(ggx, [&](auto GGX) {
-      launchPersistent(sky_mis_kernel<GB ? SKY_MIS_SRC_GBUFFER : SKY_MIS_SRC_SURFACES, GGX>, G.skyMis[(GB ? 2 : 0) + (GGX ? 1 : 0)],
+      launchPersistent(sky_mis_kernel<GB ? ITEM_SRC_GBUFFER : ITEM_SRC_SURFACES, GGX>, G.skyMis[(GB ? 2 : 0) + (GGX ? 1 : 0)],
                        Q.range.cap, numCUs, st, S, Q, cursor);
     });
   });
