@@ -23,6 +23,7 @@ AO_CHANNEL = "AmbientOcclusion"  # the channel FramePipeline.ambient_occlusion a
 GI_CHANNEL = "DiffuseGI"  # the channel FramePipeline.diffuse_gi and bdpt_render --gi write
 DIRECT_CHANNEL = "DirectLighting"  # the channel FramePipeline.direct_lighting and bdpt_render --direct write
 SKY_CHANNEL = "SkyLighting"  # the channel FramePipeline.sky_lighting and bdpt_render --sky write
+RIS_CHANNEL = "ResampledDirect"  # the channel FramePipeline.ris_lighting and bdpt_render --ris write
 
 
 class BdptError(RuntimeError):
@@ -950,6 +951,81 @@ class Context:
         gets (colour, 1).  matIndex 0 needs a camera."""
         self._check(self._lib.bdpt_sky_mis_execute(self._h, C.byref(params), C.byref(gbuffer), out_ptr, stream), "bdpt_sky_mis_execute")
 
+    # ---- resampled direct lighting (include/bdpt.h "Resampled direct lighting", DESIGN.md) ----
+    @staticmethod
+    def _ris_mode(what, candidates, samples, mat_index, area_lights, use_hints, clamp):
+        """(candidates, samples, matIndex, flags, clampUpper) of a resampled direct lighting call, checked."""
+        for name, v, top in (("candidates", candidates, abi.RIS_MAX_CANDIDATES), ("samples", samples, abi.RIS_MAX_SAMPLES)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= top:
+                raise BdptError(f"{what}: {name} must be an integer in 1 .. {top}, not {v!r}")
+        mat, _ = Context._bsdf_mode(what, mat_index, False)
+        for name, v in (("area_lights", area_lights), ("use_hints", use_hints)):
+            if not isinstance(v, bool):
+                raise BdptError(f"{what}: {name} must be a bool, not {v!r}")
+        if isinstance(clamp, bool) or not isinstance(clamp, (int, float)) or not float(clamp) >= 0.0:
+            raise BdptError(f"{what}: clamp must be a number >= 0, not {clamp!r}")
+        flags = (abi.PARAM_AREA_LIGHTS if area_lights else 0) | (abi.RIS_USE_HINTS if use_hints else 0)
+        return candidates, samples, mat, flags, float(clamp)
+
+    def ris_lighting(self, surfaces, seeds, candidates, samples=1, mat_index=1, area_lights=False, use_hints=False,
+                     clamp=float(3.4028234663852886e38), min_t=1e-4, alive=None, out=None, seeds_out=None, traced=None,
+                     reservoirs=None, count=None, stream=None):
+        """bdpt_ris_query: resampled direct lighting.  Per (N, 24) bdpt_surface record and sample, `candidates` (1 .. 32)
+        next-event samples of the pass are drawn, one is kept with probability proportional to its unshadowed, clamped
+        value at the record, and one any-hit ray is traced for it; `samples` (1 .. 64) such estimates are averaged — in one
+        launch the loop sample_lights(seeds_out=) -> a draw -> clamp, weight and reservoir update, then trace_rays("any") ->
+        ordered add, bit for bit.  seeds (N,) uint32 / int32 RNG states: two draws per candidate.  mat_index 0 GGX, 1
+        Lambertian; area_lights makes the emitter table one more candidate source; use_hints tries a selected point or spot
+        light's occluder hint before the ray (the same answer, fewer traversals); `clamp` bounds every component of a
+        candidate's value.  Returns (N, 4) float32 (colour, 1); a miss record, or an item whose `alive` byte is 0, gives
+        (diffuse, 1) without a draw.  GPU tensors only: alive (N,) uint8; seeds_out (N,) the states after the draws (it may
+        be `seeds`); traced (N,) the rays traversed; reservoirs (N, samples, 4) int32 / uint32 in the bdpt_ris_reservoir
+        layout (light | status << 16, the selected state, W and wsum as float bits).  `out` and `count` as for the other
+        queries."""
+        import torch
+        records, words = (torch.float32, torch.int32), (torch.int32, torch.uint32)
+        candidates, samples, mat, flags, clamp = self._ris_mode("ris_lighting", candidates, samples, mat_index, area_lights,
+                                                                use_hints, clamp)
+        extras = [("alive", alive, None, (torch.uint8,)), ("seeds_out", seeds_out, None, words), ("traced", traced, None, words)]
+        if reservoirs is not None:
+            n = int(surfaces.shape[0]) if getattr(surfaces, "is_cuda", False) and surfaces.dim() >= 1 else -1
+            if n < 0:
+                raise BdptError("ris_lighting: reservoirs goes with GPU tensor inputs")
+            self._check_gpu(reservoirs, "ris_lighting", "reservoirs", (n, samples, 4), words)
+
+        def run(ptrs, n, cnt, res):
+            d = abi.RisDesc()
+            d.num, d.flags, d.numDevice, d.matIndex, d.candidates, d.samples = n, flags, cnt, mat, candidates, samples
+            d.clampUpper, d.minT = clamp, float(min_t)
+            d.surfaces, d.seeds, d.color = ptrs[0], ptrs[1], res
+            d.alive, d.seedsOut, d.traced, d.reservoirs = (None if t is None else t.data_ptr()
+                                                           for t in (alive, seeds_out, traced, reservoirs))
+            return self._lib.bdpt_ris_query(self._h, C.byref(d), stream)
+
+        return self._surface_query("ris_lighting", [("surfaces", surfaces, 24, records), ("seeds", seeds, None, words)],
+                                   (4, (torch.float32,)), run, out, count, extras=extras, fn="bdpt_ris_query")
+
+    def ris_execute(self, gbuffer, out, *, candidates, samples=1, mat_index=1, area_lights=False, use_hints=False,
+                    clamp=float(3.4028234663852886e38), min_t=1e-4, frame_count=0, stream=None):
+        """bdpt_ris_execute: resampled direct lighting on the context's tile pixels — the full-frame G-buffer (abi.GBuffer)
+        and the full-frame (H, W, 4) float32 GPU image `out`, which gets (colour, 1) at the tile's pixels; seeds are
+        initRand(pixel, frame_count).  mat_index 0 needs a camera.  Returns the abi.RisParams used."""
+        import torch
+        candidates, samples, mat, flags, clamp = self._ris_mode("ris_execute", candidates, samples, mat_index, area_lights,
+                                                                use_hints, clamp)
+        if not isinstance(gbuffer, abi.GBuffer):
+            raise BdptError("ris_execute: gbuffer must be an abi.GBuffer")
+        frame = getattr(self, "_frame", None)
+        if frame is None:
+            raise BdptError("ris_execute: no frame size (resize first)")
+        self._check_gpu(out, "ris_execute", "out", frame + (4,), (torch.float32,))
+        p = abi.RisParams()
+        p.frameCount, p.clampUpper, p.minT = int(frame_count) & 0xFFFFFFFF, clamp, float(min_t)
+        p.candidates, p.samples, p.matIndex, p.flags = candidates, samples, mat, flags
+        self._check(self._lib.bdpt_ris_execute(self._h, C.byref(p), C.byref(gbuffer), C.c_void_p(out.data_ptr()), stream),
+                    "bdpt_ris_execute")
+        return p
+
     # ---- diffuse GI (include/bdpt.h "Diffuse GI", DESIGN.md) ----
     def diffuse_gi(self, surfaces, seeds, indirect=True, cosine=True, view_pos=None, normal_map=True, min_t=1e-4, alive=None,
                    out=None, hits=None, status=None, seeds_out=None, count=None, stream=None):
@@ -1570,6 +1646,8 @@ class FramePipeline:
         self.last_direct_params = None
         self.sky_frame = 0
         self.last_sky_params = None
+        self.ris_frame = 0
+        self.last_ris_params = None
         self.gi_frame = 0x1337  # CommonPasses/SimpleDiffuseGIPass.h:62
         self.last_gi_params = None
         self.accum_count = 0
@@ -1896,6 +1974,22 @@ class FramePipeline:
             raise BdptError(f"direct_lighting: use_hints must be a bool, not {use_hints!r}")
         out = self._pass_channel(DIRECT_CHANNEL)
         self.last_direct_params = self.ctx.direct_execute(self.gb, out, min_t=self.min_t, use_hints=use_hints, stream=self._stream_ptr())
+        return out
+
+    def ris_lighting(self, candidates, samples=1, mat_index=1, area_lights=False, use_hints=False,
+                     clamp=float(3.4028234663852886e38)):
+        """Resampled direct lighting on this pipeline's G-buffer as it stands and stream: Context.ris_execute with the pass's
+        frame counter (from 0, one per call, as sky_lighting keeps its own), the pipeline's min_t, `candidates` next-event
+        candidates (1 .. 32) and `samples` rays per pixel (1 .. 64), for the Lambertian surface (``mat_index`` 1) or the
+        pass's GGX material (0: MaterialSpecRough and the pipeline's camera are read as well).  area_lights adds the
+        emitter table as a candidate source, use_hints tries the lights' occluder hints first (the same image).  Returns
+        the (H, W, 4) float32 channel "ResampledDirect" ((colour, 1); a tile or stripes pipeline writes its own rows), also
+        in ``channels``; ``last_ris_params`` keeps the abi.RisParams used."""
+        out = self._pass_channel(RIS_CHANNEL)
+        self.last_ris_params = self.ctx.ris_execute(self.gb, out, candidates=candidates, samples=samples, mat_index=mat_index,
+                                                    area_lights=area_lights, use_hints=use_hints, clamp=clamp, min_t=self.min_t,
+                                                    frame_count=self.ris_frame, stream=self._stream_ptr())
+        self.ris_frame += 1
         return out
 
     def set_lights(self, lights):

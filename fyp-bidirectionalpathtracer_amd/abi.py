@@ -384,6 +384,28 @@ class SkyMisParams(C.Structure):
                 ("matIndex", C.c_uint32), ("techniques", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+RIS_USE_HINTS = 1  # bdpt_ris_desc::flags, beside PARAM_AREA_LIGHTS
+RIS_MAX_CANDIDATES, RIS_MAX_SAMPLES = 32, 64
+RIS_STATUS_RAY, RIS_STATUS_HINT_OCCLUDED, RIS_STATUS_OCCLUDED = 1, 2, 4  # bdpt_ris_reservoir::status
+RIS_NO_LIGHT = 0xFFFF
+
+
+class RisReservoir(C.Structure):
+    _fields_ = [("light", C.c_uint16), ("status", C.c_uint16), ("state", C.c_uint32), ("W", C.c_float), ("wsum", C.c_float)]
+
+
+class RisDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("flags", C.c_uint32), ("numDevice", C.c_void_p), ("matIndex", C.c_uint32),
+                ("candidates", C.c_uint32), ("samples", C.c_uint32), ("clampUpper", C.c_float), ("minT", C.c_float),
+                ("reserved", C.c_uint32), ("surfaces", C.c_void_p), ("alive", C.c_void_p), ("seeds", C.c_void_p),
+                ("color", C.c_void_p), ("seedsOut", C.c_void_p), ("traced", C.c_void_p), ("reservoirs", C.c_void_p)]
+
+
+class RisParams(C.Structure):
+    _fields_ = [("frameCount", C.c_uint32), ("clampUpper", C.c_float), ("minT", C.c_float), ("candidates", C.c_uint32),
+                ("samples", C.c_uint32), ("matIndex", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 BMFR_MAX_PLANES = BDPT_MAX_LIGHTS + 2
 
 
@@ -453,6 +475,8 @@ PROTOTYPES = {
     "bdpt_bsdf_pdf_query": (C.c_int, [C.c_void_p, C.POINTER(BsdfPdfDesc), C.c_void_p]),
     "bdpt_sky_mis_query": (C.c_int, [C.c_void_p, C.POINTER(SkyMisDesc), C.c_void_p]),
     "bdpt_sky_mis_execute": (C.c_int, [C.c_void_p, C.POINTER(SkyMisParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "bdpt_ris_query": (C.c_int, [C.c_void_p, C.POINTER(RisDesc), C.c_void_p]),
+    "bdpt_ris_execute": (C.c_int, [C.c_void_p, C.POINTER(RisParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_host_env_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "bdpt_host_env_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                         C.c_void_p]),

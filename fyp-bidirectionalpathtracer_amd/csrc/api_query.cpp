@@ -1,8 +1,8 @@
 // api_query.cpp — the per-item queries of the C ABI (include/bdpt.h): bdpt_trace_rays, bdpt_camera_rays, bdpt_shade_hits,
 // bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query, bdpt_ao_query, bdpt_gi_query,
-// bdpt_direct_query, bdpt_env_query, bdpt_sky_query, bdpt_bsdf_pdf_query, bdpt_sky_mis_query and bdpt_motion_query, on a
-// caller's arrays in device memory, and bdpt_ao_execute, bdpt_gi_execute, bdpt_direct_execute, bdpt_sky_execute and
-// bdpt_sky_mis_execute, the same kernels on the tile's G-buffer
+// bdpt_direct_query, bdpt_env_query, bdpt_sky_query, bdpt_bsdf_pdf_query, bdpt_sky_mis_query, bdpt_ris_query and bdpt_motion_query, on a
+// caller's arrays in device memory, and bdpt_ao_execute, bdpt_gi_execute, bdpt_direct_execute, bdpt_sky_execute,
+// bdpt_sky_mis_execute and bdpt_ris_execute, the same kernels on the tile's G-buffer
 // pixels.  Every one checks its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags and what goes together
 // (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
 // first use of the emitter table), so all can be captured into a hipGraph.
@@ -576,6 +576,81 @@ int bdpt_sky_mis_execute(bdpt_ctx* c, const bdpt_sky_mis_params* p, const bdpt_g
     Q.techniques = p->techniques;
     Q.frameCount = p->frameCount;
     launchSkyMis(c->scene.S, Q, true, ggx, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+namespace {
+bool risModeOk(uint32_t candidates, uint32_t samples, uint32_t matIndex, uint32_t flags, float clampUpper) {
+  return candidates && candidates <= BDPT_RIS_MAX_CANDIDATES && samples && samples <= BDPT_RIS_MAX_SAMPLES && matIndex <= 1 &&
+         !(flags & ~(BDPT_PARAM_AREA_LIGHTS | BDPT_RIS_USE_HINTS)) && clampUpper >= 0.0f;  // (a NaN fails the comparison)
+}
+const char* const kRisModeWhy =
+    "candidates outside 1 .. BDPT_RIS_MAX_CANDIDATES, samples outside 1 .. BDPT_RIS_MAX_SAMPLES, matIndex > 1, unknown flags, "
+    "non-zero reserved, or a negative or NaN clampUpper";
+// The emitter table of a call with BDPT_PARAM_AREA_LIGHTS, as bdpt_light_query takes it: the first build synchronises the
+// device, so it comes before enqueueQuery, under an ENTER of its own.  n == 0 (no emitter): the plain instances.
+int risArea(bdpt_ctx* c, uint32_t flags, void* stream, AreaDev& A) {
+  A = AreaDev{};
+  if (!(flags & BDPT_PARAM_AREA_LIGHTS)) return BDPT_OK;
+  ENTER(c);
+  if (int rc = ensureAreaLights(c, reinterpret_cast<hipStream_t>(stream))) return rc;
+  A = c->scene.area;
+  return BDPT_OK;
+}
+}  // namespace
+
+static_assert(sizeof(bdpt_ris_desc) == 96 && offsetof(bdpt_ris_desc, surfaces) == 40 && sizeof(bdpt_ris_params) == 32 &&
+                  sizeof(bdpt_ris_reservoir) == 16 && offsetof(bdpt_ris_reservoir, status) == 2,
+              "abi.RisDesc and abi.RisParams restate these layouts; ris_kernel writes a reservoir as one uint4");
+int bdpt_ris_query(bdpt_ctx* c, const bdpt_ris_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "ris_query")) return rc;
+  if (!risModeOk(d->candidates, d->samples, d->matIndex, d->flags, d->clampUpper) || d->reserved)
+    return refuse(c, BDPT_E_INVALID, "ris_query", kRisModeWhy);
+  if (!d->num) return BDPT_OK;
+  if (int rc = checkRecords(c, "ris_query", "surfaces, seeds, color, seedsOut, traced, reservoirs or numDevice",
+                            {{d->surfaces, 16}, {d->seeds, 4}, {d->color, 16}, {d->seedsOut, 4, true}, {d->traced, 4, true},
+                             {d->reservoirs, 16, true}, {d->numDevice, 4, true}}))
+    return rc;
+  AreaDev A;
+  if (int rc = risArea(c, d->flags, stream, A)) return rc;
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    RisDev Q{};
+    fillRecords<true>(Q, d);
+    Q.color = f4(d->color);
+    Q.traced = d->traced;
+    Q.reservoirs = reinterpret_cast<uint4*>(d->reservoirs);
+    Q.clampUpper = d->clampUpper;
+    Q.candidates = d->candidates;
+    Q.samples = d->samples;
+    launchRis(c->scene.S, Q, A, false, d->matIndex == 0, (d->flags & BDPT_RIS_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+int bdpt_ris_execute(bdpt_ctx* c, const bdpt_ris_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
+  if (!c || !p || !gb) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "ris_execute")) return rc;
+  if (int rc = needFrame(c, "ris_execute")) return rc;
+  const bool ggx = p->matIndex == 0;  // V comes from the camera
+  if (ggx)
+    if (int rc = needCamera(c, "ris_execute: matIndex 0")) return rc;
+  if (!risModeOk(p->candidates, p->samples, p->matIndex, p->flags, p->clampUpper) || p->reserved)
+    return refuse(c, BDPT_E_INVALID, "ris_execute", kRisModeWhy);
+  if (int rc = checkGbuffer(c, "ris_execute", gb, out, true, ggx)) return rc;
+  AreaDev A;
+  if (int rc = risArea(c, p->flags, stream, A)) return rc;
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    RisDev Q{};
+    fillGbuffer(Q, c, gb, out, p->minT);
+    Q.gbDiffuse = gb->materialDiffuse;
+    Q.gbSpecRough = gb->materialSpecRough;
+    if (ggx)
+      for (int k = 0; k < 3; k++) Q.camPos[k] = c->cam.posW[k];
+    Q.clampUpper = p->clampUpper;
+    Q.candidates = p->candidates;
+    Q.samples = p->samples;
+    Q.frameCount = p->frameCount;
+    launchRis(c->scene.S, Q, A, true, ggx, (p->flags & BDPT_RIS_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 

@@ -313,6 +313,7 @@ struct LaunchGrids {
   uint32_t direct[4] = {0, 0, 0, 0};  // [G-buffer source][HINTS] (direct.hip)
   uint32_t sky[2] = {0, 0};           // [G-buffer source] (sky.hip)
   uint32_t skyMis[4] = {0, 0, 0, 0};  // [G-buffer source][GGX] (sky_mis.hip)
+  uint32_t ris[16] = {};              // [G-buffer source][GGX][AREA][HINTS] (ris.hip)
 };
 // both random walks of the frame: one persistent launch (trace + hit/miss shading in place)
 void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,
@@ -473,6 +474,33 @@ struct DirectDev {  // fields without a comment: the item source (device_item_so
 // `cursor`: as launchTraceRays (the context's two words: zero when the launch starts, left zero)
 void launchDirect(const SceneDev& S, const DirectDev& Q, bool gbuffer, bool hints, unsigned long long* cursor, LaunchGrids& G, int numCUs,
                   hipStream_t st);
+// ris.hip: bdpt_ris_query (items are bdpt_surface records) and bdpt_ris_execute (items are the tile's pixels, read from the
+// G-buffer).  Per alive item and sample `candidates` next-event candidates of the pass, one of them kept in a one-entry
+// reservoir, and one any-hit ray for it (include/bdpt.h "Resampled direct lighting").
+struct RisDev {  // fields without a comment: the item source (device_item_source.hpp)
+  const float4* surf;           // posW, N, linearRoughness, diffuse and prim are read; GGX also V and specular
+  const uint32_t* seeds;
+  const uint8_t* alive;
+  float4* color;
+  uint32_t* seedsOut;           // query, optional: the state after 2 * candidates * samples draws (a dead item's: unchanged)
+  uint32_t* traced;             // query, optional: the rays traversed per item (0 .. samples)
+  uint4* reservoirs;            // query, optional: samples records per item, item-major (bdpt_ris_reservoir)
+  const float4* gbPosition;
+  const uint16_t* gbNormal;
+  const uint16_t* gbDiffuse;
+  const uint16_t* gbSpecRough;  // GGX only: specular = rgb, rough = a * a
+  const uint32_t* pix;
+  float4* out;
+  QueryRange range;             // minT: also of the occluder-hint test
+  float camPos[3];              // execute, GGX: V = normalize(camPos - posW)
+  float clampUpper;
+  uint32_t candidates;          // 1 .. 32
+  uint32_t samples;             // 1 .. 64
+  uint32_t frameCount;          // execute
+};
+// A.n > 0: the AREA instances (the emitter table is light numLights while its W is positive).  `cursor`: as launchTraceRays
+void launchRis(const SceneDev& S, const RisDev& Q, const AreaDev& A, bool gbuffer, bool ggx, bool hints, unsigned long long* cursor,
+               LaunchGrids& G, int numCUs, hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,

@@ -12,6 +12,7 @@
 #include "kernels.h"
 
 #include "device_area.hpp"
+#include "device_light.hpp"
 #include "device_math.hpp"
 #include "device_query.hpp"
 #include "device_scene.hpp"
@@ -21,13 +22,6 @@
 namespace bdpt {
 
 namespace {
-// the light count of the pass: the emitter table is light numLights of numLights + 1 while its W is positive
-template <bool AREA>
-__device__ __forceinline__ int lightsCountOf(const SceneDev& S, const AreaDev& A, float& areaW) {
-  areaW = AREA ? areaTotal(A) : 0.0f;
-  return (int)S.numLights + ((AREA && areaW > 0.0f) ? 1 : 0);
-}
-
 // bdpt_light_sample: three float4 per item, (org, tmin) (dir, tmax) (value, light | status << 16).  Reads the record's
 // posW, N, linearRoughness, diffuse and prim, and for GGX also V and specular (the Lambertian value uses neither, as
 // gen_nee's loadSurf<false> leaves them zero).
@@ -57,18 +51,13 @@ __device__ __forceinline__ void lightNeeLane(const SceneDev& S, const LightQuery
         spec = mk(sp.x, sp.y, sp.z);
         rough = nr.w * nr.w;  // shadeHit's roughness from linearRoughness
       }
-      int lightToSample = (int)(r * (float)lightsCount);
-      if (lightToSample > lightsCount - 1) lightToSample = lightsCount - 1;
-      f3 L, lightIntensity;
-      float distToLight;
-      const bool area = AREA && lightToSample == (int)S.numLights;
-      if (area) {
-        areaNee(S, A, areaW, seed, pos, L, distToLight, lightIntensity);
-        distToLight = distToLight * (1.0f - 1e-4f);  // the emitter does not occlude its own sample
-      } else {
-        getLightData(S.sc->lights[lightToSample], pos, L, lightIntensity, distToLight);
-      }
-      const f3 value = directIfVisible<GGX>((float)lightsCount, L, lightIntensity, mk(nr.x, nr.y, nr.z), V, mk(dif.x, dif.y, dif.z), spec, rough);
+      LightCandidate cand;
+      const f3 value = lightCandidate<GGX, AREA>(S, A, areaW, lightsCount, r, seed, pos, mk(nr.x, nr.y, nr.z), V, mk(dif.x, dif.y, dif.z),
+                                                 spec, rough, cand);
+      const int lightToSample = cand.light;
+      const bool area = cand.area;
+      const f3 L = cand.L;
+      const float distToLight = cand.dist;
       uint32_t status = allZero(value) ? 0u : BDPT_LIGHT_STATUS_NONZERO;
       // The nearest triangle the light sees towards this point is tried first, exactly as gen_nee tries it.  gen_nee tests
       // its clamped term, which is zero for a value without a positive component (NaN where NdotV is 0, or a negative

@@ -824,6 +824,73 @@ void SkyLightingPass::execute(RenderContext* pRenderContext) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// ResampledDirectPass (include/bdpt.h "Resampled direct lighting"; shaped like SkyLightingPass above)
+// ------------------------------------------------------------------------------------------------
+bool ResampledDirectPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
+  mpResManager = pResManager;
+  mpResManager->requestTextureResources({"WorldPosition", "WorldNormal", "MaterialDiffuse"});
+  if (mMatIndex == 0) mpResManager->requestTextureResource("MaterialSpecRough");
+  mpResManager->requestTextureResource(mOutputBuf);
+  mpRays = RayLaunch::create(pRenderContext);
+  if (!mpRays) return false;
+  if (mpScene) mpRays->setScene(mpScene);
+  return true;
+}
+void ResampledDirectPass::initScene(RenderContext*, Scene::SharedPtr pScene) {
+  mpScene = pScene;
+  if (mpRays) mpRays->setScene(mpScene);
+}
+void ResampledDirectPass::renderGui(Gui* pGui) {
+  int dirty = 0;
+  dirty |= (int)pGui->addIntVar("Num RIS Candidates", mCandidates, 1, (int)BDPT_RIS_MAX_CANDIDATES);
+  dirty |= (int)pGui->addIntVar("Num RIS Samples", mSamples, 1, (int)BDPT_RIS_MAX_SAMPLES);
+  dirty |= (int)pGui->addFloatVar("RIS clamp", mClampUpper, 0.0f, 3.402823466e+38f, 0.1f);
+  dirty |= (int)pGui->addIntVar("RIS material (0 GGX, 1 Lambertian)", mMatIndex, 0, 1);
+  if (dirty) setRefreshFlag();
+}
+void ResampledDirectPass::execute(RenderContext* pRenderContext) {
+  Texture::SharedPtr pDstTex = mpResManager->getClearedTexture(mOutputBuf, vec4{0.0f, 0.0f, 0.0f, 0.0f});
+  if (!pDstTex || !mpRays || !mpRays->readyToRender()) return;
+  Texture::SharedPtr pos = mpResManager->getTexture("WorldPosition"), nrm = mpResManager->getTexture("WorldNormal"),
+                     dif = mpResManager->getTexture("MaterialDiffuse");
+  if (!pos || !nrm || !dif || pos->getFormat() != ResourceFormat::RGBA32Float || nrm->getFormat() != ResourceFormat::RGBA16Float ||
+      dif->getFormat() != ResourceFormat::RGBA16Float || pDstTex->getFormat() != ResourceFormat::RGBA32Float) {
+    std::fprintf(stderr, "[ResampledDirectPass] needs WorldPosition (RGBA32F), WorldNormal and MaterialDiffuse (RGBA16F) of a G-buffer pass and an "
+                         "RGBA32F output\n");
+    return;
+  }
+  if (!mpRays->ensureSize(pDstTex->getWidth(), pDstTex->getHeight())) return;
+  hipStream_t stream = pRenderContext->getStream();
+  bdpt_gbuffer gb;
+  std::memset(&gb, 0, sizeof(gb));
+  gb.worldPosition = (float*)pos->getDevicePointer();
+  gb.worldNormal = (uint16_t*)nrm->getDevicePointer();
+  gb.materialDiffuse = (uint16_t*)dif->getDevicePointer();
+  const bool ggx = mMatIndex == 0;
+  if (ggx) {  // the GGX material reads MaterialSpecRough, and V from the scene's camera
+    Texture::SharedPtr spec = mpResManager->getTexture("MaterialSpecRough");
+    Camera::SharedPtr cam = mpScene ? mpScene->getActiveCamera() : nullptr;
+    if (!spec || spec->getFormat() != ResourceFormat::RGBA16Float || !cam) {
+      std::fprintf(stderr, "[ResampledDirectPass] the GGX material needs MaterialSpecRough (RGBA16F) of a G-buffer pass and a camera\n");
+      return;
+    }
+    gb.materialSpecRough = (uint16_t*)spec->getDevicePointer();
+    bdpt_set_camera(mpRays->ctx(), &cam->getData());
+  }
+  bdpt_ris_params p;
+  std::memset(&p, 0, sizeof(p));
+  p.frameCount = mFrameCount++;
+  p.clampUpper = mClampUpper;
+  p.minT = mpResManager->getMinTDist();
+  p.candidates = (uint32_t)mCandidates;
+  p.samples = (uint32_t)mSamples;
+  p.matIndex = ggx ? 0u : 1u;
+  p.flags = (mAreaLights ? BDPT_PARAM_AREA_LIGHTS : 0u) | (mUseHints ? BDPT_RIS_USE_HINTS : 0u);
+  if (bdpt_ris_execute(mpRays->ctx(), &p, &gb, (float*)pDstTex->getDevicePointer(), stream) != BDPT_OK)
+    std::fprintf(stderr, "[ResampledDirectPass] %s\n", mpRays->lastError());
+}
+
+// ------------------------------------------------------------------------------------------------
 // LambertianPlusShadowPass (CommonPasses/LambertianPlusShadowPass.cpp:33-83)
 // ------------------------------------------------------------------------------------------------
 bool LambertianPlusShadowPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
@@ -1387,6 +1454,21 @@ bool SkyLightingPass::loadState(RenderContext*, const uint8_t* data, size_t size
   if (size != 16) return false;
   if (get32(data + 4) != (uint32_t)mNumRaysPerPixel || get32(data + 8) != floatBits(mClampUpper) ||
       get32(data + 12) != floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f))
+    return false;
+  mFrameCount = get32(data);
+  return true;
+}
+// the frame counter, and what the image sequence depends on; hints change no bit and are not kept
+void ResampledDirectPass::saveState(RenderContext*, std::vector<uint8_t>& out) {
+  put32(out, mFrameCount);
+  put32(out, (uint32_t)mCandidates | ((uint32_t)mSamples << 8) | ((uint32_t)mMatIndex << 16) | (mAreaLights ? 1u << 24 : 0u));
+  put32(out, floatBits(mClampUpper));
+  put32(out, floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f));
+}
+bool ResampledDirectPass::loadState(RenderContext*, const uint8_t* data, size_t size) {
+  if (size != 16) return false;
+  if (get32(data + 4) != ((uint32_t)mCandidates | ((uint32_t)mSamples << 8) | ((uint32_t)mMatIndex << 16) | (mAreaLights ? 1u << 24 : 0u)) ||
+      get32(data + 8) != floatBits(mClampUpper) || get32(data + 12) != floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f))
     return false;
   mFrameCount = get32(data);
   return true;

@@ -273,6 +273,45 @@ class SkyLightingPass : public RenderPass {
   uint32_t mPreparedW = 0, mPreparedH = 0;
 };
 
+// Resampled direct lighting (include/bdpt.h "Resampled direct lighting"): WorldPosition, WorldNormal and MaterialDiffuse in, the
+// output channel out; per pixel and sample `candidates` next-event candidates, one survivor, one shadow ray: bdpt_ris_execute.
+// The project's own pass, shaped like SkyLightingPass: a frame counter from 0, one per frame, so that an accumulation pass
+// behind it converges.  Material 0 is the pass's GGX material (MaterialSpecRough and the scene's camera go in too); the
+// emitter table, the occluder hints and the clamp are the host program's configuration.
+class ResampledDirectPass : public RenderPass {
+ public:
+  using SharedPtr = std::shared_ptr<ResampledDirectPass>;
+  static SharedPtr create(const std::string& outBuf = ResourceManager::kOutputChannel) { return SharedPtr(new ResampledDirectPass(outBuf)); }
+  void setCandidates(int m) { mCandidates = m; }   // 1 .. BDPT_RIS_MAX_CANDIDATES
+  void setSamples(int k) { mSamples = k; }          // 1 .. BDPT_RIS_MAX_SAMPLES
+  void setMaterial(int matIndex) { mMatIndex = matIndex; }  // 0 GGX, 1 Lambertian
+  void setAreaLights(bool on) { mAreaLights = on; }
+  void setHints(bool on) { mUseHints = on; }
+  void setClamp(float hi) { mClampUpper = hi; }
+
+ protected:
+  ResampledDirectPass(const std::string& outBuf) : RenderPass("Resampled Direct Rays", "Resampled Direct Options"), mOutputBuf(outBuf) {}
+  bool initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) override;
+  void initScene(RenderContext* pRenderContext, Scene::SharedPtr pScene) override;
+  void renderGui(Gui* pGui) override;
+  void execute(RenderContext* pRenderContext) override;
+  bool requiresScene() override { return true; }
+  bool usesRayTracing() override { return true; }
+  void saveState(RenderContext* pRenderContext, std::vector<uint8_t>& out) override;
+  bool loadState(RenderContext* pRenderContext, const uint8_t* data, size_t size) override;
+
+  RayLaunch::SharedPtr mpRays;
+  Scene::SharedPtr mpScene;
+  std::string mOutputBuf;
+  float mClampUpper = 3.402823466e+38f;  // no clamp
+  int32_t mCandidates = 8;
+  int32_t mSamples = 1;
+  int32_t mMatIndex = 1;
+  bool mAreaLights = false;
+  bool mUseHints = false;
+  uint32_t mFrameCount = 0;
+};
+
 // Direct lighting from every light with one shadow ray each (CommonPasses/LambertianPlusShadowPass.{h,cpp}): WorldPosition,
 // WorldNormal, MaterialDiffuse and MaterialSpecRough in, the output channel out; no GUI state and no frame counter, as in the
 // reference (nothing is drawn).  Its ray generation shader with its shadow hit group is bdpt_direct_execute.

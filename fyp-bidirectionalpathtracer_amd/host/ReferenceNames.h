@@ -28,4 +28,5 @@ using bdpt::Scene;
 using bdpt::SimpleDiffuseGIPass;
 using bdpt::SimpleAccumulationPass;
 using bdpt::SkyLightingPass;
+using bdpt::ResampledDirectPass;
 using bdpt::Texture;

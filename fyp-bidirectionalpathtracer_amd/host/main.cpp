@@ -55,6 +55,13 @@ struct Options {
   float skyClamp = 0.0f;      // --sky-clamp C (with --sky, > 0): the bound of a sample's value; not given: none
   bool skyClampSet = false;
   bool skyMis = false;        // --sky-mis (with --sky): a table-sampled and a BSDF-sampled ray per sample, balance heuristic
+  int ris = -1;               // --ris M: G-buffer -> ResampledDirectPass (M candidates per sample) -> accumulation
+  int risSamples = 1;         // --ris-samples K (with --ris): shadow rays per pixel and frame
+  bool risSamplesSet = false;
+  bool risGgx = false;        // --ris-ggx (with --ris): the pass's GGX material instead of the Lambertian surface
+  bool risHints = false;      // --ris-hints (with --ris): BDPT_RIS_USE_HINTS (the same image)
+  float risClamp = 0.0f;      // --ris-clamp C (with --ris, > 0): the bound of a candidate's value; not given: none
+  bool risClampSet = false;
   bool skyGgx = false;        // --sky-ggx (with --sky-mis): the pass's GGX material instead of the Lambertian surface
   bool gi = false;            // --gi: render the G-buffer, the diffuse GI pass and the accumulation pass instead of the BDPT pipeline
   bool giDirectOnly = false;  // --gi-direct-only: untick "Shooting global illumination rays"
@@ -130,7 +137,7 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   }
   // add the passes to the rendering pipeline, as Main.cpp:12-18 does
   pipeline->setPass(0, LightProbeGBufferPass::create());
-  const size_t numPasses = (o.ao >= 0 || o.direct) ? 2 : (o.gi || o.sky >= 0) ? 3 : 4;
+  const size_t numPasses = (o.ao >= 0 || o.direct) ? 2 : (o.gi || o.sky >= 0 || o.ris >= 0) ? 3 : 4;
   if (o.direct) {  // --direct: the G-buffer and the direct lighting pass, which writes the output channel (nothing to accumulate: no draw)
     LambertianPlusShadowPass::SharedPtr lambert = LambertianPlusShadowPass::create();
     lambert->setUseHints(o.directHints);
@@ -143,6 +150,16 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
     sky->setMis(o.skyMis);
     sky->setMaterial(o.skyGgx ? 0 : 1);
     pipeline->setPass(1, sky);
+    pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
+  } else if (o.ris >= 0) {  // --ris: the G-buffer, the resampled direct lighting pass into the output channel, the accumulation pass
+    ResampledDirectPass::SharedPtr ris = ResampledDirectPass::create(ResourceManager::kOutputChannel);
+    ris->setCandidates(o.ris);
+    ris->setSamples(o.risSamples);
+    ris->setMaterial(o.risGgx ? 0 : 1);
+    ris->setAreaLights(o.areaLights);
+    ris->setHints(o.risHints);
+    if (o.risClampSet) ris->setClamp(o.risClamp);
+    pipeline->setPass(1, ris);
     pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
   } else if (o.gi) {  // --gi: the G-buffer, the diffuse GI pass into the output channel, and the accumulation pass over it
     pipeline->setPass(1, SimpleDiffuseGIPass::create(ResourceManager::kOutputChannel));
@@ -346,6 +363,10 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
       std::printf("%s %ux%u diffuse GI (%s%s): %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
                   o.giDirectOnly ? "direct only" : "one bounce", o.giUniform ? ", uniform sampling" : ", cosine sampling", o.frames - warmup, res.ms,
                   res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
+    else if (o.ris >= 0)
+      std::printf("%s %ux%u resampled direct lighting%s%s%s, %d candidates, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f",
+                  o.scene.c_str(), o.W, o.H, o.risGgx ? " (GGX)" : "", o.areaLights ? ", emitter table" : "", o.risHints ? ", occluder hints" : "",
+                  o.ris, o.risSamples, o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
     else if (o.sky >= 0)
       std::printf("%s %ux%u sky lighting%s, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
                   o.skyMis ? (o.skyGgx ? " (MIS, GGX; two rays a sample)" : " (MIS; two rays a sample)") : "", o.sky, o.frames - warmup, res.ms, res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
@@ -414,6 +435,11 @@ int main(int argc, char** argv) {
     else if (std::strcmp(argv[i], "--gi") == 0) o.gi = true;
     else if (std::strcmp(argv[i], "--gi-direct-only") == 0) o.giDirectOnly = true;
     else if (std::strcmp(argv[i], "--gi-uniform") == 0) o.giUniform = true;
+    else if (const char* v = next("--ris")) o.ris = std::max(0, std::atoi(v));
+    else if (const char* v = next("--ris-samples")) o.risSamples = std::atoi(v), o.risSamplesSet = true;
+    else if (const char* v = next("--ris-clamp")) o.risClamp = (float)std::atof(v), o.risClampSet = true;
+    else if (std::strcmp(argv[i], "--ris-ggx") == 0) o.risGgx = true;
+    else if (std::strcmp(argv[i], "--ris-hints") == 0) o.risHints = true;
     else if (std::strcmp(argv[i], "--direct") == 0) o.direct = true;
     else if (std::strcmp(argv[i], "--direct-hints") == 0) o.directHints = true;
     else if (std::strcmp(argv[i], "--no-motion") == 0) o.noMotion = true;
@@ -426,7 +452,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] [--direct [--direct-hints]] [--sky N [--sky-clamp C] [--sky-mis [--sky-ggx]]] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] [--direct [--direct-hints]] [--sky N [--sky-clamp C] [--sky-mis [--sky-ggx]]] [--ris M [--ris-samples K] [--ris-ggx] [--ris-hints] [--ris-clamp C]] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }
@@ -495,6 +521,22 @@ int main(int argc, char** argv) {
   }
   if ((o.skyMis && o.sky < 0) || (o.skyGgx && !o.skyMis)) {
     std::fprintf(stderr, "bdpt_render: --sky-mis goes with --sky N, and --sky-ggx with --sky-mis\n");
+    return 2;
+  }
+  if (o.ris < 0 && (o.risSamplesSet || o.risGgx || o.risHints || o.risClampSet)) {
+    std::fprintf(stderr, "bdpt_render: --ris-samples K, --ris-ggx, --ris-hints and --ris-clamp C go with --ris M\n");
+    return 2;
+  }
+  if (o.ris >= 0 && (o.ris < 1 || o.ris > (int)BDPT_RIS_MAX_CANDIDATES || o.risSamples < 1 || o.risSamples > (int)BDPT_RIS_MAX_SAMPLES ||
+                     o.gpus > 0 || o.world > 0 || (o.risClampSet && !(o.risClamp > 0.0f)))) {
+    std::fprintf(stderr, "bdpt_render: --ris M needs M in 1 .. %u candidates, --ris-samples K in 1 .. %u, --ris-clamp C > 0 when given, and one GPU "
+                         "(no --gpus / --world)\n", BDPT_RIS_MAX_CANDIDATES, BDPT_RIS_MAX_SAMPLES);
+    return 2;
+  }
+  // --ris replaces the BDPT and denoise passes: the switches only they read are refused, not ignored (--area-lights is read)
+  if (o.ris >= 0 && (o.ao >= 0 || o.gi || o.direct || o.sky >= 0 || o.denoise || o.noMotion)) {
+    std::fprintf(stderr, "bdpt_render: --ris M renders the G-buffer, the resampled direct lighting pass and the accumulation pass only: not with "
+                         "--ao N, --gi, --direct, --sky N, --denoise, --denoise-regression or --no-motion\n");
     return 2;
   }
   if (o.gpus < 0 || o.gpus > 64 || (o.gpus > 0 && o.world > 0)) {

@@ -1681,6 +1681,104 @@ int bdpt_test_env_table(bdpt_ctx* ctx, uint32_t* cdf, uint64_t* rowCdf);
 int bdpt_test_host_env_search(uint32_t width, uint32_t height, const uint32_t* cdf, const uint64_t* rowCdf, const float* r1, const float* r2,
                               uint32_t n, uint32_t* texels);
 
+/* ---- Resampled direct lighting -------------------------------------------------------------------------------------
+ * Direct lighting with one any-hit ray per item and sample whatever the light count: resampled importance sampling (RIS),
+ * the first stage of ReSTIR.  Per sample `candidates` (M) next-event samples of the pass are drawn, one of them is kept in
+ * a one-entry reservoir with probability proportional to its unshadowed, clamped contribution at the item, and one ray is
+ * traced for the survivor; `samples` (K) such estimates are averaged.  The emitter table (BDPT_PARAM_AREA_LIGHTS) is one
+ * more candidate source.  bdpt_direct_query is the converged answer for the scene's lights (without the pass's clamp and
+ * with its own albedo rule); this estimates the clamped next-event term of the pass.
+ *
+ * bdpt_ris_query: item i < min(*numDevice, num) is dead when alive[i] == 0 or surfaces[i].prim < 0.  A dead item takes no
+ * draw: color[i] = (diffuse, 1), traced[i] = 0, seedsOut[i] = seeds[i], its reservoirs are "no selection" records with
+ * wsum = +0 (what bdpt_sky_mis_query gives a dead item).  For an alive item
+ *   s = seeds[i]; sum = 0
+ *   lightsCount as bdpt_light_query has it: numLights, plus one for the table with BDPT_PARAM_AREA_LIGHTS while its W > 0
+ *   for k = 0 .. samples-1:
+ *     wsum = 0; nothing selected
+ *     for c = 0 .. candidates-1:
+ *       (ray_c, value_c, light_c) = what bdpt_light_query(BDPT_LIGHT_NEE, matIndex, flags & BDPT_PARAM_AREA_LIGHTS) returns
+ *         for state s: one draw, s advances once; state_c = s after that draw (the state areaNee forks its three uniforms
+ *         from).  No hint is tried for a candidate.
+ *       u_c = nextRand(s)                                    always taken
+ *       v_c = clampVec(value_c, clampUpper)                  NaN and negative components become +0
+ *       w_c = max(max(v_c.x, v_c.y), v_c.z)                  max(a, b) = b > a ? b : a; never NaN, >= 0
+ *       wsum = wsum + w_c
+ *       candidate c becomes the selection iff w_c > 0 && u_c * wsum <= w_c      (<=: the first positive one is always taken)
+ *     nothing selected: the sample's term is +0, no ray
+ *     otherwise W = (wsum / (float)candidates) / w_sel; term = v_sel * W
+ *       with BDPT_RIS_USE_HINTS, a selected point or spot light whose term has a positive component first tries the light's
+ *         occluder hint, the test bdpt_light_query makes (BDPT_LIGHT_USE_HINTS): occluded, the term counts as +0, no ray
+ *       otherwise ray_sel = (posW, minT, L, distance as bdpt_light_query gives it) is traced as BDPT_TRACE_ANY traces it;
+ *         occluded, the term counts as +0
+ *     sum = sum + term
+ *   color[i] = (sum / (float)samples, 1); seedsOut[i] = s after 2 * candidates * samples draws; traced[i] = rays traversed
+ * Every operation is one fp32 rounding in the order written, without contraction.  The record contract of "Light queries"
+ * applies unchanged: degenerate and non-finite records give what this arithmetic gives, nothing a caller supplies reaches
+ * an address.  With candidates = 1, W is exactly 1 for a finite positive weight and the call is plain next-event
+ * estimation: bdpt_light_query -> bdpt_trace_rays(ANY) -> mask.  The estimator is unbiased for the clamped direct
+ * lighting: the candidates come from one source density whose reciprocal is already inside `value`.
+ * reservoirs (optional): samples records per item, record k of item i at [i * samples + k].  No selection: light 0xffff,
+ * status 0, state 0, W = +0.  status: BDPT_RIS_STATUS_RAY a ray was needed (something was selected),
+ * BDPT_RIS_STATUS_HINT_OCCLUDED the hint answered it, BDPT_RIS_STATUS_OCCLUDED the traced ray was occluded.  `light` and
+ * `state` reproduce the sampled point for any receiver: getLightData serves a light, areaNee(state) the table
+ * (light == numLights) — what a later reuse stage needs.
+ * bdpt_ris_execute runs the same for the context's tile pixels: seeds initRand(x + y * width, frameCount, 16); the
+ * full-frame worldPosition, worldNormal and materialDiffuse, and for matIndex 0 materialSpecRough (specular = rgb, rough =
+ * a * a) with V = normalize(camera position - posW); alive iff worldPosition.w != 0, a background pixel gets (diffuse, 1).
+ * Tiles and stripes reproduce the whole frame.
+ * Both calls are stream-ordered, capturable (one kernel node) and allocate nothing, but for the emitter table, which
+ * follows bdpt_light_query's rule: bdpt_prepare(BDPT_PREPARE_AREA_LIGHTS) makes it, or the first call that needs it does;
+ * that first call inside a capture returns BDPT_E_STATE.
+ * Errors, in this order: a NULL context, desc / params or gbuffer BDPT_E_INVALID; no scene, no size (execute), no camera
+ * (execute with matIndex 0) BDPT_E_STATE; candidates outside 1 .. BDPT_RIS_MAX_CANDIDATES, samples outside 1 ..
+ * BDPT_RIS_MAX_SAMPLES, matIndex > 1, an unknown flag, non-zero reserved, a negative or NaN clampUpper BDPT_E_INVALID;
+ * then num == 0 returns BDPT_OK; then a missing or misaligned buffer BDPT_E_INVALID.  A refused call enqueues nothing. */
+#define BDPT_RIS_USE_HINTS 1u /* flags, beside BDPT_PARAM_AREA_LIGHTS */
+#define BDPT_RIS_MAX_CANDIDATES 32u
+#define BDPT_RIS_MAX_SAMPLES 64u
+#define BDPT_RIS_STATUS_RAY 1u
+#define BDPT_RIS_STATUS_HINT_OCCLUDED 2u
+#define BDPT_RIS_STATUS_OCCLUDED 4u
+#define BDPT_RIS_NO_LIGHT 0xffffu
+typedef struct bdpt_ris_reservoir {
+  uint16_t light;  /* the selected light (numLights = the emitter table), BDPT_RIS_NO_LIGHT when nothing was selected */
+  uint16_t status; /* BDPT_RIS_STATUS_* */
+  uint32_t state;  /* the RNG state after the selection draw of the selected candidate */
+  float W;         /* (wsum / candidates) / w_sel */
+  float wsum;
+} bdpt_ris_reservoir; /* 16 bytes */
+typedef struct bdpt_ris_desc {
+  uint32_t num;                 /* items; the capacity when numDevice is set */
+  uint32_t flags;               /* BDPT_PARAM_AREA_LIGHTS | BDPT_RIS_USE_HINTS */
+  const uint32_t* numDevice;    /* optional device word: min(*numDevice, num) items */
+  uint32_t matIndex;            /* 0 GGX, 1 Lambertian */
+  uint32_t candidates;          /* 1 .. BDPT_RIS_MAX_CANDIDATES */
+  uint32_t samples;             /* 1 .. BDPT_RIS_MAX_SAMPLES */
+  float clampUpper;             /* upper bound of every component of a candidate's value (clampVec); >= 0 */
+  float minT;                   /* tmin of the rays and of the hint test */
+  uint32_t reserved;            /* 0 */
+  const bdpt_surface* surfaces; /* device, 16-byte aligned, num records */
+  const uint8_t* alive;         /* optional: device, one byte per item, 0 = the item is dead */
+  const uint32_t* seeds;        /* device, num RNG states */
+  float* color;                 /* device, 16-byte aligned, num float4 */
+  uint32_t* seedsOut;           /* optional: device, num RNG states (may be `seeds`) */
+  uint32_t* traced;             /* optional: device, num words: the rays traversed */
+  bdpt_ris_reservoir* reservoirs; /* optional: device, 16-byte aligned, num * samples records */
+} bdpt_ris_desc; /* 96 bytes */
+int bdpt_ris_query(bdpt_ctx* ctx, const bdpt_ris_desc* desc, void* stream);
+typedef struct bdpt_ris_params {
+  uint32_t frameCount;
+  float clampUpper;
+  float minT;
+  uint32_t candidates; /* 1 .. BDPT_RIS_MAX_CANDIDATES */
+  uint32_t samples;    /* 1 .. BDPT_RIS_MAX_SAMPLES */
+  uint32_t matIndex;   /* 0 GGX (needs a camera), 1 Lambertian */
+  uint32_t flags;      /* BDPT_PARAM_AREA_LIGHTS | BDPT_RIS_USE_HINTS */
+  uint32_t reserved;   /* 0 */
+} bdpt_ris_params; /* 32 bytes */
+int bdpt_ris_execute(bdpt_ctx* ctx, const bdpt_ris_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
+
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
  * a split triangle covering it, every child box containing its subtree's pieces, depth within the traversal stack.
