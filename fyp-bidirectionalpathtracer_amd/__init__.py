@@ -24,6 +24,7 @@ GI_CHANNEL = "DiffuseGI"  # the channel FramePipeline.diffuse_gi and bdpt_render
 DIRECT_CHANNEL = "DirectLighting"  # the channel FramePipeline.direct_lighting and bdpt_render --direct write
 SKY_CHANNEL = "SkyLighting"  # the channel FramePipeline.sky_lighting and bdpt_render --sky write
 RIS_CHANNEL = "ResampledDirect"  # the channel FramePipeline.ris_lighting and bdpt_render --ris write
+RESTIR_CHANNEL = "RestirDirect"  # the channel FramePipeline.restir_lighting writes
 
 
 class BdptError(RuntimeError):
@@ -1006,10 +1007,12 @@ class Context:
                                    (4, (torch.float32,)), run, out, count, extras=extras, fn="bdpt_ris_query")
 
     def ris_execute(self, gbuffer, out, *, candidates, samples=1, mat_index=1, area_lights=False, use_hints=False,
-                    clamp=float(3.4028234663852886e38), min_t=1e-4, frame_count=0, stream=None):
+                    clamp=float(3.4028234663852886e38), min_t=1e-4, frame_count=0, reservoirs=None, stream=None):
         """bdpt_ris_execute: resampled direct lighting on the context's tile pixels — the full-frame G-buffer (abi.GBuffer)
         and the full-frame (H, W, 4) float32 GPU image `out`, which gets (colour, 1) at the tile's pixels; seeds are
-        initRand(pixel, frame_count).  mat_index 0 needs a camera.  Returns the abi.RisParams used."""
+        initRand(pixel, frame_count).  mat_index 0 needs a camera.  reservoirs (bdpt_ris_execute_reservoirs): a full-frame
+        (H, W, samples, 4) int32 / uint32 GPU image that gets the bdpt_ris_reservoir records of the tile's geometry pixels.
+        Returns the abi.RisParams used."""
         import torch
         candidates, samples, mat, flags, clamp = self._ris_mode("ris_execute", candidates, samples, mat_index, area_lights,
                                                                 use_hints, clamp)
@@ -1022,9 +1025,147 @@ class Context:
         p = abi.RisParams()
         p.frameCount, p.clampUpper, p.minT = int(frame_count) & 0xFFFFFFFF, clamp, float(min_t)
         p.candidates, p.samples, p.matIndex, p.flags = candidates, samples, mat, flags
+        if reservoirs is not None:
+            self._check_gpu(reservoirs, "ris_execute", "reservoirs", frame + (samples, 4), (torch.int32, torch.uint32))
+            self._check(self._lib.bdpt_ris_execute_reservoirs(self._h, C.byref(p), C.byref(gbuffer), C.c_void_p(out.data_ptr()),
+                                                              C.c_void_p(reservoirs.data_ptr()), stream), "bdpt_ris_execute_reservoirs")
+            return p
         self._check(self._lib.bdpt_ris_execute(self._h, C.byref(p), C.byref(gbuffer), C.c_void_p(out.data_ptr()), stream),
                     "bdpt_ris_execute")
         return p
+
+    def reuse_execute(self, gbuffer, out, reservoirs, *, neighbors=0, radius=0, same_pixel=False, neighbor_index=None, pool_gbuffer=None,
+                      pool_reservoirs=None, pool_camera_pos=(0.0, 0.0, 0.0), in_m=0, pool_m=0, max_m=abi.REUSE_MAX_M,
+                      normal_min=float("-inf"), plane_max=float("inf"), mat_index=1, area_lights=False,
+                      clamp=float(3.4028234663852886e38), min_t=1e-4, frame_count=0, reservoirs_out=None, stream=None):
+        """bdpt_reuse_execute: reservoir reuse on the context's tile pixels.  `reservoirs` (H, W, 4) int32 / uint32: the
+        pixels' own records; the pool is pool_gbuffer (abi.GBuffer; None: `gbuffer`) with pool_reservoirs (None:
+        `reservoirs`) and, for mat_index 0, pool_camera_pos.  Neighbours: neighbor_index (H, W, neighbors) of pool pixels, or
+        same_pixel (neighbors 1: the temporal pass), or offsets drawn within `radius`.  `out` (H, W, 4) float32 gets
+        (colour, 1) and reservoirs_out (H, W, 4) the combined records at the tile's pixels; seeds are
+        initRand(initRand(pixel, frame_count), 0x52455553).  The other arguments as reuse_lighting.  Returns the
+        abi.ReuseParams used."""
+        import torch
+        what = "reuse_execute"
+        words = (torch.int32, torch.uint32)
+        _, _, mat, flags, clamp = self._ris_mode(what, 1, 1, mat_index, area_lights, False, clamp)
+        for name, v, top in (("neighbors", neighbors, abi.REUSE_MAX_NEIGHBORS), ("radius", radius, abi.REUSE_MAX_RADIUS),
+                             ("in_m", in_m, 2**32 - 1), ("pool_m", pool_m, 2**32 - 1), ("max_m", max_m, 2**32 - 1)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= top:
+                raise BdptError(f"{what}: {name} must be an integer in 0 .. {top}, not {v!r}")
+        if not isinstance(same_pixel, bool):
+            raise BdptError(f"{what}: same_pixel must be a bool, not {same_pixel!r}")
+        if same_pixel and (neighbor_index is not None or neighbors != 1):
+            raise BdptError(f"{what}: same_pixel goes with neighbors=1 and no neighbor_index")
+        if neighbors and not same_pixel and neighbor_index is None and radius < 1:
+            raise BdptError(f"{what}: drawn offsets need a radius in 1 .. {abi.REUSE_MAX_RADIUS}")
+        for name, g in (("gbuffer", gbuffer), ("pool_gbuffer", gbuffer if pool_gbuffer is None else pool_gbuffer)):
+            if not isinstance(g, abi.GBuffer):
+                raise BdptError(f"{what}: {name} must be an abi.GBuffer")
+        frame = getattr(self, "_frame", None)
+        if frame is None:
+            raise BdptError(f"{what}: no frame size (resize first)")
+        self._check_gpu(out, what, "out", frame + (4,), (torch.float32,))
+        self._check_gpu(reservoirs, what, "reservoirs", frame + (4,), words)
+        pool_reservoirs = reservoirs if pool_reservoirs is None else pool_reservoirs
+        self._check_gpu(pool_reservoirs, what, "pool_reservoirs", frame + (4,), words)
+        if neighbor_index is not None:
+            self._check_gpu(neighbor_index, what, "neighbor_index", frame + (neighbors,), words)
+        if reservoirs_out is not None:
+            self._check_gpu(reservoirs_out, what, "reservoirs_out", frame + (4,), words)
+            if reservoirs_out.data_ptr() in (reservoirs.data_ptr(), pool_reservoirs.data_ptr()):
+                raise BdptError(f"{what}: reservoirs_out must be neither reservoirs nor pool_reservoirs")
+        p = abi.ReuseParams()
+        p.frameCount, p.clampUpper, p.minT, p.matIndex = int(frame_count) & 0xFFFFFFFF, clamp, float(min_t), mat
+        p.flags, p.neighbors, p.radius = flags | (abi.REUSE_SAME_PIXEL if same_pixel else 0), neighbors, radius
+        p.inM, p.poolM, p.maxM, p.normalMin, p.planeMax = in_m, pool_m, max_m, float(normal_min), float(plane_max)
+        p.poolCameraPos = (C.c_float * 3)(*[float(v) for v in pool_camera_pos])
+        setattr(p, "in", reservoirs.data_ptr())
+        pool_gb = gbuffer if pool_gbuffer is None else pool_gbuffer
+        p.poolGbuffer, p.pool = C.pointer(pool_gb), pool_reservoirs.data_ptr()
+        p.neighborIndex = None if neighbor_index is None else neighbor_index.data_ptr()
+        p.outReservoirs = None if reservoirs_out is None else reservoirs_out.data_ptr()
+        self._check(self._lib.bdpt_reuse_execute(self._h, C.byref(p), C.byref(gbuffer), C.c_void_p(out.data_ptr()), stream),
+                    "bdpt_reuse_execute")
+        return p
+
+    # ---- reservoir reuse (include/bdpt.h "Reservoir reuse", DESIGN.md) ----
+    def reuse_lighting(self, surfaces, seeds, reservoirs, neighbor_index=None, pool_surfaces=None, pool_reservoirs=None,
+                       pool_alive=None, in_m=0, pool_m=0, max_m=abi.REUSE_MAX_M, normal_min=float("-inf"), plane_max=float("inf"),
+                       mat_index=1, area_lights=False, clamp=float(3.4028234663852886e38), min_t=1e-4, alive=None, out=None,
+                       seeds_out=None, traced=None, reservoirs_out=None, count=None, stream=None):
+        """bdpt_reuse_query: reservoir reuse, the second stage of ReSTIR.  Per (N, 24) bdpt_surface record its own reservoir
+        (`reservoirs`, (N, 4) int32 / uint32 words: light | status << 16, state, W as float bits, M) and those of the pool
+        entries `neighbor_index` (N, neighbors) names (neighbors 0 .. 8; an index >= the pool's length, such as -1, is no
+        neighbour) are combined by the unbiased 1 / Z rule and one any-hit ray is traced for the survivor — in one launch
+        the loop prev(state) -> sample_lights -> clamp, weight and reservoir update per source, the selected sample again
+        at every neighbour for Z, then trace_rays("any"), bit for bit.  seeds (N,) RNG states: 1 + neighbors draws.  The
+        pool is pool_surfaces (P, 24), pool_reservoirs (P, 4) and the optional pool_alive (P,) uint8, or, when
+        pool_surfaces is None, the items themselves.  in_m / pool_m: non-zero, the candidate count of every own / pool
+        record (bdpt_ris_query's records: its `candidates`), 0: the records' fourth word; max_m caps a pool record's
+        count.  A neighbour needs dot(N, N_p) >= normal_min and |dot(N, pos_p - pos)| <= plane_max.  Returns (N, 4)
+        float32 (colour, 1).  GPU tensors only: alive, seeds_out, traced (N,), reservoirs_out (N, 4), which must be neither
+        `reservoirs` nor pool_reservoirs, neighbor_index and the pool.  `out` and `count` as for the other queries."""
+        import torch
+        what = "reuse_lighting"
+        records, words = (torch.float32, torch.int32), (torch.int32, torch.uint32)
+        _, _, mat, flags, clamp = self._ris_mode(what, 1, 1, mat_index, area_lights, False, clamp)
+        for name, v in (("in_m", in_m), ("pool_m", pool_m), ("max_m", max_m)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2**32:
+                raise BdptError(f"{what}: {name} must be an integer in 0 .. 2^32 - 1, not {v!r}")
+        for name, v in (("normal_min", normal_min), ("plane_max", plane_max)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise BdptError(f"{what}: {name} must be a number, not {v!r}")
+        gpu_in = getattr(surfaces, "is_cuda", False) and surfaces.dim() >= 1
+        n = int(surfaces.shape[0]) if gpu_in else -1
+        own_pool = pool_surfaces is None
+        if own_pool and (pool_reservoirs is not None or pool_alive is not None):
+            raise BdptError(f"{what}: pool_reservoirs and pool_alive go with pool_surfaces")
+        if any(t is not None for t in (neighbor_index, pool_surfaces, reservoirs_out)) and not gpu_in:
+            raise BdptError(f"{what}: neighbor_index, the pool and reservoirs_out go with GPU tensor inputs")
+        neighbors, pool_num = 0, 0
+        if neighbor_index is not None:
+            neighbors = int(neighbor_index.shape[1]) if getattr(neighbor_index, "is_cuda", False) and neighbor_index.dim() == 2 else -1
+            if not 0 <= neighbors <= abi.REUSE_MAX_NEIGHBORS:
+                raise BdptError(f"{what}: neighbor_index must be a GPU tensor (N, 0 .. {abi.REUSE_MAX_NEIGHBORS})")
+            self._check_gpu(neighbor_index, what, "neighbor_index", (n, neighbors), words)
+            if own_pool:
+                pool_surfaces, pool_reservoirs, pool_alive, pool_num = surfaces, reservoirs, alive, n
+            else:
+                pool_num = int(pool_surfaces.shape[0]) if getattr(pool_surfaces, "is_cuda", False) and pool_surfaces.dim() >= 1 else -1
+                if not 0 <= pool_num < 2**32:
+                    raise BdptError(f"{what}: pool_surfaces must be a GPU tensor (P, 24)")
+                self._check_gpu(pool_surfaces, what, "pool_surfaces", (pool_num, 24), records)
+                if pool_reservoirs is None:
+                    raise BdptError(f"{what}: pool_surfaces goes with pool_reservoirs")
+                self._check_gpu(pool_reservoirs, what, "pool_reservoirs", (pool_num, 4), words)
+                if pool_alive is not None:
+                    self._check_gpu(pool_alive, what, "pool_alive", (pool_num,), (torch.uint8,))
+        elif not own_pool:
+            raise BdptError(f"{what}: a pool goes with neighbor_index")
+        if reservoirs_out is not None:
+            self._check_gpu(reservoirs_out, what, "reservoirs_out", (n, 4), words)
+            for name, t in (("reservoirs", reservoirs), ("pool_reservoirs", pool_reservoirs if neighbors else None)):
+                if n and getattr(t, "is_cuda", False) and t.data_ptr() == reservoirs_out.data_ptr():
+                    raise BdptError(f"{what}: reservoirs_out must not be {name}")
+        extras = [("alive", alive, None, (torch.uint8,)), ("seeds_out", seeds_out, None, words), ("traced", traced, None, words)]
+
+        def run(ptrs, n, cnt, res):
+            d = abi.ReuseDesc()
+            d.num, d.flags, d.numDevice, d.matIndex, d.neighbors = n, flags, cnt, mat, neighbors
+            d.inM, d.poolM, d.maxM, d.poolNum = in_m, pool_m, max_m, pool_num
+            d.normalMin, d.planeMax, d.clampUpper, d.minT = float(normal_min), float(plane_max), clamp, float(min_t)
+            d.surfaces, d.seeds, d.color = ptrs[0], ptrs[1], res
+            setattr(d, "in", ptrs[2])
+            d.alive, d.seedsOut, d.traced, d.out = (None if t is None else t.data_ptr() for t in (alive, seeds_out, traced, reservoirs_out))
+            if neighbors:
+                d.poolSurfaces, d.pool, d.neighborIndex = pool_surfaces.data_ptr(), pool_reservoirs.data_ptr(), neighbor_index.data_ptr()
+                d.poolAlive = None if pool_alive is None else pool_alive.data_ptr()
+            return self._lib.bdpt_reuse_query(self._h, C.byref(d), stream)
+
+        return self._surface_query(what, [("surfaces", surfaces, 24, records), ("seeds", seeds, None, words),
+                                          ("reservoirs", reservoirs, 4, words)],
+                                   (4, (torch.float32,)), run, out, count, extras=extras, fn="bdpt_reuse_query")
 
     # ---- diffuse GI (include/bdpt.h "Diffuse GI", DESIGN.md) ----
     def diffuse_gi(self, surfaces, seeds, indirect=True, cosine=True, view_pos=None, normal_map=True, min_t=1e-4, alive=None,
@@ -1648,6 +1789,8 @@ class FramePipeline:
         self.last_sky_params = None
         self.ris_frame = 0
         self.last_ris_params = None
+        self.restir_frame = 0
+        self._restir = None  # restir_lighting's reservoir buffers and history, made on first use
         self.gi_frame = 0x1337  # CommonPasses/SimpleDiffuseGIPass.h:62
         self.last_gi_params = None
         self.accum_count = 0
@@ -1781,10 +1924,12 @@ class FramePipeline:
         self.ctx.update_geometry(positions, normals, bitangents, self._stream_ptr(), keep_light_maps)
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (positions, normals, bitangents))
         self.accum_count = 0
+        self._drop_restir_history()
 
     def set_skin(self, positions, bone_weights, bone_ids, num_bones, normals=None, bitangents=None):
         """Context.set_skin (synchronises: everything this pipeline enqueued has finished when it returns)."""
         self.ctx.set_skin(positions, bone_weights, bone_ids, num_bones, normals, bitangents)
+        self._drop_restir_history()
 
     def update_skinned(self, bones, normal_bones=None, keep_light_maps=False):
         """Pose the skinned scene (Context.update_skinned on this pipeline's stream); accumulation restarts, as after
@@ -1792,11 +1937,13 @@ class FramePipeline:
         self.ctx.update_skinned(bones, normal_bones, self._stream_ptr(), keep_light_maps)
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (bones, normal_bones))
         self.accum_count = 0
+        self._drop_restir_history()
 
     def set_morph(self, target_start, vertex, d_positions, d_normals=None, d_bitangents=None, positions=None, normals=None,
                   bitangents=None):
         """Context.set_morph (synchronises: everything this pipeline enqueued has finished when it returns)."""
         self.ctx.set_morph(target_start, vertex, d_positions, d_normals, d_bitangents, positions, normals, bitangents)
+        self._drop_restir_history()
 
     def update_morphed(self, weights, bones=None, normal_bones=None, keep_light_maps=False):
         """Morph (and pose) the scene (Context.update_morphed on this pipeline's stream); accumulation restarts, as after
@@ -1804,6 +1951,7 @@ class FramePipeline:
         self.ctx.update_morphed(weights, bones, normal_bones, self._stream_ptr(), keep_light_maps)
         keep_for_stream(self.torch.cuda.current_stream(self.dev), (weights, bones, normal_bones))
         self.accum_count = 0
+        self._drop_restir_history()
 
     def trace_rays(self, rays, mode="closest", out=None, count=None):
         """Context.trace_rays on this pipeline's stream, ordered after its frames.  GPU tensors (rays, outputs, count) are
@@ -1992,10 +2140,76 @@ class FramePipeline:
         self.ris_frame += 1
         return out
 
+    def restir_lighting(self, candidates, spatial=0, radius=8, temporal=False, max_m=None, mat_index=1, area_lights=False,
+                        clamp=float(3.4028234663852886e38), normal_min=0.9, plane_max=float("inf")):
+        """ReSTIR direct lighting on this pipeline's G-buffer as it stands and stream, one any-hit ray per pixel and pass:
+        Context.ris_execute with `candidates` candidates, one sample and its reservoirs; with `temporal` and a history, a
+        Context.reuse_execute whose one neighbour is the same pixel of last call's reservoirs, G-buffer copy and camera
+        position; with `spatial` > 0, a Context.reuse_execute over that many neighbours at offsets drawn within `radius`.
+        A pool reservoir counts for at most `max_m` candidates (default 20 * candidates); neighbours must pass normal_min and
+        plane_max.  The pass's frame counter (from 0, one per call) seeds the first stage; the temporal pass runs at twice
+        that count and the spatial pass at twice plus one, so no two passes share a stream.  The last pass's reservoirs,
+        the G-buffer and the camera position become the history of the next call; set_lights and every geometry update drop
+        it, since a history's samples are re-evaluated with the current lights.  Returns the (H, W, 4) float32 channel
+        "RestirDirect", also in ``channels``.  A tile or stripes pipeline raises BdptError: ranks do not exchange
+        reservoirs."""
+        torch = self.torch
+        if self.stripes is not None or (self.y0, self.y1) != (0, self.H):
+            raise BdptError("restir_lighting: a tile or stripes pipeline cannot reuse reservoirs (its neighbours and history lie on other ranks)")
+        for name, v, top in (("spatial", spatial, abi.REUSE_MAX_NEIGHBORS), ("radius", radius, abi.REUSE_MAX_RADIUS)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= top:
+                raise BdptError(f"restir_lighting: {name} must be an integer in 0 .. {top}, not {v!r}")
+        if not isinstance(temporal, bool):
+            raise BdptError(f"restir_lighting: temporal must be a bool, not {temporal!r}")
+        candidates, _, _, _, clamp = Context._ris_mode("restir_lighting", candidates, 1, mat_index, area_lights, False, clamp)
+        max_m = 20 * candidates if max_m is None else max_m
+        if isinstance(max_m, bool) or not isinstance(max_m, int) or not 1 <= max_m < 2**32:
+            raise BdptError(f"restir_lighting: max_m must be an integer in 1 .. 2^32 - 1, not {max_m!r}")
+        if spatial and radius < 1:
+            raise BdptError("restir_lighting: spatial neighbours need a radius of at least 1")
+        out = self._pass_channel(RESTIR_CHANNEL)
+        st = self._restir
+        if st is None:
+            with torch.cuda.device(self.dev):
+                st = self._restir = dict(
+                    res=[torch.zeros(self.H, self.W, 4, dtype=torch.int32, device=self.dev) for _ in range(4)],  # history, and one per pass
+                    channels=[torch.zeros_like(self.channels[n]) for n in GBUFFER_CHANNELS[:4]], cam=(0.0, 0.0, 0.0), valid=False,
+                    m=0)  # m: the candidate count of every history record; 0: the records' M words (a reuse pass wrote them)
+                st["gb"] = GBuffer(*([t.data_ptr() for t in st["channels"]] + [None, None]))
+        hist, first, second, third = st["res"]
+        frame, stream = self.restir_frame, self._stream_ptr()
+        cam = tuple(float(v) for v in self.cam.posW)
+        common = dict(mat_index=mat_index, area_lights=area_lights, clamp=clamp, min_t=self.min_t, stream=stream)
+        self.ctx.ris_execute(self.gb, out, candidates=candidates, samples=1, frame_count=frame, reservoirs=first.view(self.H, self.W, 1, 4),
+                             **common)
+        cur, in_m = first, candidates
+        if temporal and st["valid"]:
+            self.ctx.reuse_execute(self.gb, out, cur, neighbors=1, same_pixel=True, pool_gbuffer=st["gb"], pool_reservoirs=hist,
+                                   pool_camera_pos=st["cam"], in_m=in_m, pool_m=st["m"], max_m=max_m, normal_min=normal_min, plane_max=plane_max,
+                                   frame_count=2 * frame, reservoirs_out=second, **common)
+            cur, in_m = second, 0
+        if spatial:
+            self.ctx.reuse_execute(self.gb, out, cur, neighbors=spatial, radius=radius, pool_camera_pos=cam, in_m=in_m, pool_m=in_m, max_m=max_m,
+                                   normal_min=normal_min, plane_max=plane_max, frame_count=2 * frame + 1, reservoirs_out=third, **common)
+            cur, in_m = third, 0
+        # The history of the next call.  A background pixel's record may be stale (the first stage does not write it): a
+        # dead pool pixel is rejected before its record is read, which holds as long as these copies are made together.
+        hist.copy_(cur)
+        for dst, name in zip(st["channels"], GBUFFER_CHANNELS[:4]):
+            dst.copy_(self.channels[name])
+        st["cam"], st["valid"], st["m"] = cam, True, in_m  # (a first stage's records end in wsum: their count is the call's)
+        self.restir_frame += 1
+        return out
+
+    def _drop_restir_history(self):
+        if self._restir is not None:
+            self._restir["valid"] = False
+
     def set_lights(self, lights):
         """Move the scene's lights (Context.set_lights on this pipeline's stream); accumulation restarts."""
         self.ctx.set_lights(lights, self._stream_ptr())
         self.accum_count = 0
+        self._drop_restir_history()
 
     def close(self):
         self.ctx.close()

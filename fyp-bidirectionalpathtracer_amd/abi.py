@@ -406,6 +406,33 @@ class RisParams(C.Structure):
                 ("samples", C.c_uint32), ("matIndex", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+REUSE_MAX_NEIGHBORS, REUSE_MAX_M = 8, 1 << 24
+REUSE_SAME_PIXEL = 1  # bdpt_reuse_params::flags, beside PARAM_AREA_LIGHTS
+REUSE_MAX_RADIUS = 1024
+
+
+class ReuseReservoir(C.Structure):
+    _fields_ = [("light", C.c_uint16), ("status", C.c_uint16), ("state", C.c_uint32), ("W", C.c_float), ("M", C.c_uint32)]
+
+
+class ReuseDesc(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("flags", C.c_uint32), ("numDevice", C.c_void_p), ("matIndex", C.c_uint32),
+                ("neighbors", C.c_uint32), ("inM", C.c_uint32), ("poolM", C.c_uint32), ("maxM", C.c_uint32), ("poolNum", C.c_uint32),
+                ("normalMin", C.c_float), ("planeMax", C.c_float), ("clampUpper", C.c_float), ("minT", C.c_float),
+                ("reserved", C.c_uint32 * 2), ("surfaces", C.c_void_p), ("alive", C.c_void_p), ("seeds", C.c_void_p),
+                ("in", C.c_void_p), ("poolSurfaces", C.c_void_p), ("poolAlive", C.c_void_p), ("pool", C.c_void_p),
+                ("neighborIndex", C.c_void_p), ("color", C.c_void_p), ("seedsOut", C.c_void_p), ("traced", C.c_void_p),
+                ("out", C.c_void_p)]  # `in` is a Python keyword: setattr(desc, "in", pointer)
+
+
+class ReuseParams(C.Structure):
+    _fields_ = [("frameCount", C.c_uint32), ("clampUpper", C.c_float), ("minT", C.c_float), ("matIndex", C.c_uint32),
+                ("flags", C.c_uint32), ("neighbors", C.c_uint32), ("radius", C.c_uint32), ("inM", C.c_uint32), ("poolM", C.c_uint32),
+                ("maxM", C.c_uint32), ("normalMin", C.c_float), ("planeMax", C.c_float), ("poolCameraPos", C.c_float * 3),
+                ("reserved", C.c_uint32), ("in", C.c_void_p), ("poolGbuffer", C.POINTER(GBuffer)), ("pool", C.c_void_p),
+                ("neighborIndex", C.c_void_p), ("outReservoirs", C.c_void_p)]
+
+
 BMFR_MAX_PLANES = BDPT_MAX_LIGHTS + 2
 
 
@@ -477,6 +504,9 @@ PROTOTYPES = {
     "bdpt_sky_mis_execute": (C.c_int, [C.c_void_p, C.POINTER(SkyMisParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_ris_query": (C.c_int, [C.c_void_p, C.POINTER(RisDesc), C.c_void_p]),
     "bdpt_ris_execute": (C.c_int, [C.c_void_p, C.POINTER(RisParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "bdpt_ris_execute_reservoirs": (C.c_int, [C.c_void_p, C.POINTER(RisParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdpt_reuse_query": (C.c_int, [C.c_void_p, C.POINTER(ReuseDesc), C.c_void_p]),
+    "bdpt_reuse_execute": (C.c_int, [C.c_void_p, C.POINTER(ReuseParams), C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
     "bdpt_host_env_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "bdpt_host_env_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                         C.c_void_p]),

@@ -1,8 +1,8 @@
 // api_query.cpp — the per-item queries of the C ABI (include/bdpt.h): bdpt_trace_rays, bdpt_camera_rays, bdpt_shade_hits,
 // bdpt_bsdf_query, bdpt_light_query, bdpt_connect_query, bdpt_splat_add, bdpt_walk_query, bdpt_ao_query, bdpt_gi_query,
-// bdpt_direct_query, bdpt_env_query, bdpt_sky_query, bdpt_bsdf_pdf_query, bdpt_sky_mis_query, bdpt_ris_query and bdpt_motion_query, on a
+// bdpt_direct_query, bdpt_env_query, bdpt_sky_query, bdpt_bsdf_pdf_query, bdpt_sky_mis_query, bdpt_ris_query, bdpt_reuse_query and bdpt_motion_query, on a
 // caller's arrays in device memory, and bdpt_ao_execute, bdpt_gi_execute, bdpt_direct_execute, bdpt_sky_execute,
-// bdpt_sky_mis_execute and bdpt_ris_execute, the same kernels on the tile's G-buffer
+// bdpt_sky_mis_execute, bdpt_ris_execute, bdpt_ris_execute_reservoirs and bdpt_reuse_execute, the same kernels on the tile's G-buffer
 // pixels.  Every one checks its arguments in a fixed order — the context's state (BDPT_E_STATE), then mode, flags and what goes together
 // (BDPT_E_INVALID), then an empty call returns BDPT_OK, then the pointers — and a refused call enqueues nothing.  What is left goes through enqueueQuery.  None allocates or synchronises (but bdpt_light_query's
 // first use of the emitter table), so all can be captured into a hipGraph.
@@ -627,7 +627,10 @@ int bdpt_ris_query(bdpt_ctx* c, const bdpt_ris_desc* d, void* stream) {
   });
 }
 
-int bdpt_ris_execute(bdpt_ctx* c, const bdpt_ris_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
+namespace {
+// bdpt_ris_execute, and with wantReservoirs bdpt_ris_execute_reservoirs: the full-frame reservoir image beside `out`
+int risExecute(bdpt_ctx* c, const bdpt_ris_params* p, const bdpt_gbuffer* gb, float* out, bdpt_ris_reservoir* reservoirs, bool wantReservoirs,
+               void* stream) {
   if (!c || !p || !gb) return BDPT_E_INVALID;
   if (int rc = needScene(c, "ris_execute")) return rc;
   if (int rc = needFrame(c, "ris_execute")) return rc;
@@ -637,11 +640,14 @@ int bdpt_ris_execute(bdpt_ctx* c, const bdpt_ris_params* p, const bdpt_gbuffer* 
   if (!risModeOk(p->candidates, p->samples, p->matIndex, p->flags, p->clampUpper) || p->reserved)
     return refuse(c, BDPT_E_INVALID, "ris_execute", kRisModeWhy);
   if (int rc = checkGbuffer(c, "ris_execute", gb, out, true, ggx)) return rc;
+  if (wantReservoirs && !aligned(reservoirs, 16))
+    return refuse(c, BDPT_E_INVALID, "ris_execute_reservoirs", "reservoirs missing or not aligned (16 bytes)");
   AreaDev A;
   if (int rc = risArea(c, p->flags, stream, A)) return rc;
   return enqueueQuery(c, stream, [&](hipStream_t st) {
     RisDev Q{};
     fillGbuffer(Q, c, gb, out, p->minT);
+    Q.reservoirs = reinterpret_cast<uint4*>(reservoirs);
     Q.gbDiffuse = gb->materialDiffuse;
     Q.gbSpecRough = gb->materialSpecRough;
     if (ggx)
@@ -651,6 +657,125 @@ int bdpt_ris_execute(bdpt_ctx* c, const bdpt_ris_params* p, const bdpt_gbuffer* 
     Q.samples = p->samples;
     Q.frameCount = p->frameCount;
     launchRis(c->scene.S, Q, A, true, ggx, (p->flags & BDPT_RIS_USE_HINTS) != 0, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+}  // namespace
+int bdpt_ris_execute(bdpt_ctx* c, const bdpt_ris_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
+  return risExecute(c, p, gb, out, nullptr, false, stream);
+}
+int bdpt_ris_execute_reservoirs(bdpt_ctx* c, const bdpt_ris_params* p, const bdpt_gbuffer* gb, float* out, bdpt_ris_reservoir* reservoirs,
+                                void* stream) {
+  return risExecute(c, p, gb, out, reservoirs, true, stream);
+}
+
+static_assert(sizeof(bdpt_reuse_desc) == 160 && offsetof(bdpt_reuse_desc, surfaces) == 64 && sizeof(bdpt_reuse_reservoir) == 16 &&
+                  offsetof(bdpt_reuse_reservoir, M) == 12,
+              "abi.ReuseDesc restates this layout; reuse_kernel reads and writes a reservoir as one uint4");
+namespace {
+bool reuseModeOk(uint32_t neighbors, uint32_t matIndex, float clampUpper) {
+  return neighbors <= BDPT_REUSE_MAX_NEIGHBORS && matIndex <= 1 && clampUpper >= 0.0f;  // (a NaN fails the comparison)
+}
+const char* const kReuseModeWhy =
+    "neighbors > BDPT_REUSE_MAX_NEIGHBORS, matIndex > 1, unknown flags, non-zero reserved, or a negative or NaN clampUpper";
+}  // namespace
+int bdpt_reuse_query(bdpt_ctx* c, const bdpt_reuse_desc* d, void* stream) {
+  if (!c || !d) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "reuse_query")) return rc;
+  if (!reuseModeOk(d->neighbors, d->matIndex, d->clampUpper) || (d->flags & ~BDPT_PARAM_AREA_LIGHTS) || d->reserved[0] || d->reserved[1])
+    return refuse(c, BDPT_E_INVALID, "reuse_query", kReuseModeWhy);
+  if (!d->num) return BDPT_OK;
+  const bool pooled = d->neighbors && d->poolNum;  // without either no pool entry is read
+  if (int rc = checkRecords(c, "reuse_query", "surfaces, seeds, in, poolSurfaces, pool, neighborIndex, color, seedsOut, traced, out or numDevice",
+                            {{d->surfaces, 16}, {d->seeds, 4}, {d->in, 16}, {d->poolSurfaces, 16, !pooled}, {d->pool, 16, !pooled},
+                             {d->neighborIndex, 4, !d->neighbors}, {d->color, 16}, {d->seedsOut, 4, true}, {d->traced, 4, true},
+                             {d->out, 16, true}, {d->numDevice, 4, true}}))
+    return rc;
+  if (d->out && (d->out == d->in || d->out == d->pool))
+    return refuse(c, BDPT_E_INVALID, "reuse_query", "out must not be in or pool: other items read those records");
+  AreaDev A;
+  if (int rc = risArea(c, d->flags, stream, A)) return rc;
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    ReuseDev Q{};
+    fillRecords<true>(Q, d);
+    Q.color = f4(d->color);
+    Q.traced = d->traced;
+    Q.in = reinterpret_cast<const uint4*>(d->in);
+    Q.res = reinterpret_cast<uint4*>(d->out);
+    Q.poolSurf = f4(d->poolSurfaces);
+    Q.poolAlive = d->poolAlive;
+    Q.pool = reinterpret_cast<const uint4*>(d->pool);
+    Q.neighborIndex = d->neighborIndex;
+    Q.poolNum = pooled ? d->poolNum : 0u;
+    Q.neighbors = d->neighbors;
+    Q.inM = d->inM;
+    Q.poolM = d->poolM;
+    Q.maxM = d->maxM;
+    Q.normalMin = d->normalMin;
+    Q.planeMax = d->planeMax;
+    Q.clampUpper = d->clampUpper;
+    launchReuse(c->scene.S, Q, A, false, d->matIndex == 0, c->rayCursor, c->grids, c->numCUs, st);
+  });
+}
+
+static_assert(sizeof(bdpt_reuse_params) == 104 && offsetof(bdpt_reuse_params, in) == 64, "abi.ReuseParams restates this layout");
+int bdpt_reuse_execute(bdpt_ctx* c, const bdpt_reuse_params* p, const bdpt_gbuffer* gb, float* out, void* stream) {
+  if (!c || !p || !gb) return BDPT_E_INVALID;
+  if (int rc = needScene(c, "reuse_execute")) return rc;
+  if (int rc = needFrame(c, "reuse_execute")) return rc;
+  const bool ggx = p->matIndex == 0;  // V comes from the camera
+  if (ggx)
+    if (int rc = needCamera(c, "reuse_execute: matIndex 0")) return rc;
+  if (!reuseModeOk(p->neighbors, p->matIndex, p->clampUpper) || (p->flags & ~(BDPT_PARAM_AREA_LIGHTS | BDPT_REUSE_SAME_PIXEL)) || p->reserved)
+    return refuse(c, BDPT_E_INVALID, "reuse_execute", kReuseModeWhy);
+  const bool same = (p->flags & BDPT_REUSE_SAME_PIXEL) != 0;
+  const bool drawn = p->neighbors && !same && !p->neighborIndex;
+  if ((same && (p->neighborIndex || p->neighbors != 1)) || (drawn && (p->radius < 1 || p->radius > BDPT_REUSE_MAX_RADIUS)))
+    return refuse(c, BDPT_E_INVALID, "reuse_execute",
+                  "neighbours come from one source: neighborIndex, BDPT_REUSE_SAME_PIXEL with neighbors 1, or a radius in 1 .. BDPT_REUSE_MAX_RADIUS");
+  if (int rc = checkGbuffer(c, "reuse_execute", gb, out, true, ggx)) return rc;
+  if (p->neighbors) {
+    if (!p->poolGbuffer) return refuse(c, BDPT_E_INVALID, "reuse_execute", "poolGbuffer missing");
+    if (int rc = checkGbuffer(c, "reuse_execute: poolGbuffer", p->poolGbuffer, out, true, ggx)) return rc;
+  }
+  if (int rc = checkRecords(c, "reuse_execute", "in, pool, neighborIndex or outReservoirs",
+                            {{p->in, 16}, {p->pool, 16, !p->neighbors}, {p->neighborIndex, 4, true}, {p->outReservoirs, 16, true}}))
+    return rc;
+  if (p->outReservoirs && (p->outReservoirs == p->in || p->outReservoirs == p->pool))
+    return refuse(c, BDPT_E_INVALID, "reuse_execute", "outReservoirs must not be in or pool: other pixels read those records");
+  AreaDev A;
+  if (int rc = risArea(c, p->flags, stream, A)) return rc;
+  return enqueueQuery(c, stream, [&](hipStream_t st) {
+    ReuseDev Q{};
+    fillGbuffer(Q, c, gb, out, p->minT);
+    Q.gbDiffuse = gb->materialDiffuse;
+    Q.gbSpecRough = gb->materialSpecRough;
+    Q.in = reinterpret_cast<const uint4*>(p->in);
+    Q.res = reinterpret_cast<uint4*>(p->outReservoirs);
+    if (p->neighbors) {
+      Q.poolGbPosition = f4(p->poolGbuffer->worldPosition);
+      Q.poolGbNormal = p->poolGbuffer->worldNormal;
+      Q.poolGbDiffuse = p->poolGbuffer->materialDiffuse;
+      Q.poolGbSpecRough = p->poolGbuffer->materialSpecRough;
+      Q.pool = reinterpret_cast<const uint4*>(p->pool);
+      Q.neighborIndex = p->neighborIndex;
+      Q.poolNum = c->frame.W * c->frame.H;
+    }
+    for (int k = 0; k < 3; k++) {
+      Q.camPos[k] = ggx ? c->cam.posW[k] : 0.0f;
+      Q.poolCamPos[k] = p->poolCameraPos[k];
+    }
+    Q.neighbors = p->neighbors;
+    Q.inM = p->inM;
+    Q.poolM = p->poolM;
+    Q.maxM = p->maxM;
+    Q.normalMin = p->normalMin;
+    Q.planeMax = p->planeMax;
+    Q.clampUpper = p->clampUpper;
+    Q.frameCount = p->frameCount;
+    Q.width = c->frame.W;
+    Q.height = c->frame.H;
+    Q.radius = drawn ? p->radius : 0u;
+    launchReuse(c->scene.S, Q, A, true, ggx, c->rayCursor, c->grids, c->numCUs, st);
   });
 }
 

@@ -1,5 +1,5 @@
 // device_light.hpp — one next-event candidate of the pass on a caller's surface point: the text bdpt_light_query(NEE)
-// (light_query.hip) and the resampled direct lighting kernel (ris.hip) share.  It is the light part of genNeeLane
+// (light_query.hip), the resampled direct lighting kernel (ris.hip) and its reuse stage (reuse.hip) share.  It is the light part of genNeeLane
 // (kernels.hip, which keeps its own text): the uniform light choice from one draw, getLightData or the emitter table's
 // areaNee, and directIfVisible.  Every step is the pass's own device function; nothing is restated here.
 #pragma once
@@ -26,14 +26,14 @@ struct LightCandidate {
   float dist;
 };
 
-// The candidate of selection draw `r` at `pos`; `state` is the RNG state after that draw, from which areaNee forks its
-// three uniforms (by value: the caller's state does not advance).  Returns the unweighted, unclamped value of a visible
-// light, bdpt_light_sample::value.  V, spec and rough are read by the GGX form only.
+// The candidate that is light `lightToSample` (0 .. lightsCount - 1: the caller checks) at `pos`; `state` is the RNG state
+// after the selection draw that chose it, from which areaNee forks its three uniforms (by value: the caller's state does
+// not advance).  The emitter point does not depend on `pos`, so (light, state) names one light sample for every receiver:
+// what reservoir reuse (reuse.hip) re-evaluates.  Returns the unweighted, unclamped value of a visible light,
+// bdpt_light_sample::value.  V, spec and rough are read by the GGX form only.
 template <bool GGX, bool AREA>
-BD f3 lightCandidate(const SceneDev& S, const AreaDev& A, float areaW, int lightsCount, float r, uint32_t state, f3 pos, f3 N, f3 V,
-                     f3 dif, f3 spec, float rough, LightCandidate& c) {
-  int lightToSample = (int)(r * (float)lightsCount);
-  if (lightToSample > lightsCount - 1) lightToSample = lightsCount - 1;
+BD f3 lightGiven(const SceneDev& S, const AreaDev& A, float areaW, int lightsCount, int lightToSample, uint32_t state, f3 pos, f3 N, f3 V,
+                 f3 dif, f3 spec, float rough, LightCandidate& c) {
   f3 L, lightIntensity;
   float distToLight;
   const bool area = AREA && lightToSample == (int)S.numLights;
@@ -48,6 +48,15 @@ BD f3 lightCandidate(const SceneDev& S, const AreaDev& A, float areaW, int light
   c.L = L;
   c.dist = distToLight;
   return directIfVisible<GGX>((float)lightsCount, L, lightIntensity, N, V, dif, spec, rough);
+}
+
+// The candidate of selection draw `r` at `pos`: the uniform light choice, then lightGiven (`state`: after that draw).
+template <bool GGX, bool AREA>
+BD f3 lightCandidate(const SceneDev& S, const AreaDev& A, float areaW, int lightsCount, float r, uint32_t state, f3 pos, f3 N, f3 V,
+                     f3 dif, f3 spec, float rough, LightCandidate& c) {
+  int lightToSample = (int)(r * (float)lightsCount);
+  if (lightToSample > lightsCount - 1) lightToSample = lightsCount - 1;
+  return lightGiven<GGX, AREA>(S, A, areaW, lightsCount, lightToSample, state, pos, N, V, dif, spec, rough, c);
 }
 
 #undef BD

@@ -314,6 +314,7 @@ struct LaunchGrids {
   uint32_t sky[2] = {0, 0};           // [G-buffer source] (sky.hip)
   uint32_t skyMis[4] = {0, 0, 0, 0};  // [G-buffer source][GGX] (sky_mis.hip)
   uint32_t ris[16] = {};              // [G-buffer source][GGX][AREA][HINTS] (ris.hip)
+  uint32_t reuse[8] = {};             // [G-buffer source][GGX][AREA] (reuse.hip)
 };
 // both random walks of the frame: one persistent launch (trace + hit/miss shading in place)
 void launchWalk(const SceneDev& S, const FrameDev& F, const PathBuf& P, const FrameVariant& V, LaunchGrids& G, int numCUs,
@@ -484,7 +485,7 @@ struct RisDev {  // fields without a comment: the item source (device_item_sourc
   float4* color;
   uint32_t* seedsOut;           // query, optional: the state after 2 * candidates * samples draws (a dead item's: unchanged)
   uint32_t* traced;             // query, optional: the rays traversed per item (0 .. samples)
-  uint4* reservoirs;            // query, optional: samples records per item, item-major (bdpt_ris_reservoir)
+  uint4* reservoirs;            // optional: samples records per item, item-major (bdpt_ris_reservoir); execute: per frame pixel
   const float4* gbPosition;
   const uint16_t* gbNormal;
   const uint16_t* gbDiffuse;
@@ -501,6 +502,48 @@ struct RisDev {  // fields without a comment: the item source (device_item_sourc
 // A.n > 0: the AREA instances (the emitter table is light numLights while its W is positive).  `cursor`: as launchTraceRays
 void launchRis(const SceneDev& S, const RisDev& Q, const AreaDev& A, bool gbuffer, bool ggx, bool hints, unsigned long long* cursor,
                LaunchGrids& G, int numCUs, hipStream_t st);
+// reuse.hip: bdpt_reuse_query (items and pool entries are bdpt_surface records) and bdpt_reuse_execute (items are the
+// tile's pixels, pool entries the pixels of a full-frame pool G-buffer).  Per alive item its own reservoir and those of up
+// to eight pool entries are combined into one (the 1 / Z combination), and one any-hit ray is traced for the survivor
+// (include/bdpt.h "Reservoir reuse").
+struct ReuseDev {  // fields without a comment: the item source (device_item_source.hpp)
+  const float4* surf;           // posW, N, linearRoughness, diffuse and prim are read; GGX also V and specular
+  const uint32_t* seeds;
+  const uint8_t* alive;
+  float4* color;
+  uint32_t* seedsOut;           // query, optional: the state after 1 + neighbors draws (a dead item's: unchanged)
+  uint32_t* traced;             // query, optional: 1 where a ray was traversed
+  const float4* gbPosition;
+  const uint16_t* gbNormal;
+  const uint16_t* gbDiffuse;
+  const uint16_t* gbSpecRough;  // GGX only: specular = rgb, rough = a * a
+  const uint32_t* pix;
+  float4* out;
+  const uint4* in;              // the items' own records (bdpt_reuse_reservoir): per item, execute: per frame pixel
+  uint4* res;                   // optional: the combined records, indexed as `in`
+  const float4* poolSurf;       // query: the pool's records, as `surf`,
+  const uint8_t* poolAlive;     //   and optional alive bytes
+  const float4* poolGbPosition; // execute: the pool's full-frame G-buffer, as the item's
+  const uint16_t* poolGbNormal;
+  const uint16_t* poolGbDiffuse;
+  const uint16_t* poolGbSpecRough;
+  const uint4* pool;            // the pool's reservoirs
+  const uint32_t* neighborIndex;  // neighbors pool indices per item; execute, optional: per frame pixel
+  QueryRange range;
+  float camPos[3];              // execute, GGX: V = normalize(camPos - posW) of an item,
+  float poolCamPos[3];          //   and of a pool pixel
+  uint32_t poolNum;             // execute: width * height
+  uint32_t neighbors;           // 0 .. 8
+  uint32_t inM, poolM, maxM;    // candidate counts (0: the record's M word)
+  float normalMin, planeMax;    // a neighbour's rejection tests
+  float clampUpper;
+  uint32_t frameCount;          // execute
+  uint32_t width, height;       // execute: the frame
+  uint32_t radius;              // execute without neighborIndex: 0 = slot 0 is the item's own pixel, else drawn offsets
+};
+// A.n > 0: the AREA instances.  `cursor`: as launchTraceRays
+void launchReuse(const SceneDev& S, const ReuseDev& Q, const AreaDev& A, bool gbuffer, bool ggx, unsigned long long* cursor, LaunchGrids& G,
+                 int numCUs, hipStream_t st);
 void launchGather(const FrameDev& F, const PathBuf& P, const FrameVariant& V, uint32_t* lazyList, uint32_t* lazyCount, hipStream_t st);
 void launchLazyGen(const FrameDev& F, const PathBuf& P, const uint32_t* list, const uint32_t* listCount, int batch, hipStream_t st);
 void launchLazyCheck(const FrameDev& F, const PathBuf& P, const FrameVariant& V, const uint32_t* list, const uint32_t* listCount,

@@ -89,9 +89,11 @@ __device__ __forceinline__ RisShading risShading(const RisDev& Q, uint32_t i, f3
   return sd;
 }
 
-// the reservoir record of sample `k` of item `i`: (light | status << 16, the selected state, W, wsum)
+// the reservoir record of sample `k` of item `i`: (light | status << 16, the selected state, W, wsum); a pixel's records
+// lie at its place in the full frame (bdpt_ris_execute_reservoirs)
+template <int SRC>
 __device__ __forceinline__ void risStoreReservoir(const RisDev& Q, uint32_t i, uint32_t k, uint4 rec) {
-  if (Q.reservoirs) Q.reservoirs[(size_t)i * Q.samples + k] = rec;
+  if (Q.reservoirs) Q.reservoirs[(size_t)(SRC == ITEM_SRC_SURFACES ? i : Q.pix[i]) * Q.samples + k] = rec;
 }
 // the outputs of item `i` but its reservoir records
 template <int SRC>
@@ -140,7 +142,7 @@ __device__ __forceinline__ bool risNext(const SceneDev& S, const RisDev& Q, cons
     }
     const uint32_t kk = k++;
     if (sel.light < 0) {
-      risStoreReservoir(Q, i, kk, make_uint4(kRisNoLight, 0u, 0u, __float_as_uint(wsum)));
+      risStoreReservoir<SRC>(Q, i, kk, make_uint4(kRisNoLight, 0u, 0u, __float_as_uint(wsum)));
       continue;
     }
     const float W = (wsum / (float)M) / wSel;
@@ -151,7 +153,7 @@ __device__ __forceinline__ bool risNext(const SceneDev& S, const RisDev& Q, cons
       if (positive && !sel.area && S.sc->lights[sel.light].type != BDPT_LIGHT_DIRECTIONAL &&
           recOccludes(S, lightHint(S, sel.light, ld3(S.sc->lights[sel.light].posW), pos), pos, sel.L, Q.range.minT, sel.dist)) {
         // the light's nearest triangle toward the item occludes the segment: no traversal, the term counts as +0
-        risStoreReservoir(Q, i, kk, make_uint4(word | (BDPT_RIS_STATUS_HINT_OCCLUDED << 16), stateSel, __float_as_uint(W), __float_as_uint(wsum)));
+        risStoreReservoir<SRC>(Q, i, kk, make_uint4(word | (BDPT_RIS_STATUS_HINT_OCCLUDED << 16), stateSel, __float_as_uint(W), __float_as_uint(wsum)));
         continue;
       }
     }
@@ -188,8 +190,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(AREA ? BD
       // the background: the diffuse channel holds the colour, no draw, no selection; the lane stays idle.  Only a record's
       // state is stored (unchanged); a pixel's initRand is not made for nothing.
       risStore<SRC>(Q, item, itemDiffuse<SRC>(Q, item), 0u, SRC == ITEM_SRC_SURFACES ? itemSeed<SRC>(Q, item) : 0u);
-      if (SRC == ITEM_SRC_SURFACES && Q.reservoirs)
-        for (uint32_t j = 0; j < Q.samples; j++) risStoreReservoir(Q, item, j, make_uint4(kRisNoLight, 0u, 0u, 0u));
+      if (SRC == ITEM_SRC_SURFACES && Q.reservoirs)  // (a background pixel's records are not written: no stage reads them)
+        for (uint32_t j = 0; j < Q.samples; j++) risStoreReservoir<SRC>(Q, item, j, make_uint4(kRisNoLight, 0u, 0u, 0u));
       return;
     }
     rid = item;
@@ -208,7 +210,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(AREA ? BD
         sum = sum + pend;  // unoccluded
       else
         res.x |= BDPT_RIS_STATUS_OCCLUDED << 16;
-      risStoreReservoir(Q, rid, k - 1u, res);
+      risStoreReservoir<SRC>(Q, rid, k - 1u, res);
       T.cur = kDone;
     }
     if (parkedDue<BDPT_RIS_REGEN_MIN>(has && !flying, flying) && has && !flying) {

@@ -891,6 +891,131 @@ void ResampledDirectPass::execute(RenderContext* pRenderContext) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// RestirDirectPass (include/bdpt.h "Reservoir reuse"; FramePipeline.restir_lighting of the Python package is the same sequence)
+// ------------------------------------------------------------------------------------------------
+bool RestirDirectPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
+  mpResManager = pResManager;
+  mpResManager->requestTextureResources({"WorldPosition", "WorldNormal", "MaterialDiffuse", "MaterialSpecRough"});
+  mpResManager->requestTextureResource(mOutputBuf);
+  mpRays = RayLaunch::create(pRenderContext);
+  if (!mpRays) return false;
+  if (mpScene) mpRays->setScene(mpScene);
+  return true;
+}
+void RestirDirectPass::initScene(RenderContext*, Scene::SharedPtr pScene) {
+  mpScene = pScene;
+  mHistoryValid = false;
+  if (mpRays) mpRays->setScene(mpScene);
+}
+bool RestirDirectPass::ensureBuffers(uint32_t w, uint32_t h) {
+  if (mHist && mHist->getWidth() == w && mHist->getHeight() == h) return true;
+  mHistoryValid = false;
+  for (Texture::SharedPtr* t : {&mHist, &mFirst, &mSecond, &mThird, &mHistPos}) *t = Texture::create2D(w, h, ResourceFormat::RGBA32Float);
+  for (Texture::SharedPtr* t : {&mHistNrm, &mHistDif, &mHistSpec}) *t = Texture::create2D(w, h, ResourceFormat::RGBA16Float);
+  return mHist && mFirst && mSecond && mThird && mHistPos && mHistNrm && mHistDif && mHistSpec;
+}
+void RestirDirectPass::execute(RenderContext* pRenderContext) {
+  Texture::SharedPtr pDstTex = mpResManager->getClearedTexture(mOutputBuf, vec4{0.0f, 0.0f, 0.0f, 0.0f});
+  if (!pDstTex || !mpRays || !mpRays->readyToRender()) return;
+  Texture::SharedPtr pos = mpResManager->getTexture("WorldPosition"), nrm = mpResManager->getTexture("WorldNormal"),
+                     dif = mpResManager->getTexture("MaterialDiffuse"), spec = mpResManager->getTexture("MaterialSpecRough");
+  if (!pos || !nrm || !dif || !spec || pos->getFormat() != ResourceFormat::RGBA32Float || nrm->getFormat() != ResourceFormat::RGBA16Float ||
+      dif->getFormat() != ResourceFormat::RGBA16Float || spec->getFormat() != ResourceFormat::RGBA16Float ||
+      pDstTex->getFormat() != ResourceFormat::RGBA32Float) {
+    std::fprintf(stderr, "[RestirDirectPass] needs WorldPosition (RGBA32F), WorldNormal, MaterialDiffuse and MaterialSpecRough (RGBA16F) of a "
+                         "G-buffer pass and an RGBA32F output\n");
+    return;
+  }
+  const uint32_t w = pDstTex->getWidth(), h = pDstTex->getHeight();
+  if (!mpRays->ensureSize(w, h) || !ensureBuffers(w, h)) return;
+  hipStream_t stream = pRenderContext->getStream();
+  bdpt_gbuffer gb, histGb;
+  std::memset(&gb, 0, sizeof(gb));
+  gb.worldPosition = (float*)pos->getDevicePointer();
+  gb.worldNormal = (uint16_t*)nrm->getDevicePointer();
+  gb.materialDiffuse = (uint16_t*)dif->getDevicePointer();
+  gb.materialSpecRough = (uint16_t*)spec->getDevicePointer();
+  std::memset(&histGb, 0, sizeof(histGb));
+  histGb.worldPosition = (float*)mHistPos->getDevicePointer();
+  histGb.worldNormal = (uint16_t*)mHistNrm->getDevicePointer();
+  histGb.materialDiffuse = (uint16_t*)mHistDif->getDevicePointer();
+  histGb.materialSpecRough = (uint16_t*)mHistSpec->getDevicePointer();
+  Camera::SharedPtr cam = mpScene ? mpScene->getActiveCamera() : nullptr;
+  if (!cam) {
+    std::fprintf(stderr, "[RestirDirectPass] needs a camera (the GGX material's V, and the history's)\n");
+    return;
+  }
+  bdpt_set_camera(mpRays->ctx(), &cam->getData());
+  const uint32_t frame = mFrameCount++;
+  const uint32_t flags = mAreaLights ? BDPT_PARAM_AREA_LIGHTS : 0u;
+  float* out = (float*)pDstTex->getDevicePointer();
+  auto records = [](const Texture::SharedPtr& t) { return (bdpt_reuse_reservoir*)t->getDevicePointer(); };
+  bool ok = true;
+  bdpt_ris_params rp;
+  std::memset(&rp, 0, sizeof(rp));
+  rp.frameCount = frame;
+  rp.clampUpper = mClampUpper;
+  rp.minT = mpResManager->getMinTDist();
+  rp.candidates = (uint32_t)mCandidates;
+  rp.samples = 1;
+  rp.matIndex = (uint32_t)mMatIndex;
+  rp.flags = flags;
+  ok = bdpt_ris_execute_reservoirs(mpRays->ctx(), &rp, &gb, out, (bdpt_ris_reservoir*)mFirst->getDevicePointer(), stream) == BDPT_OK;
+  Texture::SharedPtr cur = mFirst;
+  uint32_t inM = (uint32_t)mCandidates;  // the first stage's records end in wsum: their count is the call's
+  bdpt_reuse_params p;
+  std::memset(&p, 0, sizeof(p));
+  p.clampUpper = mClampUpper;
+  p.minT = rp.minT;
+  p.matIndex = rp.matIndex;
+  p.maxM = maxM();
+  p.normalMin = mNormalMin;
+  p.planeMax = std::numeric_limits<float>::infinity();
+  if (ok && mTemporal && mHistoryValid) {
+    p.frameCount = 2u * frame;
+    p.flags = flags | BDPT_REUSE_SAME_PIXEL;
+    p.neighbors = 1;
+    p.inM = inM;
+    p.poolM = mHistM;
+    for (int k = 0; k < 3; k++) p.poolCameraPos[k] = mHistCam[k];
+    p.in = records(cur);
+    p.poolGbuffer = &histGb;
+    p.pool = records(mHist);
+    p.outReservoirs = records(mSecond);
+    ok = bdpt_reuse_execute(mpRays->ctx(), &p, &gb, out, stream) == BDPT_OK;
+    cur = mSecond;
+    inM = 0;
+  }
+  if (ok && mSpatial > 0) {
+    p.frameCount = 2u * frame + 1u;
+    p.flags = flags;
+    p.neighbors = (uint32_t)mSpatial;
+    p.radius = (uint32_t)mRadius;
+    p.inM = p.poolM = inM;
+    for (int k = 0; k < 3; k++) p.poolCameraPos[k] = cam->getData().posW[k];
+    p.in = p.pool = records(cur);
+    p.poolGbuffer = &gb;
+    p.outReservoirs = records(mThird);
+    ok = bdpt_reuse_execute(mpRays->ctx(), &p, &gb, out, stream) == BDPT_OK;
+    cur = mThird;
+    inM = 0;
+  }
+  if (!ok) {
+    std::fprintf(stderr, "[RestirDirectPass] %s\n", mpRays->lastError());
+    mHistoryValid = false;
+    return;
+  }
+  // The history of the next frame.  A background pixel's record may be stale (the first stage does not write it): a dead
+  // pool pixel is rejected before its record is read, which holds as long as these copies are made together.
+  const std::pair<Texture::SharedPtr, Texture::SharedPtr> copies[] = {{mHist, cur}, {mHistPos, pos}, {mHistNrm, nrm}, {mHistDif, dif}, {mHistSpec, spec}};
+  for (const auto& c : copies)
+    ok = ok && hipMemcpyAsync(c.first->getDevicePointer(), c.second->getDevicePointer(), c.first->getSizeInBytes(), hipMemcpyDeviceToDevice, stream) == hipSuccess;
+  for (int k = 0; k < 3; k++) mHistCam[k] = cam->getData().posW[k];
+  mHistM = inM;
+  mHistoryValid = ok;
+}
+
+// ------------------------------------------------------------------------------------------------
 // LambertianPlusShadowPass (CommonPasses/LambertianPlusShadowPass.cpp:33-83)
 // ------------------------------------------------------------------------------------------------
 bool LambertianPlusShadowPass::initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) {
@@ -1471,6 +1596,57 @@ bool ResampledDirectPass::loadState(RenderContext*, const uint8_t* data, size_t 
       get32(data + 8) != floatBits(mClampUpper) || get32(data + 12) != floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f))
     return false;
   mFrameCount = get32(data);
+  return true;
+}
+// [frame counter][settings][clamp][minT][maxM][history valid][history count][history camera x, y, z], and with a valid
+// history its reservoirs and G-buffer copy: the frame sequence continues bit for bit.  A state written under other settings or
+// for another frame size is refused.
+uint32_t RestirDirectPass::settingsWord() const {
+  return (uint32_t)mCandidates | ((uint32_t)mSpatial << 8) | ((uint32_t)mRadius << 12) | ((uint32_t)mMatIndex << 24) | (mAreaLights ? 1u << 25 : 0u) |
+         (mTemporal ? 1u << 26 : 0u);
+}
+void RestirDirectPass::saveState(RenderContext* pRenderContext, std::vector<uint8_t>& out) {
+  put32(out, mFrameCount);
+  put32(out, settingsWord());
+  put32(out, floatBits(mClampUpper));
+  put32(out, floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f));
+  put32(out, maxM());
+  put32(out, mHistoryValid ? 1u : 0u);
+  put32(out, mHistM);
+  for (int k = 0; k < 3; k++) put32(out, floatBits(mHistCam[k]));
+  if (!mHistoryValid) return;
+  for (const Texture::SharedPtr& t : {mHist, mHistPos, mHistNrm, mHistDif, mHistSpec}) {
+    std::vector<uint8_t> raw;
+    t->downloadRaw(pRenderContext->getStream(), raw);
+    out.insert(out.end(), raw.begin(), raw.end());
+  }
+}
+bool RestirDirectPass::loadState(RenderContext* pRenderContext, const uint8_t* data, size_t size) {
+  constexpr size_t kHead = 40;
+  if (size < kHead) return false;
+  if (get32(data + 4) != settingsWord() || get32(data + 8) != floatBits(mClampUpper) ||
+      get32(data + 12) != floatBits(mpResManager ? mpResManager->getMinTDist() : 0.0f) || get32(data + 16) != maxM() || get32(data + 20) > 1u)
+    return false;
+  const bool valid = get32(data + 20) == 1u;
+  if (!valid) {
+    if (size != kHead) return false;
+  } else {
+    if (!mW || !mH || !ensureBuffers(mW, mH)) return false;
+    size_t at = kHead;
+    for (const Texture::SharedPtr& t : {mHist, mHistPos, mHistNrm, mHistDif, mHistSpec}) {
+      const size_t bytes = t->getSizeInBytes();
+      if (size - at < bytes || !t->uploadRaw(pRenderContext->getStream(), data + at, bytes)) return false;
+      at += bytes;
+    }
+    if (at != size) return false;
+  }
+  mFrameCount = get32(data);
+  mHistM = get32(data + 24);
+  for (int k = 0; k < 3; k++) {
+    const uint32_t u = get32(data + 28 + 4 * k);
+    std::memcpy(&mHistCam[k], &u, 4);
+  }
+  mHistoryValid = valid;
   return true;
 }
 void LambertianPlusShadowPass::saveState(RenderContext*, std::vector<uint8_t>& out) {  // no counter: only what the image depends on

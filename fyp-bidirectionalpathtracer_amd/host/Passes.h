@@ -312,6 +312,59 @@ class ResampledDirectPass : public RenderPass {
   uint32_t mFrameCount = 0;
 };
 
+// ReSTIR direct lighting (include/bdpt.h "Reservoir reuse"): the resampled pass with one sample and its reservoirs
+// (bdpt_ris_execute_reservoirs), then with setTemporal and a history a bdpt_reuse_execute whose one neighbour is the same pixel
+// of last frame's reservoirs, G-buffer copy and camera position, then with setSpatial(N > 0) a bdpt_reuse_execute over N
+// neighbours at offsets drawn within the radius; one shadow ray per pixel and pass.  The first stage runs at the pass's frame
+// counter (from 0), the temporal pass at twice it, the spatial pass at twice plus one: FramePipeline.restir_lighting of the
+// Python package is the same sequence, bit for bit.  The last pass's image is the frame — the history is the accumulation, no
+// accumulation pass follows — and its reservoirs, the G-buffer and the camera position are the next frame's history, which a
+// scene move (stateRefreshed) drops and a checkpoint carries.
+class RestirDirectPass : public RenderPass {
+ public:
+  using SharedPtr = std::shared_ptr<RestirDirectPass>;
+  static SharedPtr create(const std::string& outBuf = ResourceManager::kOutputChannel) { return SharedPtr(new RestirDirectPass(outBuf)); }
+  void setCandidates(int m) { mCandidates = m; }  // 1 .. BDPT_RIS_MAX_CANDIDATES
+  void setSpatial(int n) { mSpatial = n; }        // 0 .. BDPT_REUSE_MAX_NEIGHBORS
+  void setRadius(int r) { mRadius = r; }          // 1 .. BDPT_REUSE_MAX_RADIUS
+  void setTemporal(bool on) { mTemporal = on; }
+  void setMaxM(int c) { mMaxM = c; }              // what a pool reservoir counts for at most; <= 0: 20 * candidates
+  void setMaterial(int matIndex) { mMatIndex = matIndex; }  // 0 GGX, 1 Lambertian
+  void setAreaLights(bool on) { mAreaLights = on; }
+  void setClamp(float hi) { mClampUpper = hi; }
+
+ protected:
+  RestirDirectPass(const std::string& outBuf) : RenderPass("ReSTIR Direct Rays", "ReSTIR Direct Options"), mOutputBuf(outBuf) {}
+  bool initialize(RenderContext* pRenderContext, ResourceManager::SharedPtr pResManager) override;
+  void initScene(RenderContext* pRenderContext, Scene::SharedPtr pScene) override;
+  void execute(RenderContext* pRenderContext) override;
+  void stateRefreshed() override { mHistoryValid = false; }  // other lights or geometry: the history's samples are stale
+  void resize(uint32_t width, uint32_t height) override { mW = width, mH = height, mHistoryValid = false; }
+  bool requiresScene() override { return true; }
+  bool usesRayTracing() override { return true; }
+  bool holdsTemporalState() override { return true; }
+  void saveState(RenderContext* pRenderContext, std::vector<uint8_t>& out) override;
+  bool loadState(RenderContext* pRenderContext, const uint8_t* data, size_t size) override;
+  bool ensureBuffers(uint32_t w, uint32_t h);
+  uint32_t maxM() const { return mMaxM > 0 ? (uint32_t)mMaxM : 20u * (uint32_t)mCandidates; }
+  uint32_t settingsWord() const;
+
+  RayLaunch::SharedPtr mpRays;
+  Scene::SharedPtr mpScene;
+  std::string mOutputBuf;
+  float mClampUpper = 3.402823466e+38f;  // no clamp
+  float mNormalMin = 0.9f;               // a neighbour's rejection test, FramePipeline.restir_lighting's default (no plane test)
+  int32_t mCandidates = 8, mSpatial = 0, mRadius = 8, mMaxM = 0, mMatIndex = 1;
+  bool mTemporal = false, mAreaLights = false;
+  uint32_t mFrameCount = 0;
+  // reservoir images (RGBA32F-sized: 16 bytes a record): the history and one per pass; the history's G-buffer copy
+  Texture::SharedPtr mHist, mFirst, mSecond, mThird, mHistPos, mHistNrm, mHistDif, mHistSpec;
+  float mHistCam[3] = {0.0f, 0.0f, 0.0f};
+  uint32_t mW = 0, mH = 0;  // the frame, as resize() last said
+  uint32_t mHistM = 0;  // the candidate count of every history record; 0: the records' M words (a reuse pass wrote them)
+  bool mHistoryValid = false;
+};
+
 // Direct lighting from every light with one shadow ray each (CommonPasses/LambertianPlusShadowPass.{h,cpp}): WorldPosition,
 // WorldNormal, MaterialDiffuse and MaterialSpecRough in, the output channel out; no GUI state and no frame counter, as in the
 // reference (nothing is drawn).  Its ray generation shader with its shadow hit group is bdpt_direct_execute.

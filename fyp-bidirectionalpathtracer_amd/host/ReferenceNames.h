@@ -29,4 +29,5 @@ using bdpt::SimpleDiffuseGIPass;
 using bdpt::SimpleAccumulationPass;
 using bdpt::SkyLightingPass;
 using bdpt::ResampledDirectPass;
+using bdpt::RestirDirectPass;
 using bdpt::Texture;

@@ -62,6 +62,13 @@ struct Options {
   bool risHints = false;      // --ris-hints (with --ris): BDPT_RIS_USE_HINTS (the same image)
   float risClamp = 0.0f;      // --ris-clamp C (with --ris, > 0): the bound of a candidate's value; not given: none
   bool risClampSet = false;
+  int risSpatial = 0;         // --ris-spatial N (with --ris): ReSTIR — N spatial neighbours behind the first stage (RestirDirectPass)
+  int risRadius = 8;          // --ris-radius R (with --ris-spatial): the neighbours' offsets are drawn within R pixels
+  bool risRadiusSet = false;
+  bool risTemporal = false;   // --ris-temporal (with --ris): ReSTIR — the same pixel of last frame's reservoirs is a neighbour
+  int risMaxM = 0;            // --ris-max-m C (with --ris-spatial / --ris-temporal): what a pool reservoir counts for at most; not given: 20 M
+  bool risMaxMSet = false;
+  bool restir() const { return ris >= 0 && (risSpatial > 0 || risTemporal); }
   bool skyGgx = false;        // --sky-ggx (with --sky-mis): the pass's GGX material instead of the Lambertian surface
   bool gi = false;            // --gi: render the G-buffer, the diffuse GI pass and the accumulation pass instead of the BDPT pipeline
   bool giDirectOnly = false;  // --gi-direct-only: untick "Shooting global illumination rays"
@@ -137,7 +144,7 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
   }
   // add the passes to the rendering pipeline, as Main.cpp:12-18 does
   pipeline->setPass(0, LightProbeGBufferPass::create());
-  const size_t numPasses = (o.ao >= 0 || o.direct) ? 2 : (o.gi || o.sky >= 0 || o.ris >= 0) ? 3 : 4;
+  const size_t numPasses = (o.ao >= 0 || o.direct || o.restir()) ? 2 : (o.gi || o.sky >= 0 || o.ris >= 0) ? 3 : 4;
   if (o.direct) {  // --direct: the G-buffer and the direct lighting pass, which writes the output channel (nothing to accumulate: no draw)
     LambertianPlusShadowPass::SharedPtr lambert = LambertianPlusShadowPass::create();
     lambert->setUseHints(o.directHints);
@@ -151,6 +158,17 @@ bool setUpRank(const Options& o, int device, uint32_t rank, uint32_t world, nccl
     sky->setMaterial(o.skyGgx ? 0 : 1);
     pipeline->setPass(1, sky);
     pipeline->setPass(2, SimpleAccumulationPass::create(ResourceManager::kOutputChannel));
+  } else if (o.restir()) {  // --ris with reuse: the G-buffer and the ReSTIR pass, which writes the output channel (its history accumulates)
+    RestirDirectPass::SharedPtr restir = RestirDirectPass::create(ResourceManager::kOutputChannel);
+    restir->setCandidates(o.ris);
+    restir->setSpatial(o.risSpatial);
+    restir->setRadius(o.risRadius);
+    restir->setTemporal(o.risTemporal);
+    if (o.risMaxMSet) restir->setMaxM(o.risMaxM);
+    restir->setMaterial(o.risGgx ? 0 : 1);
+    restir->setAreaLights(o.areaLights);
+    if (o.risClampSet) restir->setClamp(o.risClamp);
+    pipeline->setPass(1, restir);
   } else if (o.ris >= 0) {  // --ris: the G-buffer, the resampled direct lighting pass into the output channel, the accumulation pass
     ResampledDirectPass::SharedPtr ris = ResampledDirectPass::create(ResourceManager::kOutputChannel);
     ris->setCandidates(o.ris);
@@ -363,6 +381,11 @@ RankResult runRank(const Options& o, int device, const RankEnv& env) {
       std::printf("%s %ux%u diffuse GI (%s%s): %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f", o.scene.c_str(), o.W, o.H,
                   o.giDirectOnly ? "direct only" : "one bounce", o.giUniform ? ", uniform sampling" : ", cosine sampling", o.frames - warmup, res.ms,
                   res.ms / (o.frames - warmup), mean / (3.0 * (double)(img.size() / 4)));
+    else if (o.restir())
+      std::printf("%s %ux%u ReSTIR direct lighting%s%s, %d candidates, %d spatial neighbours within %d pixels%s: %d frames in %.2f ms (%.2f ms/frame), "
+                  "mean radiance %.6f", o.scene.c_str(), o.W, o.H, o.risGgx ? " (GGX)" : "", o.areaLights ? ", emitter table" : "", o.ris, o.risSpatial,
+                  o.risRadius, o.risTemporal ? ", temporal reuse" : "", o.frames - warmup, res.ms, res.ms / (o.frames - warmup),
+                  mean / (3.0 * (double)(img.size() / 4)));
     else if (o.ris >= 0)
       std::printf("%s %ux%u resampled direct lighting%s%s%s, %d candidates, %d rays per pixel: %d frames in %.2f ms (%.2f ms/frame), mean radiance %.6f",
                   o.scene.c_str(), o.W, o.H, o.risGgx ? " (GGX)" : "", o.areaLights ? ", emitter table" : "", o.risHints ? ", occluder hints" : "",
@@ -440,6 +463,10 @@ int main(int argc, char** argv) {
     else if (const char* v = next("--ris-clamp")) o.risClamp = (float)std::atof(v), o.risClampSet = true;
     else if (std::strcmp(argv[i], "--ris-ggx") == 0) o.risGgx = true;
     else if (std::strcmp(argv[i], "--ris-hints") == 0) o.risHints = true;
+    else if (const char* v = next("--ris-spatial")) o.risSpatial = std::atoi(v);
+    else if (const char* v = next("--ris-radius")) o.risRadius = std::atoi(v), o.risRadiusSet = true;
+    else if (const char* v = next("--ris-max-m")) o.risMaxM = std::atoi(v), o.risMaxMSet = true;
+    else if (std::strcmp(argv[i], "--ris-temporal") == 0) o.risTemporal = true;
     else if (std::strcmp(argv[i], "--direct") == 0) o.direct = true;
     else if (std::strcmp(argv[i], "--direct-hints") == 0) o.directHints = true;
     else if (std::strcmp(argv[i], "--no-motion") == 0) o.noMotion = true;
@@ -452,7 +479,7 @@ int main(int argc, char** argv) {
     else {
       std::fprintf(stderr, "usage: bdpt_render [--scene cornell|atrium|FILE.fscene|FILE.obj] [--width W] [--height H] [--frames N] [--depth D] "
                            "[--mat 0|1] [--accum-limit N] [--denoise | --denoise-regression] [--area-lights] [--out file.pfm] [--raw file.f32] "
-                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] [--direct [--direct-hints]] [--sky N [--sky-clamp C] [--sky-mis [--sky-ggx]]] [--ris M [--ris-samples K] [--ris-ggx] [--ris-hints] [--ris-clamp C]] "
+                           "[--resume file.ckpt] [--checkpoint file.ckpt] [--env probe.hdr|image|Black] [--inflight N] [--warmup N] [--sway A] [--bend A] [--no-motion] [--tight-refit] [--ao N [--ao-radius R]] [--gi [--gi-direct-only] [--gi-uniform]] [--direct [--direct-hints]] [--sky N [--sky-clamp C] [--sky-mis [--sky-ggx]]] [--ris M [--ris-samples K] [--ris-ggx] [--ris-hints] [--ris-clamp C] [--ris-spatial N [--ris-radius R]] [--ris-temporal] [--ris-max-m C]] "
                            "[--gpus N | --rank R --world N --id-file F [--job-id J] [--device D]]\n");
       return 2;
     }
@@ -531,6 +558,18 @@ int main(int argc, char** argv) {
                      o.gpus > 0 || o.world > 0 || (o.risClampSet && !(o.risClamp > 0.0f)))) {
     std::fprintf(stderr, "bdpt_render: --ris M needs M in 1 .. %u candidates, --ris-samples K in 1 .. %u, --ris-clamp C > 0 when given, and one GPU "
                          "(no --gpus / --world)\n", BDPT_RIS_MAX_CANDIDATES, BDPT_RIS_MAX_SAMPLES);
+    return 2;
+  }
+  if (o.ris < 0 && (o.risSpatial != 0 || o.risRadiusSet || o.risTemporal || o.risMaxMSet)) {
+    std::fprintf(stderr, "bdpt_render: --ris-spatial N, --ris-radius R, --ris-temporal and --ris-max-m C go with --ris M\n");
+    return 2;
+  }
+  if (o.ris >= 0 && (o.risSpatial < 0 || o.risSpatial > (int)BDPT_REUSE_MAX_NEIGHBORS || (o.risRadiusSet && o.risSpatial <= 0) || o.risRadius < 1 ||
+                     o.risRadius > (int)BDPT_REUSE_MAX_RADIUS || (o.risMaxMSet && (!o.restir() || o.risMaxM < 1)) ||
+                     (o.restir() && (o.risSamples != 1 || o.risHints || o.inflight > 1 || o.sway > 0.0f || o.bend > 0.0f)))) {
+    std::fprintf(stderr, "bdpt_render: --ris-spatial N needs N in 0 .. %u, --ris-radius R in 1 .. %u with --ris-spatial, --ris-max-m C >= 1 with "
+                         "--ris-spatial or --ris-temporal; reservoir reuse takes one sample, no hints, one frame in flight and a scene that does not "
+                         "move (no --ris-samples, --ris-hints, --inflight, --sway, --bend)\n", BDPT_REUSE_MAX_NEIGHBORS, BDPT_REUSE_MAX_RADIUS);
     return 2;
   }
   // --ris replaces the BDPT and denoise passes: the switches only they read are refused, not ignored (--area-lights is read)

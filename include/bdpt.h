@@ -1779,6 +1779,145 @@ typedef struct bdpt_ris_params {
 } bdpt_ris_params; /* 32 bytes */
 int bdpt_ris_execute(bdpt_ctx* ctx, const bdpt_ris_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
 
+/* ---- Reservoir reuse -----------------------------------------------------------------------------------------------
+ * The second stage of ReSTIR: an item combines its own reservoir with those of up to BDPT_REUSE_MAX_NEIGHBORS other
+ * surface points (spatial neighbours, or the same point a frame ago) and traces ONE any-hit ray for the survivor.  It is
+ * the unbiased 1 / Z combination of Bitterli et al. 2020, Algorithm 6.  The target is the unshadowed, clamped value, as in
+ * the first stage; visibility is not reused (the OCCLUDED bits of input records are ignored), so the result is unbiased
+ * for the clamped direct lighting, bdpt_ris_query's own contract.
+ *
+ * A reservoir's sample can be re-evaluated at any receiver.  A record's `state` is the RNG state after the selection draw
+ * that chose `light`, and the generator is invertible: prev(s) = (s - 1013904223) * 4276115653 mod 2^32.
+ * bdpt_light_query(BDPT_LIGHT_NEE) from prev(state) at any surface record draws the same light, and for the emitter table
+ * the same emitter point (areaNee forks from `state`; its point does not depend on the receiver).  The composed loop is
+ * prev(state) -> bdpt_light_query -> clamp; the kernel evaluates (light, state) directly.  `light` must be the light that
+ * prev(state) draws, as it is in every record bdpt_ris_query and this call write; for any other in-range `light` the
+ * value is that light's.
+ *
+ * bdpt_reuse_query: item i < min(*numDevice, num) is dead as bdpt_ris_query has it.  A dead item gets color (diffuse, 1),
+ * no draw (seedsOut[i] = seeds[i]), traced 0 and the empty record (BDPT_RIS_NO_LIGHT, 0, 0, +0, M = 0).  For an alive
+ * item the sources are, in order, its own record in[i] at surface i, then for n = 0 .. neighbors-1 the pool entry
+ * p_n = neighborIndex[i * neighbors + n] with record pool[p_n] at surface poolSurfaces[p_n].  A neighbour slot is skipped
+ * (its draw is still taken) when p_n >= poolNum (0xffffffff is the conventional "none"), when the pool item is dead (by
+ * poolAlive and prim, the items' rule), when !(dot(N_i, N_p) >= normalMin), or when
+ * !(fabsf(dot(N_i, pos_p - pos_i)) <= planeMax); dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z.
+ * Candidate counts: a record's count is inM (for in) / poolM (for pool) when that scalar is non-zero — how first-stage
+ * bdpt_ris_reservoir records are read, whose fourth word is wsum — and the record's M word otherwise; counts above
+ * BDPT_REUSE_MAX_M read as that; pool counts are then capped by maxM, the own count is not.
+ *   t_x(y), v_x(y): v = clampVec(value of sample y at surface x, clampUpper), t = max(max(v.x, v.y), v.z)
+ *                   value as bdpt_light_query(NEE, matIndex, flags & BDPT_PARAM_AREA_LIGHTS) gives it; y.light >=
+ *                   lightsCount or == BDPT_RIS_NO_LIGHT, or !(y.W > 0): the record is empty, w = 0
+ *   s = seeds[i]; wsum = 0; Mtot = 0 (uint32)
+ *   for each source j in order:  u_j = nextRand(s)            always taken, 1 + neighbors draws per item
+ *       skipped slot: continue
+ *       w = (t_i(y_j) * W_j) * (float)M_j;  wsum = wsum + w;  Mtot += M_j
+ *       source j becomes the selection iff w > 0 && u_j * wsum <= w
+ *   nothing selected: colour term +0, no ray, out = (BDPT_RIS_NO_LIGHT, status 0, state 0, W +0, Mtot)
+ *   Z = sum of M_j over the non-skipped sources with t_j(y_sel) > 0      (t at source j's own surface, the same material)
+ *   Z == 0: as nothing selected
+ *   W' = (wsum / (float)Z) / t_i(y_sel);  term = v_i(y_sel) * W'
+ *   one BDPT_TRACE_ANY ray (pos_i, minT, L, distance as bdpt_light_query gives them for y_sel at i); occluded: +0
+ *   color[i] = (term or +0, 1); out[i] = (light, status, state, W', Mtot) with status BDPT_RIS_STATUS_RAY, and
+ *   BDPT_RIS_STATUS_OCCLUDED when so; traced[i] = 1; seedsOut[i] = s after 1 + neighbors draws
+ * Every operation is one fp32 rounding in the order written, without contraction.  Nothing a caller supplies reaches an
+ * address: neighbour indices, light ids and counts are range-checked as above.  No occluder hints in this stage.
+ * The pool may be the item arrays themselves (spatial reuse) or another set (last frame's: temporal reuse).  Not enforced:
+ * temporal reuse assumes that the lights and the emitter table are those the history was made with, and the states that
+ * made the input reservoirs must be independent of `seeds`.
+ * The call is stream-ordered, capturable (one kernel node) and allocates nothing but the emitter table, under
+ * bdpt_ris_query's rule.  Errors, in this order: a NULL context or desc BDPT_E_INVALID; no scene BDPT_E_STATE; neighbors >
+ * BDPT_REUSE_MAX_NEIGHBORS, matIndex > 1, a flag other than BDPT_PARAM_AREA_LIGHTS, non-zero reserved, a negative or NaN
+ * clampUpper BDPT_E_INVALID; then num == 0 returns BDPT_OK; then a missing or misaligned buffer (neighborIndex with
+ * neighbors > 0, poolSurfaces and pool with neighbors > 0 and poolNum > 0), or `out` equal to `in` or `pool`,
+ * BDPT_E_INVALID.  A refused call enqueues nothing. */
+#define BDPT_REUSE_MAX_NEIGHBORS 8u
+#define BDPT_REUSE_MAX_M (1u << 24)
+typedef struct bdpt_reuse_reservoir {
+  uint16_t light;  /* as bdpt_ris_reservoir */
+  uint16_t status; /* BDPT_RIS_STATUS_* */
+  uint32_t state;  /* the RNG state after the selection draw that chose `light` */
+  float W;
+  uint32_t M;      /* the candidates the record stands for */
+} bdpt_reuse_reservoir; /* 16 bytes */
+typedef struct bdpt_reuse_desc {
+  uint32_t num;              /* items; the capacity when numDevice is set */
+  uint32_t flags;            /* BDPT_PARAM_AREA_LIGHTS */
+  const uint32_t* numDevice; /* optional device word: min(*numDevice, num) items */
+  uint32_t matIndex;         /* 0 GGX, 1 Lambertian */
+  uint32_t neighbors;        /* 0 .. BDPT_REUSE_MAX_NEIGHBORS */
+  uint32_t inM;              /* non-zero: the count of every `in` record */
+  uint32_t poolM;            /* non-zero: the count of every `pool` record */
+  uint32_t maxM;             /* cap of a pool record's count */
+  uint32_t poolNum;          /* pool entries */
+  float normalMin;           /* a neighbour needs dot(N_i, N_p) >= normalMin */
+  float planeMax;            /* ... and fabsf(dot(N_i, pos_p - pos_i)) <= planeMax */
+  float clampUpper;          /* as bdpt_ris_desc */
+  float minT;                /* tmin of the ray */
+  uint32_t reserved[2];      /* 0 */
+  const bdpt_surface* surfaces;       /* device, 16-byte aligned, num records */
+  const uint8_t* alive;               /* optional: device, one byte per item */
+  const uint32_t* seeds;              /* device, num RNG states */
+  const bdpt_reuse_reservoir* in;     /* device, 16-byte aligned, num records */
+  const bdpt_surface* poolSurfaces;   /* device, 16-byte aligned, poolNum records (may be `surfaces`) */
+  const uint8_t* poolAlive;           /* optional: device, one byte per pool entry */
+  const bdpt_reuse_reservoir* pool;   /* device, 16-byte aligned, poolNum records (may be `in`) */
+  const uint32_t* neighborIndex;      /* device, num * neighbors pool indices */
+  float* color;                       /* device, 16-byte aligned, num float4 */
+  uint32_t* seedsOut;                 /* optional: device, num RNG states (may be `seeds`) */
+  uint32_t* traced;                   /* optional: device, num words: 1 where a ray was traversed */
+  bdpt_reuse_reservoir* out;          /* optional: device, 16-byte aligned, num records; not `in`, not `pool` */
+} bdpt_reuse_desc; /* 160 bytes */
+int bdpt_reuse_query(bdpt_ctx* ctx, const bdpt_reuse_desc* desc, void* stream);
+/* bdpt_reuse_execute runs the same for the context's tile pixels.  Items: the pixels of `gbuffer` as bdpt_ris_execute reads
+ * them, with own records in[pixel] of a full-frame image.  Pool: the width * height pixels of poolGbuffer (it may be
+ * `gbuffer`, or last frame's copy) with records pool[pixel]; a pool pixel is dead where its worldPosition.w is 0, and for
+ * matIndex 0 its V is normalize(poolCameraPos - posW).  Seeds: initRand(initRand(pixel, frameCount), 0x52455553), the fork
+ * idiom of the emitter table's stream, so a caller may reuse the frame counter of bdpt_ris_execute.  Colour and `out`
+ * records are written at the tile's pixels only; two row tiles over a full-frame pool reproduce the frame.
+ * Neighbours come from exactly one of three sources:
+ *   neighborIndex set: a full-frame image, slot n of pixel p at [p * neighbors + n], of pool pixels
+ *   BDPT_REUSE_SAME_PIXEL (neighbors must be 1): slot 0 is the pool pixel with the item's own index — the temporal pass
+ *   otherwise (radius 1 .. BDPT_REUSE_MAX_RADIUS): before the selection draws each slot n = 0 .. neighbors-1 draws u1, u2;
+ *     dx = (int)(u1 * (float)(2 * radius + 1)) - radius, dy likewise from u2; the slot is none when (dx, dy) == (0, 0) or
+ *     (x + dx, y + dy) is outside the frame, else pool pixel (y + dy) * width + (x + dx).  The state after the 2 *
+ *     neighbors draws is the s of the algorithm above.
+ * Errors, in this order: a NULL context, params or gbuffer BDPT_E_INVALID; no scene, no size, no camera (matIndex 0)
+ * BDPT_E_STATE; the scalar refusals of bdpt_reuse_query, an unknown flag, neighborIndex together with
+ * BDPT_REUSE_SAME_PIXEL, BDPT_REUSE_SAME_PIXEL with neighbors != 1, or drawn offsets (neighbors > 0 and neither) with a
+ * radius outside 1 .. BDPT_REUSE_MAX_RADIUS BDPT_E_INVALID; then a missing or misaligned buffer (the pool's with neighbors
+ * > 0), or outReservoirs equal to `in` or `pool`, BDPT_E_INVALID. */
+#define BDPT_REUSE_SAME_PIXEL 1u /* flags, beside BDPT_PARAM_AREA_LIGHTS */
+#define BDPT_REUSE_MAX_RADIUS 1024u
+typedef struct bdpt_reuse_params {
+  uint32_t frameCount;
+  float clampUpper;
+  float minT;
+  uint32_t matIndex;       /* 0 GGX (needs a camera), 1 Lambertian */
+  uint32_t flags;          /* BDPT_PARAM_AREA_LIGHTS | BDPT_REUSE_SAME_PIXEL */
+  uint32_t neighbors;      /* 0 .. BDPT_REUSE_MAX_NEIGHBORS */
+  uint32_t radius;         /* drawn offsets: 1 .. BDPT_REUSE_MAX_RADIUS */
+  uint32_t inM;            /* as bdpt_reuse_desc */
+  uint32_t poolM;
+  uint32_t maxM;
+  float normalMin;
+  float planeMax;
+  float poolCameraPos[3];  /* V of pool pixels (matIndex 0) */
+  uint32_t reserved;       /* 0 */
+  const bdpt_reuse_reservoir* in;      /* device, 16-byte aligned, width * height records */
+  const bdpt_gbuffer* poolGbuffer;     /* host: the pool's full-frame G-buffer (worldPosition, worldNormal, materialDiffuse,
+                                          and for matIndex 0 materialSpecRough) */
+  const bdpt_reuse_reservoir* pool;    /* device, 16-byte aligned, width * height records (may be `in`) */
+  const uint32_t* neighborIndex;       /* optional: device, width * height * neighbors pool pixels */
+  bdpt_reuse_reservoir* outReservoirs; /* optional: device, 16-byte aligned, width * height records; not `in`, not `pool` */
+} bdpt_reuse_params; /* 104 bytes */
+int bdpt_reuse_execute(bdpt_ctx* ctx, const bdpt_reuse_params* p, const bdpt_gbuffer* gbuffer, float* out, void* stream);
+/* bdpt_ris_execute with a full-frame reservoir image: width * height * samples records, record k of pixel p at
+ * [p * samples + k], written at the tile's pixels that are geometry; a background pixel's records are left as they are
+ * (bdpt_reuse_execute reads the record of no background pixel, item or pool).  `out` is what bdpt_ris_execute writes,
+ * bit for bit.  reservoirs missing or not 16-byte aligned: BDPT_E_INVALID, with the buffers. */
+int bdpt_ris_execute_reservoirs(bdpt_ctx* ctx, const bdpt_ris_params* p, const bdpt_gbuffer* gbuffer, float* out,
+                                bdpt_ris_reservoir* reservoirs, void* stream);
+
 /* Host-only (no GPU, no context): run the acceleration-structure builder on a scene (geometry only: every triangle
  * opaque) and check its invariants — every triangle referenced, every leaf entry in exactly one leaf, the pieces of
  * a split triangle covering it, every child box containing its subtree's pieces, depth within the traversal stack.
